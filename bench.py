@@ -6,8 +6,12 @@
                                                             torch.distributed.run --standalone on 127.0.0.1)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...      (the driver's form)
 
-The timed region is run --repeat R times (default 3; each is EXACTLY K steps between barriers); `value` and `ms_per_step`
-are the MEDIAN repeat's, the others are listed under `repeats`.
+A plain run sets up, warms up, times EXACTLY K steps once (between barriers), and prints the headline line; everything
+else it can measure runs only with --full.  --dump-outputs DIR writes the timed region's frame (the f32 sum image a caller
+of the renderer reads back) as DIR/accumulation.npy.
+
+With --full the timed region is run --repeat R times (default 3 there, 1 in a plain run; each is EXACTLY K steps); `value`
+and `ms_per_step` are the MEDIAN repeat's, the others are listed under `repeats`.
 
 Workload (BASELINE.json configs[2]/[3]): Sponza stand-in ("synthetic atrium": the real assets/Sponza.glb is absent
 from the reference mount), 1920x1080, 8 bounces, default camera and sky.
@@ -21,7 +25,7 @@ is.  Inputs (scene, textures, tables) are resident in HBM before the timed regio
 scaling: total work fixed) and the per-rank tile buffers are brought to rank 0 once at frame end by the C++ RCCL
 exchange (rf_renderer_gather_frame: grouped ncclSend/ncclRecv + device un-tile), inside the timed region.
 
-The JSON line also carries
+With --full the JSON line also carries
   roofline     the closest-hit traversal kernel against the HBM roofline, in MEASURED bytes: `traffic` = fabric-side
                bytes per launch from rocprofv3 FETCH_SIZE / WRITE_SIZE -- two child passes of this workload under
                `rocprofv3 --pmc <one counter> --kernel-trace` after the timed region (`traffic_live`; the committed
@@ -566,6 +570,25 @@ def build_roofline(s, cs, per_bounce, workload, live=None):
     return roofline
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(directory, image):
+    """--dump-outputs: the timed region's (H, W, 4) f32 sum image as <directory>/accumulation.npy, so that two builds can be
+    compared output for output.  A frame above DUMP_LIMIT_BYTES (4K and up) is written as a fixed seeded sample of its pixels
+    instead: accumulation_sample.npy (n, 4) f32 and the flat pixel indices as accumulation_sample_pixels.npy (f64, exact)."""
+    os.makedirs(directory, exist_ok=True)
+    image = np.ascontiguousarray(image, np.float32)
+    if image.nbytes <= DUMP_LIMIT_BYTES - 4096:
+        np.save(os.path.join(directory, "accumulation.npy"), image)
+        return
+    pixels = image.reshape(-1, image.shape[-1])
+    n = (DUMP_LIMIT_BYTES - 8192) // (pixels.shape[1] * 4 + 8)
+    idx = np.sort(np.random.default_rng(0).choice(pixels.shape[0], size=n, replace=False))
+    np.save(os.path.join(directory, "accumulation_sample.npy"), pixels[idx])
+    np.save(os.path.join(directory, "accumulation_sample_pixels.npy"), idx.astype(np.float64))
+
+
 def self_launch(n, argv):
     """`python bench.py --gpus N` with N > 1 and no launcher environment: become the launcher.  One rank per GPU under
     torch.distributed.run (standalone rendezvous on 127.0.0.1: the container's hostname may not resolve); rank 0 prints
@@ -607,7 +630,11 @@ def main():
     ap.add_argument("--no-occluder-ablation", action="store_true", help="skip the untimed repeat with the occluder cache off")
     ap.add_argument("--no-regimes", action="store_true", help="skip the `regimes` block (the clutter and out-of-cache stand-ins, each on a renderer of its own after the headline) "
                     "and the cold-start figure")
-    ap.add_argument("--repeat", type=int, default=3, help="timed regions of K steps each; the median one is reported (min / max beside it)")
+    ap.add_argument("--repeat", type=int, default=None, help="timed regions of K steps each; the median one is reported (min / max beside it); default 1, 3 with --full")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: repeats, counting pass, ablations, batch-depth curve, live counter passes, "
+                    "roofline, CPU baseline and parity crop, BVH build, cold start and the other regimes (each --no-* option above skips its part)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write the timed region's frame (f32 sum image, rank 0) as DIR/accumulation.npy; "
+                    "above 64 MB a fixed seeded sample of its pixels (accumulation_sample.npy + accumulation_sample_pixels.npy)")
     args = ap.parse_args()
 
     if args.gpus < 1:
@@ -730,7 +757,7 @@ def main():
     # Every repeat restarts the accumulation (frameCount keeps counting: repeat i traces frames warm_spp + i spp ..
     # warm_spp + (i + 1) spp - 1, i.e. the sample indices 0..spp-1 rotated by warm_spp -- the same frames every time, so
     # every repeat produces the same image).
-    R = max(args.repeat, 1)
+    R = max(args.repeat if args.repeat is not None else (3 if args.full else 1), 1)
     r.set_timing(True)
     runs = []
     exchange_ms = []
@@ -785,10 +812,12 @@ def main():
             image = assemble(parts, W, H, world)
         else:
             image = r.read_accumulation()[0]
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, image)
 
     # counting pass (untimed): node visits / triangle tests of exactly the timed frames on this rank
     cs = None
-    if not args.no_counting:
+    if args.full and not args.no_counting:
         r.set_render_parameters(rf.make_render_parameters(W, H, cam, spp, B, sky, 0.25))
         # frameCount is now warm_spp + R spp: this pass traces the next spp frames, the same sample indices
         # (n = frameCount % spp) as every timed repeat
@@ -803,7 +832,7 @@ def main():
     # ---- the same K steps once more with the any-hit launches' occluder cache off (untimed; one GPU): what the figure above owes to it, and that
     # the image does not (kTraceWide, kFlagOccluderCache: a shadow ray first visits the leaves that stopped the last rays from its cell of the scene)
     occluder = None
-    if rank == 0 and world == 1 and not multi and not args.no_occluder_ablation and not args.no_counting:   # (--no-counting: profiling runs trace the timed launches only)
+    if args.full and rank == 0 and world == 1 and not multi and not args.no_occluder_ablation and not args.no_counting:   # (--no-counting: profiling runs trace the timed launches only)
         r.set_option("occluder_cache_bounces", 0)
         r.set_render_parameters(rf.make_render_parameters(W, H, cam, spp, B, sky, 0.375))
         # frameCount is warm_spp + R spp (+ spp of the counting pass): the same sample indices again
@@ -918,13 +947,13 @@ def main():
 
     # ---- roofline of the dominant kernel (closest-hit traversal) + one-line entries for the shadow traversal and kShade
     live = None
-    if rank == 0 and world == 1 and not multi and not args.no_live_counters and "ROCPROFILER_REGISTER_ROOT" not in os.environ and "ROCP_TOOL_LIBRARIES" not in os.environ:
+    if args.full and rank == 0 and world == 1 and not multi and not args.no_live_counters and "ROCPROFILER_REGISTER_ROOT" not in os.environ and "ROCP_TOOL_LIBRARIES" not in os.environ:
         r.synchronize()
         scene_args = (["--scene", scene_path] if scene_path else []) + ["--scene-scale", str(max(args.scene_scale, 1)), "--scene-detail", args.scene_detail]
         t_live = time.time()
         live = live_traffic(scene_args, K, SPS, W, H, B)
         log(f"[bench] live counter passes: {'ok' if live else 'unavailable'} in {time.time() - t_live:.1f} s")
-    roofline = build_roofline(s, cs, per_bounce, f"{info['name']} {W}x{H}x{B}", live)
+    roofline = build_roofline(s, cs, per_bounce, f"{info['name']} {W}x{H}x{B}", live) if args.full else None
 
     cfg_label = {(1920, 1080, 8): "BASELINE.json config 3" if world == 1 else "BASELINE.json config 4", (3840, 2160, 16): "BASELINE.json config 5",
                  (800, 600, 4): "BASELINE.json config 2"}.get((W, H, B), "custom configuration")
@@ -976,47 +1005,48 @@ def main():
                                       "kShadowFirstLook settled with one box + triangle test each (they are shadow rays of the reference all the same: `value` counts them)",
             "nan_pixels": nan_pixels,
             "per_bounce_rank0": per_bounce,
-            "roofline": roofline,
         }
-        out["self_shadow"] = self_shadow if self_shadow is not None else {"enabled": True, "shadow_rays_settled_by_kshade": int(s.get("shadow_rays_self_answered", 0)),
-                                                                          "fraction_of_shadow_rays": round(s.get("shadow_rays_self_answered", 0) / max(s["shadow_rays"], 1), 4),
-                                                                          "value_with_it_off": None, "note": "the repeat with the test off was not run (sharded / multi-rank / --no-occluder-ablation / --no-counting)"}
-        not_run = "not run: these untimed extras run on one unsharded GPU only (and not with --no-occluder-ablation / --no-counting)"
-        out["shortcuts_off"] = shortcuts_off if shortcuts_off is not None else {"value_with_cache_and_self_test_off": None, "note": not_run}
-        out["f32_transcendentals"] = f32_mode if f32_mode is not None else {"value_with_f32_transcendentals": None, "default": "off", "note": not_run}
-        out["batch_depth_curve"] = depth_curve if depth_curve is not None else [{"what": not_run, "value": None}]
-        out["occluder_cache"] = occluder if occluder is not None else {"enabled": True, "value_with_cache_off": None,
-                                                                         "note": "the untimed repeat with the cache off runs on one unsharded GPU only (and not with --no-counting)"}
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"], out["parity_crop"] = cpu_baseline(pt, W, H, B, last_first_frame, spp, args.cpu_seconds, image)
-            # scene bake beside it: the reference's recursive builder as restated on the host (one
-            # thread, what pt-format-tool does) and the GPU builder that emits the same bytes
-            tris = pt.arrays()["bvhPositionAttributes"]
-            t0 = time.perf_counter(); host_nodes, host_idx, _ = rf.build_bvh(tris); host_ms = (time.perf_counter() - t0) * 1e3
-            rf.build_bvh_gpu(tris[:4096])                                       # module load / first-launch cost outside the figure
-            gpu_nodes, gpu_idx, _, gpu_ms = rf.build_bvh_gpu(tris)
-            out["bvh_build"] = {"triangles": int(len(tris)), "nodes": int(len(host_nodes)), "host_ms_1_thread": round(host_ms, 2),
-                                "gpu_ms": round(float(gpu_ms), 3), "node_bytes_identical": bool(host_nodes.tobytes() == gpu_nodes.tobytes()),
-                                "triangle_order_identical": bool(np.array_equal(host_idx, gpu_idx))}
-        if (world == 1 and not multi and not args.no_regimes and not scene_path and max(args.scene_scale, 1) == 1 and args.scene_detail == "plain"
-                and (W, H, B) == (1920, 1080, 8)):      # (the headline workload only: config 3's frame on the plain atrium)
-            # (the headline's renderer is done: its 90 GB of path state go back before the others allocate theirs)
-            r.close()
-            try:
-                out["occluder_cache"]["value_cold_start"] = cold_start(pt, W, H, B, local_rank)
-                log(f"[bench] cold start: {out['occluder_cache']['value_cold_start']}")
-            except Exception as e:  # noqa: BLE001  (an extra: it must not take the headline down)
-                out["occluder_cache"]["value_cold_start"] = {"error": str(e)[:300]}
-            regimes = {}
-            for (name, detail, scale, steps) in (("clutter", "clutter", 1, 20), ("out_of_cache_x8", "plain", 8, 4)):   # (the step counts of their own full lines in profiles/: the whole driver command takes about a minute)
+        if args.full:
+            out["roofline"] = roofline
+            out["self_shadow"] = self_shadow if self_shadow is not None else {"enabled": True, "shadow_rays_settled_by_kshade": int(s.get("shadow_rays_self_answered", 0)),
+                                                                              "fraction_of_shadow_rays": round(s.get("shadow_rays_self_answered", 0) / max(s["shadow_rays"], 1), 4),
+                                                                              "value_with_it_off": None, "note": "the repeat with the test off was not run (sharded / multi-rank / --no-occluder-ablation / --no-counting)"}
+            not_run = "not run: these untimed extras run on one unsharded GPU only (and not with --no-occluder-ablation / --no-counting)"
+            out["shortcuts_off"] = shortcuts_off if shortcuts_off is not None else {"value_with_cache_and_self_test_off": None, "note": not_run}
+            out["f32_transcendentals"] = f32_mode if f32_mode is not None else {"value_with_f32_transcendentals": None, "default": "off", "note": not_run}
+            out["batch_depth_curve"] = depth_curve if depth_curve is not None else [{"what": not_run, "value": None}]
+            out["occluder_cache"] = occluder if occluder is not None else {"enabled": True, "value_with_cache_off": None,
+                                                                             "note": "the untimed repeat with the cache off runs on one unsharded GPU only (and not with --no-counting)"}
+            if not args.no_cpu_baseline and world == 1:
+                out["cpu_baseline"], out["parity_crop"] = cpu_baseline(pt, W, H, B, last_first_frame, spp, args.cpu_seconds, image)
+                # scene bake beside it: the reference's recursive builder as restated on the host (one
+                # thread, what pt-format-tool does) and the GPU builder that emits the same bytes
+                tris = pt.arrays()["bvhPositionAttributes"]
+                t0 = time.perf_counter(); host_nodes, host_idx, _ = rf.build_bvh(tris); host_ms = (time.perf_counter() - t0) * 1e3
+                rf.build_bvh_gpu(tris[:4096])                                       # module load / first-launch cost outside the figure
+                gpu_nodes, gpu_idx, _, gpu_ms = rf.build_bvh_gpu(tris)
+                out["bvh_build"] = {"triangles": int(len(tris)), "nodes": int(len(host_nodes)), "host_ms_1_thread": round(host_ms, 2),
+                                    "gpu_ms": round(float(gpu_ms), 3), "node_bytes_identical": bool(host_nodes.tobytes() == gpu_nodes.tobytes()),
+                                    "triangle_order_identical": bool(np.array_equal(host_idx, gpu_idx))}
+            if (world == 1 and not multi and not args.no_regimes and not scene_path and max(args.scene_scale, 1) == 1 and args.scene_detail == "plain"
+                    and (W, H, B) == (1920, 1080, 8)):      # (the headline workload only: config 3's frame on the plain atrium)
+                # (the headline's renderer is done: its 90 GB of path state go back before the others allocate theirs)
+                r.close()
                 try:
-                    regimes[name] = run_regime(name, detail, scale, steps, SPS, W, H, B, local_rank, with_parity=not args.no_cpu_baseline)
-                except Exception as e:  # noqa: BLE001
-                    regimes[name] = {"error": str(e)[:300]}
-                    log(f"[bench] regime {name} FAILED: {e}")
-            regimes["note"] = ("the other stand-ins (DESIGN.md 8.1), each on a renderer of its own after the headline: same recipe (2 warm-up steps, 3 timed regions, the median), "
-                               "one more repeat with the occluder cache off, the oracle on a 48x32 crop of the timed frames; `value` above stays on the plain atrium")
-            out["regimes"] = regimes
+                    out["occluder_cache"]["value_cold_start"] = cold_start(pt, W, H, B, local_rank)
+                    log(f"[bench] cold start: {out['occluder_cache']['value_cold_start']}")
+                except Exception as e:  # noqa: BLE001  (an extra: it must not take the headline down)
+                    out["occluder_cache"]["value_cold_start"] = {"error": str(e)[:300]}
+                regimes = {}
+                for (name, detail, scale, steps) in (("clutter", "clutter", 1, 20), ("out_of_cache_x8", "plain", 8, 4)):   # (the step counts of their own full lines in profiles/: the whole driver command takes about a minute)
+                    try:
+                        regimes[name] = run_regime(name, detail, scale, steps, SPS, W, H, B, local_rank, with_parity=not args.no_cpu_baseline)
+                    except Exception as e:  # noqa: BLE001
+                        regimes[name] = {"error": str(e)[:300]}
+                        log(f"[bench] regime {name} FAILED: {e}")
+                regimes["note"] = ("the other stand-ins (DESIGN.md 8.1), each on a renderer of its own after the headline: same recipe (2 warm-up steps, 3 timed regions, the median), "
+                                   "one more repeat with the occluder cache off, the oracle on a 48x32 crop of the timed frames; `value` above stays on the plain atrium")
+                out["regimes"] = regimes
         print(json.dumps(out), flush=True)
     if comm is not None:
         comm.close()

@@ -5,6 +5,9 @@ reference-compiled sky model under oracle/_ref; everything else comes from the o
   sky_ref.npz     outputs of the REFERENCE's own hw_skymodel.c (oracle/_ref/libhwsky_ref.so):
                   sky_state_new for a grid of (elevation, turbidity, albedo) and sky_state_radiance
                   samples.  These pin both the oracle's and the product's sky restatement.
+  sky_ref_random.npz  the same model at 200 random (elevation, turbidity, albedo, theta, gamma, channel)
+                  draws (seed 7): what test_oracle_sky_matches_live_reference_build compares the oracle with
+                  where oracle/_ref was not built.
   duck_golden.npz oracle outputs on tests/golden/Duck.glb: sha256 of the node array, per-pixel
                   nodesVisited for the bvh-visualizer camera at 256x256, hit/t of the reference's
                   own test grid (src/tests/bvh.cpp:76-101), summary counts.  The counts equal the
@@ -45,6 +48,19 @@ def sky():
     np.savez_compressed(os.path.join(HERE, "sky_ref.npz"), cases=np.array(cases, np.float32), states=np.array(states, np.float32),
                         rcs=np.array(rcs, np.int32), bad=np.array(bad, np.float32), bad_rc=np.array(bad_rc, np.int32),
                         samples=np.array(samples, np.float64))
+
+
+def sky_random():
+    ref = orc.RefSky()
+    rng = np.random.default_rng(7)
+    params, rcs, states, angles, radiances = [], [], [], [], []
+    for _ in range(200):
+        elev = np.float32(rng.uniform(0, 1.5707)); turb = np.float32(rng.uniform(1, 10)); alb = rng.uniform(0, 1, 3).astype(np.float32)
+        rc, st = ref.state_new(elev, turb, alb)
+        th = np.float32(rng.uniform(0, 1.57)); gm = np.float32(rng.uniform(0, 3.14)); ch = int(rng.integers(0, 3))
+        params.append([elev, turb, *alb]); rcs.append(rc); states.append(st); angles.append([th, gm, ch]); radiances.append(ref.radiance(st, th, gm, ch))
+    np.savez_compressed(os.path.join(HERE, "sky_ref_random.npz"), params=np.array(params, np.float32), rcs=np.array(rcs, np.int32),
+                        states=np.array(states, np.float32), angles=np.array(angles, np.float32), radiances=np.array(radiances, np.float32))
 
 
 def duck_scene():
@@ -114,6 +130,6 @@ def duck_render64():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["sky", "duck", "duck_render", "duck_render64"]
+    which = sys.argv[1:] or ["sky", "sky_random", "duck", "duck_render", "duck_render64"]
     for w in which:
         globals()[w]()

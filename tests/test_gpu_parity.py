@@ -1415,7 +1415,7 @@ def test_courtyard_asset_bake_render_and_bench(tmp_path):
     assert np.array_equal(bits(img[..., :3]), bits(ref[..., :3]))
     assert s["closest_rays"] == st.closestRays and s["shadow_rays"] == st.shadowRays > 0
     out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--scene", path.replace(".gltf", ".pt"), "--width", "320", "--height", "192",
-                                   "--steps", "1", "--warmup", "1", "--bounces", "4", "--cpu-seconds", "1", "--no-live-counters"], stderr=subprocess.DEVNULL)
+                                   "--steps", "1", "--warmup", "1", "--bounces", "4", "--cpu-seconds", "1", "--no-live-counters", "--full"], stderr=subprocess.DEVNULL)
     line = json.loads(out.decode().strip().splitlines()[-1])
     assert line["value"] > 0 and line["nan_pixels"] == 0 and line["parity_crop"]["verdict"] == "bit-identical"
     assert "courtyard.pt" in line["config"]["workload"]
@@ -1576,7 +1576,7 @@ def test_bvh_visualizer_tool_png_is_the_grey_map_of_the_node_visit_pass(duck_pt,
 
 
 # ------------------------------------------------------------------ round 4: bench.py as its own launcher; product inputs of the checker
-def _bench_line(extra, tmp_path):
+def _bench_line(extra, tmp_path, mode=("--repeat", "3", "--full")):
     import json
     import subprocess
     import sys
@@ -1586,7 +1586,7 @@ def _bench_line(extra, tmp_path):
         rf.PtFormat.from_gltf(DUCK).save(duck)
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--scene", duck, "--width", "320", "--height", "192", "--steps", "2", "--warmup", "1",
-                        "--bounces", "4", "--cpu-seconds", "1", "--repeat", "3"] + extra, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+                        "--bounces", "4", "--cpu-seconds", "1"] + list(mode) + extra, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.startswith("{")]
     assert len(lines) == 1, "exactly ONE JSON line on stdout"
@@ -1621,6 +1621,23 @@ def test_bench_line_shape_is_the_same_however_the_rank_was_started(tmp_path):
     assert plain["exchange_ms"] is None and launched["exchange_ms"] is None
     ex = looped["exchange_ms"]
     assert len(ex["per_repeat_max_over_ranks"]) == 3 and all(0.0 < v < 1000.0 for v in ex["per_repeat_max_over_ranks"]) and ex["median"] == sorted(ex["per_repeat_max_over_ranks"])[1]
+
+
+def test_plain_bench_line_times_k_steps_once_and_dumps_the_timed_frame(tmp_path):
+    """Without --full the benchmark times exactly K steps once and prints the headline fields only; --dump-outputs writes the
+    timed frame, the same bytes as a --full run's with the same arguments (whose parity crop ties that frame to the oracle)."""
+    plain, err = _bench_line(["--gpus", "1", "--dump-outputs", str(tmp_path / "plain")], tmp_path, mode=())
+    full, _ = _bench_line(["--gpus", "1", "--no-live-counters", "--dump-outputs", str(tmp_path / "full")], tmp_path)
+    assert plain["steps"] == 2 and plain["warmup"] == 1 and plain["repeats"]["count"] == 1
+    assert abs(plain["ms_per_step"] * 2 - plain["timed_region_s"] * 1e3) < 0.11
+    for k in ("metric", "unit", "higher_is_better", "dtype", "n_gpus", "rays"):
+        assert plain[k] == full[k], k
+    assert not set(plain) & {"roofline", "parity_crop", "cpu_baseline", "occluder_cache", "self_shadow", "batch_depth_curve", "regimes"}
+    assert "live counter passes" not in err and full["parity_crop"]["verdict"] == "bit-identical"
+    a, b = np.load(tmp_path / "plain" / "accumulation.npy"), np.load(tmp_path / "full" / "accumulation.npy")
+    assert a.dtype == np.float32 and a.shape == (192, 320, 4)
+    assert np.array_equal(bits(a), bits(b))
+    assert int(np.isnan(a[..., :3]).any(axis=-1).sum()) == plain["nan_pixels"] == 0 and (a[..., :3] > 0).any()
 
 
 def test_product_computed_checker_inputs_equal_the_oracles_own():
