@@ -166,6 +166,32 @@ RF_API int rf_renderer_read_accumulation(rf_renderer* r, float* dst, uint32_t* a
 /* fsMain's return value (wgsl:59-63) as the BGRA8Unorm swap-chain texel, row-major. */
 RF_API int rf_renderer_read_tonemapped(rf_renderer* r, uint32_t* dst_bgra8);
 
+/* First-hit AOVs: the auxiliary buffers a denoiser, a compositor or a debug view wants next to the noisy image (no reference counterpart in the
+ * path tracer: nlrs::DeferredRenderer rasterises an albedo / normal / depth G-buffer instead, deferred_renderer_gbuffer_pass.wgsl).
+ * For every sample (pixel x, y, frame f) the renderer takes the primary ray it traces anyway -- the thin-lens ray of wgsl:36-54, same blue noise,
+ * same origin -- and records at its closest hit:
+ *   albedo   the texel value the shading uses for that hit (textureLookup, the linear value after the sRGB table)
+ *   normal   normalize(n), n = the interpolated shading normal (wgsl:396), normalize(v) = v * (1 / sqrt(dot(v, v))); (0, 0, 0) where dot(n, n) is 0
+ *            or not finite
+ *   depth    the hit's t: the distance from the ray's origin (lens offset included) along the unit primary direction
+ *   coverage 1
+ * and, where the ray leaves the scene, 0 for every value, coverage included.  Per pixel the renderer keeps SUMS in sample order in f32, exactly as the
+ * radiance (wgsl:47-57): bit-reproducible whatever the batching, slot order or number of ranks.  Means are the caller's to form: albedo and normal
+ * divided by the AOV sample count, depth divided by coverage (where coverage > 0).
+ *
+ * rf_renderer_set_aovs: flags 0 (the default: nothing is allocated or launched, image / stats / timings exactly as without) or RF_AOV_FIRST_HIT.
+ * While on, 32 more bytes per path slot of device memory (rf_renderer_memory_info counts them; a batch that no longer fits gets shallower).
+ * The AOV sums keep their own sample count -- the samples traced while the AOVs were on -- and are cleared, with the count set to 0, when the image is
+ * (a change through rf_renderer_set_render_parameters, a new tile shard, a newly bound accumulation buffer) and when the flags change.  Turned on
+ * partway through an accumulation, they cover only the later samples: the count stays below the accumulated sample count.
+ * rf_renderer_read_aovs: row-major width*height*4 floats each, {albedo.rgb, coverage} and {normal.xyz, depth} sums (the layout of
+ * rf_renderer_read_accumulation; either pointer may be NULL) and the AOV sample count.  With a tile shard set, this rank's pixels and zeros elsewhere:
+ * the sum of the ranks' reads is the whole frame.  (rf_renderer_gather_frame does not carry the AOVs.)
+ * A NULL handle or unknown flag bits: RF_ERROR_INVALID_ARGUMENT. */
+#define RF_AOV_FIRST_HIT 1u
+RF_API int rf_renderer_set_aovs(rf_renderer* r, uint32_t flags);
+RF_API int rf_renderer_read_aovs(rf_renderer* r, float* albedo_coverage, float* normal_depth, uint32_t* aov_sample_count);
+
 /* Deferred-lighting variant (replaces nlrs::DeferredRenderer's lighting + resolve passes, src/pt/deferred_renderer.hpp,
  * deferred_renderer_lighting_pass.wgsl:96-186 -- fixed 2-bounce surfaceColor, solar disk in the sky term, the
  * 1/16384 + 1024 offset constants :498-500 -- and deferred_renderer_resolve_pass.wgsl:33-54 -- 0.1 / 0.9 exponential
@@ -284,7 +310,8 @@ RF_API int  rf_comm_transport(const rf_comm* c, uint32_t* local_out);
  * what the one exchange of the multi-GPU path costs once the rank's own frame has drained.  Waits for that exchange; -1 before the first.  (No reference
  * counterpart: the reference is single-device, reference_path_tracer.cpp:565-595.) */
 RF_API int  rf_comm_last_exchange_ms(rf_comm* c, double* ms_out);
-/* Device memory held by a handle: path state + queues (148 B per path slot: eight packed xyz streams, two float4 streams, five u32 queues / lists; allocated on demand for the largest batch traced),
+/* Device memory held by a handle: path state + queues (148 B per path slot: eight packed xyz streams, two float4 streams, five u32 queues / lists; 180 B while the first-hit
+ * AOVs are on; allocated on demand for the largest batch traced),
  * the batch depth in use (lowered automatically when the device has less free memory than the default wants: same image,
  * more batches) and the resident scene.  Any pointer may be NULL. */
 RF_API int  rf_renderer_memory_info(const rf_renderer* r, uint64_t* path_state_bytes, uint64_t* paths_allocated, uint64_t* max_paths_per_batch, uint64_t* scene_bytes);

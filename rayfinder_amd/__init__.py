@@ -472,6 +472,28 @@ class ReferencePathTracer:
         check(lib.rf_renderer_read_tonemapped(self._h, _ptr(img)))
         return img
 
+    # first-hit AOVs (rf_renderer_set_aovs / rf_renderer_read_aovs; include/rayfinder_amd.h states what they hold)
+    def set_aovs(self, enabled=True):
+        """Turn the first-hit AOVs (albedo, shading normal, depth) on or off; any change clears their sums."""
+        check(lib.rf_renderer_set_aovs(self._h, _ffi.RF_AOV_FIRST_HIT if enabled else 0))
+
+    def read_aovs(self):
+        """-> dict of per-pixel SUMS in sample order: albedo (H,W,3), normal (H,W,3), depth (H,W), coverage (H,W), and samples (the AOV sample count)."""
+        h, w = self._params.height, self._params.width
+        ac = np.zeros((h, w, 4), np.float32); nd = np.zeros((h, w, 4), np.float32)
+        n = C.c_uint32(0)
+        check(lib.rf_renderer_read_aovs(self._h, _ptr(ac), _ptr(nd), C.byref(n)))
+        return dict(albedo=ac[..., :3], normal=nd[..., :3], depth=nd[..., 3], coverage=ac[..., 3], samples=n.value)
+
+    def aov_means(self):
+        """-> dict albedo (H,W,3) and normal (H,W,3) divided by the sample count, depth (H,W) divided by the coverage (0 where nothing was hit), coverage (H,W) as a
+        fraction, and samples.  All zeros before the first AOV sample."""
+        s = self.read_aovs()
+        n = np.float32(max(s["samples"], 1))
+        cov = s["coverage"]
+        depth = np.divide(s["depth"], cov, out=np.zeros_like(cov), where=cov > 0)
+        return dict(albedo=s["albedo"] / n, normal=s["normal"] / n, depth=depth, coverage=cov / n, samples=s["samples"])
+
     # deferred-lighting variant (nlrs::DeferredRenderer's lighting + resolve passes over a primary-ray G-buffer)
     def render_deferred(self, num_frames=1):
         check(lib.rf_renderer_render_deferred(self._h, num_frames))

@@ -36,6 +36,7 @@ RF_ERROR_INVALID_ARGUMENT = 1
 RF_ERROR_RUNTIME = 2
 RF_ERROR_NO_DEVICE = 3
 RF_ERROR_OUT_OF_RANGE = 4
+RF_AOV_FIRST_HIT = 1
 
 
 class Camera(C.Structure):
@@ -114,6 +115,8 @@ SIGNATURES = {
     "rf_renderer_render_progress_percentage": (C.c_float, [C.c_void_p]),
     "rf_renderer_read_accumulation": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
     "rf_renderer_read_tonemapped": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rf_renderer_set_aovs": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "rf_renderer_read_aovs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
     "rf_renderer_render_deferred": (C.c_int, [C.c_void_p, C.c_uint32]),
     "rf_renderer_reset_deferred": (C.c_int, [C.c_void_p]),
     "rf_renderer_read_deferred": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),

@@ -1,10 +1,12 @@
 // rf-render <scene.pt|scene.glb> [--width W] [--height H] [--spp N] [--bounces B] [--vfov deg]
 //           [--zenith deg] [--azimuth deg] [--turbidity t] [--exposure-stops s] [--out image.png]
-//           [--pfm image.pfm] [--gpus N]
+//           [--pfm image.pfm] [--aov-albedo a.pfm] [--aov-normal n.pfm] [--aov-depth d.pfm] [--gpus N]
 // Offline counterpart of the interactive `pt` app (src/pt/main.cpp): same default camera pose,
 // sky and exposure; renders all samples and writes the tonemapped image (and optionally the
 // mean radiance as PFM).  --gpus N: one host thread per GPU, the image tile-sharded across them, one RCCL
 // gather to GPU 0 at frame end (rf_renderer_gather_frame).
+// --aov-*: the means of the first-hit AOVs (rf_renderer_set_aovs): albedo and normal over the samples, depth over the samples that hit
+// something (a one-channel PFM, 0 where none did).  With --gpus N each rank reads its own tiles' AOVs and the host assembles them.
 #include "cli_common.hpp"
 
 #include <algorithm>
@@ -18,14 +20,17 @@ int main(int argc, char** argv)
     if (argc < 2)
     {
         std::printf("Usage: rf-render <scene.pt|scene.glb> [--width W] [--height H] [--spp N] [--bounces B] [--vfov deg]\n"
-                    "                 [--zenith deg] [--azimuth deg] [--turbidity t] [--exposure-stops s] [--out image.png] [--pfm image.pfm] [--gpus N]\n");
+                    "                 [--zenith deg] [--azimuth deg] [--turbidity t] [--exposure-stops s] [--out image.png] [--pfm image.pfm]\n"
+                    "                 [--aov-albedo a.pfm] [--aov-normal n.pfm] [--aov-depth d.pfm] [--gpus N]\n"
+                    "  --aov-albedo / --aov-normal / --aov-depth: mean first-hit albedo, shading normal (3-channel PFM) and depth (1-channel PFM, 0 where\n"
+                    "  no sample hit) -- the auxiliary inputs of a denoiser\n");
         return 0;
     }
     uint32_t    W = 1920, H = 1080, spp = 64, bounces = 2; // UI defaults src/pt/main.cpp:46-60
     uint32_t    gpus = 1;
     float       vfov = 70.0f, zenith = 30.0f, azimuth = 0.0f, turbidity = 1.0f;
     int         stops = 2;
-    std::string out = "render.png", pfm;
+    std::string out = "render.png", pfm, aovAlbedo, aovNormal, aovDepth;
     for (int i = 2; i + 1 < argc; i += 2)
     {
         const std::string k = argv[i];
@@ -42,6 +47,9 @@ int main(int argc, char** argv)
         else if (k == "--gpus") gpus = static_cast<uint32_t>(std::max(1, std::atoi(val)));
         else if (k == "--out") out = val;
         else if (k == "--pfm") pfm = val;
+        else if (k == "--aov-albedo") aovAlbedo = val;
+        else if (k == "--aov-normal") aovNormal = val;
+        else if (k == "--aov-depth") aovDepth = val;
         else
         {
             std::fprintf(stderr, "unknown option %s\n", k.c_str());
@@ -71,6 +79,11 @@ int main(int argc, char** argv)
     std::vector<uint32_t>           bgra(static_cast<size_t>(W) * H);
     std::vector<float>              acc;
     if (!pfm.empty()) acc.resize(static_cast<size_t>(W) * H * 4);
+    // first-hit AOV sums of the whole frame ({albedo, coverage}, {normal, depth}): every rank copies in the pixels of its own tiles
+    const bool         aovs = !aovAlbedo.empty() || !aovNormal.empty() || !aovDepth.empty();
+    std::vector<float> aovAc, aovNd;
+    uint32_t           aovSamples = 0;
+    if (aovs) aovAc.resize(static_cast<size_t>(W) * H * 4), aovNd.resize(static_cast<size_t>(W) * H * 4);
     double       seconds = 0.0;
     // rank r runs on device r -- modulo the devices there are: with more ranks than GPUs RCCL refuses the communicator (two ranks on one device), the local TEST transport
     // (RF_COMM_TRANSPORT=local in the environment: rf_comm.hip) runs them all on what is there -- how the exchange is exercised with many owners on a single-GPU box
@@ -87,6 +100,7 @@ int main(int argc, char** argv)
             rfCheck(rf_renderer_set_tile_shard(renderer, rank, gpus), "tile shard");
             rfCheck(rf_comm_create(commId, rank, gpus, d.device_ordinal, &comm), "RCCL communicator");
         }
+        if (aovs) rfCheck(rf_renderer_set_aovs(renderer, RF_AOV_FIRST_HIT), "AOVs");
         const auto t0 = std::chrono::steady_clock::now();
         rfCheck(rf_renderer_render(renderer, spp), "render");
         void* gathered = nullptr;
@@ -97,6 +111,26 @@ int main(int argc, char** argv)
         rfCheck(rf_renderer_get_stats(renderer, &stats), "stats");
         closestRays += stats.closest_rays;
         shadowRays += stats.shadow_rays;
+        if (aovs)
+        {
+            // (the tiles are disjoint: each rank copies the pixels of its own tiles into the frame buffers, and no two ranks write the same pixel)
+            std::vector<float> ac(static_cast<size_t>(W) * H * 4), nd(ac.size());
+            uint32_t           n = 0, numTiles = 0;
+            rfCheck(rf_renderer_read_aovs(renderer, ac.data(), nd.data(), &n), "read AOVs");
+            rfCheck(rf_renderer_shard_tiles(renderer, nullptr, &numTiles), "shard tiles");
+            std::vector<uint32_t> tiles(numTiles);
+            rfCheck(rf_renderer_shard_tiles(renderer, tiles.data(), &numTiles), "shard tiles");
+            const uint32_t tilesX = (W + 31) / 32;
+            for (const uint32_t t : tiles)
+                for (uint32_t y = (t / tilesX) * 32; y < std::min(H, (t / tilesX) * 32 + 32); ++y)
+                    for (uint32_t x = (t % tilesX) * 32; x < std::min(W, (t % tilesX) * 32 + 32); ++x)
+                    {
+                        const size_t i = 4 * (static_cast<size_t>(y) * W + x);
+                        std::copy(ac.begin() + i, ac.begin() + i + 4, aovAc.begin() + i);
+                        std::copy(nd.begin() + i, nd.begin() + i + 4, aovNd.begin() + i);
+                    }
+            if (rank == 0) aovSamples = n;
+        }
         if (rank == 0)
         {
             if (comm)
@@ -133,6 +167,29 @@ int main(int argc, char** argv)
     }
     if (!writePngRgba(out, rgba.data(), W, H)) return 1;
     if (!pfm.empty()) writePfm(pfm, acc.data(), W, H, 1.0f / static_cast<float>(std::max(spp, 1u)));
+    if (aovs)
+    {
+        // means (f32 divisions, as ReferencePathTracer.aov_means): albedo / normal over the AOV samples, depth over the coverage
+        const float n = static_cast<float>(std::max(aovSamples, 1u));
+        const auto  write = [&](const std::string& path, uint32_t channels, auto&& value) {
+            if (path.empty()) return true;
+            FILE* fp = std::fopen(path.c_str(), "wb");
+            if (!fp) return false;
+            std::fprintf(fp, "%s\n%u %u\n-1.0\n", channels == 3 ? "PF" : "Pf", W, H);
+            std::vector<float> row(static_cast<size_t>(channels) * W);
+            for (uint32_t y = 0; y < H; ++y) // (bottom row first)
+            {
+                for (uint32_t x = 0; x < W; ++x)
+                    for (uint32_t c = 0; c < channels; ++c) row[channels * x + c] = value(4 * (static_cast<size_t>(H - 1 - y) * W + x), c);
+                std::fwrite(row.data(), sizeof(float), row.size(), fp);
+            }
+            std::fclose(fp);
+            return true;
+        };
+        const bool ok = write(aovAlbedo, 3, [&](size_t i, uint32_t c) { return aovAc[i + c] / n; }) && write(aovNormal, 3, [&](size_t i, uint32_t c) { return aovNd[i + c] / n; }) &&
+                        write(aovDepth, 1, [&](size_t i, uint32_t) { return aovAc[i + 3] > 0.0f ? aovNd[i + 3] / aovAc[i + 3] : 0.0f; });
+        if (!ok) return 1;
+    }
     rf_pt_format_destroy(pt);
     return 0;
 }

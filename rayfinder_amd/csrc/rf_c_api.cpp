@@ -20,6 +20,7 @@
 #include <vector>
 
 static_assert(sizeof(rf_camera) == sizeof(rf::Camera));
+static_assert(RF_AOV_FIRST_HIT == rf::Renderer::kAovFirstHit);
 
 struct rf_renderer
 {
@@ -233,6 +234,25 @@ int rf_renderer_read_deferred(rf_renderer* r, float* sample_rgb, float* accumula
         require(r, "null argument");
         r->impl->readDeferred(sample_rgb, accumulation_rgb, bgra8);
         if (frame_count) *frame_count = r->impl->deferredFrameCount();
+        return RF_OK;
+    });
+}
+
+int rf_renderer_set_aovs(rf_renderer* r, uint32_t flags)
+{
+    return guarded([&] {
+        require(r, "null argument");
+        require((flags & ~RF_AOV_FIRST_HIT) == 0u, "unknown AOV flag bits");
+        r->impl->setAovs(flags);
+        return RF_OK;
+    });
+}
+
+int rf_renderer_read_aovs(rf_renderer* r, float* albedo_coverage, float* normal_depth, uint32_t* aov_sample_count)
+{
+    return guarded([&] {
+        require(r, "null argument");
+        r->impl->readAovs(albedo_coverage, normal_depth, aov_sample_count);
         return RF_OK;
     });
 }

@@ -63,6 +63,9 @@ struct PathStreams
     P3*     thrOut;  // [position in the NEXT queue]
     P3*     noiseOut; // [position in the NEXT queue]: kShade copies the triple along; the shadow launch of the bounce reads it here
 };
+// (The first-hit AOV records -- [2 slot, 2 slot + 1]: {albedo.rgb, coverage}, {normal.xyz, depth}, written by kShade<false, true> at bounce 1 -- are NOT a member here: one more
+// pointer in PathStreams moves every later kernel argument of the traversal kernels, and that alone changed the code of the any-hit kTraceWide instantiations by up to
+// 3 %.  kShade takes them as its last argument, kAccumulateAov as an argument of its own.)
 
 // 12-byte load of the xyz part of a float4 stream element (global_load_dwordx3): the L1 -> VGPR return path
 // bounds the traversal kernels, so the unused .w lanes are not fetched
@@ -362,6 +365,9 @@ constexpr uint32_t kAccPixels = RF_EXP_ACC_PIXELS;
 constexpr uint32_t kAccPixels = 4;
 #endif
 constexpr uint32_t kAccMaxSamples = 1024;
+// kAccumulateAovRuns: 8 pixels x 8 AOV channels = one summing lane each of a 64-lane workgroup; their runs are staged in chunks of kAovChunk samples
+// (8 x 8 x (32 + 1) floats = 8.4 KB of LDS, whatever the batch depth)
+constexpr uint32_t kAovPixels = 8, kAovChunk = 32;
 
 // ------------------------------------------------------------------------------------------------
 // Scheduling constants of the persistent traversal kernel (tuned on the atrium, tools/gpu_ab.py).
@@ -401,7 +407,7 @@ constexpr uint32_t kNodeDone = 0xFFFFFFFEu; // ray finished, result not yet writ
 using SamplePermutationKernel = void (*)(uint32_t firstFrame, uint32_t spp, uint32_t numSamples, uint32_t* perm, uint32_t* inv);
 using RaygenKernel = void (*)(FrameParams fp, DeviceScene scene, const uint32_t* tileIds, PathStreams ps, uint32_t* queue, uint32_t* queueCount, DeviceCounters* counters);
 using TraceClosestKernel = void (*)(DeviceScene scene, PathStreams ps, const uint32_t* queue, const uint32_t* queueCount, DeviceCounters* counters);
-using ShadeKernel = void (*)(DeviceScene scene, SkyStateGpu sky, SunBasis sunBasis, PathStreams ps, const uint32_t* queue, const uint32_t* queueCount, uint32_t* hitQueue, uint32_t* hitCount, uint32_t* missQueue, uint32_t* missSlots, uint32_t* missCount, uint32_t* shadowList, uint32_t* shadowListCount, uint32_t bounceFlags, uint32_t sortScale);
+using ShadeKernel = void (*)(DeviceScene scene, SkyStateGpu sky, SunBasis sunBasis, PathStreams ps, const uint32_t* queue, const uint32_t* queueCount, uint32_t* hitQueue, uint32_t* hitCount, uint32_t* missQueue, uint32_t* missSlots, uint32_t* missCount, uint32_t* shadowList, uint32_t* shadowListCount, uint32_t bounceFlags, uint32_t sortScale, float4* aov);
 using SkyKernel = void (*)(SkyStateGpu sky, PathStreams ps, const uint32_t* missSlots, const uint32_t* missQueue, const uint32_t* missCount, uint32_t firstBounce);
 using TraceShadowKernel = void (*)(DeviceScene scene, SkyStateGpu sky, SunBasis sunBasis, PathStreams ps, const uint32_t* queue, const uint32_t* queueCount, DeviceCounters* counters, uint32_t firstBounce);
 using TraceWideKernel = void (*)(DeviceScene scene, WideScene wide, SkyStateGpu sky, SunBasis sunBasis, PathStreams ps, const uint32_t* queue, const uint32_t* queueCount, uint32_t* cursor, DeviceCounters* counters, uint32_t refillMin, uint32_t leafVote, uint32_t chunkMax, float tMax, uint32_t flags);
@@ -411,6 +417,7 @@ using HitPointsKernel = void (*)(DeviceScene scene, const float4* hit, P3* rayO,
 using BounceTotalsKernel = void (*)(const uint32_t* queueCounts, uint32_t numBounces, unsigned long long* totals, const uint32_t* listCounts, unsigned long long lookMask, unsigned long long* lookBatch, const uint32_t* shadowListCounts, unsigned long long selfMask, DeviceCounters* counters);
 using AccumulateKernel = void (*)(FrameParams fp, const uint32_t* tileIds, PathStreams ps, float4* image);
 using AccumulateRunsKernel = void (*)(FrameParams fp, const uint32_t* tileIds, PathStreams ps, float4* image);
+using AccumulateAovKernel = void (*)(FrameParams fp, const uint32_t* tileIds, const float4* aov, float4* albedoCoverage, float4* normalDepth);
 using TonemapKernel = void (*)(const float4* image, uint32_t n, uint32_t accumulatedSamples, float exposure, uint32_t* out);
 using PrimaryStatsKernel = void (*)(DeviceScene scene, Camera cam, uint32_t width, uint32_t height, uint32_t* nodesVisited, uint8_t* hitOut, float* tOut, uint32_t* triTests, DeviceCounters* counters);
 using IntersectRaysKernel = void (*)(DeviceScene scene, const float* rays, uint64_t n, float tMax, uint32_t* triOut, float* tOut, float* uvOut, float* pOut, uint32_t* nvOut, uint32_t* ttOut, DeviceCounters* counters);
@@ -430,11 +437,12 @@ OccludedRaysKernel    occludedRaysKernel();
 // rf_shade.hip
 SamplePermutationKernel samplePermutationKernel();
 RaygenKernel            raygenKernel(bool f32Transcendentals);
-ShadeKernel             shadeKernel(bool sorted);
+ShadeKernel             shadeKernel(bool sorted, bool aov = false); // aov: the bounce-1 instantiation that also writes the first-hit AOVs (unsorted only)
 SkyKernel               skyKernel(bool f32Transcendentals);
 BounceTotalsKernel      bounceTotalsKernel();
 AccumulateKernel        accumulateKernel();
 AccumulateRunsKernel    accumulateRunsKernel(uint32_t pixelsPerWorkgroup); // 1, 2 or kAccPixels
+AccumulateAovKernel     accumulateAovKernel(bool runs);                    // runs: the LDS-staged kernel for the pixel-major slot order (slotGroupShift 0)
 TonemapKernel           tonemapKernel();
 DeferredLightingKernel  deferredLightingKernel();
 } // namespace kern

@@ -162,12 +162,19 @@ struct Renderer::Impl
     float4*                 image = nullptr; // compact tile-major accumulation buffer
     uint64_t                imageBytes = 0;
     bool                    imageDirty = true; // needs zeroing before the next sample
+    // first-hit AOVs (rf_renderer_set_aovs; off by default: nothing below is allocated or launched then).  Sums in sample order like the image, in two compact
+    // tile-major float4 buffers, over the aovSamples samples traced since they were last cleared -- on the image's events (aovDirty is set wherever imageDirty is
+    // raised by a new accumulation) and whenever the flags change
+    uint32_t                aovFlags = 0, aovSamples = 0;
+    bool                    aovDirty = true;
+    DeviceBuffer<float4>    aovAlbedoCoverage, aovNormalDepth;
 
     uint64_t                validPixels = 0;     // pixels of this rank's tiles that lie inside the frame
     unsigned long long      primaryRaysHost = 0; // samples traced x validPixels since the last resetStats()
     uint64_t                maxPaths = 0;
     DeviceBuffer<P3>        sRayO, sRayD, sRayD2, sThr, sThr2, sPending, sNoise, sNoise2; // queue-position arrays, packed xyz; rayD / thr / noise: double-buffered (PathStreams)
     DeviceBuffer<float4>    sRad, sHit;
+    DeviceBuffer<float4>    sAov; // [2 slot, 2 slot + 1] the first-hit AOV record of each path (kShade<false, true>); allocated with the path state while the AOVs are on
     DeviceBuffer<uint32_t>  queueA, queueB, missQueue, missSlots, shadowList, queueCounts; // shadowList: kShade's list of the shadow rays its own-triangle test has not settled (kShadeSelfShadow)
     DeviceBuffer<DeviceCounters> counters;
     DeviceBuffer<unsigned long long> bounceTotals; // 4 x kMaxBounceStats: closest-hit rays, shadow rays, shadow rays answered by kShadowFirstLook, shadow rays settled by kShade's own-triangle test
@@ -280,11 +287,18 @@ struct Renderer::Impl
 
     // bytes of path state + queues per path slot (eight packed xyz streams, two float4 streams, five u32 queues / lists): 148
     static constexpr uint64_t kBytesPerPath = 8 * sizeof(P3) + 2 * sizeof(float4) + 5 * sizeof(uint32_t);
+    // ... plus the 32-byte AOV record while the first-hit AOVs are on
+    static constexpr uint64_t kAovBytesPerPath = 2 * sizeof(float4);
+    uint64_t bytesPerPath() const { return kBytesPerPath + (aovFlags != 0u ? kAovBytesPerPath : 0u); }
+    uint64_t pathStateBytes() const { return allocatedPaths * kBytesPerPath + sAov.count * sizeof(float4); }
+    // the path state holds a batch of `paths` (the AOV records included while the AOVs are on)
+    bool pathStateHolds(uint64_t paths) const { return paths <= allocatedPaths && (aovFlags == 0u || sAov.count >= 2 * paths); }
 
     void releasePathState()
     {
         sRayO.release(), sRayD.release(), sRayD2.release(), sThr.release(), sThr2.release(), sRad.release(), sHit.release();
         sPending.release(), sNoise.release(), sNoise2.release(), queueA.release(), queueB.release(), missQueue.release(), missSlots.release(), shadowList.release();
+        sAov.release();
         allocatedPaths = 0;
     }
 
@@ -294,7 +308,7 @@ struct Renderer::Impl
     // caller retries with a smaller batch.  allocatedPaths is only raised once every buffer exists.
     bool ensurePathState(uint64_t paths)
     {
-        if (paths <= allocatedPaths) return true;
+        if (pathStateHolds(paths)) return true;
         RF_HIP(hipStreamSynchronize(stream));
         releasePathState();
         const auto tryAlloc = [](auto& buf, uint64_t n) -> bool {
@@ -312,7 +326,8 @@ struct Renderer::Impl
         };
         const bool ok = tryAlloc(sRayO, paths) && tryAlloc(sRayD, paths) && tryAlloc(sRayD2, paths) && tryAlloc(sThr, paths) && tryAlloc(sThr2, paths) &&
                         tryAlloc(sRad, paths) && tryAlloc(sHit, paths) && tryAlloc(sPending, paths) && tryAlloc(sNoise, paths) && tryAlloc(sNoise2, paths) &&
-                        tryAlloc(queueA, paths) && tryAlloc(queueB, paths) && tryAlloc(missQueue, paths) && tryAlloc(missSlots, paths) && tryAlloc(shadowList, paths);
+                        tryAlloc(queueA, paths) && tryAlloc(queueB, paths) && tryAlloc(missQueue, paths) && tryAlloc(missSlots, paths) && tryAlloc(shadowList, paths) &&
+                        (aovFlags == 0u || tryAlloc(sAov, 2 * paths));
         if (!ok)
         {
             releasePathState();
@@ -328,8 +343,8 @@ struct Renderer::Impl
     {
         size_t freeBytes = 0, totalBytes = 0;
         RF_HIP(hipMemGetInfo(&freeBytes, &totalBytes));
-        const uint64_t budget = static_cast<uint64_t>(freeBytes) + allocatedPaths * kBytesPerPath;
-        return budget / 10 * 9 / kBytesPerPath;
+        const uint64_t budget = static_cast<uint64_t>(freeBytes) + pathStateBytes();
+        return budget / 10 * 9 / bytesPerPath();
     }
 
     void configureShard()
@@ -363,6 +378,14 @@ struct Renderer::Impl
         if (image == ownedImage.ptr) imageBytes = pixelsPadded * sizeof(float4);
         accumulated = 0;
         imageDirty = true;
+        clearAovs();
+    }
+
+    // the AOV sums start again (with the image, or when the flags change): zeroed before the next sample, sized for the shard then
+    void clearAovs()
+    {
+        aovSamples = 0;
+        aovDirty = true;
     }
 
     template<typename F>
@@ -787,10 +810,13 @@ struct Renderer::Impl
             launchTimed(2, [&] {
                 const uint32_t shadeFlags = (bounce == numBounces ? kShadeLastBounce : 0u) | (bounce == 1 ? kShadeFirstBounce : 0u) | (selfShadow ? kShadeSelfShadow : 0u);
                 const dim3     shadeGrid(optShadeBlocks ? std::min(itemBlocks, optShadeBlocks) : itemBlocks);
-                if (optShadeSortFromBounce != 0u && bounce >= optShadeSortFromBounce)
-                    hipLaunchKernelGGL(shadeKernel(true), shadeGrid, dim3(kBlock), 0, stream, scene, sky, sunBasis, ps, qIn, countIn, qOut, countOut, missQueue.ptr, missSlots.ptr, missCount, shadowList.ptr, shadowListCount, shadeFlags, sortScale);
+                // (the first-hit AOVs are written by the unsorted bounce-1 kernel, whatever shade_sort_from_bounce says: the sort is a scheduling choice)
+                if (aovFlags != 0u && bounce == 1)
+                    hipLaunchKernelGGL(shadeKernel(false, true), shadeGrid, dim3(kBlock), 0, stream, scene, sky, sunBasis, ps, qIn, countIn, qOut, countOut, missQueue.ptr, missSlots.ptr, missCount, shadowList.ptr, shadowListCount, shadeFlags, 0u, sAov.ptr);
+                else if (optShadeSortFromBounce != 0u && bounce >= optShadeSortFromBounce)
+                    hipLaunchKernelGGL(shadeKernel(true), shadeGrid, dim3(kBlock), 0, stream, scene, sky, sunBasis, ps, qIn, countIn, qOut, countOut, missQueue.ptr, missSlots.ptr, missCount, shadowList.ptr, shadowListCount, shadeFlags, sortScale, nullptr);
                 else
-                    hipLaunchKernelGGL(shadeKernel(false), shadeGrid, dim3(kBlock), 0, stream, scene, sky, sunBasis, ps, qIn, countIn, qOut, countOut, missQueue.ptr, missSlots.ptr, missCount, shadowList.ptr, shadowListCount, shadeFlags, 0u);
+                    hipLaunchKernelGGL(shadeKernel(false), shadeGrid, dim3(kBlock), 0, stream, scene, sky, sunBasis, ps, qIn, countIn, qOut, countOut, missQueue.ptr, missSlots.ptr, missCount, shadowList.ptr, shadowListCount, shadeFlags, 0u, nullptr);
                 // the paths that left the scene at this bounce, while its direction / throughput arrays are intact
                 // (its slot comes with the miss list: kSky reads nothing of the bounce's queue -- round 5: reading the slot through the queue position was a third
                 // dependent gather, and kShade + kSky went from 19.7 to 15.8 ms per 64 spp without it)
@@ -859,6 +885,16 @@ struct Renderer::Impl
             }
             else
                 hipLaunchKernelGGL(accumulateKernel(), dim3((fp.pixelsPadded + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, fp, tileIds.ptr, ps, image);
+            // the first-hit AOV sums, in the same sample order (timed with the accumulation: rf_stats has no entry of its own for them)
+            if (aovFlags != 0u && numBounces != 0u) // (no bounce, no primary hit: the records were not written)
+            {
+                if (fp.slotGroupShift == 0u && numSamples > 4u && optAccumulateRuns)
+                    hipLaunchKernelGGL(accumulateAovKernel(true), dim3((fp.pixelsPadded + kAovPixels - 1) / kAovPixels), dim3(64), 0, stream, fp, tileIds.ptr, sAov.ptr,
+                                       aovAlbedoCoverage.ptr, aovNormalDepth.ptr);
+                else
+                    hipLaunchKernelGGL(accumulateAovKernel(false), dim3((fp.pixelsPadded + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, fp, tileIds.ptr, sAov.ptr,
+                                       aovAlbedoCoverage.ptr, aovNormalDepth.ptr);
+            }
         });
         RF_HIP(hipGetLastError());
         RF_HIP(hipEventRecord(bt.stop, stream));
@@ -1181,6 +1217,7 @@ void Renderer::setRenderParameters(const RenderParameters& p)
     m.updateSunBasis();
     m.accumulated = 0;
     m.imageDirty = true;
+    m.clearAovs();
     if (resized) m.configureShard();
 }
 
@@ -1218,6 +1255,17 @@ void Renderer::render(uint32_t numFrames)
             RF_HIP(hipMemsetAsync(m.image, 0, pixelsPadded * sizeof(float4), m.stream)); // wgsl:47-49
             m.imageDirty = false;
         }
+        if (m.aovFlags != 0u && m.aovDirty)
+        {
+            if (m.aovAlbedoCoverage.count < pixelsPadded)
+            {
+                RF_HIP(hipStreamSynchronize(m.stream)); // (a smaller buffer may still be read by the last batch)
+                m.aovAlbedoCoverage.alloc(pixelsPadded), m.aovNormalDepth.alloc(pixelsPadded);
+            }
+            RF_HIP(hipMemsetAsync(m.aovAlbedoCoverage.ptr, 0, pixelsPadded * sizeof(float4), m.stream));
+            RF_HIP(hipMemsetAsync(m.aovNormalDepth.ptr, 0, pixelsPadded * sizeof(float4), m.stream));
+            m.aovDirty = false;
+        }
         // equal batches (320 samples with room for 256 per batch -> 160 + 160, not 256 + 64): a small trailing batch has
         // short launches and, with few samples per pixel, less coherent waves
         // m.maxPaths is the CONFIGURED depth (the default or the caller's) and is never changed here: what a call has to give up
@@ -1231,7 +1279,7 @@ void Renderer::render(uint32_t numFrames)
             const uint32_t numBatches = (todo + perBatch - 1) / perBatch;
             n = (todo + numBatches - 1) / numBatches;
             const uint64_t need = static_cast<uint64_t>(n) * pixelsPadded;
-            if (need <= m.allocatedPaths) break;
+            if (m.pathStateHolds(need)) break;
             // The batch depth is a speed knob, never a requirement: a device with less free memory than the
             // batch wants (a smaller or shared GPU, a second handle on this one) traces the same samples in more, smaller
             // batches -- same image.  First by what hipMemGetInfo reports, then by halving if hipMalloc still refuses.
@@ -1242,7 +1290,7 @@ void Renderer::render(uint32_t numFrames)
                 continue;
             }
             if (m.ensurePathState(need)) break;
-            if (n == 1) throw std::runtime_error("out of device memory: one sample of the frame (" + std::to_string(need * Impl::kBytesPerPath >> 20) + " MiB of path state) does not fit");
+            if (n == 1) throw std::runtime_error("out of device memory: one sample of the frame (" + std::to_string(need * m.bytesPerPath() >> 20) + " MiB of path state) does not fit");
             depth = std::max<uint64_t>(pixelsPadded, depth / 2);
         }
         if (depth != m.effectivePaths)
@@ -1259,6 +1307,7 @@ void Renderer::render(uint32_t numFrames)
         m.hostStats.batchSamplesUsed = n, m.hostStats.batchPathsUsed = static_cast<uint64_t>(n) * pixelsPadded, ++m.hostStats.batchesTraced;
         m.frameCount += n;
         m.accumulated += n;
+        if (m.aovFlags != 0u) m.aovSamples += n;
         remaining -= n;
     }
 }
@@ -1306,6 +1355,44 @@ void Renderer::readAccumulation(float* dst)
     untileHost(compact.data(), m.tiles.data(), static_cast<uint32_t>(m.tiles.size()), m.params.width, m.params.height, dst);
 }
 
+void Renderer::setAovs(uint32_t flags)
+{
+    Impl& m = *mImpl;
+    if (flags == m.aovFlags) return;
+    RF_HIP(hipSetDevice(m.device));
+    RF_HIP(hipStreamSynchronize(m.stream)); // (a batch in flight may still write the records or the sums)
+    m.aovFlags = flags;
+    m.clearAovs();
+    if (flags == 0u)
+    {
+        // off: nothing of the AOVs stays allocated (the path state keeps its depth; the next batch that needs the records allocates them again)
+        m.sAov.release();
+        m.aovAlbedoCoverage.release();
+        m.aovNormalDepth.release();
+    }
+}
+
+uint32_t Renderer::aovFlags() const { return mImpl->aovFlags; }
+
+void Renderer::readAovs(float* albedoCoverage, float* normalDepth, uint32_t* sampleCount)
+{
+    Impl& m = *mImpl;
+    synchronize();
+    const size_t pixelsPadded = m.tiles.size() * 1024;
+    const bool   empty = m.aovFlags == 0u || m.aovDirty || m.aovSamples == 0u;
+    const auto   read = [&](const DeviceBuffer<float4>& buf, float* dst) {
+        if (dst == nullptr) return;
+        std::memset(dst, 0, static_cast<size_t>(m.params.width) * m.params.height * 4 * sizeof(float));
+        if (empty || pixelsPadded == 0) return;
+        std::vector<float> compact(pixelsPadded * 4);
+        RF_HIP(hipMemcpy(compact.data(), buf.ptr, pixelsPadded * sizeof(float4), hipMemcpyDeviceToHost));
+        untileHost(compact.data(), m.tiles.data(), static_cast<uint32_t>(m.tiles.size()), m.params.width, m.params.height, dst);
+    };
+    read(m.aovAlbedoCoverage, albedoCoverage);
+    read(m.aovNormalDepth, normalDepth);
+    if (sampleCount) *sampleCount = empty ? 0u : m.aovSamples;
+}
+
 void*    Renderer::accumulationDevicePointer() const { return mImpl->image; }
 
 void Renderer::clearAccumulationIfStale()
@@ -1343,7 +1430,7 @@ void Renderer::memoryInfo(uint64_t& pathStateBytes, uint64_t& pathsAllocated, ui
 {
     const Impl& m = *mImpl;
     pathsAllocated = m.allocatedPaths;
-    pathStateBytes = m.allocatedPaths * Impl::kBytesPerPath;
+    pathStateBytes = m.pathStateBytes();
     maxPathsPerBatch = m.effectivePaths ? std::min(m.effectivePaths, m.maxPaths) : m.maxPaths;
     sceneBytes = (m.nodes.count + m.triangles.count + m.wideNodes.count + m.wideCompact.count + m.wideHot.count + m.wideOwn.count + m.wideQuad.count + m.wideQuadHalf.count + m.wideQuadLocal.count + m.wideOct.count + m.attributes.count + m.shadeRecords.count) * sizeof(float4) +
                  m.texels.count * sizeof(uint32_t) + m.bigLeaves.count * sizeof(uint2) + m.occluderGrid.count * sizeof(uint32_t); // (the occluder grid: allocated by the first batch)
@@ -1370,6 +1457,7 @@ void Renderer::bindAccumulationBuffer(void* devicePtr, uint64_t bytes)
     m.imageBytes = bytes;
     m.accumulated = 0;
     m.imageDirty = true;
+    m.clearAovs();
 }
 
 void Renderer::readTonemapped(uint32_t* dst)

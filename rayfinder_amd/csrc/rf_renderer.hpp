@@ -129,6 +129,12 @@ public:
     // Row-major width*height*4 floats (sum of samples, 16-B stride as the reference's
     // array<vec3f>); pixels outside this rank's tiles are zero.
     void readAccumulation(float* dst);
+    // First-hit AOVs (rf_renderer_set_aovs / rf_renderer_read_aovs): flags 0 = off (default), kAovFirstHit = on.  Any change of the flags clears the sums.
+    // Read: row-major width*height*4 floats each ({albedo.rgb, coverage} and {normal.xyz, depth} SUMS, this rank's pixels; NULL = skip) and the AOV sample count.
+    static constexpr uint32_t kAovFirstHit = 1u;
+    void     setAovs(uint32_t flags);
+    uint32_t aovFlags() const;
+    void     readAovs(float* albedoCoverage, float* normalDepth, uint32_t* sampleCount);
     // Device pointer of the compact tile-major accumulation buffer (numTiles*1024 float4) and a
     // way to render into caller-owned device memory (e.g. a torch tensor used for the RCCL gather).
     void*    accumulationDevicePointer() const;

@@ -111,17 +111,31 @@ __global__ __launch_bounds__(kBlock) void kRaygen(FrameParams fp, DeviceScene sc
 // occupies ONE contiguous run of the queue, so queue order stays slot order at the scale of 1024 entries (what is indexed by slot --
 // the blue-noise triple, the radiance sum -- is touched by the same workgroups as before).  `sortScale`: bin of triangle t =
 // (t * sortScale) >> 32.
+// one slot's first-hit AOV record (kShade<false, true>): two 16-byte stores, non-temporal like kShade's other streams (read once, by kAccumulateAov after the last bounce)
+typedef float v4f __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void storeAov(float4* aov, uint32_t slot, Vec3 albedo, float coverage, Vec3 normal, float depth)
+{
+    v4f* const p = reinterpret_cast<v4f*>(aov + 2 * static_cast<size_t>(slot));
+    __builtin_nontemporal_store(v4f{albedo.x, albedo.y, albedo.z, coverage}, p);
+    __builtin_nontemporal_store(v4f{normal.x, normal.y, normal.z, depth}, p + 1);
+}
+
 #if defined(RF_EXP_SHADE_WAVES)
 #define RF_SHADE_BOUNDS __launch_bounds__(kBlock, RF_EXP_SHADE_WAVES)
 #else
 #define RF_SHADE_BOUNDS __launch_bounds__(kBlock) // (SORTED: 154 registers -- 137 before the own-triangle test --, three waves per SIMD; forced into 128 for four it was 2.5 % slower)
 #endif
-template<bool SORTED>
+// AOV (launched at bounce 1 while the first-hit AOVs are on, rf_renderer_set_aovs): every entry also writes its slot's 32-byte AOV record aov[2 slot .. 2 slot + 1] --
+// {albedo.rgb, 1}, {normalize(n), t} for a hit (what this kernel holds anyway: the texel, the interpolated normal, and the .w of the hit record it reads), zeros for a
+// miss.  Every valid slot is in the bounce-1 queue exactly once, so the records need no clearing.  The default instantiations do not contain this code (`aov` is
+// their last argument, unused: resources and code as before, tools/kernel_resources.sh).
+template<bool SORTED, bool AOV>
 __global__ RF_SHADE_BOUNDS void kShade(DeviceScene scene, SkyStateGpu sky, SunBasis sunBasis, PathStreams ps, const uint32_t* queue,
                                                   const uint32_t* queueCount, uint32_t* hitQueue, uint32_t* hitCount, uint32_t* missQueue, uint32_t* missSlots,
-                                                  uint32_t* missCount, uint32_t* shadowList, uint32_t* shadowListCount, uint32_t bounceFlags, uint32_t sortScale)
+                                                  uint32_t* missCount, uint32_t* shadowList, uint32_t* shadowListCount, uint32_t bounceFlags, uint32_t sortScale, float4* aov)
 {
     static_assert(kSortBins == kBlock, "one bin per thread");
+    static_assert(!(SORTED && AOV), "the AOVs are written by the unsorted bounce-1 kernel");
     __shared__ uint32_t sScratch[8];
     __shared__ uint32_t sHist[SORTED ? kSortBins : 1], sStart[SORTED ? kSortBins : 1], sPerm[SORTED ? kItems * kBlock : 1];
     __shared__ float    sLut[256];
@@ -181,6 +195,8 @@ __global__ RF_SHADE_BOUNDS void kShade(DeviceScene scene, SkyStateGpu sky, SunBa
         hitTri[k] = tri;
         isMiss[k] = valid && tri == kMiss; // the path ends in the sky: evaluated densely by this bounce's kSky launch
         isHit[k] = valid && tri != kMiss;
+        if constexpr (AOV)
+            if (isMiss[k]) storeAov(aov, slots[k], Vec3{}, 0.0f, Vec3{}, 0.0f); // a miss: every AOV value 0, coverage included
     }
     if constexpr (SORTED)
     {
@@ -316,7 +332,7 @@ __global__ RF_SHADE_BOUNDS void kShade(DeviceScene scene, SkyStateGpu sky, SunBa
         r.a0 = rec[3], r.a1 = rec[4], r.a2 = rec[5], r.a3 = rec[6];
         return r;
     };
-    const auto shade = [&](int k, float hu, float hv, const ShadeRecord& cur, uint32_t out) -> bool {
+    const auto shade = [&](int k, float hu, float hv, float hitT, const ShadeRecord& cur, uint32_t out) -> bool {
         const uint32_t i = entryIndex(k);
         (void)i;
         Vec3 shadowOrigin;
@@ -357,6 +373,14 @@ __global__ RF_SHADE_BOUNDS void kShade(DeviceScene scene, SkyStateGpu sky, SunBa
 #else
         const Vec3    albedo = evalTexture(scene, sLut, __float_as_uint(a3.w), uvx, uvy);
 #endif
+        if constexpr (AOV)
+        {
+            // first-hit AOVs: the texel, the unit shading normal (0 where n has no direction: |n|^2 zero or not finite) and the distance along the unit primary direction
+            const float nn = dot(n, n);
+            const Vec3  unitN = (nn != 0.0f && isfinite(nn)) ? normalize(n) : Vec3{};
+            storeAov(aov, slots[k], albedo, 1.0f, unitN, hitT);
+        }
+        else (void)hitT, (void)aov;
 
         // next-event estimation towards the sun, wgsl:194-203 (cosine is not clamped)
         const Vec3 lightDirection = sunSample(sky, sunBasis, nx, cosPhi, sinPhi);
@@ -422,7 +446,7 @@ __global__ RF_SHADE_BOUNDS void kShade(DeviceScene scene, SkyStateGpu sky, SunBa
             const uint32_t p = static_cast<uint32_t>(k) * kBlock + threadIdx.x, pNext = p + kBlock; // positions in the tile's sorted order
             ShadeRecord    next{};
             if (k + 1 < kItems && pNext < tileHits) next = fetchRecord(__float_as_uint(hits[k + 1 < kItems ? k + 1 : k].x));
-            needShadow[k] = p < tileHits && shade(k, hits[k].y, hits[k].z, cur, base + p);
+            needShadow[k] = p < tileHits && shade(k, hits[k].y, hits[k].z, 0.0f, cur, base + p);
             cur = next;
         }
     }
@@ -434,8 +458,15 @@ __global__ RF_SHADE_BOUNDS void kShade(DeviceScene scene, SkyStateGpu sky, SunBa
         for (int k = 0; k < kItems; ++k)
         {
             if (!isHit[k]) continue;
-            const Vec3 h = load3(ps.hit + entryIndex(k));
-            const bool need = shade(k, h.y, h.z, fetchRecord(__float_as_uint(h.x)), outPos[k]);
+            Vec3  h;
+            float hitT = 0.0f;
+            if constexpr (AOV)
+            {
+                const float4 rec = ps.hit[entryIndex(k)]; // (the whole record: .w = t of the hit)
+                h = vec3(rec.x, rec.y, rec.z), hitT = rec.w;
+            }
+            else h = load3(ps.hit + entryIndex(k));
+            const bool need = shade(k, h.y, h.z, hitT, fetchRecord(__float_as_uint(h.x)), outPos[k]);
             // (k is a run-time index in this loop: the flag goes in through selects, not through an indexed register array)
 #pragma unroll
             for (int j = 0; j < kItems; ++j) needShadow[j] = j == k ? need : needShadow[j];
@@ -570,6 +601,63 @@ __global__ __launch_bounds__(64) void kAccumulateRuns(FrameParams fp, const uint
 #pragma unroll 8
     for (uint32_t k = 0; k < S; ++k) acc += src[k]; // sample order (wgsl:56-57): one dependent chain of f32 additions per channel
     *out = acc;
+}
+
+// First-hit AOV sums: albedoCoverage[lp] += {albedo.rgb, coverage}, normalDepth[lp] += {normal.xyz, depth} of samples 0..numSamples-1 in sample order (f32, the
+// order of the radiance sum), both compact tile-major like the image.  The per-slot records are kShade<false, true>'s (bounce 1).  Any slot order (kAccumulate's).
+__global__ __launch_bounds__(kBlock) void kAccumulateAov(FrameParams fp, const uint32_t* tileIds, const float4* aov, float4* albedoCoverage, float4* normalDepth)
+{
+    const uint32_t lp = blockIdx.x * kBlock + threadIdx.x;
+    if (lp >= fp.pixelsPadded) return;
+    uint32_t x, y;
+    if (!localPixelToXY(fp, tileIds, lp, x, y)) return;
+    float4 a = albedoCoverage[lp], b = normalDepth[lp];
+    for (uint32_t k = 0; k < fp.numSamples; ++k)
+    {
+        const size_t slot = samplePixelToSlot(fp, fp.sampleInvPerm ? fp.sampleInvPerm[k] : k, lp);
+        const float4 ra = aov[2 * slot], rb = aov[2 * slot + 1];
+        a.x += ra.x, a.y += ra.y, a.z += ra.z, a.w += ra.w;
+        b.x += rb.x, b.y += rb.y, b.z += rb.z, b.w += rb.w;
+    }
+    albedoCoverage[lp] = a;
+    normalDepth[lp] = b;
+}
+
+// The same sums for the pixel-major slot order (slotGroupShift = 0), staged in LDS like kAccumulateRuns: a pixel's samples are one run of numSamples 32-byte records.
+// One 64-lane workgroup takes kAovPixels pixels; per chunk of kAovChunk samples it reads their records (one pixel's chunk = 1 KiB, coalesced when the samples are
+// not permuted) into LDS at the sample's index, then each lane -- one (pixel, channel) -- adds the chunk in sample order onto its running sum.  8.4 KB of LDS per
+// workgroup at any batch depth (round 6: <= ~8 KB keeps twenty workgroups resident per CU, profiles/r06_raygen).
+__global__ __launch_bounds__(64) void kAccumulateAovRuns(FrameParams fp, const uint32_t* tileIds, const float4* aov, float4* albedoCoverage, float4* normalDepth)
+{
+    constexpr uint32_t R = kAovChunk + 1u; // rows padded by one float: the summing lanes walk different banks
+    __shared__ float   sRun[kAovPixels * 8u * R]; // [pixel][channel][sample of the chunk]
+    static_assert(kAovPixels * 8u == 64u && kAovPixels * kAovChunk * 2u % 64u == 0u, "one summing lane per (pixel, channel); whole load rounds");
+    const uint32_t S = fp.numSamples, lane = threadIdx.x, lp0 = blockIdx.x * kAovPixels;
+    const uint32_t px = lane / 8u, c = lane % 8u, lp = lp0 + px;
+    float          acc = 0.0f;
+    if (lp < fp.pixelsPadded) acc = reinterpret_cast<const float*>(c < 4u ? albedoCoverage + lp : normalDepth + lp)[c & 3u];
+    for (uint32_t k0 = 0; k0 < S; k0 += kAovChunk)
+    {
+        const uint32_t n = min(kAovChunk, S - k0);
+        // load round i: pixel i of the workgroup, lane = (sample of the chunk, half of the record)
+        for (uint32_t i = 0; i < kAovPixels; ++i)
+        {
+            const uint32_t kk = lane >> 1, half = lane & 1u, lpi = lp0 + i;
+            if (kk >= n || lpi >= fp.pixelsPadded) continue;
+            const uint32_t k = k0 + kk, p = fp.sampleInvPerm ? fp.sampleInvPerm[k] : k; // sample k sits at position p of the pixel's run
+            const float4   v = aov[2 * (static_cast<size_t>(lpi) * S + p) + half];
+            float*         dst = sRun + (i * 8u + half * 4u) * R + kk;
+            dst[0] = v.x, dst[R] = v.y, dst[2u * R] = v.z, dst[3u * R] = v.w;
+        }
+        __syncthreads();
+        const float* src = sRun + lane * R; // (row lane = pixel px, channel c)
+        for (uint32_t kk = 0; kk < n; ++kk) acc += src[kk]; // sample order: one dependent chain of f32 additions per channel
+        __syncthreads(); // the next chunk overwrites the rows
+    }
+    if (lp >= fp.pixelsPadded) return;
+    uint32_t x, y;
+    if (!localPixelToXY(fp, tileIds, lp, x, y)) return;
+    reinterpret_cast<float*>(c < 4u ? albedoCoverage + lp : normalDepth + lp)[c & 3u] = acc;
 }
 
 // wgsl:59-63,277-285 -> BGRA8Unorm texel
@@ -761,11 +849,12 @@ namespace kern
 {
 SamplePermutationKernel samplePermutationKernel() { return kSamplePermutation; }
 RaygenKernel            raygenKernel(bool f32) { return f32 ? kRaygen<true> : kRaygen<false>; }
-ShadeKernel             shadeKernel(bool sorted) { return sorted ? kShade<true> : kShade<false>; }
+ShadeKernel             shadeKernel(bool sorted, bool aov) { return aov ? kShade<false, true> : sorted ? kShade<true, false> : kShade<false, false>; }
 SkyKernel               skyKernel(bool f32) { return f32 ? kSky<true> : kSky<false>; }
 BounceTotalsKernel      bounceTotalsKernel() { return kBounceTotals; }
 AccumulateKernel        accumulateKernel() { return kAccumulate; }
 AccumulateRunsKernel    accumulateRunsKernel(uint32_t pixels) { return pixels == 1u ? kAccumulateRuns<1> : pixels == 2u ? kAccumulateRuns<2> : kAccumulateRuns<kAccPixels>; }
+AccumulateAovKernel     accumulateAovKernel(bool runs) { return runs ? kAccumulateAovRuns : kAccumulateAov; }
 TonemapKernel           tonemapKernel() { return kTonemap; }
 DeferredLightingKernel  deferredLightingKernel() { return kDeferredLighting; }
 } // namespace kern

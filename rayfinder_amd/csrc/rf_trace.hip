@@ -24,7 +24,7 @@ __global__ __launch_bounds__(kBlock) void kTraceClosest(DeviceScene scene, PathS
         ClosestHit h;
         traverse<false, COUNT>(scene, o, d, kTMax, &sStack[threadIdx.x], h, tc);
         if (tc.abandoned) atomicAdd(&counters->abandonedRays, 1ull);
-        ps.hit[i] = make_float4(__uint_as_float(h.triangle), h.u, h.v, 0.0f); // (kShade rebuilds the offset hit point from it)
+        ps.hit[i] = make_float4(__uint_as_float(h.triangle), h.u, h.v, h.t); // (kShade rebuilds the offset hit point from it; .w: the first-hit depth AOV)
     }
     if (COUNT)
     {
