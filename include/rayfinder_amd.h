@@ -192,6 +192,48 @@ RF_API int rf_renderer_read_tonemapped(rf_renderer* r, uint32_t* dst_bgra8);
 RF_API int rf_renderer_set_aovs(rf_renderer* r, uint32_t flags);
 RF_API int rf_renderer_read_aovs(rf_renderer* r, float* albedo_coverage, float* normal_depth, uint32_t* aov_sample_count);
 
+/* Edge-aware a-trous denoiser (Dammertz et al. 2010, "Edge-avoiding A-Trous wavelet transform for fast global illumination filtering") guided by the
+ * first-hit AOVs.  No reference counterpart.  Inputs: the per-pixel sums of one accumulation -- S (rf_renderer_read_accumulation's layout), AC = {albedo.rgb,
+ * coverage} and ND = {normal.xyz, depth} (rf_renderer_read_aovs) -- and ONE sample count N that both the accumulation and the AOVs have.
+ * All arithmetic is f32, one IEEE operation at a time in the order written (+ - * /, sqrt, compares and selects; no transcendentals): a numpy float32
+ * restatement reproduces the result bit for bit.  Nf = float(N), εa = 2^-8, εℓ = 2^-8.
+ *   prep, per pixel:  c = S.rgb / Nf per channel (kTonemap's division)
+ *                     background: AC.w == 0, or z (below) not > 0 (never from the renderer: a hit's t is > 0).  Output c exactly; never a neighbour.
+ *                     otherwise:  a = AC.rgb / Nf;  m = ND.xyz / Nf;  n = normalize(m) = m * (1 / sqrt(dot(m, m))), (0, 0, 0) where dot(m, m) is 0 or not finite;
+ *                                 z = ND.w / AC.w;  e = c / (a + εa) per channel (demodulated irradiance);  ℓ = (e.r + e.g) + e.b
+ *   iteration i = 0 .. L-1, step s = 2^i, for each non-background pixel p (background pixels keep e):
+ *     the 25 taps q = p + s (dx, dy) in row-major order (dy, then dx, each -2 .. 2), skipping taps outside the frame and background taps (no clamping);
+ *     h = k[dx] k[dy], k = {1/16, 1/4, 3/8, 1/4, 1/16} (exact);  centre tap: w = h = 9/64;  every other tap: w = ((h T(xc)) T(xn)) T(xz) with
+ *       T(x) = x < 1 ? (1 - x)(1 - x) : 0                                     (Tukey's biweight; NaN -> 0)
+ *       d = e_q - e_p;  xc = ((d.r d.r + d.g d.g) + d.b d.b) / (σc²_i (ℓ_p ℓ_p + εℓ)),  σc²_i = (σc σc) 2^-i
+ *       xn = (1 - ((n_p.x n_q.x + n_p.y n_q.y) + n_p.z n_q.z)) / σn
+ *       xz = |z_q - z_p| / ((σz s) z_p)
+ *     in tap order: sumW += w; sumE += w e_q (per channel, both from +0);  e'_p = sumE / sumW;  ℓ'_p = (e'.r + e'.g) + e'.b
+ *   finish: out = e^(L) (a + εa) per channel; background out = c;  L = 0: out = c for every pixel.  The mean is returned as {out.rgb, 1}.
+ * Parameters: 0 <= iterations <= 8, each sigma finite and > 0; defaults L = 5, σc = 1, σn = 0.1, σz = 0.1 (profiles/denoise/README.md: the sweep).
+ *
+ * rf_renderer_denoise: enqueued on the handle's stream over its own sums; params NULL = the defaults.  RF_ERROR_INVALID_ARGUMENT when the AOVs are off,
+ * when the AOV sample count differs from the accumulated count (AOVs turned on partway through), when no sample has been accumulated, or when a tile
+ * shard is set (rf_renderer_gather_frame does not carry the AOVs; use rf_denoise_images on the gathered sums).  Leaves the accumulation, the AOV sums,
+ * rf_renderer_read_tonemapped, the stats and later samples untouched.  The result is a snapshot with its sample count: its device buffers (five float4
+ * and one u32 per pixel) are allocated by the first call and freed with the handle; the snapshot is dropped whenever the AOV sums are cleared
+ * (rf_renderer_set_render_parameters, a change of the AOV flags, a new tile shard, a newly bound accumulation buffer).
+ * rf_renderer_read_denoised: row-major width*height*4 mean floats and / or the BGRA8 texels (kTonemap with accumulatedSamples = 1 and the handle's
+ * exposure) and the snapshot's sample count; any pointer may be NULL.  RF_ERROR_INVALID_ARGUMENT without a snapshot.
+ * rf_denoise_images: the same filter over row-major host sums (width*height*4 floats each, e.g. assembled from several ranks) on device
+ * device_ordinal; out_rgba / out_bgra8 may be NULL.  Synchronous.  A NULL input, a zero size or sample count and bad parameters are refused before any
+ * device call. */
+typedef struct rf_denoise_parameters
+{
+    uint32_t iterations;
+    float    sigma_color, sigma_normal, sigma_depth;
+} rf_denoise_parameters;
+RF_API int rf_denoise_default_parameters(rf_denoise_parameters* out);
+RF_API int rf_renderer_denoise(rf_renderer* r, const rf_denoise_parameters* params);
+RF_API int rf_renderer_read_denoised(rf_renderer* r, float* rgba, uint32_t* bgra8, uint32_t* sample_count);
+RF_API int rf_denoise_images(int32_t device_ordinal, uint32_t width, uint32_t height, uint32_t samples, const float* color_sum4, const float* albedo_coverage4,
+                             const float* normal_depth4, const rf_denoise_parameters* params, float exposure, float* out_rgba, uint32_t* out_bgra8);
+
 /* Deferred-lighting variant (replaces nlrs::DeferredRenderer's lighting + resolve passes, src/pt/deferred_renderer.hpp,
  * deferred_renderer_lighting_pass.wgsl:96-186 -- fixed 2-bounce surfaceColor, solar disk in the sky term, the
  * 1/16384 + 1024 offset constants :498-500 -- and deferred_renderer_resolve_pass.wgsl:33-54 -- 0.1 / 0.9 exponential

@@ -423,6 +423,36 @@ class TileComm:
 
 
 # ------------------------------------------------------------------------------------- renderer
+def denoise_defaults():
+    """-> dict of the denoiser's default parameters (rf_denoise_default_parameters)."""
+    d = _ffi.DenoiseParameters()
+    check(lib.rf_denoise_default_parameters(C.byref(d)))
+    return dict(iterations=d.iterations, sigma_color=d.sigma_color, sigma_normal=d.sigma_normal, sigma_depth=d.sigma_depth)
+
+
+def _denoise_parameters(params):
+    unknown = set(params) - {"iterations", "sigma_color", "sigma_normal", "sigma_depth"}
+    if unknown:
+        raise TypeError(f"unknown denoise parameters: {sorted(unknown)}")
+    p = dict(denoise_defaults(), **params)
+    return _ffi.DenoiseParameters(int(p["iterations"]), float(p["sigma_color"]), float(p["sigma_normal"]), float(p["sigma_depth"]))
+
+
+def denoise_images(color_sum, albedo_coverage, normal_depth, samples, exposure=1.0, device_ordinal=0, **params):
+    """rf_denoise_images: the denoiser over (H,W,4) f32 sums held on the host (accumulation, {albedo, coverage}, {normal, depth}) of `samples` samples.
+    -> (rgb (H,W,3) f32 denoised mean, bgra (H,W) u32 display texels under `exposure`)."""
+    color_sum, albedo_coverage, normal_depth = (_f32(a) for a in (color_sum, albedo_coverage, normal_depth))
+    h, w = color_sum.shape[:2]
+    for a in (color_sum, albedo_coverage, normal_depth):
+        if a.shape != (h, w, 4):
+            raise ValueError("denoise_images: the three sums must be (H, W, 4) arrays of one size")
+    rgba = np.zeros((h, w, 4), np.float32)
+    bgra = np.zeros((h, w), np.uint32)
+    check(lib.rf_denoise_images(device_ordinal, w, h, samples, _ptr(color_sum), _ptr(albedo_coverage), _ptr(normal_depth), C.byref(_denoise_parameters(params)),
+                                exposure, _ptr(rgba), _ptr(bgra)))
+    return rgba[..., :3], bgra
+
+
 class ReferencePathTracer:
     """Host-side mirror of nlrs::ReferencePathTracer (src/pt/reference_path_tracer.hpp:59-76).
 
@@ -493,6 +523,21 @@ class ReferencePathTracer:
         cov = s["coverage"]
         depth = np.divide(s["depth"], cov, out=np.zeros_like(cov), where=cov > 0)
         return dict(albedo=s["albedo"] / n, normal=s["normal"] / n, depth=depth, coverage=cov / n, samples=s["samples"])
+
+    # edge-aware a-trous denoiser (rf_renderer_denoise / rf_renderer_read_denoised; include/rayfinder_amd.h states its arithmetic)
+    def denoise(self, **params):
+        """Denoise the accumulation with the first-hit AOVs as guides (needs the AOVs on from the first sample, no tile shard).  Keyword arguments:
+        iterations, sigma_color, sigma_normal, sigma_depth (the rest: the defaults)."""
+        check(lib.rf_renderer_denoise(self._h, C.byref(_denoise_parameters(params))))
+
+    def read_denoised(self):
+        """-> (rgb (H,W,3) f32 denoised mean, bgra (H,W) u32 display texels, the sample count of the denoised accumulation)"""
+        h, w = self._params.height, self._params.width
+        rgba = np.zeros((h, w, 4), np.float32)
+        bgra = np.zeros((h, w), np.uint32)
+        n = C.c_uint32(0)
+        check(lib.rf_renderer_read_denoised(self._h, _ptr(rgba), _ptr(bgra), C.byref(n)))
+        return rgba[..., :3], bgra, n.value
 
     # deferred-lighting variant (nlrs::DeferredRenderer's lighting + resolve passes over a primary-ray G-buffer)
     def render_deferred(self, num_frames=1):

@@ -39,6 +39,10 @@ RF_ERROR_OUT_OF_RANGE = 4
 RF_AOV_FIRST_HIT = 1
 
 
+class DenoiseParameters(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float)]
+
+
 class Camera(C.Structure):
     _fields_ = [("origin", C.c_float * 3), ("lower_left_corner", C.c_float * 3), ("horizontal", C.c_float * 3),
                 ("vertical", C.c_float * 3), ("up", C.c_float * 3), ("right", C.c_float * 3), ("lens_radius", C.c_float)]
@@ -117,6 +121,11 @@ SIGNATURES = {
     "rf_renderer_read_tonemapped": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rf_renderer_set_aovs": (C.c_int, [C.c_void_p, C.c_uint32]),
     "rf_renderer_read_aovs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
+    "rf_denoise_default_parameters": (C.c_int, [C.c_void_p]),
+    "rf_renderer_denoise": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rf_renderer_read_denoised": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
+    "rf_denoise_images": (C.c_int, [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
+                                    C.c_void_p]),
     "rf_renderer_render_deferred": (C.c_int, [C.c_void_p, C.c_uint32]),
     "rf_renderer_reset_deferred": (C.c_int, [C.c_void_p]),
     "rf_renderer_read_deferred": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),

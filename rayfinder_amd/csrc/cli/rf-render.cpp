@@ -1,12 +1,16 @@
 // rf-render <scene.pt|scene.glb> [--width W] [--height H] [--spp N] [--bounces B] [--vfov deg]
 //           [--zenith deg] [--azimuth deg] [--turbidity t] [--exposure-stops s] [--out image.png]
-//           [--pfm image.pfm] [--aov-albedo a.pfm] [--aov-normal n.pfm] [--aov-depth d.pfm] [--gpus N]
+//           [--pfm image.pfm] [--aov-albedo a.pfm] [--aov-normal n.pfm] [--aov-depth d.pfm] [--denoise d.png] [--denoise-pfm d.pfm]
+//           [--denoise-iterations L] [--denoise-sigma-color s] [--denoise-sigma-normal s] [--denoise-sigma-depth s] [--gpus N]
 // Offline counterpart of the interactive `pt` app (src/pt/main.cpp): same default camera pose,
 // sky and exposure; renders all samples and writes the tonemapped image (and optionally the
 // mean radiance as PFM).  --gpus N: one host thread per GPU, the image tile-sharded across them, one RCCL
 // gather to GPU 0 at frame end (rf_renderer_gather_frame).
 // --aov-*: the means of the first-hit AOVs (rf_renderer_set_aovs): albedo and normal over the samples, depth over the samples that hit
 // something (a one-channel PFM, 0 where none did).  With --gpus N each rank reads its own tiles' AOVs and the host assembles them.
+// --denoise / --denoise-pfm: the edge-aware a-trous denoiser (rf_renderer_denoise) over the frame, guided by the AOVs (any --denoise* option turns them on
+// from the first sample).  With --gpus N > 1 it runs once, on device 0, over the gathered accumulation and the host-assembled AOV sums (rf_denoise_images):
+// the same inputs, the same kernels, the same bytes whatever N.
 #include "cli_common.hpp"
 
 #include <algorithm>
@@ -23,14 +27,20 @@ int main(int argc, char** argv)
                     "                 [--zenith deg] [--azimuth deg] [--turbidity t] [--exposure-stops s] [--out image.png] [--pfm image.pfm]\n"
                     "                 [--aov-albedo a.pfm] [--aov-normal n.pfm] [--aov-depth d.pfm] [--gpus N]\n"
                     "  --aov-albedo / --aov-normal / --aov-depth: mean first-hit albedo, shading normal (3-channel PFM) and depth (1-channel PFM, 0 where\n"
-                    "  no sample hit) -- the auxiliary inputs of a denoiser\n");
+                    "  no sample hit) -- the auxiliary inputs of a denoiser\n"
+                    "                 [--denoise d.png] [--denoise-pfm d.pfm] [--denoise-iterations L] [--denoise-sigma-color s] [--denoise-sigma-normal s]\n"
+                    "                 [--denoise-sigma-depth s]\n"
+                    "  --denoise / --denoise-pfm: the frame through the edge-aware a-trous denoiser guided by the AOVs (defaults: L 5, sigmas 1, 0.1, 0.1)\n");
         return 0;
     }
     uint32_t    W = 1920, H = 1080, spp = 64, bounces = 2; // UI defaults src/pt/main.cpp:46-60
     uint32_t    gpus = 1;
     float       vfov = 70.0f, zenith = 30.0f, azimuth = 0.0f, turbidity = 1.0f;
     int         stops = 2;
-    std::string out = "render.png", pfm, aovAlbedo, aovNormal, aovDepth;
+    std::string out = "render.png", pfm, aovAlbedo, aovNormal, aovDepth, denoisePng, denoisePfm;
+    rf_denoise_parameters denoiseParams{};
+    rf_denoise_default_parameters(&denoiseParams);
+    bool denoising = false;
     for (int i = 2; i + 1 < argc; i += 2)
     {
         const std::string k = argv[i];
@@ -50,6 +60,12 @@ int main(int argc, char** argv)
         else if (k == "--aov-albedo") aovAlbedo = val;
         else if (k == "--aov-normal") aovNormal = val;
         else if (k == "--aov-depth") aovDepth = val;
+        else if (k == "--denoise") denoisePng = val, denoising = true;
+        else if (k == "--denoise-pfm") denoisePfm = val, denoising = true;
+        else if (k == "--denoise-iterations") denoiseParams.iterations = static_cast<uint32_t>(std::atoi(val)), denoising = true;
+        else if (k == "--denoise-sigma-color") denoiseParams.sigma_color = static_cast<float>(std::atof(val)), denoising = true;
+        else if (k == "--denoise-sigma-normal") denoiseParams.sigma_normal = static_cast<float>(std::atof(val)), denoising = true;
+        else if (k == "--denoise-sigma-depth") denoiseParams.sigma_depth = static_cast<float>(std::atof(val)), denoising = true;
         else
         {
             std::fprintf(stderr, "unknown option %s\n", k.c_str());
@@ -78,9 +94,13 @@ int main(int argc, char** argv)
     std::atomic<unsigned long long> closestRays{0}, shadowRays{0};
     std::vector<uint32_t>           bgra(static_cast<size_t>(W) * H);
     std::vector<float>              acc;
-    if (!pfm.empty()) acc.resize(static_cast<size_t>(W) * H * 4);
+    // (the denoiser over several ranks needs the whole accumulation on the host)
+    if (!pfm.empty() || (denoising && gpus > 1)) acc.resize(static_cast<size_t>(W) * H * 4);
     // first-hit AOV sums of the whole frame ({albedo, coverage}, {normal, depth}): every rank copies in the pixels of its own tiles
-    const bool         aovs = !aovAlbedo.empty() || !aovNormal.empty() || !aovDepth.empty();
+    const bool         aovs = !aovAlbedo.empty() || !aovNormal.empty() || !aovDepth.empty() || denoising;
+    std::vector<float>    denoisedRgba;
+    std::vector<uint32_t> denoisedBgra;
+    if (denoising) denoisedRgba.resize(static_cast<size_t>(W) * H * 4), denoisedBgra.resize(static_cast<size_t>(W) * H);
     std::vector<float> aovAc, aovNd;
     uint32_t           aovSamples = 0;
     if (aovs) aovAc.resize(static_cast<size_t>(W) * H * 4), aovNd.resize(static_cast<size_t>(W) * H * 4);
@@ -143,6 +163,11 @@ int main(int argc, char** argv)
                 rfCheck(rf_renderer_read_tonemapped(renderer, bgra.data()), "tonemap");
                 uint32_t n = 0;
                 if (!acc.empty()) rfCheck(rf_renderer_read_accumulation(renderer, acc.data(), &n), "read accumulation");
+                if (denoising)
+                {
+                    rfCheck(rf_renderer_denoise(renderer, &denoiseParams), "denoise");
+                    rfCheck(rf_renderer_read_denoised(renderer, denoisedRgba.data(), denoisedBgra.data(), &n), "read denoised");
+                }
             }
         }
         if (comm) rf_comm_destroy(comm);
@@ -152,6 +177,10 @@ int main(int argc, char** argv)
     for (uint32_t rank = 1; rank < gpus; ++rank) threads.emplace_back(worker, rank);
     worker(0);
     for (std::thread& t : threads) t.join();
+    if (denoising && gpus > 1)
+        rfCheck(rf_denoise_images(0, W, H, aovSamples, acc.data(), aovAc.data(), aovNd.data(), &denoiseParams, desc.render_params.exposure, denoisedRgba.data(),
+                                  denoisedBgra.data()),
+                "denoise");
 
     const double rays = static_cast<double>(closestRays.load() + shadowRays.load());
     std::printf("%ux%u, %u spp, %u bounces on %u GPU(s): %.3f s, %.1f Mrays/s (%llu closest + %llu shadow rays)\n", W, H, spp, bounces, gpus, seconds,
@@ -167,6 +196,19 @@ int main(int argc, char** argv)
     }
     if (!writePngRgba(out, rgba.data(), W, H)) return 1;
     if (!pfm.empty()) writePfm(pfm, acc.data(), W, H, 1.0f / static_cast<float>(std::max(spp, 1u)));
+    if (denoising)
+    {
+        std::vector<uint8_t> d(denoisedBgra.size() * 4);
+        for (size_t i = 0; i < denoisedBgra.size(); ++i)
+        {
+            d[4 * i] = static_cast<uint8_t>(denoisedBgra[i] >> 16);
+            d[4 * i + 1] = static_cast<uint8_t>(denoisedBgra[i] >> 8);
+            d[4 * i + 2] = static_cast<uint8_t>(denoisedBgra[i]);
+            d[4 * i + 3] = 255;
+        }
+        if (!denoisePng.empty() && !writePngRgba(denoisePng, d.data(), W, H)) return 1;
+        if (!denoisePfm.empty() && !writePfm(denoisePfm, denoisedRgba.data(), W, H, 1.0f)) return 1;
+    }
     if (aovs)
     {
         // means (f32 divisions, as ReferencePathTracer.aov_means): albedo / normal over the AOV samples, depth over the coverage

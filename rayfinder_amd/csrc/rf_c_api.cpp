@@ -110,6 +110,18 @@ rf::RenderParameters toParams(const rf_render_parameters& p)
     require(p.num_bounces > 0, "num_bounces must be > 0");
     return out;
 }
+// the denoiser's parameters (NULL: the defaults), checked before anything touches a device
+rf::DenoiseParameters toDenoiseParams(const rf_denoise_parameters* p)
+{
+    rf::DenoiseParameters out;
+    if (!p) return out;
+    require(p->iterations <= 8, "denoise iterations must be 0 .. 8");
+    for (const float s : {p->sigma_color, p->sigma_normal, p->sigma_depth})
+        require(std::isfinite(s) && s > 0.0f, "denoise sigmas must be finite and > 0");
+    out.iterations = p->iterations;
+    out.sigmaColor = p->sigma_color, out.sigmaNormal = p->sigma_normal, out.sigmaDepth = p->sigma_depth;
+    return out;
+}
 } // namespace
 
 extern "C" {
@@ -253,6 +265,50 @@ int rf_renderer_read_aovs(rf_renderer* r, float* albedo_coverage, float* normal_
     return guarded([&] {
         require(r, "null argument");
         r->impl->readAovs(albedo_coverage, normal_depth, aov_sample_count);
+        return RF_OK;
+    });
+}
+
+int rf_denoise_default_parameters(rf_denoise_parameters* out)
+{
+    return guarded([&] {
+        require(out, "null argument");
+        const rf::DenoiseParameters d;
+        *out = rf_denoise_parameters{d.iterations, d.sigmaColor, d.sigmaNormal, d.sigmaDepth};
+        return RF_OK;
+    });
+}
+
+int rf_renderer_denoise(rf_renderer* r, const rf_denoise_parameters* params)
+{
+    return guarded([&] {
+        const rf::DenoiseParameters p = toDenoiseParams(params);
+        require(r, "null argument");
+        r->impl->denoise(p);
+        return RF_OK;
+    });
+}
+
+int rf_renderer_read_denoised(rf_renderer* r, float* rgba, uint32_t* bgra8, uint32_t* sample_count)
+{
+    return guarded([&] {
+        require(r, "null argument");
+        r->impl->readDenoised(rgba, bgra8, sample_count);
+        return RF_OK;
+    });
+}
+
+int rf_denoise_images(int32_t device_ordinal, uint32_t width, uint32_t height, uint32_t samples, const float* color_sum4, const float* albedo_coverage4,
+                      const float* normal_depth4, const rf_denoise_parameters* params, float exposure, float* out_rgba, uint32_t* out_bgra8)
+{
+    return guarded([&] {
+        const rf::DenoiseParameters p = toDenoiseParams(params);
+        require(color_sum4 && albedo_coverage4 && normal_depth4, "null argument");
+        require(width > 0 && height > 0, "image size must be non-zero");
+        require(static_cast<uint64_t>(width) * height < (1ull << 31), "image too large");
+        require(samples > 0, "sample count must be > 0");
+        require(std::isfinite(exposure), "exposure must be finite");
+        rf::denoiseImages(device_ordinal, width, height, samples, color_sum4, albedo_coverage4, normal_depth4, p, exposure, out_rgba, out_bgra8);
         return RF_OK;
     });
 }

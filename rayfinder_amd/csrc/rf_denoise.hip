@@ -1,0 +1,219 @@
+// rf_denoise.hip -- edge-aware a-trous wavelet denoiser (Dammertz et al. 2010) over the accumulation and the first-hit AOVs.  The arithmetic is the one
+// include/rayfinder_amd.h writes out ("Edge-aware a-trous denoiser"), one IEEE f32 operation at a time in that order (-ffp-contract=off, correctly
+// rounded divide and sqrt, no denormal flushing): tests/denoise_restatement.py reproduces it bit for bit.  No atomics: every output is one lane's
+// fixed sequence of operations.
+//   kDenoisePrep    one lane per pixel: demodulated irradiance {e, ℓ}, guide {n, z}, a + εa (or, for L = 0, the mean itself)
+//   kDenoiseAtrous  one lane per pixel, 16x16-pixel workgroups of four 8x8-pixel waves (the 25 taps of a wave touch few cache lines); the last pass
+//                   remodulates and writes the mean
+// The display image is the existing kTonemap over the mean with accumulatedSamples = 1.
+#include "rf_denoise.hpp"
+
+#include "rf_kernels.hpp"
+#include "rf_math.hpp"
+
+namespace rf
+{
+namespace
+{
+constexpr float    kEpsAlbedo = 0.00390625f; // εa = 2^-8
+constexpr float    kEpsLum = 0.00390625f;    // εℓ = 2^-8
+constexpr uint32_t kDenoiseBlock = 256;      // kDenoiseAtrous: 16x16 pixels
+
+// index of pixel (x, y) in a compact tile-major buffer that holds every tile of the frame in tile order (localPixelToXY's layout)
+__device__ __forceinline__ uint32_t tileMajorIndex(uint32_t x, uint32_t y, uint32_t tilesX)
+{
+    const uint32_t tile = (y >> 5) * tilesX + (x >> 5);
+    const uint32_t block = ((y & 31u) >> 3) * 4u + ((x & 31u) >> 3);
+    return tile * 1024u + block * 64u + (y & 7u) * 8u + (x & 7u);
+}
+
+__device__ __forceinline__ float tukey(float x)
+{
+    const float m = 1.0f - x;
+    return x < 1.0f ? m * m : 0.0f; // (NaN: 0)
+}
+
+__global__ __launch_bounds__(256) void kDenoisePrep(const float4* colorSum, const float4* albedoCoverage, const float4* normalDepth, uint32_t width, uint32_t height,
+                                                    uint32_t tilesX, float nf, float4* e, float4* guide, float4* albedo, float4* meanOut)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= width * height) return;
+    const uint32_t y = i / width, x = i - y * width;
+    const uint32_t src = tilesX ? tileMajorIndex(x, y, tilesX) : i;
+    const float4   S = colorSum[src];
+    const Vec3     c = vec3(S.x / nf, S.y / nf, S.z / nf); // (kTonemap's division)
+    if (meanOut) // L = 0: the mean, exactly
+    {
+        meanOut[i] = make_float4(c.x, c.y, c.z, 1.0f);
+        return;
+    }
+    const float4 AC = albedoCoverage[src], ND = normalDepth[src];
+    const float  z = ND.w / AC.w;
+    if (AC.w == 0.0f || !(z > 0.0f)) // background: passes through, never a neighbour
+    {
+        e[i] = make_float4(c.x, c.y, c.z, 0.0f);
+        guide[i] = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+        albedo[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        return;
+    }
+    const Vec3  a = vec3(AC.x / nf, AC.y / nf, AC.z / nf);
+    const Vec3  m = vec3(ND.x / nf, ND.y / nf, ND.z / nf);
+    const float d = dot(m, m);
+    const Vec3  n = (d != 0.0f && fabsf(d) <= FLT_MAX) ? normalize(m) : splat(0.0f);
+    const Vec3  ae = a + splat(kEpsAlbedo);
+    const Vec3  ev = vec3(c.x / ae.x, c.y / ae.y, c.z / ae.z);
+    e[i] = make_float4(ev.x, ev.y, ev.z, (ev.x + ev.y) + ev.z);
+    guide[i] = make_float4(n.x, n.y, n.z, z);
+    albedo[i] = make_float4(ae.x, ae.y, ae.z, 0.0f);
+}
+
+// One pass of step `step` = 2^i: sc2 = (σc σc) 2^-i, szs = σz step.  last: out = the mean {e' (a + εa), 1} (background: {c, 1}); else out = {e', ℓ'}.
+__global__ __launch_bounds__(kDenoiseBlock) void kDenoiseAtrous(const float4* eIn, const float4* guide, const float4* albedo, float4* out, uint32_t width, uint32_t height,
+                                                               int step, float sc2, float sigmaN, float szs, uint32_t last)
+{
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t x = blockIdx.x * 16u + (wave & 1u) * 8u + (lane & 7u);
+    const uint32_t y = blockIdx.y * 16u + (wave >> 1) * 8u + (lane >> 3);
+    if (x >= width || y >= height) return;
+    const uint32_t p = y * width + x;
+    const float4   ep = eIn[p];
+    const float4   gp = guide[p];
+    if (!(gp.w > 0.0f))
+    {
+        out[p] = last ? make_float4(ep.x, ep.y, ep.z, 1.0f) : ep;
+        return;
+    }
+    constexpr float k[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
+    const float     denC = sc2 * (ep.w * ep.w + kEpsLum);
+    const float     denZ = szs * gp.w;
+    float           sumW = 0.0f, sx = 0.0f, sy = 0.0f, sz = 0.0f;
+#pragma unroll
+    for (int dy = -2; dy <= 2; ++dy)
+    {
+        const int qy = static_cast<int>(y) + step * dy;
+        if (qy < 0 || qy >= static_cast<int>(height)) continue; // (a row outside the frame: all five taps skipped)
+#pragma unroll
+        for (int dx = -2; dx <= 2; ++dx)
+        {
+            const int   qx = static_cast<int>(x) + step * dx;
+            const float h = k[dx + 2] * k[dy + 2];
+            float       w;
+            float4      eq;
+            if (dx == 0 && dy == 0)
+            {
+                w = h;
+                eq = ep;
+            }
+            else
+            {
+                if (qx < 0 || qx >= static_cast<int>(width)) continue;
+                const uint32_t q = static_cast<uint32_t>(qy) * width + static_cast<uint32_t>(qx);
+                const float4   gq = guide[q];
+                if (!(gq.w > 0.0f)) continue;
+                eq = eIn[q];
+                const float dr = eq.x - ep.x, dg = eq.y - ep.y, db = eq.z - ep.z;
+                const float xc = ((dr * dr + dg * dg) + db * db) / denC;
+                const float xn = (1.0f - ((gp.x * gq.x + gp.y * gq.y) + gp.z * gq.z)) / sigmaN;
+                const float xz = fabsf(gq.w - gp.w) / denZ;
+                w = ((h * tukey(xc)) * tukey(xn)) * tukey(xz);
+            }
+            sumW += w;
+            sx += w * eq.x;
+            sy += w * eq.y;
+            sz += w * eq.z;
+        }
+    }
+    const float ex = sx / sumW, ey = sy / sumW, ez = sz / sumW;
+    if (last)
+    {
+        const float4 ae = albedo[p];
+        out[p] = make_float4(ex * ae.x, ey * ae.y, ez * ae.z, 1.0f);
+    }
+    else
+        out[p] = make_float4(ex, ey, ez, (ex + ey) + ez);
+}
+} // namespace
+
+void DenoiseWork::reserve(uint64_t n, hipStream_t stream)
+{
+    if (n <= pixels) return;
+    RF_HIP(hipStreamSynchronize(stream)); // (a smaller set may still be in use by the last run)
+    release();
+    float4** f4[] = {&e[0], &e[1], &guide, &albedo, &out};
+    for (float4** b : f4) RF_HIP(hipMalloc(reinterpret_cast<void**>(b), n * sizeof(float4)));
+    RF_HIP(hipMalloc(reinterpret_cast<void**>(&bgra), n * sizeof(uint32_t)));
+    pixels = n;
+}
+
+void DenoiseWork::release()
+{
+    for (void* b : {static_cast<void*>(e[0]), static_cast<void*>(e[1]), static_cast<void*>(guide), static_cast<void*>(albedo), static_cast<void*>(out), static_cast<void*>(bgra)})
+        if (b) (void)hipFree(b);
+    e[0] = e[1] = guide = albedo = out = nullptr;
+    bgra = nullptr;
+    pixels = 0;
+}
+
+void enqueueDenoise(hipStream_t stream, DenoiseWork& w, const float4* colorSum, const float4* albedoCoverage, const float4* normalDepth, uint32_t width,
+                    uint32_t height, uint32_t tilesX, uint32_t samples, const DenoiseParameters& p, float exposure)
+{
+    const uint32_t n = width * height;
+    w.reserve(n, stream);
+    const float nf = static_cast<float>(samples);
+    const dim3  prepGrid((n + 255) / 256);
+    if (p.iterations == 0)
+        hipLaunchKernelGGL(kDenoisePrep, prepGrid, dim3(256), 0, stream, colorSum, albedoCoverage, normalDepth, width, height, tilesX, nf, static_cast<float4*>(nullptr),
+                           static_cast<float4*>(nullptr), static_cast<float4*>(nullptr), w.out);
+    else
+    {
+        hipLaunchKernelGGL(kDenoisePrep, prepGrid, dim3(256), 0, stream, colorSum, albedoCoverage, normalDepth, width, height, tilesX, nf, w.e[0], w.guide, w.albedo,
+                           static_cast<float4*>(nullptr));
+        const dim3 grid((width + 15) / 16, (height + 15) / 16);
+        for (uint32_t i = 0; i < p.iterations; ++i)
+        {
+            const bool  last = i + 1 == p.iterations;
+            const float sc2 = (p.sigmaColor * p.sigmaColor) * std::ldexp(1.0f, -static_cast<int>(i)); // (exact: a power of two)
+            const float szs = p.sigmaDepth * static_cast<float>(1u << i);
+            hipLaunchKernelGGL(kDenoiseAtrous, grid, dim3(kDenoiseBlock), 0, stream, w.e[i & 1u], w.guide, w.albedo, last ? w.out : w.e[(i + 1) & 1u], width, height,
+                               static_cast<int>(1u << i), sc2, p.sigmaNormal, szs, last ? 1u : 0u);
+        }
+    }
+    hipLaunchKernelGGL(tonemapKernel(), dim3((n + 255) / 256), dim3(256), 0, stream, static_cast<const float4*>(w.out), n, 1u, exposure, w.bgra);
+    RF_HIP(hipGetLastError());
+}
+
+void denoiseImages(int deviceOrdinal, uint32_t width, uint32_t height, uint32_t samples, const float* colorSum, const float* albedoCoverage, const float* normalDepth,
+                   const DenoiseParameters& params, float exposure, float* outRgba, uint32_t* outBgra8)
+{
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) throw std::runtime_error("rayfinder_amd: no HIP device available (this library has no CPU fallback)");
+    if (deviceOrdinal < 0 || deviceOrdinal >= count) throw std::invalid_argument("device ordinal out of range");
+    RF_HIP(hipSetDevice(deviceOrdinal));
+    const uint64_t n = static_cast<uint64_t>(width) * height;
+    struct Scope
+    {
+        hipStream_t stream = nullptr;
+        float4*     in[3] = {};
+        DenoiseWork work;
+        ~Scope()
+        {
+            if (stream) (void)hipStreamSynchronize(stream);
+            for (float4* b : in)
+                if (b) (void)hipFree(b);
+            work.release();
+            if (stream) (void)hipStreamDestroy(stream);
+        }
+    } s;
+    RF_HIP(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
+    const float* src[3] = {colorSum, albedoCoverage, normalDepth};
+    for (int b = 0; b < 3; ++b)
+    {
+        RF_HIP(hipMalloc(reinterpret_cast<void**>(&s.in[b]), n * sizeof(float4)));
+        RF_HIP(hipMemcpyAsync(s.in[b], src[b], n * sizeof(float4), hipMemcpyHostToDevice, s.stream));
+    }
+    enqueueDenoise(s.stream, s.work, s.in[0], s.in[1], s.in[2], width, height, 0u, samples, params, exposure);
+    if (outRgba) RF_HIP(hipMemcpyAsync(outRgba, s.work.out, n * sizeof(float4), hipMemcpyDeviceToHost, s.stream));
+    if (outBgra8) RF_HIP(hipMemcpyAsync(outBgra8, s.work.bgra, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream));
+    RF_HIP(hipStreamSynchronize(s.stream));
+}
+} // namespace rf

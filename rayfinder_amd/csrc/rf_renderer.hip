@@ -21,6 +21,7 @@
 //
 // Kernel grids are sized for the worst case (all paths alive) and read the live count from
 // device memory, so a whole batch is enqueued without any host round trip.
+#include "rf_denoise.hpp"
 #include "rf_kernels.hpp"
 
 #include <map>
@@ -168,6 +169,10 @@ struct Renderer::Impl
     uint32_t                aovFlags = 0, aovSamples = 0;
     bool                    aovDirty = true;
     DeviceBuffer<float4>    aovAlbedoCoverage, aovNormalDepth;
+    // the denoiser (rf_renderer_denoise): its work buffers, allocated by the first denoise, and the snapshot they hold -- valid until the AOV sums are cleared
+    DenoiseWork             denoiseWork;
+    bool                    denoisedValid = false;
+    uint32_t                denoisedSamples = 0;
 
     uint64_t                validPixels = 0;     // pixels of this rank's tiles that lie inside the frame
     unsigned long long      primaryRaysHost = 0; // samples traced x validPixels since the last resetStats()
@@ -386,6 +391,7 @@ struct Renderer::Impl
     {
         aovSamples = 0;
         aovDirty = true;
+        denoisedValid = false;
     }
 
     template<typename F>
@@ -1391,6 +1397,34 @@ void Renderer::readAovs(float* albedoCoverage, float* normalDepth, uint32_t* sam
     read(m.aovAlbedoCoverage, albedoCoverage);
     read(m.aovNormalDepth, normalDepth);
     if (sampleCount) *sampleCount = empty ? 0u : m.aovSamples;
+}
+
+void Renderer::denoise(const DenoiseParameters& params)
+{
+    Impl& m = *mImpl;
+    if (m.aovFlags == 0u) throw std::invalid_argument("denoise needs the first-hit AOVs: turn them on (rf_renderer_set_aovs) before the first sample");
+    if (m.worldSize != 1u) throw std::invalid_argument("denoise needs the whole frame: a tile shard is set (use rf_denoise_images on the gathered sums)");
+    if (m.accumulated == 0u || m.imageDirty) throw std::invalid_argument("denoise: no sample has been accumulated");
+    if (m.aovDirty || m.aovSamples != m.accumulated)
+        throw std::invalid_argument("denoise: the AOV sample count (" + std::to_string(m.aovSamples) + ") differs from the accumulated sample count (" +
+                                    std::to_string(m.accumulated) + "): turn the AOVs on before the first sample");
+    RF_HIP(hipSetDevice(m.device));
+    const uint32_t tilesX = (m.params.width + kTileSize - 1) / kTileSize;
+    enqueueDenoise(m.stream, m.denoiseWork, m.image, m.aovAlbedoCoverage.ptr, m.aovNormalDepth.ptr, m.params.width, m.params.height, tilesX, m.accumulated, params,
+                   m.params.exposure);
+    m.denoisedValid = true;
+    m.denoisedSamples = m.accumulated;
+}
+
+void Renderer::readDenoised(float* rgba, uint32_t* bgra8, uint32_t* sampleCount)
+{
+    Impl& m = *mImpl;
+    if (!m.denoisedValid) throw std::invalid_argument("no denoised image: call rf_renderer_denoise first (the image is dropped when the accumulation or the AOVs are cleared)");
+    synchronize();
+    const size_t n = static_cast<size_t>(m.params.width) * m.params.height;
+    if (rgba) RF_HIP(hipMemcpy(rgba, m.denoiseWork.out, n * sizeof(float4), hipMemcpyDeviceToHost));
+    if (bgra8) RF_HIP(hipMemcpy(bgra8, m.denoiseWork.bgra, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (sampleCount) *sampleCount = m.denoisedSamples;
 }
 
 void*    Renderer::accumulationDevicePointer() const { return mImpl->image; }

@@ -100,6 +100,17 @@ std::vector<uint32_t> tilesForRank(uint32_t width, uint32_t height, uint32_t ran
 // compact tile-major float4 buffer -> row-major width*height*4 image (pixels of other ranks' tiles untouched)
 void untileHost(const float* compact, const uint32_t* tileIds, uint32_t numTiles, uint32_t width, uint32_t height, float* image);
 
+// Edge-aware a-trous denoiser (rf_denoise.hip): iterations 0..8, every sigma finite and > 0 (the C ABI checks them before any device call)
+struct DenoiseParameters
+{
+    uint32_t iterations = 5;
+    float    sigmaColor = 1.0f, sigmaNormal = 0.1f, sigmaDepth = 0.1f;
+};
+// The denoiser over host-assembled row-major width*height*4 sums ({color, -}, {albedo, coverage}, {normal, depth}) of `samples` samples, on device
+// `deviceOrdinal`: the mean RGBA (.w = 1) and / or its BGRA8 under `exposure` (NULL = skip).  Synchronous; allocates and frees its own device memory.
+void denoiseImages(int deviceOrdinal, uint32_t width, uint32_t height, uint32_t samples, const float* colorSum, const float* albedoCoverage, const float* normalDepth,
+                   const DenoiseParameters& params, float exposure, float* outRgba, uint32_t* outBgra8);
+
 class Renderer
 {
 public:
@@ -135,6 +146,12 @@ public:
     void     setAovs(uint32_t flags);
     uint32_t aovFlags() const;
     void     readAovs(float* albedoCoverage, float* normalDepth, uint32_t* sampleCount);
+    // Edge-aware a-trous denoiser over the accumulation and the first-hit AOVs (rf_renderer_denoise; the arithmetic: include/rayfinder_amd.h).  denoise enqueues on the
+    // handle's stream and keeps a snapshot (allocated on the first call); it throws std::invalid_argument when the AOVs are off, their count differs from the
+    // accumulated count, nothing is accumulated or a tile shard is set.  readDenoised: row-major width*height*4 mean floats and / or BGRA8 (NULL = skip) and the
+    // snapshot's sample count; std::invalid_argument without a snapshot (none yet, or cleared with the AOV sums).
+    void denoise(const DenoiseParameters& params);
+    void readDenoised(float* rgba, uint32_t* bgra8, uint32_t* sampleCount);
     // Device pointer of the compact tile-major accumulation buffer (numTiles*1024 float4) and a
     // way to render into caller-owned device memory (e.g. a torch tensor used for the RCCL gather).
     void*    accumulationDevicePointer() const;
