@@ -1846,7 +1846,13 @@ uint32_t checkWideLayouts(std::span<const BvhNode> nodes, float* quadHalfAreaRat
         if (wb.quadHalf.size() * 2 != wb.quad.size()) throw std::runtime_error("wide layout mismatch: half-precision quad records do not pair up with the quad records");
         double R = 0.0;
         for (const float c : {wb.rootLo.x, wb.rootLo.y, wb.rootLo.z, wb.rootHi.x, wb.rootHi.y, wb.rootHi.z}) R = std::max(R, static_cast<double>(std::fabs(c)));
-        const double margin = 1.1920928955078125e-07 * (4.0 * static_cast<double>(wb.originBound) + 3.0 * R) * 1.0001; // what the proof needs (the builder leaves twice that)
+        // What the proof needs (rf_wide.hpp): margin >= u (4 originBound + 3 R + margin) with u = 2^-24, the unit roundoff of the f32 operations it counts.  `built` is
+        // the margin buildWide adds before its directed roundings, the largest a plane can be displaced by, and stands for the `+ margin` term.  The builder's
+        // 2^-21 (originBound + R) = u (40 R + 8) is more than twice u (19 R + 4 + margin) at EVERY R.  (Until the scale sweep this line had 2^-23 for u: a requirement of
+        // 2^-21 (4.75 R + 1) * 1.0001, which for R < 4e-4 is MORE than the builder's 2^-21 (5 R + 1) -- a plane that the directed rounding leaves exactly on the
+        // builder's target, such as an upper plane rounded to binary16 zero, then failed a check that the proof does not ask for.  The builder was right.)
+        const double built = (static_cast<double>(wb.originBound) + R) * 4.76837158203125e-07;
+        const double margin = 5.9604644775390625e-08 * (4.0 * static_cast<double>(wb.originBound) + 3.0 * R + built) * 1.0001;
         if (!(static_cast<double>(wb.originBound) >= 4.0 * R)) throw std::runtime_error("wide layout mismatch: origin bound of the half-precision quad records");
         for (size_t r = 0; r < wb.quadHalf.size() / 4; ++r)
         {
@@ -1897,6 +1903,7 @@ uint32_t checkWideLayouts(std::span<const BvhNode> nodes, float* quadHalfAreaRat
                 int          ex = 0;
                 const double m = std::frexp(static_cast<double>(scale[ax]), &ex);
                 if (!(m == 0.5) || !std::isfinite(anchor[ax])) fail(r, "local-grid quad record: scale is not a power of two, or the anchor is not finite");
+                // (u = 2^-24 as in the proof; the builder's 2^-18 (originBound + R) = u (320 R + 64) against u (46 R + 6) here: 6.9 x at R >> 1, 10.6 x at R << 1)
                 const double margin = 5.9604644775390625e-08 * (6.03 * (static_cast<double>(wb.originBound) + R) + 1024.0 * static_cast<double>(scale[ax])) * 1.0001;
                 for (int e = 0; e < 4; ++e)
                 {
@@ -2042,7 +2049,9 @@ uint32_t checkWideLayouts(std::span<const BvhNode> nodes, float* quadHalfAreaRat
         // must put the slots into the order in which the reference's walk (wgsl:409-417 at each of the three levels) reaches them.
         double R = 0.0;
         for (const float c : {wb.rootLo.x, wb.rootLo.y, wb.rootLo.z, wb.rootHi.x, wb.rootHi.y, wb.rootHi.z}) R = std::max(R, static_cast<double>(std::fabs(c)));
-        const double margin = (static_cast<double>(wb.originBound) + R) * 3.814697265625e-06 * 0.999; // 2^-18 (a hair less: the builder's own rounding)
+        // 2^-18 (originBound + R), the margin the builder ADDS (a hair less: its floor / ceil run in double) -- 6.9 x what the proof of the local-grid records needs at
+        // any R (see the local-grid check above), so this asks for more than the proof; it holds because the decoded planes anchor + byte * scale are exact in double
+        const double margin = (static_cast<double>(wb.originBound) + R) * 3.814697265625e-06 * 0.999;
         const size_t numOct = wb.oct.size() / 8;
         struct Item
         {

@@ -131,7 +131,8 @@ struct WideBuild
     // instruction) where the reference evaluates t = ((plane - o) * 1/d) with two roundings.  With u = 2^-24, |o| <= originBound and
     // |plane| <= R (the root box):  t' <= T' + u |o / d| + u |t'|  and  t >= T - 2u |T|  for the real values T' = (plane' - o) / d,
     // T = (plane - o) / d, so  margin >= u (4 originBound + 3 R + margin)  makes every near t' <= its t and every far t' >= its t
-    // (margin = 2^-21 (originBound + R): twice that).  NaNs (an axis-parallel ray: inf - inf) drop out of v_min / v_max, i.e. that
+    // (margin = 2^-21 (originBound + R) = u (40 R + 8) against u (19 R + 4 + margin): more than twice that at every R, for R << 1 as for R >> 1; checkWideLayouts
+    // asks for exactly this inequality, with u = 2^-24).  NaNs (an axis-parallel ray: inf - inf) drop out of v_min / v_max, i.e. that
     // axis does not constrain: conservative as well.  So a quad-half step accepts a SUPERSET of what the exact step accepts --
     // which is all an interior test has to do, because every LEAF is then tested against its EXACT box (kept in the spare floats
     // of the leaf's first 64-byte triangle record: leafBoxesIntoTriangles) with the reference's formula, a leaf's exact slab

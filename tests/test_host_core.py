@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import rayfinder_amd as rf
+import scale_scenes as ss
 from conftest import DUCK, GOLDEN, ROOT, bits
 from oracle import gltf_ref, orc
 
@@ -925,3 +926,92 @@ def test_clutter_atrium_is_the_harder_stand_in_and_leaves_the_plain_one_alone():
     facing = (geo * (N[:, 0:3] + N[:, 3:6] + N[:, 6:9])).sum(axis=1)
     assert (facing[-200000:] > 0).mean() > 0.995               # the props (the last ~214 k triangles): geometric and shading normals on the same side
     assert scenes.atrium(1)[1]["digest"] == "206d06350b4893c2" and scenes.atrium(1)[1]["triangles"] == 265024
+
+
+# ------------------------------------------------------------------ the scale / placement sweep (tests/scale_scenes.py), host side
+def _seed_soup_nodes(seed, scale):
+    rng = np.random.default_rng(seed); n = 600
+    tris = ((rng.uniform(-3, 3, (n, 1, 3)) + rng.normal(0, 0.25, (n, 3, 3))) * scale).astype(np.float32)
+    return rf.build_bvh(tris.reshape(n, 9))[0]
+
+
+def test_half_precision_margin_check_at_micro_scale_seed_7():
+    """The regression by name.  For R << 1 the builder leaves 2^-21 (1 + 5 R); the checker used to demand 2^-23 (4 originBound + 3 R) * 1.0001 =
+    2^-21 (1 + 4.75 R) * 1.0001 -- twice what the proof in rf_wide.hpp needs (its u is 2^-24), and MORE than the builder's margin once R < 4e-4: record 106 of
+    this tree has an upper plane that the directed rounding leaves exactly on the builder's target (binary16 zero), and the check threw."""
+    assert rf.check_wide_layouts(_seed_soup_nodes(7, 1e-6)) == {"regular": True, "compact": True, "hot": True, "quad": True, "quad_half": True, "quad_local": True, "oct": True}
+
+
+@pytest.mark.parametrize("scale", [1e-7, 1e-6, 1e-5, 1e-4])
+def test_wide_layout_margins_over_twenty_seeds_at_small_scales(scale):
+    for seed in range(20):
+        st = rf.wide_layout_stats(_seed_soup_nodes(seed, scale))     # (throws where a plane does not keep the margin of the proof)
+        assert st["flags"] & 0x78 == 0x78, (seed, scale, st)
+
+
+def _scale_row_scene(name):
+    pt = ss.soup_pt(ss.triangles(name))
+    return pt, pt.arrays()
+
+
+@pytest.mark.parametrize("name", ss.ROW_NAMES + [r[0] for r in ss.CHECKER_ONLY_ROWS])
+def test_wide_layout_checks_over_the_scale_table(name):
+    """check_wide_layouts / wide_layout_stats must not throw on any row; the half-precision records (flag 16) exist exactly when the padded root box fits
+    binary16; the exact quad, local-grid and oct records (8, 32, 64) exist for every finite scene with an interior node -- they have no range limit."""
+    _, a = _scale_row_scene(name)
+    nodes = a["bvhNodes"]
+    assert len(nodes) > 100
+    st = rf.wide_layout_stats(nodes)
+    got = rf.check_wide_layouts(nodes)
+    print(name, "nodes", len(nodes), "flags", st["flags"], "area ratio", st["quad_half_area_ratio"])
+    assert got["regular"] and got["quad"] and got["quad_local"] and got["oct"], got
+    assert got["quad_half"] is ss.root_fits_binary16(nodes), (got, ss.origin_bound(nodes))
+    assert bool(st["flags"] & 16) is got["quad_half"]
+    if got["quad_half"]:
+        assert st["quad_half_area_ratio"] >= 1.0
+    s, t = ss.row(name)[1], ss.row(name)[2]
+    if np.ndim(s) == 0 and not np.any(t):                       # centred rows: the table's own statement of which side of 65504 they are on
+        assert got["quad_half"] is (float(s) <= 65000.0 / float(np.abs(ss.base_soup()).max())), name
+
+
+@pytest.mark.parametrize("name", ss.ROW_NAMES)
+def test_host_query_over_the_scale_table(name):
+    """The product's CPU query against the oracle on the scaled scenes and the sweep's ray set, every output bit -- and the condition the device sweep
+    depends on, checked where no device is needed: the oracle's own closest-hit fraction on the main rays lies in (0.05, 0.95), so no row passes vacuously."""
+    from oracle import orc
+    _, a = _scale_row_scene(name)
+    nodes, tris = a["bvhNodes"], a["trianglePositionAttributes"]
+    rays, n_main = ss.scene_rays(nodes)
+    unit = ss.row(name)[3]
+    for tmax in (np.float32(10000.0 * unit), np.float32(1.5 * unit), np.float32(ss.FLT_MAX)):
+        with np.errstate(all="ignore"):
+            out = rf.intersect_bvh_batch(rays, nodes, tris, tmax, threads=2)
+            ref = orc.intersect_bvh_batch(nodes, tris, rays, tmax)
+        assert np.array_equal(out["hit"], ref["hit"]) and np.array_equal(out["nodesVisited"], ref["nodesVisited"])
+        assert np.array_equal(out["triTests"], ref["triTests"]) and np.array_equal(out["stackHigh"], ref["stackHigh"])
+        h = out["hit"] == 1
+        assert np.array_equal(out["tri"][h], ref["tri"][h]) and np.array_equal(bits(out["t"][h]), bits(ref["t"][h]))
+        assert np.array_equal(bits(out["p"][h]), bits(ref["p"][h])) and np.array_equal(bits(out["uv"][h]), bits(ref["uv"][h]))
+        frac = float(ref["hit"][:n_main].mean())
+        print(name, "tmax", float(tmax), "oracle hit fraction, main rays", round(frac, 4), "all rays", round(float(ref["hit"].mean()), 4))
+        if tmax == np.float32(ss.FLT_MAX):
+            assert 0.05 < frac < 0.95, (name, frac)
+
+
+@pytest.mark.parametrize("name", ss.ROW_NAMES)
+def test_scale_table_cameras_see_hits_and_misses(name):
+    """Both cameras of every row: the oracle's primary rays (pixel centres) hit the scene in some pixels and miss it in others, and the cameras stand on the
+    sides of the origin bound the device sweep says they do."""
+    from oracle import orc
+    _, a = _scale_row_scene(name)
+    nodes, tris = a["bvhNodes"], a["trianglePositionAttributes"]
+    W, H = ss.FRAME
+    cams = ss.cameras(nodes, W, H)
+    assert [inside for _, _, inside in cams] == [True, False]
+    for label, cam, _ in cams:
+        c19 = rf.camera_to_array(cam)
+        rays = np.array([orc.generate_camera_ray(c19, (x + 0.5) / W, (y + 0.5) / H) for y in range(H) for x in range(W)], np.float32).reshape(-1, 6)
+        with np.errstate(all="ignore"):
+            hit = orc.intersect_bvh_batch(nodes, tris, rays, ss.FLT_MAX)["hit"]
+        print(name, label, "primary hit fraction", round(float(hit.mean()), 4))
+        assert 0 < hit.sum() < hit.size, (name, label)
