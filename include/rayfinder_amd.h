@@ -234,6 +234,59 @@ RF_API int rf_renderer_read_denoised(rf_renderer* r, float* rgba, uint32_t* bgra
 RF_API int rf_denoise_images(int32_t device_ordinal, uint32_t width, uint32_t height, uint32_t samples, const float* color_sum4, const float* albedo_coverage4,
                              const float* normal_depth4, const rf_denoise_parameters* params, float exposure, float* out_rgba, uint32_t* out_bgra8);
 
+/* Radiance second moments and the noise estimate: how noisy the accumulation still is, per pixel, per 32x32 tile and for the frame, and a render call that stops
+ * at a noise target.  No reference counterpart (the reference counts samples: renderProgressPercentage).
+ *
+ * rf_renderer_set_moments: 0 (the default: nothing is allocated or launched, image / stats / timings exactly as without) or 1.  While on, the handle keeps one more
+ * per-pixel f32 buffer next to the accumulation, Q = {sum r.x r.x, sum r.y r.y, sum r.z r.z, 0}, where r is the radiance the accumulation adds for that sample
+ * (wgsl:55-57), each square is one f32 multiply, and the squares are added in f32 in sample-index order, one dependent chain per channel -- the order of the radiance
+ * sum: bit-reproducible whatever the batching, slot order or number of ranks.  16 bytes per pixel of device memory and nothing per path slot
+ * (rf_renderer_memory_info's figures do not change).  The moments keep their own sample count -- the samples traced while they were on -- and are cleared, with the
+ * count set to 0, when the image is (a change through rf_renderer_set_render_parameters, a new tile shard, a newly bound accumulation buffer) and when the switch
+ * changes.  Turned on partway through an accumulation, they cover only the later samples: the count stays below the accumulated sample count.
+ * rf_renderer_read_moments: row-major width*height*4 floats (the layout of rf_renderer_read_accumulation; may be NULL) and the moment sample count.  With a tile
+ * shard set, this rank's pixels and zeros elsewhere: the sum of the ranks' reads is the whole frame.  (rf_renderer_gather_frame does not carry the moments.)
+ *
+ * The estimate.  Inputs: the per-pixel sums S (the accumulation) and Q of one accumulation and ONE sample count N >= 2 that both have.  All arithmetic is f32, one
+ * IEEE operation at a time in the order written (+ - * /, sqrt, compares and selects): a numpy float32 restatement reproduces every output bit for bit.
+ * Nf = float(N).
+ *   per pixel, per channel c:  mu = S_c / Nf;  v = (Q_c - S_c mu) / (Nf - 1);  v = (v > 0) ? v : 0  (NaN -> 0)
+ *   per pixel:                 s2 = ((v_r + v_g) + v_b) / Nf;  l = (mu_r + mu_g) + mu_b;  e = sqrt(s2) / (l + 2^-8)
+ *                              -- the standard error of the pixel's mean relative to its level.  Where e <= FLT_MAX is false (NaN, +inf) the pixel is counted as
+ *                              non-finite and its e is 0.
+ *   per 32x32 tile of the renderer's tile grid (tile t = tile_y * ceil(width / 32) + tile_x):  a[i] = e of the pixel at tile-local (tx, ty), i = ty 32 + tx, and 0 for
+ *                              pixels outside the frame (not counted);  for h = 512, 256, ..., 1:  a[i] = a[i] + a[i + h] for every i < h;  tile_sum = a[0];
+ *                              tile_max = the maximum of e over the tile's in-frame pixels (a maximum of -0 is returned as +0);  tile_pixels, tile_nonfinite: counts.
+ *   frame, on the host:        mean_error = (sum over t of double(tile_sum[t]), t ascending, in f64) / pixels;  max_error = the maximum of tile_max[t], worst_tile the
+ *                              first tile that attains it;  pixels, nonfinite_pixels: the counts' totals.
+ *
+ * rf_renderer_noise_estimate: over the handle's own sums; enqueued on the handle's stream and then waited for.  error_map (row-major width*height floats), tile_sum
+ * and tile_max (ceil(width / 32) * ceil(height / 32) floats each) may be NULL.  RF_ERROR_INVALID_ARGUMENT when the moments are off, when the moment sample count
+ * differs from the accumulated count (moments turned on partway through), when fewer than 2 samples are accumulated, or when a tile shard is set (use
+ * rf_noise_estimate_images on the sum of the ranks' reads).  Leaves the accumulation, the AOV sums, the denoise snapshot, the stats and later samples untouched; its
+ * device buffers (a few words per tile, one float per pixel once a map was asked for) are allocated by the first call and freed with the moments.
+ * rf_noise_estimate_images: the same kernel over row-major host sums (width*height*4 floats each, e.g. assembled from several ranks) on device device_ordinal.
+ * Synchronous.  A NULL input or `out`, a zero size and samples < 2 are refused before any device call.
+ * rf_renderer_render_until: rf_renderer_render in steps -- render min(check_every, frames left) frames, estimate (once 2 samples are accumulated), repeat -- until
+ * mean_error <= target_mean_error, max_frames frames have been rendered or the accumulation holds num_samples_per_pixel samples (frames past that are not rendered).
+ * The image it leaves is the image rf_renderer_render(*frames_rendered) leaves.  *last (may be NULL): the last estimate made; samples = 0 when none was (fewer than 2
+ * samples).  RF_ERROR_INVALID_ARGUMENT when the moments are off or do not cover the whole accumulation, a tile shard is set, or check_every is 0.  Waits for the work
+ * it enqueues. */
+typedef struct rf_noise_estimate
+{
+    double   mean_error;
+    float    max_error;
+    uint32_t worst_tile, samples;
+    uint64_t pixels, nonfinite_pixels;
+} rf_noise_estimate;
+RF_API int rf_renderer_set_moments(rf_renderer* r, int enabled);
+RF_API int rf_renderer_read_moments(rf_renderer* r, float* sumsq4, uint32_t* moment_sample_count);
+RF_API int rf_renderer_noise_estimate(rf_renderer* r, rf_noise_estimate* out, float* error_map, float* tile_sum, float* tile_max);
+RF_API int rf_noise_estimate_images(int32_t device_ordinal, uint32_t width, uint32_t height, uint32_t samples, const float* color_sum4, const float* sumsq4,
+                                    rf_noise_estimate* out, float* error_map, float* tile_sum, float* tile_max);
+RF_API int rf_renderer_render_until(rf_renderer* r, float target_mean_error, uint32_t check_every, uint32_t max_frames, uint32_t* frames_rendered,
+                                    rf_noise_estimate* last);
+
 /* Deferred-lighting variant (replaces nlrs::DeferredRenderer's lighting + resolve passes, src/pt/deferred_renderer.hpp,
  * deferred_renderer_lighting_pass.wgsl:96-186 -- fixed 2-bounce surfaceColor, solar disk in the sky term, the
  * 1/16384 + 1024 offset constants :498-500 -- and deferred_renderer_resolve_pass.wgsl:33-54 -- 0.1 / 0.9 exponential
@@ -353,7 +406,8 @@ RF_API int  rf_comm_transport(const rf_comm* c, uint32_t* local_out);
  * counterpart: the reference is single-device, reference_path_tracer.cpp:565-595.) */
 RF_API int  rf_comm_last_exchange_ms(rf_comm* c, double* ms_out);
 /* Device memory held by a handle: path state + queues (148 B per path slot: eight packed xyz streams, two float4 streams, five u32 queues / lists; 180 B while the first-hit
- * AOVs are on; allocated on demand for the largest batch traced),
+ * AOVs are on; allocated on demand for the largest batch traced; the radiance second moments add 16 B per pixel of the shard's tiles and nothing per path slot, so
+ * they are not part of these figures),
  * the batch depth in use (lowered automatically when the device has less free memory than the default wants: same image,
  * more batches) and the resident scene.  Any pointer may be NULL. */
 RF_API int  rf_renderer_memory_info(const rf_renderer* r, uint64_t* path_state_bytes, uint64_t* paths_allocated, uint64_t* max_paths_per_batch, uint64_t* scene_bytes);

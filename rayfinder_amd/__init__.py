@@ -453,6 +453,30 @@ def denoise_images(color_sum, albedo_coverage, normal_depth, samples, exposure=1
     return rgba[..., :3], bgra
 
 
+def _noise_result(est, error_map, tile_sum, tile_max):
+    out = {k: getattr(est, k) for k, _ in est._fields_}
+    out.update(error_map=error_map, tile_sum=tile_sum, tile_max=tile_max)
+    return out
+
+
+def _noise_tiles(width, height):
+    return ((width + TILE - 1) // TILE) * ((height + TILE - 1) // TILE)
+
+
+def noise_estimate_images(color_sum, sumsq, samples, device_ordinal=0):
+    """rf_noise_estimate_images: the noise estimate over (H,W,4) f32 sums held on the host (the accumulation and the radiance second moments) of `samples` >= 2
+    samples.  -> dict(mean_error, max_error, worst_tile, samples, pixels, nonfinite_pixels, error_map (H,W), tile_sum, tile_max (one entry per 32x32 tile))."""
+    color_sum, sumsq = _f32(color_sum), _f32(sumsq)
+    h, w = color_sum.shape[:2]
+    if color_sum.shape != (h, w, 4) or sumsq.shape != (h, w, 4):
+        raise ValueError("noise_estimate_images: the two sums must be (H, W, 4) arrays of one size")
+    est = _ffi.NoiseEstimate()
+    emap = np.zeros((h, w), np.float32)
+    tsum = np.zeros(_noise_tiles(w, h), np.float32); tmax = np.zeros_like(tsum)
+    check(lib.rf_noise_estimate_images(device_ordinal, w, h, samples, _ptr(color_sum), _ptr(sumsq), C.byref(est), _ptr(emap), _ptr(tsum), _ptr(tmax)))
+    return _noise_result(est, emap, tsum, tmax)
+
+
 class ReferencePathTracer:
     """Host-side mirror of nlrs::ReferencePathTracer (src/pt/reference_path_tracer.hpp:59-76).
 
@@ -538,6 +562,36 @@ class ReferencePathTracer:
         n = C.c_uint32(0)
         check(lib.rf_renderer_read_denoised(self._h, _ptr(rgba), _ptr(bgra), C.byref(n)))
         return rgba[..., :3], bgra, n.value
+
+    # radiance second moments, the noise estimate and render-to-a-noise-target (include/rayfinder_amd.h states the estimate's arithmetic)
+    def set_moments(self, enabled=True):
+        """Turn the per-pixel radiance second moments on or off; any change clears them."""
+        check(lib.rf_renderer_set_moments(self._h, int(bool(enabled))))
+
+    def read_moments(self):
+        """-> ((H, W, 4) f32 sums of the squared per-sample radiance {r*r, g*g, b*b, 0} in sample order, the moment sample count)"""
+        q = np.zeros((self._params.height, self._params.width, 4), np.float32)
+        n = C.c_uint32(0)
+        check(lib.rf_renderer_read_moments(self._h, _ptr(q), C.byref(n)))
+        return q, n.value
+
+    def noise_estimate(self):
+        """The noise estimate over the accumulation and the moments (needs the moments on from the first sample, >= 2 samples, no tile shard).
+        -> dict(mean_error, max_error, worst_tile, samples, pixels, nonfinite_pixels, error_map (H,W), tile_sum, tile_max (one entry per 32x32 tile))."""
+        h, w = self._params.height, self._params.width
+        est = _ffi.NoiseEstimate()
+        emap = np.zeros((h, w), np.float32)
+        tsum = np.zeros(_noise_tiles(w, h), np.float32); tmax = np.zeros_like(tsum)
+        check(lib.rf_renderer_noise_estimate(self._h, C.byref(est), _ptr(emap), _ptr(tsum), _ptr(tmax)))
+        return _noise_result(est, emap, tsum, tmax)
+
+    def render_until(self, target_mean_error, check_every=8, max_frames=0xFFFFFFFF):
+        """Render in steps of check_every frames until the estimate's mean_error is <= target_mean_error, max_frames frames have been rendered or the accumulation
+        is full.  -> (frames rendered, dict of the last estimate's scalars, or None when fewer than 2 samples were accumulated)."""
+        frames = C.c_uint32(0)
+        est = _ffi.NoiseEstimate()
+        check(lib.rf_renderer_render_until(self._h, target_mean_error, check_every, max_frames, C.byref(frames), C.byref(est)))
+        return frames.value, ({k: getattr(est, k) for k, _ in est._fields_} if est.samples else None)
 
     # deferred-lighting variant (nlrs::DeferredRenderer's lighting + resolve passes over a primary-ray G-buffer)
     def render_deferred(self, num_frames=1):

@@ -43,6 +43,11 @@ class DenoiseParameters(C.Structure):
     _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float)]
 
 
+class NoiseEstimate(C.Structure):
+    _fields_ = [("mean_error", C.c_double), ("max_error", C.c_float), ("worst_tile", C.c_uint32), ("samples", C.c_uint32), ("pixels", C.c_uint64),
+                ("nonfinite_pixels", C.c_uint64)]
+
+
 class Camera(C.Structure):
     _fields_ = [("origin", C.c_float * 3), ("lower_left_corner", C.c_float * 3), ("horizontal", C.c_float * 3),
                 ("vertical", C.c_float * 3), ("up", C.c_float * 3), ("right", C.c_float * 3), ("lens_radius", C.c_float)]
@@ -126,6 +131,11 @@ SIGNATURES = {
     "rf_renderer_read_denoised": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
     "rf_denoise_images": (C.c_int, [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
                                     C.c_void_p]),
+    "rf_renderer_set_moments": (C.c_int, [C.c_void_p, C.c_int]),
+    "rf_renderer_read_moments": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
+    "rf_renderer_noise_estimate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rf_noise_estimate_images": (C.c_int, [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rf_renderer_render_until": (C.c_int, [C.c_void_p, C.c_float, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p]),
     "rf_renderer_render_deferred": (C.c_int, [C.c_void_p, C.c_uint32]),
     "rf_renderer_reset_deferred": (C.c_int, [C.c_void_p]),
     "rf_renderer_read_deferred": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),

@@ -1,7 +1,8 @@
 // rf-render <scene.pt|scene.glb> [--width W] [--height H] [--spp N] [--bounces B] [--vfov deg]
 //           [--zenith deg] [--azimuth deg] [--turbidity t] [--exposure-stops s] [--out image.png]
 //           [--pfm image.pfm] [--aov-albedo a.pfm] [--aov-normal n.pfm] [--aov-depth d.pfm] [--denoise d.png] [--denoise-pfm d.pfm]
-//           [--denoise-iterations L] [--denoise-sigma-color s] [--denoise-sigma-normal s] [--denoise-sigma-depth s] [--gpus N]
+//           [--denoise-iterations L] [--denoise-sigma-color s] [--denoise-sigma-normal s] [--denoise-sigma-depth s]
+//           [--noise-map m.pfm] [--noise-target t] [--noise-check-every k] [--gpus N]
 // Offline counterpart of the interactive `pt` app (src/pt/main.cpp): same default camera pose,
 // sky and exposure; renders all samples and writes the tonemapped image (and optionally the
 // mean radiance as PFM).  --gpus N: one host thread per GPU, the image tile-sharded across them, one RCCL
@@ -11,6 +12,11 @@
 // --denoise / --denoise-pfm: the edge-aware a-trous denoiser (rf_renderer_denoise) over the frame, guided by the AOVs (any --denoise* option turns them on
 // from the first sample).  With --gpus N > 1 it runs once, on device 0, over the gathered accumulation and the host-assembled AOV sums (rf_denoise_images):
 // the same inputs, the same kernels, the same bytes whatever N.
+// --noise-map: the per-pixel relative standard error of the frame (rf_renderer_noise_estimate's error map, a one-channel PFM) from the radiance second moments
+// (rf_renderer_set_moments, on from the first sample).  With --gpus N > 1 each rank reads its own tiles' moments, the host assembles them, and the estimate runs once,
+// on device 0, over the gathered accumulation (rf_noise_estimate_images): the same map whatever N.
+// --noise-target t [--noise-check-every k]: stop as soon as the frame's mean error is <= t, checked every k samples (default 8), at --spp at the latest
+// (rf_renderer_render_until).  One GPU only: stopping several ranks in step is not implemented.
 #include "cli_common.hpp"
 
 #include <algorithm>
@@ -30,7 +36,10 @@ int main(int argc, char** argv)
                     "  no sample hit) -- the auxiliary inputs of a denoiser\n"
                     "                 [--denoise d.png] [--denoise-pfm d.pfm] [--denoise-iterations L] [--denoise-sigma-color s] [--denoise-sigma-normal s]\n"
                     "                 [--denoise-sigma-depth s]\n"
-                    "  --denoise / --denoise-pfm: the frame through the edge-aware a-trous denoiser guided by the AOVs (defaults: L 5, sigmas 1, 0.1, 0.1)\n");
+                    "  --denoise / --denoise-pfm: the frame through the edge-aware a-trous denoiser guided by the AOVs (defaults: L 5, sigmas 1, 0.1, 0.1)\n"
+                    "                 [--noise-map m.pfm] [--noise-target t] [--noise-check-every k]\n"
+                    "  --noise-map: the per-pixel relative standard error of the frame (1-channel PFM); --noise-target: stop once the frame's mean error is <= t,\n"
+                    "  checked every k samples (default 8), at --spp at the latest (one GPU only)\n");
         return 0;
     }
     uint32_t    W = 1920, H = 1080, spp = 64, bounces = 2; // UI defaults src/pt/main.cpp:46-60
@@ -41,6 +50,10 @@ int main(int argc, char** argv)
     rf_denoise_parameters denoiseParams{};
     rf_denoise_default_parameters(&denoiseParams);
     bool denoising = false;
+    std::string noiseMap;
+    float       noiseTarget = 0.0f;
+    bool        noiseTargetSet = false;
+    uint32_t    noiseCheckEvery = 8;
     for (int i = 2; i + 1 < argc; i += 2)
     {
         const std::string k = argv[i];
@@ -66,11 +79,19 @@ int main(int argc, char** argv)
         else if (k == "--denoise-sigma-color") denoiseParams.sigma_color = static_cast<float>(std::atof(val)), denoising = true;
         else if (k == "--denoise-sigma-normal") denoiseParams.sigma_normal = static_cast<float>(std::atof(val)), denoising = true;
         else if (k == "--denoise-sigma-depth") denoiseParams.sigma_depth = static_cast<float>(std::atof(val)), denoising = true;
+        else if (k == "--noise-map") noiseMap = val;
+        else if (k == "--noise-target") noiseTarget = static_cast<float>(std::atof(val)), noiseTargetSet = true;
+        else if (k == "--noise-check-every") noiseCheckEvery = static_cast<uint32_t>(std::max(1, std::atoi(val)));
         else
         {
             std::fprintf(stderr, "unknown option %s\n", k.c_str());
             return 1;
         }
+    }
+    if (noiseTargetSet && gpus > 1)
+    {
+        std::fprintf(stderr, "--noise-target needs --gpus 1: stopping several ranks in step at a noise target is not implemented (render a fixed --spp and use --noise-map)\n");
+        return 1;
     }
     rf_pt_format*     pt = loadScene(argv[1]);
     rf_pt_format_view v;
@@ -95,7 +116,14 @@ int main(int argc, char** argv)
     std::vector<uint32_t>           bgra(static_cast<size_t>(W) * H);
     std::vector<float>              acc;
     // (the denoiser over several ranks needs the whole accumulation on the host)
-    if (!pfm.empty() || (denoising && gpus > 1)) acc.resize(static_cast<size_t>(W) * H * 4);
+    // radiance second moments of the whole frame (every rank copies in the pixels of its own tiles), the error map, and the samples actually rendered
+    const bool         noise = !noiseMap.empty() || noiseTargetSet;
+    std::vector<float> momentsFrame, errorMap;
+    rf_noise_estimate  estimate{};
+    uint32_t           sppReached = spp;
+    if (!noiseMap.empty()) errorMap.resize(static_cast<size_t>(W) * H);
+    if (!noiseMap.empty() && gpus > 1) momentsFrame.resize(static_cast<size_t>(W) * H * 4);
+    if (!pfm.empty() || ((denoising || !noiseMap.empty()) && gpus > 1)) acc.resize(static_cast<size_t>(W) * H * 4);
     // first-hit AOV sums of the whole frame ({albedo, coverage}, {normal, depth}): every rank copies in the pixels of its own tiles
     const bool         aovs = !aovAlbedo.empty() || !aovNormal.empty() || !aovDepth.empty() || denoising;
     std::vector<float>    denoisedRgba;
@@ -121,8 +149,10 @@ int main(int argc, char** argv)
             rfCheck(rf_comm_create(commId, rank, gpus, d.device_ordinal, &comm), "RCCL communicator");
         }
         if (aovs) rfCheck(rf_renderer_set_aovs(renderer, RF_AOV_FIRST_HIT), "AOVs");
+        if (noise) rfCheck(rf_renderer_set_moments(renderer, 1), "moments");
         const auto t0 = std::chrono::steady_clock::now();
-        rfCheck(rf_renderer_render(renderer, spp), "render");
+        if (noiseTargetSet) rfCheck(rf_renderer_render_until(renderer, noiseTarget, noiseCheckEvery, spp, &sppReached, &estimate), "render to the noise target");
+        else rfCheck(rf_renderer_render(renderer, spp), "render");
         void* gathered = nullptr;
         if (comm) rfCheck(rf_renderer_gather_frame(renderer, comm, 0, 0, &gathered), "gather");
         rfCheck(rf_renderer_synchronize(renderer), "synchronize");
@@ -151,8 +181,25 @@ int main(int argc, char** argv)
                     }
             if (rank == 0) aovSamples = n;
         }
+        if (!momentsFrame.empty())
+        {
+            std::vector<float> q(momentsFrame.size());
+            uint32_t           n = 0, numTiles = 0;
+            rfCheck(rf_renderer_read_moments(renderer, q.data(), &n), "read moments");
+            rfCheck(rf_renderer_shard_tiles(renderer, nullptr, &numTiles), "shard tiles");
+            std::vector<uint32_t> tiles(numTiles);
+            rfCheck(rf_renderer_shard_tiles(renderer, tiles.data(), &numTiles), "shard tiles");
+            const uint32_t tilesX = (W + 31) / 32;
+            for (const uint32_t t : tiles)
+                for (uint32_t y = (t / tilesX) * 32; y < std::min(H, (t / tilesX) * 32 + 32); ++y)
+                {
+                    const size_t i = 4 * (static_cast<size_t>(y) * W + (t % tilesX) * 32), len = 4 * static_cast<size_t>(std::min(W, (t % tilesX) * 32 + 32) - (t % tilesX) * 32);
+                    std::copy(q.begin() + i, q.begin() + i + len, momentsFrame.begin() + i);
+                }
+        }
         if (rank == 0)
         {
+            if (!noiseMap.empty() && !comm) rfCheck(rf_renderer_noise_estimate(renderer, &estimate, errorMap.data(), nullptr, nullptr), "noise estimate");
             if (comm)
             {
                 rfCheck(rf_renderer_tonemap_device_image(renderer, gathered, static_cast<uint64_t>(W) * H, spp, bgra.data()), "tonemap");
@@ -182,9 +229,17 @@ int main(int argc, char** argv)
                                   denoisedBgra.data()),
                 "denoise");
 
+    if (!noiseMap.empty() && gpus > 1)
+        rfCheck(rf_noise_estimate_images(0, W, H, spp, acc.data(), momentsFrame.data(), &estimate, errorMap.data(), nullptr, nullptr), "noise estimate");
+
     const double rays = static_cast<double>(closestRays.load() + shadowRays.load());
-    std::printf("%ux%u, %u spp, %u bounces on %u GPU(s): %.3f s, %.1f Mrays/s (%llu closest + %llu shadow rays)\n", W, H, spp, bounces, gpus, seconds,
+    std::printf("%ux%u, %u spp, %u bounces on %u GPU(s): %.3f s, %.1f Mrays/s (%llu closest + %llu shadow rays)\n", W, H, sppReached, bounces, gpus, seconds,
                 rays / seconds * 1e-6, closestRays.load(), shadowRays.load());
+    if (noiseTargetSet)
+        std::printf("noise target %g: stopped at %u of %u spp, mean error %.6g (estimated at %u spp)\n", noiseTarget, sppReached, spp, estimate.mean_error, estimate.samples);
+    if (!noiseMap.empty())
+        std::printf("noise at %u spp: mean error %.6g, max error %.6g in tile %u, %llu non-finite pixel(s)\n", estimate.samples, estimate.mean_error, estimate.max_error,
+                    estimate.worst_tile, static_cast<unsigned long long>(estimate.nonfinite_pixels));
 
     std::vector<uint8_t> rgba(bgra.size() * 4);
     for (size_t i = 0; i < bgra.size(); ++i)
@@ -195,7 +250,7 @@ int main(int argc, char** argv)
         rgba[4 * i + 3] = 255;
     }
     if (!writePngRgba(out, rgba.data(), W, H)) return 1;
-    if (!pfm.empty()) writePfm(pfm, acc.data(), W, H, 1.0f / static_cast<float>(std::max(spp, 1u)));
+    if (!pfm.empty()) writePfm(pfm, acc.data(), W, H, 1.0f / static_cast<float>(std::max(sppReached, 1u)));
     if (denoising)
     {
         std::vector<uint8_t> d(denoisedBgra.size() * 4);
@@ -209,25 +264,27 @@ int main(int argc, char** argv)
         if (!denoisePng.empty() && !writePngRgba(denoisePng, d.data(), W, H)) return 1;
         if (!denoisePfm.empty() && !writePfm(denoisePfm, denoisedRgba.data(), W, H, 1.0f)) return 1;
     }
+    // a 3- or 1-channel PFM of value(4 * pixel index, channel)
+    const auto write = [&](const std::string& path, uint32_t channels, auto&& value) {
+        if (path.empty()) return true;
+        FILE* fp = std::fopen(path.c_str(), "wb");
+        if (!fp) return false;
+        std::fprintf(fp, "%s\n%u %u\n-1.0\n", channels == 3 ? "PF" : "Pf", W, H);
+        std::vector<float> row(static_cast<size_t>(channels) * W);
+        for (uint32_t y = 0; y < H; ++y) // (bottom row first)
+        {
+            for (uint32_t x = 0; x < W; ++x)
+                for (uint32_t c = 0; c < channels; ++c) row[channels * x + c] = value(4 * (static_cast<size_t>(H - 1 - y) * W + x), c);
+            std::fwrite(row.data(), sizeof(float), row.size(), fp);
+        }
+        std::fclose(fp);
+        return true;
+    };
+    if (!write(noiseMap, 1, [&](size_t i, uint32_t) { return errorMap[i / 4]; })) return 1;
     if (aovs)
     {
         // means (f32 divisions, as ReferencePathTracer.aov_means): albedo / normal over the AOV samples, depth over the coverage
         const float n = static_cast<float>(std::max(aovSamples, 1u));
-        const auto  write = [&](const std::string& path, uint32_t channels, auto&& value) {
-            if (path.empty()) return true;
-            FILE* fp = std::fopen(path.c_str(), "wb");
-            if (!fp) return false;
-            std::fprintf(fp, "%s\n%u %u\n-1.0\n", channels == 3 ? "PF" : "Pf", W, H);
-            std::vector<float> row(static_cast<size_t>(channels) * W);
-            for (uint32_t y = 0; y < H; ++y) // (bottom row first)
-            {
-                for (uint32_t x = 0; x < W; ++x)
-                    for (uint32_t c = 0; c < channels; ++c) row[channels * x + c] = value(4 * (static_cast<size_t>(H - 1 - y) * W + x), c);
-                std::fwrite(row.data(), sizeof(float), row.size(), fp);
-            }
-            std::fclose(fp);
-            return true;
-        };
         const bool ok = write(aovAlbedo, 3, [&](size_t i, uint32_t c) { return aovAc[i + c] / n; }) && write(aovNormal, 3, [&](size_t i, uint32_t c) { return aovNd[i + c] / n; }) &&
                         write(aovDepth, 1, [&](size_t i, uint32_t) { return aovAc[i + 3] > 0.0f ? aovNd[i + 3] / aovAc[i + 3] : 0.0f; });
         if (!ok) return 1;

@@ -122,6 +122,10 @@ rf::DenoiseParameters toDenoiseParams(const rf_denoise_parameters* p)
     out.sigmaColor = p->sigma_color, out.sigmaNormal = p->sigma_normal, out.sigmaDepth = p->sigma_depth;
     return out;
 }
+rf_noise_estimate toNoiseEstimate(const rf::NoiseEstimate& e)
+{
+    return rf_noise_estimate{e.meanError, e.maxError, e.worstTile, e.samples, e.pixels, e.nonfinitePixels};
+}
 } // namespace
 
 extern "C" {
@@ -309,6 +313,58 @@ int rf_denoise_images(int32_t device_ordinal, uint32_t width, uint32_t height, u
         require(samples > 0, "sample count must be > 0");
         require(std::isfinite(exposure), "exposure must be finite");
         rf::denoiseImages(device_ordinal, width, height, samples, color_sum4, albedo_coverage4, normal_depth4, p, exposure, out_rgba, out_bgra8);
+        return RF_OK;
+    });
+}
+
+int rf_renderer_set_moments(rf_renderer* r, int enabled)
+{
+    return guarded([&] {
+        require(r, "null argument");
+        r->impl->setMoments(enabled != 0);
+        return RF_OK;
+    });
+}
+
+int rf_renderer_read_moments(rf_renderer* r, float* sumsq4, uint32_t* moment_sample_count)
+{
+    return guarded([&] {
+        require(r, "null argument");
+        r->impl->readMoments(sumsq4, moment_sample_count);
+        return RF_OK;
+    });
+}
+
+int rf_renderer_noise_estimate(rf_renderer* r, rf_noise_estimate* out, float* error_map, float* tile_sum, float* tile_max)
+{
+    return guarded([&] {
+        require(r && out, "null argument");
+        *out = toNoiseEstimate(r->impl->noiseEstimate(error_map, tile_sum, tile_max));
+        return RF_OK;
+    });
+}
+
+int rf_noise_estimate_images(int32_t device_ordinal, uint32_t width, uint32_t height, uint32_t samples, const float* color_sum4, const float* sumsq4, rf_noise_estimate* out,
+                             float* error_map, float* tile_sum, float* tile_max)
+{
+    return guarded([&] {
+        require(color_sum4 && sumsq4 && out, "null argument");
+        require(width > 0 && height > 0, "image size must be non-zero");
+        require(static_cast<uint64_t>(width) * height < (1ull << 31), "image too large");
+        require(samples >= 2, "a variance needs a sample count >= 2");
+        *out = toNoiseEstimate(rf::noiseEstimateImages(device_ordinal, width, height, samples, color_sum4, sumsq4, error_map, tile_sum, tile_max));
+        return RF_OK;
+    });
+}
+
+int rf_renderer_render_until(rf_renderer* r, float target_mean_error, uint32_t check_every, uint32_t max_frames, uint32_t* frames_rendered, rf_noise_estimate* last)
+{
+    return guarded([&] {
+        require(r, "null argument");
+        rf::NoiseEstimate e;
+        const uint32_t    frames = r->impl->renderUntil(target_mean_error, check_every, max_frames, &e);
+        if (frames_rendered) *frames_rendered = frames;
+        if (last) *last = toNoiseEstimate(e);
         return RF_OK;
     });
 }

@@ -1,0 +1,244 @@
+// rf_noise.hip -- per-pixel radiance second moments and the noise estimate over them.  The arithmetic is the one include/rayfinder_amd.h writes out ("Radiance
+// second moments and the noise estimate"), one IEEE f32 operation at a time in that order (-ffp-contract=off, correctly rounded divide and sqrt, no denormal
+// flushing): tests/noise_restatement.py reproduces it bit for bit.  No floating-point atomics: every output is one lane's fixed sequence of operations.
+//   kAccumulateMoments      one lane per pixel, any slot order (kAccumulate's addressing): Q += r r per channel, samples in index order
+//   kAccumulateMomentsRuns  the same sums for the pixel-major slot order, the runs staged (squared) in LDS in fixed-size chunks (kAccumulateAovRuns' shape)
+//   kNoiseEstimate          one 256-lane workgroup per 32x32 tile: the per-pixel relative standard error, the tile's halving-tree sum, maximum and counts
+// Both accumulation kernels read the per-slot radiance stream the image is accumulated from (ps.rad) and nothing else of the path state: the trace and shading
+// kernels do not know about them.
+#include "rf_noise.hpp"
+
+#include "rf_math.hpp"
+
+#include <vector>
+
+namespace rf
+{
+namespace
+{
+constexpr float kEpsLum = 0.00390625f; // 2^-8
+
+__global__ __launch_bounds__(kBlock) void kAccumulateMoments(FrameParams fp, const uint32_t* tileIds, const float4* rad, float4* moments)
+{
+    const uint32_t lp = blockIdx.x * kBlock + threadIdx.x;
+    if (lp >= fp.pixelsPadded) return;
+    uint32_t x, y;
+    if (!localPixelToXY(fp, tileIds, lp, x, y)) return;
+    float4 q = moments[lp];
+    for (uint32_t k = 0; k < fp.numSamples; ++k)
+    {
+        const Vec3 r = load3(rad + samplePixelToSlot(fp, fp.sampleInvPerm ? fp.sampleInvPerm[k] : k, lp));
+        q.x += r.x * r.x;
+        q.y += r.y * r.y;
+        q.z += r.z * r.z;
+    }
+    moments[lp] = q;
+}
+
+// Pixel-major slot order (slotGroupShift = 0): a pixel's samples are one run of numSamples float4.  One 64-lane workgroup takes kMomentPixels pixels; per chunk of
+// kMomentChunk samples it reads their radiance (two pixels' chunks = 1 KiB per load round, coalesced when the samples are not permuted), squares it -- in parallel,
+// one multiply per channel -- and stores the squares in LDS at the sample's index; then each of the 48 summing lanes -- one (pixel, channel) -- adds the chunk in
+// sample order onto its running sum.  6.3 KB of LDS per workgroup at any batch depth (<= ~8 KB keeps twenty workgroups resident per CU, profiles/r06_raygen).
+__global__ __launch_bounds__(64) void kAccumulateMomentsRuns(FrameParams fp, const uint32_t* tileIds, const float4* rad, float4* moments)
+{
+    constexpr uint32_t R = kMomentChunk + 1u; // rows padded by one float: the summing lanes walk different banks
+    __shared__ float   sRun[kMomentPixels * 3u * R]; // [pixel][channel][sample of the chunk]
+    static_assert(kMomentPixels * 3u <= 64u && kMomentChunk * 2u == 64u && kMomentPixels % 2u == 0u, "one summing lane per (pixel, channel); two pixels' chunks per load round");
+    const uint32_t S = fp.numSamples, lane = threadIdx.x, lp0 = blockIdx.x * kMomentPixels;
+    const uint32_t px = lane / 3u, c = lane - 3u * px, lp = lp0 + px;
+    const bool     sums = lane < kMomentPixels * 3u && lp < fp.pixelsPadded;
+    float          acc = sums ? reinterpret_cast<const float*>(moments + lp)[c] : 0.0f;
+    for (uint32_t k0 = 0; k0 < S; k0 += kMomentChunk)
+    {
+        const uint32_t n = min(kMomentChunk, S - k0), kk = lane & (kMomentChunk - 1u), half = lane >> 5;
+        if (kk < n)
+        {
+            const uint32_t k = k0 + kk, p = fp.sampleInvPerm ? fp.sampleInvPerm[k] : k; // sample k sits at position p of the pixel's run
+            // load round i: pixels 2 i and 2 i + 1 of the workgroup, lane = (pixel of the pair, sample of the chunk)
+#pragma unroll
+            for (uint32_t i = 0; i < kMomentPixels / 2u; ++i)
+            {
+                const uint32_t pi = 2u * i + half, lpi = lp0 + pi;
+                if (lpi >= fp.pixelsPadded) continue;
+                const Vec3 v = load3(rad + static_cast<size_t>(lpi) * S + p);
+                float*     dst = sRun + pi * 3u * R + kk;
+                dst[0] = v.x * v.x, dst[R] = v.y * v.y, dst[2u * R] = v.z * v.z;
+            }
+        }
+        __syncthreads();
+        if (sums)
+        {
+            const float* src = sRun + lane * R; // (row lane = pixel px, channel c)
+            for (uint32_t j = 0; j < n; ++j) acc += src[j]; // sample order: one dependent chain of f32 additions per channel
+        }
+        __syncthreads(); // the next chunk overwrites the rows
+    }
+    if (!sums) return;
+    uint32_t x, y;
+    if (!localPixelToXY(fp, tileIds, lp, x, y)) return;
+    reinterpret_cast<float*>(moments + lp)[c] = acc;
+}
+
+// One workgroup per tile of the 32x32 grid.  tileMajor: entry j of the tile sits at S[tile * 1024 + j] (8x8 blocks, localPixelToXY's layout: the workgroup reads
+// two contiguous 16 KB runs); else the sums are row-major.  nf = float(N), nf1 = nf - 1.  errorMap (row-major) may be nullptr.
+__global__ __launch_bounds__(256) void kNoiseEstimate(const float4* colorSum, const float4* sumSq, uint32_t width, uint32_t height, uint32_t tilesX, uint32_t tileMajor, float nf,
+                                                      float nf1, float* errorMap, float* tileSum, float* tileMax, uint32_t* tilePixels, uint32_t* tileNonfinite)
+{
+    __shared__ float    a[1024]; // a[ty * 32 + tx]
+    __shared__ float    sMax[256];
+    __shared__ uint32_t sCount[2];
+    const uint32_t t = threadIdx.x, tile = blockIdx.x, tileY = tile / tilesX, tileX = tile - tileY * tilesX;
+    if (t < 2u) sCount[t] = 0u;
+    __syncthreads();
+    float    m = -__builtin_inff();
+    uint32_t pixels = 0, bad = 0;
+    for (uint32_t j = t; j < 1024u; j += 256u)
+    {
+        const uint32_t block = j >> 6, lane = j & 63u;
+        const uint32_t tx = tileMajor ? (block & 3u) * 8u + (lane & 7u) : (j & 31u), ty = tileMajor ? (block >> 2) * 8u + (lane >> 3) : (j >> 5);
+        const uint32_t x = tileX * kTileSize + tx, y = tileY * kTileSize + ty;
+        float          e = 0.0f;
+        if (x < width && y < height)
+        {
+            const size_t src = tileMajor ? static_cast<size_t>(tile) * 1024u + j : static_cast<size_t>(y) * width + x;
+            const float4 s4 = colorSum[src], q4 = sumSq[src];
+            const float  s[3] = {s4.x, s4.y, s4.z}, q[3] = {q4.x, q4.y, q4.z};
+            float        mu[3], v[3];
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch)
+            {
+                mu[ch] = s[ch] / nf;
+                const float sm = s[ch] * mu[ch];
+                const float d = q[ch] - sm;
+                const float vv = d / nf1;
+                v[ch] = vv > 0.0f ? vv : 0.0f; // (NaN: 0)
+            }
+            const float s2 = ((v[0] + v[1]) + v[2]) / nf;
+            const float l = (mu[0] + mu[1]) + mu[2];
+            e = rf_sqrt(s2) / (l + kEpsLum);
+            ++pixels;
+            if (!(e <= FLT_MAX))
+            {
+                ++bad;
+                e = 0.0f;
+            }
+            m = e > m ? e : m;
+            if (errorMap) errorMap[static_cast<size_t>(y) * width + x] = e;
+        }
+        a[ty * 32u + tx] = e;
+    }
+    sMax[t] = m;
+    atomicAdd(&sCount[0], pixels);
+    if (bad) atomicAdd(&sCount[1], bad);
+    __syncthreads();
+    for (uint32_t h = 512u; h >= 1u; h >>= 1)
+    {
+        for (uint32_t i = t; i < h; i += 256u) a[i] = a[i] + a[i + h];
+        if (h <= 128u && t < h)
+        {
+            const float o = sMax[t + h];
+            if (o > sMax[t]) sMax[t] = o;
+        }
+        __syncthreads();
+    }
+    if (t == 0u)
+    {
+        tileSum[tile] = a[0];
+        tileMax[tile] = sMax[0] + 0.0f; // (a maximum of -0 is returned as +0: which zero a maximum keeps is not an IEEE operation)
+        tilePixels[tile] = sCount[0];
+        tileNonfinite[tile] = sCount[1];
+    }
+}
+} // namespace
+
+AccumulateMomentsKernel accumulateMomentsKernel(bool runs) { return runs ? kAccumulateMomentsRuns : kAccumulateMoments; }
+
+void NoiseWork::reserve(uint64_t nTiles, uint64_t nMap, hipStream_t stream)
+{
+    if (nTiles <= tiles && nMap <= mapPixels) return;
+    RF_HIP(hipStreamSynchronize(stream)); // (a smaller set may still be in use by the last run)
+    nTiles = std::max(nTiles, tiles), nMap = std::max(nMap, mapPixels);
+    release();
+    RF_HIP(hipMalloc(reinterpret_cast<void**>(&tileSumMax), 2 * nTiles * sizeof(float)));
+    RF_HIP(hipMalloc(reinterpret_cast<void**>(&tileCounts), 2 * nTiles * sizeof(uint32_t)));
+    if (nMap) RF_HIP(hipMalloc(reinterpret_cast<void**>(&errorMap), nMap * sizeof(float)));
+    tiles = nTiles, mapPixels = nMap;
+}
+
+void NoiseWork::release()
+{
+    for (void* b : {static_cast<void*>(tileSumMax), static_cast<void*>(tileCounts), static_cast<void*>(errorMap)})
+        if (b) (void)hipFree(b);
+    tileSumMax = errorMap = nullptr;
+    tileCounts = nullptr;
+    tiles = mapPixels = 0;
+}
+
+NoiseEstimate runNoiseEstimate(hipStream_t stream, NoiseWork& w, const float4* colorSum, const float4* sumSq, uint32_t width, uint32_t height, bool tileMajor, uint32_t samples,
+                               float* errorMap, float* tileSum, float* tileMax)
+{
+    const uint32_t tilesX = (width + kTileSize - 1) / kTileSize, tilesY = (height + kTileSize - 1) / kTileSize, tiles = tilesX * tilesY;
+    const uint64_t n = static_cast<uint64_t>(width) * height;
+    w.reserve(tiles, errorMap ? n : 0, stream);
+    const float nf = static_cast<float>(samples), nf1 = nf - 1.0f;
+    hipLaunchKernelGGL(kNoiseEstimate, dim3(tiles), dim3(256), 0, stream, colorSum, sumSq, width, height, tilesX, tileMajor ? 1u : 0u, nf, nf1,
+                       errorMap ? w.errorMap : static_cast<float*>(nullptr), w.tileSumMax, w.tileSumMax + w.tiles, w.tileCounts, w.tileCounts + w.tiles);
+    RF_HIP(hipGetLastError());
+    std::vector<float>    sums(tiles), maxima(tiles);
+    std::vector<uint32_t> pixels(tiles), nonfinite(tiles);
+    RF_HIP(hipMemcpyAsync(sums.data(), w.tileSumMax, tiles * sizeof(float), hipMemcpyDeviceToHost, stream));
+    RF_HIP(hipMemcpyAsync(maxima.data(), w.tileSumMax + w.tiles, tiles * sizeof(float), hipMemcpyDeviceToHost, stream));
+    RF_HIP(hipMemcpyAsync(pixels.data(), w.tileCounts, tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    RF_HIP(hipMemcpyAsync(nonfinite.data(), w.tileCounts + w.tiles, tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    if (errorMap) RF_HIP(hipMemcpyAsync(errorMap, w.errorMap, n * sizeof(float), hipMemcpyDeviceToHost, stream));
+    RF_HIP(hipStreamSynchronize(stream));
+    // the frame, on the host: tile sums added in f64 in ascending tile order; the first tile that attains the maximum
+    NoiseEstimate out;
+    out.samples = samples;
+    double total = 0.0;
+    out.maxError = maxima[0];
+    for (uint32_t t = 0; t < tiles; ++t)
+    {
+        total += static_cast<double>(sums[t]);
+        if (maxima[t] > out.maxError) out.maxError = maxima[t], out.worstTile = t;
+        out.pixels += pixels[t];
+        out.nonfinitePixels += nonfinite[t];
+    }
+    out.meanError = total / static_cast<double>(out.pixels);
+    if (tileSum) std::memcpy(tileSum, sums.data(), tiles * sizeof(float));
+    if (tileMax) std::memcpy(tileMax, maxima.data(), tiles * sizeof(float));
+    return out;
+}
+
+NoiseEstimate noiseEstimateImages(int deviceOrdinal, uint32_t width, uint32_t height, uint32_t samples, const float* colorSum, const float* sumSq, float* errorMap, float* tileSum,
+                                  float* tileMax)
+{
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) throw std::runtime_error("rayfinder_amd: no HIP device available (this library has no CPU fallback)");
+    if (deviceOrdinal < 0 || deviceOrdinal >= count) throw std::invalid_argument("device ordinal out of range");
+    RF_HIP(hipSetDevice(deviceOrdinal));
+    const uint64_t n = static_cast<uint64_t>(width) * height;
+    struct Scope
+    {
+        hipStream_t stream = nullptr;
+        float4*     in[2] = {};
+        NoiseWork   work;
+        ~Scope()
+        {
+            if (stream) (void)hipStreamSynchronize(stream);
+            for (float4* b : in)
+                if (b) (void)hipFree(b);
+            work.release();
+            if (stream) (void)hipStreamDestroy(stream);
+        }
+    } s;
+    RF_HIP(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
+    const float* src[2] = {colorSum, sumSq};
+    for (int b = 0; b < 2; ++b)
+    {
+        RF_HIP(hipMalloc(reinterpret_cast<void**>(&s.in[b]), n * sizeof(float4)));
+        RF_HIP(hipMemcpyAsync(s.in[b], src[b], n * sizeof(float4), hipMemcpyHostToDevice, s.stream));
+    }
+    return runNoiseEstimate(s.stream, s.work, s.in[0], s.in[1], width, height, false, samples, errorMap, tileSum, tileMax);
+}
+} // namespace rf

@@ -1,0 +1,36 @@
+// rf_noise.hpp -- per-pixel radiance second moments and the noise estimate over them (rf_noise.hip): the two accumulation kernels the renderer launches while
+// rf_renderer_set_moments is on, and the launch sequence of the estimate, shared by rf_renderer_noise_estimate (inputs: the handle's own compact tile-major sums)
+// and the standalone rf_noise_estimate_images (inputs: row-major sums).
+#pragma once
+
+#include "rf_kernels.hpp"
+
+namespace rf
+{
+// Q[lp] += {r.x r.x, r.y r.y, r.z r.z, 0} of samples 0 .. numSamples-1 in sample order, r = rad[slot of (sample, lp)] (what kAccumulate adds); compact tile-major like the image
+using AccumulateMomentsKernel = void (*)(FrameParams fp, const uint32_t* tileIds, const float4* rad, float4* moments);
+// kAccumulateMomentsRuns: 16 pixels x 3 channels = 48 summing lanes of a 64-lane workgroup; their runs are staged, squared, in chunks of kMomentChunk samples
+// (16 x 3 x (32 + 1) floats = 6.3 KB of LDS, whatever the batch depth)
+constexpr uint32_t kMomentPixels = 16, kMomentChunk = 32;
+AccumulateMomentsKernel accumulateMomentsKernel(bool runs); // runs: the LDS-staged kernel for the pixel-major slot order (slotGroupShift 0)
+
+// Device buffers of one estimate: per-tile {sum, max} and {pixels, non-finite pixels}, and the row-major error map (only when a caller asks for it)
+struct NoiseWork
+{
+    float*    tileSumMax = nullptr; // [tiles] sums, then [tiles] maxima
+    uint32_t* tileCounts = nullptr; // [tiles] in-frame pixels, then [tiles] non-finite pixels
+    float*    errorMap = nullptr;   // width * height
+    uint64_t  tiles = 0, mapPixels = 0;
+
+    // room for `tiles` tiles and, if wanted, a map of `pixels` (stream-synchronises before it frees a smaller set)
+    void reserve(uint64_t tiles, uint64_t mapPixels, hipStream_t stream);
+    void release();
+    ~NoiseWork() { release(); }
+};
+
+// Enqueue kNoiseEstimate on `stream`, copy the per-tile results (and the map) back, wait, and reduce them on the host (the definition: include/rayfinder_amd.h).
+// tileMajor: the sums are compact tile-major buffers holding every tile of the frame in tile order (a handle without a tile shard); else row-major.
+// errorMap (width * height), tileSum, tileMax (one entry per tile of the 32 x 32 grid): host pointers, NULL = skip.  samples >= 2, width * height < 2^31.
+NoiseEstimate runNoiseEstimate(hipStream_t stream, NoiseWork& work, const float4* colorSum, const float4* sumSq, uint32_t width, uint32_t height, bool tileMajor,
+                               uint32_t samples, float* errorMap, float* tileSum, float* tileMax);
+} // namespace rf

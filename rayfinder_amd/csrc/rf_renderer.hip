@@ -23,6 +23,7 @@
 // device memory, so a whole batch is enqueued without any host round trip.
 #include "rf_denoise.hpp"
 #include "rf_kernels.hpp"
+#include "rf_noise.hpp"
 
 #include <map>
 
@@ -173,6 +174,12 @@ struct Renderer::Impl
     DenoiseWork             denoiseWork;
     bool                    denoisedValid = false;
     uint32_t                denoisedSamples = 0;
+    // radiance second moments (rf_renderer_set_moments; off by default: nothing below is allocated or launched then).  One compact tile-major float4 buffer of
+    // {sum r r per channel, 0} in sample order, over the momentSamples samples traced since it was last cleared -- on the image's events and when the switch changes
+    bool                    momentsOn = false, momentsDirty = true;
+    uint32_t                momentSamples = 0;
+    DeviceBuffer<float4>    moments;
+    NoiseWork               noiseWork; // the estimate's device buffers, allocated by the first rf_renderer_noise_estimate
 
     uint64_t                validPixels = 0;     // pixels of this rank's tiles that lie inside the frame
     unsigned long long      primaryRaysHost = 0; // samples traced x validPixels since the last resetStats()
@@ -384,6 +391,7 @@ struct Renderer::Impl
         accumulated = 0;
         imageDirty = true;
         clearAovs();
+        clearMoments();
     }
 
     // the AOV sums start again (with the image, or when the flags change): zeroed before the next sample, sized for the shard then
@@ -392,6 +400,13 @@ struct Renderer::Impl
         aovSamples = 0;
         aovDirty = true;
         denoisedValid = false;
+    }
+
+    // the second moments start again (with the image, or when the switch changes): zeroed before the next sample, sized for the shard then
+    void clearMoments()
+    {
+        momentSamples = 0;
+        momentsDirty = true;
     }
 
     template<typename F>
@@ -901,6 +916,16 @@ struct Renderer::Impl
                     hipLaunchKernelGGL(accumulateAovKernel(false), dim3((fp.pixelsPadded + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, fp, tileIds.ptr, sAov.ptr,
                                        aovAlbedoCoverage.ptr, aovNormalDepth.ptr);
             }
+            // the radiance second moments, over the same stream in the same sample order (timed with the accumulation as well)
+            if (momentsOn)
+            {
+                if (fp.slotGroupShift == 0u && numSamples > 4u && optAccumulateRuns)
+                    hipLaunchKernelGGL(accumulateMomentsKernel(true), dim3((fp.pixelsPadded + kMomentPixels - 1) / kMomentPixels), dim3(64), 0, stream, fp, tileIds.ptr,
+                                       static_cast<const float4*>(ps.rad), moments.ptr);
+                else
+                    hipLaunchKernelGGL(accumulateMomentsKernel(false), dim3((fp.pixelsPadded + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, fp, tileIds.ptr,
+                                       static_cast<const float4*>(ps.rad), moments.ptr);
+            }
         });
         RF_HIP(hipGetLastError());
         RF_HIP(hipEventRecord(bt.stop, stream));
@@ -1224,6 +1249,7 @@ void Renderer::setRenderParameters(const RenderParameters& p)
     m.accumulated = 0;
     m.imageDirty = true;
     m.clearAovs();
+    m.clearMoments();
     if (resized) m.configureShard();
 }
 
@@ -1272,6 +1298,16 @@ void Renderer::render(uint32_t numFrames)
             RF_HIP(hipMemsetAsync(m.aovNormalDepth.ptr, 0, pixelsPadded * sizeof(float4), m.stream));
             m.aovDirty = false;
         }
+        if (m.momentsOn && m.momentsDirty)
+        {
+            if (m.moments.count < pixelsPadded)
+            {
+                RF_HIP(hipStreamSynchronize(m.stream)); // (a smaller buffer may still be read by the last estimate)
+                m.moments.alloc(pixelsPadded);
+            }
+            RF_HIP(hipMemsetAsync(m.moments.ptr, 0, pixelsPadded * sizeof(float4), m.stream));
+            m.momentsDirty = false;
+        }
         // equal batches (320 samples with room for 256 per batch -> 160 + 160, not 256 + 64): a small trailing batch has
         // short launches and, with few samples per pixel, less coherent waves
         // m.maxPaths is the CONFIGURED depth (the default or the caller's) and is never changed here: what a call has to give up
@@ -1314,6 +1350,7 @@ void Renderer::render(uint32_t numFrames)
         m.frameCount += n;
         m.accumulated += n;
         if (m.aovFlags != 0u) m.aovSamples += n;
+        if (m.momentsOn) m.momentSamples += n;
         remaining -= n;
     }
 }
@@ -1427,6 +1464,80 @@ void Renderer::readDenoised(float* rgba, uint32_t* bgra8, uint32_t* sampleCount)
     if (sampleCount) *sampleCount = m.denoisedSamples;
 }
 
+void Renderer::setMoments(bool enabled)
+{
+    Impl& m = *mImpl;
+    if (enabled == m.momentsOn) return;
+    RF_HIP(hipSetDevice(m.device));
+    RF_HIP(hipStreamSynchronize(m.stream)); // (a batch in flight may still write the sums)
+    m.momentsOn = enabled;
+    m.clearMoments();
+    if (!enabled)
+    {
+        // off: nothing of the moments stays allocated
+        m.moments.release();
+        m.noiseWork.release();
+    }
+}
+
+bool Renderer::momentsEnabled() const { return mImpl->momentsOn; }
+
+void Renderer::readMoments(float* sumSq, uint32_t* sampleCount)
+{
+    Impl& m = *mImpl;
+    synchronize();
+    const size_t pixelsPadded = m.tiles.size() * 1024;
+    const bool   empty = !m.momentsOn || m.momentsDirty || m.momentSamples == 0u;
+    if (sumSq)
+    {
+        std::memset(sumSq, 0, static_cast<size_t>(m.params.width) * m.params.height * 4 * sizeof(float));
+        if (!empty && pixelsPadded != 0)
+        {
+            std::vector<float> compact(pixelsPadded * 4);
+            RF_HIP(hipMemcpy(compact.data(), m.moments.ptr, pixelsPadded * sizeof(float4), hipMemcpyDeviceToHost));
+            untileHost(compact.data(), m.tiles.data(), static_cast<uint32_t>(m.tiles.size()), m.params.width, m.params.height, sumSq);
+        }
+    }
+    if (sampleCount) *sampleCount = empty ? 0u : m.momentSamples;
+}
+
+NoiseEstimate Renderer::noiseEstimate(float* errorMap, float* tileSum, float* tileMax)
+{
+    Impl& m = *mImpl;
+    if (!m.momentsOn) throw std::invalid_argument("the noise estimate needs the radiance second moments: turn them on (rf_renderer_set_moments) before the first sample");
+    if (m.worldSize != 1u) throw std::invalid_argument("the noise estimate needs the whole frame: a tile shard is set (use rf_noise_estimate_images on the ranks' sums)");
+    if (m.imageDirty || m.momentsDirty || m.momentSamples != m.accumulated)
+        throw std::invalid_argument("noise estimate: the moment sample count (" + std::to_string(m.momentsDirty ? 0u : m.momentSamples) + ") differs from the accumulated sample count (" +
+                                    std::to_string(m.imageDirty ? 0u : m.accumulated) + "): turn the moments on before the first sample");
+    if (m.accumulated < 2u) throw std::invalid_argument("noise estimate: a variance needs at least 2 accumulated samples");
+    RF_HIP(hipSetDevice(m.device));
+    return runNoiseEstimate(m.stream, m.noiseWork, m.image, m.moments.ptr, m.params.width, m.params.height, true, m.accumulated, errorMap, tileSum, tileMax);
+}
+
+uint32_t Renderer::renderUntil(float targetMeanError, uint32_t checkEvery, uint32_t maxFrames, NoiseEstimate* last)
+{
+    Impl& m = *mImpl;
+    if (!m.momentsOn) throw std::invalid_argument("render_until needs the radiance second moments: turn them on (rf_renderer_set_moments) before the first sample");
+    if (m.worldSize != 1u) throw std::invalid_argument("render_until needs the whole frame: a tile shard is set");
+    if (checkEvery == 0u) throw std::invalid_argument("render_until: check_every must be >= 1");
+    if (m.accumulated != 0u && (m.momentsDirty || m.momentSamples != m.accumulated))
+        throw std::invalid_argument("render_until: the moments do not cover the accumulation (turned on partway through): restart the accumulation first");
+    const uint32_t spp = m.params.samplingParams.numSamplesPerPixel;
+    NoiseEstimate  estimate;
+    uint32_t       frames = 0;
+    while (frames < maxFrames && m.accumulated < spp)
+    {
+        const uint32_t n = std::min({checkEvery, maxFrames - frames, spp - m.accumulated});
+        render(n);
+        frames += n;
+        if (m.accumulated < 2u) continue;
+        estimate = noiseEstimate(nullptr, nullptr, nullptr);
+        if (estimate.meanError <= static_cast<double>(targetMeanError)) break;
+    }
+    if (last) *last = estimate;
+    return frames;
+}
+
 void*    Renderer::accumulationDevicePointer() const { return mImpl->image; }
 
 void Renderer::clearAccumulationIfStale()
@@ -1492,6 +1603,7 @@ void Renderer::bindAccumulationBuffer(void* devicePtr, uint64_t bytes)
     m.accumulated = 0;
     m.imageDirty = true;
     m.clearAovs();
+    m.clearMoments();
 }
 
 void Renderer::readTonemapped(uint32_t* dst)

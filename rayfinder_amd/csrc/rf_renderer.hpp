@@ -111,6 +111,20 @@ struct DenoiseParameters
 void denoiseImages(int deviceOrdinal, uint32_t width, uint32_t height, uint32_t samples, const float* colorSum, const float* albedoCoverage, const float* normalDepth,
                    const DenoiseParameters& params, float exposure, float* outRgba, uint32_t* outBgra8);
 
+// The noise estimate over the accumulation and the radiance second moments (rf_noise.hip; the definition: include/rayfinder_amd.h)
+struct NoiseEstimate
+{
+    double   meanError = 0.0;
+    float    maxError = 0.0f;
+    uint32_t worstTile = 0, samples = 0;
+    uint64_t pixels = 0, nonfinitePixels = 0;
+};
+// The estimate over host-assembled row-major width*height*4 sums (the accumulation and the second moments) of `samples` >= 2 samples, on device `deviceOrdinal`:
+// errorMap (width * height), tileSum, tileMax (one entry per tile of the 32 x 32 grid) are host pointers, NULL = skip.  Synchronous; allocates and frees its own
+// device memory.
+NoiseEstimate noiseEstimateImages(int deviceOrdinal, uint32_t width, uint32_t height, uint32_t samples, const float* colorSum, const float* sumSq, float* errorMap,
+                                  float* tileSum, float* tileMax);
+
 class Renderer
 {
 public:
@@ -152,6 +166,19 @@ public:
     // snapshot's sample count; std::invalid_argument without a snapshot (none yet, or cleared with the AOV sums).
     void denoise(const DenoiseParameters& params);
     void readDenoised(float* rgba, uint32_t* bgra8, uint32_t* sampleCount);
+    // Radiance second moments (rf_renderer_set_moments / rf_renderer_read_moments): off by default.  While on, one more compact tile-major float4 buffer holds
+    // {sum r.x r.x, sum r.y r.y, sum r.z r.z, 0} over the samples traced since it was last cleared (with the image, or when the switch changes), in sample order.
+    // Read: row-major width*height*4 floats (this rank's pixels; NULL = skip) and the moment sample count.
+    void     setMoments(bool enabled);
+    bool     momentsEnabled() const;
+    void     readMoments(float* sumSq, uint32_t* sampleCount);
+    // The noise estimate over the handle's own sums (rf_renderer_noise_estimate): enqueued on the handle's stream, then waited for.  std::invalid_argument when the
+    // moments are off, their count differs from the accumulated count, fewer than 2 samples are accumulated or a tile shard is set.  Host pointers, NULL = skip.
+    NoiseEstimate noiseEstimate(float* errorMap, float* tileSum, float* tileMax);
+    // render() in steps of checkEvery frames with an estimate after each step (once 2 samples are accumulated), until the mean error is <= target, maxFrames frames
+    // have been rendered or the accumulation is full.  -> frames rendered; *last: the last estimate (samples = 0: none was made).  Needs the moments on (covering
+    // the whole accumulation), no tile shard and checkEvery >= 1.
+    uint32_t renderUntil(float targetMeanError, uint32_t checkEvery, uint32_t maxFrames, NoiseEstimate* last);
     // Device pointer of the compact tile-major accumulation buffer (numTiles*1024 float4) and a
     // way to render into caller-owned device memory (e.g. a torch tensor used for the RCCL gather).
     void*    accumulationDevicePointer() const;

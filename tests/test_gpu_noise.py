@@ -1,0 +1,339 @@
+"""Radiance second moments, the noise estimate and render-to-a-noise-target on the GPU (-m gpu): the sums kAccumulateMoments / kAccumulateMomentsRuns keep and
+every output of kNoiseEstimate are bit-identical to the numpy restatement (tests/noise_restatement.py) fed with the oracle's per-sample radiance, leave the image
+and the ray counts alone, do not depend on any scheduling choice, and follow the bookkeeping include/rayfinder_amd.h states."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import rayfinder_amd as rf
+from conftest import ROOT, bits, oracle_scene_from_pt
+from noise_restatement import estimate, moment_sums, oracle_samples, same_estimate
+from oracle import orc
+
+pytestmark = pytest.mark.gpu
+INVALID = rf._ffi.RF_ERROR_INVALID_ARGUMENT
+
+
+def _renderer(pt, w, h, spp, bounces, cam=None, **kw):
+    cam = cam if cam is not None else rf.fly_camera(w, h)
+    params = rf.make_render_parameters(w, h, cam, spp, bounces, rf.make_sky(), 0.25)
+    return rf.ReferencePathTracer(params, pt.scene(), **kw), params
+
+
+def _rp(params):
+    return orc.make_render_params(params.width, params.height, rf.camera_to_array(params.camera), params.num_samples_per_pixel, params.num_bounces, 0.25,
+                                  rf.aligned_sky_state(params.sky))
+
+
+def _same(a, b):
+    return np.array_equal(bits(a[0]), bits(b[0])) and a[1] == b[1]
+
+
+def _refused(call):
+    with pytest.raises(rf.RayfinderError) as err:
+        call()
+    return err.value.status == INVALID
+
+
+@pytest.fixture(scope="module")
+def atrium():
+    from rayfinder_amd import scenes
+    pt, _ = scenes.atrium()
+    return pt
+
+
+@pytest.mark.parametrize("aperture", [0.0, 0.15])
+def test_duck_moments_bit_identical_to_the_restatement(duck_pt, aperture):
+    W, H, spp = 64, 48, 16
+    cam = rf.fly_camera(W, H, aperture=aperture, focus_distance=2.0) if aperture else rf.fly_camera(W, H)
+    r, params = _renderer(duck_pt, W, H, spp, 3, cam=cam)
+    r.set_moments(True)
+    r.render(spp)
+    q, n = r.read_moments()
+    img, acc = r.read_accumulation()
+    r.close()
+    assert n == spp and acc == spp
+    sc, _ = oracle_scene_from_pt(duck_pt)
+    samples = list(oracle_samples(orc, sc, _rp(params), range(spp)))
+    s = np.zeros((H, W, 4), np.float32)
+    for one in samples:
+        s = s + one
+    assert np.array_equal(bits(img[..., :3]), bits(s[..., :3])), "the per-sample radiance sums to the accumulation"
+    want = moment_sums(samples)
+    assert want[..., :3].any() and np.array_equal(bits(q), bits(want))
+
+
+def test_atrium_1080p_one_batch_crops_and_the_image_is_unchanged(atrium):
+    """32 spp of a 1080p frame in ONE batch: the LDS-staged kernel (pixel-major slots, permuted samples); three 32x32 crops bit-identical to the restatement.
+    The same frame with the moments off: the same image and the same ray counts, bit for bit."""
+    W, H, spp, bounces = 1920, 1080, 32, 2
+    tiles = ((W + 31) // 32) * ((H + 31) // 32)
+    out = {}
+    for on in (True, False):
+        r, params = _renderer(atrium, W, H, spp, bounces, max_paths_in_flight=spp * tiles * 1024)
+        if on:
+            r.set_moments(True)
+        r.render(spp)
+        img, acc = r.read_accumulation()
+        s = r.stats()
+        assert acc == spp and s["batches_traced"] == 1
+        out[on] = (img, {k: s[k] for k in ("primary_rays", "closest_rays", "shadow_rays", "shadow_rays_self_answered")}, r.read_moments() if on else None)
+        r.close()
+    assert np.array_equal(bits(out[True][0]), bits(out[False][0]))
+    assert out[True][1] == out[False][1]
+    q, n = out[True][2]
+    assert n == spp
+    sc, _ = oracle_scene_from_pt(atrium)
+    rp = _rp(params)
+    for (x0, y0) in [(928, 508), (64, 64), (1500, 300)]:
+        want = moment_sums(oracle_samples(orc, sc, rp, range(spp), x0, y0, x0 + 32, y0 + 32))
+        assert want[..., :3].any()
+        assert np.array_equal(bits(q[y0:y0 + 32, x0:x0 + 32]), bits(want)), (x0, y0)
+
+
+def test_batching_slot_orders_and_kernels_are_invisible_to_the_moments(duck_pt):
+    W, H, spp, bounces = 150, 90, 16, 3
+    tiles = ((W + 31) // 32) * ((H + 31) // 32)
+
+    def run(opts=(), max_paths=0, steps=(spp,), expect_batches=None):
+        r, _ = _renderer(duck_pt, W, H, spp, bounces, max_paths_in_flight=max_paths)
+        for k, v in dict(opts).items():
+            r.set_option(k, v)
+        r.set_moments(True)
+        for n in steps:
+            r.render(n)
+        got = r.read_moments()
+        if expect_batches is not None:
+            assert expect_batches(r.stats()["batches_traced"])
+        r.close()
+        return got
+
+    want = run(expect_batches=lambda b: b == 1)
+    assert want[1] == spp and want[0][..., :3].any()
+    assert _same(run(max_paths=5 * tiles * 1024, expect_batches=lambda b: b > 1), want), "shallow batches"
+    assert _same(run(max_paths=tiles * 1024, expect_batches=lambda b: b == spp), want), "one sample per batch"
+    assert _same(run(steps=(5, 11)), want), "render(5); render(11)"
+    for opts in (dict(slot_group_shift=-1), dict(slot_group_shift=2), dict(slot_group_shift=6, sample_sort=0), dict(slot_group_shift=10, accumulate_runs=0),
+                 dict(sample_sort=0), dict(accumulate_runs=0), dict(reserve_samples=4)):
+        for max_paths in (0, 5 * tiles * 1024):
+            assert _same(run(opts, max_paths=max_paths), want), (opts, max_paths)
+
+
+def test_moment_bookkeeping_and_shards(duck_pt):
+    W, H, spp = 64, 48, 12
+    r, params = _renderer(duck_pt, W, H, spp, 2)
+    sc, _ = oracle_scene_from_pt(duck_pt)
+    rp = _rp(params)
+    # off by default: nothing to read, and the estimate is refused
+    r.render(5)
+    q, n = r.read_moments()
+    assert n == 0 and not q.any()
+    assert _refused(r.noise_estimate)
+    mem_off = r.memory_info()
+    # on after 5 frames: the sums cover frames 5.. only; the count stays below the accumulated count and the estimate is refused
+    r.set_moments(True)
+    r.render(4)
+    q, n = r.read_moments()
+    assert n == 4 and r.read_accumulation()[1] == 9
+    assert np.array_equal(bits(q), bits(moment_sums(oracle_samples(orc, sc, rp, range(5, 9)))))
+    assert _refused(r.noise_estimate)
+    assert _refused(lambda: r.render_until(0.0, 1, 1))
+    assert r.memory_info() == mem_off                                    # nothing per path slot
+    # set_render_parameters with a change clears
+    r.set_render_parameters(rf.make_render_parameters(W, H, params.camera, spp, 2, params.sky, 0.5))
+    q, n = r.read_moments()
+    assert n == 0 and not q.any()
+    r.render(3)
+    assert r.read_moments()[1] == 3 and r.noise_estimate()["samples"] == 3
+    # the switch clears, both ways
+    r.set_moments(False)
+    q, n = r.read_moments()
+    assert n == 0 and not q.any()
+    r.set_moments(True)
+    assert r.read_moments()[1] == 0
+    r.render(2)
+    assert r.read_moments()[1] == 2 and r.read_accumulation()[1] == 5
+    # a new shard clears; the estimate and render_until are refused while one is set
+    r.set_tile_shard(0, 2)
+    q, n = r.read_moments()
+    assert n == 0 and not q.any()
+    r.render(4)
+    assert r.read_moments()[1] == 4
+    assert _refused(r.noise_estimate)
+    assert _refused(lambda: r.render_until(0.5, 2, 4))
+    r.close()
+
+    def run(shard=None):
+        h, _ = _renderer(duck_pt, W, H, spp, 2)
+        if shard is not None:
+            h.set_tile_shard(*shard)
+        h.set_moments(True)
+        h.render(spp)
+        got = h.read_moments()
+        h.close()
+        return got
+
+    want = run()
+    assert want[1] == spp
+    for world in (2, 3):
+        union = np.zeros_like(want[0])
+        covered = np.zeros((H, W), np.int32)
+        for rank in range(world):
+            part, n = run((rank, world))
+            assert n == spp
+            union += part
+            covered += part[..., :3].any(-1)
+        assert covered.max() == 1                                        # the ranks' pixels are disjoint
+        assert np.array_equal(bits(union), bits(want[0])), world
+
+
+def _check_estimate(r, W, H, spp):
+    img, acc = r.read_accumulation()
+    q, n = r.read_moments()
+    assert acc == spp and n == spp
+    want = estimate(img, q, spp)
+    got = r.noise_estimate()
+    assert same_estimate(got, want) == []
+    assert got["pixels"] == W * H and got["mean_error"] > 0 and got["error_map"].any()
+    assert same_estimate(rf.noise_estimate_images(img, q, spp), want) == []
+    # and it leaves everything else alone
+    img2, acc2 = r.read_accumulation()
+    assert acc2 == acc and np.array_equal(bits(img2), bits(img)) and _same(r.read_moments(), (q, n))
+    return got
+
+
+def test_estimate_bit_identical_to_the_restatement_on_duck_and_atrium(duck_pt, atrium):
+    for pt, W, H, spp, bounces in ((duck_pt, 64, 48, 16, 3), (atrium, 150, 80, 8, 2)):       # ragged tiles: 48 = 32 + 16; 150 = 4 x 32 + 22, 80 = 2 x 32 + 16
+        r, _ = _renderer(pt, W, H, spp, bounces)
+        r.set_moments(True)
+        r.set_counting(True)
+        r.render(spp)
+        before = r.stats()
+        _check_estimate(r, W, H, spp)
+        assert r.stats() == before                                      # the stats are untouched
+        r.close()
+
+
+def test_estimate_of_crafted_sums_matches_the_restatement():
+    W, H, N = 40, 33, 4
+    S = np.full((H, W, 4), 4.0, np.float32)
+    Q = np.full((H, W, 4), 8.0, np.float32)
+    rng = np.random.default_rng(3)
+    S[..., :3] *= rng.uniform(0.5, 2.0, (H, W, 3)).astype(np.float32)
+    S[0, 0, 0] = np.nan
+    Q[1, 1, 1] = np.inf
+    S[2, 2, :3] = np.inf
+    S[32, 39, 2] = -np.inf
+    S[3, 3, :3] = 0.0
+    Q[3, 3, :3] = 0.0                                # all-zero pixel
+    Q[4, 4, :3] = 1.0                                # negative variance
+    S[5, 5, :3] = -4.0                               # a negative level: a negative error (finite: it is summed as it is)
+    Q[6, 6, 0] = np.nan                              # a NaN second moment: that channel's v is 0 (v > 0 is false), the pixel stays finite
+    want = estimate(S, Q, N)
+    assert want["nonfinite_pixels"] == 2             # the NaN sum and the inf second moment
+    got = rf.noise_estimate_images(S, Q, N)
+    assert same_estimate(got, want) == []
+    assert got["error_map"][0, 0] == 0 and got["error_map"][1, 1] == 0 and got["error_map"][6, 6] > 0 and got["error_map"][5, 5] < 0
+
+
+def test_the_mean_error_falls_as_samples_accumulate(duck_pt):
+    W, H = 64, 48
+    errors = {}
+    for spp in (4, 16, 64):
+        r, _ = _renderer(duck_pt, W, H, spp, 3)
+        r.set_moments(True)
+        r.render(spp)
+        errors[spp] = r.noise_estimate()["mean_error"]
+        r.close()
+    print("mean_error at 4 / 16 / 64 spp:", errors)
+    assert errors[64] < errors[16] < errors[4]
+
+
+def test_render_until_stops_at_the_first_check_under_the_target(duck_pt):
+    W, H, spp, bounces, every = 64, 48, 64, 3, 8
+    # replay: the estimates a run checked every 8 samples sees
+    r, _ = _renderer(duck_pt, W, H, spp, bounces)
+    r.set_moments(True)
+    replay = {}
+    for k in range(every, 32 + 1, every):
+        r.render(every)
+        replay[k] = r.noise_estimate()["mean_error"]
+    r.close()
+    assert replay[32] < replay[8]
+    target = 0.5 * (replay[8] + replay[32])
+    stop = next(k for k in sorted(replay) if replay[k] <= np.float32(target))
+    assert stop > every and replay[stop - every] > np.float32(target)     # the check before it was above the target
+
+    r, _ = _renderer(duck_pt, W, H, spp, bounces)
+    r.set_moments(True)
+    frames, last = r.render_until(target, every)
+    assert frames == stop and last["samples"] == stop and last["mean_error"] == replay[stop]
+    img, acc = r.read_accumulation()
+    assert acc == stop
+    # max_frames stops it (a target of 0 is never met): 8 + 4 frames, estimated at 12
+    r.set_render_parameters(rf.make_render_parameters(W, H, rf.fly_camera(W, H), spp, bounces, rf.make_sky(), 0.5))
+    frames, last = r.render_until(0.0, every, 12)
+    assert frames == 12 and last["samples"] == 12 and r.read_accumulation()[1] == 12
+    frames, last = r.render_until(0.0, every, 1)
+    assert frames == 1 and last["samples"] == 13
+    r.close()
+    fresh, _ = _renderer(duck_pt, W, H, spp, bounces)
+    fresh.render(stop)
+    assert np.array_equal(bits(fresh.read_accumulation()[0]), bits(img))
+    fresh.close()
+    # the spp cap stops it, and a single sample makes no estimate
+    r, _ = _renderer(duck_pt, W, H, 10, bounces)
+    r.set_moments(True)
+    frames, last = r.render_until(0.0, 1, 1)
+    assert frames == 1 and last is None
+    frames, last = r.render_until(0.0, 4)
+    assert frames == 9 and last["samples"] == 10 and r.read_accumulation()[1] == 10
+    assert r.render_until(0.0, 4) == (0, None)
+    r.close()
+    # refused with the moments off or a shard set, and with check_every 0
+    r, _ = _renderer(duck_pt, W, H, spp, bounces)
+    assert _refused(lambda: r.render_until(0.5, every))
+    r.set_moments(True)
+    assert _refused(lambda: r.render_until(0.5, 0))
+    r.set_tile_shard(1, 2)
+    assert _refused(lambda: r.render_until(0.5, every))
+    assert r.read_accumulation()[1] == 0
+    r.close()
+
+
+def _read_pfm(path):
+    data = open(path, "rb").read()
+    parts = data.split(b"\n", 3)
+    kind, (w, h) = parts[0], map(int, parts[1].split())
+    assert kind == b"Pf" and parts[2] == b"-1.0"
+    return np.frombuffer(parts[3], "<f4").reshape(h, w)[::-1]
+
+
+def test_rf_render_noise_map_equals_the_api_and_does_not_depend_on_the_rank_count(duck_pt, tmp_path):
+    scene = tmp_path / "Duck.pt"
+    duck_pt.save(scene)
+    exe = os.path.join(ROOT, "rayfinder_amd", "bin", "rf-render")
+    W, H, spp, bounces = 200, 150, 8, 3
+    env = dict(os.environ, RF_COMM_TRANSPORT="local", RF_COMM_TIMEOUT_S="120")
+    base = [exe, str(scene), "--width", str(W), "--height", str(H), "--spp", str(spp), "--bounces", str(bounces)]
+    files = {}
+    for gpus in (1, 2):
+        name = tmp_path / f"g{gpus}_noise.pfm"
+        txt = subprocess.check_output(base + ["--out", str(tmp_path / f"g{gpus}.png"), "--noise-map", str(name), "--gpus", str(gpus)], env=env, timeout=300).decode()
+        assert f"on {gpus} GPU(s)" in txt and f"noise at {spp} spp" in txt
+        files[gpus] = open(name, "rb").read()
+    assert files[2] == files[1]
+    r, _ = _renderer(duck_pt, W, H, spp, bounces)          # rf-render's defaults: fly camera, default sky
+    r.set_moments(True)
+    r.render(spp)
+    want = r.noise_estimate()
+    r.close()
+    assert np.array_equal(bits(_read_pfm(tmp_path / "g1_noise.pfm")), bits(want["error_map"]))
+    # --noise-target: stops early and says where; refused with several ranks
+    txt = subprocess.check_output(base + ["--spp", "64", "--out", str(tmp_path / "t.png"), "--noise-target", str(2.0 * want["mean_error"]), "--noise-check-every", "4"],
+                                  env=env, timeout=300).decode()
+    assert "stopped at 4 of 64 spp" in txt or "stopped at 8 of 64 spp" in txt, txt
+    bad = subprocess.run(base + ["--out", str(tmp_path / "b.png"), "--noise-target", "0.1", "--gpus", "2"], env=env, capture_output=True, timeout=300)
+    assert bad.returncode != 0 and b"--noise-target needs --gpus 1" in bad.stderr
