@@ -405,3 +405,17 @@ def tonemap(image, acc, exposure):
     out = np.zeros((img.shape[0], 3), np.float32)
     lib().orc_tonemap(_p(img), img.shape[0], acc, np.float32(exposure), _p(out))
     return out
+
+
+def quantise_unorm8(srgb):
+    """The swap chain's BGRA8Unorm store of a value in [0, 1]: floor(x * 255 + 0.5) in f32.  Documented choice: NaN -> level 0
+    (what the device's float -> u32 conversion gives; numpy's astype of a NaN is not defined)."""
+    with np.errstate(invalid="ignore"):
+        q = np.floor(f32(srgb) * np.float32(255.0) + np.float32(0.5))
+    return np.where(np.isnan(q), np.float32(0.0), q).astype(np.uint32)
+
+
+def tonemap_bgra8(image, acc, exposure):
+    """tonemap() quantised and packed like kTonemap's output: (n,) u32, B | G << 8 | R << 16 | 255 << 24."""
+    q = quantise_unorm8(tonemap(image, acc, exposure))
+    return q[:, 2] | (q[:, 1] << np.uint32(8)) | (q[:, 0] << np.uint32(16)) | np.uint32(255 << 24)

@@ -983,13 +983,21 @@ ORC_API float orc_wgsl_sky_radiance(const float* sky40, float theta, float gamma
     return sky_radiance(sky40, theta, gamma, channel);
 }
 
+/* u32(e) of wgsl:557-558 for e = fract(uv) * size, which is in [0, size] or NaN.  A C cast of a NaN is undefined
+ * behaviour; the choice is stated here instead: NaN -> 0. */
+static inline uint32_t texel_coord(float e) { return (e != e) ? 0u : (uint32_t)e; }
+
 static v3 texture_lookup(const OrcScene* sc, uint32_t descIdx, float uvx, float uvy, OrcStats* st)
-{ /* wgsl:303-307, 552-565.  Out-of-range texel index (fract()*w rounding up to w on the last
-   * row): WGSL robust buffer access clamps the index into the array -- documented choice. */
+{ /* wgsl:303-307, 552-565.  Two documented choices:
+   *  - out-of-range texel index (fract()*w rounding up to w on the last row): WGSL robust buffer access clamps the
+   *    index into the array.  (The same rounding on any other row reads the first texel of the next row, and on the
+   *    last row of a texture that is not the last one the first texel of the next texture: plain index arithmetic.)
+   *  - a NaN or infinite uv (fract(inf) = inf - inf = NaN) reads texel (0,0) of its texture: u32(NaN) = 0, which is
+   *    what the device's float -> u32 conversion gives. */
     const OrcTextureDescriptor d = sc->texDescs[descIdx];
     const float u = W_FRACT(uvx), v = W_FRACT(uvy);
-    const uint32_t j = (uint32_t)(u * (float)d.width);
-    const uint32_t i = (uint32_t)(v * (float)d.height);
+    const uint32_t j = texel_coord(u * (float)d.width);
+    const uint32_t i = texel_coord(v * (float)d.height);
     uint64_t idx = (uint64_t)d.offset + (uint64_t)(i * d.width + j);
     if (idx >= sc->numTexels) { idx = sc->numTexels - 1; if (st) st->texelOobClamps++; }
     const uint32_t bgra = sc->texels[idx];

@@ -421,7 +421,10 @@ __device__ __forceinline__ float skyRadiance(const SkyStateGpu& sky, float cosTh
 }
 
 // wgsl:303-307,552-565.  An index past the end of the texel array (fract()*w rounding up on the
-// last row of the last texture) is clamped into the array, as WGSL robust buffer access does.
+// last row of the last texture) is clamped into the array, as WGSL robust buffer access does.  (The same rounding on another
+// row reads the first texel of the next row; on the last row of a texture that is not the last, the first texel of the next texture.)
+// A NaN or infinite uv (fract(inf) = inf - inf = NaN) reads texel (0,0) of its texture: the float -> u32 conversion of a NaN is 0 here
+// (v_cvt_u32_f32), the documented choice next to the clamp; tests/test_gpu_shade_edges.py holds the kernels to it.
 // `lut`: the 256-entry sRGB -> linear table, in LDS in kShade (three look-ups per hit that then bypass the vector L1)
 __device__ __forceinline__ Vec3 evalTexture(const DeviceScene& scene, const float* lut, uint32_t descriptorIdx, float uvx, float uvy)
 {
