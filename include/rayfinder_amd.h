@@ -287,6 +287,63 @@ RF_API int rf_noise_estimate_images(int32_t device_ordinal, uint32_t width, uint
 RF_API int rf_renderer_render_until(rf_renderer* r, float target_mean_error, uint32_t check_every, uint32_t max_frames, uint32_t* frames_rendered,
                                     rf_noise_estimate* last);
 
+/* Tile-adaptive sampling: a render call that keeps sampling only the 32x32 tiles that are still noisy, and the per-tile sample count that the reads then honour.
+ * No reference counterpart.  Whole frame only (no tile shard); needs the moments on from the first sample and the AOVs off.
+ *
+ * The handle keeps one more word per tile, tile_samples[t], t in the estimate's tile numbering (tile_y * ceil(width / 32) + tile_x).  rf_renderer_render(n) adds n to
+ * every tile (min(n, samples left), as it does to the accumulated count); the counts are cleared, to 0, whenever the image is.  L, the LEADING count, is the
+ * accumulated sample count (0 at the start); no tile ever holds more.
+ *
+ * rf_renderer_render_adaptive(r, params, result).  cap = params->max_samples, where 0 means num_samples_per_pixel and a larger value is clamped to it.  The loop:
+ *   1. the ACTIVE tiles are those with tile_samples[t] == L;
+ *   2. n = min(check_every, cap - L) more samples of the active tiles only are traced and added to S and Q -- samples frameCount, frameCount + 1, ..., exactly the
+ *      ones rf_renderer_render would trace next (frameCount is the handle's frame counter, which advances by n) -- and L and the active tiles' counts grow by n;
+ *   3. once L >= max(2, min_samples): the estimate above over the active tiles, Nf = float(L);
+ *   4. an active tile with tile_sum / float(tile_pixels) <= target_tile_error (one f32 division; tile_pixels: its in-frame pixels) STOPS: it keeps its count for the
+ *      rest of the accumulation.  A NaN compares false: such a tile goes on;
+ *   5. repeat from 1 until no tile is active or L == cap.  (An estimate is made after the last step as well.)
+ * All active tiles share one count at all times, and a stopped tile is never sampled again.  The defining property: afterwards, S and Q of every pixel of tile t are bit
+ * for bit what rf_renderer_render(tile_samples[t]) leaves there in a fresh accumulation (with the moments on) -- each pixel's sums are its first tile_samples[t] samples
+ * in sample order -- whatever the batching, the slot order or the options.  rf_stats' primary_rays counts the pixel-samples traced.
+ * A later call, with the same or other parameters, continues with the tiles still at the leading count only (stopped tiles are not revived, the active set is not
+ * dilated to neighbouring tiles, and counts are per tile, not per pixel).  Waits for the work it enqueues.
+ * RF_ERROR_INVALID_ARGUMENT: the moments are off or do not cover the accumulation, the AOVs are on (their sums and rf_denoise_images keep ONE sample count), a tile
+ * shard is set (rf_renderer_gather_frame carries no counts), check_every is 0, or target_tile_error is negative or not finite.
+ * *result (may be NULL): estimate_passes made by this call; tiles and stopped_tiles (tiles below L) of the frame; the minimum and maximum tile count; pixel_samples =
+ * the sum over the tiles of in-frame pixels x tile_samples[t]; last = the estimate of the call's last pass, over the tiles that were active in it (mean_error, max_error,
+ * pixels and nonfinite_pixels over those tiles, worst_tile in the frame's numbering, samples = L at that pass; samples = 0 when the call made no pass).
+ *
+ * While some tile is below L (the NON-UNIFORM state), rf_renderer_render, rf_renderer_render_until, rf_renderer_denoise, rf_renderer_set_tile_shard and
+ * rf_renderer_gather_frame return RF_ERROR_INVALID_ARGUMENT with a message that says so: each of them assumes one count for the frame.
+ * rf_renderer_set_render_parameters (with a change) and a newly bound accumulation buffer clear the counts with the image.  When every tile is at L -- a target of 0 ran
+ * every tile to the cap, a huge target stopped every tile at the first check -- the handle is in the ordinary state and none of them refuses.  In the non-uniform state:
+ *   rf_renderer_read_accumulation, rf_renderer_read_moments: the sums as they are; the count they report is L, and the divisor of a pixel is its tile's own count.
+ *   rf_renderer_read_tile_samples: the counts (tile_samples may be NULL) and ceil(width / 32) * ceil(height / 32).  Uniform state: every tile of the shard at the
+ *       accumulated count, a tile outside the shard 0.
+ *   rf_renderer_read_mean: row-major width*height*4 floats {S.rgb / float(tile_samples[t]), 1}, one f32 division per channel; {0, 0, 0, 1} in a tile without a sample.
+ *       Works in the uniform state too (pixels outside a shard's tiles: four zeros).
+ *   rf_renderer_read_tonemapped: kTonemap over that mean with accumulatedSamples = 1 (rf_renderer_read_denoised's display path; x / 1 is exact, so in the uniform
+ *       state the texels are those of the sums divided by the accumulated count).
+ *   rf_renderer_noise_estimate: Nf = float(tile_samples[t]) for the pixels of tile t (every count is >= 2: a tile stops at an estimate); out->samples = L.
+ * rf_noise_estimate_tiles: rf_noise_estimate_images with one count per tile (tile_samples: ceil(width / 32) * ceil(height / 32) words); out->samples = the largest.
+ * A NULL input or `out`, a zero size and any tile count below 2 are refused before any device call. */
+typedef struct rf_adaptive_parameters
+{
+    float    target_tile_error;
+    uint32_t check_every, min_samples, max_samples;
+} rf_adaptive_parameters;
+typedef struct rf_adaptive_result
+{
+    uint32_t          estimate_passes, tiles, stopped_tiles, min_tile_samples, max_tile_samples, reserved;
+    uint64_t          pixel_samples;
+    rf_noise_estimate last;
+} rf_adaptive_result;
+RF_API int rf_renderer_render_adaptive(rf_renderer* r, const rf_adaptive_parameters* params, rf_adaptive_result* result);
+RF_API int rf_renderer_read_tile_samples(rf_renderer* r, uint32_t* tile_samples, uint32_t* num_tiles);
+RF_API int rf_renderer_read_mean(rf_renderer* r, float* rgba);
+RF_API int rf_noise_estimate_tiles(int32_t device_ordinal, uint32_t width, uint32_t height, const uint32_t* tile_samples, const float* color_sum4, const float* sumsq4,
+                                   rf_noise_estimate* out, float* error_map, float* tile_sum, float* tile_max);
+
 /* Deferred-lighting variant (replaces nlrs::DeferredRenderer's lighting + resolve passes, src/pt/deferred_renderer.hpp,
  * deferred_renderer_lighting_pass.wgsl:96-186 -- fixed 2-bounce surfaceColor, solar disk in the sky term, the
  * 1/16384 + 1024 offset constants :498-500 -- and deferred_renderer_resolve_pass.wgsl:33-54 -- 0.1 / 0.9 exponential

@@ -477,6 +477,23 @@ def noise_estimate_images(color_sum, sumsq, samples, device_ordinal=0):
     return _noise_result(est, emap, tsum, tmax)
 
 
+def noise_estimate_tiles(color_sum, sumsq, tile_samples, device_ordinal=0):
+    """rf_noise_estimate_tiles: noise_estimate_images with one sample count (>= 2) per 32x32 tile, tile_samples in tile order (tile_y * ceil(W / 32) + tile_x).
+    -> the same dict; samples = the largest count."""
+    color_sum, sumsq = _f32(color_sum), _f32(sumsq)
+    h, w = color_sum.shape[:2]
+    if color_sum.shape != (h, w, 4) or sumsq.shape != (h, w, 4):
+        raise ValueError("noise_estimate_tiles: the two sums must be (H, W, 4) arrays of one size")
+    counts = np.ascontiguousarray(tile_samples, np.uint32).reshape(-1)
+    if counts.size != _noise_tiles(w, h):
+        raise ValueError(f"noise_estimate_tiles: {_noise_tiles(w, h)} tile counts expected, got {counts.size}")
+    est = _ffi.NoiseEstimate()
+    emap = np.zeros((h, w), np.float32)
+    tsum = np.zeros(counts.size, np.float32); tmax = np.zeros_like(tsum)
+    check(lib.rf_noise_estimate_tiles(device_ordinal, w, h, _ptr(counts), _ptr(color_sum), _ptr(sumsq), C.byref(est), _ptr(emap), _ptr(tsum), _ptr(tmax)))
+    return _noise_result(est, emap, tsum, tmax)
+
+
 class ReferencePathTracer:
     """Host-side mirror of nlrs::ReferencePathTracer (src/pt/reference_path_tracer.hpp:59-76).
 
@@ -592,6 +609,33 @@ class ReferencePathTracer:
         est = _ffi.NoiseEstimate()
         check(lib.rf_renderer_render_until(self._h, target_mean_error, check_every, max_frames, C.byref(frames), C.byref(est)))
         return frames.value, ({k: getattr(est, k) for k, _ in est._fields_} if est.samples else None)
+
+    # tile-adaptive sampling (include/rayfinder_amd.h states the loop and what the reads return while the tiles hold different counts)
+    def render_adaptive(self, target_tile_error, check_every=8, min_samples=0, max_samples=0):
+        """Keep sampling only the 32x32 tiles whose mean error is above target_tile_error, checking every check_every samples from min_samples on, up to max_samples
+        (0: the frame's samples per pixel).  Needs the moments on from the first sample, the AOVs off and no tile shard.
+        -> dict(estimate_passes, tiles, stopped_tiles, min_tile_samples, max_tile_samples, pixel_samples, last: the last pass's estimate scalars or None)."""
+        p = _ffi.AdaptiveParameters(target_tile_error, check_every, min_samples, max_samples)
+        res = _ffi.AdaptiveResult()
+        check(lib.rf_renderer_render_adaptive(self._h, C.byref(p), C.byref(res)))
+        out = {k: getattr(res, k) for k, _ in res._fields_ if k not in ("reserved", "last")}
+        out["last"] = {k: getattr(res.last, k) for k, _ in res.last._fields_} if res.last.samples else None
+        return out
+
+    def read_tile_samples(self):
+        """-> (tiles_y, tiles_x) u32: the sample count of every 32x32 tile"""
+        h, w = self._params.height, self._params.width
+        counts = np.zeros(((h + TILE - 1) // TILE, (w + TILE - 1) // TILE), np.uint32)
+        n = C.c_uint32(0)
+        check(lib.rf_renderer_read_tile_samples(self._h, _ptr(counts), C.byref(n)))
+        assert n.value == counts.size
+        return counts
+
+    def read_mean(self):
+        """-> (H, W, 4) f32 {sum.rgb / the tile's sample count, 1}"""
+        mean = np.zeros((self._params.height, self._params.width, 4), np.float32)
+        check(lib.rf_renderer_read_mean(self._h, _ptr(mean)))
+        return mean
 
     # deferred-lighting variant (nlrs::DeferredRenderer's lighting + resolve passes over a primary-ray G-buffer)
     def render_deferred(self, num_frames=1):

@@ -48,6 +48,15 @@ class NoiseEstimate(C.Structure):
                 ("nonfinite_pixels", C.c_uint64)]
 
 
+class AdaptiveParameters(C.Structure):
+    _fields_ = [("target_tile_error", C.c_float), ("check_every", C.c_uint32), ("min_samples", C.c_uint32), ("max_samples", C.c_uint32)]
+
+
+class AdaptiveResult(C.Structure):
+    _fields_ = [("estimate_passes", C.c_uint32), ("tiles", C.c_uint32), ("stopped_tiles", C.c_uint32), ("min_tile_samples", C.c_uint32),
+                ("max_tile_samples", C.c_uint32), ("reserved", C.c_uint32), ("pixel_samples", C.c_uint64), ("last", NoiseEstimate)]
+
+
 class Camera(C.Structure):
     _fields_ = [("origin", C.c_float * 3), ("lower_left_corner", C.c_float * 3), ("horizontal", C.c_float * 3),
                 ("vertical", C.c_float * 3), ("up", C.c_float * 3), ("right", C.c_float * 3), ("lens_radius", C.c_float)]
@@ -136,6 +145,10 @@ SIGNATURES = {
     "rf_renderer_noise_estimate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rf_noise_estimate_images": (C.c_int, [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rf_renderer_render_until": (C.c_int, [C.c_void_p, C.c_float, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p]),
+    "rf_renderer_render_adaptive": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rf_renderer_read_tile_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
+    "rf_renderer_read_mean": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rf_noise_estimate_tiles": (C.c_int, [C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rf_renderer_render_deferred": (C.c_int, [C.c_void_p, C.c_uint32]),
     "rf_renderer_reset_deferred": (C.c_int, [C.c_void_p]),
     "rf_renderer_read_deferred": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),

@@ -3,6 +3,7 @@
 //           [--pfm image.pfm] [--aov-albedo a.pfm] [--aov-normal n.pfm] [--aov-depth d.pfm] [--denoise d.png] [--denoise-pfm d.pfm]
 //           [--denoise-iterations L] [--denoise-sigma-color s] [--denoise-sigma-normal s] [--denoise-sigma-depth s]
 //           [--noise-map m.pfm] [--noise-target t] [--noise-check-every k] [--gpus N]
+//           [--adaptive T] [--adaptive-min n] [--adaptive-every n] [--sample-map s.pfm]
 // Offline counterpart of the interactive `pt` app (src/pt/main.cpp): same default camera pose,
 // sky and exposure; renders all samples and writes the tonemapped image (and optionally the
 // mean radiance as PFM).  --gpus N: one host thread per GPU, the image tile-sharded across them, one RCCL
@@ -15,6 +16,9 @@
 // --noise-map: the per-pixel relative standard error of the frame (rf_renderer_noise_estimate's error map, a one-channel PFM) from the radiance second moments
 // (rf_renderer_set_moments, on from the first sample).  With --gpus N > 1 each rank reads its own tiles' moments, the host assembles them, and the estimate runs once,
 // on device 0, over the gathered accumulation (rf_noise_estimate_images): the same map whatever N.
+// --adaptive T [--adaptive-min n] [--adaptive-every n]: tile-adaptive sampling (rf_renderer_render_adaptive): every 32x32 tile is sampled until its mean error is <= T,
+// checked every n samples (default 8) from --adaptive-min samples on, --spp at the latest; the image is the per-tile mean.  --gpus 1, no AOVs / denoiser.
+// --sample-map s.pfm: the sample count of every pixel's tile (a one-channel PFM)
 // --noise-target t [--noise-check-every k]: stop as soon as the frame's mean error is <= t, checked every k samples (default 8), at --spp at the latest
 // (rf_renderer_render_until).  One GPU only: stopping several ranks in step is not implemented.
 #include "cli_common.hpp"
@@ -37,6 +41,9 @@ int main(int argc, char** argv)
                     "                 [--denoise d.png] [--denoise-pfm d.pfm] [--denoise-iterations L] [--denoise-sigma-color s] [--denoise-sigma-normal s]\n"
                     "                 [--denoise-sigma-depth s]\n"
                     "  --denoise / --denoise-pfm: the frame through the edge-aware a-trous denoiser guided by the AOVs (defaults: L 5, sigmas 1, 0.1, 0.1)\n"
+                    "                 [--adaptive T] [--adaptive-min n] [--adaptive-every n] [--sample-map s.pfm]\n"
+                    "  --adaptive: sample every 32x32 tile until its mean error is <= T (checked every n samples, default 8; --spp at the latest); --sample-map: the\n"
+                    "  tiles' sample counts (1-channel PFM)\n"
                     "                 [--noise-map m.pfm] [--noise-target t] [--noise-check-every k]\n"
                     "  --noise-map: the per-pixel relative standard error of the frame (1-channel PFM); --noise-target: stop once the frame's mean error is <= t,\n"
                     "  checked every k samples (default 8), at --spp at the latest (one GPU only)\n");
@@ -54,6 +61,10 @@ int main(int argc, char** argv)
     float       noiseTarget = 0.0f;
     bool        noiseTargetSet = false;
     uint32_t    noiseCheckEvery = 8;
+    std::string sampleMap;
+    bool        adaptive = false;
+    rf_adaptive_parameters adaptiveParams{0.0f, 8u, 0u, 0u};
+    rf_adaptive_result     adaptiveResult{};
     for (int i = 2; i + 1 < argc; i += 2)
     {
         const std::string k = argv[i];
@@ -82,6 +93,10 @@ int main(int argc, char** argv)
         else if (k == "--noise-map") noiseMap = val;
         else if (k == "--noise-target") noiseTarget = static_cast<float>(std::atof(val)), noiseTargetSet = true;
         else if (k == "--noise-check-every") noiseCheckEvery = static_cast<uint32_t>(std::max(1, std::atoi(val)));
+        else if (k == "--adaptive") adaptiveParams.target_tile_error = static_cast<float>(std::atof(val)), adaptive = true;
+        else if (k == "--adaptive-min") adaptiveParams.min_samples = static_cast<uint32_t>(std::max(0, std::atoi(val)));
+        else if (k == "--adaptive-every") adaptiveParams.check_every = static_cast<uint32_t>(std::max(1, std::atoi(val)));
+        else if (k == "--sample-map") sampleMap = val;
         else
         {
             std::fprintf(stderr, "unknown option %s\n", k.c_str());
@@ -91,6 +106,11 @@ int main(int argc, char** argv)
     if (noiseTargetSet && gpus > 1)
     {
         std::fprintf(stderr, "--noise-target needs --gpus 1: stopping several ranks in step at a noise target is not implemented (render a fixed --spp and use --noise-map)\n");
+        return 1;
+    }
+    if (adaptive && (gpus > 1 || noiseTargetSet || denoising || !aovAlbedo.empty() || !aovNormal.empty() || !aovDepth.empty()))
+    {
+        std::fprintf(stderr, "--adaptive needs --gpus 1 and goes with neither --noise-target nor the AOVs / the denoiser (they keep one sample count for the frame)\n");
         return 1;
     }
     rf_pt_format*     pt = loadScene(argv[1]);
@@ -117,7 +137,8 @@ int main(int argc, char** argv)
     std::vector<float>              acc;
     // (the denoiser over several ranks needs the whole accumulation on the host)
     // radiance second moments of the whole frame (every rank copies in the pixels of its own tiles), the error map, and the samples actually rendered
-    const bool         noise = !noiseMap.empty() || noiseTargetSet;
+    const bool         noise = !noiseMap.empty() || noiseTargetSet || adaptive;
+    std::vector<uint32_t> tileSamples;
     std::vector<float> momentsFrame, errorMap;
     rf_noise_estimate  estimate{};
     uint32_t           sppReached = spp;
@@ -151,7 +172,8 @@ int main(int argc, char** argv)
         if (aovs) rfCheck(rf_renderer_set_aovs(renderer, RF_AOV_FIRST_HIT), "AOVs");
         if (noise) rfCheck(rf_renderer_set_moments(renderer, 1), "moments");
         const auto t0 = std::chrono::steady_clock::now();
-        if (noiseTargetSet) rfCheck(rf_renderer_render_until(renderer, noiseTarget, noiseCheckEvery, spp, &sppReached, &estimate), "render to the noise target");
+        if (adaptive) rfCheck(rf_renderer_render_adaptive(renderer, &adaptiveParams, &adaptiveResult), "adaptive render");
+        else if (noiseTargetSet) rfCheck(rf_renderer_render_until(renderer, noiseTarget, noiseCheckEvery, spp, &sppReached, &estimate), "render to the noise target");
         else rfCheck(rf_renderer_render(renderer, spp), "render");
         void* gathered = nullptr;
         if (comm) rfCheck(rf_renderer_gather_frame(renderer, comm, 0, 0, &gathered), "gather");
@@ -209,7 +231,14 @@ int main(int argc, char** argv)
             {
                 rfCheck(rf_renderer_read_tonemapped(renderer, bgra.data()), "tonemap");
                 uint32_t n = 0;
-                if (!acc.empty()) rfCheck(rf_renderer_read_accumulation(renderer, acc.data(), &n), "read accumulation");
+                if (!acc.empty()) rfCheck(adaptive ? rf_renderer_read_mean(renderer, acc.data()) : rf_renderer_read_accumulation(renderer, acc.data(), &n), "read accumulation");
+                if (!sampleMap.empty())
+                {
+                    uint32_t numTiles = 0;
+                    rfCheck(rf_renderer_read_tile_samples(renderer, nullptr, &numTiles), "tile samples");
+                    tileSamples.resize(numTiles);
+                    rfCheck(rf_renderer_read_tile_samples(renderer, tileSamples.data(), &numTiles), "tile samples");
+                }
                 if (denoising)
                 {
                     rfCheck(rf_renderer_denoise(renderer, &denoiseParams), "denoise");
@@ -237,6 +266,10 @@ int main(int argc, char** argv)
                 rays / seconds * 1e-6, closestRays.load(), shadowRays.load());
     if (noiseTargetSet)
         std::printf("noise target %g: stopped at %u of %u spp, mean error %.6g (estimated at %u spp)\n", noiseTarget, sppReached, spp, estimate.mean_error, estimate.samples);
+    if (adaptive)
+        std::printf("adaptive target %g: %u of %u tiles stopped early, %u .. %u spp per tile, %llu of %llu pixel-samples, %u estimate pass(es)\n", adaptiveParams.target_tile_error,
+                    adaptiveResult.stopped_tiles, adaptiveResult.tiles, adaptiveResult.min_tile_samples, adaptiveResult.max_tile_samples,
+                    static_cast<unsigned long long>(adaptiveResult.pixel_samples), static_cast<unsigned long long>(W) * H * spp, adaptiveResult.estimate_passes);
     if (!noiseMap.empty())
         std::printf("noise at %u spp: mean error %.6g, max error %.6g in tile %u, %llu non-finite pixel(s)\n", estimate.samples, estimate.mean_error, estimate.max_error,
                     estimate.worst_tile, static_cast<unsigned long long>(estimate.nonfinite_pixels));
@@ -250,7 +283,7 @@ int main(int argc, char** argv)
         rgba[4 * i + 3] = 255;
     }
     if (!writePngRgba(out, rgba.data(), W, H)) return 1;
-    if (!pfm.empty()) writePfm(pfm, acc.data(), W, H, 1.0f / static_cast<float>(std::max(sppReached, 1u)));
+    if (!pfm.empty()) writePfm(pfm, acc.data(), W, H, adaptive ? 1.0f : 1.0f / static_cast<float>(std::max(sppReached, 1u))); // (--adaptive: acc holds the per-tile mean)
     if (denoising)
     {
         std::vector<uint8_t> d(denoisedBgra.size() * 4);
@@ -281,6 +314,8 @@ int main(int argc, char** argv)
         return true;
     };
     if (!write(noiseMap, 1, [&](size_t i, uint32_t) { return errorMap[i / 4]; })) return 1;
+    if (!sampleMap.empty() && tileSamples.empty()) tileSamples.assign(static_cast<size_t>((W + 31) / 32) * ((H + 31) / 32), sppReached); // (several ranks: one count)
+    if (!write(sampleMap, 1, [&](size_t i, uint32_t) { return static_cast<float>(tileSamples[((i / 4) / W / 32) * ((W + 31) / 32) + ((i / 4) % W) / 32]); })) return 1;
     if (aovs)
     {
         // means (f32 divisions, as ReferencePathTracer.aov_means): albedo / normal over the AOV samples, depth over the coverage

@@ -369,6 +369,54 @@ int rf_renderer_render_until(rf_renderer* r, float target_mean_error, uint32_t c
     });
 }
 
+int rf_renderer_render_adaptive(rf_renderer* r, const rf_adaptive_parameters* params, rf_adaptive_result* result)
+{
+    return guarded([&] {
+        require(r && params, "null argument");
+        const rf::AdaptiveResult a = r->impl->renderAdaptive(rf::AdaptiveParameters{params->target_tile_error, params->check_every, params->min_samples, params->max_samples});
+        if (result)
+            *result = rf_adaptive_result{a.estimatePasses, a.tiles, a.stoppedTiles, a.minTileSamples, a.maxTileSamples, 0u, a.pixelSamples, toNoiseEstimate(a.last)};
+        return RF_OK;
+    });
+}
+
+int rf_renderer_read_tile_samples(rf_renderer* r, uint32_t* tile_samples, uint32_t* num_tiles)
+{
+    return guarded([&] {
+        require(r && num_tiles, "null argument");
+        *num_tiles = r->impl->readTileSamples(tile_samples);
+        return RF_OK;
+    });
+}
+
+int rf_renderer_read_mean(rf_renderer* r, float* rgba)
+{
+    return guarded([&] {
+        require(r && rgba, "null argument");
+        r->impl->readMean(rgba);
+        return RF_OK;
+    });
+}
+
+int rf_noise_estimate_tiles(int32_t device_ordinal, uint32_t width, uint32_t height, const uint32_t* tile_samples, const float* color_sum4, const float* sumsq4,
+                            rf_noise_estimate* out, float* error_map, float* tile_sum, float* tile_max)
+{
+    return guarded([&] {
+        require(tile_samples && color_sum4 && sumsq4 && out, "null argument");
+        require(width > 0 && height > 0, "image size must be non-zero");
+        require(static_cast<uint64_t>(width) * height < (1ull << 31), "image too large");
+        const uint32_t tiles = ((width + 31u) / 32u) * ((height + 31u) / 32u);
+        uint32_t       leading = 0;
+        for (uint32_t t = 0; t < tiles; ++t)
+        {
+            require(tile_samples[t] >= 2, "a variance needs a sample count >= 2 in every tile");
+            leading = tile_samples[t] > leading ? tile_samples[t] : leading;
+        }
+        *out = toNoiseEstimate(rf::noiseEstimateTiles(device_ordinal, width, height, tile_samples, leading, color_sum4, sumsq4, error_map, tile_sum, tile_max));
+        return RF_OK;
+    });
+}
+
 int rf_renderer_set_counting(rf_renderer* r, int enabled)
 {
     return guarded([&] {
@@ -543,6 +591,7 @@ int rf_renderer_gather_frame(rf_renderer* r, rf_comm* c, uint32_t root, uint32_t
                 "the renderer's tile shard differs from the communicator's rank / world size (call rf_renderer_set_tile_shard first)");
         // the exchange is enqueued on the renderer's stream with the communicator's device current: they must be one device
         require(r->impl->deviceOrdinal() == c->impl->deviceOrdinal(), "the renderer and the communicator are on different devices");
+        r->impl->requireUniformTileSamples("rf_renderer_gather_frame"); // (the exchange carries no per-tile counts)
         r->impl->clearAccumulationIfStale(); // nothing rendered since the last reset: send zeros, not the previous frame
         const void* image = c->impl->gatherFrame(r->impl->accumulationDevicePointer(), r->impl->width(), r->impl->height(), root, r->impl->streamHandle(),
                                                  (flags & RF_GATHER_LOOPBACK) != 0);

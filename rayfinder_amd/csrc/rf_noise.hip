@@ -4,6 +4,10 @@
 //   kAccumulateMoments      one lane per pixel, any slot order (kAccumulate's addressing): Q += r r per channel, samples in index order
 //   kAccumulateMomentsRuns  the same sums for the pixel-major slot order, the runs staged (squared) in LDS in fixed-size chunks (kAccumulateAovRuns' shape)
 //   kNoiseEstimate          one 256-lane workgroup per 32x32 tile: the per-pixel relative standard error, the tile's halving-tree sum, maximum and counts
+//   kAccumulateTiles        tile-adaptive sampling: S += r AND Q += r r in one pass, for a LIST of tiles of the whole frame, written at the listed tiles' own places
+//   kAccumulateTilesRuns    the same sums for the pixel-major slot order, the runs staged in LDS (kAccumulateMomentsRuns' shape)
+//   kNoiseEstimateTiles     kNoiseEstimate's body (estimateTile) for a list of tiles and / or one sample count per tile
+//   kTileMean               {S.rgb / float(tile's sample count), 1} per pixel
 // Both accumulation kernels read the per-slot radiance stream the image is accumulated from (ps.rad) and nothing else of the path state: the trace and shading
 // kernels do not know about them.
 #include "rf_noise.hpp"
@@ -81,13 +85,14 @@ __global__ __launch_bounds__(64) void kAccumulateMomentsRuns(FrameParams fp, con
 
 // One workgroup per tile of the 32x32 grid.  tileMajor: entry j of the tile sits at S[tile * 1024 + j] (8x8 blocks, localPixelToXY's layout: the workgroup reads
 // two contiguous 16 KB runs); else the sums are row-major.  nf = float(N), nf1 = nf - 1.  errorMap (row-major) may be nullptr.
-__global__ __launch_bounds__(256) void kNoiseEstimate(const float4* colorSum, const float4* sumSq, uint32_t width, uint32_t height, uint32_t tilesX, uint32_t tileMajor, float nf,
-                                                      float nf1, float* errorMap, float* tileSum, float* tileMax, uint32_t* tilePixels, uint32_t* tileNonfinite)
+// (estimateTile: the work of one 256-lane workgroup for tile `tile`, shared by kNoiseEstimate and kNoiseEstimateTiles)
+__device__ __forceinline__ void estimateTile(const float4* colorSum, const float4* sumSq, uint32_t width, uint32_t height, uint32_t tilesX, uint32_t tileMajor, uint32_t tile, float nf,
+                                             float nf1, float* errorMap, float* tileSum, float* tileMax, uint32_t* tilePixels, uint32_t* tileNonfinite)
 {
     __shared__ float    a[1024]; // a[ty * 32 + tx]
     __shared__ float    sMax[256];
     __shared__ uint32_t sCount[2];
-    const uint32_t t = threadIdx.x, tile = blockIdx.x, tileY = tile / tilesX, tileX = tile - tileY * tilesX;
+    const uint32_t t = threadIdx.x, tileY = tile / tilesX, tileX = tile - tileY * tilesX;
     if (t < 2u) sCount[t] = 0u;
     __syncthreads();
     float    m = -__builtin_inff();
@@ -149,7 +154,112 @@ __global__ __launch_bounds__(256) void kNoiseEstimate(const float4* colorSum, co
         tileNonfinite[tile] = sCount[1];
     }
 }
+
+__global__ __launch_bounds__(256) void kNoiseEstimate(const float4* colorSum, const float4* sumSq, uint32_t width, uint32_t height, uint32_t tilesX, uint32_t tileMajor, float nf,
+                                                      float nf1, float* errorMap, float* tileSum, float* tileMax, uint32_t* tilePixels, uint32_t* tileNonfinite)
+{
+    estimateTile(colorSum, sumSq, width, height, tilesX, tileMajor, blockIdx.x, nf, nf1, errorMap, tileSum, tileMax, tilePixels, tileNonfinite);
+}
+
+// One workgroup per LISTED tile (tileList == nullptr: tile blockIdx.x), with the tile's own sample count (tileSamples[tile]; nullptr: nf for all).  Nf = float(count),
+// Nf - 1 one f32 subtraction, as the host computes them for kNoiseEstimate.  Every per-tile output is written at the tile's own index: entries of unlisted tiles stay.
+__global__ __launch_bounds__(256) void kNoiseEstimateTiles(const float4* colorSum, const float4* sumSq, uint32_t width, uint32_t height, uint32_t tilesX, uint32_t tileMajor,
+                                                           const uint32_t* tileList, const uint32_t* tileSamples, float nf, float* errorMap, float* tileSum, float* tileMax,
+                                                           uint32_t* tilePixels, uint32_t* tileNonfinite)
+{
+    const uint32_t tile = tileList ? tileList[blockIdx.x] : blockIdx.x;
+    const float    n = tileSamples ? static_cast<float>(tileSamples[tile]) : nf;
+    estimateTile(colorSum, sumSq, width, height, tilesX, tileMajor, tile, n, n - 1.0f, errorMap, tileSum, tileMax, tilePixels, tileNonfinite);
+}
+
+// Tile-adaptive sampling: the batch's path slots belong to the fp.numTiles tiles tileIds lists (local pixel lp = list position * 1024 + pixel of the tile), and the
+// handle's sums hold the WHOLE frame, compact slot == tile id: the sums of lp sit at tileIds[lp >> 10] * 1024 + (lp & 1023).  S += r and Q += r r per channel, samples
+// in index order: kAccumulate's and kAccumulateMoments' chains (one add; one multiply and one add), from one read of the radiance.  Any slot order.
+__global__ __launch_bounds__(kBlock) void kAccumulateTiles(FrameParams fp, const uint32_t* tileIds, const float4* rad, float4* image, float4* moments)
+{
+    const uint32_t lp = blockIdx.x * kBlock + threadIdx.x;
+    if (lp >= fp.pixelsPadded) return;
+    uint32_t x, y;
+    if (!localPixelToXY(fp, tileIds, lp, x, y)) return;
+    const size_t at = static_cast<size_t>(tileIds[lp >> 10]) * 1024u + (lp & 1023u);
+    float4       s = image[at], q = moments[at];
+    for (uint32_t k = 0; k < fp.numSamples; ++k)
+    {
+        const Vec3 r = load3(rad + samplePixelToSlot(fp, fp.sampleInvPerm ? fp.sampleInvPerm[k] : k, lp));
+        s.x += r.x;
+        s.y += r.y;
+        s.z += r.z;
+        q.x += r.x * r.x;
+        q.y += r.y * r.y;
+        q.z += r.z * r.z;
+    }
+    image[at] = s;
+    moments[at] = q;
+}
+
+// The same sums for the pixel-major slot order (slotGroupShift = 0), in kAccumulateMomentsRuns' shape: one 64-lane workgroup takes kMomentPixels pixels, stages their
+// runs' radiance in LDS in chunks of kMomentChunk samples (at the sample's index), and each of the 48 summing lanes -- one (pixel, channel) -- walks its row in sample
+// order with TWO running sums: S += r, Q += r r.  The row holds r, not r r: the square is the same one f32 multiply wherever it is taken, and one row serves both
+// sums -- 6.3 KB of LDS per workgroup, kAccumulateMomentsRuns' figure, for one read of the radiance instead of kAccumulateRuns' and kAccumulateMomentsRuns' two.
+__global__ __launch_bounds__(64) void kAccumulateTilesRuns(FrameParams fp, const uint32_t* tileIds, const float4* rad, float4* image, float4* moments)
+{
+    constexpr uint32_t R = kMomentChunk + 1u; // rows padded by one float: the summing lanes walk different banks
+    __shared__ float   sRun[kMomentPixels * 3u * R]; // [pixel][channel][sample of the chunk]
+    const uint32_t S = fp.numSamples, lane = threadIdx.x, lp0 = blockIdx.x * kMomentPixels;
+    const uint32_t px = lane / 3u, c = lane - 3u * px, lp = lp0 + px;
+    uint32_t       x, y;
+    const bool     sums = lane < kMomentPixels * 3u && lp < fp.pixelsPadded && localPixelToXY(fp, tileIds, lp, x, y); // (pixels outside the frame: read, never summed)
+    const size_t   at = sums ? static_cast<size_t>(tileIds[lp >> 10]) * 1024u + (lp & 1023u) : 0u;
+    float          accS = sums ? reinterpret_cast<const float*>(image + at)[c] : 0.0f;
+    float          accQ = sums ? reinterpret_cast<const float*>(moments + at)[c] : 0.0f;
+    for (uint32_t k0 = 0; k0 < S; k0 += kMomentChunk)
+    {
+        const uint32_t n = min(kMomentChunk, S - k0), kk = lane & (kMomentChunk - 1u), half = lane >> 5;
+        if (kk < n)
+        {
+            const uint32_t k = k0 + kk, p = fp.sampleInvPerm ? fp.sampleInvPerm[k] : k; // sample k sits at position p of the pixel's run
+#pragma unroll
+            for (uint32_t i = 0; i < kMomentPixels / 2u; ++i)
+            {
+                const uint32_t pi = 2u * i + half, lpi = lp0 + pi;
+                if (lpi >= fp.pixelsPadded) continue;
+                const Vec3 v = load3(rad + static_cast<size_t>(lpi) * S + p);
+                float*     dst = sRun + pi * 3u * R + kk;
+                dst[0] = v.x, dst[R] = v.y, dst[2u * R] = v.z;
+            }
+        }
+        __syncthreads();
+        if (sums)
+        {
+            const float* src = sRun + lane * R; // (row lane = pixel px, channel c)
+            for (uint32_t j = 0; j < n; ++j)
+            {
+                const float r = src[j];
+                accS += r; // sample order: one dependent chain of f32 additions per channel and sum
+                accQ += r * r;
+            }
+        }
+        __syncthreads(); // the next chunk overwrites the rows
+    }
+    if (!sums) return;
+    reinterpret_cast<float*>(image + at)[c] = accS;
+    reinterpret_cast<float*>(moments + at)[c] = accQ;
+}
+
+// mean[i] = {S.rgb / float(n), 1}, n = the sample count of the pixel's tile (tileSamples[i >> 10]; nullptr: `samples` for all); n = 0: {0, 0, 0, 1}.  Compact tile-major.
+__global__ __launch_bounds__(256) void kTileMean(const float4* image, const uint32_t* tileSamples, uint32_t samples, uint32_t n, float4* mean)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t count = tileSamples ? tileSamples[i >> 10] : samples;
+    const float4   s = image[i];
+    const float    nf = static_cast<float>(count);
+    mean[i] = count ? make_float4(s.x / nf, s.y / nf, s.z / nf, 1.0f) : make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+}
 } // namespace
+
+AccumulateTilesKernel accumulateTilesKernel(bool runs) { return runs ? kAccumulateTilesRuns : kAccumulateTiles; }
+TileMeanKernel        tileMeanKernel() { return kTileMean; }
 
 AccumulateMomentsKernel accumulateMomentsKernel(bool runs) { return runs ? kAccumulateMomentsRuns : kAccumulateMoments; }
 
@@ -177,12 +287,27 @@ void NoiseWork::release()
 NoiseEstimate runNoiseEstimate(hipStream_t stream, NoiseWork& w, const float4* colorSum, const float4* sumSq, uint32_t width, uint32_t height, bool tileMajor, uint32_t samples,
                                float* errorMap, float* tileSum, float* tileMax)
 {
+    return runNoiseEstimateTiles(stream, w, colorSum, sumSq, width, height, tileMajor, TileSelection{}, samples, errorMap, tileSum, tileMax, nullptr);
+}
+
+NoiseEstimate runNoiseEstimateTiles(hipStream_t stream, NoiseWork& w, const float4* colorSum, const float4* sumSq, uint32_t width, uint32_t height, bool tileMajor,
+                                    const TileSelection& sel, uint32_t samples, float* errorMap, float* tileSum, float* tileMax, uint32_t* tilePixels)
+{
     const uint32_t tilesX = (width + kTileSize - 1) / kTileSize, tilesY = (height + kTileSize - 1) / kTileSize, tiles = tilesX * tilesY;
+    const uint32_t listed = sel.listDevice ? sel.listCount : tiles;
     const uint64_t n = static_cast<uint64_t>(width) * height;
+    NoiseEstimate  out;
+    out.samples = samples;
+    if (listed == 0) return out;
     w.reserve(tiles, errorMap ? n : 0, stream);
     const float nf = static_cast<float>(samples), nf1 = nf - 1.0f;
-    hipLaunchKernelGGL(kNoiseEstimate, dim3(tiles), dim3(256), 0, stream, colorSum, sumSq, width, height, tilesX, tileMajor ? 1u : 0u, nf, nf1,
-                       errorMap ? w.errorMap : static_cast<float*>(nullptr), w.tileSumMax, w.tileSumMax + w.tiles, w.tileCounts, w.tileCounts + w.tiles);
+    float* const map = errorMap ? w.errorMap : static_cast<float*>(nullptr);
+    if (sel.listDevice == nullptr && sel.tileSamplesDevice == nullptr)
+        hipLaunchKernelGGL(kNoiseEstimate, dim3(tiles), dim3(256), 0, stream, colorSum, sumSq, width, height, tilesX, tileMajor ? 1u : 0u, nf, nf1, map, w.tileSumMax,
+                           w.tileSumMax + w.tiles, w.tileCounts, w.tileCounts + w.tiles);
+    else
+        hipLaunchKernelGGL(kNoiseEstimateTiles, dim3(listed), dim3(256), 0, stream, colorSum, sumSq, width, height, tilesX, tileMajor ? 1u : 0u, sel.listDevice, sel.tileSamplesDevice,
+                           nf, map, w.tileSumMax, w.tileSumMax + w.tiles, w.tileCounts, w.tileCounts + w.tiles);
     RF_HIP(hipGetLastError());
     std::vector<float>    sums(tiles), maxima(tiles);
     std::vector<uint32_t> pixels(tiles), nonfinite(tiles);
@@ -192,42 +317,54 @@ NoiseEstimate runNoiseEstimate(hipStream_t stream, NoiseWork& w, const float4* c
     RF_HIP(hipMemcpyAsync(nonfinite.data(), w.tileCounts + w.tiles, tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     if (errorMap) RF_HIP(hipMemcpyAsync(errorMap, w.errorMap, n * sizeof(float), hipMemcpyDeviceToHost, stream));
     RF_HIP(hipStreamSynchronize(stream));
-    // the frame, on the host: tile sums added in f64 in ascending tile order; the first tile that attains the maximum
-    NoiseEstimate out;
-    out.samples = samples;
+    // the frame (or the listed tiles), on the host: tile sums added in f64 in ascending tile order; the first tile that attains the maximum
+    const auto tileAt = [&](uint32_t i) { return sel.listDevice ? sel.listHost[i] : i; };
     double total = 0.0;
-    out.maxError = maxima[0];
-    for (uint32_t t = 0; t < tiles; ++t)
+    out.maxError = maxima[tileAt(0)];
+    out.worstTile = tileAt(0);
+    for (uint32_t i = 0; i < listed; ++i)
     {
+        const uint32_t t = tileAt(i);
         total += static_cast<double>(sums[t]);
         if (maxima[t] > out.maxError) out.maxError = maxima[t], out.worstTile = t;
         out.pixels += pixels[t];
         out.nonfinitePixels += nonfinite[t];
     }
     out.meanError = total / static_cast<double>(out.pixels);
+    // (with a list, the entries of unlisted tiles are whatever an earlier run left: the caller reads the listed ones)
     if (tileSum) std::memcpy(tileSum, sums.data(), tiles * sizeof(float));
     if (tileMax) std::memcpy(tileMax, maxima.data(), tiles * sizeof(float));
+    if (tilePixels) std::memcpy(tilePixels, pixels.data(), tiles * sizeof(uint32_t));
     return out;
 }
 
 NoiseEstimate noiseEstimateImages(int deviceOrdinal, uint32_t width, uint32_t height, uint32_t samples, const float* colorSum, const float* sumSq, float* errorMap, float* tileSum,
                                   float* tileMax)
 {
+    return noiseEstimateTiles(deviceOrdinal, width, height, nullptr, samples, colorSum, sumSq, errorMap, tileSum, tileMax);
+}
+
+NoiseEstimate noiseEstimateTiles(int deviceOrdinal, uint32_t width, uint32_t height, const uint32_t* tileSamples, uint32_t samples, const float* colorSum, const float* sumSq,
+                                 float* errorMap, float* tileSum, float* tileMax)
+{
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count == 0) throw std::runtime_error("rayfinder_amd: no HIP device available (this library has no CPU fallback)");
     if (deviceOrdinal < 0 || deviceOrdinal >= count) throw std::invalid_argument("device ordinal out of range");
     RF_HIP(hipSetDevice(deviceOrdinal));
     const uint64_t n = static_cast<uint64_t>(width) * height;
+    const uint32_t tiles = ((width + kTileSize - 1) / kTileSize) * ((height + kTileSize - 1) / kTileSize);
     struct Scope
     {
         hipStream_t stream = nullptr;
         float4*     in[2] = {};
+        uint32_t*   counts = nullptr;
         NoiseWork   work;
         ~Scope()
         {
             if (stream) (void)hipStreamSynchronize(stream);
             for (float4* b : in)
                 if (b) (void)hipFree(b);
+            if (counts) (void)hipFree(counts);
             work.release();
             if (stream) (void)hipStreamDestroy(stream);
         }
@@ -239,6 +376,13 @@ NoiseEstimate noiseEstimateImages(int deviceOrdinal, uint32_t width, uint32_t he
         RF_HIP(hipMalloc(reinterpret_cast<void**>(&s.in[b]), n * sizeof(float4)));
         RF_HIP(hipMemcpyAsync(s.in[b], src[b], n * sizeof(float4), hipMemcpyHostToDevice, s.stream));
     }
-    return runNoiseEstimate(s.stream, s.work, s.in[0], s.in[1], width, height, false, samples, errorMap, tileSum, tileMax);
+    TileSelection sel;
+    if (tileSamples)
+    {
+        RF_HIP(hipMalloc(reinterpret_cast<void**>(&s.counts), tiles * sizeof(uint32_t)));
+        RF_HIP(hipMemcpyAsync(s.counts, tileSamples, tiles * sizeof(uint32_t), hipMemcpyHostToDevice, s.stream));
+        sel.tileSamplesDevice = s.counts;
+    }
+    return runNoiseEstimateTiles(s.stream, s.work, s.in[0], s.in[1], width, height, false, sel, samples, errorMap, tileSum, tileMax, nullptr);
 }
 } // namespace rf

@@ -14,6 +14,14 @@ using AccumulateMomentsKernel = void (*)(FrameParams fp, const uint32_t* tileIds
 constexpr uint32_t kMomentPixels = 16, kMomentChunk = 32;
 AccumulateMomentsKernel accumulateMomentsKernel(bool runs); // runs: the LDS-staged kernel for the pixel-major slot order (slotGroupShift 0)
 
+// Tile-adaptive sampling (rf_renderer_render_adaptive).  S[at] += r and Q[at] += {r.x r.x, r.y r.y, r.z r.z} of samples 0 .. numSamples-1 in sample order, in one pass
+// over rad, for the fp.numTiles tiles that tileIds lists: at = tileIds[lp >> 10] * 1024 + (lp & 1023), the place of the tile in the whole frame's compact buffers
+using AccumulateTilesKernel = void (*)(FrameParams fp, const uint32_t* tileIds, const float4* rad, float4* image, float4* moments);
+AccumulateTilesKernel accumulateTilesKernel(bool runs); // runs: the LDS-staged kernel for the pixel-major slot order (kMomentPixels pixels per 64-lane workgroup)
+// mean[i] = {S.rgb / float(count), 1} over n compact tile-major pixels; count = tileSamples[i >> 10], or `samples` for all when tileSamples is nullptr; count 0: rgb 0
+using TileMeanKernel = void (*)(const float4* image, const uint32_t* tileSamples, uint32_t samples, uint32_t n, float4* mean);
+TileMeanKernel tileMeanKernel();
+
 // Device buffers of one estimate: per-tile {sum, max} and {pixels, non-finite pixels}, and the row-major error map (only when a caller asks for it)
 struct NoiseWork
 {
@@ -33,4 +41,18 @@ struct NoiseWork
 // errorMap (width * height), tileSum, tileMax (one entry per tile of the 32 x 32 grid): host pointers, NULL = skip.  samples >= 2, width * height < 2^31.
 NoiseEstimate runNoiseEstimate(hipStream_t stream, NoiseWork& work, const float4* colorSum, const float4* sumSq, uint32_t width, uint32_t height, bool tileMajor,
                                uint32_t samples, float* errorMap, float* tileSum, float* tileMax);
+
+// Which tiles an estimate covers and with what counts.  listDevice / listHost: the same ascending list of listCount tile ids (nullptr: every tile of the frame);
+// tileSamplesDevice: one sample count per tile of the frame, each >= 2 (nullptr: `samples` for all).  Both nullptr: kNoiseEstimate itself.
+struct TileSelection
+{
+    const uint32_t* listDevice = nullptr;
+    const uint32_t* listHost = nullptr;
+    uint32_t        listCount = 0;
+    const uint32_t* tileSamplesDevice = nullptr;
+};
+// runNoiseEstimate for a selection: the result's mean, maximum and counts are over the listed tiles (worst_tile in the frame's numbering).  tilePixels (host, one entry
+// per tile of the frame, NULL = skip): in-frame pixels.  With a list, only the listed tiles' entries of tileSum / tileMax / tilePixels and of the map are written.
+NoiseEstimate runNoiseEstimateTiles(hipStream_t stream, NoiseWork& work, const float4* colorSum, const float4* sumSq, uint32_t width, uint32_t height, bool tileMajor,
+                                    const TileSelection& selection, uint32_t samples, float* errorMap, float* tileSum, float* tileMax, uint32_t* tilePixels);
 } // namespace rf

@@ -180,6 +180,20 @@ struct Renderer::Impl
     uint32_t                momentSamples = 0;
     DeviceBuffer<float4>    moments;
     NoiseWork               noiseWork; // the estimate's device buffers, allocated by the first rf_renderer_noise_estimate
+    // tile-adaptive sampling (rf_renderer_render_adaptive).  tileSamples[t], t in the frame's tile numbering, is the sample count of tile t; EMPTY = the uniform
+    // state: every tile holds `accumulated` samples (the only state a handle that never called render_adaptive is ever in).  Non-empty: the counts differ, `accumulated`
+    // is the leading count L, and the tiles still at L are the only ones a later render_adaptive samples.  Cleared with the image.
+    std::vector<uint32_t>   tileSamples;
+    DeviceBuffer<uint32_t>  tileSamplesDevice; // the counts for the per-tile reads (mean, tonemap, estimate), uploaded by them
+    DeviceBuffer<float4>    meanImage;         // rf_renderer_read_mean / the non-uniform rf_renderer_read_tonemapped: compact tile-major, allocated by the first read
+
+    bool nonUniform() const { return !tileSamples.empty(); }
+    void requireUniform(const char* what) const
+    {
+        if (nonUniform())
+            throw std::invalid_argument(std::string(what) + ": the tiles hold different sample counts after rf_renderer_render_adaptive (continue with render_adaptive, or restart the "
+                                                            "accumulation with rf_renderer_set_render_parameters)");
+    }
 
     uint64_t                validPixels = 0;     // pixels of this rank's tiles that lie inside the frame
     unsigned long long      primaryRaysHost = 0; // samples traced x validPixels since the last resetStats()
@@ -390,6 +404,7 @@ struct Renderer::Impl
         if (image == ownedImage.ptr) imageBytes = pixelsPadded * sizeof(float4);
         accumulated = 0;
         imageDirty = true;
+        tileSamples.clear();
         clearAovs();
         clearMoments();
     }
@@ -681,9 +696,141 @@ struct Renderer::Impl
         }
     }
 
-    // Trace `numSamples` consecutive samples (sample indices start at frame `firstFrame`).
-    void traceBatch(uint32_t firstFrame, uint32_t numSamples)
+    // Before the first sample of an accumulation: zero the sums that were cleared (the image, and the AOV sums / moments while they are on), sized for the shard
+    void clearStaleSums(uint64_t pixelsPadded)
     {
+        if (imageDirty)
+        {
+            RF_HIP(hipMemsetAsync(image, 0, pixelsPadded * sizeof(float4), stream)); // wgsl:47-49
+            imageDirty = false;
+        }
+        if (aovFlags != 0u && aovDirty)
+        {
+            if (aovAlbedoCoverage.count < pixelsPadded)
+            {
+                RF_HIP(hipStreamSynchronize(stream)); // (a smaller buffer may still be read by the last batch)
+                aovAlbedoCoverage.alloc(pixelsPadded), aovNormalDepth.alloc(pixelsPadded);
+            }
+            RF_HIP(hipMemsetAsync(aovAlbedoCoverage.ptr, 0, pixelsPadded * sizeof(float4), stream));
+            RF_HIP(hipMemsetAsync(aovNormalDepth.ptr, 0, pixelsPadded * sizeof(float4), stream));
+            aovDirty = false;
+        }
+        if (momentsOn && momentsDirty)
+        {
+            if (moments.count < pixelsPadded)
+            {
+                RF_HIP(hipStreamSynchronize(stream)); // (a smaller buffer may still be read by the last estimate)
+                moments.alloc(pixelsPadded);
+            }
+            RF_HIP(hipMemsetAsync(moments.ptr, 0, pixelsPadded * sizeof(float4), stream));
+            momentsDirty = false;
+        }
+    }
+
+    // Samples per batch for `todo` samples of `pixelsPadded` path slots per sample (the shard's tiles, or the active tiles of render_adaptive), with the path state
+    // for it allocated.
+    uint32_t batchSamples(uint32_t todo, uint64_t pixelsPadded)
+    {
+        // equal batches (320 samples with room for 256 per batch -> 160 + 160, not 256 + 64): a small trailing batch has
+        // short launches and, with few samples per pixel, less coherent waves
+        // maxPaths is the CONFIGURED depth (the default or the caller's) and is never changed here: what a call has to give up
+        // because memory is short at that moment (another handle alive, a shared GPU) is given up for that call only.
+        uint32_t       n = 0;
+        uint64_t       depth = maxPaths;
+        for (;;)
+        {
+            const uint32_t perBatch = static_cast<uint32_t>(std::max<uint64_t>(1, depth / pixelsPadded));
+            const uint32_t numBatches = (todo + perBatch - 1) / perBatch;
+            n = (todo + numBatches - 1) / numBatches;
+            const uint64_t need = static_cast<uint64_t>(n) * pixelsPadded;
+            if (pathStateHolds(need)) break;
+            // The batch depth is a speed knob (DESIGN.md 8.2), never a requirement: a device with less free memory than the
+            // batch wants (a smaller or shared GPU, a second handle on this one) traces the same samples in more, smaller
+            // batches -- same image.  First by what hipMemGetInfo reports, then by halving if hipMalloc still refuses.
+            const uint64_t fit = pathsThatFit();
+            if (need > fit && n > 1)
+            {
+                depth = std::max<uint64_t>(pixelsPadded, std::min(depth / 2, fit));
+                continue;
+            }
+            if (ensurePathState(need)) break;
+            if (n == 1) throw std::runtime_error("out of device memory: one sample of the frame (" + std::to_string(need * bytesPerPath() >> 20) + " MiB of path state) does not fit");
+            depth = std::max<uint64_t>(pixelsPadded, depth / 2);
+        }
+        if (depth != effectivePaths)
+        {
+            // said once per change, not per batch: shallower batches are a silent loss of speed otherwise (DESIGN.md 8.2)
+            if (depth < maxPaths)
+                std::fprintf(stderr, "[rf] device memory is short: batches of %llu paths instead of the configured %llu (%u samples per batch); same image, shorter launches\n",
+                             static_cast<unsigned long long>(depth), static_cast<unsigned long long>(maxPaths), n);
+            else if (effectivePaths != 0 && effectivePaths < maxPaths)
+                std::fprintf(stderr, "[rf] device memory is back: batches of the configured %llu paths again\n", static_cast<unsigned long long>(maxPaths));
+            effectivePaths = depth;
+        }
+        return n;
+    }
+
+    // the non-uniform counts on the device, for the per-tile reads (the stream is made idle first: an earlier read may still use the buffer)
+    const uint32_t* uploadTileSamples()
+    {
+        RF_HIP(hipStreamSynchronize(stream));
+        if (tileSamplesDevice.count < tileSamples.size()) tileSamplesDevice.alloc(tileSamples.size());
+        RF_HIP(hipMemcpy(tileSamplesDevice.ptr, tileSamples.data(), tileSamples.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        return tileSamplesDevice.ptr;
+    }
+    // kTileMean over the accumulation into meanImage, waited for: every pixel divided by its tile's count (uniform state: the accumulated count; nothing accumulated: 0)
+    const float4* meanOnDevice()
+    {
+        const uint32_t n = static_cast<uint32_t>(tiles.size() * 1024);
+        RF_HIP(hipStreamSynchronize(stream));
+        if (meanImage.count < n) meanImage.alloc(n);
+        if (imageDirty)
+        {
+            RF_HIP(hipMemsetAsync(image, 0, static_cast<size_t>(n) * sizeof(float4), stream));
+            imageDirty = false;
+        }
+        const uint32_t* counts = nonUniform() ? uploadTileSamples() : nullptr;
+        hipLaunchKernelGGL(tileMeanKernel(), dim3((n + 255) / 256), dim3(256), 0, stream, static_cast<const float4*>(image), counts, accumulated, n, meanImage.ptr);
+        RF_HIP(hipGetLastError());
+        RF_HIP(hipStreamSynchronize(stream));
+        return meanImage.ptr;
+    }
+
+    // The tile list a batch of rf_renderer_render_adaptive traces: while one is in use, tileIds / tileValidBefore hold IT (uploadTileList) and not the shard's list
+    struct ActiveTiles
+    {
+        uint32_t numTiles;
+        uint64_t validPixels;
+    };
+    // tileIds / tileValidBefore <- a list of tile ids (ascending) of the whole frame.  The stream must be idle (the copies are synchronous).  -> pixels inside the frame
+    uint64_t uploadTileList(const std::vector<uint32_t>& list)
+    {
+        const uint32_t tilesX = (params.width + kTileSize - 1) / kTileSize;
+        uint64_t       valid = 0;
+        std::vector<uint32_t> before;
+        before.reserve(list.size() + 1);
+        for (const uint32_t t : list)
+        {
+            before.push_back(static_cast<uint32_t>(valid));
+            valid += tilePixelsInFrame(t, tilesX);
+        }
+        before.push_back(static_cast<uint32_t>(valid));
+        if (list.size() > tileIds.count || before.size() > tileValidBefore.count) throw std::logic_error("tile list longer than the frame's");
+        if (!list.empty()) RF_HIP(hipMemcpy(tileIds.ptr, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        RF_HIP(hipMemcpy(tileValidBefore.ptr, before.data(), before.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        return valid;
+    }
+    uint32_t tilePixelsInFrame(uint32_t t, uint32_t tilesX) const
+    {
+        const uint32_t x0 = (t % tilesX) * kTileSize, y0 = (t / tilesX) * kTileSize;
+        return std::min(kTileSize, params.width - x0) * std::min(kTileSize, params.height - y0);
+    }
+
+    // Trace `numSamples` consecutive samples (sample indices start at frame `firstFrame`) of the shard's tiles -- or, active != nullptr, of the tile list that
+    // tileIds / tileValidBefore hold then: the radiance and its squares are added by the tile-list kernel, at the listed tiles' own places.
+    void traceBatch(uint32_t firstFrame, uint32_t numSamples, const ActiveTiles* active = nullptr)
+    {
+        const uint64_t validPixels = active ? active->validPixels : this->validPixels;
         FrameParams fp{};
         fp.width = params.width;
         fp.height = params.height;
@@ -692,7 +839,7 @@ struct Renderer::Impl
         fp.numBounces = params.samplingParams.numBounces;
         fp.firstFrame = firstFrame;
         fp.numSamples = numSamples;
-        fp.numTiles = static_cast<uint32_t>(tiles.size());
+        fp.numTiles = active ? active->numTiles : static_cast<uint32_t>(tiles.size());
         fp.pixelsPadded = fp.numTiles * 1024u;
         fp.slotGroupShift = optSlotGroupShift;
         fp.samplePerm = fp.sampleInvPerm = nullptr;
@@ -897,6 +1044,17 @@ struct Renderer::Impl
         }
         if (wide.occGrid != nullptr) occluderGridWarm = true;
         launchTimed(4, [&] {
+            if (active)
+            {
+                // (whole frame: compact slot == tile id, so the listed tiles' sums sit at tile id * 1024 of the image and the moments)
+                if (fp.slotGroupShift == 0u && numSamples > 4u && optAccumulateRuns)
+                    hipLaunchKernelGGL(accumulateTilesKernel(true), dim3((fp.pixelsPadded + kMomentPixels - 1) / kMomentPixels), dim3(64), 0, stream, fp, tileIds.ptr,
+                                       static_cast<const float4*>(ps.rad), image, moments.ptr);
+                else
+                    hipLaunchKernelGGL(accumulateTilesKernel(false), dim3((fp.pixelsPadded + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, fp, tileIds.ptr,
+                                       static_cast<const float4*>(ps.rad), image, moments.ptr);
+                return;
+            }
             if (fp.slotGroupShift == 0u && numSamples > 4u && numSamples <= kAccMaxSamples && optAccumulateRuns)
             {
                 // (pixels per workgroup by the LDS their runs take: <= ~8 KB per workgroup keeps twenty of them resident per CU)
@@ -1248,6 +1406,7 @@ void Renderer::setRenderParameters(const RenderParameters& p)
     m.updateSunBasis();
     m.accumulated = 0;
     m.imageDirty = true;
+    m.tileSamples.clear();
     m.clearAovs();
     m.clearMoments();
     if (resized) m.configureShard();
@@ -1257,6 +1416,7 @@ void Renderer::setTileShard(uint32_t rank, uint32_t worldSize)
 {
     Impl& m = *mImpl;
     if (worldSize == 0 || rank >= worldSize) throw std::runtime_error("invalid tile shard");
+    m.requireUniform("rf_renderer_set_tile_shard");
     RF_HIP(hipSetDevice(m.device));
     RF_HIP(hipStreamSynchronize(m.stream));
     m.rank = rank;
@@ -1269,6 +1429,7 @@ std::span<const uint32_t> Renderer::shardTiles() const { return mImpl->tiles; }
 void Renderer::render(uint32_t numFrames)
 {
     Impl& m = *mImpl;
+    m.requireUniform("rf_renderer_render");
     RF_HIP(hipSetDevice(m.device));
     const uint32_t spp = m.params.samplingParams.numSamplesPerPixel;
     const uint64_t pixelsPadded = static_cast<uint64_t>(m.tiles.size()) * 1024;
@@ -1282,69 +1443,8 @@ void Renderer::render(uint32_t numFrames)
             m.frameCount += remaining;
             break;
         }
-        if (m.imageDirty)
-        {
-            RF_HIP(hipMemsetAsync(m.image, 0, pixelsPadded * sizeof(float4), m.stream)); // wgsl:47-49
-            m.imageDirty = false;
-        }
-        if (m.aovFlags != 0u && m.aovDirty)
-        {
-            if (m.aovAlbedoCoverage.count < pixelsPadded)
-            {
-                RF_HIP(hipStreamSynchronize(m.stream)); // (a smaller buffer may still be read by the last batch)
-                m.aovAlbedoCoverage.alloc(pixelsPadded), m.aovNormalDepth.alloc(pixelsPadded);
-            }
-            RF_HIP(hipMemsetAsync(m.aovAlbedoCoverage.ptr, 0, pixelsPadded * sizeof(float4), m.stream));
-            RF_HIP(hipMemsetAsync(m.aovNormalDepth.ptr, 0, pixelsPadded * sizeof(float4), m.stream));
-            m.aovDirty = false;
-        }
-        if (m.momentsOn && m.momentsDirty)
-        {
-            if (m.moments.count < pixelsPadded)
-            {
-                RF_HIP(hipStreamSynchronize(m.stream)); // (a smaller buffer may still be read by the last estimate)
-                m.moments.alloc(pixelsPadded);
-            }
-            RF_HIP(hipMemsetAsync(m.moments.ptr, 0, pixelsPadded * sizeof(float4), m.stream));
-            m.momentsDirty = false;
-        }
-        // equal batches (320 samples with room for 256 per batch -> 160 + 160, not 256 + 64): a small trailing batch has
-        // short launches and, with few samples per pixel, less coherent waves
-        // m.maxPaths is the CONFIGURED depth (the default or the caller's) and is never changed here: what a call has to give up
-        // because memory is short at that moment (another handle alive, a shared GPU) is given up for that call only.
-        const uint32_t todo = std::min(remaining, spp - m.accumulated);
-        uint32_t       n = 0;
-        uint64_t       depth = m.maxPaths;
-        for (;;)
-        {
-            const uint32_t perBatch = static_cast<uint32_t>(std::max<uint64_t>(1, depth / pixelsPadded));
-            const uint32_t numBatches = (todo + perBatch - 1) / perBatch;
-            n = (todo + numBatches - 1) / numBatches;
-            const uint64_t need = static_cast<uint64_t>(n) * pixelsPadded;
-            if (m.pathStateHolds(need)) break;
-            // The batch depth is a speed knob (DESIGN.md 8.2), never a requirement: a device with less free memory than the
-            // batch wants (a smaller or shared GPU, a second handle on this one) traces the same samples in more, smaller
-            // batches -- same image.  First by what hipMemGetInfo reports, then by halving if hipMalloc still refuses.
-            const uint64_t fit = m.pathsThatFit();
-            if (need > fit && n > 1)
-            {
-                depth = std::max<uint64_t>(pixelsPadded, std::min(depth / 2, fit));
-                continue;
-            }
-            if (m.ensurePathState(need)) break;
-            if (n == 1) throw std::runtime_error("out of device memory: one sample of the frame (" + std::to_string(need * m.bytesPerPath() >> 20) + " MiB of path state) does not fit");
-            depth = std::max<uint64_t>(pixelsPadded, depth / 2);
-        }
-        if (depth != m.effectivePaths)
-        {
-            // said once per change, not per batch: shallower batches are a silent loss of speed otherwise (DESIGN.md 8.2)
-            if (depth < m.maxPaths)
-                std::fprintf(stderr, "[rf] device memory is short: batches of %llu paths instead of the configured %llu (%u samples per batch); same image, shorter launches\n",
-                             static_cast<unsigned long long>(depth), static_cast<unsigned long long>(m.maxPaths), n);
-            else if (m.effectivePaths != 0 && m.effectivePaths < m.maxPaths)
-                std::fprintf(stderr, "[rf] device memory is back: batches of the configured %llu paths again\n", static_cast<unsigned long long>(m.maxPaths));
-            m.effectivePaths = depth;
-        }
+        m.clearStaleSums(pixelsPadded);
+        const uint32_t n = m.batchSamples(std::min(remaining, spp - m.accumulated), pixelsPadded);
         m.traceBatch(m.frameCount, n);
         m.hostStats.batchSamplesUsed = n, m.hostStats.batchPathsUsed = static_cast<uint64_t>(n) * pixelsPadded, ++m.hostStats.batchesTraced;
         m.frameCount += n;
@@ -1439,6 +1539,7 @@ void Renderer::readAovs(float* albedoCoverage, float* normalDepth, uint32_t* sam
 void Renderer::denoise(const DenoiseParameters& params)
 {
     Impl& m = *mImpl;
+    m.requireUniform("rf_renderer_denoise"); // (the filter divides by ONE sample count)
     if (m.aovFlags == 0u) throw std::invalid_argument("denoise needs the first-hit AOVs: turn them on (rf_renderer_set_aovs) before the first sample");
     if (m.worldSize != 1u) throw std::invalid_argument("denoise needs the whole frame: a tile shard is set (use rf_denoise_images on the gathered sums)");
     if (m.accumulated == 0u || m.imageDirty) throw std::invalid_argument("denoise: no sample has been accumulated");
@@ -1511,7 +1612,132 @@ NoiseEstimate Renderer::noiseEstimate(float* errorMap, float* tileSum, float* ti
                                     std::to_string(m.imageDirty ? 0u : m.accumulated) + "): turn the moments on before the first sample");
     if (m.accumulated < 2u) throw std::invalid_argument("noise estimate: a variance needs at least 2 accumulated samples");
     RF_HIP(hipSetDevice(m.device));
+    if (m.nonUniform())
+    {
+        // every tile with its own count (each >= 2: a tile stops at an estimate); `samples` reports the leading count
+        TileSelection sel;
+        sel.tileSamplesDevice = m.uploadTileSamples();
+        return runNoiseEstimateTiles(m.stream, m.noiseWork, m.image, m.moments.ptr, m.params.width, m.params.height, true, sel, m.accumulated, errorMap, tileSum, tileMax, nullptr);
+    }
     return runNoiseEstimate(m.stream, m.noiseWork, m.image, m.moments.ptr, m.params.width, m.params.height, true, m.accumulated, errorMap, tileSum, tileMax);
+}
+
+AdaptiveResult Renderer::renderAdaptive(const AdaptiveParameters& p)
+{
+    Impl& m = *mImpl;
+    if (!m.momentsOn) throw std::invalid_argument("render_adaptive needs the radiance second moments: turn them on (rf_renderer_set_moments) before the first sample");
+    if (m.aovFlags != 0u) throw std::invalid_argument("render_adaptive: the first-hit AOVs are on (their sums and the denoiser keep ONE sample count): turn them off first");
+    if (m.worldSize != 1u) throw std::invalid_argument("render_adaptive needs the whole frame: a tile shard is set");
+    if (p.checkEvery == 0u) throw std::invalid_argument("render_adaptive: check_every must be >= 1");
+    if (!std::isfinite(p.targetTileError) || p.targetTileError < 0.0f) throw std::invalid_argument("render_adaptive: target_tile_error must be finite and >= 0");
+    if (m.accumulated != 0u && (m.imageDirty || m.momentsDirty || m.momentSamples != m.accumulated))
+        throw std::invalid_argument("render_adaptive: the moments do not cover the accumulation (turned on partway through): restart the accumulation first");
+    RF_HIP(hipSetDevice(m.device));
+    const uint32_t spp = m.params.samplingParams.numSamplesPerPixel;
+    const uint32_t cap = p.maxSamples == 0u ? spp : std::min(p.maxSamples, spp);
+    const uint32_t numTiles = static_cast<uint32_t>(m.tiles.size()), tilesX = (m.params.width + kTileSize - 1) / kTileSize;
+    const uint32_t firstCheck = std::max(2u, p.minSamples);
+
+    // the counts as a vector for the length of the call (the uniform state: every tile at the accumulated count); the tiles at the leading count are the active ones
+    std::vector<uint32_t> counts = m.nonUniform() ? m.tileSamples : std::vector<uint32_t>(numTiles, m.accumulated);
+    std::vector<uint32_t> active;
+    for (uint32_t t = 0; t < numTiles; ++t)
+        if (counts[t] == m.accumulated) active.push_back(t);
+
+    AdaptiveResult        out;
+    std::vector<float>    sums(numTiles);
+    std::vector<uint32_t> pixels(numTiles);
+    // tileIds / tileValidBefore hold the active list while it is shorter than the frame's; whatever happens, they hold the frame's list again afterwards
+    struct Restore
+    {
+        Impl& m;
+        bool  armed = false;
+        ~Restore()
+        {
+            if (!armed) return;
+            (void)hipStreamSynchronize(m.stream);
+            try { m.uploadTileList(m.tiles); } catch (...) {}
+        }
+    } restore{m};
+    Impl::ActiveTiles list{numTiles, m.validPixels};
+    bool              listStale = active.size() != numTiles;
+    while (!active.empty() && m.accumulated < cap)
+    {
+        const uint64_t pixelsPadded = static_cast<uint64_t>(active.size()) * 1024;
+        if (listStale)
+        {
+            RF_HIP(hipStreamSynchronize(m.stream));
+            restore.armed = true;
+            list = Impl::ActiveTiles{static_cast<uint32_t>(active.size()), m.uploadTileList(active)};
+            listStale = false;
+        }
+        m.clearStaleSums(static_cast<uint64_t>(numTiles) * 1024);
+        uint32_t remaining = std::min(p.checkEvery, cap - m.accumulated);
+        while (remaining > 0)
+        {
+            const uint32_t n = m.batchSamples(remaining, pixelsPadded);
+            m.traceBatch(m.frameCount, n, &list);
+            m.hostStats.batchSamplesUsed = n, m.hostStats.batchPathsUsed = static_cast<uint64_t>(n) * pixelsPadded, ++m.hostStats.batchesTraced;
+            m.frameCount += n;
+            m.accumulated += n;
+            m.momentSamples += n;
+            remaining -= n;
+        }
+        for (const uint32_t t : active) counts[t] = m.accumulated;
+        m.tileSamples = counts; // (non-uniform from here on, should an estimate throw; settled below)
+        if (m.accumulated < firstCheck) continue;
+        // the active tiles' estimate, Nf = float(L) for all of them; tileIds holds the list (the frame's own while every tile is active)
+        TileSelection sel;
+        sel.listDevice = m.tileIds.ptr, sel.listHost = active.data(), sel.listCount = static_cast<uint32_t>(active.size());
+        out.last = runNoiseEstimateTiles(m.stream, m.noiseWork, m.image, m.moments.ptr, m.params.width, m.params.height, true, sel, m.accumulated, nullptr, sums.data(), nullptr,
+                                         pixels.data());
+        ++out.estimatePasses;
+        std::vector<uint32_t> still;
+        for (const uint32_t t : active)
+            if (!(sums[t] / static_cast<float>(pixels[t]) <= p.targetTileError)) still.push_back(t); // (NaN: never <=, the tile goes on)
+        if (still.size() != active.size()) listStale = true;
+        active.swap(still);
+    }
+    RF_HIP(hipStreamSynchronize(m.stream)); // (waits for the work it enqueued, as render_until does)
+
+    out.tiles = numTiles;
+    out.minTileSamples = out.maxTileSamples = numTiles ? counts[0] : 0u;
+    for (uint32_t t = 0; t < numTiles; ++t)
+    {
+        out.minTileSamples = std::min(out.minTileSamples, counts[t]), out.maxTileSamples = std::max(out.maxTileSamples, counts[t]);
+        if (counts[t] != m.accumulated) ++out.stoppedTiles;
+        out.pixelSamples += static_cast<uint64_t>(m.tilePixelsInFrame(m.tiles[t], tilesX)) * counts[t];
+    }
+    if (out.stoppedTiles == 0u) m.tileSamples.clear(); // every tile at the leading count: the ordinary state
+    else m.tileSamples = counts;
+    return out;
+}
+
+bool Renderer::tileSamplesUniform() const { return !mImpl->nonUniform(); }
+void Renderer::requireUniformTileSamples(const char* what) const { mImpl->requireUniform(what); }
+
+uint32_t Renderer::readTileSamples(uint32_t* tileSamples) const
+{
+    const Impl&    m = *mImpl;
+    const uint32_t frameTiles = ((m.params.width + kTileSize - 1) / kTileSize) * ((m.params.height + kTileSize - 1) / kTileSize);
+    if (tileSamples)
+    {
+        std::fill(tileSamples, tileSamples + frameTiles, 0u);
+        for (size_t i = 0; i < m.tiles.size(); ++i) tileSamples[m.tiles[i]] = m.nonUniform() ? m.tileSamples[i] : (m.imageDirty ? 0u : m.accumulated);
+    }
+    return frameTiles;
+}
+
+void Renderer::readMean(float* rgba)
+{
+    Impl& m = *mImpl;
+    synchronize();
+    const size_t pixelsPadded = m.tiles.size() * 1024;
+    std::memset(rgba, 0, static_cast<size_t>(m.params.width) * m.params.height * 4 * sizeof(float));
+    if (pixelsPadded == 0) return;
+    std::vector<float> compact(pixelsPadded * 4);
+    RF_HIP(hipMemcpy(compact.data(), m.meanOnDevice(), pixelsPadded * sizeof(float4), hipMemcpyDeviceToHost));
+    untileHost(compact.data(), m.tiles.data(), static_cast<uint32_t>(m.tiles.size()), m.params.width, m.params.height, rgba);
 }
 
 uint32_t Renderer::renderUntil(float targetMeanError, uint32_t checkEvery, uint32_t maxFrames, NoiseEstimate* last)
@@ -1520,6 +1746,7 @@ uint32_t Renderer::renderUntil(float targetMeanError, uint32_t checkEvery, uint3
     if (!m.momentsOn) throw std::invalid_argument("render_until needs the radiance second moments: turn them on (rf_renderer_set_moments) before the first sample");
     if (m.worldSize != 1u) throw std::invalid_argument("render_until needs the whole frame: a tile shard is set");
     if (checkEvery == 0u) throw std::invalid_argument("render_until: check_every must be >= 1");
+    m.requireUniform("rf_renderer_render_until");
     if (m.accumulated != 0u && (m.momentsDirty || m.momentSamples != m.accumulated))
         throw std::invalid_argument("render_until: the moments do not cover the accumulation (turned on partway through): restart the accumulation first");
     const uint32_t spp = m.params.samplingParams.numSamplesPerPixel;
@@ -1602,6 +1829,7 @@ void Renderer::bindAccumulationBuffer(void* devicePtr, uint64_t bytes)
     m.imageBytes = bytes;
     m.accumulated = 0;
     m.imageDirty = true;
+    m.tileSamples.clear();
     m.clearAovs();
     m.clearMoments();
 }
@@ -1618,7 +1846,10 @@ void Renderer::readTonemapped(uint32_t* dst)
         RF_HIP(hipMemsetAsync(m.image, 0, static_cast<size_t>(n) * sizeof(float4), m.stream));
         m.imageDirty = false;
     }
-    if (n) hipLaunchKernelGGL(tonemapKernel(), dim3((n + 255) / 256), dim3(256), 0, m.stream, m.image, n, m.accumulated, m.params.exposure, out.ptr);
+    // (non-uniform tile counts: kTonemap over the per-tile mean with accumulatedSamples = 1, the denoiser's display path; x / 1 is exact, so the uniform state's texels are
+    // the ones the direct launch gives)
+    if (n && m.nonUniform()) hipLaunchKernelGGL(tonemapKernel(), dim3((n + 255) / 256), dim3(256), 0, m.stream, m.meanOnDevice(), n, 1u, m.params.exposure, out.ptr);
+    else if (n) hipLaunchKernelGGL(tonemapKernel(), dim3((n + 255) / 256), dim3(256), 0, m.stream, m.image, n, m.accumulated, m.params.exposure, out.ptr);
     RF_HIP(hipStreamSynchronize(m.stream));
     std::vector<uint32_t> compact(n);
     if (n) RF_HIP(hipMemcpy(compact.data(), out.ptr, static_cast<size_t>(n) * 4, hipMemcpyDeviceToHost));

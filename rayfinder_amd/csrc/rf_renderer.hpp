@@ -125,6 +125,26 @@ struct NoiseEstimate
 NoiseEstimate noiseEstimateImages(int deviceOrdinal, uint32_t width, uint32_t height, uint32_t samples, const float* colorSum, const float* sumSq, float* errorMap,
                                   float* tileSum, float* tileMax);
 
+// The same with one sample count per tile of the 32 x 32 grid (tileSamples[t] >= 2, tile t = tile_y * ceil(width / 32) + tile_x): Nf = float(tileSamples[t]) for the
+// pixels of tile t.  tileSamples == nullptr: `samples` for every tile.  The result's `samples` is `samples` as given.
+NoiseEstimate noiseEstimateTiles(int deviceOrdinal, uint32_t width, uint32_t height, const uint32_t* tileSamples, uint32_t samples, const float* colorSum, const float* sumSq,
+                                 float* errorMap, float* tileSum, float* tileMax);
+
+// Tile-adaptive sampling (rf_renderer_render_adaptive; the loop: include/rayfinder_amd.h)
+struct AdaptiveParameters
+{
+    float    targetTileError = 0.0f;
+    uint32_t checkEvery = 8, minSamples = 0, maxSamples = 0; // maxSamples 0: numSamplesPerPixel
+};
+struct AdaptiveResult
+{
+    uint32_t      estimatePasses = 0;
+    uint32_t      tiles = 0, stoppedTiles = 0; // stopped: tiles below the leading count
+    uint32_t      minTileSamples = 0, maxTileSamples = 0;
+    uint64_t      pixelSamples = 0;            // sum over the tiles of in-frame pixels x sample count
+    NoiseEstimate last;                        // the last pass's estimate, over the tiles that were active in it (samples = 0: no pass was made)
+};
+
 class Renderer
 {
 public:
@@ -179,6 +199,17 @@ public:
     // have been rendered or the accumulation is full.  -> frames rendered; *last: the last estimate (samples = 0: none was made).  Needs the moments on (covering
     // the whole accumulation), no tile shard and checkEvery >= 1.
     uint32_t renderUntil(float targetMeanError, uint32_t checkEvery, uint32_t maxFrames, NoiseEstimate* last);
+    // Tile-adaptive sampling: keep sampling only the 32 x 32 tiles whose mean error is still above the target.  Afterwards the tiles may hold different sample counts
+    // (the non-uniform state): render, renderUntil, denoise, setTileShard and the frame gather then throw std::invalid_argument (requireUniformTileSamples), the
+    // reads report the leading count, and readTileSamples / readMean / readTonemapped / noiseEstimate honour the per-tile counts.  std::invalid_argument when the moments
+    // are off or do not cover the accumulation, the AOVs are on, a tile shard is set, checkEvery is 0 or the target is negative or not finite.
+    AdaptiveResult renderAdaptive(const AdaptiveParameters& params);
+    bool           tileSamplesUniform() const;
+    void           requireUniformTileSamples(const char* what) const;
+    // one count per tile of the frame's grid (tile_y * ceil(width / 32) + tile_x); a tile outside this rank's shard: 0.  -> the number of tiles
+    uint32_t readTileSamples(uint32_t* tileSamples) const;
+    // Row-major width*height*4 floats {S.rgb / float(the tile's count), 1}; rgb 0 where the tile has no sample; pixels outside this rank's tiles are zero.
+    void readMean(float* rgba);
     // Device pointer of the compact tile-major accumulation buffer (numTiles*1024 float4) and a
     // way to render into caller-owned device memory (e.g. a torch tensor used for the RCCL gather).
     void*    accumulationDevicePointer() const;
