@@ -42,6 +42,7 @@
 #include "rf_bvh_gpu.hpp"
 
 #include "rf_aabb.hpp"
+#include "rf_hip_host.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -55,14 +56,6 @@ namespace rf
 {
 namespace
 {
-#define RF_HIP(expr)                                                                                          \
-    do                                                                                                        \
-    {                                                                                                         \
-        const hipError_t _e = (expr);                                                                         \
-        if (_e != hipSuccess)                                                                                 \
-            throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(_e) + " in " #expr);      \
-    } while (0)
-
 constexpr uint32_t kBuckets = 12;
 constexpr uint32_t kMaxLeaf = 255;       // bvh.cpp:203-206: more than this is always split
 constexpr float    kTraversalCost = 0.5f;
@@ -873,16 +866,6 @@ __global__ void kEmit(const GNode* nodes, uint32_t numNodes, const BvhNode* pool
     out[g.dfs] = nd;
 }
 
-template<typename T>
-struct Dev
-{
-    T*   p = nullptr;
-    void alloc(size_t n) { RF_HIP(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(n, 1) * sizeof(T))); }
-    ~Dev()
-    {
-        if (p) (void)hipFree(p);
-    }
-};
 inline dim3 gridFor(uint64_t n, int threads = kThreads) { return dim3(static_cast<uint32_t>((n + threads - 1) / threads)); }
 } // namespace
 
@@ -905,20 +888,20 @@ Bvh buildBvhGpu(std::span<const Positions> triangles, int deviceOrdinal, float* 
     // (disjoint ranges); small tasks hold at least one triangle each; GNodes = large nodes + small roots
     const uint32_t maxSmall = n + 2;
     const uint32_t maxGNodes = 2 * n + 64;
-    Dev<Positions> dTris;
-    Dev<float4>    a0, b0, a1, b1;
-    Dev<float2>    c0, c1;
-    Dev<int32_t>   nodeOf0, nodeOf1;
-    Dev<uint32_t>  flags, scan, blockSums, inv;
-    Dev<EncBox>    rootBoxes;
-    Dev<GNode>     gnodes;
-    Dev<LevelNode> levelA, levelB;
-    Dev<Bucket>    buckets;
-    Dev<SmallTask> small;
-    Dev<Counters>  ctr;
-    Dev<BvhNode>   pool, nodesOut;
-    Dev<uint64_t>  triIdx;
-    Dev<uint8_t>   inSmall;
+    DeviceBuffer<Positions> dTris;
+    DeviceBuffer<float4>    a0, b0, a1, b1;
+    DeviceBuffer<float2>    c0, c1;
+    DeviceBuffer<int32_t>   nodeOf0, nodeOf1;
+    DeviceBuffer<uint32_t>  flags, scan, blockSums, inv;
+    DeviceBuffer<EncBox>    rootBoxes;
+    DeviceBuffer<GNode>     gnodes;
+    DeviceBuffer<LevelNode> levelA, levelB;
+    DeviceBuffer<Bucket>    buckets;
+    DeviceBuffer<SmallTask> small;
+    DeviceBuffer<Counters>  ctr;
+    DeviceBuffer<BvhNode>   pool, nodesOut;
+    DeviceBuffer<uint64_t>  triIdx;
+    DeviceBuffer<uint8_t>   inSmall;
     dTris.alloc(n);
     a0.alloc(n), b0.alloc(n), c0.alloc(n), a1.alloc(n), b1.alloc(n), c1.alloc(n);
     nodeOf0.alloc(n), nodeOf1.alloc(n);
@@ -940,7 +923,7 @@ Bvh buildBvhGpu(std::span<const Positions> triangles, int deviceOrdinal, float* 
     hipEvent_t  e0, e1;
     RF_HIP(hipEventCreate(&e0));
     RF_HIP(hipEventCreate(&e1));
-    RF_HIP(hipMemcpy(dTris.p, triangles.data(), n64 * sizeof(Positions), hipMemcpyHostToDevice));
+    RF_HIP(hipMemcpy(dTris.ptr, triangles.data(), n64 * sizeof(Positions), hipMemcpyHostToDevice));
     RF_HIP(hipEventRecord(e0, stream));
     {
         EncBox init[2];
@@ -949,38 +932,38 @@ Bvh buildBvhGpu(std::span<const Positions> triangles, int deviceOrdinal, float* 
             init[0].lo[k] = init[1].lo[k] = encodeFloat(FLT_MAX);
             init[0].hi[k] = init[1].hi[k] = encodeFloat(-FLT_MAX);
         }
-        RF_HIP(hipMemcpyAsync(rootBoxes.p, init, sizeof init, hipMemcpyHostToDevice, stream));
-        RF_HIP(hipMemsetAsync(ctr.p, 0, sizeof(Counters), stream));
-        RF_HIP(hipMemsetAsync(inSmall.p, 0, n, stream));
+        RF_HIP(hipMemcpyAsync(rootBoxes.ptr, init, sizeof init, hipMemcpyHostToDevice, stream));
+        RF_HIP(hipMemsetAsync(ctr.ptr, 0, sizeof(Counters), stream));
+        RF_HIP(hipMemsetAsync(inSmall.ptr, 0, n, stream));
     }
-    PrimStreams cur{a0.p, b0.p, c0.p}, nxt{a1.p, b1.p, c1.p};
-    int32_t *   nodeOf = nodeOf0.p, *nodeOfNext = nodeOf1.p;
-    LevelNode * level = levelA.p, *nextLevel = levelB.p;
+    PrimStreams cur{a0.ptr, b0.ptr, c0.ptr}, nxt{a1.ptr, b1.ptr, c1.ptr};
+    int32_t *   nodeOf = nodeOf0.ptr, *nodeOfNext = nodeOf1.ptr;
+    LevelNode * level = levelA.ptr, *nextLevel = levelB.ptr;
 
-    hipLaunchKernelGGL(kSetup, gridFor(n), dim3(kThreads), 0, stream, dTris.p, n, cur, nodeOf, rootBoxes.p);
-    hipLaunchKernelGGL(kRoot, dim3(1), dim3(1), 0, stream, n, rootBoxes.p, gnodes.p, level, small.p, ctr.p, nodeOf);
+    hipLaunchKernelGGL(kSetup, gridFor(n), dim3(kThreads), 0, stream, dTris.ptr, n, cur, nodeOf, rootBoxes.ptr);
+    hipLaunchKernelGGL(kRoot, dim3(1), dim3(1), 0, stream, n, rootBoxes.ptr, gnodes.ptr, level, small.ptr, ctr.ptr, nodeOf);
 
     // large phase
     std::vector<uint32_t> levelEnds; // GNode count after each level (levels are contiguous GNode index ranges)
     levelEnds.push_back(1);
     Counters h{};
-    RF_HIP(hipMemcpyAsync(&h, ctr.p, sizeof h, hipMemcpyDeviceToHost, stream));
+    RF_HIP(hipMemcpyAsync(&h, ctr.ptr, sizeof h, hipMemcpyDeviceToHost, stream));
     RF_HIP(hipStreamSynchronize(stream));
     uint32_t active = h.nextCount;
     while (active > 0)
     {
         if (active > maxLevelNodes) throw std::runtime_error("buildBvhGpu: level overflow");
-        hipLaunchKernelGGL(kClearBuckets, gridFor(static_cast<uint64_t>(active) * kBuckets), dim3(kThreads), 0, stream, buckets.p, active);
-        hipLaunchKernelGGL(kHistogram, gridFor(n), dim3(kThreads), 0, stream, n, cur, nodeOf, level, buckets.p);
-        RF_HIP(hipMemsetAsync(&ctr.p->nextCount, 0, sizeof(uint32_t), stream));
-        hipLaunchKernelGGL(kSplitLarge, gridFor(active, 64), dim3(64), 0, stream, active, level, buckets.p, gnodes.p, nextLevel, small.p, ctr.p);
-        hipLaunchKernelGGL(kFlags, gridFor(n), dim3(kThreads), 0, stream, n, cur, nodeOf, level, flags.p);
-        hipLaunchKernelGGL(kScanBlocks, dim3(scanBlocks), dim3(kThreads), 0, stream, flags.p, scan.p, n, blockSums.p);
-        hipLaunchKernelGGL(kScanSums, dim3(1), dim3(1024), 0, stream, blockSums.p, scanBlocks);
-        hipLaunchKernelGGL(kScanAdd, dim3(scanBlocks), dim3(kThreads), 0, stream, scan.p, n, blockSums.p);
-        hipLaunchKernelGGL(kInverse, gridFor(n), dim3(kThreads), 0, stream, n, nodeOf, level, flags.p, scan.p, inv.p);
-        hipLaunchKernelGGL(kScatter, gridFor(n), dim3(kThreads), 0, stream, n, cur, nxt, nodeOf, nodeOfNext, level, flags.p, scan.p, inv.p);
-        RF_HIP(hipMemcpyAsync(&h, ctr.p, sizeof h, hipMemcpyDeviceToHost, stream));
+        hipLaunchKernelGGL(kClearBuckets, gridFor(static_cast<uint64_t>(active) * kBuckets), dim3(kThreads), 0, stream, buckets.ptr, active);
+        hipLaunchKernelGGL(kHistogram, gridFor(n), dim3(kThreads), 0, stream, n, cur, nodeOf, level, buckets.ptr);
+        RF_HIP(hipMemsetAsync(&ctr.ptr->nextCount, 0, sizeof(uint32_t), stream));
+        hipLaunchKernelGGL(kSplitLarge, gridFor(active, 64), dim3(64), 0, stream, active, level, buckets.ptr, gnodes.ptr, nextLevel, small.ptr, ctr.ptr);
+        hipLaunchKernelGGL(kFlags, gridFor(n), dim3(kThreads), 0, stream, n, cur, nodeOf, level, flags.ptr);
+        hipLaunchKernelGGL(kScanBlocks, dim3(scanBlocks), dim3(kThreads), 0, stream, flags.ptr, scan.ptr, n, blockSums.ptr);
+        hipLaunchKernelGGL(kScanSums, dim3(1), dim3(1024), 0, stream, blockSums.ptr, scanBlocks);
+        hipLaunchKernelGGL(kScanAdd, dim3(scanBlocks), dim3(kThreads), 0, stream, scan.ptr, n, blockSums.ptr);
+        hipLaunchKernelGGL(kInverse, gridFor(n), dim3(kThreads), 0, stream, n, nodeOf, level, flags.ptr, scan.ptr, inv.ptr);
+        hipLaunchKernelGGL(kScatter, gridFor(n), dim3(kThreads), 0, stream, n, cur, nxt, nodeOf, nodeOfNext, level, flags.ptr, scan.ptr, inv.ptr);
+        RF_HIP(hipMemcpyAsync(&h, ctr.ptr, sizeof h, hipMemcpyDeviceToHost, stream));
         RF_HIP(hipStreamSynchronize(stream));
         if (h.numNodes > maxGNodes || h.smallCount > maxSmall) throw std::runtime_error("buildBvhGpu: node pool overflow");
         levelEnds.push_back(h.numNodes);
@@ -994,35 +977,35 @@ Bvh buildBvhGpu(std::span<const Positions> triangles, int deviceOrdinal, float* 
     const uint32_t numSmall = h.smallCount;
     if (numSmall)
     {
-        hipLaunchKernelGGL(kMarkSmall, dim3(numSmall), dim3(64), 0, stream, numSmall, small.p, inSmall.p);
-        hipLaunchKernelGGL(kSmall, dim3((numSmall + kSmallWaves - 1) / kSmallWaves), dim3(64 * kSmallWaves), 0, stream, numSmall, small.p, cur, gnodes.p,
-                           pool.p, ctr.p, triIdx.p);
+        hipLaunchKernelGGL(kMarkSmall, dim3(numSmall), dim3(64), 0, stream, numSmall, small.ptr, inSmall.ptr);
+        hipLaunchKernelGGL(kSmall, dim3((numSmall + kSmallWaves - 1) / kSmallWaves), dim3(64 * kSmallWaves), 0, stream, numSmall, small.ptr, cur, gnodes.ptr,
+                           pool.ptr, ctr.ptr, triIdx.ptr);
     }
-    hipLaunchKernelGGL(kLargeLeafIndices, gridFor(n), dim3(kThreads), 0, stream, n, cur, inSmall.p, triIdx.p);
+    hipLaunchKernelGGL(kLargeLeafIndices, gridFor(n), dim3(kThreads), 0, stream, n, cur, inSmall.ptr, triIdx.ptr);
 
     // numbering: sizes bottom-up, preorder top-down, over the level ranges of the GNode array
     const uint32_t numG = h.numNodes;
     for (size_t l = levelEnds.size(); l-- > 0;)
     {
         const uint32_t begin = l == 0 ? 0 : levelEnds[l - 1], end = levelEnds[l];
-        if (end > begin) hipLaunchKernelGGL(kSizes, gridFor(end - begin), dim3(kThreads), 0, stream, gnodes.p, begin, end);
+        if (end > begin) hipLaunchKernelGGL(kSizes, gridFor(end - begin), dim3(kThreads), 0, stream, gnodes.ptr, begin, end);
     }
     for (size_t l = 0; l < levelEnds.size(); ++l)
     {
         const uint32_t begin = l == 0 ? 0 : levelEnds[l - 1], end = levelEnds[l];
-        if (end > begin) hipLaunchKernelGGL(kPreorder, gridFor(end - begin), dim3(kThreads), 0, stream, gnodes.p, begin, end);
+        if (end > begin) hipLaunchKernelGGL(kPreorder, gridFor(end - begin), dim3(kThreads), 0, stream, gnodes.ptr, begin, end);
     }
-    hipLaunchKernelGGL(kEmit, dim3(numG), dim3(64), 0, stream, gnodes.p, numG, pool.p, nodesOut.p);
+    hipLaunchKernelGGL(kEmit, dim3(numG), dim3(64), 0, stream, gnodes.ptr, numG, pool.ptr, nodesOut.ptr);
     RF_HIP(hipGetLastError());
     RF_HIP(hipEventRecord(e1, stream));
 
     GNode root{};
-    RF_HIP(hipMemcpy(&root, gnodes.p, sizeof root, hipMemcpyDeviceToHost));
-    RF_HIP(hipMemcpy(&h, ctr.p, sizeof h, hipMemcpyDeviceToHost));
+    RF_HIP(hipMemcpy(&root, gnodes.ptr, sizeof root, hipMemcpyDeviceToHost));
+    RF_HIP(hipMemcpy(&h, ctr.ptr, sizeof h, hipMemcpyDeviceToHost));
     out.nodes.resize(root.size);
-    RF_HIP(hipMemcpy(out.nodes.data(), nodesOut.p, static_cast<size_t>(root.size) * sizeof(BvhNode), hipMemcpyDeviceToHost));
+    RF_HIP(hipMemcpy(out.nodes.data(), nodesOut.ptr, static_cast<size_t>(root.size) * sizeof(BvhNode), hipMemcpyDeviceToHost));
     std::vector<uint64_t> idx(n);
-    RF_HIP(hipMemcpy(idx.data(), triIdx.p, n64 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    RF_HIP(hipMemcpy(idx.data(), triIdx.ptr, n64 * sizeof(uint64_t), hipMemcpyDeviceToHost));
     out.triangleIndices.assign(idx.begin(), idx.end());
     out.depth = static_cast<int>(h.maxDepth);
     if (buildMsOut)

@@ -1,7 +1,8 @@
 // rf_comm.hip -- RCCL gather of tile shards + device un-tile (see rf_comm.hpp).
 #include "rf_comm.hpp"
 
-#include "rf_renderer.hpp" // tilesForRank, kTileSize
+#include "rf_hip_host.hpp"
+#include "rf_renderer.hpp" // tilesForRank, TileGrid
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -25,13 +26,6 @@ namespace rf
 {
 namespace
 {
-#define RF_HIP(expr)                                                                                          \
-    do                                                                                                        \
-    {                                                                                                         \
-        const hipError_t _e = (expr);                                                                         \
-        if (_e != hipSuccess)                                                                                 \
-            throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(_e) + " in " #expr);      \
-    } while (0)
 #define RF_NCCL(expr)                                                                                         \
     do                                                                                                        \
     {                                                                                                         \
@@ -62,33 +56,15 @@ __global__ __launch_bounds__(256) void kUntile(const float4* __restrict__ stagin
     }
 }
 
-template<typename T>
-struct DevBuf
-{
-    T*     p = nullptr;
-    size_t n = 0;
-    void   ensure(size_t count)
-    {
-        if (count <= n) return;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-        RF_HIP(hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T)));
-        n = count;
-    }
-    ~DevBuf()
-    {
-        if (p) (void)hipFree(p);
-    }
-};
 } // namespace
 
 GatherLayout gatherLayout(uint32_t width, uint32_t height, uint32_t worldSize)
 {
     GatherLayout g;
-    g.tilesX = (width + kTileSize - 1) / kTileSize;
-    g.tilesY = (height + kTileSize - 1) / kTileSize;
-    const uint32_t n = g.tilesX * g.tilesY;
+    const TileGrid grid(width, height);
+    g.tilesX = grid.tilesX;
+    g.tilesY = grid.tilesY;
+    const uint32_t n = grid.count();
     g.tileSlot.assign(n, 0);
     g.tileOwner.assign(n, 0);
     g.rankFirstTile.assign(worldSize + 1, 0);
@@ -231,9 +207,9 @@ struct TileComm::Impl
 
     uint32_t         layoutW = 0, layoutH = 0;
     GatherLayout     layout;
-    DevBuf<uint32_t> dTileSlot, dTileOwner;
-    DevBuf<float4>   staging, image;
-    DevBuf<double>   scalar;
+    DeviceBuffer<uint32_t> dTileSlot, dTileOwner;
+    DeviceBuffer<float4>   staging, image;
+    DeviceBuffer<double>   scalar;
     uint32_t         imageW = 0, imageH = 0;
     bool             firstGatherDone = false;
     // HIP events around the last exchange on the caller's stream (sends / receives + the root's un-tile): what the frame-end gather costs THIS rank
@@ -250,8 +226,8 @@ struct TileComm::Impl
         layout = gatherLayout(w, h, world);
         dTileSlot.ensure(layout.tileSlot.size());
         dTileOwner.ensure(layout.tileOwner.size());
-        RF_HIP(hipMemcpyAsync(dTileSlot.p, layout.tileSlot.data(), layout.tileSlot.size() * 4, hipMemcpyHostToDevice, stream));
-        RF_HIP(hipMemcpyAsync(dTileOwner.p, layout.tileOwner.data(), layout.tileOwner.size() * 4, hipMemcpyHostToDevice, stream));
+        RF_HIP(hipMemcpyAsync(dTileSlot.ptr, layout.tileSlot.data(), layout.tileSlot.size() * 4, hipMemcpyHostToDevice, stream));
+        RF_HIP(hipMemcpyAsync(dTileOwner.ptr, layout.tileOwner.data(), layout.tileOwner.size() * 4, hipMemcpyHostToDevice, stream));
         RF_HIP(hipStreamSynchronize(stream)); // (`layout` outlives the copy anyway; this keeps pageable-copy semantics out of the picture)
         layoutW = w;
         layoutH = h;
@@ -375,7 +351,7 @@ const void* TileComm::gatherFrame(const void* compactDevice, uint32_t width, uin
     if (isRoot)
     {
         const size_t stagingWant = static_cast<size_t>(g.rankFirstTile[m.world]) * kTilePixels, imageWant = static_cast<size_t>(width) * height;
-        if (stagingWant > m.staging.n || imageWant > m.image.n) RF_HIP(hipStreamSynchronize(stream)); // a consumer of the old buffers may still run
+        if (stagingWant > m.staging.count || imageWant > m.image.count) RF_HIP(hipStreamSynchronize(stream)); // a consumer of the old buffers may still run
         m.staging.ensure(stagingWant);
         m.image.ensure(imageWant);
         m.imageW = width;
@@ -457,7 +433,7 @@ const void* TileComm::gatherFrame(const void* compactDevice, uint32_t width, uin
                 throw std::runtime_error("local transport: rank " + std::to_string(op.peer) + " sends " + std::to_string(post->bytes) + " bytes, rank " + std::to_string(m.rank) + " expects " +
                                          std::to_string(op.countTiles * floatsPerTile * sizeof(float)) + " (the ranks disagree about the frame)");
             RF_HIP(hipStreamWaitEvent(stream, post->ready, 0));
-            RF_HIP(hipMemcpyAsync(m.staging.p + static_cast<size_t>(op.offsetTiles) * kTilePixels, post->src, post->bytes, hipMemcpyDeviceToDevice, stream));
+            RF_HIP(hipMemcpyAsync(m.staging.ptr + static_cast<size_t>(op.offsetTiles) * kTilePixels, post->src, post->bytes, hipMemcpyDeviceToDevice, stream));
             RF_HIP(hipEventRecord(post->consumed, stream));
             {
                 std::lock_guard<std::mutex> lock(f.mutex);
@@ -488,7 +464,7 @@ const void* TileComm::gatherFrame(const void* compactDevice, uint32_t width, uin
             if (op.isSend)
                 RF_NCCL(ncclSend(static_cast<const float*>(compactDevice) + op.offsetTiles * floatsPerTile, op.countTiles * floatsPerTile, ncclFloat, static_cast<int>(op.peer), m.comm, stream));
             else
-                RF_NCCL(ncclRecv(m.staging.p + static_cast<size_t>(op.offsetTiles) * kTilePixels, op.countTiles * floatsPerTile, ncclFloat, static_cast<int>(op.peer), m.comm, stream));
+                RF_NCCL(ncclRecv(m.staging.ptr + static_cast<size_t>(op.offsetTiles) * kTilePixels, op.countTiles * floatsPerTile, ncclFloat, static_cast<int>(op.peer), m.comm, stream));
         }
     }
     catch (...)
@@ -559,12 +535,12 @@ const void* TileComm::gatherFrame(const void* compactDevice, uint32_t width, uin
     }
 
     const uint32_t numTiles = g.tilesX * g.tilesY;
-    hipLaunchKernelGGL(kUntile, dim3(numTiles), dim3(256), 0, stream, m.staging.p, static_cast<const float4*>(compactDevice), loopback ? 0xFFFFFFFFu : m.rank,
-                       g.rankFirstTile[m.rank], m.dTileSlot.p, m.dTileOwner.p, width, height, g.tilesX, m.image.p);
+    hipLaunchKernelGGL(kUntile, dim3(numTiles), dim3(256), 0, stream, m.staging.ptr, static_cast<const float4*>(compactDevice), loopback ? 0xFFFFFFFFu : m.rank,
+                       g.rankFirstTile[m.rank], m.dTileSlot.ptr, m.dTileOwner.ptr, width, height, g.tilesX, m.image.ptr);
     RF_HIP(hipGetLastError());
     RF_HIP(hipEventRecord(m.exchangeStop, stream));
     m.exchangeTimed = true;
-    return m.image.p;
+    return m.image.ptr;
 }
 
 double TileComm::lastExchangeMs()
@@ -581,10 +557,10 @@ double TileComm::lastExchangeMs()
 void TileComm::readFrame(float* dstHost, void* streamHandle)
 {
     Impl& m = *mImpl;
-    if (m.image.p == nullptr || m.imageW == 0) throw std::runtime_error("no gathered frame on this rank (only the gather root has one)");
+    if (m.image.ptr == nullptr || m.imageW == 0) throw std::runtime_error("no gathered frame on this rank (only the gather root has one)");
     hipStream_t stream = static_cast<hipStream_t>(streamHandle);
     RF_HIP(hipSetDevice(m.device));
-    RF_HIP(hipMemcpyAsync(dstHost, m.image.p, static_cast<size_t>(m.imageW) * m.imageH * sizeof(float4), hipMemcpyDeviceToHost, stream));
+    RF_HIP(hipMemcpyAsync(dstHost, m.image.ptr, static_cast<size_t>(m.imageW) * m.imageH * sizeof(float4), hipMemcpyDeviceToHost, stream));
     RF_HIP(hipStreamSynchronize(stream));
 }
 
@@ -619,10 +595,10 @@ double TileComm::allReduceMax(double value, void* streamHandle)
         return f.result;
     }
     m.scalar.ensure(2);
-    RF_HIP(hipMemcpyAsync(m.scalar.p, &value, sizeof value, hipMemcpyHostToDevice, stream));
-    RF_NCCL(ncclAllReduce(m.scalar.p, m.scalar.p + 1, 1, ncclDouble, ncclMax, m.comm, stream));
+    RF_HIP(hipMemcpyAsync(m.scalar.ptr, &value, sizeof value, hipMemcpyHostToDevice, stream));
+    RF_NCCL(ncclAllReduce(m.scalar.ptr, m.scalar.ptr + 1, 1, ncclDouble, ncclMax, m.comm, stream));
     double out = 0.0;
-    RF_HIP(hipMemcpyAsync(&out, m.scalar.p + 1, sizeof out, hipMemcpyDeviceToHost, stream));
+    RF_HIP(hipMemcpyAsync(&out, m.scalar.ptr + 1, sizeof out, hipMemcpyDeviceToHost, stream));
     RF_HIP(hipStreamSynchronize(stream));
     return out;
 }

@@ -136,22 +136,13 @@ __global__ __launch_bounds__(kDenoiseBlock) void kDenoiseAtrous(const float4* eI
 
 void DenoiseWork::reserve(uint64_t n, hipStream_t stream)
 {
-    if (n <= pixels) return;
+    if (n <= bgra.count) return; // (allocated last: it has room only when every buffer has)
     RF_HIP(hipStreamSynchronize(stream)); // (a smaller set may still be in use by the last run)
-    release();
-    float4** f4[] = {&e[0], &e[1], &guide, &albedo, &out};
-    for (float4** b : f4) RF_HIP(hipMalloc(reinterpret_cast<void**>(b), n * sizeof(float4)));
-    RF_HIP(hipMalloc(reinterpret_cast<void**>(&bgra), n * sizeof(uint32_t)));
-    pixels = n;
-}
-
-void DenoiseWork::release()
-{
-    for (void* b : {static_cast<void*>(e[0]), static_cast<void*>(e[1]), static_cast<void*>(guide), static_cast<void*>(albedo), static_cast<void*>(out), static_cast<void*>(bgra)})
-        if (b) (void)hipFree(b);
-    e[0] = e[1] = guide = albedo = out = nullptr;
-    bgra = nullptr;
-    pixels = 0;
+    DeviceBuffer<float4>* const f4[] = {&e[0], &e[1], &guide, &albedo, &out};
+    for (auto* b : f4) b->release(); // (the whole set goes before any of the new one comes)
+    bgra.release();
+    for (auto* b : f4) b->alloc(n);
+    bgra.alloc(n);
 }
 
 void enqueueDenoise(hipStream_t stream, DenoiseWork& w, const float4* colorSum, const float4* albedoCoverage, const float4* normalDepth, uint32_t width,
@@ -163,10 +154,10 @@ void enqueueDenoise(hipStream_t stream, DenoiseWork& w, const float4* colorSum, 
     const dim3  prepGrid((n + 255) / 256);
     if (p.iterations == 0)
         hipLaunchKernelGGL(kDenoisePrep, prepGrid, dim3(256), 0, stream, colorSum, albedoCoverage, normalDepth, width, height, tilesX, nf, static_cast<float4*>(nullptr),
-                           static_cast<float4*>(nullptr), static_cast<float4*>(nullptr), w.out);
+                           static_cast<float4*>(nullptr), static_cast<float4*>(nullptr), w.out.ptr);
     else
     {
-        hipLaunchKernelGGL(kDenoisePrep, prepGrid, dim3(256), 0, stream, colorSum, albedoCoverage, normalDepth, width, height, tilesX, nf, w.e[0], w.guide, w.albedo,
+        hipLaunchKernelGGL(kDenoisePrep, prepGrid, dim3(256), 0, stream, colorSum, albedoCoverage, normalDepth, width, height, tilesX, nf, w.e[0].ptr, w.guide.ptr, w.albedo.ptr,
                            static_cast<float4*>(nullptr));
         const dim3 grid((width + 15) / 16, (height + 15) / 16);
         for (uint32_t i = 0; i < p.iterations; ++i)
@@ -174,46 +165,33 @@ void enqueueDenoise(hipStream_t stream, DenoiseWork& w, const float4* colorSum, 
             const bool  last = i + 1 == p.iterations;
             const float sc2 = (p.sigmaColor * p.sigmaColor) * std::ldexp(1.0f, -static_cast<int>(i)); // (exact: a power of two)
             const float szs = p.sigmaDepth * static_cast<float>(1u << i);
-            hipLaunchKernelGGL(kDenoiseAtrous, grid, dim3(kDenoiseBlock), 0, stream, w.e[i & 1u], w.guide, w.albedo, last ? w.out : w.e[(i + 1) & 1u], width, height,
+            hipLaunchKernelGGL(kDenoiseAtrous, grid, dim3(kDenoiseBlock), 0, stream, w.e[i & 1u].ptr, w.guide.ptr, w.albedo.ptr, last ? w.out.ptr : w.e[(i + 1) & 1u].ptr, width, height,
                                static_cast<int>(1u << i), sc2, p.sigmaNormal, szs, last ? 1u : 0u);
         }
     }
-    hipLaunchKernelGGL(tonemapKernel(), dim3((n + 255) / 256), dim3(256), 0, stream, static_cast<const float4*>(w.out), n, 1u, exposure, w.bgra);
+    hipLaunchKernelGGL(tonemapKernel(), dim3((n + 255) / 256), dim3(256), 0, stream, static_cast<const float4*>(w.out.ptr), n, 1u, exposure, w.bgra.ptr);
     RF_HIP(hipGetLastError());
 }
 
 void denoiseImages(int deviceOrdinal, uint32_t width, uint32_t height, uint32_t samples, const float* colorSum, const float* albedoCoverage, const float* normalDepth,
                    const DenoiseParameters& params, float exposure, float* outRgba, uint32_t* outBgra8)
 {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) throw std::runtime_error("rayfinder_amd: no HIP device available (this library has no CPU fallback)");
-    if (deviceOrdinal < 0 || deviceOrdinal >= count) throw std::invalid_argument("device ordinal out of range");
-    RF_HIP(hipSetDevice(deviceOrdinal));
+    requireDevice(deviceOrdinal);
     const uint64_t n = static_cast<uint64_t>(width) * height;
-    struct Scope
-    {
-        hipStream_t stream = nullptr;
-        float4*     in[3] = {};
-        DenoiseWork work;
-        ~Scope()
-        {
-            if (stream) (void)hipStreamSynchronize(stream);
-            for (float4* b : in)
-                if (b) (void)hipFree(b);
-            work.release();
-            if (stream) (void)hipStreamDestroy(stream);
-        }
-    } s;
-    RF_HIP(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
-    const float* src[3] = {colorSum, albedoCoverage, normalDepth};
+    // (leaving the scope: the stream is synchronised, the buffers are freed, the stream is destroyed -- ScopedStream)
+    ScopedStream         stream;
+    DeviceBuffer<float4> in[3];
+    DenoiseWork          work;
+    ScopedStream::Drain  drain{stream};
+    const float*         src[3] = {colorSum, albedoCoverage, normalDepth};
     for (int b = 0; b < 3; ++b)
     {
-        RF_HIP(hipMalloc(reinterpret_cast<void**>(&s.in[b]), n * sizeof(float4)));
-        RF_HIP(hipMemcpyAsync(s.in[b], src[b], n * sizeof(float4), hipMemcpyHostToDevice, s.stream));
+        in[b].alloc(n);
+        RF_HIP(hipMemcpyAsync(in[b].ptr, src[b], n * sizeof(float4), hipMemcpyHostToDevice, stream.handle));
     }
-    enqueueDenoise(s.stream, s.work, s.in[0], s.in[1], s.in[2], width, height, 0u, samples, params, exposure);
-    if (outRgba) RF_HIP(hipMemcpyAsync(outRgba, s.work.out, n * sizeof(float4), hipMemcpyDeviceToHost, s.stream));
-    if (outBgra8) RF_HIP(hipMemcpyAsync(outBgra8, s.work.bgra, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream));
-    RF_HIP(hipStreamSynchronize(s.stream));
+    enqueueDenoise(stream.handle, work, in[0].ptr, in[1].ptr, in[2].ptr, width, height, 0u, samples, params, exposure);
+    if (outRgba) RF_HIP(hipMemcpyAsync(outRgba, work.out.ptr, n * sizeof(float4), hipMemcpyDeviceToHost, stream.handle));
+    if (outBgra8) RF_HIP(hipMemcpyAsync(outBgra8, work.bgra.ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream.handle));
+    RF_HIP(hipStreamSynchronize(stream.handle));
 }
 } // namespace rf

@@ -2,6 +2,7 @@
 // rf_renderer_denoise (inputs: the handle's own compact tile-major sums) and the standalone rf_denoise_images (inputs: row-major sums).
 #pragma once
 
+#include "rf_hip_host.hpp"
 #include "rf_renderer.hpp"
 
 #include <hip/hip_runtime.h>
@@ -12,17 +13,14 @@ namespace rf
 {
 struct DenoiseWork
 {
-    float4*   e[2] = {};          // ping-pong demodulated irradiance {e.rgb, ℓ}
-    float4*   guide = nullptr;    // {n.xyz, z}; z <= 0 (or NaN): background
-    float4*   albedo = nullptr;   // {a + εa, 0}
-    float4*   out = nullptr;      // the denoised mean {rgb, 1}
-    uint32_t* bgra = nullptr;     // kTonemap of `out` (accumulatedSamples = 1)
-    uint64_t  pixels = 0;         // capacity
+    DeviceBuffer<float4>   e[2];   // ping-pong demodulated irradiance {e.rgb, ℓ}
+    DeviceBuffer<float4>   guide;  // {n.xyz, z}; z <= 0 (or NaN): background
+    DeviceBuffer<float4>   albedo; // {a + εa, 0}
+    DeviceBuffer<float4>   out;    // the denoised mean {rgb, 1}
+    DeviceBuffer<uint32_t> bgra;   // kTonemap of `out` (accumulatedSamples = 1)
 
-    // room for `pixels` (stream-synchronises before it frees a smaller set)
+    // room for `pixels` in every buffer (stream-synchronises before it frees a smaller set)
     void reserve(uint64_t pixels, hipStream_t stream);
-    void release();
-    ~DenoiseWork() { release(); }
 };
 
 // Enqueue kDenoisePrep, the L kDenoiseAtrous passes and kTonemap on `stream`.  tilesX != 0: the sums are compact tile-major buffers holding every tile of the

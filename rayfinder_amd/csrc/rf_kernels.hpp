@@ -11,6 +11,7 @@
 #include "rf_camera.hpp"
 #include "rf_data.hpp"
 #include "rf_device.hpp"
+#include "rf_hip_host.hpp"
 #include "rf_wide.hpp"
 
 #include <hip/hip_runtime.h>
@@ -30,14 +31,6 @@ namespace rf
 {
 namespace kern
 {
-#define RF_HIP(expr)                                                                                          \
-    do                                                                                                        \
-    {                                                                                                         \
-        const hipError_t _e = (expr);                                                                         \
-        if (_e != hipSuccess)                                                                                 \
-            throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(_e) + " in " #expr);      \
-    } while (0)
-
 struct __attribute__((packed, aligned(4))) P3
 {
     float x, y, z;

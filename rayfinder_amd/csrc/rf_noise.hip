@@ -265,23 +265,20 @@ AccumulateMomentsKernel accumulateMomentsKernel(bool runs) { return runs ? kAccu
 
 void NoiseWork::reserve(uint64_t nTiles, uint64_t nMap, hipStream_t stream)
 {
-    if (nTiles <= tiles && nMap <= mapPixels) return;
+    if (nTiles <= tiles && nMap <= errorMap.count) return;
     RF_HIP(hipStreamSynchronize(stream)); // (a smaller set may still be in use by the last run)
-    nTiles = std::max(nTiles, tiles), nMap = std::max(nMap, mapPixels);
-    release();
-    RF_HIP(hipMalloc(reinterpret_cast<void**>(&tileSumMax), 2 * nTiles * sizeof(float)));
-    RF_HIP(hipMalloc(reinterpret_cast<void**>(&tileCounts), 2 * nTiles * sizeof(uint32_t)));
-    if (nMap) RF_HIP(hipMalloc(reinterpret_cast<void**>(&errorMap), nMap * sizeof(float)));
-    tiles = nTiles, mapPixels = nMap;
+    nTiles = std::max(nTiles, tiles), nMap = std::max<uint64_t>(nMap, errorMap.count);
+    release(); // (the whole set goes before any of the new one comes)
+    tileSumMax.alloc(2 * nTiles);
+    tileCounts.alloc(2 * nTiles);
+    errorMap.alloc(nMap);
+    tiles = nTiles;
 }
 
 void NoiseWork::release()
 {
-    for (void* b : {static_cast<void*>(tileSumMax), static_cast<void*>(tileCounts), static_cast<void*>(errorMap)})
-        if (b) (void)hipFree(b);
-    tileSumMax = errorMap = nullptr;
-    tileCounts = nullptr;
-    tiles = mapPixels = 0;
+    tileSumMax.release(), tileCounts.release(), errorMap.release();
+    tiles = 0;
 }
 
 NoiseEstimate runNoiseEstimate(hipStream_t stream, NoiseWork& w, const float4* colorSum, const float4* sumSq, uint32_t width, uint32_t height, bool tileMajor, uint32_t samples,
@@ -293,7 +290,7 @@ NoiseEstimate runNoiseEstimate(hipStream_t stream, NoiseWork& w, const float4* c
 NoiseEstimate runNoiseEstimateTiles(hipStream_t stream, NoiseWork& w, const float4* colorSum, const float4* sumSq, uint32_t width, uint32_t height, bool tileMajor,
                                     const TileSelection& sel, uint32_t samples, float* errorMap, float* tileSum, float* tileMax, uint32_t* tilePixels)
 {
-    const uint32_t tilesX = (width + kTileSize - 1) / kTileSize, tilesY = (height + kTileSize - 1) / kTileSize, tiles = tilesX * tilesY;
+    const uint32_t tilesX = TileGrid(width, height).tilesX, tiles = TileGrid(width, height).count();
     const uint32_t listed = sel.listDevice ? sel.listCount : tiles;
     const uint64_t n = static_cast<uint64_t>(width) * height;
     NoiseEstimate  out;
@@ -301,21 +298,21 @@ NoiseEstimate runNoiseEstimateTiles(hipStream_t stream, NoiseWork& w, const floa
     if (listed == 0) return out;
     w.reserve(tiles, errorMap ? n : 0, stream);
     const float nf = static_cast<float>(samples), nf1 = nf - 1.0f;
-    float* const map = errorMap ? w.errorMap : static_cast<float*>(nullptr);
+    float* const map = errorMap ? w.errorMap.ptr : static_cast<float*>(nullptr);
     if (sel.listDevice == nullptr && sel.tileSamplesDevice == nullptr)
-        hipLaunchKernelGGL(kNoiseEstimate, dim3(tiles), dim3(256), 0, stream, colorSum, sumSq, width, height, tilesX, tileMajor ? 1u : 0u, nf, nf1, map, w.tileSumMax,
-                           w.tileSumMax + w.tiles, w.tileCounts, w.tileCounts + w.tiles);
+        hipLaunchKernelGGL(kNoiseEstimate, dim3(tiles), dim3(256), 0, stream, colorSum, sumSq, width, height, tilesX, tileMajor ? 1u : 0u, nf, nf1, map, w.tileSumMax.ptr,
+                           w.tileSumMax.ptr + w.tiles, w.tileCounts.ptr, w.tileCounts.ptr + w.tiles);
     else
         hipLaunchKernelGGL(kNoiseEstimateTiles, dim3(listed), dim3(256), 0, stream, colorSum, sumSq, width, height, tilesX, tileMajor ? 1u : 0u, sel.listDevice, sel.tileSamplesDevice,
-                           nf, map, w.tileSumMax, w.tileSumMax + w.tiles, w.tileCounts, w.tileCounts + w.tiles);
+                           nf, map, w.tileSumMax.ptr, w.tileSumMax.ptr + w.tiles, w.tileCounts.ptr, w.tileCounts.ptr + w.tiles);
     RF_HIP(hipGetLastError());
     std::vector<float>    sums(tiles), maxima(tiles);
     std::vector<uint32_t> pixels(tiles), nonfinite(tiles);
-    RF_HIP(hipMemcpyAsync(sums.data(), w.tileSumMax, tiles * sizeof(float), hipMemcpyDeviceToHost, stream));
-    RF_HIP(hipMemcpyAsync(maxima.data(), w.tileSumMax + w.tiles, tiles * sizeof(float), hipMemcpyDeviceToHost, stream));
-    RF_HIP(hipMemcpyAsync(pixels.data(), w.tileCounts, tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    RF_HIP(hipMemcpyAsync(nonfinite.data(), w.tileCounts + w.tiles, tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    if (errorMap) RF_HIP(hipMemcpyAsync(errorMap, w.errorMap, n * sizeof(float), hipMemcpyDeviceToHost, stream));
+    RF_HIP(hipMemcpyAsync(sums.data(), w.tileSumMax.ptr, tiles * sizeof(float), hipMemcpyDeviceToHost, stream));
+    RF_HIP(hipMemcpyAsync(maxima.data(), w.tileSumMax.ptr + w.tiles, tiles * sizeof(float), hipMemcpyDeviceToHost, stream));
+    RF_HIP(hipMemcpyAsync(pixels.data(), w.tileCounts.ptr, tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    RF_HIP(hipMemcpyAsync(nonfinite.data(), w.tileCounts.ptr + w.tiles, tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    if (errorMap) RF_HIP(hipMemcpyAsync(errorMap, w.errorMap.ptr, n * sizeof(float), hipMemcpyDeviceToHost, stream));
     RF_HIP(hipStreamSynchronize(stream));
     // the frame (or the listed tiles), on the host: tile sums added in f64 in ascending tile order; the first tile that attains the maximum
     const auto tileAt = [&](uint32_t i) { return sel.listDevice ? sel.listHost[i] : i; };
@@ -347,42 +344,28 @@ NoiseEstimate noiseEstimateImages(int deviceOrdinal, uint32_t width, uint32_t he
 NoiseEstimate noiseEstimateTiles(int deviceOrdinal, uint32_t width, uint32_t height, const uint32_t* tileSamples, uint32_t samples, const float* colorSum, const float* sumSq,
                                  float* errorMap, float* tileSum, float* tileMax)
 {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) throw std::runtime_error("rayfinder_amd: no HIP device available (this library has no CPU fallback)");
-    if (deviceOrdinal < 0 || deviceOrdinal >= count) throw std::invalid_argument("device ordinal out of range");
-    RF_HIP(hipSetDevice(deviceOrdinal));
+    requireDevice(deviceOrdinal);
     const uint64_t n = static_cast<uint64_t>(width) * height;
-    const uint32_t tiles = ((width + kTileSize - 1) / kTileSize) * ((height + kTileSize - 1) / kTileSize);
-    struct Scope
-    {
-        hipStream_t stream = nullptr;
-        float4*     in[2] = {};
-        uint32_t*   counts = nullptr;
-        NoiseWork   work;
-        ~Scope()
-        {
-            if (stream) (void)hipStreamSynchronize(stream);
-            for (float4* b : in)
-                if (b) (void)hipFree(b);
-            if (counts) (void)hipFree(counts);
-            work.release();
-            if (stream) (void)hipStreamDestroy(stream);
-        }
-    } s;
-    RF_HIP(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
-    const float* src[2] = {colorSum, sumSq};
+    const uint32_t tiles = TileGrid(width, height).count();
+    // (leaving the scope: the stream is synchronised, the buffers are freed, the stream is destroyed -- ScopedStream)
+    ScopedStream           stream;
+    DeviceBuffer<float4>   in[2];
+    DeviceBuffer<uint32_t> counts;
+    NoiseWork              work;
+    ScopedStream::Drain    drain{stream};
+    const float*           src[2] = {colorSum, sumSq};
     for (int b = 0; b < 2; ++b)
     {
-        RF_HIP(hipMalloc(reinterpret_cast<void**>(&s.in[b]), n * sizeof(float4)));
-        RF_HIP(hipMemcpyAsync(s.in[b], src[b], n * sizeof(float4), hipMemcpyHostToDevice, s.stream));
+        in[b].alloc(n);
+        RF_HIP(hipMemcpyAsync(in[b].ptr, src[b], n * sizeof(float4), hipMemcpyHostToDevice, stream.handle));
     }
     TileSelection sel;
     if (tileSamples)
     {
-        RF_HIP(hipMalloc(reinterpret_cast<void**>(&s.counts), tiles * sizeof(uint32_t)));
-        RF_HIP(hipMemcpyAsync(s.counts, tileSamples, tiles * sizeof(uint32_t), hipMemcpyHostToDevice, s.stream));
-        sel.tileSamplesDevice = s.counts;
+        counts.alloc(tiles);
+        RF_HIP(hipMemcpyAsync(counts.ptr, tileSamples, tiles * sizeof(uint32_t), hipMemcpyHostToDevice, stream.handle));
+        sel.tileSamplesDevice = counts.ptr;
     }
-    return runNoiseEstimateTiles(s.stream, s.work, s.in[0], s.in[1], width, height, false, sel, samples, errorMap, tileSum, tileMax, nullptr);
+    return runNoiseEstimateTiles(stream.handle, work, in[0].ptr, in[1].ptr, width, height, false, sel, samples, errorMap, tileSum, tileMax, nullptr);
 }
 } // namespace rf

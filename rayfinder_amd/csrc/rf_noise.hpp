@@ -25,15 +25,14 @@ TileMeanKernel tileMeanKernel();
 // Device buffers of one estimate: per-tile {sum, max} and {pixels, non-finite pixels}, and the row-major error map (only when a caller asks for it)
 struct NoiseWork
 {
-    float*    tileSumMax = nullptr; // [tiles] sums, then [tiles] maxima
-    uint32_t* tileCounts = nullptr; // [tiles] in-frame pixels, then [tiles] non-finite pixels
-    float*    errorMap = nullptr;   // width * height
-    uint64_t  tiles = 0, mapPixels = 0;
+    DeviceBuffer<float>    tileSumMax; // [tiles] sums, then [tiles] maxima
+    DeviceBuffer<uint32_t> tileCounts; // [tiles] in-frame pixels, then [tiles] non-finite pixels
+    DeviceBuffer<float>    errorMap;   // width * height
+    uint64_t               tiles = 0;  // capacity in tiles (the map's: errorMap.count)
 
     // room for `tiles` tiles and, if wanted, a map of `pixels` (stream-synchronises before it frees a smaller set)
     void reserve(uint64_t tiles, uint64_t mapPixels, hipStream_t stream);
     void release();
-    ~NoiseWork() { release(); }
 };
 
 // Enqueue kNoiseEstimate on `stream`, copy the per-tile results (and the map) back, wait, and reduce them on the host (the definition: include/rayfinder_amd.h).

@@ -48,31 +48,6 @@ bool operator==(const RenderParameters& a, const RenderParameters& b)
 
 namespace
 {
-template<typename T>
-struct DeviceBuffer
-{
-    T*     ptr = nullptr;
-    size_t count = 0;
-    void   alloc(size_t n)
-    {
-        release();
-        count = n;
-        if (n) RF_HIP(hipMalloc(reinterpret_cast<void**>(&ptr), n * sizeof(T)));
-    }
-    void upload(const T* src, size_t n)
-    {
-        alloc(n);
-        if (n) RF_HIP(hipMemcpy(ptr, src, n * sizeof(T), hipMemcpyHostToDevice));
-    }
-    void release()
-    {
-        if (ptr) (void)hipFree(ptr);
-        ptr = nullptr;
-        count = 0;
-    }
-    ~DeviceBuffer() { release(); }
-};
-
 // Morton (Z-order) key of a tile position
 uint32_t tileMortonKey(uint32_t tx, uint32_t ty)
 {
@@ -90,8 +65,7 @@ uint32_t tileMortonKey(uint32_t tx, uint32_t ty)
 
 std::vector<uint32_t> tilesForRank(uint32_t width, uint32_t height, uint32_t rank, uint32_t worldSize)
 {
-    const uint32_t tilesX = (width + kTileSize - 1) / kTileSize, tilesY = (height + kTileSize - 1) / kTileSize;
-    const uint32_t n = tilesX * tilesY;
+    const uint32_t tilesX = TileGrid(width, height).tilesX, n = TileGrid(width, height).count();
     std::vector<uint32_t> order(n);
     for (uint32_t i = 0; i < n; ++i) order[i] = i;
     if (worldSize > 1)
@@ -114,7 +88,14 @@ std::vector<uint32_t> tilesForRank(uint32_t width, uint32_t height, uint32_t ran
 
 void untileHost(const float* compact, const uint32_t* tileIds, uint32_t numTiles, uint32_t width, uint32_t height, float* image)
 {
-    const uint32_t tilesX = (width + kTileSize - 1) / kTileSize;
+    untileHostTexels(compact, tileIds, numTiles, width, height, 4 * sizeof(float), image);
+}
+
+void untileHostTexels(const void* compact, const uint32_t* tileIds, uint32_t numTiles, uint32_t width, uint32_t height, size_t texelBytes, void* image)
+{
+    const uint32_t tilesX = TileGrid(width, height).tilesX;
+    const auto*    src = static_cast<const unsigned char*>(compact);
+    auto*          dst = static_cast<unsigned char*>(image);
     for (uint32_t t = 0; t < numTiles; ++t)
     {
         const uint32_t tx = tileIds[t] % tilesX, ty = tileIds[t] / tilesX;
@@ -124,10 +105,52 @@ void untileHost(const float* compact, const uint32_t* tileIds, uint32_t numTiles
             const uint32_t x = tx * kTileSize + (block & 3u) * 8u + (lane & 7u);
             const uint32_t y = ty * kTileSize + (block >> 2) * 8u + (lane >> 3);
             if (x >= width || y >= height) continue;
-            std::memcpy(image + 4 * (static_cast<size_t>(y) * width + x), compact + 4 * (static_cast<size_t>(t) * 1024 + w), 16);
+            std::memcpy(dst + texelBytes * (static_cast<size_t>(y) * width + x), src + texelBytes * (static_cast<size_t>(t) * 1024 + w), texelBytes);
         }
     }
 }
+
+// One sum over the samples of an accumulation, and its books: the image (always on; its buffer is the handle's own or a bound one, Impl::image), the first-hit
+// AOV sums (two buffers), the radiance second moments (one).  All compact tile-major float4 buffers of the shard, summed in sample order.
+// What the driver relies on (Impl::restartAccumulation, Impl::clearStaleSums and Impl::step are the only writers):
+//   * dirty is raised only together with samples = 0, and cleared only by the zeroing in front of the next sample: dirty implies samples == 0;
+//   * the image's dirty flag is raised only by restartAccumulation, which sets accumulated = 0 and restarts every channel: a dirty image implies
+//     accumulated == 0 and every channel dirty.  (A read may zero a dirty image and clear the flag before any sample: accumulated == 0 does not imply dirty);
+//   * hence covers(accumulated) with accumulated != 0 says that the channel was on for every sample of the accumulation, whatever the image's flag says.
+struct SumChannel
+{
+    bool                 on = false;
+    bool                 dirty = true; // restarted: to be zeroed before the next sample
+    uint32_t             samples = 0;  // samples summed since it was last restarted
+    DeviceBuffer<float4> buffers[2];   // the AOVs: {albedo.rgb, coverage}, {normal.xyz, depth}; the moments: [0]; the image: none (Impl::image)
+    uint32_t             numBuffers = 0;
+
+    SumChannel(bool on_, uint32_t numBuffers_) : on(on_), numBuffers(numBuffers_) {}
+    // the sums start again: zeroed before the next sample, sized for the shard then
+    void restart()
+    {
+        samples = 0;
+        dirty = true;
+    }
+    void release()
+    {
+        for (auto& b : buffers) b.release();
+    }
+    bool covers(uint32_t accumulated) const { return !dirty && samples == accumulated; }
+    bool empty() const { return !on || dirty || samples == 0u; }
+    // before the first sample after a restart: room for the shard (the stream is waited for before a smaller buffer is freed), then zeros
+    void zeroIfStale(hipStream_t stream, uint64_t pixelsPadded)
+    {
+        if (!on || !dirty) return;
+        if (numBuffers != 0u && buffers[0].count < pixelsPadded)
+        {
+            RF_HIP(hipStreamSynchronize(stream)); // (a smaller buffer may still be read by the last batch or estimate)
+            for (uint32_t i = 0; i < numBuffers; ++i) buffers[i].alloc(pixelsPadded);
+        }
+        for (uint32_t i = 0; i < numBuffers; ++i) RF_HIP(hipMemsetAsync(buffers[i].ptr, 0, pixelsPadded * sizeof(float4), stream));
+        dirty = false;
+    }
+};
 
 // ------------------------------------------------------------------------------------------------
 struct Renderer::Impl
@@ -163,26 +186,23 @@ struct Renderer::Impl
     DeviceBuffer<float4>    ownedImage;
     float4*                 image = nullptr; // compact tile-major accumulation buffer
     uint64_t                imageBytes = 0;
-    bool                    imageDirty = true; // needs zeroing before the next sample
-    // first-hit AOVs (rf_renderer_set_aovs; off by default: nothing below is allocated or launched then).  Sums in sample order like the image, in two compact
-    // tile-major float4 buffers, over the aovSamples samples traced since they were last cleared -- on the image's events (aovDirty is set wherever imageDirty is
-    // raised by a new accumulation) and whenever the flags change
-    uint32_t                aovFlags = 0, aovSamples = 0;
-    bool                    aovDirty = true;
-    DeviceBuffer<float4>    aovAlbedoCoverage, aovNormalDepth;
-    // the denoiser (rf_renderer_denoise): its work buffers, allocated by the first denoise, and the snapshot they hold -- valid until the AOV sums are cleared
+    // The sums (SumChannel).  The image restarts on the events of restartAccumulation; the other two on those and whenever their switch changes.
+    SumChannel              imageSums{true, 0};
+    // first-hit AOVs (rf_renderer_set_aovs; off by default: nothing is allocated or launched then)
+    SumChannel              aovSums{false, 2};
+    // radiance second moments (rf_renderer_set_moments; off by default: nothing is allocated or launched then): {sum r r per channel, 0}
+    SumChannel              momentSums{false, 1};
+    float4*                 aovAlbedoCoverage() const { return aovSums.buffers[0].ptr; }
+    float4*                 aovNormalDepth() const { return aovSums.buffers[1].ptr; }
+    float4*                 moments() const { return momentSums.buffers[0].ptr; }
+    // the denoiser (rf_renderer_denoise): its work buffers, allocated by the first denoise, and the snapshot they hold -- valid until the AOV sums are restarted
     DenoiseWork             denoiseWork;
     bool                    denoisedValid = false;
     uint32_t                denoisedSamples = 0;
-    // radiance second moments (rf_renderer_set_moments; off by default: nothing below is allocated or launched then).  One compact tile-major float4 buffer of
-    // {sum r r per channel, 0} in sample order, over the momentSamples samples traced since it was last cleared -- on the image's events and when the switch changes
-    bool                    momentsOn = false, momentsDirty = true;
-    uint32_t                momentSamples = 0;
-    DeviceBuffer<float4>    moments;
     NoiseWork               noiseWork; // the estimate's device buffers, allocated by the first rf_renderer_noise_estimate
     // tile-adaptive sampling (rf_renderer_render_adaptive).  tileSamples[t], t in the frame's tile numbering, is the sample count of tile t; EMPTY = the uniform
     // state: every tile holds `accumulated` samples (the only state a handle that never called render_adaptive is ever in).  Non-empty: the counts differ, `accumulated`
-    // is the leading count L, and the tiles still at L are the only ones a later render_adaptive samples.  Cleared with the image.
+    // is the leading count L, and the tiles still at L are the only ones a later render_adaptive samples.  Cleared by restartAccumulation.
     std::vector<uint32_t>   tileSamples;
     DeviceBuffer<uint32_t>  tileSamplesDevice; // the counts for the per-tile reads (mean, tonemap, estimate), uploaded by them
     DeviceBuffer<float4>    meanImage;         // rf_renderer_read_mean / the non-uniform rf_renderer_read_tonemapped: compact tile-major, allocated by the first read
@@ -315,10 +335,10 @@ struct Renderer::Impl
     static constexpr uint64_t kBytesPerPath = 8 * sizeof(P3) + 2 * sizeof(float4) + 5 * sizeof(uint32_t);
     // ... plus the 32-byte AOV record while the first-hit AOVs are on
     static constexpr uint64_t kAovBytesPerPath = 2 * sizeof(float4);
-    uint64_t bytesPerPath() const { return kBytesPerPath + (aovFlags != 0u ? kAovBytesPerPath : 0u); }
+    uint64_t bytesPerPath() const { return kBytesPerPath + (aovSums.on ? kAovBytesPerPath : 0u); }
     uint64_t pathStateBytes() const { return allocatedPaths * kBytesPerPath + sAov.count * sizeof(float4); }
     // the path state holds a batch of `paths` (the AOV records included while the AOVs are on)
-    bool pathStateHolds(uint64_t paths) const { return paths <= allocatedPaths && (aovFlags == 0u || sAov.count >= 2 * paths); }
+    bool pathStateHolds(uint64_t paths) const { return paths <= allocatedPaths && (!aovSums.on || sAov.count >= 2 * paths); }
 
     void releasePathState()
     {
@@ -353,7 +373,7 @@ struct Renderer::Impl
         const bool ok = tryAlloc(sRayO, paths) && tryAlloc(sRayD, paths) && tryAlloc(sRayD2, paths) && tryAlloc(sThr, paths) && tryAlloc(sThr2, paths) &&
                         tryAlloc(sRad, paths) && tryAlloc(sHit, paths) && tryAlloc(sPending, paths) && tryAlloc(sNoise, paths) && tryAlloc(sNoise2, paths) &&
                         tryAlloc(queueA, paths) && tryAlloc(queueB, paths) && tryAlloc(missQueue, paths) && tryAlloc(missSlots, paths) && tryAlloc(shadowList, paths) &&
-                        (aovFlags == 0u || tryAlloc(sAov, 2 * paths));
+                        (!aovSums.on || tryAlloc(sAov, 2 * paths));
         if (!ok)
         {
             releasePathState();
@@ -378,20 +398,9 @@ struct Renderer::Impl
         tiles = tilesForRank(params.width, params.height, rank, worldSize);
         tileIds.upload(tiles.data(), tiles.size());
         const uint64_t pixelsPadded = static_cast<uint64_t>(tiles.size()) * 1024;
-        {
-            const uint32_t tilesX = (params.width + kTileSize - 1) / kTileSize;
-            validPixels = 0;
-            std::vector<uint32_t> before;
-            before.reserve(tiles.size() + 1);
-            for (const uint32_t t : tiles)
-            {
-                const uint32_t x0 = (t % tilesX) * kTileSize, y0 = (t / tilesX) * kTileSize;
-                before.push_back(static_cast<uint32_t>(validPixels));
-                validPixels += static_cast<uint64_t>(std::min(kTileSize, params.width - x0)) * std::min(kTileSize, params.height - y0);
-            }
-            before.push_back(static_cast<uint32_t>(validPixels));
-            tileValidBefore.upload(before.data(), before.size());
-        }
+        const TileGrid::Prefix valid = grid().validPrefix(tiles);
+        validPixels = valid.total;
+        tileValidBefore.upload(valid.before.data(), valid.before.size());
         if (image == nullptr || image == ownedImage.ptr)
         {
             ownedImage.alloc(std::max<uint64_t>(pixelsPadded, 1));
@@ -402,26 +411,46 @@ struct Renderer::Impl
             throw std::runtime_error("bound accumulation buffer is too small for this shard");
         }
         if (image == ownedImage.ptr) imageBytes = pixelsPadded * sizeof(float4);
-        accumulated = 0;
-        imageDirty = true;
-        tileSamples.clear();
-        clearAovs();
-        clearMoments();
+        restartAccumulation();
     }
 
-    // the AOV sums start again (with the image, or when the flags change): zeroed before the next sample, sized for the shard then
-    void clearAovs()
+    // A new accumulation (new parameters, another shard, another accumulation buffer): no sample, every tile at the same count, every sum to be zeroed before the
+    // next sample, no denoised snapshot.  The only place that does this.
+    void restartAccumulation()
     {
-        aovSamples = 0;
-        aovDirty = true;
+        accumulated = 0;
+        tileSamples.clear();
+        imageSums.restart();
+        restartAovs();
+        momentSums.restart();
+    }
+    // (also when the AOV switch changes: the snapshot was filtered with these sums as guides)
+    void restartAovs()
+    {
+        aovSums.restart();
         denoisedValid = false;
     }
-
-    // the second moments start again (with the image, or when the switch changes): zeroed before the next sample, sized for the shard then
-    void clearMoments()
+    // Zero `bytes` of the image (on the stream) if no sample has gone into it since the accumulation was restarted.  The callers' byte counts, kept as they were:
+    //   clearStaleSums (render, render_adaptive)    the shard's tiles x 1024 x 16
+    //   meanOnDevice, readTonemapped                the same, from the 32-bit pixel count these two launch their kernels with
+    //   clearAccumulationIfStale (the frame gather) min(the shard's tiles x 1024 x 16, imageBytes): a bound buffer is never written past the size its owner gave
+    // (configureShard and bindAccumulationBuffer refuse a bound buffer smaller than the shard, so the first two stay inside it as well)
+    void zeroImageIfStale(uint64_t bytes)
     {
-        momentSamples = 0;
-        momentsDirty = true;
+        if (!imageSums.dirty) return;
+        RF_HIP(hipMemsetAsync(image, 0, bytes, stream)); // wgsl:47-49
+        imageSums.dirty = false;
+    }
+    TileGrid grid() const { return TileGrid(params.width, params.height); }
+    // row-major width * height * 4 floats <- a compact tile-major buffer of the shard; nullptr (nothing summed yet): all zeros, without a device copy
+    void readCompact(const float4* device, float* dst) const
+    {
+        const size_t pixelsPadded = tiles.size() * 1024;
+        std::memset(dst, 0, static_cast<size_t>(params.width) * params.height * 4 * sizeof(float));
+        if (device == nullptr || pixelsPadded == 0) return;
+        std::vector<float> compact(pixelsPadded * 4);
+        RF_HIP(hipMemcpy(compact.data(), device, pixelsPadded * sizeof(float4), hipMemcpyDeviceToHost));
+        untileHost(compact.data(), tiles.data(), static_cast<uint32_t>(tiles.size()), params.width, params.height, dst);
     }
 
     template<typename F>
@@ -699,32 +728,9 @@ struct Renderer::Impl
     // Before the first sample of an accumulation: zero the sums that were cleared (the image, and the AOV sums / moments while they are on), sized for the shard
     void clearStaleSums(uint64_t pixelsPadded)
     {
-        if (imageDirty)
-        {
-            RF_HIP(hipMemsetAsync(image, 0, pixelsPadded * sizeof(float4), stream)); // wgsl:47-49
-            imageDirty = false;
-        }
-        if (aovFlags != 0u && aovDirty)
-        {
-            if (aovAlbedoCoverage.count < pixelsPadded)
-            {
-                RF_HIP(hipStreamSynchronize(stream)); // (a smaller buffer may still be read by the last batch)
-                aovAlbedoCoverage.alloc(pixelsPadded), aovNormalDepth.alloc(pixelsPadded);
-            }
-            RF_HIP(hipMemsetAsync(aovAlbedoCoverage.ptr, 0, pixelsPadded * sizeof(float4), stream));
-            RF_HIP(hipMemsetAsync(aovNormalDepth.ptr, 0, pixelsPadded * sizeof(float4), stream));
-            aovDirty = false;
-        }
-        if (momentsOn && momentsDirty)
-        {
-            if (moments.count < pixelsPadded)
-            {
-                RF_HIP(hipStreamSynchronize(stream)); // (a smaller buffer may still be read by the last estimate)
-                moments.alloc(pixelsPadded);
-            }
-            RF_HIP(hipMemsetAsync(moments.ptr, 0, pixelsPadded * sizeof(float4), stream));
-            momentsDirty = false;
-        }
+        zeroImageIfStale(pixelsPadded * sizeof(float4));
+        aovSums.zeroIfStale(stream, pixelsPadded);
+        momentSums.zeroIfStale(stream, pixelsPadded);
     }
 
     // Samples per batch for `todo` samples of `pixelsPadded` path slots per sample (the shard's tiles, or the active tiles of render_adaptive), with the path state
@@ -784,11 +790,7 @@ struct Renderer::Impl
         const uint32_t n = static_cast<uint32_t>(tiles.size() * 1024);
         RF_HIP(hipStreamSynchronize(stream));
         if (meanImage.count < n) meanImage.alloc(n);
-        if (imageDirty)
-        {
-            RF_HIP(hipMemsetAsync(image, 0, static_cast<size_t>(n) * sizeof(float4), stream));
-            imageDirty = false;
-        }
+        zeroImageIfStale(static_cast<size_t>(n) * sizeof(float4));
         const uint32_t* counts = nonUniform() ? uploadTileSamples() : nullptr;
         hipLaunchKernelGGL(tileMeanKernel(), dim3((n + 255) / 256), dim3(256), 0, stream, static_cast<const float4*>(image), counts, accumulated, n, meanImage.ptr);
         RF_HIP(hipGetLastError());
@@ -805,25 +807,24 @@ struct Renderer::Impl
     // tileIds / tileValidBefore <- a list of tile ids (ascending) of the whole frame.  The stream must be idle (the copies are synchronous).  -> pixels inside the frame
     uint64_t uploadTileList(const std::vector<uint32_t>& list)
     {
-        const uint32_t tilesX = (params.width + kTileSize - 1) / kTileSize;
-        uint64_t       valid = 0;
-        std::vector<uint32_t> before;
-        before.reserve(list.size() + 1);
-        for (const uint32_t t : list)
-        {
-            before.push_back(static_cast<uint32_t>(valid));
-            valid += tilePixelsInFrame(t, tilesX);
-        }
-        before.push_back(static_cast<uint32_t>(valid));
+        const auto [before, valid] = grid().validPrefix(list);
         if (list.size() > tileIds.count || before.size() > tileValidBefore.count) throw std::logic_error("tile list longer than the frame's");
         if (!list.empty()) RF_HIP(hipMemcpy(tileIds.ptr, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         RF_HIP(hipMemcpy(tileValidBefore.ptr, before.data(), before.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         return valid;
     }
-    uint32_t tilePixelsInFrame(uint32_t t, uint32_t tilesX) const
+
+    // One batch of at most `todo` samples of `pixelsPadded` path slots each (the shard's tiles, or the `active` list of render_adaptive), and its books.  -> samples traced
+    uint32_t step(uint32_t todo, uint64_t pixelsPadded, const ActiveTiles* active)
     {
-        const uint32_t x0 = (t % tilesX) * kTileSize, y0 = (t / tilesX) * kTileSize;
-        return std::min(kTileSize, params.width - x0) * std::min(kTileSize, params.height - y0);
+        const uint32_t n = batchSamples(todo, pixelsPadded);
+        traceBatch(frameCount, n, active);
+        hostStats.batchSamplesUsed = n, hostStats.batchPathsUsed = static_cast<uint64_t>(n) * pixelsPadded, ++hostStats.batchesTraced;
+        frameCount += n;
+        accumulated += n;
+        if (aovSums.on) aovSums.samples += n;
+        if (momentSums.on) momentSums.samples += n;
+        return n;
     }
 
     // Trace `numSamples` consecutive samples (sample indices start at frame `firstFrame`) of the shard's tiles -- or, active != nullptr, of the tile list that
@@ -851,7 +852,7 @@ struct Renderer::Impl
             fp.samplePerm = samplePerm.ptr;
             fp.sampleInvPerm = samplePerm.ptr + numSamples;
         }
-        fp.tilesX = (params.width + kTileSize - 1) / kTileSize;
+        fp.tilesX = grid().tilesX;
         if (fp.numTiles == 0) return;
         fp.divNumSamples = FastDiv::make(fp.numSamples), fp.divPixelsPadded = FastDiv::make(fp.pixelsPadded), fp.divTilesX = FastDiv::make(fp.tilesX);
         fp.divSamplesPerPixel = FastDiv::make(fp.samplesPerPixel);
@@ -945,10 +946,8 @@ struct Renderer::Impl
             // wave-wide stall: bounce 1 -4 % at 256 entries, the deep bounces +0.5 %)
             const uint32_t chunkNow = bounce <= optChunkEarlyBounces ? optChunkEarly : optChunk;
             const int      layoutClosest = closestLayoutFor(bounce);
-            const bool     conservativeClosest = layoutClosest == kLayoutOct || layoutClosest == kLayoutQuadHalf || layoutClosest == kLayoutQuadLocal;
             // (scenes with long leaves -- the DENSE_LEAVES instantiations -- keep 22: a phase over dense (lane, triangle) pairs wants many parked lanes; clutter atrium +2.4 % at 12: profiles/r06_lanes)
             const uint32_t refillClosest = bounce >= optRefillDeepFromBounce ? (layoutClosest == kLayoutQuad ? optRefillMinDeepQuad : (denseWanted(uniformFlag) ? optRefillMinDeepDense : optRefillMinDeep)) : optRefillMin;
-            (void)conservativeClosest;
             // (kInfinityCacheBytes: the scene's records + triangles against the 256-MB Infinity Cache, as the layout selector's own test)
             const uint32_t leafVoteClosest = (!counting && !denseWanted(uniformFlag) && treeBytes <= (192ull << 20)) ? optLeafVoteClosest : 0u;
             launchTimed(1, [&] {
@@ -979,7 +978,7 @@ struct Renderer::Impl
                 const uint32_t shadeFlags = (bounce == numBounces ? kShadeLastBounce : 0u) | (bounce == 1 ? kShadeFirstBounce : 0u) | (selfShadow ? kShadeSelfShadow : 0u);
                 const dim3     shadeGrid(optShadeBlocks ? std::min(itemBlocks, optShadeBlocks) : itemBlocks);
                 // (the first-hit AOVs are written by the unsorted bounce-1 kernel, whatever shade_sort_from_bounce says: the sort is a scheduling choice)
-                if (aovFlags != 0u && bounce == 1)
+                if (aovSums.on && bounce == 1)
                     hipLaunchKernelGGL(shadeKernel(false, true), shadeGrid, dim3(kBlock), 0, stream, scene, sky, sunBasis, ps, qIn, countIn, qOut, countOut, missQueue.ptr, missSlots.ptr, missCount, shadowList.ptr, shadowListCount, shadeFlags, 0u, sAov.ptr);
                 else if (optShadeSortFromBounce != 0u && bounce >= optShadeSortFromBounce)
                     hipLaunchKernelGGL(shadeKernel(true), shadeGrid, dim3(kBlock), 0, stream, scene, sky, sunBasis, ps, qIn, countIn, qOut, countOut, missQueue.ptr, missSlots.ptr, missCount, shadowList.ptr, shadowListCount, shadeFlags, sortScale, nullptr);
@@ -1043,19 +1042,22 @@ struct Renderer::Impl
             lookPending = true;
         }
         if (wide.occGrid != nullptr) occluderGridWarm = true;
+        // The sums in sample order.  Where the slot order is pixel-major and the step long enough, the LDS-staged "runs" kernels (a 64-lane workgroup per
+        // `pixelsPerGroup` pixels); else one thread per pixel
+        const bool runs = fp.slotGroupShift == 0u && numSamples > 4u && optAccumulateRuns;
+        const auto sumGrid = [&](uint32_t pixelsPerGroup) {
+            const uint32_t perGroup = runs ? pixelsPerGroup : static_cast<uint32_t>(kBlock);
+            return dim3((fp.pixelsPadded + perGroup - 1) / perGroup);
+        };
+        const dim3 sumBlock(runs ? 64u : static_cast<uint32_t>(kBlock));
         launchTimed(4, [&] {
             if (active)
             {
                 // (whole frame: compact slot == tile id, so the listed tiles' sums sit at tile id * 1024 of the image and the moments)
-                if (fp.slotGroupShift == 0u && numSamples > 4u && optAccumulateRuns)
-                    hipLaunchKernelGGL(accumulateTilesKernel(true), dim3((fp.pixelsPadded + kMomentPixels - 1) / kMomentPixels), dim3(64), 0, stream, fp, tileIds.ptr,
-                                       static_cast<const float4*>(ps.rad), image, moments.ptr);
-                else
-                    hipLaunchKernelGGL(accumulateTilesKernel(false), dim3((fp.pixelsPadded + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, fp, tileIds.ptr,
-                                       static_cast<const float4*>(ps.rad), image, moments.ptr);
+                hipLaunchKernelGGL(accumulateTilesKernel(runs), sumGrid(kMomentPixels), sumBlock, 0, stream, fp, tileIds.ptr, static_cast<const float4*>(ps.rad), image, moments());
                 return;
             }
-            if (fp.slotGroupShift == 0u && numSamples > 4u && numSamples <= kAccMaxSamples && optAccumulateRuns)
+            if (runs && numSamples <= kAccMaxSamples)
             {
                 // (pixels per workgroup by the LDS their runs take: <= ~8 KB per workgroup keeps twenty of them resident per CU)
                 const uint32_t accPixels = numSamples > 640u ? 1u : (numSamples > 160u ? 2u : kAccPixels);
@@ -1065,25 +1067,11 @@ struct Renderer::Impl
             else
                 hipLaunchKernelGGL(accumulateKernel(), dim3((fp.pixelsPadded + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, fp, tileIds.ptr, ps, image);
             // the first-hit AOV sums, in the same sample order (timed with the accumulation: rf_stats has no entry of its own for them)
-            if (aovFlags != 0u && numBounces != 0u) // (no bounce, no primary hit: the records were not written)
-            {
-                if (fp.slotGroupShift == 0u && numSamples > 4u && optAccumulateRuns)
-                    hipLaunchKernelGGL(accumulateAovKernel(true), dim3((fp.pixelsPadded + kAovPixels - 1) / kAovPixels), dim3(64), 0, stream, fp, tileIds.ptr, sAov.ptr,
-                                       aovAlbedoCoverage.ptr, aovNormalDepth.ptr);
-                else
-                    hipLaunchKernelGGL(accumulateAovKernel(false), dim3((fp.pixelsPadded + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, fp, tileIds.ptr, sAov.ptr,
-                                       aovAlbedoCoverage.ptr, aovNormalDepth.ptr);
-            }
+            if (aovSums.on && numBounces != 0u) // (no bounce, no primary hit: the records were not written)
+                hipLaunchKernelGGL(accumulateAovKernel(runs), sumGrid(kAovPixels), sumBlock, 0, stream, fp, tileIds.ptr, sAov.ptr, aovAlbedoCoverage(), aovNormalDepth());
             // the radiance second moments, over the same stream in the same sample order (timed with the accumulation as well)
-            if (momentsOn)
-            {
-                if (fp.slotGroupShift == 0u && numSamples > 4u && optAccumulateRuns)
-                    hipLaunchKernelGGL(accumulateMomentsKernel(true), dim3((fp.pixelsPadded + kMomentPixels - 1) / kMomentPixels), dim3(64), 0, stream, fp, tileIds.ptr,
-                                       static_cast<const float4*>(ps.rad), moments.ptr);
-                else
-                    hipLaunchKernelGGL(accumulateMomentsKernel(false), dim3((fp.pixelsPadded + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, fp, tileIds.ptr,
-                                       static_cast<const float4*>(ps.rad), moments.ptr);
-            }
+            if (momentSums.on)
+                hipLaunchKernelGGL(accumulateMomentsKernel(runs), sumGrid(kMomentPixels), sumBlock, 0, stream, fp, tileIds.ptr, static_cast<const float4*>(ps.rad), moments());
         });
         RF_HIP(hipGetLastError());
         RF_HIP(hipEventRecord(bt.stop, stream));
@@ -1096,11 +1084,9 @@ struct Renderer::Impl
 Renderer::Renderer(const RendererDescriptor& desc, const SceneView& sceneView) : mImpl(std::make_unique<Impl>())
 {
     Impl& m = *mImpl;
-    int   deviceCount = 0;
-    if (hipGetDeviceCount(&deviceCount) != hipSuccess || deviceCount == 0)
-        throw std::runtime_error("rayfinder_amd: no HIP device available (this library has no CPU fallback)");
+    requireAnyDevice();
     m.device = desc.deviceOrdinal;
-    RF_HIP(hipSetDevice(m.device));
+    RF_HIP(hipSetDevice(m.device)); // (not requireDevice: an ordinal that names no device has always been reported here as the HIP error it is)
     RF_HIP(hipStreamCreateWithFlags(&m.stream, hipStreamNonBlocking));
 
     if (sceneView.bvhNodes.empty()) throw std::runtime_error("scene has no BVH nodes");
@@ -1350,7 +1336,8 @@ Renderer::Renderer(const RendererDescriptor& desc, const SceneView& sceneView) :
 
     m.maxWidth = desc.maxWidth ? desc.maxWidth : desc.renderParams.width;
     m.maxHeight = desc.maxHeight ? desc.maxHeight : desc.renderParams.height;
-    const uint64_t maxTiles = static_cast<uint64_t>((m.maxWidth + kTileSize - 1) / kTileSize) * ((m.maxHeight + kTileSize - 1) / kTileSize);
+    const TileGrid maxGrid(m.maxWidth, m.maxHeight);
+    const uint64_t maxTiles = static_cast<uint64_t>(maxGrid.tilesX) * maxGrid.tilesY;
     // 1 Gi paths per batch by default (133 GB of path state + queues out of 288 GB; allocated on demand, so a render only ever
     // takes samples x pixels x 124 B): later bounces of a batch keep ~15 % of
     // the paths, a traversal launch needs millions of rays to fill 6144 persistent waves and to amortise its tail, and the
@@ -1404,11 +1391,7 @@ void Renderer::setRenderParameters(const RenderParameters& p)
     m.params = p;
     m.sky = sky;
     m.updateSunBasis();
-    m.accumulated = 0;
-    m.imageDirty = true;
-    m.tileSamples.clear();
-    m.clearAovs();
-    m.clearMoments();
+    m.restartAccumulation();
     if (resized) m.configureShard();
 }
 
@@ -1444,14 +1427,7 @@ void Renderer::render(uint32_t numFrames)
             break;
         }
         m.clearStaleSums(pixelsPadded);
-        const uint32_t n = m.batchSamples(std::min(remaining, spp - m.accumulated), pixelsPadded);
-        m.traceBatch(m.frameCount, n);
-        m.hostStats.batchSamplesUsed = n, m.hostStats.batchPathsUsed = static_cast<uint64_t>(n) * pixelsPadded, ++m.hostStats.batchesTraced;
-        m.frameCount += n;
-        m.accumulated += n;
-        if (m.aovFlags != 0u) m.aovSamples += n;
-        if (m.momentsOn) m.momentSamples += n;
-        remaining -= n;
+        remaining -= m.step(std::min(remaining, spp - m.accumulated), pixelsPadded, nullptr);
     }
 }
 
@@ -1490,65 +1466,49 @@ void Renderer::readAccumulation(float* dst)
 {
     Impl& m = *mImpl;
     synchronize();
-    const size_t       pixelsPadded = m.tiles.size() * 1024;
-    std::vector<float> compact(pixelsPadded * 4);
-    if (m.imageDirty) std::fill(compact.begin(), compact.end(), 0.0f);
-    else if (pixelsPadded) RF_HIP(hipMemcpy(compact.data(), m.image, pixelsPadded * sizeof(float4), hipMemcpyDeviceToHost));
-    std::memset(dst, 0, static_cast<size_t>(m.params.width) * m.params.height * 4 * sizeof(float));
-    untileHost(compact.data(), m.tiles.data(), static_cast<uint32_t>(m.tiles.size()), m.params.width, m.params.height, dst);
+    m.readCompact(m.imageSums.dirty ? nullptr : m.image, dst);
 }
 
 void Renderer::setAovs(uint32_t flags)
 {
     Impl& m = *mImpl;
-    if (flags == m.aovFlags) return;
+    if ((flags != 0u) == m.aovSums.on) return; // (kAovFirstHit is the only flag)
     RF_HIP(hipSetDevice(m.device));
     RF_HIP(hipStreamSynchronize(m.stream)); // (a batch in flight may still write the records or the sums)
-    m.aovFlags = flags;
-    m.clearAovs();
-    if (flags == 0u)
+    m.aovSums.on = flags != 0u;
+    m.restartAovs();
+    if (!m.aovSums.on)
     {
         // off: nothing of the AOVs stays allocated (the path state keeps its depth; the next batch that needs the records allocates them again)
         m.sAov.release();
-        m.aovAlbedoCoverage.release();
-        m.aovNormalDepth.release();
+        m.aovSums.release();
     }
 }
 
-uint32_t Renderer::aovFlags() const { return mImpl->aovFlags; }
+uint32_t Renderer::aovFlags() const { return mImpl->aovSums.on ? kAovFirstHit : 0u; }
 
 void Renderer::readAovs(float* albedoCoverage, float* normalDepth, uint32_t* sampleCount)
 {
     Impl& m = *mImpl;
     synchronize();
-    const size_t pixelsPadded = m.tiles.size() * 1024;
-    const bool   empty = m.aovFlags == 0u || m.aovDirty || m.aovSamples == 0u;
-    const auto   read = [&](const DeviceBuffer<float4>& buf, float* dst) {
-        if (dst == nullptr) return;
-        std::memset(dst, 0, static_cast<size_t>(m.params.width) * m.params.height * 4 * sizeof(float));
-        if (empty || pixelsPadded == 0) return;
-        std::vector<float> compact(pixelsPadded * 4);
-        RF_HIP(hipMemcpy(compact.data(), buf.ptr, pixelsPadded * sizeof(float4), hipMemcpyDeviceToHost));
-        untileHost(compact.data(), m.tiles.data(), static_cast<uint32_t>(m.tiles.size()), m.params.width, m.params.height, dst);
-    };
-    read(m.aovAlbedoCoverage, albedoCoverage);
-    read(m.aovNormalDepth, normalDepth);
-    if (sampleCount) *sampleCount = empty ? 0u : m.aovSamples;
+    const bool empty = m.aovSums.empty();
+    if (albedoCoverage) m.readCompact(empty ? nullptr : m.aovAlbedoCoverage(), albedoCoverage);
+    if (normalDepth) m.readCompact(empty ? nullptr : m.aovNormalDepth(), normalDepth);
+    if (sampleCount) *sampleCount = empty ? 0u : m.aovSums.samples;
 }
 
 void Renderer::denoise(const DenoiseParameters& params)
 {
     Impl& m = *mImpl;
     m.requireUniform("rf_renderer_denoise"); // (the filter divides by ONE sample count)
-    if (m.aovFlags == 0u) throw std::invalid_argument("denoise needs the first-hit AOVs: turn them on (rf_renderer_set_aovs) before the first sample");
+    if (!m.aovSums.on) throw std::invalid_argument("denoise needs the first-hit AOVs: turn them on (rf_renderer_set_aovs) before the first sample");
     if (m.worldSize != 1u) throw std::invalid_argument("denoise needs the whole frame: a tile shard is set (use rf_denoise_images on the gathered sums)");
-    if (m.accumulated == 0u || m.imageDirty) throw std::invalid_argument("denoise: no sample has been accumulated");
-    if (m.aovDirty || m.aovSamples != m.accumulated)
-        throw std::invalid_argument("denoise: the AOV sample count (" + std::to_string(m.aovSamples) + ") differs from the accumulated sample count (" +
+    if (m.accumulated == 0u) throw std::invalid_argument("denoise: no sample has been accumulated");
+    if (!m.aovSums.covers(m.accumulated))
+        throw std::invalid_argument("denoise: the AOV sample count (" + std::to_string(m.aovSums.samples) + ") differs from the accumulated sample count (" +
                                     std::to_string(m.accumulated) + "): turn the AOVs on before the first sample");
     RF_HIP(hipSetDevice(m.device));
-    const uint32_t tilesX = (m.params.width + kTileSize - 1) / kTileSize;
-    enqueueDenoise(m.stream, m.denoiseWork, m.image, m.aovAlbedoCoverage.ptr, m.aovNormalDepth.ptr, m.params.width, m.params.height, tilesX, m.accumulated, params,
+    enqueueDenoise(m.stream, m.denoiseWork, m.image, m.aovAlbedoCoverage(), m.aovNormalDepth(), m.params.width, m.params.height, m.grid().tilesX, m.accumulated, params,
                    m.params.exposure);
     m.denoisedValid = true;
     m.denoisedSamples = m.accumulated;
@@ -1560,56 +1520,47 @@ void Renderer::readDenoised(float* rgba, uint32_t* bgra8, uint32_t* sampleCount)
     if (!m.denoisedValid) throw std::invalid_argument("no denoised image: call rf_renderer_denoise first (the image is dropped when the accumulation or the AOVs are cleared)");
     synchronize();
     const size_t n = static_cast<size_t>(m.params.width) * m.params.height;
-    if (rgba) RF_HIP(hipMemcpy(rgba, m.denoiseWork.out, n * sizeof(float4), hipMemcpyDeviceToHost));
-    if (bgra8) RF_HIP(hipMemcpy(bgra8, m.denoiseWork.bgra, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (rgba) RF_HIP(hipMemcpy(rgba, m.denoiseWork.out.ptr, n * sizeof(float4), hipMemcpyDeviceToHost));
+    if (bgra8) RF_HIP(hipMemcpy(bgra8, m.denoiseWork.bgra.ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (sampleCount) *sampleCount = m.denoisedSamples;
 }
 
 void Renderer::setMoments(bool enabled)
 {
     Impl& m = *mImpl;
-    if (enabled == m.momentsOn) return;
+    if (enabled == m.momentSums.on) return;
     RF_HIP(hipSetDevice(m.device));
     RF_HIP(hipStreamSynchronize(m.stream)); // (a batch in flight may still write the sums)
-    m.momentsOn = enabled;
-    m.clearMoments();
+    m.momentSums.on = enabled;
+    m.momentSums.restart();
     if (!enabled)
     {
         // off: nothing of the moments stays allocated
-        m.moments.release();
+        m.momentSums.release();
         m.noiseWork.release();
     }
 }
 
-bool Renderer::momentsEnabled() const { return mImpl->momentsOn; }
+bool Renderer::momentsEnabled() const { return mImpl->momentSums.on; }
 
 void Renderer::readMoments(float* sumSq, uint32_t* sampleCount)
 {
     Impl& m = *mImpl;
     synchronize();
-    const size_t pixelsPadded = m.tiles.size() * 1024;
-    const bool   empty = !m.momentsOn || m.momentsDirty || m.momentSamples == 0u;
-    if (sumSq)
-    {
-        std::memset(sumSq, 0, static_cast<size_t>(m.params.width) * m.params.height * 4 * sizeof(float));
-        if (!empty && pixelsPadded != 0)
-        {
-            std::vector<float> compact(pixelsPadded * 4);
-            RF_HIP(hipMemcpy(compact.data(), m.moments.ptr, pixelsPadded * sizeof(float4), hipMemcpyDeviceToHost));
-            untileHost(compact.data(), m.tiles.data(), static_cast<uint32_t>(m.tiles.size()), m.params.width, m.params.height, sumSq);
-        }
-    }
-    if (sampleCount) *sampleCount = empty ? 0u : m.momentSamples;
+    const bool empty = m.momentSums.empty();
+    if (sumSq) m.readCompact(empty ? nullptr : m.moments(), sumSq);
+    if (sampleCount) *sampleCount = empty ? 0u : m.momentSums.samples;
 }
 
 NoiseEstimate Renderer::noiseEstimate(float* errorMap, float* tileSum, float* tileMax)
 {
     Impl& m = *mImpl;
-    if (!m.momentsOn) throw std::invalid_argument("the noise estimate needs the radiance second moments: turn them on (rf_renderer_set_moments) before the first sample");
+    if (!m.momentSums.on) throw std::invalid_argument("the noise estimate needs the radiance second moments: turn them on (rf_renderer_set_moments) before the first sample");
     if (m.worldSize != 1u) throw std::invalid_argument("the noise estimate needs the whole frame: a tile shard is set (use rf_noise_estimate_images on the ranks' sums)");
-    if (m.imageDirty || m.momentsDirty || m.momentSamples != m.accumulated)
-        throw std::invalid_argument("noise estimate: the moment sample count (" + std::to_string(m.momentsDirty ? 0u : m.momentSamples) + ") differs from the accumulated sample count (" +
-                                    std::to_string(m.imageDirty ? 0u : m.accumulated) + "): turn the moments on before the first sample");
+    // (a dirty channel's count is 0 and a dirty image's accumulated count is 0 -- SumChannel -- so the counts print as they are)
+    if (!m.momentSums.covers(m.accumulated))
+        throw std::invalid_argument("noise estimate: the moment sample count (" + std::to_string(m.momentSums.samples) + ") differs from the accumulated sample count (" +
+                                    std::to_string(m.accumulated) + "): turn the moments on before the first sample");
     if (m.accumulated < 2u) throw std::invalid_argument("noise estimate: a variance needs at least 2 accumulated samples");
     RF_HIP(hipSetDevice(m.device));
     if (m.nonUniform())
@@ -1617,25 +1568,25 @@ NoiseEstimate Renderer::noiseEstimate(float* errorMap, float* tileSum, float* ti
         // every tile with its own count (each >= 2: a tile stops at an estimate); `samples` reports the leading count
         TileSelection sel;
         sel.tileSamplesDevice = m.uploadTileSamples();
-        return runNoiseEstimateTiles(m.stream, m.noiseWork, m.image, m.moments.ptr, m.params.width, m.params.height, true, sel, m.accumulated, errorMap, tileSum, tileMax, nullptr);
+        return runNoiseEstimateTiles(m.stream, m.noiseWork, m.image, m.moments(), m.params.width, m.params.height, true, sel, m.accumulated, errorMap, tileSum, tileMax, nullptr);
     }
-    return runNoiseEstimate(m.stream, m.noiseWork, m.image, m.moments.ptr, m.params.width, m.params.height, true, m.accumulated, errorMap, tileSum, tileMax);
+    return runNoiseEstimate(m.stream, m.noiseWork, m.image, m.moments(), m.params.width, m.params.height, true, m.accumulated, errorMap, tileSum, tileMax);
 }
 
 AdaptiveResult Renderer::renderAdaptive(const AdaptiveParameters& p)
 {
     Impl& m = *mImpl;
-    if (!m.momentsOn) throw std::invalid_argument("render_adaptive needs the radiance second moments: turn them on (rf_renderer_set_moments) before the first sample");
-    if (m.aovFlags != 0u) throw std::invalid_argument("render_adaptive: the first-hit AOVs are on (their sums and the denoiser keep ONE sample count): turn them off first");
+    if (!m.momentSums.on) throw std::invalid_argument("render_adaptive needs the radiance second moments: turn them on (rf_renderer_set_moments) before the first sample");
+    if (m.aovSums.on) throw std::invalid_argument("render_adaptive: the first-hit AOVs are on (their sums and the denoiser keep ONE sample count): turn them off first");
     if (m.worldSize != 1u) throw std::invalid_argument("render_adaptive needs the whole frame: a tile shard is set");
     if (p.checkEvery == 0u) throw std::invalid_argument("render_adaptive: check_every must be >= 1");
     if (!std::isfinite(p.targetTileError) || p.targetTileError < 0.0f) throw std::invalid_argument("render_adaptive: target_tile_error must be finite and >= 0");
-    if (m.accumulated != 0u && (m.imageDirty || m.momentsDirty || m.momentSamples != m.accumulated))
+    if (m.accumulated != 0u && !m.momentSums.covers(m.accumulated))
         throw std::invalid_argument("render_adaptive: the moments do not cover the accumulation (turned on partway through): restart the accumulation first");
     RF_HIP(hipSetDevice(m.device));
     const uint32_t spp = m.params.samplingParams.numSamplesPerPixel;
     const uint32_t cap = p.maxSamples == 0u ? spp : std::min(p.maxSamples, spp);
-    const uint32_t numTiles = static_cast<uint32_t>(m.tiles.size()), tilesX = (m.params.width + kTileSize - 1) / kTileSize;
+    const uint32_t numTiles = static_cast<uint32_t>(m.tiles.size());
     const uint32_t firstCheck = std::max(2u, p.minSamples);
 
     // the counts as a vector for the length of the call (the uniform state: every tile at the accumulated count); the tiles at the leading count are the active ones
@@ -1673,23 +1624,14 @@ AdaptiveResult Renderer::renderAdaptive(const AdaptiveParameters& p)
         }
         m.clearStaleSums(static_cast<uint64_t>(numTiles) * 1024);
         uint32_t remaining = std::min(p.checkEvery, cap - m.accumulated);
-        while (remaining > 0)
-        {
-            const uint32_t n = m.batchSamples(remaining, pixelsPadded);
-            m.traceBatch(m.frameCount, n, &list);
-            m.hostStats.batchSamplesUsed = n, m.hostStats.batchPathsUsed = static_cast<uint64_t>(n) * pixelsPadded, ++m.hostStats.batchesTraced;
-            m.frameCount += n;
-            m.accumulated += n;
-            m.momentSamples += n;
-            remaining -= n;
-        }
+        while (remaining > 0) remaining -= m.step(remaining, pixelsPadded, &list);
         for (const uint32_t t : active) counts[t] = m.accumulated;
         m.tileSamples = counts; // (non-uniform from here on, should an estimate throw; settled below)
         if (m.accumulated < firstCheck) continue;
         // the active tiles' estimate, Nf = float(L) for all of them; tileIds holds the list (the frame's own while every tile is active)
         TileSelection sel;
         sel.listDevice = m.tileIds.ptr, sel.listHost = active.data(), sel.listCount = static_cast<uint32_t>(active.size());
-        out.last = runNoiseEstimateTiles(m.stream, m.noiseWork, m.image, m.moments.ptr, m.params.width, m.params.height, true, sel, m.accumulated, nullptr, sums.data(), nullptr,
+        out.last = runNoiseEstimateTiles(m.stream, m.noiseWork, m.image, m.moments(), m.params.width, m.params.height, true, sel, m.accumulated, nullptr, sums.data(), nullptr,
                                          pixels.data());
         ++out.estimatePasses;
         std::vector<uint32_t> still;
@@ -1706,7 +1648,7 @@ AdaptiveResult Renderer::renderAdaptive(const AdaptiveParameters& p)
     {
         out.minTileSamples = std::min(out.minTileSamples, counts[t]), out.maxTileSamples = std::max(out.maxTileSamples, counts[t]);
         if (counts[t] != m.accumulated) ++out.stoppedTiles;
-        out.pixelSamples += static_cast<uint64_t>(m.tilePixelsInFrame(m.tiles[t], tilesX)) * counts[t];
+        out.pixelSamples += static_cast<uint64_t>(m.grid().pixelsInFrame(m.tiles[t])) * counts[t];
     }
     if (out.stoppedTiles == 0u) m.tileSamples.clear(); // every tile at the leading count: the ordinary state
     else m.tileSamples = counts;
@@ -1719,11 +1661,11 @@ void Renderer::requireUniformTileSamples(const char* what) const { mImpl->requir
 uint32_t Renderer::readTileSamples(uint32_t* tileSamples) const
 {
     const Impl&    m = *mImpl;
-    const uint32_t frameTiles = ((m.params.width + kTileSize - 1) / kTileSize) * ((m.params.height + kTileSize - 1) / kTileSize);
+    const uint32_t frameTiles = m.grid().count();
     if (tileSamples)
     {
         std::fill(tileSamples, tileSamples + frameTiles, 0u);
-        for (size_t i = 0; i < m.tiles.size(); ++i) tileSamples[m.tiles[i]] = m.nonUniform() ? m.tileSamples[i] : (m.imageDirty ? 0u : m.accumulated);
+        for (size_t i = 0; i < m.tiles.size(); ++i) tileSamples[m.tiles[i]] = m.nonUniform() ? m.tileSamples[i] : m.accumulated; // (0 after a restart)
     }
     return frameTiles;
 }
@@ -1732,22 +1674,17 @@ void Renderer::readMean(float* rgba)
 {
     Impl& m = *mImpl;
     synchronize();
-    const size_t pixelsPadded = m.tiles.size() * 1024;
-    std::memset(rgba, 0, static_cast<size_t>(m.params.width) * m.params.height * 4 * sizeof(float));
-    if (pixelsPadded == 0) return;
-    std::vector<float> compact(pixelsPadded * 4);
-    RF_HIP(hipMemcpy(compact.data(), m.meanOnDevice(), pixelsPadded * sizeof(float4), hipMemcpyDeviceToHost));
-    untileHost(compact.data(), m.tiles.data(), static_cast<uint32_t>(m.tiles.size()), m.params.width, m.params.height, rgba);
+    m.readCompact(m.tiles.empty() ? nullptr : m.meanOnDevice(), rgba);
 }
 
 uint32_t Renderer::renderUntil(float targetMeanError, uint32_t checkEvery, uint32_t maxFrames, NoiseEstimate* last)
 {
     Impl& m = *mImpl;
-    if (!m.momentsOn) throw std::invalid_argument("render_until needs the radiance second moments: turn them on (rf_renderer_set_moments) before the first sample");
+    if (!m.momentSums.on) throw std::invalid_argument("render_until needs the radiance second moments: turn them on (rf_renderer_set_moments) before the first sample");
     if (m.worldSize != 1u) throw std::invalid_argument("render_until needs the whole frame: a tile shard is set");
     if (checkEvery == 0u) throw std::invalid_argument("render_until: check_every must be >= 1");
     m.requireUniform("rf_renderer_render_until");
-    if (m.accumulated != 0u && (m.momentsDirty || m.momentSamples != m.accumulated))
+    if (m.accumulated != 0u && !m.momentSums.covers(m.accumulated))
         throw std::invalid_argument("render_until: the moments do not cover the accumulation (turned on partway through): restart the accumulation first");
     const uint32_t spp = m.params.samplingParams.numSamplesPerPixel;
     NoiseEstimate  estimate;
@@ -1770,12 +1707,9 @@ void*    Renderer::accumulationDevicePointer() const { return mImpl->image; }
 void Renderer::clearAccumulationIfStale()
 {
     Impl& m = *mImpl;
-    if (!m.imageDirty || m.image == nullptr) return;
+    if (!m.imageSums.dirty || m.image == nullptr) return;
     RF_HIP(hipSetDevice(m.device));
-    // (this shard's part of the buffer; a bound buffer is never written past the size its owner gave in bindAccumulationBuffer --
-    // configureShard refuses a shard that needs more)
-    RF_HIP(hipMemsetAsync(m.image, 0, std::min<uint64_t>(accumulationBytes(), m.imageBytes), m.stream)); // wgsl:47-49
-    m.imageDirty = false;
+    m.zeroImageIfStale(std::min<uint64_t>(accumulationBytes(), m.imageBytes));
 }
 
 void Renderer::layoutInfo(uint32_t (&layouts)[48], uint32_t (&misc)[4], float& quadHalfAreaRatio, uint64_t& treeBytes) const
@@ -1827,11 +1761,7 @@ void Renderer::bindAccumulationBuffer(void* devicePtr, uint64_t bytes)
     if (bytes < accumulationBytes()) throw std::runtime_error("accumulation buffer too small");
     m.image = static_cast<float4*>(devicePtr);
     m.imageBytes = bytes;
-    m.accumulated = 0;
-    m.imageDirty = true;
-    m.tileSamples.clear();
-    m.clearAovs();
-    m.clearMoments();
+    m.restartAccumulation();
 }
 
 void Renderer::readTonemapped(uint32_t* dst)
@@ -1841,11 +1771,7 @@ void Renderer::readTonemapped(uint32_t* dst)
     const uint32_t         n = static_cast<uint32_t>(m.tiles.size() * 1024);
     DeviceBuffer<uint32_t> out;
     out.alloc(std::max<uint32_t>(n, 1));
-    if (m.imageDirty)
-    {
-        RF_HIP(hipMemsetAsync(m.image, 0, static_cast<size_t>(n) * sizeof(float4), m.stream));
-        m.imageDirty = false;
-    }
+    m.zeroImageIfStale(static_cast<size_t>(n) * sizeof(float4));
     // (non-uniform tile counts: kTonemap over the per-tile mean with accumulatedSamples = 1, the denoiser's display path; x / 1 is exact, so the uniform state's texels are
     // the ones the direct launch gives)
     if (n && m.nonUniform()) hipLaunchKernelGGL(tonemapKernel(), dim3((n + 255) / 256), dim3(256), 0, m.stream, m.meanOnDevice(), n, 1u, m.params.exposure, out.ptr);
@@ -1854,15 +1780,7 @@ void Renderer::readTonemapped(uint32_t* dst)
     std::vector<uint32_t> compact(n);
     if (n) RF_HIP(hipMemcpy(compact.data(), out.ptr, static_cast<size_t>(n) * 4, hipMemcpyDeviceToHost));
     std::memset(dst, 0, static_cast<size_t>(m.params.width) * m.params.height * 4);
-    const uint32_t tilesX = (m.params.width + kTileSize - 1) / kTileSize;
-    for (size_t t = 0; t < m.tiles.size(); ++t)
-        for (uint32_t w = 0; w < 1024; ++w)
-        {
-            const uint32_t block = w >> 6, lane = w & 63u;
-            const uint32_t x = (m.tiles[t] % tilesX) * kTileSize + (block & 3u) * 8u + (lane & 7u);
-            const uint32_t y = (m.tiles[t] / tilesX) * kTileSize + (block >> 2) * 8u + (lane >> 3);
-            if (x < m.params.width && y < m.params.height) dst[static_cast<size_t>(y) * m.params.width + x] = compact[t * 1024 + w];
-        }
+    untileHostTexels(compact.data(), m.tiles.data(), static_cast<uint32_t>(m.tiles.size()), m.params.width, m.params.height, sizeof(uint32_t), dst);
 }
 
 void Renderer::tonemapDeviceImage(const void* imageDevice, uint64_t numPixels, uint32_t samples, uint32_t* dst)

@@ -14,6 +14,8 @@
 #include "rf_sky.hpp"
 #include "rf_types.hpp"
 
+#include <algorithm>
+#include <cstddef>
 #include <cstdint>
 #include <deque>
 #include <memory>
@@ -95,10 +97,44 @@ struct RenderStats
 
 constexpr uint32_t kTileSize = 32; // shard tile edge in pixels (32x32 = 16 waves of 8x8 pixels)
 
+// The grid of kTileSize x kTileSize tiles over a width x height frame: tile t = tile_y * tilesX + tile_x; the last column and the last row may reach past the frame.
+// The one place that knows the tile arithmetic of the host code (the kernels' own: rf_kernels.hpp).
+struct TileGrid
+{
+    uint32_t width, height, tilesX, tilesY;
+    TileGrid(uint32_t w, uint32_t h) : width(w), height(h), tilesX((w + kTileSize - 1) / kTileSize), tilesY((h + kTileSize - 1) / kTileSize) {}
+    uint32_t count() const { return tilesX * tilesY; }
+    uint32_t pixelsInFrame(uint32_t tile) const
+    {
+        const uint32_t x0 = (tile % tilesX) * kTileSize, y0 = (tile / tilesX) * kTileSize;
+        return std::min(kTileSize, width - x0) * std::min(kTileSize, height - y0);
+    }
+    // before[i] = the in-frame pixels of tiles[0 .. i) (tiles.size() + 1 entries: kRaygen's queue positions, FrameParams::tileValidBefore) and their total
+    struct Prefix
+    {
+        std::vector<uint32_t> before;
+        uint64_t              total = 0;
+    };
+    Prefix validPrefix(std::span<const uint32_t> tiles) const
+    {
+        Prefix p;
+        p.before.reserve(tiles.size() + 1);
+        for (const uint32_t t : tiles)
+        {
+            p.before.push_back(static_cast<uint32_t>(p.total));
+            p.total += pixelsInFrame(t);
+        }
+        p.before.push_back(static_cast<uint32_t>(p.total));
+        return p;
+    }
+};
+
 // Deterministic tile -> rank assignment (tiles along a Z-order curve dealt round-robin: equal counts +-1, every compact block of the image split over all ranks).
 std::vector<uint32_t> tilesForRank(uint32_t width, uint32_t height, uint32_t rank, uint32_t worldSize);
 // compact tile-major float4 buffer -> row-major width*height*4 image (pixels of other ranks' tiles untouched)
 void untileHost(const float* compact, const uint32_t* tileIds, uint32_t numTiles, uint32_t width, uint32_t height, float* image);
+// the same for texels of any size (float4 sums: 16 bytes, BGRA8: 4)
+void untileHostTexels(const void* compact, const uint32_t* tileIds, uint32_t numTiles, uint32_t width, uint32_t height, size_t texelBytes, void* image);
 
 // Edge-aware a-trous denoiser (rf_denoise.hip): iterations 0..8, every sigma finite and > 0 (the C ABI checks them before any device call)
 struct DenoiseParameters
