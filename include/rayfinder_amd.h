@@ -488,6 +488,42 @@ typedef struct rf_layout_info
     uint64_t tree_bytes;              /* quad records + triangle records */
 } rf_layout_info;
 RF_API int  rf_renderer_layout_info(const rf_renderer* r, rf_layout_info* out);
+/* The launches of bounce `bounce` (1 .. the handle's bounce count) of the handle's NEXT batch of num_samples samples, as the host driver would enqueue them in its
+ * present state (scene, options, camera, AOV / moment switches, counting, and whether an earlier batch has warmed the occluder grid): read from the very plans the
+ * render path enqueues from; nothing is enqueued.  No reference counterpart (the reference has one kernel per pass).  None of this shows in the image -- the
+ * contract is "same image with any setting" -- so this is where a test can pin which kernel instantiation runs, at which refill threshold, claim size and exit
+ * vote, and which words of the device counters each launch reads.  Every field is one uint32_t; *_word: offset in 32-bit words from the start of the batch's counter
+ * block; kernels: 0 = one ray per thread, 1 = packet (RF_EXP_LEGACY_LAYOUTS builds), 2 = kTraceWide; layouts: RF_LAYOUT_*.  RF_ERROR_INVALID_ARGUMENT for a bounce
+ * outside 1 .. the bounce count or num_samples == 0. */
+typedef struct rf_launch_plan
+{
+    /* the batch */
+    uint32_t num_samples, num_bounces;
+    uint32_t sample_perm;         /* 1: the samples of a pixel are traced in the order of their direction key */
+    uint32_t dense_raygen;        /* 1: kRaygen computes its queue positions (no atomic) */
+    uint32_t const_origin;        /* 1: the primary launch takes the pinhole camera's origin as an argument, kRaygen writes no origins */
+    uint32_t primary_layout;
+    uint32_t occluder_grid, occluder_scale_bits, occluder_mask; /* the occluder grid's cells: scale (the bits of a float) and mask; 0: no grid */
+    uint32_t runs;                /* 1: the sums run in the LDS-staged kernels */
+    uint32_t tile_list;           /* 1: the tile-list kernel adds the image and the moments (rf_renderer_render_adaptive's batches; never through this call) */
+    uint32_t accumulate_kernel;   /* 0 = one thread per pixel, 1 = runs, 2 = tile list */
+    uint32_t accumulate_pixels, aov_pixels, moment_pixels; /* pixels per workgroup of each sum's launch; 0: not launched */
+    uint32_t raygen_count_word;
+    /* the closest-hit launch */
+    uint32_t closest_kernel, closest_layout, closest_counting, closest_nearest, closest_dense, closest_refill_min, closest_chunk, closest_leaf_vote, closest_flags, closest_extra_lds;
+    uint32_t closest_count_word, closest_cursor_word;
+    /* kShade */
+    uint32_t shade_sorted, shade_aov, shade_flags, shade_sort_scale, shade_grid_cap;
+    /* the any-hit launch */
+    uint32_t shadow_kernel, shadow_layout, shadow_counting, shadow_nearest, shadow_dense, shadow_refill_min, shadow_chunk, shadow_leaf_vote, shadow_flags, shadow_extra_lds;
+    uint32_t shadow_count_word, shadow_cursor_word;
+    uint32_t shadow_cached;       /* it starts at the occluder cache's entries */
+    uint32_t shadow_first_look;   /* it runs behind kShadowFirstLook */
+    uint32_t shadow_self;         /* kShade settles the shadow rays that their own triangle answers and lists the rest */
+    uint32_t shadow_source;       /* whose count and list it reads: 0 = kShade's output queue, 1 = kShade's list of unsettled shadow rays, 2 = kShadowFirstLook's list */
+    uint32_t look_flags, look_count_word, look_list_word; /* kShadowFirstLook's flags, the count it reads, the length of the list it leaves; 0 without a first look */
+} rf_launch_plan;
+RF_API int  rf_renderer_launch_plan(const rf_renderer* r, uint32_t bounce, uint32_t num_samples, rf_launch_plan* out);
 /* Host helpers (no GPU needed). */
 /* The point-to-point operations rank `rank` posts (one RCCL group) for a gather to `root`: exactly the list
  * rf_renderer_gather_frame executes.  Offsets / counts in tiles (1024 float4): a receive lands at offset_tiles of the root's

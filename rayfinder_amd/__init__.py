@@ -681,6 +681,24 @@ class ReferencePathTracer:
                     occluder_hint_levels=int(raw[48]), shadow_first_look_from_bounce=int(raw[49]), dense_leaf_min=int(raw[50]), legacy_layouts_compiled=bool(raw[51]),
                     quad_half_area_ratio=float(raw[52:53].view(np.float32)[0]), tree_bytes=int(raw[54:56].view(np.uint64)[0]))
 
+    # rf_launch_plan, word by word
+    LAUNCH_PLAN_FIELDS = (
+        "num_samples", "num_bounces", "sample_perm", "dense_raygen", "const_origin", "primary_layout", "occluder_grid", "occluder_scale_bits", "occluder_mask", "runs",
+        "tile_list", "accumulate_kernel", "accumulate_pixels", "aov_pixels", "moment_pixels", "raygen_count_word",
+        "closest_kernel", "closest_layout", "closest_counting", "closest_nearest", "closest_dense", "closest_refill_min", "closest_chunk", "closest_leaf_vote", "closest_flags",
+        "closest_extra_lds", "closest_count_word", "closest_cursor_word",
+        "shade_sorted", "shade_aov", "shade_flags", "shade_sort_scale", "shade_grid_cap",
+        "shadow_kernel", "shadow_layout", "shadow_counting", "shadow_nearest", "shadow_dense", "shadow_refill_min", "shadow_chunk", "shadow_leaf_vote", "shadow_flags",
+        "shadow_extra_lds", "shadow_count_word", "shadow_cursor_word", "shadow_cached", "shadow_first_look", "shadow_self", "shadow_source", "look_flags", "look_count_word",
+        "look_list_word")
+
+    def launch_plan(self, bounce, num_samples):
+        """rf_renderer_launch_plan: the launches of bounce `bounce` (1-based) of this renderer's next batch of num_samples samples, as it would enqueue them in its
+        present state -> dict of ints (include/rayfinder_amd.h: rf_launch_plan)."""
+        raw = np.zeros(len(self.LAUNCH_PLAN_FIELDS), np.uint32)
+        check(lib.rf_renderer_launch_plan(self._h, bounce, num_samples, _ptr(raw)))
+        return dict(zip(self.LAUNCH_PLAN_FIELDS, (int(v) for v in raw)))
+
     def memory_info(self):
         """Device memory held by the handle: dict(path_state_bytes, paths_allocated, max_paths_per_batch, scene_bytes)."""
         v = [C.c_uint64(0) for _ in range(4)]

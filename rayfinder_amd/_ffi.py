@@ -171,6 +171,7 @@ SIGNATURES = {
     "rf_comm_all_reduce_max": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     "rf_comm_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]),
     "rf_renderer_layout_info": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rf_renderer_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "rf_renderer_memory_info": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_uint64)] * 4),
     "rf_gather_plan": (C.c_int, [C.c_uint32] * 6 + [C.c_void_p, C.POINTER(C.c_uint32)]),
     "rf_gather_layout": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),

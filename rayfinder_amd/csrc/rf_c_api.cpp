@@ -753,6 +753,15 @@ int rf_renderer_layout_info(const rf_renderer* r, rf_layout_info* out)
     });
 }
 
+int rf_renderer_launch_plan(const rf_renderer* r, uint32_t bounce, uint32_t num_samples, rf_launch_plan* out)
+{
+    return guarded([&] {
+        require(r && out, "null argument");
+        r->impl->launchPlan(bounce, num_samples, *out);
+        return RF_OK;
+    });
+}
+
 int rf_renderer_memory_info(const rf_renderer* r, uint64_t* path_state_bytes, uint64_t* paths_allocated, uint64_t* max_paths_per_batch, uint64_t* scene_bytes)
 {
     return guarded([&] {

@@ -21,6 +21,7 @@
 //
 // Kernel grids are sized for the worst case (all paths alive) and read the live count from
 // device memory, so a whole batch is enqueued without any host round trip.
+#include "rayfinder_amd.h"
 #include "rf_denoise.hpp"
 #include "rf_kernels.hpp"
 #include "rf_noise.hpp"
@@ -510,22 +511,79 @@ struct Renderer::Impl
         pendingBatches.clear();
     }
 
-    // ---- which record layout a launch reads (kTraceWide's COMPACT parameter), and the launch itself
+    // ---- The launch policy.  planBatch (once per batch) and planBounce (once per bounce) are the only places that decide which kernel runs with which parameters, and
+    // BatchCounters is the only place that knows the words of queueCounts; traceBatch and its launch members enqueue what the plans say.  The plans hold no pointer, and
+    // planning enqueues nothing and touches no device memory: rf_renderer_launch_plan reads the same plans out.
+    enum : uint32_t { kKernelScalar = 0, kKernelPacket = 1, kKernelWide = 2 };            // TraversalPlan::kernel
+    enum : uint32_t { kFromQueue = 0, kFromShadeList = 1, kFromLookList = 2 };            // BouncePlan::shadowSource
+    enum : uint32_t { kAccumulatePixels = 0, kAccumulateRuns = 1, kAccumulateTiles = 2 }; // BatchPlan::accumulateKernel
+    // One traversal launch, resolved: what actually runs.  kKernelWide: the kTraceWide instantiation named by (any-hit, counting build, nearest-first, record layout,
+    // dense leaf phase) from rf_trace.hip's table and its scheduling arguments; the other two kernels take the flags only.
+    struct TraversalPlan
+    {
+        uint32_t kernel;
+        int      layout; // which record layout the launch reads (kTraceWide's COMPACT parameter), or kLayoutScalar / kLayoutPacket
+        bool     anyHit, count, nearest, dense;
+        uint32_t refillMin, chunk, leafVote, flags, extraLds;
+    };
+    struct BatchPlan
+    {
+        uint32_t numSamples, numBounces, numTiles, pixelsPadded;
+        bool     samplePerm, denseRaygen, constOrigin;
+        int      primaryLayout;
+        bool     occluderGrid; // the batch's any-hit launches get the occluder grid: occluderGridEntries words, cells found by occScale / occMask
+        uint64_t occluderGridEntries;
+        float    occScale;
+        uint32_t occMask;
+        bool     firstLookReady; // a fact the batch mutates, as it stands for THIS batch (traceBatch / nextBatchFirstLookReady): the grid is warm and no hold-off runs
+        bool     runs, tileList;
+        uint32_t accumulateKernel, accumulatePixels, aovPixels, momentPixels; // pixels per workgroup of the sums' launches; 0: that sum is not launched
+    };
+    struct BouncePlan
+    {
+        TraversalPlan closest, shadow;
+        bool          shadeSorted, shadeAov;
+        uint32_t      shadeFlags, sortScale, skyFirstBounce;
+        uint32_t      itemGridCap; // kShade's and kShadowFirstLook's grid cap (0: one workgroup per 1 024 entries)
+        bool          cached, firstLook, selfShadow;
+        uint32_t      lookFlags, shadowSource; // shadowSource: whose count word and list the any-hit launch reads
+    };
+    // queueCounts by name.  Device words, one per 64-byte line (they are all hot atomics): the queue lengths [0, B] (0: raygen's queue, b: what kShade of bounce b
+    // leaves), the miss-list length per bounce, two work cursors of kShards lines per bounce for the traversal launches, the lengths of the lists kShadowFirstLook
+    // leaves to the any-hit launches per bounce, the lengths of kShade's lists of shadow rays still to trace (kShadeSelfShadow) per bounce.  b = 1 .. numBounces.
+    struct BatchCounters
+    {
+        uint32_t*                 base;
+        uint32_t                  numBounces;
+        static constexpr uint32_t kLine = kLineWords, kCursorWords = kLine * kShards;
+        uint32_t words() const { return kLine * (2 * numBounces + 1) + kCursorWords * 2 * numBounces + kLine * numBounces + kLine * numBounces; }
+        uint32_t queueWord(uint32_t b) const { return kLine * b; }
+        uint32_t missWord(uint32_t b) const { return kLine * (numBounces + 1) + kLine * (b - 1); }
+        uint32_t cursorClosestWord(uint32_t b) const { return kLine * (2 * numBounces + 1) + kCursorWords * 2 * (b - 1); }
+        uint32_t cursorShadowWord(uint32_t b) const { return cursorClosestWord(b) + kCursorWords; }
+        uint32_t listWord(uint32_t b) const { return kLine * (2 * numBounces + 1) + kCursorWords * 2 * numBounces + kLine * (b - 1); }
+        uint32_t shadowListWord(uint32_t b) const { return listWord(b) + kLine * numBounces; }
+        // the count word an any-hit launch (or kShadowFirstLook) of bounce b reads, by BouncePlan::shadowSource
+        uint32_t shadowCountWord(uint32_t b, uint32_t source) const { return source == kFromLookList ? listWord(b) : (source == kFromShadeList ? shadowListWord(b) : queueWord(b)); }
+        uint32_t* queueCount(uint32_t b) const { return base + queueWord(b); }
+        uint32_t* missCount(uint32_t b) const { return base + missWord(b); }
+        uint32_t* cursorClosest(uint32_t b) const { return base + cursorClosestWord(b); }
+        uint32_t* cursorShadow(uint32_t b) const { return base + cursorShadowWord(b); }
+        uint32_t* listCount(uint32_t b) const { return base + listWord(b); }
+        uint32_t* shadowListCount(uint32_t b) const { return base + shadowListWord(b); }
+        uint32_t* shadowCount(uint32_t b, uint32_t source) const { return base + shadowCountWord(b, source); }
+    };
+    // what a kTraceWide launch takes besides its plan: the streams, the queue with its count and cursor, the batch's geometry
     struct WideArgs
     {
         PathStreams     ps;
         const uint32_t* queue;
         const uint32_t* count;
         uint32_t*       cursor;
-        uint32_t        refillMin, chunk;
-        uint32_t        leafVote; // 0: optLeafVote
         float           tMax;
         dim3            grid;
-        uint32_t        extraLds;
         uint32_t        blocksWanted = 0; // != 0: the launch's worst-case workgroup count; the grid becomes min(this, what the device holds of the kernel launched)
     };
-    // One kTraceWide launch: the instantiation named by (any-hit, counting build, nearest-first, record layout, dense leaf phase) from rf_trace.hip's table; a
-    // combination the table does not hold falls back to the same one without the dense leaf phase (options can ask for it on a layout it is not built for)
     // Workgroups of THIS instantiation the device holds at once.  The persistent grid used to be sized once, from the closest-hit kernel (6 per CU: 80 VGPRs, 24 KB of LDS); the
     // any-hit instantiations need 63 ... 72 VGPRs and -- round 6: their stack holds child words only, 4 bytes per entry -- 12 KB: most of them fit 7 per CU.
     uint32_t residentBlocks(TraceWideKernel k, uint32_t extraLds)
@@ -539,14 +597,14 @@ struct Renderer::Impl
         residentCache[key] = n;
         return n;
     }
-    void launchWide(bool anyHit, bool count, bool nearest, int compact, bool dense, const WideScene& w, const WideArgs& a, uint32_t flags)
+    // One kTraceWide launch, as its plan says
+    void launchWide(const TraversalPlan& t, const WideScene& w, const WideArgs& a)
     {
-        TraceWideKernel k = traceWideKernel(anyHit, count, nearest, compact, dense);
-        if (k == nullptr && dense) k = traceWideKernel(anyHit, count, nearest, compact, false);
-        if (k == nullptr) throw std::logic_error("kTraceWide: record layout " + std::to_string(compact) + " is not compiled into this build");
+        const TraceWideKernel k = traceWideKernel(t.anyHit, t.count, t.nearest, t.layout, t.dense);
+        if (k == nullptr) throw std::logic_error("kTraceWide: record layout " + std::to_string(t.layout) + " is not compiled into this build");
         dim3 grid = a.grid;
-        if (a.blocksWanted != 0u && !wideBlocksForced && !count) grid = dim3(std::min(a.blocksWanted, residentBlocks(k, a.extraLds)));
-        hipLaunchKernelGGL(k, grid, dim3(kBlock), a.extraLds, stream, scene, w, sky, sunBasis, a.ps, a.queue, a.count, a.cursor, counters.ptr, a.refillMin, a.leafVote ? a.leafVote : optLeafVote, a.chunk, a.tMax, flags);
+        if (a.blocksWanted != 0u && !wideBlocksForced && !t.count) grid = dim3(std::min(a.blocksWanted, residentBlocks(k, t.extraLds)));
+        hipLaunchKernelGGL(k, grid, dim3(kBlock), t.extraLds, stream, scene, w, sky, sunBasis, a.ps, a.queue, a.count, a.cursor, counters.ptr, t.refillMin, t.leafVote, t.chunk, a.tMax, t.flags);
     }
     // the layout a test asks for, if this scene has it (else the binary records)
     int layoutIfPresent(int want) const
@@ -569,17 +627,29 @@ struct Renderer::Impl
         const uint32_t threshold = (flags >> kFlagDenseLeafShift) & 15u;
         return threshold != 0u && maxLeafTriangles >= threshold;
     }
-    void launchClosestWide(int layout, bool count, const WideScene& w, const WideArgs& a, uint32_t flags)
+    // the conservative layouts (VALU bound): the half-precision and the local-grid quad records
+    static bool conservativeLayout(int layout) { return layout == kLayoutQuadLocal || layout == kLayoutQuadHalf; }
+    // the layouts whose any-hit launch can work through a list of queue positions (the kTraceWide instantiations with the occluder-cache code: quad / half / local-grid records)
+    static bool worksThroughList(int layout) { return layout == kLayoutQuad || layout == kLayoutQuadHalf || layout == kLayoutQuadLocal; }
+    // The traversal launch of a layout, resolved (render path and ray queries alike).  nearest (any-hit): entries ordered by slab distance (NEAREST_FIRST); else record
+    // order (the conservative layouts' default: optShadowSignOrder) -- the compact and hot records always nearest-first.  A combination rf_trace.hip's table does not
+    // hold falls back to the same one without the dense leaf phase (options can ask for it on a layout it is not built for): the plan then says dense = false.
+    TraversalPlan resolveTraversal(bool anyHit, int layout, bool count, bool nearest, uint32_t flags, uint32_t refillMin, uint32_t chunk, uint32_t leafVote, uint32_t extraLds) const
     {
-        if (count) return launchWide(false, true, false, 0, false, w, a, flags);
-        launchWide(false, false, false, layout <= kLayoutOct ? layout : kLayoutBinary, denseWanted(flags), w, a, flags);
-    }
-    // nearest: entries ordered by slab distance (NEAREST_FIRST); else record order (the conservative layouts' default: optShadowSignOrder)
-    void launchShadowWide(int layout, bool nearest, bool count, const WideScene& w, const WideArgs& a, uint32_t flags)
-    {
-        if (count) return launchWide(true, true, nearest, 0, false, w, a, flags);
-        const int compact = (layout <= kLayoutQuadLocal) ? layout : kLayoutBinary;
-        launchWide(true, false, (compact == kLayoutCompact || compact == kLayoutHot) ? true : nearest, compact, denseWanted(flags), w, a, flags);
+        TraversalPlan t{};
+        t.kernel = layout == kLayoutScalar ? kKernelScalar : (layout == kLayoutPacket ? kKernelPacket : kKernelWide);
+        t.layout = layout, t.anyHit = anyHit, t.count = count, t.flags = flags;
+        if (t.kernel != kKernelWide) return t;
+        if (count) t.layout = kLayoutBinary, t.nearest = anyHit && nearest;
+        else if (!anyHit) t.layout = layout <= kLayoutOct ? layout : kLayoutBinary;
+        else
+        {
+            t.layout = (layout <= kLayoutQuadLocal) ? layout : kLayoutBinary;
+            t.nearest = (t.layout == kLayoutCompact || t.layout == kLayoutHot) ? true : nearest;
+        }
+        t.dense = !count && denseWanted(flags) && traceWideKernel(anyHit, false, t.nearest, t.layout, true) != nullptr;
+        t.refillMin = refillMin, t.chunk = chunk, t.leafVote = leafVote ? leafVote : optLeafVote, t.extraLds = extraLds; // (leafVote 0: optLeafVote)
+        return t;
     }
     // The layout the renderer picks BY ITSELF for the closest-hit / any-hit launch of a bounce (the per-scene defaults set at upload + the options; reported by
     // rf_renderer_layout_info and used by traceBatch): kLayoutScalar = the one-ray-per-thread kernels (trees the packed tests cannot serve), kLayoutPacket = kTracePacket
@@ -629,9 +699,117 @@ struct Renderer::Impl
     bool cachedShadowFor(uint32_t bounce) const
     {
         const int layout = shadowLayoutFor(bounce);
-        const bool conservative = layout == kLayoutQuadLocal || layout == kLayoutQuadHalf;
         const bool exactQuad = layout == kLayoutQuad && leafBoxesValid; // (its leaf visits then apply the box in the leaf's triangle record)
-        return !counting && shadowNearestFirst && (conservative || exactQuad) && bounce <= optOccluderCacheBounces && optOccluderGridCells != 0u;
+        return layout != kLayoutScalar && layout != kLayoutPacket && !counting && shadowNearestFirst && (conservativeLayout(layout) || exactQuad) && bounce <= optOccluderCacheBounces &&
+               optOccluderGridCells != 0u;
+    }
+
+    // The tile list a batch of rf_renderer_render_adaptive traces: while one is in use, tileIds / tileValidBefore hold IT (uploadTileList) and not the shard's list
+    struct ActiveTiles
+    {
+        uint32_t numTiles;
+        uint64_t validPixels;
+    };
+    // The once-per-batch decisions, for a batch of numSamples samples of the shard's tiles (or of the `active` list of render_adaptive)
+    BatchPlan planBatch(uint32_t numSamples, const ActiveTiles* active) const
+    {
+        BatchPlan b{};
+        const uint64_t validPixels = active ? active->validPixels : this->validPixels;
+        b.numSamples = numSamples;
+        b.numBounces = params.samplingParams.numBounces;
+        b.numTiles = active ? active->numTiles : static_cast<uint32_t>(tiles.size());
+        b.pixelsPadded = b.numTiles * 1024u;
+        // (kSamplePermutation ranks by counting, O(S^2): fine for the few hundred samples a batch of a real frame holds,
+        // skipped for the huge sample counts a tiny frame can put into one batch)
+        b.samplePerm = optSampleSort && numSamples > 1 && numSamples <= 8192 && optSlotGroupShift != kSlotSampleMajor;
+        // Pinhole camera (lensRadius == 0): kRaygen's origin = camera.origin + (0 * right + 0 * up) is camera.origin itself for every path, bit for bit, as long as no
+        // component of camera.origin is a zero (whose sign the +-0 addend could flip) and right / up are finite (0 * inf = NaN).  The primary launch then takes it as a kernel
+        // argument and kRaygen writes 28 instead of 40 bytes per path.  Only the wide traversal kernels know the flag (the scalar kernels read ps.rayO).
+        const auto finite3 = [](Vec3 v) { return std::isfinite(v.x) && std::isfinite(v.y) && std::isfinite(v.z); };
+        const Camera& camNow = params.camera;
+        b.primaryLayout = closestLayoutFor(1);
+        b.constOrigin = optConstPrimaryOrigin && camNow.lensRadius == 0.0f && camNow.origin.x != 0.0f && camNow.origin.y != 0.0f && camNow.origin.z != 0.0f &&
+                        finite3(camNow.origin) && finite3(camNow.right) && finite3(camNow.up) && b.primaryLayout != kLayoutScalar && b.primaryLayout != kLayoutPacket;
+        // (kRaygen computes its queue positions instead of appending with one atomic per 1 024 slots, where the slot order allows it: FrameParams::tileValidBefore)
+        b.denseRaygen = optDenseRaygen && (optSlotGroupShift == 0u || optSlotGroupShift == kSlotSampleMajor) && static_cast<uint64_t>(validPixels) * numSamples <= 0xFFFFFFFFull;
+        b.occluderGrid = optOccluderCacheBounces != 0u && optOccluderGridCells != 0u;
+        if (b.occluderGrid)
+        {
+            b.occluderGridEntries = (uint64_t{1} << optOccluderGridLog2Cells) * kOccSlots;
+            const float extent = std::max({wide.rootHi.x - wide.rootLo.x, wide.rootHi.y - wide.rootLo.y, wide.rootHi.z - wide.rootLo.z, 1e-20f});
+            b.occScale = static_cast<float>(optOccluderGridCells) / extent;
+            b.occMask = static_cast<uint32_t>(b.occluderGridEntries / kOccSlots - 1);
+        }
+        // The sums in sample order.  Where the slot order is pixel-major and the step long enough, the LDS-staged "runs" kernels (a 64-lane workgroup per
+        // `pixelsPerGroup` pixels); else one thread per pixel
+        b.runs = optSlotGroupShift == 0u && numSamples > 4u && optAccumulateRuns;
+        b.tileList = active != nullptr;
+        const uint32_t perThread = static_cast<uint32_t>(kBlock);
+        if (b.tileList) b.accumulateKernel = kAccumulateTiles, b.accumulatePixels = b.runs ? kMomentPixels : perThread;
+        else if (b.runs && numSamples <= kAccMaxSamples)
+        {
+            // (pixels per workgroup by the LDS their runs take: <= ~8 KB per workgroup keeps twenty of them resident per CU)
+            b.accumulateKernel = kAccumulateRuns, b.accumulatePixels = numSamples > 640u ? 1u : (numSamples > 160u ? 2u : kAccPixels);
+        }
+        else b.accumulateKernel = kAccumulatePixels, b.accumulatePixels = perThread;
+        // the first-hit AOV sums (no bounce, no primary hit: the records were not written) and the radiance second moments: launches of their own unless the tile-list kernel runs
+        b.aovPixels = (!b.tileList && aovSums.on && b.numBounces != 0u) ? (b.runs ? kAovPixels : perThread) : 0u;
+        b.momentPixels = (!b.tileList && momentSums.on) ? (b.runs ? kMomentPixels : perThread) : 0u;
+        return b;
+    }
+    // Is a cached any-hit launch of the handle's NEXT batch free to run behind kShadowFirstLook, as far as the books a batch keeps go?  traceBatch's own bookkeeping,
+    // foreseen without touching it (rf_renderer_launch_plan): a grid of another size starts cold, a report that has landed may start a hold-off, a running one counts down.
+    bool nextBatchFirstLookReady(const BatchPlan& b) const
+    {
+        if (!b.occluderGrid || occluderGrid.count != b.occluderGridEntries || !occluderGridWarm) return false;
+        if (lookPending && hipEventQuery(lookEvent) == hipSuccess) return !(lookBatchHost[1] != 0ull && lookBatchHost[0] * 4ull < lookBatchHost[1]) && firstLookHoldOff == 0u;
+        return firstLookHoldOff <= 1u;
+    }
+    // Everything the launches of one bounce need
+    BouncePlan planBounce(uint32_t bounce, const BatchPlan& batch) const
+    {
+        BouncePlan p{};
+        const uint32_t uniformFlag = ((optUniformFetch < 0 ? bounce <= 2 : optUniformFetch > 0) ? kFlagUniformFetch : 0u) | (optUniformFetch >= 2 ? kFlagUniformTri : 0u) |
+                                     (bounce >= optDenseLeafFromBounce ? (std::min(optDenseLeafMin, 15u) << kFlagDenseLeafShift) : 0u);
+        // incoherent closest-hit launches refill earlier: their rays differ most in length, so lanes go idle sooner (per-bounce
+        // sweep, profiles/r02_final/bounce_sweep*.log: bounces 3-8 -4 % at 20-24 idle lanes, bounces 1-2 and the shadow launches +6 .. +10 %)
+        // ... and the coherent launches of the first bounces, whose rays are short and alike, claim larger chunks (one cursor atomic = one
+        // wave-wide stall: bounce 1 -4 % at 256 entries, the deep bounces +0.5 %)
+        const uint32_t chunkNow = bounce <= optChunkEarlyBounces ? optChunkEarly : optChunk;
+        const int      layoutClosest = closestLayoutFor(bounce);
+        // (scenes with long leaves -- the DENSE_LEAVES instantiations -- keep 22: a phase over dense (lane, triangle) pairs wants many parked lanes; clutter atrium +2.4 % at 12: profiles/r06_lanes)
+        const uint32_t refillClosest = bounce >= optRefillDeepFromBounce ? (layoutClosest == kLayoutQuad ? optRefillMinDeepQuad : (denseWanted(uniformFlag) ? optRefillMinDeepDense : optRefillMinDeep)) : optRefillMin;
+        // (kInfinityCacheBytes: the scene's records + triangles against the 256-MB Infinity Cache, as the layout selector's own test)
+        const uint32_t leafVoteClosest = (!counting && !denseWanted(uniformFlag) && treeBytes <= (192ull << 20)) ? optLeafVoteClosest : 0u;
+        const bool     wideClosest = layoutClosest != kLayoutScalar && layoutClosest != kLayoutPacket; // (the other two kernels take no flags)
+        p.closest = resolveTraversal(false, layoutClosest, counting, false, wideClosest ? (uniformFlag | (bounce == 1 && batch.constOrigin ? kFlagConstOrigin : 0u)) : 0u,
+                                     counting ? optRefillMin : refillClosest, chunkNow, leafVoteClosest, counting ? 0u : optExtraLds);
+        // kShade's own-triangle test of the shadow rays (kShadeSelfShadow): wherever this bounce's any-hit launch is one that can work through a list of queue positions
+        // and nothing has to be counted node by node
+        const int layoutShadow = shadowLayoutFor(bounce);
+        // (bounce <= 64: kBounceTotals keeps one mask bit per bounce -- as for firstLook below; deeper bounces trace every shadow ray and count them in the launch: ADVICE r5)
+        p.selfShadow = optShadowSelfTest && selfShadowOk && !counting && bounce <= 64u && worksThroughList(layoutShadow);
+        // (the first-hit AOVs are written by the unsorted bounce-1 kernel, whatever shade_sort_from_bounce says: the sort is a scheduling choice)
+        p.shadeAov = aovSums.on && bounce == 1;
+        p.shadeSorted = !p.shadeAov && optShadeSortFromBounce != 0u && bounce >= optShadeSortFromBounce;
+        p.shadeFlags = (bounce == batch.numBounces ? kShadeLastBounce : 0u) | (bounce == 1 ? kShadeFirstBounce : 0u) | (p.selfShadow ? kShadeSelfShadow : 0u);
+        p.sortScale = p.shadeSorted ? sortScale : 0u;
+        p.skyFirstBounce = bounce == 1 ? 1u : 0u;
+        p.itemGridCap = optShadeBlocks;
+        // occluder cache (kTraceWide, kFlagOccluderCache): the conservative-record any-hit launches of bounces 1..optOccluderCacheBounces; their rays are
+        // short (a third of the steps), so the deep launches refill earlier
+        p.cached = cachedShadowFor(bounce);
+        // ... behind kShadowFirstLook (see there) from the second batch on: the first batch of a renderer fills the grid (the traversal kernel's own first look serves)
+        p.firstLook = p.cached && occluderHintLevels == 0u && optShadowFirstLookFromBounce != 0u && bounce >= optShadowFirstLookFromBounce && bounce <= 64u && batch.firstLookReady;
+        p.shadowSource = p.firstLook ? kFromLookList : (p.selfShadow ? kFromShadeList : kFromQueue);
+        p.lookFlags = p.firstLook ? ((bounce == 1 ? kLookFirstBounce : 0u) | (p.selfShadow ? kLookNoRayCount : 0u)) : 0u;
+        const uint32_t shadowFlags = (bounce == 1 ? kFlagFirstBounce : 0u) | uniformFlag | (p.cached ? kFlagOccluderCache : 0u) | (p.firstLook ? (kFlagOccluderNoTry | kFlagNoRayCount) : 0u) | (p.selfShadow ? kFlagNoRayCount : 0u);
+        // the conservative layouts (VALU bound) visit a record's entries in record order unless asked otherwise; the exact and binary records nearest-first
+        const bool nearest = shadowNearestFirst && !(conservativeLayout(layoutShadow) && optShadowSignOrder);
+        // (the one-ray-per-thread kernel takes "first bounce" alone, the packet kernel that bit of the flag word)
+        const uint32_t flagsRun = layoutShadow == kLayoutScalar ? (bounce == 1 ? 1u : 0u) : (layoutShadow == kLayoutPacket ? (shadowFlags & kFlagFirstBounce) : shadowFlags);
+        p.shadow = resolveTraversal(true, layoutShadow, counting, nearest, flagsRun, optRefillMin, chunkNow, 0u, counting ? 0u : optExtraLds);
+        return p;
     }
 
     // Test hook (option query_variant = 2): arbitrary rays through the render path's persistent
@@ -655,14 +833,15 @@ struct Renderer::Impl
         RF_HIP(hipMemcpyAsync(sRayO.ptr, o.data(), n * sizeof(P3), hipMemcpyHostToDevice, stream));
         RF_HIP(hipMemcpyAsync(sRayD.ptr, d.data(), n * sizeof(P3), hipMemcpyHostToDevice, stream));
         RF_HIP(hipMemcpyAsync(queueA.ptr, ids.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-        const uint32_t words = kLineWords * (1 + kShards);
+        const BatchCounters qc{nullptr, 0u}; // (no bounce: the queue's length, then the one launch's cursor)
+        const uint32_t words = qc.words() + BatchCounters::kCursorWords;
         if (queueCounts.count < words) queueCounts.alloc(words);
         RF_HIP(hipMemsetAsync(queueCounts.ptr, 0, queueCounts.count * sizeof(uint32_t), stream));
         const uint32_t count = static_cast<uint32_t>(n);
         RF_HIP(hipMemcpyAsync(queueCounts.ptr, &count, sizeof count, hipMemcpyHostToDevice, stream));
         PathStreams ps{sRayO.ptr, sRayD.ptr, sThr.ptr, sRad.ptr, sHit.ptr, sPending.ptr, sNoise.ptr, sRayD2.ptr, sThr2.ptr, sNoise2.ptr};
         const dim3  grid(std::min<uint32_t>(static_cast<uint32_t>((n + kBlock - 1) / kBlock), wideBlocks));
-        const WideArgs wa{ps, queueA.ptr, queueCounts.ptr, queueCounts.ptr + kLineWords, optRefillMin, optChunk, 0u, tMax, grid, 0u};
+        const WideArgs wa{ps, queueA.ptr, queueCounts.ptr + qc.queueWord(0), queueCounts.ptr + qc.cursorClosestWord(1), tMax, grid};
         if (shadow)
         {
             // rad = 0, pending = 1: rad.x becomes visibility * SOLAR_INV_PDF
@@ -672,7 +851,7 @@ struct Renderer::Impl
             RF_HIP(hipStreamSynchronize(stream)); // `ones` leaves scope before the launches are waited for
             // (the ray-query entry points take the layout the test asks for -- query_compact -- where the scene has it; the oct records serve closest-hit rays only)
             const int layout = layoutIfPresent((optQueryCompact == kLayoutOct || (!shadowNearestFirst && optQueryCompact < kLayoutQuad)) ? kLayoutBinary : optQueryCompact);
-            launchShadowWide(layout, shadowNearestFirst, false, wide, wa, kFlagShadowDirFromStream | denseFlag);
+            launchWide(resolveTraversal(true, layout, false, shadowNearestFirst, kFlagShadowDirFromStream | denseFlag, optRefillMin, optChunk, 0u, 0u), wide, wa);
         }
         else
         {
@@ -699,7 +878,7 @@ struct Renderer::Impl
                 RF_HIP(hipEventCreate(&e1));
                 RF_HIP(hipEventRecord(e0, stream));
             }
-            launchClosestWide(layoutIfPresent(optQueryCompact), false, wq, wa, denseFlag);
+            launchWide(resolveTraversal(false, layoutIfPresent(optQueryCompact), false, false, denseFlag, optRefillMin, optChunk, 0u, 0u), wq, wa);
             if (timed) RF_HIP(hipEventRecord(e1, stream));
             hipLaunchKernelGGL(hitPointsKernel(), dim3((count + 255) / 256), dim3(256), 0, stream, scene, sHit.ptr, sRayO.ptr, count);
             if (timed)
@@ -798,12 +977,6 @@ struct Renderer::Impl
         return meanImage.ptr;
     }
 
-    // The tile list a batch of rf_renderer_render_adaptive traces: while one is in use, tileIds / tileValidBefore hold IT (uploadTileList) and not the shard's list
-    struct ActiveTiles
-    {
-        uint32_t numTiles;
-        uint64_t validPixels;
-    };
     // tileIds / tileValidBefore <- a list of tile ids (ascending) of the whole frame.  The stream must be idle (the copies are synchronous).  -> pixels inside the frame
     uint64_t uploadTileList(const std::vector<uint32_t>& list)
     {
@@ -827,26 +1000,107 @@ struct Renderer::Impl
         return n;
     }
 
+    // ---- the launch groups of a bounce: they enqueue what the bounce's plan says, on the queues and words of BounceIo
+    struct BounceIo
+    {
+        uint32_t      bounce;
+        PathStreams   ps;
+        uint32_t*     in;  // the bounce's queue
+        uint32_t*     out; // the hits kShade appends: the next bounce's queue and this bounce's shadow rays
+        BatchCounters words;
+        uint32_t      blocks, itemBlocks; // workgroups for one thread per path / per kItems paths
+        dim3          persistentGrid;
+    };
+    static dim3 cappedGrid(uint32_t blocks, uint32_t cap) { return dim3(cap ? std::min(blocks, cap) : blocks); }
+    void enqueueClosest(const TraversalPlan& t, const BounceIo& io)
+    {
+        uint32_t* const countIn = io.words.queueCount(io.bounce - 1);
+        if (t.kernel == kKernelScalar)
+            hipLaunchKernelGGL(traceClosestKernel(t.count), dim3(io.blocks), dim3(kBlock), 0, stream, scene, io.ps, io.in, countIn, counters.ptr);
+#if defined(RF_EXP_LEGACY_LAYOUTS)
+        else if (t.kernel == kKernelPacket)
+            hipLaunchKernelGGL(tracePacketKernel(false), io.persistentGrid, dim3(kBlock), 0, stream, scene, wide, sky, sunBasis, io.ps, io.in, countIn, counters.ptr, kTMax, t.flags);
+#endif
+        else
+            launchWide(t, wide, WideArgs{io.ps, io.in, countIn, io.words.cursorClosest(io.bounce), kTMax, io.persistentGrid, io.blocks});
+    }
+    void enqueueShadeAndSky(const BouncePlan& p, const BounceIo& io)
+    {
+        uint32_t* const missCount = io.words.missCount(io.bounce);
+        hipLaunchKernelGGL(shadeKernel(p.shadeSorted, p.shadeAov), cappedGrid(io.itemBlocks, p.itemGridCap), dim3(kBlock), 0, stream, scene, sky, sunBasis, io.ps, io.in,
+                           io.words.queueCount(io.bounce - 1), io.out, io.words.queueCount(io.bounce), missQueue.ptr, missSlots.ptr, missCount, shadowList.ptr,
+                           io.words.shadowListCount(io.bounce), p.shadeFlags, p.sortScale, p.shadeAov ? sAov.ptr : nullptr);
+        // the paths that left the scene at this bounce, while its direction / throughput arrays are intact
+        // (its slot comes with the miss list: kSky reads nothing of the bounce's queue -- round 5: reading the slot through the queue position was a third
+        // dependent gather, and kShade + kSky went from 19.7 to 15.8 ms per 64 spp without it)
+        hipLaunchKernelGGL(skyKernel(optTranscendentalsF32), dim3(std::min(io.blocks, skyBlocks)), dim3(kBlock), 0, stream, sky, io.ps, missSlots.ptr, missQueue.ptr, missCount, p.skyFirstBounce);
+    }
+    void enqueueShadow(const BouncePlan& p, const BounceIo& io)
+    {
+        uint32_t* const countOut = io.words.queueCount(io.bounce);
+        WideScene       wide = this->wide; // (the launches below name `wide`)
+        if (p.firstLook)
+        {
+            // (the bounce's input queue is free by now -- kShade and kSky have consumed it -- and holds the list)
+            hipLaunchKernelGGL(shadowFirstLookKernel(), cappedGrid(io.itemBlocks, p.itemGridCap), dim3(kBlock), 0, stream, scene, wide, sky, sunBasis, io.ps, io.out,
+                               p.selfShadow ? shadowList.ptr : nullptr, io.words.shadowCount(io.bounce, p.selfShadow ? kFromShadeList : kFromQueue), io.in, io.words.listCount(io.bounce),
+                               counters.ptr, kTMax, p.lookFlags);
+            wide.rayList = io.in;
+        }
+        else if (p.selfShadow) wide.rayList = shadowList.ptr; // (positions only: bit 31 clear, the traversal kernel takes its own first look)
+        const TraversalPlan& t = p.shadow;
+        if (t.kernel == kKernelScalar)
+            hipLaunchKernelGGL(traceShadowKernel(t.count), dim3(io.blocks), dim3(kBlock), 0, stream, scene, sky, sunBasis, io.ps, io.out, countOut, counters.ptr, t.flags);
+#if defined(RF_EXP_LEGACY_LAYOUTS)
+        else if (t.kernel == kKernelPacket)
+            hipLaunchKernelGGL(tracePacketKernel(true), io.persistentGrid, dim3(kBlock), 0, stream, scene, wide, sky, sunBasis, io.ps, io.out, countOut, counters.ptr, kTMax, t.flags);
+#endif
+        else
+            launchWide(t, wide, WideArgs{io.ps, io.out, io.words.shadowCount(io.bounce, p.shadowSource), io.words.cursorShadow(io.bounce), kTMax, io.persistentGrid, io.blocks});
+    }
+    // the batch's sums in sample order: the image, then the first-hit AOV sums and the radiance second moments (timed with the accumulation: rf_stats has no entry of
+    // their own for them) -- or the tile-list kernel for the image and the moments at once
+    void enqueueSums(const BatchPlan& b, const FrameParams& fp, const PathStreams& ps)
+    {
+        const auto sumGrid = [&](uint32_t pixelsPerGroup) { return dim3((fp.pixelsPadded + pixelsPerGroup - 1) / pixelsPerGroup); };
+        const dim3 sumBlock(b.runs ? 64u : static_cast<uint32_t>(kBlock));
+        if (b.accumulateKernel == kAccumulateTiles)
+        {
+            // (whole frame: compact slot == tile id, so the listed tiles' sums sit at tile id * 1024 of the image and the moments)
+            hipLaunchKernelGGL(accumulateTilesKernel(b.runs), sumGrid(b.accumulatePixels), sumBlock, 0, stream, fp, tileIds.ptr, static_cast<const float4*>(ps.rad), image, moments());
+            return;
+        }
+        if (b.accumulateKernel == kAccumulateRuns)
+            hipLaunchKernelGGL(accumulateRunsKernel(b.accumulatePixels), sumGrid(b.accumulatePixels), dim3(64), b.accumulatePixels * 3u * (b.numSamples + 1u) * sizeof(float), stream, fp,
+                               tileIds.ptr, ps, image);
+        else
+            hipLaunchKernelGGL(accumulateKernel(), sumGrid(b.accumulatePixels), dim3(kBlock), 0, stream, fp, tileIds.ptr, ps, image);
+        if (b.aovPixels != 0u)
+            hipLaunchKernelGGL(accumulateAovKernel(b.runs), sumGrid(b.aovPixels), sumBlock, 0, stream, fp, tileIds.ptr, sAov.ptr, aovAlbedoCoverage(), aovNormalDepth());
+        if (b.momentPixels != 0u)
+            hipLaunchKernelGGL(accumulateMomentsKernel(b.runs), sumGrid(b.momentPixels), sumBlock, 0, stream, fp, tileIds.ptr, static_cast<const float4*>(ps.rad), moments());
+    }
+
     // Trace `numSamples` consecutive samples (sample indices start at frame `firstFrame`) of the shard's tiles -- or, active != nullptr, of the tile list that
     // tileIds / tileValidBefore hold then: the radiance and its squares are added by the tile-list kernel, at the listed tiles' own places.
+    // The enqueue loop: frame parameters, planBatch, the counters, raygen, per bounce planBounce and its three launch groups, the totals, the sums.
     void traceBatch(uint32_t firstFrame, uint32_t numSamples, const ActiveTiles* active = nullptr)
     {
         const uint64_t validPixels = active ? active->validPixels : this->validPixels;
-        FrameParams fp{};
+        BatchPlan      batch = planBatch(numSamples, active);
+        FrameParams    fp{};
         fp.width = params.width;
         fp.height = params.height;
         fp.camera = params.camera;
         fp.samplesPerPixel = params.samplingParams.numSamplesPerPixel;
-        fp.numBounces = params.samplingParams.numBounces;
+        fp.numBounces = batch.numBounces;
         fp.firstFrame = firstFrame;
         fp.numSamples = numSamples;
-        fp.numTiles = active ? active->numTiles : static_cast<uint32_t>(tiles.size());
-        fp.pixelsPadded = fp.numTiles * 1024u;
+        fp.numTiles = batch.numTiles;
+        fp.pixelsPadded = batch.pixelsPadded;
         fp.slotGroupShift = optSlotGroupShift;
         fp.samplePerm = fp.sampleInvPerm = nullptr;
-        // (kSamplePermutation ranks by counting, O(S^2): fine for the few hundred samples a batch of a real frame holds,
-        // skipped for the huge sample counts a tiny frame can put into one batch)
-        if (optSampleSort && numSamples > 1 && numSamples <= 8192 && optSlotGroupShift != kSlotSampleMajor)
+        if (batch.samplePerm)
         {
             if (samplePerm.count < 2ull * numSamples) samplePerm.alloc(2ull * numSamples); // (the stream is idle the first time; later batches are no larger)
             fp.samplePerm = samplePerm.ptr;
@@ -856,20 +1110,10 @@ struct Renderer::Impl
         if (fp.numTiles == 0) return;
         fp.divNumSamples = FastDiv::make(fp.numSamples), fp.divPixelsPadded = FastDiv::make(fp.pixelsPadded), fp.divTilesX = FastDiv::make(fp.tilesX);
         fp.divSamplesPerPixel = FastDiv::make(fp.samplesPerPixel);
-        // Pinhole camera (lensRadius == 0): kRaygen's origin = camera.origin + (0 * right + 0 * up) is camera.origin itself for every path, bit for bit, as long as no
-        // component of camera.origin is a zero (whose sign the +-0 addend could flip) and right / up are finite (0 * inf = NaN).  The primary launch then takes it as a kernel
-        // argument and kRaygen writes 28 instead of 40 bytes per path.  Only the wide traversal kernels know the flag (the scalar kernels read ps.rayO).
-        const auto finite3 = [](Vec3 v) { return std::isfinite(v.x) && std::isfinite(v.y) && std::isfinite(v.z); };
-        const Camera& camNow = params.camera;
-        const int     primaryLayout = closestLayoutFor(1);
-        const bool    constOrigin = optConstPrimaryOrigin && camNow.lensRadius == 0.0f && camNow.origin.x != 0.0f && camNow.origin.y != 0.0f && camNow.origin.z != 0.0f &&
-                                 finite3(camNow.origin) && finite3(camNow.right) && finite3(camNow.up) && primaryLayout != kLayoutScalar && primaryLayout != kLayoutPacket;
-        fp.skipOrigins = constOrigin ? 1u : 0u;
-        // (kRaygen computes its queue positions instead of appending with one atomic per 1 024 slots, where the slot order allows it: FrameParams::tileValidBefore)
-        const bool denseRaygen = optDenseRaygen && (fp.slotGroupShift == 0u || fp.slotGroupShift == kSlotSampleMajor) && static_cast<uint64_t>(validPixels) * numSamples <= 0xFFFFFFFFull;
-        fp.tileValidBefore = denseRaygen ? tileValidBefore.ptr : nullptr;
+        fp.skipOrigins = batch.constOrigin ? 1u : 0u;
+        fp.tileValidBefore = batch.denseRaygen ? tileValidBefore.ptr : nullptr;
         fp.validPixels = static_cast<uint32_t>(validPixels);
-        wide.constOriginX = camNow.origin.x, wide.constOriginY = camNow.origin.y, wide.constOriginZ = camNow.origin.z;
+        wide.constOriginX = params.camera.origin.x, wide.constOriginY = params.camera.origin.y, wide.constOriginZ = params.camera.origin.z;
 
         const uint64_t paths = static_cast<uint64_t>(numSamples) * fp.pixelsPadded;
         const uint32_t blocks = static_cast<uint32_t>((paths + kBlock - 1) / kBlock);
@@ -878,21 +1122,20 @@ struct Renderer::Impl
         PathStreams    ps{sRayO.ptr, sRayD.ptr, sThr.ptr, sRad.ptr, sHit.ptr, sPending.ptr, sNoise.ptr, sRayD2.ptr, sThr2.ptr, sNoise2.ptr};
         const uint32_t numBounces = fp.numBounces;
 
+        // the books a batch keeps (allocation on first use, the grid's warmth, the first-look hold-off): the plan takes them as facts
         wide.occGrid = nullptr;
         wide.rayList = nullptr;
-        if (optOccluderCacheBounces != 0u && optOccluderGridCells != 0u)
+        if (batch.occluderGrid)
         {
-            const size_t kOccluderGridEntries = (size_t{1} << optOccluderGridLog2Cells) * kOccSlots;
-            if (occluderGrid.count != kOccluderGridEntries)
+            if (occluderGrid.count != batch.occluderGridEntries)
             {
-                occluderGrid.alloc(kOccluderGridEntries);
+                occluderGrid.alloc(batch.occluderGridEntries);
                 occluderGridWarm = false;
-                RF_HIP(hipMemsetAsync(occluderGrid.ptr, 0, kOccluderGridEntries * sizeof(uint32_t), stream));
+                RF_HIP(hipMemsetAsync(occluderGrid.ptr, 0, batch.occluderGridEntries * sizeof(uint32_t), stream));
             }
-            const float extent = std::max({wide.rootHi.x - wide.rootLo.x, wide.rootHi.y - wide.rootLo.y, wide.rootHi.z - wide.rootLo.z, 1e-20f});
             wide.occGrid = occluderGrid.ptr;
-            wide.occScale = static_cast<float>(optOccluderGridCells) / extent;
-            wide.occMask = static_cast<uint32_t>(kOccluderGridEntries / kOccSlots - 1);
+            wide.occScale = batch.occScale;
+            wide.occMask = batch.occMask;
         }
         if (lookBatch.count == 0)
         {
@@ -906,135 +1149,39 @@ struct Renderer::Impl
             if (lookBatchHost[1] != 0ull && lookBatchHost[0] * 4ull < lookBatchHost[1]) firstLookHoldOff = 16u;
         }
         else if (firstLookHoldOff != 0u) --firstLookHoldOff;
+        batch.firstLookReady = occluderGridWarm && firstLookHoldOff == 0u;
         RF_HIP(hipMemsetAsync(lookBatch.ptr, 0, 2 * sizeof(unsigned long long), stream));
         BatchTiming bt{getEvent(), getEvent(), numSamples};
         RF_HIP(hipEventRecord(bt.start, stream));
 
-        // device words, one per 64-byte line (they are all hot atomics): [0, B]: queue lengths per
-        // bounce; [B+1, 2B]: miss-list length per bounce; then two work cursors per bounce for the traversal launches
-        constexpr uint32_t kLine = kLineWords;
-        const uint32_t words = kLine * (2 * numBounces + 1) + kLine * kShards * 2 * numBounces + kLine * numBounces + kLine * numBounces;
-        if (queueCounts.count < words) queueCounts.alloc(words);
-        uint32_t* const missCounts = queueCounts.ptr + kLine * (numBounces + 1);
-        uint32_t* const cursors = queueCounts.ptr + kLine * (2 * numBounces + 1);
-        uint32_t* const listCounts = cursors + kLine * kShards * 2 * numBounces; // lengths of the lists kShadowFirstLook leaves to the any-hit launches, per bounce
-        uint32_t* const shadowListCounts = listCounts + kLine * numBounces; // lengths of kShade's lists of shadow rays still to trace (kShadeSelfShadow), per bounce
-        unsigned long long lookMask = 0ull, selfMask = 0ull;
-        const uint32_t  itemBlocks = static_cast<uint32_t>((paths + kBlock * kItems - 1) / (kBlock * kItems));
+        const uint32_t countWords = BatchCounters{nullptr, numBounces}.words();
+        if (queueCounts.count < countWords) queueCounts.alloc(countWords);
+        const BatchCounters words{queueCounts.ptr, numBounces};
+        unsigned long long  lookMask = 0ull, selfMask = 0ull;
+        const uint32_t      itemBlocks = static_cast<uint32_t>((paths + kBlock * kItems - 1) / (kBlock * kItems));
         RF_HIP(hipMemsetAsync(queueCounts.ptr, 0, queueCounts.count * sizeof(uint32_t), stream));
 
-        uint32_t* qIn = queueA.ptr;
-        uint32_t* qOut = queueB.ptr;
+        BounceIo io{0u, ps, queueA.ptr, queueB.ptr, words, blocks, itemBlocks, dim3(std::min(blocks, wideBlocks))};
         if (fp.samplePerm)
             hipLaunchKernelGGL(samplePermutationKernel(), dim3((numSamples + 255) / 256), dim3(256), 0, stream, firstFrame, fp.samplesPerPixel, numSamples,
                                const_cast<uint32_t*>(fp.samplePerm), const_cast<uint32_t*>(fp.sampleInvPerm));
         launchTimed(0, [&] {
-            hipLaunchKernelGGL(raygenKernel(optTranscendentalsF32), dim3(itemBlocks), dim3(kBlock), 0, stream, fp, scene, tileIds.ptr, ps, qIn, queueCounts.ptr, counters.ptr);
+            hipLaunchKernelGGL(raygenKernel(optTranscendentalsF32), dim3(itemBlocks), dim3(kBlock), 0, stream, fp, scene, tileIds.ptr, io.ps, io.in, words.queueCount(0), counters.ptr);
         });
-        const dim3 persistentGrid(std::min(blocks, wideBlocks));
-        for (uint32_t bounce = 1; bounce <= numBounces; ++bounce)
+        for (io.bounce = 1; io.bounce <= numBounces; ++io.bounce)
         {
-            uint32_t* countIn = queueCounts.ptr + kLine * (bounce - 1);
-            uint32_t* countOut = queueCounts.ptr + kLine * bounce;
-            uint32_t* cursorClosest = cursors + kLine * kShards * 2 * (bounce - 1);
-            uint32_t* cursorShadow = cursorClosest + kLine * kShards;
-            const uint32_t uniformFlag = ((optUniformFetch < 0 ? bounce <= 2 : optUniformFetch > 0) ? kFlagUniformFetch : 0u) | (optUniformFetch >= 2 ? kFlagUniformTri : 0u) |
-                                         (bounce >= optDenseLeafFromBounce ? (std::min(optDenseLeafMin, 15u) << kFlagDenseLeafShift) : 0u);
-            // incoherent closest-hit launches refill earlier: their rays differ most in length, so lanes go idle sooner (per-bounce
-            // sweep, profiles/r02_final/bounce_sweep*.log: bounces 3-8 -4 % at 20-24 idle lanes, bounces 1-2 and the shadow launches +6 .. +10 %)
-            // ... and the coherent launches of the first bounces, whose rays are short and alike, claim larger chunks (one cursor atomic = one
-            // wave-wide stall: bounce 1 -4 % at 256 entries, the deep bounces +0.5 %)
-            const uint32_t chunkNow = bounce <= optChunkEarlyBounces ? optChunkEarly : optChunk;
-            const int      layoutClosest = closestLayoutFor(bounce);
-            // (scenes with long leaves -- the DENSE_LEAVES instantiations -- keep 22: a phase over dense (lane, triangle) pairs wants many parked lanes; clutter atrium +2.4 % at 12: profiles/r06_lanes)
-            const uint32_t refillClosest = bounce >= optRefillDeepFromBounce ? (layoutClosest == kLayoutQuad ? optRefillMinDeepQuad : (denseWanted(uniformFlag) ? optRefillMinDeepDense : optRefillMinDeep)) : optRefillMin;
-            // (kInfinityCacheBytes: the scene's records + triangles against the 256-MB Infinity Cache, as the layout selector's own test)
-            const uint32_t leafVoteClosest = (!counting && !denseWanted(uniformFlag) && treeBytes <= (192ull << 20)) ? optLeafVoteClosest : 0u;
-            launchTimed(1, [&] {
-                if (layoutClosest == kLayoutScalar)
-                {
-                    if (counting)
-                        hipLaunchKernelGGL(traceClosestKernel(true), dim3(blocks), dim3(kBlock), 0, stream, scene, ps, qIn, countIn, counters.ptr);
-                    else
-                        hipLaunchKernelGGL(traceClosestKernel(false), dim3(blocks), dim3(kBlock), 0, stream, scene, ps, qIn, countIn, counters.ptr);
-                }
-#if defined(RF_EXP_LEGACY_LAYOUTS)
-                else if (layoutClosest == kLayoutPacket)
-                    hipLaunchKernelGGL(tracePacketKernel(false), persistentGrid, dim3(kBlock), 0, stream, scene, wide, sky, sunBasis, ps, qIn, countIn, counters.ptr, kTMax, 0u);
-#endif
-                else
-                    launchClosestWide(layoutClosest, counting, wide, WideArgs{ps, qIn, countIn, cursorClosest, counting ? optRefillMin : refillClosest, chunkNow, leafVoteClosest, kTMax, persistentGrid, counting ? 0u : optExtraLds, blocks},
-                                      uniformFlag | (bounce == 1 && constOrigin ? kFlagConstOrigin : 0u));
-            }, bounce - 1);
-            uint32_t* const missCount = missCounts + kLine * (bounce - 1);
-            // kShade's own-triangle test of the shadow rays (kShadeSelfShadow): wherever this bounce's any-hit launch is one that can work through a list of queue positions
-            // (the kTraceWide instantiations with the occluder-cache code: quad / half / local-grid records) and nothing has to be counted node by node
-            const int      layoutShadow = shadowLayoutFor(bounce);
-            // (bounce <= 64: kBounceTotals keeps one mask bit per bounce -- as for firstLook below; deeper bounces trace every shadow ray and count them in the launch: ADVICE r5)
-            const bool     selfShadow = optShadowSelfTest && selfShadowOk && !counting && bounce <= 64u && (layoutShadow == kLayoutQuad || layoutShadow == kLayoutQuadHalf || layoutShadow == kLayoutQuadLocal);
-            uint32_t* const shadowListCount = shadowListCounts + kLine * (bounce - 1);
-            if (selfShadow) selfMask |= 1ull << (bounce - 1);
-            launchTimed(2, [&] {
-                const uint32_t shadeFlags = (bounce == numBounces ? kShadeLastBounce : 0u) | (bounce == 1 ? kShadeFirstBounce : 0u) | (selfShadow ? kShadeSelfShadow : 0u);
-                const dim3     shadeGrid(optShadeBlocks ? std::min(itemBlocks, optShadeBlocks) : itemBlocks);
-                // (the first-hit AOVs are written by the unsorted bounce-1 kernel, whatever shade_sort_from_bounce says: the sort is a scheduling choice)
-                if (aovSums.on && bounce == 1)
-                    hipLaunchKernelGGL(shadeKernel(false, true), shadeGrid, dim3(kBlock), 0, stream, scene, sky, sunBasis, ps, qIn, countIn, qOut, countOut, missQueue.ptr, missSlots.ptr, missCount, shadowList.ptr, shadowListCount, shadeFlags, 0u, sAov.ptr);
-                else if (optShadeSortFromBounce != 0u && bounce >= optShadeSortFromBounce)
-                    hipLaunchKernelGGL(shadeKernel(true), shadeGrid, dim3(kBlock), 0, stream, scene, sky, sunBasis, ps, qIn, countIn, qOut, countOut, missQueue.ptr, missSlots.ptr, missCount, shadowList.ptr, shadowListCount, shadeFlags, sortScale, nullptr);
-                else
-                    hipLaunchKernelGGL(shadeKernel(false), shadeGrid, dim3(kBlock), 0, stream, scene, sky, sunBasis, ps, qIn, countIn, qOut, countOut, missQueue.ptr, missSlots.ptr, missCount, shadowList.ptr, shadowListCount, shadeFlags, 0u, nullptr);
-                // the paths that left the scene at this bounce, while its direction / throughput arrays are intact
-                // (its slot comes with the miss list: kSky reads nothing of the bounce's queue -- round 5: reading the slot through the queue position was a third
-                // dependent gather, and kShade + kSky went from 19.7 to 15.8 ms per 64 spp without it)
-                hipLaunchKernelGGL(skyKernel(optTranscendentalsF32), dim3(std::min(blocks, skyBlocks)), dim3(kBlock), 0, stream, sky, ps, missSlots.ptr, missQueue.ptr, missCount, bounce == 1 ? 1u : 0u);
-            });
-            // occluder cache (kTraceWide, kFlagOccluderCache): the conservative-record any-hit launches of bounces 1..optOccluderCacheBounces; their rays are
-            // short (a third of the steps), so the deep launches refill earlier
-            const bool     cachedShadow = layoutShadow != kLayoutScalar && layoutShadow != kLayoutPacket && cachedShadowFor(bounce);
-            // ... behind kShadowFirstLook (see there) from the second batch on: the first batch of a renderer fills the grid (the traversal kernel's own first look serves)
-            const bool      firstLook = cachedShadow && occluderHintLevels == 0u && optShadowFirstLookFromBounce != 0u && bounce >= optShadowFirstLookFromBounce && bounce <= 64u && occluderGridWarm && firstLookHoldOff == 0u;
-            uint32_t* const listCount = listCounts + kLine * (bounce - 1);
-            uint32_t* const countShadow = firstLook ? listCount : (selfShadow ? shadowListCount : countOut);
-            if (firstLook) lookMask |= 1ull << (bounce - 1);
-            const uint32_t shadowFlags = (bounce == 1 ? kFlagFirstBounce : 0u) | uniformFlag | (cachedShadow ? kFlagOccluderCache : 0u) | (firstLook ? (kFlagOccluderNoTry | kFlagNoRayCount) : 0u) | (selfShadow ? kFlagNoRayCount : 0u);
-            launchTimed(3, [&] {
-                WideScene wide = this->wide; // (the launches below name `wide`)
-                if (firstLook)
-                {
-                    // (the bounce's input queue is free by now -- kShade and kSky have consumed it -- and holds the list)
-                    const dim3 lookGrid(optShadeBlocks ? std::min(itemBlocks, optShadeBlocks) : itemBlocks);
-                    hipLaunchKernelGGL(shadowFirstLookKernel(), lookGrid, dim3(kBlock), 0, stream, scene, wide, sky, sunBasis, ps, qOut, selfShadow ? shadowList.ptr : nullptr,
-                                       selfShadow ? shadowListCount : countOut, qIn, listCount, counters.ptr, kTMax, (bounce == 1 ? kLookFirstBounce : 0u) | (selfShadow ? kLookNoRayCount : 0u));
-                    wide.rayList = qIn;
-                }
-                else if (selfShadow) wide.rayList = shadowList.ptr; // (positions only: bit 31 clear, the traversal kernel takes its own first look)
-                if (layoutShadow == kLayoutScalar)
-                {
-                    if (counting)
-                        hipLaunchKernelGGL(traceShadowKernel(true), dim3(blocks), dim3(kBlock), 0, stream, scene, sky, sunBasis, ps, qOut, countOut, counters.ptr, bounce == 1 ? 1u : 0u);
-                    else
-                        hipLaunchKernelGGL(traceShadowKernel(false), dim3(blocks), dim3(kBlock), 0, stream, scene, sky, sunBasis, ps, qOut, countOut, counters.ptr, bounce == 1 ? 1u : 0u);
-                }
-#if defined(RF_EXP_LEGACY_LAYOUTS)
-                else if (layoutShadow == kLayoutPacket)
-                    hipLaunchKernelGGL(tracePacketKernel(true), persistentGrid, dim3(kBlock), 0, stream, scene, wide, sky, sunBasis, ps, qOut, countOut, counters.ptr, kTMax,
-                                       shadowFlags & kFlagFirstBounce);
-#endif
-                else
-                {
-                    // the conservative layouts (VALU bound) visit a record's entries in record order unless asked otherwise; the exact and binary records nearest-first
-                    const bool conservative = layoutShadow == kLayoutQuadLocal || layoutShadow == kLayoutQuadHalf;
-                    const bool nearest = shadowNearestFirst && !(conservative && optShadowSignOrder);
-                    launchShadowWide(layoutShadow, nearest, counting, wide, WideArgs{ps, qOut, countShadow, cursorShadow, optRefillMin, chunkNow, 0u, kTMax, persistentGrid, counting ? 0u : optExtraLds, blocks}, shadowFlags);
-                }
-            }, bounce - 1);
-            std::swap(qIn, qOut);
-            std::swap(ps.rayD, ps.rayDOut);
-            std::swap(ps.thr, ps.thrOut);
-            std::swap(ps.noise, ps.noiseOut);
+            const BouncePlan plan = planBounce(io.bounce, batch);
+            if (plan.selfShadow) selfMask |= 1ull << (io.bounce - 1);
+            if (plan.firstLook) lookMask |= 1ull << (io.bounce - 1);
+            launchTimed(1, [&] { enqueueClosest(plan.closest, io); }, io.bounce - 1);
+            launchTimed(2, [&] { enqueueShadeAndSky(plan, io); });
+            launchTimed(3, [&] { enqueueShadow(plan, io); }, io.bounce - 1);
+            std::swap(io.in, io.out);
+            std::swap(io.ps.rayD, io.ps.rayDOut);
+            std::swap(io.ps.thr, io.ps.thrOut);
+            std::swap(io.ps.noise, io.ps.noiseOut);
         }
-        hipLaunchKernelGGL(bounceTotalsKernel(), dim3(1), dim3(64), 0, stream, queueCounts.ptr, std::min(numBounces, 64u), bounceTotals.ptr, listCounts, lookMask, lookBatch.ptr, shadowListCounts, selfMask, counters.ptr);
+        hipLaunchKernelGGL(bounceTotalsKernel(), dim3(1), dim3(64), 0, stream, words.base, std::min(numBounces, 64u), bounceTotals.ptr, words.listCount(1), lookMask, lookBatch.ptr, words.shadowListCount(1), selfMask, counters.ptr);
         if (lookMask != 0ull && lookBatchHost != nullptr)
         {
             RF_HIP(hipMemcpyAsync(lookBatchHost, lookBatch.ptr, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
@@ -1042,37 +1189,7 @@ struct Renderer::Impl
             lookPending = true;
         }
         if (wide.occGrid != nullptr) occluderGridWarm = true;
-        // The sums in sample order.  Where the slot order is pixel-major and the step long enough, the LDS-staged "runs" kernels (a 64-lane workgroup per
-        // `pixelsPerGroup` pixels); else one thread per pixel
-        const bool runs = fp.slotGroupShift == 0u && numSamples > 4u && optAccumulateRuns;
-        const auto sumGrid = [&](uint32_t pixelsPerGroup) {
-            const uint32_t perGroup = runs ? pixelsPerGroup : static_cast<uint32_t>(kBlock);
-            return dim3((fp.pixelsPadded + perGroup - 1) / perGroup);
-        };
-        const dim3 sumBlock(runs ? 64u : static_cast<uint32_t>(kBlock));
-        launchTimed(4, [&] {
-            if (active)
-            {
-                // (whole frame: compact slot == tile id, so the listed tiles' sums sit at tile id * 1024 of the image and the moments)
-                hipLaunchKernelGGL(accumulateTilesKernel(runs), sumGrid(kMomentPixels), sumBlock, 0, stream, fp, tileIds.ptr, static_cast<const float4*>(ps.rad), image, moments());
-                return;
-            }
-            if (runs && numSamples <= kAccMaxSamples)
-            {
-                // (pixels per workgroup by the LDS their runs take: <= ~8 KB per workgroup keeps twenty of them resident per CU)
-                const uint32_t accPixels = numSamples > 640u ? 1u : (numSamples > 160u ? 2u : kAccPixels);
-                hipLaunchKernelGGL(accumulateRunsKernel(accPixels), dim3((fp.pixelsPadded + accPixels - 1) / accPixels), dim3(64), accPixels * 3u * (numSamples + 1u) * sizeof(float), stream, fp,
-                                   tileIds.ptr, ps, image);
-            }
-            else
-                hipLaunchKernelGGL(accumulateKernel(), dim3((fp.pixelsPadded + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, fp, tileIds.ptr, ps, image);
-            // the first-hit AOV sums, in the same sample order (timed with the accumulation: rf_stats has no entry of its own for them)
-            if (aovSums.on && numBounces != 0u) // (no bounce, no primary hit: the records were not written)
-                hipLaunchKernelGGL(accumulateAovKernel(runs), sumGrid(kAovPixels), sumBlock, 0, stream, fp, tileIds.ptr, sAov.ptr, aovAlbedoCoverage(), aovNormalDepth());
-            // the radiance second moments, over the same stream in the same sample order (timed with the accumulation as well)
-            if (momentSums.on)
-                hipLaunchKernelGGL(accumulateMomentsKernel(runs), sumGrid(kMomentPixels), sumBlock, 0, stream, fp, tileIds.ptr, static_cast<const float4*>(ps.rad), moments());
-        });
+        launchTimed(4, [&] { enqueueSums(batch, fp, io.ps); });
         RF_HIP(hipGetLastError());
         RF_HIP(hipEventRecord(bt.stop, stream));
         pendingBatches.push_back(bt);
@@ -1714,13 +1831,14 @@ void Renderer::clearAccumulationIfStale()
 
 void Renderer::layoutInfo(uint32_t (&layouts)[48], uint32_t (&misc)[4], float& quadHalfAreaRatio, uint64_t& treeBytes) const
 {
-    const Impl& m = *mImpl;
+    const Impl&           m = *mImpl;
+    const Impl::BatchPlan batch = m.planBatch(1u, nullptr);
     for (uint32_t b = 1; b <= 16; ++b)
     {
-        const int ls = m.shadowLayoutFor(b);
-        layouts[b - 1] = static_cast<uint32_t>(m.closestLayoutFor(b));
-        layouts[16 + b - 1] = static_cast<uint32_t>(ls);
-        layouts[32 + b - 1] = (ls != kLayoutScalar && ls != kLayoutPacket && m.cachedShadowFor(b)) ? 1u : 0u;
+        const Impl::BouncePlan p = m.planBounce(b, batch);
+        layouts[b - 1] = static_cast<uint32_t>(p.closest.layout);
+        layouts[16 + b - 1] = static_cast<uint32_t>(p.shadow.layout);
+        layouts[32 + b - 1] = p.cached ? 1u : 0u;
     }
     misc[0] = m.occluderHintLevels, misc[1] = m.optShadowFirstLookFromBounce, misc[2] = m.optDenseLeafMin;
 #if defined(RF_EXP_LEGACY_LAYOUTS)
@@ -1730,6 +1848,38 @@ void Renderer::layoutInfo(uint32_t (&layouts)[48], uint32_t (&misc)[4], float& q
 #endif
     quadHalfAreaRatio = m.quadHalfAreaRatio;
     treeBytes = m.treeBytes;
+}
+
+void Renderer::launchPlan(uint32_t bounce, uint32_t numSamples, rf_launch_plan& out) const
+{
+    const Impl& m = *mImpl;
+    if (bounce == 0u || bounce > m.params.samplingParams.numBounces || numSamples == 0u) throw std::invalid_argument("launch plan: bounce must be 1 .. the bounce count, num_samples >= 1");
+    (void)hipSetDevice(m.device);
+    Impl::BatchPlan batch = m.planBatch(numSamples, nullptr);
+    batch.firstLookReady = m.nextBatchFirstLookReady(batch);
+    const Impl::BouncePlan    p = m.planBounce(bounce, batch);
+    const Impl::BatchCounters words{nullptr, batch.numBounces};
+    static_assert(sizeof(rf_launch_plan) == 52 * sizeof(uint32_t) && offsetof(rf_launch_plan, closest_extra_lds) - offsetof(rf_launch_plan, closest_kernel) == 9 * sizeof(uint32_t) &&
+                  offsetof(rf_launch_plan, shadow_extra_lds) - offsetof(rf_launch_plan, shadow_kernel) == 9 * sizeof(uint32_t));
+    out = rf_launch_plan{};
+    out.num_samples = batch.numSamples, out.num_bounces = batch.numBounces;
+    out.sample_perm = batch.samplePerm, out.dense_raygen = batch.denseRaygen, out.const_origin = batch.constOrigin, out.primary_layout = static_cast<uint32_t>(batch.primaryLayout);
+    out.occluder_grid = batch.occluderGrid, out.occluder_mask = batch.occMask;
+    std::memcpy(&out.occluder_scale_bits, &batch.occScale, sizeof(uint32_t));
+    out.runs = batch.runs, out.tile_list = batch.tileList, out.accumulate_kernel = batch.accumulateKernel, out.accumulate_pixels = batch.accumulatePixels;
+    out.aov_pixels = batch.aovPixels, out.moment_pixels = batch.momentPixels, out.raygen_count_word = words.queueWord(0);
+    const auto traversal = [](const Impl::TraversalPlan& t, uint32_t* w) { // the ten words of a traversal launch, in the struct's order
+        const uint32_t v[10] = {t.kernel, static_cast<uint32_t>(t.layout), t.count, t.nearest, t.dense, t.refillMin, t.chunk, t.leafVote, t.flags, t.extraLds};
+        std::memcpy(w, v, sizeof v);
+    };
+    traversal(p.closest, &out.closest_kernel);
+    out.closest_count_word = words.queueWord(bounce - 1), out.closest_cursor_word = p.closest.kernel == Impl::kKernelWide ? words.cursorClosestWord(bounce) : 0u;
+    out.shade_sorted = p.shadeSorted, out.shade_aov = p.shadeAov, out.shade_flags = p.shadeFlags, out.shade_sort_scale = p.sortScale, out.shade_grid_cap = p.itemGridCap;
+    traversal(p.shadow, &out.shadow_kernel);
+    out.shadow_count_word = words.shadowCountWord(bounce, p.shadowSource);
+    out.shadow_cursor_word = p.shadow.kernel == Impl::kKernelWide ? words.cursorShadowWord(bounce) : 0u;
+    out.shadow_cached = p.cached, out.shadow_first_look = p.firstLook, out.shadow_self = p.selfShadow, out.shadow_source = p.shadowSource, out.look_flags = p.lookFlags;
+    if (p.firstLook) out.look_count_word = words.shadowCountWord(bounce, p.selfShadow ? Impl::kFromShadeList : Impl::kFromQueue), out.look_list_word = words.listWord(bounce);
 }
 
 void Renderer::memoryInfo(uint64_t& pathStateBytes, uint64_t& pathsAllocated, uint64_t& maxPathsPerBatch, uint64_t& sceneBytes) const

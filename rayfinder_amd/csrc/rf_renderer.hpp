@@ -23,6 +23,8 @@
 #include <string>
 #include <vector>
 
+struct rf_launch_plan; // include/rayfinder_amd.h
+
 namespace rf
 {
 struct SamplingParams
@@ -257,6 +259,9 @@ public:
     // rf_renderer_layout_info: layouts[0..15] = closest-hit, [16..31] = any-hit, [32..47] = any-hit launch starts at the occluder cache; misc = {hint levels, first look from bounce,
     // dense leaf min, legacy build}
     void     layoutInfo(uint32_t (&layouts)[48], uint32_t (&misc)[4], float& quadHalfAreaRatio, uint64_t& treeBytes) const;
+    // rf_renderer_launch_plan: what the launches of bounce 1..numBounces of the handle's NEXT batch of numSamples samples would be, in its present state (the same
+    // plans traceBatch enqueues from; nothing is enqueued).  std::invalid_argument for a bounce outside 1..numBounces or no sample.
+    void     launchPlan(uint32_t bounce, uint32_t numSamples, ::rf_launch_plan& out) const;
     void     memoryInfo(uint64_t& pathStateBytes, uint64_t& pathsAllocated, uint64_t& maxPathsPerBatch, uint64_t& sceneBytes) const;
     uint64_t accumulationBytes() const;
     void     bindAccumulationBuffer(void* devicePtr, uint64_t bytes);
