@@ -179,16 +179,24 @@ RF_API int rf_renderer_read_tonemapped(rf_renderer* r, uint32_t* dst_bgra8);
  * radiance (wgsl:47-57): bit-reproducible whatever the batching, slot order or number of ranks.  Means are the caller's to form: albedo and normal
  * divided by the AOV sample count, depth divided by coverage (where coverage > 0).
  *
- * rf_renderer_set_aovs: flags 0 (the default: nothing is allocated or launched, image / stats / timings exactly as without) or RF_AOV_FIRST_HIT.
+ * rf_renderer_set_aovs: flags 0 (the default: nothing is allocated or launched, image / stats / timings exactly as without), RF_AOV_FIRST_HIT, or
+ * RF_AOV_FIRST_HIT | RF_AOV_TILE_COUNTS.  The low byte of the flags says WHICH AOVs are kept, the bits from 8 up HOW they are kept.  RF_AOV_TILE_COUNTS: the sums
+ * follow the per-tile sample counts of rf_renderer_render_adaptive (below: after that call the AOV sums of a pixel are those of its tile's first tile_samples[t]
+ * samples, as S and Q are), and rf_renderer_denoise then runs in the non-uniform state.  Until rf_renderer_render_adaptive is called, a handle with the bit behaves
+ * bit for bit like one with RF_AOV_FIRST_HIT alone: sums, image, stats and launches are the same.  The bit on its own is refused.
  * While on, 32 more bytes per path slot of device memory (rf_renderer_memory_info counts them; a batch that no longer fits gets shallower).
  * The AOV sums keep their own sample count -- the samples traced while the AOVs were on -- and are cleared, with the count set to 0, when the image is
- * (a change through rf_renderer_set_render_parameters, a new tile shard, a newly bound accumulation buffer) and when the flags change.  Turned on
- * partway through an accumulation, they cover only the later samples: the count stays below the accumulated sample count.
+ * (a change through rf_renderer_set_render_parameters, a new tile shard, a newly bound accumulation buffer) and when the flags value changes in any way
+ * (RF_AOV_FIRST_HIT <-> RF_AOV_FIRST_HIT | RF_AOV_TILE_COUNTS included).  Turned on partway through an accumulation, they cover only the later samples: the
+ * count stays below the accumulated sample count.
  * rf_renderer_read_aovs: row-major width*height*4 floats each, {albedo.rgb, coverage} and {normal.xyz, depth} sums (the layout of
  * rf_renderer_read_accumulation; either pointer may be NULL) and the AOV sample count.  With a tile shard set, this rank's pixels and zeros elsewhere:
- * the sum of the ranks' reads is the whole frame.  (rf_renderer_gather_frame does not carry the AOVs.)
- * A NULL handle or unknown flag bits: RF_ERROR_INVALID_ARGUMENT. */
+ * the sum of the ranks' reads is the whole frame.  (rf_renderer_gather_frame does not carry the AOVs.)  In the non-uniform state of
+ * rf_renderer_render_adaptive: the sums as they are; the count reported is the leading count L, and the divisor of a pixel is its tile's own count
+ * (rf_renderer_read_tile_samples), as for rf_renderer_read_accumulation and rf_renderer_read_moments.
+ * A NULL handle, unknown flag bits or RF_AOV_TILE_COUNTS without RF_AOV_FIRST_HIT: RF_ERROR_INVALID_ARGUMENT, the state kept. */
 #define RF_AOV_FIRST_HIT 1u
+#define RF_AOV_TILE_COUNTS 0x100u
 RF_API int rf_renderer_set_aovs(rf_renderer* r, uint32_t flags);
 RF_API int rf_renderer_read_aovs(rf_renderer* r, float* albedo_coverage, float* normal_depth, uint32_t* aov_sample_count);
 
@@ -211,18 +219,29 @@ RF_API int rf_renderer_read_aovs(rf_renderer* r, float* albedo_coverage, float* 
  *     in tap order: sumW += w; sumE += w e_q (per channel, both from +0);  e'_p = sumE / sumW;  ℓ'_p = (e'.r + e'.g) + e'.b
  *   finish: out = e^(L) (a + εa) per channel; background out = c;  L = 0: out = c for every pixel.  The mean is returned as {out.rgb, 1}.
  * Parameters: 0 <= iterations <= 8, each sigma finite and > 0; defaults L = 5, σc = 1, σn = 0.1, σz = 0.1 (profiles/denoise/README.md: the sweep).
+ * With one sample count per 32x32 tile (a frame of rf_renderer_render_adaptive; rf_denoise_tiles) the definition changes in exactly one place: in prep, Nf of
+ * pixel p is float(tile_samples[tile of p]), tile = (y >> 5) ceil(width / 32) + (x >> 5), for c, a and m alike (z = ND.w / AC.w does not involve N).  Everything
+ * after prep is as written: the taps cross tile borders freely -- a tile stopped at 4 samples filters against its 32-sample neighbour -- and no term weighs a tap
+ * by its count or its variance.  With all counts equal to N the result is bit for bit that of the one-count filter.
  *
  * rf_renderer_denoise: enqueued on the handle's stream over its own sums; params NULL = the defaults.  RF_ERROR_INVALID_ARGUMENT when the AOVs are off,
  * when the AOV sample count differs from the accumulated count (AOVs turned on partway through), when no sample has been accumulated, or when a tile
- * shard is set (rf_renderer_gather_frame does not carry the AOVs; use rf_denoise_images on the gathered sums).  Leaves the accumulation, the AOV sums,
- * rf_renderer_read_tonemapped, the stats and later samples untouched.  The result is a snapshot with its sample count: its device buffers (five float4
+ * shard is set (rf_renderer_gather_frame does not carry the AOVs; use rf_denoise_images on the gathered sums).  In the non-uniform state of
+ * rf_renderer_render_adaptive it runs, with each tile's own count in prep, when the AOVs are on with RF_AOV_TILE_COUNTS and their count equals the accumulated
+ * (leading) count L -- the snapshot's sample count is then L, and the call is not purely an enqueue: it first waits for the handle's stream and copies the
+ * per-tile counts to the device (8 KB at 1080p), as the other per-tile reads do; otherwise it is refused with the non-uniform state's message ("different
+ * sample counts"), which comes before the checks above.  Leaves the accumulation, the AOV sums, the tile counts, rf_renderer_read_tonemapped, the stats and
+ * later samples untouched.  The result is a snapshot with its sample count: its device buffers (five float4
  * and one u32 per pixel) are allocated by the first call and freed with the handle; the snapshot is dropped whenever the AOV sums are cleared
  * (rf_renderer_set_render_parameters, a change of the AOV flags, a new tile shard, a newly bound accumulation buffer).
  * rf_renderer_read_denoised: row-major width*height*4 mean floats and / or the BGRA8 texels (kTonemap with accumulatedSamples = 1 and the handle's
  * exposure) and the snapshot's sample count; any pointer may be NULL.  RF_ERROR_INVALID_ARGUMENT without a snapshot.
  * rf_denoise_images: the same filter over row-major host sums (width*height*4 floats each, e.g. assembled from several ranks) on device
  * device_ordinal; out_rgba / out_bgra8 may be NULL.  Synchronous.  A NULL input, a zero size or sample count and bad parameters are refused before any
- * device call. */
+ * device call.
+ * rf_denoise_tiles: rf_denoise_images with one count per 32x32 tile: tile_samples holds ceil(width / 32) * ceil(height / 32) words in the estimate's tile numbering
+ * (tile_y * ceil(width / 32) + tile_x), exactly as for rf_noise_estimate_tiles.  Synchronous.  A NULL input, a zero size, any tile count of 0 and bad parameters
+ * are refused before any device call. */
 typedef struct rf_denoise_parameters
 {
     uint32_t iterations;
@@ -233,6 +252,9 @@ RF_API int rf_renderer_denoise(rf_renderer* r, const rf_denoise_parameters* para
 RF_API int rf_renderer_read_denoised(rf_renderer* r, float* rgba, uint32_t* bgra8, uint32_t* sample_count);
 RF_API int rf_denoise_images(int32_t device_ordinal, uint32_t width, uint32_t height, uint32_t samples, const float* color_sum4, const float* albedo_coverage4,
                              const float* normal_depth4, const rf_denoise_parameters* params, float exposure, float* out_rgba, uint32_t* out_bgra8);
+RF_API int rf_denoise_tiles(int32_t device_ordinal, uint32_t width, uint32_t height, const uint32_t* tile_samples, const float* color_sum4,
+                            const float* albedo_coverage4, const float* normal_depth4, const rf_denoise_parameters* params, float exposure, float* out_rgba,
+                            uint32_t* out_bgra8);
 
 /* Radiance second moments and the noise estimate: how noisy the accumulation still is, per pixel, per 32x32 tile and for the frame, and a render call that stops
  * at a noise target.  No reference counterpart (the reference counts samples: renderProgressPercentage).
@@ -288,7 +310,8 @@ RF_API int rf_renderer_render_until(rf_renderer* r, float target_mean_error, uin
                                     rf_noise_estimate* last);
 
 /* Tile-adaptive sampling: a render call that keeps sampling only the 32x32 tiles that are still noisy, and the per-tile sample count that the reads then honour.
- * No reference counterpart.  Whole frame only (no tile shard); needs the moments on from the first sample and the AOVs off.
+ * No reference counterpart.  Whole frame only (no tile shard); needs the moments on from the first sample and the AOVs off, or on with RF_AOV_TILE_COUNTS
+ * (from the first sample as well).
  *
  * The handle keeps one more word per tile, tile_samples[t], t in the estimate's tile numbering (tile_y * ceil(width / 32) + tile_x).  rf_renderer_render(n) adds n to
  * every tile (min(n, samples left), as it does to the accumulated count); the counts are cleared, to 0, whenever the image is.  L, the LEADING count, is the
@@ -305,19 +328,27 @@ RF_API int rf_renderer_render_until(rf_renderer* r, float target_mean_error, uin
  * All active tiles share one count at all times, and a stopped tile is never sampled again.  The defining property: afterwards, S and Q of every pixel of tile t are bit
  * for bit what rf_renderer_render(tile_samples[t]) leaves there in a fresh accumulation (with the moments on) -- each pixel's sums are its first tile_samples[t] samples
  * in sample order -- whatever the batching, the slot order or the options.  rf_stats' primary_rays counts the pixel-samples traced.
+ * With RF_AOV_FIRST_HIT | RF_AOV_TILE_COUNTS the same holds for the AOV sums: AC = {albedo.rgb, coverage} and ND = {normal.xyz, depth} of every pixel of tile t are
+ * bit for bit what rf_renderer_render(tile_samples[t]) leaves there in a fresh accumulation with the AOVs on; the AOV sample count advances with L, as the moment
+ * count does; and S, Q, the schedule (which tile stops when) and *result are exactly what they are with the AOVs off.
  * A later call, with the same or other parameters, continues with the tiles still at the leading count only (stopped tiles are not revived, the active set is not
  * dilated to neighbouring tiles, and counts are per tile, not per pixel).  Waits for the work it enqueues.
- * RF_ERROR_INVALID_ARGUMENT: the moments are off or do not cover the accumulation, the AOVs are on (their sums and rf_denoise_images keep ONE sample count), a tile
+ * RF_ERROR_INVALID_ARGUMENT: the moments are off or do not cover the accumulation, the AOVs are on without RF_AOV_TILE_COUNTS (their sums then keep ONE sample
+ * count) or with it but do not cover the accumulation (turned on partway through), a tile
  * shard is set (rf_renderer_gather_frame carries no counts), check_every is 0, or target_tile_error is negative or not finite.
  * *result (may be NULL): estimate_passes made by this call; tiles and stopped_tiles (tiles below L) of the frame; the minimum and maximum tile count; pixel_samples =
  * the sum over the tiles of in-frame pixels x tile_samples[t]; last = the estimate of the call's last pass, over the tiles that were active in it (mean_error, max_error,
  * pixels and nonfinite_pixels over those tiles, worst_tile in the frame's numbering, samples = L at that pass; samples = 0 when the call made no pass).
  *
- * While some tile is below L (the NON-UNIFORM state), rf_renderer_render, rf_renderer_render_until, rf_renderer_denoise, rf_renderer_set_tile_shard and
- * rf_renderer_gather_frame return RF_ERROR_INVALID_ARGUMENT with a message that says so: each of them assumes one count for the frame.
- * rf_renderer_set_render_parameters (with a change) and a newly bound accumulation buffer clear the counts with the image.  When every tile is at L -- a target of 0 ran
- * every tile to the cap, a huge target stopped every tile at the first check -- the handle is in the ordinary state and none of them refuses.  In the non-uniform state:
- *   rf_renderer_read_accumulation, rf_renderer_read_moments: the sums as they are; the count they report is L, and the divisor of a pixel is its tile's own count.
+ * While some tile is below L (the NON-UNIFORM state), rf_renderer_render, rf_renderer_render_until, rf_renderer_set_tile_shard and rf_renderer_gather_frame
+ * return RF_ERROR_INVALID_ARGUMENT with a message that says so: each of them assumes one count for the frame.  So does rf_renderer_denoise, unless the AOVs are on
+ * with RF_AOV_TILE_COUNTS and cover the accumulation: it then filters with each tile's own count (the denoiser's block above).
+ * rf_renderer_set_render_parameters (with a change) and a newly bound accumulation buffer clear the counts with the image.  When every tile is at L -- every tile
+ * ran to the cap, a huge target stopped every tile at the first check -- the handle is in the ordinary state and none of them refuses.  (A target of 0 runs a tile to
+ * the cap only while its mean error is > 0: a tile in which no pixel has shown any variance so far -- black, constant or non-finite pixels have e = 0 -- is <= 0
+ * and stops at the first check, as step 4 says.  min_samples = cap puts the only check at the cap: no tile can stop.)  In the non-uniform state:
+ *   rf_renderer_read_accumulation, rf_renderer_read_moments, rf_renderer_read_aovs: the sums as they are; the count they report is L, and the divisor of a pixel is
+ *       its tile's own count.
  *   rf_renderer_read_tile_samples: the counts (tile_samples may be NULL) and ceil(width / 32) * ceil(height / 32).  Uniform state: every tile of the shard at the
  *       accumulated count, a tile outside the shard 0.
  *   rf_renderer_read_mean: row-major width*height*4 floats {S.rgb / float(tile_samples[t]), 1}, one f32 division per channel; {0, 0, 0, 1} in a tile without a sample.

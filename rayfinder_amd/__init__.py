@@ -453,6 +453,24 @@ def denoise_images(color_sum, albedo_coverage, normal_depth, samples, exposure=1
     return rgba[..., :3], bgra
 
 
+def denoise_tiles(color_sum, albedo_coverage, normal_depth, tile_samples, exposure=1.0, device_ordinal=0, **params):
+    """rf_denoise_tiles: denoise_images with one sample count (> 0) per 32x32 tile, tile_samples in tile order (tile_y * ceil(W / 32) + tile_x): every pixel's sums
+    are divided by its own tile's count.  -> (rgb (H,W,3) f32 denoised mean, bgra (H,W) u32 display texels under `exposure`)."""
+    color_sum, albedo_coverage, normal_depth = (_f32(a) for a in (color_sum, albedo_coverage, normal_depth))
+    h, w = color_sum.shape[:2]
+    for a in (color_sum, albedo_coverage, normal_depth):
+        if a.shape != (h, w, 4):
+            raise ValueError("denoise_tiles: the three sums must be (H, W, 4) arrays of one size")
+    counts = np.ascontiguousarray(tile_samples, np.uint32).reshape(-1)
+    if counts.size != _noise_tiles(w, h):
+        raise ValueError(f"denoise_tiles: {_noise_tiles(w, h)} tile counts expected, got {counts.size}")
+    rgba = np.zeros((h, w, 4), np.float32)
+    bgra = np.zeros((h, w), np.uint32)
+    check(lib.rf_denoise_tiles(device_ordinal, w, h, _ptr(counts), _ptr(color_sum), _ptr(albedo_coverage), _ptr(normal_depth), C.byref(_denoise_parameters(params)),
+                               exposure, _ptr(rgba), _ptr(bgra)))
+    return rgba[..., :3], bgra
+
+
 def _noise_result(est, error_map, tile_sum, tile_max):
     out = {k: getattr(est, k) for k, _ in est._fields_}
     out.update(error_map=error_map, tile_sum=tile_sum, tile_max=tile_max)
@@ -544,9 +562,11 @@ class ReferencePathTracer:
         return img
 
     # first-hit AOVs (rf_renderer_set_aovs / rf_renderer_read_aovs; include/rayfinder_amd.h states what they hold)
-    def set_aovs(self, enabled=True):
-        """Turn the first-hit AOVs (albedo, shading normal, depth) on or off; any change clears their sums."""
-        check(lib.rf_renderer_set_aovs(self._h, _ffi.RF_AOV_FIRST_HIT if enabled else 0))
+    def set_aovs(self, enabled=True, tile_counts=False):
+        """Turn the first-hit AOVs (albedo, shading normal, depth) on or off; any change clears their sums.  tile_counts (RF_AOV_TILE_COUNTS): the sums follow the
+        per-tile sample counts of render_adaptive, which then runs with the AOVs on, and denoise works on the frame it leaves; until render_adaptive is called,
+        nothing differs.  Changing it clears the sums too; it is refused without `enabled`."""
+        check(lib.rf_renderer_set_aovs(self._h, (_ffi.RF_AOV_FIRST_HIT if enabled else 0) | (_ffi.RF_AOV_TILE_COUNTS if tile_counts else 0)))
 
     def read_aovs(self):
         """-> dict of per-pixel SUMS in sample order: albedo (H,W,3), normal (H,W,3), depth (H,W), coverage (H,W), and samples (the AOV sample count)."""
@@ -558,17 +578,23 @@ class ReferencePathTracer:
 
     def aov_means(self):
         """-> dict albedo (H,W,3) and normal (H,W,3) divided by the sample count, depth (H,W) divided by the coverage (0 where nothing was hit), coverage (H,W) as a
-        fraction, and samples.  All zeros before the first AOV sample."""
+        fraction, and samples.  All zeros before the first AOV sample.  After render_adaptive (the tiles hold different counts) every pixel is divided by its own
+        tile's count; samples is the leading count."""
         s = self.read_aovs()
-        n = np.float32(max(s["samples"], 1))
         cov = s["coverage"]
         depth = np.divide(s["depth"], cov, out=np.zeros_like(cov), where=cov > 0)
+        if s["samples"] and not self.tile_samples_uniform():
+            n = np.repeat(np.repeat(np.maximum(self.read_tile_samples(), 1), TILE, 0), TILE, 1)[:cov.shape[0], :cov.shape[1]].astype(np.float32)
+            return dict(albedo=s["albedo"] / n[..., None], normal=s["normal"] / n[..., None], depth=depth, coverage=cov / n, samples=s["samples"])
+        n = np.float32(max(s["samples"], 1))
         return dict(albedo=s["albedo"] / n, normal=s["normal"] / n, depth=depth, coverage=cov / n, samples=s["samples"])
 
     # edge-aware a-trous denoiser (rf_renderer_denoise / rf_renderer_read_denoised; include/rayfinder_amd.h states its arithmetic)
     def denoise(self, **params):
-        """Denoise the accumulation with the first-hit AOVs as guides (needs the AOVs on from the first sample, no tile shard).  Keyword arguments:
-        iterations, sigma_color, sigma_normal, sigma_depth (the rest: the defaults)."""
+        """Denoise the accumulation with the first-hit AOVs as guides (needs the AOVs on from the first sample, no tile shard).  After render_adaptive, while the
+        tiles hold different counts, it needs set_aovs(True, tile_counts=True) from the first sample: every pixel is then divided by its own tile's count before
+        the filter, and the snapshot's sample count is the leading count.  Keyword arguments: iterations, sigma_color, sigma_normal, sigma_depth (the rest: the
+        defaults)."""
         check(lib.rf_renderer_denoise(self._h, C.byref(_denoise_parameters(params))))
 
     def read_denoised(self):
@@ -613,7 +639,8 @@ class ReferencePathTracer:
     # tile-adaptive sampling (include/rayfinder_amd.h states the loop and what the reads return while the tiles hold different counts)
     def render_adaptive(self, target_tile_error, check_every=8, min_samples=0, max_samples=0):
         """Keep sampling only the 32x32 tiles whose mean error is above target_tile_error, checking every check_every samples from min_samples on, up to max_samples
-        (0: the frame's samples per pixel).  Needs the moments on from the first sample, the AOVs off and no tile shard.
+        (0: the frame's samples per pixel).  Needs the moments on from the first sample, no tile shard, and the AOVs off or on with tile_counts=True from the first
+        sample (their sums then hold, per tile, the tile's own first samples, as the image does).
         -> dict(estimate_passes, tiles, stopped_tiles, min_tile_samples, max_tile_samples, pixel_samples, last: the last pass's estimate scalars or None)."""
         p = _ffi.AdaptiveParameters(target_tile_error, check_every, min_samples, max_samples)
         res = _ffi.AdaptiveResult()
@@ -630,6 +657,11 @@ class ReferencePathTracer:
         check(lib.rf_renderer_read_tile_samples(self._h, _ptr(counts), C.byref(n)))
         assert n.value == counts.size
         return counts
+
+    def tile_samples_uniform(self):
+        """-> False while the tiles of this handle's shard hold different sample counts (after render_adaptive stopped some of them)"""
+        counts = self.read_tile_samples()
+        return np.unique(counts[counts > 0]).size <= 1                      # (0: a tile of another rank's shard)
 
     def read_mean(self):
         """-> (H, W, 4) f32 {sum.rgb / the tile's sample count, 1}"""

@@ -37,6 +37,7 @@ RF_ERROR_RUNTIME = 2
 RF_ERROR_NO_DEVICE = 3
 RF_ERROR_OUT_OF_RANGE = 4
 RF_AOV_FIRST_HIT = 1
+RF_AOV_TILE_COUNTS = 0x100
 
 
 class DenoiseParameters(C.Structure):
@@ -140,6 +141,7 @@ SIGNATURES = {
     "rf_renderer_read_denoised": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
     "rf_denoise_images": (C.c_int, [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
                                     C.c_void_p]),
+    "rf_denoise_tiles": (C.c_int, [C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
     "rf_renderer_set_moments": (C.c_int, [C.c_void_p, C.c_int]),
     "rf_renderer_read_moments": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
     "rf_renderer_noise_estimate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -17,7 +17,9 @@
 // (rf_renderer_set_moments, on from the first sample).  With --gpus N > 1 each rank reads its own tiles' moments, the host assembles them, and the estimate runs once,
 // on device 0, over the gathered accumulation (rf_noise_estimate_images): the same map whatever N.
 // --adaptive T [--adaptive-min n] [--adaptive-every n]: tile-adaptive sampling (rf_renderer_render_adaptive): every 32x32 tile is sampled until its mean error is <= T,
-// checked every n samples (default 8) from --adaptive-min samples on, --spp at the latest; the image is the per-tile mean.  --gpus 1, no AOVs / denoiser.
+// checked every n samples (default 8) from --adaptive-min samples on, --spp at the latest; the image is the per-tile mean.  --gpus 1 only, and not with --noise-target.
+// With --aov-* / --denoise* the AOVs are kept per tile count (RF_AOV_FIRST_HIT | RF_AOV_TILE_COUNTS): the AOV PFMs are divided by each pixel's tile count, and the
+// denoiser (rf_renderer_denoise) divides every pixel by its own tile's count before it filters.
 // --sample-map s.pfm: the sample count of every pixel's tile (a one-channel PFM)
 // --noise-target t [--noise-check-every k]: stop as soon as the frame's mean error is <= t, checked every k samples (default 8), at --spp at the latest
 // (rf_renderer_render_until).  One GPU only: stopping several ranks in step is not implemented.
@@ -43,7 +45,8 @@ int main(int argc, char** argv)
                     "  --denoise / --denoise-pfm: the frame through the edge-aware a-trous denoiser guided by the AOVs (defaults: L 5, sigmas 1, 0.1, 0.1)\n"
                     "                 [--adaptive T] [--adaptive-min n] [--adaptive-every n] [--sample-map s.pfm]\n"
                     "  --adaptive: sample every 32x32 tile until its mean error is <= T (checked every n samples, default 8; --spp at the latest); --sample-map: the\n"
-                    "  tiles' sample counts (1-channel PFM)\n"
+                    "  tiles' sample counts (1-channel PFM).  --gpus 1 only, not with --noise-target; with --aov-* / --denoise* the AOVs and the denoiser use each\n"
+                    "  tile's own sample count\n"
                     "                 [--noise-map m.pfm] [--noise-target t] [--noise-check-every k]\n"
                     "  --noise-map: the per-pixel relative standard error of the frame (1-channel PFM); --noise-target: stop once the frame's mean error is <= t,\n"
                     "  checked every k samples (default 8), at --spp at the latest (one GPU only)\n");
@@ -108,9 +111,9 @@ int main(int argc, char** argv)
         std::fprintf(stderr, "--noise-target needs --gpus 1: stopping several ranks in step at a noise target is not implemented (render a fixed --spp and use --noise-map)\n");
         return 1;
     }
-    if (adaptive && (gpus > 1 || noiseTargetSet || denoising || !aovAlbedo.empty() || !aovNormal.empty() || !aovDepth.empty()))
+    if (adaptive && (gpus > 1 || noiseTargetSet))
     {
-        std::fprintf(stderr, "--adaptive needs --gpus 1 and goes with neither --noise-target nor the AOVs / the denoiser (they keep one sample count for the frame)\n");
+        std::fprintf(stderr, "--adaptive needs --gpus 1 and does not go with --noise-target (the per-tile counts are carried neither by the frame gather nor by render_until)\n");
         return 1;
     }
     rf_pt_format*     pt = loadScene(argv[1]);
@@ -169,7 +172,8 @@ int main(int argc, char** argv)
             rfCheck(rf_renderer_set_tile_shard(renderer, rank, gpus), "tile shard");
             rfCheck(rf_comm_create(commId, rank, gpus, d.device_ordinal, &comm), "RCCL communicator");
         }
-        if (aovs) rfCheck(rf_renderer_set_aovs(renderer, RF_AOV_FIRST_HIT), "AOVs");
+        // (--adaptive: the AOV sums follow the per-tile counts)
+        if (aovs) rfCheck(rf_renderer_set_aovs(renderer, RF_AOV_FIRST_HIT | (adaptive ? RF_AOV_TILE_COUNTS : 0u)), "AOVs");
         if (noise) rfCheck(rf_renderer_set_moments(renderer, 1), "moments");
         const auto t0 = std::chrono::steady_clock::now();
         if (adaptive) rfCheck(rf_renderer_render_adaptive(renderer, &adaptiveParams, &adaptiveResult), "adaptive render");
@@ -232,7 +236,7 @@ int main(int argc, char** argv)
                 rfCheck(rf_renderer_read_tonemapped(renderer, bgra.data()), "tonemap");
                 uint32_t n = 0;
                 if (!acc.empty()) rfCheck(adaptive ? rf_renderer_read_mean(renderer, acc.data()) : rf_renderer_read_accumulation(renderer, acc.data(), &n), "read accumulation");
-                if (!sampleMap.empty())
+                if (!sampleMap.empty() || (adaptive && aovs))
                 {
                     uint32_t numTiles = 0;
                     rfCheck(rf_renderer_read_tile_samples(renderer, nullptr, &numTiles), "tile samples");
@@ -318,9 +322,12 @@ int main(int argc, char** argv)
     if (!write(sampleMap, 1, [&](size_t i, uint32_t) { return static_cast<float>(tileSamples[((i / 4) / W / 32) * ((W + 31) / 32) + ((i / 4) % W) / 32]); })) return 1;
     if (aovs)
     {
-        // means (f32 divisions, as ReferencePathTracer.aov_means): albedo / normal over the AOV samples, depth over the coverage
-        const float n = static_cast<float>(std::max(aovSamples, 1u));
-        const bool ok = write(aovAlbedo, 3, [&](size_t i, uint32_t c) { return aovAc[i + c] / n; }) && write(aovNormal, 3, [&](size_t i, uint32_t c) { return aovNd[i + c] / n; }) &&
+        // means (f32 divisions, as ReferencePathTracer.aov_means): albedo / normal over the AOV samples -- with --adaptive the pixel's tile's own count --, depth over the coverage
+        const auto n = [&](size_t i) {
+            const uint32_t count = adaptive ? tileSamples[((i / 4) / W / 32) * ((W + 31) / 32) + ((i / 4) % W) / 32] : aovSamples;
+            return static_cast<float>(std::max(count, 1u));
+        };
+        const bool ok = write(aovAlbedo, 3, [&](size_t i, uint32_t c) { return aovAc[i + c] / n(i); }) && write(aovNormal, 3, [&](size_t i, uint32_t c) { return aovNd[i + c] / n(i); }) &&
                         write(aovDepth, 1, [&](size_t i, uint32_t) { return aovAc[i + 3] > 0.0f ? aovNd[i + 3] / aovAc[i + 3] : 0.0f; });
         if (!ok) return 1;
     }

@@ -21,6 +21,7 @@
 
 static_assert(sizeof(rf_camera) == sizeof(rf::Camera));
 static_assert(RF_AOV_FIRST_HIT == rf::Renderer::kAovFirstHit);
+static_assert(RF_AOV_TILE_COUNTS == rf::Renderer::kAovTileCounts);
 
 struct rf_renderer
 {
@@ -257,8 +258,10 @@ int rf_renderer_read_deferred(rf_renderer* r, float* sample_rgb, float* accumula
 int rf_renderer_set_aovs(rf_renderer* r, uint32_t flags)
 {
     return guarded([&] {
+        // (the flags first: a bad value is refused whatever the handle is, and is never confused with a bad handle)
+        require((flags & ~(RF_AOV_FIRST_HIT | RF_AOV_TILE_COUNTS)) == 0u, "unknown AOV flag bits");
+        require((flags & RF_AOV_TILE_COUNTS) == 0u || (flags & RF_AOV_FIRST_HIT) != 0u, "RF_AOV_TILE_COUNTS says how the AOVs are kept: valid only together with RF_AOV_FIRST_HIT");
         require(r, "null argument");
-        require((flags & ~RF_AOV_FIRST_HIT) == 0u, "unknown AOV flag bits");
         r->impl->setAovs(flags);
         return RF_OK;
     });
@@ -313,6 +316,27 @@ int rf_denoise_images(int32_t device_ordinal, uint32_t width, uint32_t height, u
         require(samples > 0, "sample count must be > 0");
         require(std::isfinite(exposure), "exposure must be finite");
         rf::denoiseImages(device_ordinal, width, height, samples, color_sum4, albedo_coverage4, normal_depth4, p, exposure, out_rgba, out_bgra8);
+        return RF_OK;
+    });
+}
+
+int rf_denoise_tiles(int32_t device_ordinal, uint32_t width, uint32_t height, const uint32_t* tile_samples, const float* color_sum4, const float* albedo_coverage4,
+                     const float* normal_depth4, const rf_denoise_parameters* params, float exposure, float* out_rgba, uint32_t* out_bgra8)
+{
+    return guarded([&] {
+        const rf::DenoiseParameters p = toDenoiseParams(params);
+        require(tile_samples && color_sum4 && albedo_coverage4 && normal_depth4, "null argument");
+        require(width > 0 && height > 0, "image size must be non-zero");
+        require(static_cast<uint64_t>(width) * height < (1ull << 31), "image too large");
+        const uint32_t tiles = ((width + 31u) / 32u) * ((height + 31u) / 32u);
+        uint32_t       leading = 0;
+        for (uint32_t t = 0; t < tiles; ++t)
+        {
+            require(tile_samples[t] > 0, "the sample count of every tile must be > 0");
+            leading = tile_samples[t] > leading ? tile_samples[t] : leading;
+        }
+        require(std::isfinite(exposure), "exposure must be finite");
+        rf::denoiseTiles(device_ordinal, width, height, tile_samples, leading, color_sum4, albedo_coverage4, normal_depth4, p, exposure, out_rgba, out_bgra8);
         return RF_OK;
     });
 }

@@ -3,6 +3,7 @@
 // rounded divide and sqrt, no denormal flushing): tests/denoise_restatement.py reproduces it bit for bit.  No atomics: every output is one lane's
 // fixed sequence of operations.
 //   kDenoisePrep    one lane per pixel: demodulated irradiance {e, ℓ}, guide {n, z}, a + εa (or, for L = 0, the mean itself)
+//   kDenoisePrepTiles  the same with the sample count of the pixel's 32x32 tile (a frame of rf_renderer_render_adaptive, rf_denoise_tiles)
 //   kDenoiseAtrous  one lane per pixel, 16x16-pixel workgroups of four 8x8-pixel waves (the 25 taps of a wave touch few cache lines); the last pass
 //                   remodulates and writes the mean
 // The display image is the existing kTonemap over the mean with accumulatedSamples = 1.
@@ -33,12 +34,10 @@ __device__ __forceinline__ float tukey(float x)
     return x < 1.0f ? m * m : 0.0f; // (NaN: 0)
 }
 
-__global__ __launch_bounds__(256) void kDenoisePrep(const float4* colorSum, const float4* albedoCoverage, const float4* normalDepth, uint32_t width, uint32_t height,
-                                                    uint32_t tilesX, float nf, float4* e, float4* guide, float4* albedo, float4* meanOut)
+// prep of pixel i = (x, y) with its sample count as a float: shared by kDenoisePrep (one count for the frame) and kDenoisePrepTiles (the count of the pixel's tile)
+__device__ __forceinline__ void prepPixel(const float4* colorSum, const float4* albedoCoverage, const float4* normalDepth, uint32_t i, uint32_t x, uint32_t y, uint32_t tilesX,
+                                          float nf, float4* e, float4* guide, float4* albedo, float4* meanOut)
 {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= width * height) return;
-    const uint32_t y = i / width, x = i - y * width;
     const uint32_t src = tilesX ? tileMajorIndex(x, y, tilesX) : i;
     const float4   S = colorSum[src];
     const Vec3     c = vec3(S.x / nf, S.y / nf, S.z / nf); // (kTonemap's division)
@@ -65,6 +64,28 @@ __global__ __launch_bounds__(256) void kDenoisePrep(const float4* colorSum, cons
     e[i] = make_float4(ev.x, ev.y, ev.z, (ev.x + ev.y) + ev.z);
     guide[i] = make_float4(n.x, n.y, n.z, z);
     albedo[i] = make_float4(ae.x, ae.y, ae.z, 0.0f);
+}
+
+__global__ __launch_bounds__(256) void kDenoisePrep(const float4* colorSum, const float4* albedoCoverage, const float4* normalDepth, uint32_t width, uint32_t height,
+                                                    uint32_t tilesX, float nf, float4* e, float4* guide, float4* albedo, float4* meanOut)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= width * height) return;
+    const uint32_t y = i / width, x = i - y * width;
+    prepPixel(colorSum, albedoCoverage, normalDepth, i, x, y, tilesX, nf, e, guide, albedo, meanOut);
+}
+
+// The same with one sample count per 32x32 tile of the frame: Nf = float(tileSamples[tile of the pixel]), tile = tile_y * frameTilesX + tile_x (the estimate's
+// numbering).  frameTilesX is the frame's tiles per row whatever the layout of the sums (tilesX is 0 for row-major sums); every count is > 0.
+__global__ __launch_bounds__(256) void kDenoisePrepTiles(const float4* colorSum, const float4* albedoCoverage, const float4* normalDepth, uint32_t width, uint32_t height,
+                                                         uint32_t tilesX, const uint32_t* tileSamples, uint32_t frameTilesX, float4* e, float4* guide, float4* albedo,
+                                                         float4* meanOut)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= width * height) return;
+    const uint32_t y = i / width, x = i - y * width;
+    const float    nf = static_cast<float>(tileSamples[(y >> 5) * frameTilesX + (x >> 5)]);
+    prepPixel(colorSum, albedoCoverage, normalDepth, i, x, y, tilesX, nf, e, guide, albedo, meanOut);
 }
 
 // One pass of step `step` = 2^i: sc2 = (σc σc) 2^-i, szs = σz step.  last: out = the mean {e' (a + εa), 1} (background: {c, 1}); else out = {e', ℓ'}.
@@ -146,19 +167,24 @@ void DenoiseWork::reserve(uint64_t n, hipStream_t stream)
 }
 
 void enqueueDenoise(hipStream_t stream, DenoiseWork& w, const float4* colorSum, const float4* albedoCoverage, const float4* normalDepth, uint32_t width,
-                    uint32_t height, uint32_t tilesX, uint32_t samples, const DenoiseParameters& p, float exposure)
+                    uint32_t height, uint32_t tilesX, uint32_t samples, const DenoiseParameters& p, float exposure, const uint32_t* tileSamples)
 {
     const uint32_t n = width * height;
     w.reserve(n, stream);
     const float nf = static_cast<float>(samples);
     const dim3  prepGrid((n + 255) / 256);
-    if (p.iterations == 0)
-        hipLaunchKernelGGL(kDenoisePrep, prepGrid, dim3(256), 0, stream, colorSum, albedoCoverage, normalDepth, width, height, tilesX, nf, static_cast<float4*>(nullptr),
-                           static_cast<float4*>(nullptr), static_cast<float4*>(nullptr), w.out.ptr);
+    // prep into (e, guide, albedo), or for L = 0 into the mean: with the frame's one count, or with each pixel's tile's own
+    const auto prep = [&](float4* e, float4* guide, float4* albedo, float4* meanOut) {
+        if (tileSamples)
+            hipLaunchKernelGGL(kDenoisePrepTiles, prepGrid, dim3(256), 0, stream, colorSum, albedoCoverage, normalDepth, width, height, tilesX, tileSamples,
+                               TileGrid(width, height).tilesX, e, guide, albedo, meanOut);
+        else
+            hipLaunchKernelGGL(kDenoisePrep, prepGrid, dim3(256), 0, stream, colorSum, albedoCoverage, normalDepth, width, height, tilesX, nf, e, guide, albedo, meanOut);
+    };
+    if (p.iterations == 0) prep(nullptr, nullptr, nullptr, w.out.ptr);
     else
     {
-        hipLaunchKernelGGL(kDenoisePrep, prepGrid, dim3(256), 0, stream, colorSum, albedoCoverage, normalDepth, width, height, tilesX, nf, w.e[0].ptr, w.guide.ptr, w.albedo.ptr,
-                           static_cast<float4*>(nullptr));
+        prep(w.e[0].ptr, w.guide.ptr, w.albedo.ptr, nullptr);
         const dim3 grid((width + 15) / 16, (height + 15) / 16);
         for (uint32_t i = 0; i < p.iterations; ++i)
         {
@@ -176,20 +202,33 @@ void enqueueDenoise(hipStream_t stream, DenoiseWork& w, const float4* colorSum, 
 void denoiseImages(int deviceOrdinal, uint32_t width, uint32_t height, uint32_t samples, const float* colorSum, const float* albedoCoverage, const float* normalDepth,
                    const DenoiseParameters& params, float exposure, float* outRgba, uint32_t* outBgra8)
 {
+    denoiseTiles(deviceOrdinal, width, height, nullptr, samples, colorSum, albedoCoverage, normalDepth, params, exposure, outRgba, outBgra8);
+}
+
+void denoiseTiles(int deviceOrdinal, uint32_t width, uint32_t height, const uint32_t* tileSamples, uint32_t samples, const float* colorSum, const float* albedoCoverage,
+                  const float* normalDepth, const DenoiseParameters& params, float exposure, float* outRgba, uint32_t* outBgra8)
+{
     requireDevice(deviceOrdinal);
     const uint64_t n = static_cast<uint64_t>(width) * height;
+    const uint32_t tiles = TileGrid(width, height).count();
     // (leaving the scope: the stream is synchronised, the buffers are freed, the stream is destroyed -- ScopedStream)
-    ScopedStream         stream;
-    DeviceBuffer<float4> in[3];
-    DenoiseWork          work;
-    ScopedStream::Drain  drain{stream};
+    ScopedStream           stream;
+    DeviceBuffer<float4>   in[3];
+    DeviceBuffer<uint32_t> counts;
+    DenoiseWork            work;
+    ScopedStream::Drain    drain{stream};
+    if (tileSamples)
+    {
+        counts.alloc(tiles);
+        RF_HIP(hipMemcpyAsync(counts.ptr, tileSamples, tiles * sizeof(uint32_t), hipMemcpyHostToDevice, stream.handle));
+    }
     const float*         src[3] = {colorSum, albedoCoverage, normalDepth};
     for (int b = 0; b < 3; ++b)
     {
         in[b].alloc(n);
         RF_HIP(hipMemcpyAsync(in[b].ptr, src[b], n * sizeof(float4), hipMemcpyHostToDevice, stream.handle));
     }
-    enqueueDenoise(stream.handle, work, in[0].ptr, in[1].ptr, in[2].ptr, width, height, 0u, samples, params, exposure);
+    enqueueDenoise(stream.handle, work, in[0].ptr, in[1].ptr, in[2].ptr, width, height, 0u, samples, params, exposure, counts.ptr);
     if (outRgba) RF_HIP(hipMemcpyAsync(outRgba, work.out.ptr, n * sizeof(float4), hipMemcpyDeviceToHost, stream.handle));
     if (outBgra8) RF_HIP(hipMemcpyAsync(outBgra8, work.bgra.ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream.handle));
     RF_HIP(hipStreamSynchronize(stream.handle));

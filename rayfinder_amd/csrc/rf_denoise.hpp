@@ -25,6 +25,8 @@ struct DenoiseWork
 
 // Enqueue kDenoisePrep, the L kDenoiseAtrous passes and kTonemap on `stream`.  tilesX != 0: the sums are compact tile-major buffers holding every tile of the
 // frame in tile order (a handle without a tile shard), tilesX tiles per row; 0: row-major.  width * height < 2^31; the parameters are valid.
+// tileSamples (device, one count > 0 per tile of the frame's 32 x 32 grid, tile_y * ceil(width / 32) + tile_x) != nullptr: prep divides each pixel by its tile's
+// count (kDenoisePrepTiles) and `samples` is not used; the buffer must stay as it is until the stream has run the prep.
 void enqueueDenoise(hipStream_t stream, DenoiseWork& work, const float4* colorSum, const float4* albedoCoverage, const float4* normalDepth, uint32_t width,
-                    uint32_t height, uint32_t tilesX, uint32_t samples, const DenoiseParameters& params, float exposure);
+                    uint32_t height, uint32_t tilesX, uint32_t samples, const DenoiseParameters& params, float exposure, const uint32_t* tileSamples = nullptr);
 } // namespace rf

@@ -18,6 +18,9 @@ AccumulateMomentsKernel accumulateMomentsKernel(bool runs); // runs: the LDS-sta
 // over rad, for the fp.numTiles tiles that tileIds lists: at = tileIds[lp >> 10] * 1024 + (lp & 1023), the place of the tile in the whole frame's compact buffers
 using AccumulateTilesKernel = void (*)(FrameParams fp, const uint32_t* tileIds, const float4* rad, float4* image, float4* moments);
 AccumulateTilesKernel accumulateTilesKernel(bool runs); // runs: the LDS-staged kernel for the pixel-major slot order (kMomentPixels pixels per 64-lane workgroup)
+// The first-hit AOV sums of such a batch (the AOVs on with RF_AOV_TILE_COUNTS): kAccumulateAov's sums from the batch's records aov[2 slot, 2 slot + 1], added at the
+// same places `at` of the frame's two AOV sum buffers.  runs: kAovPixels pixels per 64-lane workgroup
+AccumulateAovKernel accumulateTilesAovKernel(bool runs);
 // mean[i] = {S.rgb / float(count), 1} over n compact tile-major pixels; count = tileSamples[i >> 10], or `samples` for all when tileSamples is nullptr; count 0: rgb 0
 using TileMeanKernel = void (*)(const float4* image, const uint32_t* tileSamples, uint32_t samples, uint32_t n, float4* mean);
 TileMeanKernel tileMeanKernel();

@@ -191,6 +191,8 @@ struct Renderer::Impl
     SumChannel              imageSums{true, 0};
     // first-hit AOVs (rf_renderer_set_aovs; off by default: nothing is allocated or launched then)
     SumChannel              aovSums{false, 2};
+    uint32_t                aovFlags = 0; // the flags as set (rf_renderer_set_aovs): kAovFirstHit says which AOVs are kept (aovSums.on), kAovTileCounts how
+    bool                    aovTileCounts() const { return (aovFlags & kAovTileCounts) != 0u; }
     // radiance second moments (rf_renderer_set_moments; off by default: nothing is allocated or launched then): {sum r r per channel, 0}
     SumChannel              momentSums{false, 1};
     float4*                 aovAlbedoCoverage() const { return aovSums.buffers[0].ptr; }
@@ -209,11 +211,11 @@ struct Renderer::Impl
     DeviceBuffer<float4>    meanImage;         // rf_renderer_read_mean / the non-uniform rf_renderer_read_tonemapped: compact tile-major, allocated by the first read
 
     bool nonUniform() const { return !tileSamples.empty(); }
-    void requireUniform(const char* what) const
+    void requireUniform(const char* what, const char* unless = "") const
     {
         if (nonUniform())
-            throw std::invalid_argument(std::string(what) + ": the tiles hold different sample counts after rf_renderer_render_adaptive (continue with render_adaptive, or restart the "
-                                                            "accumulation with rf_renderer_set_render_parameters)");
+            throw std::invalid_argument(std::string(what) + ": the tiles hold different sample counts after rf_renderer_render_adaptive" + unless +
+                                        " (continue with render_adaptive, or restart the accumulation with rf_renderer_set_render_parameters)");
     }
 
     uint64_t                validPixels = 0;     // pixels of this rank's tiles that lie inside the frame
@@ -752,8 +754,9 @@ struct Renderer::Impl
             b.accumulateKernel = kAccumulateRuns, b.accumulatePixels = numSamples > 640u ? 1u : (numSamples > 160u ? 2u : kAccPixels);
         }
         else b.accumulateKernel = kAccumulatePixels, b.accumulatePixels = perThread;
-        // the first-hit AOV sums (no bounce, no primary hit: the records were not written) and the radiance second moments: launches of their own unless the tile-list kernel runs
-        b.aovPixels = (!b.tileList && aovSums.on && b.numBounces != 0u) ? (b.runs ? kAovPixels : perThread) : 0u;
+        // the first-hit AOV sums (no bounce, no primary hit: the records were not written): a launch of their own, under a tile list the tile-list AOV kernel; the
+        // radiance second moments: a launch of their own unless the tile-list kernel adds them with the image
+        b.aovPixels = (aovSums.on && b.numBounces != 0u) ? (b.runs ? kAovPixels : perThread) : 0u;
         b.momentPixels = (!b.tileList && momentSums.on) ? (b.runs ? kMomentPixels : perThread) : 0u;
         return b;
     }
@@ -1059,7 +1062,7 @@ struct Renderer::Impl
             launchWide(t, wide, WideArgs{io.ps, io.out, io.words.shadowCount(io.bounce, p.shadowSource), io.words.cursorShadow(io.bounce), kTMax, io.persistentGrid, io.blocks});
     }
     // the batch's sums in sample order: the image, then the first-hit AOV sums and the radiance second moments (timed with the accumulation: rf_stats has no entry of
-    // their own for them) -- or the tile-list kernel for the image and the moments at once
+    // their own for them) -- or the tile-list kernels: one for the image and the moments at once, one for the AOV sums
     void enqueueSums(const BatchPlan& b, const FrameParams& fp, const PathStreams& ps)
     {
         const auto sumGrid = [&](uint32_t pixelsPerGroup) { return dim3((fp.pixelsPadded + pixelsPerGroup - 1) / pixelsPerGroup); };
@@ -1068,6 +1071,10 @@ struct Renderer::Impl
         {
             // (whole frame: compact slot == tile id, so the listed tiles' sums sit at tile id * 1024 of the image and the moments)
             hipLaunchKernelGGL(accumulateTilesKernel(b.runs), sumGrid(b.accumulatePixels), sumBlock, 0, stream, fp, tileIds.ptr, static_cast<const float4*>(ps.rad), image, moments());
+            // (the AOVs on with kAovTileCounts: the batch's records, added at the same places of the frame's two AOV sum buffers)
+            if (b.aovPixels != 0u)
+                hipLaunchKernelGGL(accumulateTilesAovKernel(b.runs), sumGrid(b.aovPixels), sumBlock, 0, stream, fp, tileIds.ptr, static_cast<const float4*>(sAov.ptr), aovAlbedoCoverage(),
+                                   aovNormalDepth());
             return;
         }
         if (b.accumulateKernel == kAccumulateRuns)
@@ -1589,10 +1596,12 @@ void Renderer::readAccumulation(float* dst)
 void Renderer::setAovs(uint32_t flags)
 {
     Impl& m = *mImpl;
-    if ((flags != 0u) == m.aovSums.on) return; // (kAovFirstHit is the only flag)
+    if (flags == m.aovFlags) return;
     RF_HIP(hipSetDevice(m.device));
     RF_HIP(hipStreamSynchronize(m.stream)); // (a batch in flight may still write the records or the sums)
-    m.aovSums.on = flags != 0u;
+    // any change of the value restarts the sums, kAovFirstHit <-> kAovFirstHit | kAovTileCounts included (the buffers stay: they are the same two either way)
+    m.aovFlags = flags;
+    m.aovSums.on = (flags & kAovFirstHit) != 0u;
     m.restartAovs();
     if (!m.aovSums.on)
     {
@@ -1602,7 +1611,7 @@ void Renderer::setAovs(uint32_t flags)
     }
 }
 
-uint32_t Renderer::aovFlags() const { return mImpl->aovSums.on ? kAovFirstHit : 0u; }
+uint32_t Renderer::aovFlags() const { return mImpl->aovFlags; }
 
 void Renderer::readAovs(float* albedoCoverage, float* normalDepth, uint32_t* sampleCount)
 {
@@ -1617,7 +1626,11 @@ void Renderer::readAovs(float* albedoCoverage, float* normalDepth, uint32_t* sam
 void Renderer::denoise(const DenoiseParameters& params)
 {
     Impl& m = *mImpl;
-    m.requireUniform("rf_renderer_denoise"); // (the filter divides by ONE sample count)
+    // the non-uniform state: prep divides each pixel by its tile's own count, which the AOV sums must have been kept for (kAovTileCounts, from the first sample on)
+    const bool perTile = m.nonUniform();
+    if (perTile && !(m.aovSums.on && m.aovTileCounts() && m.aovSums.covers(m.accumulated)))
+        m.requireUniform("rf_renderer_denoise", ", and the first-hit AOVs were not kept with per-tile counts for the whole accumulation: set RF_AOV_FIRST_HIT | RF_AOV_TILE_COUNTS "
+                                                "(rf_renderer_set_aovs) before the first sample and rf_renderer_denoise runs in this state");
     if (!m.aovSums.on) throw std::invalid_argument("denoise needs the first-hit AOVs: turn them on (rf_renderer_set_aovs) before the first sample");
     if (m.worldSize != 1u) throw std::invalid_argument("denoise needs the whole frame: a tile shard is set (use rf_denoise_images on the gathered sums)");
     if (m.accumulated == 0u) throw std::invalid_argument("denoise: no sample has been accumulated");
@@ -1625,8 +1638,9 @@ void Renderer::denoise(const DenoiseParameters& params)
         throw std::invalid_argument("denoise: the AOV sample count (" + std::to_string(m.aovSums.samples) + ") differs from the accumulated sample count (" +
                                     std::to_string(m.accumulated) + "): turn the AOVs on before the first sample");
     RF_HIP(hipSetDevice(m.device));
+    // (the snapshot's sample count is the leading count)
     enqueueDenoise(m.stream, m.denoiseWork, m.image, m.aovAlbedoCoverage(), m.aovNormalDepth(), m.params.width, m.params.height, m.grid().tilesX, m.accumulated, params,
-                   m.params.exposure);
+                   m.params.exposure, perTile ? m.uploadTileSamples() : nullptr);
     m.denoisedValid = true;
     m.denoisedSamples = m.accumulated;
 }
@@ -1694,12 +1708,16 @@ AdaptiveResult Renderer::renderAdaptive(const AdaptiveParameters& p)
 {
     Impl& m = *mImpl;
     if (!m.momentSums.on) throw std::invalid_argument("render_adaptive needs the radiance second moments: turn them on (rf_renderer_set_moments) before the first sample");
-    if (m.aovSums.on) throw std::invalid_argument("render_adaptive: the first-hit AOVs are on (their sums and the denoiser keep ONE sample count): turn them off first");
+    if (m.aovSums.on && !m.aovTileCounts())
+        throw std::invalid_argument("render_adaptive: the first-hit AOVs are on without RF_AOV_TILE_COUNTS (their sums and the denoiser then keep ONE sample count): set "
+                                    "RF_AOV_FIRST_HIT | RF_AOV_TILE_COUNTS before the first sample, or turn the AOVs off");
     if (m.worldSize != 1u) throw std::invalid_argument("render_adaptive needs the whole frame: a tile shard is set");
     if (p.checkEvery == 0u) throw std::invalid_argument("render_adaptive: check_every must be >= 1");
     if (!std::isfinite(p.targetTileError) || p.targetTileError < 0.0f) throw std::invalid_argument("render_adaptive: target_tile_error must be finite and >= 0");
     if (m.accumulated != 0u && !m.momentSums.covers(m.accumulated))
         throw std::invalid_argument("render_adaptive: the moments do not cover the accumulation (turned on partway through): restart the accumulation first");
+    if (m.aovSums.on && m.accumulated != 0u && !m.aovSums.covers(m.accumulated))
+        throw std::invalid_argument("render_adaptive: the AOV sample count does not cover the accumulation (the AOVs were turned on partway through): restart the accumulation first");
     RF_HIP(hipSetDevice(m.device));
     const uint32_t spp = m.params.samplingParams.numSamplesPerPixel;
     const uint32_t cap = p.maxSamples == 0u ? spp : std::min(p.maxSamples, spp);

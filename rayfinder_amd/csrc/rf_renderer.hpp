@@ -148,6 +148,10 @@ struct DenoiseParameters
 // `deviceOrdinal`: the mean RGBA (.w = 1) and / or its BGRA8 under `exposure` (NULL = skip).  Synchronous; allocates and frees its own device memory.
 void denoiseImages(int deviceOrdinal, uint32_t width, uint32_t height, uint32_t samples, const float* colorSum, const float* albedoCoverage, const float* normalDepth,
                    const DenoiseParameters& params, float exposure, float* outRgba, uint32_t* outBgra8);
+// The same with one sample count per tile of the 32 x 32 grid (tileSamples[t] > 0, tile t = tile_y * ceil(width / 32) + tile_x): prep's Nf = float(tileSamples[t]) for
+// the pixels of tile t.  tileSamples == nullptr: `samples` for every tile.
+void denoiseTiles(int deviceOrdinal, uint32_t width, uint32_t height, const uint32_t* tileSamples, uint32_t samples, const float* colorSum, const float* albedoCoverage,
+                  const float* normalDepth, const DenoiseParameters& params, float exposure, float* outRgba, uint32_t* outBgra8);
 
 // The noise estimate over the accumulation and the radiance second moments (rf_noise.hip; the definition: include/rayfinder_amd.h)
 struct NoiseEstimate
@@ -212,16 +216,20 @@ public:
     // Row-major width*height*4 floats (sum of samples, 16-B stride as the reference's
     // array<vec3f>); pixels outside this rank's tiles are zero.
     void readAccumulation(float* dst);
-    // First-hit AOVs (rf_renderer_set_aovs / rf_renderer_read_aovs): flags 0 = off (default), kAovFirstHit = on.  Any change of the flags clears the sums.
+    // First-hit AOVs (rf_renderer_set_aovs / rf_renderer_read_aovs): flags 0 = off (default), kAovFirstHit = on, kAovFirstHit | kAovTileCounts = on and kept per tile
+    // count under renderAdaptive (until that is called: exactly kAovFirstHit).  Any change of the flags value clears the sums.
     // Read: row-major width*height*4 floats each ({albedo.rgb, coverage} and {normal.xyz, depth} SUMS, this rank's pixels; NULL = skip) and the AOV sample count.
-    static constexpr uint32_t kAovFirstHit = 1u;
+    static constexpr uint32_t kAovFirstHit = 1u, kAovTileCounts = 0x100u;
     void     setAovs(uint32_t flags);
     uint32_t aovFlags() const;
     void     readAovs(float* albedoCoverage, float* normalDepth, uint32_t* sampleCount);
     // Edge-aware a-trous denoiser over the accumulation and the first-hit AOVs (rf_renderer_denoise; the arithmetic: include/rayfinder_amd.h).  denoise enqueues on the
     // handle's stream and keeps a snapshot (allocated on the first call); it throws std::invalid_argument when the AOVs are off, their count differs from the
-    // accumulated count, nothing is accumulated or a tile shard is set.  readDenoised: row-major width*height*4 mean floats and / or BGRA8 (NULL = skip) and the
-    // snapshot's sample count; std::invalid_argument without a snapshot (none yet, or cleared with the AOV sums).
+    // accumulated count, nothing is accumulated or a tile shard is set.  In the non-uniform state it runs when the AOVs carry kAovTileCounts and cover the accumulation
+    // (prep then divides each pixel by its tile's count; the snapshot's count is the leading count; the call first waits for the stream and copies the counts to the
+    // device, as the other per-tile reads do), and refuses as requireUniformTileSamples does otherwise.
+    // readDenoised: row-major width*height*4 mean floats and / or BGRA8 (NULL = skip) and the snapshot's sample count; std::invalid_argument without a snapshot
+    // (none yet, or cleared with the AOV sums).
     void denoise(const DenoiseParameters& params);
     void readDenoised(float* rgba, uint32_t* bgra8, uint32_t* sampleCount);
     // Radiance second moments (rf_renderer_set_moments / rf_renderer_read_moments): off by default.  While on, one more compact tile-major float4 buffer holds
@@ -238,9 +246,11 @@ public:
     // the whole accumulation), no tile shard and checkEvery >= 1.
     uint32_t renderUntil(float targetMeanError, uint32_t checkEvery, uint32_t maxFrames, NoiseEstimate* last);
     // Tile-adaptive sampling: keep sampling only the 32 x 32 tiles whose mean error is still above the target.  Afterwards the tiles may hold different sample counts
-    // (the non-uniform state): render, renderUntil, denoise, setTileShard and the frame gather then throw std::invalid_argument (requireUniformTileSamples), the
-    // reads report the leading count, and readTileSamples / readMean / readTonemapped / noiseEstimate honour the per-tile counts.  std::invalid_argument when the moments
-    // are off or do not cover the accumulation, the AOVs are on, a tile shard is set, checkEvery is 0 or the target is negative or not finite.
+    // (the non-uniform state): render, renderUntil, setTileShard and the frame gather then throw std::invalid_argument (requireUniformTileSamples), as does denoise
+    // unless the AOVs were kept with kAovTileCounts; the reads report the leading count, and readTileSamples / readMean / readTonemapped / noiseEstimate / denoise honour
+    // the per-tile counts.  With kAovFirstHit | kAovTileCounts the AOV sums of tile t are those of its first tileSamples[t] samples, as S and Q are.
+    // std::invalid_argument when the moments are off or do not cover the accumulation, the AOVs are on without kAovTileCounts or do not cover it, a tile shard is set,
+    // checkEvery is 0 or the target is negative or not finite.
     AdaptiveResult renderAdaptive(const AdaptiveParameters& params);
     bool           tileSamplesUniform() const;
     void           requireUniformTileSamples(const char* what) const;
