@@ -191,7 +191,8 @@ RF_API int rf_renderer_read_tonemapped(rf_renderer* r, uint32_t* dst_bgra8);
  * count stays below the accumulated sample count.
  * rf_renderer_read_aovs: row-major width*height*4 floats each, {albedo.rgb, coverage} and {normal.xyz, depth} sums (the layout of
  * rf_renderer_read_accumulation; either pointer may be NULL) and the AOV sample count.  With a tile shard set, this rank's pixels and zeros elsewhere:
- * the sum of the ranks' reads is the whole frame.  (rf_renderer_gather_frame does not carry the AOVs.)  In the non-uniform state of
+ * the sum of the ranks' reads is the whole frame.  (rf_renderer_gather_frame carries them with RF_GATHER_AOVS: the root then holds the whole frame's AC and ND
+ * sums in device memory, rf_comm_read_plane planes 1 and 2.)  In the non-uniform state of
  * rf_renderer_render_adaptive: the sums as they are; the count reported is the leading count L, and the divisor of a pixel is its tile's own count
  * (rf_renderer_read_tile_samples), as for rf_renderer_read_accumulation and rf_renderer_read_moments.
  * A NULL handle, unknown flag bits or RF_AOV_TILE_COUNTS without RF_AOV_FIRST_HIT: RF_ERROR_INVALID_ARGUMENT, the state kept. */
@@ -226,7 +227,8 @@ RF_API int rf_renderer_read_aovs(rf_renderer* r, float* albedo_coverage, float* 
  *
  * rf_renderer_denoise: enqueued on the handle's stream over its own sums; params NULL = the defaults.  RF_ERROR_INVALID_ARGUMENT when the AOVs are off,
  * when the AOV sample count differs from the accumulated count (AOVs turned on partway through), when no sample has been accumulated, or when a tile
- * shard is set (rf_renderer_gather_frame does not carry the AOVs; use rf_denoise_images on the gathered sums).  In the non-uniform state of
+ * shard is set (rf_renderer_gather_frame carries them with RF_GATHER_AOVS, and rf_comm_denoise then runs this filter on the root over the gathered sums, in
+ * device memory; rf_denoise_images does the same from host memory).  In the non-uniform state of
  * rf_renderer_render_adaptive it runs, with each tile's own count in prep, when the AOVs are on with RF_AOV_TILE_COUNTS and their count equals the accumulated
  * (leading) count L -- the snapshot's sample count is then L, and the call is not purely an enqueue: it first waits for the handle's stream and copies the
  * per-tile counts to the device (8 KB at 1080p), as the other per-tile reads do; otherwise it is refused with the non-uniform state's message ("different
@@ -267,7 +269,8 @@ RF_API int rf_denoise_tiles(int32_t device_ordinal, uint32_t width, uint32_t hei
  * count set to 0, when the image is (a change through rf_renderer_set_render_parameters, a new tile shard, a newly bound accumulation buffer) and when the switch
  * changes.  Turned on partway through an accumulation, they cover only the later samples: the count stays below the accumulated sample count.
  * rf_renderer_read_moments: row-major width*height*4 floats (the layout of rf_renderer_read_accumulation; may be NULL) and the moment sample count.  With a tile
- * shard set, this rank's pixels and zeros elsewhere: the sum of the ranks' reads is the whole frame.  (rf_renderer_gather_frame does not carry the moments.)
+ * shard set, this rank's pixels and zeros elsewhere: the sum of the ranks' reads is the whole frame.  (rf_renderer_gather_frame carries them with
+ * RF_GATHER_MOMENTS: the root then holds the whole frame's Q in device memory, rf_comm_read_plane plane 3.)
  *
  * The estimate.  Inputs: the per-pixel sums S (the accumulation) and Q of one accumulation and ONE sample count N >= 2 that both have.  All arithmetic is f32, one
  * IEEE operation at a time in the order written (+ - * /, sqrt, compares and selects): a numpy float32 restatement reproduces every output bit for bit.
@@ -284,8 +287,8 @@ RF_API int rf_denoise_tiles(int32_t device_ordinal, uint32_t width, uint32_t hei
  *
  * rf_renderer_noise_estimate: over the handle's own sums; enqueued on the handle's stream and then waited for.  error_map (row-major width*height floats), tile_sum
  * and tile_max (ceil(width / 32) * ceil(height / 32) floats each) may be NULL.  RF_ERROR_INVALID_ARGUMENT when the moments are off, when the moment sample count
- * differs from the accumulated count (moments turned on partway through), when fewer than 2 samples are accumulated, or when a tile shard is set (use
- * rf_noise_estimate_images on the sum of the ranks' reads).  Leaves the accumulation, the AOV sums, the denoise snapshot, the stats and later samples untouched; its
+ * differs from the accumulated count (moments turned on partway through), when fewer than 2 samples are accumulated, or when a tile shard is set (gather with
+ * RF_GATHER_MOMENTS and use rf_comm_noise_estimate on the root, or rf_noise_estimate_images on the sum of the ranks' reads).  Leaves the accumulation, the AOV sums, the denoise snapshot, the stats and later samples untouched; its
  * device buffers (a few words per tile, one float per pixel once a map was asked for) are allocated by the first call and freed with the moments.
  * rf_noise_estimate_images: the same kernel over row-major host sums (width*height*4 floats each, e.g. assembled from several ranks) on device device_ordinal.
  * Synchronous.  A NULL input or `out`, a zero size and samples < 2 are refused before any device call.
@@ -460,13 +463,47 @@ RF_API int rf_renderer_bind_accumulation_buffer(rf_renderer* r, void* device_ptr
  * a newly bound buffer) the accumulation buffer is ZEROED on the handle's stream first (wgsl:47-49: a restarted frame starts from
  * zero), and that includes a caller-owned buffer bound with rf_renderer_bind_accumulation_buffer (its first
  * rf_renderer_accumulation_device_buffer() bytes).  RF_GATHER_LOOPBACK: the root's own shard also
- * goes through ncclSend/ncclRecv instead of being read in place (self-test of the RCCL path at world size 1). */
+ * goes through ncclSend/ncclRecv instead of being read in place (self-test of the RCCL path at world size 1).
+ *
+ * PLANES.  The exchange can carry every per-pixel sum the handle keeps, in the same single group of sends and receives.  The sums are numbered in a fixed order:
+ * plane 0 = S (the image, always carried), 1 = AC = {albedo.rgb, coverage}, 2 = ND = {normal.xyz, depth} (both with RF_GATHER_AOVS), 3 = Q, the radiance second
+ * moments (RF_GATHER_MOMENTS).  A gather carries plane 0 and the planes its flags ask for, in that order: the plan is the one-plane plan once per carried plane
+ * (rf_gather_plan_planes) -- on the root, for each plane in order, the receives of that plane in rank order; on a sender, its sends in plane order; per (source,
+ * destination) pair the k-th send meets the k-th receive.  On the root every plane has its own staging area (rf_gather_layout; the areas lie one after another in one
+ * allocation) and its own row-major width*height float4 image, and ONE kernel un-tiles all carried planes.  With neither flag a gather enqueues exactly what it
+ * always did, and rf_comm_last_exchange_ms brackets the whole exchange, the un-tile included, either way.
+ * RF_GATHER_AOVS is refused with RF_ERROR_INVALID_ARGUMENT -- the state kept, nothing enqueued on this rank -- when the AOVs are off, when the AOV sample count
+ * differs from the accumulated count (AOVs turned on partway through) or when no sample has been accumulated; RF_GATHER_MOMENTS likewise for the moments.  (A rank
+ * whose shard holds no tile -- more ranks than tiles -- sends nothing, and only the switch is checked on it.)  The refusal of the non-uniform state of
+ * rf_renderer_render_adaptive comes first, with its own message: the gather carries no per-tile counts.  The ranks must run in step, as for the image: a rank that
+ * is refused leaves its peers waiting for it.
+ * The communicator records what the last gather left on the root: the carried planes, the frame size and the sample count N = the root handle's accumulated count
+ * (0 on a root whose shard holds no tile).  A later gather replaces all of it (a plain gather drops the extra planes) and drops the denoised snapshot.
+ *
+ * DEFINING PROPERTY.  After the same samples, the gathered planes 0 .. 3 are bit for bit what a handle WITHOUT a tile shard reads through
+ * rf_renderer_read_accumulation, rf_renderer_read_aovs (AC, ND) and rf_renderer_read_moments; rf_comm_read_denoised and rf_comm_noise_estimate are bit for bit that
+ * handle's rf_renderer_read_denoised (after rf_renderer_denoise with the same parameters) and rf_renderer_noise_estimate: the same filter and estimate definitions
+ * (above), over row-major instead of tile-major sums.
+ *
+ * The root-side calls below take the communicator and the ROOT's handle, whose stream, device and exposure they use.  Each returns RF_ERROR_INVALID_ARGUMENT, with a
+ * message that says which case applies, when this rank was not the root of the last gather, when no gather has been made, or when the last gather did not carry the
+ * planes the call needs (the AOVs for the denoiser, the moments for the estimate, the plane asked for).
+ * rf_comm_gathered_planes: RF_GATHER_AOVS / RF_GATHER_MOMENTS as carried by the last gather, its frame size and N; any pointer may be NULL.
+ * rf_comm_read_plane: waits for the handle's stream and copies plane 0 .. 3 to the host (width*height*4 floats, row-major).  rf_comm_plane_device: the plane's
+ * image in device memory (owned by the comm, valid until the next gather; work on it belongs on the handle's stream).
+ * rf_comm_denoise: the a-trous denoiser (the definition above, one count N) enqueued on the handle's stream over the gathered planes 0, 1, 2 where they lie: the
+ * sums never leave the device.  params NULL = the defaults; bad parameters are refused as everywhere else.  The snapshot is owned by the comm (its buffers are
+ * allocated by the first call) and is dropped by the next gather.  rf_comm_read_denoised: as rf_renderer_read_denoised; RF_ERROR_INVALID_ARGUMENT without a snapshot.
+ * rf_comm_noise_estimate: the noise estimate (the definition above) over the gathered planes 0 and 3; enqueued on the handle's stream, then waited for, as
+ * rf_renderer_noise_estimate.  Also refused when N < 2.  error_map, tile_sum and tile_max may be NULL. */
 /* MI355X devices this process sees (hipGetDeviceCount; 0 without a GPU).  No reference counterpart (the reference asks Dawn for one adapter,
  * gpu_context.cpp); what a host application sizes `--gpus N` against. */
 RF_API int rf_device_count(int32_t* count_out);
 typedef struct rf_comm rf_comm;
 #define RF_COMM_ID_BYTES 128
 #define RF_GATHER_LOOPBACK 1u
+#define RF_GATHER_AOVS    2u  /* with the image: AC = {albedo.rgb, coverage} and ND = {normal.xyz, depth} */
+#define RF_GATHER_MOMENTS 4u  /* with the image: Q */
 RF_API int  rf_comm_unique_id(uint8_t id_out[RF_COMM_ID_BYTES]);
 RF_API int  rf_comm_create(const uint8_t id[RF_COMM_ID_BYTES], uint32_t rank, uint32_t world_size, int32_t device_ordinal, rf_comm** out);
 RF_API void rf_comm_destroy(rf_comm* c);
@@ -477,6 +514,12 @@ RF_API int  rf_renderer_tonemap_device_image(rf_renderer* r, const void* image_d
 /* Root: wait for the exchange and copy the gathered image to the host (width*height*4 floats, row-major, the
  * layout of rf_renderer_read_accumulation). */
 RF_API int  rf_comm_read_frame(rf_comm* c, rf_renderer* r, float* dst);
+RF_API int  rf_comm_gathered_planes(const rf_comm* c, uint32_t* flags_out, uint32_t* width, uint32_t* height, uint32_t* samples);
+RF_API int  rf_comm_read_plane(rf_comm* c, rf_renderer* r, uint32_t plane /* 0..3 */, float* dst);   /* width*height*4 floats, row-major */
+RF_API int  rf_comm_plane_device(rf_comm* c, uint32_t plane, void** device_ptr);
+RF_API int  rf_comm_denoise(rf_comm* c, rf_renderer* r, const rf_denoise_parameters* params);          /* NULL = defaults */
+RF_API int  rf_comm_read_denoised(rf_comm* c, rf_renderer* r, float* rgba, uint32_t* bgra8, uint32_t* sample_count);
+RF_API int  rf_comm_noise_estimate(rf_comm* c, rf_renderer* r, rf_noise_estimate* out, float* error_map, float* tile_sum, float* tile_max);
 /* Max over ranks of *value (timing plumbing for hosts without another collective layer; also a barrier). */
 RF_API int  rf_comm_all_reduce_max(rf_comm* c, rf_renderer* r /* NULL: default stream */, double* value);
 /* What RCCL reports for the communicator (ncclCommCount / ncclCommUserRank / ncclCommCuDevice); any pointer may be NULL.
@@ -564,6 +607,15 @@ typedef struct rf_gather_op
     uint32_t is_send, peer, offset_tiles, count_tiles;
 } rf_gather_op;
 RF_API int rf_gather_plan(uint32_t width, uint32_t height, uint32_t world_size, uint32_t rank, uint32_t root, uint32_t flags, rf_gather_op* ops, uint32_t* num_ops);
+/* The same for a gather with RF_GATHER_AOVS / RF_GATHER_MOMENTS in `flags`: the one-plane list once per carried plane (plane 0 = S, 1 = AC, 2 = ND, 3 = Q), the
+ * receives of all planes first (plane after plane, each in rank order), then the sends in plane order.  offset_tiles counts from the start of THAT plane's own staging
+ * area (a receive) or compact buffer (a send).  With neither flag the list is rf_gather_plan's with plane = 0.  ops == NULL: count query. */
+typedef struct rf_gather_plane_op
+{
+    uint32_t is_send, peer, plane, offset_tiles, count_tiles;
+} rf_gather_plane_op;
+RF_API int rf_gather_plan_planes(uint32_t width, uint32_t height, uint32_t world_size, uint32_t rank, uint32_t root, uint32_t flags, rf_gather_plane_op* ops,
+                                 uint32_t* num_ops);
 /* The staging layout the gather uses: shards rank after rank, each rank's tiles in ascending tile id.
  * rank_first_tile[world_size + 1], tile_slot[tiles] (staging position of a tile, in tiles), tile_owner[tiles]. */
 RF_API int rf_gather_layout(uint32_t width, uint32_t height, uint32_t world_size, uint32_t* rank_first_tile, uint32_t* tile_slot, uint32_t* tile_owner);

@@ -339,6 +339,12 @@ def scene_from_arrays(nodes, positions48, attrs80, textures):
 
 # ------------------------------------------------------------------------------------- multi-GPU frame exchange
 RF_GATHER_LOOPBACK = 1
+RF_GATHER_AOVS = 2      # with the image: plane 1 = {albedo.rgb, coverage}, plane 2 = {normal.xyz, depth}
+RF_GATHER_MOMENTS = 4   # with the image: plane 3 = the radiance second moments
+
+
+def _gather_flags(loopback=False, aovs=False, moments=False):
+    return (RF_GATHER_LOOPBACK if loopback else 0) | (RF_GATHER_AOVS if aovs else 0) | (RF_GATHER_MOMENTS if moments else 0)
 
 
 def gather_layout(width, height, world_size):
@@ -357,6 +363,18 @@ def gather_plan(width, height, world_size, rank, root=0, loopback=False):
     check(lib.rf_gather_plan(width, height, world_size, rank, root, flags, None, C.byref(n)))
     ops = np.zeros((n.value, 4), np.uint32)
     check(lib.rf_gather_plan(width, height, world_size, rank, root, flags, _ptr(ops), C.byref(n)))
+    return ops
+
+
+def gather_plan_planes(width, height, world_size, rank, root=0, loopback=False, aovs=False, moments=False):
+    """gather_plan for a gather that also carries the AOV sums (planes 1, 2) and / or the second moments (plane 3) in the one group:
+    (n, 5) u32 rows {is_send, peer, plane, offset_tiles, count_tiles}; offsets count from the start of the plane's own staging area / compact buffer.
+    Host arithmetic, no GPU."""
+    n = C.c_uint32(0)
+    flags = _gather_flags(loopback, aovs, moments)
+    check(lib.rf_gather_plan_planes(width, height, world_size, rank, root, flags, None, C.byref(n)))
+    ops = np.zeros((n.value, 5), np.uint32)
+    check(lib.rf_gather_plan_planes(width, height, world_size, rank, root, flags, _ptr(ops), C.byref(n)))
     return ops
 
 
@@ -420,6 +438,47 @@ class TileComm:
         v = C.c_double(value)
         check(lib.rf_comm_all_reduce_max(self._h, renderer._h if renderer is not None else None, C.byref(v)))
         return v.value
+
+    # the root's side of a gather that carried more than the image (Renderer.gather_frame(..., aovs=True, moments=True)); every call is refused on another rank,
+    # before any gather, and when the last gather did not carry the planes it needs
+    def gathered_planes(self):
+        """What the last gather left on this (root) rank: dict(aovs, moments, width, height, samples)."""
+        f, w, h, n = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        check(lib.rf_comm_gathered_planes(self._h, C.byref(f), C.byref(w), C.byref(h), C.byref(n)))
+        return dict(aovs=bool(f.value & RF_GATHER_AOVS), moments=bool(f.value & RF_GATHER_MOMENTS), width=w.value, height=h.value, samples=n.value)
+
+    def read_plane(self, renderer, plane):
+        """Root: the gathered row-major (H, W, 4) f32 sums of plane 0 = S, 1 = {albedo, coverage}, 2 = {normal, depth}, 3 = the second moments."""
+        g = self.gathered_planes()
+        img = np.zeros((g["height"], g["width"], 4), np.float32)
+        check(lib.rf_comm_read_plane(self._h, renderer._h, plane, _ptr(img)))
+        return img
+
+    def denoise(self, renderer, params=None):
+        """Root: the a-trous denoiser over the gathered image and AOV sums, in device memory, on the renderer's stream.  params: a dict of iterations, sigma_color,
+        sigma_normal, sigma_depth (the rest, or None: the defaults)."""
+        check(lib.rf_comm_denoise(self._h, renderer._h, C.byref(_denoise_parameters(dict(params or {})))))
+
+    def read_denoised(self, renderer):
+        """-> (rgb (H,W,3) f32 denoised mean, bgra (H,W) u32 display texels under the renderer's exposure, the sample count of the gathered sums)"""
+        g = self.gathered_planes()
+        rgba = np.zeros((g["height"], g["width"], 4), np.float32)
+        bgra = np.zeros((g["height"], g["width"]), np.uint32)
+        n = C.c_uint32(0)
+        check(lib.rf_comm_read_denoised(self._h, renderer._h, _ptr(rgba), _ptr(bgra), C.byref(n)))
+        return rgba[..., :3], bgra, n.value
+
+    def noise_estimate(self, renderer, maps=True):
+        """Root: the noise estimate over the gathered image and second moments (needs >= 2 samples).  -> the dict of ReferencePathTracer.noise_estimate; maps=False:
+        the scalars alone (error_map, tile_sum, tile_max are None and are not computed / copied)."""
+        g = self.gathered_planes()
+        est = _ffi.NoiseEstimate()
+        emap = tsum = tmax = None
+        if maps:
+            emap = np.zeros((g["height"], g["width"]), np.float32)
+            tsum = np.zeros(_noise_tiles(g["width"], g["height"]), np.float32); tmax = np.zeros_like(tsum)
+        check(lib.rf_comm_noise_estimate(self._h, renderer._h, C.byref(est), _ptr(emap) if maps else None, _ptr(tsum) if maps else None, _ptr(tmax) if maps else None))
+        return _noise_result(est, emap, tsum, tmax)
 
 
 # ------------------------------------------------------------------------------------- renderer
@@ -763,11 +822,13 @@ class ReferencePathTracer:
         check(lib.rf_renderer_accumulation_device_buffer(self._h, C.byref(p), C.byref(n)))
         return p.value, n.value
 
-    def gather_frame(self, comm, root=0, loopback=False):
+    def gather_frame(self, comm, root=0, loopback=False, aovs=False, moments=False):
         """Frame-end RCCL exchange (collective; enqueued on the handle's stream).  Root: device pointer of the
-        row-major W*H float4 image; other ranks: None."""
+        row-major W*H float4 image; other ranks: None.  aovs / moments: the first-hit AOV sums / the radiance second moments travel in the same group
+        and are un-tiled with the image (they must be on from the first sample); the root then reads, denoises and estimates the gathered frame through
+        comm.read_plane / denoise / noise_estimate."""
         p = C.c_void_p()
-        check(lib.rf_renderer_gather_frame(self._h, comm._h, root, RF_GATHER_LOOPBACK if loopback else 0, C.byref(p)))
+        check(lib.rf_renderer_gather_frame(self._h, comm._h, root, _gather_flags(loopback, aovs, moments), C.byref(p)))
         return p.value
 
     def tonemap_device_image(self, device_ptr, width, height, samples):

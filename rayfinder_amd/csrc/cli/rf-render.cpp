@@ -7,15 +7,16 @@
 // Offline counterpart of the interactive `pt` app (src/pt/main.cpp): same default camera pose,
 // sky and exposure; renders all samples and writes the tonemapped image (and optionally the
 // mean radiance as PFM).  --gpus N: one host thread per GPU, the image tile-sharded across them, one RCCL
-// gather to GPU 0 at frame end (rf_renderer_gather_frame).
+// gather to GPU 0 at frame end (rf_renderer_gather_frame), which also carries the AOV sums and the second moments when an option below needs them
+// (RF_GATHER_AOVS / RF_GATHER_MOMENTS: the same one group of sends and receives, one un-tile kernel on rank 0).
 // --aov-*: the means of the first-hit AOVs (rf_renderer_set_aovs): albedo and normal over the samples, depth over the samples that hit
-// something (a one-channel PFM, 0 where none did).  With --gpus N each rank reads its own tiles' AOVs and the host assembles them.
+// something (a one-channel PFM, 0 where none did).  With --gpus N > 1 they are read from the planes gathered on rank 0 (rf_comm_read_plane).
 // --denoise / --denoise-pfm: the edge-aware a-trous denoiser (rf_renderer_denoise) over the frame, guided by the AOVs (any --denoise* option turns them on
-// from the first sample).  With --gpus N > 1 it runs once, on device 0, over the gathered accumulation and the host-assembled AOV sums (rf_denoise_images):
+// from the first sample).  With --gpus N > 1 it runs once, on rank 0, over the gathered sums where they lie in device memory (rf_comm_denoise):
 // the same inputs, the same kernels, the same bytes whatever N.
 // --noise-map: the per-pixel relative standard error of the frame (rf_renderer_noise_estimate's error map, a one-channel PFM) from the radiance second moments
-// (rf_renderer_set_moments, on from the first sample).  With --gpus N > 1 each rank reads its own tiles' moments, the host assembles them, and the estimate runs once,
-// on device 0, over the gathered accumulation (rf_noise_estimate_images): the same map whatever N.
+// (rf_renderer_set_moments, on from the first sample).  With --gpus N > 1 the estimate runs once, on rank 0, over the gathered accumulation and moments
+// (rf_comm_noise_estimate): the same map whatever N.
 // --adaptive T [--adaptive-min n] [--adaptive-every n]: tile-adaptive sampling (rf_renderer_render_adaptive): every 32x32 tile is sampled until its mean error is <= T,
 // checked every n samples (default 8) from --adaptive-min samples on, --spp at the latest; the image is the per-tile mean.  --gpus 1 only, and not with --noise-target.
 // With --aov-* / --denoise* the AOVs are kept per tile count (RF_AOV_FIRST_HIT | RF_AOV_TILE_COUNTS): the AOV PFMs are divided by each pixel's tile count, and the
@@ -138,24 +139,24 @@ int main(int argc, char** argv)
     std::atomic<unsigned long long> closestRays{0}, shadowRays{0};
     std::vector<uint32_t>           bgra(static_cast<size_t>(W) * H);
     std::vector<float>              acc;
-    // (the denoiser over several ranks needs the whole accumulation on the host)
-    // radiance second moments of the whole frame (every rank copies in the pixels of its own tiles), the error map, and the samples actually rendered
+    // the error map, and the samples actually rendered
     const bool         noise = !noiseMap.empty() || noiseTargetSet || adaptive;
     std::vector<uint32_t> tileSamples;
-    std::vector<float> momentsFrame, errorMap;
+    std::vector<float> errorMap;
     rf_noise_estimate  estimate{};
     uint32_t           sppReached = spp;
     if (!noiseMap.empty()) errorMap.resize(static_cast<size_t>(W) * H);
-    if (!noiseMap.empty() && gpus > 1) momentsFrame.resize(static_cast<size_t>(W) * H * 4);
-    if (!pfm.empty() || ((denoising || !noiseMap.empty()) && gpus > 1)) acc.resize(static_cast<size_t>(W) * H * 4);
-    // first-hit AOV sums of the whole frame ({albedo, coverage}, {normal, depth}): every rank copies in the pixels of its own tiles
-    const bool         aovs = !aovAlbedo.empty() || !aovNormal.empty() || !aovDepth.empty() || denoising;
+    if (!pfm.empty()) acc.resize(static_cast<size_t>(W) * H * 4);
+    // first-hit AOV sums of the whole frame ({albedo, coverage}, {normal, depth}), read on rank 0 when a file is made from them: from the handle, or (several ranks)
+    // from the planes the gather left there
+    const bool         aovFiles = !aovAlbedo.empty() || !aovNormal.empty() || !aovDepth.empty();
+    const bool         aovs = aovFiles || denoising;
     std::vector<float>    denoisedRgba;
     std::vector<uint32_t> denoisedBgra;
     if (denoising) denoisedRgba.resize(static_cast<size_t>(W) * H * 4), denoisedBgra.resize(static_cast<size_t>(W) * H);
     std::vector<float> aovAc, aovNd;
     uint32_t           aovSamples = 0;
-    if (aovs) aovAc.resize(static_cast<size_t>(W) * H * 4), aovNd.resize(static_cast<size_t>(W) * H * 4);
+    if (aovFiles) aovAc.resize(static_cast<size_t>(W) * H * 4), aovNd.resize(static_cast<size_t>(W) * H * 4);
     double       seconds = 0.0;
     // rank r runs on device r -- modulo the devices there are: with more ranks than GPUs RCCL refuses the communicator (two ranks on one device), the local TEST transport
     // (RF_COMM_TRANSPORT=local in the environment: rf_comm.hip) runs them all on what is there -- how the exchange is exercised with many owners on a single-GPU box
@@ -179,62 +180,41 @@ int main(int argc, char** argv)
         if (adaptive) rfCheck(rf_renderer_render_adaptive(renderer, &adaptiveParams, &adaptiveResult), "adaptive render");
         else if (noiseTargetSet) rfCheck(rf_renderer_render_until(renderer, noiseTarget, noiseCheckEvery, spp, &sppReached, &estimate), "render to the noise target");
         else rfCheck(rf_renderer_render(renderer, spp), "render");
+        // (several ranks: the sums the outputs need travel with the image, in the one exchange)
         void* gathered = nullptr;
-        if (comm) rfCheck(rf_renderer_gather_frame(renderer, comm, 0, 0, &gathered), "gather");
+        if (comm) rfCheck(rf_renderer_gather_frame(renderer, comm, 0, (aovs ? RF_GATHER_AOVS : 0u) | (!noiseMap.empty() ? RF_GATHER_MOMENTS : 0u), &gathered), "gather");
         rfCheck(rf_renderer_synchronize(renderer), "synchronize");
         if (rank == 0) seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         rf_stats stats;
         rfCheck(rf_renderer_get_stats(renderer, &stats), "stats");
         closestRays += stats.closest_rays;
         shadowRays += stats.shadow_rays;
-        if (aovs)
-        {
-            // (the tiles are disjoint: each rank copies the pixels of its own tiles into the frame buffers, and no two ranks write the same pixel)
-            std::vector<float> ac(static_cast<size_t>(W) * H * 4), nd(ac.size());
-            uint32_t           n = 0, numTiles = 0;
-            rfCheck(rf_renderer_read_aovs(renderer, ac.data(), nd.data(), &n), "read AOVs");
-            rfCheck(rf_renderer_shard_tiles(renderer, nullptr, &numTiles), "shard tiles");
-            std::vector<uint32_t> tiles(numTiles);
-            rfCheck(rf_renderer_shard_tiles(renderer, tiles.data(), &numTiles), "shard tiles");
-            const uint32_t tilesX = (W + 31) / 32;
-            for (const uint32_t t : tiles)
-                for (uint32_t y = (t / tilesX) * 32; y < std::min(H, (t / tilesX) * 32 + 32); ++y)
-                    for (uint32_t x = (t % tilesX) * 32; x < std::min(W, (t % tilesX) * 32 + 32); ++x)
-                    {
-                        const size_t i = 4 * (static_cast<size_t>(y) * W + x);
-                        std::copy(ac.begin() + i, ac.begin() + i + 4, aovAc.begin() + i);
-                        std::copy(nd.begin() + i, nd.begin() + i + 4, aovNd.begin() + i);
-                    }
-            if (rank == 0) aovSamples = n;
-        }
-        if (!momentsFrame.empty())
-        {
-            std::vector<float> q(momentsFrame.size());
-            uint32_t           n = 0, numTiles = 0;
-            rfCheck(rf_renderer_read_moments(renderer, q.data(), &n), "read moments");
-            rfCheck(rf_renderer_shard_tiles(renderer, nullptr, &numTiles), "shard tiles");
-            std::vector<uint32_t> tiles(numTiles);
-            rfCheck(rf_renderer_shard_tiles(renderer, tiles.data(), &numTiles), "shard tiles");
-            const uint32_t tilesX = (W + 31) / 32;
-            for (const uint32_t t : tiles)
-                for (uint32_t y = (t / tilesX) * 32; y < std::min(H, (t / tilesX) * 32 + 32); ++y)
-                {
-                    const size_t i = 4 * (static_cast<size_t>(y) * W + (t % tilesX) * 32), len = 4 * static_cast<size_t>(std::min(W, (t % tilesX) * 32 + 32) - (t % tilesX) * 32);
-                    std::copy(q.begin() + i, q.begin() + i + len, momentsFrame.begin() + i);
-                }
-        }
         if (rank == 0)
         {
-            if (!noiseMap.empty() && !comm) rfCheck(rf_renderer_noise_estimate(renderer, &estimate, errorMap.data(), nullptr, nullptr), "noise estimate");
+            uint32_t n = 0;
             if (comm)
             {
+                // the gathered frame lies un-tiled in device memory here: tonemap, denoise and estimate it where it is
                 rfCheck(rf_renderer_tonemap_device_image(renderer, gathered, static_cast<uint64_t>(W) * H, spp, bgra.data()), "tonemap");
                 if (!acc.empty()) rfCheck(rf_comm_read_frame(comm, renderer, acc.data()), "read frame");
+                rfCheck(rf_comm_gathered_planes(comm, nullptr, nullptr, nullptr, &aovSamples), "gathered planes");
+                if (aovFiles)
+                {
+                    rfCheck(rf_comm_read_plane(comm, renderer, 1, aovAc.data()), "read AOVs");
+                    rfCheck(rf_comm_read_plane(comm, renderer, 2, aovNd.data()), "read AOVs");
+                }
+                if (denoising)
+                {
+                    rfCheck(rf_comm_denoise(comm, renderer, &denoiseParams), "denoise");
+                    rfCheck(rf_comm_read_denoised(comm, renderer, denoisedRgba.data(), denoisedBgra.data(), &n), "read denoised");
+                }
+                if (!noiseMap.empty()) rfCheck(rf_comm_noise_estimate(comm, renderer, &estimate, errorMap.data(), nullptr, nullptr), "noise estimate");
             }
             else
             {
+                if (aovFiles) rfCheck(rf_renderer_read_aovs(renderer, aovAc.data(), aovNd.data(), &aovSamples), "read AOVs");
+                if (!noiseMap.empty()) rfCheck(rf_renderer_noise_estimate(renderer, &estimate, errorMap.data(), nullptr, nullptr), "noise estimate");
                 rfCheck(rf_renderer_read_tonemapped(renderer, bgra.data()), "tonemap");
-                uint32_t n = 0;
                 if (!acc.empty()) rfCheck(adaptive ? rf_renderer_read_mean(renderer, acc.data()) : rf_renderer_read_accumulation(renderer, acc.data(), &n), "read accumulation");
                 if (!sampleMap.empty() || (adaptive && aovs))
                 {
@@ -257,14 +237,6 @@ int main(int argc, char** argv)
     for (uint32_t rank = 1; rank < gpus; ++rank) threads.emplace_back(worker, rank);
     worker(0);
     for (std::thread& t : threads) t.join();
-    if (denoising && gpus > 1)
-        rfCheck(rf_denoise_images(0, W, H, aovSamples, acc.data(), aovAc.data(), aovNd.data(), &denoiseParams, desc.render_params.exposure, denoisedRgba.data(),
-                                  denoisedBgra.data()),
-                "denoise");
-
-    if (!noiseMap.empty() && gpus > 1)
-        rfCheck(rf_noise_estimate_images(0, W, H, spp, acc.data(), momentsFrame.data(), &estimate, errorMap.data(), nullptr, nullptr), "noise estimate");
-
     const double rays = static_cast<double>(closestRays.load() + shadowRays.load());
     std::printf("%ux%u, %u spp, %u bounces on %u GPU(s): %.3f s, %.1f Mrays/s (%llu closest + %llu shadow rays)\n", W, H, sppReached, bounces, gpus, seconds,
                 rays / seconds * 1e-6, closestRays.load(), shadowRays.load());
@@ -320,7 +292,7 @@ int main(int argc, char** argv)
     if (!write(noiseMap, 1, [&](size_t i, uint32_t) { return errorMap[i / 4]; })) return 1;
     if (!sampleMap.empty() && tileSamples.empty()) tileSamples.assign(static_cast<size_t>((W + 31) / 32) * ((H + 31) / 32), sppReached); // (several ranks: one count)
     if (!write(sampleMap, 1, [&](size_t i, uint32_t) { return static_cast<float>(tileSamples[((i / 4) / W / 32) * ((W + 31) / 32) + ((i / 4) % W) / 32]); })) return 1;
-    if (aovs)
+    if (aovFiles)
     {
         // means (f32 divisions, as ReferencePathTracer.aov_means): albedo / normal over the AOV samples -- with --adaptive the pixel's tile's own count --, depth over the coverage
         const auto n = [&](size_t i) {

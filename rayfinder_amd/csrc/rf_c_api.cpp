@@ -616,9 +616,33 @@ int rf_renderer_gather_frame(rf_renderer* r, rf_comm* c, uint32_t root, uint32_t
         // the exchange is enqueued on the renderer's stream with the communicator's device current: they must be one device
         require(r->impl->deviceOrdinal() == c->impl->deviceOrdinal(), "the renderer and the communicator are on different devices");
         r->impl->requireUniformTileSamples("rf_renderer_gather_frame"); // (the exchange carries no per-tile counts)
-        r->impl->clearAccumulationIfStale(); // nothing rendered since the last reset: send zeros, not the previous frame
-        const void* image = c->impl->gatherFrame(r->impl->accumulationDevicePointer(), r->impl->width(), r->impl->height(), root, r->impl->streamHandle(),
-                                                 (flags & RF_GATHER_LOOPBACK) != 0);
+        // the extra planes: a sum travels only when it holds exactly the accumulated samples (a rank whose shard has no tile has nothing to send and nothing to check
+        // but the switch).  Refused before anything is enqueued or cleared.
+        rf::Renderer&  h = *r->impl;
+        const bool     ownsTiles = !h.shardTiles().empty();
+        const uint32_t n = h.accumulatedSampleCount();
+        uint32_t       planeMask = rf::kPlaneMaskImage;
+        if (flags & RF_GATHER_AOVS)
+        {
+            require(h.aovFlags() != 0u, "rf_renderer_gather_frame: RF_GATHER_AOVS needs the first-hit AOVs: turn them on (rf_renderer_set_aovs) before the first sample");
+            require(!ownsTiles || n != 0u, "rf_renderer_gather_frame: RF_GATHER_AOVS: no sample has been accumulated");
+            if (ownsTiles && !h.aovsCoverAccumulation())
+                throw std::invalid_argument("rf_renderer_gather_frame: RF_GATHER_AOVS: the AOV sample count (" + std::to_string(h.aovSampleCount()) +
+                                            ") differs from the accumulated sample count (" + std::to_string(n) + "): turn the AOVs on before the first sample");
+            planeMask |= rf::kPlaneMaskAovs;
+        }
+        if (flags & RF_GATHER_MOMENTS)
+        {
+            require(h.momentsEnabled(), "rf_renderer_gather_frame: RF_GATHER_MOMENTS needs the radiance second moments: turn them on (rf_renderer_set_moments) before the first sample");
+            require(!ownsTiles || n != 0u, "rf_renderer_gather_frame: RF_GATHER_MOMENTS: no sample has been accumulated");
+            if (ownsTiles && !h.momentsCoverAccumulation())
+                throw std::invalid_argument("rf_renderer_gather_frame: RF_GATHER_MOMENTS: the moment sample count (" + std::to_string(h.momentSampleCount()) +
+                                            ") differs from the accumulated sample count (" + std::to_string(n) + "): turn the moments on before the first sample");
+            planeMask |= rf::kPlaneMaskMoments;
+        }
+        h.clearAccumulationIfStale(); // nothing rendered since the last reset: send zeros, not the previous frame
+        const void* const planes[rf::kGatherPlanes] = {h.accumulationDevicePointer(), h.aovAlbedoCoverageDevicePointer(), h.aovNormalDepthDevicePointer(), h.momentsDevicePointer()};
+        const void*       image = c->impl->gatherPlanes(planes, planeMask, n, h.width(), h.height(), root, h.streamHandle(), (flags & RF_GATHER_LOOPBACK) != 0);
         if (image_device_out) *image_device_out = const_cast<void*>(image);
         return RF_OK;
     });
@@ -639,6 +663,68 @@ int rf_comm_read_frame(rf_comm* c, rf_renderer* r, float* dst)
     return guarded([&] {
         require(c && r && dst, "null argument");
         c->impl->readFrame(dst, r->impl->streamHandle());
+        return RF_OK;
+    });
+}
+
+int rf_comm_gathered_planes(const rf_comm* c, uint32_t* flags_out, uint32_t* width, uint32_t* height, uint32_t* samples)
+{
+    return guarded([&] {
+        require(c, "null argument");
+        uint32_t mask = 0, w = 0, h = 0, n = 0;
+        c->impl->gatheredPlanes(mask, w, h, n);
+        if (flags_out) *flags_out = ((mask & rf::kPlaneMaskAovs) == rf::kPlaneMaskAovs ? RF_GATHER_AOVS : 0u) | ((mask & rf::kPlaneMaskMoments) ? RF_GATHER_MOMENTS : 0u);
+        if (width) *width = w;
+        if (height) *height = h;
+        if (samples) *samples = n;
+        return RF_OK;
+    });
+}
+
+int rf_comm_read_plane(rf_comm* c, rf_renderer* r, uint32_t plane, float* dst)
+{
+    return guarded([&] {
+        require(c && r && dst, "null argument");
+        c->impl->readPlane(plane, dst, r->impl->streamHandle());
+        return RF_OK;
+    });
+}
+
+int rf_comm_plane_device(rf_comm* c, uint32_t plane, void** device_ptr)
+{
+    return guarded([&] {
+        require(c && device_ptr, "null argument");
+        *device_ptr = const_cast<void*>(c->impl->planeDevice(plane));
+        return RF_OK;
+    });
+}
+
+int rf_comm_denoise(rf_comm* c, rf_renderer* r, const rf_denoise_parameters* params)
+{
+    return guarded([&] {
+        const rf::DenoiseParameters p = toDenoiseParams(params);
+        require(c && r, "null argument");
+        require(r->impl->deviceOrdinal() == c->impl->deviceOrdinal(), "the renderer and the communicator are on different devices");
+        c->impl->denoise(p, r->impl->exposure(), r->impl->streamHandle());
+        return RF_OK;
+    });
+}
+
+int rf_comm_read_denoised(rf_comm* c, rf_renderer* r, float* rgba, uint32_t* bgra8, uint32_t* sample_count)
+{
+    return guarded([&] {
+        require(c && r, "null argument");
+        c->impl->readDenoised(rgba, bgra8, sample_count, r->impl->streamHandle());
+        return RF_OK;
+    });
+}
+
+int rf_comm_noise_estimate(rf_comm* c, rf_renderer* r, rf_noise_estimate* out, float* error_map, float* tile_sum, float* tile_max)
+{
+    return guarded([&] {
+        require(c && r && out, "null argument");
+        require(r->impl->deviceOrdinal() == c->impl->deviceOrdinal(), "the renderer and the communicator are on different devices");
+        *out = toNoiseEstimate(c->impl->noiseEstimate(error_map, tile_sum, tile_max, r->impl->streamHandle()));
         return RF_OK;
     });
 }
@@ -756,6 +842,26 @@ int rf_gather_plan(uint32_t width, uint32_t height, uint32_t world_size, uint32_
         {
             require(*num_ops >= plan.size(), "ops array too small");
             std::memcpy(ops, plan.data(), plan.size() * sizeof(rf::GatherOp));
+        }
+        *num_ops = static_cast<uint32_t>(plan.size());
+        return RF_OK;
+    });
+}
+
+int rf_gather_plan_planes(uint32_t width, uint32_t height, uint32_t world_size, uint32_t rank, uint32_t root, uint32_t flags, rf_gather_plane_op* ops, uint32_t* num_ops)
+{
+    return guarded([&] {
+        require(width > 0 && height > 0 && world_size > 0, "empty frame or world");
+        require(rank < world_size && root < world_size, "rank / root out of range");
+        require(num_ops, "null argument");
+        static_assert(sizeof(rf_gather_plane_op) == sizeof(rf::GatherPlaneOp));
+        const uint32_t mask = rf::kPlaneMaskImage | ((flags & RF_GATHER_AOVS) ? rf::kPlaneMaskAovs : 0u) | ((flags & RF_GATHER_MOMENTS) ? rf::kPlaneMaskMoments : 0u);
+        const rf::GatherLayout               g = rf::gatherLayout(width, height, world_size);
+        const std::vector<rf::GatherPlaneOp> plan = rf::gatherPlanPlanes(g, world_size, rank, root, (flags & RF_GATHER_LOOPBACK) != 0, mask);
+        if (ops)
+        {
+            require(*num_ops >= plan.size(), "ops array too small");
+            std::memcpy(ops, plan.data(), plan.size() * sizeof(rf::GatherPlaneOp));
         }
         *num_ops = static_cast<uint32_t>(plan.size());
         return RF_OK;

@@ -1,7 +1,9 @@
 // rf_comm.hip -- RCCL gather of tile shards + device un-tile (see rf_comm.hpp).
 #include "rf_comm.hpp"
 
+#include "rf_denoise.hpp"
 #include "rf_hip_host.hpp"
+#include "rf_noise.hpp"
 #include "rf_renderer.hpp" // tilesForRank, TileGrid
 
 #include <hip/hip_runtime.h>
@@ -56,6 +58,38 @@ __global__ __launch_bounds__(256) void kUntile(const float4* __restrict__ stagin
     }
 }
 
+// The same for every carried plane of a multi-plane gather in ONE launch: grid (tiles of the frame, carried planes); blockIdx.y picks the plane's pointers from the
+// by-value argument struct (kernel arguments: no device-side table, no upload), everything else is kUntile -- wave k of a workgroup moves the tile's 8x8 blocks with
+// 1-KiB contiguous reads and 128-byte row-segment writes; own / staging per tile from the same tileSlot / tileOwner tables.
+struct UntilePlane
+{
+    const float4* staging; // this plane's staging area
+    const float4* own;     // the root's shard of this plane, read in place
+    float4*       image;   // this plane's row-major image
+};
+struct UntilePlaneArgs
+{
+    UntilePlane plane[kGatherPlanes]; // [blockIdx.y]: the carried planes in plane order
+};
+__global__ __launch_bounds__(256) void kUntilePlanes(UntilePlaneArgs args, uint32_t ownRank, uint32_t ownFirstTile, const uint32_t* __restrict__ tileSlot,
+                                                     const uint32_t* __restrict__ tileOwner, uint32_t width, uint32_t height, uint32_t tilesX)
+{
+    const UntilePlane             pl = args.plane[blockIdx.y];
+    const uint32_t                tile = blockIdx.x;
+    const uint32_t                slot = tileSlot[tile];
+    const float4* __restrict__    src = tileOwner[tile] == ownRank ? pl.own + static_cast<size_t>(slot - ownFirstTile) * kTilePixels : pl.staging + static_cast<size_t>(slot) * kTilePixels;
+    float4* __restrict__          image = pl.image;
+    const uint32_t                x0 = (tile % tilesX) * kTileSize, y0 = (tile / tilesX) * kTileSize;
+#pragma unroll
+    for (uint32_t k = 0; k < kTilePixels / 256; ++k)
+    {
+        const uint32_t w = k * 256 + threadIdx.x;
+        const uint32_t block = w >> 6, lane = w & 63u;
+        const uint32_t x = x0 + (block & 3u) * 8u + (lane & 7u), y = y0 + (block >> 2) * 8u + (lane >> 3);
+        if (x < width && y < height) image[static_cast<size_t>(y) * width + x] = src[w];
+    }
+}
+
 } // namespace
 
 GatherLayout gatherLayout(uint32_t width, uint32_t height, uint32_t worldSize)
@@ -96,6 +130,21 @@ std::vector<GatherOp> gatherPlan(const GatherLayout& g, uint32_t worldSize, uint
             ops.push_back(GatherOp{0u, p, g.rankFirstTile[p], tilesOf(p)});
         }
     if (tilesOf(rank) > 0 && (rank != root || loopback)) ops.push_back(GatherOp{1u, root, 0u, tilesOf(rank)});
+    return ops;
+}
+
+std::vector<GatherPlaneOp> gatherPlanPlanes(const GatherLayout& g, uint32_t worldSize, uint32_t rank, uint32_t root, bool loopback, uint32_t planeMask)
+{
+    // the one-plane plan once per carried plane: its receives (rank order), then its send, keep their places within the plane; receives of all planes come first
+    const std::vector<GatherOp> one = gatherPlan(g, worldSize, rank, root, loopback);
+    std::vector<GatherPlaneOp>  ops;
+    for (const uint32_t sends : {0u, 1u})
+        for (uint32_t p = 0; p < kGatherPlanes; ++p)
+        {
+            if (((planeMask | kPlaneMaskImage) >> p & 1u) == 0u) continue;
+            for (const GatherOp& op : one)
+                if (op.isSend == sends) ops.push_back(GatherPlaneOp{op.isSend, op.peer, p, op.offsetTiles, op.countTiles});
+        }
     return ops;
 }
 
@@ -208,9 +257,18 @@ struct TileComm::Impl
     uint32_t         layoutW = 0, layoutH = 0;
     GatherLayout     layout;
     DeviceBuffer<uint32_t> dTileSlot, dTileOwner;
-    DeviceBuffer<float4>   staging, image;
+    DeviceBuffer<float4>   staging;               // one GatherLayout area per carried plane, one after another
+    DeviceBuffer<float4>   images[kGatherPlanes]; // per plane: the row-major image the root un-tiles into (allocated when first carried)
     DeviceBuffer<double>   scalar;
     uint32_t         imageW = 0, imageH = 0;
+    // What the last gather left here (replaced as a whole by the next one): whether one was made, its root, and on the root the carried planes (0: none valid) and
+    // the sample count the caller gave.  A plain gather drops the extra planes' validity, not their buffers.
+    bool             gatherMade = false;
+    uint32_t         lastRoot = 0, gatheredMask = 0, gatheredSamples = 0;
+    // the root-side denoiser and estimate over the gathered planes: their work buffers, allocated by the first call; the snapshot is dropped by the next gather
+    DenoiseWork      denoiseWork;
+    bool             denoisedValid = false;
+    NoiseWork        noiseWork;
     bool             firstGatherDone = false;
     // HIP events around the last exchange on the caller's stream (sends / receives + the root's un-tile): what the frame-end gather costs THIS rank
     // once its own frame kernels have drained (lastExchangeMs())
@@ -231,6 +289,17 @@ struct TileComm::Impl
         RF_HIP(hipStreamSynchronize(stream)); // (`layout` outlives the copy anyway; this keeps pageable-copy semantics out of the picture)
         layoutW = w;
         layoutH = h;
+    }
+
+    // the root-side calls: this rank was the root of the last gather and that gather carried `need`
+    void requireGathered(const char* what, uint32_t need, const char* needName) const
+    {
+        if (!gatherMade) throw std::invalid_argument(std::string(what) + ": no gather has been made on this communicator (call rf_renderer_gather_frame first)");
+        if (rank != lastRoot)
+            throw std::invalid_argument(std::string(what) + ": rank " + std::to_string(rank) + " was not the root of the last gather (rank " + std::to_string(lastRoot) +
+                                        " was): the gathered planes exist on the root only");
+        if ((gatheredMask & need) != need)
+            throw std::invalid_argument(std::string(what) + ": the last gather did not carry " + needName);
     }
 };
 
@@ -336,10 +405,22 @@ void TileComm::rcclInfo(uint32_t& count, uint32_t& userRank, int& device) const
 
 const void* TileComm::gatherFrame(const void* compactDevice, uint32_t width, uint32_t height, uint32_t root, void* streamHandle, bool loopback)
 {
+    const void* const planes[kGatherPlanes] = {compactDevice, nullptr, nullptr, nullptr};
+    return gatherPlanes(planes, kPlaneMaskImage, 0u, width, height, root, streamHandle, loopback);
+}
+
+const void* TileComm::gatherPlanes(const void* const compactDevice[kGatherPlanes], uint32_t planeMask, uint32_t samples, uint32_t width, uint32_t height, uint32_t root,
+                                   void* streamHandle, bool loopback)
+{
     Impl& m = *mImpl;
     if (m.comm == nullptr && !m.fabric) throw std::runtime_error("the RCCL communicator was aborted");
     if (root >= m.world) throw std::invalid_argument("gather root out of range");
     if (width == 0 || height == 0) throw std::invalid_argument("empty frame");
+    if ((planeMask & kPlaneMaskImage) == 0u || (planeMask >> kGatherPlanes) != 0u) throw std::invalid_argument("gather plane mask: plane 0 always travels, planes 0 .. 3 exist");
+    // the carried planes in plane order; carriedIndex[p]: which staging area plane p has
+    uint32_t carried[kGatherPlanes] = {}, carriedIndex[kGatherPlanes] = {}, numPlanes = 0;
+    for (uint32_t p = 0; p < kGatherPlanes; ++p)
+        if (planeMask >> p & 1u) carriedIndex[p] = numPlanes, carried[numPlanes++] = p;
     hipStream_t stream = static_cast<hipStream_t>(streamHandle);
     RF_HIP(hipSetDevice(m.device));
     m.ensureLayout(width, height, stream);
@@ -347,19 +428,31 @@ const void* TileComm::gatherFrame(const void* compactDevice, uint32_t width, uin
     const auto          tilesOf = [&](uint32_t r) { return g.rankFirstTile[r + 1] - g.rankFirstTile[r]; };
     const size_t        floatsPerTile = static_cast<size_t>(kTilePixels) * 4;
     const bool          isRoot = m.rank == root;
-    if (tilesOf(m.rank) > 0 && compactDevice == nullptr) throw std::invalid_argument("null tile buffer");
+    for (uint32_t k = 0; k < numPlanes; ++k)
+        if (tilesOf(m.rank) > 0 && compactDevice[carried[k]] == nullptr) throw std::invalid_argument("null tile buffer");
+    // the record of the last gather goes now: whatever happens below, nothing stale is read through the root-side calls
+    m.gatherMade = true;
+    m.lastRoot = root;
+    m.gatheredMask = 0;
+    m.gatheredSamples = 0;
+    m.denoisedValid = false;
+    const size_t planeStagingPixels = static_cast<size_t>(g.rankFirstTile[m.world]) * kTilePixels; // one plane's staging area
     if (isRoot)
     {
-        const size_t stagingWant = static_cast<size_t>(g.rankFirstTile[m.world]) * kTilePixels, imageWant = static_cast<size_t>(width) * height;
-        if (stagingWant > m.staging.count || imageWant > m.image.count) RF_HIP(hipStreamSynchronize(stream)); // a consumer of the old buffers may still run
+        const size_t stagingWant = planeStagingPixels * numPlanes, imageWant = static_cast<size_t>(width) * height;
+        bool         grows = stagingWant > m.staging.count;
+        for (uint32_t k = 0; k < numPlanes; ++k) grows = grows || imageWant > m.images[carried[k]].count;
+        if (grows) RF_HIP(hipStreamSynchronize(stream)); // a consumer of the old buffers may still run
         m.staging.ensure(stagingWant);
-        m.image.ensure(imageWant);
+        for (uint32_t k = 0; k < numPlanes; ++k) m.images[carried[k]].ensure(imageWant);
         m.imageW = width;
         m.imageH = height;
     }
+    const auto stagingOf = [&](const GatherPlaneOp& op) { return m.staging.ptr + carriedIndex[op.plane] * planeStagingPixels + static_cast<size_t>(op.offsetTiles) * kTilePixels; };
+    const auto compactOf = [&](const GatherPlaneOp& op) { return static_cast<const float*>(compactDevice[op.plane]) + op.offsetTiles * floatsPerTile; };
 
-    // one group: exactly the operations of gatherPlan() (the list the CPU tests check for every rank of a world)
-    const std::vector<GatherOp> plan = gatherPlan(g, m.world, m.rank, root, loopback);
+    // one group: exactly the operations of gatherPlanPlanes() -- with the image alone, gatherPlan()'s (the lists the CPU tests check for every rank of a world)
+    const std::vector<GatherPlaneOp> plan = gatherPlanPlanes(g, m.world, m.rank, root, loopback, planeMask);
     // (first exchange only) marks the end of what was queued on the stream BEFORE the exchange -- this rank's frame kernels: the
     // watchdog below measures the exchange, not the render in front of it
     hipEvent_t queuedBefore = nullptr;
@@ -398,11 +491,11 @@ const void* TileComm::gatherFrame(const void* compactDevice, uint32_t width, uin
             else f.cv.wait(lock, ready);
         };
         std::vector<std::shared_ptr<LocalPost>> mine;
-        for (const GatherOp& op : plan) // 1. post every send
+        for (const GatherPlaneOp& op : plan) // 1. post every send
         {
             if (!op.isSend) continue;
             auto post = std::make_shared<LocalPost>();
-            post->src = static_cast<const float*>(compactDevice) + op.offsetTiles * floatsPerTile;
+            post->src = compactOf(op);
             post->bytes = op.countTiles * floatsPerTile * sizeof(float);
             post->srcDevice = m.device;
             {
@@ -417,7 +510,7 @@ const void* TileComm::gatherFrame(const void* compactDevice, uint32_t width, uin
             f.cv.notify_all();
             mine.push_back(post);
         }
-        for (const GatherOp& op : plan) // 2. every receive: wait for the peer's send, copy behind it
+        for (const GatherPlaneOp& op : plan) // 2. every receive: wait for the peer's send, copy behind it
         {
             if (op.isSend) continue;
             std::shared_ptr<LocalPost> post;
@@ -433,7 +526,7 @@ const void* TileComm::gatherFrame(const void* compactDevice, uint32_t width, uin
                 throw std::runtime_error("local transport: rank " + std::to_string(op.peer) + " sends " + std::to_string(post->bytes) + " bytes, rank " + std::to_string(m.rank) + " expects " +
                                          std::to_string(op.countTiles * floatsPerTile * sizeof(float)) + " (the ranks disagree about the frame)");
             RF_HIP(hipStreamWaitEvent(stream, post->ready, 0));
-            RF_HIP(hipMemcpyAsync(m.staging.ptr + static_cast<size_t>(op.offsetTiles) * kTilePixels, post->src, post->bytes, hipMemcpyDeviceToDevice, stream));
+            RF_HIP(hipMemcpyAsync(stagingOf(op), post->src, post->bytes, hipMemcpyDeviceToDevice, stream));
             RF_HIP(hipEventRecord(post->consumed, stream));
             {
                 std::lock_guard<std::mutex> lock(f.mutex);
@@ -459,12 +552,10 @@ const void* TileComm::gatherFrame(const void* compactDevice, uint32_t width, uin
     RF_NCCL(ncclGroupStart());
     try
     {
-        for (const GatherOp& op : plan)
+        for (const GatherPlaneOp& op : plan)
         {
-            if (op.isSend)
-                RF_NCCL(ncclSend(static_cast<const float*>(compactDevice) + op.offsetTiles * floatsPerTile, op.countTiles * floatsPerTile, ncclFloat, static_cast<int>(op.peer), m.comm, stream));
-            else
-                RF_NCCL(ncclRecv(m.staging.ptr + static_cast<size_t>(op.offsetTiles) * kTilePixels, op.countTiles * floatsPerTile, ncclFloat, static_cast<int>(op.peer), m.comm, stream));
+            if (op.isSend) RF_NCCL(ncclSend(compactOf(op), op.countTiles * floatsPerTile, ncclFloat, static_cast<int>(op.peer), m.comm, stream));
+            else RF_NCCL(ncclRecv(stagingOf(op), op.countTiles * floatsPerTile, ncclFloat, static_cast<int>(op.peer), m.comm, stream));
         }
     }
     catch (...)
@@ -535,12 +626,23 @@ const void* TileComm::gatherFrame(const void* compactDevice, uint32_t width, uin
     }
 
     const uint32_t numTiles = g.tilesX * g.tilesY;
-    hipLaunchKernelGGL(kUntile, dim3(numTiles), dim3(256), 0, stream, m.staging.ptr, static_cast<const float4*>(compactDevice), loopback ? 0xFFFFFFFFu : m.rank,
-                       g.rankFirstTile[m.rank], m.dTileSlot.ptr, m.dTileOwner.ptr, width, height, g.tilesX, m.image.ptr);
+    if (numPlanes == 1)
+        hipLaunchKernelGGL(kUntile, dim3(numTiles), dim3(256), 0, stream, m.staging.ptr, static_cast<const float4*>(compactDevice[kPlaneImage]), loopback ? 0xFFFFFFFFu : m.rank,
+                           g.rankFirstTile[m.rank], m.dTileSlot.ptr, m.dTileOwner.ptr, width, height, g.tilesX, m.images[kPlaneImage].ptr);
+    else
+    {
+        UntilePlaneArgs args{};
+        for (uint32_t k = 0; k < numPlanes; ++k)
+            args.plane[k] = UntilePlane{m.staging.ptr + k * planeStagingPixels, static_cast<const float4*>(compactDevice[carried[k]]), m.images[carried[k]].ptr};
+        hipLaunchKernelGGL(kUntilePlanes, dim3(numTiles, numPlanes), dim3(256), 0, stream, args, loopback ? 0xFFFFFFFFu : m.rank, g.rankFirstTile[m.rank], m.dTileSlot.ptr,
+                           m.dTileOwner.ptr, width, height, g.tilesX);
+    }
     RF_HIP(hipGetLastError());
     RF_HIP(hipEventRecord(m.exchangeStop, stream));
     m.exchangeTimed = true;
-    return m.image.ptr;
+    m.gatheredMask = planeMask;
+    m.gatheredSamples = samples;
+    return m.images[kPlaneImage].ptr;
 }
 
 double TileComm::lastExchangeMs()
@@ -557,11 +659,81 @@ double TileComm::lastExchangeMs()
 void TileComm::readFrame(float* dstHost, void* streamHandle)
 {
     Impl& m = *mImpl;
-    if (m.image.ptr == nullptr || m.imageW == 0) throw std::runtime_error("no gathered frame on this rank (only the gather root has one)");
+    if (m.images[kPlaneImage].ptr == nullptr || m.imageW == 0) throw std::runtime_error("no gathered frame on this rank (only the gather root has one)");
     hipStream_t stream = static_cast<hipStream_t>(streamHandle);
     RF_HIP(hipSetDevice(m.device));
-    RF_HIP(hipMemcpyAsync(dstHost, m.image.ptr, static_cast<size_t>(m.imageW) * m.imageH * sizeof(float4), hipMemcpyDeviceToHost, stream));
+    RF_HIP(hipMemcpyAsync(dstHost, m.images[kPlaneImage].ptr, static_cast<size_t>(m.imageW) * m.imageH * sizeof(float4), hipMemcpyDeviceToHost, stream));
     RF_HIP(hipStreamSynchronize(stream));
+}
+
+namespace
+{
+const char* const kPlaneNames[kGatherPlanes] = {"the image (plane 0)", "the first-hit AOVs (plane 1, AC: gather with RF_GATHER_AOVS)", "the first-hit AOVs (plane 2, ND: gather with RF_GATHER_AOVS)",
+                                                "the radiance second moments (plane 3, Q: gather with RF_GATHER_MOMENTS)"};
+}
+
+void TileComm::gatheredPlanes(uint32_t& planeMask, uint32_t& width, uint32_t& height, uint32_t& samples) const
+{
+    const Impl& m = *mImpl;
+    m.requireGathered("rf_comm_gathered_planes", kPlaneMaskImage, kPlaneNames[kPlaneImage]); // (no image: the last gather threw on this rank)
+    planeMask = m.gatheredMask, width = m.imageW, height = m.imageH, samples = m.gatheredSamples;
+}
+
+const void* TileComm::planeDevice(uint32_t plane) const
+{
+    const Impl& m = *mImpl;
+    if (plane >= kGatherPlanes) throw std::invalid_argument("plane out of range: 0 = S, 1 = AC, 2 = ND, 3 = Q");
+    m.requireGathered("rf_comm_plane_device", 1u << plane, kPlaneNames[plane]);
+    return m.images[plane].ptr;
+}
+
+void TileComm::readPlane(uint32_t plane, float* dstHost, void* streamHandle)
+{
+    Impl& m = *mImpl;
+    if (plane >= kGatherPlanes) throw std::invalid_argument("plane out of range: 0 = S, 1 = AC, 2 = ND, 3 = Q");
+    m.requireGathered("rf_comm_read_plane", 1u << plane, kPlaneNames[plane]);
+    hipStream_t stream = static_cast<hipStream_t>(streamHandle);
+    RF_HIP(hipSetDevice(m.device));
+    RF_HIP(hipMemcpyAsync(dstHost, m.images[plane].ptr, static_cast<size_t>(m.imageW) * m.imageH * sizeof(float4), hipMemcpyDeviceToHost, stream));
+    RF_HIP(hipStreamSynchronize(stream));
+}
+
+void TileComm::denoise(const DenoiseParameters& params, float exposure, void* streamHandle)
+{
+    Impl& m = *mImpl;
+    m.requireGathered("rf_comm_denoise", kPlaneMaskImage | kPlaneMaskAovs, "the first-hit AOVs (gather with RF_GATHER_AOVS)");
+    if (m.gatheredSamples == 0u) throw std::invalid_argument("rf_comm_denoise: the gathered sums hold no sample");
+    if (static_cast<uint64_t>(m.imageW) * m.imageH >= (1ull << 31)) throw std::invalid_argument("rf_comm_denoise: image too large");
+    RF_HIP(hipSetDevice(m.device));
+    // the gathered planes are row-major (tilesX = 0) and hold one count N: the filter rf_denoise_images runs, without the sums leaving the device
+    enqueueDenoise(static_cast<hipStream_t>(streamHandle), m.denoiseWork, m.images[kPlaneImage].ptr, m.images[kPlaneAlbedoCoverage].ptr, m.images[kPlaneNormalDepth].ptr, m.imageW,
+                   m.imageH, 0u, m.gatheredSamples, params, exposure);
+    m.denoisedValid = true;
+}
+
+void TileComm::readDenoised(float* rgba, uint32_t* bgra8, uint32_t* sampleCount, void* streamHandle)
+{
+    Impl& m = *mImpl;
+    m.requireGathered("rf_comm_read_denoised", kPlaneMaskImage | kPlaneMaskAovs, "the first-hit AOVs (gather with RF_GATHER_AOVS)");
+    if (!m.denoisedValid) throw std::invalid_argument("no denoised image: call rf_comm_denoise first (the image is dropped by the next gather)");
+    hipStream_t stream = static_cast<hipStream_t>(streamHandle);
+    RF_HIP(hipSetDevice(m.device));
+    const size_t n = static_cast<size_t>(m.imageW) * m.imageH;
+    if (rgba) RF_HIP(hipMemcpyAsync(rgba, m.denoiseWork.out.ptr, n * sizeof(float4), hipMemcpyDeviceToHost, stream));
+    if (bgra8) RF_HIP(hipMemcpyAsync(bgra8, m.denoiseWork.bgra.ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    RF_HIP(hipStreamSynchronize(stream));
+    if (sampleCount) *sampleCount = m.gatheredSamples;
+}
+
+NoiseEstimate TileComm::noiseEstimate(float* errorMap, float* tileSum, float* tileMax, void* streamHandle)
+{
+    Impl& m = *mImpl;
+    m.requireGathered("rf_comm_noise_estimate", kPlaneMaskImage | kPlaneMaskMoments, "the radiance second moments (gather with RF_GATHER_MOMENTS)");
+    if (m.gatheredSamples < 2u) throw std::invalid_argument("rf_comm_noise_estimate: a variance needs at least 2 accumulated samples");
+    if (static_cast<uint64_t>(m.imageW) * m.imageH >= (1ull << 31)) throw std::invalid_argument("rf_comm_noise_estimate: image too large");
+    RF_HIP(hipSetDevice(m.device));
+    return runNoiseEstimate(static_cast<hipStream_t>(streamHandle), m.noiseWork, m.images[kPlaneImage].ptr, m.images[kPlaneMoments].ptr, m.imageW, m.imageH, false,
+                            m.gatheredSamples, errorMap, tileSum, tileMax);
 }
 
 double TileComm::allReduceMax(double value, void* streamHandle)

@@ -6,7 +6,11 @@
 // at frame end every rank sends that buffer to the root over RCCL (point-to-point ncclSend / ncclRecv in one
 // group: all of the root's xGMI ingress links are used at once; no reduction, no ring), and the root turns the
 // shards into the row-major width x height float4 image with one kernel.  One process (or host thread) per GPU.
+// The same one group can carry the handle's other per-pixel sums (the first-hit AOV sums, the radiance second moments) as further PLANES, un-tiled by one kernel with
+// the image; the root then denoises and estimates the gathered frame where it lies, in device memory (gatherPlanes, denoise, noiseEstimate below).
 #pragma once
+
+#include "rf_renderer.hpp" // DenoiseParameters, NoiseEstimate
 
 #include <cstdint>
 #include <memory>
@@ -41,6 +45,23 @@ struct GatherOp
 };
 std::vector<GatherOp> gatherPlan(const GatherLayout& layout, uint32_t worldSize, uint32_t rank, uint32_t root, bool loopback);
 
+// The sums a gather can carry, one PLANE each, in this fixed order: the image S, the first-hit AOV sums AC = {albedo.rgb, coverage} and ND = {normal.xyz, depth},
+// and the radiance second moments Q.  Every plane is a compact tile-major float4 buffer of the rank's shard, and has its own staging area (GatherLayout) and its own
+// row-major image on the root.  A plane mask has bit p set for every carried plane; plane 0 always travels.
+constexpr uint32_t kGatherPlanes = 4;
+constexpr uint32_t kPlaneImage = 0, kPlaneAlbedoCoverage = 1, kPlaneNormalDepth = 2, kPlaneMoments = 3;
+constexpr uint32_t kPlaneMaskImage = 1u << kPlaneImage, kPlaneMaskAovs = (1u << kPlaneAlbedoCoverage) | (1u << kPlaneNormalDepth), kPlaneMaskMoments = 1u << kPlaneMoments;
+
+// gatherPlan() once per carried plane, still ONE group: on the root, for each plane in order, the receives of that plane in rank order; on a sender, its sends in plane
+// order -- so per (source, destination) pair the k-th send meets the k-th receive, which is what both RCCL's grouped point-to-point calls and the local transport's
+// FIFO matching rely on.  offsetTiles counts from the start of THAT plane's staging area (receive) or compact buffer (send).  With planeMask == kPlaneMaskImage the
+// list is gatherPlan()'s with plane = 0.  Pure host arithmetic (tests/test_gather_sums_api.py).
+struct GatherPlaneOp
+{
+    uint32_t isSend, peer, plane, offsetTiles, countTiles;
+};
+std::vector<GatherPlaneOp> gatherPlanPlanes(const GatherLayout& layout, uint32_t worldSize, uint32_t rank, uint32_t root, bool loopback, uint32_t planeMask);
+
 // HIP devices this process sees (0 without a GPU or a driver; never throws)
 int deviceCount();
 
@@ -71,11 +92,33 @@ public:
     // (returned; valid until the next gather); other ranks get nullptr.  loopback: the root's own shard also
     // travels through ncclSend / ncclRecv (to itself) instead of being read in place -- the world-size-1 self-test.
     const void* gatherFrame(const void* compactDevice, uint32_t width, uint32_t height, uint32_t root, void* stream, bool loopback = false);
+    // The same exchange carrying every plane of planeMask (plane 0 included) in the one group: compactDevice[p] is this rank's tile-major buffer of plane p (unused
+    // entries ignored).  The root stages each plane in its own area of one allocation and un-tiles them all with ONE kernel (kUntilePlanes) into one row-major image per
+    // plane; -> the image of plane 0 on the root, nullptr elsewhere.  planeMask == kPlaneMaskImage enqueues exactly what gatherFrame() enqueues.  `samples`: the sample
+    // count N of the sums, recorded on the root for denoise() / noiseEstimate().  Every gather replaces the record of the one before (planes, frame size, N) and drops
+    // the denoised snapshot.
+    const void* gatherPlanes(const void* const compactDevice[kGatherPlanes], uint32_t planeMask, uint32_t samples, uint32_t width, uint32_t height, uint32_t root, void* stream,
+                             bool loopback = false);
     // Device time of the LAST gatherFrame() on the caller's stream, HIP events around it: from the moment the rank's queued frame kernels have drained and the
     // exchange starts to the end of its sends / receives (+ the un-tile on the root).  Waits for that exchange; -1 before the first one.
     double lastExchangeMs();
     // Root: wait for the stream and copy the gathered image to the host (width * height * 4 floats, row-major).
     void readFrame(float* dstHost, void* stream);
+
+    // ---- the root's side of the last gather.  Each of these throws std::invalid_argument that says which case applies when this rank was not the root of the last
+    // gather, when no gather has been made, or when the last gather did not carry the planes the call needs.
+    // What the last gather left on this rank: the carried planes, the frame size and N.
+    void gatheredPlanes(uint32_t& planeMask, uint32_t& width, uint32_t& height, uint32_t& samples) const;
+    // The row-major width * height float4 image of plane `plane` in device memory (owned by this object; valid until the next gather)
+    const void* planeDevice(uint32_t plane) const;
+    // Wait for the stream and copy that image to the host (width * height * 4 floats)
+    void readPlane(uint32_t plane, float* dstHost, void* stream);
+    // The a-trous denoiser (rf_denoise.hpp: enqueueDenoise, row-major, N) over the gathered planes 0, 1, 2 where they lie, enqueued on `stream`; the snapshot lives in a
+    // DenoiseWork of this object until the next gather.  Needs kPlaneMaskAovs.
+    void denoise(const DenoiseParameters& params, float exposure, void* stream);
+    void readDenoised(float* rgba, uint32_t* bgra8, uint32_t* sampleCount, void* stream);
+    // The noise estimate (rf_noise.hpp: runNoiseEstimate, row-major, N) over the gathered planes 0 and 3; enqueued on `stream`, then waited for.  Needs kPlaneMaskMoments and N >= 2.
+    NoiseEstimate noiseEstimate(float* errorMap, float* tileSum, float* tileMax, void* stream);
     // Max over ranks of a host double / barrier (timing plumbing for callers that have no other collective layer).
     double allReduceMax(double value, void* stream);
 

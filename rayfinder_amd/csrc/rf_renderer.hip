@@ -1577,6 +1577,7 @@ uint32_t Renderer::height() const { return mImpl->params.height; }
 uint32_t Renderer::shardRank() const { return mImpl->rank; }
 uint32_t Renderer::shardWorldSize() const { return mImpl->worldSize; }
 int      Renderer::deviceOrdinal() const { return mImpl->device; }
+float    Renderer::exposure() const { return mImpl->params.exposure; }
 void*    Renderer::streamHandle() const { return mImpl->stream; }
 uint32_t Renderer::numBounces() const { return mImpl->params.samplingParams.numBounces; }
 
@@ -1838,6 +1839,13 @@ uint32_t Renderer::renderUntil(float targetMeanError, uint32_t checkEvery, uint3
 }
 
 void*    Renderer::accumulationDevicePointer() const { return mImpl->image; }
+void*    Renderer::aovAlbedoCoverageDevicePointer() const { return mImpl->aovAlbedoCoverage(); }
+void*    Renderer::aovNormalDepthDevicePointer() const { return mImpl->aovNormalDepth(); }
+void*    Renderer::momentsDevicePointer() const { return mImpl->moments(); }
+bool     Renderer::aovsCoverAccumulation() const { return mImpl->aovSums.on && mImpl->accumulated != 0u && mImpl->aovSums.covers(mImpl->accumulated); }
+bool     Renderer::momentsCoverAccumulation() const { return mImpl->momentSums.on && mImpl->accumulated != 0u && mImpl->momentSums.covers(mImpl->accumulated); }
+uint32_t Renderer::aovSampleCount() const { return mImpl->aovSums.samples; }
+uint32_t Renderer::momentSampleCount() const { return mImpl->momentSums.samples; }
 
 void Renderer::clearAccumulationIfStale()
 {

@@ -210,6 +210,7 @@ public:
     uint32_t shardRank() const;
     uint32_t shardWorldSize() const;
     int      deviceOrdinal() const;
+    float    exposure() const; // of the current render parameters: what the display transforms scale by
     // The handle's HIP stream (a hipStream_t): work a caller wants ordered behind the frame's kernels (the RCCL
     // frame exchange, rf_comm.hpp) is enqueued here.
     void* streamHandle() const;
@@ -261,6 +262,16 @@ public:
     // Device pointer of the compact tile-major accumulation buffer (numTiles*1024 float4) and a
     // way to render into caller-owned device memory (e.g. a torch tensor used for the RCCL gather).
     void*    accumulationDevicePointer() const;
+    // Device pointers of the other compact tile-major sums of the shard, for the frame gather (rf_comm.hpp: planes 1 .. 3): {albedo.rgb, coverage}, {normal.xyz, depth}
+    // and the radiance second moments -- nullptr while the channel is off or has not been sized yet -- and whether a channel holds exactly the accumulated samples
+    // (on from the first sample, at least one accumulated): what the gather requires before it sends them.
+    void*    aovAlbedoCoverageDevicePointer() const;
+    void*    aovNormalDepthDevicePointer() const;
+    void*    momentsDevicePointer() const;
+    bool     aovsCoverAccumulation() const;
+    bool     momentsCoverAccumulation() const;
+    uint32_t aovSampleCount() const;
+    uint32_t momentSampleCount() const;
     // Zero the accumulation buffer (on the handle's stream) if nothing has been rendered into it since the last reset, so that a
     // reader on the device (the frame exchange) never sees the previous frame's sums.
     void     clearAccumulationIfStale();
