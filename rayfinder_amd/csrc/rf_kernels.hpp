@@ -1,8 +1,9 @@
-// rf_kernels.hpp -- what the three translation units of the wavefront path tracer share (round 5: rf_renderer.hip, one 4 600-line unit until then,
-// is now rf_trace.hip -- the traversal kernels --, rf_shade.hip -- ray generation, shading, sky, accumulation, display, the deferred variant -- and
-// rf_renderer.hip -- the host driver).  Path-state streams, queue / slot arithmetic, wave helpers, the launch flags and scheduling constants of the
-// traversal kernels, and the typed entry points through which the host unit launches kernels that live in the other two: each kernel unit hands out the
-// ADDRESS of its kernels (xxxKernel() accessors), the host launches through the pointer -- same arguments, same type checking as a direct launch.
+// rf_kernels.hpp -- what the translation units of the wavefront path tracer share (round 5: rf_renderer.hip, one 4 600-line unit until then,
+// is now rf_trace.hip -- the traversal kernels --, rf_shade.hip -- ray generation, shading, sky, display, the deferred variant --, rf_sums.hip -- the
+// per-pixel sums in sample order, entry points in rf_sums.hpp -- and rf_renderer.hip -- the host driver).  Path-state streams, queue / slot arithmetic, wave
+// helpers, the launch flags and scheduling constants of the traversal kernels, and the typed entry points through which the host unit launches kernels that
+// live in the others: each kernel unit hands out the ADDRESS of its kernels (xxxKernel() accessors), the host launches through the pointer -- same
+// arguments, same type checking as a direct launch.
 #pragma once
 
 #include "rf_renderer.hpp"
@@ -58,7 +59,7 @@ struct PathStreams
 };
 // (The first-hit AOV records -- [2 slot, 2 slot + 1]: {albedo.rgb, coverage}, {normal.xyz, depth}, written by kShade<false, true> at bounce 1 -- are NOT a member here: one more
 // pointer in PathStreams moves every later kernel argument of the traversal kernels, and that alone changed the code of the any-hit kTraceWide instantiations by up to
-// 3 %.  kShade takes them as its last argument, kAccumulateAov as an argument of its own.)
+// 3 %.  kShade takes them as its last argument, the AOV sum kernels (rf_sums.hip) as their source.)
 
 // 12-byte load of the xyz part of a float4 stream element (global_load_dwordx3): the L1 -> VGPR return path
 // bounds the traversal kernels, so the unused .w lanes are not fetched
@@ -352,15 +353,6 @@ constexpr uint32_t kLookFirstBounce = 1u, kLookNoRayCount = 2u; // kShadowFirstL
 
 
 constexpr uint32_t kSortBins = 256; // kShade<SORTED>: triangle ranges of its counting sort (the host derives sortScale from it)
-#if defined(RF_EXP_ACC_PIXELS)
-constexpr uint32_t kAccPixels = RF_EXP_ACC_PIXELS;
-#else
-constexpr uint32_t kAccPixels = 4;
-#endif
-constexpr uint32_t kAccMaxSamples = 1024;
-// kAccumulateAovRuns: 8 pixels x 8 AOV channels = one summing lane each of a 64-lane workgroup; their runs are staged in chunks of kAovChunk samples
-// (8 x 8 x (32 + 1) floats = 8.4 KB of LDS, whatever the batch depth)
-constexpr uint32_t kAovPixels = 8, kAovChunk = 32;
 
 // ------------------------------------------------------------------------------------------------
 // Scheduling constants of the persistent traversal kernel (tuned on the atrium, tools/gpu_ab.py).
@@ -408,9 +400,6 @@ using ShadowFirstLookKernel = void (*)(DeviceScene scene, WideScene wide, SkySta
 using TracePacketKernel = void (*)(DeviceScene scene, WideScene wide, SkyStateGpu sky, SunBasis sunBasis, PathStreams ps, const uint32_t* queue, const uint32_t* queueCount, DeviceCounters* counters, float tMax, uint32_t flags);
 using HitPointsKernel = void (*)(DeviceScene scene, const float4* hit, P3* rayO, uint32_t n);
 using BounceTotalsKernel = void (*)(const uint32_t* queueCounts, uint32_t numBounces, unsigned long long* totals, const uint32_t* listCounts, unsigned long long lookMask, unsigned long long* lookBatch, const uint32_t* shadowListCounts, unsigned long long selfMask, DeviceCounters* counters);
-using AccumulateKernel = void (*)(FrameParams fp, const uint32_t* tileIds, PathStreams ps, float4* image);
-using AccumulateRunsKernel = void (*)(FrameParams fp, const uint32_t* tileIds, PathStreams ps, float4* image);
-using AccumulateAovKernel = void (*)(FrameParams fp, const uint32_t* tileIds, const float4* aov, float4* albedoCoverage, float4* normalDepth);
 using TonemapKernel = void (*)(const float4* image, uint32_t n, uint32_t accumulatedSamples, float exposure, uint32_t* out);
 using PrimaryStatsKernel = void (*)(DeviceScene scene, Camera cam, uint32_t width, uint32_t height, uint32_t* nodesVisited, uint8_t* hitOut, float* tOut, uint32_t* triTests, DeviceCounters* counters);
 using IntersectRaysKernel = void (*)(DeviceScene scene, const float* rays, uint64_t n, float tMax, uint32_t* triOut, float* tOut, float* uvOut, float* pOut, uint32_t* nvOut, uint32_t* ttOut, DeviceCounters* counters);
@@ -433,9 +422,6 @@ RaygenKernel            raygenKernel(bool f32Transcendentals);
 ShadeKernel             shadeKernel(bool sorted, bool aov = false); // aov: the bounce-1 instantiation that also writes the first-hit AOVs (unsorted only)
 SkyKernel               skyKernel(bool f32Transcendentals);
 BounceTotalsKernel      bounceTotalsKernel();
-AccumulateKernel        accumulateKernel();
-AccumulateRunsKernel    accumulateRunsKernel(uint32_t pixelsPerWorkgroup); // 1, 2 or kAccPixels
-AccumulateAovKernel     accumulateAovKernel(bool runs);                    // runs: the LDS-staged kernel for the pixel-major slot order (slotGroupShift 0)
 TonemapKernel           tonemapKernel();
 DeferredLightingKernel  deferredLightingKernel();
 } // namespace kern

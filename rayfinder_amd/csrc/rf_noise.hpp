@@ -1,26 +1,12 @@
-// rf_noise.hpp -- per-pixel radiance second moments and the noise estimate over them (rf_noise.hip): the two accumulation kernels the renderer launches while
-// rf_renderer_set_moments is on, and the launch sequence of the estimate, shared by rf_renderer_noise_estimate (inputs: the handle's own compact tile-major sums)
-// and the standalone rf_noise_estimate_images (inputs: row-major sums).
+// rf_noise.hpp -- the noise estimate over the radiance sum and its second moments (rf_noise.hip; the sums themselves: rf_sums.hpp): the launch sequence of the
+// estimate, shared by rf_renderer_noise_estimate (inputs: the handle's own compact tile-major sums) and the standalone rf_noise_estimate_images (inputs: row-major
+// sums), and the per-tile mean.
 #pragma once
 
 #include "rf_kernels.hpp"
 
 namespace rf
 {
-// Q[lp] += {r.x r.x, r.y r.y, r.z r.z, 0} of samples 0 .. numSamples-1 in sample order, r = rad[slot of (sample, lp)] (what kAccumulate adds); compact tile-major like the image
-using AccumulateMomentsKernel = void (*)(FrameParams fp, const uint32_t* tileIds, const float4* rad, float4* moments);
-// kAccumulateMomentsRuns: 16 pixels x 3 channels = 48 summing lanes of a 64-lane workgroup; their runs are staged, squared, in chunks of kMomentChunk samples
-// (16 x 3 x (32 + 1) floats = 6.3 KB of LDS, whatever the batch depth)
-constexpr uint32_t kMomentPixels = 16, kMomentChunk = 32;
-AccumulateMomentsKernel accumulateMomentsKernel(bool runs); // runs: the LDS-staged kernel for the pixel-major slot order (slotGroupShift 0)
-
-// Tile-adaptive sampling (rf_renderer_render_adaptive).  S[at] += r and Q[at] += {r.x r.x, r.y r.y, r.z r.z} of samples 0 .. numSamples-1 in sample order, in one pass
-// over rad, for the fp.numTiles tiles that tileIds lists: at = tileIds[lp >> 10] * 1024 + (lp & 1023), the place of the tile in the whole frame's compact buffers
-using AccumulateTilesKernel = void (*)(FrameParams fp, const uint32_t* tileIds, const float4* rad, float4* image, float4* moments);
-AccumulateTilesKernel accumulateTilesKernel(bool runs); // runs: the LDS-staged kernel for the pixel-major slot order (kMomentPixels pixels per 64-lane workgroup)
-// The first-hit AOV sums of such a batch (the AOVs on with RF_AOV_TILE_COUNTS): kAccumulateAov's sums from the batch's records aov[2 slot, 2 slot + 1], added at the
-// same places `at` of the frame's two AOV sum buffers.  runs: kAovPixels pixels per 64-lane workgroup
-AccumulateAovKernel accumulateTilesAovKernel(bool runs);
 // mean[i] = {S.rgb / float(count), 1} over n compact tile-major pixels; count = tileSamples[i >> 10], or `samples` for all when tileSamples is nullptr; count 0: rgb 0
 using TileMeanKernel = void (*)(const float4* image, const uint32_t* tileSamples, uint32_t samples, uint32_t n, float4* mean);
 TileMeanKernel tileMeanKernel();

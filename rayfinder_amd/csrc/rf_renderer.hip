@@ -1,4 +1,4 @@
-// rf_renderer.hip -- wavefront path tracer for MI355X (gfx950): the host driver (the kernels live in rf_trace.hip and rf_shade.hip, what the three
+// rf_renderer.hip -- wavefront path tracer for MI355X (gfx950): the host driver (the kernels live in rf_trace.hip, rf_shade.hip and rf_sums.hip, what the
 // units share in rf_kernels.hpp).
 //
 // The reference traces one full path per fragment-shader invocation
@@ -25,6 +25,7 @@
 #include "rf_denoise.hpp"
 #include "rf_kernels.hpp"
 #include "rf_noise.hpp"
+#include "rf_sums.hpp"
 
 #include <map>
 
@@ -1062,30 +1063,33 @@ struct Renderer::Impl
             launchWide(t, wide, WideArgs{io.ps, io.out, io.words.shadowCount(io.bounce, p.shadowSource), io.words.cursorShadow(io.bounce), kTMax, io.persistentGrid, io.blocks});
     }
     // the batch's sums in sample order: the image, then the first-hit AOV sums and the radiance second moments (timed with the accumulation: rf_stats has no entry of
-    // their own for them) -- or the tile-list kernels: one for the image and the moments at once, one for the AOV sums
+    // their own for them) -- or, under a tile list, the image and the moments from one launch, then the AOV sums
     void enqueueSums(const BatchPlan& b, const FrameParams& fp, const PathStreams& ps)
     {
-        const auto sumGrid = [&](uint32_t pixelsPerGroup) { return dim3((fp.pixelsPadded + pixelsPerGroup - 1) / pixelsPerGroup); };
-        const dim3 sumBlock(b.runs ? 64u : static_cast<uint32_t>(kBlock));
-        if (b.accumulateKernel == kAccumulateTiles)
+        struct SumLaunch
         {
-            // (whole frame: compact slot == tile id, so the listed tiles' sums sit at tile id * 1024 of the image and the moments)
-            hipLaunchKernelGGL(accumulateTilesKernel(b.runs), sumGrid(b.accumulatePixels), sumBlock, 0, stream, fp, tileIds.ptr, static_cast<const float4*>(ps.rad), image, moments());
-            // (the AOVs on with kAovTileCounts: the batch's records, added at the same places of the frame's two AOV sum buffers)
-            if (b.aovPixels != 0u)
-                hipLaunchKernelGGL(accumulateTilesAovKernel(b.runs), sumGrid(b.aovPixels), sumBlock, 0, stream, fp, tileIds.ptr, static_cast<const float4*>(sAov.ptr), aovAlbedoCoverage(),
-                                   aovNormalDepth());
-            return;
-        }
+            SumKernel     kernel;
+            uint32_t      pixels; // per workgroup
+            bool          runs;   // an LDS-staged kernel: a 64-lane workgroup; else one lane per pixel, kBlock of them
+            const float4* src;
+            float4 *      dst0, *dst1;
+        };
+        const auto sumGrid = [&](uint32_t pixelsPerGroup) { return dim3((fp.pixelsPadded + pixelsPerGroup - 1) / pixelsPerGroup); };
+        SumLaunch  launches[3];
+        uint32_t   n = 0;
+        // (the headline image kernel, the whole runs in dynamic LDS, keeps its own argument list: rf_sums.hip)
         if (b.accumulateKernel == kAccumulateRuns)
             hipLaunchKernelGGL(accumulateRunsKernel(b.accumulatePixels), sumGrid(b.accumulatePixels), dim3(64), b.accumulatePixels * 3u * (b.numSamples + 1u) * sizeof(float), stream, fp,
                                tileIds.ptr, ps, image);
-        else
-            hipLaunchKernelGGL(accumulateKernel(), sumGrid(b.accumulatePixels), dim3(kBlock), 0, stream, fp, tileIds.ptr, ps, image);
-        if (b.aovPixels != 0u)
-            hipLaunchKernelGGL(accumulateAovKernel(b.runs), sumGrid(b.aovPixels), sumBlock, 0, stream, fp, tileIds.ptr, sAov.ptr, aovAlbedoCoverage(), aovNormalDepth());
-        if (b.momentPixels != 0u)
-            hipLaunchKernelGGL(accumulateMomentsKernel(b.runs), sumGrid(b.momentPixels), sumBlock, 0, stream, fp, tileIds.ptr, static_cast<const float4*>(ps.rad), moments());
+        else if (b.accumulateKernel == kAccumulateTiles) launches[n++] = {sumKernel(Sum::RadianceMoments, b.runs, true), b.accumulatePixels, b.runs, ps.rad, image, moments()};
+        else launches[n++] = {sumKernel(Sum::Radiance, false, false), b.accumulatePixels, false, ps.rad, image, nullptr};
+        if (b.aovPixels != 0u) launches[n++] = {sumKernel(Sum::Aov, b.runs, b.tileList), b.aovPixels, b.runs, sAov.ptr, aovAlbedoCoverage(), aovNormalDepth()};
+        if (b.momentPixels != 0u) launches[n++] = {sumKernel(Sum::Moments, b.runs, false), b.momentPixels, b.runs, ps.rad, moments(), nullptr};
+        for (uint32_t i = 0; i < n; ++i)
+        {
+            const SumLaunch& l = launches[i];
+            hipLaunchKernelGGL(l.kernel, sumGrid(l.pixels), dim3(l.runs ? 64u : static_cast<uint32_t>(kBlock)), 0, stream, fp, tileIds.ptr, l.src, l.dst0, l.dst1);
+        }
     }
 
     // Trace `numSamples` consecutive samples (sample indices start at frame `firstFrame`) of the shard's tiles -- or, active != nullptr, of the tile list that
@@ -1925,7 +1929,7 @@ void Renderer::bindAccumulationBuffer(void* devicePtr, uint64_t bytes)
     synchronize();
     // The caller's buffer was produced on streams this library does not know (e.g. torch's current stream filling
     // it with zeros), and the handle's stream is non-blocking: wait for the whole device once, here, so that the
-    // first memset / kAccumulate into the buffer cannot overtake the caller's own writes.  After this call the buffer
+    // first memset / sum kernel into the buffer cannot overtake the caller's own writes.  After this call the buffer
     // belongs to the handle's stream until rf_renderer_synchronize() returns ("Streams").
     RF_HIP(hipDeviceSynchronize());
     if (devicePtr == nullptr)

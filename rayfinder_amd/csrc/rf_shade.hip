@@ -1,6 +1,6 @@
 // rf_shade.hip -- everything of the wavefront pipeline that is not traversal (MI355X, gfx950): sample permutation + ray generation (wgsl:42-54,236-245,594-616),
-// kShade (albedo, NEE term, cosine bounce: wgsl:189-228,294-319,546-592), kSky (wgsl:212-228,247-275), per-bounce totals, the k-ordered accumulation
-// (wgsl:47-57), the display transform (wgsl:59-63,277-285) and the deferred-lighting variant.  Launched from rf_renderer.hip through the accessors at the
+// kShade (albedo, NEE term, cosine bounce: wgsl:189-228,294-319,546-592), kSky (wgsl:212-228,247-275), per-bounce totals, the display transform
+// (wgsl:59-63,277-285) and the deferred-lighting variant.  (The k-ordered accumulation, wgsl:47-57, and the other sums in sample order: rf_sums.hip.)  Launched from rf_renderer.hip through the accessors at the
 // end of this file (rf_kernels.hpp).
 #include "rf_kernels.hpp"
 
@@ -111,7 +111,7 @@ __global__ __launch_bounds__(kBlock) void kRaygen(FrameParams fp, DeviceScene sc
 // occupies ONE contiguous run of the queue, so queue order stays slot order at the scale of 1024 entries (what is indexed by slot --
 // the blue-noise triple, the radiance sum -- is touched by the same workgroups as before).  `sortScale`: bin of triangle t =
 // (t * sortScale) >> 32.
-// one slot's first-hit AOV record (kShade<false, true>): two 16-byte stores, non-temporal like kShade's other streams (read once, by kAccumulateAov after the last bounce)
+// one slot's first-hit AOV record (kShade<false, true>): two 16-byte stores, non-temporal like kShade's other streams (read once, by the AOV sum kernel after the last bounce)
 typedef float v4f __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void storeAov(float4* aov, uint32_t slot, Vec3 albedo, float coverage, Vec3 normal, float depth)
 {
@@ -540,126 +540,6 @@ __global__ void kBounceTotals(const uint32_t* queueCounts, uint32_t numBounces, 
     }
 }
 
-// image[lp] += radiance of samples 0..numSamples-1 in order (f32, wgsl:55); image is the compact
-// tile-major float4 buffer.
-__global__ __launch_bounds__(kBlock) void kAccumulate(FrameParams fp, const uint32_t* tileIds, PathStreams ps, float4* image)
-{
-    const uint32_t lp = blockIdx.x * kBlock + threadIdx.x;
-    if (lp >= fp.pixelsPadded) return;
-    uint32_t x, y;
-    if (!localPixelToXY(fp, tileIds, lp, x, y)) return;
-    float4 acc = image[lp];
-    for (uint32_t k = 0; k < fp.numSamples; ++k)
-    {
-        const float4 r = ps.rad[samplePixelToSlot(fp, fp.sampleInvPerm ? fp.sampleInvPerm[k] : k, lp)];
-        acc.x += r.x;
-        acc.y += r.y;
-        acc.z += r.z;
-    }
-    image[lp] = acc;
-}
-
-// The same sum for the pixel-major slot order (slotGroupShift = 0), where a pixel's samples sit in one contiguous run of
-// numSamples float4: there kAccumulate's per-thread reads are a 16-byte gather at a stride of numSamples * 16 bytes (8.2 ms per
-// 320 spp of a 1080p frame).  Here one wave takes kAccPixels pixels: their runs are read coalesced (1 KiB per load) into LDS, then
-// one lane per (pixel, channel) adds its samples in sample-index order -- the order is the result (f32, H15), so the
-// additions stay sequential; only the memory traffic changes.  Dynamic LDS: kAccPixels * (numSamples + 1) * 12 bytes (rows padded by one float: bank-conflict-free sums).
-
-// PIXELS per 64-lane workgroup: the runs of PIXELS pixels are staged in LDS (PIXELS x 3 x (S + 1) floats), so deep batches take fewer pixels per workgroup to keep workgroups
-// resident (round 6: 320 spp per batch: 4 pixels = 15 KB, ten workgroups per CU, 3.36 ms; 2 pixels: 2.24 ms; 64 spp: 4 pixels 0.37 ms, 2 pixels 0.43: profiles/r06_raygen)
-template<uint32_t PIXELS>
-__global__ __launch_bounds__(64) void kAccumulateRuns(FrameParams fp, const uint32_t* tileIds, PathStreams ps, float4* image)
-{
-    extern __shared__ float sRun[]; // [pixel][channel][sample], rows of S + 1 floats: the twelve lanes that sum walk twelve different banks
-    const uint32_t S = fp.numSamples, R = S + 1u, lane = threadIdx.x;
-    const uint32_t lp0 = blockIdx.x * PIXELS;
-    for (uint32_t px = 0; px < PIXELS; ++px)
-    {
-        const uint32_t lp = lp0 + px;
-        if (lp >= fp.pixelsPadded) break;
-        const float4* run = ps.rad + static_cast<size_t>(lp) * S;
-        float*        dst = sRun + px * 3u * R;
-        for (uint32_t p = lane; p < S; p += 64u)
-        {
-            // position p of the run holds sample samplePerm[p]: stored at ITS index, so that the sums below walk LDS in order
-            const Vec3     v = load3(run + p);
-            const uint32_t k = fp.samplePerm ? fp.samplePerm[p] : p;
-            dst[k] = v.x;
-            dst[R + k] = v.y;
-            dst[2u * R + k] = v.z;
-        }
-    }
-    __syncthreads();
-    if (lane >= PIXELS * 3u) return;
-    const uint32_t px = lane / 3u, c = lane % 3u, lp = lp0 + px;
-    if (lp >= fp.pixelsPadded) return;
-    uint32_t x, y;
-    if (!localPixelToXY(fp, tileIds, lp, x, y)) return;
-    float*       out = reinterpret_cast<float*>(image + lp) + c;
-    float        acc = *out;
-    const float* src = sRun + (px * 3u + c) * R;
-#pragma unroll 8
-    for (uint32_t k = 0; k < S; ++k) acc += src[k]; // sample order (wgsl:56-57): one dependent chain of f32 additions per channel
-    *out = acc;
-}
-
-// First-hit AOV sums: albedoCoverage[lp] += {albedo.rgb, coverage}, normalDepth[lp] += {normal.xyz, depth} of samples 0..numSamples-1 in sample order (f32, the
-// order of the radiance sum), both compact tile-major like the image.  The per-slot records are kShade<false, true>'s (bounce 1).  Any slot order (kAccumulate's).
-__global__ __launch_bounds__(kBlock) void kAccumulateAov(FrameParams fp, const uint32_t* tileIds, const float4* aov, float4* albedoCoverage, float4* normalDepth)
-{
-    const uint32_t lp = blockIdx.x * kBlock + threadIdx.x;
-    if (lp >= fp.pixelsPadded) return;
-    uint32_t x, y;
-    if (!localPixelToXY(fp, tileIds, lp, x, y)) return;
-    float4 a = albedoCoverage[lp], b = normalDepth[lp];
-    for (uint32_t k = 0; k < fp.numSamples; ++k)
-    {
-        const size_t slot = samplePixelToSlot(fp, fp.sampleInvPerm ? fp.sampleInvPerm[k] : k, lp);
-        const float4 ra = aov[2 * slot], rb = aov[2 * slot + 1];
-        a.x += ra.x, a.y += ra.y, a.z += ra.z, a.w += ra.w;
-        b.x += rb.x, b.y += rb.y, b.z += rb.z, b.w += rb.w;
-    }
-    albedoCoverage[lp] = a;
-    normalDepth[lp] = b;
-}
-
-// The same sums for the pixel-major slot order (slotGroupShift = 0), staged in LDS like kAccumulateRuns: a pixel's samples are one run of numSamples 32-byte records.
-// One 64-lane workgroup takes kAovPixels pixels; per chunk of kAovChunk samples it reads their records (one pixel's chunk = 1 KiB, coalesced when the samples are
-// not permuted) into LDS at the sample's index, then each lane -- one (pixel, channel) -- adds the chunk in sample order onto its running sum.  8.4 KB of LDS per
-// workgroup at any batch depth (round 6: <= ~8 KB keeps twenty workgroups resident per CU, profiles/r06_raygen).
-__global__ __launch_bounds__(64) void kAccumulateAovRuns(FrameParams fp, const uint32_t* tileIds, const float4* aov, float4* albedoCoverage, float4* normalDepth)
-{
-    constexpr uint32_t R = kAovChunk + 1u; // rows padded by one float: the summing lanes walk different banks
-    __shared__ float   sRun[kAovPixels * 8u * R]; // [pixel][channel][sample of the chunk]
-    static_assert(kAovPixels * 8u == 64u && kAovPixels * kAovChunk * 2u % 64u == 0u, "one summing lane per (pixel, channel); whole load rounds");
-    const uint32_t S = fp.numSamples, lane = threadIdx.x, lp0 = blockIdx.x * kAovPixels;
-    const uint32_t px = lane / 8u, c = lane % 8u, lp = lp0 + px;
-    float          acc = 0.0f;
-    if (lp < fp.pixelsPadded) acc = reinterpret_cast<const float*>(c < 4u ? albedoCoverage + lp : normalDepth + lp)[c & 3u];
-    for (uint32_t k0 = 0; k0 < S; k0 += kAovChunk)
-    {
-        const uint32_t n = min(kAovChunk, S - k0);
-        // load round i: pixel i of the workgroup, lane = (sample of the chunk, half of the record)
-        for (uint32_t i = 0; i < kAovPixels; ++i)
-        {
-            const uint32_t kk = lane >> 1, half = lane & 1u, lpi = lp0 + i;
-            if (kk >= n || lpi >= fp.pixelsPadded) continue;
-            const uint32_t k = k0 + kk, p = fp.sampleInvPerm ? fp.sampleInvPerm[k] : k; // sample k sits at position p of the pixel's run
-            const float4   v = aov[2 * (static_cast<size_t>(lpi) * S + p) + half];
-            float*         dst = sRun + (i * 8u + half * 4u) * R + kk;
-            dst[0] = v.x, dst[R] = v.y, dst[2u * R] = v.z, dst[3u * R] = v.w;
-        }
-        __syncthreads();
-        const float* src = sRun + lane * R; // (row lane = pixel px, channel c)
-        for (uint32_t kk = 0; kk < n; ++kk) acc += src[kk]; // sample order: one dependent chain of f32 additions per channel
-        __syncthreads(); // the next chunk overwrites the rows
-    }
-    if (lp >= fp.pixelsPadded) return;
-    uint32_t x, y;
-    if (!localPixelToXY(fp, tileIds, lp, x, y)) return;
-    reinterpret_cast<float*>(c < 4u ? albedoCoverage + lp : normalDepth + lp)[c & 3u] = acc;
-}
-
 // wgsl:59-63,277-285 -> BGRA8Unorm texel
 __global__ void kTonemap(const float4* image, uint32_t n, uint32_t accumulatedSamples, float exposure, uint32_t* out)
 {
@@ -852,9 +732,6 @@ RaygenKernel            raygenKernel(bool f32) { return f32 ? kRaygen<true> : kR
 ShadeKernel             shadeKernel(bool sorted, bool aov) { return aov ? kShade<false, true> : sorted ? kShade<true, false> : kShade<false, false>; }
 SkyKernel               skyKernel(bool f32) { return f32 ? kSky<true> : kSky<false>; }
 BounceTotalsKernel      bounceTotalsKernel() { return kBounceTotals; }
-AccumulateKernel        accumulateKernel() { return kAccumulate; }
-AccumulateRunsKernel    accumulateRunsKernel(uint32_t pixels) { return pixels == 1u ? kAccumulateRuns<1> : pixels == 2u ? kAccumulateRuns<2> : kAccumulateRuns<kAccPixels>; }
-AccumulateAovKernel     accumulateAovKernel(bool runs) { return runs ? kAccumulateAovRuns : kAccumulateAov; }
 TonemapKernel           tonemapKernel() { return kTonemap; }
 DeferredLightingKernel  deferredLightingKernel() { return kDeferredLighting; }
 } // namespace kern

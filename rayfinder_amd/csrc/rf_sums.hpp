@@ -1,0 +1,43 @@
+// rf_sums.hpp -- the per-pixel sums in sample order (rf_sums.hip): every kernel that adds a batch's per-slot records onto a running sum of the handle -- the image S,
+// the radiance second moments Q, the two first-hit AOV sums -- and the constants of their launches.  The host (Impl::planBatch / enqueueSums) picks a kernel by
+// (sum, LDS-staged or one lane per pixel, shard-compact or tile-list addressing) and launches them with one argument list; the headline image kernel keeps its own.
+#pragma once
+
+#include "rf_kernels.hpp"
+
+namespace rf
+{
+// What a launch adds.  Each channel of each sum is ONE dependent chain of f32 additions in sample-index order (Q's term: one f32 multiply of the loaded value with
+// itself), no atomics, no contraction: the bit-exactness contract of the sums.
+enum class Sum : uint32_t
+{
+    Radiance,        // dst0 = S: += r.rgb of src[slot]
+    Moments,         // dst0 = Q: += {r.x r.x, r.y r.y, r.z r.z} of src[slot]
+    RadianceMoments, // dst0 = S, dst1 = Q, from one read of src[slot] (tile-adaptive sampling)
+    Aov,             // dst0 += {albedo.rgb, coverage} = src[2 slot], dst1 += {normal.xyz, depth} = src[2 slot + 1] (kShade<false, true>'s records of bounce 1)
+};
+// src: the batch's per-slot records; dst0 / dst1: the handle's sums, compact tile-major (dst1 unused by the sums that have one buffer).  The sums of local pixel lp
+// sit at lp -- or, tileList (rf_renderer_render_adaptive: the batch's path slots belong to the fp.numTiles tiles that tileIds lists, the sums hold the WHOLE frame,
+// compact slot == tile id), at tileIds[lp >> 10] * 1024 + (lp & 1023).  The sums of pixels outside the frame are neither read nor written.
+using SumKernel = void (*)(FrameParams fp, const uint32_t* tileIds, const float4* src, float4* dst0, float4* dst1);
+
+// runs: the LDS-staged kernel for the pixel-major slot order (slotGroupShift 0), a 64-lane workgroup per kMomentPixels (Moments, RadianceMoments) or kAovPixels (Aov)
+// pixels, their runs staged in chunks of 32 samples: (pixels x channels) rows of (32 + 1) floats = 6 336 B / 8 448 B of LDS at any batch depth (<= ~8 KB keeps twenty
+// workgroups resident per CU, profiles/r06_raygen).  Else one lane per pixel, kBlock pixels per workgroup, any slot order.
+// Compiled: Radiance (one lane per pixel; its staged kernel is accumulateRunsKernel) and Moments with shard-compact addressing, RadianceMoments with a tile list, Aov
+// with both; anything else throws.
+constexpr uint32_t kMomentPixels = 16, kMomentChunk = 32;
+constexpr uint32_t kAovPixels = 8, kAovChunk = 32;
+SumKernel sumKernel(Sum sum, bool runs, bool tileList);
+
+// Radiance, pixel-major slot order, the WHOLE run in LDS: pixelsPerWorkgroup (1, 2 or kAccPixels) x 3 x (numSamples + 1) floats of dynamic LDS, numSamples <= kAccMaxSamples;
+// the image sits at lp (no tile list).  Its source is ps.rad
+#if defined(RF_EXP_ACC_PIXELS)
+constexpr uint32_t kAccPixels = RF_EXP_ACC_PIXELS;
+#else
+constexpr uint32_t kAccPixels = 4;
+#endif
+constexpr uint32_t kAccMaxSamples = 1024;
+using AccumulateRunsKernel = void (*)(FrameParams fp, const uint32_t* tileIds, PathStreams ps, float4* image);
+AccumulateRunsKernel accumulateRunsKernel(uint32_t pixelsPerWorkgroup);
+} // namespace rf

@@ -154,7 +154,7 @@ def test_scheduling_is_invisible(duck_pt, baseline, name, opts, paths):
 
 @pytest.mark.parametrize("every", [8, 16])
 def test_longer_steps_take_the_lds_staged_kernel_and_leave_the_same_sums(duck_pt, every):
-    """check_every > 4 with pixel-major slots: kAccumulateTilesRuns (steps of 4 take the one-lane-per-pixel kernel).  The schedule is the restatement's for that step."""
+    """check_every > 4 with pixel-major slots: kSumRuns<RadianceMomentSum, true> (steps of 4 take the one-lane-per-pixel kernel).  The schedule is the restatement's for that step."""
     S, Q, _ = _oracle(W, H, SPP)
     want = play(S, Q, W, H, _target(), every, min_samples=every)
     assert len(set(want["counts"].tolist())) >= 2

@@ -1,4 +1,4 @@
-"""First-hit AOVs on the GPU (-m gpu): the sums kShade<false, true> + kAccumulateAov keep are bit-identical to the restatement built on the
+"""First-hit AOVs on the GPU (-m gpu): the sums kShade<false, true> + the AOV sum kernels (rf_sums.hip) keep are bit-identical to the restatement built on the
 oracle's primitives (tests/aov_restatement.py), leave the image and the ray counts alone, do not depend on any scheduling choice, and follow the
 bookkeeping include/rayfinder_amd.h states."""
 import os

@@ -1,4 +1,4 @@
-"""Radiance second moments, the noise estimate and render-to-a-noise-target on the GPU (-m gpu): the sums kAccumulateMoments / kAccumulateMomentsRuns keep and
+"""Radiance second moments, the noise estimate and render-to-a-noise-target on the GPU (-m gpu): the sums the moment kernels (rf_sums.hip) keep and
 every output of kNoiseEstimate are bit-identical to the numpy restatement (tests/noise_restatement.py) fed with the oracle's per-sample radiance, leave the image
 and the ray counts alone, do not depend on any scheduling choice, and follow the bookkeeping include/rayfinder_amd.h states."""
 import os
