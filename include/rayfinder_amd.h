@@ -313,7 +313,7 @@ RF_API int rf_renderer_render_until(rf_renderer* r, float target_mean_error, uin
                                     rf_noise_estimate* last);
 
 /* Tile-adaptive sampling: a render call that keeps sampling only the 32x32 tiles that are still noisy, and the per-tile sample count that the reads then honour.
- * No reference counterpart.  Whole frame only (no tile shard); needs the moments on from the first sample and the AOVs off, or on with RF_AOV_TILE_COUNTS
+ * No reference counterpart.  rf_renderer_render_adaptive: the whole frame only (no tile shard; across ranks: rf_comm_render_adaptive, below); needs the moments on from the first sample and the AOVs off, or on with RF_AOV_TILE_COUNTS
  * (from the first sample as well).
  *
  * The handle keeps one more word per tile, tile_samples[t], t in the estimate's tile numbering (tile_y * ceil(width / 32) + tile_x).  rf_renderer_render(n) adds n to
@@ -338,12 +338,12 @@ RF_API int rf_renderer_render_until(rf_renderer* r, float target_mean_error, uin
  * dilated to neighbouring tiles, and counts are per tile, not per pixel).  Waits for the work it enqueues.
  * RF_ERROR_INVALID_ARGUMENT: the moments are off or do not cover the accumulation, the AOVs are on without RF_AOV_TILE_COUNTS (their sums then keep ONE sample
  * count) or with it but do not cover the accumulation (turned on partway through), a tile
- * shard is set (rf_renderer_gather_frame carries no counts), check_every is 0, or target_tile_error is negative or not finite.
+ * shard is set (rf_comm_render_adaptive is the call for a sharded frame), check_every is 0, or target_tile_error is negative or not finite.
  * *result (may be NULL): estimate_passes made by this call; tiles and stopped_tiles (tiles below L) of the frame; the minimum and maximum tile count; pixel_samples =
  * the sum over the tiles of in-frame pixels x tile_samples[t]; last = the estimate of the call's last pass, over the tiles that were active in it (mean_error, max_error,
  * pixels and nonfinite_pixels over those tiles, worst_tile in the frame's numbering, samples = L at that pass; samples = 0 when the call made no pass).
  *
- * While some tile is below L (the NON-UNIFORM state), rf_renderer_render, rf_renderer_render_until, rf_renderer_set_tile_shard and rf_renderer_gather_frame
+ * While some tile is below L (the NON-UNIFORM state), rf_renderer_render, rf_renderer_render_until, rf_renderer_set_tile_shard and rf_renderer_gather_frame (without RF_GATHER_TILE_COUNTS)
  * return RF_ERROR_INVALID_ARGUMENT with a message that says so: each of them assumes one count for the frame.  So does rf_renderer_denoise, unless the AOVs are on
  * with RF_AOV_TILE_COUNTS and cover the accumulation: it then filters with each tile's own count (the denoiser's block above).
  * rf_renderer_set_render_parameters (with a change) and a newly bound accumulation buffer clear the counts with the image.  When every tile is at L -- every tile
@@ -475,7 +475,7 @@ RF_API int rf_renderer_bind_accumulation_buffer(rf_renderer* r, void* device_ptr
  * RF_GATHER_AOVS is refused with RF_ERROR_INVALID_ARGUMENT -- the state kept, nothing enqueued on this rank -- when the AOVs are off, when the AOV sample count
  * differs from the accumulated count (AOVs turned on partway through) or when no sample has been accumulated; RF_GATHER_MOMENTS likewise for the moments.  (A rank
  * whose shard holds no tile -- more ranks than tiles -- sends nothing, and only the switch is checked on it.)  The refusal of the non-uniform state of
- * rf_renderer_render_adaptive comes first, with its own message: the gather carries no per-tile counts.  The ranks must run in step, as for the image: a rank that
+ * rf_renderer_render_adaptive / rf_comm_render_adaptive comes first, with its own message: without RF_GATHER_TILE_COUNTS the gather carries no per-tile counts.  The ranks must run in step, as for the image: a rank that
  * is refused leaves its peers waiting for it.
  * The communicator records what the last gather left on the root: the carried planes, the frame size and the sample count N = the root handle's accumulated count
  * (0 on a root whose shard holds no tile).  A later gather replaces all of it (a plain gather drops the extra planes) and drops the denoised snapshot.
@@ -495,7 +495,38 @@ RF_API int rf_renderer_bind_accumulation_buffer(rf_renderer* r, void* device_ptr
  * sums never leave the device.  params NULL = the defaults; bad parameters are refused as everywhere else.  The snapshot is owned by the comm (its buffers are
  * allocated by the first call) and is dropped by the next gather.  rf_comm_read_denoised: as rf_renderer_read_denoised; RF_ERROR_INVALID_ARGUMENT without a snapshot.
  * rf_comm_noise_estimate: the noise estimate (the definition above) over the gathered planes 0 and 3; enqueued on the handle's stream, then waited for, as
- * rf_renderer_noise_estimate.  Also refused when N < 2.  error_map, tile_sum and tile_max may be NULL. */
+ * rf_renderer_noise_estimate.  Also refused when N < 2.  error_map, tile_sum and tile_max may be NULL.
+ *
+ * TILE-ADAPTIVE SAMPLING ACROSS RANKS.  rf_comm_render_adaptive(c, r, params, result) is rf_renderer_render_adaptive for a frame whose tiles are dealt to the ranks of a
+ * communicator: COLLECTIVE, every rank calls it with the same parameters (the caller's duty, as the frame size is).  r's tile shard must be (rank, world_size) of c.
+ * The frame's leading count L is the largest accumulated count of any rank (one all-reduce at the start of the call).  A rank's active tiles are those of its shard
+ * at L -- it may have none, and a rank without an active tile, or without a tile, traces nothing but takes part in the exchanges -- and from there the loop is
+ * rf_renderer_render_adaptive's own, over the rank's tiles, with no further exchange: a tile stops on its own estimate, which reads that tile's S and Q alone, at the
+ * same checks as on one GPU.  At the end three all-reduces give the frame's figures, and every rank's frame counter stands where the leading tiles' ranks left
+ * theirs: whatever is traced next, after a restart of the accumulation too, is the sample a handle without a tile shard would trace.
+ * DEFINING PROPERTY.  For any sequence of calls with the same parameters on every rank, the count and S, Q, AC, ND of every tile are bit for bit what ONE handle
+ * without a tile shard holds after the same sequence of rf_renderer_render_adaptive calls.  That includes continuation: a tile below the frame's L is never revived,
+ * also on a rank whose tiles all share one lower count.
+ * Every argument and precondition is checked BEFORE the first exchange, so that a refusal (RF_ERROR_INVALID_ARGUMENT; the state kept) leaves no peer waiting when
+ * all ranks are refused alike: rf_renderer_render_adaptive's checks of the moments, the AOV flags, check_every and the target, then the communicator's rank and
+ * world size against the shard.
+ * *result (may be NULL): rank = rf_adaptive_result over this rank's tiles (stopped_tiles: those below the FRAME's leading count; pixel_samples: in-frame pixels x
+ * count over this rank's tiles; last: over this rank's tiles active in the last pass); frame_leading_samples and frame_min_tile_samples: the largest and the smallest
+ * tile count of the frame afterwards; max_rank_pixel_samples: the pixel-samples the busiest rank traced in this call (what the call's duration follows).
+ * Every rank keeps the two frame counts.  While they differ the handle is in the NON-UNIFORM state on every rank, also on one whose own tiles share one count:
+ * rf_renderer_render, rf_renderer_render_until, rf_renderer_set_tile_shard and a gather without RF_GATHER_TILE_COUNTS refuse as above.  The reads behave as they do
+ * under a tile shard: this rank's pixels, each tile with its own divisor, zeros elsewhere; rf_renderer_read_accumulation reports the rank's own leading count.  When
+ * the two are equal every rank is in the ordinary state.  A restart of the accumulation clears it all.
+ * RF_GATHER_TILE_COUNTS: in the same one group, behind its planes, every sender also sends the counts of its shard's tiles from device memory (one uint32 per tile,
+ * in the order of rf_renderer_shard_tiles); the root stages them rank after rank (rf_gather_plan_counts lists the operations, in words) and one small kernel leaves
+ * one count per tile of the frame in device memory.  Allowed in the ordinary state (every tile then carries the accumulated count); required in the non-uniform one.
+ * The root waits for such an exchange.  rf_comm_gathered_planes reports the flag, and N is the largest count.  After such a gather, on the root:
+ *   rf_comm_denoise: each tile with its own count (rf_denoise_tiles' filter; every count must be >= 1); rf_comm_read_denoised reports the largest count.
+ *   rf_comm_noise_estimate: Nf = float(the tile's count) (rf_noise_estimate_tiles' estimate; every count must be >= 2); out->samples = the largest count.
+ *   rf_comm_read_tile_samples: the counts (tile_samples may be NULL) and the number of tiles.
+ *   rf_comm_read_mean: row-major width*height*4 floats {S.rgb / float(the tile's count), 1}; {0, 0, 0, 1} in a tile without a sample.
+ * The gathered planes, counts, mean, denoised frame and estimate are bit for bit the un-sharded handle's reads (rf_renderer_read_tile_samples, rf_renderer_read_mean,
+ * rf_renderer_denoise in the non-uniform state, rf_renderer_noise_estimate). */
 /* MI355X devices this process sees (hipGetDeviceCount; 0 without a GPU).  No reference counterpart (the reference asks Dawn for one adapter,
  * gpu_context.cpp); what a host application sizes `--gpus N` against. */
 RF_API int rf_device_count(int32_t* count_out);
@@ -504,6 +535,7 @@ typedef struct rf_comm rf_comm;
 #define RF_GATHER_LOOPBACK 1u
 #define RF_GATHER_AOVS    2u  /* with the image: AC = {albedo.rgb, coverage} and ND = {normal.xyz, depth} */
 #define RF_GATHER_MOMENTS 4u  /* with the image: Q */
+#define RF_GATHER_TILE_COUNTS 8u /* with the image: one sample count per tile (tile-adaptive sampling across ranks, below) */
 RF_API int  rf_comm_unique_id(uint8_t id_out[RF_COMM_ID_BYTES]);
 RF_API int  rf_comm_create(const uint8_t id[RF_COMM_ID_BYTES], uint32_t rank, uint32_t world_size, int32_t device_ordinal, rf_comm** out);
 RF_API void rf_comm_destroy(rf_comm* c);
@@ -520,6 +552,16 @@ RF_API int  rf_comm_plane_device(rf_comm* c, uint32_t plane, void** device_ptr);
 RF_API int  rf_comm_denoise(rf_comm* c, rf_renderer* r, const rf_denoise_parameters* params);          /* NULL = defaults */
 RF_API int  rf_comm_read_denoised(rf_comm* c, rf_renderer* r, float* rgba, uint32_t* bgra8, uint32_t* sample_count);
 RF_API int  rf_comm_noise_estimate(rf_comm* c, rf_renderer* r, rf_noise_estimate* out, float* error_map, float* tile_sum, float* tile_max);
+typedef struct rf_comm_adaptive_result
+{
+    rf_adaptive_result rank;          /* this rank's tiles only; "stopped" = below the FRAME's leading count */
+    uint32_t frame_leading_samples;   /* max tile count over all ranks */
+    uint32_t frame_min_tile_samples;  /* min tile count over all ranks (tiles that exist) */
+    uint64_t max_rank_pixel_samples;  /* the busiest rank's pixel-samples traced by this call */
+} rf_comm_adaptive_result;
+RF_API int  rf_comm_render_adaptive(rf_comm* c, rf_renderer* r, const rf_adaptive_parameters* params, rf_comm_adaptive_result* result);
+RF_API int  rf_comm_read_tile_samples(rf_comm* c, uint32_t* tile_samples /* may be NULL */, uint32_t* num_tiles);
+RF_API int  rf_comm_read_mean(rf_comm* c, rf_renderer* r, float* rgba);
 /* Max over ranks of *value (timing plumbing for hosts without another collective layer; also a barrier). */
 RF_API int  rf_comm_all_reduce_max(rf_comm* c, rf_renderer* r /* NULL: default stream */, double* value);
 /* What RCCL reports for the communicator (ncclCommCount / ncclCommUserRank / ncclCommCuDevice); any pointer may be NULL.
@@ -607,6 +649,9 @@ typedef struct rf_gather_op
     uint32_t is_send, peer, offset_tiles, count_tiles;
 } rf_gather_op;
 RF_API int rf_gather_plan(uint32_t width, uint32_t height, uint32_t world_size, uint32_t rank, uint32_t root, uint32_t flags, rf_gather_op* ops, uint32_t* num_ops);
+/* The operations a gather with RF_GATHER_TILE_COUNTS posts for the counts, behind those of its planes: {is_send, peer, offset_words, count_words} -- the fields of
+ * rf_gather_op read as uint32 words (one per tile) of the root's count staging area (receive) or of the rank's own counts (send).  Host arithmetic. */
+RF_API int rf_gather_plan_counts(uint32_t width, uint32_t height, uint32_t world_size, uint32_t rank, uint32_t root, uint32_t flags, rf_gather_op* ops, uint32_t* num_ops);
 /* The same for a gather with RF_GATHER_AOVS / RF_GATHER_MOMENTS in `flags`: the one-plane list once per carried plane (plane 0 = S, 1 = AC, 2 = ND, 3 = Q), the
  * receives of all planes first (plane after plane, each in rank order), then the sends in plane order.  offset_tiles counts from the start of THAT plane's own staging
  * area (a receive) or compact buffer (a send).  With neither flag the list is rf_gather_plan's with plane = 0.  ops == NULL: count query. */

@@ -341,10 +341,11 @@ def scene_from_arrays(nodes, positions48, attrs80, textures):
 RF_GATHER_LOOPBACK = 1
 RF_GATHER_AOVS = 2      # with the image: plane 1 = {albedo.rgb, coverage}, plane 2 = {normal.xyz, depth}
 RF_GATHER_MOMENTS = 4   # with the image: plane 3 = the radiance second moments
+RF_GATHER_TILE_COUNTS = 8   # with the image: one sample count per tile (TileComm.render_adaptive)
 
 
-def _gather_flags(loopback=False, aovs=False, moments=False):
-    return (RF_GATHER_LOOPBACK if loopback else 0) | (RF_GATHER_AOVS if aovs else 0) | (RF_GATHER_MOMENTS if moments else 0)
+def _gather_flags(loopback=False, aovs=False, moments=False, tile_counts=False):
+    return (RF_GATHER_LOOPBACK if loopback else 0) | (RF_GATHER_AOVS if aovs else 0) | (RF_GATHER_MOMENTS if moments else 0) | (RF_GATHER_TILE_COUNTS if tile_counts else 0)
 
 
 def gather_layout(width, height, world_size):
@@ -375,6 +376,17 @@ def gather_plan_planes(width, height, world_size, rank, root=0, loopback=False, 
     check(lib.rf_gather_plan_planes(width, height, world_size, rank, root, flags, None, C.byref(n)))
     ops = np.zeros((n.value, 5), np.uint32)
     check(lib.rf_gather_plan_planes(width, height, world_size, rank, root, flags, _ptr(ops), C.byref(n)))
+    return ops
+
+
+def gather_plan_counts(width, height, world_size, rank, root=0, loopback=False):
+    """The operations a gather with tile_counts=True posts for the per-tile sample counts, behind those of its planes: (n, 4) u32 rows
+    {is_send, peer, offset_words, count_words}, one u32 word per tile.  Host arithmetic, no GPU."""
+    n = C.c_uint32(0)
+    flags = RF_GATHER_LOOPBACK if loopback else 0
+    check(lib.rf_gather_plan_counts(width, height, world_size, rank, root, flags, None, C.byref(n)))
+    ops = np.zeros((n.value, 4), np.uint32)
+    check(lib.rf_gather_plan_counts(width, height, world_size, rank, root, flags, _ptr(ops), C.byref(n)))
     return ops
 
 
@@ -445,7 +457,10 @@ class TileComm:
         """What the last gather left on this (root) rank: dict(aovs, moments, width, height, samples)."""
         f, w, h, n = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
         check(lib.rf_comm_gathered_planes(self._h, C.byref(f), C.byref(w), C.byref(h), C.byref(n)))
-        return dict(aovs=bool(f.value & RF_GATHER_AOVS), moments=bool(f.value & RF_GATHER_MOMENTS), width=w.value, height=h.value, samples=n.value)
+        out = dict(aovs=bool(f.value & RF_GATHER_AOVS), moments=bool(f.value & RF_GATHER_MOMENTS), width=w.value, height=h.value, samples=n.value)
+        if f.value & RF_GATHER_TILE_COUNTS:                                   # (a key of its own, and only then: a gather without counts reports what it always did)
+            out["tile_counts"] = True
+        return out
 
     def read_plane(self, renderer, plane):
         """Root: the gathered row-major (H, W, 4) f32 sums of plane 0 = S, 1 = {albedo, coverage}, 2 = {normal, depth}, 3 = the second moments."""
@@ -479,6 +494,37 @@ class TileComm:
             tsum = np.zeros(_noise_tiles(g["width"], g["height"]), np.float32); tmax = np.zeros_like(tsum)
         check(lib.rf_comm_noise_estimate(self._h, renderer._h, C.byref(est), _ptr(emap) if maps else None, _ptr(tsum) if maps else None, _ptr(tmax) if maps else None))
         return _noise_result(est, emap, tsum, tmax)
+
+
+    # tile-adaptive sampling across the ranks of the communicator (include/rayfinder_amd.h: "TILE-ADAPTIVE SAMPLING ACROSS RANKS")
+    def render_adaptive(self, renderer, target_tile_error, check_every=8, min_samples=0, max_samples=0):
+        """ReferencePathTracer.render_adaptive for a frame whose tiles are dealt to the ranks: COLLECTIVE, the same parameters on every rank; renderer's tile shard is
+        this communicator's (rank, world_size).  Every tile ends with the count and the sums one un-sharded handle gives it.
+        -> dict(rank: render_adaptive's dict over this rank's tiles (stopped_tiles: below the frame's leading count), frame_leading_samples, frame_min_tile_samples,
+        max_rank_pixel_samples).  While the two frame counts differ, gather with tile_counts=True."""
+        p = _ffi.AdaptiveParameters(target_tile_error, check_every, min_samples, max_samples)
+        res = _ffi.CommAdaptiveResult()
+        check(lib.rf_comm_render_adaptive(self._h, renderer._h, C.byref(p), C.byref(res)))
+        rank = {k: getattr(res.rank, k) for k, _ in res.rank._fields_ if k not in ("reserved", "last")}
+        rank["last"] = {k: getattr(res.rank.last, k) for k, _ in res.rank.last._fields_} if res.rank.last.samples else None
+        return dict(rank=rank, frame_leading_samples=res.frame_leading_samples, frame_min_tile_samples=res.frame_min_tile_samples,
+                    max_rank_pixel_samples=res.max_rank_pixel_samples)
+
+    def read_tile_samples(self):
+        """Root, after a gather with tile_counts=True: (tiles_y, tiles_x) u32, the sample count of every 32x32 tile of the frame."""
+        g = self.gathered_planes()
+        counts = np.zeros(((g["height"] + TILE - 1) // TILE, (g["width"] + TILE - 1) // TILE), np.uint32)
+        n = C.c_uint32(0)
+        check(lib.rf_comm_read_tile_samples(self._h, _ptr(counts), C.byref(n)))
+        assert n.value == counts.size
+        return counts
+
+    def read_mean(self, renderer):
+        """Root, after a gather with tile_counts=True: (H, W, 4) f32 {sum.rgb / the tile's sample count, 1}."""
+        g = self.gathered_planes()
+        mean = np.zeros((g["height"], g["width"], 4), np.float32)
+        check(lib.rf_comm_read_mean(self._h, renderer._h, _ptr(mean)))
+        return mean
 
 
 # ------------------------------------------------------------------------------------- renderer
@@ -822,13 +868,14 @@ class ReferencePathTracer:
         check(lib.rf_renderer_accumulation_device_buffer(self._h, C.byref(p), C.byref(n)))
         return p.value, n.value
 
-    def gather_frame(self, comm, root=0, loopback=False, aovs=False, moments=False):
+    def gather_frame(self, comm, root=0, loopback=False, aovs=False, moments=False, tile_counts=False):
         """Frame-end RCCL exchange (collective; enqueued on the handle's stream).  Root: device pointer of the
         row-major W*H float4 image; other ranks: None.  aovs / moments: the first-hit AOV sums / the radiance second moments travel in the same group
         and are un-tiled with the image (they must be on from the first sample); the root then reads, denoises and estimates the gathered frame through
-        comm.read_plane / denoise / noise_estimate."""
+        comm.read_plane / denoise / noise_estimate.  tile_counts: the per-tile sample counts travel too (needed after comm.render_adaptive stopped some tiles):
+        the root's denoise / noise_estimate then take each tile's own count, and comm.read_tile_samples / read_mean read them."""
         p = C.c_void_p()
-        check(lib.rf_renderer_gather_frame(self._h, comm._h, root, _gather_flags(loopback, aovs, moments), C.byref(p)))
+        check(lib.rf_renderer_gather_frame(self._h, comm._h, root, _gather_flags(loopback, aovs, moments, tile_counts), C.byref(p)))
         return p.value
 
     def tonemap_device_image(self, device_ptr, width, height, samples):

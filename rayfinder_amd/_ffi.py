@@ -58,6 +58,10 @@ class AdaptiveResult(C.Structure):
                 ("max_tile_samples", C.c_uint32), ("reserved", C.c_uint32), ("pixel_samples", C.c_uint64), ("last", NoiseEstimate)]
 
 
+class CommAdaptiveResult(C.Structure):
+    _fields_ = [("rank", AdaptiveResult), ("frame_leading_samples", C.c_uint32), ("frame_min_tile_samples", C.c_uint32), ("max_rank_pixel_samples", C.c_uint64)]
+
+
 class Camera(C.Structure):
     _fields_ = [("origin", C.c_float * 3), ("lower_left_corner", C.c_float * 3), ("horizontal", C.c_float * 3),
                 ("vertical", C.c_float * 3), ("up", C.c_float * 3), ("right", C.c_float * 3), ("lens_radius", C.c_float)]
@@ -177,12 +181,16 @@ SIGNATURES = {
     "rf_comm_denoise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "rf_comm_read_denoised": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
     "rf_comm_noise_estimate": (C.c_int, [C.c_void_p] * 6),
+    "rf_comm_render_adaptive": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rf_comm_read_tile_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
+    "rf_comm_read_mean": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "rf_comm_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]),
     "rf_renderer_layout_info": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rf_renderer_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "rf_renderer_memory_info": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_uint64)] * 4),
     "rf_gather_plan": (C.c_int, [C.c_uint32] * 6 + [C.c_void_p, C.POINTER(C.c_uint32)]),
     "rf_gather_plan_planes": (C.c_int, [C.c_uint32] * 6 + [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "rf_gather_plan_counts": (C.c_int, [C.c_uint32] * 6 + [C.c_void_p, C.POINTER(C.c_uint32)]),
     "rf_gather_layout": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rf_tiles_for_rank": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]),
     "rf_untile": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),

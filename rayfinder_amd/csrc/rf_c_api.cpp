@@ -615,7 +615,7 @@ int rf_renderer_gather_frame(rf_renderer* r, rf_comm* c, uint32_t root, uint32_t
                 "the renderer's tile shard differs from the communicator's rank / world size (call rf_renderer_set_tile_shard first)");
         // the exchange is enqueued on the renderer's stream with the communicator's device current: they must be one device
         require(r->impl->deviceOrdinal() == c->impl->deviceOrdinal(), "the renderer and the communicator are on different devices");
-        r->impl->requireUniformTileSamples("rf_renderer_gather_frame"); // (the exchange carries no per-tile counts)
+        if (!(flags & RF_GATHER_TILE_COUNTS)) r->impl->requireUniformTileSamples("rf_renderer_gather_frame"); // (such an exchange carries no per-tile counts)
         // the extra planes: a sum travels only when it holds exactly the accumulated samples (a rank whose shard has no tile has nothing to send and nothing to check
         // but the switch).  Refused before anything is enqueued or cleared.
         rf::Renderer&  h = *r->impl;
@@ -641,8 +641,11 @@ int rf_renderer_gather_frame(rf_renderer* r, rf_comm* c, uint32_t root, uint32_t
             planeMask |= rf::kPlaneMaskMoments;
         }
         h.clearAccumulationIfStale(); // nothing rendered since the last reset: send zeros, not the previous frame
+        // the shard's per-tile counts, in slot order, from device memory (the ordinary state: every tile at the accumulated count)
+        const uint32_t* counts = nullptr;
+        if (flags & RF_GATHER_TILE_COUNTS) planeMask |= rf::kGatherMaskTileCounts, counts = h.shardTileSamplesDevice();
         const void* const planes[rf::kGatherPlanes] = {h.accumulationDevicePointer(), h.aovAlbedoCoverageDevicePointer(), h.aovNormalDepthDevicePointer(), h.momentsDevicePointer()};
-        const void*       image = c->impl->gatherPlanes(planes, planeMask, n, h.width(), h.height(), root, h.streamHandle(), (flags & RF_GATHER_LOOPBACK) != 0);
+        const void*       image = c->impl->gatherPlanes(planes, planeMask, n, h.width(), h.height(), root, h.streamHandle(), (flags & RF_GATHER_LOOPBACK) != 0, counts);
         if (image_device_out) *image_device_out = const_cast<void*>(image);
         return RF_OK;
     });
@@ -673,7 +676,8 @@ int rf_comm_gathered_planes(const rf_comm* c, uint32_t* flags_out, uint32_t* wid
         require(c, "null argument");
         uint32_t mask = 0, w = 0, h = 0, n = 0;
         c->impl->gatheredPlanes(mask, w, h, n);
-        if (flags_out) *flags_out = ((mask & rf::kPlaneMaskAovs) == rf::kPlaneMaskAovs ? RF_GATHER_AOVS : 0u) | ((mask & rf::kPlaneMaskMoments) ? RF_GATHER_MOMENTS : 0u);
+        if (flags_out) *flags_out = ((mask & rf::kPlaneMaskAovs) == rf::kPlaneMaskAovs ? RF_GATHER_AOVS : 0u) | ((mask & rf::kPlaneMaskMoments) ? RF_GATHER_MOMENTS : 0u) |
+                                        ((mask & rf::kGatherMaskTileCounts) ? RF_GATHER_TILE_COUNTS : 0u);
         if (width) *width = w;
         if (height) *height = h;
         if (samples) *samples = n;
@@ -725,6 +729,58 @@ int rf_comm_noise_estimate(rf_comm* c, rf_renderer* r, rf_noise_estimate* out, f
         require(c && r && out, "null argument");
         require(r->impl->deviceOrdinal() == c->impl->deviceOrdinal(), "the renderer and the communicator are on different devices");
         *out = toNoiseEstimate(c->impl->noiseEstimate(error_map, tile_sum, tile_max, r->impl->streamHandle()));
+        return RF_OK;
+    });
+}
+
+int rf_comm_read_tile_samples(rf_comm* c, uint32_t* tile_samples, uint32_t* num_tiles)
+{
+    return guarded([&] {
+        require(c && num_tiles, "null argument");
+        *num_tiles = c->impl->readTileSamples(tile_samples);
+        return RF_OK;
+    });
+}
+
+int rf_comm_read_mean(rf_comm* c, rf_renderer* r, float* rgba)
+{
+    return guarded([&] {
+        require(c && r && rgba, "null argument");
+        require(r->impl->deviceOrdinal() == c->impl->deviceOrdinal(), "the renderer and the communicator are on different devices");
+        c->impl->readMean(rgba, r->impl->streamHandle());
+        return RF_OK;
+    });
+}
+
+int rf_comm_render_adaptive(rf_comm* c, rf_renderer* r, const rf_adaptive_parameters* params, rf_comm_adaptive_result* result)
+{
+    return guarded([&] {
+        // every refusal comes before the first collective: a refused rank leaves no peer waiting as long as the ranks pass the same arguments
+        require(c && r && params, "null argument");
+        rf::Renderer&                h = *r->impl;
+        rf::TileComm&                comm = *c->impl;
+        const rf::AdaptiveParameters p{params->target_tile_error, params->check_every, params->min_samples, params->max_samples};
+        h.checkAdaptive(p);
+        require(h.shardRank() == comm.rank() && h.shardWorldSize() == comm.worldSize(),
+                "the renderer's tile shard differs from the communicator's rank / world size (call rf_renderer_set_tile_shard first)");
+        require(h.deviceOrdinal() == comm.deviceOrdinal(), "the renderer and the communicator are on different devices");
+        void* const stream = h.streamHandle();
+        // the frame's leading count: the largest accumulated count of any rank.  From here the loop is this rank's own: a tile's stop reads its own sums alone
+        const uint32_t           leading = static_cast<uint32_t>(comm.allReduceMax(static_cast<double>(h.accumulatedSampleCount()), stream));
+        const rf::AdaptiveResult a = h.renderAdaptiveFrom(p, leading, true);
+        // the frame's figures (exact in a double; a minimum as the maximum of the negated value; a rank without a tile has no minimum to offer)
+        const double noTile = -4294967296.0;
+        const auto   frameLeading = static_cast<uint32_t>(comm.allReduceMax(a.tiles ? static_cast<double>(a.maxTileSamples) : 0.0, stream));
+        const auto   frameMin = static_cast<uint32_t>(-comm.allReduceMax(a.tiles ? -static_cast<double>(a.minTileSamples) : noTile, stream));
+        const auto   busiest = static_cast<uint64_t>(comm.allReduceMax(static_cast<double>(a.tracedPixelSamples), stream));
+        h.setFrameTileSamples(frameLeading, frameMin);
+        // the frame's leading tiles moved the frame counter of the ranks that hold them by frameLeading - leading; a rank that stopped earlier, or never started, follows
+        h.skipFrames(frameLeading - leading - a.framesTraced);
+        if (result)
+        {
+            result->rank = rf_adaptive_result{a.estimatePasses, a.tiles, h.shardTilesBelow(frameLeading), a.minTileSamples, a.maxTileSamples, 0u, a.pixelSamples, toNoiseEstimate(a.last)};
+            result->frame_leading_samples = frameLeading, result->frame_min_tile_samples = frameMin, result->max_rank_pixel_samples = busiest;
+        }
         return RF_OK;
     });
 }
@@ -862,6 +918,24 @@ int rf_gather_plan_planes(uint32_t width, uint32_t height, uint32_t world_size, 
         {
             require(*num_ops >= plan.size(), "ops array too small");
             std::memcpy(ops, plan.data(), plan.size() * sizeof(rf::GatherPlaneOp));
+        }
+        *num_ops = static_cast<uint32_t>(plan.size());
+        return RF_OK;
+    });
+}
+
+int rf_gather_plan_counts(uint32_t width, uint32_t height, uint32_t world_size, uint32_t rank, uint32_t root, uint32_t flags, rf_gather_op* ops, uint32_t* num_ops)
+{
+    return guarded([&] {
+        require(width > 0 && height > 0 && world_size > 0, "empty frame or world");
+        require(rank < world_size && root < world_size, "rank / root out of range");
+        require(num_ops, "null argument");
+        const rf::GatherLayout          g = rf::gatherLayout(width, height, world_size);
+        const std::vector<rf::GatherOp> plan = rf::gatherPlanCounts(g, world_size, rank, root, (flags & RF_GATHER_LOOPBACK) != 0);
+        if (ops)
+        {
+            require(*num_ops >= plan.size(), "ops array too small");
+            std::memcpy(ops, plan.data(), plan.size() * sizeof(rf::GatherOp));
         }
         *num_ops = static_cast<uint32_t>(plan.size());
         return RF_OK;

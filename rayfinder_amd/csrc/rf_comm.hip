@@ -90,6 +90,17 @@ __global__ __launch_bounds__(256) void kUntilePlanes(UntilePlaneArgs args, uint3
     }
 }
 
+
+// The gathered per-tile sample counts, one lane per tile of the frame: frameCounts[tile] = the count its owner sent (staged rank after rank, in slot order: tileSlot) or,
+// for the root's own tiles without loop-back, the root's counts read in place.
+__global__ __launch_bounds__(256) void kUntileCounts(const uint32_t* __restrict__ staged, const uint32_t* __restrict__ own, uint32_t ownRank, uint32_t ownFirstTile,
+                                                     const uint32_t* __restrict__ tileSlot, const uint32_t* __restrict__ tileOwner, uint32_t numTiles, uint32_t* __restrict__ frameCounts)
+{
+    const uint32_t tile = blockIdx.x * 256u + threadIdx.x;
+    if (tile >= numTiles) return;
+    const uint32_t slot = tileSlot[tile];
+    frameCounts[tile] = tileOwner[tile] == ownRank ? own[slot - ownFirstTile] : staged[slot];
+}
 } // namespace
 
 GatherLayout gatherLayout(uint32_t width, uint32_t height, uint32_t worldSize)
@@ -146,6 +157,11 @@ std::vector<GatherPlaneOp> gatherPlanPlanes(const GatherLayout& g, uint32_t worl
                 if (op.isSend == sends) ops.push_back(GatherPlaneOp{op.isSend, op.peer, p, op.offsetTiles, op.countTiles});
         }
     return ops;
+}
+
+std::vector<GatherOp> gatherPlanCounts(const GatherLayout& g, uint32_t worldSize, uint32_t rank, uint32_t root, bool loopback)
+{
+    return gatherPlan(g, worldSize, rank, root, loopback); // (one word per tile: the offsets and counts in words are the one-plane plan's in tiles)
 }
 
 namespace
@@ -260,6 +276,10 @@ struct TileComm::Impl
     DeviceBuffer<float4>   staging;               // one GatherLayout area per carried plane, one after another
     DeviceBuffer<float4>   images[kGatherPlanes]; // per plane: the row-major image the root un-tiles into (allocated when first carried)
     DeviceBuffer<double>   scalar;
+    // the per-tile sample counts of a gather with kGatherMaskTileCounts: staged rank after rank as they arrive, then per tile of the frame (kUntileCounts), and that on the host
+    DeviceBuffer<uint32_t> countStaging, frameCounts;
+    std::vector<uint32_t>  frameCountsHost;
+    DeviceBuffer<float4>   meanImage; // readMean's, allocated by the first call
     uint32_t         imageW = 0, imageH = 0;
     // What the last gather left here (replaced as a whole by the next one): whether one was made, its root, and on the root the carried planes (0: none valid) and
     // the sample count the caller gave.  A plain gather drops the extra planes' validity, not their buffers.
@@ -410,13 +430,15 @@ const void* TileComm::gatherFrame(const void* compactDevice, uint32_t width, uin
 }
 
 const void* TileComm::gatherPlanes(const void* const compactDevice[kGatherPlanes], uint32_t planeMask, uint32_t samples, uint32_t width, uint32_t height, uint32_t root,
-                                   void* streamHandle, bool loopback)
+                                   void* streamHandle, bool loopback, const uint32_t* tileCountsDevice)
 {
     Impl& m = *mImpl;
     if (m.comm == nullptr && !m.fabric) throw std::runtime_error("the RCCL communicator was aborted");
     if (root >= m.world) throw std::invalid_argument("gather root out of range");
     if (width == 0 || height == 0) throw std::invalid_argument("empty frame");
-    if ((planeMask & kPlaneMaskImage) == 0u || (planeMask >> kGatherPlanes) != 0u) throw std::invalid_argument("gather plane mask: plane 0 always travels, planes 0 .. 3 exist");
+    const bool withCounts = (planeMask & kGatherMaskTileCounts) != 0u;
+    if ((planeMask & kPlaneMaskImage) == 0u || ((planeMask & ~kGatherMaskTileCounts) >> kGatherPlanes) != 0u)
+        throw std::invalid_argument("gather plane mask: plane 0 always travels, planes 0 .. 3 exist");
     // the carried planes in plane order; carriedIndex[p]: which staging area plane p has
     uint32_t carried[kGatherPlanes] = {}, carriedIndex[kGatherPlanes] = {}, numPlanes = 0;
     for (uint32_t p = 0; p < kGatherPlanes; ++p)
@@ -430,6 +452,7 @@ const void* TileComm::gatherPlanes(const void* const compactDevice[kGatherPlanes
     const bool          isRoot = m.rank == root;
     for (uint32_t k = 0; k < numPlanes; ++k)
         if (tilesOf(m.rank) > 0 && compactDevice[carried[k]] == nullptr) throw std::invalid_argument("null tile buffer");
+    if (withCounts && tilesOf(m.rank) > 0 && tileCountsDevice == nullptr) throw std::invalid_argument("null tile count buffer");
     // the record of the last gather goes now: whatever happens below, nothing stale is read through the root-side calls
     m.gatherMade = true;
     m.lastRoot = root;
@@ -442,7 +465,10 @@ const void* TileComm::gatherPlanes(const void* const compactDevice[kGatherPlanes
         const size_t stagingWant = planeStagingPixels * numPlanes, imageWant = static_cast<size_t>(width) * height;
         bool         grows = stagingWant > m.staging.count;
         for (uint32_t k = 0; k < numPlanes; ++k) grows = grows || imageWant > m.images[carried[k]].count;
+        const size_t frameTiles = static_cast<size_t>(g.tilesX) * g.tilesY;
+        if (withCounts) grows = grows || g.rankFirstTile[m.world] > m.countStaging.count || frameTiles > m.frameCounts.count;
         if (grows) RF_HIP(hipStreamSynchronize(stream)); // a consumer of the old buffers may still run
+        if (withCounts) m.countStaging.ensure(g.rankFirstTile[m.world]), m.frameCounts.ensure(frameTiles);
         m.staging.ensure(stagingWant);
         for (uint32_t k = 0; k < numPlanes; ++k) m.images[carried[k]].ensure(imageWant);
         m.imageW = width;
@@ -451,8 +477,24 @@ const void* TileComm::gatherPlanes(const void* const compactDevice[kGatherPlanes
     const auto stagingOf = [&](const GatherPlaneOp& op) { return m.staging.ptr + carriedIndex[op.plane] * planeStagingPixels + static_cast<size_t>(op.offsetTiles) * kTilePixels; };
     const auto compactOf = [&](const GatherPlaneOp& op) { return static_cast<const float*>(compactDevice[op.plane]) + op.offsetTiles * floatsPerTile; };
 
-    // one group: exactly the operations of gatherPlanPlanes() -- with the image alone, gatherPlan()'s (the lists the CPU tests check for every rank of a world)
-    const std::vector<GatherPlaneOp> plan = gatherPlanPlanes(g, m.world, m.rank, root, loopback, planeMask);
+    // one group: exactly the operations of gatherPlanPlanes() -- with the image alone, gatherPlan()'s (the lists the CPU tests check for every rank of a world) -- and
+    // behind them, with the counts, those of gatherPlanCounts(): per (source, destination) pair the counts are the last send and the last receive
+    struct Transfer
+    {
+        bool           isSend;
+        uint32_t       peer;
+        const void*    from; // a send's source
+        void*          to;   // a receive's destination
+        size_t         words; // 4-byte elements
+        ncclDataType_t type;
+    };
+    std::vector<Transfer> plan;
+    for (const GatherPlaneOp& op : gatherPlanPlanes(g, m.world, m.rank, root, loopback, planeMask & ~kGatherMaskTileCounts))
+        plan.push_back(Transfer{op.isSend != 0u, op.peer, op.isSend ? compactOf(op) : nullptr, op.isSend ? nullptr : stagingOf(op), op.countTiles * floatsPerTile, ncclFloat});
+    if (withCounts)
+        for (const GatherOp& op : gatherPlanCounts(g, m.world, m.rank, root, loopback))
+            plan.push_back(Transfer{op.isSend != 0u, op.peer, op.isSend ? tileCountsDevice + op.offsetTiles : nullptr, op.isSend ? nullptr : m.countStaging.ptr + op.offsetTiles,
+                                    op.countTiles, ncclUint32});
     // (first exchange only) marks the end of what was queued on the stream BEFORE the exchange -- this rank's frame kernels: the
     // watchdog below measures the exchange, not the render in front of it
     hipEvent_t queuedBefore = nullptr;
@@ -491,12 +533,12 @@ const void* TileComm::gatherPlanes(const void* const compactDevice[kGatherPlanes
             else f.cv.wait(lock, ready);
         };
         std::vector<std::shared_ptr<LocalPost>> mine;
-        for (const GatherPlaneOp& op : plan) // 1. post every send
+        for (const Transfer& op : plan) // 1. post every send
         {
             if (!op.isSend) continue;
             auto post = std::make_shared<LocalPost>();
-            post->src = compactOf(op);
-            post->bytes = op.countTiles * floatsPerTile * sizeof(float);
+            post->src = op.from;
+            post->bytes = op.words * sizeof(uint32_t);
             post->srcDevice = m.device;
             {
                 std::lock_guard<std::mutex> lock(f.mutex);
@@ -510,7 +552,7 @@ const void* TileComm::gatherPlanes(const void* const compactDevice[kGatherPlanes
             f.cv.notify_all();
             mine.push_back(post);
         }
-        for (const GatherPlaneOp& op : plan) // 2. every receive: wait for the peer's send, copy behind it
+        for (const Transfer& op : plan) // 2. every receive: wait for the peer's send, copy behind it
         {
             if (op.isSend) continue;
             std::shared_ptr<LocalPost> post;
@@ -522,11 +564,11 @@ const void* TileComm::gatherPlanes(const void* const compactDevice[kGatherPlanes
                 box.pop_front();
                 post->consumed = f.takeEvent();
             }
-            if (post->bytes != op.countTiles * floatsPerTile * sizeof(float))
+            if (post->bytes != op.words * sizeof(uint32_t)) // (a plane's tiles or a shard's counts: each operation has its own size)
                 throw std::runtime_error("local transport: rank " + std::to_string(op.peer) + " sends " + std::to_string(post->bytes) + " bytes, rank " + std::to_string(m.rank) + " expects " +
-                                         std::to_string(op.countTiles * floatsPerTile * sizeof(float)) + " (the ranks disagree about the frame)");
+                                         std::to_string(op.words * sizeof(uint32_t)) + " (the ranks disagree about the frame)");
             RF_HIP(hipStreamWaitEvent(stream, post->ready, 0));
-            RF_HIP(hipMemcpyAsync(stagingOf(op), post->src, post->bytes, hipMemcpyDeviceToDevice, stream));
+            RF_HIP(hipMemcpyAsync(op.to, post->src, post->bytes, hipMemcpyDeviceToDevice, stream));
             RF_HIP(hipEventRecord(post->consumed, stream));
             {
                 std::lock_guard<std::mutex> lock(f.mutex);
@@ -552,10 +594,10 @@ const void* TileComm::gatherPlanes(const void* const compactDevice[kGatherPlanes
     RF_NCCL(ncclGroupStart());
     try
     {
-        for (const GatherPlaneOp& op : plan)
+        for (const Transfer& op : plan)
         {
-            if (op.isSend) RF_NCCL(ncclSend(compactOf(op), op.countTiles * floatsPerTile, ncclFloat, static_cast<int>(op.peer), m.comm, stream));
-            else RF_NCCL(ncclRecv(stagingOf(op), op.countTiles * floatsPerTile, ncclFloat, static_cast<int>(op.peer), m.comm, stream));
+            if (op.isSend) RF_NCCL(ncclSend(op.from, op.words, op.type, static_cast<int>(op.peer), m.comm, stream));
+            else RF_NCCL(ncclRecv(op.to, op.words, op.type, static_cast<int>(op.peer), m.comm, stream));
         }
     }
     catch (...)
@@ -637,9 +679,20 @@ const void* TileComm::gatherPlanes(const void* const compactDevice[kGatherPlanes
         hipLaunchKernelGGL(kUntilePlanes, dim3(numTiles, numPlanes), dim3(256), 0, stream, args, loopback ? 0xFFFFFFFFu : m.rank, g.rankFirstTile[m.rank], m.dTileSlot.ptr,
                            m.dTileOwner.ptr, width, height, g.tilesX);
     }
+    if (withCounts)
+        hipLaunchKernelGGL(kUntileCounts, dim3((numTiles + 255u) / 256u), dim3(256), 0, stream, m.countStaging.ptr, tileCountsDevice, loopback ? 0xFFFFFFFFu : m.rank,
+                           g.rankFirstTile[m.rank], m.dTileSlot.ptr, m.dTileOwner.ptr, numTiles, m.frameCounts.ptr);
     RF_HIP(hipGetLastError());
     RF_HIP(hipEventRecord(m.exchangeStop, stream));
     m.exchangeTimed = true;
+    if (withCounts)
+    {
+        // the counts on the host as well (the root-side calls check them, N is the largest): the one wait of such a gather, on the root alone
+        m.frameCountsHost.assign(numTiles, 0u);
+        RF_HIP(hipMemcpyAsync(m.frameCountsHost.data(), m.frameCounts.ptr, numTiles * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        RF_HIP(hipStreamSynchronize(stream));
+        samples = *std::max_element(m.frameCountsHost.begin(), m.frameCountsHost.end());
+    }
     m.gatheredMask = planeMask;
     m.gatheredSamples = samples;
     return m.images[kPlaneImage].ptr;
@@ -704,10 +757,13 @@ void TileComm::denoise(const DenoiseParameters& params, float exposure, void* st
     m.requireGathered("rf_comm_denoise", kPlaneMaskImage | kPlaneMaskAovs, "the first-hit AOVs (gather with RF_GATHER_AOVS)");
     if (m.gatheredSamples == 0u) throw std::invalid_argument("rf_comm_denoise: the gathered sums hold no sample");
     if (static_cast<uint64_t>(m.imageW) * m.imageH >= (1ull << 31)) throw std::invalid_argument("rf_comm_denoise: image too large");
+    const bool perTile = (m.gatheredMask & kGatherMaskTileCounts) != 0u;
+    if (perTile && *std::min_element(m.frameCountsHost.begin(), m.frameCountsHost.end()) == 0u) throw std::invalid_argument("rf_comm_denoise: a tile of the gathered frame holds no sample");
     RF_HIP(hipSetDevice(m.device));
-    // the gathered planes are row-major (tilesX = 0) and hold one count N: the filter rf_denoise_images runs, without the sums leaving the device
+    // the gathered planes are row-major (tilesX = 0) and hold one count N: the filter rf_denoise_images runs, without the sums leaving the device -- or, gathered with
+    // the counts, each tile its own: rf_denoise_tiles'
     enqueueDenoise(static_cast<hipStream_t>(streamHandle), m.denoiseWork, m.images[kPlaneImage].ptr, m.images[kPlaneAlbedoCoverage].ptr, m.images[kPlaneNormalDepth].ptr, m.imageW,
-                   m.imageH, 0u, m.gatheredSamples, params, exposure);
+                   m.imageH, 0u, m.gatheredSamples, params, exposure, perTile ? m.frameCounts.ptr : nullptr);
     m.denoisedValid = true;
 }
 
@@ -732,8 +788,44 @@ NoiseEstimate TileComm::noiseEstimate(float* errorMap, float* tileSum, float* ti
     if (m.gatheredSamples < 2u) throw std::invalid_argument("rf_comm_noise_estimate: a variance needs at least 2 accumulated samples");
     if (static_cast<uint64_t>(m.imageW) * m.imageH >= (1ull << 31)) throw std::invalid_argument("rf_comm_noise_estimate: image too large");
     RF_HIP(hipSetDevice(m.device));
+    if (m.gatheredMask & kGatherMaskTileCounts)
+    {
+        // every tile with its own count; `samples` reports the largest
+        if (*std::min_element(m.frameCountsHost.begin(), m.frameCountsHost.end()) < 2u)
+            throw std::invalid_argument("rf_comm_noise_estimate: a variance needs at least 2 samples in every tile of the gathered frame");
+        TileSelection sel;
+        sel.tileSamplesDevice = m.frameCounts.ptr;
+        return runNoiseEstimateTiles(static_cast<hipStream_t>(streamHandle), m.noiseWork, m.images[kPlaneImage].ptr, m.images[kPlaneMoments].ptr, m.imageW, m.imageH, false, sel,
+                                     m.gatheredSamples, errorMap, tileSum, tileMax, nullptr);
+    }
     return runNoiseEstimate(static_cast<hipStream_t>(streamHandle), m.noiseWork, m.images[kPlaneImage].ptr, m.images[kPlaneMoments].ptr, m.imageW, m.imageH, false,
                             m.gatheredSamples, errorMap, tileSum, tileMax);
+}
+
+uint32_t TileComm::readTileSamples(uint32_t* tileSamples) const
+{
+    const Impl& m = *mImpl;
+    m.requireGathered("rf_comm_read_tile_samples", kPlaneMaskImage | kGatherMaskTileCounts, "the per-tile sample counts (gather with RF_GATHER_TILE_COUNTS)");
+    if (tileSamples) std::copy(m.frameCountsHost.begin(), m.frameCountsHost.end(), tileSamples);
+    return static_cast<uint32_t>(m.frameCountsHost.size());
+}
+
+void TileComm::readMean(float* rgba, void* streamHandle)
+{
+    Impl& m = *mImpl;
+    m.requireGathered("rf_comm_read_mean", kPlaneMaskImage | kGatherMaskTileCounts, "the per-tile sample counts (gather with RF_GATHER_TILE_COUNTS)");
+    const size_t n = static_cast<size_t>(m.imageW) * m.imageH;
+    if (n >= (1ull << 31)) throw std::invalid_argument("rf_comm_read_mean: image too large");
+    hipStream_t stream = static_cast<hipStream_t>(streamHandle);
+    RF_HIP(hipSetDevice(m.device));
+    if (m.meanImage.count < n)
+    {
+        RF_HIP(hipStreamSynchronize(stream)); // (an earlier read may still use the smaller one)
+        m.meanImage.alloc(n);
+    }
+    enqueueTileMeanRows(stream, m.images[kPlaneImage].ptr, m.frameCounts.ptr, m.imageW, m.imageH, m.meanImage.ptr);
+    RF_HIP(hipMemcpyAsync(rgba, m.meanImage.ptr, n * sizeof(float4), hipMemcpyDeviceToHost, stream));
+    RF_HIP(hipStreamSynchronize(stream));
 }
 
 double TileComm::allReduceMax(double value, void* streamHandle)

@@ -62,6 +62,12 @@ struct GatherPlaneOp
 };
 std::vector<GatherPlaneOp> gatherPlanPlanes(const GatherLayout& layout, uint32_t worldSize, uint32_t rank, uint32_t root, bool loopback, uint32_t planeMask);
 
+// A gather can also carry the per-tile sample counts of the shards (tile-adaptive sampling across ranks): bit kGatherPlanes of the plane mask.  Every sender then sends,
+// in the same one group and behind its planes, one uint32 per tile of its shard in slot order; the root stages them rank after rank.  gatherPlanCounts: those
+// operations -- gatherPlan()'s with offsetTiles / countTiles counting uint32 WORDS of the count staging area (receive) or of the rank's count array (send).
+constexpr uint32_t kGatherMaskTileCounts = 1u << kGatherPlanes;
+std::vector<GatherOp> gatherPlanCounts(const GatherLayout& layout, uint32_t worldSize, uint32_t rank, uint32_t root, bool loopback);
+
 // HIP devices this process sees (0 without a GPU or a driver; never throws)
 int deviceCount();
 
@@ -97,8 +103,10 @@ public:
     // plane; -> the image of plane 0 on the root, nullptr elsewhere.  planeMask == kPlaneMaskImage enqueues exactly what gatherFrame() enqueues.  `samples`: the sample
     // count N of the sums, recorded on the root for denoise() / noiseEstimate().  Every gather replaces the record of the one before (planes, frame size, N) and drops
     // the denoised snapshot.
+    // planeMask & kGatherMaskTileCounts: tileCountsDevice, this rank's per-tile sample counts in slot order (device memory, one uint32 per tile of the shard), travels too;
+    // the root assembles one count per tile of the frame (kUntileCounts), waits for the exchange, and records N = the largest count instead of `samples`.
     const void* gatherPlanes(const void* const compactDevice[kGatherPlanes], uint32_t planeMask, uint32_t samples, uint32_t width, uint32_t height, uint32_t root, void* stream,
-                             bool loopback = false);
+                             bool loopback = false, const uint32_t* tileCountsDevice = nullptr);
     // Device time of the LAST gatherFrame() on the caller's stream, HIP events around it: from the moment the rank's queued frame kernels have drained and the
     // exchange starts to the end of its sends / receives (+ the un-tile on the root).  Waits for that exchange; -1 before the first one.
     double lastExchangeMs();
@@ -119,6 +127,11 @@ public:
     void readDenoised(float* rgba, uint32_t* bgra8, uint32_t* sampleCount, void* stream);
     // The noise estimate (rf_noise.hpp: runNoiseEstimate, row-major, N) over the gathered planes 0 and 3; enqueued on `stream`, then waited for.  Needs kPlaneMaskMoments and N >= 2.
     NoiseEstimate noiseEstimate(float* errorMap, float* tileSum, float* tileMax, void* stream);
+    // After a gather with kGatherMaskTileCounts, denoise() and noiseEstimate() take each tile's own count (every count >= 1 / >= 2), and:
+    // the gathered counts, one per tile of the frame (tileSamples may be nullptr) -> the number of tiles
+    uint32_t readTileSamples(uint32_t* tileSamples) const;
+    // row-major width * height * 4 floats {S.rgb / float(the tile's count), 1}, {0, 0, 0, 1} in a tile without a sample; enqueued on `stream`, then waited for
+    void readMean(float* rgba, void* stream);
     // Max over ranks of a host double / barrier (timing plumbing for callers that have no other collective layer).
     double allReduceMax(double value, void* stream);
 

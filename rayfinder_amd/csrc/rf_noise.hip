@@ -4,7 +4,9 @@
 // sequence of operations.
 //   kNoiseEstimate          one 256-lane workgroup per 32x32 tile: the per-pixel relative standard error, the tile's halving-tree sum, maximum and counts
 //   kNoiseEstimateTiles     kNoiseEstimate's body (estimateTile) for a list of tiles and / or one sample count per tile
+//   kNoiseEstimateSlots     the same for a list of tiles of a tile shard: the tile's sums sit at its SLOT of the shard's compact buffers
 //   kTileMean               {S.rgb / float(tile's sample count), 1} per pixel
+//   kTileMeanRows           the same over a row-major frame
 #include "rf_noise.hpp"
 
 #include "rf_math.hpp"
@@ -18,10 +20,11 @@ namespace
 constexpr float kEpsLum = 0.00390625f; // 2^-8
 
 // One workgroup per tile of the 32x32 grid.  tileMajor: entry j of the tile sits at S[tile * 1024 + j] (8x8 blocks, localPixelToXY's layout: the workgroup reads
-// two contiguous 16 KB runs); else the sums are row-major.  nf = float(N), nf1 = nf - 1.  errorMap (row-major) may be nullptr.
+// two contiguous 16 KB runs); else the sums are row-major.  nf = float(N), nf1 = nf - 1.  errorMap (row-major) may be nullptr.  srcTile: where the tile's sums sit in
+// a tile-major buffer (`tile` itself, or its slot in a shard's compact buffer); the coordinates and every output belong to `tile`.
 // (estimateTile: the work of one 256-lane workgroup for tile `tile`, shared by kNoiseEstimate and kNoiseEstimateTiles)
-__device__ __forceinline__ void estimateTile(const float4* colorSum, const float4* sumSq, uint32_t width, uint32_t height, uint32_t tilesX, uint32_t tileMajor, uint32_t tile, float nf,
-                                             float nf1, float* errorMap, float* tileSum, float* tileMax, uint32_t* tilePixels, uint32_t* tileNonfinite)
+__device__ __forceinline__ void estimateTile(const float4* colorSum, const float4* sumSq, uint32_t width, uint32_t height, uint32_t tilesX, uint32_t tileMajor, uint32_t tile, uint32_t srcTile,
+                                             float nf, float nf1, float* errorMap, float* tileSum, float* tileMax, uint32_t* tilePixels, uint32_t* tileNonfinite)
 {
     __shared__ float    a[1024]; // a[ty * 32 + tx]
     __shared__ float    sMax[256];
@@ -39,7 +42,7 @@ __device__ __forceinline__ void estimateTile(const float4* colorSum, const float
         float          e = 0.0f;
         if (x < width && y < height)
         {
-            const size_t src = tileMajor ? static_cast<size_t>(tile) * 1024u + j : static_cast<size_t>(y) * width + x;
+            const size_t src = tileMajor ? static_cast<size_t>(srcTile) * 1024u + j : static_cast<size_t>(y) * width + x;
             const float4 s4 = colorSum[src], q4 = sumSq[src];
             const float  s[3] = {s4.x, s4.y, s4.z}, q[3] = {q4.x, q4.y, q4.z};
             float        mu[3], v[3];
@@ -92,7 +95,7 @@ __device__ __forceinline__ void estimateTile(const float4* colorSum, const float
 __global__ __launch_bounds__(256) void kNoiseEstimate(const float4* colorSum, const float4* sumSq, uint32_t width, uint32_t height, uint32_t tilesX, uint32_t tileMajor, float nf,
                                                       float nf1, float* errorMap, float* tileSum, float* tileMax, uint32_t* tilePixels, uint32_t* tileNonfinite)
 {
-    estimateTile(colorSum, sumSq, width, height, tilesX, tileMajor, blockIdx.x, nf, nf1, errorMap, tileSum, tileMax, tilePixels, tileNonfinite);
+    estimateTile(colorSum, sumSq, width, height, tilesX, tileMajor, blockIdx.x, blockIdx.x, nf, nf1, errorMap, tileSum, tileMax, tilePixels, tileNonfinite);
 }
 
 // One workgroup per LISTED tile (tileList == nullptr: tile blockIdx.x), with the tile's own sample count (tileSamples[tile]; nullptr: nf for all).  Nf = float(count),
@@ -103,7 +106,15 @@ __global__ __launch_bounds__(256) void kNoiseEstimateTiles(const float4* colorSu
 {
     const uint32_t tile = tileList ? tileList[blockIdx.x] : blockIdx.x;
     const float    n = tileSamples ? static_cast<float>(tileSamples[tile]) : nf;
-    estimateTile(colorSum, sumSq, width, height, tilesX, tileMajor, tile, n, n - 1.0f, errorMap, tileSum, tileMax, tilePixels, tileNonfinite);
+    estimateTile(colorSum, sumSq, width, height, tilesX, tileMajor, tile, tile, n, n - 1.0f, errorMap, tileSum, tileMax, tilePixels, tileNonfinite);
+}
+
+// One workgroup per listed tile of a tile SHARD (rf_comm_render_adaptive): tileList holds the `listed` frame tile ids and, behind them, the tiles' slots in the shard's
+// compact tile-major sums.  Nf = nf for all; the per-tile outputs at the tile's frame id, as above.
+__global__ __launch_bounds__(256) void kNoiseEstimateSlots(const float4* colorSum, const float4* sumSq, uint32_t width, uint32_t height, uint32_t tilesX, const uint32_t* tileList,
+                                                           uint32_t listed, float nf, float* errorMap, float* tileSum, float* tileMax, uint32_t* tilePixels, uint32_t* tileNonfinite)
+{
+    estimateTile(colorSum, sumSq, width, height, tilesX, 1u, tileList[blockIdx.x], tileList[listed + blockIdx.x], nf, nf - 1.0f, errorMap, tileSum, tileMax, tilePixels, tileNonfinite);
 }
 
 // mean[i] = {S.rgb / float(n), 1}, n = the sample count of the pixel's tile (tileSamples[i >> 10]; nullptr: `samples` for all); n = 0: {0, 0, 0, 1}.  Compact tile-major.
@@ -116,9 +127,28 @@ __global__ __launch_bounds__(256) void kTileMean(const float4* image, const uint
     const float    nf = static_cast<float>(count);
     mean[i] = count ? make_float4(s.x / nf, s.y / nf, s.z / nf, 1.0f) : make_float4(0.0f, 0.0f, 0.0f, 1.0f);
 }
+
+// The same over a row-major width x height frame (the gathered image on the root): n = tileSamples[tile of the pixel], tile = (y / 32) * tilesX + x / 32
+__global__ __launch_bounds__(256) void kTileMeanRows(const float4* image, const uint32_t* tileSamples, uint32_t width, uint32_t height, uint32_t tilesX, float4* mean)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= width * height) return;
+    const uint32_t y = i / width, x = i - y * width;
+    const uint32_t count = tileSamples[(y / kTileSize) * tilesX + x / kTileSize];
+    const float4   s = image[i];
+    const float    nf = static_cast<float>(count);
+    mean[i] = count ? make_float4(s.x / nf, s.y / nf, s.z / nf, 1.0f) : make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+}
 } // namespace
 
 TileMeanKernel tileMeanKernel() { return kTileMean; }
+
+void enqueueTileMeanRows(hipStream_t stream, const float4* image, const uint32_t* tileSamples, uint32_t width, uint32_t height, float4* mean)
+{
+    const uint32_t n = width * height; // (< 2^31: the callers check)
+    hipLaunchKernelGGL(kTileMeanRows, dim3((n + 255u) / 256u), dim3(256), 0, stream, image, tileSamples, width, height, TileGrid(width, height).tilesX, mean);
+    RF_HIP(hipGetLastError());
+}
 
 void NoiseWork::reserve(uint64_t nTiles, uint64_t nMap, hipStream_t stream)
 {
@@ -156,7 +186,13 @@ NoiseEstimate runNoiseEstimateTiles(hipStream_t stream, NoiseWork& w, const floa
     w.reserve(tiles, errorMap ? n : 0, stream);
     const float nf = static_cast<float>(samples), nf1 = nf - 1.0f;
     float* const map = errorMap ? w.errorMap.ptr : static_cast<float*>(nullptr);
-    if (sel.listDevice == nullptr && sel.tileSamplesDevice == nullptr)
+    if (sel.slotsBehindList)
+    {
+        if (!tileMajor || sel.listDevice == nullptr || sel.tileSamplesDevice != nullptr) throw std::logic_error("a shard's slot list: tile-major sums, a list, one count");
+        hipLaunchKernelGGL(kNoiseEstimateSlots, dim3(listed), dim3(256), 0, stream, colorSum, sumSq, width, height, tilesX, sel.listDevice, listed, nf, map, w.tileSumMax.ptr,
+                           w.tileSumMax.ptr + w.tiles, w.tileCounts.ptr, w.tileCounts.ptr + w.tiles);
+    }
+    else if (sel.listDevice == nullptr && sel.tileSamplesDevice == nullptr)
         hipLaunchKernelGGL(kNoiseEstimate, dim3(tiles), dim3(256), 0, stream, colorSum, sumSq, width, height, tilesX, tileMajor ? 1u : 0u, nf, nf1, map, w.tileSumMax.ptr,
                            w.tileSumMax.ptr + w.tiles, w.tileCounts.ptr, w.tileCounts.ptr + w.tiles);
     else

@@ -10,6 +10,8 @@ namespace rf
 // mean[i] = {S.rgb / float(count), 1} over n compact tile-major pixels; count = tileSamples[i >> 10], or `samples` for all when tileSamples is nullptr; count 0: rgb 0
 using TileMeanKernel = void (*)(const float4* image, const uint32_t* tileSamples, uint32_t samples, uint32_t n, float4* mean);
 TileMeanKernel tileMeanKernel();
+// The same over a row-major width x height frame (width * height < 2^31), enqueued on `stream`: tileSamples has one count per tile of the frame's 32 x 32 grid
+void enqueueTileMeanRows(hipStream_t stream, const float4* image, const uint32_t* tileSamples, uint32_t width, uint32_t height, float4* mean);
 
 // Device buffers of one estimate: per-tile {sum, max} and {pixels, non-finite pixels}, and the row-major error map (only when a caller asks for it)
 struct NoiseWork
@@ -32,12 +34,15 @@ NoiseEstimate runNoiseEstimate(hipStream_t stream, NoiseWork& work, const float4
 
 // Which tiles an estimate covers and with what counts.  listDevice / listHost: the same ascending list of listCount tile ids (nullptr: every tile of the frame);
 // tileSamplesDevice: one sample count per tile of the frame, each >= 2 (nullptr: `samples` for all).  Both nullptr: kNoiseEstimate itself.
+// slotsBehindList: the sums are the compact tile-major buffers of a tile SHARD, and listDevice holds, behind the listCount ids, each listed tile's slot in them
+// (tile-major, a list and no per-tile counts: rf_comm_render_adaptive's estimate).
 struct TileSelection
 {
     const uint32_t* listDevice = nullptr;
     const uint32_t* listHost = nullptr;
     uint32_t        listCount = 0;
     const uint32_t* tileSamplesDevice = nullptr;
+    bool            slotsBehindList = false;
 };
 // runNoiseEstimate for a selection: the result's mean, maximum and counts are over the listed tiles (worst_tile in the frame's numbering).  tilePixels (host, one entry
 // per tile of the frame, NULL = skip): in-frame pixels.  With a list, only the listed tiles' entries of tileSum / tileMax / tilePixels and of the map are written.

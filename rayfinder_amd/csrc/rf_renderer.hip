@@ -182,7 +182,7 @@ struct Renderer::Impl
     uint32_t         rank = 0, worldSize = 1;
 
     std::vector<uint32_t>   tiles;
-    DeviceBuffer<uint32_t>  tileIds;
+    DeviceBuffer<uint32_t>  tileIds; // the tile list of the next batch: the shard's own (configureShard) or an active list (uploadTileList), and behind the ids each tile's slot in the shard
     DeviceBuffer<uint32_t>  tileValidBefore; // prefix sum of the valid pixels of the shard's tiles (numTiles + 1): kRaygen's queue positions without an atomic (FrameParams)
     bool                    optDenseRaygen = true;
     DeviceBuffer<float4>    ownedImage;
@@ -211,10 +211,15 @@ struct Renderer::Impl
     DeviceBuffer<uint32_t>  tileSamplesDevice; // the counts for the per-tile reads (mean, tonemap, estimate), uploaded by them
     DeviceBuffer<float4>    meanImage;         // rf_renderer_read_mean / the non-uniform rf_renderer_read_tonemapped: compact tile-major, allocated by the first read
 
-    bool nonUniform() const { return !tileSamples.empty(); }
+    // Under a tile shard (rf_comm_render_adaptive) the FRAME's largest and smallest tile count over all ranks, as the call's all-reduces left them on every rank:
+    // while they differ the frame is non-uniform, on a rank whose own tiles share one count too.  Both 0: no such call since the accumulation was restarted.
+    uint32_t                frameLeadingSamples = 0, frameMinTileSamples = 0;
+
+    bool nonUniform() const { return !tileSamples.empty(); } // this handle's own tiles: which form its per-tile reads take
+    bool frameNonUniform() const { return frameLeadingSamples != frameMinTileSamples; }
     void requireUniform(const char* what, const char* unless = "") const
     {
-        if (nonUniform())
+        if (nonUniform() || frameNonUniform())
             throw std::invalid_argument(std::string(what) + ": the tiles hold different sample counts after rf_renderer_render_adaptive" + unless +
                                         " (continue with render_adaptive, or restart the accumulation with rf_renderer_set_render_parameters)");
     }
@@ -400,11 +405,12 @@ struct Renderer::Impl
     void configureShard()
     {
         tiles = tilesForRank(params.width, params.height, rank, worldSize);
-        tileIds.upload(tiles.data(), tiles.size());
+        tileIds.alloc(2 * tiles.size());
         const uint64_t pixelsPadded = static_cast<uint64_t>(tiles.size()) * 1024;
         const TileGrid::Prefix valid = grid().validPrefix(tiles);
         validPixels = valid.total;
-        tileValidBefore.upload(valid.before.data(), valid.before.size());
+        tileValidBefore.alloc(valid.before.size());
+        uploadTileList(tiles, nullptr);
         if (image == nullptr || image == ownedImage.ptr)
         {
             ownedImage.alloc(std::max<uint64_t>(pixelsPadded, 1));
@@ -424,6 +430,7 @@ struct Renderer::Impl
     {
         accumulated = 0;
         tileSamples.clear();
+        frameLeadingSamples = frameMinTileSamples = 0;
         imageSums.restart();
         restartAovs();
         momentSums.restart();
@@ -540,6 +547,7 @@ struct Renderer::Impl
         uint32_t occMask;
         bool     firstLookReady; // a fact the batch mutates, as it stands for THIS batch (traceBatch / nextBatchFirstLookReady): the grid is warm and no hold-off runs
         bool     runs, tileList;
+        bool     shardList; // a tile list under a tile shard: the sums are addressed through the slots behind the ids (SumAddressing::ShardList)
         uint32_t accumulateKernel, accumulatePixels, aovPixels, momentPixels; // pixels per workgroup of the sums' launches; 0: that sum is not launched
     };
     struct BouncePlan
@@ -712,6 +720,7 @@ struct Renderer::Impl
     {
         uint32_t numTiles;
         uint64_t validPixels;
+        bool     shardSlots; // the sums are addressed through the slots behind the ids (rf_comm_render_adaptive: the handle's sums are compact over its shard)
     };
     // The once-per-batch decisions, for a batch of numSamples samples of the shard's tiles (or of the `active` list of render_adaptive)
     BatchPlan planBatch(uint32_t numSamples, const ActiveTiles* active) const
@@ -747,6 +756,7 @@ struct Renderer::Impl
         // `pixelsPerGroup` pixels); else one thread per pixel
         b.runs = optSlotGroupShift == 0u && numSamples > 4u && optAccumulateRuns;
         b.tileList = active != nullptr;
+        b.shardList = b.tileList && active->shardSlots;
         const uint32_t perThread = static_cast<uint32_t>(kBlock);
         if (b.tileList) b.accumulateKernel = kAccumulateTiles, b.accumulatePixels = b.runs ? kMomentPixels : perThread;
         else if (b.runs && numSamples <= kAccMaxSamples)
@@ -981,12 +991,15 @@ struct Renderer::Impl
         return meanImage.ptr;
     }
 
-    // tileIds / tileValidBefore <- a list of tile ids (ascending) of the whole frame.  The stream must be idle (the copies are synchronous).  -> pixels inside the frame
-    uint64_t uploadTileList(const std::vector<uint32_t>& list)
+    // tileIds / tileValidBefore <- a list of tile ids (ascending) of the shard's tiles and, behind the ids, their slots in the shard (slots == nullptr: 0, 1, ...: the
+    // shard's own list).  The stream must be idle (the copies are synchronous).  -> pixels inside the frame
+    uint64_t uploadTileList(const std::vector<uint32_t>& list, const std::vector<uint32_t>* slots)
     {
         const auto [before, valid] = grid().validPrefix(list);
-        if (list.size() > tileIds.count || before.size() > tileValidBefore.count) throw std::logic_error("tile list longer than the frame's");
-        if (!list.empty()) RF_HIP(hipMemcpy(tileIds.ptr, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        if (2 * list.size() > tileIds.count || before.size() > tileValidBefore.count || (slots && slots->size() != list.size())) throw std::logic_error("tile list longer than the shard's");
+        std::vector<uint32_t> both(list);
+        for (uint32_t k = 0; k < list.size(); ++k) both.push_back(slots ? (*slots)[k] : k);
+        if (!both.empty()) RF_HIP(hipMemcpy(tileIds.ptr, both.data(), both.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         RF_HIP(hipMemcpy(tileValidBefore.ptr, before.data(), before.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         return valid;
     }
@@ -1077,14 +1090,15 @@ struct Renderer::Impl
         const auto sumGrid = [&](uint32_t pixelsPerGroup) { return dim3((fp.pixelsPadded + pixelsPerGroup - 1) / pixelsPerGroup); };
         SumLaunch  launches[3];
         uint32_t   n = 0;
+        const SumAddressing listAddressing = b.shardList ? SumAddressing::ShardList : SumAddressing::TileList;
         // (the headline image kernel, the whole runs in dynamic LDS, keeps its own argument list: rf_sums.hip)
         if (b.accumulateKernel == kAccumulateRuns)
             hipLaunchKernelGGL(accumulateRunsKernel(b.accumulatePixels), sumGrid(b.accumulatePixels), dim3(64), b.accumulatePixels * 3u * (b.numSamples + 1u) * sizeof(float), stream, fp,
                                tileIds.ptr, ps, image);
-        else if (b.accumulateKernel == kAccumulateTiles) launches[n++] = {sumKernel(Sum::RadianceMoments, b.runs, true), b.accumulatePixels, b.runs, ps.rad, image, moments()};
-        else launches[n++] = {sumKernel(Sum::Radiance, false, false), b.accumulatePixels, false, ps.rad, image, nullptr};
-        if (b.aovPixels != 0u) launches[n++] = {sumKernel(Sum::Aov, b.runs, b.tileList), b.aovPixels, b.runs, sAov.ptr, aovAlbedoCoverage(), aovNormalDepth()};
-        if (b.momentPixels != 0u) launches[n++] = {sumKernel(Sum::Moments, b.runs, false), b.momentPixels, b.runs, ps.rad, moments(), nullptr};
+        else if (b.accumulateKernel == kAccumulateTiles) launches[n++] = {sumKernel(Sum::RadianceMoments, b.runs, listAddressing), b.accumulatePixels, b.runs, ps.rad, image, moments()};
+        else launches[n++] = {sumKernel(Sum::Radiance, false, SumAddressing::Compact), b.accumulatePixels, false, ps.rad, image, nullptr};
+        if (b.aovPixels != 0u) launches[n++] = {sumKernel(Sum::Aov, b.runs, b.tileList ? listAddressing : SumAddressing::Compact), b.aovPixels, b.runs, sAov.ptr, aovAlbedoCoverage(), aovNormalDepth()};
+        if (b.momentPixels != 0u) launches[n++] = {sumKernel(Sum::Moments, b.runs, SumAddressing::Compact), b.momentPixels, b.runs, ps.rad, moments(), nullptr};
         for (uint32_t i = 0; i < n; ++i)
         {
             const SumLaunch& l = launches[i];
@@ -1709,36 +1723,64 @@ NoiseEstimate Renderer::noiseEstimate(float* errorMap, float* tileSum, float* ti
     return runNoiseEstimate(m.stream, m.noiseWork, m.image, m.moments(), m.params.width, m.params.height, true, m.accumulated, errorMap, tileSum, tileMax);
 }
 
-AdaptiveResult Renderer::renderAdaptive(const AdaptiveParameters& p)
+// What rf_renderer_render_adaptive and rf_comm_render_adaptive check alike before anything is traced (or exchanged)
+void Renderer::checkAdaptive(const AdaptiveParameters& p) const
 {
-    Impl& m = *mImpl;
+    const Impl& m = *mImpl;
     if (!m.momentSums.on) throw std::invalid_argument("render_adaptive needs the radiance second moments: turn them on (rf_renderer_set_moments) before the first sample");
     if (m.aovSums.on && !m.aovTileCounts())
         throw std::invalid_argument("render_adaptive: the first-hit AOVs are on without RF_AOV_TILE_COUNTS (their sums and the denoiser then keep ONE sample count): set "
                                     "RF_AOV_FIRST_HIT | RF_AOV_TILE_COUNTS before the first sample, or turn the AOVs off");
-    if (m.worldSize != 1u) throw std::invalid_argument("render_adaptive needs the whole frame: a tile shard is set");
     if (p.checkEvery == 0u) throw std::invalid_argument("render_adaptive: check_every must be >= 1");
     if (!std::isfinite(p.targetTileError) || p.targetTileError < 0.0f) throw std::invalid_argument("render_adaptive: target_tile_error must be finite and >= 0");
     if (m.accumulated != 0u && !m.momentSums.covers(m.accumulated))
         throw std::invalid_argument("render_adaptive: the moments do not cover the accumulation (turned on partway through): restart the accumulation first");
     if (m.aovSums.on && m.accumulated != 0u && !m.aovSums.covers(m.accumulated))
         throw std::invalid_argument("render_adaptive: the AOV sample count does not cover the accumulation (the AOVs were turned on partway through): restart the accumulation first");
+}
+
+AdaptiveResult Renderer::renderAdaptive(const AdaptiveParameters& p)
+{
+    Impl& m = *mImpl;
+    // (the order of the checks, and so which message a call with several faults gets, is the one this call always had)
+    if (!m.momentSums.on || (m.aovSums.on && !m.aovTileCounts())) checkAdaptive(p);
+    if (m.worldSize != 1u) throw std::invalid_argument("render_adaptive needs the whole frame: a tile shard is set (rf_comm_render_adaptive samples a sharded frame adaptively)");
+    checkAdaptive(p);
+    return renderAdaptiveFrom(p, m.accumulated, false);
+}
+
+// The loop of rf_renderer_render_adaptive over the handle's own tiles -- the whole frame, or a tile shard -- with `leading` the frame's leading count: the handle's
+// accumulated count, or under a shard the largest over all ranks.  A tile is numbered twice here: its SLOT k in the shard (where its sums and its count
+// live) and its frame id m.tiles[k] (coordinates, the estimate's per-tile outputs); without a shard the two are equal, and shardSlots == false keeps the kernels that
+// take the id for the slot (rf_renderer_render_adaptive's, as ever).  rf_comm_render_adaptive passes true at every world size, 1 included.
+AdaptiveResult Renderer::renderAdaptiveFrom(const AdaptiveParameters& p, uint32_t leading, bool shardSlots)
+{
+    if (!shardSlots && mImpl->worldSize != 1u) throw std::logic_error("a tile shard's sums are addressed by slot");
+    Impl& m = *mImpl;
     RF_HIP(hipSetDevice(m.device));
     const uint32_t spp = m.params.samplingParams.numSamplesPerPixel;
     const uint32_t cap = p.maxSamples == 0u ? spp : std::min(p.maxSamples, spp);
-    const uint32_t numTiles = static_cast<uint32_t>(m.tiles.size());
+    const uint32_t numTiles = static_cast<uint32_t>(m.tiles.size()), frameTiles = m.grid().count();
     const uint32_t firstCheck = std::max(2u, p.minSamples);
+    const auto     pixelSamples = [&](const std::vector<uint32_t>& counts) {
+        uint64_t n = 0;
+        for (uint32_t k = 0; k < numTiles; ++k) n += static_cast<uint64_t>(m.grid().pixelsInFrame(m.tiles[k])) * counts[k];
+        return n;
+    };
 
-    // the counts as a vector for the length of the call (the uniform state: every tile at the accumulated count); the tiles at the leading count are the active ones
+    // the counts (by slot) as a vector for the length of the call (the uniform state: every tile at the accumulated count); the tiles at the leading count are the
+    // active ones -- none on a rank whose tiles all stopped below the frame's leading count
     std::vector<uint32_t> counts = m.nonUniform() ? m.tileSamples : std::vector<uint32_t>(numTiles, m.accumulated);
-    std::vector<uint32_t> active;
-    for (uint32_t t = 0; t < numTiles; ++t)
-        if (counts[t] == m.accumulated) active.push_back(t);
+    std::vector<uint32_t> active, activeIds; // slots; their frame ids
+    for (uint32_t k = 0; k < numTiles; ++k)
+        if (counts[k] == leading) active.push_back(k);
+    const uint64_t pixelSamplesBefore = pixelSamples(counts);
+    const uint32_t frameCountBefore = m.frameCount;
 
     AdaptiveResult        out;
-    std::vector<float>    sums(numTiles);
-    std::vector<uint32_t> pixels(numTiles);
-    // tileIds / tileValidBefore hold the active list while it is shorter than the frame's; whatever happens, they hold the frame's list again afterwards
+    std::vector<float>    sums(frameTiles);
+    std::vector<uint32_t> pixels(frameTiles);
+    // tileIds / tileValidBefore hold the active list while it is shorter than the shard's; whatever happens, they hold the shard's list again afterwards
     struct Restore
     {
         Impl& m;
@@ -1747,11 +1789,17 @@ AdaptiveResult Renderer::renderAdaptive(const AdaptiveParameters& p)
         {
             if (!armed) return;
             (void)hipStreamSynchronize(m.stream);
-            try { m.uploadTileList(m.tiles); } catch (...) {}
+            try { m.uploadTileList(m.tiles, nullptr); } catch (...) {}
         }
     } restore{m};
-    Impl::ActiveTiles list{numTiles, m.validPixels};
+    Impl::ActiveTiles list{numTiles, m.validPixels, shardSlots};
     bool              listStale = active.size() != numTiles;
+    const auto        idsOf = [&](const std::vector<uint32_t>& slots) {
+        std::vector<uint32_t> ids;
+        for (const uint32_t k : slots) ids.push_back(m.tiles[k]);
+        return ids;
+    };
+    activeIds = idsOf(active);
     while (!active.empty() && m.accumulated < cap)
     {
         const uint64_t pixelsPadded = static_cast<uint64_t>(active.size()) * 1024;
@@ -1759,43 +1807,74 @@ AdaptiveResult Renderer::renderAdaptive(const AdaptiveParameters& p)
         {
             RF_HIP(hipStreamSynchronize(m.stream));
             restore.armed = true;
-            list = Impl::ActiveTiles{static_cast<uint32_t>(active.size()), m.uploadTileList(active)};
+            list = Impl::ActiveTiles{static_cast<uint32_t>(active.size()), m.uploadTileList(activeIds, &active), shardSlots};
             listStale = false;
         }
         m.clearStaleSums(static_cast<uint64_t>(numTiles) * 1024);
         uint32_t remaining = std::min(p.checkEvery, cap - m.accumulated);
         while (remaining > 0) remaining -= m.step(remaining, pixelsPadded, &list);
-        for (const uint32_t t : active) counts[t] = m.accumulated;
+        for (const uint32_t k : active) counts[k] = m.accumulated;
         m.tileSamples = counts; // (non-uniform from here on, should an estimate throw; settled below)
         if (m.accumulated < firstCheck) continue;
-        // the active tiles' estimate, Nf = float(L) for all of them; tileIds holds the list (the frame's own while every tile is active)
+        // the active tiles' estimate, Nf = float(L) for all of them; tileIds holds the list (the shard's own while every tile is active)
         TileSelection sel;
-        sel.listDevice = m.tileIds.ptr, sel.listHost = active.data(), sel.listCount = static_cast<uint32_t>(active.size());
+        sel.listDevice = m.tileIds.ptr, sel.listHost = activeIds.data(), sel.listCount = static_cast<uint32_t>(active.size());
+        sel.slotsBehindList = shardSlots;
         out.last = runNoiseEstimateTiles(m.stream, m.noiseWork, m.image, m.moments(), m.params.width, m.params.height, true, sel, m.accumulated, nullptr, sums.data(), nullptr,
                                          pixels.data());
         ++out.estimatePasses;
         std::vector<uint32_t> still;
-        for (const uint32_t t : active)
-            if (!(sums[t] / static_cast<float>(pixels[t]) <= p.targetTileError)) still.push_back(t); // (NaN: never <=, the tile goes on)
+        for (const uint32_t k : active)
+            if (!(sums[m.tiles[k]] / static_cast<float>(pixels[m.tiles[k]]) <= p.targetTileError)) still.push_back(k); // (NaN: never <=, the tile goes on)
         if (still.size() != active.size()) listStale = true;
         active.swap(still);
+        activeIds = idsOf(active);
     }
     RF_HIP(hipStreamSynchronize(m.stream)); // (waits for the work it enqueued, as render_until does)
 
     out.tiles = numTiles;
     out.minTileSamples = out.maxTileSamples = numTiles ? counts[0] : 0u;
-    for (uint32_t t = 0; t < numTiles; ++t)
+    for (uint32_t k = 0; k < numTiles; ++k)
     {
-        out.minTileSamples = std::min(out.minTileSamples, counts[t]), out.maxTileSamples = std::max(out.maxTileSamples, counts[t]);
-        if (counts[t] != m.accumulated) ++out.stoppedTiles;
-        out.pixelSamples += static_cast<uint64_t>(m.grid().pixelsInFrame(m.tiles[t])) * counts[t];
+        out.minTileSamples = std::min(out.minTileSamples, counts[k]), out.maxTileSamples = std::max(out.maxTileSamples, counts[k]);
+        if (counts[k] != m.accumulated) ++out.stoppedTiles;
     }
-    if (out.stoppedTiles == 0u) m.tileSamples.clear(); // every tile at the leading count: the ordinary state
+    out.pixelSamples = pixelSamples(counts);
+    out.tracedPixelSamples = out.pixelSamples - pixelSamplesBefore;
+    out.framesTraced = m.frameCount - frameCountBefore;
+    if (out.stoppedTiles == 0u) m.tileSamples.clear(); // every tile of the handle at its leading count: its per-tile reads take the ordinary form
     else m.tileSamples = counts;
     return out;
 }
 
-bool Renderer::tileSamplesUniform() const { return !mImpl->nonUniform(); }
+void Renderer::setFrameTileSamples(uint32_t leading, uint32_t minimum)
+{
+    mImpl->frameLeadingSamples = leading, mImpl->frameMinTileSamples = minimum;
+}
+void     Renderer::skipFrames(uint32_t numFrames) { mImpl->frameCount += numFrames; }
+
+uint32_t Renderer::shardTilesBelow(uint32_t count) const
+{
+    const Impl& m = *mImpl;
+    uint32_t    n = 0;
+    for (size_t k = 0; k < m.tiles.size(); ++k) n += (m.nonUniform() ? m.tileSamples[k] : m.accumulated) < count ? 1u : 0u;
+    return n;
+}
+
+const uint32_t* Renderer::shardTileSamplesDevice()
+{
+    Impl& m = *mImpl;
+    RF_HIP(hipSetDevice(m.device));
+    if (m.nonUniform()) return m.uploadTileSamples();
+    // the ordinary form: every tile of the shard at the accumulated count
+    const std::vector<uint32_t> counts(m.tiles.size(), m.accumulated);
+    RF_HIP(hipStreamSynchronize(m.stream));
+    if (m.tileSamplesDevice.count < counts.size()) m.tileSamplesDevice.alloc(counts.size());
+    if (!counts.empty()) RF_HIP(hipMemcpy(m.tileSamplesDevice.ptr, counts.data(), counts.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return m.tileSamplesDevice.ptr;
+}
+
+bool Renderer::tileSamplesUniform() const { return !mImpl->nonUniform() && !mImpl->frameNonUniform(); }
 void Renderer::requireUniformTileSamples(const char* what) const { mImpl->requireUniform(what); }
 
 uint32_t Renderer::readTileSamples(uint32_t* tileSamples) const
@@ -1821,9 +1900,9 @@ uint32_t Renderer::renderUntil(float targetMeanError, uint32_t checkEvery, uint3
 {
     Impl& m = *mImpl;
     if (!m.momentSums.on) throw std::invalid_argument("render_until needs the radiance second moments: turn them on (rf_renderer_set_moments) before the first sample");
+    m.requireUniform("rf_renderer_render_until"); // (first: under a tile shard this is the state rf_comm_render_adaptive left)
     if (m.worldSize != 1u) throw std::invalid_argument("render_until needs the whole frame: a tile shard is set");
     if (checkEvery == 0u) throw std::invalid_argument("render_until: check_every must be >= 1");
-    m.requireUniform("rf_renderer_render_until");
     if (m.accumulated != 0u && !m.momentSums.covers(m.accumulated))
         throw std::invalid_argument("render_until: the moments do not cover the accumulation (turned on partway through): restart the accumulation first");
     const uint32_t spp = m.params.samplingParams.numSamplesPerPixel;

@@ -184,6 +184,8 @@ struct AdaptiveResult
     uint32_t      tiles = 0, stoppedTiles = 0; // stopped: tiles below the leading count
     uint32_t      minTileSamples = 0, maxTileSamples = 0;
     uint64_t      pixelSamples = 0;            // sum over the tiles of in-frame pixels x sample count
+    uint64_t      tracedPixelSamples = 0;      // of those, the ones this call traced
+    uint32_t      framesTraced = 0;            // how far the call moved the handle's frame counter
     NoiseEstimate last;                        // the last pass's estimate, over the tiles that were active in it (samples = 0: no pass was made)
 };
 
@@ -253,6 +255,23 @@ public:
     // std::invalid_argument when the moments are off or do not cover the accumulation, the AOVs are on without kAovTileCounts or do not cover it, a tile shard is set,
     // checkEvery is 0 or the target is negative or not finite.
     AdaptiveResult renderAdaptive(const AdaptiveParameters& params);
+    // The same over a tile shard, one rank's part of rf_comm_render_adaptive (rf_c_api.cpp makes the exchanges around it).  checkAdaptive: renderAdaptive's checks but
+    // the shard's, throwing before anything is traced -- there, before the first collective.  renderAdaptiveFrom: the loop over this handle's tiles with `leading` the
+    // FRAME's leading count (the largest accumulated count over the ranks): the active tiles are those at `leading` -- none when this handle's own count is lower -- and
+    // the result speaks of this handle's tiles (stoppedTiles: below its own accumulated count); shardSlots: the sums are addressed through each listed tile's slot in the
+    // shard (always so through rf_comm_render_adaptive, at world size 1 as well).  setFrameTileSamples: the frame's largest and smallest tile count after
+    // the call, the same on every rank; while they differ the handle is in the non-uniform state (requireUniformTileSamples) whatever its own tiles hold.  Cleared with
+    // the accumulation.
+    void           checkAdaptive(const AdaptiveParameters& params) const;
+    AdaptiveResult renderAdaptiveFrom(const AdaptiveParameters& params, uint32_t leading, bool shardSlots);
+    void           setFrameTileSamples(uint32_t leading, uint32_t minimum);
+    // Advance the frame counter without tracing: a rank whose tiles all stopped while the frame's leading tiles went on stays in step with them -- the next sample
+    // any rank traces (after a restart of the accumulation too) is the one a handle without a shard would trace
+    void           skipFrames(uint32_t numFrames);
+    uint32_t       shardTilesBelow(uint32_t count) const;
+    // The counts of the shard's tiles in slot order (the order of shardTiles()) in device memory, for the frame gather; waits for the stream.  Valid until the next
+    // per-tile read or gather of this handle.
+    const uint32_t* shardTileSamplesDevice();
     bool           tileSamplesUniform() const;
     void           requireUniformTileSamples(const char* what) const;
     // one count per tile of the frame's grid (tile_y * ceil(width / 32) + tile_x); a tile outside this rank's shard: 0.  -> the number of tiles

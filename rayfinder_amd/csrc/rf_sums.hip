@@ -1,6 +1,6 @@
 // rf_sums.hip -- the per-pixel sums in sample order (rf_sums.hpp): the image S, the radiance second moments Q and the two first-hit AOV sums, from the per-slot
 // records a batch leaves (the radiance stream ps.rad; kShade<false, true>'s AOV records of bounce 1).  The trace and shading kernels do not know about them.
-//   kSumPixels<Sum, TILE_LIST>   one lane per pixel, any slot order
+//   kSumPixels<Sum, TILE_LIST>   one lane per pixel, any slot order                         (Sum = ShardList<...>: the tile list of a tile shard, see sumIndex)
 //   kSumRuns<Sum, TILE_LIST>     pixel-major slot order: a 64-lane workgroup stages its pixels' runs in LDS in 32-sample chunks, one summing lane per (pixel, channel)
 //   kAccumulateRuns<PIXELS>      pixel-major slot order, the image alone: the WHOLE runs of PIXELS pixels in dynamic LDS (the headline path, profiles/r06_raygen)
 // What is summed is a policy struct (below); where a pixel's sums live is sumIndex.  The contract all three keep: each channel of each sum is one dependent chain of
@@ -12,12 +12,26 @@ namespace rf
 {
 namespace
 {
-// Where the sums of local pixel lp live: the ONLY place that knows.  Shard-compact: at lp.  TILE_LIST: the batch's path slots belong to the fp.numTiles tiles that
-// tileIds lists (lp = list position * 1024 + pixel of the tile), the sums hold the whole frame, compact slot == tile id.
-template<bool TILE_LIST>
-__device__ __forceinline__ size_t sumIndex(const uint32_t* tileIds, uint32_t lp)
+// ShardList<SUM>: the sum SUM under a tile list of a handle WITH a tile shard (rf_comm_render_adaptive).  The handle's sums are then compact over the shard, so a listed
+// tile has two numbers: its frame tile id tileIds[k], which the pixel coordinates come from, and its SLOT in the shard, tileIds[numTiles + k] -- the host uploads the
+// slots behind the ids.  A wrapper of the policy and not a third template parameter of the kernels, so that the kernels compiled before it keep their names.
+template<class SUM>
+struct ShardList : SUM
 {
-    return TILE_LIST ? static_cast<size_t>(tileIds[lp >> 10]) * 1024u + (lp & 1023u) : lp;
+};
+template<class SUM>
+constexpr bool kShardList = false;
+template<class SUM>
+constexpr bool kShardList<ShardList<SUM>> = true;
+
+// Where the sums of local pixel lp live: the ONLY place that knows.  Shard-compact: at lp.  TILE_LIST: the batch's path slots belong to the numTiles tiles that
+// tileIds lists (lp = list position * 1024 + pixel of the tile); the sums hold the whole frame, compact slot == tile id -- or, SUM = ShardList<...>, the shard, at the
+// slots listed behind the ids.
+template<class SUM, bool TILE_LIST>
+__device__ __forceinline__ size_t sumIndex(const uint32_t* tileIds, uint32_t numTiles, uint32_t lp)
+{
+    static_assert(TILE_LIST || !kShardList<SUM>, "a shard's slot list is a tile list");
+    return TILE_LIST ? static_cast<size_t>(tileIds[(kShardList<SUM> ? numTiles : 0u) + (lp >> 10)]) * 1024u + (lp & 1023u) : lp;
 }
 // A pixel's running sums are the eight floats {dst0[at].xyzw, dst1[at].xyzw}: term i of channel c is float c + 4 i of them
 __device__ __forceinline__ float* sumFloat(float4* dst0, float4* dst1, size_t at, uint32_t f) { return reinterpret_cast<float*>((f < 4u ? dst0 : dst1) + at) + (f & 3u); }
@@ -84,7 +98,7 @@ __global__ __launch_bounds__(kBlock) void kSumPixels(FrameParams fp, const uint3
     if (lp >= fp.pixelsPadded) return;
     uint32_t x, y;
     if (!localPixelToXY(fp, tileIds, lp, x, y)) return;
-    const size_t at = sumIndex<TILE_LIST>(tileIds, lp);
+    const size_t at = sumIndex<SUM, TILE_LIST>(tileIds, fp.numTiles, lp);
     float4       sum[kSumBuffers<SUM>]; // the pixel's running sums: float c + 4 i of them is term i of channel c (sumFloat)
 #pragma unroll
     for (uint32_t d = 0; d < kSumBuffers<SUM>; ++d) sum[d] = (d == 0u ? dst0 : dst1)[at];
@@ -120,7 +134,7 @@ __global__ __launch_bounds__(64) void kSumRuns(FrameParams fp, const uint32_t* t
     const uint32_t px = lane / C, c = lane - C * px, lp = lp0 + px;
     uint32_t       x, y;
     const bool     sums = lane < PIXELS * C && lp < fp.pixelsPadded && localPixelToXY(fp, tileIds, lp, x, y); // (pixels outside the frame: staged, never summed)
-    const size_t   at = sums ? sumIndex<TILE_LIST>(tileIds, lp) : 0u;
+    const size_t   at = sums ? sumIndex<SUM, TILE_LIST>(tileIds, fp.numTiles, lp) : 0u;
     float          acc[SUM::kTerms];
 #pragma unroll
     for (uint32_t i = 0; i < SUM::kTerms; ++i) acc[i] = sums ? *sumFloat(dst0, dst1, at, c + 4u * i) : 0.0f;
@@ -214,8 +228,15 @@ __global__ __launch_bounds__(64) void kAccumulateRuns(FrameParams fp, const uint
 }
 } // namespace
 
-SumKernel sumKernel(Sum sum, bool runs, bool tileList)
+SumKernel sumKernel(Sum sum, bool runs, SumAddressing addressing)
 {
+    const bool tileList = addressing == SumAddressing::TileList;
+    if (addressing == SumAddressing::ShardList)
+    {
+        if (sum == Sum::RadianceMoments) return runs ? kSumRuns<ShardList<RadianceMomentSum>, true> : kSumPixels<ShardList<RadianceMomentSum>, true>;
+        if (sum == Sum::Aov) return runs ? kSumRuns<ShardList<AovSum>, true> : kSumPixels<ShardList<AovSum>, true>;
+        throw std::logic_error("sumKernel: no such kernel is compiled");
+    }
     if (sum == Sum::Radiance && !runs && !tileList) return kSumPixels<RadianceSum, false>;
     if (sum == Sum::Moments && !tileList) return runs ? kSumRuns<MomentSum, false> : kSumPixels<MomentSum, false>;
     if (sum == Sum::RadianceMoments && tileList) return runs ? kSumRuns<RadianceMomentSum, true> : kSumPixels<RadianceMomentSum, true>;

@@ -18,17 +18,25 @@ enum class Sum : uint32_t
 };
 // src: the batch's per-slot records; dst0 / dst1: the handle's sums, compact tile-major (dst1 unused by the sums that have one buffer).  The sums of local pixel lp
 // sit at lp -- or, tileList (rf_renderer_render_adaptive: the batch's path slots belong to the fp.numTiles tiles that tileIds lists, the sums hold the WHOLE frame,
-// compact slot == tile id), at tileIds[lp >> 10] * 1024 + (lp & 1023).  The sums of pixels outside the frame are neither read nor written.
+// compact slot == tile id), at tileIds[lp >> 10] * 1024 + (lp & 1023) -- or, shardList (rf_comm_render_adaptive: the same under a tile shard, the sums hold the
+// SHARD; tileIds holds the fp.numTiles listed tile ids and behind them the tiles' slots in the shard), at tileIds[fp.numTiles + (lp >> 10)] * 1024 + (lp & 1023).
+// The sums of pixels outside the frame are neither read nor written.
 using SumKernel = void (*)(FrameParams fp, const uint32_t* tileIds, const float4* src, float4* dst0, float4* dst1);
 
 // runs: the LDS-staged kernel for the pixel-major slot order (slotGroupShift 0), a 64-lane workgroup per kMomentPixels (Moments, RadianceMoments) or kAovPixels (Aov)
 // pixels, their runs staged in chunks of 32 samples: (pixels x channels) rows of (32 + 1) floats = 6 336 B / 8 448 B of LDS at any batch depth (<= ~8 KB keeps twenty
 // workgroups resident per CU, profiles/r06_raygen).  Else one lane per pixel, kBlock pixels per workgroup, any slot order.
 // Compiled: Radiance (one lane per pixel; its staged kernel is accumulateRunsKernel) and Moments with shard-compact addressing, RadianceMoments with a tile list, Aov
-// with both; anything else throws.
+// with both, RadianceMoments and Aov with a shard's slot list; anything else throws.
 constexpr uint32_t kMomentPixels = 16, kMomentChunk = 32;
 constexpr uint32_t kAovPixels = 8, kAovChunk = 32;
-SumKernel sumKernel(Sum sum, bool runs, bool tileList);
+enum class SumAddressing : uint32_t
+{
+    Compact,   // the sums of local pixel lp at lp
+    TileList,  // a tile list over a whole-frame handle
+    ShardList, // a tile list over a tile shard: ids, then slots
+};
+SumKernel sumKernel(Sum sum, bool runs, SumAddressing addressing);
 
 // Radiance, pixel-major slot order, the WHOLE run in LDS: pixelsPerWorkgroup (1, 2 or kAccPixels) x 3 x (numSamples + 1) floats of dynamic LDS, numSamples <= kAccMaxSamples;
 // the image sits at lp (no tile list).  Its source is ps.rad
