@@ -127,6 +127,13 @@ rf_noise_estimate toNoiseEstimate(const rf::NoiseEstimate& e)
 {
     return rf_noise_estimate{e.meanError, e.maxError, e.worstTile, e.samples, e.pixels, e.nonfinitePixels};
 }
+
+rf::AdaptiveParameters toAdaptiveParams(const rf_adaptive_parameters& p) { return rf::AdaptiveParameters{p.target_tile_error, p.check_every, p.min_samples, p.max_samples}; }
+
+rf_adaptive_result toAdaptiveResult(const rf::AdaptiveResult& a)
+{
+    return rf_adaptive_result{a.estimatePasses, a.tiles, a.stoppedTiles, a.minTileSamples, a.maxTileSamples, 0u, a.pixelSamples, toNoiseEstimate(a.last)};
+}
 } // namespace
 
 extern "C" {
@@ -397,9 +404,8 @@ int rf_renderer_render_adaptive(rf_renderer* r, const rf_adaptive_parameters* pa
 {
     return guarded([&] {
         require(r && params, "null argument");
-        const rf::AdaptiveResult a = r->impl->renderAdaptive(rf::AdaptiveParameters{params->target_tile_error, params->check_every, params->min_samples, params->max_samples});
-        if (result)
-            *result = rf_adaptive_result{a.estimatePasses, a.tiles, a.stoppedTiles, a.minTileSamples, a.maxTileSamples, 0u, a.pixelSamples, toNoiseEstimate(a.last)};
+        const rf::AdaptiveResult a = r->impl->renderAdaptive(toAdaptiveParams(*params));
+        if (result) *result = toAdaptiveResult(a);
         return RF_OK;
     });
 }
@@ -610,42 +616,7 @@ int rf_renderer_gather_frame(rf_renderer* r, rf_comm* c, uint32_t root, uint32_t
 {
     return guarded([&] {
         require(r && c, "null argument");
-        require(root < c->impl->worldSize(), "gather root out of range");
-        require(r->impl->shardRank() == c->impl->rank() && r->impl->shardWorldSize() == c->impl->worldSize(),
-                "the renderer's tile shard differs from the communicator's rank / world size (call rf_renderer_set_tile_shard first)");
-        // the exchange is enqueued on the renderer's stream with the communicator's device current: they must be one device
-        require(r->impl->deviceOrdinal() == c->impl->deviceOrdinal(), "the renderer and the communicator are on different devices");
-        if (!(flags & RF_GATHER_TILE_COUNTS)) r->impl->requireUniformTileSamples("rf_renderer_gather_frame"); // (such an exchange carries no per-tile counts)
-        // the extra planes: a sum travels only when it holds exactly the accumulated samples (a rank whose shard has no tile has nothing to send and nothing to check
-        // but the switch).  Refused before anything is enqueued or cleared.
-        rf::Renderer&  h = *r->impl;
-        const bool     ownsTiles = !h.shardTiles().empty();
-        const uint32_t n = h.accumulatedSampleCount();
-        uint32_t       planeMask = rf::kPlaneMaskImage;
-        if (flags & RF_GATHER_AOVS)
-        {
-            require(h.aovFlags() != 0u, "rf_renderer_gather_frame: RF_GATHER_AOVS needs the first-hit AOVs: turn them on (rf_renderer_set_aovs) before the first sample");
-            require(!ownsTiles || n != 0u, "rf_renderer_gather_frame: RF_GATHER_AOVS: no sample has been accumulated");
-            if (ownsTiles && !h.aovsCoverAccumulation())
-                throw std::invalid_argument("rf_renderer_gather_frame: RF_GATHER_AOVS: the AOV sample count (" + std::to_string(h.aovSampleCount()) +
-                                            ") differs from the accumulated sample count (" + std::to_string(n) + "): turn the AOVs on before the first sample");
-            planeMask |= rf::kPlaneMaskAovs;
-        }
-        if (flags & RF_GATHER_MOMENTS)
-        {
-            require(h.momentsEnabled(), "rf_renderer_gather_frame: RF_GATHER_MOMENTS needs the radiance second moments: turn them on (rf_renderer_set_moments) before the first sample");
-            require(!ownsTiles || n != 0u, "rf_renderer_gather_frame: RF_GATHER_MOMENTS: no sample has been accumulated");
-            if (ownsTiles && !h.momentsCoverAccumulation())
-                throw std::invalid_argument("rf_renderer_gather_frame: RF_GATHER_MOMENTS: the moment sample count (" + std::to_string(h.momentSampleCount()) +
-                                            ") differs from the accumulated sample count (" + std::to_string(n) + "): turn the moments on before the first sample");
-            planeMask |= rf::kPlaneMaskMoments;
-        }
-        h.clearAccumulationIfStale(); // nothing rendered since the last reset: send zeros, not the previous frame
-        // the shard's per-tile counts, in slot order, from device memory (the ordinary state: every tile at the accumulated count)
-        const uint32_t* counts = nullptr;
-        if (flags & RF_GATHER_TILE_COUNTS) planeMask |= rf::kGatherMaskTileCounts, counts = h.shardTileSamplesDevice();
-        const void* const planes[rf::kGatherPlanes] = {h.accumulationDevicePointer(), h.aovAlbedoCoverageDevicePointer(), h.aovNormalDepthDevicePointer(), h.momentsDevicePointer()};
-        const void*       image = c->impl->gatherPlanes(planes, planeMask, n, h.width(), h.height(), root, h.streamHandle(), (flags & RF_GATHER_LOOPBACK) != 0, counts);
+        const void* image = rf::gatherFrame(*r->impl, *c->impl, root, flags);
         if (image_device_out) *image_device_out = const_cast<void*>(image);
         return RF_OK;
     });
@@ -755,32 +726,9 @@ int rf_comm_read_mean(rf_comm* c, rf_renderer* r, float* rgba)
 int rf_comm_render_adaptive(rf_comm* c, rf_renderer* r, const rf_adaptive_parameters* params, rf_comm_adaptive_result* result)
 {
     return guarded([&] {
-        // every refusal comes before the first collective: a refused rank leaves no peer waiting as long as the ranks pass the same arguments
         require(c && r && params, "null argument");
-        rf::Renderer&                h = *r->impl;
-        rf::TileComm&                comm = *c->impl;
-        const rf::AdaptiveParameters p{params->target_tile_error, params->check_every, params->min_samples, params->max_samples};
-        h.checkAdaptive(p);
-        require(h.shardRank() == comm.rank() && h.shardWorldSize() == comm.worldSize(),
-                "the renderer's tile shard differs from the communicator's rank / world size (call rf_renderer_set_tile_shard first)");
-        require(h.deviceOrdinal() == comm.deviceOrdinal(), "the renderer and the communicator are on different devices");
-        void* const stream = h.streamHandle();
-        // the frame's leading count: the largest accumulated count of any rank.  From here the loop is this rank's own: a tile's stop reads its own sums alone
-        const uint32_t           leading = static_cast<uint32_t>(comm.allReduceMax(static_cast<double>(h.accumulatedSampleCount()), stream));
-        const rf::AdaptiveResult a = h.renderAdaptiveFrom(p, leading, true);
-        // the frame's figures (exact in a double; a minimum as the maximum of the negated value; a rank without a tile has no minimum to offer)
-        const double noTile = -4294967296.0;
-        const auto   frameLeading = static_cast<uint32_t>(comm.allReduceMax(a.tiles ? static_cast<double>(a.maxTileSamples) : 0.0, stream));
-        const auto   frameMin = static_cast<uint32_t>(-comm.allReduceMax(a.tiles ? -static_cast<double>(a.minTileSamples) : noTile, stream));
-        const auto   busiest = static_cast<uint64_t>(comm.allReduceMax(static_cast<double>(a.tracedPixelSamples), stream));
-        h.setFrameTileSamples(frameLeading, frameMin);
-        // the frame's leading tiles moved the frame counter of the ranks that hold them by frameLeading - leading; a rank that stopped earlier, or never started, follows
-        h.skipFrames(frameLeading - leading - a.framesTraced);
-        if (result)
-        {
-            result->rank = rf_adaptive_result{a.estimatePasses, a.tiles, h.shardTilesBelow(frameLeading), a.minTileSamples, a.maxTileSamples, 0u, a.pixelSamples, toNoiseEstimate(a.last)};
-            result->frame_leading_samples = frameLeading, result->frame_min_tile_samples = frameMin, result->max_rank_pixel_samples = busiest;
-        }
+        const rf::ShardedAdaptiveResult f = rf::renderAdaptive(*r->impl, *c->impl, toAdaptiveParams(*params));
+        if (result) *result = rf_comm_adaptive_result{toAdaptiveResult(f.rank), f.frameLeadingSamples, f.frameMinTileSamples, f.maxRankPixelSamples};
         return RF_OK;
     });
 }

@@ -1,25 +1,21 @@
-// rf_comm.hip -- RCCL gather of tile shards + device un-tile (see rf_comm.hpp).
+// rf_comm.hip -- the frame exchange (rf_comm.hpp): the gather plans, TileComm (one gather as its steps, the device un-tile, the root-side calls) and RcclTransport,
+// the RCCL side of the transport seam (rf_transport.hpp).  The local test transport: rf_comm_local.cpp; the sharded calls over a handle: rf_comm_sharded.cpp.
 #include "rf_comm.hpp"
 
 #include "rf_denoise.hpp"
 #include "rf_hip_host.hpp"
 #include "rf_noise.hpp"
 #include "rf_renderer.hpp" // tilesForRank, TileGrid
+#include "rf_transport.hpp"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
 #include <algorithm>
-#include <array>
 #include <chrono>
-#include <condition_variable>
 #include <cstdlib>
 #include <cstring>
-#include <deque>
 #include <future>
-#include <map>
-#include <mutex>
-#include <random>
 #include <stdexcept>
 #include <string>
 #include <thread>
@@ -38,15 +34,14 @@ namespace
 
 constexpr uint32_t kTilePixels = kTileSize * kTileSize; // 1024
 
-// One workgroup per tile of the frame: tile-major (8x8-pixel blocks, one wave each) -> row-major.  Reads are
-// 1-KiB contiguous per wave, writes 128-byte row segments.  `own`: the root's shard, read in place.
-__global__ __launch_bounds__(256) void kUntile(const float4* __restrict__ staging, const float4* __restrict__ own, uint32_t ownRank, uint32_t ownFirstTile,
-                                               const uint32_t* __restrict__ tileSlot, const uint32_t* __restrict__ tileOwner, uint32_t width, uint32_t height,
-                                               uint32_t tilesX, float4* __restrict__ image)
+// One workgroup per tile of the frame: tile-major (8x8-pixel blocks, one wave each) -> row-major.  Reads are 1-KiB contiguous per wave, writes 128-byte row segments.
+// `own`: the root's shard of the plane, read in place; every other tile comes from the staging area, at its slot.
+__device__ __forceinline__ void untileTile(const float4* __restrict__ staging, const float4* __restrict__ own, float4* __restrict__ image, uint32_t ownRank, uint32_t ownFirstTile,
+                                           const uint32_t* __restrict__ tileSlot, const uint32_t* __restrict__ tileOwner, uint32_t width, uint32_t height, uint32_t tilesX)
 {
     const uint32_t tile = blockIdx.x;
     const uint32_t slot = tileSlot[tile];
-    const float4*  src = tileOwner[tile] == ownRank ? own + static_cast<size_t>(slot - ownFirstTile) * kTilePixels : staging + static_cast<size_t>(slot) * kTilePixels;
+    const float4* __restrict__ src = tileOwner[tile] == ownRank ? own + static_cast<size_t>(slot - ownFirstTile) * kTilePixels : staging + static_cast<size_t>(slot) * kTilePixels;
     const uint32_t x0 = (tile % tilesX) * kTileSize, y0 = (tile / tilesX) * kTileSize;
 #pragma unroll
     for (uint32_t k = 0; k < kTilePixels / 256; ++k)
@@ -58,9 +53,15 @@ __global__ __launch_bounds__(256) void kUntile(const float4* __restrict__ stagin
     }
 }
 
+__global__ __launch_bounds__(256) void kUntile(const float4* __restrict__ staging, const float4* __restrict__ own, uint32_t ownRank, uint32_t ownFirstTile,
+                                               const uint32_t* __restrict__ tileSlot, const uint32_t* __restrict__ tileOwner, uint32_t width, uint32_t height,
+                                               uint32_t tilesX, float4* __restrict__ image)
+{
+    untileTile(staging, own, image, ownRank, ownFirstTile, tileSlot, tileOwner, width, height, tilesX);
+}
+
 // The same for every carried plane of a multi-plane gather in ONE launch: grid (tiles of the frame, carried planes); blockIdx.y picks the plane's pointers from the
-// by-value argument struct (kernel arguments: no device-side table, no upload), everything else is kUntile -- wave k of a workgroup moves the tile's 8x8 blocks with
-// 1-KiB contiguous reads and 128-byte row-segment writes; own / staging per tile from the same tileSlot / tileOwner tables.
+// by-value argument struct (kernel arguments: no device-side table, no upload).
 struct UntilePlane
 {
     const float4* staging; // this plane's staging area
@@ -74,22 +75,9 @@ struct UntilePlaneArgs
 __global__ __launch_bounds__(256) void kUntilePlanes(UntilePlaneArgs args, uint32_t ownRank, uint32_t ownFirstTile, const uint32_t* __restrict__ tileSlot,
                                                      const uint32_t* __restrict__ tileOwner, uint32_t width, uint32_t height, uint32_t tilesX)
 {
-    const UntilePlane             pl = args.plane[blockIdx.y];
-    const uint32_t                tile = blockIdx.x;
-    const uint32_t                slot = tileSlot[tile];
-    const float4* __restrict__    src = tileOwner[tile] == ownRank ? pl.own + static_cast<size_t>(slot - ownFirstTile) * kTilePixels : pl.staging + static_cast<size_t>(slot) * kTilePixels;
-    float4* __restrict__          image = pl.image;
-    const uint32_t                x0 = (tile % tilesX) * kTileSize, y0 = (tile / tilesX) * kTileSize;
-#pragma unroll
-    for (uint32_t k = 0; k < kTilePixels / 256; ++k)
-    {
-        const uint32_t w = k * 256 + threadIdx.x;
-        const uint32_t block = w >> 6, lane = w & 63u;
-        const uint32_t x = x0 + (block & 3u) * 8u + (lane & 7u), y = y0 + (block >> 2) * 8u + (lane >> 3);
-        if (x < width && y < height) image[static_cast<size_t>(y) * width + x] = src[w];
-    }
+    const UntilePlane pl = args.plane[blockIdx.y];
+    untileTile(pl.staging, pl.own, pl.image, ownRank, ownFirstTile, tileSlot, tileOwner, width, height, tilesX);
 }
-
 
 // The gathered per-tile sample counts, one lane per tile of the frame: frameCounts[tile] = the count its owner sent (staged rank after rank, in slot order: tileSlot) or,
 // for the root's own tiles without loop-back, the root's counts read in place.
@@ -164,109 +152,203 @@ std::vector<GatherOp> gatherPlanCounts(const GatherLayout& g, uint32_t worldSize
     return gatherPlan(g, worldSize, rank, root, loopback); // (one word per tile: the offsets and counts in words are the one-plane plan's in tiles)
 }
 
-namespace
-{
-// ------------------------------------------------------------------------------------------------
-// The LOCAL transport (round 6; a TEST transport, RF_COMM_TRANSPORT=local): the same exchange -- the same gatherPlan(), the same staging offsets, the same
-// kUntile -- with every ncclSend / ncclRecv pair replaced by a device-to-device copy between the buffers of N communicators that live in ONE process, one host
-// thread per rank.  RCCL refuses two ranks on one device, and the boxes this is developed on have one GPU: without this, TileComm::gatherFrame() and kUntile
-// had only ever executed with one owner (world 1: every tile `own`, or every tile staging in loop-back).  With it, worlds 2 / 3 / 4 / 8 run on one GPU: the
-// root's receives land at rankFirstTile[peer] of its staging area, kUntile picks own / staging per tile from tileOwner / tileSlot, and the image must equal
-// the single-rank one bit for bit (tests/test_gpu_parity.py: test_local_transport_gather_*).  What it does NOT exercise: RCCL itself and xGMI.
-//
-// Semantics mirror a group of point-to-point operations: a send is matched with the receive the peer posts for it, in posting order per (source,
-// destination); the receiver's stream waits for the sender's stream (an event recorded behind the sender's frame kernels), copies, and the sender's stream
-// waits for the copy before anything queued behind the exchange may touch the buffer again.  Host side a rank posts all its sends, then performs its
-// receives (each waits for its send to be posted), then waits until its sends have been taken -- dead-lock free for the gather (and for loop-back).  A
-// peer that never arrives is an error after RF_COMM_TIMEOUT_S, as with RCCL.
-// ------------------------------------------------------------------------------------------------
-constexpr char kLocalMagic[8] = {'R', 'F', 'L', 'O', 'C', 'A', 'L', '1'};
-
-struct LocalPost
-{
-    const void* src = nullptr;
-    size_t      bytes = 0;
-    int         srcDevice = 0;
-    hipEvent_t  ready = nullptr;    // recorded on the sender's stream behind everything queued before the exchange
-    hipEvent_t  consumed = nullptr; // recorded on the receiver's stream behind its copy (set when `taken`)
-    bool        taken = false;
-};
-
-struct LocalFabric
-{
-    uint32_t                world = 0;
-    std::mutex              mutex;
-    std::condition_variable cv;
-    std::map<std::pair<uint32_t, uint32_t>, std::deque<std::shared_ptr<LocalPost>>> mail; // (source, destination) -> sends not yet received, oldest first
-    std::vector<hipEvent_t> freeEvents, allEvents;
-    // allReduceMax: a generation barrier
-    uint64_t generation = 0;
-    uint32_t arrived = 0;
-    double   running = 0.0, result = 0.0;
-    uint32_t attached = 0;
-
-    hipEvent_t takeEvent() // (mutex held)
-    {
-        if (!freeEvents.empty())
-        {
-            hipEvent_t e = freeEvents.back();
-            freeEvents.pop_back();
-            return e;
-        }
-        hipEvent_t e = nullptr;
-        RF_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        allEvents.push_back(e);
-        return e;
-    }
-    ~LocalFabric()
-    {
-        for (hipEvent_t e : allEvents) (void)hipEventDestroy(e);
-    }
-};
-
-std::mutex                                                                    gFabricMutex;
-std::map<std::array<uint8_t, kCommIdBytes>, std::weak_ptr<LocalFabric>>        gFabrics;
-
-bool localTransportRequested()
-{
-    const char* v = std::getenv("RF_COMM_TRANSPORT");
-    return v != nullptr && std::strcmp(v, "local") == 0;
-}
-bool isLocalId(const uint8_t id[kCommIdBytes]) { return std::memcmp(id, kLocalMagic, sizeof kLocalMagic) == 0; }
-
-std::shared_ptr<LocalFabric> attachFabric(const uint8_t id[kCommIdBytes], uint32_t world)
-{
-    std::array<uint8_t, kCommIdBytes> key;
-    std::memcpy(key.data(), id, kCommIdBytes);
-    std::lock_guard<std::mutex> lock(gFabricMutex);
-    std::shared_ptr<LocalFabric> f = gFabrics[key].lock();
-    if (!f)
-    {
-        f = std::make_shared<LocalFabric>();
-        f->world = world;
-        gFabrics[key] = f;
-    }
-    if (f->world != world) throw std::runtime_error("local transport: the ranks of one id disagree about the world size");
-    for (auto it = gFabrics.begin(); it != gFabrics.end();) it = it->second.expired() ? gFabrics.erase(it) : std::next(it);
-    return f;
-}
-} // namespace
-
-namespace
-{
-// seconds a rank waits for its peers in ncclCommInitRank and in its FIRST gather before it gives up with an error
-// instead of hanging (a missing rank, a wrong id, a dead xGMI link); RF_COMM_TIMEOUT_S overrides, 0 = wait forever
 double commTimeoutSeconds()
 {
     if (const char* v = std::getenv("RF_COMM_TIMEOUT_S")) return std::atof(v);
     return 180.0;
 }
+
+namespace
+{
+// The RCCL transport: the transfers as ncclSend / ncclRecv in one group (all of the root's xGMI ingress links carry data concurrently)
+class RcclTransport final : public Transport
+{
+    ncclComm_t           mComm = nullptr; // nullptr again once the first exchange's watchdog has aborted it
+    uint32_t             mRank;
+    int                  mDevice;
+    bool                 mFirstExchangeDone = false;
+    DeviceBuffer<double> mScalar;
+
+    RcclTransport(uint32_t rank, int device) : mRank(rank), mDevice(device) {}
+    void abort()
+    {
+        (void)ncclCommAbort(mComm);
+        mComm = nullptr;
+    }
+    void watchFirstExchange(hipStream_t stream, hipEvent_t queuedBefore);
+
+public:
+    static std::unique_ptr<Transport> create(const uint8_t idBytes[kCommIdBytes], uint32_t rank, uint32_t worldSize, int device);
+    ~RcclTransport() override
+    {
+        if (!mComm) return;
+        (void)hipSetDevice(mDevice);
+        (void)ncclCommDestroy(mComm);
+    }
+
+    bool isLocal() const override { return false; }
+    void info(uint32_t& count, uint32_t& userRank, int& device) const override
+    {
+        int c = 0, r = 0, d = 0;
+        RF_NCCL(ncclCommCount(mComm, &c));
+        RF_NCCL(ncclCommUserRank(mComm, &r));
+        RF_NCCL(ncclCommCuDevice(mComm, &d));
+        count = static_cast<uint32_t>(c), userRank = static_cast<uint32_t>(r), device = d;
+    }
+    void requireAlive() const override
+    {
+        if (mComm == nullptr) throw std::runtime_error("the RCCL communicator was aborted");
+    }
+
+    void exchange(const std::vector<Transfer>& transfers, hipStream_t stream) override
+    {
+        // (first exchange only) marks the end of what was queued on the stream BEFORE the exchange -- this rank's frame kernels: the watchdog measures the exchange,
+        // not the render in front of it
+        hipEvent_t queuedBefore = nullptr;
+        struct EventGuard
+        {
+            hipEvent_t& e;
+            ~EventGuard()
+            {
+                if (e) (void)hipEventDestroy(e);
+            }
+        } eventGuard{queuedBefore};
+        if (!mFirstExchangeDone)
+        {
+            RF_HIP(hipEventCreateWithFlags(&queuedBefore, hipEventDisableTiming));
+            RF_HIP(hipEventRecord(queuedBefore, stream));
+        }
+        RF_NCCL(ncclGroupStart());
+        try
+        {
+            for (const Transfer& op : transfers)
+            {
+                const ncclDataType_t type = op.kind == Transfer::Kind::F32 ? ncclFloat : ncclUint32;
+                if (op.isSend) RF_NCCL(ncclSend(op.from, op.words, type, static_cast<int>(op.peer), mComm, stream));
+                else RF_NCCL(ncclRecv(op.to, op.words, type, static_cast<int>(op.peer), mComm, stream));
+            }
+        }
+        catch (...)
+        {
+            (void)ncclGroupEnd(); // never leave the thread inside an open group
+            throw;
+        }
+        RF_NCCL(ncclGroupEnd());
+        if (mFirstExchangeDone) return; // (later exchanges stay fully asynchronous)
+        watchFirstExchange(stream, queuedBefore);
+        mFirstExchangeDone = true;
+    }
+
+    double allReduceMax(double value, hipStream_t stream) override
+    {
+        mScalar.ensure(2);
+        RF_HIP(hipMemcpyAsync(mScalar.ptr, &value, sizeof value, hipMemcpyHostToDevice, stream));
+        RF_NCCL(ncclAllReduce(mScalar.ptr, mScalar.ptr + 1, 1, ncclDouble, ncclMax, mComm, stream));
+        double out = 0.0;
+        RF_HIP(hipMemcpyAsync(&out, mScalar.ptr + 1, sizeof out, hipMemcpyDeviceToHost, stream));
+        RF_HIP(hipStreamSynchronize(stream));
+        return out;
+    }
+};
+
+std::unique_ptr<Transport> RcclTransport::create(const uint8_t idBytes[kCommIdBytes], uint32_t rank, uint32_t worldSize, int device)
+{
+    std::unique_ptr<RcclTransport> t(new RcclTransport(rank, device));
+    ncclUniqueId                   id;
+    std::memcpy(&id, idBytes, kCommIdBytes);
+    // ncclCommInitRank blocks until every rank of the world has called it.  It runs on a helper thread so that a rank whose
+    // peers never arrive reports that after RF_COMM_TIMEOUT_S instead of hanging the job (the helper is abandoned then: the
+    // caller is expected to exit).
+    const double timeout = commTimeoutSeconds();
+    auto         task = std::make_shared<std::packaged_task<ncclResult_t()>>([device, worldSize, rank, id, comm = &t->mComm]() -> ncclResult_t {
+        if (hipSetDevice(device) != hipSuccess) return ncclUnhandledCudaError;
+        return ncclCommInitRank(comm, static_cast<int>(worldSize), id, static_cast<int>(rank));
+    });
+    std::future<ncclResult_t> done = task->get_future();
+    std::thread([task] { (*task)(); }).detach();
+    if (timeout > 0.0 && done.wait_for(std::chrono::duration<double>(timeout)) != std::future_status::ready)
+    {
+        (void)t.release(); // the helper still writes into it: leaked on purpose
+        throw std::runtime_error("RCCL: ncclCommInitRank did not complete within " + std::to_string(static_cast<int>(timeout)) + " s on rank " + std::to_string(rank) + " of " +
+                                 std::to_string(worldSize) + " (a rank is missing, or the ranks do not share one unique id); RF_COMM_TIMEOUT_S changes the limit");
+    }
+    RF_NCCL(done.get());
+    int count = 0;
+    RF_NCCL(ncclCommCount(t->mComm, &count));
+    if (static_cast<uint32_t>(count) != worldSize) throw std::runtime_error("RCCL communicator spans " + std::to_string(count) + " ranks, expected " + std::to_string(worldSize));
+    return t;
+}
+
+// The first exchange of a communicator also sets up its peer connections; a peer that never posts its side (it died, it
+// disagrees about the frame size or the root) would leave this stream stuck forever.  Watch this one exchange: past the
+// time limit the communicator is aborted and the caller gets an error instead of a hang.  NOTE: an exception thrown on
+// one rank leaves its peers waiting in their own gather until THEIR limit expires.  The clock starts when the work queued
+// on this stream before the exchange (Renderer::render() is asynchronous: the whole frame may still be in front of it) has
+// drained, so a long first frame does not abort a healthy job; what remains inside the limit is the connection set-up, the
+// transfer, and the wait for the slowest peer to finish ITS frame -- ranks own equal tile counts (+-1), so that wait is a
+// fraction of a frame.
+// A second, much larger cap (kDrainFactor x the limit, from loop entry) covers the case the first clock never starts in: this rank's OWN queued kernels
+// never drain (a hung or faulted kernel keeps the event at hipErrorNotReady forever) -- the loop would otherwise spin without any limit.
+void RcclTransport::watchFirstExchange(hipStream_t stream, hipEvent_t queuedBefore)
+{
+    constexpr double kDrainFactor = 20.0;
+    const double     timeout = commTimeoutSeconds();
+    const auto       entered = std::chrono::steady_clock::now();
+    auto             t0 = entered;
+    bool             drained = false;
+    for (;;)
+    {
+        const hipError_t q = hipStreamQuery(stream);
+        if (q == hipSuccess) break;
+        if (q != hipErrorNotReady) RF_HIP(q);
+        if (!drained)
+        {
+            const hipError_t e = hipEventQuery(queuedBefore);
+            if (e == hipSuccess)
+            {
+                drained = true;
+                t0 = std::chrono::steady_clock::now();
+            }
+            else if (e != hipErrorNotReady) RF_HIP(e);
+        }
+        ncclResult_t async = ncclSuccess;
+        RF_NCCL(ncclCommGetAsyncError(mComm, &async));
+        if (async != ncclSuccess && async != ncclInProgress) throw std::runtime_error(std::string("RCCL error during the first frame exchange: ") + ncclGetErrorString(async));
+        if (drained && timeout > 0.0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > timeout)
+        {
+            abort();
+            throw std::runtime_error("RCCL: the first frame exchange did not complete within " + std::to_string(static_cast<int>(timeout)) + " s on rank " +
+                                     std::to_string(mRank) + " (a peer is missing or disagrees about frame size / root); communicator aborted");
+        }
+        if (!drained && timeout > 0.0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - entered).count() > kDrainFactor * timeout)
+        {
+            abort();
+            throw std::runtime_error("RCCL: the work queued in front of the first frame exchange did not drain within " + std::to_string(static_cast<int>(kDrainFactor * timeout)) +
+                                     " s on rank " + std::to_string(mRank) + " (a kernel of this rank's own frame hangs); communicator aborted");
+        }
+        std::this_thread::sleep_for(std::chrono::microseconds(200));
+    }
+}
 } // namespace
+
+void makeUniqueId(uint8_t out[kCommIdBytes])
+{
+    static_assert(sizeof(ncclUniqueId) == kCommIdBytes);
+    if (makeLocalUniqueId(out)) return;
+    ncclUniqueId id;
+    RF_NCCL(ncclGetUniqueId(&id));
+    std::memcpy(out, &id, kCommIdBytes);
+}
+
+std::unique_ptr<Transport> makeTransport(const uint8_t id[kCommIdBytes], uint32_t rank, uint32_t worldSize, int device)
+{
+    if (std::unique_ptr<Transport> local = makeLocalTransport(id, rank, worldSize, device)) return local;
+    return RcclTransport::create(id, rank, worldSize, device);
+}
 
 struct TileComm::Impl
 {
-    ncclComm_t comm = nullptr;
-    std::shared_ptr<LocalFabric> fabric; // the local (test) transport instead of RCCL: see LocalFabric
+    std::unique_ptr<Transport> transport;
     uint32_t   rank = 0, world = 1;
     int        device = 0;
 
@@ -275,7 +357,6 @@ struct TileComm::Impl
     DeviceBuffer<uint32_t> dTileSlot, dTileOwner;
     DeviceBuffer<float4>   staging;               // one GatherLayout area per carried plane, one after another
     DeviceBuffer<float4>   images[kGatherPlanes]; // per plane: the row-major image the root un-tiles into (allocated when first carried)
-    DeviceBuffer<double>   scalar;
     // the per-tile sample counts of a gather with kGatherMaskTileCounts: staged rank after rank as they arrive, then per tile of the frame (kUntileCounts), and that on the host
     DeviceBuffer<uint32_t> countStaging, frameCounts;
     std::vector<uint32_t>  frameCountsHost;
@@ -289,7 +370,6 @@ struct TileComm::Impl
     DenoiseWork      denoiseWork;
     bool             denoisedValid = false;
     NoiseWork        noiseWork;
-    bool             firstGatherDone = false;
     // HIP events around the last exchange on the caller's stream (sends / receives + the root's un-tile): what the frame-end gather costs THIS rank
     // once its own frame kernels have drained (lastExchangeMs())
     hipEvent_t       exchangeStart = nullptr, exchangeStop = nullptr;
@@ -321,6 +401,136 @@ struct TileComm::Impl
         if ((gatheredMask & need) != need)
             throw std::invalid_argument(std::string(what) + ": the last gather did not carry " + needName);
     }
+
+    // ---- one gather, step by step (TileComm::gatherPlanes).  What the steps share:
+    struct Gather
+    {
+        const void* const* compact; // [plane]: this rank's tile-major buffers
+        const uint32_t*    tileCounts;
+        uint32_t           planeMask, width, height, root;
+        bool               loopback, withCounts, isRoot;
+        hipStream_t        stream;
+        uint32_t           carried[kGatherPlanes] = {}, carriedIndex[kGatherPlanes] = {}, numPlanes = 0; // the carried planes in plane order; carriedIndex[p]: plane p's staging area
+        size_t             planeStagingPixels = 0;                                                       // one plane's staging area
+        uint32_t           ownRank() const { return loopback ? 0xFFFFFFFFu : root; }                      // (the root's un-tile: no tile is read in place under loop-back)
+    };
+    uint32_t tilesOf(uint32_t r) const { return layout.rankFirstTile[r + 1] - layout.rankFirstTile[r]; }
+
+    // 1. the arguments; the device current and the layout of this frame size in place
+    void checkGather(Gather& g)
+    {
+        transport->requireAlive();
+        if (g.root >= world) throw std::invalid_argument("gather root out of range");
+        if (g.width == 0 || g.height == 0) throw std::invalid_argument("empty frame");
+        g.withCounts = (g.planeMask & kGatherMaskTileCounts) != 0u;
+        if ((g.planeMask & kPlaneMaskImage) == 0u || ((g.planeMask & ~kGatherMaskTileCounts) >> kGatherPlanes) != 0u)
+            throw std::invalid_argument("gather plane mask: plane 0 always travels, planes 0 .. 3 exist");
+        for (uint32_t p = 0; p < kGatherPlanes; ++p)
+            if (g.planeMask >> p & 1u) g.carriedIndex[p] = g.numPlanes, g.carried[g.numPlanes++] = p;
+        g.isRoot = rank == g.root;
+        RF_HIP(hipSetDevice(device));
+        ensureLayout(g.width, g.height, g.stream);
+        for (uint32_t k = 0; k < g.numPlanes; ++k)
+            if (tilesOf(rank) > 0 && g.compact[g.carried[k]] == nullptr) throw std::invalid_argument("null tile buffer");
+        if (g.withCounts && tilesOf(rank) > 0 && g.tileCounts == nullptr) throw std::invalid_argument("null tile count buffer");
+        g.planeStagingPixels = static_cast<size_t>(layout.rankFirstTile[world]) * kTilePixels;
+    }
+
+    // 2. the record of the last gather goes now: whatever happens afterwards, nothing stale is read through the root-side calls
+    void dropLastGather(uint32_t root)
+    {
+        gatherMade = true;
+        lastRoot = root;
+        gatheredMask = 0;
+        gatheredSamples = 0;
+        denoisedValid = false;
+    }
+
+    // 3. (root) room for the staged shards and the row-major images
+    void sizeRootBuffers(const Gather& g)
+    {
+        const size_t stagingWant = g.planeStagingPixels * g.numPlanes, imageWant = static_cast<size_t>(g.width) * g.height;
+        bool         grows = stagingWant > staging.count;
+        for (uint32_t k = 0; k < g.numPlanes; ++k) grows = grows || imageWant > images[g.carried[k]].count;
+        const size_t frameTiles = static_cast<size_t>(layout.tilesX) * layout.tilesY;
+        if (g.withCounts) grows = grows || layout.rankFirstTile[world] > countStaging.count || frameTiles > frameCounts.count;
+        if (grows) RF_HIP(hipStreamSynchronize(g.stream)); // a consumer of the old buffers may still run
+        if (g.withCounts) countStaging.ensure(layout.rankFirstTile[world]), frameCounts.ensure(frameTiles);
+        staging.ensure(stagingWant);
+        for (uint32_t k = 0; k < g.numPlanes; ++k) images[g.carried[k]].ensure(imageWant);
+        imageW = g.width;
+        imageH = g.height;
+    }
+
+    // 4. one group: exactly the operations of gatherPlanPlanes() -- with the image alone, gatherPlan()'s (the lists the CPU tests check for every rank of a world) -- and
+    // behind them, with the counts, those of gatherPlanCounts(): per (source, destination) pair the counts are the last send and the last receive
+    std::vector<Transfer> transferList(const Gather& g) const
+    {
+        const size_t floatsPerTile = static_cast<size_t>(kTilePixels) * 4;
+        const auto   stagingOf = [&](const GatherPlaneOp& op) { return staging.ptr + g.carriedIndex[op.plane] * g.planeStagingPixels + static_cast<size_t>(op.offsetTiles) * kTilePixels; };
+        const auto   compactOf = [&](const GatherPlaneOp& op) { return static_cast<const float*>(g.compact[op.plane]) + op.offsetTiles * floatsPerTile; };
+        std::vector<Transfer> list;
+        for (const GatherPlaneOp& op : gatherPlanPlanes(layout, world, rank, g.root, g.loopback, g.planeMask & ~kGatherMaskTileCounts))
+            list.push_back(Transfer{op.isSend != 0u, op.peer, op.isSend ? compactOf(op) : nullptr, op.isSend ? nullptr : stagingOf(op), op.countTiles * floatsPerTile, Transfer::Kind::F32});
+        if (g.withCounts)
+            for (const GatherOp& op : gatherPlanCounts(layout, world, rank, g.root, g.loopback))
+                list.push_back(Transfer{op.isSend != 0u, op.peer, op.isSend ? g.tileCounts + op.offsetTiles : nullptr, op.isSend ? nullptr : countStaging.ptr + op.offsetTiles, op.countTiles,
+                                        Transfer::Kind::U32});
+        return list;
+    }
+
+    // 5. the exchange between its two events: exchangeStop follows the un-tile on the root, the exchange elsewhere
+    void startExchangeClock(hipStream_t stream)
+    {
+        if (exchangeStart == nullptr)
+        {
+            RF_HIP(hipEventCreate(&exchangeStart));
+            RF_HIP(hipEventCreate(&exchangeStop));
+        }
+        exchangeTimed = false;
+        RF_HIP(hipEventRecord(exchangeStart, stream));
+    }
+    void stopExchangeClock(hipStream_t stream)
+    {
+        RF_HIP(hipEventRecord(exchangeStop, stream));
+        exchangeTimed = true;
+    }
+
+    // 6. (root) staged shards + the root's own -> row-major images, and one count per tile of the frame
+    void untile(const Gather& g)
+    {
+        const uint32_t numTiles = layout.tilesX * layout.tilesY;
+        if (g.numPlanes == 1)
+            hipLaunchKernelGGL(kUntile, dim3(numTiles), dim3(256), 0, g.stream, staging.ptr, static_cast<const float4*>(g.compact[kPlaneImage]), g.ownRank(), layout.rankFirstTile[rank],
+                               dTileSlot.ptr, dTileOwner.ptr, g.width, g.height, layout.tilesX, images[kPlaneImage].ptr);
+        else
+        {
+            UntilePlaneArgs args{};
+            for (uint32_t k = 0; k < g.numPlanes; ++k)
+                args.plane[k] = UntilePlane{staging.ptr + k * g.planeStagingPixels, static_cast<const float4*>(g.compact[g.carried[k]]), images[g.carried[k]].ptr};
+            hipLaunchKernelGGL(kUntilePlanes, dim3(numTiles, g.numPlanes), dim3(256), 0, g.stream, args, g.ownRank(), layout.rankFirstTile[rank], dTileSlot.ptr, dTileOwner.ptr, g.width,
+                               g.height, layout.tilesX);
+        }
+        if (g.withCounts)
+            hipLaunchKernelGGL(kUntileCounts, dim3((numTiles + 255u) / 256u), dim3(256), 0, g.stream, countStaging.ptr, g.tileCounts, g.ownRank(), layout.rankFirstTile[rank], dTileSlot.ptr,
+                               dTileOwner.ptr, numTiles, frameCounts.ptr);
+        RF_HIP(hipGetLastError());
+    }
+
+    // 7. (root) what this gather left.  With the counts: they come to the host as well (the root-side calls check them) and N is the largest -- the one wait of such a
+    // gather, on the root alone
+    void recordGather(const Gather& g, uint32_t samples)
+    {
+        if (g.withCounts)
+        {
+            frameCountsHost.assign(layout.tilesX * layout.tilesY, 0u);
+            RF_HIP(hipMemcpyAsync(frameCountsHost.data(), frameCounts.ptr, frameCountsHost.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream));
+            RF_HIP(hipStreamSynchronize(g.stream));
+            samples = *std::max_element(frameCountsHost.begin(), frameCountsHost.end());
+        }
+        gatheredMask = g.planeMask;
+        gatheredSamples = samples;
+    }
 };
 
 int deviceCount()
@@ -334,21 +544,7 @@ int deviceCount()
     return n;
 }
 
-void TileComm::uniqueId(uint8_t out[kCommIdBytes])
-{
-    static_assert(sizeof(ncclUniqueId) == kCommIdBytes);
-    if (localTransportRequested())
-    {
-        // the local transport's ids carry a magic prefix (TileComm's constructor recognises them whatever the environment says by then) + 120 random bytes
-        std::memcpy(out, kLocalMagic, sizeof kLocalMagic);
-        std::random_device rd;
-        for (uint32_t i = sizeof kLocalMagic; i < kCommIdBytes; ++i) out[i] = static_cast<uint8_t>(rd());
-        return;
-    }
-    ncclUniqueId id;
-    RF_NCCL(ncclGetUniqueId(&id));
-    std::memcpy(out, &id, kCommIdBytes);
-}
+void TileComm::uniqueId(uint8_t out[kCommIdBytes]) { makeUniqueId(out); }
 
 TileComm::TileComm(const uint8_t idBytes[kCommIdBytes], uint32_t rank, uint32_t worldSize, int deviceOrdinal) : mImpl(std::make_unique<Impl>())
 {
@@ -360,43 +556,13 @@ TileComm::TileComm(const uint8_t idBytes[kCommIdBytes], uint32_t rank, uint32_t 
     mImpl->world = worldSize;
     mImpl->device = deviceOrdinal;
     RF_HIP(hipSetDevice(deviceOrdinal));
-    if (isLocalId(idBytes))
-    {
-        mImpl->fabric = attachFabric(idBytes, worldSize); // (not collective: a rank's peers are waited for in the exchange itself)
-        return;
-    }
-    ncclUniqueId id;
-    std::memcpy(&id, idBytes, kCommIdBytes);
-    // ncclCommInitRank blocks until every rank of the world has called it.  It runs on a helper thread so that a rank whose
-    // peers never arrive reports that after RF_COMM_TIMEOUT_S instead of hanging the job (the helper is abandoned then: the
-    // caller is expected to exit).
-    const double timeout = commTimeoutSeconds();
-    auto         task = std::make_shared<std::packaged_task<ncclResult_t()>>([deviceOrdinal, worldSize, rank, id, comm = &mImpl->comm]() -> ncclResult_t {
-        if (hipSetDevice(deviceOrdinal) != hipSuccess) return ncclUnhandledCudaError;
-        return ncclCommInitRank(comm, static_cast<int>(worldSize), id, static_cast<int>(rank));
-    });
-    std::future<ncclResult_t> done = task->get_future();
-    std::thread([task] { (*task)(); }).detach();
-    if (timeout > 0.0 && done.wait_for(std::chrono::duration<double>(timeout)) != std::future_status::ready)
-    {
-        mImpl.release(); // the helper still writes into it: leaked on purpose
-        throw std::runtime_error("RCCL: ncclCommInitRank did not complete within " + std::to_string(static_cast<int>(timeout)) + " s on rank " + std::to_string(rank) + " of " +
-                                 std::to_string(worldSize) + " (a rank is missing, or the ranks do not share one unique id); RF_COMM_TIMEOUT_S changes the limit");
-    }
-    RF_NCCL(done.get());
-    int count = 0;
-    RF_NCCL(ncclCommCount(mImpl->comm, &count));
-    if (static_cast<uint32_t>(count) != worldSize) throw std::runtime_error("RCCL communicator spans " + std::to_string(count) + " ranks, expected " + std::to_string(worldSize));
+    mImpl->transport = makeTransport(idBytes, rank, worldSize, deviceOrdinal);
 }
 
 TileComm::~TileComm()
 {
-    if (mImpl && mImpl->comm)
-    {
-        (void)hipSetDevice(mImpl->device);
-        (void)ncclCommDestroy(mImpl->comm);
-    }
-    if (mImpl && mImpl->exchangeStart)
+    mImpl->transport.reset(); // (first: the communicator goes before the events and the buffers)
+    if (mImpl->exchangeStart)
     {
         (void)hipEventDestroy(mImpl->exchangeStart);
         (void)hipEventDestroy(mImpl->exchangeStop);
@@ -407,21 +573,8 @@ uint32_t TileComm::rank() const { return mImpl->rank; }
 uint32_t TileComm::worldSize() const { return mImpl->world; }
 int      TileComm::deviceOrdinal() const { return mImpl->device; }
 
-bool TileComm::localTransport() const { return mImpl->fabric != nullptr; }
-
-void TileComm::rcclInfo(uint32_t& count, uint32_t& userRank, int& device) const
-{
-    if (mImpl->fabric)
-    {
-        count = mImpl->world, userRank = mImpl->rank, device = mImpl->device; // (no RCCL communicator behind it: localTransport() says so)
-        return;
-    }
-    int c = 0, r = 0, d = 0;
-    RF_NCCL(ncclCommCount(mImpl->comm, &c));
-    RF_NCCL(ncclCommUserRank(mImpl->comm, &r));
-    RF_NCCL(ncclCommCuDevice(mImpl->comm, &d));
-    count = static_cast<uint32_t>(c), userRank = static_cast<uint32_t>(r), device = d;
-}
+bool TileComm::localTransport() const { return mImpl->transport->isLocal(); }
+void TileComm::rcclInfo(uint32_t& count, uint32_t& userRank, int& device) const { mImpl->transport->info(count, userRank, device); }
 
 const void* TileComm::gatherFrame(const void* compactDevice, uint32_t width, uint32_t height, uint32_t root, void* streamHandle, bool loopback)
 {
@@ -432,269 +585,18 @@ const void* TileComm::gatherFrame(const void* compactDevice, uint32_t width, uin
 const void* TileComm::gatherPlanes(const void* const compactDevice[kGatherPlanes], uint32_t planeMask, uint32_t samples, uint32_t width, uint32_t height, uint32_t root,
                                    void* streamHandle, bool loopback, const uint32_t* tileCountsDevice)
 {
-    Impl& m = *mImpl;
-    if (m.comm == nullptr && !m.fabric) throw std::runtime_error("the RCCL communicator was aborted");
-    if (root >= m.world) throw std::invalid_argument("gather root out of range");
-    if (width == 0 || height == 0) throw std::invalid_argument("empty frame");
-    const bool withCounts = (planeMask & kGatherMaskTileCounts) != 0u;
-    if ((planeMask & kPlaneMaskImage) == 0u || ((planeMask & ~kGatherMaskTileCounts) >> kGatherPlanes) != 0u)
-        throw std::invalid_argument("gather plane mask: plane 0 always travels, planes 0 .. 3 exist");
-    // the carried planes in plane order; carriedIndex[p]: which staging area plane p has
-    uint32_t carried[kGatherPlanes] = {}, carriedIndex[kGatherPlanes] = {}, numPlanes = 0;
-    for (uint32_t p = 0; p < kGatherPlanes; ++p)
-        if (planeMask >> p & 1u) carriedIndex[p] = numPlanes, carried[numPlanes++] = p;
-    hipStream_t stream = static_cast<hipStream_t>(streamHandle);
-    RF_HIP(hipSetDevice(m.device));
-    m.ensureLayout(width, height, stream);
-    const GatherLayout& g = m.layout;
-    const auto          tilesOf = [&](uint32_t r) { return g.rankFirstTile[r + 1] - g.rankFirstTile[r]; };
-    const size_t        floatsPerTile = static_cast<size_t>(kTilePixels) * 4;
-    const bool          isRoot = m.rank == root;
-    for (uint32_t k = 0; k < numPlanes; ++k)
-        if (tilesOf(m.rank) > 0 && compactDevice[carried[k]] == nullptr) throw std::invalid_argument("null tile buffer");
-    if (withCounts && tilesOf(m.rank) > 0 && tileCountsDevice == nullptr) throw std::invalid_argument("null tile count buffer");
-    // the record of the last gather goes now: whatever happens below, nothing stale is read through the root-side calls
-    m.gatherMade = true;
-    m.lastRoot = root;
-    m.gatheredMask = 0;
-    m.gatheredSamples = 0;
-    m.denoisedValid = false;
-    const size_t planeStagingPixels = static_cast<size_t>(g.rankFirstTile[m.world]) * kTilePixels; // one plane's staging area
-    if (isRoot)
-    {
-        const size_t stagingWant = planeStagingPixels * numPlanes, imageWant = static_cast<size_t>(width) * height;
-        bool         grows = stagingWant > m.staging.count;
-        for (uint32_t k = 0; k < numPlanes; ++k) grows = grows || imageWant > m.images[carried[k]].count;
-        const size_t frameTiles = static_cast<size_t>(g.tilesX) * g.tilesY;
-        if (withCounts) grows = grows || g.rankFirstTile[m.world] > m.countStaging.count || frameTiles > m.frameCounts.count;
-        if (grows) RF_HIP(hipStreamSynchronize(stream)); // a consumer of the old buffers may still run
-        if (withCounts) m.countStaging.ensure(g.rankFirstTile[m.world]), m.frameCounts.ensure(frameTiles);
-        m.staging.ensure(stagingWant);
-        for (uint32_t k = 0; k < numPlanes; ++k) m.images[carried[k]].ensure(imageWant);
-        m.imageW = width;
-        m.imageH = height;
-    }
-    const auto stagingOf = [&](const GatherPlaneOp& op) { return m.staging.ptr + carriedIndex[op.plane] * planeStagingPixels + static_cast<size_t>(op.offsetTiles) * kTilePixels; };
-    const auto compactOf = [&](const GatherPlaneOp& op) { return static_cast<const float*>(compactDevice[op.plane]) + op.offsetTiles * floatsPerTile; };
-
-    // one group: exactly the operations of gatherPlanPlanes() -- with the image alone, gatherPlan()'s (the lists the CPU tests check for every rank of a world) -- and
-    // behind them, with the counts, those of gatherPlanCounts(): per (source, destination) pair the counts are the last send and the last receive
-    struct Transfer
-    {
-        bool           isSend;
-        uint32_t       peer;
-        const void*    from; // a send's source
-        void*          to;   // a receive's destination
-        size_t         words; // 4-byte elements
-        ncclDataType_t type;
-    };
-    std::vector<Transfer> plan;
-    for (const GatherPlaneOp& op : gatherPlanPlanes(g, m.world, m.rank, root, loopback, planeMask & ~kGatherMaskTileCounts))
-        plan.push_back(Transfer{op.isSend != 0u, op.peer, op.isSend ? compactOf(op) : nullptr, op.isSend ? nullptr : stagingOf(op), op.countTiles * floatsPerTile, ncclFloat});
-    if (withCounts)
-        for (const GatherOp& op : gatherPlanCounts(g, m.world, m.rank, root, loopback))
-            plan.push_back(Transfer{op.isSend != 0u, op.peer, op.isSend ? tileCountsDevice + op.offsetTiles : nullptr, op.isSend ? nullptr : m.countStaging.ptr + op.offsetTiles,
-                                    op.countTiles, ncclUint32});
-    // (first exchange only) marks the end of what was queued on the stream BEFORE the exchange -- this rank's frame kernels: the
-    // watchdog below measures the exchange, not the render in front of it
-    hipEvent_t queuedBefore = nullptr;
-    if (!m.firstGatherDone)
-    {
-        RF_HIP(hipEventCreateWithFlags(&queuedBefore, hipEventDisableTiming));
-        RF_HIP(hipEventRecord(queuedBefore, stream));
-    }
-    struct EventGuard
-    {
-        hipEvent_t& e;
-        ~EventGuard()
-        {
-            if (e) (void)hipEventDestroy(e);
-        }
-    } eventGuard{queuedBefore};
-    if (m.exchangeStart == nullptr)
-    {
-        RF_HIP(hipEventCreate(&m.exchangeStart));
-        RF_HIP(hipEventCreate(&m.exchangeStop));
-    }
-    m.exchangeTimed = false;
-    RF_HIP(hipEventRecord(m.exchangeStart, stream));
-    if (m.fabric)
-    {
-        // ---- the local transport: the plan's operations as device-to-device copies between the ranks' buffers (see LocalFabric)
-        LocalFabric&  f = *m.fabric;
-        const double  timeout = commTimeoutSeconds();
-        const auto    waitFor = [&](std::unique_lock<std::mutex>& lock, auto&& ready, const char* what) {
-            if (timeout > 0.0)
-            {
-                if (!f.cv.wait_for(lock, std::chrono::duration<double>(timeout), ready))
-                    throw std::runtime_error(std::string("local transport: ") + what + " did not happen within " + std::to_string(static_cast<int>(timeout)) + " s on rank " +
-                                             std::to_string(m.rank) + " (a peer is missing or disagrees about frame size / root)");
-            }
-            else f.cv.wait(lock, ready);
-        };
-        std::vector<std::shared_ptr<LocalPost>> mine;
-        for (const Transfer& op : plan) // 1. post every send
-        {
-            if (!op.isSend) continue;
-            auto post = std::make_shared<LocalPost>();
-            post->src = op.from;
-            post->bytes = op.words * sizeof(uint32_t);
-            post->srcDevice = m.device;
-            {
-                std::lock_guard<std::mutex> lock(f.mutex);
-                post->ready = f.takeEvent();
-            }
-            RF_HIP(hipEventRecord(post->ready, stream));
-            {
-                std::lock_guard<std::mutex> lock(f.mutex);
-                f.mail[{m.rank, op.peer}].push_back(post);
-            }
-            f.cv.notify_all();
-            mine.push_back(post);
-        }
-        for (const Transfer& op : plan) // 2. every receive: wait for the peer's send, copy behind it
-        {
-            if (op.isSend) continue;
-            std::shared_ptr<LocalPost> post;
-            {
-                std::unique_lock<std::mutex> lock(f.mutex);
-                auto&                        box = f.mail[{op.peer, m.rank}];
-                waitFor(lock, [&] { return !box.empty(); }, "a peer's send");
-                post = box.front();
-                box.pop_front();
-                post->consumed = f.takeEvent();
-            }
-            if (post->bytes != op.words * sizeof(uint32_t)) // (a plane's tiles or a shard's counts: each operation has its own size)
-                throw std::runtime_error("local transport: rank " + std::to_string(op.peer) + " sends " + std::to_string(post->bytes) + " bytes, rank " + std::to_string(m.rank) + " expects " +
-                                         std::to_string(op.words * sizeof(uint32_t)) + " (the ranks disagree about the frame)");
-            RF_HIP(hipStreamWaitEvent(stream, post->ready, 0));
-            RF_HIP(hipMemcpyAsync(op.to, post->src, post->bytes, hipMemcpyDeviceToDevice, stream));
-            RF_HIP(hipEventRecord(post->consumed, stream));
-            {
-                std::lock_guard<std::mutex> lock(f.mutex);
-                post->taken = true;
-            }
-            f.cv.notify_all();
-        }
-        for (const std::shared_ptr<LocalPost>& post : mine) // 3. my sends: the buffer is mine again once the receiver's copy has run
-        {
-            {
-                std::unique_lock<std::mutex> lock(f.mutex);
-                waitFor(lock, [&] { return post->taken; }, "the root's receive");
-            }
-            RF_HIP(hipStreamWaitEvent(stream, post->consumed, 0));
-            std::lock_guard<std::mutex> lock(f.mutex);
-            f.freeEvents.push_back(post->ready);
-            f.freeEvents.push_back(post->consumed);
-        }
-        m.firstGatherDone = true;
-    }
-    else
-    {
-    RF_NCCL(ncclGroupStart());
-    try
-    {
-        for (const Transfer& op : plan)
-        {
-            if (op.isSend) RF_NCCL(ncclSend(op.from, op.words, op.type, static_cast<int>(op.peer), m.comm, stream));
-            else RF_NCCL(ncclRecv(op.to, op.words, op.type, static_cast<int>(op.peer), m.comm, stream));
-        }
-    }
-    catch (...)
-    {
-        (void)ncclGroupEnd(); // never leave the thread inside an open group
-        throw;
-    }
-    RF_NCCL(ncclGroupEnd());
-    if (!m.firstGatherDone)
-    {
-        // The first exchange of a communicator also sets up its peer connections; a peer that never posts its side (it died, it
-        // disagrees about the frame size or the root) would leave this stream stuck forever.  Watch this one exchange: past the
-        // time limit the communicator is aborted and the caller gets an error instead of a hang.  Later gathers are not watched
-        // (they stay fully asynchronous).  NOTE: an exception thrown on one rank leaves its peers waiting in their own gather
-        // until THEIR limit expires.  The clock starts when the work queued on this stream before the exchange (Renderer::render()
-        // is asynchronous: the whole frame may still be in front of it) has drained, so a long first frame does not abort a healthy
-        // job; what remains inside the limit is the connection set-up, the transfer, and the wait for the slowest peer to finish ITS
-        // frame -- ranks own equal tile counts (+-1), so that wait is a fraction of a frame.
-        // A second, much larger cap (kDrainFactor x the limit, from loop entry) covers the case the first clock never starts in: this rank's OWN queued kernels
-        // never drain (a hung or faulted kernel keeps the event at hipErrorNotReady forever) -- the loop would otherwise spin without any limit.
-        constexpr double kDrainFactor = 20.0;
-        const double timeout = commTimeoutSeconds();
-        const auto   entered = std::chrono::steady_clock::now();
-        auto         t0 = entered;
-        bool         drained = false;
-        for (;;)
-        {
-            const hipError_t q = hipStreamQuery(stream);
-            if (q == hipSuccess) break;
-            if (q != hipErrorNotReady) RF_HIP(q);
-            if (!drained)
-            {
-                const hipError_t e = hipEventQuery(queuedBefore);
-                if (e == hipSuccess)
-                {
-                    drained = true;
-                    t0 = std::chrono::steady_clock::now();
-                }
-                else if (e != hipErrorNotReady) RF_HIP(e);
-            }
-            ncclResult_t async = ncclSuccess;
-            RF_NCCL(ncclCommGetAsyncError(m.comm, &async));
-            if (async != ncclSuccess && async != ncclInProgress) throw std::runtime_error(std::string("RCCL error during the first frame exchange: ") + ncclGetErrorString(async));
-            if (drained && timeout > 0.0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > timeout)
-            {
-                (void)ncclCommAbort(m.comm);
-                m.comm = nullptr;
-                throw std::runtime_error("RCCL: the first frame exchange did not complete within " + std::to_string(static_cast<int>(timeout)) + " s on rank " +
-                                         std::to_string(m.rank) + " (a peer is missing or disagrees about frame size / root); communicator aborted");
-            }
-            if (!drained && timeout > 0.0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - entered).count() > kDrainFactor * timeout)
-            {
-                (void)ncclCommAbort(m.comm);
-                m.comm = nullptr;
-                throw std::runtime_error("RCCL: the work queued in front of the first frame exchange did not drain within " + std::to_string(static_cast<int>(kDrainFactor * timeout)) +
-                                         " s on rank " + std::to_string(m.rank) + " (a kernel of this rank's own frame hangs); communicator aborted");
-            }
-            std::this_thread::sleep_for(std::chrono::microseconds(200));
-        }
-        m.firstGatherDone = true;
-    }
-    } // (RCCL transport)
-    if (!isRoot)
-    {
-        RF_HIP(hipEventRecord(m.exchangeStop, stream));
-        m.exchangeTimed = true;
-        return nullptr;
-    }
-
-    const uint32_t numTiles = g.tilesX * g.tilesY;
-    if (numPlanes == 1)
-        hipLaunchKernelGGL(kUntile, dim3(numTiles), dim3(256), 0, stream, m.staging.ptr, static_cast<const float4*>(compactDevice[kPlaneImage]), loopback ? 0xFFFFFFFFu : m.rank,
-                           g.rankFirstTile[m.rank], m.dTileSlot.ptr, m.dTileOwner.ptr, width, height, g.tilesX, m.images[kPlaneImage].ptr);
-    else
-    {
-        UntilePlaneArgs args{};
-        for (uint32_t k = 0; k < numPlanes; ++k)
-            args.plane[k] = UntilePlane{m.staging.ptr + k * planeStagingPixels, static_cast<const float4*>(compactDevice[carried[k]]), m.images[carried[k]].ptr};
-        hipLaunchKernelGGL(kUntilePlanes, dim3(numTiles, numPlanes), dim3(256), 0, stream, args, loopback ? 0xFFFFFFFFu : m.rank, g.rankFirstTile[m.rank], m.dTileSlot.ptr,
-                           m.dTileOwner.ptr, width, height, g.tilesX);
-    }
-    if (withCounts)
-        hipLaunchKernelGGL(kUntileCounts, dim3((numTiles + 255u) / 256u), dim3(256), 0, stream, m.countStaging.ptr, tileCountsDevice, loopback ? 0xFFFFFFFFu : m.rank,
-                           g.rankFirstTile[m.rank], m.dTileSlot.ptr, m.dTileOwner.ptr, numTiles, m.frameCounts.ptr);
-    RF_HIP(hipGetLastError());
-    RF_HIP(hipEventRecord(m.exchangeStop, stream));
-    m.exchangeTimed = true;
-    if (withCounts)
-    {
-        // the counts on the host as well (the root-side calls check them, N is the largest): the one wait of such a gather, on the root alone
-        m.frameCountsHost.assign(numTiles, 0u);
-        RF_HIP(hipMemcpyAsync(m.frameCountsHost.data(), m.frameCounts.ptr, numTiles * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        RF_HIP(hipStreamSynchronize(stream));
-        samples = *std::max_element(m.frameCountsHost.begin(), m.frameCountsHost.end());
-    }
-    m.gatheredMask = planeMask;
-    m.gatheredSamples = samples;
+    Impl&        m = *mImpl;
+    Impl::Gather g{compactDevice, tileCountsDevice, planeMask, width, height, root, loopback, false, false, static_cast<hipStream_t>(streamHandle)};
+    m.checkGather(g);
+    m.dropLastGather(root);
+    if (g.isRoot) m.sizeRootBuffers(g);
+    const std::vector<Transfer> transfers = m.transferList(g);
+    m.startExchangeClock(g.stream);
+    m.transport->exchange(transfers, g.stream);
+    if (g.isRoot) m.untile(g);
+    m.stopExchangeClock(g.stream);
+    if (!g.isRoot) return nullptr;
+    m.recordGather(g, samples);
     return m.images[kPlaneImage].ptr;
 }
 
@@ -830,40 +732,7 @@ void TileComm::readMean(float* rgba, void* streamHandle)
 
 double TileComm::allReduceMax(double value, void* streamHandle)
 {
-    Impl&       m = *mImpl;
-    hipStream_t stream = static_cast<hipStream_t>(streamHandle);
-    RF_HIP(hipSetDevice(m.device));
-    if (m.fabric)
-    {
-        // local transport: a generation barrier over the fabric's ranks (host side; the caller's stream is drained first, as the RCCL path's read-back does)
-        RF_HIP(hipStreamSynchronize(stream));
-        LocalFabric&                 f = *m.fabric;
-        std::unique_lock<std::mutex> lock(f.mutex);
-        const uint64_t               gen = f.generation;
-        f.running = f.arrived == 0 ? value : std::max(f.running, value);
-        if (++f.arrived == f.world)
-        {
-            f.result = f.running;
-            f.arrived = 0;
-            ++f.generation;
-            f.cv.notify_all();
-            return f.result;
-        }
-        const double timeout = commTimeoutSeconds();
-        const auto   released = [&] { return f.generation != gen; };
-        if (timeout > 0.0)
-        {
-            if (!f.cv.wait_for(lock, std::chrono::duration<double>(timeout), released)) throw std::runtime_error("local transport: all-reduce timed out on rank " + std::to_string(m.rank));
-        }
-        else f.cv.wait(lock, released);
-        return f.result;
-    }
-    m.scalar.ensure(2);
-    RF_HIP(hipMemcpyAsync(m.scalar.ptr, &value, sizeof value, hipMemcpyHostToDevice, stream));
-    RF_NCCL(ncclAllReduce(m.scalar.ptr, m.scalar.ptr + 1, 1, ncclDouble, ncclMax, m.comm, stream));
-    double out = 0.0;
-    RF_HIP(hipMemcpyAsync(&out, m.scalar.ptr + 1, sizeof out, hipMemcpyDeviceToHost, stream));
-    RF_HIP(hipStreamSynchronize(stream));
-    return out;
+    RF_HIP(hipSetDevice(mImpl->device));
+    return mImpl->transport->allReduceMax(value, static_cast<hipStream_t>(streamHandle));
 }
 } // namespace rf

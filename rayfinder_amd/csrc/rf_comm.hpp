@@ -8,6 +8,11 @@
 // shards into the row-major width x height float4 image with one kernel.  One process (or host thread) per GPU.
 // The same one group can carry the handle's other per-pixel sums (the first-hit AOV sums, the radiance second moments) as further PLANES, un-tiled by one kernel with
 // the image; the root then denoises and estimates the gathered frame where it lies, in device memory (gatherPlanes, denoise, noiseEstimate below).
+//
+// Units: rf_comm.hip          the plans, TileComm (a gather as its steps, the un-tile kernels, the root-side calls) and the RCCL transport
+//        rf_transport.hpp     what TileComm asks of a transport (internal)
+//        rf_comm_local.cpp    the local test transport (RF_COMM_TRANSPORT=local)
+//        rf_comm_sharded.cpp  gatherFrame / renderAdaptive below: a tile-sharded handle's calls over a communicator
 #pragma once
 
 #include "rf_renderer.hpp" // DenoiseParameters, NoiseEstimate
@@ -89,7 +94,7 @@ public:
     // many ranks the exchange really spans.
     void rcclInfo(uint32_t& count, uint32_t& userRank, int& device) const;
     // true: this communicator runs on the LOCAL test transport (RF_COMM_TRANSPORT=local when its id was made: N ranks in one process, one host thread each,
-    // ncclSend / ncclRecv replaced by device-to-device copies -- the same plan, staging offsets and un-tile; rf_comm.hip), not on RCCL
+    // every send / receive pair a device-to-device copy -- the same plan, staging offsets and un-tile; rf_comm_local.cpp), not on RCCL
     bool localTransport() const;
 
     // Frame-end exchange, enqueued on `stream` (a hipStream_t: the renderer's, so the exchange is ordered behind
@@ -139,4 +144,17 @@ private:
     struct Impl;
     std::unique_ptr<Impl> mImpl;
 };
+
+// ---- a tile-sharded handle's calls over its communicator (rf_renderer_gather_frame, rf_comm_render_adaptive).  Every refusal (std::invalid_argument) comes before
+// the first collective: a refused rank leaves no peer waiting as long as the ranks pass the same arguments.
+// The frame-end gather of the handle's sums on its own stream; `flags`: RF_GATHER_* (include/rayfinder_amd.h).  -> the root's image (plane 0), nullptr elsewhere
+const void* gatherFrame(Renderer& handle, TileComm& comm, uint32_t root, uint32_t flags);
+// Tile-adaptive sampling of the sharded frame: Renderer::renderAdaptiveFrom on every rank from the frame's leading count, then the frame's figures, the same on every rank
+struct ShardedAdaptiveResult
+{
+    AdaptiveResult rank; // this rank's tiles; stoppedTiles: those below the FRAME's leading count
+    uint32_t       frameLeadingSamples = 0, frameMinTileSamples = 0;
+    uint64_t       maxRankPixelSamples = 0; // the pixel samples traced by the busiest rank
+};
+ShardedAdaptiveResult renderAdaptive(Renderer& handle, TileComm& comm, const AdaptiveParameters& params);
 } // namespace rf

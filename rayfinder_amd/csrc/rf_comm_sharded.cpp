@@ -1,0 +1,79 @@
+// rf_comm_sharded.cpp -- a tile-sharded handle's calls over its communicator (rf_comm.hpp: gatherFrame, renderAdaptive).  Host code only.
+#include "../../include/rayfinder_amd.h" // RF_GATHER_*
+
+#include "rf_comm.hpp"
+
+#include <stdexcept>
+#include <string>
+
+namespace rf
+{
+namespace
+{
+void require(bool cond, const char* what)
+{
+    if (!cond) throw std::invalid_argument(what);
+}
+
+// the handle's shard is the communicator's rank, and the exchange is enqueued on the handle's stream with the communicator's device current: they must be one device
+void requireOneRank(const Renderer& h, const TileComm& comm)
+{
+    require(h.shardRank() == comm.rank() && h.shardWorldSize() == comm.worldSize(),
+            "the renderer's tile shard differs from the communicator's rank / world size (call rf_renderer_set_tile_shard first)");
+    require(h.deviceOrdinal() == comm.deviceOrdinal(), "the renderer and the communicator are on different devices");
+}
+} // namespace
+
+const void* gatherFrame(Renderer& h, TileComm& comm, uint32_t root, uint32_t flags)
+{
+    require(root < comm.worldSize(), "gather root out of range");
+    requireOneRank(h, comm);
+    if (!(flags & RF_GATHER_TILE_COUNTS)) h.requireUniformTileSamples("rf_renderer_gather_frame"); // (such an exchange carries no per-tile counts)
+    // the extra planes: a sum travels only when it holds exactly the accumulated samples (a rank whose shard has no tile has nothing to send and nothing to check
+    // but the switch).  Refused before anything is enqueued or cleared.
+    const Renderer::ShardSums s = h.shardSums();
+    uint32_t                  planeMask = kPlaneMaskImage;
+    const auto                differs = [&](const char* flag, const char* count, uint32_t samples, const char* name) {
+        return std::invalid_argument(std::string("rf_renderer_gather_frame: ") + flag + ": the " + count + " sample count (" + std::to_string(samples) +
+                                     ") differs from the accumulated sample count (" + std::to_string(s.accumulated) + "): turn the " + name + " on before the first sample");
+    };
+    if (flags & RF_GATHER_AOVS)
+    {
+        require(s.aovs.on, "rf_renderer_gather_frame: RF_GATHER_AOVS needs the first-hit AOVs: turn them on (rf_renderer_set_aovs) before the first sample");
+        require(!s.ownsTiles || s.accumulated != 0u, "rf_renderer_gather_frame: RF_GATHER_AOVS: no sample has been accumulated");
+        if (s.ownsTiles && !s.aovs.coversAccumulation) throw differs("RF_GATHER_AOVS", "AOV", s.aovs.samples, "AOVs");
+        planeMask |= kPlaneMaskAovs;
+    }
+    if (flags & RF_GATHER_MOMENTS)
+    {
+        require(s.moments.on, "rf_renderer_gather_frame: RF_GATHER_MOMENTS needs the radiance second moments: turn them on (rf_renderer_set_moments) before the first sample");
+        require(!s.ownsTiles || s.accumulated != 0u, "rf_renderer_gather_frame: RF_GATHER_MOMENTS: no sample has been accumulated");
+        if (s.ownsTiles && !s.moments.coversAccumulation) throw differs("RF_GATHER_MOMENTS", "moment", s.moments.samples, "moments");
+        planeMask |= kPlaneMaskMoments;
+    }
+    h.clearAccumulationIfStale(); // nothing rendered since the last reset: send zeros, not the previous frame
+    // the shard's per-tile counts, in slot order, from device memory (the ordinary state: every tile at the accumulated count)
+    const uint32_t* counts = nullptr;
+    if (flags & RF_GATHER_TILE_COUNTS) planeMask |= kGatherMaskTileCounts, counts = h.shardTileSamplesDevice();
+    return comm.gatherPlanes(s.planes, planeMask, s.accumulated, h.width(), h.height(), root, h.streamHandle(), (flags & RF_GATHER_LOOPBACK) != 0, counts);
+}
+
+ShardedAdaptiveResult renderAdaptive(Renderer& h, TileComm& comm, const AdaptiveParameters& p)
+{
+    h.checkAdaptive(p);
+    requireOneRank(h, comm);
+    void* const stream = h.streamHandle();
+    // the frame's leading count: the largest accumulated count of any rank.  From here the loop is this rank's own: a tile's stop reads its own sums alone
+    const uint32_t        leading = static_cast<uint32_t>(comm.allReduceMax(static_cast<double>(h.accumulatedSampleCount()), stream));
+    ShardedAdaptiveResult out;
+    AdaptiveResult&       a = out.rank = h.renderAdaptiveFrom(p, leading, true);
+    // the frame's figures (exact in a double; a minimum as the maximum of the negated value; a rank without a tile has no minimum to offer)
+    const double noTile = -4294967296.0;
+    out.frameLeadingSamples = static_cast<uint32_t>(comm.allReduceMax(a.tiles ? static_cast<double>(a.maxTileSamples) : 0.0, stream));
+    out.frameMinTileSamples = static_cast<uint32_t>(-comm.allReduceMax(a.tiles ? -static_cast<double>(a.minTileSamples) : noTile, stream));
+    out.maxRankPixelSamples = static_cast<uint64_t>(comm.allReduceMax(static_cast<double>(a.tracedPixelSamples), stream));
+    // the frame's leading tiles moved the frame counter of the ranks that hold them by frameLeading - leading; a rank that stopped earlier, or never started, follows
+    a.stoppedTiles = h.settleFrameTileSamples(out.frameLeadingSamples, out.frameMinTileSamples, out.frameLeadingSamples - leading - a.framesTraced);
+    return out;
+}
+} // namespace rf

@@ -1847,18 +1847,14 @@ AdaptiveResult Renderer::renderAdaptiveFrom(const AdaptiveParameters& p, uint32_
     return out;
 }
 
-void Renderer::setFrameTileSamples(uint32_t leading, uint32_t minimum)
+uint32_t Renderer::settleFrameTileSamples(uint32_t leading, uint32_t minimum, uint32_t skipFrames)
 {
-    mImpl->frameLeadingSamples = leading, mImpl->frameMinTileSamples = minimum;
-}
-void     Renderer::skipFrames(uint32_t numFrames) { mImpl->frameCount += numFrames; }
-
-uint32_t Renderer::shardTilesBelow(uint32_t count) const
-{
-    const Impl& m = *mImpl;
-    uint32_t    n = 0;
-    for (size_t k = 0; k < m.tiles.size(); ++k) n += (m.nonUniform() ? m.tileSamples[k] : m.accumulated) < count ? 1u : 0u;
-    return n;
+    Impl& m = *mImpl;
+    m.frameLeadingSamples = leading, m.frameMinTileSamples = minimum;
+    m.frameCount += skipFrames;
+    uint32_t below = 0;
+    for (size_t k = 0; k < m.tiles.size(); ++k) below += (m.nonUniform() ? m.tileSamples[k] : m.accumulated) < leading ? 1u : 0u;
+    return below;
 }
 
 const uint32_t* Renderer::shardTileSamplesDevice()
@@ -1922,13 +1918,13 @@ uint32_t Renderer::renderUntil(float targetMeanError, uint32_t checkEvery, uint3
 }
 
 void*    Renderer::accumulationDevicePointer() const { return mImpl->image; }
-void*    Renderer::aovAlbedoCoverageDevicePointer() const { return mImpl->aovAlbedoCoverage(); }
-void*    Renderer::aovNormalDepthDevicePointer() const { return mImpl->aovNormalDepth(); }
-void*    Renderer::momentsDevicePointer() const { return mImpl->moments(); }
-bool     Renderer::aovsCoverAccumulation() const { return mImpl->aovSums.on && mImpl->accumulated != 0u && mImpl->aovSums.covers(mImpl->accumulated); }
-bool     Renderer::momentsCoverAccumulation() const { return mImpl->momentSums.on && mImpl->accumulated != 0u && mImpl->momentSums.covers(mImpl->accumulated); }
-uint32_t Renderer::aovSampleCount() const { return mImpl->aovSums.samples; }
-uint32_t Renderer::momentSampleCount() const { return mImpl->momentSums.samples; }
+
+Renderer::ShardSums Renderer::shardSums() const
+{
+    const Impl& m = *mImpl;
+    const auto  channel = [&](const auto& sums) { return ShardSums::Channel{sums.on, sums.on && m.accumulated != 0u && sums.covers(m.accumulated), sums.samples}; };
+    return ShardSums{{m.image, m.aovAlbedoCoverage(), m.aovNormalDepth(), m.moments()}, channel(m.aovSums), channel(m.momentSums), m.accumulated, !m.tiles.empty()};
+}
 
 void Renderer::clearAccumulationIfStale()
 {

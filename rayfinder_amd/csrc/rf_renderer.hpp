@@ -255,20 +255,18 @@ public:
     // std::invalid_argument when the moments are off or do not cover the accumulation, the AOVs are on without kAovTileCounts or do not cover it, a tile shard is set,
     // checkEvery is 0 or the target is negative or not finite.
     AdaptiveResult renderAdaptive(const AdaptiveParameters& params);
-    // The same over a tile shard, one rank's part of rf_comm_render_adaptive (rf_c_api.cpp makes the exchanges around it).  checkAdaptive: renderAdaptive's checks but
-    // the shard's, throwing before anything is traced -- there, before the first collective.  renderAdaptiveFrom: the loop over this handle's tiles with `leading` the
-    // FRAME's leading count (the largest accumulated count over the ranks): the active tiles are those at `leading` -- none when this handle's own count is lower -- and
+    // The same over a tile shard, one rank's part of rf_comm_render_adaptive (renderAdaptive of rf_comm.hpp makes the exchanges around it).  checkAdaptive: renderAdaptive's
+    // checks but the shard's, throwing before anything is traced -- there, before the first collective.  renderAdaptiveFrom: the loop over this handle's tiles with `leading`
+    // the FRAME's leading count (the largest accumulated count over the ranks): the active tiles are those at `leading` -- none when this handle's own count is lower -- and
     // the result speaks of this handle's tiles (stoppedTiles: below its own accumulated count); shardSlots: the sums are addressed through each listed tile's slot in the
-    // shard (always so through rf_comm_render_adaptive, at world size 1 as well).  setFrameTileSamples: the frame's largest and smallest tile count after
-    // the call, the same on every rank; while they differ the handle is in the non-uniform state (requireUniformTileSamples) whatever its own tiles hold.  Cleared with
-    // the accumulation.
+    // shard (always so through rf_comm_render_adaptive, at world size 1 as well).
     void           checkAdaptive(const AdaptiveParameters& params) const;
     AdaptiveResult renderAdaptiveFrom(const AdaptiveParameters& params, uint32_t leading, bool shardSlots);
-    void           setFrameTileSamples(uint32_t leading, uint32_t minimum);
-    // Advance the frame counter without tracing: a rank whose tiles all stopped while the frame's leading tiles went on stays in step with them -- the next sample
-    // any rank traces (after a restart of the accumulation too) is the one a handle without a shard would trace
-    void           skipFrames(uint32_t numFrames);
-    uint32_t       shardTilesBelow(uint32_t count) const;
+    // What follows the loop once the ranks have agreed on the frame: its largest and smallest tile count, the same on every rank -- while they differ the handle is in the
+    // non-uniform state (requireUniformTileSamples) whatever its own tiles hold; cleared with the accumulation -- and `skipFrames` more on the frame counter without
+    // tracing: a rank whose tiles all stopped while the frame's leading tiles went on stays in step with them, so the next sample any rank traces (after a restart of the
+    // accumulation too) is the one a handle without a shard would trace.  -> how many of the shard's tiles are below `leading`
+    uint32_t       settleFrameTileSamples(uint32_t leading, uint32_t minimum, uint32_t skipFrames);
     // The counts of the shard's tiles in slot order (the order of shardTiles()) in device memory, for the frame gather; waits for the stream.  Valid until the next
     // per-tile read or gather of this handle.
     const uint32_t* shardTileSamplesDevice();
@@ -281,16 +279,22 @@ public:
     // Device pointer of the compact tile-major accumulation buffer (numTiles*1024 float4) and a
     // way to render into caller-owned device memory (e.g. a torch tensor used for the RCCL gather).
     void*    accumulationDevicePointer() const;
-    // Device pointers of the other compact tile-major sums of the shard, for the frame gather (rf_comm.hpp: planes 1 .. 3): {albedo.rgb, coverage}, {normal.xyz, depth}
-    // and the radiance second moments -- nullptr while the channel is off or has not been sized yet -- and whether a channel holds exactly the accumulated samples
-    // (on from the first sample, at least one accumulated): what the gather requires before it sends them.
-    void*    aovAlbedoCoverageDevicePointer() const;
-    void*    aovNormalDepthDevicePointer() const;
-    void*    momentsDevicePointer() const;
-    bool     aovsCoverAccumulation() const;
-    bool     momentsCoverAccumulation() const;
-    uint32_t aovSampleCount() const;
-    uint32_t momentSampleCount() const;
+    // The compact tile-major sums of the shard as the frame gather sees them (rf_comm.hpp: planes 0 .. 3 = S, {albedo.rgb, coverage}, {normal.xyz, depth}, Q): each
+    // plane's device pointer -- nullptr while its channel is off or has not been sized yet -- and per channel whether it is on, whether it holds exactly the accumulated
+    // samples (on from the first sample, at least one accumulated: what the gather requires before it sends them) and its own sample count.
+    struct ShardSums
+    {
+        struct Channel
+        {
+            bool     on, coversAccumulation;
+            uint32_t samples;
+        };
+        const void* planes[4];
+        Channel     aovs, moments;
+        uint32_t    accumulated;
+        bool        ownsTiles;
+    };
+    ShardSums shardSums() const;
     // Zero the accumulation buffer (on the handle's stream) if nothing has been rendered into it since the last reset, so that a
     // reader on the device (the frame exchange) never sees the previous frame's sums.
     void     clearAccumulationIfStale();

@@ -208,6 +208,49 @@ def test_noise_estimate_on_the_root_equals_the_whole_frame_handle_s(duck_pt, mon
     assert _local_world(duck_pt, BIG, world, script, aovs=False)["root finished"] == root
 
 
+RAGGED = (72, 40, 3, 4)     # 3 x 2 tiles, ragged on both edges: a world of 8 leaves ranks 6 and 7 without a tile
+
+
+@functools.lru_cache(maxsize=None)
+def _whole_with_counts():
+    """ONE handle without a tile shard over RAGGED, the AOVs kept with tile counts: its four sums and its per-tile counts.  Computed once; read-only."""
+    r = _handle(_PT["duck"], RAGGED, aovs=False)
+    r.set_aovs(True, tile_counts=True)
+    r.render(RAGGED[2])
+    planes, n = _sums(r)
+    counts = r.read_tile_samples()
+    r.close()
+    for a in planes + [counts]:
+        a.setflags(write=False)
+    return dict(planes=planes, samples=n, counts=counts)
+
+
+@pytest.mark.parametrize("world,root", [(3, 2), (8, 7)])
+def test_one_gather_carries_every_plane_and_the_tile_counts(duck_pt, monkeypatch, world, root):
+    """ONE gather with the AOVs, the moments and the per-tile counts in its group, to a root that is not rank 0 and, at world 8, owns no tile (it passes no buffer of
+    its own and un-tiles from the staging areas alone): the four planes and the counts on the root equal the whole-frame handle's reads bit for bit."""
+    _local(monkeypatch)
+    want = _whole_with_counts()
+    assert _owns_tiles(RAGGED, root, world) == (world == 3)
+
+    def script(rank, r, comm, out):
+        r.set_aovs(True, tile_counts=True)
+        r.render(RAGGED[2])
+        ptr = r.gather_frame(comm, root=root, aovs=True, moments=True, tile_counts=True)
+        assert bool(ptr) == (rank == root)
+        if rank != root:
+            return
+        g = comm.gathered_planes()
+        assert g.get("tile_counts") and g["aovs"] and g["moments"] and (g["width"], g["height"], g["samples"]) == (RAGGED[0], RAGGED[1], want["samples"]), g
+        for plane in range(4):
+            assert np.array_equal(bits(comm.read_plane(r, plane)), bits(want["planes"][plane])), plane
+        got = comm.read_tile_samples()
+        assert got.dtype == want["counts"].dtype and np.array_equal(got, want["counts"]), got
+        out["root finished"] = rank
+
+    assert _local_world(duck_pt, RAGGED, world, script, aovs=False)["root finished"] == root
+
+
 def test_refusals_keep_the_state(duck_pt, monkeypatch):
     """Every refusal is an RF_ERROR_INVALID_ARGUMENT that leaves the handle and the communicator as they were: the valid call that follows succeeds.  Both ranks walk
     the same script (each owns tiles of the 70 x 45 frame), so a gather refused on one is refused on the other and nobody waits."""
