@@ -312,6 +312,62 @@ RF_API int rf_noise_estimate_images(int32_t device_ordinal, uint32_t width, uint
 RF_API int rf_renderer_render_until(rf_renderer* r, float target_mean_error, uint32_t check_every, uint32_t max_frames, uint32_t* frames_rendered,
                                     rf_noise_estimate* last);
 
+/* Bucket sums and the robust mean: a firefly-robust estimate of the image, a median-of-means over K sums of every K-th sample whose trim follows the spread of the
+ * buckets (after Buisine et al. 2021, "Firefly removal in Monte Carlo rendering with adaptive Median of meaNs"; the definition below is this library's own).  No
+ * reference counterpart.  The plain mean S / N is the one estimator a single firefly ruins; this one gives it up to (K - 1) / 2 buckets to discard.
+ *
+ * rf_renderer_set_buckets(r, K): K = 0 (the default: nothing is allocated or launched, image / stats / timings exactly as without) or K odd with 3 <= K <= 15;
+ * anything else is RF_ERROR_INVALID_ARGUMENT and the state is kept.  While on, the handle keeps K more per-pixel f32 planes next to the accumulation, one after
+ * another in one allocation, each laid out like the accumulation:  B_b = {sum r.x, sum r.y, sum r.z, 0} over the samples whose ORDINAL j satisfies j mod K == b,
+ * where r is the radiance the accumulation adds for that sample (wgsl:55-57) and j is the bucket sample count just before that sample -- 0 for the first sample
+ * traced with the buckets on.  Each channel of each bucket is one dependent chain of f32 additions in sample order, no atomics, no contraction: bit-reproducible
+ * whatever the batching, slot order or options.  (S is NOT bitwise the sum of the B_b: that is another addition order.)  K x 16 bytes per pixel of device memory and
+ * nothing per path slot (rf_renderer_memory_info's figures do not change); under a tile shard the planes are shard-compact, as Q is.  S, Q, the AOV sums and the
+ * ray counts are bit for bit what they are with the buckets off.  The buckets keep their own sample count -- the samples traced while they were on -- and are
+ * cleared, with the count set to 0, when the image is (a change through rf_renderer_set_render_parameters, a new tile shard, a newly bound accumulation buffer) and
+ * when K changes.  Turned on partway through an accumulation, they cover only the later samples.
+ * The buckets are for the uniform state: while they are on, rf_renderer_render_adaptive and rf_comm_render_adaptive return RF_ERROR_INVALID_ARGUMENT (the message
+ * names the buckets) before anything is traced or exchanged, and rf_renderer_set_buckets(K > 0) is refused in the non-uniform state.  rf_renderer_render,
+ * rf_renderer_render_until, rf_renderer_set_tile_shard and rf_renderer_gather_frame work as before; the frame gather does not carry the bucket planes.
+ * rf_renderer_read_buckets: K x width*height*4 floats, plane after plane, each row-major (the layout of rf_renderer_read_accumulation; may be NULL), K and the bucket
+ * sample count (either may be NULL).  With a tile shard set, this rank's pixels and zeros elsewhere: the sum of the ranks' reads is the whole frame.  Buckets off:
+ * nothing is written to `buckets`, K = 0, count = 0.
+ *
+ * The robust mean.  Inputs: the K bucket sums of one accumulation and their count N >= K.  All arithmetic is f32, one IEEE operation at a time in the order written
+ * (+ - * /, floor, compares and selects; no transcendentals): a numpy float32 restatement reproduces M and trim bit for bit.  Per pixel:
+ *   bucket sizes and means:  n_b = N / K + (b < N mod K ? 1 : 0) in integer arithmetic;  m_b = B_b.rgb / float(n_b) per channel
+ *   sort key:                l_b = (m_b.r + m_b.g) + m_b.b;  key_b = (l_b <= FLT_MAX) ? l_b : +inf   (a NaN becomes +inf)
+ *   order:                   the buckets ascending by key, ties by bucket index (a stable sort): r_0 ... r_{K-1}
+ *   Gini coefficient:        num = sum over i = 0 .. K-1 of float(2i - (K - 1)) key_{r_i}, each term one multiply, added in i order from +0;
+ *                            den = float(K) (sum over i of key_{r_i}, in i order from +0);  G = (den > 0) ? num / den : 0
+ *   trim count:              t = G (float(K) 0.5f);  c = (t >= 0) ? min(uint(floor(t)), (K - 1) / 2) : (K - 1) / 2  -- the minimum is taken before the conversion (t >=
+ *                            float((K - 1) / 2) gives (K - 1) / 2), so a huge t is never converted; a NaN t compares false: a pixel with a non-finite bucket takes
+ *                            the median
+ *   output:                  M.rgb = (sum over i = c .. K-1-c of m_{r_i}, per channel, in i order from +0) / float(K - 2c);  M.a = 1;  trim = c (uint8)
+ * All buckets equal: G = 0, c = 0, the mean of the means.  One bucket far above the rest: G approaches (K - 1) / K and c grows until the outlier is cut; c = (K - 1) / 2
+ * is the median of the means.  The estimate is biased low on pixels whose samples are skewed, the more so the fewer samples a bucket holds.
+ *
+ * rf_renderer_robust_mean: enqueued on the handle's stream over its own bucket sums.  It keeps a snapshot -- M, trim, the BGRA8 texels (kTonemap with
+ * accumulatedSamples = 1 and the handle's exposure) and the count N; one float4, one byte and one u32 per pixel -- allocated by the first call and dropped whenever
+ * the bucket sums are cleared.  RF_ERROR_INVALID_ARGUMENT when the buckets are off, when the bucket sample count differs from the accumulated count (turned on
+ * partway through), when N < K, when a tile shard is set (use rf_robust_mean_images on the sum of the ranks' rf_renderer_read_buckets) or in the non-uniform state.
+ * Leaves every sum, the denoise snapshot, the stats and later samples untouched.
+ * rf_renderer_read_robust_mean: row-major width*height*4 mean floats, the BGRA8 texels, one trim count per pixel and the snapshot's sample count; any pointer may be
+ * NULL.  RF_ERROR_INVALID_ARGUMENT without a snapshot.
+ * rf_robust_mean_images: the same kernel over host bucket planes (K x width*height*4 floats, each plane row-major, e.g. the sum of several ranks' reads) of `samples`
+ * samples on device device_ordinal; the outputs may be NULL.  Synchronous.  A NULL input, a zero size, a K that is not odd in 3 .. 15 and samples < K are refused
+ * before any device call.  Row-major and tile-major inputs give bit-identical results.
+ * rf_renderer_denoise_robust: rf_renderer_robust_mean, then the a-trous filter of rf_renderer_denoise, whose definition changes in exactly one place: in prep,
+ * c = M.rgb instead of S.rgb / Nf (a = AC.rgb / Nf and m = ND.xyz / Nf as ever, everything after prep as written; L = 0 returns M).  The result is the ordinary denoise
+ * snapshot (rf_renderer_read_denoised).  Refused as rf_renderer_denoise is, and also when rf_renderer_robust_mean would be.  rf_renderer_denoise itself is unchanged. */
+RF_API int rf_renderer_set_buckets(rf_renderer* r, uint32_t K);
+RF_API int rf_renderer_read_buckets(rf_renderer* r, float* buckets, uint32_t* K, uint32_t* bucket_sample_count);
+RF_API int rf_renderer_robust_mean(rf_renderer* r);
+RF_API int rf_renderer_read_robust_mean(rf_renderer* r, float* rgba, uint32_t* bgra8, uint8_t* trim, uint32_t* sample_count);
+RF_API int rf_robust_mean_images(int32_t device_ordinal, uint32_t width, uint32_t height, uint32_t K, uint32_t samples, const float* buckets, float exposure,
+                                 float* out_rgba, uint32_t* out_bgra8, uint8_t* out_trim);
+RF_API int rf_renderer_denoise_robust(rf_renderer* r, const rf_denoise_parameters* params);
+
 /* Tile-adaptive sampling: a render call that keeps sampling only the 32x32 tiles that are still noisy, and the per-tile sample count that the reads then honour.
  * No reference counterpart.  rf_renderer_render_adaptive: the whole frame only (no tile shard; across ranks: rf_comm_render_adaptive, below); needs the moments on from the first sample and the AOVs off, or on with RF_AOV_TILE_COUNTS
  * (from the first sample as well).

@@ -576,6 +576,20 @@ def denoise_tiles(color_sum, albedo_coverage, normal_depth, tile_samples, exposu
     return rgba[..., :3], bgra
 
 
+def robust_mean_images(buckets, samples, exposure=1.0, device_ordinal=0):
+    """rf_robust_mean_images: the firefly-robust mean over (K, H, W, 4) f32 bucket sums held on the host (e.g. the sum of several ranks' read_buckets) of `samples`
+    >= K samples, K odd in 3 .. 15.  -> dict(mean (H,W,3) f32, bgra8 (H,W) u32 display texels under `exposure`, trim (H,W) u8, samples)."""
+    buckets = _f32(buckets)
+    if buckets.ndim != 4 or buckets.shape[3] != 4:
+        raise ValueError("robust_mean_images: the bucket sums must be a (K, H, W, 4) array")
+    k, h, w = buckets.shape[:3]
+    rgba = np.zeros((h, w, 4), np.float32)
+    bgra = np.zeros((h, w), np.uint32)
+    trim = np.zeros((h, w), np.uint8)
+    check(lib.rf_robust_mean_images(device_ordinal, w, h, k, samples, _ptr(buckets), exposure, _ptr(rgba), _ptr(bgra), _ptr(trim)))
+    return dict(mean=rgba[..., :3], bgra8=bgra, trim=trim, samples=int(samples))
+
+
 def _noise_result(est, error_map, tile_sum, tile_max):
     out = {k: getattr(est, k) for k, _ in est._fields_}
     out.update(error_map=error_map, tile_sum=tile_sum, tile_max=tile_max)
@@ -722,6 +736,40 @@ class ReferencePathTracer:
         n = C.c_uint32(0)
         check(lib.rf_renderer_read_moments(self._h, _ptr(q), C.byref(n)))
         return q, n.value
+
+    # bucket sums and the firefly-robust mean (include/rayfinder_amd.h states what the buckets hold and the combine's arithmetic)
+    def set_buckets(self, k):
+        """Keep k bucket sums (k odd, 3 .. 15; 0: off, the default): bucket b sums the radiance of the samples whose ordinal is b mod k.  Any change clears them.
+        The uniform state only: render_adaptive is refused while they are on."""
+        check(lib.rf_renderer_set_buckets(self._h, int(k)))
+
+    def read_buckets(self):
+        """-> ((K, H, W, 4) f32 bucket sums {r, g, b, 0} in sample order, the bucket sample count); K = 0 while the buckets are off"""
+        k, n = C.c_uint32(0), C.c_uint32(0)
+        check(lib.rf_renderer_read_buckets(self._h, None, C.byref(k), C.byref(n)))
+        b = np.zeros((k.value, self._params.height, self._params.width, 4), np.float32)
+        if k.value:
+            check(lib.rf_renderer_read_buckets(self._h, _ptr(b), C.byref(k), C.byref(n)))
+        return b, n.value
+
+    def robust_mean(self):
+        """Combine the bucket sums into the robust mean (needs the buckets on from the first sample, at least K samples, no tile shard); read_robust_mean reads it."""
+        check(lib.rf_renderer_robust_mean(self._h))
+
+    def read_robust_mean(self):
+        """-> dict(mean (H,W,3) f32, bgra8 (H,W) u32 display texels, trim (H,W) u8: the buckets cut from each end, samples: the count of the combined accumulation)"""
+        h, w = self._params.height, self._params.width
+        rgba = np.zeros((h, w, 4), np.float32)
+        bgra = np.zeros((h, w), np.uint32)
+        trim = np.zeros((h, w), np.uint8)
+        n = C.c_uint32(0)
+        check(lib.rf_renderer_read_robust_mean(self._h, _ptr(rgba), _ptr(bgra), _ptr(trim), C.byref(n)))
+        return dict(mean=rgba[..., :3], bgra8=bgra, trim=trim, samples=n.value)
+
+    def denoise_robust(self, **params):
+        """robust_mean, then denoise with the robust mean in place of the plain mean (needs what both need); read_denoised reads the result.  Keyword arguments as
+        for denoise."""
+        check(lib.rf_renderer_denoise_robust(self._h, C.byref(_denoise_parameters(params))))
 
     def noise_estimate(self):
         """The noise estimate over the accumulation and the moments (needs the moments on from the first sample, >= 2 samples, no tile shard).

@@ -148,6 +148,12 @@ SIGNATURES = {
     "rf_denoise_tiles": (C.c_int, [C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
     "rf_renderer_set_moments": (C.c_int, [C.c_void_p, C.c_int]),
     "rf_renderer_read_moments": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
+    "rf_renderer_set_buckets": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "rf_renderer_read_buckets": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "rf_renderer_robust_mean": (C.c_int, [C.c_void_p]),
+    "rf_renderer_read_robust_mean": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
+    "rf_robust_mean_images": (C.c_int, [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rf_renderer_denoise_robust": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rf_renderer_noise_estimate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rf_noise_estimate_images": (C.c_int, [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rf_renderer_render_until": (C.c_int, [C.c_void_p, C.c_float, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p]),

@@ -4,6 +4,7 @@
 //           [--denoise-iterations L] [--denoise-sigma-color s] [--denoise-sigma-normal s] [--denoise-sigma-depth s]
 //           [--noise-map m.pfm] [--noise-target t] [--noise-check-every k] [--gpus N]
 //           [--adaptive T] [--adaptive-min n] [--adaptive-every n] [--sample-map s.pfm]
+//           [--buckets K] [--robust-mean out.pfm|out.png] [--trim-map t.pfm] [--denoise-robust d.png]
 // Offline counterpart of the interactive `pt` app (src/pt/main.cpp): same default camera pose,
 // sky and exposure; renders all samples and writes the tonemapped image (and optionally the
 // mean radiance as PFM).  --gpus N: one host thread per GPU, the image tile-sharded across them, one RCCL
@@ -22,6 +23,10 @@
 // With --aov-* / --denoise* the AOVs are kept per tile count (RF_AOV_FIRST_HIT | RF_AOV_TILE_COUNTS): the AOV PFMs are divided by each pixel's tile count, and the
 // denoiser (rf_renderer_denoise) divides every pixel by its own tile's count before it filters.
 // --sample-map s.pfm: the sample count of every pixel's tile (a one-channel PFM)
+// --buckets K: keep K bucket sums (rf_renderer_set_buckets; K odd, 3 .. 15) from the first sample.  --robust-mean: the firefly-robust mean of the frame
+// (rf_renderer_robust_mean) as a PFM, or tonemapped as a PNG; --trim-map: how many buckets the combine cut from each end, per pixel (a one-channel PFM);
+// --denoise-robust: the robust mean through the denoiser (rf_renderer_denoise_robust; turns the AOVs on, takes the --denoise-* parameters) as a PNG.  These three need
+// --buckets.  --gpus 1 only and not with --adaptive: the bucket planes are not carried by the frame gather and keep one sample count for the frame.
 // --noise-target t [--noise-check-every k]: stop as soon as the frame's mean error is <= t, checked every k samples (default 8), at --spp at the latest
 // (rf_renderer_render_until).  One GPU only: stopping several ranks in step is not implemented.
 #include "cli_common.hpp"
@@ -48,6 +53,9 @@ int main(int argc, char** argv)
                     "  --adaptive: sample every 32x32 tile until its mean error is <= T (checked every n samples, default 8; --spp at the latest); --sample-map: the\n"
                     "  tiles' sample counts (1-channel PFM).  --gpus 1 only, not with --noise-target; with --aov-* / --denoise* the AOVs and the denoiser use each\n"
                     "  tile's own sample count\n"
+                    "                 [--buckets K] [--robust-mean out.pfm|out.png] [--trim-map t.pfm] [--denoise-robust d.png]\n"
+                    "  --buckets: keep K bucket sums (K odd, 3 .. 15); --robust-mean: the firefly-robust median-of-means image (PFM, or PNG tonemapped); --trim-map: the\n"
+                    "  buckets cut from each end per pixel (1-channel PFM); --denoise-robust: the robust mean through the denoiser.  --gpus 1 only, not with --adaptive\n"
                     "                 [--noise-map m.pfm] [--noise-target t] [--noise-check-every k]\n"
                     "  --noise-map: the per-pixel relative standard error of the frame (1-channel PFM); --noise-target: stop once the frame's mean error is <= t,\n"
                     "  checked every k samples (default 8), at --spp at the latest (one GPU only)\n");
@@ -69,6 +77,8 @@ int main(int argc, char** argv)
     bool        adaptive = false;
     rf_adaptive_parameters adaptiveParams{0.0f, 8u, 0u, 0u};
     rf_adaptive_result     adaptiveResult{};
+    uint32_t    buckets = 0;
+    std::string robustMean, trimMap, denoiseRobust;
     for (int i = 2; i + 1 < argc; i += 2)
     {
         const std::string k = argv[i];
@@ -101,6 +111,10 @@ int main(int argc, char** argv)
         else if (k == "--adaptive-min") adaptiveParams.min_samples = static_cast<uint32_t>(std::max(0, std::atoi(val)));
         else if (k == "--adaptive-every") adaptiveParams.check_every = static_cast<uint32_t>(std::max(1, std::atoi(val)));
         else if (k == "--sample-map") sampleMap = val;
+        else if (k == "--buckets") buckets = static_cast<uint32_t>(std::max(0, std::atoi(val)));
+        else if (k == "--robust-mean") robustMean = val;
+        else if (k == "--trim-map") trimMap = val;
+        else if (k == "--denoise-robust") denoiseRobust = val;
         else
         {
             std::fprintf(stderr, "unknown option %s\n", k.c_str());
@@ -115,6 +129,18 @@ int main(int argc, char** argv)
     if (adaptive && (gpus > 1 || noiseTargetSet))
     {
         std::fprintf(stderr, "--adaptive needs --gpus 1 and does not go with --noise-target (the per-tile counts are carried neither by the frame gather nor by render_until)\n");
+        return 1;
+    }
+    const bool robust = !robustMean.empty() || !trimMap.empty() || !denoiseRobust.empty();
+    if ((buckets != 0u || robust) && (gpus > 1 || adaptive))
+    {
+        std::fprintf(stderr, "--buckets / --robust-mean / --trim-map / --denoise-robust need --gpus 1 and do not go with --adaptive (the bucket sums are not carried by the "
+                             "frame gather and keep one sample count for the frame)\n");
+        return 1;
+    }
+    if (robust && buckets == 0u)
+    {
+        std::fprintf(stderr, "--robust-mean / --trim-map / --denoise-robust need --buckets K (K odd, 3 .. 15)\n");
         return 1;
     }
     rf_pt_format*     pt = loadScene(argv[1]);
@@ -150,7 +176,13 @@ int main(int argc, char** argv)
     // first-hit AOV sums of the whole frame ({albedo, coverage}, {normal, depth}), read on rank 0 when a file is made from them: from the handle, or (several ranks)
     // from the planes the gather left there
     const bool         aovFiles = !aovAlbedo.empty() || !aovNormal.empty() || !aovDepth.empty();
-    const bool         aovs = aovFiles || denoising;
+    const bool         aovs = aovFiles || denoising || !denoiseRobust.empty();
+    // the robust mean's snapshot (rank 0; one GPU): the mean, its display texels, the trim counts, and the robust mean through the denoiser
+    std::vector<float>    robustRgba;
+    std::vector<uint32_t> robustBgra, robustDenoisedBgra;
+    std::vector<uint8_t>  robustTrim;
+    if (robust) robustRgba.resize(static_cast<size_t>(W) * H * 4), robustBgra.resize(static_cast<size_t>(W) * H), robustTrim.resize(static_cast<size_t>(W) * H);
+    if (!denoiseRobust.empty()) robustDenoisedBgra.resize(static_cast<size_t>(W) * H);
     std::vector<float>    denoisedRgba;
     std::vector<uint32_t> denoisedBgra;
     if (denoising) denoisedRgba.resize(static_cast<size_t>(W) * H * 4), denoisedBgra.resize(static_cast<size_t>(W) * H);
@@ -176,6 +208,7 @@ int main(int argc, char** argv)
         // (--adaptive: the AOV sums follow the per-tile counts)
         if (aovs) rfCheck(rf_renderer_set_aovs(renderer, RF_AOV_FIRST_HIT | (adaptive ? RF_AOV_TILE_COUNTS : 0u)), "AOVs");
         if (noise) rfCheck(rf_renderer_set_moments(renderer, 1), "moments");
+        if (buckets != 0u) rfCheck(rf_renderer_set_buckets(renderer, buckets), "buckets");
         const auto t0 = std::chrono::steady_clock::now();
         if (adaptive) rfCheck(rf_renderer_render_adaptive(renderer, &adaptiveParams, &adaptiveResult), "adaptive render");
         else if (noiseTargetSet) rfCheck(rf_renderer_render_until(renderer, noiseTarget, noiseCheckEvery, spp, &sppReached, &estimate), "render to the noise target");
@@ -228,6 +261,16 @@ int main(int argc, char** argv)
                     rfCheck(rf_renderer_denoise(renderer, &denoiseParams), "denoise");
                     rfCheck(rf_renderer_read_denoised(renderer, denoisedRgba.data(), denoisedBgra.data(), &n), "read denoised");
                 }
+                if (robust)
+                {
+                    rfCheck(rf_renderer_robust_mean(renderer), "robust mean");
+                    rfCheck(rf_renderer_read_robust_mean(renderer, robustRgba.data(), robustBgra.data(), robustTrim.data(), &n), "read robust mean");
+                }
+                if (!denoiseRobust.empty())
+                {
+                    rfCheck(rf_renderer_denoise_robust(renderer, &denoiseParams), "denoise robust");
+                    rfCheck(rf_renderer_read_denoised(renderer, nullptr, robustDenoisedBgra.data(), &n), "read denoised");
+                }
             }
         }
         if (comm) rf_comm_destroy(comm);
@@ -250,15 +293,20 @@ int main(int argc, char** argv)
         std::printf("noise at %u spp: mean error %.6g, max error %.6g in tile %u, %llu non-finite pixel(s)\n", estimate.samples, estimate.mean_error, estimate.max_error,
                     estimate.worst_tile, static_cast<unsigned long long>(estimate.nonfinite_pixels));
 
-    std::vector<uint8_t> rgba(bgra.size() * 4);
-    for (size_t i = 0; i < bgra.size(); ++i)
-    {
-        rgba[4 * i] = static_cast<uint8_t>(bgra[i] >> 16);
-        rgba[4 * i + 1] = static_cast<uint8_t>(bgra[i] >> 8);
-        rgba[4 * i + 2] = static_cast<uint8_t>(bgra[i]);
-        rgba[4 * i + 3] = 255;
-    }
-    if (!writePngRgba(out, rgba.data(), W, H)) return 1;
+    const auto writeBgraPng = [&](const std::string& path, const std::vector<uint32_t>& texels) {
+        std::vector<uint8_t> px(texels.size() * 4);
+        for (size_t i = 0; i < texels.size(); ++i)
+        {
+            px[4 * i] = static_cast<uint8_t>(texels[i] >> 16);
+            px[4 * i + 1] = static_cast<uint8_t>(texels[i] >> 8);
+            px[4 * i + 2] = static_cast<uint8_t>(texels[i]);
+            px[4 * i + 3] = 255;
+        }
+        return writePngRgba(path, px.data(), W, H);
+    };
+    if (!writeBgraPng(out, bgra)) return 1;
+    if (!robustMean.empty() && !(endsWith(robustMean, ".png") ? writeBgraPng(robustMean, robustBgra) : writePfm(robustMean, robustRgba.data(), W, H, 1.0f))) return 1;
+    if (!denoiseRobust.empty() && !writeBgraPng(denoiseRobust, robustDenoisedBgra)) return 1;
     if (!pfm.empty()) writePfm(pfm, acc.data(), W, H, adaptive ? 1.0f : 1.0f / static_cast<float>(std::max(sppReached, 1u))); // (--adaptive: acc holds the per-tile mean)
     if (denoising)
     {
@@ -290,6 +338,7 @@ int main(int argc, char** argv)
         return true;
     };
     if (!write(noiseMap, 1, [&](size_t i, uint32_t) { return errorMap[i / 4]; })) return 1;
+    if (!write(trimMap, 1, [&](size_t i, uint32_t) { return static_cast<float>(robustTrim[i / 4]); })) return 1;
     if (!sampleMap.empty() && tileSamples.empty()) tileSamples.assign(static_cast<size_t>((W + 31) / 32) * ((H + 31) / 32), sppReached); // (several ranks: one count)
     if (!write(sampleMap, 1, [&](size_t i, uint32_t) { return static_cast<float>(tileSamples[((i / 4) / W / 32) * ((W + 31) / 32) + ((i / 4) % W) / 32]); })) return 1;
     if (aovFiles)

@@ -366,6 +366,68 @@ int rf_renderer_read_moments(rf_renderer* r, float* sumsq4, uint32_t* moment_sam
     });
 }
 
+int rf_renderer_set_buckets(rf_renderer* r, uint32_t K)
+{
+    return guarded([&] {
+        require(K == 0u || (K % 2u == 1u && K >= 3u && K <= 15u), "set_buckets: K must be 0 (off) or odd with 3 <= K <= 15");
+        require(r, "null argument");
+        r->impl->setBuckets(K);
+        return RF_OK;
+    });
+}
+
+int rf_renderer_read_buckets(rf_renderer* r, float* buckets, uint32_t* K, uint32_t* bucket_sample_count)
+{
+    return guarded([&] {
+        require(r, "null argument");
+        r->impl->readBuckets(buckets, K, bucket_sample_count);
+        return RF_OK;
+    });
+}
+
+int rf_renderer_robust_mean(rf_renderer* r)
+{
+    return guarded([&] {
+        require(r, "null argument");
+        r->impl->robustMean();
+        return RF_OK;
+    });
+}
+
+int rf_renderer_read_robust_mean(rf_renderer* r, float* rgba, uint32_t* bgra8, uint8_t* trim, uint32_t* sample_count)
+{
+    return guarded([&] {
+        require(r, "null argument");
+        r->impl->readRobustMean(rgba, bgra8, trim, sample_count);
+        return RF_OK;
+    });
+}
+
+int rf_robust_mean_images(int32_t device_ordinal, uint32_t width, uint32_t height, uint32_t K, uint32_t samples, const float* buckets, float exposure, float* out_rgba,
+                          uint32_t* out_bgra8, uint8_t* out_trim)
+{
+    return guarded([&] {
+        require(buckets, "null argument");
+        require(width > 0 && height > 0, "image size must be non-zero");
+        require(static_cast<uint64_t>(width) * height < (1ull << 31), "image too large");
+        require(K % 2u == 1u && K >= 3u && K <= 15u, "K must be odd with 3 <= K <= 15");
+        require(samples >= K, "every bucket needs a sample: the sample count must be >= K");
+        require(std::isfinite(exposure), "exposure must be finite");
+        rf::robustMeanImages(device_ordinal, width, height, K, samples, buckets, exposure, out_rgba, out_bgra8, out_trim);
+        return RF_OK;
+    });
+}
+
+int rf_renderer_denoise_robust(rf_renderer* r, const rf_denoise_parameters* params)
+{
+    return guarded([&] {
+        const rf::DenoiseParameters p = toDenoiseParams(params);
+        require(r, "null argument");
+        r->impl->denoiseRobust(p);
+        return RF_OK;
+    });
+}
+
 int rf_renderer_noise_estimate(rf_renderer* r, rf_noise_estimate* out, float* error_map, float* tile_sum, float* tile_max)
 {
     return guarded([&] {

@@ -4,6 +4,7 @@
 // fixed sequence of operations.
 //   kDenoisePrep    one lane per pixel: demodulated irradiance {e, ℓ}, guide {n, z}, a + εa (or, for L = 0, the mean itself)
 //   kDenoisePrepTiles  the same with the sample count of the pixel's 32x32 tile (a frame of rf_renderer_render_adaptive, rf_denoise_tiles)
+//   kDenoisePrepMean   the same with the colour c taken from a row-major mean image (the robust mean, rf_renderer_denoise_robust) instead of S / Nf
 //   kDenoiseAtrous  one lane per pixel, 16x16-pixel workgroups of four 8x8-pixel waves (the 25 taps of a wave touch few cache lines); the last pass
 //                   remodulates and writes the mean
 // The display image is the existing kTonemap over the mean with accumulatedSamples = 1.
@@ -34,13 +35,15 @@ __device__ __forceinline__ float tukey(float x)
     return x < 1.0f ? m * m : 0.0f; // (NaN: 0)
 }
 
-// prep of pixel i = (x, y) with its sample count as a float: shared by kDenoisePrep (one count for the frame) and kDenoisePrepTiles (the count of the pixel's tile)
+// prep of pixel i = (x, y) with its sample count as a float: shared by kDenoisePrep (one count for the frame), kDenoisePrepTiles (the count of the pixel's tile) and
+// kDenoisePrepMean (MEAN: colorSum is a row-major image of means and c = its rgb as it is; the AOV sums are divided by nf as ever)
+template<bool MEAN = false>
 __device__ __forceinline__ void prepPixel(const float4* colorSum, const float4* albedoCoverage, const float4* normalDepth, uint32_t i, uint32_t x, uint32_t y, uint32_t tilesX,
                                           float nf, float4* e, float4* guide, float4* albedo, float4* meanOut)
 {
     const uint32_t src = tilesX ? tileMajorIndex(x, y, tilesX) : i;
-    const float4   S = colorSum[src];
-    const Vec3     c = vec3(S.x / nf, S.y / nf, S.z / nf); // (kTonemap's division)
+    const float4   S = colorSum[MEAN ? i : src];
+    const Vec3     c = MEAN ? vec3(S.x, S.y, S.z) : vec3(S.x / nf, S.y / nf, S.z / nf); // (kTonemap's division)
     if (meanOut) // L = 0: the mean, exactly
     {
         meanOut[i] = make_float4(c.x, c.y, c.z, 1.0f);
@@ -86,6 +89,16 @@ __global__ __launch_bounds__(256) void kDenoisePrepTiles(const float4* colorSum,
     const uint32_t y = i / width, x = i - y * width;
     const float    nf = static_cast<float>(tileSamples[(y >> 5) * frameTilesX + (x >> 5)]);
     prepPixel(colorSum, albedoCoverage, normalDepth, i, x, y, tilesX, nf, e, guide, albedo, meanOut);
+}
+
+// The same with the colour given: c = mean[i].rgb (row-major, the robust mean of rf_robust.hip) instead of S.rgb / Nf; a and m are AC.rgb / Nf and ND.xyz / Nf.
+__global__ __launch_bounds__(256) void kDenoisePrepMean(const float4* mean, const float4* albedoCoverage, const float4* normalDepth, uint32_t width, uint32_t height,
+                                                        uint32_t tilesX, float nf, float4* e, float4* guide, float4* albedo, float4* meanOut)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= width * height) return;
+    const uint32_t y = i / width, x = i - y * width;
+    prepPixel<true>(mean, albedoCoverage, normalDepth, i, x, y, tilesX, nf, e, guide, albedo, meanOut);
 }
 
 // One pass of step `step` = 2^i: sc2 = (σc σc) 2^-i, szs = σz step.  last: out = the mean {e' (a + εa), 1} (background: {c, 1}); else out = {e', ℓ'}.
@@ -167,7 +180,7 @@ void DenoiseWork::reserve(uint64_t n, hipStream_t stream)
 }
 
 void enqueueDenoise(hipStream_t stream, DenoiseWork& w, const float4* colorSum, const float4* albedoCoverage, const float4* normalDepth, uint32_t width,
-                    uint32_t height, uint32_t tilesX, uint32_t samples, const DenoiseParameters& p, float exposure, const uint32_t* tileSamples)
+                    uint32_t height, uint32_t tilesX, uint32_t samples, const DenoiseParameters& p, float exposure, const uint32_t* tileSamples, const float4* mean)
 {
     const uint32_t n = width * height;
     w.reserve(n, stream);
@@ -175,7 +188,9 @@ void enqueueDenoise(hipStream_t stream, DenoiseWork& w, const float4* colorSum, 
     const dim3  prepGrid((n + 255) / 256);
     // prep into (e, guide, albedo), or for L = 0 into the mean: with the frame's one count, or with each pixel's tile's own
     const auto prep = [&](float4* e, float4* guide, float4* albedo, float4* meanOut) {
-        if (tileSamples)
+        if (mean)
+            hipLaunchKernelGGL(kDenoisePrepMean, prepGrid, dim3(256), 0, stream, mean, albedoCoverage, normalDepth, width, height, tilesX, nf, e, guide, albedo, meanOut);
+        else if (tileSamples)
             hipLaunchKernelGGL(kDenoisePrepTiles, prepGrid, dim3(256), 0, stream, colorSum, albedoCoverage, normalDepth, width, height, tilesX, tileSamples,
                                TileGrid(width, height).tilesX, e, guide, albedo, meanOut);
         else

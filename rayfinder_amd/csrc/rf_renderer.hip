@@ -25,6 +25,7 @@
 #include "rf_denoise.hpp"
 #include "rf_kernels.hpp"
 #include "rf_noise.hpp"
+#include "rf_robust.hpp"
 #include "rf_sums.hpp"
 
 #include <map>
@@ -126,6 +127,7 @@ struct SumChannel
     uint32_t             samples = 0;  // samples summed since it was last restarted
     DeviceBuffer<float4> buffers[2];   // the AOVs: {albedo.rgb, coverage}, {normal.xyz, depth}; the moments: [0]; the image: none (Impl::image)
     uint32_t             numBuffers = 0;
+    uint32_t             planes = 1;   // float4 per pixel in each buffer, plane after plane (the bucket sums: K)
 
     SumChannel(bool on_, uint32_t numBuffers_) : on(on_), numBuffers(numBuffers_) {}
     // the sums start again: zeroed before the next sample, sized for the shard then
@@ -144,12 +146,13 @@ struct SumChannel
     void zeroIfStale(hipStream_t stream, uint64_t pixelsPadded)
     {
         if (!on || !dirty) return;
-        if (numBuffers != 0u && buffers[0].count < pixelsPadded)
+        const uint64_t texels = pixelsPadded * planes;
+        if (numBuffers != 0u && buffers[0].count < texels)
         {
             RF_HIP(hipStreamSynchronize(stream)); // (a smaller buffer may still be read by the last batch or estimate)
-            for (uint32_t i = 0; i < numBuffers; ++i) buffers[i].alloc(pixelsPadded);
+            for (uint32_t i = 0; i < numBuffers; ++i) buffers[i].alloc(texels);
         }
-        for (uint32_t i = 0; i < numBuffers; ++i) RF_HIP(hipMemsetAsync(buffers[i].ptr, 0, pixelsPadded * sizeof(float4), stream));
+        for (uint32_t i = 0; i < numBuffers; ++i) RF_HIP(hipMemsetAsync(buffers[i].ptr, 0, texels * sizeof(float4), stream));
         dirty = false;
     }
 };
@@ -199,6 +202,15 @@ struct Renderer::Impl
     float4*                 aovAlbedoCoverage() const { return aovSums.buffers[0].ptr; }
     float4*                 aovNormalDepth() const { return aovSums.buffers[1].ptr; }
     float4*                 moments() const { return momentSums.buffers[0].ptr; }
+    // bucket sums (rf_renderer_set_buckets; off by default: nothing is allocated or launched then): bucketSums.planes = K planes of the shard's tiles x 1024 float4 each
+    // in one buffer, plane b = the radiance sum over the samples of ordinal b mod K; the robust mean's buffers and the snapshot they hold -- valid until the bucket
+    // sums are restarted
+    SumChannel              bucketSums{false, 1};
+    float4*                 bucketPlanes() const { return bucketSums.buffers[0].ptr; }
+    size_t                  bucketStride() const { return tiles.size() * 1024; }
+    RobustWork              robustWork;
+    bool                    robustValid = false;
+    uint32_t                robustSamples = 0;
     // the denoiser (rf_renderer_denoise): its work buffers, allocated by the first denoise, and the snapshot they hold -- valid until the AOV sums are restarted
     DenoiseWork             denoiseWork;
     bool                    denoisedValid = false;
@@ -434,6 +446,13 @@ struct Renderer::Impl
         imageSums.restart();
         restartAovs();
         momentSums.restart();
+        restartBuckets();
+    }
+    // (also when K changes: the snapshot was combined from these sums)
+    void restartBuckets()
+    {
+        bucketSums.restart();
+        robustValid = false;
     }
     // (also when the AOV switch changes: the snapshot was filtered with these sums as guides)
     void restartAovs()
@@ -549,6 +568,7 @@ struct Renderer::Impl
         bool     runs, tileList;
         bool     shardList; // a tile list under a tile shard: the sums are addressed through the slots behind the ids (SumAddressing::ShardList)
         uint32_t accumulateKernel, accumulatePixels, aovPixels, momentPixels; // pixels per workgroup of the sums' launches; 0: that sum is not launched
+        uint32_t bucketPixels, buckets, bucketPhase; // the bucket sums' launch: K planes, the batch's sample k onto plane (bucketPhase + k) mod K
     };
     struct BouncePlan
     {
@@ -769,6 +789,10 @@ struct Renderer::Impl
         // radiance second moments: a launch of their own unless the tile-list kernel adds them with the image
         b.aovPixels = (aovSums.on && b.numBounces != 0u) ? (b.runs ? kAovPixels : perThread) : 0u;
         b.momentPixels = (!b.tileList && momentSums.on) ? (b.runs ? kMomentPixels : perThread) : 0u;
+        // the bucket sums (the uniform state only: never under a tile list): the batch's first sample has ordinal bucketSums.samples
+        b.bucketPixels = (!b.tileList && bucketSums.on) ? (b.runs ? kBucketPixels : perThread) : 0u;
+        b.buckets = bucketSums.on ? bucketSums.planes : 0u;
+        b.bucketPhase = bucketSums.on ? bucketSums.samples % bucketSums.planes : 0u;
         return b;
     }
     // Is a cached any-hit launch of the handle's NEXT batch free to run behind kShadowFirstLook, as far as the books a batch keeps go?  traceBatch's own bookkeeping,
@@ -924,6 +948,7 @@ struct Renderer::Impl
         zeroImageIfStale(pixelsPadded * sizeof(float4));
         aovSums.zeroIfStale(stream, pixelsPadded);
         momentSums.zeroIfStale(stream, pixelsPadded);
+        bucketSums.zeroIfStale(stream, pixelsPadded);
     }
 
     // Samples per batch for `todo` samples of `pixelsPadded` path slots per sample (the shard's tiles, or the active tiles of render_adaptive), with the path state
@@ -1014,6 +1039,7 @@ struct Renderer::Impl
         accumulated += n;
         if (aovSums.on) aovSums.samples += n;
         if (momentSums.on) momentSums.samples += n;
+        if (bucketSums.on) bucketSums.samples += n;
         return n;
     }
 
@@ -1076,7 +1102,7 @@ struct Renderer::Impl
             launchWide(t, wide, WideArgs{io.ps, io.out, io.words.shadowCount(io.bounce, p.shadowSource), io.words.cursorShadow(io.bounce), kTMax, io.persistentGrid, io.blocks});
     }
     // the batch's sums in sample order: the image, then the first-hit AOV sums and the radiance second moments (timed with the accumulation: rf_stats has no entry of
-    // their own for them) -- or, under a tile list, the image and the moments from one launch, then the AOV sums
+    // their own for them) -- or, under a tile list, the image and the moments from one launch, then the AOV sums --, then the bucket sums (their own argument list)
     void enqueueSums(const BatchPlan& b, const FrameParams& fp, const PathStreams& ps)
     {
         struct SumLaunch
@@ -1104,6 +1130,9 @@ struct Renderer::Impl
             const SumLaunch& l = launches[i];
             hipLaunchKernelGGL(l.kernel, sumGrid(l.pixels), dim3(l.runs ? 64u : static_cast<uint32_t>(kBlock)), 0, stream, fp, tileIds.ptr, l.src, l.dst0, l.dst1);
         }
+        if (b.bucketPixels != 0u)
+            hipLaunchKernelGGL(bucketKernel(b.runs), sumGrid(b.bucketPixels), dim3(b.runs ? 64u : static_cast<uint32_t>(kBlock)), 0, stream, fp, tileIds.ptr, ps.rad, bucketPlanes(),
+                               bucketStride(), b.buckets, b.bucketPhase);
     }
 
     // Trace `numSamples` consecutive samples (sample indices start at frame `firstFrame`) of the shard's tiles -- or, active != nullptr, of the tile list that
@@ -1702,6 +1731,90 @@ void Renderer::readMoments(float* sumSq, uint32_t* sampleCount)
     if (sampleCount) *sampleCount = empty ? 0u : m.momentSums.samples;
 }
 
+void Renderer::setBuckets(uint32_t K)
+{
+    Impl& m = *mImpl;
+    if (K != 0u && (K % 2u == 0u || K < 3u || K > kMaxBuckets)) throw std::invalid_argument("set_buckets: K must be 0 (off) or odd with 3 <= K <= 15");
+    if (K != 0u) m.requireUniform("rf_renderer_set_buckets", ": the bucket sums keep ONE sample count for the frame");
+    if (K == (m.bucketSums.on ? m.bucketSums.planes : 0u)) return;
+    RF_HIP(hipSetDevice(m.device));
+    RF_HIP(hipStreamSynchronize(m.stream)); // (a batch in flight may still write the sums)
+    m.bucketSums.on = K != 0u;
+    m.bucketSums.planes = K != 0u ? K : 1u;
+    m.restartBuckets();
+    // another K is another allocation (sized before the next sample); off: nothing of the buckets stays allocated
+    m.bucketSums.release();
+    if (K == 0u) m.robustWork.release();
+}
+
+uint32_t Renderer::buckets() const { return mImpl->bucketSums.on ? mImpl->bucketSums.planes : 0u; }
+
+void Renderer::readBuckets(float* planes, uint32_t* K, uint32_t* sampleCount)
+{
+    Impl& m = *mImpl;
+    synchronize();
+    const bool   empty = m.bucketSums.empty();
+    const size_t plane = static_cast<size_t>(m.params.width) * m.params.height * 4;
+    if (planes)
+        for (uint32_t b = 0; b < buckets(); ++b) m.readCompact(empty ? nullptr : m.bucketPlanes() + b * m.bucketStride(), planes + b * plane);
+    if (K) *K = buckets();
+    if (sampleCount) *sampleCount = empty ? 0u : m.bucketSums.samples;
+}
+
+// What rf_renderer_robust_mean and rf_renderer_denoise_robust check alike
+static void requireRobustMean(const char* what, bool on, bool covers, uint32_t K, uint32_t bucketSamples, uint32_t accumulated, uint32_t worldSize)
+{
+    const std::string w(what);
+    if (!on) throw std::invalid_argument(w + " needs the bucket sums: turn them on (rf_renderer_set_buckets) before the first sample");
+    if (worldSize != 1u) throw std::invalid_argument(w + " needs the whole frame: a tile shard is set (use rf_robust_mean_images on the sum of the ranks' bucket reads)");
+    // (first: with nothing accumulated the counts agree, at 0, and there is still nothing to combine)
+    if (accumulated < K) throw std::invalid_argument(w + ": every one of the " + std::to_string(K) + " buckets needs a sample, and only " + std::to_string(accumulated) + " are accumulated");
+    if (!covers)
+        throw std::invalid_argument(w + ": the bucket sample count (" + std::to_string(bucketSamples) + ") differs from the accumulated sample count (" +
+                                    std::to_string(accumulated) + "): turn the buckets on before the first sample");
+}
+
+void Renderer::robustMean()
+{
+    Impl& m = *mImpl;
+    m.requireUniform("rf_renderer_robust_mean");
+    requireRobustMean("robust_mean", m.bucketSums.on, m.bucketSums.covers(m.accumulated), buckets(), m.bucketSums.samples, m.accumulated, m.worldSize);
+    RF_HIP(hipSetDevice(m.device));
+    enqueueRobustMean(m.stream, m.robustWork, m.bucketPlanes(), m.bucketStride(), m.params.width, m.params.height, m.grid().tilesX, buckets(), m.accumulated, m.params.exposure);
+    m.robustValid = true;
+    m.robustSamples = m.accumulated;
+}
+
+void Renderer::readRobustMean(float* rgba, uint32_t* bgra8, uint8_t* trim, uint32_t* sampleCount)
+{
+    Impl& m = *mImpl;
+    if (!m.robustValid) throw std::invalid_argument("no robust mean: call rf_renderer_robust_mean first (the image is dropped when the accumulation or the bucket sums are cleared)");
+    synchronize();
+    const size_t n = static_cast<size_t>(m.params.width) * m.params.height;
+    if (rgba) RF_HIP(hipMemcpy(rgba, m.robustWork.mean.ptr, n * sizeof(float4), hipMemcpyDeviceToHost));
+    if (bgra8) RF_HIP(hipMemcpy(bgra8, m.robustWork.bgra.ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (trim) RF_HIP(hipMemcpy(trim, m.robustWork.trim.ptr, n * sizeof(uint8_t), hipMemcpyDeviceToHost));
+    if (sampleCount) *sampleCount = m.robustSamples;
+}
+
+void Renderer::denoiseRobust(const DenoiseParameters& params)
+{
+    Impl& m = *mImpl;
+    // rf_renderer_denoise's refusals (the uniform state only: the buckets keep one count), then the robust mean's
+    m.requireUniform("rf_renderer_denoise_robust");
+    if (!m.aovSums.on) throw std::invalid_argument("denoise_robust needs the first-hit AOVs: turn them on (rf_renderer_set_aovs) before the first sample");
+    if (m.worldSize != 1u) throw std::invalid_argument("denoise_robust needs the whole frame: a tile shard is set");
+    if (m.accumulated == 0u) throw std::invalid_argument("denoise_robust: no sample has been accumulated");
+    if (!m.aovSums.covers(m.accumulated))
+        throw std::invalid_argument("denoise_robust: the AOV sample count (" + std::to_string(m.aovSums.samples) + ") differs from the accumulated sample count (" +
+                                    std::to_string(m.accumulated) + "): turn the AOVs on before the first sample");
+    robustMean();
+    enqueueDenoise(m.stream, m.denoiseWork, m.image, m.aovAlbedoCoverage(), m.aovNormalDepth(), m.params.width, m.params.height, m.grid().tilesX, m.accumulated, params,
+                   m.params.exposure, nullptr, m.robustWork.mean.ptr);
+    m.denoisedValid = true;
+    m.denoisedSamples = m.accumulated;
+}
+
 NoiseEstimate Renderer::noiseEstimate(float* errorMap, float* tileSum, float* tileMax)
 {
     Impl& m = *mImpl;
@@ -1727,6 +1840,9 @@ NoiseEstimate Renderer::noiseEstimate(float* errorMap, float* tileSum, float* ti
 void Renderer::checkAdaptive(const AdaptiveParameters& p) const
 {
     const Impl& m = *mImpl;
+    if (m.bucketSums.on)
+        throw std::invalid_argument("render_adaptive: the bucket sums are on (rf_renderer_set_buckets), and they keep ONE sample count for the frame: turn the buckets off "
+                                    "(rf_renderer_set_buckets(r, 0)) before sampling adaptively");
     if (!m.momentSums.on) throw std::invalid_argument("render_adaptive needs the radiance second moments: turn them on (rf_renderer_set_moments) before the first sample");
     if (m.aovSums.on && !m.aovTileCounts())
         throw std::invalid_argument("render_adaptive: the first-hit AOVs are on without RF_AOV_TILE_COUNTS (their sums and the denoiser then keep ONE sample count): set "
@@ -1743,7 +1859,7 @@ AdaptiveResult Renderer::renderAdaptive(const AdaptiveParameters& p)
 {
     Impl& m = *mImpl;
     // (the order of the checks, and so which message a call with several faults gets, is the one this call always had)
-    if (!m.momentSums.on || (m.aovSums.on && !m.aovTileCounts())) checkAdaptive(p);
+    if (m.bucketSums.on || !m.momentSums.on || (m.aovSums.on && !m.aovTileCounts())) checkAdaptive(p);
     if (m.worldSize != 1u) throw std::invalid_argument("render_adaptive needs the whole frame: a tile shard is set (rf_comm_render_adaptive samples a sharded frame adaptively)");
     checkAdaptive(p);
     return renderAdaptiveFrom(p, m.accumulated, false);

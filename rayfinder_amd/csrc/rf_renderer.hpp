@@ -153,6 +153,12 @@ void denoiseImages(int deviceOrdinal, uint32_t width, uint32_t height, uint32_t 
 void denoiseTiles(int deviceOrdinal, uint32_t width, uint32_t height, const uint32_t* tileSamples, uint32_t samples, const float* colorSum, const float* albedoCoverage,
                   const float* normalDepth, const DenoiseParameters& params, float exposure, float* outRgba, uint32_t* outBgra8);
 
+// The firefly-robust mean (rf_robust.hip; the definition: include/rayfinder_amd.h) over host-assembled bucket planes -- K x width*height*4 floats, plane after plane,
+// each row-major -- of `samples` >= K samples, on device `deviceOrdinal`: the mean RGBA (.w = 1), its BGRA8 under `exposure` and the trim count of every pixel
+// (NULL = skip).  K odd, 3 .. 15.  Synchronous; allocates and frees its own device memory.
+void robustMeanImages(int deviceOrdinal, uint32_t width, uint32_t height, uint32_t K, uint32_t samples, const float* buckets, float exposure, float* outRgba,
+                      uint32_t* outBgra8, uint8_t* outTrim);
+
 // The noise estimate over the accumulation and the radiance second moments (rf_noise.hip; the definition: include/rayfinder_amd.h)
 struct NoiseEstimate
 {
@@ -241,6 +247,23 @@ public:
     void     setMoments(bool enabled);
     bool     momentsEnabled() const;
     void     readMoments(float* sumSq, uint32_t* sampleCount);
+    // Bucket sums (rf_renderer_set_buckets / rf_renderer_read_buckets): K = 0 off (the default), else odd, 3 .. 15.  While on, K more compact tile-major float4 planes
+    // in one allocation: plane b holds {sum r.x, sum r.y, sum r.z, 0} over the samples whose ordinal -- the bucket sample count just before the sample -- is b mod K,
+    // in sample order.  Their own sample count; cleared with the image and whenever K changes.  The uniform state only: std::invalid_argument for a bad K, and for
+    // K > 0 in the non-uniform state; renderAdaptive / checkAdaptive refuse while they are on.
+    // Read: K x width*height*4 floats, plane after plane, each row-major (this rank's pixels; NULL = skip), K and the bucket sample count.
+    void     setBuckets(uint32_t K);
+    uint32_t buckets() const;
+    void     readBuckets(float* planes, uint32_t* K, uint32_t* sampleCount);
+    // The robust mean over the handle's own bucket sums (rf_renderer_robust_mean; the arithmetic: include/rayfinder_amd.h): enqueued on the handle's stream, keeps a
+    // snapshot (allocated by the first call, dropped whenever the bucket sums are cleared).  std::invalid_argument when the buckets are off, their count differs from
+    // the accumulated count or is below K, a tile shard is set or the tiles hold different counts.
+    // readRobustMean: row-major width*height*4 mean floats, BGRA8, one trim count per pixel (NULL = skip) and the snapshot's sample count; std::invalid_argument
+    // without a snapshot.
+    void robustMean();
+    void readRobustMean(float* rgba, uint32_t* bgra8, uint8_t* trim, uint32_t* sampleCount);
+    // robustMean, then the a-trous filter of denoise with prep's colour c = M.rgb: the result is denoise's snapshot (readDenoised).  Refused as denoise and robustMean are.
+    void denoiseRobust(const DenoiseParameters& params);
     // The noise estimate over the handle's own sums (rf_renderer_noise_estimate): enqueued on the handle's stream, then waited for.  std::invalid_argument when the
     // moments are off, their count differs from the accumulated count, fewer than 2 samples are accumulated or a tile shard is set.  Host pointers, NULL = skip.
     NoiseEstimate noiseEstimate(float* errorMap, float* tileSum, float* tileMax);

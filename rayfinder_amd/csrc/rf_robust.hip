@@ -1,0 +1,147 @@
+// rf_robust.hip -- the firefly-robust mean of an accumulation: a median-of-means over the K bucket sums (rf_sums.hip) whose trim count follows the Gini coefficient of
+// the buckets' levels (after Buisine et al. 2021, "Firefly removal in Monte Carlo rendering with adaptive Median of meaNs").  The arithmetic is the one
+// include/rayfinder_amd.h writes out ("Bucket sums and the robust mean"), one IEEE f32 operation at a time in that order (-ffp-contract=off, correctly rounded
+// divide, no denormal flushing): tests/robust_restatement.py reproduces it bit for bit.  No atomics: every output is one lane's fixed sequence of operations.
+//   kRobustMean<K>  one lane per pixel; K is a compile-time constant, so the K bucket means and keys live in registers and the sort is a fixed network
+// The display image is the existing kTonemap over the mean with accumulatedSamples = 1.
+#include "rf_robust.hpp"
+
+#include "rf_kernels.hpp"
+#include "rf_math.hpp"
+
+#include <cfloat>
+
+namespace rf
+{
+namespace
+{
+// index of pixel (x, y) in a compact tile-major buffer that holds every tile of the frame in tile order (localPixelToXY's layout)
+__device__ __forceinline__ uint32_t tileMajorIndex(uint32_t x, uint32_t y, uint32_t tilesX)
+{
+    const uint32_t tile = (y >> 5) * tilesX + (x >> 5);
+    const uint32_t block = ((y & 31u) >> 3) * 4u + ((x & 31u) >> 3);
+    return tile * 1024u + block * 64u + (y & 7u) * 8u + (x & 7u);
+}
+
+template<uint32_t K>
+__global__ __launch_bounds__(256) void kRobustMean(const float4* planes, size_t planeStride, uint32_t width, uint32_t height, uint32_t tilesX, uint32_t samples, float4* mean,
+                                                   uint8_t* trim)
+{
+    static_assert(K % 2u == 1u && K >= 3u && K <= 15u, "K odd, 3 .. 15");
+    constexpr uint32_t HALF = (K - 1u) / 2u;
+    const uint32_t     i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= width * height) return;
+    const uint32_t y = i / width, x = i - y * width;
+    const uint32_t src = tilesX ? tileMajorIndex(x, y, tilesX) : i;
+    const uint32_t each = samples / K, more = samples - each * K; // buckets 0 .. more - 1 hold one sample more
+    float          mr[K], mg[K], mb[K], key[K];
+#pragma unroll
+    for (uint32_t b = 0; b < K; ++b)
+    {
+        const float  nf = static_cast<float>(each + (b < more ? 1u : 0u));
+        const float4 B = planes[b * planeStride + src];
+        mr[b] = B.x / nf, mg[b] = B.y / nf, mb[b] = B.z / nf;
+        const float l = (mr[b] + mg[b]) + mb[b];
+        key[b] = l <= FLT_MAX ? l : __builtin_inff(); // (NaN: +inf)
+    }
+    // ascending by key, ties by bucket index: an odd-even transposition network (K rounds) that exchanges two NEIGHBOURS only when the left key is strictly greater,
+    // so equal keys never pass each other
+#pragma unroll
+    for (uint32_t round = 0; round < K; ++round)
+#pragma unroll
+        for (uint32_t j = round & 1u; j + 1u < K; j += 2u)
+        {
+            const bool  swap = key[j] > key[j + 1u];
+            const float k0 = key[j], k1 = key[j + 1u], r0 = mr[j], r1 = mr[j + 1u], g0 = mg[j], g1 = mg[j + 1u], b0 = mb[j], b1 = mb[j + 1u];
+            key[j] = swap ? k1 : k0, key[j + 1u] = swap ? k0 : k1;
+            mr[j] = swap ? r1 : r0, mr[j + 1u] = swap ? r0 : r1;
+            mg[j] = swap ? g1 : g0, mg[j + 1u] = swap ? g0 : g1;
+            mb[j] = swap ? b1 : b0, mb[j + 1u] = swap ? b0 : b1;
+        }
+    float num = 0.0f, sum = 0.0f;
+#pragma unroll
+    for (uint32_t r = 0; r < K; ++r)
+    {
+        num += static_cast<float>(2 * static_cast<int>(r) - static_cast<int>(K - 1u)) * key[r];
+        sum += key[r];
+    }
+    const float    den = static_cast<float>(K) * sum;
+    const float    G = den > 0.0f ? num / den : 0.0f;
+    const float    t = G * (static_cast<float>(K) * 0.5f);
+    // min(uint(floor(t)), HALF), the comparison taken in f32 first (a huge t never reaches the conversion); NaN: every comparison false, the median
+    const uint32_t c = t >= 0.0f ? (t >= static_cast<float>(HALF) ? HALF : static_cast<uint32_t>(floorf(t))) : HALF;
+    float          sr = 0.0f, sg = 0.0f, sb = 0.0f;
+#pragma unroll
+    for (uint32_t r = 0; r < K; ++r)
+    {
+        const bool kept = r >= c && r + c <= K - 1u;
+        sr = kept ? sr + mr[r] : sr, sg = kept ? sg + mg[r] : sg, sb = kept ? sb + mb[r] : sb;
+    }
+    const float nk = static_cast<float>(K - 2u * c);
+    mean[i] = make_float4(sr / nk, sg / nk, sb / nk, 1.0f);
+    trim[i] = static_cast<uint8_t>(c);
+}
+
+using RobustKernel = void (*)(const float4*, size_t, uint32_t, uint32_t, uint32_t, uint32_t, float4*, uint8_t*);
+RobustKernel robustKernel(uint32_t K)
+{
+    switch (K)
+    {
+    case 3: return kRobustMean<3>;
+    case 5: return kRobustMean<5>;
+    case 7: return kRobustMean<7>;
+    case 9: return kRobustMean<9>;
+    case 11: return kRobustMean<11>;
+    case 13: return kRobustMean<13>;
+    case 15: return kRobustMean<15>;
+    default: throw std::logic_error("robustKernel: no such kernel is compiled");
+    }
+}
+} // namespace
+
+void RobustWork::reserve(uint64_t n, hipStream_t stream)
+{
+    if (n <= bgra.count) return; // (allocated last: it has room only when every buffer has)
+    RF_HIP(hipStreamSynchronize(stream)); // (a smaller set may still be in use by the last run)
+    release();
+    mean.alloc(n);
+    trim.alloc(n);
+    bgra.alloc(n);
+}
+
+void RobustWork::release()
+{
+    mean.release();
+    trim.release();
+    bgra.release();
+}
+
+void enqueueRobustMean(hipStream_t stream, RobustWork& w, const float4* planes, size_t planeStride, uint32_t width, uint32_t height, uint32_t tilesX, uint32_t K,
+                       uint32_t samples, float exposure)
+{
+    const uint32_t n = width * height;
+    w.reserve(n, stream);
+    hipLaunchKernelGGL(robustKernel(K), dim3((n + 255) / 256), dim3(256), 0, stream, planes, planeStride, width, height, tilesX, samples, w.mean.ptr, w.trim.ptr);
+    hipLaunchKernelGGL(tonemapKernel(), dim3((n + 255) / 256), dim3(256), 0, stream, static_cast<const float4*>(w.mean.ptr), n, 1u, exposure, w.bgra.ptr);
+    RF_HIP(hipGetLastError());
+}
+
+void robustMeanImages(int deviceOrdinal, uint32_t width, uint32_t height, uint32_t K, uint32_t samples, const float* buckets, float exposure, float* outRgba,
+                      uint32_t* outBgra8, uint8_t* outTrim)
+{
+    requireDevice(deviceOrdinal);
+    const uint64_t n = static_cast<uint64_t>(width) * height;
+    // (leaving the scope: the stream is synchronised, the buffers are freed, the stream is destroyed -- ScopedStream)
+    ScopedStream         stream;
+    DeviceBuffer<float4> in;
+    RobustWork           work;
+    ScopedStream::Drain  drain{stream};
+    in.alloc(K * n);
+    RF_HIP(hipMemcpyAsync(in.ptr, buckets, K * n * sizeof(float4), hipMemcpyHostToDevice, stream.handle));
+    enqueueRobustMean(stream.handle, work, in.ptr, n, width, height, 0u, K, samples, exposure);
+    if (outRgba) RF_HIP(hipMemcpyAsync(outRgba, work.mean.ptr, n * sizeof(float4), hipMemcpyDeviceToHost, stream.handle));
+    if (outBgra8) RF_HIP(hipMemcpyAsync(outBgra8, work.bgra.ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream.handle));
+    if (outTrim) RF_HIP(hipMemcpyAsync(outTrim, work.trim.ptr, n * sizeof(uint8_t), hipMemcpyDeviceToHost, stream.handle));
+    RF_HIP(hipStreamSynchronize(stream.handle));
+}
+} // namespace rf

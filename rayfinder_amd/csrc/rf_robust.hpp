@@ -1,0 +1,30 @@
+// rf_robust.hpp -- the firefly-robust mean over the bucket sums (rf_robust.hip; the definition: include/rayfinder_amd.h, "Bucket sums and the robust mean"): its
+// device buffers and its launch sequence, shared by the renderer's rf_renderer_robust_mean (inputs: the handle's own compact tile-major bucket planes) and the
+// standalone rf_robust_mean_images (inputs: row-major planes).
+#pragma once
+
+#include "rf_hip_host.hpp"
+#include "rf_renderer.hpp"
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace rf
+{
+struct RobustWork
+{
+    DeviceBuffer<float4>   mean; // M = {rgb, 1}, row-major
+    DeviceBuffer<uint8_t>  trim; // c of every pixel, row-major
+    DeviceBuffer<uint32_t> bgra; // kTonemap of `mean` (accumulatedSamples = 1)
+
+    // room for `pixels` in every buffer (stream-synchronises before it frees a smaller set)
+    void reserve(uint64_t pixels, hipStream_t stream);
+    void release();
+};
+
+// Enqueue kRobustMean<K> and kTonemap on `stream`.  planes: K planes of planeStride float4 each.  tilesX != 0: every plane is a compact tile-major buffer holding every
+// tile of the frame in tile order (a handle without a tile shard), tilesX tiles per row; 0: row-major.  width * height < 2^31; K odd, 3 .. 15; samples >= K.
+void enqueueRobustMean(hipStream_t stream, RobustWork& work, const float4* planes, size_t planeStride, uint32_t width, uint32_t height, uint32_t tilesX, uint32_t K,
+                       uint32_t samples, float exposure);
+} // namespace rf

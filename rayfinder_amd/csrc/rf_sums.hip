@@ -3,6 +3,7 @@
 //   kSumPixels<Sum, TILE_LIST>   one lane per pixel, any slot order                         (Sum = ShardList<...>: the tile list of a tile shard, see sumIndex)
 //   kSumRuns<Sum, TILE_LIST>     pixel-major slot order: a 64-lane workgroup stages its pixels' runs in LDS in 32-sample chunks, one summing lane per (pixel, channel)
 //   kAccumulateRuns<PIXELS>      pixel-major slot order, the image alone: the WHOLE runs of PIXELS pixels in dynamic LDS (the headline path, profiles/r06_raygen)
+//   kBucketSumPixels / kBucketSumRuns  the K bucket planes (rf_renderer_set_buckets): sample k of the batch goes to plane (phase + k) mod K; the same two forms
 // What is summed is a policy struct (below); where a pixel's sums live is sumIndex.  The contract all three keep: each channel of each sum is one dependent chain of
 // f32 additions in sample-index order (Q's term: one f32 multiply of the loaded value with itself), no atomics, no contraction (-ffp-contract=off).
 // To add a sum: one policy struct, one enumerator of Sum, its instantiations in sumKernel's table, one entry in Impl::enqueueSums' list.
@@ -226,6 +227,92 @@ __global__ __launch_bounds__(64) void kAccumulateRuns(FrameParams fp, const uint
     for (uint32_t k = 0; k < S; ++k) acc += src[k]; // sample order (wgsl:56-57): one dependent chain of f32 additions per channel
     *out = acc;
 }
+
+// ---- The bucket sums: the radiance of sample k of the batch onto plane (phase + k) mod K, K a launch argument.  No lane keeps K accumulators (an array indexed at run
+// time would go to scratch): a summing lane owns ONE bucket at a time and visits that bucket's samples, k = first, first + K, ..., in sample order.
+// the first sample of [k0, ...) that belongs to bucket b, as an offset from k0: the smallest f >= 0 with (phase + k0 + f) mod K == b
+__device__ __forceinline__ uint32_t firstOfBucket(uint32_t b, uint32_t phaseAtK0, uint32_t K) { return b >= phaseAtK0 ? b - phaseAtK0 : b + K - phaseAtK0; }
+
+// One lane per pixel, any slot order: plane after plane, each plane's sums in registers while its samples are added.
+__global__ __launch_bounds__(kBlock) void kBucketSumPixels(FrameParams fp, const uint32_t* tileIds, const float4* src, float4* planes, size_t planeStride, uint32_t K,
+                                                              uint32_t phase)
+{
+    const uint32_t lp = blockIdx.x * kBlock + threadIdx.x;
+    if (lp >= fp.pixelsPadded) return;
+    uint32_t x, y;
+    if (!localPixelToXY(fp, tileIds, lp, x, y)) return;
+    for (uint32_t b = 0; b < K; ++b)
+    {
+        const uint32_t first = firstOfBucket(b, phase, K);
+        if (first >= fp.numSamples) continue; // (a batch shorter than K: this plane gets no sample)
+        float4* const dst = planes + b * planeStride + lp;
+        float4        sum = *dst;
+        for (uint32_t k = first; k < fp.numSamples; k += K)
+        {
+            const float4 r = src[samplePixelToSlot(fp, fp.sampleInvPerm ? fp.sampleInvPerm[k] : k, lp)];
+            sum.x += r.x, sum.y += r.y, sum.z += r.z; // sample order: one dependent chain of f32 additions per channel and bucket
+        }
+        *dst = sum;
+    }
+}
+
+// Pixel-major slot order, patterned on kSumRuns: a 64-lane workgroup takes kBucketPixels pixels, stages their radiance in LDS in chunks of kBucketChunk samples (two
+// coalesced load rounds of 1 KiB), then the summing slots -- slot = (pixel, channel) * K + bucket, kBucketPixels * 3 * K <= 180 of them, up to three per lane at fixed
+// register positions -- each walk their row from their bucket's first sample of the chunk at stride K.
+__global__ __launch_bounds__(64) void kBucketSumRuns(FrameParams fp, const uint32_t* tileIds, const float4* src, float4* planes, size_t planeStride, uint32_t K, uint32_t phase)
+{
+    constexpr uint32_t PIXELS = kBucketPixels, CHUNK = kBucketChunk, R = CHUNK + 1u, ROUND = 64u / CHUNK, ROWS = PIXELS * 3u;
+    constexpr uint32_t SLOTS = (ROWS * kMaxBuckets + 63u) / 64u; // summing slots per lane
+    __shared__ float   sRun[ROWS * R];                           // [pixel][channel][sample of the chunk]
+    static_assert(ROUND * CHUNK == 64u && PIXELS % ROUND == 0u, "whole load rounds");
+    const uint32_t S = fp.numSamples, lane = threadIdx.x, lp0 = blockIdx.x * PIXELS;
+    // slot s of this lane: row = (pixel, channel), bucket, where its running sum lives
+    uint32_t row[SLOTS], bucket[SLOTS];
+    float*   out[SLOTS];
+    float    acc[SLOTS];
+#pragma unroll
+    for (uint32_t s = 0; s < SLOTS; ++s)
+    {
+        const uint32_t slot = lane + 64u * s;
+        row[s] = slot / K, bucket[s] = slot - row[s] * K;
+        const uint32_t px = row[s] / 3u, c = row[s] - 3u * px, lp = lp0 + px;
+        uint32_t       x, y;
+        const bool     sums = row[s] < ROWS && lp < fp.pixelsPadded && localPixelToXY(fp, tileIds, lp, x, y); // (pixels outside the frame: staged, never summed)
+        out[s] = sums ? reinterpret_cast<float*>(planes + bucket[s] * planeStride + lp) + c : nullptr;
+        acc[s] = sums ? *out[s] : 0.0f;
+    }
+    const uint32_t kk = lane % CHUNK, pr = lane / CHUNK; // loading lane = (pixel of the round, sample of the chunk)
+    for (uint32_t k0 = 0; k0 < S; k0 += CHUNK)
+    {
+        const uint32_t n = min(CHUNK, S - k0);
+        if (kk < n)
+        {
+            const uint32_t k = k0 + kk, p = fp.sampleInvPerm ? fp.sampleInvPerm[k] : k; // sample k sits at position p of the pixel's run
+#pragma unroll
+            for (uint32_t i = 0; i < PIXELS / ROUND; ++i)
+            {
+                const uint32_t pi = ROUND * i + pr;
+                if (lp0 + pi >= fp.pixelsPadded) continue;
+                const float4 r = src[static_cast<size_t>(lp0 + pi) * S + p];
+                float*       dst = sRun + pi * 3u * R + kk;
+                dst[0] = r.x, dst[R] = r.y, dst[2u * R] = r.z;
+            }
+        }
+        __syncthreads();
+        const uint32_t phaseAtK0 = (phase + k0) % K;
+#pragma unroll
+        for (uint32_t s = 0; s < SLOTS; ++s)
+        {
+            if (out[s] == nullptr) continue;
+            const float* run = sRun + row[s] * R;
+            for (uint32_t j = firstOfBucket(bucket[s], phaseAtK0, K); j < n; j += K) acc[s] += run[j]; // sample order: one dependent chain of f32 additions per channel and bucket
+        }
+        __syncthreads(); // the next chunk overwrites the rows
+    }
+#pragma unroll
+    for (uint32_t s = 0; s < SLOTS; ++s)
+        if (out[s] != nullptr) *out[s] = acc[s];
+}
 } // namespace
 
 SumKernel sumKernel(Sum sum, bool runs, SumAddressing addressing)
@@ -244,5 +331,6 @@ SumKernel sumKernel(Sum sum, bool runs, SumAddressing addressing)
     if (sum == Sum::Aov) return runs ? kSumRuns<AovSum, false> : kSumPixels<AovSum, false>;
     throw std::logic_error("sumKernel: no such kernel is compiled");
 }
+BucketKernel bucketKernel(bool runs) { return runs ? kBucketSumRuns : kBucketSumPixels; }
 AccumulateRunsKernel accumulateRunsKernel(uint32_t pixels) { return pixels == 1u ? kAccumulateRuns<1> : pixels == 2u ? kAccumulateRuns<2> : kAccumulateRuns<kAccPixels>; }
 } // namespace rf

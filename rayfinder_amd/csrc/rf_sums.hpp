@@ -1,6 +1,7 @@
 // rf_sums.hpp -- the per-pixel sums in sample order (rf_sums.hip): every kernel that adds a batch's per-slot records onto a running sum of the handle -- the image S,
-// the radiance second moments Q, the two first-hit AOV sums -- and the constants of their launches.  The host (Impl::planBatch / enqueueSums) picks a kernel by
-// (sum, LDS-staged or one lane per pixel, shard-compact or tile-list addressing) and launches them with one argument list; the headline image kernel keeps its own.
+// the radiance second moments Q, the two first-hit AOV sums, the K bucket sums -- and the constants of their launches.  The host (Impl::planBatch / enqueueSums) picks a
+// kernel by (sum, LDS-staged or one lane per pixel, shard-compact or tile-list addressing) and launches them with one argument list; the headline image kernel and the
+// bucket kernels (K planes, a phase) keep their own.
 #pragma once
 
 #include "rf_kernels.hpp"
@@ -48,4 +49,14 @@ constexpr uint32_t kAccPixels = 4;
 constexpr uint32_t kAccMaxSamples = 1024;
 using AccumulateRunsKernel = void (*)(FrameParams fp, const uint32_t* tileIds, PathStreams ps, float4* image);
 AccumulateRunsKernel accumulateRunsKernel(uint32_t pixelsPerWorkgroup);
+
+// The bucket sums (rf_renderer_set_buckets): K planes of `planeStride` float4 each, one after another, every plane laid out like the image (shard-compact, the sums of
+// local pixel lp at lp).  Sample k of the batch is added to plane (phase + k) mod K, phase = (the bucket sample count before the batch) mod K < K: plane b holds
+// {sum r.x, sum r.y, sum r.z, 0} over the samples of ordinal b mod K, each channel of each plane one dependent chain of f32 additions in sample order -- the contract above.
+// 3 <= K <= kMaxBuckets.  runs: the LDS-staged kernel for the pixel-major slot order, a 64-lane workgroup per kBucketPixels pixels, their runs staged in chunks of
+// kBucketChunk samples (kBucketPixels x 3 rows of kBucketChunk + 1 floats = 1 584 B of LDS), one summing lane per (pixel, channel, bucket) walking its row at stride K;
+// else one lane per pixel (kBlock per workgroup, any slot order), plane after plane.  Its source is ps.rad.
+constexpr uint32_t kMaxBuckets = 15, kBucketPixels = 4, kBucketChunk = 32;
+using BucketKernel = void (*)(FrameParams fp, const uint32_t* tileIds, const float4* src, float4* planes, size_t planeStride, uint32_t K, uint32_t phase);
+BucketKernel bucketKernel(bool runs);
 } // namespace rf
