@@ -326,9 +326,19 @@ RF_API int rf_renderer_render_until(rf_renderer* r, float target_mean_error, uin
  * ray counts are bit for bit what they are with the buckets off.  The buckets keep their own sample count -- the samples traced while they were on -- and are
  * cleared, with the count set to 0, when the image is (a change through rf_renderer_set_render_parameters, a new tile shard, a newly bound accumulation buffer) and
  * when K changes.  Turned on partway through an accumulation, they cover only the later samples.
- * The buckets are for the uniform state: while they are on, rf_renderer_render_adaptive and rf_comm_render_adaptive return RF_ERROR_INVALID_ARGUMENT (the message
- * names the buckets) before anything is traced or exchanged, and rf_renderer_set_buckets(K > 0) is refused in the non-uniform state.  rf_renderer_render,
- * rf_renderer_render_until, rf_renderer_set_tile_shard and rf_renderer_gather_frame work as before; the frame gather does not carry the bucket planes.
+ * The buckets and tile-adaptive sampling.  As set with K alone the buckets keep ONE sample count for the frame: while they are on, rf_renderer_render_adaptive and
+ * rf_comm_render_adaptive return RF_ERROR_INVALID_ARGUMENT (the message names the buckets) before anything is traced or exchanged.
+ * rf_renderer_set_buckets(r, K | RF_BUCKETS_TILE_COUNTS), K > 0 (the low byte of the argument is K, the bits from bit 8 up say how; the bit with K = 0 and any other
+ * bit are RF_ERROR_INVALID_ARGUMENT), opts in to per-tile counts, as RF_AOV_TILE_COUNTS does for the AOV sums: until rf_renderer_render_adaptive is called the handle is
+ * bit for bit the handle without the bit (the same kernels, the same planes, the same memory figures); rf_renderer_render_adaptive then runs -- refused, "restart the
+ * accumulation first", when samples are accumulated and the bucket sample count does not cover them -- and afterwards the K planes of every pixel of tile t are bit for
+ * bit what rf_renderer_render(tile_samples[t]) leaves there in a fresh accumulation with the buckets on: sample j of the tile in plane j mod K, the same chains, whatever
+ * the batching, the slot order or the options (all active tiles share one count, so one bucket phase serves a batch; a batch shorter than K leaves the planes it does
+ * not reach untouched).  The bucket sample count advances with the leading count L.  S, Q, the AOV sums, which tile stops when, *result and the ray counts are exactly
+ * what they are with the buckets off.  A change of the bit alone clears the bucket sums, as a change of K does; rf_renderer_read_buckets reports K without the bit, and
+ * in the non-uniform state the planes as they are and L.  rf_comm_render_adaptive stays refused while the buckets are on, in either form (bucket planes under a tile
+ * shard keep one count).  rf_renderer_set_buckets(K > 0), with or without the bit, is refused in the non-uniform state: the buckets could not cover the accumulation.
+ * rf_renderer_render, rf_renderer_render_until, rf_renderer_set_tile_shard and rf_renderer_gather_frame work as before; the frame gather does not carry the bucket planes.
  * rf_renderer_read_buckets: K x width*height*4 floats, plane after plane, each row-major (the layout of rf_renderer_read_accumulation; may be NULL), K and the bucket
  * sample count (either may be NULL).  With a tile shard set, this rank's pixels and zeros elsewhere: the sum of the ranks' reads is the whole frame.  Buckets off:
  * nothing is written to `buckets`, K = 0, count = 0.
@@ -346,26 +356,40 @@ RF_API int rf_renderer_render_until(rf_renderer* r, float target_mean_error, uin
  *   output:                  M.rgb = (sum over i = c .. K-1-c of m_{r_i}, per channel, in i order from +0) / float(K - 2c);  M.a = 1;  trim = c (uint8)
  * All buckets equal: G = 0, c = 0, the mean of the means.  One bucket far above the rest: G approaches (K - 1) / K and c grows until the outlier is cut; c = (K - 1) / 2
  * is the median of the means.  The estimate is biased low on pixels whose samples are skewed, the more so the fewer samples a bucket holds.
+ * One count per tile (the tiles combine): the same per pixel with N = tile_samples[t] >= K, t = (y / 32) ceil(width / 32) + (x / 32) the pixel's 32x32 tile, and nothing
+ * else changed: no term looks at a neighbour, so a tile's result does not depend on the other tiles' counts, and with all counts equal to N it is bit for bit the
+ * one-count form at N.
  *
  * rf_renderer_robust_mean: enqueued on the handle's stream over its own bucket sums.  It keeps a snapshot -- M, trim, the BGRA8 texels (kTonemap with
  * accumulatedSamples = 1 and the handle's exposure) and the count N; one float4, one byte and one u32 per pixel -- allocated by the first call and dropped whenever
  * the bucket sums are cleared.  RF_ERROR_INVALID_ARGUMENT when the buckets are off, when the bucket sample count differs from the accumulated count (turned on
- * partway through), when N < K, when a tile shard is set (use rf_robust_mean_images on the sum of the ranks' rf_renderer_read_buckets) or in the non-uniform state.
- * Leaves every sum, the denoise snapshot, the stats and later samples untouched.
+ * partway through), when N < K, when a tile shard is set (use rf_robust_mean_images on the sum of the ranks' rf_renderer_read_buckets) or in the non-uniform state
+ * -- unless the buckets were set with RF_BUCKETS_TILE_COUNTS: the tiles combine then runs over the handle's per-tile counts, the snapshot's count is the leading count L,
+ * and the call is refused when any tile holds fewer than K samples (the message names K and the smallest count; sample with min_samples >= K); like the other per-tile
+ * reads it first waits for the stream and copies the counts to the device.  When rf_renderer_render_adaptive left every tile at L the state is uniform again and the
+ * one-count form runs.  Leaves every sum, the denoise snapshot, the stats and later samples untouched.
  * rf_renderer_read_robust_mean: row-major width*height*4 mean floats, the BGRA8 texels, one trim count per pixel and the snapshot's sample count; any pointer may be
  * NULL.  RF_ERROR_INVALID_ARGUMENT without a snapshot.
  * rf_robust_mean_images: the same kernel over host bucket planes (K x width*height*4 floats, each plane row-major, e.g. the sum of several ranks' reads) of `samples`
  * samples on device device_ordinal; the outputs may be NULL.  Synchronous.  A NULL input, a zero size, a K that is not odd in 3 .. 15 and samples < K are refused
  * before any device call.  Row-major and tile-major inputs give bit-identical results.
+ * rf_robust_mean_tiles: rf_robust_mean_images with one count per 32x32 tile: tile_samples holds ceil(width / 32) * ceil(height / 32) words in the estimate's tile
+ * numbering, exactly as for rf_denoise_tiles (e.g. rf_renderer_read_tile_samples next to rf_renderer_read_buckets).  Synchronous.  A NULL input, a zero size, a K that is
+ * not odd in 3 .. 15 and any tile count below K are refused before any device call.
  * rf_renderer_denoise_robust: rf_renderer_robust_mean, then the a-trous filter of rf_renderer_denoise, whose definition changes in exactly one place: in prep,
  * c = M.rgb instead of S.rgb / Nf (a = AC.rgb / Nf and m = ND.xyz / Nf as ever, everything after prep as written; L = 0 returns M).  The result is the ordinary denoise
- * snapshot (rf_renderer_read_denoised).  Refused as rf_renderer_denoise is, and also when rf_renderer_robust_mean would be.  rf_renderer_denoise itself is unchanged. */
+ * snapshot (rf_renderer_read_denoised).  Refused as rf_renderer_denoise is, and also when rf_renderer_robust_mean would be.  In the non-uniform state it runs the tiles
+ * combine and then prep with Nf = float(the count of the pixel's tile) for a and m (c = M.rgb as it is; the passes unchanged): it needs the AOVs on with
+ * RF_AOV_TILE_COUNTS and the buckets with RF_BUCKETS_TILE_COUNTS, both covering the accumulation.  rf_renderer_denoise itself is unchanged. */
+#define RF_BUCKETS_TILE_COUNTS 0x100u /* ORed into K: keep the bucket sums per tile count under rf_renderer_render_adaptive */
 RF_API int rf_renderer_set_buckets(rf_renderer* r, uint32_t K);
 RF_API int rf_renderer_read_buckets(rf_renderer* r, float* buckets, uint32_t* K, uint32_t* bucket_sample_count);
 RF_API int rf_renderer_robust_mean(rf_renderer* r);
 RF_API int rf_renderer_read_robust_mean(rf_renderer* r, float* rgba, uint32_t* bgra8, uint8_t* trim, uint32_t* sample_count);
 RF_API int rf_robust_mean_images(int32_t device_ordinal, uint32_t width, uint32_t height, uint32_t K, uint32_t samples, const float* buckets, float exposure,
                                  float* out_rgba, uint32_t* out_bgra8, uint8_t* out_trim);
+RF_API int rf_robust_mean_tiles(int32_t device_ordinal, uint32_t width, uint32_t height, uint32_t K, const uint32_t* tile_samples, const float* buckets, float exposure,
+                                float* out_rgba, uint32_t* out_bgra8, uint8_t* out_trim);
 RF_API int rf_renderer_denoise_robust(rf_renderer* r, const rf_denoise_parameters* params);
 
 /* Tile-adaptive sampling: a render call that keeps sampling only the 32x32 tiles that are still noisy, and the per-tile sample count that the reads then honour.

@@ -590,6 +590,23 @@ def robust_mean_images(buckets, samples, exposure=1.0, device_ordinal=0):
     return dict(mean=rgba[..., :3], bgra8=bgra, trim=trim, samples=int(samples))
 
 
+def robust_mean_tiles(buckets, tile_samples, exposure=1.0, device_ordinal=0):
+    """rf_robust_mean_tiles: robust_mean_images with one sample count (>= K) per 32x32 tile, tile_samples in tile order (tile_y * ceil(W / 32) + tile_x): every
+    pixel is combined with its own tile's count (read_buckets and read_tile_samples of a frame of render_adaptive).  -> dict(mean, bgra8, trim, tile_samples)."""
+    buckets = _f32(buckets)
+    if buckets.ndim != 4 or buckets.shape[3] != 4:
+        raise ValueError("robust_mean_tiles: the bucket sums must be a (K, H, W, 4) array")
+    k, h, w = buckets.shape[:3]
+    counts = np.ascontiguousarray(tile_samples, np.uint32).reshape(-1)
+    if counts.size != _noise_tiles(w, h):
+        raise ValueError(f"robust_mean_tiles: {_noise_tiles(w, h)} tile counts expected, got {counts.size}")
+    rgba = np.zeros((h, w, 4), np.float32)
+    bgra = np.zeros((h, w), np.uint32)
+    trim = np.zeros((h, w), np.uint8)
+    check(lib.rf_robust_mean_tiles(device_ordinal, w, h, k, _ptr(counts), _ptr(buckets), exposure, _ptr(rgba), _ptr(bgra), _ptr(trim)))
+    return dict(mean=rgba[..., :3], bgra8=bgra, trim=trim, tile_samples=counts)
+
+
 def _noise_result(est, error_map, tile_sum, tile_max):
     out = {k: getattr(est, k) for k, _ in est._fields_}
     out.update(error_map=error_map, tile_sum=tile_sum, tile_max=tile_max)
@@ -738,10 +755,12 @@ class ReferencePathTracer:
         return q, n.value
 
     # bucket sums and the firefly-robust mean (include/rayfinder_amd.h states what the buckets hold and the combine's arithmetic)
-    def set_buckets(self, k):
+    def set_buckets(self, k, tile_counts=False):
         """Keep k bucket sums (k odd, 3 .. 15; 0: off, the default): bucket b sums the radiance of the samples whose ordinal is b mod k.  Any change clears them.
-        The uniform state only: render_adaptive is refused while they are on."""
-        check(lib.rf_renderer_set_buckets(self._h, int(k)))
+        Without tile_counts they keep one count for the frame: render_adaptive is refused while they are on.  tile_counts (RF_BUCKETS_TILE_COUNTS, k > 0): the sums
+        follow the per-tile sample counts of render_adaptive, which then runs with the buckets on, and robust_mean / denoise_robust work on the frame it leaves;
+        until render_adaptive is called, nothing differs."""
+        check(lib.rf_renderer_set_buckets(self._h, int(k) | (_ffi.RF_BUCKETS_TILE_COUNTS if tile_counts else 0)))
 
     def read_buckets(self):
         """-> ((K, H, W, 4) f32 bucket sums {r, g, b, 0} in sample order, the bucket sample count); K = 0 while the buckets are off"""
@@ -753,7 +772,8 @@ class ReferencePathTracer:
         return b, n.value
 
     def robust_mean(self):
-        """Combine the bucket sums into the robust mean (needs the buckets on from the first sample, at least K samples, no tile shard); read_robust_mean reads it."""
+        """Combine the bucket sums into the robust mean (needs the buckets on from the first sample, at least K samples -- after render_adaptive: in every tile, and
+        the buckets set with tile_counts --, no tile shard); read_robust_mean reads it."""
         check(lib.rf_renderer_robust_mean(self._h))
 
     def read_robust_mean(self):

@@ -38,6 +38,7 @@ RF_ERROR_NO_DEVICE = 3
 RF_ERROR_OUT_OF_RANGE = 4
 RF_AOV_FIRST_HIT = 1
 RF_AOV_TILE_COUNTS = 0x100
+RF_BUCKETS_TILE_COUNTS = 0x100
 
 
 class DenoiseParameters(C.Structure):
@@ -153,6 +154,7 @@ SIGNATURES = {
     "rf_renderer_robust_mean": (C.c_int, [C.c_void_p]),
     "rf_renderer_read_robust_mean": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
     "rf_robust_mean_images": (C.c_int, [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rf_robust_mean_tiles": (C.c_int, [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rf_renderer_denoise_robust": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rf_renderer_noise_estimate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rf_noise_estimate_images": (C.c_int, [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

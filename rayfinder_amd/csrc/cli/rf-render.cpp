@@ -4,7 +4,7 @@
 //           [--denoise-iterations L] [--denoise-sigma-color s] [--denoise-sigma-normal s] [--denoise-sigma-depth s]
 //           [--noise-map m.pfm] [--noise-target t] [--noise-check-every k] [--gpus N]
 //           [--adaptive T] [--adaptive-min n] [--adaptive-every n] [--sample-map s.pfm]
-//           [--buckets K] [--robust-mean out.pfm|out.png] [--trim-map t.pfm] [--denoise-robust d.png]
+//           [--buckets K] [--buckets-tile-counts] [--robust-mean out.pfm|out.png] [--trim-map t.pfm] [--denoise-robust d.png]
 // Offline counterpart of the interactive `pt` app (src/pt/main.cpp): same default camera pose,
 // sky and exposure; renders all samples and writes the tonemapped image (and optionally the
 // mean radiance as PFM).  --gpus N: one host thread per GPU, the image tile-sharded across them, one RCCL
@@ -27,6 +27,9 @@
 // (rf_renderer_robust_mean) as a PFM, or tonemapped as a PNG; --trim-map: how many buckets the combine cut from each end, per pixel (a one-channel PFM);
 // --denoise-robust: the robust mean through the denoiser (rf_renderer_denoise_robust; turns the AOVs on, takes the --denoise-* parameters) as a PNG.  These three need
 // --buckets.  --gpus 1 only and not with --adaptive: the bucket planes are not carried by the frame gather and keep one sample count for the frame.
+// --buckets-tile-counts (a switch, no value): keep the bucket sums per tile count (K | RF_BUCKETS_TILE_COUNTS).  With it --buckets K --adaptive T runs on --gpus 1, and
+// --robust-mean, --trim-map and --denoise-robust write the adaptive frame's images, every pixel combined with its own tile's count (--adaptive-min >= K, or a tile
+// may stop with an empty bucket and the combine is refused).
 // --noise-target t [--noise-check-every k]: stop as soon as the frame's mean error is <= t, checked every k samples (default 8), at --spp at the latest
 // (rf_renderer_render_until).  One GPU only: stopping several ranks in step is not implemented.
 #include "cli_common.hpp"
@@ -53,9 +56,10 @@ int main(int argc, char** argv)
                     "  --adaptive: sample every 32x32 tile until its mean error is <= T (checked every n samples, default 8; --spp at the latest); --sample-map: the\n"
                     "  tiles' sample counts (1-channel PFM).  --gpus 1 only, not with --noise-target; with --aov-* / --denoise* the AOVs and the denoiser use each\n"
                     "  tile's own sample count\n"
-                    "                 [--buckets K] [--robust-mean out.pfm|out.png] [--trim-map t.pfm] [--denoise-robust d.png]\n"
+                    "                 [--buckets K] [--buckets-tile-counts] [--robust-mean out.pfm|out.png] [--trim-map t.pfm] [--denoise-robust d.png]\n"
                     "  --buckets: keep K bucket sums (K odd, 3 .. 15); --robust-mean: the firefly-robust median-of-means image (PFM, or PNG tonemapped); --trim-map: the\n"
                     "  buckets cut from each end per pixel (1-channel PFM); --denoise-robust: the robust mean through the denoiser.  --gpus 1 only, not with --adaptive\n"
+                    "  unless --buckets-tile-counts (no value) is given: the bucket sums then follow the tiles' sample counts, and the three images are the adaptive frame's\n"
                     "                 [--noise-map m.pfm] [--noise-target t] [--noise-check-every k]\n"
                     "  --noise-map: the per-pixel relative standard error of the frame (1-channel PFM); --noise-target: stop once the frame's mean error is <= t,\n"
                     "  checked every k samples (default 8), at --spp at the latest (one GPU only)\n");
@@ -78,9 +82,18 @@ int main(int argc, char** argv)
     rf_adaptive_parameters adaptiveParams{0.0f, 8u, 0u, 0u};
     rf_adaptive_result     adaptiveResult{};
     uint32_t    buckets = 0;
+    bool        bucketsTileCounts = false;
     std::string robustMean, trimMap, denoiseRobust;
-    for (int i = 2; i + 1 < argc; i += 2)
+    for (int i = 2; i < argc; i += 2)
     {
+        // (the one switch without a value)
+        if (std::string(argv[i]) == "--buckets-tile-counts")
+        {
+            bucketsTileCounts = true;
+            --i;
+            continue;
+        }
+        if (i + 1 >= argc) break;
         const std::string k = argv[i];
         const char*       val = argv[i + 1];
         if (k == "--width") W = static_cast<uint32_t>(std::atoi(val));
@@ -132,7 +145,12 @@ int main(int argc, char** argv)
         return 1;
     }
     const bool robust = !robustMean.empty() || !trimMap.empty() || !denoiseRobust.empty();
-    if ((buckets != 0u || robust) && (gpus > 1 || adaptive))
+    if (bucketsTileCounts && buckets == 0u)
+    {
+        std::fprintf(stderr, "--buckets-tile-counts needs --buckets K (K odd, 3 .. 15)\n");
+        return 1;
+    }
+    if ((buckets != 0u || robust) && (gpus > 1 || (adaptive && !bucketsTileCounts)))
     {
         std::fprintf(stderr, "--buckets / --robust-mean / --trim-map / --denoise-robust need --gpus 1 and do not go with --adaptive (the bucket sums are not carried by the "
                              "frame gather and keep one sample count for the frame)\n");
@@ -208,7 +226,7 @@ int main(int argc, char** argv)
         // (--adaptive: the AOV sums follow the per-tile counts)
         if (aovs) rfCheck(rf_renderer_set_aovs(renderer, RF_AOV_FIRST_HIT | (adaptive ? RF_AOV_TILE_COUNTS : 0u)), "AOVs");
         if (noise) rfCheck(rf_renderer_set_moments(renderer, 1), "moments");
-        if (buckets != 0u) rfCheck(rf_renderer_set_buckets(renderer, buckets), "buckets");
+        if (buckets != 0u) rfCheck(rf_renderer_set_buckets(renderer, buckets | (bucketsTileCounts ? RF_BUCKETS_TILE_COUNTS : 0u)), "buckets");
         const auto t0 = std::chrono::steady_clock::now();
         if (adaptive) rfCheck(rf_renderer_render_adaptive(renderer, &adaptiveParams, &adaptiveResult), "adaptive render");
         else if (noiseTargetSet) rfCheck(rf_renderer_render_until(renderer, noiseTarget, noiseCheckEvery, spp, &sppReached, &estimate), "render to the noise target");

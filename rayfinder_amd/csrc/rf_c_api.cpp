@@ -22,6 +22,7 @@
 static_assert(sizeof(rf_camera) == sizeof(rf::Camera));
 static_assert(RF_AOV_FIRST_HIT == rf::Renderer::kAovFirstHit);
 static_assert(RF_AOV_TILE_COUNTS == rf::Renderer::kAovTileCounts);
+static_assert(RF_BUCKETS_TILE_COUNTS == rf::Renderer::kBucketsTileCounts);
 
 struct rf_renderer
 {
@@ -369,7 +370,10 @@ int rf_renderer_read_moments(rf_renderer* r, float* sumsq4, uint32_t* moment_sam
 int rf_renderer_set_buckets(rf_renderer* r, uint32_t K)
 {
     return guarded([&] {
-        require(K == 0u || (K % 2u == 1u && K >= 3u && K <= 15u), "set_buckets: K must be 0 (off) or odd with 3 <= K <= 15");
+        // (the low byte is K; RF_BUCKETS_TILE_COUNTS is the one bit known above it, and only with K > 0)
+        const uint32_t k = K & 0xFFu;
+        require((K & ~(0xFFu | RF_BUCKETS_TILE_COUNTS)) == 0u && (k != 0u || K == 0u) && (k == 0u || (k % 2u == 1u && k >= 3u && k <= 15u)),
+                "set_buckets: K must be 0 (off) or odd with 3 <= K <= 15, alone or ORed with RF_BUCKETS_TILE_COUNTS (K > 0 only)");
         require(r, "null argument");
         r->impl->setBuckets(K);
         return RF_OK;
@@ -414,6 +418,22 @@ int rf_robust_mean_images(int32_t device_ordinal, uint32_t width, uint32_t heigh
         require(samples >= K, "every bucket needs a sample: the sample count must be >= K");
         require(std::isfinite(exposure), "exposure must be finite");
         rf::robustMeanImages(device_ordinal, width, height, K, samples, buckets, exposure, out_rgba, out_bgra8, out_trim);
+        return RF_OK;
+    });
+}
+
+int rf_robust_mean_tiles(int32_t device_ordinal, uint32_t width, uint32_t height, uint32_t K, const uint32_t* tile_samples, const float* buckets, float exposure,
+                         float* out_rgba, uint32_t* out_bgra8, uint8_t* out_trim)
+{
+    return guarded([&] {
+        require(buckets && tile_samples, "null argument");
+        require(width > 0 && height > 0, "image size must be non-zero");
+        require(static_cast<uint64_t>(width) * height < (1ull << 31), "image too large");
+        require(K % 2u == 1u && K >= 3u && K <= 15u, "K must be odd with 3 <= K <= 15");
+        const uint32_t tiles = ((width + 31u) / 32u) * ((height + 31u) / 32u);
+        for (uint32_t t = 0; t < tiles; ++t) require(tile_samples[t] >= K, "every bucket of every tile needs a sample: every tile count must be >= K");
+        require(std::isfinite(exposure), "exposure must be finite");
+        rf::robustMeanTiles(device_ordinal, width, height, K, tile_samples, buckets, exposure, out_rgba, out_bgra8, out_trim);
         return RF_OK;
     });
 }

@@ -60,7 +60,7 @@ const void* gatherFrame(Renderer& h, TileComm& comm, uint32_t root, uint32_t fla
 
 ShardedAdaptiveResult renderAdaptive(Renderer& h, TileComm& comm, const AdaptiveParameters& p)
 {
-    h.checkAdaptive(p);
+    h.checkAdaptive(p, true);
     requireOneRank(h, comm);
     void* const stream = h.streamHandle();
     // the frame's leading count: the largest accumulated count of any rank.  From here the loop is this rank's own: a tile's stop reads its own sums alone

@@ -5,6 +5,7 @@
 //   kDenoisePrep    one lane per pixel: demodulated irradiance {e, ℓ}, guide {n, z}, a + εa (or, for L = 0, the mean itself)
 //   kDenoisePrepTiles  the same with the sample count of the pixel's 32x32 tile (a frame of rf_renderer_render_adaptive, rf_denoise_tiles)
 //   kDenoisePrepMean   the same with the colour c taken from a row-major mean image (the robust mean, rf_renderer_denoise_robust) instead of S / Nf
+//   kDenoisePrepMeanTiles  kDenoisePrepMean with the sample count of the pixel's tile (rf_renderer_denoise_robust in the non-uniform state)
 //   kDenoiseAtrous  one lane per pixel, 16x16-pixel workgroups of four 8x8-pixel waves (the 25 taps of a wave touch few cache lines); the last pass
 //                   remodulates and writes the mean
 // The display image is the existing kTonemap over the mean with accumulatedSamples = 1.
@@ -101,6 +102,18 @@ __global__ __launch_bounds__(256) void kDenoisePrepMean(const float4* mean, cons
     prepPixel<true>(mean, albedoCoverage, normalDepth, i, x, y, tilesX, nf, e, guide, albedo, meanOut);
 }
 
+// kDenoisePrepMean with one sample count per 32x32 tile: c = mean[i].rgb as it is, a = AC.rgb / Nf and m = ND.xyz / Nf with Nf = float(tileSamples[tile of the pixel])
+__global__ __launch_bounds__(256) void kDenoisePrepMeanTiles(const float4* mean, const float4* albedoCoverage, const float4* normalDepth, uint32_t width, uint32_t height,
+                                                             uint32_t tilesX, const uint32_t* tileSamples, uint32_t frameTilesX, float4* e, float4* guide, float4* albedo,
+                                                             float4* meanOut)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= width * height) return;
+    const uint32_t y = i / width, x = i - y * width;
+    const float    nf = static_cast<float>(tileSamples[(y >> 5) * frameTilesX + (x >> 5)]);
+    prepPixel<true>(mean, albedoCoverage, normalDepth, i, x, y, tilesX, nf, e, guide, albedo, meanOut);
+}
+
 // One pass of step `step` = 2^i: sc2 = (σc σc) 2^-i, szs = σz step.  last: out = the mean {e' (a + εa), 1} (background: {c, 1}); else out = {e', ℓ'}.
 __global__ __launch_bounds__(kDenoiseBlock) void kDenoiseAtrous(const float4* eIn, const float4* guide, const float4* albedo, float4* out, uint32_t width, uint32_t height,
                                                                int step, float sc2, float sigmaN, float szs, uint32_t last)
@@ -188,7 +201,10 @@ void enqueueDenoise(hipStream_t stream, DenoiseWork& w, const float4* colorSum, 
     const dim3  prepGrid((n + 255) / 256);
     // prep into (e, guide, albedo), or for L = 0 into the mean: with the frame's one count, or with each pixel's tile's own
     const auto prep = [&](float4* e, float4* guide, float4* albedo, float4* meanOut) {
-        if (mean)
+        if (mean && tileSamples)
+            hipLaunchKernelGGL(kDenoisePrepMeanTiles, prepGrid, dim3(256), 0, stream, mean, albedoCoverage, normalDepth, width, height, tilesX, tileSamples,
+                               TileGrid(width, height).tilesX, e, guide, albedo, meanOut);
+        else if (mean)
             hipLaunchKernelGGL(kDenoisePrepMean, prepGrid, dim3(256), 0, stream, mean, albedoCoverage, normalDepth, width, height, tilesX, nf, e, guide, albedo, meanOut);
         else if (tileSamples)
             hipLaunchKernelGGL(kDenoisePrepTiles, prepGrid, dim3(256), 0, stream, colorSum, albedoCoverage, normalDepth, width, height, tilesX, tileSamples,

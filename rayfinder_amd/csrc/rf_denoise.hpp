@@ -27,8 +27,8 @@ struct DenoiseWork
 // frame in tile order (a handle without a tile shard), tilesX tiles per row; 0: row-major.  width * height < 2^31; the parameters are valid.
 // tileSamples (device, one count > 0 per tile of the frame's 32 x 32 grid, tile_y * ceil(width / 32) + tile_x) != nullptr: prep divides each pixel by its tile's
 // count (kDenoisePrepTiles) and `samples` is not used; the buffer must stay as it is until the stream has run the prep.
-// mean (device, row-major width * height, tileSamples == nullptr) != nullptr: prep takes c = mean.rgb instead of colorSum.rgb / float(samples) (kDenoisePrepMean:
-// rf_renderer_denoise_robust hands in the robust mean); colorSum is not read.
+// mean (device, row-major width * height) != nullptr: prep takes c = mean.rgb instead of colorSum.rgb / Nf (kDenoisePrepMean: rf_renderer_denoise_robust hands in
+// the robust mean; with tileSamples, kDenoisePrepMeanTiles: the AOV sums are divided by each pixel's tile's count); colorSum is not read.
 void enqueueDenoise(hipStream_t stream, DenoiseWork& work, const float4* colorSum, const float4* albedoCoverage, const float4* normalDepth, uint32_t width,
                     uint32_t height, uint32_t tilesX, uint32_t samples, const DenoiseParameters& params, float exposure, const uint32_t* tileSamples = nullptr,
                     const float4* mean = nullptr);

@@ -203,9 +203,10 @@ struct Renderer::Impl
     float4*                 aovNormalDepth() const { return aovSums.buffers[1].ptr; }
     float4*                 moments() const { return momentSums.buffers[0].ptr; }
     // bucket sums (rf_renderer_set_buckets; off by default: nothing is allocated or launched then): bucketSums.planes = K planes of the shard's tiles x 1024 float4 each
-    // in one buffer, plane b = the radiance sum over the samples of ordinal b mod K; the robust mean's buffers and the snapshot they hold -- valid until the bucket
-    // sums are restarted
+    // in one buffer, plane b = the radiance sum over the samples of ordinal b mod K (under render_adaptive, bucketTileCounts: of the TILE's samples -- every active tile
+    // holds bucketSums.samples of them); the robust mean's buffers and the snapshot they hold -- valid until the bucket sums are restarted
     SumChannel              bucketSums{false, 1};
+    bool                    bucketTileCounts = false; // kBucketsTileCounts as set: render_adaptive runs with the buckets on and the planes follow the per-tile counts
     float4*                 bucketPlanes() const { return bucketSums.buffers[0].ptr; }
     size_t                  bucketStride() const { return tiles.size() * 1024; }
     RobustWork              robustWork;
@@ -789,8 +790,9 @@ struct Renderer::Impl
         // radiance second moments: a launch of their own unless the tile-list kernel adds them with the image
         b.aovPixels = (aovSums.on && b.numBounces != 0u) ? (b.runs ? kAovPixels : perThread) : 0u;
         b.momentPixels = (!b.tileList && momentSums.on) ? (b.runs ? kMomentPixels : perThread) : 0u;
-        // the bucket sums (the uniform state only: never under a tile list): the batch's first sample has ordinal bucketSums.samples
-        b.bucketPixels = (!b.tileList && bucketSums.on) ? (b.runs ? kBucketPixels : perThread) : 0u;
+        // the bucket sums (under a tile list -- kBucketsTileCounts, checkAdaptive -- their tile-list kernels: every active tile holds bucketSums.samples samples, so one
+        // phase serves the list): the batch's first sample has ordinal bucketSums.samples
+        b.bucketPixels = bucketSums.on ? (b.runs ? kBucketPixels : perThread) : 0u;
         b.buckets = bucketSums.on ? bucketSums.planes : 0u;
         b.bucketPhase = bucketSums.on ? bucketSums.samples % bucketSums.planes : 0u;
         return b;
@@ -1131,7 +1133,7 @@ struct Renderer::Impl
             hipLaunchKernelGGL(l.kernel, sumGrid(l.pixels), dim3(l.runs ? 64u : static_cast<uint32_t>(kBlock)), 0, stream, fp, tileIds.ptr, l.src, l.dst0, l.dst1);
         }
         if (b.bucketPixels != 0u)
-            hipLaunchKernelGGL(bucketKernel(b.runs), sumGrid(b.bucketPixels), dim3(b.runs ? 64u : static_cast<uint32_t>(kBlock)), 0, stream, fp, tileIds.ptr, ps.rad, bucketPlanes(),
+            hipLaunchKernelGGL(bucketKernel(b.runs, b.tileList), sumGrid(b.bucketPixels), dim3(b.runs ? 64u : static_cast<uint32_t>(kBlock)), 0, stream, fp, tileIds.ptr, ps.rad, bucketPlanes(),
                                bucketStride(), b.buckets, b.bucketPhase);
     }
 
@@ -1731,16 +1733,21 @@ void Renderer::readMoments(float* sumSq, uint32_t* sampleCount)
     if (sampleCount) *sampleCount = empty ? 0u : m.momentSums.samples;
 }
 
-void Renderer::setBuckets(uint32_t K)
+void Renderer::setBuckets(uint32_t word)
 {
     Impl& m = *mImpl;
-    if (K != 0u && (K % 2u == 0u || K < 3u || K > kMaxBuckets)) throw std::invalid_argument("set_buckets: K must be 0 (off) or odd with 3 <= K <= 15");
+    // the low byte is K, HOW starts at bit 8 (as in the AOV flags word)
+    const uint32_t K = word & 0xFFu;
+    const bool     tileCounts = (word & kBucketsTileCounts) != 0u;
+    if ((word & ~(0xFFu | kBucketsTileCounts)) != 0u || (K == 0u && tileCounts) || (K != 0u && (K % 2u == 0u || K < 3u || K > kMaxBuckets)))
+        throw std::invalid_argument("set_buckets: K must be 0 (off) or odd with 3 <= K <= 15, alone or ORed with RF_BUCKETS_TILE_COUNTS (K > 0 only)");
     if (K != 0u) m.requireUniform("rf_renderer_set_buckets", ": the bucket sums keep ONE sample count for the frame");
-    if (K == (m.bucketSums.on ? m.bucketSums.planes : 0u)) return;
+    if (K == (m.bucketSums.on ? m.bucketSums.planes : 0u) && tileCounts == m.bucketTileCounts) return;
     RF_HIP(hipSetDevice(m.device));
     RF_HIP(hipStreamSynchronize(m.stream)); // (a batch in flight may still write the sums)
     m.bucketSums.on = K != 0u;
     m.bucketSums.planes = K != 0u ? K : 1u;
+    m.bucketTileCounts = tileCounts; // (a change of the bit alone clears the sums too)
     m.restartBuckets();
     // another K is another allocation (sized before the next sample); off: nothing of the buckets stays allocated
     m.bucketSums.release();
@@ -1774,13 +1781,29 @@ static void requireRobustMean(const char* what, bool on, bool covers, uint32_t K
                                     std::to_string(accumulated) + "): turn the buckets on before the first sample");
 }
 
+// the non-uniform state: the planes follow the per-tile counts when the buckets carry kBucketsTileCounts (they were on before render_adaptive made the state)
+bool Renderer::bucketsPerTile() const { return mImpl->nonUniform() && !mImpl->frameNonUniform() && mImpl->bucketSums.on && mImpl->bucketTileCounts; }
+
+// What the two check on top in that state: every bucket of every tile needs a sample
+static void requireTileBuckets(const char* what, uint32_t K, const std::vector<uint32_t>& tileSamples)
+{
+    const uint32_t least = *std::min_element(tileSamples.begin(), tileSamples.end());
+    if (least < K)
+        throw std::invalid_argument(std::string(what) + ": every one of the " + std::to_string(K) + " buckets of every tile needs a sample, and the smallest tile count is " +
+                                    std::to_string(least) + " (sample adaptively with min_samples >= K)");
+}
+
 void Renderer::robustMean()
 {
     Impl& m = *mImpl;
-    m.requireUniform("rf_renderer_robust_mean");
+    const bool perTile = bucketsPerTile();
+    if (!perTile) m.requireUniform("rf_renderer_robust_mean");
     requireRobustMean("robust_mean", m.bucketSums.on, m.bucketSums.covers(m.accumulated), buckets(), m.bucketSums.samples, m.accumulated, m.worldSize);
+    if (perTile) requireTileBuckets("robust_mean", buckets(), m.tileSamples);
     RF_HIP(hipSetDevice(m.device));
-    enqueueRobustMean(m.stream, m.robustWork, m.bucketPlanes(), m.bucketStride(), m.params.width, m.params.height, m.grid().tilesX, buckets(), m.accumulated, m.params.exposure);
+    // (per tile: the call first waits for the stream and copies the counts to the device, as the other per-tile reads do; the snapshot's count is the leading count)
+    enqueueRobustMean(m.stream, m.robustWork, m.bucketPlanes(), m.bucketStride(), m.params.width, m.params.height, m.grid().tilesX, buckets(), m.accumulated, m.params.exposure,
+                      perTile ? m.uploadTileSamples() : nullptr);
     m.robustValid = true;
     m.robustSamples = m.accumulated;
 }
@@ -1800,8 +1823,13 @@ void Renderer::readRobustMean(float* rgba, uint32_t* bgra8, uint8_t* trim, uint3
 void Renderer::denoiseRobust(const DenoiseParameters& params)
 {
     Impl& m = *mImpl;
-    // rf_renderer_denoise's refusals (the uniform state only: the buckets keep one count), then the robust mean's
-    m.requireUniform("rf_renderer_denoise_robust");
+    // rf_renderer_denoise's refusals (the non-uniform state: as there, the AOV sums must have been kept per tile count for the whole accumulation -- and the buckets
+    // too), then the robust mean's
+    const bool perTile = m.nonUniform();
+    if (perTile && !(m.aovSums.on && m.aovTileCounts() && m.aovSums.covers(m.accumulated)))
+        m.requireUniform("rf_renderer_denoise_robust", ", and the first-hit AOVs were not kept with per-tile counts for the whole accumulation: set RF_AOV_FIRST_HIT | "
+                                                       "RF_AOV_TILE_COUNTS (rf_renderer_set_aovs) before the first sample and rf_renderer_denoise_robust runs in this state");
+    if (!perTile) m.requireUniform("rf_renderer_denoise_robust");
     if (!m.aovSums.on) throw std::invalid_argument("denoise_robust needs the first-hit AOVs: turn them on (rf_renderer_set_aovs) before the first sample");
     if (m.worldSize != 1u) throw std::invalid_argument("denoise_robust needs the whole frame: a tile shard is set");
     if (m.accumulated == 0u) throw std::invalid_argument("denoise_robust: no sample has been accumulated");
@@ -1809,8 +1837,9 @@ void Renderer::denoiseRobust(const DenoiseParameters& params)
         throw std::invalid_argument("denoise_robust: the AOV sample count (" + std::to_string(m.aovSums.samples) + ") differs from the accumulated sample count (" +
                                     std::to_string(m.accumulated) + "): turn the AOVs on before the first sample");
     robustMean();
+    // (per tile: the counts robustMean uploaded are still on the device, and nothing but this stream reads them)
     enqueueDenoise(m.stream, m.denoiseWork, m.image, m.aovAlbedoCoverage(), m.aovNormalDepth(), m.params.width, m.params.height, m.grid().tilesX, m.accumulated, params,
-                   m.params.exposure, nullptr, m.robustWork.mean.ptr);
+                   m.params.exposure, perTile ? m.tileSamplesDevice.ptr : nullptr, m.robustWork.mean.ptr);
     m.denoisedValid = true;
     m.denoisedSamples = m.accumulated;
 }
@@ -1837,10 +1866,13 @@ NoiseEstimate Renderer::noiseEstimate(float* errorMap, float* tileSum, float* ti
 }
 
 // What rf_renderer_render_adaptive and rf_comm_render_adaptive check alike before anything is traced (or exchanged)
-void Renderer::checkAdaptive(const AdaptiveParameters& p) const
+void Renderer::checkAdaptive(const AdaptiveParameters& p, bool sharded) const
 {
     const Impl& m = *mImpl;
-    if (m.bucketSums.on)
+    if (m.bucketSums.on && m.bucketTileCounts && sharded)
+        throw std::invalid_argument("render_adaptive: the bucket sums are on (rf_renderer_set_buckets), and RF_BUCKETS_TILE_COUNTS covers rf_renderer_render_adaptive only: "
+                                    "bucket planes under a tile shard are not kept per tile count; turn the buckets off (rf_renderer_set_buckets(r, 0)) first");
+    if (m.bucketSums.on && !m.bucketTileCounts)
         throw std::invalid_argument("render_adaptive: the bucket sums are on (rf_renderer_set_buckets), and they keep ONE sample count for the frame: turn the buckets off "
                                     "(rf_renderer_set_buckets(r, 0)) before sampling adaptively");
     if (!m.momentSums.on) throw std::invalid_argument("render_adaptive needs the radiance second moments: turn them on (rf_renderer_set_moments) before the first sample");
@@ -1853,13 +1885,15 @@ void Renderer::checkAdaptive(const AdaptiveParameters& p) const
         throw std::invalid_argument("render_adaptive: the moments do not cover the accumulation (turned on partway through): restart the accumulation first");
     if (m.aovSums.on && m.accumulated != 0u && !m.aovSums.covers(m.accumulated))
         throw std::invalid_argument("render_adaptive: the AOV sample count does not cover the accumulation (the AOVs were turned on partway through): restart the accumulation first");
+    if (m.bucketSums.on && m.accumulated != 0u && !m.bucketSums.covers(m.accumulated))
+        throw std::invalid_argument("render_adaptive: the bucket sample count does not cover the accumulation (the buckets were turned on partway through): restart the accumulation first");
 }
 
 AdaptiveResult Renderer::renderAdaptive(const AdaptiveParameters& p)
 {
     Impl& m = *mImpl;
     // (the order of the checks, and so which message a call with several faults gets, is the one this call always had)
-    if (m.bucketSums.on || !m.momentSums.on || (m.aovSums.on && !m.aovTileCounts())) checkAdaptive(p);
+    if ((m.bucketSums.on && !m.bucketTileCounts) || !m.momentSums.on || (m.aovSums.on && !m.aovTileCounts())) checkAdaptive(p);
     if (m.worldSize != 1u) throw std::invalid_argument("render_adaptive needs the whole frame: a tile shard is set (rf_comm_render_adaptive samples a sharded frame adaptively)");
     checkAdaptive(p);
     return renderAdaptiveFrom(p, m.accumulated, false);

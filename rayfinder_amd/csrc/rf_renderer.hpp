@@ -158,6 +158,10 @@ void denoiseTiles(int deviceOrdinal, uint32_t width, uint32_t height, const uint
 // (NULL = skip).  K odd, 3 .. 15.  Synchronous; allocates and frees its own device memory.
 void robustMeanImages(int deviceOrdinal, uint32_t width, uint32_t height, uint32_t K, uint32_t samples, const float* buckets, float exposure, float* outRgba,
                       uint32_t* outBgra8, uint8_t* outTrim);
+// The same with one sample count >= K per 32x32 tile (host memory, ceil(width / 32) * ceil(height / 32) words, tile_y * ceil(width / 32) + tile_x): the bucket planes of
+// a frame of renderAdaptive with kBucketsTileCounts
+void robustMeanTiles(int deviceOrdinal, uint32_t width, uint32_t height, uint32_t K, const uint32_t* tileSamples, const float* buckets, float exposure, float* outRgba,
+                     uint32_t* outBgra8, uint8_t* outTrim);
 
 // The noise estimate over the accumulation and the radiance second moments (rf_noise.hip; the definition: include/rayfinder_amd.h)
 struct NoiseEstimate
@@ -249,20 +253,26 @@ public:
     void     readMoments(float* sumSq, uint32_t* sampleCount);
     // Bucket sums (rf_renderer_set_buckets / rf_renderer_read_buckets): K = 0 off (the default), else odd, 3 .. 15.  While on, K more compact tile-major float4 planes
     // in one allocation: plane b holds {sum r.x, sum r.y, sum r.z, 0} over the samples whose ordinal -- the bucket sample count just before the sample -- is b mod K,
-    // in sample order.  Their own sample count; cleared with the image and whenever K changes.  The uniform state only: std::invalid_argument for a bad K, and for
-    // K > 0 in the non-uniform state; renderAdaptive / checkAdaptive refuse while they are on.
-    // Read: K x width*height*4 floats, plane after plane, each row-major (this rank's pixels; NULL = skip), K and the bucket sample count.
-    void     setBuckets(uint32_t K);
+    // in sample order.  Their own sample count; cleared with the image and whenever the word changes.  The word is K, or K | kBucketsTileCounts (K > 0): until
+    // renderAdaptive is called the same handle; renderAdaptive then runs with the buckets on, the planes of tile t hold its first tileSamples[t] samples (sample j of the
+    // tile in plane j mod K), and robustMean / denoiseRobust combine every pixel with its tile's count.  Without the bit renderAdaptive / checkAdaptive refuse while the
+    // buckets are on.  std::invalid_argument for a bad word, and for K > 0 in the non-uniform state.
+    // Read: K x width*height*4 floats, plane after plane, each row-major (this rank's pixels; NULL = skip), K and the bucket sample count (the leading count).
+    static constexpr uint32_t kBucketsTileCounts = 0x100u;
+    void     setBuckets(uint32_t word);
     uint32_t buckets() const;
+    bool     bucketsPerTile() const; // the non-uniform state of a whole-frame handle whose buckets carry kBucketsTileCounts
     void     readBuckets(float* planes, uint32_t* K, uint32_t* sampleCount);
     // The robust mean over the handle's own bucket sums (rf_renderer_robust_mean; the arithmetic: include/rayfinder_amd.h): enqueued on the handle's stream, keeps a
     // snapshot (allocated by the first call, dropped whenever the bucket sums are cleared).  std::invalid_argument when the buckets are off, their count differs from
-    // the accumulated count or is below K, a tile shard is set or the tiles hold different counts.
+    // the accumulated count or is below K, a tile shard is set or the tiles hold different counts -- unless bucketsPerTile(): then every pixel is combined with its
+    // tile's count (refused when a tile holds fewer than K samples) and the snapshot's count is the leading count.
     // readRobustMean: row-major width*height*4 mean floats, BGRA8, one trim count per pixel (NULL = skip) and the snapshot's sample count; std::invalid_argument
     // without a snapshot.
     void robustMean();
     void readRobustMean(float* rgba, uint32_t* bgra8, uint8_t* trim, uint32_t* sampleCount);
-    // robustMean, then the a-trous filter of denoise with prep's colour c = M.rgb: the result is denoise's snapshot (readDenoised).  Refused as denoise and robustMean are.
+    // robustMean, then the a-trous filter of denoise with prep's colour c = M.rgb: the result is denoise's snapshot (readDenoised).  Refused as denoise and robustMean are
+    // (the non-uniform state: the AOVs with kAovTileCounts and the buckets with kBucketsTileCounts, both covering the accumulation; prep divides by each tile's count).
     void denoiseRobust(const DenoiseParameters& params);
     // The noise estimate over the handle's own sums (rf_renderer_noise_estimate): enqueued on the handle's stream, then waited for.  std::invalid_argument when the
     // moments are off, their count differs from the accumulated count, fewer than 2 samples are accumulated or a tile shard is set.  Host pointers, NULL = skip.
@@ -275,7 +285,9 @@ public:
     // (the non-uniform state): render, renderUntil, setTileShard and the frame gather then throw std::invalid_argument (requireUniformTileSamples), as does denoise
     // unless the AOVs were kept with kAovTileCounts; the reads report the leading count, and readTileSamples / readMean / readTonemapped / noiseEstimate / denoise honour
     // the per-tile counts.  With kAovFirstHit | kAovTileCounts the AOV sums of tile t are those of its first tileSamples[t] samples, as S and Q are.
-    // std::invalid_argument when the moments are off or do not cover the accumulation, the AOVs are on without kAovTileCounts or do not cover it, a tile shard is set,
+    // With K | kBucketsTileCounts the bucket planes of tile t are those of its first tileSamples[t] samples too, and robustMean / denoiseRobust honour the counts.
+    // std::invalid_argument when the moments are off or do not cover the accumulation, the AOVs are on without kAovTileCounts or do not cover it, the buckets are on
+    // without kBucketsTileCounts or do not cover it, a tile shard is set,
     // checkEvery is 0 or the target is negative or not finite.
     AdaptiveResult renderAdaptive(const AdaptiveParameters& params);
     // The same over a tile shard, one rank's part of rf_comm_render_adaptive (renderAdaptive of rf_comm.hpp makes the exchanges around it).  checkAdaptive: renderAdaptive's
@@ -283,7 +295,8 @@ public:
     // the FRAME's leading count (the largest accumulated count over the ranks): the active tiles are those at `leading` -- none when this handle's own count is lower -- and
     // the result speaks of this handle's tiles (stoppedTiles: below its own accumulated count); shardSlots: the sums are addressed through each listed tile's slot in the
     // shard (always so through rf_comm_render_adaptive, at world size 1 as well).
-    void           checkAdaptive(const AdaptiveParameters& params) const;
+    // sharded: the call is rf_comm_render_adaptive's, which the buckets refuse in either form (kBucketsTileCounts covers renderAdaptive alone).
+    void           checkAdaptive(const AdaptiveParameters& params, bool sharded = false) const;
     AdaptiveResult renderAdaptiveFrom(const AdaptiveParameters& params, uint32_t leading, bool shardSlots);
     // What follows the loop once the ranks have agreed on the frame: its largest and smallest tile count, the same on every rank -- while they differ the handle is in the
     // non-uniform state (requireUniformTileSamples) whatever its own tiles hold; cleared with the accumulation -- and `skipFrames` more on the frame counter without

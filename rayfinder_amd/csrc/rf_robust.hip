@@ -2,7 +2,8 @@
 // the buckets' levels (after Buisine et al. 2021, "Firefly removal in Monte Carlo rendering with adaptive Median of meaNs").  The arithmetic is the one
 // include/rayfinder_amd.h writes out ("Bucket sums and the robust mean"), one IEEE f32 operation at a time in that order (-ffp-contract=off, correctly rounded
 // divide, no denormal flushing): tests/robust_restatement.py reproduces it bit for bit.  No atomics: every output is one lane's fixed sequence of operations.
-//   kRobustMean<K>  one lane per pixel; K is a compile-time constant, so the K bucket means and keys live in registers and the sort is a fixed network
+//   kRobustMean<K>       one lane per pixel; K is a compile-time constant, so the K bucket means and keys live in registers and the sort is a fixed network
+//   kRobustMeanTiles<K>  the same with the sample count of the pixel's 32x32 tile (a frame of rf_renderer_render_adaptive, rf_robust_mean_tiles)
 // The display image is the existing kTonemap over the mean with accumulatedSamples = 1.
 #include "rf_robust.hpp"
 
@@ -23,9 +24,11 @@ __device__ __forceinline__ uint32_t tileMajorIndex(uint32_t x, uint32_t y, uint3
     return tile * 1024u + block * 64u + (y & 7u) * 8u + (x & 7u);
 }
 
-template<uint32_t K>
-__global__ __launch_bounds__(256) void kRobustMean(const float4* planes, size_t planeStride, uint32_t width, uint32_t height, uint32_t tilesX, uint32_t samples, float4* mean,
-                                                   uint8_t* trim)
+// The body both kernels share: one lane's pixel i = (x, y) over its sample count >= K -- samplesAll (kRobustMean: one count for the frame) or, TILES, the count of the
+// pixel's tile, tileSamples[(y / 32) frameTilesX + (x / 32)] (kRobustMeanTiles); nothing else differs
+template<uint32_t K, bool TILES>
+__device__ __forceinline__ void robustPixel(const float4* planes, size_t planeStride, uint32_t width, uint32_t height, uint32_t tilesX, uint32_t samplesAll,
+                                            const uint32_t* tileSamples, uint32_t frameTilesX, float4* mean, uint8_t* trim)
 {
     static_assert(K % 2u == 1u && K >= 3u && K <= 15u, "K odd, 3 .. 15");
     constexpr uint32_t HALF = (K - 1u) / 2u;
@@ -33,6 +36,7 @@ __global__ __launch_bounds__(256) void kRobustMean(const float4* planes, size_t 
     if (i >= width * height) return;
     const uint32_t y = i / width, x = i - y * width;
     const uint32_t src = tilesX ? tileMajorIndex(x, y, tilesX) : i;
+    const uint32_t samples = TILES ? tileSamples[(y >> 5) * frameTilesX + (x >> 5)] : samplesAll;
     const uint32_t each = samples / K, more = samples - each * K; // buckets 0 .. more - 1 hold one sample more
     float          mr[K], mg[K], mb[K], key[K];
 #pragma unroll
@@ -82,6 +86,22 @@ __global__ __launch_bounds__(256) void kRobustMean(const float4* planes, size_t 
     trim[i] = static_cast<uint8_t>(c);
 }
 
+template<uint32_t K>
+__global__ __launch_bounds__(256) void kRobustMean(const float4* planes, size_t planeStride, uint32_t width, uint32_t height, uint32_t tilesX, uint32_t samples, float4* mean,
+                                                   uint8_t* trim)
+{
+    robustPixel<K, false>(planes, planeStride, width, height, tilesX, samples, nullptr, 0u, mean, trim);
+}
+
+// The same with one count per 32x32 tile: tileSamples[tile_y * frameTilesX + tile_x] >= K, frameTilesX = ceil(width / 32) (the estimate's tile numbering; the planes
+// may still be row-major, tilesX == 0)
+template<uint32_t K>
+__global__ __launch_bounds__(256) void kRobustMeanTiles(const float4* planes, size_t planeStride, uint32_t width, uint32_t height, uint32_t tilesX, const uint32_t* tileSamples,
+                                                        uint32_t frameTilesX, float4* mean, uint8_t* trim)
+{
+    robustPixel<K, true>(planes, planeStride, width, height, tilesX, 0u, tileSamples, frameTilesX, mean, trim);
+}
+
 using RobustKernel = void (*)(const float4*, size_t, uint32_t, uint32_t, uint32_t, uint32_t, float4*, uint8_t*);
 RobustKernel robustKernel(uint32_t K)
 {
@@ -95,6 +115,21 @@ RobustKernel robustKernel(uint32_t K)
     case 13: return kRobustMean<13>;
     case 15: return kRobustMean<15>;
     default: throw std::logic_error("robustKernel: no such kernel is compiled");
+    }
+}
+using RobustTilesKernel = void (*)(const float4*, size_t, uint32_t, uint32_t, uint32_t, const uint32_t*, uint32_t, float4*, uint8_t*);
+RobustTilesKernel robustTilesKernel(uint32_t K)
+{
+    switch (K)
+    {
+    case 3: return kRobustMeanTiles<3>;
+    case 5: return kRobustMeanTiles<5>;
+    case 7: return kRobustMeanTiles<7>;
+    case 9: return kRobustMeanTiles<9>;
+    case 11: return kRobustMeanTiles<11>;
+    case 13: return kRobustMeanTiles<13>;
+    case 15: return kRobustMeanTiles<15>;
+    default: throw std::logic_error("robustTilesKernel: no such kernel is compiled");
     }
 }
 } // namespace
@@ -117,31 +152,55 @@ void RobustWork::release()
 }
 
 void enqueueRobustMean(hipStream_t stream, RobustWork& w, const float4* planes, size_t planeStride, uint32_t width, uint32_t height, uint32_t tilesX, uint32_t K,
-                       uint32_t samples, float exposure)
+                       uint32_t samples, float exposure, const uint32_t* tileSamples)
 {
     const uint32_t n = width * height;
     w.reserve(n, stream);
-    hipLaunchKernelGGL(robustKernel(K), dim3((n + 255) / 256), dim3(256), 0, stream, planes, planeStride, width, height, tilesX, samples, w.mean.ptr, w.trim.ptr);
+    if (tileSamples)
+        hipLaunchKernelGGL(robustTilesKernel(K), dim3((n + 255) / 256), dim3(256), 0, stream, planes, planeStride, width, height, tilesX, tileSamples,
+                           TileGrid(width, height).tilesX, w.mean.ptr, w.trim.ptr);
+    else
+        hipLaunchKernelGGL(robustKernel(K), dim3((n + 255) / 256), dim3(256), 0, stream, planes, planeStride, width, height, tilesX, samples, w.mean.ptr, w.trim.ptr);
     hipLaunchKernelGGL(tonemapKernel(), dim3((n + 255) / 256), dim3(256), 0, stream, static_cast<const float4*>(w.mean.ptr), n, 1u, exposure, w.bgra.ptr);
     RF_HIP(hipGetLastError());
+}
+
+// rf_robust_mean_images (tileSamples == nullptr) and rf_robust_mean_tiles (one count per tile of the frame's grid, host memory)
+static void robustMeanHost(int deviceOrdinal, uint32_t width, uint32_t height, uint32_t K, uint32_t samples, const uint32_t* tileSamples, const float* buckets, float exposure,
+                           float* outRgba, uint32_t* outBgra8, uint8_t* outTrim)
+{
+    requireDevice(deviceOrdinal);
+    const uint64_t n = static_cast<uint64_t>(width) * height;
+    // (leaving the scope: the stream is synchronised, the buffers are freed, the stream is destroyed -- ScopedStream)
+    ScopedStream           stream;
+    DeviceBuffer<float4>   in;
+    DeviceBuffer<uint32_t> counts;
+    RobustWork             work;
+    ScopedStream::Drain    drain{stream};
+    in.alloc(K * n);
+    RF_HIP(hipMemcpyAsync(in.ptr, buckets, K * n * sizeof(float4), hipMemcpyHostToDevice, stream.handle));
+    if (tileSamples)
+    {
+        const uint32_t tiles = TileGrid(width, height).count();
+        counts.alloc(tiles);
+        RF_HIP(hipMemcpyAsync(counts.ptr, tileSamples, tiles * sizeof(uint32_t), hipMemcpyHostToDevice, stream.handle));
+    }
+    enqueueRobustMean(stream.handle, work, in.ptr, n, width, height, 0u, K, samples, exposure, tileSamples ? counts.ptr : nullptr);
+    if (outRgba) RF_HIP(hipMemcpyAsync(outRgba, work.mean.ptr, n * sizeof(float4), hipMemcpyDeviceToHost, stream.handle));
+    if (outBgra8) RF_HIP(hipMemcpyAsync(outBgra8, work.bgra.ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream.handle));
+    if (outTrim) RF_HIP(hipMemcpyAsync(outTrim, work.trim.ptr, n * sizeof(uint8_t), hipMemcpyDeviceToHost, stream.handle));
+    RF_HIP(hipStreamSynchronize(stream.handle));
 }
 
 void robustMeanImages(int deviceOrdinal, uint32_t width, uint32_t height, uint32_t K, uint32_t samples, const float* buckets, float exposure, float* outRgba,
                       uint32_t* outBgra8, uint8_t* outTrim)
 {
-    requireDevice(deviceOrdinal);
-    const uint64_t n = static_cast<uint64_t>(width) * height;
-    // (leaving the scope: the stream is synchronised, the buffers are freed, the stream is destroyed -- ScopedStream)
-    ScopedStream         stream;
-    DeviceBuffer<float4> in;
-    RobustWork           work;
-    ScopedStream::Drain  drain{stream};
-    in.alloc(K * n);
-    RF_HIP(hipMemcpyAsync(in.ptr, buckets, K * n * sizeof(float4), hipMemcpyHostToDevice, stream.handle));
-    enqueueRobustMean(stream.handle, work, in.ptr, n, width, height, 0u, K, samples, exposure);
-    if (outRgba) RF_HIP(hipMemcpyAsync(outRgba, work.mean.ptr, n * sizeof(float4), hipMemcpyDeviceToHost, stream.handle));
-    if (outBgra8) RF_HIP(hipMemcpyAsync(outBgra8, work.bgra.ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream.handle));
-    if (outTrim) RF_HIP(hipMemcpyAsync(outTrim, work.trim.ptr, n * sizeof(uint8_t), hipMemcpyDeviceToHost, stream.handle));
-    RF_HIP(hipStreamSynchronize(stream.handle));
+    robustMeanHost(deviceOrdinal, width, height, K, samples, nullptr, buckets, exposure, outRgba, outBgra8, outTrim);
+}
+
+void robustMeanTiles(int deviceOrdinal, uint32_t width, uint32_t height, uint32_t K, const uint32_t* tileSamples, const float* buckets, float exposure, float* outRgba,
+                     uint32_t* outBgra8, uint8_t* outTrim)
+{
+    robustMeanHost(deviceOrdinal, width, height, K, 0u, tileSamples, buckets, exposure, outRgba, outBgra8, outTrim);
 }
 } // namespace rf

@@ -25,6 +25,8 @@ struct RobustWork
 
 // Enqueue kRobustMean<K> and kTonemap on `stream`.  planes: K planes of planeStride float4 each.  tilesX != 0: every plane is a compact tile-major buffer holding every
 // tile of the frame in tile order (a handle without a tile shard), tilesX tiles per row; 0: row-major.  width * height < 2^31; K odd, 3 .. 15; samples >= K.
+// tileSamples (device, one count >= K per tile of the frame's 32 x 32 grid, tile_y * ceil(width / 32) + tile_x) != nullptr: every pixel is combined with its tile's
+// count (kRobustMeanTiles<K>) and `samples` is not used; the buffer must stay as it is until the stream has run the kernel.
 void enqueueRobustMean(hipStream_t stream, RobustWork& work, const float4* planes, size_t planeStride, uint32_t width, uint32_t height, uint32_t tilesX, uint32_t K,
-                       uint32_t samples, float exposure);
+                       uint32_t samples, float exposure, const uint32_t* tileSamples = nullptr);
 } // namespace rf

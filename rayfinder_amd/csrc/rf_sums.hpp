@@ -56,7 +56,10 @@ AccumulateRunsKernel accumulateRunsKernel(uint32_t pixelsPerWorkgroup);
 // 3 <= K <= kMaxBuckets.  runs: the LDS-staged kernel for the pixel-major slot order, a 64-lane workgroup per kBucketPixels pixels, their runs staged in chunks of
 // kBucketChunk samples (kBucketPixels x 3 rows of kBucketChunk + 1 floats = 1 584 B of LDS), one summing lane per (pixel, channel, bucket) walking its row at stride K;
 // else one lane per pixel (kBlock per workgroup, any slot order), plane after plane.  Its source is ps.rad.
+// tileList (rf_renderer_render_adaptive with RF_BUCKETS_TILE_COUNTS): the batch's path slots belong to the fp.numTiles tiles that tileIds lists and every plane holds
+// the WHOLE frame: the sums of local pixel lp sit at tileIds[lp >> 10] * 1024 + (lp & 1023) of every plane, as the other sums' do.  All listed tiles share one bucket
+// sample count, so one phase serves the launch; a batch shorter than K leaves the planes it does not reach untouched.  (No form for a tile shard's slot list.)
 constexpr uint32_t kMaxBuckets = 15, kBucketPixels = 4, kBucketChunk = 32;
 using BucketKernel = void (*)(FrameParams fp, const uint32_t* tileIds, const float4* src, float4* planes, size_t planeStride, uint32_t K, uint32_t phase);
-BucketKernel bucketKernel(bool runs);
+BucketKernel bucketKernel(bool runs, bool tileList);
 } // namespace rf
