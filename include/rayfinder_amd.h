@@ -193,7 +193,8 @@ RF_API int rf_renderer_read_tonemapped(rf_renderer* r, uint32_t* dst_bgra8);
  * rf_renderer_read_accumulation; either pointer may be NULL) and the AOV sample count.  With a tile shard set, this rank's pixels and zeros elsewhere:
  * the sum of the ranks' reads is the whole frame.  (rf_renderer_gather_frame carries them with RF_GATHER_AOVS: the root then holds the whole frame's AC and ND
  * sums in device memory, rf_comm_read_plane planes 1 and 2.)  In the non-uniform state of
- * rf_renderer_render_adaptive: the sums as they are; the count reported is the leading count L, and the divisor of a pixel is its tile's own count
+ * rf_renderer_render_adaptive: the sums as they are; the count reported is the AOV sample count -- the leading count L, since the sums cover the accumulation (the
+ * call that made the state needs that); 0, with zero sums, once the flags were changed in that state -- and the divisor of a pixel is its tile's own count
  * (rf_renderer_read_tile_samples), as for rf_renderer_read_accumulation and rf_renderer_read_moments.
  * A NULL handle, unknown flag bits or RF_AOV_TILE_COUNTS without RF_AOV_FIRST_HIT: RF_ERROR_INVALID_ARGUMENT, the state kept. */
 #define RF_AOV_FIRST_HIT 1u
@@ -431,7 +432,8 @@ RF_API int rf_renderer_denoise_robust(rf_renderer* r, const rf_denoise_parameter
  * the cap only while its mean error is > 0: a tile in which no pixel has shown any variance so far -- black, constant or non-finite pixels have e = 0 -- is <= 0
  * and stops at the first check, as step 4 says.  min_samples = cap puts the only check at the cap: no tile can stop.)  In the non-uniform state:
  *   rf_renderer_read_accumulation, rf_renderer_read_moments, rf_renderer_read_aovs: the sums as they are; the count they report is L, and the divisor of a pixel is
- *       its tile's own count.
+ *       its tile's own count.  (For the moments and the AOV sums that is their own sample count, as ever: it IS L while they cover the accumulation, which the call
+ *       that made the state requires; a switch changed in the state clears its sums, and its count then reads 0 -- see INTERLEAVINGS below.)
  *   rf_renderer_read_tile_samples: the counts (tile_samples may be NULL) and ceil(width / 32) * ceil(height / 32).  Uniform state: every tile of the shard at the
  *       accumulated count, a tile outside the shard 0.
  *   rf_renderer_read_mean: row-major width*height*4 floats {S.rgb / float(tile_samples[t]), 1}, one f32 division per channel; {0, 0, 0, 1} in a tile without a sample.
@@ -440,7 +442,28 @@ RF_API int rf_renderer_denoise_robust(rf_renderer* r, const rf_denoise_parameter
  *       state the texels are those of the sums divided by the accumulated count).
  *   rf_renderer_noise_estimate: Nf = float(tile_samples[t]) for the pixels of tile t (every count is >= 2: a tile stops at an estimate); out->samples = L.
  * rf_noise_estimate_tiles: rf_noise_estimate_images with one count per tile (tile_samples: ceil(width / 32) * ceil(height / 32) words); out->samples = the largest.
- * A NULL input or `out`, a zero size and any tile count below 2 are refused before any device call. */
+ * A NULL input or `out`, a zero size and any tile count below 2 are refused before any device call.
+ *
+ * INTERLEAVINGS.  What the paragraphs above leave open between the switches, the sums and the two states follows from two general rules -- a sum covers the
+ * accumulation only if it was on from its first sample, and whatever clears the image clears every sum with its count, the per-tile counts (both states) and both
+ * snapshots -- and is stated here once (tests/handle_model.py is these rules as a program; tests/test_gpu_handle_walk.py holds the handle to it over random call
+ * sequences):
+ *   - A refused call (RF_ERROR_INVALID_ARGUMENT) changes nothing: no sum, count, snapshot or switch, and not the frame counter.  Where several refusals apply to one
+ *     call, only the order stated above holds (the non-uniform state's message comes first for rf_renderer_denoise, and so for rf_renderer_denoise_robust, which is
+ *     refused as it is); otherwise which of the messages is given is not promised.
+ *   - rf_renderer_set_moments and rf_renderer_set_aovs are accepted in the non-uniform state.  A change clears that family's sums and sets its count to 0, as always;
+ *     the family then no longer covers the accumulation, so a further rf_renderer_render_adaptive is refused (the AOVs: unless they were turned off) and the per-tile
+ *     reads that need the family (rf_renderer_noise_estimate; rf_renderer_denoise) are refused until the accumulation is restarted.
+ *     rf_renderer_set_buckets(0) is accepted there too; K > 0 is refused, as said above, also when K and the bit are the ones already set.
+ *   - Every accepted rf_renderer_set_tile_shard restarts the accumulation, a call with the rank and world size already set included (the tiles are dealt anew).  So does
+ *     every accepted rf_renderer_bind_accumulation_buffer: binding a buffer, binding another, and unbinding (NULL: back to the handle's own buffer).  The frame counter
+ *     keeps counting through all of them, as through rf_renderer_set_render_parameters; the parameters compare equal or not as a whole, and an equal set restarts nothing.
+ *   - rf_renderer_render(n) into a full accumulation traces nothing and advances the frame counter by n: the next accumulation starts n frames later.
+ *     rf_renderer_render_until advances it by *frames_rendered, rf_renderer_render_adaptive by the growth of L.
+ *   - A restarted accumulation reads as nothing: every sum zero with count 0, every tile of the shard at 0, rf_renderer_read_mean {0, 0, 0, 1} in the shard's tiles and
+ *     rf_renderer_read_tonemapped the texel of that mean (opaque black); outside the shard's tiles the mean is four zeros and the texel 0.
+ *   - The snapshots: rf_renderer_read_denoised's is dropped with the AOV sums (above) and NOT by a change of the buckets, also when rf_renderer_denoise_robust made it;
+ *     rf_renderer_read_robust_mean's is dropped with the bucket sums and NOT by a change of the AOV flags.  Later samples leave both as they are, with their counts. */
 typedef struct rf_adaptive_parameters
 {
     float    target_tile_error;
