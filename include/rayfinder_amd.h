@@ -339,7 +339,8 @@ RF_API int rf_renderer_render_until(rf_renderer* r, float target_mean_error, uin
  * what they are with the buckets off.  A change of the bit alone clears the bucket sums, as a change of K does; rf_renderer_read_buckets reports K without the bit, and
  * in the non-uniform state the planes as they are and L.  rf_comm_render_adaptive stays refused while the buckets are on, in either form (bucket planes under a tile
  * shard keep one count).  rf_renderer_set_buckets(K > 0), with or without the bit, is refused in the non-uniform state: the buckets could not cover the accumulation.
- * rf_renderer_render, rf_renderer_render_until, rf_renderer_set_tile_shard and rf_renderer_gather_frame work as before; the frame gather does not carry the bucket planes.
+ * rf_renderer_render, rf_renderer_render_until, rf_renderer_set_tile_shard and rf_renderer_gather_frame work as before; the frame gather does not carry the bucket planes
+ * themselves: with RF_GATHER_ROBUST_MEAN every rank combines its own and ONE plane travels (ROBUST MEAN ACROSS RANKS, below).
  * rf_renderer_read_buckets: K x width*height*4 floats, plane after plane, each row-major (the layout of rf_renderer_read_accumulation; may be NULL), K and the bucket
  * sample count (either may be NULL).  With a tile shard set, this rank's pixels and zeros elsewhere: the sum of the ranks' reads is the whole frame.  Buckets off:
  * nothing is written to `buckets`, K = 0, count = 0.
@@ -570,11 +571,12 @@ RF_API int rf_renderer_bind_accumulation_buffer(rf_renderer* r, void* device_ptr
  *
  * PLANES.  The exchange can carry every per-pixel sum the handle keeps, in the same single group of sends and receives.  The sums are numbered in a fixed order:
  * plane 0 = S (the image, always carried), 1 = AC = {albedo.rgb, coverage}, 2 = ND = {normal.xyz, depth} (both with RF_GATHER_AOVS), 3 = Q, the radiance second
- * moments (RF_GATHER_MOMENTS).  A gather carries plane 0 and the planes its flags ask for, in that order: the plan is the one-plane plan once per carried plane
+ * moments (RF_GATHER_MOMENTS), 4 = {M.rgb, float(c)}, the robust mean of the rank's own pixels (RF_GATHER_ROBUST_MEAN; no sum: ROBUST MEAN ACROSS RANKS, below).  A gather carries plane 0 and the planes its flags ask for, in that order: the plan is the one-plane plan once per carried plane
  * (rf_gather_plan_planes) -- on the root, for each plane in order, the receives of that plane in rank order; on a sender, its sends in plane order; per (source,
  * destination) pair the k-th send meets the k-th receive.  On the root every plane has its own staging area (rf_gather_layout; the areas lie one after another in one
- * allocation) and its own row-major width*height float4 image, and ONE kernel un-tiles all carried planes.  With neither flag a gather enqueues exactly what it
- * always did, and rf_comm_last_exchange_ms brackets the whole exchange, the un-tile included, either way.
+ * allocation) and its own row-major width*height float4 image, and ONE kernel un-tiles all carried planes 0 .. 3 (plane 4 has a launch of its own behind it, which
+ * splits it into M and the trim image).  With neither flag a gather enqueues exactly what it
+ * always did, and without RF_GATHER_ROBUST_MEAN exactly what it did before that flag existed, and rf_comm_last_exchange_ms brackets the whole exchange, the un-tile included, either way.
  * RF_GATHER_AOVS is refused with RF_ERROR_INVALID_ARGUMENT -- the state kept, nothing enqueued on this rank -- when the AOVs are off, when the AOV sample count
  * differs from the accumulated count (AOVs turned on partway through) or when no sample has been accumulated; RF_GATHER_MOMENTS likewise for the moments.  (A rank
  * whose shard holds no tile -- more ranks than tiles -- sends nothing, and only the switch is checked on it.)  The refusal of the non-uniform state of
@@ -587,11 +589,40 @@ RF_API int rf_renderer_bind_accumulation_buffer(rf_renderer* r, void* device_ptr
  * rf_renderer_read_accumulation, rf_renderer_read_aovs (AC, ND) and rf_renderer_read_moments; rf_comm_read_denoised and rf_comm_noise_estimate are bit for bit that
  * handle's rf_renderer_read_denoised (after rf_renderer_denoise with the same parameters) and rf_renderer_noise_estimate: the same filter and estimate definitions
  * (above), over row-major instead of tile-major sums.
+ * After the same samples, rf_comm_read_robust_mean on the root (mean, texels, trim, count) is bit for bit rf_renderer_read_robust_mean of one handle without a tile
+ * shard after rf_renderer_robust_mean.  rf_comm_read_denoised after rf_comm_denoise_robust is bit for bit that handle's rf_renderer_read_denoised after
+ * rf_renderer_denoise_robust with the same parameters.  Planes 0 to 3, rf_comm_denoise and rf_comm_noise_estimate of the same gather are what they are without the flag.
+ *
+ * ROBUST MEAN ACROSS RANKS.  The robust mean (the definition above) is per pixel -- no term looks at a neighbour -- so a sharded frame needs no bucket plane on the
+ * root: with RF_GATHER_ROBUST_MEAN every rank that owns tiles first runs the combine over its own shard-compact bucket planes, on the handle's stream, with the one
+ * count N = its accumulated count, into a shard-compact tile-major float4 buffer {M.rgb, float(c)} owned by the handle (allocated by the first such gather, freed
+ * where the bucket planes are freed: a change of K, of the bit, or the buckets switched off; NOT the snapshot of rf_renderer_read_robust_mean, which a sharded handle cannot have).  That buffer travels as plane 4, in the same one
+ * group, behind planes 0 .. 3 and in front of the counts: ONE plane on the wire instead of K, no K row-major images on the root, and the same bits by construction.
+ * The trim count c <= 7 is exact in an f32 and M.a is the constant 1, so c rides in .w and no byte plane is exchanged.  The padding pixels of ragged tiles hold zero
+ * sums, combine to M = 0, c = 0 and are never un-tiled.  On the root the un-tile of plane 4 leaves a row-major {M.rgb, 1} image and a row-major uint8 trim image in
+ * device memory owned by the comm; the root's own shard is read in place at gather time, as the other planes are, so the root-side calls see the state AT THE GATHER
+ * whatever is rendered afterwards.  The flag combines with every other flag, RF_GATHER_LOOPBACK included.
+ * Refused with RF_ERROR_INVALID_ARGUMENT -- every check of the handle's state before anything is enqueued, the state kept, as for RF_GATHER_AOVS, the non-uniform
+ * state's refusal first (the communicator's own checks -- an aborted transport -- follow the combine, which writes the handle's plane-4 buffer and nothing else) --
+ * in the NON-UNIFORM state whatever the other flags are (RF_GATHER_TILE_COUNTS does not lift it: plane 4 is combined with ONE count, and a whole-frame handle at
+ * world size 1 may hold bucket planes per tile count after rf_renderer_render_adaptive -- rf_renderer_robust_mean is the call for that handle), when the buckets are off, when nothing has been accumulated, when the bucket sample count differs from the accumulated count (the message names both) or when
+ * N < K (the message names K and N).  A rank whose shard holds no tile checks only the switch and sends nothing.  Under a tile shard the buckets always keep ONE
+ * count: RF_BUCKETS_TILE_COUNTS makes no difference there, rf_comm_render_adaptive stays refused while the buckets are on, and with RF_GATHER_TILE_COUNTS in the
+ * ordinary state the combine is unchanged.
+ * rf_comm_gathered_planes reports the flag.  rf_comm_read_plane and rf_comm_plane_device stay 0 .. 3: plane 4 is read through
+ * rf_comm_read_robust_mean(c, r, rgba, bgra8, trim, K, sample_count): row-major width*height*4 floats {M.rgb, 1}, BGRA8 texels (kTonemap over M with
+ * accumulatedSamples = 1 and the exposure of the handle passed in, enqueued on that handle's stream and waited for), one trim byte per pixel, the K of the combine and
+ * sample_count = the N the gather recorded (rf_comm_gathered_planes' N: 0 on a root whose shard holds no tile, unless the counts travelled).  Any pointer may be NULL.
+ * rf_comm_denoise_robust(c, r, params): rf_comm_denoise with prep's colour c = the gathered M (rf_renderer_denoise_robust's filter), per tile count when the gather
+ * carried counts; needs RF_GATHER_AOVS | RF_GATHER_ROBUST_MEAN; refused as rf_comm_denoise is (N = 0, a tile without a sample, bad parameters).  The result is the
+ * comm's ordinary denoise snapshot, read with rf_comm_read_denoised, and is dropped by the next gather.
+ * Out of scope: `rf-render --gpus N --buckets` stays refused; bucket planes per tile count across ranks stay unsupported; raw bucket planes are not gathered (every
+ * rank's rf_renderer_read_buckets is still the way to them).
  *
  * The root-side calls below take the communicator and the ROOT's handle, whose stream, device and exposure they use.  Each returns RF_ERROR_INVALID_ARGUMENT, with a
  * message that says which case applies, when this rank was not the root of the last gather, when no gather has been made, or when the last gather did not carry the
  * planes the call needs (the AOVs for the denoiser, the moments for the estimate, the plane asked for).
- * rf_comm_gathered_planes: RF_GATHER_AOVS / RF_GATHER_MOMENTS as carried by the last gather, its frame size and N; any pointer may be NULL.
+ * rf_comm_gathered_planes: RF_GATHER_AOVS / RF_GATHER_MOMENTS / RF_GATHER_TILE_COUNTS / RF_GATHER_ROBUST_MEAN as carried by the last gather, its frame size and N; any pointer may be NULL.
  * rf_comm_read_plane: waits for the handle's stream and copies plane 0 .. 3 to the host (width*height*4 floats, row-major).  rf_comm_plane_device: the plane's
  * image in device memory (owned by the comm, valid until the next gather; work on it belongs on the handle's stream).
  * rf_comm_denoise: the a-trous denoiser (the definition above, one count N) enqueued on the handle's stream over the gathered planes 0, 1, 2 where they lie: the
@@ -639,6 +670,7 @@ typedef struct rf_comm rf_comm;
 #define RF_GATHER_AOVS    2u  /* with the image: AC = {albedo.rgb, coverage} and ND = {normal.xyz, depth} */
 #define RF_GATHER_MOMENTS 4u  /* with the image: Q */
 #define RF_GATHER_TILE_COUNTS 8u /* with the image: one sample count per tile (tile-adaptive sampling across ranks, below) */
+#define RF_GATHER_ROBUST_MEAN 16u /* with the image: the robust mean of every rank's own pixels, combined before the exchange: plane 4 = {M.rgb, float(c)} */
 RF_API int  rf_comm_unique_id(uint8_t id_out[RF_COMM_ID_BYTES]);
 RF_API int  rf_comm_create(const uint8_t id[RF_COMM_ID_BYTES], uint32_t rank, uint32_t world_size, int32_t device_ordinal, rf_comm** out);
 RF_API void rf_comm_destroy(rf_comm* c);
@@ -665,6 +697,9 @@ typedef struct rf_comm_adaptive_result
 RF_API int  rf_comm_render_adaptive(rf_comm* c, rf_renderer* r, const rf_adaptive_parameters* params, rf_comm_adaptive_result* result);
 RF_API int  rf_comm_read_tile_samples(rf_comm* c, uint32_t* tile_samples /* may be NULL */, uint32_t* num_tiles);
 RF_API int  rf_comm_read_mean(rf_comm* c, rf_renderer* r, float* rgba);
+/* After a gather with RF_GATHER_ROBUST_MEAN, on the root (ROBUST MEAN ACROSS RANKS, above); any out pointer may be NULL */
+RF_API int  rf_comm_read_robust_mean(rf_comm* c, rf_renderer* r, float* rgba, uint32_t* bgra8, uint8_t* trim, uint32_t* K, uint32_t* sample_count);
+RF_API int  rf_comm_denoise_robust(rf_comm* c, rf_renderer* r, const rf_denoise_parameters* params);   /* NULL = defaults; needs RF_GATHER_AOVS | RF_GATHER_ROBUST_MEAN */
 /* Max over ranks of *value (timing plumbing for hosts without another collective layer; also a barrier). */
 RF_API int  rf_comm_all_reduce_max(rf_comm* c, rf_renderer* r /* NULL: default stream */, double* value);
 /* What RCCL reports for the communicator (ncclCommCount / ncclCommUserRank / ncclCommCuDevice); any pointer may be NULL.
@@ -755,7 +790,7 @@ RF_API int rf_gather_plan(uint32_t width, uint32_t height, uint32_t world_size, 
 /* The operations a gather with RF_GATHER_TILE_COUNTS posts for the counts, behind those of its planes: {is_send, peer, offset_words, count_words} -- the fields of
  * rf_gather_op read as uint32 words (one per tile) of the root's count staging area (receive) or of the rank's own counts (send).  Host arithmetic. */
 RF_API int rf_gather_plan_counts(uint32_t width, uint32_t height, uint32_t world_size, uint32_t rank, uint32_t root, uint32_t flags, rf_gather_op* ops, uint32_t* num_ops);
-/* The same for a gather with RF_GATHER_AOVS / RF_GATHER_MOMENTS in `flags`: the one-plane list once per carried plane (plane 0 = S, 1 = AC, 2 = ND, 3 = Q), the
+/* The same for a gather with RF_GATHER_AOVS / RF_GATHER_MOMENTS / RF_GATHER_ROBUST_MEAN in `flags`: the one-plane list once per carried plane (plane 0 = S, 1 = AC, 2 = ND, 3 = Q, 4 = the robust mean), the
  * receives of all planes first (plane after plane, each in rank order), then the sends in plane order.  offset_tiles counts from the start of THAT plane's own staging
  * area (a receive) or compact buffer (a send).  With neither flag the list is rf_gather_plan's with plane = 0.  ops == NULL: count query. */
 typedef struct rf_gather_plane_op

@@ -342,10 +342,23 @@ RF_GATHER_LOOPBACK = 1
 RF_GATHER_AOVS = 2      # with the image: plane 1 = {albedo.rgb, coverage}, plane 2 = {normal.xyz, depth}
 RF_GATHER_MOMENTS = 4   # with the image: plane 3 = the radiance second moments
 RF_GATHER_TILE_COUNTS = 8   # with the image: one sample count per tile (TileComm.render_adaptive)
+RF_GATHER_ROBUST_MEAN = 16  # with the image: plane 4 = the robust mean of every rank's own pixels {M.rgb, float(trim)}, combined before the exchange
 
 
-def _gather_flags(loopback=False, aovs=False, moments=False, tile_counts=False):
-    return (RF_GATHER_LOOPBACK if loopback else 0) | (RF_GATHER_AOVS if aovs else 0) | (RF_GATHER_MOMENTS if moments else 0) | (RF_GATHER_TILE_COUNTS if tile_counts else 0)
+def _gather_flags(loopback=False, aovs=False, moments=False, tile_counts=False, robust_mean=False):
+    return ((RF_GATHER_LOOPBACK if loopback else 0) | (RF_GATHER_AOVS if aovs else 0) | (RF_GATHER_MOMENTS if moments else 0) | (RF_GATHER_TILE_COUNTS if tile_counts else 0)
+            | (RF_GATHER_ROBUST_MEAN if robust_mean else 0))
+
+
+class _GatheredPlanes(dict):
+    """TileComm.gathered_planes()'s dict.  The flags that came later, tile_counts and robust_mean, are ABSENT WHEN FALSE: they are stored only when the gather carried
+    them, so a gather without them still compares equal to the dict it always gave.  Only the subscript reads an absent one as False (g["robust_mean"]); `in`, .get()
+    and iteration see the keys that are stored, and dict(g) is a plain dict without this.  Prefer g.get("robust_mean", False) in new code."""
+
+    def __missing__(self, key):
+        if key in ("tile_counts", "robust_mean"):
+            return False
+        raise KeyError(key)
 
 
 def gather_layout(width, height, world_size):
@@ -367,12 +380,12 @@ def gather_plan(width, height, world_size, rank, root=0, loopback=False):
     return ops
 
 
-def gather_plan_planes(width, height, world_size, rank, root=0, loopback=False, aovs=False, moments=False):
-    """gather_plan for a gather that also carries the AOV sums (planes 1, 2) and / or the second moments (plane 3) in the one group:
+def gather_plan_planes(width, height, world_size, rank, root=0, loopback=False, aovs=False, moments=False, robust_mean=False):
+    """gather_plan for a gather that also carries the AOV sums (planes 1, 2), the second moments (plane 3) and / or the robust mean (plane 4) in the one group:
     (n, 5) u32 rows {is_send, peer, plane, offset_tiles, count_tiles}; offsets count from the start of the plane's own staging area / compact buffer.
     Host arithmetic, no GPU."""
     n = C.c_uint32(0)
-    flags = _gather_flags(loopback, aovs, moments)
+    flags = _gather_flags(loopback, aovs, moments, robust_mean=robust_mean)
     check(lib.rf_gather_plan_planes(width, height, world_size, rank, root, flags, None, C.byref(n)))
     ops = np.zeros((n.value, 5), np.uint32)
     check(lib.rf_gather_plan_planes(width, height, world_size, rank, root, flags, _ptr(ops), C.byref(n)))
@@ -454,12 +467,15 @@ class TileComm:
     # the root's side of a gather that carried more than the image (Renderer.gather_frame(..., aovs=True, moments=True)); every call is refused on another rank,
     # before any gather, and when the last gather did not carry the planes it needs
     def gathered_planes(self):
-        """What the last gather left on this (root) rank: dict(aovs, moments, width, height, samples)."""
+        """What the last gather left on this (root) rank: dict(aovs, moments, width, height, samples), and tile_counts / robust_mean = True when it carried them
+        (looked up after a gather without them: False)."""
         f, w, h, n = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
         check(lib.rf_comm_gathered_planes(self._h, C.byref(f), C.byref(w), C.byref(h), C.byref(n)))
-        out = dict(aovs=bool(f.value & RF_GATHER_AOVS), moments=bool(f.value & RF_GATHER_MOMENTS), width=w.value, height=h.value, samples=n.value)
+        out = _GatheredPlanes(aovs=bool(f.value & RF_GATHER_AOVS), moments=bool(f.value & RF_GATHER_MOMENTS), width=w.value, height=h.value, samples=n.value)
         if f.value & RF_GATHER_TILE_COUNTS:                                   # (a key of its own, and only then: a gather without counts reports what it always did)
             out["tile_counts"] = True
+        if f.value & RF_GATHER_ROBUST_MEAN:
+            out["robust_mean"] = True
         return out
 
     def read_plane(self, renderer, plane):
@@ -525,6 +541,24 @@ class TileComm:
         mean = np.zeros((g["height"], g["width"], 4), np.float32)
         check(lib.rf_comm_read_mean(self._h, renderer._h, _ptr(mean)))
         return mean
+
+    # the robust mean of the sharded frame (include/rayfinder_amd.h: "ROBUST MEAN ACROSS RANKS"): every rank combined its own pixels before the exchange
+    def read_robust_mean(self, renderer):
+        """Root, after a gather with robust_mean=True: the dict of ReferencePathTracer.read_robust_mean (mean, bgra8 under the renderer's exposure, trim, samples: the
+        N the gather recorded) plus K, as the gather left them."""
+        g = self.gathered_planes()
+        h, w = g["height"], g["width"]
+        rgba = np.zeros((h, w, 4), np.float32)
+        bgra = np.zeros((h, w), np.uint32)
+        trim = np.zeros((h, w), np.uint8)
+        k, n = C.c_uint32(0), C.c_uint32(0)
+        check(lib.rf_comm_read_robust_mean(self._h, renderer._h, _ptr(rgba), _ptr(bgra), _ptr(trim), C.byref(k), C.byref(n)))
+        return dict(mean=rgba[..., :3], bgra8=bgra, trim=trim, samples=n.value, K=k.value)
+
+    def denoise_robust(self, renderer, params=None):
+        """Root: denoise with the gathered robust mean in place of the plain mean (the gather needs aovs=True and robust_mean=True); read_denoised reads the result.
+        params as for denoise."""
+        check(lib.rf_comm_denoise_robust(self._h, renderer._h, C.byref(_denoise_parameters(dict(params or {})))))
 
 
 # ------------------------------------------------------------------------------------- renderer
@@ -936,14 +970,16 @@ class ReferencePathTracer:
         check(lib.rf_renderer_accumulation_device_buffer(self._h, C.byref(p), C.byref(n)))
         return p.value, n.value
 
-    def gather_frame(self, comm, root=0, loopback=False, aovs=False, moments=False, tile_counts=False):
+    def gather_frame(self, comm, root=0, loopback=False, aovs=False, moments=False, tile_counts=False, robust_mean=False):
         """Frame-end RCCL exchange (collective; enqueued on the handle's stream).  Root: device pointer of the
         row-major W*H float4 image; other ranks: None.  aovs / moments: the first-hit AOV sums / the radiance second moments travel in the same group
         and are un-tiled with the image (they must be on from the first sample); the root then reads, denoises and estimates the gathered frame through
         comm.read_plane / denoise / noise_estimate.  tile_counts: the per-tile sample counts travel too (needed after comm.render_adaptive stopped some tiles):
-        the root's denoise / noise_estimate then take each tile's own count, and comm.read_tile_samples / read_mean read them."""
+        the root's denoise / noise_estimate then take each tile's own count, and comm.read_tile_samples / read_mean read them.  robust_mean: every rank combines
+        its own bucket sums (set_buckets from the first sample, at least K samples) before the exchange and the result travels as one more plane; the root reads it
+        through comm.read_robust_mean and denoises with it through comm.denoise_robust."""
         p = C.c_void_p()
-        check(lib.rf_renderer_gather_frame(self._h, comm._h, root, _gather_flags(loopback, aovs, moments, tile_counts), C.byref(p)))
+        check(lib.rf_renderer_gather_frame(self._h, comm._h, root, _gather_flags(loopback, aovs, moments, tile_counts, robust_mean), C.byref(p)))
         return p.value
 
     def tonemap_device_image(self, device_ptr, width, height, samples):

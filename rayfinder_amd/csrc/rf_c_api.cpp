@@ -730,7 +730,7 @@ int rf_comm_gathered_planes(const rf_comm* c, uint32_t* flags_out, uint32_t* wid
         uint32_t mask = 0, w = 0, h = 0, n = 0;
         c->impl->gatheredPlanes(mask, w, h, n);
         if (flags_out) *flags_out = ((mask & rf::kPlaneMaskAovs) == rf::kPlaneMaskAovs ? RF_GATHER_AOVS : 0u) | ((mask & rf::kPlaneMaskMoments) ? RF_GATHER_MOMENTS : 0u) |
-                                        ((mask & rf::kGatherMaskTileCounts) ? RF_GATHER_TILE_COUNTS : 0u);
+                                        ((mask & rf::kGatherMaskTileCounts) ? RF_GATHER_TILE_COUNTS : 0u) | ((mask & rf::kPlaneMaskRobustMean) ? RF_GATHER_ROBUST_MEAN : 0u);
         if (width) *width = w;
         if (height) *height = h;
         if (samples) *samples = n;
@@ -801,6 +801,27 @@ int rf_comm_read_mean(rf_comm* c, rf_renderer* r, float* rgba)
         require(c && r && rgba, "null argument");
         require(r->impl->deviceOrdinal() == c->impl->deviceOrdinal(), "the renderer and the communicator are on different devices");
         c->impl->readMean(rgba, r->impl->streamHandle());
+        return RF_OK;
+    });
+}
+
+int rf_comm_read_robust_mean(rf_comm* c, rf_renderer* r, float* rgba, uint32_t* bgra8, uint8_t* trim, uint32_t* K, uint32_t* sample_count)
+{
+    return guarded([&] {
+        require(c && r, "null argument");
+        require(r->impl->deviceOrdinal() == c->impl->deviceOrdinal(), "the renderer and the communicator are on different devices");
+        c->impl->readRobustMean(rgba, bgra8, trim, K, sample_count, r->impl->exposure(), r->impl->streamHandle());
+        return RF_OK;
+    });
+}
+
+int rf_comm_denoise_robust(rf_comm* c, rf_renderer* r, const rf_denoise_parameters* params)
+{
+    return guarded([&] {
+        const rf::DenoiseParameters p = toDenoiseParams(params);
+        require(c && r, "null argument");
+        require(r->impl->deviceOrdinal() == c->impl->deviceOrdinal(), "the renderer and the communicator are on different devices");
+        c->impl->denoiseRobust(p, r->impl->exposure(), r->impl->streamHandle());
         return RF_OK;
     });
 }
@@ -941,7 +962,8 @@ int rf_gather_plan_planes(uint32_t width, uint32_t height, uint32_t world_size, 
         require(rank < world_size && root < world_size, "rank / root out of range");
         require(num_ops, "null argument");
         static_assert(sizeof(rf_gather_plane_op) == sizeof(rf::GatherPlaneOp));
-        const uint32_t mask = rf::kPlaneMaskImage | ((flags & RF_GATHER_AOVS) ? rf::kPlaneMaskAovs : 0u) | ((flags & RF_GATHER_MOMENTS) ? rf::kPlaneMaskMoments : 0u);
+        const uint32_t mask = rf::kPlaneMaskImage | ((flags & RF_GATHER_AOVS) ? rf::kPlaneMaskAovs : 0u) | ((flags & RF_GATHER_MOMENTS) ? rf::kPlaneMaskMoments : 0u) |
+                              ((flags & RF_GATHER_ROBUST_MEAN) ? rf::kPlaneMaskRobustMean : 0u);
         const rf::GatherLayout               g = rf::gatherLayout(width, height, world_size);
         const std::vector<rf::GatherPlaneOp> plan = rf::gatherPlanPlanes(g, world_size, rank, root, (flags & RF_GATHER_LOOPBACK) != 0, mask);
         if (ops)

@@ -6,6 +6,7 @@
 #include "rf_hip_host.hpp"
 #include "rf_noise.hpp"
 #include "rf_renderer.hpp" // tilesForRank, TileGrid
+#include "rf_robust.hpp"
 #include "rf_transport.hpp"
 
 #include <hip/hip_runtime.h>
@@ -35,9 +36,10 @@ namespace
 constexpr uint32_t kTilePixels = kTileSize * kTileSize; // 1024
 
 // One workgroup per tile of the frame: tile-major (8x8-pixel blocks, one wave each) -> row-major.  Reads are 1-KiB contiguous per wave, writes 128-byte row segments.
-// `own`: the root's shard of the plane, read in place; every other tile comes from the staging area, at its slot.
-__device__ __forceinline__ void untileTile(const float4* __restrict__ staging, const float4* __restrict__ own, float4* __restrict__ image, uint32_t ownRank, uint32_t ownFirstTile,
-                                           const uint32_t* __restrict__ tileSlot, const uint32_t* __restrict__ tileOwner, uint32_t width, uint32_t height, uint32_t tilesX)
+// `own`: the root's shard of the plane, read in place; every other tile comes from the staging area, at its slot.  store(row-major index, the pixel) writes it out.
+template<class Store>
+__device__ __forceinline__ void untileTileTo(const float4* __restrict__ staging, const float4* __restrict__ own, uint32_t ownRank, uint32_t ownFirstTile,
+                                             const uint32_t* __restrict__ tileSlot, const uint32_t* __restrict__ tileOwner, uint32_t width, uint32_t height, uint32_t tilesX, Store store)
 {
     const uint32_t tile = blockIdx.x;
     const uint32_t slot = tileSlot[tile];
@@ -49,8 +51,13 @@ __device__ __forceinline__ void untileTile(const float4* __restrict__ staging, c
         const uint32_t w = k * 256 + threadIdx.x;
         const uint32_t block = w >> 6, lane = w & 63u;
         const uint32_t x = x0 + (block & 3u) * 8u + (lane & 7u), y = y0 + (block >> 2) * 8u + (lane >> 3);
-        if (x < width && y < height) image[static_cast<size_t>(y) * width + x] = src[w];
+        if (x < width && y < height) store(static_cast<size_t>(y) * width + x, src[w]);
     }
+}
+__device__ __forceinline__ void untileTile(const float4* __restrict__ staging, const float4* __restrict__ own, float4* __restrict__ image, uint32_t ownRank, uint32_t ownFirstTile,
+                                           const uint32_t* __restrict__ tileSlot, const uint32_t* __restrict__ tileOwner, uint32_t width, uint32_t height, uint32_t tilesX)
+{
+    untileTileTo(staging, own, ownRank, ownFirstTile, tileSlot, tileOwner, width, height, tilesX, [=](size_t at, const float4& v) { image[at] = v; });
 }
 
 __global__ __launch_bounds__(256) void kUntile(const float4* __restrict__ staging, const float4* __restrict__ own, uint32_t ownRank, uint32_t ownFirstTile,
@@ -70,13 +77,26 @@ struct UntilePlane
 };
 struct UntilePlaneArgs
 {
-    UntilePlane plane[kGatherPlanes]; // [blockIdx.y]: the carried planes in plane order
+    UntilePlane plane[kSumPlanes]; // [blockIdx.y]: the carried sum planes in plane order
 };
 __global__ __launch_bounds__(256) void kUntilePlanes(UntilePlaneArgs args, uint32_t ownRank, uint32_t ownFirstTile, const uint32_t* __restrict__ tileSlot,
                                                      const uint32_t* __restrict__ tileOwner, uint32_t width, uint32_t height, uint32_t tilesX)
 {
     const UntilePlane pl = args.plane[blockIdx.y];
     untileTile(pl.staging, pl.own, pl.image, ownRank, ownFirstTile, tileSlot, tileOwner, width, height, tilesX);
+}
+
+// The un-tile of plane 4, the ranks' {M.rgb, float(c)}: the same walk, and every pixel is split on its way out -- mean = {M.rgb, 1} and trim = uint8(c), both
+// row-major.  A launch of its own behind the sum planes' (their kernels, arguments and grids stay what they are without the plane).  Reads 1 KiB contiguous per wave;
+// writes 128-byte row segments of the mean and 8-byte ones of the trim image.
+__global__ __launch_bounds__(256) void kUntileRobust(const float4* __restrict__ staging, const float4* __restrict__ own, uint32_t ownRank, uint32_t ownFirstTile,
+                                                     const uint32_t* __restrict__ tileSlot, const uint32_t* __restrict__ tileOwner, uint32_t width, uint32_t height,
+                                                     uint32_t tilesX, float4* __restrict__ mean, uint8_t* __restrict__ trim)
+{
+    untileTileTo(staging, own, ownRank, ownFirstTile, tileSlot, tileOwner, width, height, tilesX, [=](size_t at, const float4& v) {
+        mean[at] = make_float4(v.x, v.y, v.z, 1.0f);
+        trim[at] = static_cast<uint8_t>(v.w);
+    });
 }
 
 // The gathered per-tile sample counts, one lane per tile of the frame: frameCounts[tile] = the count its owner sent (staged rank after rank, in slot order: tileSlot) or,
@@ -361,11 +381,14 @@ struct TileComm::Impl
     DeviceBuffer<uint32_t> countStaging, frameCounts;
     std::vector<uint32_t>  frameCountsHost;
     DeviceBuffer<float4>   meanImage; // readMean's, allocated by the first call
+    // plane 4's un-tile leaves images[kPlaneRobustMean] = {M.rgb, 1} and this, one trim byte per pixel; readRobustMean's texels, allocated by the first call that asks for them
+    DeviceBuffer<uint8_t>  trimImage;
+    DeviceBuffer<uint32_t> robustBgra;
     uint32_t         imageW = 0, imageH = 0;
     // What the last gather left here (replaced as a whole by the next one): whether one was made, its root, and on the root the carried planes (0: none valid) and
     // the sample count the caller gave.  A plain gather drops the extra planes' validity, not their buffers.
     bool             gatherMade = false;
-    uint32_t         lastRoot = 0, gatheredMask = 0, gatheredSamples = 0;
+    uint32_t         lastRoot = 0, gatheredMask = 0, gatheredSamples = 0, gatheredRobustK = 0;
     // the root-side denoiser and estimate over the gathered planes: their work buffers, allocated by the first call; the snapshot is dropped by the next gather
     DenoiseWork      denoiseWork;
     bool             denoisedValid = false;
@@ -410,6 +433,7 @@ struct TileComm::Impl
         uint32_t           planeMask, width, height, root;
         bool               loopback, withCounts, isRoot;
         hipStream_t        stream;
+        uint32_t           robustK; // the K of plane 4's combine
         uint32_t           carried[kGatherPlanes] = {}, carriedIndex[kGatherPlanes] = {}, numPlanes = 0; // the carried planes in plane order; carriedIndex[p]: plane p's staging area
         size_t             planeStagingPixels = 0;                                                       // one plane's staging area
         uint32_t           ownRank() const { return loopback ? 0xFFFFFFFFu : root; }                      // (the root's un-tile: no tile is read in place under loop-back)
@@ -424,7 +448,7 @@ struct TileComm::Impl
         if (g.width == 0 || g.height == 0) throw std::invalid_argument("empty frame");
         g.withCounts = (g.planeMask & kGatherMaskTileCounts) != 0u;
         if ((g.planeMask & kPlaneMaskImage) == 0u || ((g.planeMask & ~kGatherMaskTileCounts) >> kGatherPlanes) != 0u)
-            throw std::invalid_argument("gather plane mask: plane 0 always travels, planes 0 .. 3 exist");
+            throw std::invalid_argument("gather plane mask: plane 0 always travels, planes 0 .. 4 exist");
         for (uint32_t p = 0; p < kGatherPlanes; ++p)
             if (g.planeMask >> p & 1u) g.carriedIndex[p] = g.numPlanes, g.carried[g.numPlanes++] = p;
         g.isRoot = rank == g.root;
@@ -454,10 +478,13 @@ struct TileComm::Impl
         for (uint32_t k = 0; k < g.numPlanes; ++k) grows = grows || imageWant > images[g.carried[k]].count;
         const size_t frameTiles = static_cast<size_t>(layout.tilesX) * layout.tilesY;
         if (g.withCounts) grows = grows || layout.rankFirstTile[world] > countStaging.count || frameTiles > frameCounts.count;
+        const bool robust = (g.planeMask & kPlaneMaskRobustMean) != 0u;
+        if (robust) grows = grows || imageWant > trimImage.count;
         if (grows) RF_HIP(hipStreamSynchronize(g.stream)); // a consumer of the old buffers may still run
         if (g.withCounts) countStaging.ensure(layout.rankFirstTile[world]), frameCounts.ensure(frameTiles);
         staging.ensure(stagingWant);
         for (uint32_t k = 0; k < g.numPlanes; ++k) images[g.carried[k]].ensure(imageWant);
+        if (robust) trimImage.ensure(imageWant);
         imageW = g.width;
         imageH = g.height;
     }
@@ -500,17 +527,24 @@ struct TileComm::Impl
     void untile(const Gather& g)
     {
         const uint32_t numTiles = layout.tilesX * layout.tilesY;
-        if (g.numPlanes == 1)
+        // (plane 4 is the last carried plane and has a launch of its own: the sum planes go as they go without it)
+        const bool     robust = (g.planeMask & kPlaneMaskRobustMean) != 0u;
+        const uint32_t sumPlanes = g.numPlanes - (robust ? 1u : 0u);
+        if (sumPlanes == 1)
             hipLaunchKernelGGL(kUntile, dim3(numTiles), dim3(256), 0, g.stream, staging.ptr, static_cast<const float4*>(g.compact[kPlaneImage]), g.ownRank(), layout.rankFirstTile[rank],
                                dTileSlot.ptr, dTileOwner.ptr, g.width, g.height, layout.tilesX, images[kPlaneImage].ptr);
         else
         {
             UntilePlaneArgs args{};
-            for (uint32_t k = 0; k < g.numPlanes; ++k)
+            for (uint32_t k = 0; k < sumPlanes; ++k)
                 args.plane[k] = UntilePlane{staging.ptr + k * g.planeStagingPixels, static_cast<const float4*>(g.compact[g.carried[k]]), images[g.carried[k]].ptr};
-            hipLaunchKernelGGL(kUntilePlanes, dim3(numTiles, g.numPlanes), dim3(256), 0, g.stream, args, g.ownRank(), layout.rankFirstTile[rank], dTileSlot.ptr, dTileOwner.ptr, g.width,
+            hipLaunchKernelGGL(kUntilePlanes, dim3(numTiles, sumPlanes), dim3(256), 0, g.stream, args, g.ownRank(), layout.rankFirstTile[rank], dTileSlot.ptr, dTileOwner.ptr, g.width,
                                g.height, layout.tilesX);
         }
+        if (robust)
+            hipLaunchKernelGGL(kUntileRobust, dim3(numTiles), dim3(256), 0, g.stream, staging.ptr + g.carriedIndex[kPlaneRobustMean] * g.planeStagingPixels,
+                               static_cast<const float4*>(g.compact[kPlaneRobustMean]), g.ownRank(), layout.rankFirstTile[rank], dTileSlot.ptr, dTileOwner.ptr, g.width, g.height,
+                               layout.tilesX, images[kPlaneRobustMean].ptr, trimImage.ptr);
         if (g.withCounts)
             hipLaunchKernelGGL(kUntileCounts, dim3((numTiles + 255u) / 256u), dim3(256), 0, g.stream, countStaging.ptr, g.tileCounts, g.ownRank(), layout.rankFirstTile[rank], dTileSlot.ptr,
                                dTileOwner.ptr, numTiles, frameCounts.ptr);
@@ -530,6 +564,7 @@ struct TileComm::Impl
         }
         gatheredMask = g.planeMask;
         gatheredSamples = samples;
+        gatheredRobustK = g.robustK;
     }
 };
 
@@ -578,15 +613,15 @@ void TileComm::rcclInfo(uint32_t& count, uint32_t& userRank, int& device) const 
 
 const void* TileComm::gatherFrame(const void* compactDevice, uint32_t width, uint32_t height, uint32_t root, void* streamHandle, bool loopback)
 {
-    const void* const planes[kGatherPlanes] = {compactDevice, nullptr, nullptr, nullptr};
+    const void* const planes[kGatherPlanes] = {compactDevice, nullptr, nullptr, nullptr, nullptr};
     return gatherPlanes(planes, kPlaneMaskImage, 0u, width, height, root, streamHandle, loopback);
 }
 
 const void* TileComm::gatherPlanes(const void* const compactDevice[kGatherPlanes], uint32_t planeMask, uint32_t samples, uint32_t width, uint32_t height, uint32_t root,
-                                   void* streamHandle, bool loopback, const uint32_t* tileCountsDevice)
+                                   void* streamHandle, bool loopback, const uint32_t* tileCountsDevice, uint32_t robustK)
 {
     Impl&        m = *mImpl;
-    Impl::Gather g{compactDevice, tileCountsDevice, planeMask, width, height, root, loopback, false, false, static_cast<hipStream_t>(streamHandle)};
+    Impl::Gather g{compactDevice, tileCountsDevice, planeMask, width, height, root, loopback, false, false, static_cast<hipStream_t>(streamHandle), robustK};
     m.checkGather(g);
     m.dropLastGather(root);
     if (g.isRoot) m.sizeRootBuffers(g);
@@ -623,7 +658,7 @@ void TileComm::readFrame(float* dstHost, void* streamHandle)
 
 namespace
 {
-const char* const kPlaneNames[kGatherPlanes] = {"the image (plane 0)", "the first-hit AOVs (plane 1, AC: gather with RF_GATHER_AOVS)", "the first-hit AOVs (plane 2, ND: gather with RF_GATHER_AOVS)",
+const char* const kPlaneNames[kSumPlanes] = {"the image (plane 0)", "the first-hit AOVs (plane 1, AC: gather with RF_GATHER_AOVS)", "the first-hit AOVs (plane 2, ND: gather with RF_GATHER_AOVS)",
                                                 "the radiance second moments (plane 3, Q: gather with RF_GATHER_MOMENTS)"};
 }
 
@@ -637,7 +672,7 @@ void TileComm::gatheredPlanes(uint32_t& planeMask, uint32_t& width, uint32_t& he
 const void* TileComm::planeDevice(uint32_t plane) const
 {
     const Impl& m = *mImpl;
-    if (plane >= kGatherPlanes) throw std::invalid_argument("plane out of range: 0 = S, 1 = AC, 2 = ND, 3 = Q");
+    if (plane >= kSumPlanes) throw std::invalid_argument("plane out of range: 0 = S, 1 = AC, 2 = ND, 3 = Q");
     m.requireGathered("rf_comm_plane_device", 1u << plane, kPlaneNames[plane]);
     return m.images[plane].ptr;
 }
@@ -645,7 +680,7 @@ const void* TileComm::planeDevice(uint32_t plane) const
 void TileComm::readPlane(uint32_t plane, float* dstHost, void* streamHandle)
 {
     Impl& m = *mImpl;
-    if (plane >= kGatherPlanes) throw std::invalid_argument("plane out of range: 0 = S, 1 = AC, 2 = ND, 3 = Q");
+    if (plane >= kSumPlanes) throw std::invalid_argument("plane out of range: 0 = S, 1 = AC, 2 = ND, 3 = Q");
     m.requireGathered("rf_comm_read_plane", 1u << plane, kPlaneNames[plane]);
     hipStream_t stream = static_cast<hipStream_t>(streamHandle);
     RF_HIP(hipSetDevice(m.device));
@@ -728,6 +763,48 @@ void TileComm::readMean(float* rgba, void* streamHandle)
     enqueueTileMeanRows(stream, m.images[kPlaneImage].ptr, m.frameCounts.ptr, m.imageW, m.imageH, m.meanImage.ptr);
     RF_HIP(hipMemcpyAsync(rgba, m.meanImage.ptr, n * sizeof(float4), hipMemcpyDeviceToHost, stream));
     RF_HIP(hipStreamSynchronize(stream));
+}
+
+void TileComm::readRobustMean(float* rgba, uint32_t* bgra8, uint8_t* trim, uint32_t* K, uint32_t* sampleCount, float exposure, void* streamHandle)
+{
+    Impl& m = *mImpl;
+    m.requireGathered("rf_comm_read_robust_mean", kPlaneMaskImage | kPlaneMaskRobustMean, "the robust mean (plane 4: gather with RF_GATHER_ROBUST_MEAN)");
+    const size_t n = static_cast<size_t>(m.imageW) * m.imageH;
+    if (n >= (1ull << 31)) throw std::invalid_argument("rf_comm_read_robust_mean: image too large");
+    hipStream_t stream = static_cast<hipStream_t>(streamHandle);
+    RF_HIP(hipSetDevice(m.device));
+    if (rgba) RF_HIP(hipMemcpyAsync(rgba, m.images[kPlaneRobustMean].ptr, n * sizeof(float4), hipMemcpyDeviceToHost, stream));
+    if (trim) RF_HIP(hipMemcpyAsync(trim, m.trimImage.ptr, n * sizeof(uint8_t), hipMemcpyDeviceToHost, stream));
+    if (bgra8)
+    {
+        if (m.robustBgra.count < n)
+        {
+            RF_HIP(hipStreamSynchronize(stream)); // (an earlier read may still use the smaller one)
+            m.robustBgra.alloc(n);
+        }
+        enqueueRobustTexels(stream, m.images[kPlaneRobustMean].ptr, static_cast<uint32_t>(n), exposure, m.robustBgra.ptr);
+        RF_HIP(hipMemcpyAsync(bgra8, m.robustBgra.ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    }
+    RF_HIP(hipStreamSynchronize(stream));
+    if (K) *K = m.gatheredRobustK;
+    if (sampleCount) *sampleCount = m.gatheredSamples;
+}
+
+void TileComm::denoiseRobust(const DenoiseParameters& params, float exposure, void* streamHandle)
+{
+    Impl& m = *mImpl;
+    m.requireGathered("rf_comm_denoise_robust", kPlaneMaskImage | kPlaneMaskAovs, "the first-hit AOVs (gather with RF_GATHER_AOVS | RF_GATHER_ROBUST_MEAN)");
+    m.requireGathered("rf_comm_denoise_robust", kPlaneMaskRobustMean, "the robust mean (plane 4: gather with RF_GATHER_AOVS | RF_GATHER_ROBUST_MEAN)");
+    if (m.gatheredSamples == 0u) throw std::invalid_argument("rf_comm_denoise_robust: the gathered sums hold no sample");
+    if (static_cast<uint64_t>(m.imageW) * m.imageH >= (1ull << 31)) throw std::invalid_argument("rf_comm_denoise_robust: image too large");
+    const bool perTile = (m.gatheredMask & kGatherMaskTileCounts) != 0u;
+    if (perTile && *std::min_element(m.frameCountsHost.begin(), m.frameCountsHost.end()) == 0u)
+        throw std::invalid_argument("rf_comm_denoise_robust: a tile of the gathered frame holds no sample");
+    RF_HIP(hipSetDevice(m.device));
+    // denoise()'s call with prep's colour = the gathered M (rf_denoise.hpp: plane 0 is then not read)
+    enqueueDenoise(static_cast<hipStream_t>(streamHandle), m.denoiseWork, m.images[kPlaneImage].ptr, m.images[kPlaneAlbedoCoverage].ptr, m.images[kPlaneNormalDepth].ptr, m.imageW,
+                   m.imageH, 0u, m.gatheredSamples, params, exposure, perTile ? m.frameCounts.ptr : nullptr, m.images[kPlaneRobustMean].ptr);
+    m.denoisedValid = true;
 }
 
 double TileComm::allReduceMax(double value, void* streamHandle)

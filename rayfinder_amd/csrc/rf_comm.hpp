@@ -53,9 +53,13 @@ std::vector<GatherOp> gatherPlan(const GatherLayout& layout, uint32_t worldSize,
 // The sums a gather can carry, one PLANE each, in this fixed order: the image S, the first-hit AOV sums AC = {albedo.rgb, coverage} and ND = {normal.xyz, depth},
 // and the radiance second moments Q.  Every plane is a compact tile-major float4 buffer of the rank's shard, and has its own staging area (GatherLayout) and its own
 // row-major image on the root.  A plane mask has bit p set for every carried plane; plane 0 always travels.
-constexpr uint32_t kGatherPlanes = 4;
-constexpr uint32_t kPlaneImage = 0, kPlaneAlbedoCoverage = 1, kPlaneNormalDepth = 2, kPlaneMoments = 3;
-constexpr uint32_t kPlaneMaskImage = 1u << kPlaneImage, kPlaneMaskAovs = (1u << kPlaneAlbedoCoverage) | (1u << kPlaneNormalDepth), kPlaneMaskMoments = 1u << kPlaneMoments;
+// Plane 4 is no sum: the robust mean of the rank's own pixels, {M.rgb, float(c)} (Renderer::enqueueShardRobustMean: the combine is per pixel, so every rank runs it over its
+// own bucket planes BEFORE the exchange and one plane travels instead of K).  It is staged like the others; the root's un-tile splits it into a row-major {M.rgb, 1}
+// image and a row-major uint8 trim image.  The sum planes 0 .. kSumPlanes - 1 are the ones readPlane / planeDevice serve.
+constexpr uint32_t kGatherPlanes = 5, kSumPlanes = 4;
+constexpr uint32_t kPlaneImage = 0, kPlaneAlbedoCoverage = 1, kPlaneNormalDepth = 2, kPlaneMoments = 3, kPlaneRobustMean = 4;
+constexpr uint32_t kPlaneMaskImage = 1u << kPlaneImage, kPlaneMaskAovs = (1u << kPlaneAlbedoCoverage) | (1u << kPlaneNormalDepth), kPlaneMaskMoments = 1u << kPlaneMoments,
+                   kPlaneMaskRobustMean = 1u << kPlaneRobustMean;
 
 // gatherPlan() once per carried plane, still ONE group: on the root, for each plane in order, the receives of that plane in rank order; on a sender, its sends in plane
 // order -- so per (source, destination) pair the k-th send meets the k-th receive, which is what both RCCL's grouped point-to-point calls and the local transport's
@@ -110,8 +114,10 @@ public:
     // the denoised snapshot.
     // planeMask & kGatherMaskTileCounts: tileCountsDevice, this rank's per-tile sample counts in slot order (device memory, one uint32 per tile of the shard), travels too;
     // the root assembles one count per tile of the frame (kUntileCounts), waits for the exchange, and records N = the largest count instead of `samples`.
+    // planeMask & kPlaneMaskRobustMean: compactDevice[4] is the rank's {M.rgb, float(c)} buffer; it is un-tiled by a launch of its own (kUntileRobust) behind the one of
+    // the sum planes, and `robustK` -- the K of the combine -- is recorded on the root for readRobustMean().
     const void* gatherPlanes(const void* const compactDevice[kGatherPlanes], uint32_t planeMask, uint32_t samples, uint32_t width, uint32_t height, uint32_t root, void* stream,
-                             bool loopback = false, const uint32_t* tileCountsDevice = nullptr);
+                             bool loopback = false, const uint32_t* tileCountsDevice = nullptr, uint32_t robustK = 0);
     // Device time of the LAST gatherFrame() on the caller's stream, HIP events around it: from the moment the rank's queued frame kernels have drained and the
     // exchange starts to the end of its sends / receives (+ the un-tile on the root).  Waits for that exchange; -1 before the first one.
     double lastExchangeMs();
@@ -137,6 +143,12 @@ public:
     uint32_t readTileSamples(uint32_t* tileSamples) const;
     // row-major width * height * 4 floats {S.rgb / float(the tile's count), 1}, {0, 0, 0, 1} in a tile without a sample; enqueued on `stream`, then waited for
     void readMean(float* rgba, void* stream);
+    // After a gather with kPlaneMaskRobustMean: the gathered robust mean as the gather left it (row-major width * height: 4 floats {M.rgb, 1}, BGRA8 texels -- kTonemap
+    // over M with accumulatedSamples = 1 and `exposure`, enqueued on `stream` --, one trim byte; any pointer may be nullptr), the K of the combine and N.  Waits for the stream.
+    void readRobustMean(float* rgba, uint32_t* bgra8, uint8_t* trim, uint32_t* K, uint32_t* sampleCount, float exposure, void* stream);
+    // denoise() with prep's colour = the gathered M instead of S / N (Renderer::denoiseRobust's filter over row-major planes); needs kPlaneMaskAovs | kPlaneMaskRobustMean.
+    // The snapshot is denoise()'s: readDenoised.
+    void denoiseRobust(const DenoiseParameters& params, float exposure, void* stream);
     // Max over ranks of a host double / barrier (timing plumbing for callers that have no other collective layer).
     double allReduceMax(double value, void* stream);
 

@@ -29,6 +29,12 @@ const void* gatherFrame(Renderer& h, TileComm& comm, uint32_t root, uint32_t fla
     require(root < comm.worldSize(), "gather root out of range");
     requireOneRank(h, comm);
     if (!(flags & RF_GATHER_TILE_COUNTS)) h.requireUniformTileSamples("rf_renderer_gather_frame"); // (such an exchange carries no per-tile counts)
+    // ... and the robust mean is combined with ONE count whatever else travels: a whole-frame handle (world size 1) can be in the non-uniform state with its bucket
+    // planes kept per tile count (RF_BUCKETS_TILE_COUNTS, rf_renderer_render_adaptive), and the accumulated count is then only the leading tiles'
+    if ((flags & RF_GATHER_ROBUST_MEAN) && !h.tileSamplesUniform())
+        throw std::invalid_argument("rf_renderer_gather_frame: RF_GATHER_ROBUST_MEAN: the tiles hold different sample counts after rf_renderer_render_adaptive, and the gathered "
+                                    "robust mean is combined with ONE count for the frame (rf_renderer_robust_mean combines a whole-frame handle per tile count; or restart "
+                                    "the accumulation with rf_renderer_set_render_parameters)");
     // the extra planes: a sum travels only when it holds exactly the accumulated samples (a rank whose shard has no tile has nothing to send and nothing to check
     // but the switch).  Refused before anything is enqueued or cleared.
     const Renderer::ShardSums s = h.shardSums();
@@ -51,11 +57,27 @@ const void* gatherFrame(Renderer& h, TileComm& comm, uint32_t root, uint32_t fla
         if (s.ownsTiles && !s.moments.coversAccumulation) throw differs("RF_GATHER_MOMENTS", "moment", s.moments.samples, "moments");
         planeMask |= kPlaneMaskMoments;
     }
+    // the robust mean (the ordinary state: refused above otherwise): the buckets must cover the accumulation, and every bucket needs a sample (N >= K)
+    if (flags & RF_GATHER_ROBUST_MEAN)
+    {
+        require(s.buckets.on, "rf_renderer_gather_frame: RF_GATHER_ROBUST_MEAN needs the bucket sums: turn them on (rf_renderer_set_buckets) before the first sample");
+        require(!s.ownsTiles || s.accumulated != 0u, "rf_renderer_gather_frame: RF_GATHER_ROBUST_MEAN: no sample has been accumulated");
+        if (s.ownsTiles && !s.buckets.coversAccumulation) throw differs("RF_GATHER_ROBUST_MEAN", "bucket", s.buckets.samples, "buckets");
+        if (s.ownsTiles && s.accumulated < s.bucketsK)
+            throw std::invalid_argument("rf_renderer_gather_frame: RF_GATHER_ROBUST_MEAN: every one of the " + std::to_string(s.bucketsK) + " buckets needs a sample, and only " +
+                                        std::to_string(s.accumulated) + " are accumulated");
+        planeMask |= kPlaneMaskRobustMean;
+    }
     h.clearAccumulationIfStale(); // nothing rendered since the last reset: send zeros, not the previous frame
     // the shard's per-tile counts, in slot order, from device memory (the ordinary state: every tile at the accumulated count)
     const uint32_t* counts = nullptr;
     if (flags & RF_GATHER_TILE_COUNTS) planeMask |= kGatherMaskTileCounts, counts = h.shardTileSamplesDevice();
-    return comm.gatherPlanes(s.planes, planeMask, s.accumulated, h.width(), h.height(), root, h.streamHandle(), (flags & RF_GATHER_LOOPBACK) != 0, counts);
+    // every check of the handle's state is behind us: the rank's own combine goes onto the handle's stream in front of the exchange, and its output travels as plane 4.
+    // (The communicator's own checks -- an aborted transport, the plane mask, a null buffer: gatherPlanes -- follow it, as they follow the clearing above; a gather
+    // they refuse has written the handle's own plane-4 buffer and nothing else.)
+    const void* planes[kGatherPlanes] = {s.planes[0], s.planes[1], s.planes[2], s.planes[3], nullptr};
+    if (flags & RF_GATHER_ROBUST_MEAN) planes[kPlaneRobustMean] = h.enqueueShardRobustMean();
+    return comm.gatherPlanes(planes, planeMask, s.accumulated, h.width(), h.height(), root, h.streamHandle(), (flags & RF_GATHER_LOOPBACK) != 0, counts, s.bucketsK);
 }
 
 ShardedAdaptiveResult renderAdaptive(Renderer& h, TileComm& comm, const AdaptiveParameters& p)

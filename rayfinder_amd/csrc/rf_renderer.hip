@@ -210,6 +210,7 @@ struct Renderer::Impl
     float4*                 bucketPlanes() const { return bucketSums.buffers[0].ptr; }
     size_t                  bucketStride() const { return tiles.size() * 1024; }
     RobustWork              robustWork;
+    DeviceBuffer<float4>    robustShard; // enqueueShardRobustMean's {M.rgb, float(c)} of the shard's pixels, shard-compact tile-major: what the frame gather sends as plane 4
     bool                    robustValid = false;
     uint32_t                robustSamples = 0;
     // the denoiser (rf_renderer_denoise): its work buffers, allocated by the first denoise, and the snapshot they hold -- valid until the AOV sums are restarted
@@ -1751,6 +1752,7 @@ void Renderer::setBuckets(uint32_t word)
     m.restartBuckets();
     // another K is another allocation (sized before the next sample); off: nothing of the buckets stays allocated
     m.bucketSums.release();
+    m.robustShard.release();
     if (K == 0u) m.robustWork.release();
 }
 
@@ -2073,7 +2075,23 @@ Renderer::ShardSums Renderer::shardSums() const
 {
     const Impl& m = *mImpl;
     const auto  channel = [&](const auto& sums) { return ShardSums::Channel{sums.on, sums.on && m.accumulated != 0u && sums.covers(m.accumulated), sums.samples}; };
-    return ShardSums{{m.image, m.aovAlbedoCoverage(), m.aovNormalDepth(), m.moments()}, channel(m.aovSums), channel(m.momentSums), m.accumulated, !m.tiles.empty()};
+    return ShardSums{{m.image, m.aovAlbedoCoverage(), m.aovNormalDepth(), m.moments()}, channel(m.aovSums), channel(m.momentSums), m.accumulated, !m.tiles.empty(),
+                     channel(m.bucketSums), buckets()};
+}
+
+const void* Renderer::enqueueShardRobustMean()
+{
+    Impl& m = *mImpl;
+    if (m.tiles.empty()) return nullptr;
+    if (!m.bucketSums.on || !m.bucketSums.covers(m.accumulated) || m.accumulated < buckets()) throw std::logic_error("enqueueShardRobustMean: the bucket sums do not cover the accumulation");
+    RF_HIP(hipSetDevice(m.device));
+    if (m.robustShard.count < m.bucketStride())
+    {
+        RF_HIP(hipStreamSynchronize(m.stream)); // (the last gather may still read the smaller one)
+        m.robustShard.alloc(m.bucketStride());
+    }
+    enqueueRobustMeanShard(m.stream, m.bucketPlanes(), m.bucketStride(), static_cast<uint32_t>(m.tiles.size()), buckets(), m.accumulated, m.robustShard.ptr);
+    return m.robustShard.ptr;
 }
 
 void Renderer::clearAccumulationIfStale()

@@ -329,8 +329,14 @@ public:
         Channel     aovs, moments;
         uint32_t    accumulated;
         bool        ownsTiles;
+        Channel     buckets;  // the bucket sums: on, covering the accumulation, their own sample count
+        uint32_t    bucketsK; // K while they are on, else 0
     };
     ShardSums shardSums() const;
+    // The robust mean of the shard's own pixels, for the frame gather (rf_comm.hpp: plane 4): kRobustMeanShard over the shard-compact bucket planes with the accumulated
+    // count, enqueued on the handle's stream -> the shard-compact tile-major buffer {M.rgb, float(c)} (owned by the handle: allocated by the first call, freed where the
+    // bucket planes are -- setBuckets with another word --, regrown like them for a larger shard; nullptr and nothing enqueued when the shard holds no tile).  The caller has checked that the buckets cover the accumulation and that it holds >= K samples.
+    const void* enqueueShardRobustMean();
     // Zero the accumulation buffer (on the handle's stream) if nothing has been rendered into it since the last reset, so that a
     // reader on the device (the frame exchange) never sees the previous frame's sums.
     void     clearAccumulationIfStale();

@@ -4,6 +4,7 @@
 // divide, no denormal flushing): tests/robust_restatement.py reproduces it bit for bit.  No atomics: every output is one lane's fixed sequence of operations.
 //   kRobustMean<K>       one lane per pixel; K is a compile-time constant, so the K bucket means and keys live in registers and the sort is a fixed network
 //   kRobustMeanTiles<K>  the same with the sample count of the pixel's 32x32 tile (a frame of rf_renderer_render_adaptive, rf_robust_mean_tiles)
+//   kRobustMeanShard<K>  a tile shard's own pixels in place, {M.rgb, float(c)} per pixel: what the frame gather carries as plane 4 (RF_GATHER_ROBUST_MEAN)
 // The display image is the existing kTonemap over the mean with accumulatedSamples = 1.
 #include "rf_robust.hpp"
 
@@ -24,18 +25,19 @@ __device__ __forceinline__ uint32_t tileMajorIndex(uint32_t x, uint32_t y, uint3
     return tile * 1024u + block * 64u + (y & 7u) * 8u + (x & 7u);
 }
 
-// The body both kernels share: one lane's pixel i = (x, y) over its sample count >= K -- samplesAll (kRobustMean: one count for the frame) or, TILES, the count of the
-// pixel's tile, tileSamples[(y / 32) frameTilesX + (x / 32)] (kRobustMeanTiles); nothing else differs
-template<uint32_t K, bool TILES>
+// The body every kernel shares: one lane's pixel i = (x, y) over its sample count >= K -- samplesAll (kRobustMean: one count for the frame) or, TILES, the count of the
+// pixel's tile, tileSamples[(y / 32) frameTilesX + (x / 32)] (kRobustMeanTiles); nothing else differs.  SHARD (kRobustMeanShard): pixel i of a shard-compact tile-major
+// buffer of `width` pixels, read and written in place -- no coordinates, no tile table --, the count samplesAll, and the output {M.rgb, float(c)} in `mean` alone
+template<uint32_t K, bool TILES, bool SHARD = false>
 __device__ __forceinline__ void robustPixel(const float4* planes, size_t planeStride, uint32_t width, uint32_t height, uint32_t tilesX, uint32_t samplesAll,
                                             const uint32_t* tileSamples, uint32_t frameTilesX, float4* mean, uint8_t* trim)
 {
     static_assert(K % 2u == 1u && K >= 3u && K <= 15u, "K odd, 3 .. 15");
     constexpr uint32_t HALF = (K - 1u) / 2u;
     const uint32_t     i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= width * height) return;
-    const uint32_t y = i / width, x = i - y * width;
-    const uint32_t src = tilesX ? tileMajorIndex(x, y, tilesX) : i;
+    if (i >= (SHARD ? width : width * height)) return;
+    const uint32_t y = SHARD ? 0u : i / width, x = i - y * width;
+    const uint32_t src = !SHARD && tilesX ? tileMajorIndex(x, y, tilesX) : i;
     const uint32_t samples = TILES ? tileSamples[(y >> 5) * frameTilesX + (x >> 5)] : samplesAll;
     const uint32_t each = samples / K, more = samples - each * K; // buckets 0 .. more - 1 hold one sample more
     float          mr[K], mg[K], mb[K], key[K];
@@ -82,8 +84,8 @@ __device__ __forceinline__ void robustPixel(const float4* planes, size_t planeSt
         sr = kept ? sr + mr[r] : sr, sg = kept ? sg + mg[r] : sg, sb = kept ? sb + mb[r] : sb;
     }
     const float nk = static_cast<float>(K - 2u * c);
-    mean[i] = make_float4(sr / nk, sg / nk, sb / nk, 1.0f);
-    trim[i] = static_cast<uint8_t>(c);
+    mean[i] = make_float4(sr / nk, sg / nk, sb / nk, SHARD ? static_cast<float>(c) : 1.0f);
+    if (!SHARD) trim[i] = static_cast<uint8_t>(c);
 }
 
 template<uint32_t K>
@@ -132,6 +134,33 @@ RobustTilesKernel robustTilesKernel(uint32_t K)
     default: throw std::logic_error("robustTilesKernel: no such kernel is compiled");
     }
 }
+
+// A tile shard's own combine, ahead of the frame gather (RF_GATHER_ROBUST_MEAN): one lane per pixel of the shard-compact tile-major planes, the output in the same
+// place of a buffer laid out the same way -- source index = destination index = i, no coordinates, no tile table.  out[i] = {M.rgb, float(c)}: c <= 7 is exact in an
+// f32 and M.a is the constant 1, so the trim count travels in .w and the root's un-tile splits it off again.  The padding pixels of ragged tiles hold zero sums: M = 0,
+// c = 0 (0 / n = 0, den = 0 so G = 0), and the un-tile never reads them.
+template<uint32_t K>
+__global__ __launch_bounds__(256) void kRobustMeanShard(const float4* __restrict__ planes, size_t planeStride, uint32_t pixels, uint32_t samples, float4* __restrict__ out)
+{
+    // SHARD: `width` is the pixel count; height, tilesX, tileSamples, frameTilesX and trim are not used
+    robustPixel<K, false, true>(planes, planeStride, /* width = */ pixels, /* height */ 1u, /* tilesX */ 0u, samples, /* tileSamples */ nullptr, /* frameTilesX */ 0u, out, /* trim */ nullptr);
+}
+
+using RobustShardKernel = void (*)(const float4*, size_t, uint32_t, uint32_t, float4*);
+RobustShardKernel robustShardKernel(uint32_t K)
+{
+    switch (K)
+    {
+    case 3: return kRobustMeanShard<3>;
+    case 5: return kRobustMeanShard<5>;
+    case 7: return kRobustMeanShard<7>;
+    case 9: return kRobustMeanShard<9>;
+    case 11: return kRobustMeanShard<11>;
+    case 13: return kRobustMeanShard<13>;
+    case 15: return kRobustMeanShard<15>;
+    default: throw std::logic_error("robustShardKernel: no such kernel is compiled");
+    }
+}
 } // namespace
 
 void RobustWork::reserve(uint64_t n, hipStream_t stream)
@@ -162,6 +191,20 @@ void enqueueRobustMean(hipStream_t stream, RobustWork& w, const float4* planes, 
     else
         hipLaunchKernelGGL(robustKernel(K), dim3((n + 255) / 256), dim3(256), 0, stream, planes, planeStride, width, height, tilesX, samples, w.mean.ptr, w.trim.ptr);
     hipLaunchKernelGGL(tonemapKernel(), dim3((n + 255) / 256), dim3(256), 0, stream, static_cast<const float4*>(w.mean.ptr), n, 1u, exposure, w.bgra.ptr);
+    RF_HIP(hipGetLastError());
+}
+
+void enqueueRobustMeanShard(hipStream_t stream, const float4* planes, size_t planeStride, uint32_t shardTiles, uint32_t K, uint32_t samples, float4* out)
+{
+    const uint32_t n = shardTiles * 1024u;
+    if (n == 0u) return;
+    hipLaunchKernelGGL(robustShardKernel(K), dim3((n + 255) / 256), dim3(256), 0, stream, planes, planeStride, n, samples, out);
+    RF_HIP(hipGetLastError());
+}
+
+void enqueueRobustTexels(hipStream_t stream, const float4* mean, uint32_t pixels, float exposure, uint32_t* bgra)
+{
+    hipLaunchKernelGGL(tonemapKernel(), dim3((pixels + 255) / 256), dim3(256), 0, stream, mean, pixels, 1u, exposure, bgra);
     RF_HIP(hipGetLastError());
 }
 
