@@ -337,8 +337,19 @@ RF_API int rf_renderer_render_until(rf_renderer* r, float target_mean_error, uin
  * the batching, the slot order or the options (all active tiles share one count, so one bucket phase serves a batch; a batch shorter than K leaves the planes it does
  * not reach untouched).  The bucket sample count advances with the leading count L.  S, Q, the AOV sums, which tile stops when, *result and the ray counts are exactly
  * what they are with the buckets off.  A change of the bit alone clears the bucket sums, as a change of K does; rf_renderer_read_buckets reports K without the bit, and
- * in the non-uniform state the planes as they are and L.  rf_comm_render_adaptive stays refused while the buckets are on, in either form (bucket planes under a tile
- * shard keep one count).  rf_renderer_set_buckets(K > 0), with or without the bit, is refused in the non-uniform state: the buckets could not cover the accumulation.
+ * in the non-uniform state the planes as they are and L.  rf_comm_render_adaptive stays refused while the buckets are on, in either of these two forms (bucket planes
+ * under a tile shard then keep one count).  rf_renderer_set_buckets(K > 0), with or without the bits, is refused in the non-uniform state: the buckets could not cover
+ * the accumulation.
+ * rf_renderer_set_buckets(r, K | RF_BUCKETS_TILE_COUNTS | RF_BUCKETS_SHARD_TILE_COUNTS) -- the second bit is valid only on top of the first; 0x200 stays unknown and
+ * refused -- says that the per-tile-count planes are also kept UNDER A TILE SHARD and may leave the handle through the frame gather; one bit serves both calls.
+ * rf_comm_render_adaptive then runs with the buckets on -- refused, "restart the accumulation first", when the bucket sample count does not cover the accumulation --:
+ * the bucket kernels address every plane through the shard's slot list, a rank's active tiles all sit at the frame's leading count, which is that rank's bucket sample
+ * count, so one phase serves a batch, and after any sequence of calls with the same parameters on every rank the K planes of every tile (rf_renderer_read_buckets on its
+ * owner) are bit for bit the whole-frame handle's after the same rf_renderer_render_adaptive calls.  S, Q, the AOV sums, the schedule, the ray counts and the result
+ * structs are what they are with the buckets off.  And rf_renderer_gather_frame carries plane 4 in the non-uniform state (ROBUST MEAN ACROSS RANKS, below).  A change
+ * of the bit alone clears the bucket sums and frees the plane-4 buffer, as a change of RF_BUCKETS_TILE_COUNTS does.  On a handle without a tile shard
+ * rf_renderer_render_adaptive, rf_renderer_robust_mean and rf_renderer_denoise_robust behave exactly as with RF_BUCKETS_TILE_COUNTS alone, and without the bit every
+ * call and every refusal is what it is without it.
  * rf_renderer_render, rf_renderer_render_until, rf_renderer_set_tile_shard and rf_renderer_gather_frame work as before; the frame gather does not carry the bucket planes
  * themselves: with RF_GATHER_ROBUST_MEAN every rank combines its own and ONE plane travels (ROBUST MEAN ACROSS RANKS, below).
  * rf_renderer_read_buckets: K x width*height*4 floats, plane after plane, each row-major (the layout of rf_renderer_read_accumulation; may be NULL), K and the bucket
@@ -384,6 +395,7 @@ RF_API int rf_renderer_render_until(rf_renderer* r, float target_mean_error, uin
  * combine and then prep with Nf = float(the count of the pixel's tile) for a and m (c = M.rgb as it is; the passes unchanged): it needs the AOVs on with
  * RF_AOV_TILE_COUNTS and the buckets with RF_BUCKETS_TILE_COUNTS, both covering the accumulation.  rf_renderer_denoise itself is unchanged. */
 #define RF_BUCKETS_TILE_COUNTS 0x100u /* ORed into K: keep the bucket sums per tile count under rf_renderer_render_adaptive */
+#define RF_BUCKETS_SHARD_TILE_COUNTS 0x400u /* ORed into K | RF_BUCKETS_TILE_COUNTS: ... under a tile shard too (rf_comm_render_adaptive), and through the frame gather */
 RF_API int rf_renderer_set_buckets(rf_renderer* r, uint32_t K);
 RF_API int rf_renderer_read_buckets(rf_renderer* r, float* buckets, uint32_t* K, uint32_t* bucket_sample_count);
 RF_API int rf_renderer_robust_mean(rf_renderer* r);
@@ -604,11 +616,22 @@ RF_API int rf_renderer_bind_accumulation_buffer(rf_renderer* r, void* device_ptr
  * whatever is rendered afterwards.  The flag combines with every other flag, RF_GATHER_LOOPBACK included.
  * Refused with RF_ERROR_INVALID_ARGUMENT -- every check of the handle's state before anything is enqueued, the state kept, as for RF_GATHER_AOVS, the non-uniform
  * state's refusal first (the communicator's own checks -- an aborted transport -- follow the combine, which writes the handle's plane-4 buffer and nothing else) --
- * in the NON-UNIFORM state whatever the other flags are (RF_GATHER_TILE_COUNTS does not lift it: plane 4 is combined with ONE count, and a whole-frame handle at
+ * in the NON-UNIFORM state whatever the other flags are, unless the buckets carry RF_BUCKETS_SHARD_TILE_COUNTS (ONE COUNT PER TILE, below; RF_GATHER_TILE_COUNTS alone
+ * does not lift it: plane 4 is combined with ONE count, and a whole-frame handle at
  * world size 1 may hold bucket planes per tile count after rf_renderer_render_adaptive -- rf_renderer_robust_mean is the call for that handle), when the buckets are off, when nothing has been accumulated, when the bucket sample count differs from the accumulated count (the message names both) or when
- * N < K (the message names K and N).  A rank whose shard holds no tile checks only the switch and sends nothing.  Under a tile shard the buckets always keep ONE
- * count: RF_BUCKETS_TILE_COUNTS makes no difference there, rf_comm_render_adaptive stays refused while the buckets are on, and with RF_GATHER_TILE_COUNTS in the
- * ordinary state the combine is unchanged.
+ * N < K (the message names K and N).  A rank whose shard holds no tile checks only the switch and sends nothing.  Under a tile shard the buckets keep ONE
+ * count unless they carry RF_BUCKETS_SHARD_TILE_COUNTS: RF_BUCKETS_TILE_COUNTS alone makes no difference there, rf_comm_render_adaptive stays refused while such
+ * buckets are on, and with RF_GATHER_TILE_COUNTS in the ordinary state the combine is unchanged, with or without either bit.
+ * ONE COUNT PER TILE.  When the buckets carry RF_BUCKETS_SHARD_TILE_COUNTS, the handle is in the non-uniform state and the gather carries RF_GATHER_ROBUST_MEAN |
+ * RF_GATHER_TILE_COUNTS, the rank's combine is the tiles combine (above) over its shard: pixel i of the shard-compact planes with the count of its slot, i / 1024 --
+ * the device array the gather sends as counts, which also covers a rank whose own tiles share one count below the frame's leading count.  Plane 4 travels as ever; the
+ * root's un-tile, rf_comm_read_robust_mean (sample_count = the largest count) and rf_comm_denoise_robust (each tile's count) are the same kernels.  After the same
+ * rf_comm_render_adaptive / rf_renderer_render_adaptive calls M, the texels, the trim image, the counts and the robust-denoised frame on the root are bit for bit one
+ * whole-frame handle's (rf_renderer_robust_mean, rf_renderer_read_tile_samples, rf_renderer_denoise_robust); planes 0 .. 3, rf_comm_denoise and rf_comm_noise_estimate
+ * are what they are without the flag.  Refused, before anything is enqueued and the state kept: without RF_GATHER_TILE_COUNTS (the non-uniform state's own refusal,
+ * first); without the bit (the refusal above, word for word); when the buckets do not cover the accumulation; when the smallest count known to the rank is below K
+ * (the message names K and that count) -- after rf_comm_render_adaptive that is the FRAME's smallest count, which every rank holds, so all ranks are refused alike and
+ * no peer waits; otherwise the smallest of the rank's own tiles (a whole-frame handle at world size 1 after rf_renderer_render_adaptive).
  * rf_comm_gathered_planes reports the flag.  rf_comm_read_plane and rf_comm_plane_device stay 0 .. 3: plane 4 is read through
  * rf_comm_read_robust_mean(c, r, rgba, bgra8, trim, K, sample_count): row-major width*height*4 floats {M.rgb, 1}, BGRA8 texels (kTonemap over M with
  * accumulatedSamples = 1 and the exposure of the handle passed in, enqueued on that handle's stream and waited for), one trim byte per pixel, the K of the combine and
@@ -616,8 +639,8 @@ RF_API int rf_renderer_bind_accumulation_buffer(rf_renderer* r, void* device_ptr
  * rf_comm_denoise_robust(c, r, params): rf_comm_denoise with prep's colour c = the gathered M (rf_renderer_denoise_robust's filter), per tile count when the gather
  * carried counts; needs RF_GATHER_AOVS | RF_GATHER_ROBUST_MEAN; refused as rf_comm_denoise is (N = 0, a tile without a sample, bad parameters).  The result is the
  * comm's ordinary denoise snapshot, read with rf_comm_read_denoised, and is dropped by the next gather.
- * Out of scope: `rf-render --gpus N --buckets` stays refused; bucket planes per tile count across ranks stay unsupported; raw bucket planes are not gathered (every
- * rank's rf_renderer_read_buckets is still the way to them).
+ * Out of scope: `rf-render --gpus N --buckets` and `rf-render --gpus N --adaptive` stay refused; raw bucket planes are not gathered (every rank's
+ * rf_renderer_read_buckets is still the way to them).
  *
  * The root-side calls below take the communicator and the ROOT's handle, whose stream, device and exposure they use.  Each returns RF_ERROR_INVALID_ARGUMENT, with a
  * message that says which case applies, when this rank was not the root of the last gather, when no gather has been made, or when the last gather did not carry the

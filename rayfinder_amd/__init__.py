@@ -517,7 +517,8 @@ class TileComm:
         """ReferencePathTracer.render_adaptive for a frame whose tiles are dealt to the ranks: COLLECTIVE, the same parameters on every rank; renderer's tile shard is
         this communicator's (rank, world_size).  Every tile ends with the count and the sums one un-sharded handle gives it.
         -> dict(rank: render_adaptive's dict over this rank's tiles (stopped_tiles: below the frame's leading count), frame_leading_samples, frame_min_tile_samples,
-        max_rank_pixel_samples).  While the two frame counts differ, gather with tile_counts=True."""
+        max_rank_pixel_samples).  While the two frame counts differ, gather with tile_counts=True.  Refused while the bucket sums are on, unless they were set with
+        set_buckets(k, tile_counts=True, shard=True): the bucket planes of every tile are then the un-sharded handle's too."""
         p = _ffi.AdaptiveParameters(target_tile_error, check_every, min_samples, max_samples)
         res = _ffi.CommAdaptiveResult()
         check(lib.rf_comm_render_adaptive(self._h, renderer._h, C.byref(p), C.byref(res)))
@@ -789,12 +790,14 @@ class ReferencePathTracer:
         return q, n.value
 
     # bucket sums and the firefly-robust mean (include/rayfinder_amd.h states what the buckets hold and the combine's arithmetic)
-    def set_buckets(self, k, tile_counts=False):
+    def set_buckets(self, k, tile_counts=False, shard=False):
         """Keep k bucket sums (k odd, 3 .. 15; 0: off, the default): bucket b sums the radiance of the samples whose ordinal is b mod k.  Any change clears them.
         Without tile_counts they keep one count for the frame: render_adaptive is refused while they are on.  tile_counts (RF_BUCKETS_TILE_COUNTS, k > 0): the sums
         follow the per-tile sample counts of render_adaptive, which then runs with the buckets on, and robust_mean / denoise_robust work on the frame it leaves;
-        until render_adaptive is called, nothing differs."""
-        check(lib.rf_renderer_set_buckets(self._h, int(k) | (_ffi.RF_BUCKETS_TILE_COUNTS if tile_counts else 0)))
+        until render_adaptive is called, nothing differs.  shard (RF_BUCKETS_SHARD_TILE_COUNTS, only with tile_counts): the per-tile-count sums are also kept under
+        a tile shard -- TileComm.render_adaptive then runs with the buckets on -- and gather_frame(robust_mean=True, tile_counts=True) carries the robust mean of the
+        frame it leaves; without a tile shard nothing differs from tile_counts alone."""
+        check(lib.rf_renderer_set_buckets(self._h, int(k) | (_ffi.RF_BUCKETS_TILE_COUNTS if tile_counts else 0) | (_ffi.RF_BUCKETS_SHARD_TILE_COUNTS if shard else 0)))
 
     def read_buckets(self):
         """-> ((K, H, W, 4) f32 bucket sums {r, g, b, 0} in sample order, the bucket sample count); K = 0 while the buckets are off"""
@@ -977,7 +980,8 @@ class ReferencePathTracer:
         comm.read_plane / denoise / noise_estimate.  tile_counts: the per-tile sample counts travel too (needed after comm.render_adaptive stopped some tiles):
         the root's denoise / noise_estimate then take each tile's own count, and comm.read_tile_samples / read_mean read them.  robust_mean: every rank combines
         its own bucket sums (set_buckets from the first sample, at least K samples) before the exchange and the result travels as one more plane; the root reads it
-        through comm.read_robust_mean and denoises with it through comm.denoise_robust."""
+        through comm.read_robust_mean and denoises with it through comm.denoise_robust.  While the tiles hold different counts, robust_mean needs tile_counts and
+        buckets set with set_buckets(k, tile_counts=True, shard=True), every tile at k samples or more: each rank then combines every tile with its own count."""
         p = C.c_void_p()
         check(lib.rf_renderer_gather_frame(self._h, comm._h, root, _gather_flags(loopback, aovs, moments, tile_counts, robust_mean), C.byref(p)))
         return p.value

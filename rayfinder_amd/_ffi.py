@@ -39,6 +39,7 @@ RF_ERROR_OUT_OF_RANGE = 4
 RF_AOV_FIRST_HIT = 1
 RF_AOV_TILE_COUNTS = 0x100
 RF_BUCKETS_TILE_COUNTS = 0x100
+RF_BUCKETS_SHARD_TILE_COUNTS = 0x400
 
 
 class DenoiseParameters(C.Structure):

@@ -23,6 +23,7 @@ static_assert(sizeof(rf_camera) == sizeof(rf::Camera));
 static_assert(RF_AOV_FIRST_HIT == rf::Renderer::kAovFirstHit);
 static_assert(RF_AOV_TILE_COUNTS == rf::Renderer::kAovTileCounts);
 static_assert(RF_BUCKETS_TILE_COUNTS == rf::Renderer::kBucketsTileCounts);
+static_assert(RF_BUCKETS_SHARD_TILE_COUNTS == rf::Renderer::kBucketsShardTileCounts);
 
 struct rf_renderer
 {
@@ -370,10 +371,12 @@ int rf_renderer_read_moments(rf_renderer* r, float* sumsq4, uint32_t* moment_sam
 int rf_renderer_set_buckets(rf_renderer* r, uint32_t K)
 {
     return guarded([&] {
-        // (the low byte is K; RF_BUCKETS_TILE_COUNTS is the one bit known above it, and only with K > 0)
+        // (the low byte is K; above it RF_BUCKETS_TILE_COUNTS, only with K > 0, and RF_BUCKETS_SHARD_TILE_COUNTS, only together with it)
         const uint32_t k = K & 0xFFu;
-        require((K & ~(0xFFu | RF_BUCKETS_TILE_COUNTS)) == 0u && (k != 0u || K == 0u) && (k == 0u || (k % 2u == 1u && k >= 3u && k <= 15u)),
-                "set_buckets: K must be 0 (off) or odd with 3 <= K <= 15, alone or ORed with RF_BUCKETS_TILE_COUNTS (K > 0 only)");
+        require((K & ~(0xFFu | RF_BUCKETS_TILE_COUNTS | RF_BUCKETS_SHARD_TILE_COUNTS)) == 0u && (k != 0u || K == 0u) && (k == 0u || (k % 2u == 1u && k >= 3u && k <= 15u)) &&
+                    (!(K & RF_BUCKETS_SHARD_TILE_COUNTS) || (K & RF_BUCKETS_TILE_COUNTS)),
+                "set_buckets: K must be 0 (off) or odd with 3 <= K <= 15, alone or ORed with RF_BUCKETS_TILE_COUNTS (K > 0 only), and with RF_BUCKETS_SHARD_TILE_COUNTS on top "
+                "of that bit only");
         require(r, "null argument");
         r->impl->setBuckets(K);
         return RF_OK;

@@ -30,14 +30,16 @@ const void* gatherFrame(Renderer& h, TileComm& comm, uint32_t root, uint32_t fla
     requireOneRank(h, comm);
     if (!(flags & RF_GATHER_TILE_COUNTS)) h.requireUniformTileSamples("rf_renderer_gather_frame"); // (such an exchange carries no per-tile counts)
     // ... and the robust mean is combined with ONE count whatever else travels: a whole-frame handle (world size 1) can be in the non-uniform state with its bucket
-    // planes kept per tile count (RF_BUCKETS_TILE_COUNTS, rf_renderer_render_adaptive), and the accumulated count is then only the leading tiles'
-    if ((flags & RF_GATHER_ROBUST_MEAN) && !h.tileSamplesUniform())
+    // planes kept per tile count (RF_BUCKETS_TILE_COUNTS, rf_renderer_render_adaptive), and the accumulated count is then only the leading tiles' -- unless the buckets
+    // carry RF_BUCKETS_SHARD_TILE_COUNTS: the rank's combine then takes one count per slot, the counts the gather sends (the flag is there: checked above)
+    const Renderer::ShardSums s = h.shardSums();
+    const bool                robustPerSlot = (flags & RF_GATHER_ROBUST_MEAN) && !h.tileSamplesUniform();
+    if (robustPerSlot && !s.bucketsShardTileCounts)
         throw std::invalid_argument("rf_renderer_gather_frame: RF_GATHER_ROBUST_MEAN: the tiles hold different sample counts after rf_renderer_render_adaptive, and the gathered "
                                     "robust mean is combined with ONE count for the frame (rf_renderer_robust_mean combines a whole-frame handle per tile count; or restart "
                                     "the accumulation with rf_renderer_set_render_parameters)");
     // the extra planes: a sum travels only when it holds exactly the accumulated samples (a rank whose shard has no tile has nothing to send and nothing to check
     // but the switch).  Refused before anything is enqueued or cleared.
-    const Renderer::ShardSums s = h.shardSums();
     uint32_t                  planeMask = kPlaneMaskImage;
     const auto                differs = [&](const char* flag, const char* count, uint32_t samples, const char* name) {
         return std::invalid_argument(std::string("rf_renderer_gather_frame: ") + flag + ": the " + count + " sample count (" + std::to_string(samples) +
@@ -57,7 +59,9 @@ const void* gatherFrame(Renderer& h, TileComm& comm, uint32_t root, uint32_t fla
         if (s.ownsTiles && !s.moments.coversAccumulation) throw differs("RF_GATHER_MOMENTS", "moment", s.moments.samples, "moments");
         planeMask |= kPlaneMaskMoments;
     }
-    // the robust mean (the ordinary state: refused above otherwise): the buckets must cover the accumulation, and every bucket needs a sample (N >= K)
+    // the robust mean: the buckets must cover the accumulation, and every bucket needs a sample (N >= K) -- in the non-uniform state (refused above without
+    // RF_BUCKETS_SHARD_TILE_COUNTS) every bucket of every tile: the smallest count the rank knows of, after rf_comm_render_adaptive the FRAME's, which every rank holds
+    // -- one without a tile too --, so that all ranks are refused alike and no peer waits for an exchange
     if (flags & RF_GATHER_ROBUST_MEAN)
     {
         require(s.buckets.on, "rf_renderer_gather_frame: RF_GATHER_ROBUST_MEAN needs the bucket sums: turn them on (rf_renderer_set_buckets) before the first sample");
@@ -66,6 +70,10 @@ const void* gatherFrame(Renderer& h, TileComm& comm, uint32_t root, uint32_t fla
         if (s.ownsTiles && s.accumulated < s.bucketsK)
             throw std::invalid_argument("rf_renderer_gather_frame: RF_GATHER_ROBUST_MEAN: every one of the " + std::to_string(s.bucketsK) + " buckets needs a sample, and only " +
                                         std::to_string(s.accumulated) + " are accumulated");
+        if (robustPerSlot && s.minTileSamples < s.bucketsK)
+            throw std::invalid_argument("rf_renderer_gather_frame: RF_GATHER_ROBUST_MEAN: every one of the " + std::to_string(s.bucketsK) +
+                                        " buckets of every tile needs a sample, and the smallest tile count is " + std::to_string(s.minTileSamples) +
+                                        " (sample adaptively with min_samples >= K)");
         planeMask |= kPlaneMaskRobustMean;
     }
     h.clearAccumulationIfStale(); // nothing rendered since the last reset: send zeros, not the previous frame
@@ -76,7 +84,7 @@ const void* gatherFrame(Renderer& h, TileComm& comm, uint32_t root, uint32_t fla
     // (The communicator's own checks -- an aborted transport, the plane mask, a null buffer: gatherPlanes -- follow it, as they follow the clearing above; a gather
     // they refuse has written the handle's own plane-4 buffer and nothing else.)
     const void* planes[kGatherPlanes] = {s.planes[0], s.planes[1], s.planes[2], s.planes[3], nullptr};
-    if (flags & RF_GATHER_ROBUST_MEAN) planes[kPlaneRobustMean] = h.enqueueShardRobustMean();
+    if (flags & RF_GATHER_ROBUST_MEAN) planes[kPlaneRobustMean] = h.enqueueShardRobustMean(robustPerSlot ? counts : nullptr);
     return comm.gatherPlanes(planes, planeMask, s.accumulated, h.width(), h.height(), root, h.streamHandle(), (flags & RF_GATHER_LOOPBACK) != 0, counts, s.bucketsK);
 }
 

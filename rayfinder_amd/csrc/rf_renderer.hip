@@ -207,6 +207,7 @@ struct Renderer::Impl
     // holds bucketSums.samples of them); the robust mean's buffers and the snapshot they hold -- valid until the bucket sums are restarted
     SumChannel              bucketSums{false, 1};
     bool                    bucketTileCounts = false; // kBucketsTileCounts as set: render_adaptive runs with the buckets on and the planes follow the per-tile counts
+    bool                    bucketShardTileCounts = false; // kBucketsShardTileCounts as set: so under a tile shard (rf_comm_render_adaptive), and through the frame gather
     float4*                 bucketPlanes() const { return bucketSums.buffers[0].ptr; }
     size_t                  bucketStride() const { return tiles.size() * 1024; }
     RobustWork              robustWork;
@@ -791,8 +792,8 @@ struct Renderer::Impl
         // radiance second moments: a launch of their own unless the tile-list kernel adds them with the image
         b.aovPixels = (aovSums.on && b.numBounces != 0u) ? (b.runs ? kAovPixels : perThread) : 0u;
         b.momentPixels = (!b.tileList && momentSums.on) ? (b.runs ? kMomentPixels : perThread) : 0u;
-        // the bucket sums (under a tile list -- kBucketsTileCounts, checkAdaptive -- their tile-list kernels: every active tile holds bucketSums.samples samples, so one
-        // phase serves the list): the batch's first sample has ordinal bucketSums.samples
+        // the bucket sums (under a tile list -- kBucketsTileCounts, checkAdaptive -- their tile-list kernels, under a shard's -- kBucketsShardTileCounts -- their
+        // slot-list kernels: every active tile holds bucketSums.samples samples, so one phase serves the list): the batch's first sample has ordinal bucketSums.samples
         b.bucketPixels = bucketSums.on ? (b.runs ? kBucketPixels : perThread) : 0u;
         b.buckets = bucketSums.on ? bucketSums.planes : 0u;
         b.bucketPhase = bucketSums.on ? bucketSums.samples % bucketSums.planes : 0u;
@@ -1134,7 +1135,7 @@ struct Renderer::Impl
             hipLaunchKernelGGL(l.kernel, sumGrid(l.pixels), dim3(l.runs ? 64u : static_cast<uint32_t>(kBlock)), 0, stream, fp, tileIds.ptr, l.src, l.dst0, l.dst1);
         }
         if (b.bucketPixels != 0u)
-            hipLaunchKernelGGL(bucketKernel(b.runs, b.tileList), sumGrid(b.bucketPixels), dim3(b.runs ? 64u : static_cast<uint32_t>(kBlock)), 0, stream, fp, tileIds.ptr, ps.rad, bucketPlanes(),
+            hipLaunchKernelGGL(bucketKernel(b.runs, b.tileList ? listAddressing : SumAddressing::Compact), sumGrid(b.bucketPixels), dim3(b.runs ? 64u : static_cast<uint32_t>(kBlock)), 0, stream, fp, tileIds.ptr, ps.rad, bucketPlanes(),
                                bucketStride(), b.buckets, b.bucketPhase);
     }
 
@@ -1739,16 +1740,19 @@ void Renderer::setBuckets(uint32_t word)
     Impl& m = *mImpl;
     // the low byte is K, HOW starts at bit 8 (as in the AOV flags word)
     const uint32_t K = word & 0xFFu;
-    const bool     tileCounts = (word & kBucketsTileCounts) != 0u;
-    if ((word & ~(0xFFu | kBucketsTileCounts)) != 0u || (K == 0u && tileCounts) || (K != 0u && (K % 2u == 0u || K < 3u || K > kMaxBuckets)))
-        throw std::invalid_argument("set_buckets: K must be 0 (off) or odd with 3 <= K <= 15, alone or ORed with RF_BUCKETS_TILE_COUNTS (K > 0 only)");
+    const bool     tileCounts = (word & kBucketsTileCounts) != 0u, shardTileCounts = (word & kBucketsShardTileCounts) != 0u;
+    if ((word & ~(0xFFu | kBucketsTileCounts | kBucketsShardTileCounts)) != 0u || (K == 0u && tileCounts) || (K != 0u && (K % 2u == 0u || K < 3u || K > kMaxBuckets)) ||
+        (shardTileCounts && !tileCounts))
+        throw std::invalid_argument("set_buckets: K must be 0 (off) or odd with 3 <= K <= 15, alone or ORed with RF_BUCKETS_TILE_COUNTS (K > 0 only), and with "
+                                    "RF_BUCKETS_SHARD_TILE_COUNTS on top of that bit only");
     if (K != 0u) m.requireUniform("rf_renderer_set_buckets", ": the bucket sums keep ONE sample count for the frame");
-    if (K == (m.bucketSums.on ? m.bucketSums.planes : 0u) && tileCounts == m.bucketTileCounts) return;
+    if (K == (m.bucketSums.on ? m.bucketSums.planes : 0u) && tileCounts == m.bucketTileCounts && shardTileCounts == m.bucketShardTileCounts) return;
     RF_HIP(hipSetDevice(m.device));
     RF_HIP(hipStreamSynchronize(m.stream)); // (a batch in flight may still write the sums)
     m.bucketSums.on = K != 0u;
     m.bucketSums.planes = K != 0u ? K : 1u;
-    m.bucketTileCounts = tileCounts; // (a change of the bit alone clears the sums too)
+    m.bucketTileCounts = tileCounts; // (a change of either bit alone clears the sums too)
+    m.bucketShardTileCounts = shardTileCounts;
     m.restartBuckets();
     // another K is another allocation (sized before the next sample); off: nothing of the buckets stays allocated
     m.bucketSums.release();
@@ -1871,7 +1875,7 @@ NoiseEstimate Renderer::noiseEstimate(float* errorMap, float* tileSum, float* ti
 void Renderer::checkAdaptive(const AdaptiveParameters& p, bool sharded) const
 {
     const Impl& m = *mImpl;
-    if (m.bucketSums.on && m.bucketTileCounts && sharded)
+    if (m.bucketSums.on && m.bucketTileCounts && sharded && !m.bucketShardTileCounts)
         throw std::invalid_argument("render_adaptive: the bucket sums are on (rf_renderer_set_buckets), and RF_BUCKETS_TILE_COUNTS covers rf_renderer_render_adaptive only: "
                                     "bucket planes under a tile shard are not kept per tile count; turn the buckets off (rf_renderer_set_buckets(r, 0)) first");
     if (m.bucketSums.on && !m.bucketTileCounts)
@@ -2075,11 +2079,15 @@ Renderer::ShardSums Renderer::shardSums() const
 {
     const Impl& m = *mImpl;
     const auto  channel = [&](const auto& sums) { return ShardSums::Channel{sums.on, sums.on && m.accumulated != 0u && sums.covers(m.accumulated), sums.samples}; };
+    // (frameLeadingSamples != 0: rf_comm_render_adaptive has settled the frame's figures since the accumulation was restarted)
+    uint32_t least = m.accumulated;
+    if (m.frameLeadingSamples != 0u) least = m.frameMinTileSamples;
+    else if (m.nonUniform()) least = *std::min_element(m.tileSamples.begin(), m.tileSamples.end());
     return ShardSums{{m.image, m.aovAlbedoCoverage(), m.aovNormalDepth(), m.moments()}, channel(m.aovSums), channel(m.momentSums), m.accumulated, !m.tiles.empty(),
-                     channel(m.bucketSums), buckets()};
+                     channel(m.bucketSums), buckets(), m.bucketSums.on && m.bucketShardTileCounts, least};
 }
 
-const void* Renderer::enqueueShardRobustMean()
+const void* Renderer::enqueueShardRobustMean(const uint32_t* slotCounts)
 {
     Impl& m = *mImpl;
     if (m.tiles.empty()) return nullptr;
@@ -2090,7 +2098,7 @@ const void* Renderer::enqueueShardRobustMean()
         RF_HIP(hipStreamSynchronize(m.stream)); // (the last gather may still read the smaller one)
         m.robustShard.alloc(m.bucketStride());
     }
-    enqueueRobustMeanShard(m.stream, m.bucketPlanes(), m.bucketStride(), static_cast<uint32_t>(m.tiles.size()), buckets(), m.accumulated, m.robustShard.ptr);
+    enqueueRobustMeanShard(m.stream, m.bucketPlanes(), m.bucketStride(), static_cast<uint32_t>(m.tiles.size()), buckets(), m.accumulated, m.robustShard.ptr, slotCounts);
     return m.robustShard.ptr;
 }
 

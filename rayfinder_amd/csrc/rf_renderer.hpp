@@ -257,8 +257,11 @@ public:
     // renderAdaptive is called the same handle; renderAdaptive then runs with the buckets on, the planes of tile t hold its first tileSamples[t] samples (sample j of the
     // tile in plane j mod K), and robustMean / denoiseRobust combine every pixel with its tile's count.  Without the bit renderAdaptive / checkAdaptive refuse while the
     // buckets are on.  std::invalid_argument for a bad word, and for K > 0 in the non-uniform state.
+    // K | kBucketsTileCounts | kBucketsShardTileCounts (valid only with the first bit): the per-tile-count planes are also kept under a tile shard -- checkAdaptive(p, true)
+    // passes, renderAdaptiveFrom adds the bucket sums through the shard's slot list -- and they may leave the handle through the frame gather (enqueueShardRobustMean with
+    // one count per slot).  On a whole-frame handle nothing else changes.  A change of either bit alone clears the sums like a change of K.
     // Read: K x width*height*4 floats, plane after plane, each row-major (this rank's pixels; NULL = skip), K and the bucket sample count (the leading count).
-    static constexpr uint32_t kBucketsTileCounts = 0x100u;
+    static constexpr uint32_t kBucketsTileCounts = 0x100u, kBucketsShardTileCounts = 0x400u;
     void     setBuckets(uint32_t word);
     uint32_t buckets() const;
     bool     bucketsPerTile() const; // the non-uniform state of a whole-frame handle whose buckets carry kBucketsTileCounts
@@ -295,7 +298,8 @@ public:
     // the FRAME's leading count (the largest accumulated count over the ranks): the active tiles are those at `leading` -- none when this handle's own count is lower -- and
     // the result speaks of this handle's tiles (stoppedTiles: below its own accumulated count); shardSlots: the sums are addressed through each listed tile's slot in the
     // shard (always so through rf_comm_render_adaptive, at world size 1 as well).
-    // sharded: the call is rf_comm_render_adaptive's, which the buckets refuse in either form (kBucketsTileCounts covers renderAdaptive alone).
+    // sharded: the call is rf_comm_render_adaptive's, which the buckets refuse (kBucketsTileCounts covers renderAdaptive alone) unless they carry
+    // kBucketsShardTileCounts as well.
     void           checkAdaptive(const AdaptiveParameters& params, bool sharded = false) const;
     AdaptiveResult renderAdaptiveFrom(const AdaptiveParameters& params, uint32_t leading, bool shardSlots);
     // What follows the loop once the ranks have agreed on the frame: its largest and smallest tile count, the same on every rank -- while they differ the handle is in the
@@ -331,12 +335,18 @@ public:
         bool        ownsTiles;
         Channel     buckets;  // the bucket sums: on, covering the accumulation, their own sample count
         uint32_t    bucketsK; // K while they are on, else 0
+        bool        bucketsShardTileCounts; // the buckets carry kBucketsShardTileCounts: the planes follow the per-slot counts and may be gathered in the non-uniform state
+        // the smallest tile count known to the rank: the frame's minimum after rf_comm_render_adaptive (the same on every rank, one without a tile too), else the
+        // smallest of the rank's own tiles (no tile: the accumulated count)
+        uint32_t    minTileSamples;
     };
     ShardSums shardSums() const;
     // The robust mean of the shard's own pixels, for the frame gather (rf_comm.hpp: plane 4): kRobustMeanShard over the shard-compact bucket planes with the accumulated
     // count, enqueued on the handle's stream -> the shard-compact tile-major buffer {M.rgb, float(c)} (owned by the handle: allocated by the first call, freed where the
     // bucket planes are -- setBuckets with another word --, regrown like them for a larger shard; nullptr and nothing enqueued when the shard holds no tile).  The caller has checked that the buckets cover the accumulation and that it holds >= K samples.
-    const void* enqueueShardRobustMean();
+    // slotCounts != nullptr -- the non-uniform state; the caller has checked kBucketsShardTileCounts and that every tile holds >= K samples --: what
+    // shardTileSamplesDevice() returned, and kRobustMeanShardTiles combines every slot with its own count.
+    const void* enqueueShardRobustMean(const uint32_t* slotCounts = nullptr);
     // Zero the accumulation buffer (on the handle's stream) if nothing has been rendered into it since the last reset, so that a
     // reader on the device (the frame exchange) never sees the previous frame's sums.
     void     clearAccumulationIfStale();

@@ -5,6 +5,7 @@
 //   kRobustMean<K>       one lane per pixel; K is a compile-time constant, so the K bucket means and keys live in registers and the sort is a fixed network
 //   kRobustMeanTiles<K>  the same with the sample count of the pixel's 32x32 tile (a frame of rf_renderer_render_adaptive, rf_robust_mean_tiles)
 //   kRobustMeanShard<K>  a tile shard's own pixels in place, {M.rgb, float(c)} per pixel: what the frame gather carries as plane 4 (RF_GATHER_ROBUST_MEAN)
+//   kRobustMeanShardTiles<K>  the same with one count per slot of the shard (a frame of rf_comm_render_adaptive with RF_BUCKETS_SHARD_TILE_COUNTS)
 // The display image is the existing kTonemap over the mean with accumulatedSamples = 1.
 #include "rf_robust.hpp"
 
@@ -27,7 +28,8 @@ __device__ __forceinline__ uint32_t tileMajorIndex(uint32_t x, uint32_t y, uint3
 
 // The body every kernel shares: one lane's pixel i = (x, y) over its sample count >= K -- samplesAll (kRobustMean: one count for the frame) or, TILES, the count of the
 // pixel's tile, tileSamples[(y / 32) frameTilesX + (x / 32)] (kRobustMeanTiles); nothing else differs.  SHARD (kRobustMeanShard): pixel i of a shard-compact tile-major
-// buffer of `width` pixels, read and written in place -- no coordinates, no tile table --, the count samplesAll, and the output {M.rgb, float(c)} in `mean` alone
+// buffer of `width` pixels, read and written in place -- no coordinates, no tile table --, the count samplesAll, and the output {M.rgb, float(c)} in `mean` alone;
+// SHARD and TILES (kRobustMeanShardTiles): the count of the pixel's slot, tileSamples[i / 1024] -- one count per 256-lane workgroup, so it stays a scalar
 template<uint32_t K, bool TILES, bool SHARD = false>
 __device__ __forceinline__ void robustPixel(const float4* planes, size_t planeStride, uint32_t width, uint32_t height, uint32_t tilesX, uint32_t samplesAll,
                                             const uint32_t* tileSamples, uint32_t frameTilesX, float4* mean, uint8_t* trim)
@@ -38,7 +40,8 @@ __device__ __forceinline__ void robustPixel(const float4* planes, size_t planeSt
     if (i >= (SHARD ? width : width * height)) return;
     const uint32_t y = SHARD ? 0u : i / width, x = i - y * width;
     const uint32_t src = !SHARD && tilesX ? tileMajorIndex(x, y, tilesX) : i;
-    const uint32_t samples = TILES ? tileSamples[(y >> 5) * frameTilesX + (x >> 5)] : samplesAll;
+    // (SHARD: i >> 10 from the workgroup's first pixel -- 256 lanes never straddle a slot of 1 024 --, which the compiler can see is uniform)
+    const uint32_t samples = TILES ? tileSamples[SHARD ? (blockIdx.x * blockDim.x) >> 10 : (y >> 5) * frameTilesX + (x >> 5)] : samplesAll;
     const uint32_t each = samples / K, more = samples - each * K; // buckets 0 .. more - 1 hold one sample more
     float          mr[K], mg[K], mb[K], key[K];
 #pragma unroll
@@ -146,6 +149,15 @@ __global__ __launch_bounds__(256) void kRobustMeanShard(const float4* __restrict
     robustPixel<K, false, true>(planes, planeStride, /* width = */ pixels, /* height */ 1u, /* tilesX */ 0u, samples, /* tileSamples */ nullptr, /* frameTilesX */ 0u, out, /* trim */ nullptr);
 }
 
+// The same with one count per slot of the shard: slotCounts[i >> 10] >= K, the shard's per-tile counts in slot order (Renderer::shardTileSamplesDevice: what the
+// gather sends as counts).  A tile shard after rf_comm_render_adaptive, its own tiles at different counts or all at one count below the frame's leading count.
+template<uint32_t K>
+__global__ __launch_bounds__(256) void kRobustMeanShardTiles(const float4* __restrict__ planes, size_t planeStride, uint32_t pixels, const uint32_t* __restrict__ slotCounts,
+                                                             float4* __restrict__ out)
+{
+    robustPixel<K, true, true>(planes, planeStride, /* width = */ pixels, /* height */ 1u, /* tilesX */ 0u, /* samplesAll */ 0u, slotCounts, /* frameTilesX */ 0u, out, /* trim */ nullptr);
+}
+
 using RobustShardKernel = void (*)(const float4*, size_t, uint32_t, uint32_t, float4*);
 RobustShardKernel robustShardKernel(uint32_t K)
 {
@@ -159,6 +171,21 @@ RobustShardKernel robustShardKernel(uint32_t K)
     case 13: return kRobustMeanShard<13>;
     case 15: return kRobustMeanShard<15>;
     default: throw std::logic_error("robustShardKernel: no such kernel is compiled");
+    }
+}
+using RobustShardTilesKernel = void (*)(const float4*, size_t, uint32_t, const uint32_t*, float4*);
+RobustShardTilesKernel robustShardTilesKernel(uint32_t K)
+{
+    switch (K)
+    {
+    case 3: return kRobustMeanShardTiles<3>;
+    case 5: return kRobustMeanShardTiles<5>;
+    case 7: return kRobustMeanShardTiles<7>;
+    case 9: return kRobustMeanShardTiles<9>;
+    case 11: return kRobustMeanShardTiles<11>;
+    case 13: return kRobustMeanShardTiles<13>;
+    case 15: return kRobustMeanShardTiles<15>;
+    default: throw std::logic_error("robustShardTilesKernel: no such kernel is compiled");
     }
 }
 } // namespace
@@ -194,11 +221,13 @@ void enqueueRobustMean(hipStream_t stream, RobustWork& w, const float4* planes, 
     RF_HIP(hipGetLastError());
 }
 
-void enqueueRobustMeanShard(hipStream_t stream, const float4* planes, size_t planeStride, uint32_t shardTiles, uint32_t K, uint32_t samples, float4* out)
+void enqueueRobustMeanShard(hipStream_t stream, const float4* planes, size_t planeStride, uint32_t shardTiles, uint32_t K, uint32_t samples, float4* out,
+                            const uint32_t* slotCounts)
 {
     const uint32_t n = shardTiles * 1024u;
     if (n == 0u) return;
-    hipLaunchKernelGGL(robustShardKernel(K), dim3((n + 255) / 256), dim3(256), 0, stream, planes, planeStride, n, samples, out);
+    if (slotCounts) hipLaunchKernelGGL(robustShardTilesKernel(K), dim3((n + 255) / 256), dim3(256), 0, stream, planes, planeStride, n, slotCounts, out);
+    else hipLaunchKernelGGL(robustShardKernel(K), dim3((n + 255) / 256), dim3(256), 0, stream, planes, planeStride, n, samples, out);
     RF_HIP(hipGetLastError());
 }
 

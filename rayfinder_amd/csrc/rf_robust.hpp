@@ -32,8 +32,10 @@ void enqueueRobustMean(hipStream_t stream, RobustWork& work, const float4* plane
 
 // A tile shard's own combine ahead of the frame gather: enqueue kRobustMeanShard<K> on `stream` over the shard-compact tile-major planes (K planes of planeStride float4
 // each, shardTiles * 1024 pixels used, one count `samples` >= K) -> out[i] = {M.rgb, float(c)} in the same layout (shardTiles * 1024 float4).  Nothing is enqueued
-// for an empty shard.
-void enqueueRobustMeanShard(hipStream_t stream, const float4* planes, size_t planeStride, uint32_t shardTiles, uint32_t K, uint32_t samples, float4* out);
+// for an empty shard.  slotCounts (device, one count >= K per slot of the shard) != nullptr: every pixel is combined with its slot's count
+// (kRobustMeanShardTiles<K>) and `samples` is not used; the buffer must stay as it is until the stream has run the kernel.
+void enqueueRobustMeanShard(hipStream_t stream, const float4* planes, size_t planeStride, uint32_t shardTiles, uint32_t K, uint32_t samples, float4* out,
+                            const uint32_t* slotCounts = nullptr);
 // kTonemap over a row-major mean image M (accumulatedSamples = 1): the robust mean's display texels
 void enqueueRobustTexels(hipStream_t stream, const float4* mean, uint32_t pixels, float exposure, uint32_t* bgra);
 } // namespace rf

@@ -3,8 +3,8 @@
 //   kSumPixels<Sum, TILE_LIST>   one lane per pixel, any slot order                         (Sum = ShardList<...>: the tile list of a tile shard, see sumIndex)
 //   kSumRuns<Sum, TILE_LIST>     pixel-major slot order: a 64-lane workgroup stages its pixels' runs in LDS in 32-sample chunks, one summing lane per (pixel, channel)
 //   kAccumulateRuns<PIXELS>      pixel-major slot order, the image alone: the WHOLE runs of PIXELS pixels in dynamic LDS (the headline path, profiles/r06_raygen)
-//   kBucketSumPixels<TILE_LIST> / kBucketSumRuns<TILE_LIST>  the K bucket planes (rf_renderer_set_buckets): sample k of the batch goes to plane (phase + k) mod K; the
-//                                same two forms, every plane addressed through sumIndex
+//   kBucketSumPixels<TILE_LIST, Sum> / kBucketSumRuns<TILE_LIST, Sum>  the K bucket planes (rf_renderer_set_buckets): sample k of the batch goes to plane
+//                                (phase + k) mod K; the same two forms, every plane addressed through sumIndex (Sum = ShardList<RadianceSum>: a tile shard's slot list)
 // What is summed is a policy struct (below); where a pixel's sums live is sumIndex.  The contract all three keep: each channel of each sum is one dependent chain of
 // f32 additions in sample-index order (Q's term: one f32 multiply of the loaded value with itself), no atomics, no contraction (-ffp-contract=off).
 // To add a sum: one policy struct, one enumerator of Sum, its instantiations in sumKernel's table, one entry in Impl::enqueueSums' list.
@@ -234,12 +234,13 @@ __global__ __launch_bounds__(64) void kAccumulateRuns(FrameParams fp, const uint
 // the first sample of [k0, ...) that belongs to bucket b, as an offset from k0: the smallest f >= 0 with (phase + k0 + f) mod K == b
 __device__ __forceinline__ uint32_t firstOfBucket(uint32_t b, uint32_t phaseAtK0, uint32_t K) { return b >= phaseAtK0 ? b - phaseAtK0 : b + K - phaseAtK0; }
 
-// Where a pixel's bucket sums live in every plane: the image's place (sumIndex of the radiance sum; a tile shard's slot list is not compiled for the buckets)
-template<bool TILE_LIST>
-__device__ __forceinline__ size_t bucketIndex(const uint32_t* tileIds, uint32_t numTiles, uint32_t lp) { return sumIndex<RadianceSum, TILE_LIST>(tileIds, numTiles, lp); }
+// Where a pixel's bucket sums live in every plane: the image's place (sumIndex of the radiance sum SUM: RadianceSum, or ShardList<RadianceSum> under a tile shard's
+// slot list -- rf_comm_render_adaptive with RF_BUCKETS_SHARD_TILE_COUNTS)
+template<class SUM, bool TILE_LIST>
+__device__ __forceinline__ size_t bucketIndex(const uint32_t* tileIds, uint32_t numTiles, uint32_t lp) { return sumIndex<SUM, TILE_LIST>(tileIds, numTiles, lp); }
 
 // One lane per pixel, any slot order: plane after plane, each plane's sums in registers while its samples are added.
-template<bool TILE_LIST>
+template<bool TILE_LIST, class SUM = RadianceSum>
 __global__ __launch_bounds__(kBlock) void kBucketSumPixels(FrameParams fp, const uint32_t* tileIds, const float4* src, float4* planes, size_t planeStride, uint32_t K,
                                                               uint32_t phase)
 {
@@ -247,7 +248,7 @@ __global__ __launch_bounds__(kBlock) void kBucketSumPixels(FrameParams fp, const
     if (lp >= fp.pixelsPadded) return;
     uint32_t x, y;
     if (!localPixelToXY(fp, tileIds, lp, x, y)) return;
-    const size_t at = bucketIndex<TILE_LIST>(tileIds, fp.numTiles, lp);
+    const size_t at = bucketIndex<SUM, TILE_LIST>(tileIds, fp.numTiles, lp);
     for (uint32_t b = 0; b < K; ++b)
     {
         const uint32_t first = firstOfBucket(b, phase, K);
@@ -266,7 +267,7 @@ __global__ __launch_bounds__(kBlock) void kBucketSumPixels(FrameParams fp, const
 // Pixel-major slot order, patterned on kSumRuns: a 64-lane workgroup takes kBucketPixels pixels, stages their radiance in LDS in chunks of kBucketChunk samples (two
 // coalesced load rounds of 1 KiB), then the summing slots -- slot = (pixel, channel) * K + bucket, kBucketPixels * 3 * K <= 180 of them, up to three per lane at fixed
 // register positions -- each walk their row from their bucket's first sample of the chunk at stride K.
-template<bool TILE_LIST>
+template<bool TILE_LIST, class SUM = RadianceSum>
 __global__ __launch_bounds__(64) void kBucketSumRuns(FrameParams fp, const uint32_t* tileIds, const float4* src, float4* planes, size_t planeStride, uint32_t K, uint32_t phase)
 {
     constexpr uint32_t PIXELS = kBucketPixels, CHUNK = kBucketChunk, R = CHUNK + 1u, ROUND = 64u / CHUNK, ROWS = PIXELS * 3u;
@@ -286,7 +287,7 @@ __global__ __launch_bounds__(64) void kBucketSumRuns(FrameParams fp, const uint3
         const uint32_t px = row[s] / 3u, c = row[s] - 3u * px, lp = lp0 + px;
         uint32_t       x, y;
         const bool     sums = row[s] < ROWS && lp < fp.pixelsPadded && localPixelToXY(fp, tileIds, lp, x, y); // (pixels outside the frame: staged, never summed)
-        out[s] = sums ? reinterpret_cast<float*>(planes + bucket[s] * planeStride + bucketIndex<TILE_LIST>(tileIds, fp.numTiles, lp)) + c : nullptr;
+        out[s] = sums ? reinterpret_cast<float*>(planes + bucket[s] * planeStride + bucketIndex<SUM, TILE_LIST>(tileIds, fp.numTiles, lp)) + c : nullptr;
         acc[s] = sums ? *out[s] : 0.0f;
     }
     const uint32_t kk = lane % CHUNK, pr = lane / CHUNK; // loading lane = (pixel of the round, sample of the chunk)
@@ -339,9 +340,10 @@ SumKernel sumKernel(Sum sum, bool runs, SumAddressing addressing)
     if (sum == Sum::Aov) return runs ? kSumRuns<AovSum, false> : kSumPixels<AovSum, false>;
     throw std::logic_error("sumKernel: no such kernel is compiled");
 }
-BucketKernel bucketKernel(bool runs, bool tileList)
+BucketKernel bucketKernel(bool runs, SumAddressing addressing)
 {
-    if (tileList) return runs ? kBucketSumRuns<true> : kBucketSumPixels<true>;
+    if (addressing == SumAddressing::ShardList) return runs ? kBucketSumRuns<true, ShardList<RadianceSum>> : kBucketSumPixels<true, ShardList<RadianceSum>>;
+    if (addressing == SumAddressing::TileList) return runs ? kBucketSumRuns<true> : kBucketSumPixels<true>;
     return runs ? kBucketSumRuns<false> : kBucketSumPixels<false>;
 }
 AccumulateRunsKernel accumulateRunsKernel(uint32_t pixels) { return pixels == 1u ? kAccumulateRuns<1> : pixels == 2u ? kAccumulateRuns<2> : kAccumulateRuns<kAccPixels>; }

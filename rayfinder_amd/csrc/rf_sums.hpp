@@ -58,8 +58,11 @@ AccumulateRunsKernel accumulateRunsKernel(uint32_t pixelsPerWorkgroup);
 // else one lane per pixel (kBlock per workgroup, any slot order), plane after plane.  Its source is ps.rad.
 // tileList (rf_renderer_render_adaptive with RF_BUCKETS_TILE_COUNTS): the batch's path slots belong to the fp.numTiles tiles that tileIds lists and every plane holds
 // the WHOLE frame: the sums of local pixel lp sit at tileIds[lp >> 10] * 1024 + (lp & 1023) of every plane, as the other sums' do.  All listed tiles share one bucket
-// sample count, so one phase serves the launch; a batch shorter than K leaves the planes it does not reach untouched.  (No form for a tile shard's slot list.)
+// sample count, so one phase serves the launch; a batch shorter than K leaves the planes it does not reach untouched.
+// shardList (rf_comm_render_adaptive with RF_BUCKETS_SHARD_TILE_COUNTS): the same under a tile shard, every plane holds the SHARD and the sums of local pixel lp sit at
+// tileIds[fp.numTiles + (lp >> 10)] * 1024 + (lp & 1023) of it.  A rank's active tiles all sit at the frame's leading count, which is that rank's bucket sample count:
+// one phase serves the launch there too.
 constexpr uint32_t kMaxBuckets = 15, kBucketPixels = 4, kBucketChunk = 32;
 using BucketKernel = void (*)(FrameParams fp, const uint32_t* tileIds, const float4* src, float4* planes, size_t planeStride, uint32_t K, uint32_t phase);
-BucketKernel bucketKernel(bool runs, bool tileList);
+BucketKernel bucketKernel(bool runs, SumAddressing addressing);
 } // namespace rf
