@@ -259,6 +259,52 @@ RF_API int rf_denoise_tiles(int32_t device_ordinal, uint32_t width, uint32_t hei
                             const float* albedo_coverage4, const float* normal_depth4, const rf_denoise_parameters* params, float exposure, float* out_rgba,
                             uint32_t* out_bgra8);
 
+/* Direct radiance sums: where the light came from, next to albedo, normal and depth.  No reference counterpart as a buffer; as a value it is the reference's own:
+ * what rayColor returns with numBounces = 1 (reference_path_tracer.wgsl:181-234: the primary miss's sky term, or the first hit's sun term times its visibility).
+ *
+ * rf_renderer_set_direct: 0 (the default: nothing is allocated or launched, image / stats / timings / launch plans exactly as without) or 1.  While on, the handle
+ * keeps one more per-pixel f32 buffer next to the accumulation, D = {sum d.x, sum d.y, sum d.z, 0}, where d is the sample's radiance as it stands after bounce 1,
+ * added in f32 in sample-index order, one dependent chain per channel, by the kernel that adds the image: all four floats of D are bit for bit what
+ * rf_renderer_read_accumulation returns from a handle that differs only in num_bounces = 1 and has traced the same samples, whatever the batching, slot order or
+ * number of ranks; on a handle whose own num_bounces is 1, D == S.  Indirect light is not stored: it is (S - D) per channel, one f32 subtraction, formed by whoever
+ * needs it, and it may be negative (the reference does not clamp dot(n, l)).  One more launch per batch, behind bounce 1's shadow launch (rf_stats counts it with the
+ * accumulation: ms_accumulate, launches_accumulate), and 16 bytes per pixel of device memory (rf_renderer_memory_info counts them in path_state_bytes while they are
+ * allocated); S, Q, the AOV sums, the bucket sums and the ray counts are bit for bit what they are with it off.  D keeps its own sample count -- the samples traced
+ * while it was on -- and is cleared, with the count set to 0, when the image is (a change through rf_renderer_set_render_parameters, a new tile shard, a newly bound
+ * accumulation buffer) and when the switch changes.  Turned on partway through an accumulation, D covers only the later samples.
+ * While on, rf_renderer_render_adaptive and rf_comm_render_adaptive return RF_ERROR_INVALID_ARGUMENT (the message names the direct sums) before anything is traced
+ * or exchanged, the state kept; rf_renderer_set_direct(r, 1) is refused in the non-uniform state.  rf_renderer_gather_frame does not carry D.
+ * rf_renderer_read_direct: row-major width*height*4 floats (the layout of rf_renderer_read_accumulation; may be NULL) and the direct sample count.  With a tile shard
+ * set, this rank's pixels and zeros elsewhere: the sum of the ranks' reads is the whole frame.
+ *
+ * Split-component denoiser: the a-trous filter above run on the direct and the indirect light separately, each with its own parameters, and recombined (what SVGF
+ * does with its two components).  The sun's term at the first hit is nearly noise-free and carries the hard shadow edges, the bounced light carries the variance:
+ * one colour sigma cannot serve both.  Inputs: S, D, AC, ND of one accumulation and ONE sample count N that all of them have; two parameter sets, direct and
+ * indirect (L_D, σc_D, σn_D, σz_D and L_I, σc_I, σn_I, σz_I), each within the limits above.  f32, one IEEE operation at a time in the order written.
+ *   prep, per pixel:  c, the background test, a, n, z and ae = a + εa exactly as above.
+ *                     background: eD = c, eI = 0; never a neighbour; output c exactly.
+ *                     otherwise:  cD = D.rgb / Nf;  cI = (S.rgb - D.rgb) / Nf (one subtraction, one division);  eD = cD / ae;  eI = cI / ae per channel;
+ *                                 each component X has its own ℓ_X = (e_X.r + e_X.g) + e_X.b
+ *   passes:           component X in {D, I} runs iterations i = 0 .. L_X - 1 of the pass defined above over its own e_X and ℓ_X with its own σc, σn, σz; the two
+ *                     chains never read each other.  A component past its L_X keeps its value.
+ *   finish:           out = (eD' + eI') ae per channel -- one add, one multiply; background out = c;  L_D = L_I = 0: out = c for every pixel.  {out.rgb, 1}.
+ * With D == S and L_D >= 1 the indirect chain is exactly +0 throughout and the result is bit for bit the one filter's with the direct parameters.
+ * rf_denoise_split_default_parameters: the two default sets (either pointer may be NULL, not both): direct L = 1, σc = 0.25; indirect L = 2, σc = 256; σn = σz = 0.1
+ * for both (profiles/split_denoise/README.md: the sweep behind them, at 4 samples per pixel).
+ * rf_renderer_denoise_split: enqueued on the handle's stream over its own sums; a NULL parameter set = that component's default.  The result is the snapshot that
+ * rf_renderer_read_denoised reads, with the invalidation rules above, and it is also dropped whenever D is cleared.  RF_ERROR_INVALID_ARGUMENT in the non-uniform
+ * state (that state's message, before the other checks), when the AOVs or the direct sums are off, when the AOV or the direct sample count differs from the accumulated
+ * count, when no sample has been accumulated, or when a tile shard is set.  The first call allocates two more float4 per pixel next to rf_renderer_denoise's buffers.
+ * rf_denoise_split_images: the same filter over row-major host sums on device device_ordinal; out_rgba / out_bgra8 may be NULL.  Synchronous.  A NULL input, a zero
+ * size or sample count and bad parameters are refused before any device call. */
+RF_API int rf_renderer_set_direct(rf_renderer* r, int enabled);
+RF_API int rf_renderer_read_direct(rf_renderer* r, float* direct_sum4, uint32_t* direct_sample_count);
+RF_API int rf_denoise_split_default_parameters(rf_denoise_parameters* direct, rf_denoise_parameters* indirect);
+RF_API int rf_renderer_denoise_split(rf_renderer* r, const rf_denoise_parameters* direct, const rf_denoise_parameters* indirect);
+RF_API int rf_denoise_split_images(int32_t device_ordinal, uint32_t width, uint32_t height, uint32_t samples, const float* color_sum4, const float* direct_sum4,
+                                   const float* albedo_coverage4, const float* normal_depth4, const rf_denoise_parameters* direct, const rf_denoise_parameters* indirect,
+                                   float exposure, float* out_rgba, uint32_t* out_bgra8);
+
 /* Radiance second moments and the noise estimate: how noisy the accumulation still is, per pixel, per 32x32 tile and for the frame, and a render call that stops
  * at a noise target.  No reference counterpart (the reference counts samples: renderProgressPercentage).
  *

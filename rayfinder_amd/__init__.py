@@ -593,6 +593,42 @@ def denoise_images(color_sum, albedo_coverage, normal_depth, samples, exposure=1
     return rgba[..., :3], bgra
 
 
+def denoise_split_defaults():
+    """-> (direct, indirect): the split-component denoiser's two default parameter dicts (rf_denoise_split_default_parameters)."""
+    d, i = _ffi.DenoiseParameters(), _ffi.DenoiseParameters()
+    check(lib.rf_denoise_split_default_parameters(C.byref(d), C.byref(i)))
+    return tuple(dict(iterations=p.iterations, sigma_color=p.sigma_color, sigma_normal=p.sigma_normal, sigma_depth=p.sigma_depth) for p in (d, i))
+
+
+def _split_parameters(direct, indirect):
+    out = []
+    for params, base in zip((direct, indirect), denoise_split_defaults()):
+        params = dict(params or {})
+        unknown = set(params) - set(base)
+        if unknown:
+            raise TypeError(f"unknown denoise parameters: {sorted(unknown)}")
+        p = dict(base, **params)
+        out.append(_ffi.DenoiseParameters(int(p["iterations"]), float(p["sigma_color"]), float(p["sigma_normal"]), float(p["sigma_depth"])))
+    return out
+
+
+def denoise_split_images(color_sum, direct_sum, albedo_coverage, normal_depth, samples, exposure=1.0, device_ordinal=0, direct=None, indirect=None):
+    """rf_denoise_split_images: the split-component denoiser over (H,W,4) f32 sums held on the host (accumulation S, direct sums D, {albedo, coverage}, {normal,
+    depth}) of `samples` samples; direct / indirect: dicts of iterations, sigma_color, sigma_normal, sigma_depth for that component (the rest: its defaults).
+    -> (rgb (H,W,3) f32 denoised mean, bgra (H,W) u32 display texels under `exposure`)."""
+    color_sum, direct_sum, albedo_coverage, normal_depth = (_f32(a) for a in (color_sum, direct_sum, albedo_coverage, normal_depth))
+    h, w = color_sum.shape[:2]
+    for a in (color_sum, direct_sum, albedo_coverage, normal_depth):
+        if a.shape != (h, w, 4):
+            raise ValueError("denoise_split_images: the four sums must be (H, W, 4) arrays of one size")
+    pd, pi = _split_parameters(direct, indirect)
+    rgba = np.zeros((h, w, 4), np.float32)
+    bgra = np.zeros((h, w), np.uint32)
+    check(lib.rf_denoise_split_images(device_ordinal, w, h, samples, _ptr(color_sum), _ptr(direct_sum), _ptr(albedo_coverage), _ptr(normal_depth), C.byref(pd), C.byref(pi),
+                                      exposure, _ptr(rgba), _ptr(bgra)))
+    return rgba[..., :3], bgra
+
+
 def denoise_tiles(color_sum, albedo_coverage, normal_depth, tile_samples, exposure=1.0, device_ordinal=0, **params):
     """rf_denoise_tiles: denoise_images with one sample count (> 0) per 32x32 tile, tile_samples in tile order (tile_y * ceil(W / 32) + tile_x): every pixel's sums
     are divided by its own tile's count.  -> (rgb (H,W,3) f32 denoised mean, bgra (H,W) u32 display texels under `exposure`)."""
@@ -776,6 +812,25 @@ class ReferencePathTracer:
         n = C.c_uint32(0)
         check(lib.rf_renderer_read_denoised(self._h, _ptr(rgba), _ptr(bgra), C.byref(n)))
         return rgba[..., :3], bgra, n.value
+
+    # direct radiance sums and the split-component denoiser (include/rayfinder_amd.h states what D holds and the filter's arithmetic)
+    def set_direct(self, enabled=True):
+        """Turn the per-pixel direct radiance sums on or off; any change clears them.  While on, render_adaptive is refused."""
+        check(lib.rf_renderer_set_direct(self._h, int(bool(enabled))))
+
+    def read_direct(self):
+        """-> ((H, W, 4) f32 sums of each sample's radiance after bounce 1 (sky on a primary miss, the first hit's sun term), in sample order; the direct sample
+        count).  Indirect light is read_accumulation()[0] - this, per channel."""
+        d = np.zeros((self._params.height, self._params.width, 4), np.float32)
+        n = C.c_uint32(0)
+        check(lib.rf_renderer_read_direct(self._h, _ptr(d), C.byref(n)))
+        return d, n.value
+
+    def denoise_split(self, direct=None, indirect=None):
+        """Denoise the direct and the indirect light separately and recombine them (needs the AOVs and the direct sums on from the first sample, no tile shard);
+        read_denoised reads the result.  direct / indirect: dicts of iterations, sigma_color, sigma_normal, sigma_depth (the rest: that component's defaults)."""
+        pd, pi = _split_parameters(direct, indirect)
+        check(lib.rf_renderer_denoise_split(self._h, C.byref(pd), C.byref(pi)))
 
     # radiance second moments, the noise estimate and render-to-a-noise-target (include/rayfinder_amd.h states the estimate's arithmetic)
     def set_moments(self, enabled=True):

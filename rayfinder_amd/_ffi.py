@@ -148,6 +148,12 @@ SIGNATURES = {
     "rf_denoise_images": (C.c_int, [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
                                     C.c_void_p]),
     "rf_denoise_tiles": (C.c_int, [C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
+    "rf_renderer_set_direct": (C.c_int, [C.c_void_p, C.c_int]),
+    "rf_renderer_read_direct": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
+    "rf_denoise_split_default_parameters": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rf_renderer_denoise_split": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rf_denoise_split_images": (C.c_int, [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
+                                          C.c_void_p, C.c_void_p]),
     "rf_renderer_set_moments": (C.c_int, [C.c_void_p, C.c_int]),
     "rf_renderer_read_moments": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
     "rf_renderer_set_buckets": (C.c_int, [C.c_void_p, C.c_uint32]),

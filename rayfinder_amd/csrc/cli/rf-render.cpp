@@ -5,6 +5,7 @@
 //           [--noise-map m.pfm] [--noise-target t] [--noise-check-every k] [--gpus N]
 //           [--adaptive T] [--adaptive-min n] [--adaptive-every n] [--sample-map s.pfm]
 //           [--buckets K] [--buckets-tile-counts] [--robust-mean out.pfm|out.png] [--trim-map t.pfm] [--denoise-robust d.png]
+//           [--direct d.pfm] [--indirect i.pfm] [--denoise-split out.png]
 // Offline counterpart of the interactive `pt` app (src/pt/main.cpp): same default camera pose,
 // sky and exposure; renders all samples and writes the tonemapped image (and optionally the
 // mean radiance as PFM).  --gpus N: one host thread per GPU, the image tile-sharded across them, one RCCL
@@ -30,6 +31,10 @@
 // --buckets-tile-counts (a switch, no value): keep the bucket sums per tile count (K | RF_BUCKETS_TILE_COUNTS).  With it --buckets K --adaptive T runs on --gpus 1, and
 // --robust-mean, --trim-map and --denoise-robust write the adaptive frame's images, every pixel combined with its own tile's count (--adaptive-min >= K, or a tile
 // may stop with an empty bucket and the combine is refused).
+// --direct d.pfm / --indirect i.pfm: the light split of the frame from the direct radiance sums (rf_renderer_set_direct, on from the first sample): D / N, the mean
+// of each sample's radiance after bounce 1 (sky on a primary miss, the first hit's sun term), and (S - D) / N per channel (it may be negative).  --denoise-split out.png:
+// the two components denoised separately and recombined (rf_renderer_denoise_split at its defaults; turns the AOVs on).  --gpus 1 only and not with --adaptive: the
+// frame gather does not carry D, and D keeps one sample count for the frame.
 // --noise-target t [--noise-check-every k]: stop as soon as the frame's mean error is <= t, checked every k samples (default 8), at --spp at the latest
 // (rf_renderer_render_until).  One GPU only: stopping several ranks in step is not implemented.
 #include "cli_common.hpp"
@@ -60,6 +65,9 @@ int main(int argc, char** argv)
                     "  --buckets: keep K bucket sums (K odd, 3 .. 15); --robust-mean: the firefly-robust median-of-means image (PFM, or PNG tonemapped); --trim-map: the\n"
                     "  buckets cut from each end per pixel (1-channel PFM); --denoise-robust: the robust mean through the denoiser.  --gpus 1 only, not with --adaptive\n"
                     "  unless --buckets-tile-counts (no value) is given: the bucket sums then follow the tiles' sample counts, and the three images are the adaptive frame's\n"
+                    "                 [--direct d.pfm] [--indirect i.pfm] [--denoise-split out.png]\n"
+                    "  --direct / --indirect: the mean direct light (after bounce 1) and the rest, (S - D) / N (3-channel PFMs); --denoise-split: the two denoised\n"
+                    "  separately and recombined, at the split defaults.  --gpus 1 only, not with --adaptive\n"
                     "                 [--noise-map m.pfm] [--noise-target t] [--noise-check-every k]\n"
                     "  --noise-map: the per-pixel relative standard error of the frame (1-channel PFM); --noise-target: stop once the frame's mean error is <= t,\n"
                     "  checked every k samples (default 8), at --spp at the latest (one GPU only)\n");
@@ -84,6 +92,7 @@ int main(int argc, char** argv)
     uint32_t    buckets = 0;
     bool        bucketsTileCounts = false;
     std::string robustMean, trimMap, denoiseRobust;
+    std::string directPfm, indirectPfm, denoiseSplit;
     for (int i = 2; i < argc; i += 2)
     {
         // (the one switch without a value)
@@ -128,6 +137,9 @@ int main(int argc, char** argv)
         else if (k == "--robust-mean") robustMean = val;
         else if (k == "--trim-map") trimMap = val;
         else if (k == "--denoise-robust") denoiseRobust = val;
+        else if (k == "--direct") directPfm = val;
+        else if (k == "--indirect") indirectPfm = val;
+        else if (k == "--denoise-split") denoiseSplit = val;
         else
         {
             std::fprintf(stderr, "unknown option %s\n", k.c_str());
@@ -159,6 +171,13 @@ int main(int argc, char** argv)
     if (robust && buckets == 0u)
     {
         std::fprintf(stderr, "--robust-mean / --trim-map / --denoise-robust need --buckets K (K odd, 3 .. 15)\n");
+        return 1;
+    }
+    const bool direct = !directPfm.empty() || !indirectPfm.empty() || !denoiseSplit.empty();
+    if (direct && (gpus > 1 || adaptive))
+    {
+        std::fprintf(stderr, "--direct / --indirect / --denoise-split need --gpus 1 and do not go with --adaptive (the direct sums are not carried by the frame gather and "
+                             "keep one sample count for the frame)\n");
         return 1;
     }
     rf_pt_format*     pt = loadScene(argv[1]);
@@ -194,7 +213,13 @@ int main(int argc, char** argv)
     // first-hit AOV sums of the whole frame ({albedo, coverage}, {normal, depth}), read on rank 0 when a file is made from them: from the handle, or (several ranks)
     // from the planes the gather left there
     const bool         aovFiles = !aovAlbedo.empty() || !aovNormal.empty() || !aovDepth.empty();
-    const bool         aovs = aovFiles || denoising || !denoiseRobust.empty();
+    const bool         aovs = aovFiles || denoising || !denoiseRobust.empty() || !denoiseSplit.empty();
+    // the direct sums and, next to them, the accumulation (rank 0; one GPU), and the split-denoised frame's texels
+    std::vector<float>    directSum, directAcc;
+    std::vector<uint32_t> splitBgra;
+    uint32_t              directSamples = 0;
+    if (!directPfm.empty() || !indirectPfm.empty()) directSum.resize(static_cast<size_t>(W) * H * 4), directAcc.resize(static_cast<size_t>(W) * H * 4);
+    if (!denoiseSplit.empty()) splitBgra.resize(static_cast<size_t>(W) * H);
     // the robust mean's snapshot (rank 0; one GPU): the mean, its display texels, the trim counts, and the robust mean through the denoiser
     std::vector<float>    robustRgba;
     std::vector<uint32_t> robustBgra, robustDenoisedBgra;
@@ -227,6 +252,7 @@ int main(int argc, char** argv)
         if (aovs) rfCheck(rf_renderer_set_aovs(renderer, RF_AOV_FIRST_HIT | (adaptive ? RF_AOV_TILE_COUNTS : 0u)), "AOVs");
         if (noise) rfCheck(rf_renderer_set_moments(renderer, 1), "moments");
         if (buckets != 0u) rfCheck(rf_renderer_set_buckets(renderer, buckets | (bucketsTileCounts ? RF_BUCKETS_TILE_COUNTS : 0u)), "buckets");
+        if (direct) rfCheck(rf_renderer_set_direct(renderer, 1), "direct sums");
         const auto t0 = std::chrono::steady_clock::now();
         if (adaptive) rfCheck(rf_renderer_render_adaptive(renderer, &adaptiveParams, &adaptiveResult), "adaptive render");
         else if (noiseTargetSet) rfCheck(rf_renderer_render_until(renderer, noiseTarget, noiseCheckEvery, spp, &sppReached, &estimate), "render to the noise target");
@@ -284,6 +310,16 @@ int main(int argc, char** argv)
                     rfCheck(rf_renderer_robust_mean(renderer), "robust mean");
                     rfCheck(rf_renderer_read_robust_mean(renderer, robustRgba.data(), robustBgra.data(), robustTrim.data(), &n), "read robust mean");
                 }
+                if (!directSum.empty())
+                {
+                    rfCheck(rf_renderer_read_direct(renderer, directSum.data(), &directSamples), "read direct sums");
+                    rfCheck(rf_renderer_read_accumulation(renderer, directAcc.data(), &n), "read accumulation");
+                }
+                if (!denoiseSplit.empty())
+                {
+                    rfCheck(rf_renderer_denoise_split(renderer, nullptr, nullptr), "denoise split");
+                    rfCheck(rf_renderer_read_denoised(renderer, nullptr, splitBgra.data(), &n), "read denoised");
+                }
                 if (!denoiseRobust.empty())
                 {
                     rfCheck(rf_renderer_denoise_robust(renderer, &denoiseParams), "denoise robust");
@@ -325,6 +361,7 @@ int main(int argc, char** argv)
     if (!writeBgraPng(out, bgra)) return 1;
     if (!robustMean.empty() && !(endsWith(robustMean, ".png") ? writeBgraPng(robustMean, robustBgra) : writePfm(robustMean, robustRgba.data(), W, H, 1.0f))) return 1;
     if (!denoiseRobust.empty() && !writeBgraPng(denoiseRobust, robustDenoisedBgra)) return 1;
+    if (!denoiseSplit.empty() && !writeBgraPng(denoiseSplit, splitBgra)) return 1;
     if (!pfm.empty()) writePfm(pfm, acc.data(), W, H, adaptive ? 1.0f : 1.0f / static_cast<float>(std::max(sppReached, 1u))); // (--adaptive: acc holds the per-tile mean)
     if (denoising)
     {
@@ -355,6 +392,10 @@ int main(int argc, char** argv)
         std::fclose(fp);
         return true;
     };
+    // (f32 divisions by the direct sample count, as a caller of rf_renderer_read_direct forms them; indirect: one f32 subtraction first)
+    const float directN = static_cast<float>(std::max(directSamples, 1u));
+    if (!write(directPfm, 3, [&](size_t i, uint32_t c) { return directSum[i + c] / directN; })) return 1;
+    if (!write(indirectPfm, 3, [&](size_t i, uint32_t c) { return (directAcc[i + c] - directSum[i + c]) / directN; })) return 1;
     if (!write(noiseMap, 1, [&](size_t i, uint32_t) { return errorMap[i / 4]; })) return 1;
     if (!write(trimMap, 1, [&](size_t i, uint32_t) { return static_cast<float>(robustTrim[i / 4]); })) return 1;
     if (!sampleMap.empty() && tileSamples.empty()) tileSamples.assign(static_cast<size_t>((W + 31) / 32) * ((H + 31) / 32), sppReached); // (several ranks: one count)

@@ -125,6 +125,8 @@ rf::DenoiseParameters toDenoiseParams(const rf_denoise_parameters* p)
     out.sigmaColor = p->sigma_color, out.sigmaNormal = p->sigma_normal, out.sigmaDepth = p->sigma_depth;
     return out;
 }
+// one component's parameters of the split-component denoiser (NULL: that component's default)
+rf::DenoiseParameters toSplitParams(const rf_denoise_parameters* p, const rf::DenoiseParameters& fallback) { return p ? toDenoiseParams(p) : fallback; }
 rf_noise_estimate toNoiseEstimate(const rf::NoiseEstimate& e)
 {
     return rf_noise_estimate{e.meanError, e.maxError, e.worstTile, e.samples, e.pixels, e.nonfinitePixels};
@@ -346,6 +348,63 @@ int rf_denoise_tiles(int32_t device_ordinal, uint32_t width, uint32_t height, co
         }
         require(std::isfinite(exposure), "exposure must be finite");
         rf::denoiseTiles(device_ordinal, width, height, tile_samples, leading, color_sum4, albedo_coverage4, normal_depth4, p, exposure, out_rgba, out_bgra8);
+        return RF_OK;
+    });
+}
+
+int rf_renderer_set_direct(rf_renderer* r, int enabled)
+{
+    return guarded([&] {
+        require(r, "null argument");
+        r->impl->setDirect(enabled != 0);
+        return RF_OK;
+    });
+}
+
+int rf_renderer_read_direct(rf_renderer* r, float* direct_sum4, uint32_t* direct_sample_count)
+{
+    return guarded([&] {
+        require(r, "null argument");
+        r->impl->readDirect(direct_sum4, direct_sample_count);
+        return RF_OK;
+    });
+}
+
+int rf_denoise_split_default_parameters(rf_denoise_parameters* direct, rf_denoise_parameters* indirect)
+{
+    return guarded([&] {
+        require(direct || indirect, "null argument");
+        const rf::SplitDenoiseDefaults d = rf::splitDenoiseDefaults();
+        if (direct) *direct = rf_denoise_parameters{d.direct.iterations, d.direct.sigmaColor, d.direct.sigmaNormal, d.direct.sigmaDepth};
+        if (indirect) *indirect = rf_denoise_parameters{d.indirect.iterations, d.indirect.sigmaColor, d.indirect.sigmaNormal, d.indirect.sigmaDepth};
+        return RF_OK;
+    });
+}
+
+int rf_renderer_denoise_split(rf_renderer* r, const rf_denoise_parameters* direct, const rf_denoise_parameters* indirect)
+{
+    return guarded([&] {
+        const rf::SplitDenoiseDefaults d = rf::splitDenoiseDefaults();
+        const rf::DenoiseParameters    pd = toSplitParams(direct, d.direct), pi = toSplitParams(indirect, d.indirect);
+        require(r, "null argument");
+        r->impl->denoiseSplit(pd, pi);
+        return RF_OK;
+    });
+}
+
+int rf_denoise_split_images(int32_t device_ordinal, uint32_t width, uint32_t height, uint32_t samples, const float* color_sum4, const float* direct_sum4,
+                            const float* albedo_coverage4, const float* normal_depth4, const rf_denoise_parameters* direct, const rf_denoise_parameters* indirect,
+                            float exposure, float* out_rgba, uint32_t* out_bgra8)
+{
+    return guarded([&] {
+        const rf::SplitDenoiseDefaults d = rf::splitDenoiseDefaults();
+        const rf::DenoiseParameters    pd = toSplitParams(direct, d.direct), pi = toSplitParams(indirect, d.indirect);
+        require(color_sum4 && direct_sum4 && albedo_coverage4 && normal_depth4, "null argument");
+        require(width > 0 && height > 0, "image size must be non-zero");
+        require(static_cast<uint64_t>(width) * height < (1ull << 31), "image too large");
+        require(samples > 0, "sample count must be > 0");
+        require(std::isfinite(exposure), "exposure must be finite");
+        rf::denoiseSplitImages(device_ordinal, width, height, samples, color_sum4, direct_sum4, albedo_coverage4, normal_depth4, pd, pi, exposure, out_rgba, out_bgra8);
         return RF_OK;
     });
 }

@@ -8,6 +8,10 @@
 //   kDenoisePrepMeanTiles  kDenoisePrepMean with the sample count of the pixel's tile (rf_renderer_denoise_robust in the non-uniform state)
 //   kDenoiseAtrous  one lane per pixel, 16x16-pixel workgroups of four 8x8-pixel waves (the 25 taps of a wave touch few cache lines); the last pass
 //                   remodulates and writes the mean
+//   kDenoisePrepSplit    the split-component filter's prep (rf_renderer_denoise_split): two demodulated irradiances, of D and of S - D, over one guide and one a + εa
+//   kDenoiseAtrousSplit  one pass of both components at once: one guide load per tap (and one evaluation of the normal and depth terms when the components share
+//                   σn and σz), two colour terms, two accumulator sets; a component past its own iteration count is not filtered; the last pass adds the two,
+//                   remodulates and writes the mean
 // The display image is the existing kTonemap over the mean with accumulatedSamples = 1.
 #include "rf_denoise.hpp"
 
@@ -179,17 +183,174 @@ __global__ __launch_bounds__(kDenoiseBlock) void kDenoiseAtrous(const float4* eI
     else
         out[p] = make_float4(ex, ey, ez, (ex + ey) + ez);
 }
+
+// ---- The split-component filter (include/rayfinder_amd.h, "Split-component denoiser"): the direct light D and the indirect light S - D, demodulated by the same
+// a + εa, each filtered by a chain of its own -- today's pass with its own σ and its own e, ℓ -- and added before the remodulation.
+
+// prep: c, the background test, a, n, z and a + εa exactly as prepPixel; then eD = (D.rgb / Nf) / (a + εa), eI = ((S.rgb - D.rgb) / Nf) / (a + εa), each with its own ℓ.
+// Background: eD = {c, 0}, eI = 0.  meanOut (L_D = L_I = 0): the mean c, exactly.  tilesX != 0: S, D and the AOV sums are compact tile-major; 0: row-major.
+__global__ __launch_bounds__(256) void kDenoisePrepSplit(const float4* colorSum, const float4* directSum, const float4* albedoCoverage, const float4* normalDepth, uint32_t width,
+                                                         uint32_t height, uint32_t tilesX, float nf, float4* eD, float4* eI, float4* guide, float4* albedo, float4* meanOut)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= width * height) return;
+    const uint32_t y = i / width, x = i - y * width;
+    const uint32_t src = tilesX ? tileMajorIndex(x, y, tilesX) : i;
+    const float4   S = colorSum[src];
+    const Vec3     c = vec3(S.x / nf, S.y / nf, S.z / nf);
+    if (meanOut)
+    {
+        meanOut[i] = make_float4(c.x, c.y, c.z, 1.0f);
+        return;
+    }
+    const float4 AC = albedoCoverage[src], ND = normalDepth[src];
+    const float  z = ND.w / AC.w;
+    if (AC.w == 0.0f || !(z > 0.0f)) // background: passes through, never a neighbour
+    {
+        eD[i] = make_float4(c.x, c.y, c.z, 0.0f);
+        eI[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        guide[i] = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+        albedo[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        return;
+    }
+    const float4 D = directSum[src];
+    const Vec3   a = vec3(AC.x / nf, AC.y / nf, AC.z / nf);
+    const Vec3   m = vec3(ND.x / nf, ND.y / nf, ND.z / nf);
+    const float  d = dot(m, m);
+    const Vec3   n = (d != 0.0f && fabsf(d) <= FLT_MAX) ? normalize(m) : splat(0.0f);
+    const Vec3   ae = a + splat(kEpsAlbedo);
+    const Vec3   cD = vec3(D.x / nf, D.y / nf, D.z / nf);
+    const Vec3   cI = vec3((S.x - D.x) / nf, (S.y - D.y) / nf, (S.z - D.z) / nf);
+    const Vec3   vD = vec3(cD.x / ae.x, cD.y / ae.y, cD.z / ae.z);
+    const Vec3   vI = vec3(cI.x / ae.x, cI.y / ae.y, cI.z / ae.z);
+    eD[i] = make_float4(vD.x, vD.y, vD.z, (vD.x + vD.y) + vD.z);
+    eI[i] = make_float4(vI.x, vI.y, vI.z, (vI.x + vI.y) + vI.z);
+    guide[i] = make_float4(n.x, n.y, n.z, z);
+    albedo[i] = make_float4(ae.x, ae.y, ae.z, 0.0f);
+}
+
+// one component's constants of a pass of step 2^i: sc2 = (σc σc) 2^-i, σn, szs = σz step
+struct SplitPass
+{
+    float sc2, sigmaN, szs;
+};
+
+// One pass of step `step` over both components.  DIRECT / INDIRECT: the component is active in this pass (it has not run its own L passes yet) -- it is filtered from
+// dIn / iIn exactly as kDenoiseAtrous filters, with its own constants; an inactive one is neither filtered nor written, and the last pass reads its value at the pixel
+// itself.  SHARED (both active, the same σn and szs): the normal and depth terms of a tap are evaluated once for both.
+// last: out = {(eD' + eI') (a + εa), 1} (background: {eD.rgb, 1} = {c, 1}); else the active components' {e', ℓ'} go to dOut / iOut (background: a copy).
+template<bool DIRECT, bool INDIRECT, bool SHARED>
+__global__ __launch_bounds__(kDenoiseBlock) void kDenoiseAtrousSplit(const float4* dIn, const float4* iIn, const float4* guide, const float4* albedo, float4* dOut, float4* iOut,
+                                                                    float4* out, uint32_t width, uint32_t height, int step, SplitPass pd, SplitPass pi, uint32_t last)
+{
+    static_assert(DIRECT || INDIRECT, "a pass filters at least one component");
+    static_assert(!SHARED || (DIRECT && INDIRECT), "only two active components share their guide terms");
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t x = blockIdx.x * 16u + (wave & 1u) * 8u + (lane & 7u);
+    const uint32_t y = blockIdx.y * 16u + (wave >> 1) * 8u + (lane >> 3);
+    if (x >= width || y >= height) return;
+    const uint32_t p = y * width + x;
+    const float4   gp = guide[p];
+    // (an inactive component's value is needed by the last pass alone)
+    const float4   dp = (DIRECT || last) ? dIn[p] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    const float4   ip = (INDIRECT || last) ? iIn[p] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (!(gp.w > 0.0f))
+    {
+        if (last) out[p] = make_float4(dp.x, dp.y, dp.z, 1.0f);
+        else
+        {
+            if (DIRECT) dOut[p] = dp;
+            if (INDIRECT) iOut[p] = ip;
+        }
+        return;
+    }
+    constexpr float k[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
+    const float     denCD = pd.sc2 * (dp.w * dp.w + kEpsLum), denCI = pi.sc2 * (ip.w * ip.w + kEpsLum);
+    const float     denZD = pd.szs * gp.w, denZI = pi.szs * gp.w;
+    float           sumWD = 0.0f, dx_ = 0.0f, dy_ = 0.0f, dz_ = 0.0f;
+    float           sumWI = 0.0f, ix_ = 0.0f, iy_ = 0.0f, iz_ = 0.0f;
+#pragma unroll
+    for (int dy = -2; dy <= 2; ++dy)
+    {
+        const int qy = static_cast<int>(y) + step * dy;
+        if (qy < 0 || qy >= static_cast<int>(height)) continue; // (a row outside the frame: all five taps skipped)
+#pragma unroll
+        for (int dx = -2; dx <= 2; ++dx)
+        {
+            const int   qx = static_cast<int>(x) + step * dx;
+            const float h = k[dx + 2] * k[dy + 2];
+            float       wD = h, wI = h;
+            float4      dq = dp, iq = ip;
+            if (!(dx == 0 && dy == 0))
+            {
+                if (qx < 0 || qx >= static_cast<int>(width)) continue;
+                const uint32_t q = static_cast<uint32_t>(qy) * width + static_cast<uint32_t>(qx);
+                const float4   gq = guide[q];
+                if (!(gq.w > 0.0f)) continue;
+                const float nd = 1.0f - ((gp.x * gq.x + gp.y * gq.y) + gp.z * gq.z);
+                const float zd = fabsf(gq.w - gp.w);
+                const float tnD = tukey(nd / pd.sigmaN), tzD = tukey(zd / denZD);
+                const float tnI = SHARED ? tnD : tukey(nd / pi.sigmaN), tzI = SHARED ? tzD : tukey(zd / denZI);
+                if (DIRECT)
+                {
+                    dq = dIn[q];
+                    const float dr = dq.x - dp.x, dg = dq.y - dp.y, db = dq.z - dp.z;
+                    const float xc = ((dr * dr + dg * dg) + db * db) / denCD;
+                    wD = ((h * tukey(xc)) * tnD) * tzD;
+                }
+                if (INDIRECT)
+                {
+                    iq = iIn[q];
+                    const float dr = iq.x - ip.x, dg = iq.y - ip.y, db = iq.z - ip.z;
+                    const float xc = ((dr * dr + dg * dg) + db * db) / denCI;
+                    wI = ((h * tukey(xc)) * tnI) * tzI;
+                }
+            }
+            if (DIRECT)
+            {
+                sumWD += wD;
+                dx_ += wD * dq.x;
+                dy_ += wD * dq.y;
+                dz_ += wD * dq.z;
+            }
+            if (INDIRECT)
+            {
+                sumWI += wI;
+                ix_ += wI * iq.x;
+                iy_ += wI * iq.y;
+                iz_ += wI * iq.z;
+            }
+        }
+    }
+    // e' of an active component; an inactive one keeps its value
+    const float dX = DIRECT ? dx_ / sumWD : dp.x, dY = DIRECT ? dy_ / sumWD : dp.y, dZ = DIRECT ? dz_ / sumWD : dp.z;
+    const float iX = INDIRECT ? ix_ / sumWI : ip.x, iY = INDIRECT ? iy_ / sumWI : ip.y, iZ = INDIRECT ? iz_ / sumWI : ip.z;
+    if (last)
+    {
+        const float4 ae = albedo[p];
+        out[p] = make_float4((dX + iX) * ae.x, (dY + iY) * ae.y, (dZ + iZ) * ae.z, 1.0f);
+        return;
+    }
+    if (DIRECT) dOut[p] = make_float4(dX, dY, dZ, (dX + dY) + dZ);
+    if (INDIRECT) iOut[p] = make_float4(iX, iY, iZ, (iX + iY) + iZ);
+}
 } // namespace
 
-void DenoiseWork::reserve(uint64_t n, hipStream_t stream)
+void DenoiseWork::reserve(uint64_t n, hipStream_t stream, bool split)
 {
-    if (n <= bgra.count) return; // (allocated last: it has room only when every buffer has)
+    // (bgra and eI[1] are allocated last: each has room only when every buffer of its set has)
+    const bool needSplit = split && eI[1].count < n;
+    if (n <= bgra.count && !needSplit) return;
     RF_HIP(hipStreamSynchronize(stream)); // (a smaller set may still be in use by the last run)
+    const bool            withSplit = split || eI[1].count != 0;
+    const uint64_t        room = std::max<uint64_t>(n, bgra.count);
     DeviceBuffer<float4>* const f4[] = {&e[0], &e[1], &guide, &albedo, &out};
     for (auto* b : f4) b->release(); // (the whole set goes before any of the new one comes)
     bgra.release();
-    for (auto* b : f4) b->alloc(n);
-    bgra.alloc(n);
+    eI[0].release(), eI[1].release();
+    for (auto* b : f4) b->alloc(room);
+    bgra.alloc(room);
+    if (withSplit) eI[0].alloc(room), eI[1].alloc(room);
 }
 
 void enqueueDenoise(hipStream_t stream, DenoiseWork& w, const float4* colorSum, const float4* albedoCoverage, const float4* normalDepth, uint32_t width,
@@ -228,6 +389,71 @@ void enqueueDenoise(hipStream_t stream, DenoiseWork& w, const float4* colorSum, 
     }
     hipLaunchKernelGGL(tonemapKernel(), dim3((n + 255) / 256), dim3(256), 0, stream, static_cast<const float4*>(w.out.ptr), n, 1u, exposure, w.bgra.ptr);
     RF_HIP(hipGetLastError());
+}
+
+// The pair with the lowest error of the sweep over both components' L and σc (profiles/split_denoise/README.md: 4-spp frames against 1024 spp): the direct light is all
+// but noise-free and wants next to no filtering; the indirect light wants a short chain whose colour term is as good as off, its edges left to the normal and depth terms.
+SplitDenoiseDefaults splitDenoiseDefaults() { return SplitDenoiseDefaults{DenoiseParameters{1u, 0.25f, 0.1f, 0.1f}, DenoiseParameters{2u, 256.0f, 0.1f, 0.1f}}; }
+
+void enqueueDenoiseSplit(hipStream_t stream, DenoiseWork& w, const float4* colorSum, const float4* directSum, const float4* albedoCoverage, const float4* normalDepth,
+                         uint32_t width, uint32_t height, uint32_t tilesX, uint32_t samples, const DenoiseParameters& pd, const DenoiseParameters& pi, float exposure)
+{
+    const uint32_t n = width * height;
+    w.reserve(n, stream, true);
+    const float    nf = static_cast<float>(samples);
+    const dim3     prepGrid((n + 255) / 256);
+    const uint32_t passes = std::max(pd.iterations, pi.iterations);
+    if (passes == 0)
+        hipLaunchKernelGGL(kDenoisePrepSplit, prepGrid, dim3(256), 0, stream, colorSum, directSum, albedoCoverage, normalDepth, width, height, tilesX, nf,
+                           static_cast<float4*>(nullptr), static_cast<float4*>(nullptr), static_cast<float4*>(nullptr), static_cast<float4*>(nullptr), w.out.ptr);
+    else
+    {
+        hipLaunchKernelGGL(kDenoisePrepSplit, prepGrid, dim3(256), 0, stream, colorSum, directSum, albedoCoverage, normalDepth, width, height, tilesX, nf, w.e[0].ptr,
+                           w.eI[0].ptr, w.guide.ptr, w.albedo.ptr, static_cast<float4*>(nullptr));
+        const dim3 grid((width + 15) / 16, (height + 15) / 16);
+        uint32_t   curD = 0, curI = 0; // which of its two buffers holds each component's current value
+        for (uint32_t i = 0; i < passes; ++i)
+        {
+            const bool last = i + 1 == passes, actD = i < pd.iterations, actI = i < pi.iterations;
+            const auto pass = [&](const DenoiseParameters& p) {
+                return SplitPass{(p.sigmaColor * p.sigmaColor) * std::ldexp(1.0f, -static_cast<int>(i)) /* exact: a power of two */, p.sigmaNormal,
+                                 p.sigmaDepth * static_cast<float>(1u << i)};
+            };
+            const SplitPass sd = pass(pd), si = pass(pi);
+            const bool      shared = actD && actI && sd.sigmaN == si.sigmaN && sd.szs == si.szs;
+            const auto      kernel = actD && actI ? (shared ? kDenoiseAtrousSplit<true, true, true> : kDenoiseAtrousSplit<true, true, false>)
+                                                  : (actD ? kDenoiseAtrousSplit<true, false, false> : kDenoiseAtrousSplit<false, true, false>);
+            hipLaunchKernelGGL(kernel, grid, dim3(kDenoiseBlock), 0, stream, static_cast<const float4*>(w.e[curD].ptr), static_cast<const float4*>(w.eI[curI].ptr),
+                               static_cast<const float4*>(w.guide.ptr), static_cast<const float4*>(w.albedo.ptr), w.e[curD ^ 1u].ptr, w.eI[curI ^ 1u].ptr, w.out.ptr, width, height,
+                               static_cast<int>(1u << i), sd, si, last ? 1u : 0u);
+            if (actD) curD ^= 1u;
+            if (actI) curI ^= 1u;
+        }
+    }
+    hipLaunchKernelGGL(tonemapKernel(), dim3((n + 255) / 256), dim3(256), 0, stream, static_cast<const float4*>(w.out.ptr), n, 1u, exposure, w.bgra.ptr);
+    RF_HIP(hipGetLastError());
+}
+
+void denoiseSplitImages(int deviceOrdinal, uint32_t width, uint32_t height, uint32_t samples, const float* colorSum, const float* directSum, const float* albedoCoverage,
+                        const float* normalDepth, const DenoiseParameters& direct, const DenoiseParameters& indirect, float exposure, float* outRgba, uint32_t* outBgra8)
+{
+    requireDevice(deviceOrdinal);
+    const uint64_t n = static_cast<uint64_t>(width) * height;
+    // (leaving the scope: the stream is synchronised, the buffers are freed, the stream is destroyed -- ScopedStream)
+    ScopedStream         stream;
+    DeviceBuffer<float4> in[4];
+    DenoiseWork          work;
+    ScopedStream::Drain  drain{stream};
+    const float*         src[4] = {colorSum, directSum, albedoCoverage, normalDepth};
+    for (int b = 0; b < 4; ++b)
+    {
+        in[b].alloc(n);
+        RF_HIP(hipMemcpyAsync(in[b].ptr, src[b], n * sizeof(float4), hipMemcpyHostToDevice, stream.handle));
+    }
+    enqueueDenoiseSplit(stream.handle, work, in[0].ptr, in[1].ptr, in[2].ptr, in[3].ptr, width, height, 0u, samples, direct, indirect, exposure);
+    if (outRgba) RF_HIP(hipMemcpyAsync(outRgba, work.out.ptr, n * sizeof(float4), hipMemcpyDeviceToHost, stream.handle));
+    if (outBgra8) RF_HIP(hipMemcpyAsync(outBgra8, work.bgra.ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream.handle));
+    RF_HIP(hipStreamSynchronize(stream.handle));
 }
 
 void denoiseImages(int deviceOrdinal, uint32_t width, uint32_t height, uint32_t samples, const float* colorSum, const float* albedoCoverage, const float* normalDepth,

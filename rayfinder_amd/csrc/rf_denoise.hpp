@@ -18,9 +18,12 @@ struct DenoiseWork
     DeviceBuffer<float4>   albedo; // {a + εa, 0}
     DeviceBuffer<float4>   out;    // the denoised mean {rgb, 1}
     DeviceBuffer<uint32_t> bgra;   // kTonemap of `out` (accumulatedSamples = 1)
+    DeviceBuffer<float4>   eI[2];  // the split-component filter's second ping-pong pair, the indirect component's {e.rgb, ℓ} (e[] then holds the direct one's); empty
+                                   // until the first split run
 
-    // room for `pixels` in every buffer (stream-synchronises before it frees a smaller set)
-    void reserve(uint64_t pixels, hipStream_t stream);
+    // room for `pixels` in every buffer (stream-synchronises before it frees a smaller set); split: in eI[] as well.  Whatever has to grow, the whole set is freed
+    // and allocated again in one go.
+    void reserve(uint64_t pixels, hipStream_t stream, bool split = false);
 };
 
 // Enqueue kDenoisePrep, the L kDenoiseAtrous passes and kTonemap on `stream`.  tilesX != 0: the sums are compact tile-major buffers holding every tile of the
@@ -32,4 +35,10 @@ struct DenoiseWork
 void enqueueDenoise(hipStream_t stream, DenoiseWork& work, const float4* colorSum, const float4* albedoCoverage, const float4* normalDepth, uint32_t width,
                     uint32_t height, uint32_t tilesX, uint32_t samples, const DenoiseParameters& params, float exposure, const uint32_t* tileSamples = nullptr,
                     const float4* mean = nullptr);
+
+// The split-component filter (rf_renderer_denoise_split): kDenoisePrepSplit, max(L_D, L_I) kDenoiseAtrousSplit passes -- the last one adds the components and
+// remodulates -- and kTonemap on `stream`; the result in work.out / work.bgra as enqueueDenoise leaves it.  directSum: D, laid out like colorSum.  tilesX as above.
+void enqueueDenoiseSplit(hipStream_t stream, DenoiseWork& work, const float4* colorSum, const float4* directSum, const float4* albedoCoverage, const float4* normalDepth,
+                         uint32_t width, uint32_t height, uint32_t tilesX, uint32_t samples, const DenoiseParameters& direct, const DenoiseParameters& indirect,
+                         float exposure);
 } // namespace rf

@@ -202,6 +202,10 @@ struct Renderer::Impl
     float4*                 aovAlbedoCoverage() const { return aovSums.buffers[0].ptr; }
     float4*                 aovNormalDepth() const { return aovSums.buffers[1].ptr; }
     float4*                 moments() const { return momentSums.buffers[0].ptr; }
+    // direct radiance sums (rf_renderer_set_direct; off by default: nothing is allocated or launched then): D = the sum of each sample's radiance as it stands after
+    // bounce 1 (the primary miss's sky term, or the first hit's sun term times its visibility), in the image's layout and the image's order
+    SumChannel              directSums{false, 1};
+    float4*                 direct() const { return directSums.buffers[0].ptr; }
     // bucket sums (rf_renderer_set_buckets; off by default: nothing is allocated or launched then): bucketSums.planes = K planes of the shard's tiles x 1024 float4 each
     // in one buffer, plane b = the radiance sum over the samples of ordinal b mod K (under render_adaptive, bucketTileCounts: of the TILE's samples -- every active tile
     // holds bucketSums.samples of them); the robust mean's buffers and the snapshot they hold -- valid until the bucket sums are restarted
@@ -450,6 +454,13 @@ struct Renderer::Impl
         restartAovs();
         momentSums.restart();
         restartBuckets();
+        restartDirect();
+    }
+    // (also when the switch changes: a split-denoised snapshot was filtered from these sums)
+    void restartDirect()
+    {
+        directSums.restart();
+        denoisedValid = false;
     }
     // (also when K changes: the snapshot was combined from these sums)
     void restartBuckets()
@@ -953,6 +964,7 @@ struct Renderer::Impl
         aovSums.zeroIfStale(stream, pixelsPadded);
         momentSums.zeroIfStale(stream, pixelsPadded);
         bucketSums.zeroIfStale(stream, pixelsPadded);
+        directSums.zeroIfStale(stream, pixelsPadded);
     }
 
     // Samples per batch for `todo` samples of `pixelsPadded` path slots per sample (the shard's tiles, or the active tiles of render_adaptive), with the path state
@@ -1044,6 +1056,7 @@ struct Renderer::Impl
         if (aovSums.on) aovSums.samples += n;
         if (momentSums.on) momentSums.samples += n;
         if (bucketSums.on) bucketSums.samples += n;
+        if (directSums.on) directSums.samples += n;
         return n;
     }
 
@@ -1137,6 +1150,21 @@ struct Renderer::Impl
         if (b.bucketPixels != 0u)
             hipLaunchKernelGGL(bucketKernel(b.runs, b.tileList ? listAddressing : SumAddressing::Compact), sumGrid(b.bucketPixels), dim3(b.runs ? 64u : static_cast<uint32_t>(kBlock)), 0, stream, fp, tileIds.ptr, ps.rad, bucketPlanes(),
                                bucketStride(), b.buckets, b.bucketPhase);
+    }
+
+    // The direct sums (rf_renderer_set_direct), enqueued right behind bounce 1's launch groups: ps.rad then holds each sample's direct light, and D gets it through the
+    // accumulate kernel the plan chose for the batch's image -- the same ordered chain, whatever the batch depth or slot order.  Never under a tile list: render_adaptive
+    // is refused while the direct sums are on (checkAdaptive).
+    void enqueueDirect(const BatchPlan& b, const FrameParams& fp, const PathStreams& ps)
+    {
+        const auto sumGrid = [&](uint32_t pixelsPerGroup) { return dim3((fp.pixelsPadded + pixelsPerGroup - 1) / pixelsPerGroup); };
+        if (b.accumulateKernel == kAccumulateRuns)
+            hipLaunchKernelGGL(accumulateRunsKernel(b.accumulatePixels), sumGrid(b.accumulatePixels), dim3(64), b.accumulatePixels * 3u * (b.numSamples + 1u) * sizeof(float), stream, fp,
+                               tileIds.ptr, ps, direct());
+        else if (b.accumulateKernel == kAccumulatePixels)
+            hipLaunchKernelGGL(sumKernel(Sum::Radiance, false, SumAddressing::Compact), sumGrid(b.accumulatePixels), dim3(static_cast<uint32_t>(kBlock)), 0, stream, fp, tileIds.ptr,
+                               static_cast<const float4*>(ps.rad), direct(), static_cast<float4*>(nullptr));
+        else throw std::logic_error("the direct sums have no tile-list kernel");
     }
 
     // Trace `numSamples` consecutive samples (sample indices start at frame `firstFrame`) of the shard's tiles -- or, active != nullptr, of the tile list that
@@ -1234,6 +1262,7 @@ struct Renderer::Impl
             launchTimed(1, [&] { enqueueClosest(plan.closest, io); }, io.bounce - 1);
             launchTimed(2, [&] { enqueueShadeAndSky(plan, io); });
             launchTimed(3, [&] { enqueueShadow(plan, io); }, io.bounce - 1);
+            if (io.bounce == 1u && directSums.on) launchTimed(4, [&] { enqueueDirect(batch, fp, io.ps); });
             std::swap(io.in, io.out);
             std::swap(io.ps.rayD, io.ps.rayDOut);
             std::swap(io.ps.thr, io.ps.thrOut);
@@ -1735,6 +1764,51 @@ void Renderer::readMoments(float* sumSq, uint32_t* sampleCount)
     if (sampleCount) *sampleCount = empty ? 0u : m.momentSums.samples;
 }
 
+void Renderer::setDirect(bool enabled)
+{
+    Impl& m = *mImpl;
+    if (enabled) m.requireUniform("rf_renderer_set_direct", ": the direct sums keep ONE sample count for the frame");
+    if (enabled == m.directSums.on) return;
+    RF_HIP(hipSetDevice(m.device));
+    RF_HIP(hipStreamSynchronize(m.stream)); // (a batch in flight may still write the sums)
+    m.directSums.on = enabled;
+    m.restartDirect();
+    // off: nothing of the direct sums stays allocated
+    if (!enabled) m.directSums.release();
+}
+
+bool Renderer::directEnabled() const { return mImpl->directSums.on; }
+
+void Renderer::readDirect(float* directSum, uint32_t* sampleCount)
+{
+    Impl& m = *mImpl;
+    synchronize();
+    const bool empty = m.directSums.empty();
+    if (directSum) m.readCompact(empty ? nullptr : m.direct(), directSum);
+    if (sampleCount) *sampleCount = empty ? 0u : m.directSums.samples;
+}
+
+void Renderer::denoiseSplit(const DenoiseParameters& direct, const DenoiseParameters& indirect)
+{
+    Impl& m = *mImpl;
+    m.requireUniform("rf_renderer_denoise_split");
+    if (!m.aovSums.on) throw std::invalid_argument("denoise_split needs the first-hit AOVs: turn them on (rf_renderer_set_aovs) before the first sample");
+    if (!m.directSums.on) throw std::invalid_argument("denoise_split needs the direct sums: turn them on (rf_renderer_set_direct) before the first sample");
+    if (m.worldSize != 1u) throw std::invalid_argument("denoise_split needs the whole frame: a tile shard is set (use rf_denoise_split_images on the sum of the ranks' reads)");
+    if (m.accumulated == 0u) throw std::invalid_argument("denoise_split: no sample has been accumulated");
+    if (!m.aovSums.covers(m.accumulated))
+        throw std::invalid_argument("denoise_split: the AOV sample count (" + std::to_string(m.aovSums.samples) + ") differs from the accumulated sample count (" +
+                                    std::to_string(m.accumulated) + "): turn the AOVs on before the first sample");
+    if (!m.directSums.covers(m.accumulated))
+        throw std::invalid_argument("denoise_split: the direct sample count (" + std::to_string(m.directSums.samples) + ") differs from the accumulated sample count (" +
+                                    std::to_string(m.accumulated) + "): turn the direct sums on before the first sample");
+    RF_HIP(hipSetDevice(m.device));
+    enqueueDenoiseSplit(m.stream, m.denoiseWork, m.image, m.direct(), m.aovAlbedoCoverage(), m.aovNormalDepth(), m.params.width, m.params.height, m.grid().tilesX, m.accumulated,
+                        direct, indirect, m.params.exposure);
+    m.denoisedValid = true;
+    m.denoisedSamples = m.accumulated;
+}
+
 void Renderer::setBuckets(uint32_t word)
 {
     Impl& m = *mImpl;
@@ -1875,6 +1949,9 @@ NoiseEstimate Renderer::noiseEstimate(float* errorMap, float* tileSum, float* ti
 void Renderer::checkAdaptive(const AdaptiveParameters& p, bool sharded) const
 {
     const Impl& m = *mImpl;
+    if (m.directSums.on)
+        throw std::invalid_argument("render_adaptive: the direct sums are on (rf_renderer_set_direct), and they keep ONE sample count for the frame: turn them off "
+                                    "(rf_renderer_set_direct(r, 0)) before sampling adaptively");
     if (m.bucketSums.on && m.bucketTileCounts && sharded && !m.bucketShardTileCounts)
         throw std::invalid_argument("render_adaptive: the bucket sums are on (rf_renderer_set_buckets), and RF_BUCKETS_TILE_COUNTS covers rf_renderer_render_adaptive only: "
                                     "bucket planes under a tile shard are not kept per tile count; turn the buckets off (rf_renderer_set_buckets(r, 0)) first");
@@ -1899,7 +1976,7 @@ AdaptiveResult Renderer::renderAdaptive(const AdaptiveParameters& p)
 {
     Impl& m = *mImpl;
     // (the order of the checks, and so which message a call with several faults gets, is the one this call always had)
-    if ((m.bucketSums.on && !m.bucketTileCounts) || !m.momentSums.on || (m.aovSums.on && !m.aovTileCounts())) checkAdaptive(p);
+    if (m.directSums.on || (m.bucketSums.on && !m.bucketTileCounts) || !m.momentSums.on || (m.aovSums.on && !m.aovTileCounts())) checkAdaptive(p);
     if (m.worldSize != 1u) throw std::invalid_argument("render_adaptive needs the whole frame: a tile shard is set (rf_comm_render_adaptive samples a sharded frame adaptively)");
     checkAdaptive(p);
     return renderAdaptiveFrom(p, m.accumulated, false);
@@ -2167,7 +2244,7 @@ void Renderer::memoryInfo(uint64_t& pathStateBytes, uint64_t& pathsAllocated, ui
 {
     const Impl& m = *mImpl;
     pathsAllocated = m.allocatedPaths;
-    pathStateBytes = m.pathStateBytes();
+    pathStateBytes = m.pathStateBytes() + m.directSums.buffers[0].count * sizeof(float4); // (the direct sums, while they are on: 16 B per pixel of the shard's tiles)
     maxPathsPerBatch = m.effectivePaths ? std::min(m.effectivePaths, m.maxPaths) : m.maxPaths;
     sceneBytes = (m.nodes.count + m.triangles.count + m.wideNodes.count + m.wideCompact.count + m.wideHot.count + m.wideOwn.count + m.wideQuad.count + m.wideQuadHalf.count + m.wideQuadLocal.count + m.wideOct.count + m.attributes.count + m.shadeRecords.count) * sizeof(float4) +
                  m.texels.count * sizeof(uint32_t) + m.bigLeaves.count * sizeof(uint2) + m.occluderGrid.count * sizeof(uint32_t); // (the occluder grid: allocated by the first batch)

@@ -153,6 +153,15 @@ void denoiseImages(int deviceOrdinal, uint32_t width, uint32_t height, uint32_t 
 void denoiseTiles(int deviceOrdinal, uint32_t width, uint32_t height, const uint32_t* tileSamples, uint32_t samples, const float* colorSum, const float* albedoCoverage,
                   const float* normalDepth, const DenoiseParameters& params, float exposure, float* outRgba, uint32_t* outBgra8);
 
+// The split-component denoiser over host-assembled row-major sums: colorSum = S, directSum = D (the layout of S), the rest as denoiseImages.  Synchronous.
+struct SplitDenoiseDefaults
+{
+    DenoiseParameters direct, indirect;
+};
+SplitDenoiseDefaults splitDenoiseDefaults();
+void denoiseSplitImages(int deviceOrdinal, uint32_t width, uint32_t height, uint32_t samples, const float* colorSum, const float* directSum, const float* albedoCoverage,
+                        const float* normalDepth, const DenoiseParameters& direct, const DenoiseParameters& indirect, float exposure, float* outRgba, uint32_t* outBgra8);
+
 // The firefly-robust mean (rf_robust.hip; the definition: include/rayfinder_amd.h) over host-assembled bucket planes -- K x width*height*4 floats, plane after plane,
 // each row-major -- of `samples` >= K samples, on device `deviceOrdinal`: the mean RGBA (.w = 1), its BGRA8 under `exposure` and the trim count of every pixel
 // (NULL = skip).  K odd, 3 .. 15.  Synchronous; allocates and frees its own device memory.
@@ -251,6 +260,18 @@ public:
     void     setMoments(bool enabled);
     bool     momentsEnabled() const;
     void     readMoments(float* sumSq, uint32_t* sampleCount);
+    // Direct radiance sums (rf_renderer_set_direct / rf_renderer_read_direct): off by default.  While on, one more compact tile-major float4 buffer holds D = the sum, in
+    // sample order, of each sample's radiance as it stands after bounce 1 -- what the image of a handle with numBounces = 1 holds, bit for bit -- over the samples traced
+    // since it was last cleared (with the image, or when the switch changes).  Indirect light is S - D, formed by whoever needs it.  One more launch per batch, behind
+    // bounce 1's shadow launch.  While on, renderAdaptive / checkAdaptive refuse; turning it on is refused in the non-uniform state.
+    // Read: row-major width*height*4 floats (this rank's pixels; NULL = skip) and the direct sample count.
+    void     setDirect(bool enabled);
+    bool     directEnabled() const;
+    void     readDirect(float* directSum, uint32_t* sampleCount);
+    // The split-component denoiser (rf_renderer_denoise_split; the arithmetic: include/rayfinder_amd.h): D and S - D demodulated and filtered separately, each with its
+    // own parameters, and recombined; the result is denoise's snapshot (readDenoised).  std::invalid_argument in the non-uniform state, when the AOVs or the direct sums
+    // are off or do not cover the accumulation, nothing is accumulated or a tile shard is set.
+    void denoiseSplit(const DenoiseParameters& direct, const DenoiseParameters& indirect);
     // Bucket sums (rf_renderer_set_buckets / rf_renderer_read_buckets): K = 0 off (the default), else odd, 3 .. 15.  While on, K more compact tile-major float4 planes
     // in one allocation: plane b holds {sum r.x, sum r.y, sum r.z, 0} over the samples whose ordinal -- the bucket sample count just before the sample -- is b mod K,
     // in sample order.  Their own sample count; cleared with the image and whenever the word changes.  The word is K, or K | kBucketsTileCounts (K > 0): until
