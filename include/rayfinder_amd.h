@@ -272,8 +272,22 @@ RF_API int rf_denoise_tiles(int32_t device_ordinal, uint32_t width, uint32_t hei
  * allocated); S, Q, the AOV sums, the bucket sums and the ray counts are bit for bit what they are with it off.  D keeps its own sample count -- the samples traced
  * while it was on -- and is cleared, with the count set to 0, when the image is (a change through rf_renderer_set_render_parameters, a new tile shard, a newly bound
  * accumulation buffer) and when the switch changes.  Turned on partway through an accumulation, D covers only the later samples.
- * While on, rf_renderer_render_adaptive and rf_comm_render_adaptive return RF_ERROR_INVALID_ARGUMENT (the message names the direct sums) before anything is traced
- * or exchanged, the state kept; rf_renderer_set_direct(r, 1) is refused in the non-uniform state.  rf_renderer_gather_frame does not carry D.
+ * While on with plain 1, rf_renderer_render_adaptive and rf_comm_render_adaptive return RF_ERROR_INVALID_ARGUMENT (the message names the direct sums) before anything
+ * is traced or exchanged, the state kept; turning D on, in either form, is refused in the non-uniform state.  rf_renderer_gather_frame does not carry D.
+ * The argument's domain is checked (until RF_DIRECT_TILE_COUNTS was added any non-zero value meant "on"): 0, 1 and 1 | RF_DIRECT_TILE_COUNTS; the bit alone and any
+ * other bit are RF_ERROR_INVALID_ARGUMENT, the state kept.
+ * rf_renderer_set_direct(r, 1 | RF_DIRECT_TILE_COUNTS) opts in to per-tile counts, as RF_AOV_TILE_COUNTS does for the AOV sums.  Until rf_renderer_render_adaptive or
+ * rf_comm_render_adaptive is called the handle behaves bit for bit like one with plain 1: sums, image, stats, launch plans, rf_renderer_memory_info.  The adaptive calls
+ * then run with D on: D of every pixel of tile t is bit for bit what rf_renderer_render(tile_samples[t]) leaves there in a fresh accumulation with D on -- equally,
+ * the accumulation of a num_bounces = 1 handle after tile_samples[t] samples --, added under the call's tile list by the list-addressed radiance sum (one lane per
+ * pixel for batches of at most 4 samples or a slot order that is not pixel-major, else LDS-staged; the same ordered chain either way); the direct sample count
+ * advances with L; S, Q, the AOV sums, the schedule and *result are exactly what they are with D off.  The calls are still refused (the message names the direct sums
+ * and says "restart the accumulation first") when D is on but does not cover the accumulation.  Any change of the argument's value clears D and drops a
+ * split-denoised snapshot, 1 <-> 1 | RF_DIRECT_TILE_COUNTS included.  In the non-uniform state rf_renderer_read_direct returns the sums as they are and the leading
+ * count L; a pixel's divisor is its tile's count (rf_renderer_read_tile_samples).
+ * Across ranks the one bit covers rf_comm_render_adaptive too (D is shard-compact and addressed through the shard's slot list): afterwards the sum of the ranks'
+ * rf_renderer_read_direct is the whole-frame handle's D, bit for bit.  NOT covered: the frame gather still does not carry D, and there is no root-side
+ * rf_comm_denoise_split -- the ranks' reads are summed on the host and handed to rf_denoise_split_tiles with the gathered counts.
  * rf_renderer_read_direct: row-major width*height*4 floats (the layout of rf_renderer_read_accumulation; may be NULL) and the direct sample count.  With a tile shard
  * set, this rank's pixels and zeros elsewhere: the sum of the ranks' reads is the whole frame.
  *
@@ -296,7 +310,14 @@ RF_API int rf_denoise_tiles(int32_t device_ordinal, uint32_t width, uint32_t hei
  * state (that state's message, before the other checks), when the AOVs or the direct sums are off, when the AOV or the direct sample count differs from the accumulated
  * count, when no sample has been accumulated, or when a tile shard is set.  The first call allocates two more float4 per pixel next to rf_renderer_denoise's buffers.
  * rf_denoise_split_images: the same filter over row-major host sums on device device_ordinal; out_rgba / out_bgra8 may be NULL.  Synchronous.  A NULL input, a zero
- * size or sample count and bad parameters are refused before any device call. */
+ * size or sample count and bad parameters are refused before any device call.
+ * ONE COUNT PER TILE.  In the non-uniform state rf_renderer_denoise_split runs when D carries RF_DIRECT_TILE_COUNTS, the AOVs carry RF_AOV_TILE_COUNTS and both cover
+ * the accumulation: prep's Nf is float(tile_samples[t]) of the pixel's tile t, for c, a, m, cD and cI alike; the passes and the finish are unchanged.  The call first
+ * waits for the handle's stream and copies the counts to the device, as rf_renderer_denoise does in this state; the snapshot's sample count is L.  With every count
+ * equal to N the result is bit for bit the one-count filter's.  Otherwise the non-uniform state's refusal stands ("different sample counts"), before the other checks.
+ * rf_denoise_split_tiles: rf_denoise_split_images with rf_denoise_tiles' tile_samples (one count > 0 per tile of the 32x32 grid, host memory) in place of the one
+ * sample count.  A NULL input, a zero size, any count of 0 and bad parameters are refused before any device call.  Synchronous. */
+#define RF_DIRECT_TILE_COUNTS 0x100u /* ORed into rf_renderer_set_direct's 1: keep D per tile count under rf_renderer_render_adaptive / rf_comm_render_adaptive */
 RF_API int rf_renderer_set_direct(rf_renderer* r, int enabled);
 RF_API int rf_renderer_read_direct(rf_renderer* r, float* direct_sum4, uint32_t* direct_sample_count);
 RF_API int rf_denoise_split_default_parameters(rf_denoise_parameters* direct, rf_denoise_parameters* indirect);
@@ -304,6 +325,9 @@ RF_API int rf_renderer_denoise_split(rf_renderer* r, const rf_denoise_parameters
 RF_API int rf_denoise_split_images(int32_t device_ordinal, uint32_t width, uint32_t height, uint32_t samples, const float* color_sum4, const float* direct_sum4,
                                    const float* albedo_coverage4, const float* normal_depth4, const rf_denoise_parameters* direct, const rf_denoise_parameters* indirect,
                                    float exposure, float* out_rgba, uint32_t* out_bgra8);
+RF_API int rf_denoise_split_tiles(int32_t device_ordinal, uint32_t width, uint32_t height, const uint32_t* tile_samples, const float* color_sum4, const float* direct_sum4,
+                                  const float* albedo_coverage4, const float* normal_depth4, const rf_denoise_parameters* direct, const rf_denoise_parameters* indirect,
+                                  float exposure, float* out_rgba, uint32_t* out_bgra8);
 
 /* Radiance second moments and the noise estimate: how noisy the accumulation still is, per pixel, per 32x32 tile and for the frame, and a render call that stops
  * at a noise target.  No reference counterpart (the reference counts samples: renderProgressPercentage).
@@ -474,10 +498,12 @@ RF_API int rf_renderer_denoise_robust(rf_renderer* r, const rf_denoise_parameter
  * With RF_AOV_FIRST_HIT | RF_AOV_TILE_COUNTS the same holds for the AOV sums: AC = {albedo.rgb, coverage} and ND = {normal.xyz, depth} of every pixel of tile t are
  * bit for bit what rf_renderer_render(tile_samples[t]) leaves there in a fresh accumulation with the AOVs on; the AOV sample count advances with L, as the moment
  * count does; and S, Q, the schedule (which tile stops when) and *result are exactly what they are with the AOVs off.
+ * With rf_renderer_set_direct(r, 1 | RF_DIRECT_TILE_COUNTS) the same holds for the direct sums D (the direct sums' block above).
  * A later call, with the same or other parameters, continues with the tiles still at the leading count only (stopped tiles are not revived, the active set is not
  * dilated to neighbouring tiles, and counts are per tile, not per pixel).  Waits for the work it enqueues.
  * RF_ERROR_INVALID_ARGUMENT: the moments are off or do not cover the accumulation, the AOVs are on without RF_AOV_TILE_COUNTS (their sums then keep ONE sample
- * count) or with it but do not cover the accumulation (turned on partway through), a tile
+ * count) or with it but do not cover the accumulation (turned on partway through), the bucket sums or the direct sums are on without their tile-count bit or with
+ * it but do not cover the accumulation, a tile
  * shard is set (rf_comm_render_adaptive is the call for a sharded frame), check_every is 0, or target_tile_error is negative or not finite.
  * *result (may be NULL): estimate_passes made by this call; tiles and stopped_tiles (tiles below L) of the frame; the minimum and maximum tile count; pixel_samples =
  * the sum over the tiles of in-frame pixels x tile_samples[t]; last = the estimate of the call's last pass, over the tiles that were active in it (mean_error, max_error,
@@ -485,7 +511,8 @@ RF_API int rf_renderer_denoise_robust(rf_renderer* r, const rf_denoise_parameter
  *
  * While some tile is below L (the NON-UNIFORM state), rf_renderer_render, rf_renderer_render_until, rf_renderer_set_tile_shard and rf_renderer_gather_frame (without RF_GATHER_TILE_COUNTS)
  * return RF_ERROR_INVALID_ARGUMENT with a message that says so: each of them assumes one count for the frame.  So does rf_renderer_denoise, unless the AOVs are on
- * with RF_AOV_TILE_COUNTS and cover the accumulation: it then filters with each tile's own count (the denoiser's block above).
+ * with RF_AOV_TILE_COUNTS and cover the accumulation: it then filters with each tile's own count (the denoiser's block above).  rf_renderer_denoise_split
+ * likewise needs both RF_AOV_TILE_COUNTS and RF_DIRECT_TILE_COUNTS.
  * rf_renderer_set_render_parameters (with a change) and a newly bound accumulation buffer clear the counts with the image.  When every tile is at L -- every tile
  * ran to the cap, a huge target stopped every tile at the first check -- the handle is in the ordinary state and none of them refuses.  (A target of 0 runs a tile to
  * the cap only while its mean error is > 0: a tile in which no pixel has shown any variance so far -- black, constant or non-finite pixels have e = 0 -- is <= 0

@@ -647,6 +647,27 @@ def denoise_tiles(color_sum, albedo_coverage, normal_depth, tile_samples, exposu
     return rgba[..., :3], bgra
 
 
+def denoise_split_tiles(color_sum, direct_sum, albedo_coverage, normal_depth, tile_samples, exposure=1.0, device_ordinal=0, direct=None, indirect=None):
+    """rf_denoise_split_tiles: denoise_split_images with one sample count (> 0) per 32x32 tile, tile_samples in tile order (tile_y * ceil(W / 32) + tile_x): every
+    pixel's sums -- S, D and the AOV sums alike -- are divided by its own tile's count (a frame of render_adaptive with set_direct(True, tile_counts=True) and
+    set_aovs(True, tile_counts=True), or the sum of the ranks' reads after TileComm.render_adaptive with the gathered counts).
+    -> (rgb (H,W,3) f32 denoised mean, bgra (H,W) u32 display texels under `exposure`)."""
+    color_sum, direct_sum, albedo_coverage, normal_depth = (_f32(a) for a in (color_sum, direct_sum, albedo_coverage, normal_depth))
+    h, w = color_sum.shape[:2]
+    for a in (color_sum, direct_sum, albedo_coverage, normal_depth):
+        if a.shape != (h, w, 4):
+            raise ValueError("denoise_split_tiles: the four sums must be (H, W, 4) arrays of one size")
+    counts = np.ascontiguousarray(tile_samples, np.uint32).reshape(-1)
+    if counts.size != _noise_tiles(w, h):
+        raise ValueError(f"denoise_split_tiles: {_noise_tiles(w, h)} tile counts expected, got {counts.size}")
+    pd, pi = _split_parameters(direct, indirect)
+    rgba = np.zeros((h, w, 4), np.float32)
+    bgra = np.zeros((h, w), np.uint32)
+    check(lib.rf_denoise_split_tiles(device_ordinal, w, h, _ptr(counts), _ptr(color_sum), _ptr(direct_sum), _ptr(albedo_coverage), _ptr(normal_depth), C.byref(pd),
+                                     C.byref(pi), exposure, _ptr(rgba), _ptr(bgra)))
+    return rgba[..., :3], bgra
+
+
 def robust_mean_images(buckets, samples, exposure=1.0, device_ordinal=0):
     """rf_robust_mean_images: the firefly-robust mean over (K, H, W, 4) f32 bucket sums held on the host (e.g. the sum of several ranks' read_buckets) of `samples`
     >= K samples, K odd in 3 .. 15.  -> dict(mean (H,W,3) f32, bgra8 (H,W) u32 display texels under `exposure`, trim (H,W) u8, samples)."""
@@ -814,9 +835,10 @@ class ReferencePathTracer:
         return rgba[..., :3], bgra, n.value
 
     # direct radiance sums and the split-component denoiser (include/rayfinder_amd.h states what D holds and the filter's arithmetic)
-    def set_direct(self, enabled=True):
-        """Turn the per-pixel direct radiance sums on or off; any change clears them.  While on, render_adaptive is refused."""
-        check(lib.rf_renderer_set_direct(self._h, int(bool(enabled))))
+    def set_direct(self, enabled=True, tile_counts=False):
+        """Turn the per-pixel direct radiance sums on or off; any change clears them.  tile_counts (RF_DIRECT_TILE_COUNTS): the sums follow the per-tile counts under
+        render_adaptive (and TileComm.render_adaptive), and denoise_split then runs in the non-uniform state; without it render_adaptive is refused while they are on."""
+        check(lib.rf_renderer_set_direct(self._h, int(bool(enabled)) | (_ffi.RF_DIRECT_TILE_COUNTS if tile_counts else 0)))
 
     def read_direct(self):
         """-> ((H, W, 4) f32 sums of each sample's radiance after bounce 1 (sky on a primary miss, the first hit's sun term), in sample order; the direct sample
@@ -827,7 +849,8 @@ class ReferencePathTracer:
         return d, n.value
 
     def denoise_split(self, direct=None, indirect=None):
-        """Denoise the direct and the indirect light separately and recombine them (needs the AOVs and the direct sums on from the first sample, no tile shard);
+        """Denoise the direct and the indirect light separately and recombine them (needs the AOVs and the direct sums on from the first sample, no tile shard; after
+        render_adaptive both with tile_counts=True: every pixel is then divided by its tile's count);
         read_denoised reads the result.  direct / indirect: dicts of iterations, sigma_color, sigma_normal, sigma_depth (the rest: that component's defaults)."""
         pd, pi = _split_parameters(direct, indirect)
         check(lib.rf_renderer_denoise_split(self._h, C.byref(pd), C.byref(pi)))

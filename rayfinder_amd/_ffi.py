@@ -39,6 +39,7 @@ RF_ERROR_OUT_OF_RANGE = 4
 RF_AOV_FIRST_HIT = 1
 RF_AOV_TILE_COUNTS = 0x100
 RF_BUCKETS_TILE_COUNTS = 0x100
+RF_DIRECT_TILE_COUNTS = 0x100
 RF_BUCKETS_SHARD_TILE_COUNTS = 0x400
 
 
@@ -154,6 +155,8 @@ SIGNATURES = {
     "rf_renderer_denoise_split": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "rf_denoise_split_images": (C.c_int, [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
                                           C.c_void_p, C.c_void_p]),
+    "rf_denoise_split_tiles": (C.c_int, [C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
+                                         C.c_void_p, C.c_void_p]),
     "rf_renderer_set_moments": (C.c_int, [C.c_void_p, C.c_int]),
     "rf_renderer_read_moments": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
     "rf_renderer_set_buckets": (C.c_int, [C.c_void_p, C.c_uint32]),

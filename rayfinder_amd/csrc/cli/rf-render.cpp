@@ -33,8 +33,9 @@
 // may stop with an empty bucket and the combine is refused).
 // --direct d.pfm / --indirect i.pfm: the light split of the frame from the direct radiance sums (rf_renderer_set_direct, on from the first sample): D / N, the mean
 // of each sample's radiance after bounce 1 (sky on a primary miss, the first hit's sun term), and (S - D) / N per channel (it may be negative).  --denoise-split out.png:
-// the two components denoised separately and recombined (rf_renderer_denoise_split at its defaults; turns the AOVs on).  --gpus 1 only and not with --adaptive: the
-// frame gather does not carry D, and D keeps one sample count for the frame.
+// the two components denoised separately and recombined (rf_renderer_denoise_split at its defaults; turns the AOVs on).  --gpus 1 only: the frame gather does not
+// carry D.  With --adaptive T the direct sums and the AOVs are kept per tile count (1 | RF_DIRECT_TILE_COUNTS, RF_AOV_FIRST_HIT | RF_AOV_TILE_COUNTS): the two PFMs
+// divide every pixel by its own tile's count, and the split denoiser divides every pixel by its tile's count before it filters.
 // --noise-target t [--noise-check-every k]: stop as soon as the frame's mean error is <= t, checked every k samples (default 8), at --spp at the latest
 // (rf_renderer_render_until).  One GPU only: stopping several ranks in step is not implemented.
 #include "cli_common.hpp"
@@ -67,7 +68,8 @@ int main(int argc, char** argv)
                     "  unless --buckets-tile-counts (no value) is given: the bucket sums then follow the tiles' sample counts, and the three images are the adaptive frame's\n"
                     "                 [--direct d.pfm] [--indirect i.pfm] [--denoise-split out.png]\n"
                     "  --direct / --indirect: the mean direct light (after bounce 1) and the rest, (S - D) / N (3-channel PFMs); --denoise-split: the two denoised\n"
-                    "  separately and recombined, at the split defaults.  --gpus 1 only, not with --adaptive\n"
+                    "  separately and recombined, at the split defaults.  --gpus 1 only; with --adaptive the direct sums follow the tiles' sample counts and the\n"
+                    "  three images are the adaptive frame's\n"
                     "                 [--noise-map m.pfm] [--noise-target t] [--noise-check-every k]\n"
                     "  --noise-map: the per-pixel relative standard error of the frame (1-channel PFM); --noise-target: stop once the frame's mean error is <= t,\n"
                     "  checked every k samples (default 8), at --spp at the latest (one GPU only)\n");
@@ -174,10 +176,9 @@ int main(int argc, char** argv)
         return 1;
     }
     const bool direct = !directPfm.empty() || !indirectPfm.empty() || !denoiseSplit.empty();
-    if (direct && (gpus > 1 || adaptive))
+    if (direct && gpus > 1)
     {
-        std::fprintf(stderr, "--direct / --indirect / --denoise-split need --gpus 1 and do not go with --adaptive (the direct sums are not carried by the frame gather and "
-                             "keep one sample count for the frame)\n");
+        std::fprintf(stderr, "--direct / --indirect / --denoise-split need --gpus 1 (the direct sums are not carried by the frame gather)\n");
         return 1;
     }
     rf_pt_format*     pt = loadScene(argv[1]);
@@ -252,7 +253,8 @@ int main(int argc, char** argv)
         if (aovs) rfCheck(rf_renderer_set_aovs(renderer, RF_AOV_FIRST_HIT | (adaptive ? RF_AOV_TILE_COUNTS : 0u)), "AOVs");
         if (noise) rfCheck(rf_renderer_set_moments(renderer, 1), "moments");
         if (buckets != 0u) rfCheck(rf_renderer_set_buckets(renderer, buckets | (bucketsTileCounts ? RF_BUCKETS_TILE_COUNTS : 0u)), "buckets");
-        if (direct) rfCheck(rf_renderer_set_direct(renderer, 1), "direct sums");
+        // (--adaptive: the direct sums follow the per-tile counts too)
+        if (direct) rfCheck(rf_renderer_set_direct(renderer, static_cast<int>(1u | (adaptive ? RF_DIRECT_TILE_COUNTS : 0u))), "direct sums");
         const auto t0 = std::chrono::steady_clock::now();
         if (adaptive) rfCheck(rf_renderer_render_adaptive(renderer, &adaptiveParams, &adaptiveResult), "adaptive render");
         else if (noiseTargetSet) rfCheck(rf_renderer_render_until(renderer, noiseTarget, noiseCheckEvery, spp, &sppReached, &estimate), "render to the noise target");
@@ -293,7 +295,7 @@ int main(int argc, char** argv)
                 if (!noiseMap.empty()) rfCheck(rf_renderer_noise_estimate(renderer, &estimate, errorMap.data(), nullptr, nullptr), "noise estimate");
                 rfCheck(rf_renderer_read_tonemapped(renderer, bgra.data()), "tonemap");
                 if (!acc.empty()) rfCheck(adaptive ? rf_renderer_read_mean(renderer, acc.data()) : rf_renderer_read_accumulation(renderer, acc.data(), &n), "read accumulation");
-                if (!sampleMap.empty() || (adaptive && aovs))
+                if (!sampleMap.empty() || (adaptive && (aovs || direct)))
                 {
                     uint32_t numTiles = 0;
                     rfCheck(rf_renderer_read_tile_samples(renderer, nullptr, &numTiles), "tile samples");
@@ -392,10 +394,14 @@ int main(int argc, char** argv)
         std::fclose(fp);
         return true;
     };
-    // (f32 divisions by the direct sample count, as a caller of rf_renderer_read_direct forms them; indirect: one f32 subtraction first)
-    const float directN = static_cast<float>(std::max(directSamples, 1u));
-    if (!write(directPfm, 3, [&](size_t i, uint32_t c) { return directSum[i + c] / directN; })) return 1;
-    if (!write(indirectPfm, 3, [&](size_t i, uint32_t c) { return (directAcc[i + c] - directSum[i + c]) / directN; })) return 1;
+    // (f32 divisions by the direct sample count -- with --adaptive the pixel's tile's own count --, as a caller of rf_renderer_read_direct forms them; indirect: one
+    // f32 subtraction first)
+    const auto directN = [&](size_t i) {
+        const uint32_t count = adaptive ? tileSamples[((i / 4) / W / 32) * ((W + 31) / 32) + ((i / 4) % W) / 32] : directSamples;
+        return static_cast<float>(std::max(count, 1u));
+    };
+    if (!write(directPfm, 3, [&](size_t i, uint32_t c) { return directSum[i + c] / directN(i); })) return 1;
+    if (!write(indirectPfm, 3, [&](size_t i, uint32_t c) { return (directAcc[i + c] - directSum[i + c]) / directN(i); })) return 1;
     if (!write(noiseMap, 1, [&](size_t i, uint32_t) { return errorMap[i / 4]; })) return 1;
     if (!write(trimMap, 1, [&](size_t i, uint32_t) { return static_cast<float>(robustTrim[i / 4]); })) return 1;
     if (!sampleMap.empty() && tileSamples.empty()) tileSamples.assign(static_cast<size_t>((W + 31) / 32) * ((H + 31) / 32), sppReached); // (several ranks: one count)

@@ -22,6 +22,7 @@
 static_assert(sizeof(rf_camera) == sizeof(rf::Camera));
 static_assert(RF_AOV_FIRST_HIT == rf::Renderer::kAovFirstHit);
 static_assert(RF_AOV_TILE_COUNTS == rf::Renderer::kAovTileCounts);
+static_assert(RF_DIRECT_TILE_COUNTS == rf::Renderer::kDirectTileCounts && rf::Renderer::kDirectOn == 1u);
 static_assert(RF_BUCKETS_TILE_COUNTS == rf::Renderer::kBucketsTileCounts);
 static_assert(RF_BUCKETS_SHARD_TILE_COUNTS == rf::Renderer::kBucketsShardTileCounts);
 
@@ -356,7 +357,10 @@ int rf_renderer_set_direct(rf_renderer* r, int enabled)
 {
     return guarded([&] {
         require(r, "null argument");
-        r->impl->setDirect(enabled != 0);
+        const uint32_t word = static_cast<uint32_t>(enabled);
+        require((word & ~(1u | RF_DIRECT_TILE_COUNTS)) == 0u, "unknown direct flag bits: the word is 0, 1 or 1 | RF_DIRECT_TILE_COUNTS");
+        require((word & RF_DIRECT_TILE_COUNTS) == 0u || (word & 1u) != 0u, "RF_DIRECT_TILE_COUNTS says how the direct sums are kept: valid only together with 1");
+        r->impl->setDirect(word);
         return RF_OK;
     });
 }
@@ -405,6 +409,30 @@ int rf_denoise_split_images(int32_t device_ordinal, uint32_t width, uint32_t hei
         require(samples > 0, "sample count must be > 0");
         require(std::isfinite(exposure), "exposure must be finite");
         rf::denoiseSplitImages(device_ordinal, width, height, samples, color_sum4, direct_sum4, albedo_coverage4, normal_depth4, pd, pi, exposure, out_rgba, out_bgra8);
+        return RF_OK;
+    });
+}
+
+int rf_denoise_split_tiles(int32_t device_ordinal, uint32_t width, uint32_t height, const uint32_t* tile_samples, const float* color_sum4, const float* direct_sum4,
+                           const float* albedo_coverage4, const float* normal_depth4, const rf_denoise_parameters* direct, const rf_denoise_parameters* indirect,
+                           float exposure, float* out_rgba, uint32_t* out_bgra8)
+{
+    return guarded([&] {
+        const rf::SplitDenoiseDefaults d = rf::splitDenoiseDefaults();
+        const rf::DenoiseParameters    pd = toSplitParams(direct, d.direct), pi = toSplitParams(indirect, d.indirect);
+        require(tile_samples && color_sum4 && direct_sum4 && albedo_coverage4 && normal_depth4, "null argument");
+        require(width > 0 && height > 0, "image size must be non-zero");
+        require(static_cast<uint64_t>(width) * height < (1ull << 31), "image too large");
+        const uint32_t tiles = ((width + 31u) / 32u) * ((height + 31u) / 32u);
+        uint32_t       leading = 0;
+        for (uint32_t t = 0; t < tiles; ++t)
+        {
+            require(tile_samples[t] > 0, "the sample count of every tile must be > 0");
+            leading = tile_samples[t] > leading ? tile_samples[t] : leading;
+        }
+        require(std::isfinite(exposure), "exposure must be finite");
+        rf::denoiseSplitTiles(device_ordinal, width, height, tile_samples, leading, color_sum4, direct_sum4, albedo_coverage4, normal_depth4, pd, pi, exposure, out_rgba,
+                              out_bgra8);
         return RF_OK;
     });
 }

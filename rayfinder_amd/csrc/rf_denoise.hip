@@ -9,6 +9,7 @@
 //   kDenoiseAtrous  one lane per pixel, 16x16-pixel workgroups of four 8x8-pixel waves (the 25 taps of a wave touch few cache lines); the last pass
 //                   remodulates and writes the mean
 //   kDenoisePrepSplit    the split-component filter's prep (rf_renderer_denoise_split): two demodulated irradiances, of D and of S - D, over one guide and one a + εa
+//   kDenoisePrepSplitTiles  the same with the sample count of the pixel's tile (rf_renderer_denoise_split in the non-uniform state, rf_denoise_split_tiles)
 //   kDenoiseAtrousSplit  one pass of both components at once: one guide load per tap (and one evaluation of the normal and depth terms when the components share
 //                   σn and σz), two colour terms, two accumulator sets; a component past its own iteration count is not filtered; the last pass adds the two,
 //                   remodulates and writes the mean
@@ -189,12 +190,10 @@ __global__ __launch_bounds__(kDenoiseBlock) void kDenoiseAtrous(const float4* eI
 
 // prep: c, the background test, a, n, z and a + εa exactly as prepPixel; then eD = (D.rgb / Nf) / (a + εa), eI = ((S.rgb - D.rgb) / Nf) / (a + εa), each with its own ℓ.
 // Background: eD = {c, 0}, eI = 0.  meanOut (L_D = L_I = 0): the mean c, exactly.  tilesX != 0: S, D and the AOV sums are compact tile-major; 0: row-major.
-__global__ __launch_bounds__(256) void kDenoisePrepSplit(const float4* colorSum, const float4* directSum, const float4* albedoCoverage, const float4* normalDepth, uint32_t width,
-                                                         uint32_t height, uint32_t tilesX, float nf, float4* eD, float4* eI, float4* guide, float4* albedo, float4* meanOut)
+// Pixel i = (x, y) with its sample count as a float: shared by kDenoisePrepSplit (one count for the frame) and kDenoisePrepSplitTiles (the count of the pixel's tile).
+__device__ __forceinline__ void prepSplitPixel(const float4* colorSum, const float4* directSum, const float4* albedoCoverage, const float4* normalDepth, uint32_t i, uint32_t x,
+                                               uint32_t y, uint32_t tilesX, float nf, float4* eD, float4* eI, float4* guide, float4* albedo, float4* meanOut)
 {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= width * height) return;
-    const uint32_t y = i / width, x = i - y * width;
     const uint32_t src = tilesX ? tileMajorIndex(x, y, tilesX) : i;
     const float4   S = colorSum[src];
     const Vec3     c = vec3(S.x / nf, S.y / nf, S.z / nf);
@@ -227,6 +226,28 @@ __global__ __launch_bounds__(256) void kDenoisePrepSplit(const float4* colorSum,
     eI[i] = make_float4(vI.x, vI.y, vI.z, (vI.x + vI.y) + vI.z);
     guide[i] = make_float4(n.x, n.y, n.z, z);
     albedo[i] = make_float4(ae.x, ae.y, ae.z, 0.0f);
+}
+
+__global__ __launch_bounds__(256) void kDenoisePrepSplit(const float4* colorSum, const float4* directSum, const float4* albedoCoverage, const float4* normalDepth, uint32_t width,
+                                                         uint32_t height, uint32_t tilesX, float nf, float4* eD, float4* eI, float4* guide, float4* albedo, float4* meanOut)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= width * height) return;
+    const uint32_t y = i / width, x = i - y * width;
+    prepSplitPixel(colorSum, directSum, albedoCoverage, normalDepth, i, x, y, tilesX, nf, eD, eI, guide, albedo, meanOut);
+}
+
+// The same with one sample count per 32x32 tile of the frame, for c, a, m, cD and cI alike: Nf = float(tileSamples[tile of the pixel]) as kDenoisePrepTiles takes it
+// (frameTilesX: the frame's tiles per row whatever the layout of the sums; every count is > 0).  With every count equal to N: kDenoisePrepSplit's bits.
+__global__ __launch_bounds__(256) void kDenoisePrepSplitTiles(const float4* colorSum, const float4* directSum, const float4* albedoCoverage, const float4* normalDepth,
+                                                              uint32_t width, uint32_t height, uint32_t tilesX, const uint32_t* tileSamples, uint32_t frameTilesX, float4* eD,
+                                                              float4* eI, float4* guide, float4* albedo, float4* meanOut)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= width * height) return;
+    const uint32_t y = i / width, x = i - y * width;
+    const float    nf = static_cast<float>(tileSamples[(y >> 5) * frameTilesX + (x >> 5)]);
+    prepSplitPixel(colorSum, directSum, albedoCoverage, normalDepth, i, x, y, tilesX, nf, eD, eI, guide, albedo, meanOut);
 }
 
 // one component's constants of a pass of step 2^i: sc2 = (σc σc) 2^-i, σn, szs = σz step
@@ -396,20 +417,27 @@ void enqueueDenoise(hipStream_t stream, DenoiseWork& w, const float4* colorSum, 
 SplitDenoiseDefaults splitDenoiseDefaults() { return SplitDenoiseDefaults{DenoiseParameters{1u, 0.25f, 0.1f, 0.1f}, DenoiseParameters{2u, 256.0f, 0.1f, 0.1f}}; }
 
 void enqueueDenoiseSplit(hipStream_t stream, DenoiseWork& w, const float4* colorSum, const float4* directSum, const float4* albedoCoverage, const float4* normalDepth,
-                         uint32_t width, uint32_t height, uint32_t tilesX, uint32_t samples, const DenoiseParameters& pd, const DenoiseParameters& pi, float exposure)
+                         uint32_t width, uint32_t height, uint32_t tilesX, uint32_t samples, const DenoiseParameters& pd, const DenoiseParameters& pi, float exposure,
+                         const uint32_t* tileSamples)
 {
     const uint32_t n = width * height;
     w.reserve(n, stream, true);
     const float    nf = static_cast<float>(samples);
     const dim3     prepGrid((n + 255) / 256);
     const uint32_t passes = std::max(pd.iterations, pi.iterations);
-    if (passes == 0)
-        hipLaunchKernelGGL(kDenoisePrepSplit, prepGrid, dim3(256), 0, stream, colorSum, directSum, albedoCoverage, normalDepth, width, height, tilesX, nf,
-                           static_cast<float4*>(nullptr), static_cast<float4*>(nullptr), static_cast<float4*>(nullptr), static_cast<float4*>(nullptr), w.out.ptr);
+    // prep into (eD, eI, guide, albedo), or for L_D = L_I = 0 into the mean: with the frame's one count, or with each pixel's tile's own
+    const auto prep = [&](float4* eD, float4* eI, float4* guide, float4* albedo, float4* meanOut) {
+        if (tileSamples)
+            hipLaunchKernelGGL(kDenoisePrepSplitTiles, prepGrid, dim3(256), 0, stream, colorSum, directSum, albedoCoverage, normalDepth, width, height, tilesX, tileSamples,
+                               TileGrid(width, height).tilesX, eD, eI, guide, albedo, meanOut);
+        else
+            hipLaunchKernelGGL(kDenoisePrepSplit, prepGrid, dim3(256), 0, stream, colorSum, directSum, albedoCoverage, normalDepth, width, height, tilesX, nf, eD, eI, guide,
+                               albedo, meanOut);
+    };
+    if (passes == 0) prep(nullptr, nullptr, nullptr, nullptr, w.out.ptr);
     else
     {
-        hipLaunchKernelGGL(kDenoisePrepSplit, prepGrid, dim3(256), 0, stream, colorSum, directSum, albedoCoverage, normalDepth, width, height, tilesX, nf, w.e[0].ptr,
-                           w.eI[0].ptr, w.guide.ptr, w.albedo.ptr, static_cast<float4*>(nullptr));
+        prep(w.e[0].ptr, w.eI[0].ptr, w.guide.ptr, w.albedo.ptr, nullptr);
         const dim3 grid((width + 15) / 16, (height + 15) / 16);
         uint32_t   curD = 0, curI = 0; // which of its two buffers holds each component's current value
         for (uint32_t i = 0; i < passes; ++i)
@@ -437,20 +465,34 @@ void enqueueDenoiseSplit(hipStream_t stream, DenoiseWork& w, const float4* color
 void denoiseSplitImages(int deviceOrdinal, uint32_t width, uint32_t height, uint32_t samples, const float* colorSum, const float* directSum, const float* albedoCoverage,
                         const float* normalDepth, const DenoiseParameters& direct, const DenoiseParameters& indirect, float exposure, float* outRgba, uint32_t* outBgra8)
 {
+    denoiseSplitTiles(deviceOrdinal, width, height, nullptr, samples, colorSum, directSum, albedoCoverage, normalDepth, direct, indirect, exposure, outRgba, outBgra8);
+}
+
+void denoiseSplitTiles(int deviceOrdinal, uint32_t width, uint32_t height, const uint32_t* tileSamples, uint32_t samples, const float* colorSum, const float* directSum,
+                       const float* albedoCoverage, const float* normalDepth, const DenoiseParameters& direct, const DenoiseParameters& indirect, float exposure,
+                       float* outRgba, uint32_t* outBgra8)
+{
     requireDevice(deviceOrdinal);
     const uint64_t n = static_cast<uint64_t>(width) * height;
+    const uint32_t tiles = TileGrid(width, height).count();
     // (leaving the scope: the stream is synchronised, the buffers are freed, the stream is destroyed -- ScopedStream)
-    ScopedStream         stream;
-    DeviceBuffer<float4> in[4];
-    DenoiseWork          work;
-    ScopedStream::Drain  drain{stream};
-    const float*         src[4] = {colorSum, directSum, albedoCoverage, normalDepth};
+    ScopedStream           stream;
+    DeviceBuffer<float4>   in[4];
+    DeviceBuffer<uint32_t> counts;
+    DenoiseWork            work;
+    ScopedStream::Drain    drain{stream};
+    if (tileSamples)
+    {
+        counts.alloc(tiles);
+        RF_HIP(hipMemcpyAsync(counts.ptr, tileSamples, tiles * sizeof(uint32_t), hipMemcpyHostToDevice, stream.handle));
+    }
+    const float*           src[4] = {colorSum, directSum, albedoCoverage, normalDepth};
     for (int b = 0; b < 4; ++b)
     {
         in[b].alloc(n);
         RF_HIP(hipMemcpyAsync(in[b].ptr, src[b], n * sizeof(float4), hipMemcpyHostToDevice, stream.handle));
     }
-    enqueueDenoiseSplit(stream.handle, work, in[0].ptr, in[1].ptr, in[2].ptr, in[3].ptr, width, height, 0u, samples, direct, indirect, exposure);
+    enqueueDenoiseSplit(stream.handle, work, in[0].ptr, in[1].ptr, in[2].ptr, in[3].ptr, width, height, 0u, samples, direct, indirect, exposure, counts.ptr);
     if (outRgba) RF_HIP(hipMemcpyAsync(outRgba, work.out.ptr, n * sizeof(float4), hipMemcpyDeviceToHost, stream.handle));
     if (outBgra8) RF_HIP(hipMemcpyAsync(outBgra8, work.bgra.ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream.handle));
     RF_HIP(hipStreamSynchronize(stream.handle));

@@ -38,7 +38,8 @@ void enqueueDenoise(hipStream_t stream, DenoiseWork& work, const float4* colorSu
 
 // The split-component filter (rf_renderer_denoise_split): kDenoisePrepSplit, max(L_D, L_I) kDenoiseAtrousSplit passes -- the last one adds the components and
 // remodulates -- and kTonemap on `stream`; the result in work.out / work.bgra as enqueueDenoise leaves it.  directSum: D, laid out like colorSum.  tilesX as above.
+// tileSamples as above: prep divides S, D and the AOV sums of each pixel by its tile's count (kDenoisePrepSplitTiles) and `samples` is not used.
 void enqueueDenoiseSplit(hipStream_t stream, DenoiseWork& work, const float4* colorSum, const float4* directSum, const float4* albedoCoverage, const float4* normalDepth,
                          uint32_t width, uint32_t height, uint32_t tilesX, uint32_t samples, const DenoiseParameters& direct, const DenoiseParameters& indirect,
-                         float exposure);
+                         float exposure, const uint32_t* tileSamples = nullptr);
 } // namespace rf

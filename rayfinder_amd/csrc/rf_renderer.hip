@@ -205,6 +205,8 @@ struct Renderer::Impl
     // direct radiance sums (rf_renderer_set_direct; off by default: nothing is allocated or launched then): D = the sum of each sample's radiance as it stands after
     // bounce 1 (the primary miss's sky term, or the first hit's sun term times its visibility), in the image's layout and the image's order
     SumChannel              directSums{false, 1};
+    uint32_t                directFlags = 0; // the word as set (rf_renderer_set_direct): kDirectOn says that D is kept (directSums.on), kDirectTileCounts how
+    bool                    directTileCounts() const { return (directFlags & kDirectTileCounts) != 0u; }
     float4*                 direct() const { return directSums.buffers[0].ptr; }
     // bucket sums (rf_renderer_set_buckets; off by default: nothing is allocated or launched then): bucketSums.planes = K planes of the shard's tiles x 1024 float4 each
     // in one buffer, plane b = the radiance sum over the samples of ordinal b mod K (under render_adaptive, bucketTileCounts: of the TILE's samples -- every active tile
@@ -1153,8 +1155,8 @@ struct Renderer::Impl
     }
 
     // The direct sums (rf_renderer_set_direct), enqueued right behind bounce 1's launch groups: ps.rad then holds each sample's direct light, and D gets it through the
-    // accumulate kernel the plan chose for the batch's image -- the same ordered chain, whatever the batch depth or slot order.  Never under a tile list: render_adaptive
-    // is refused while the direct sums are on (checkAdaptive).
+    // accumulate kernel the plan chose for the batch's image -- the same ordered chain, whatever the batch depth or slot order.  Under a tile list (render_adaptive
+    // with kDirectTileCounts; checkAdaptive refuses the call without the bit) the list-addressed radiance sum, staged or one lane per pixel as the batch's other sums are.
     void enqueueDirect(const BatchPlan& b, const FrameParams& fp, const PathStreams& ps)
     {
         const auto sumGrid = [&](uint32_t pixelsPerGroup) { return dim3((fp.pixelsPadded + pixelsPerGroup - 1) / pixelsPerGroup); };
@@ -1164,7 +1166,9 @@ struct Renderer::Impl
         else if (b.accumulateKernel == kAccumulatePixels)
             hipLaunchKernelGGL(sumKernel(Sum::Radiance, false, SumAddressing::Compact), sumGrid(b.accumulatePixels), dim3(static_cast<uint32_t>(kBlock)), 0, stream, fp, tileIds.ptr,
                                static_cast<const float4*>(ps.rad), direct(), static_cast<float4*>(nullptr));
-        else throw std::logic_error("the direct sums have no tile-list kernel");
+        else
+            hipLaunchKernelGGL(sumKernel(Sum::Radiance, b.runs, b.shardList ? SumAddressing::ShardList : SumAddressing::TileList), sumGrid(b.accumulatePixels),
+                               dim3(b.runs ? 64u : static_cast<uint32_t>(kBlock)), 0, stream, fp, tileIds.ptr, static_cast<const float4*>(ps.rad), direct(), static_cast<float4*>(nullptr));
     }
 
     // Trace `numSamples` consecutive samples (sample indices start at frame `firstFrame`) of the shard's tiles -- or, active != nullptr, of the tile list that
@@ -1764,20 +1768,27 @@ void Renderer::readMoments(float* sumSq, uint32_t* sampleCount)
     if (sampleCount) *sampleCount = empty ? 0u : m.momentSums.samples;
 }
 
-void Renderer::setDirect(bool enabled)
+void Renderer::setDirect(uint32_t flags)
 {
     Impl& m = *mImpl;
+    if ((flags & ~(kDirectOn | kDirectTileCounts)) != 0u || flags == kDirectTileCounts)
+        throw std::invalid_argument("set_direct: the word must be 0 (off), 1 (on) or 1 | RF_DIRECT_TILE_COUNTS (the bit says how D is kept: valid only together with 1)");
+    const bool enabled = (flags & kDirectOn) != 0u;
+    // (with the bit too: D must hold every tile's samples from the tile's first one on, and the tiles below the leading count get no more)
     if (enabled) m.requireUniform("rf_renderer_set_direct", ": the direct sums keep ONE sample count for the frame");
-    if (enabled == m.directSums.on) return;
+    if (flags == m.directFlags) return;
     RF_HIP(hipSetDevice(m.device));
     RF_HIP(hipStreamSynchronize(m.stream)); // (a batch in flight may still write the sums)
+    // any change of the value restarts the sums, kDirectOn <-> kDirectOn | kDirectTileCounts included (the buffer stays: it is the same one either way)
+    m.directFlags = flags;
     m.directSums.on = enabled;
     m.restartDirect();
     // off: nothing of the direct sums stays allocated
     if (!enabled) m.directSums.release();
 }
 
-bool Renderer::directEnabled() const { return mImpl->directSums.on; }
+bool     Renderer::directEnabled() const { return mImpl->directSums.on; }
+uint32_t Renderer::directFlags() const { return mImpl->directFlags; }
 
 void Renderer::readDirect(float* directSum, uint32_t* sampleCount)
 {
@@ -1791,7 +1802,13 @@ void Renderer::readDirect(float* directSum, uint32_t* sampleCount)
 void Renderer::denoiseSplit(const DenoiseParameters& direct, const DenoiseParameters& indirect)
 {
     Impl& m = *mImpl;
-    m.requireUniform("rf_renderer_denoise_split");
+    // the non-uniform state: prep divides each pixel by its tile's own count, which D and the AOV sums must both have been kept for, from the first sample on
+    const bool perTile = m.nonUniform();
+    if (perTile && !(m.directSums.on && m.directTileCounts() && m.directSums.covers(m.accumulated) && m.aovSums.on && m.aovTileCounts() && m.aovSums.covers(m.accumulated)))
+        m.requireUniform("rf_renderer_denoise_split", ", and the direct sums and the first-hit AOVs were not both kept with per-tile counts for the whole accumulation: set "
+                                                      "1 | RF_DIRECT_TILE_COUNTS (rf_renderer_set_direct) and RF_AOV_FIRST_HIT | RF_AOV_TILE_COUNTS (rf_renderer_set_aovs) "
+                                                      "before the first sample and rf_renderer_denoise_split runs in this state");
+    if (!perTile) m.requireUniform("rf_renderer_denoise_split");
     if (!m.aovSums.on) throw std::invalid_argument("denoise_split needs the first-hit AOVs: turn them on (rf_renderer_set_aovs) before the first sample");
     if (!m.directSums.on) throw std::invalid_argument("denoise_split needs the direct sums: turn them on (rf_renderer_set_direct) before the first sample");
     if (m.worldSize != 1u) throw std::invalid_argument("denoise_split needs the whole frame: a tile shard is set (use rf_denoise_split_images on the sum of the ranks' reads)");
@@ -1803,8 +1820,9 @@ void Renderer::denoiseSplit(const DenoiseParameters& direct, const DenoiseParame
         throw std::invalid_argument("denoise_split: the direct sample count (" + std::to_string(m.directSums.samples) + ") differs from the accumulated sample count (" +
                                     std::to_string(m.accumulated) + "): turn the direct sums on before the first sample");
     RF_HIP(hipSetDevice(m.device));
+    // (per tile: the call first waits for the stream and copies the counts to the device; the snapshot's sample count is the leading count)
     enqueueDenoiseSplit(m.stream, m.denoiseWork, m.image, m.direct(), m.aovAlbedoCoverage(), m.aovNormalDepth(), m.params.width, m.params.height, m.grid().tilesX, m.accumulated,
-                        direct, indirect, m.params.exposure);
+                        direct, indirect, m.params.exposure, perTile ? m.uploadTileSamples() : nullptr);
     m.denoisedValid = true;
     m.denoisedSamples = m.accumulated;
 }
@@ -1949,7 +1967,7 @@ NoiseEstimate Renderer::noiseEstimate(float* errorMap, float* tileSum, float* ti
 void Renderer::checkAdaptive(const AdaptiveParameters& p, bool sharded) const
 {
     const Impl& m = *mImpl;
-    if (m.directSums.on)
+    if (m.directSums.on && !m.directTileCounts())
         throw std::invalid_argument("render_adaptive: the direct sums are on (rf_renderer_set_direct), and they keep ONE sample count for the frame: turn them off "
                                     "(rf_renderer_set_direct(r, 0)) before sampling adaptively");
     if (m.bucketSums.on && m.bucketTileCounts && sharded && !m.bucketShardTileCounts)
@@ -1970,13 +1988,15 @@ void Renderer::checkAdaptive(const AdaptiveParameters& p, bool sharded) const
         throw std::invalid_argument("render_adaptive: the AOV sample count does not cover the accumulation (the AOVs were turned on partway through): restart the accumulation first");
     if (m.bucketSums.on && m.accumulated != 0u && !m.bucketSums.covers(m.accumulated))
         throw std::invalid_argument("render_adaptive: the bucket sample count does not cover the accumulation (the buckets were turned on partway through): restart the accumulation first");
+    if (m.directSums.on && m.accumulated != 0u && !m.directSums.covers(m.accumulated))
+        throw std::invalid_argument("render_adaptive: the direct sample count does not cover the accumulation (the direct sums were turned on partway through): restart the accumulation first");
 }
 
 AdaptiveResult Renderer::renderAdaptive(const AdaptiveParameters& p)
 {
     Impl& m = *mImpl;
     // (the order of the checks, and so which message a call with several faults gets, is the one this call always had)
-    if (m.directSums.on || (m.bucketSums.on && !m.bucketTileCounts) || !m.momentSums.on || (m.aovSums.on && !m.aovTileCounts())) checkAdaptive(p);
+    if ((m.directSums.on && !m.directTileCounts()) || (m.bucketSums.on && !m.bucketTileCounts) || !m.momentSums.on || (m.aovSums.on && !m.aovTileCounts())) checkAdaptive(p);
     if (m.worldSize != 1u) throw std::invalid_argument("render_adaptive needs the whole frame: a tile shard is set (rf_comm_render_adaptive samples a sharded frame adaptively)");
     checkAdaptive(p);
     return renderAdaptiveFrom(p, m.accumulated, false);
@@ -2161,7 +2181,7 @@ Renderer::ShardSums Renderer::shardSums() const
     if (m.frameLeadingSamples != 0u) least = m.frameMinTileSamples;
     else if (m.nonUniform()) least = *std::min_element(m.tileSamples.begin(), m.tileSamples.end());
     return ShardSums{{m.image, m.aovAlbedoCoverage(), m.aovNormalDepth(), m.moments()}, channel(m.aovSums), channel(m.momentSums), m.accumulated, !m.tiles.empty(),
-                     channel(m.bucketSums), buckets(), m.bucketSums.on && m.bucketShardTileCounts, least};
+                     channel(m.bucketSums), buckets(), m.bucketSums.on && m.bucketShardTileCounts, least, channel(m.directSums), m.directSums.on && m.directTileCounts()};
 }
 
 const void* Renderer::enqueueShardRobustMean(const uint32_t* slotCounts)

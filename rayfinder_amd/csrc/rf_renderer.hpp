@@ -161,6 +161,11 @@ struct SplitDenoiseDefaults
 SplitDenoiseDefaults splitDenoiseDefaults();
 void denoiseSplitImages(int deviceOrdinal, uint32_t width, uint32_t height, uint32_t samples, const float* colorSum, const float* directSum, const float* albedoCoverage,
                         const float* normalDepth, const DenoiseParameters& direct, const DenoiseParameters& indirect, float exposure, float* outRgba, uint32_t* outBgra8);
+// The same with one sample count per tile of the 32 x 32 grid (tileSamples[t] > 0, as denoiseTiles takes them): prep's Nf = float(tileSamples[t]) for S, D and the AOV
+// sums of the pixels of tile t.  tileSamples == nullptr: `samples` for every tile.
+void denoiseSplitTiles(int deviceOrdinal, uint32_t width, uint32_t height, const uint32_t* tileSamples, uint32_t samples, const float* colorSum, const float* directSum,
+                       const float* albedoCoverage, const float* normalDepth, const DenoiseParameters& direct, const DenoiseParameters& indirect, float exposure,
+                       float* outRgba, uint32_t* outBgra8);
 
 // The firefly-robust mean (rf_robust.hip; the definition: include/rayfinder_amd.h) over host-assembled bucket planes -- K x width*height*4 floats, plane after plane,
 // each row-major -- of `samples` >= K samples, on device `deviceOrdinal`: the mean RGBA (.w = 1), its BGRA8 under `exposure` and the trim count of every pixel
@@ -263,14 +268,21 @@ public:
     // Direct radiance sums (rf_renderer_set_direct / rf_renderer_read_direct): off by default.  While on, one more compact tile-major float4 buffer holds D = the sum, in
     // sample order, of each sample's radiance as it stands after bounce 1 -- what the image of a handle with numBounces = 1 holds, bit for bit -- over the samples traced
     // since it was last cleared (with the image, or when the switch changes).  Indirect light is S - D, formed by whoever needs it.  One more launch per batch, behind
-    // bounce 1's shadow launch.  While on, renderAdaptive / checkAdaptive refuse; turning it on is refused in the non-uniform state.
-    // Read: row-major width*height*4 floats (this rank's pixels; NULL = skip) and the direct sample count.
-    void     setDirect(bool enabled);
+    // bounce 1's shadow launch.  The word is 0 = off, kDirectOn = on, kDirectOn | kDirectTileCounts = on and kept per tile count under renderAdaptive /
+    // renderAdaptiveFrom (until one of them is called: exactly kDirectOn): D of tile t is then that of its first tileSamples[t] samples, as S and Q are, added through
+    // the tile list's radiance-sum kernels (rf_sums.hpp).  Without the bit renderAdaptive / checkAdaptive refuse while D is on.  Any change of the word clears D and
+    // drops a split-denoised snapshot; turning D on is refused in the non-uniform state, with or without the bit.  std::invalid_argument for any other word.
+    // Read: row-major width*height*4 floats (this rank's pixels; NULL = skip) and the direct sample count (the non-uniform state: the leading count).
+    static constexpr uint32_t kDirectOn = 1u, kDirectTileCounts = 0x100u;
+    void     setDirect(uint32_t flags);
     bool     directEnabled() const;
+    uint32_t directFlags() const;
     void     readDirect(float* directSum, uint32_t* sampleCount);
     // The split-component denoiser (rf_renderer_denoise_split; the arithmetic: include/rayfinder_amd.h): D and S - D demodulated and filtered separately, each with its
-    // own parameters, and recombined; the result is denoise's snapshot (readDenoised).  std::invalid_argument in the non-uniform state, when the AOVs or the direct sums
-    // are off or do not cover the accumulation, nothing is accumulated or a tile shard is set.
+    // own parameters, and recombined; the result is denoise's snapshot (readDenoised).  std::invalid_argument when the AOVs or the direct sums are off or do not cover
+    // the accumulation, nothing is accumulated or a tile shard is set.  In the non-uniform state it runs when D carries kDirectTileCounts, the AOVs carry kAovTileCounts
+    // and both cover the accumulation (prep then divides each pixel by its tile's count; the snapshot's count is the leading count; the call first waits for the
+    // stream and copies the counts to the device), and refuses as requireUniformTileSamples does otherwise -- before any other check.
     void denoiseSplit(const DenoiseParameters& direct, const DenoiseParameters& indirect);
     // Bucket sums (rf_renderer_set_buckets / rf_renderer_read_buckets): K = 0 off (the default), else odd, 3 .. 15.  While on, K more compact tile-major float4 planes
     // in one allocation: plane b holds {sum r.x, sum r.y, sum r.z, 0} over the samples whose ordinal -- the bucket sample count just before the sample -- is b mod K,
@@ -310,8 +322,9 @@ public:
     // unless the AOVs were kept with kAovTileCounts; the reads report the leading count, and readTileSamples / readMean / readTonemapped / noiseEstimate / denoise honour
     // the per-tile counts.  With kAovFirstHit | kAovTileCounts the AOV sums of tile t are those of its first tileSamples[t] samples, as S and Q are.
     // With K | kBucketsTileCounts the bucket planes of tile t are those of its first tileSamples[t] samples too, and robustMean / denoiseRobust honour the counts.
+    // With kDirectOn | kDirectTileCounts so is D of tile t, and denoiseSplit honours the counts (given the AOVs' bit as well).
     // std::invalid_argument when the moments are off or do not cover the accumulation, the AOVs are on without kAovTileCounts or do not cover it, the buckets are on
-    // without kBucketsTileCounts or do not cover it, a tile shard is set,
+    // without kBucketsTileCounts or do not cover it, the direct sums are on without kDirectTileCounts or do not cover it, a tile shard is set,
     // checkEvery is 0 or the target is negative or not finite.
     AdaptiveResult renderAdaptive(const AdaptiveParameters& params);
     // The same over a tile shard, one rank's part of rf_comm_render_adaptive (renderAdaptive of rf_comm.hpp makes the exchanges around it).  checkAdaptive: renderAdaptive's
@@ -360,6 +373,8 @@ public:
         // the smallest tile count known to the rank: the frame's minimum after rf_comm_render_adaptive (the same on every rank, one without a tile too), else the
         // smallest of the rank's own tiles (no tile: the accumulated count)
         uint32_t    minTileSamples;
+        Channel     direct;           // the direct sums: on, covering the accumulation, their own sample count (the frame gather does not carry D)
+        bool        directTileCounts; // D carries kDirectTileCounts: it follows the per-slot counts under rf_comm_render_adaptive
     };
     ShardSums shardSums() const;
     // The robust mean of the shard's own pixels, for the frame gather (rf_comm.hpp: plane 4): kRobustMeanShard over the shard-compact bucket planes with the accumulated

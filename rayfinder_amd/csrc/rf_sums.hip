@@ -42,9 +42,14 @@ __device__ __forceinline__ float* sumFloat(float4* dst0, float4* dst1, size_t at
 // kSumRuns' loading lanes stage in LDS --; term(v, i) is what a value adds to the channel's running sum i < kTerms; kRunPixels x kChannels <= 64 summing lanes.
 // kTestPerRound: kSumRuns takes the sample-in-chunk test and the permutation entry in every load round (true) or once per chunk (false): each sum keeps the form it was
 // measured with.
-struct RadianceSum // S += r.  One lane per pixel only (no kRunPixels / kChunk): its staged kernel is kAccumulateRuns
-{
-    static constexpr uint32_t kChannels = 3, kRecords = 1, kTerms = 1;
+struct RadianceSum // S += r.  Shard-compact: one lane per pixel only (its staged kernel there is kAccumulateRuns); under a tile list (the direct sums D of
+{                  // rf_renderer_set_direct with RF_DIRECT_TILE_COUNTS) both forms, the staged one with MomentSum's constants
+    static constexpr uint32_t kChannels = 3, kRecords = 1, kTerms = 1, kRunPixels = kMomentPixels, kChunk = kMomentChunk;
+#if defined(RF_EXP_DIRECT_TEST_PER_ROUND) // (the A/B of profiles/direct_adaptive: the test and the permutation entry in every load round measured 122 us against 90)
+    static constexpr bool     kTestPerRound = true;
+#else
+    static constexpr bool     kTestPerRound = false;
+#endif
     __device__ static __forceinline__ void values(const float4* rec, float (&v)[4])
     {
         const float4 r = *rec;
@@ -331,9 +336,11 @@ SumKernel sumKernel(Sum sum, bool runs, SumAddressing addressing)
     {
         if (sum == Sum::RadianceMoments) return runs ? kSumRuns<ShardList<RadianceMomentSum>, true> : kSumPixels<ShardList<RadianceMomentSum>, true>;
         if (sum == Sum::Aov) return runs ? kSumRuns<ShardList<AovSum>, true> : kSumPixels<ShardList<AovSum>, true>;
+        if (sum == Sum::Radiance) return runs ? kSumRuns<ShardList<RadianceSum>, true> : kSumPixels<ShardList<RadianceSum>, true>;
         throw std::logic_error("sumKernel: no such kernel is compiled");
     }
     if (sum == Sum::Radiance && !runs && !tileList) return kSumPixels<RadianceSum, false>;
+    if (sum == Sum::Radiance && tileList) return runs ? kSumRuns<RadianceSum, true> : kSumPixels<RadianceSum, true>;
     if (sum == Sum::Moments && !tileList) return runs ? kSumRuns<MomentSum, false> : kSumPixels<MomentSum, false>;
     if (sum == Sum::RadianceMoments && tileList) return runs ? kSumRuns<RadianceMomentSum, true> : kSumPixels<RadianceMomentSum, true>;
     if (sum == Sum::Aov && tileList) return runs ? kSumRuns<AovSum, true> : kSumPixels<AovSum, true>;

@@ -28,7 +28,8 @@ using SumKernel = void (*)(FrameParams fp, const uint32_t* tileIds, const float4
 // pixels, their runs staged in chunks of 32 samples: (pixels x channels) rows of (32 + 1) floats = 6 336 B / 8 448 B of LDS at any batch depth (<= ~8 KB keeps twenty
 // workgroups resident per CU, profiles/r06_raygen).  Else one lane per pixel, kBlock pixels per workgroup, any slot order.
 // Compiled: Radiance (one lane per pixel; its staged kernel is accumulateRunsKernel) and Moments with shard-compact addressing, RadianceMoments with a tile list, Aov
-// with both, RadianceMoments and Aov with a shard's slot list; anything else throws.
+// with both, RadianceMoments and Aov with a shard's slot list; Radiance with a tile list and with a shard's slot list in both forms (the direct sums D under
+// RF_DIRECT_TILE_COUNTS: the staged form takes kMomentPixels pixels in chunks of kMomentChunk, 6 336 B of LDS); anything else throws.
 constexpr uint32_t kMomentPixels = 16, kMomentChunk = 32;
 constexpr uint32_t kAovPixels = 8, kAovChunk = 32;
 enum class SumAddressing : uint32_t
