@@ -273,7 +273,7 @@ RF_API int rf_denoise_tiles(int32_t device_ordinal, uint32_t width, uint32_t hei
  * while it was on -- and is cleared, with the count set to 0, when the image is (a change through rf_renderer_set_render_parameters, a new tile shard, a newly bound
  * accumulation buffer) and when the switch changes.  Turned on partway through an accumulation, D covers only the later samples.
  * While on with plain 1, rf_renderer_render_adaptive and rf_comm_render_adaptive return RF_ERROR_INVALID_ARGUMENT (the message names the direct sums) before anything
- * is traced or exchanged, the state kept; turning D on, in either form, is refused in the non-uniform state.  rf_renderer_gather_frame does not carry D.
+ * is traced or exchanged, the state kept; turning D on, in either form, is refused in the non-uniform state.  rf_renderer_gather_frame carries D with RF_GATHER_DIRECT (DIRECT SUMS ACROSS RANKS, below).
  * The argument's domain is checked (until RF_DIRECT_TILE_COUNTS was added any non-zero value meant "on"): 0, 1 and 1 | RF_DIRECT_TILE_COUNTS; the bit alone and any
  * other bit are RF_ERROR_INVALID_ARGUMENT, the state kept.
  * rf_renderer_set_direct(r, 1 | RF_DIRECT_TILE_COUNTS) opts in to per-tile counts, as RF_AOV_TILE_COUNTS does for the AOV sums.  Until rf_renderer_render_adaptive or
@@ -286,8 +286,9 @@ RF_API int rf_denoise_tiles(int32_t device_ordinal, uint32_t width, uint32_t hei
  * split-denoised snapshot, 1 <-> 1 | RF_DIRECT_TILE_COUNTS included.  In the non-uniform state rf_renderer_read_direct returns the sums as they are and the leading
  * count L; a pixel's divisor is its tile's count (rf_renderer_read_tile_samples).
  * Across ranks the one bit covers rf_comm_render_adaptive too (D is shard-compact and addressed through the shard's slot list): afterwards the sum of the ranks'
- * rf_renderer_read_direct is the whole-frame handle's D, bit for bit.  NOT covered: the frame gather still does not carry D, and there is no root-side
- * rf_comm_denoise_split -- the ranks' reads are summed on the host and handed to rf_denoise_split_tiles with the gathered counts.
+ * rf_renderer_read_direct is the whole-frame handle's D, bit for bit.  The frame gather carries D with RF_GATHER_DIRECT, per tile count together with
+ * RF_GATHER_TILE_COUNTS, and rf_comm_denoise_split / rf_comm_read_split then run on the root over the gathered sums (DIRECT SUMS ACROSS RANKS, below).  NOT covered:
+ * `rf-render --gpus N --direct / --indirect / --denoise-split` stays refused; lifting that is the follow-up.
  * rf_renderer_read_direct: row-major width*height*4 floats (the layout of rf_renderer_read_accumulation; may be NULL) and the direct sample count.  With a tile shard
  * set, this rank's pixels and zeros elsewhere: the sum of the ranks' reads is the whole frame.
  *
@@ -656,12 +657,12 @@ RF_API int rf_renderer_bind_accumulation_buffer(rf_renderer* r, void* device_ptr
  *
  * PLANES.  The exchange can carry every per-pixel sum the handle keeps, in the same single group of sends and receives.  The sums are numbered in a fixed order:
  * plane 0 = S (the image, always carried), 1 = AC = {albedo.rgb, coverage}, 2 = ND = {normal.xyz, depth} (both with RF_GATHER_AOVS), 3 = Q, the radiance second
- * moments (RF_GATHER_MOMENTS), 4 = {M.rgb, float(c)}, the robust mean of the rank's own pixels (RF_GATHER_ROBUST_MEAN; no sum: ROBUST MEAN ACROSS RANKS, below).  A gather carries plane 0 and the planes its flags ask for, in that order: the plan is the one-plane plan once per carried plane
+ * moments (RF_GATHER_MOMENTS), 4 = {M.rgb, float(c)}, the robust mean of the rank's own pixels (RF_GATHER_ROBUST_MEAN; no sum: ROBUST MEAN ACROSS RANKS, below), 5 = D, the direct radiance sums (RF_GATHER_DIRECT: DIRECT SUMS ACROSS RANKS, below).  The sum planes are 0, 1, 2, 3 and 5.  A gather carries plane 0 and the planes its flags ask for, in that order: the plan is the one-plane plan once per carried plane
  * (rf_gather_plan_planes) -- on the root, for each plane in order, the receives of that plane in rank order; on a sender, its sends in plane order; per (source,
  * destination) pair the k-th send meets the k-th receive.  On the root every plane has its own staging area (rf_gather_layout; the areas lie one after another in one
- * allocation) and its own row-major width*height float4 image, and ONE kernel un-tiles all carried planes 0 .. 3 (plane 4 has a launch of its own behind it, which
+ * allocation) and its own row-major width*height float4 image, and ONE kernel un-tiles all carried sum planes, D included (plane 4 has a launch of its own behind it, which
  * splits it into M and the trim image).  With neither flag a gather enqueues exactly what it
- * always did, and without RF_GATHER_ROBUST_MEAN exactly what it did before that flag existed, and rf_comm_last_exchange_ms brackets the whole exchange, the un-tile included, either way.
+ * always did, and without RF_GATHER_ROBUST_MEAN or RF_GATHER_DIRECT exactly what it did before that flag existed, and rf_comm_last_exchange_ms brackets the whole exchange, the un-tile included, either way.
  * RF_GATHER_AOVS is refused with RF_ERROR_INVALID_ARGUMENT -- the state kept, nothing enqueued on this rank -- when the AOVs are off, when the AOV sample count
  * differs from the accumulated count (AOVs turned on partway through) or when no sample has been accumulated; RF_GATHER_MOMENTS likewise for the moments.  (A rank
  * whose shard holds no tile -- more ranks than tiles -- sends nothing, and only the switch is checked on it.)  The refusal of the non-uniform state of
@@ -705,7 +706,7 @@ RF_API int rf_renderer_bind_accumulation_buffer(rf_renderer* r, void* device_ptr
  * first); without the bit (the refusal above, word for word); when the buckets do not cover the accumulation; when the smallest count known to the rank is below K
  * (the message names K and that count) -- after rf_comm_render_adaptive that is the FRAME's smallest count, which every rank holds, so all ranks are refused alike and
  * no peer waits; otherwise the smallest of the rank's own tiles (a whole-frame handle at world size 1 after rf_renderer_render_adaptive).
- * rf_comm_gathered_planes reports the flag.  rf_comm_read_plane and rf_comm_plane_device stay 0 .. 3: plane 4 is read through
+ * rf_comm_gathered_planes reports the flag.  rf_comm_read_plane and rf_comm_plane_device serve the sum planes alone (0 .. 3 and 5): plane 4 is read through
  * rf_comm_read_robust_mean(c, r, rgba, bgra8, trim, K, sample_count): row-major width*height*4 floats {M.rgb, 1}, BGRA8 texels (kTonemap over M with
  * accumulatedSamples = 1 and the exposure of the handle passed in, enqueued on that handle's stream and waited for), one trim byte per pixel, the K of the combine and
  * sample_count = the N the gather recorded (rf_comm_gathered_planes' N: 0 on a root whose shard holds no tile, unless the counts travelled).  Any pointer may be NULL.
@@ -715,11 +716,37 @@ RF_API int rf_renderer_bind_accumulation_buffer(rf_renderer* r, void* device_ptr
  * Out of scope: `rf-render --gpus N --buckets` and `rf-render --gpus N --adaptive` stay refused; raw bucket planes are not gathered (every rank's
  * rf_renderer_read_buckets is still the way to them).
  *
+ * DIRECT SUMS ACROSS RANKS.  With RF_GATHER_DIRECT the gather carries D (rf_renderer_set_direct) as plane 5: a sum plane like planes 0 .. 3, the rank's
+ * shard-compact tile-major float4 buffer on the wire, in the same one group, behind plane 4 when both travel and in front of the counts.  On the root it has its own
+ * staging area and its own row-major image, un-tiled by the sum planes' one launch as one more plane of it.  The flag combines with every other flag,
+ * RF_GATHER_LOOPBACK included; without it a gather posts and enqueues exactly what it did before the flag existed.
+ * DEFINING PROPERTY.  After the same samples, plane 5 on the root is bit for bit what one handle without a tile shard reads through rf_renderer_read_direct;
+ * rf_comm_read_denoised after rf_comm_denoise_split is bit for bit that handle's rf_renderer_read_denoised after rf_renderer_denoise_split with the same parameters;
+ * planes 0 .. 4 and every other root-side call of the same gather are what they are without the flag.
+ * Refused with RF_ERROR_INVALID_ARGUMENT -- every check before anything is enqueued or cleared, the state kept, as for RF_GATHER_AOVS: when the direct sums are
+ * off; when no sample has been accumulated; when the direct sample count differs from the accumulated count (D turned on partway through; the message names both).  A
+ * rank whose shard holds no tile checks only the switch and sends nothing.  In the NON-UNIFORM state the refusal of a gather without RF_GATHER_TILE_COUNTS comes
+ * first, as ever; with the counts, D must carry RF_DIRECT_TILE_COUNTS (the message names the bit) -- the adaptive calls refuse plain 1 in the first place.
+ * On the root, after such a gather:
+ *   rf_comm_read_plane / rf_comm_plane_device serve plane 5 (plane 4 stays "plane out of range": it is read through rf_comm_read_robust_mean; planes >= 6 do not
+ *   exist); after a gather without the flag plane 5 is refused with a message that names RF_GATHER_DIRECT.  rf_comm_gathered_planes reports the flag.
+ *   rf_comm_denoise_split(c, r, direct, indirect): the split-component denoiser (the definition above) enqueued on the handle's stream over the gathered S, D, AC and
+ *   ND where they lie; needs RF_GATHER_AOVS | RF_GATHER_DIRECT (the message names what is missing); a NULL parameter set = that component's default; each tile with
+ *   its own count when the gather carried RF_GATHER_TILE_COUNTS (rf_denoise_split_tiles' filter); refused as rf_comm_denoise is (N = 0, a tile without a sample, bad
+ *   parameters).  The result is the comm's one denoise snapshot, read with rf_comm_read_denoised: of rf_comm_denoise, rf_comm_denoise_robust and this call the last
+ *   one wins, and the next gather drops it.
+ *   rf_comm_read_split(c, r, direct_rgba, indirect_rgba): the two components as means, row-major width*height*4 floats each (either pointer may be NULL, not both):
+ *   direct = {D.rgb / float(n), 1}, indirect = {(S.rgb - D.rgb) / float(n), 1} -- per channel one f32 subtraction, then one IEEE division -- with n = N, or the
+ *   pixel's tile's count when the gather carried counts.  A tile with count 0 is handled as rf_comm_read_mean handles it: {0, 0, 0, 1} in both images; without the
+ *   counts N = 0 (a root whose shard holds no tile) is refused.  One kernel over the gathered planes, enqueued on the handle's stream, then waited for, as
+ *   rf_comm_read_mean.  Needs RF_GATHER_DIRECT.  These are the expressions `rf-render --direct / --indirect` evaluates on the host.
+ * Out of scope: `rf-render --gpus N --direct / --indirect / --denoise-split` stays refused.
+ *
  * The root-side calls below take the communicator and the ROOT's handle, whose stream, device and exposure they use.  Each returns RF_ERROR_INVALID_ARGUMENT, with a
  * message that says which case applies, when this rank was not the root of the last gather, when no gather has been made, or when the last gather did not carry the
  * planes the call needs (the AOVs for the denoiser, the moments for the estimate, the plane asked for).
- * rf_comm_gathered_planes: RF_GATHER_AOVS / RF_GATHER_MOMENTS / RF_GATHER_TILE_COUNTS / RF_GATHER_ROBUST_MEAN as carried by the last gather, its frame size and N; any pointer may be NULL.
- * rf_comm_read_plane: waits for the handle's stream and copies plane 0 .. 3 to the host (width*height*4 floats, row-major).  rf_comm_plane_device: the plane's
+ * rf_comm_gathered_planes: RF_GATHER_AOVS / RF_GATHER_MOMENTS / RF_GATHER_TILE_COUNTS / RF_GATHER_ROBUST_MEAN / RF_GATHER_DIRECT as carried by the last gather, its frame size and N; any pointer may be NULL.
+ * rf_comm_read_plane: waits for the handle's stream and copies a sum plane (0 .. 3, 5) to the host (width*height*4 floats, row-major).  rf_comm_plane_device: the plane's
  * image in device memory (owned by the comm, valid until the next gather; work on it belongs on the handle's stream).
  * rf_comm_denoise: the a-trous denoiser (the definition above, one count N) enqueued on the handle's stream over the gathered planes 0, 1, 2 where they lie: the
  * sums never leave the device.  params NULL = the defaults; bad parameters are refused as everywhere else.  The snapshot is owned by the comm (its buffers are
@@ -767,6 +794,7 @@ typedef struct rf_comm rf_comm;
 #define RF_GATHER_MOMENTS 4u  /* with the image: Q */
 #define RF_GATHER_TILE_COUNTS 8u /* with the image: one sample count per tile (tile-adaptive sampling across ranks, below) */
 #define RF_GATHER_ROBUST_MEAN 16u /* with the image: the robust mean of every rank's own pixels, combined before the exchange: plane 4 = {M.rgb, float(c)} */
+#define RF_GATHER_DIRECT 32u /* with the image: D, the direct radiance sums (rf_renderer_set_direct): plane 5 */
 RF_API int  rf_comm_unique_id(uint8_t id_out[RF_COMM_ID_BYTES]);
 RF_API int  rf_comm_create(const uint8_t id[RF_COMM_ID_BYTES], uint32_t rank, uint32_t world_size, int32_t device_ordinal, rf_comm** out);
 RF_API void rf_comm_destroy(rf_comm* c);
@@ -778,7 +806,7 @@ RF_API int  rf_renderer_tonemap_device_image(rf_renderer* r, const void* image_d
  * layout of rf_renderer_read_accumulation). */
 RF_API int  rf_comm_read_frame(rf_comm* c, rf_renderer* r, float* dst);
 RF_API int  rf_comm_gathered_planes(const rf_comm* c, uint32_t* flags_out, uint32_t* width, uint32_t* height, uint32_t* samples);
-RF_API int  rf_comm_read_plane(rf_comm* c, rf_renderer* r, uint32_t plane /* 0..3 */, float* dst);   /* width*height*4 floats, row-major */
+RF_API int  rf_comm_read_plane(rf_comm* c, rf_renderer* r, uint32_t plane /* 0..3, 5 */, float* dst);   /* width*height*4 floats, row-major */
 RF_API int  rf_comm_plane_device(rf_comm* c, uint32_t plane, void** device_ptr);
 RF_API int  rf_comm_denoise(rf_comm* c, rf_renderer* r, const rf_denoise_parameters* params);          /* NULL = defaults */
 RF_API int  rf_comm_read_denoised(rf_comm* c, rf_renderer* r, float* rgba, uint32_t* bgra8, uint32_t* sample_count);
@@ -796,6 +824,9 @@ RF_API int  rf_comm_read_mean(rf_comm* c, rf_renderer* r, float* rgba);
 /* After a gather with RF_GATHER_ROBUST_MEAN, on the root (ROBUST MEAN ACROSS RANKS, above); any out pointer may be NULL */
 RF_API int  rf_comm_read_robust_mean(rf_comm* c, rf_renderer* r, float* rgba, uint32_t* bgra8, uint8_t* trim, uint32_t* K, uint32_t* sample_count);
 RF_API int  rf_comm_denoise_robust(rf_comm* c, rf_renderer* r, const rf_denoise_parameters* params);   /* NULL = defaults; needs RF_GATHER_AOVS | RF_GATHER_ROBUST_MEAN */
+/* After a gather with RF_GATHER_DIRECT, on the root (DIRECT SUMS ACROSS RANKS, above) */
+RF_API int  rf_comm_denoise_split(rf_comm* c, rf_renderer* r, const rf_denoise_parameters* direct, const rf_denoise_parameters* indirect); /* NULL = that component's default; needs RF_GATHER_AOVS | RF_GATHER_DIRECT */
+RF_API int  rf_comm_read_split(rf_comm* c, rf_renderer* r, float* direct_rgba, float* indirect_rgba);  /* either may be NULL, not both */
 /* Max over ranks of *value (timing plumbing for hosts without another collective layer; also a barrier). */
 RF_API int  rf_comm_all_reduce_max(rf_comm* c, rf_renderer* r /* NULL: default stream */, double* value);
 /* What RCCL reports for the communicator (ncclCommCount / ncclCommUserRank / ncclCommCuDevice); any pointer may be NULL.
@@ -886,9 +917,10 @@ RF_API int rf_gather_plan(uint32_t width, uint32_t height, uint32_t world_size, 
 /* The operations a gather with RF_GATHER_TILE_COUNTS posts for the counts, behind those of its planes: {is_send, peer, offset_words, count_words} -- the fields of
  * rf_gather_op read as uint32 words (one per tile) of the root's count staging area (receive) or of the rank's own counts (send).  Host arithmetic. */
 RF_API int rf_gather_plan_counts(uint32_t width, uint32_t height, uint32_t world_size, uint32_t rank, uint32_t root, uint32_t flags, rf_gather_op* ops, uint32_t* num_ops);
-/* The same for a gather with RF_GATHER_AOVS / RF_GATHER_MOMENTS / RF_GATHER_ROBUST_MEAN in `flags`: the one-plane list once per carried plane (plane 0 = S, 1 = AC, 2 = ND, 3 = Q, 4 = the robust mean), the
- * receives of all planes first (plane after plane, each in rank order), then the sends in plane order.  offset_tiles counts from the start of THAT plane's own staging
- * area (a receive) or compact buffer (a send).  With neither flag the list is rf_gather_plan's with plane = 0.  ops == NULL: count query. */
+/* The same for a gather with RF_GATHER_AOVS / RF_GATHER_MOMENTS / RF_GATHER_ROBUST_MEAN / RF_GATHER_DIRECT in `flags`: the one-plane list once per carried plane (plane 0 = S, 1 = AC, 2 = ND, 3 = Q, 4 = the robust mean, 5 = D), the
+ * receives of planes 0 .. 4 first (plane after plane, each in rank order), then their sends in plane order.  offset_tiles counts from the start of THAT plane's own staging
+ * area (a receive) or compact buffer (a send).  With neither flag the list is rf_gather_plan's with plane = 0.  With RF_GATHER_DIRECT the list is the list without the
+ * flag followed by rf_gather_plan's tagged plane 5 (its receives, then its send).  ops == NULL: count query. */
 typedef struct rf_gather_plane_op
 {
     uint32_t is_send, peer, plane, offset_tiles, count_tiles;

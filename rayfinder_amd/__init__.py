@@ -343,20 +343,21 @@ RF_GATHER_AOVS = 2      # with the image: plane 1 = {albedo.rgb, coverage}, plan
 RF_GATHER_MOMENTS = 4   # with the image: plane 3 = the radiance second moments
 RF_GATHER_TILE_COUNTS = 8   # with the image: one sample count per tile (TileComm.render_adaptive)
 RF_GATHER_ROBUST_MEAN = 16  # with the image: plane 4 = the robust mean of every rank's own pixels {M.rgb, float(trim)}, combined before the exchange
+RF_GATHER_DIRECT = 32       # with the image: plane 5 = the direct radiance sums D (set_direct)
 
 
-def _gather_flags(loopback=False, aovs=False, moments=False, tile_counts=False, robust_mean=False):
+def _gather_flags(loopback=False, aovs=False, moments=False, tile_counts=False, robust_mean=False, direct=False):
     return ((RF_GATHER_LOOPBACK if loopback else 0) | (RF_GATHER_AOVS if aovs else 0) | (RF_GATHER_MOMENTS if moments else 0) | (RF_GATHER_TILE_COUNTS if tile_counts else 0)
-            | (RF_GATHER_ROBUST_MEAN if robust_mean else 0))
+            | (RF_GATHER_ROBUST_MEAN if robust_mean else 0) | (RF_GATHER_DIRECT if direct else 0))
 
 
 class _GatheredPlanes(dict):
-    """TileComm.gathered_planes()'s dict.  The flags that came later, tile_counts and robust_mean, are ABSENT WHEN FALSE: they are stored only when the gather carried
+    """TileComm.gathered_planes()'s dict.  The flags that came later, tile_counts, robust_mean and direct, are ABSENT WHEN FALSE: they are stored only when the gather carried
     them, so a gather without them still compares equal to the dict it always gave.  Only the subscript reads an absent one as False (g["robust_mean"]); `in`, .get()
     and iteration see the keys that are stored, and dict(g) is a plain dict without this.  Prefer g.get("robust_mean", False) in new code."""
 
     def __missing__(self, key):
-        if key in ("tile_counts", "robust_mean"):
+        if key in ("tile_counts", "robust_mean", "direct"):
             return False
         raise KeyError(key)
 
@@ -380,12 +381,12 @@ def gather_plan(width, height, world_size, rank, root=0, loopback=False):
     return ops
 
 
-def gather_plan_planes(width, height, world_size, rank, root=0, loopback=False, aovs=False, moments=False, robust_mean=False):
-    """gather_plan for a gather that also carries the AOV sums (planes 1, 2), the second moments (plane 3) and / or the robust mean (plane 4) in the one group:
-    (n, 5) u32 rows {is_send, peer, plane, offset_tiles, count_tiles}; offsets count from the start of the plane's own staging area / compact buffer.
-    Host arithmetic, no GPU."""
+def gather_plan_planes(width, height, world_size, rank, root=0, loopback=False, aovs=False, moments=False, robust_mean=False, direct=False):
+    """gather_plan for a gather that also carries the AOV sums (planes 1, 2), the second moments (plane 3), the robust mean (plane 4) and / or the direct sums
+    (plane 5) in the one group: (n, 5) u32 rows {is_send, peer, plane, offset_tiles, count_tiles}; offsets count from the start of the plane's own staging area /
+    compact buffer.  direct=True: the list without it, followed by gather_plan's rows tagged plane 5.  Host arithmetic, no GPU."""
     n = C.c_uint32(0)
-    flags = _gather_flags(loopback, aovs, moments, robust_mean=robust_mean)
+    flags = _gather_flags(loopback, aovs, moments, robust_mean=robust_mean, direct=direct)
     check(lib.rf_gather_plan_planes(width, height, world_size, rank, root, flags, None, C.byref(n)))
     ops = np.zeros((n.value, 5), np.uint32)
     check(lib.rf_gather_plan_planes(width, height, world_size, rank, root, flags, _ptr(ops), C.byref(n)))
@@ -476,10 +477,13 @@ class TileComm:
             out["tile_counts"] = True
         if f.value & RF_GATHER_ROBUST_MEAN:
             out["robust_mean"] = True
+        if f.value & RF_GATHER_DIRECT:
+            out["direct"] = True
         return out
 
     def read_plane(self, renderer, plane):
-        """Root: the gathered row-major (H, W, 4) f32 sums of plane 0 = S, 1 = {albedo, coverage}, 2 = {normal, depth}, 3 = the second moments."""
+        """Root: the gathered row-major (H, W, 4) f32 sums of plane 0 = S, 1 = {albedo, coverage}, 2 = {normal, depth}, 3 = the second moments, 5 = the direct sums
+        (plane 4, the robust mean, is read through read_robust_mean)."""
         g = self.gathered_planes()
         img = np.zeros((g["height"], g["width"], 4), np.float32)
         check(lib.rf_comm_read_plane(self._h, renderer._h, plane, _ptr(img)))
@@ -560,6 +564,23 @@ class TileComm:
         """Root: denoise with the gathered robust mean in place of the plain mean (the gather needs aovs=True and robust_mean=True); read_denoised reads the result.
         params as for denoise."""
         check(lib.rf_comm_denoise_robust(self._h, renderer._h, C.byref(_denoise_parameters(dict(params or {})))))
+
+    # the direct sums of the sharded frame (include/rayfinder_amd.h: "DIRECT SUMS ACROSS RANKS"): plane 5 of a gather with direct=True
+    def denoise_split(self, renderer, direct=None, indirect=None):
+        """Root: the split-component denoiser over the gathered S, D and AOV sums, in device memory, on the renderer's stream (the gather needs aovs=True and
+        direct=True; with tile_counts=True every pixel is divided by its tile's count); read_denoised reads the result.  direct / indirect as for
+        ReferencePathTracer.denoise_split."""
+        pd, pi = _split_parameters(direct, indirect)
+        check(lib.rf_comm_denoise_split(self._h, renderer._h, C.byref(pd), C.byref(pi)))
+
+    def read_split(self, renderer):
+        """Root, after a gather with direct=True: ((H, W, 4) f32 {D.rgb / n, 1}, (H, W, 4) f32 {(S.rgb - D.rgb) / n, 1}), the direct and the indirect light as means;
+        n = the gathered sample count, or the pixel's tile's count after a gather with tile_counts=True ({0, 0, 0, 1} in a tile without a sample)."""
+        g = self.gathered_planes()
+        direct = np.zeros((g["height"], g["width"], 4), np.float32)
+        indirect = np.zeros_like(direct)
+        check(lib.rf_comm_read_split(self._h, renderer._h, _ptr(direct), _ptr(indirect)))
+        return direct, indirect
 
 
 # ------------------------------------------------------------------------------------- renderer
@@ -1051,7 +1072,7 @@ class ReferencePathTracer:
         check(lib.rf_renderer_accumulation_device_buffer(self._h, C.byref(p), C.byref(n)))
         return p.value, n.value
 
-    def gather_frame(self, comm, root=0, loopback=False, aovs=False, moments=False, tile_counts=False, robust_mean=False):
+    def gather_frame(self, comm, root=0, loopback=False, aovs=False, moments=False, tile_counts=False, robust_mean=False, direct=False):
         """Frame-end RCCL exchange (collective; enqueued on the handle's stream).  Root: device pointer of the
         row-major W*H float4 image; other ranks: None.  aovs / moments: the first-hit AOV sums / the radiance second moments travel in the same group
         and are un-tiled with the image (they must be on from the first sample); the root then reads, denoises and estimates the gathered frame through
@@ -1059,9 +1080,11 @@ class ReferencePathTracer:
         the root's denoise / noise_estimate then take each tile's own count, and comm.read_tile_samples / read_mean read them.  robust_mean: every rank combines
         its own bucket sums (set_buckets from the first sample, at least K samples) before the exchange and the result travels as one more plane; the root reads it
         through comm.read_robust_mean and denoises with it through comm.denoise_robust.  While the tiles hold different counts, robust_mean needs tile_counts and
-        buckets set with set_buckets(k, tile_counts=True, shard=True), every tile at k samples or more: each rank then combines every tile with its own count."""
+        buckets set with set_buckets(k, tile_counts=True, shard=True), every tile at k samples or more: each rank then combines every tile with its own count.
+        direct: the direct sums (set_direct from the first sample; after comm.render_adaptive with tile_counts=True) travel as plane 5; the root reads them through
+        comm.read_plane(r, 5) and comm.read_split, and with aovs=True denoises the two components through comm.denoise_split."""
         p = C.c_void_p()
-        check(lib.rf_renderer_gather_frame(self._h, comm._h, root, _gather_flags(loopback, aovs, moments, tile_counts, robust_mean), C.byref(p)))
+        check(lib.rf_renderer_gather_frame(self._h, comm._h, root, _gather_flags(loopback, aovs, moments, tile_counts, robust_mean, direct), C.byref(p)))
         return p.value
 
     def tonemap_device_image(self, device_ptr, width, height, samples):

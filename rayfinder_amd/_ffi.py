@@ -204,6 +204,8 @@ SIGNATURES = {
     "rf_comm_read_mean": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "rf_comm_read_robust_mean": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "rf_comm_denoise_robust": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rf_comm_denoise_split": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rf_comm_read_split": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rf_comm_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]),
     "rf_renderer_layout_info": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rf_renderer_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),

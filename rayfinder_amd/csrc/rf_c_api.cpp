@@ -820,7 +820,8 @@ int rf_comm_gathered_planes(const rf_comm* c, uint32_t* flags_out, uint32_t* wid
         uint32_t mask = 0, w = 0, h = 0, n = 0;
         c->impl->gatheredPlanes(mask, w, h, n);
         if (flags_out) *flags_out = ((mask & rf::kPlaneMaskAovs) == rf::kPlaneMaskAovs ? RF_GATHER_AOVS : 0u) | ((mask & rf::kPlaneMaskMoments) ? RF_GATHER_MOMENTS : 0u) |
-                                        ((mask & rf::kGatherMaskTileCounts) ? RF_GATHER_TILE_COUNTS : 0u) | ((mask & rf::kPlaneMaskRobustMean) ? RF_GATHER_ROBUST_MEAN : 0u);
+                                        ((mask & rf::kGatherMaskTileCounts) ? RF_GATHER_TILE_COUNTS : 0u) | ((mask & rf::kPlaneMaskRobustMean) ? RF_GATHER_ROBUST_MEAN : 0u) |
+                                        ((mask & rf::kPlaneMaskDirect) ? RF_GATHER_DIRECT : 0u);
         if (width) *width = w;
         if (height) *height = h;
         if (samples) *samples = n;
@@ -912,6 +913,28 @@ int rf_comm_denoise_robust(rf_comm* c, rf_renderer* r, const rf_denoise_paramete
         require(c && r, "null argument");
         require(r->impl->deviceOrdinal() == c->impl->deviceOrdinal(), "the renderer and the communicator are on different devices");
         c->impl->denoiseRobust(p, r->impl->exposure(), r->impl->streamHandle());
+        return RF_OK;
+    });
+}
+
+int rf_comm_denoise_split(rf_comm* c, rf_renderer* r, const rf_denoise_parameters* direct, const rf_denoise_parameters* indirect)
+{
+    return guarded([&] {
+        const rf::SplitDenoiseDefaults d = rf::splitDenoiseDefaults();
+        const rf::DenoiseParameters    pd = toSplitParams(direct, d.direct), pi = toSplitParams(indirect, d.indirect);
+        require(c && r, "null argument");
+        require(r->impl->deviceOrdinal() == c->impl->deviceOrdinal(), "the renderer and the communicator are on different devices");
+        c->impl->denoiseSplit(pd, pi, r->impl->exposure(), r->impl->streamHandle());
+        return RF_OK;
+    });
+}
+
+int rf_comm_read_split(rf_comm* c, rf_renderer* r, float* direct_rgba, float* indirect_rgba)
+{
+    return guarded([&] {
+        require(c && r && (direct_rgba || indirect_rgba), "null argument");
+        require(r->impl->deviceOrdinal() == c->impl->deviceOrdinal(), "the renderer and the communicator are on different devices");
+        c->impl->readSplit(direct_rgba, indirect_rgba, r->impl->streamHandle());
         return RF_OK;
     });
 }
@@ -1053,7 +1076,7 @@ int rf_gather_plan_planes(uint32_t width, uint32_t height, uint32_t world_size, 
         require(num_ops, "null argument");
         static_assert(sizeof(rf_gather_plane_op) == sizeof(rf::GatherPlaneOp));
         const uint32_t mask = rf::kPlaneMaskImage | ((flags & RF_GATHER_AOVS) ? rf::kPlaneMaskAovs : 0u) | ((flags & RF_GATHER_MOMENTS) ? rf::kPlaneMaskMoments : 0u) |
-                              ((flags & RF_GATHER_ROBUST_MEAN) ? rf::kPlaneMaskRobustMean : 0u);
+                              ((flags & RF_GATHER_ROBUST_MEAN) ? rf::kPlaneMaskRobustMean : 0u) | ((flags & RF_GATHER_DIRECT) ? rf::kPlaneMaskDirect : 0u);
         const rf::GatherLayout               g = rf::gatherLayout(width, height, world_size);
         const std::vector<rf::GatherPlaneOp> plan = rf::gatherPlanPlanes(g, world_size, rank, root, (flags & RF_GATHER_LOOPBACK) != 0, mask);
         if (ops)

@@ -158,12 +158,16 @@ std::vector<GatherPlaneOp> gatherPlanPlanes(const GatherLayout& g, uint32_t worl
     const std::vector<GatherOp> one = gatherPlan(g, worldSize, rank, root, loopback);
     std::vector<GatherPlaneOp>  ops;
     for (const uint32_t sends : {0u, 1u})
-        for (uint32_t p = 0; p < kGatherPlanes; ++p)
+        for (uint32_t p = 0; p < kPlaneDirect; ++p)
         {
             if (((planeMask | kPlaneMaskImage) >> p & 1u) == 0u) continue;
             for (const GatherOp& op : one)
                 if (op.isSend == sends) ops.push_back(GatherPlaneOp{op.isSend, op.peer, p, op.offsetTiles, op.countTiles});
         }
+    // plane 5 follows as a whole, its receives and then its send: the list is the one without it plus the one-plane plan (per pair the k-th send still meets the k-th
+    // receive: the sends among themselves and the receives among themselves stay in plane order)
+    if (planeMask & kPlaneMaskDirect)
+        for (const GatherOp& op : one) ops.push_back(GatherPlaneOp{op.isSend, op.peer, kPlaneDirect, op.offsetTiles, op.countTiles});
     return ops;
 }
 
@@ -381,6 +385,7 @@ struct TileComm::Impl
     DeviceBuffer<uint32_t> countStaging, frameCounts;
     std::vector<uint32_t>  frameCountsHost;
     DeviceBuffer<float4>   meanImage; // readMean's, allocated by the first call
+    DeviceBuffer<float4>   splitImages; // readSplit's: the direct component, then the indirect one; allocated by the first call
     // plane 4's un-tile leaves images[kPlaneRobustMean] = {M.rgb, 1} and this, one trim byte per pixel; readRobustMean's texels, allocated by the first call that asks for them
     DeviceBuffer<uint8_t>  trimImage;
     DeviceBuffer<uint32_t> robustBgra;
@@ -448,7 +453,7 @@ struct TileComm::Impl
         if (g.width == 0 || g.height == 0) throw std::invalid_argument("empty frame");
         g.withCounts = (g.planeMask & kGatherMaskTileCounts) != 0u;
         if ((g.planeMask & kPlaneMaskImage) == 0u || ((g.planeMask & ~kGatherMaskTileCounts) >> kGatherPlanes) != 0u)
-            throw std::invalid_argument("gather plane mask: plane 0 always travels, planes 0 .. 4 exist");
+            throw std::invalid_argument("gather plane mask: plane 0 always travels, planes 0 .. 5 exist");
         for (uint32_t p = 0; p < kGatherPlanes; ++p)
             if (g.planeMask >> p & 1u) g.carriedIndex[p] = g.numPlanes, g.carried[g.numPlanes++] = p;
         g.isRoot = rank == g.root;
@@ -527,20 +532,21 @@ struct TileComm::Impl
     void untile(const Gather& g)
     {
         const uint32_t numTiles = layout.tilesX * layout.tilesY;
-        // (plane 4 is the last carried plane and has a launch of its own: the sum planes go as they go without it)
-        const bool     robust = (g.planeMask & kPlaneMaskRobustMean) != 0u;
-        const uint32_t sumPlanes = g.numPlanes - (robust ? 1u : 0u);
+        // (plane 4 has a launch of its own: the sum planes go as they go without it, each from its own staging area -- D's lies behind plane 4's)
+        const bool      robust = (g.planeMask & kPlaneMaskRobustMean) != 0u;
+        UntilePlaneArgs args{};
+        uint32_t        sumPlanes = 0;
+        for (uint32_t k = 0; k < g.numPlanes; ++k)
+        {
+            const uint32_t p = g.carried[k];
+            if (isSumPlane(p)) args.plane[sumPlanes++] = UntilePlane{staging.ptr + k * g.planeStagingPixels, static_cast<const float4*>(g.compact[p]), images[p].ptr};
+        }
         if (sumPlanes == 1)
             hipLaunchKernelGGL(kUntile, dim3(numTiles), dim3(256), 0, g.stream, staging.ptr, static_cast<const float4*>(g.compact[kPlaneImage]), g.ownRank(), layout.rankFirstTile[rank],
                                dTileSlot.ptr, dTileOwner.ptr, g.width, g.height, layout.tilesX, images[kPlaneImage].ptr);
         else
-        {
-            UntilePlaneArgs args{};
-            for (uint32_t k = 0; k < sumPlanes; ++k)
-                args.plane[k] = UntilePlane{staging.ptr + k * g.planeStagingPixels, static_cast<const float4*>(g.compact[g.carried[k]]), images[g.carried[k]].ptr};
             hipLaunchKernelGGL(kUntilePlanes, dim3(numTiles, sumPlanes), dim3(256), 0, g.stream, args, g.ownRank(), layout.rankFirstTile[rank], dTileSlot.ptr, dTileOwner.ptr, g.width,
                                g.height, layout.tilesX);
-        }
         if (robust)
             hipLaunchKernelGGL(kUntileRobust, dim3(numTiles), dim3(256), 0, g.stream, staging.ptr + g.carriedIndex[kPlaneRobustMean] * g.planeStagingPixels,
                                static_cast<const float4*>(g.compact[kPlaneRobustMean]), g.ownRank(), layout.rankFirstTile[rank], dTileSlot.ptr, dTileOwner.ptr, g.width, g.height,
@@ -613,7 +619,7 @@ void TileComm::rcclInfo(uint32_t& count, uint32_t& userRank, int& device) const 
 
 const void* TileComm::gatherFrame(const void* compactDevice, uint32_t width, uint32_t height, uint32_t root, void* streamHandle, bool loopback)
 {
-    const void* const planes[kGatherPlanes] = {compactDevice, nullptr, nullptr, nullptr, nullptr};
+    const void* const planes[kGatherPlanes] = {compactDevice}; // (the other planes: nullptr)
     return gatherPlanes(planes, kPlaneMaskImage, 0u, width, height, root, streamHandle, loopback);
 }
 
@@ -658,8 +664,18 @@ void TileComm::readFrame(float* dstHost, void* streamHandle)
 
 namespace
 {
-const char* const kPlaneNames[kSumPlanes] = {"the image (plane 0)", "the first-hit AOVs (plane 1, AC: gather with RF_GATHER_AOVS)", "the first-hit AOVs (plane 2, ND: gather with RF_GATHER_AOVS)",
-                                                "the radiance second moments (plane 3, Q: gather with RF_GATHER_MOMENTS)"};
+// [plane]; plane 4 is no sum plane (rf_comm.hpp: isSumPlane) and is not served by readPlane / planeDevice
+const char* const kPlaneNames[kGatherPlanes] = {"the image (plane 0)",
+                                                "the first-hit AOVs (plane 1, AC: gather with RF_GATHER_AOVS)",
+                                                "the first-hit AOVs (plane 2, ND: gather with RF_GATHER_AOVS)",
+                                                "the radiance second moments (plane 3, Q: gather with RF_GATHER_MOMENTS)",
+                                                "the robust mean (plane 4: gather with RF_GATHER_ROBUST_MEAN)",
+                                                "the direct sums (plane 5, D: gather with RF_GATHER_DIRECT)"};
+void requireSumPlane(uint32_t plane)
+{
+    if (!isSumPlane(plane))
+        throw std::invalid_argument("plane out of range: 0 = S, 1 = AC, 2 = ND, 3 = Q, 5 = D (plane 4, the robust mean, is read through rf_comm_read_robust_mean)");
+}
 }
 
 void TileComm::gatheredPlanes(uint32_t& planeMask, uint32_t& width, uint32_t& height, uint32_t& samples) const
@@ -672,7 +688,7 @@ void TileComm::gatheredPlanes(uint32_t& planeMask, uint32_t& width, uint32_t& he
 const void* TileComm::planeDevice(uint32_t plane) const
 {
     const Impl& m = *mImpl;
-    if (plane >= kSumPlanes) throw std::invalid_argument("plane out of range: 0 = S, 1 = AC, 2 = ND, 3 = Q");
+    requireSumPlane(plane);
     m.requireGathered("rf_comm_plane_device", 1u << plane, kPlaneNames[plane]);
     return m.images[plane].ptr;
 }
@@ -680,7 +696,7 @@ const void* TileComm::planeDevice(uint32_t plane) const
 void TileComm::readPlane(uint32_t plane, float* dstHost, void* streamHandle)
 {
     Impl& m = *mImpl;
-    if (plane >= kSumPlanes) throw std::invalid_argument("plane out of range: 0 = S, 1 = AC, 2 = ND, 3 = Q");
+    requireSumPlane(plane);
     m.requireGathered("rf_comm_read_plane", 1u << plane, kPlaneNames[plane]);
     hipStream_t stream = static_cast<hipStream_t>(streamHandle);
     RF_HIP(hipSetDevice(m.device));
@@ -805,6 +821,46 @@ void TileComm::denoiseRobust(const DenoiseParameters& params, float exposure, vo
     enqueueDenoise(static_cast<hipStream_t>(streamHandle), m.denoiseWork, m.images[kPlaneImage].ptr, m.images[kPlaneAlbedoCoverage].ptr, m.images[kPlaneNormalDepth].ptr, m.imageW,
                    m.imageH, 0u, m.gatheredSamples, params, exposure, perTile ? m.frameCounts.ptr : nullptr, m.images[kPlaneRobustMean].ptr);
     m.denoisedValid = true;
+}
+
+void TileComm::denoiseSplit(const DenoiseParameters& direct, const DenoiseParameters& indirect, float exposure, void* streamHandle)
+{
+    Impl& m = *mImpl;
+    m.requireGathered("rf_comm_denoise_split", kPlaneMaskImage | kPlaneMaskAovs, "the first-hit AOVs (gather with RF_GATHER_AOVS | RF_GATHER_DIRECT)");
+    m.requireGathered("rf_comm_denoise_split", kPlaneMaskDirect, "the direct sums (plane 5, D: gather with RF_GATHER_AOVS | RF_GATHER_DIRECT)");
+    if (m.gatheredSamples == 0u) throw std::invalid_argument("rf_comm_denoise_split: the gathered sums hold no sample");
+    if (static_cast<uint64_t>(m.imageW) * m.imageH >= (1ull << 31)) throw std::invalid_argument("rf_comm_denoise_split: image too large");
+    const bool perTile = (m.gatheredMask & kGatherMaskTileCounts) != 0u;
+    if (perTile && *std::min_element(m.frameCountsHost.begin(), m.frameCountsHost.end()) == 0u)
+        throw std::invalid_argument("rf_comm_denoise_split: a tile of the gathered frame holds no sample");
+    RF_HIP(hipSetDevice(m.device));
+    // the filter rf_denoise_split_images runs over row-major sums (tilesX = 0), without the sums leaving the device -- or, gathered with the counts, rf_denoise_split_tiles'
+    enqueueDenoiseSplit(static_cast<hipStream_t>(streamHandle), m.denoiseWork, m.images[kPlaneImage].ptr, m.images[kPlaneDirect].ptr, m.images[kPlaneAlbedoCoverage].ptr,
+                        m.images[kPlaneNormalDepth].ptr, m.imageW, m.imageH, 0u, m.gatheredSamples, direct, indirect, exposure, perTile ? m.frameCounts.ptr : nullptr);
+    m.denoisedValid = true;
+}
+
+void TileComm::readSplit(float* directRgba, float* indirectRgba, void* streamHandle)
+{
+    Impl& m = *mImpl;
+    m.requireGathered("rf_comm_read_split", kPlaneMaskImage | kPlaneMaskDirect, kPlaneNames[kPlaneDirect]);
+    const bool perTile = (m.gatheredMask & kGatherMaskTileCounts) != 0u;
+    if (!perTile && m.gatheredSamples == 0u) throw std::invalid_argument("rf_comm_read_split: the gathered sums hold no sample");
+    const size_t n = static_cast<size_t>(m.imageW) * m.imageH;
+    if (n >= (1ull << 31)) throw std::invalid_argument("rf_comm_read_split: image too large");
+    hipStream_t stream = static_cast<hipStream_t>(streamHandle);
+    RF_HIP(hipSetDevice(m.device));
+    if (m.splitImages.count < 2 * n)
+    {
+        RF_HIP(hipStreamSynchronize(stream)); // (an earlier read may still use the smaller one)
+        m.splitImages.alloc(2 * n);
+    }
+    float4* const direct = m.splitImages.ptr;
+    float4* const indirect = m.splitImages.ptr + n;
+    enqueueSplitMeanRows(stream, m.images[kPlaneImage].ptr, m.images[kPlaneDirect].ptr, perTile ? m.frameCounts.ptr : nullptr, m.gatheredSamples, m.imageW, m.imageH, direct, indirect);
+    if (directRgba) RF_HIP(hipMemcpyAsync(directRgba, direct, n * sizeof(float4), hipMemcpyDeviceToHost, stream));
+    if (indirectRgba) RF_HIP(hipMemcpyAsync(indirectRgba, indirect, n * sizeof(float4), hipMemcpyDeviceToHost, stream));
+    RF_HIP(hipStreamSynchronize(stream));
 }
 
 double TileComm::allReduceMax(double value, void* streamHandle)

@@ -51,20 +51,24 @@ struct GatherOp
 std::vector<GatherOp> gatherPlan(const GatherLayout& layout, uint32_t worldSize, uint32_t rank, uint32_t root, bool loopback);
 
 // The sums a gather can carry, one PLANE each, in this fixed order: the image S, the first-hit AOV sums AC = {albedo.rgb, coverage} and ND = {normal.xyz, depth},
-// and the radiance second moments Q.  Every plane is a compact tile-major float4 buffer of the rank's shard, and has its own staging area (GatherLayout) and its own
-// row-major image on the root.  A plane mask has bit p set for every carried plane; plane 0 always travels.
+// the radiance second moments Q and, behind plane 4, the direct radiance sums D.  Every plane is a compact tile-major float4 buffer of the rank's shard, and has its own
+// staging area (GatherLayout) and its own row-major image on the root.  A plane mask has bit p set for every carried plane; plane 0 always travels.
 // Plane 4 is no sum: the robust mean of the rank's own pixels, {M.rgb, float(c)} (Renderer::enqueueShardRobustMean: the combine is per pixel, so every rank runs it over its
 // own bucket planes BEFORE the exchange and one plane travels instead of K).  It is staged like the others; the root's un-tile splits it into a row-major {M.rgb, 1}
-// image and a row-major uint8 trim image.  The sum planes 0 .. kSumPlanes - 1 are the ones readPlane / planeDevice serve.
-constexpr uint32_t kGatherPlanes = 5, kSumPlanes = 4;
-constexpr uint32_t kPlaneImage = 0, kPlaneAlbedoCoverage = 1, kPlaneNormalDepth = 2, kPlaneMoments = 3, kPlaneRobustMean = 4;
+// image and a row-major uint8 trim image.  The SUM planes -- kPlaneIsSum: {0, 1, 2, 3, 5}, kSumPlanes of them -- are the ones readPlane / planeDevice serve and the one
+// kUntilePlanes launch un-tiles; whoever asks "is p a sum plane" asks isSumPlane(p).
+constexpr uint32_t kGatherPlanes = 6, kSumPlanes = 5;
+constexpr uint32_t kPlaneImage = 0, kPlaneAlbedoCoverage = 1, kPlaneNormalDepth = 2, kPlaneMoments = 3, kPlaneRobustMean = 4, kPlaneDirect = 5;
+constexpr bool     kPlaneIsSum[kGatherPlanes] = {true, true, true, true, false, true};
+constexpr bool     isSumPlane(uint32_t plane) { return plane < kGatherPlanes && kPlaneIsSum[plane]; }
 constexpr uint32_t kPlaneMaskImage = 1u << kPlaneImage, kPlaneMaskAovs = (1u << kPlaneAlbedoCoverage) | (1u << kPlaneNormalDepth), kPlaneMaskMoments = 1u << kPlaneMoments,
-                   kPlaneMaskRobustMean = 1u << kPlaneRobustMean;
+                   kPlaneMaskRobustMean = 1u << kPlaneRobustMean, kPlaneMaskDirect = 1u << kPlaneDirect;
 
 // gatherPlan() once per carried plane, still ONE group: on the root, for each plane in order, the receives of that plane in rank order; on a sender, its sends in plane
 // order -- so per (source, destination) pair the k-th send meets the k-th receive, which is what both RCCL's grouped point-to-point calls and the local transport's
 // FIFO matching rely on.  offsetTiles counts from the start of THAT plane's staging area (receive) or compact buffer (send).  With planeMask == kPlaneMaskImage the
-// list is gatherPlan()'s with plane = 0.  Pure host arithmetic (tests/test_gather_sums_api.py).
+// list is gatherPlan()'s with plane = 0.  Plane 5 comes behind all of that as a whole -- its receives, then its send: the list with it is the list without it followed by
+// gatherPlan()'s with plane = 5, and the pairing rule holds as before.  Pure host arithmetic (tests/test_gather_sums_api.py, tests/test_gather_direct_api.py).
 struct GatherPlaneOp
 {
     uint32_t isSend, peer, plane, offsetTiles, countTiles;
@@ -116,6 +120,7 @@ public:
     // the root assembles one count per tile of the frame (kUntileCounts), waits for the exchange, and records N = the largest count instead of `samples`.
     // planeMask & kPlaneMaskRobustMean: compactDevice[4] is the rank's {M.rgb, float(c)} buffer; it is un-tiled by a launch of its own (kUntileRobust) behind the one of
     // the sum planes, and `robustK` -- the K of the combine -- is recorded on the root for readRobustMean().
+    // planeMask & kPlaneMaskDirect: compactDevice[5] is the rank's D; it travels behind plane 4 and is un-tiled with the other sum planes, one more blockIdx.y of their launch.
     const void* gatherPlanes(const void* const compactDevice[kGatherPlanes], uint32_t planeMask, uint32_t samples, uint32_t width, uint32_t height, uint32_t root, void* stream,
                              bool loopback = false, const uint32_t* tileCountsDevice = nullptr, uint32_t robustK = 0);
     // Device time of the LAST gatherFrame() on the caller's stream, HIP events around it: from the moment the rank's queued frame kernels have drained and the
@@ -149,6 +154,13 @@ public:
     // denoise() with prep's colour = the gathered M instead of S / N (Renderer::denoiseRobust's filter over row-major planes); needs kPlaneMaskAovs | kPlaneMaskRobustMean.
     // The snapshot is denoise()'s: readDenoised.
     void denoiseRobust(const DenoiseParameters& params, float exposure, void* stream);
+    // After a gather with kPlaneMaskDirect: the split-component filter (rf_denoise.hpp: enqueueDenoiseSplit, row-major) over the gathered S, D, AC and ND where they lie, per
+    // tile count when the counts travelled; needs kPlaneMaskAovs | kPlaneMaskDirect.  The snapshot is denoise()'s: readDenoised.
+    void denoiseSplit(const DenoiseParameters& direct, const DenoiseParameters& indirect, float exposure, void* stream);
+    // The two components of the gathered frame, row-major width * height * 4 floats each (either may be nullptr, not both): direct = {D.rgb / float(n), 1} and
+    // indirect = {(S.rgb - D.rgb) / float(n), 1}, n = N or, gathered with the counts, the pixel's tile's count ({0, 0, 0, 1} for both in a tile without a sample: readMean's
+    // rule; without the counts N = 0 is refused).  One kernel (rf_noise.hpp: enqueueSplitMeanRows) on `stream`, then waited for.  Needs kPlaneMaskDirect.
+    void readSplit(float* directRgba, float* indirectRgba, void* stream);
     // Max over ranks of a host double / barrier (timing plumbing for callers that have no other collective layer).
     double allReduceMax(double value, void* stream);
 

@@ -76,6 +76,17 @@ const void* gatherFrame(Renderer& h, TileComm& comm, uint32_t root, uint32_t fla
                                         " (sample adaptively with min_samples >= K)");
         planeMask |= kPlaneMaskRobustMean;
     }
+    // the direct sums, a sum plane like the AOVs' and the moments'; in the non-uniform state (the counts travel: checked above) D must have been kept per tile count
+    if (flags & RF_GATHER_DIRECT)
+    {
+        require(s.direct.on, "rf_renderer_gather_frame: RF_GATHER_DIRECT needs the direct sums: turn them on (rf_renderer_set_direct) before the first sample");
+        require(!s.ownsTiles || s.accumulated != 0u, "rf_renderer_gather_frame: RF_GATHER_DIRECT: no sample has been accumulated");
+        if (s.ownsTiles && !s.direct.coversAccumulation) throw differs("RF_GATHER_DIRECT", "direct", s.direct.samples, "direct sums");
+        require(h.tileSamplesUniform() || s.directTileCounts,
+                "rf_renderer_gather_frame: RF_GATHER_DIRECT: the tiles hold different sample counts, and the direct sums were not kept per tile count: set "
+                "1 | RF_DIRECT_TILE_COUNTS (rf_renderer_set_direct) before the first sample");
+        planeMask |= kPlaneMaskDirect;
+    }
     h.clearAccumulationIfStale(); // nothing rendered since the last reset: send zeros, not the previous frame
     // the shard's per-tile counts, in slot order, from device memory (the ordinary state: every tile at the accumulated count)
     const uint32_t* counts = nullptr;
@@ -83,7 +94,7 @@ const void* gatherFrame(Renderer& h, TileComm& comm, uint32_t root, uint32_t fla
     // every check of the handle's state is behind us: the rank's own combine goes onto the handle's stream in front of the exchange, and its output travels as plane 4.
     // (The communicator's own checks -- an aborted transport, the plane mask, a null buffer: gatherPlanes -- follow it, as they follow the clearing above; a gather
     // they refuse has written the handle's own plane-4 buffer and nothing else.)
-    const void* planes[kGatherPlanes] = {s.planes[0], s.planes[1], s.planes[2], s.planes[3], nullptr};
+    const void* planes[kGatherPlanes] = {s.planes[0], s.planes[1], s.planes[2], s.planes[3], nullptr, s.directPlane};
     if (flags & RF_GATHER_ROBUST_MEAN) planes[kPlaneRobustMean] = h.enqueueShardRobustMean(robustPerSlot ? counts : nullptr);
     return comm.gatherPlanes(planes, planeMask, s.accumulated, h.width(), h.height(), root, h.streamHandle(), (flags & RF_GATHER_LOOPBACK) != 0, counts, s.bucketsK);
 }

@@ -7,6 +7,7 @@
 //   kNoiseEstimateSlots     the same for a list of tiles of a tile shard: the tile's sums sit at its SLOT of the shard's compact buffers
 //   kTileMean               {S.rgb / float(tile's sample count), 1} per pixel
 //   kTileMeanRows           the same over a row-major frame
+//   kSplitMeanRows          {D.rgb / float(n), 1} and {(S.rgb - D.rgb) / float(n), 1} per pixel of a row-major frame (the gathered frame's two components)
 #include "rf_noise.hpp"
 
 #include "rf_math.hpp"
@@ -139,6 +140,27 @@ __global__ __launch_bounds__(256) void kTileMeanRows(const float4* image, const 
     const float    nf = static_cast<float>(count);
     mean[i] = count ? make_float4(s.x / nf, s.y / nf, s.z / nf, 1.0f) : make_float4(0.0f, 0.0f, 0.0f, 1.0f);
 }
+
+// The two components of a row-major width x height frame (the gathered S and D on the root), one lane per pixel, S and D read once each:
+// direct[i] = {D.rgb / float(n), 1}, indirect[i] = {(S.rgb - D.rgb) / float(n), 1} -- one f32 subtraction, then one IEEE division, per channel.  n = the count of the
+// pixel's tile (tileSamples, as kTileMeanRows) or, tileSamples == nullptr, `samples` for all; n = 0: {0, 0, 0, 1} for both.  No LDS; 32 bytes in and out per pixel.
+__global__ __launch_bounds__(256) void kSplitMeanRows(const float4* __restrict__ image, const float4* __restrict__ directSum, const uint32_t* __restrict__ tileSamples, uint32_t samples,
+                                                      uint32_t width, uint32_t height, uint32_t tilesX, float4* __restrict__ direct, float4* __restrict__ indirect)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= width * height) return;
+    uint32_t count = samples;
+    if (tileSamples)
+    {
+        const uint32_t y = i / width, x = i - y * width;
+        count = tileSamples[(y / kTileSize) * tilesX + x / kTileSize];
+    }
+    const float4 s = image[i], d = directSum[i];
+    const float  nf = static_cast<float>(count);
+    const float4 none = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+    direct[i] = count ? make_float4(d.x / nf, d.y / nf, d.z / nf, 1.0f) : none;
+    indirect[i] = count ? make_float4((s.x - d.x) / nf, (s.y - d.y) / nf, (s.z - d.z) / nf, 1.0f) : none;
+}
 } // namespace
 
 TileMeanKernel tileMeanKernel() { return kTileMean; }
@@ -147,6 +169,15 @@ void enqueueTileMeanRows(hipStream_t stream, const float4* image, const uint32_t
 {
     const uint32_t n = width * height; // (< 2^31: the callers check)
     hipLaunchKernelGGL(kTileMeanRows, dim3((n + 255u) / 256u), dim3(256), 0, stream, image, tileSamples, width, height, TileGrid(width, height).tilesX, mean);
+    RF_HIP(hipGetLastError());
+}
+
+void enqueueSplitMeanRows(hipStream_t stream, const float4* image, const float4* directSum, const uint32_t* tileSamples, uint32_t samples, uint32_t width, uint32_t height,
+                          float4* direct, float4* indirect)
+{
+    const uint32_t n = width * height; // (< 2^31: the callers check)
+    hipLaunchKernelGGL(kSplitMeanRows, dim3((n + 255u) / 256u), dim3(256), 0, stream, image, directSum, tileSamples, samples, width, height, TileGrid(width, height).tilesX, direct,
+                       indirect);
     RF_HIP(hipGetLastError());
 }
 

@@ -12,6 +12,11 @@ using TileMeanKernel = void (*)(const float4* image, const uint32_t* tileSamples
 TileMeanKernel tileMeanKernel();
 // The same over a row-major width x height frame (width * height < 2^31), enqueued on `stream`: tileSamples has one count per tile of the frame's 32 x 32 grid
 void enqueueTileMeanRows(hipStream_t stream, const float4* image, const uint32_t* tileSamples, uint32_t width, uint32_t height, float4* mean);
+// The direct and the indirect component of a row-major width x height frame (width * height < 2^31) from its sums S (`image`) and D, one launch of kSplitMeanRows on
+// `stream`: direct[i] = {D.rgb / float(n), 1}, indirect[i] = {(S.rgb - D.rgb) / float(n), 1}; n = the pixel's tile's count (tileSamples as above) or, tileSamples ==
+// nullptr, `samples`; n = 0: {0, 0, 0, 1} for both
+void enqueueSplitMeanRows(hipStream_t stream, const float4* image, const float4* directSum, const uint32_t* tileSamples, uint32_t samples, uint32_t width, uint32_t height,
+                          float4* direct, float4* indirect);
 
 // Device buffers of one estimate: per-tile {sum, max} and {pixels, non-finite pixels}, and the row-major error map (only when a caller asks for it)
 struct NoiseWork

@@ -2181,7 +2181,7 @@ Renderer::ShardSums Renderer::shardSums() const
     if (m.frameLeadingSamples != 0u) least = m.frameMinTileSamples;
     else if (m.nonUniform()) least = *std::min_element(m.tileSamples.begin(), m.tileSamples.end());
     return ShardSums{{m.image, m.aovAlbedoCoverage(), m.aovNormalDepth(), m.moments()}, channel(m.aovSums), channel(m.momentSums), m.accumulated, !m.tiles.empty(),
-                     channel(m.bucketSums), buckets(), m.bucketSums.on && m.bucketShardTileCounts, least, channel(m.directSums), m.directSums.on && m.directTileCounts()};
+                     channel(m.bucketSums), buckets(), m.bucketSums.on && m.bucketShardTileCounts, least, channel(m.directSums), m.directSums.on && m.directTileCounts(), m.direct()};
 }
 
 const void* Renderer::enqueueShardRobustMean(const uint32_t* slotCounts)

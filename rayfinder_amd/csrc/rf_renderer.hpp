@@ -353,7 +353,7 @@ public:
     // Device pointer of the compact tile-major accumulation buffer (numTiles*1024 float4) and a
     // way to render into caller-owned device memory (e.g. a torch tensor used for the RCCL gather).
     void*    accumulationDevicePointer() const;
-    // The compact tile-major sums of the shard as the frame gather sees them (rf_comm.hpp: planes 0 .. 3 = S, {albedo.rgb, coverage}, {normal.xyz, depth}, Q): each
+    // The compact tile-major sums of the shard as the frame gather sees them (rf_comm.hpp: planes 0 .. 3 = S, {albedo.rgb, coverage}, {normal.xyz, depth}, Q; plane 5 = D): each
     // plane's device pointer -- nullptr while its channel is off or has not been sized yet -- and per channel whether it is on, whether it holds exactly the accumulated
     // samples (on from the first sample, at least one accumulated: what the gather requires before it sends them) and its own sample count.
     struct ShardSums
@@ -373,8 +373,9 @@ public:
         // the smallest tile count known to the rank: the frame's minimum after rf_comm_render_adaptive (the same on every rank, one without a tile too), else the
         // smallest of the rank's own tiles (no tile: the accumulated count)
         uint32_t    minTileSamples;
-        Channel     direct;           // the direct sums: on, covering the accumulation, their own sample count (the frame gather does not carry D)
+        Channel     direct;           // the direct sums: on, covering the accumulation, their own sample count
         bool        directTileCounts; // D carries kDirectTileCounts: it follows the per-slot counts under rf_comm_render_adaptive
+        const void* directPlane;      // D, shard-compact tile-major like planes[] (rf_comm.hpp: plane 5); nullptr while off or not sized yet
     };
     ShardSums shardSums() const;
     // The robust mean of the shard's own pixels, for the frame gather (rf_comm.hpp: plane 4): kRobustMeanShard over the shard-compact bucket planes with the accumulated
