@@ -33,6 +33,7 @@ typedef enum rf_status
     RF_ERROR_RUNTIME = 2,      /* what the reference reports with std::runtime_error */
     RF_ERROR_NO_DEVICE = 3,    /* no HIP device: this library has NO CPU fallback for rendering */
     RF_ERROR_OUT_OF_RANGE = 4, /* sky parameters out of range (sky_state_result != success) */
+    RF_ERROR_CORRUPT = 5,      /* rf_renderer_load_checkpoint: what the copies left in device memory does not digest to what the blob stores */
 } rf_status;
 
 /* Text of the last error on the calling thread ("" if none). */
@@ -640,6 +641,66 @@ RF_API int rf_renderer_set_tile_shard(rf_renderer* r, uint32_t rank, uint32_t wo
 RF_API int rf_renderer_shard_tiles(rf_renderer* r, uint32_t* tile_ids /* may be NULL */, uint32_t* num_tiles);
 RF_API int rf_renderer_accumulation_device_buffer(rf_renderer* r, void** device_ptr, uint64_t* bytes);
 RF_API int rf_renderer_bind_accumulation_buffer(rf_renderer* r, void* device_ptr, uint64_t bytes);
+
+/* State digest and checkpoints (no reference counterpart).
+ *
+ * Every sum of a handle is kept in sample order, and every tile's sums are what a uniform render of that tile's own count leaves: a render is a function of the scene,
+ * the parameters, the frame counter and the per-tile counts.  A checkpoint stores exactly that, keyed by tile, and the digest says whether two states are the same
+ * without reading a plane back.
+ *
+ * THE DIGEST.  All arithmetic is mod 2^64 (tests/digest_restatement.py restates it in Python integers).
+ *   mix64(z):  z ^= z >> 30;  z *= 0xBF58476D1CE4E5B9;  z ^= z >> 27;  z *= 0x94D049BB133111EB;  z ^= z >> 31.
+ *   Plane ids p follow the gather's numbering: 0 = S, 1 = AC {albedo, coverage}, 2 = ND {normal, depth}, 3 = Q, 5 = D, 16 + b = bucket plane b.
+ *   For the in-frame pixel (x, y) of plane p: i = y * width + x (the FRAME's index: the digest does not depend on the tile layout), w0 .. w3 the bit patterns of the texel's
+ *   four floats, k = mix64((u64(p) << 32) | i),
+ *     term = mix64(k ^ (u64(w1) << 32 | w0)) + mix64((k + 0x9E3779B97F4A7C15) ^ (u64(w3) << 32 | w2)).
+ *   Tile digest d[p][t] = the sum of term over the in-frame pixels of tile t (the padding texels of a ragged tile are never read); plane digest = the sum of d[p][t]
+ *   over the handle's own tiles; counts digest = the sum over the handle's tiles of mix64(mix64((u64(0xC0) << 32) | t) ^ u64(tile_samples[t])).
+ * Hence: the digests of the ranks of a tile-sharded frame add up (mod 2^64) to the whole-frame handle's; -0.0 and +0.0 differ; a swap of two pixels, two planes or
+ * two tiles changes the digest.  The tile digests come from one kernel (kDigestTiles: one workgroup per tile and plane, integer sums, no atomics); the host adds them.
+ *
+ * rf_renderer_state_digest: enqueued on the handle's stream, then waited for.  A family that is off has digest 0 and family_on 0; a restarted family digests as the
+ * zeros its read returns (its sums are zeroed first, as the next sample would) with family_samples 0.  Families: 0 = S, 1 = the AOVs, 2 = Q, 3 = D, 4 = the buckets.
+ * Works in the uniform and the non-uniform state, with or without a tile shard (then: over the shard's tiles) and on a bound accumulation buffer.
+ *
+ * rf_renderer_save_checkpoint: dst NULL = size query (*bytes out); else *bytes in = the buffer's size, out = the bytes written.  Waits for the stream.  The blob holds
+ * the frame counter, the counts, the switch words, a guard of the render parameters (camera, sky, numBounces, width, height -- not numSamplesPerPixel, a cap, nor the
+ * exposure, display only) and of the scene (the counts of BVH nodes, triangles, textures, texels and the root box: a guard against the wrong file, not a proof), the
+ * handle's tile ids and per-tile counts, one digest per stored plane and tile, and every plane of every family that is on and holds samples.  Snapshots (denoised,
+ * robust mean), statistics and the deferred variant are not saved.  The byte layout: INTEGRATION.md 3.
+ * rf_checkpoint_info: host only (no device needed): the header of a blob, after the same checks of every length and count against `bytes` that a load makes.
+ * rf_renderer_load_checkpoint: the blobs together must hold every tile of the handle's shard exactly once among the tiles the handle owns; tiles it does not own are
+ * ignored -- one whole-frame blob feeds any shard, N shard blobs feed a whole-frame handle, N feed M.  RF_ERROR_INVALID_ARGUMENT, the handle unchanged and the message
+ * naming the cause, before anything touches the device: bad magic or version, a length or count that does not fit the blob, blobs that disagree on anything but
+ * their tiles, another frame size, camera, sky, numBounces or scene than the handle's, switch words that differ from the handle's (set them first: rf_checkpoint_info),
+ * accumulated > the handle's numSamplesPerPixel, an own tile missing or given twice.  Then the accumulation is restarted, the planes are copied in, and kDigestTiles
+ * runs over what lies in device memory: a tile whose digest differs from the blob's -> the accumulation restarted again, the frame counter as before the call,
+ * RF_ERROR_CORRUPT, the handle usable.  Else the handle is indistinguishable -- through every read, every later render call and rf_renderer_state_digest -- from the
+ * handle that saved, whatever process, handle history or shard layout that was.  Under a tile shard the accumulated count becomes the largest count among the handle's
+ * own tiles (a rank without a tile: 0, as rf_comm_render_adaptive leaves it) and the frame's leading and smallest counts come from the blobs. */
+typedef struct rf_state_digest
+{
+    uint64_t accumulation, albedo_coverage, normal_depth, moments, direct, bucket[15], counts;
+    uint32_t family_on[5], family_samples[5];
+    uint32_t frame_count, accumulated, num_tiles;
+    uint32_t aov_flags, moments_on, direct_word, buckets_word;
+    float    kernel_ms; /* kDigestTiles' own time in this call (two events on the handle's stream); not part of the state: two equal states report different times */
+} rf_state_digest;
+/* (the struct shares its name with the call, so it has no typedef: write `struct rf_checkpoint_info`) */
+struct rf_checkpoint_info
+{
+    uint32_t   version, width, height, num_tiles, frame_count, accumulated, frame_leading_samples, frame_min_tile_samples;
+    uint32_t   aov_flags, moments_on, direct_word, buckets_word;
+    uint32_t   family_samples[5], family_restarted[5];
+    uint32_t   num_bounces, stored_planes;
+    uint64_t   total_bytes;
+    rf_camera  camera;
+    rf_sky     sky;
+};
+RF_API int rf_renderer_state_digest(rf_renderer* r, rf_state_digest* out);
+RF_API int rf_renderer_save_checkpoint(rf_renderer* r, void* dst /* NULL = size query */, uint64_t* bytes);
+RF_API int rf_checkpoint_info(const void* blob, uint64_t bytes, struct rf_checkpoint_info* out);
+RF_API int rf_renderer_load_checkpoint(rf_renderer* r, const void* const* blobs, const uint64_t* sizes, uint32_t count);
 
 /* Frame-end exchange behind the C ABI (no reference counterpart): one RCCL communicator per rank
  * (one process or host thread per GPU).  Rank 0 calls rf_comm_unique_id and hands the 128 bytes to the other ranks

@@ -7,6 +7,7 @@ bench.py and torch.distributed plumbing can drive it; it mirrors the reference's
 src/common/bvh.hpp:33, src/common/camera.hpp:24-34) by name.  No CPU fallback exists.
 """
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -761,6 +762,24 @@ def noise_estimate_tiles(color_sum, sumsq, tile_samples, device_ordinal=0):
     return _noise_result(est, emap, tsum, tmax)
 
 
+def _checkpoint_bytes(blob_or_path):
+    if isinstance(blob_or_path, (str, os.PathLike)):
+        with open(blob_or_path, "rb") as f:
+            return f.read()
+    return bytes(blob_or_path)
+
+
+def checkpoint_info(blob):
+    """The header of a checkpoint blob (bytes or a path), host only: sizes, counts, the four switch words, per family (S, AOVs, Q, D, buckets) family_samples /
+    family_restarted, and the camera and sky it was rendered with.  RayfinderError (RF_ERROR_INVALID_ARGUMENT) for a blob a load would refuse by its own bytes."""
+    data = _checkpoint_bytes(blob)
+    info = _ffi.CheckpointInfo()
+    check(lib.rf_checkpoint_info(C.c_char_p(data), len(data), C.byref(info)))  # (the pointer of an empty blob is still a pointer)
+    out = {k: int(getattr(info, k)) for k, _ in info._fields_ if k not in ("family_samples", "family_restarted", "camera", "sky")}
+    out.update(family_samples=[int(v) for v in info.family_samples], family_restarted=[int(v) for v in info.family_restarted], camera=info.camera, sky=info.sky)
+    return out
+
+
 class ReferencePathTracer:
     """Host-side mirror of nlrs::ReferencePathTracer (src/pt/reference_path_tracer.hpp:59-76).
 
@@ -1094,6 +1113,56 @@ class ReferencePathTracer:
 
     def bind_accumulation_buffer(self, device_ptr, nbytes):
         check(lib.rf_renderer_bind_accumulation_buffer(self._h, C.c_void_p(device_ptr), nbytes))
+
+    # state digest and checkpoints (rf_renderer_state_digest / _save_checkpoint / _load_checkpoint; include/rayfinder_amd.h defines the digest)
+    def state_digest(self, timing=False):
+        """-> dict of Python ints: the plane digests (accumulation, albedo_coverage, normal_depth, moments, direct, bucket: a list of 15), the counts digest, per
+        family (S, AOVs, Q, D, buckets) family_on / family_samples, frame_count, accumulated, num_tiles and the four switch words: two handles in the same state
+        return equal dicts.  timing: also kernel_ms, the digest kernel's own time in this call (a float; not part of the state)."""
+        d = _ffi.StateDigest()
+        check(lib.rf_renderer_state_digest(self._h, C.byref(d)))
+        out = {k: int(getattr(d, k)) for k, _ in d._fields_ if k not in ("bucket", "family_on", "family_samples", "kernel_ms")}
+        out.update(bucket=[int(v) for v in d.bucket], family_on=[int(v) for v in d.family_on], family_samples=[int(v) for v in d.family_samples])
+        if timing:
+            out["kernel_ms"] = float(d.kernel_ms)
+        return out
+
+    def save_checkpoint(self, path=None):
+        """-> the checkpoint blob (bytes).  With a path it is also written there: to a temporary file beside it first, then renamed over it."""
+        n = C.c_uint64(0)
+        check(lib.rf_renderer_save_checkpoint(self._h, None, C.byref(n)))
+        buf = bytearray(n.value)
+        check(lib.rf_renderer_save_checkpoint(self._h, (C.c_char * len(buf)).from_buffer(buf), C.byref(n)))
+        if path is not None:
+            # (the file is written from the buffer the library filled; the one copy made is the bytes object returned)
+            tmp = f"{os.fspath(path)}.tmp{os.getpid()}"
+            with open(tmp, "wb") as f:
+                f.write(buf)
+                f.flush()
+                os.fsync(f.fileno())
+            os.replace(tmp, path)
+        return bytes(buf)
+
+    def load_checkpoint(self, blobs):
+        """One blob (bytes), a path, or a list of either: together they must hold every tile of this handle's shard exactly once (other tiles are ignored).
+        RayfinderError with status RF_ERROR_INVALID_ARGUMENT: refused, the handle unchanged; RF_ERROR_CORRUPT: the accumulation was restarted."""
+        if isinstance(blobs, (bytes, bytearray, memoryview, str, os.PathLike)):
+            blobs = [blobs]
+        arrays = [np.frombuffer(_checkpoint_bytes(b) if isinstance(b, (str, os.PathLike)) else b, np.uint8) for b in blobs]  # (a blob in memory is read where it lies)
+        ptrs = (C.c_void_p * len(arrays))(*[a.ctypes.data for a in arrays])
+        sizes = (C.c_uint64 * len(arrays))(*[a.size for a in arrays])
+        check(lib.rf_renderer_load_checkpoint(self._h, ptrs, sizes, len(arrays)))
+
+    def resume(self, path):
+        """Set the four switches (AOVs, moments, direct, buckets) as the checkpoint's info says, then load it.  -> the info."""
+        blob = _checkpoint_bytes(path)
+        info = checkpoint_info(blob)
+        check(lib.rf_renderer_set_aovs(self._h, info["aov_flags"]))
+        check(lib.rf_renderer_set_moments(self._h, info["moments_on"]))
+        check(lib.rf_renderer_set_direct(self._h, info["direct_word"]))
+        check(lib.rf_renderer_set_buckets(self._h, info["buckets_word"]))
+        self.load_checkpoint(blob)
+        return info
 
     # BVH queries
     def trace_primary_stats(self, camera, width, height):

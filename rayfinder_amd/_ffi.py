@@ -36,6 +36,7 @@ RF_ERROR_INVALID_ARGUMENT = 1
 RF_ERROR_RUNTIME = 2
 RF_ERROR_NO_DEVICE = 3
 RF_ERROR_OUT_OF_RANGE = 4
+RF_ERROR_CORRUPT = 5
 RF_AOV_FIRST_HIT = 1
 RF_AOV_TILE_COUNTS = 0x100
 RF_BUCKETS_TILE_COUNTS = 0x100
@@ -73,6 +74,21 @@ class Camera(C.Structure):
 class Sky(C.Structure):
     _fields_ = [("turbidity", C.c_float), ("albedo", C.c_float * 3), ("sun_zenith_degrees", C.c_float),
                 ("sun_azimuth_degrees", C.c_float)]
+
+
+class StateDigest(C.Structure):
+    _fields_ = [("accumulation", C.c_uint64), ("albedo_coverage", C.c_uint64), ("normal_depth", C.c_uint64), ("moments", C.c_uint64), ("direct", C.c_uint64),
+                ("bucket", C.c_uint64 * 15), ("counts", C.c_uint64), ("family_on", C.c_uint32 * 5), ("family_samples", C.c_uint32 * 5),
+                ("frame_count", C.c_uint32), ("accumulated", C.c_uint32), ("num_tiles", C.c_uint32), ("aov_flags", C.c_uint32), ("moments_on", C.c_uint32),
+                ("direct_word", C.c_uint32), ("buckets_word", C.c_uint32), ("kernel_ms", C.c_float)]
+
+
+class CheckpointInfo(C.Structure):
+    _fields_ = [("version", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("num_tiles", C.c_uint32), ("frame_count", C.c_uint32),
+                ("accumulated", C.c_uint32), ("frame_leading_samples", C.c_uint32), ("frame_min_tile_samples", C.c_uint32),
+                ("aov_flags", C.c_uint32), ("moments_on", C.c_uint32), ("direct_word", C.c_uint32), ("buckets_word", C.c_uint32),
+                ("family_samples", C.c_uint32 * 5), ("family_restarted", C.c_uint32 * 5), ("num_bounces", C.c_uint32), ("stored_planes", C.c_uint32),
+                ("total_bytes", C.c_uint64), ("camera", Camera), ("sky", Sky)]
 
 
 class RenderParameters(C.Structure):
@@ -185,6 +201,10 @@ SIGNATURES = {
     "rf_renderer_shard_tiles": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
     "rf_renderer_accumulation_device_buffer": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
     "rf_renderer_bind_accumulation_buffer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "rf_renderer_state_digest": (C.c_int, [C.c_void_p, C.POINTER(StateDigest)]),
+    "rf_renderer_save_checkpoint": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "rf_checkpoint_info": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(CheckpointInfo)]),
+    "rf_renderer_load_checkpoint": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.c_uint32]),
     "rf_device_count": (C.c_int, [C.POINTER(C.c_int32)]),
     "rf_comm_unique_id": (C.c_int, [C.c_void_p]),
     "rf_comm_create": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32, C.POINTER(C.c_void_p)]),

@@ -38,9 +38,14 @@
 // divide every pixel by its own tile's count, and the split denoiser divides every pixel by its tile's count before it filters.
 // --noise-target t [--noise-check-every k]: stop as soon as the frame's mean error is <= t, checked every k samples (default 8), at --spp at the latest
 // (rf_renderer_render_until).  One GPU only: stopping several ranks in step is not implemented.
+// --checkpoint FILE [--checkpoint-every N]: rf_renderer_save_checkpoint into FILE (a temporary file, then a rename) after every N samples and at the end; with
+// --adaptive / --noise-target after the call.  --resume FILE: the four switches from rf_checkpoint_info, rf_renderer_load_checkpoint, then the render continues to
+// --spp: the images are those of an uninterrupted run.  --gpus 1 only.
 #include "cli_common.hpp"
 
 #include <algorithm>
+#include <cstdio>
+#include <cstdlib>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -72,7 +77,10 @@ int main(int argc, char** argv)
                     "  three images are the adaptive frame's\n"
                     "                 [--noise-map m.pfm] [--noise-target t] [--noise-check-every k]\n"
                     "  --noise-map: the per-pixel relative standard error of the frame (1-channel PFM); --noise-target: stop once the frame's mean error is <= t,\n"
-                    "  checked every k samples (default 8), at --spp at the latest (one GPU only)\n");
+                    "  checked every k samples (default 8), at --spp at the latest (one GPU only)\n"
+                    "                 [--checkpoint FILE] [--checkpoint-every N] [--resume FILE]\n"
+                    "  --checkpoint: save the render's state at the end, and after every N samples with --checkpoint-every (with --adaptive / --noise-target: after the\n"
+                    "  call); --resume: set the sums' switches as the file says, load it and continue to --spp.  --gpus 1 only\n");
         return 0;
     }
     uint32_t    W = 1920, H = 1080, spp = 64, bounces = 2; // UI defaults src/pt/main.cpp:46-60
@@ -95,6 +103,8 @@ int main(int argc, char** argv)
     bool        bucketsTileCounts = false;
     std::string robustMean, trimMap, denoiseRobust;
     std::string directPfm, indirectPfm, denoiseSplit;
+    std::string checkpointPath, resumePath;
+    uint32_t    checkpointEvery = 0;
     for (int i = 2; i < argc; i += 2)
     {
         // (the one switch without a value)
@@ -142,6 +152,9 @@ int main(int argc, char** argv)
         else if (k == "--direct") directPfm = val;
         else if (k == "--indirect") indirectPfm = val;
         else if (k == "--denoise-split") denoiseSplit = val;
+        else if (k == "--checkpoint") checkpointPath = val;
+        else if (k == "--checkpoint-every") checkpointEvery = static_cast<uint32_t>(std::max(0, std::atoi(val)));
+        else if (k == "--resume") resumePath = val;
         else
         {
             std::fprintf(stderr, "unknown option %s\n", k.c_str());
@@ -180,6 +193,33 @@ int main(int argc, char** argv)
     {
         std::fprintf(stderr, "--direct / --indirect / --denoise-split need --gpus 1 (the direct sums are not carried by the frame gather)\n");
         return 1;
+    }
+    if ((!checkpointPath.empty() || !resumePath.empty()) && gpus > 1)
+    {
+        std::fprintf(stderr, "--checkpoint / --resume need --gpus 1 (saving and loading one blob per rank is not wired into this tool; rf_renderer_save_checkpoint and "
+                             "rf_renderer_load_checkpoint work on tile-sharded handles)\n");
+        return 1;
+    }
+    if (checkpointEvery != 0u && checkpointPath.empty())
+    {
+        std::fprintf(stderr, "--checkpoint-every needs --checkpoint FILE\n");
+        return 1;
+    }
+    // --resume: the file is read and its header checked before the scene is loaded
+    std::vector<unsigned char> resumeBlob;
+    struct rf_checkpoint_info  resumeInfo{};
+    if (!resumePath.empty())
+    {
+        std::FILE* f = std::fopen(resumePath.c_str(), "rb");
+        if (!f)
+        {
+            std::fprintf(stderr, "cannot open %s\n", resumePath.c_str());
+            return 1;
+        }
+        unsigned char chunk[1 << 16];
+        for (size_t got; (got = std::fread(chunk, 1, sizeof chunk, f)) != 0u;) resumeBlob.insert(resumeBlob.end(), chunk, chunk + got);
+        std::fclose(f);
+        rfCheck(rf_checkpoint_info(resumeBlob.data(), resumeBlob.size(), &resumeInfo), "checkpoint info");
     }
     rf_pt_format*     pt = loadScene(argv[1]);
     rf_pt_format_view v;
@@ -255,10 +295,56 @@ int main(int argc, char** argv)
         if (buckets != 0u) rfCheck(rf_renderer_set_buckets(renderer, buckets | (bucketsTileCounts ? RF_BUCKETS_TILE_COUNTS : 0u)), "buckets");
         // (--adaptive: the direct sums follow the per-tile counts too)
         if (direct) rfCheck(rf_renderer_set_direct(renderer, static_cast<int>(1u | (adaptive ? RF_DIRECT_TILE_COUNTS : 0u))), "direct sums");
+        // --resume: the four switches as the checkpoint's header has them, then the load; the render continues to --spp
+        uint32_t resumed = 0;
+        if (!resumeBlob.empty())
+        {
+            rfCheck(rf_renderer_set_aovs(renderer, resumeInfo.aov_flags), "AOVs of the checkpoint");
+            rfCheck(rf_renderer_set_moments(renderer, static_cast<int>(resumeInfo.moments_on)), "moments of the checkpoint");
+            rfCheck(rf_renderer_set_direct(renderer, static_cast<int>(resumeInfo.direct_word)), "direct sums of the checkpoint");
+            rfCheck(rf_renderer_set_buckets(renderer, resumeInfo.buckets_word), "buckets of the checkpoint");
+            const void* const blobs[1] = {resumeBlob.data()};
+            const uint64_t    sizes[1] = {resumeBlob.size()};
+            rfCheck(rf_renderer_load_checkpoint(renderer, blobs, sizes, 1), "load checkpoint");
+            resumed = resumeInfo.accumulated;
+        }
+        // --checkpoint: the blob to a temporary file beside the target, then renamed over it
+        const auto saveCheckpoint = [&] {
+            if (checkpointPath.empty()) return;
+            uint64_t bytes = 0;
+            rfCheck(rf_renderer_save_checkpoint(renderer, nullptr, &bytes), "checkpoint size");
+            std::vector<unsigned char> blob(bytes);
+            rfCheck(rf_renderer_save_checkpoint(renderer, blob.data(), &bytes), "save checkpoint");
+            const std::string tmp = checkpointPath + ".tmp";
+            std::FILE*        f = std::fopen(tmp.c_str(), "wb");
+            const bool        ok = f && std::fwrite(blob.data(), 1, bytes, f) == bytes;
+            if (f) std::fclose(f);
+            if (!ok || std::rename(tmp.c_str(), checkpointPath.c_str()) != 0)
+            {
+                std::fprintf(stderr, "cannot write %s\n", checkpointPath.c_str());
+                std::exit(1);
+            }
+        };
         const auto t0 = std::chrono::steady_clock::now();
         if (adaptive) rfCheck(rf_renderer_render_adaptive(renderer, &adaptiveParams, &adaptiveResult), "adaptive render");
-        else if (noiseTargetSet) rfCheck(rf_renderer_render_until(renderer, noiseTarget, noiseCheckEvery, spp, &sppReached, &estimate), "render to the noise target");
-        else rfCheck(rf_renderer_render(renderer, spp), "render");
+        else if (noiseTargetSet)
+        {
+            rfCheck(rf_renderer_render_until(renderer, noiseTarget, noiseCheckEvery, spp - std::min(spp, resumed), &sppReached, &estimate), "render to the noise target");
+            sppReached += resumed;
+        }
+        else
+        {
+            // (in steps of --checkpoint-every samples, a checkpoint after each: the samples and their order are those of one call)
+            uint32_t todo = spp - std::min(spp, resumed);
+            while (todo != 0u)
+            {
+                const uint32_t n = checkpointEvery != 0u ? std::min(checkpointEvery, todo) : todo;
+                rfCheck(rf_renderer_render(renderer, n), "render");
+                todo -= n;
+                if (checkpointEvery != 0u && todo != 0u) saveCheckpoint();
+            }
+        }
+        saveCheckpoint();
         // (several ranks: the sums the outputs need travel with the image, in the one exchange)
         void* gathered = nullptr;
         if (comm) rfCheck(rf_renderer_gather_frame(renderer, comm, 0, (aovs ? RF_GATHER_AOVS : 0u) | (!noiseMap.empty() ? RF_GATHER_MOMENTS : 0u), &gathered), "gather");

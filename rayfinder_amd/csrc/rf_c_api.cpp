@@ -5,6 +5,7 @@
 #include "rf_bvh.hpp"
 #include "rf_bvh_gpu.hpp"
 #include "rf_camera.hpp"
+#include "rf_checkpoint.hpp"
 #include "rf_comm.hpp"
 #include "rf_gltf.hpp"
 #include "rf_pt_format.hpp"
@@ -67,6 +68,11 @@ int guarded(F&& f)
     {
         gLastError = "out of host memory";
         return RF_ERROR_RUNTIME;
+    }
+    catch (const rf::CheckpointCorrupt& e)
+    {
+        gLastError = e.what();
+        return RF_ERROR_CORRUPT;
     }
     catch (const std::exception& e)
     {
@@ -748,6 +754,62 @@ int rf_renderer_bind_accumulation_buffer(rf_renderer* r, void* device_ptr, uint6
     return guarded([&] {
         require(r, "null argument");
         r->impl->bindAccumulationBuffer(device_ptr, bytes);
+        return RF_OK;
+    });
+}
+
+// ---------------------------------------------------------------------------------------- state digest and checkpoints
+int rf_renderer_state_digest(rf_renderer* r, rf_state_digest* out)
+{
+    return guarded([&] {
+        require(r && out, "null argument");
+        const rf::StateDigest d = rf::stateDigest(*r->impl);
+        *out = rf_state_digest{};
+        out->accumulation = d.plane[0], out->albedo_coverage = d.plane[1], out->normal_depth = d.plane[2], out->moments = d.plane[3], out->direct = d.plane[4];
+        for (uint32_t b = 0; b < 15; ++b) out->bucket[b] = d.plane[5 + b];
+        out->counts = d.counts;
+        for (uint32_t f = 0; f < 5; ++f) out->family_on[f] = d.familyOn[f], out->family_samples[f] = d.familySamples[f];
+        out->frame_count = d.frameCount, out->accumulated = d.accumulated, out->num_tiles = d.numTiles;
+        out->aov_flags = d.aovFlags, out->moments_on = d.moments, out->direct_word = d.directWord, out->buckets_word = d.bucketsWord;
+        out->kernel_ms = d.kernelMs;
+        return RF_OK;
+    });
+}
+
+int rf_renderer_save_checkpoint(rf_renderer* r, void* dst, uint64_t* bytes)
+{
+    return guarded([&] {
+        require(r && bytes, "null argument");
+        rf::saveCheckpoint(*r->impl, dst, bytes);
+        return RF_OK;
+    });
+}
+
+int rf_checkpoint_info(const void* blob, uint64_t bytes, struct rf_checkpoint_info* out)
+{
+    return guarded([&] {
+        require(blob && out, "null argument");
+        const rf::ckpt::View    v = rf::ckpt::parse(blob, bytes);
+        const rf::ckpt::Header& h = v.header;
+        std::memset(out, 0, sizeof *out);
+        out->version = h.version, out->width = h.width, out->height = h.height, out->num_tiles = h.numTiles, out->frame_count = h.frameCount, out->accumulated = h.accumulated;
+        out->frame_leading_samples = h.frameLeadingSamples, out->frame_min_tile_samples = h.frameMinTileSamples;
+        out->aov_flags = h.aovFlags, out->moments_on = h.moments, out->direct_word = h.directWord, out->buckets_word = h.bucketsWord;
+        for (uint32_t f = 0; f < 5; ++f) out->family_samples[f] = h.family[f].samples, out->family_restarted[f] = h.family[f].restarted;
+        out->num_bounces = h.numBounces, out->stored_planes = v.numPlanes, out->total_bytes = h.totalBytes;
+        static_assert(sizeof out->camera == sizeof h.camera && sizeof out->sky == sizeof h.sky);
+        std::memcpy(&out->camera, h.camera, sizeof h.camera);
+        std::memcpy(&out->sky, h.sky, sizeof h.sky);
+        return RF_OK;
+    });
+}
+
+int rf_renderer_load_checkpoint(rf_renderer* r, const void* const* blobs, const uint64_t* sizes, uint32_t count)
+{
+    return guarded([&] {
+        require(r && blobs && sizes && count > 0, "null argument");
+        for (uint32_t i = 0; i < count; ++i) require(blobs[i] != nullptr, "null blob");
+        rf::loadCheckpoint(*r->impl, blobs, sizes, count);
         return RF_OK;
     });
 }

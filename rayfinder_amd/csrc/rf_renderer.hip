@@ -183,6 +183,10 @@ struct Renderer::Impl
     uint32_t         maxWidth = 0, maxHeight = 0;
     uint32_t         frameCount = 0, accumulated = 0;
     uint32_t         rank = 0, worldSize = 1;
+    // a checkpoint's scene guard (checkpointBooks): the counts of BVH nodes, triangles, textures and texels the handle was created with, and the root node's box
+    uint64_t         sceneCounts[4] = {};
+    uint32_t         sceneRootBounds[6] = {};
+    DeviceBuffer<uint64_t> checkpointWork; // the state digest's tile words and, behind them, its tile table (checkpointScratch): grown on demand, kept
 
     std::vector<uint32_t>   tiles;
     DeviceBuffer<uint32_t>  tileIds; // the tile list of the next batch: the shard's own (configureShard) or an active list (uploadTileList), and behind the ids each tile's slot in the shard
@@ -1303,6 +1307,14 @@ Renderer::Renderer(const RendererDescriptor& desc, const SceneView& sceneView) :
     // child links, leaf ranges and texture indices are followed blindly on the device: check them once here
     validateScene(sceneView.bvhNodes, sceneView.positionAttributes.size(), sceneView.vertexAttributes, sceneView.baseColorTextures.size());
     m.sortScale = static_cast<uint32_t>(std::min<uint64_t>((static_cast<uint64_t>(kSortBins) << 32) / std::max<uint64_t>(sceneView.positionAttributes.size(), 1), 0xFFFFFFFFull));
+    {
+        uint64_t texelCount = 0;
+        for (const TextureView& t : sceneView.baseColorTextures) texelCount += static_cast<uint64_t>(t.width) * t.height;
+        m.sceneCounts[0] = sceneView.bvhNodes.size(), m.sceneCounts[1] = sceneView.positionAttributes.size(), m.sceneCounts[2] = sceneView.baseColorTextures.size(), m.sceneCounts[3] = texelCount;
+        const Aabb& root = sceneView.bvhNodes[0].aabb;
+        const float bounds[6] = {root.min.x, root.min.y, root.min.z, root.max.x, root.max.y, root.max.z};
+        std::memcpy(m.sceneRootBounds, bounds, sizeof bounds);
+    }
 
     // 48-B reference nodes -> 32-B device nodes
     bool                  treeNestedRegular = false; // every child's box inside its parent's, all finite and ordered (buildWide)
@@ -2197,6 +2209,73 @@ const void* Renderer::enqueueShardRobustMean(const uint32_t* slotCounts)
     }
     enqueueRobustMeanShard(m.stream, m.bucketPlanes(), m.bucketStride(), static_cast<uint32_t>(m.tiles.size()), buckets(), m.accumulated, m.robustShard.ptr, slotCounts);
     return m.robustShard.ptr;
+}
+
+void* Renderer::checkpointScratch(uint64_t bytes)
+{
+    Impl& m = *mImpl;
+    if (m.checkpointWork.count * sizeof(uint64_t) < bytes)
+    {
+        synchronize(); // (an earlier digest may still use the smaller one)
+        m.checkpointWork.alloc((bytes + sizeof(uint64_t) - 1) / sizeof(uint64_t));
+    }
+    return m.checkpointWork.ptr;
+}
+
+Renderer::CheckpointBooks Renderer::checkpointBooks(bool prepare)
+{
+    Impl& m = *mImpl;
+    const uint64_t pixelsPadded = prepare ? static_cast<uint64_t>(m.tiles.size()) * 1024 : 0u;
+    if (prepare) synchronize();
+    if (pixelsPadded != 0u) m.clearStaleSums(pixelsPadded);
+    CheckpointBooks b;
+    b.frameCount = m.frameCount, b.accumulated = m.accumulated, b.frameLeadingSamples = m.frameLeadingSamples, b.frameMinTileSamples = m.frameMinTileSamples;
+    b.aovFlags = m.aovFlags, b.moments = m.momentSums.on ? 1u : 0u, b.directWord = m.directFlags;
+    b.bucketsWord = buckets() == 0u ? 0u : (buckets() | (m.bucketTileCounts ? kBucketsTileCounts : 0u) | (m.bucketShardTileCounts ? kBucketsShardTileCounts : 0u));
+    const SumChannel* const channels[5] = {&m.imageSums, &m.aovSums, &m.momentSums, &m.directSums, &m.bucketSums};
+    for (uint32_t f = 0; f < 5; ++f) b.family[f] = {channels[f]->on, (!channels[f]->on || channels[f]->dirty) ? 0u : channels[f]->samples};
+    b.family[0].samples = m.accumulated; // (the image keeps no count of its own)
+    b.tileSamples = m.nonUniform() ? m.tileSamples : std::vector<uint32_t>(m.tiles.size(), m.accumulated);
+    if (pixelsPadded != 0u)
+    {
+        b.planes[0] = m.image;
+        if (m.aovSums.on) b.planes[1] = m.aovAlbedoCoverage(), b.planes[2] = m.aovNormalDepth();
+        if (m.momentSums.on) b.planes[3] = m.moments();
+        if (m.directSums.on) b.planes[4] = m.direct();
+        for (uint32_t k = 0; k < buckets(); ++k) b.planes[5 + k] = m.bucketPlanes() + k * m.bucketStride();
+    }
+    static_assert(sizeof(Camera) == sizeof b.camera && sizeof(float) * 6 == sizeof b.sky);
+    std::memcpy(b.camera, &m.params.camera, sizeof b.camera);
+    const float sky[6] = {m.params.sky.turbidity, m.params.sky.albedo[0], m.params.sky.albedo[1], m.params.sky.albedo[2], m.params.sky.sunZenithDegrees, m.params.sky.sunAzimuthDegrees};
+    std::memcpy(b.sky, sky, sizeof sky);
+    b.numBounces = m.params.samplingParams.numBounces, b.samplesPerPixel = m.params.samplingParams.numSamplesPerPixel;
+    std::memcpy(b.sceneCounts, m.sceneCounts, sizeof b.sceneCounts);
+    std::memcpy(b.rootBounds, m.sceneRootBounds, sizeof b.rootBounds);
+    return b;
+}
+
+void Renderer::checkpointRestart(bool zeroNow)
+{
+    Impl& m = *mImpl;
+    synchronize();
+    m.restartAccumulation();
+    const uint64_t pixelsPadded = static_cast<uint64_t>(m.tiles.size()) * 1024;
+    if (zeroNow && pixelsPadded != 0u) m.clearStaleSums(pixelsPadded);
+}
+
+void Renderer::checkpointAdopt(const CheckpointBooks& b)
+{
+    Impl& m = *mImpl;
+    if (b.tileSamples.size() != m.tiles.size()) throw std::logic_error("checkpointAdopt: one count per tile of the shard");
+    m.frameCount = b.frameCount;
+    m.accumulated = b.accumulated;
+    SumChannel* const channels[5] = {&m.imageSums, &m.aovSums, &m.momentSums, &m.directSums, &m.bucketSums};
+    for (uint32_t f = 1; f < 5; ++f)
+        if (channels[f]->on) channels[f]->samples = b.family[f].samples;
+    const bool uniform = std::all_of(b.tileSamples.begin(), b.tileSamples.end(), [&](uint32_t c) { return c == b.accumulated; });
+    if (uniform) m.tileSamples.clear();
+    else m.tileSamples = b.tileSamples;
+    m.frameLeadingSamples = b.frameLeadingSamples, m.frameMinTileSamples = b.frameMinTileSamples;
 }
 
 void Renderer::clearAccumulationIfStale()

@@ -384,6 +384,34 @@ public:
     // slotCounts != nullptr -- the non-uniform state; the caller has checked kBucketsShardTileCounts and that every tile holds >= K samples --: what
     // shardTileSamplesDevice() returned, and kRobustMeanShardTiles combines every slot with its own count.
     const void* enqueueShardRobustMean(const uint32_t* slotCounts = nullptr);
+    // The checkpoint seam (rf_checkpoint.hip: the state digest, save and load are written against these three calls and the public reads alone).
+    // checkpointBooks: waits for the stream, zeroes every restarted sum that is on as the next sample would (so that a restarted family lies in device memory as the
+    // zeros its read returns), and -> the books a checkpoint carries and the compact tile-major planes as they lie (device pointers; nullptr: off, or a shard without a tile).
+    // checkpointRestart: a new accumulation (restartAccumulation; the frame counter stays) and, zeroNow, every sum that is on sized for the shard and zeroed at once: what a load copies into.
+    // checkpointAdopt: the books of a load whose planes lie in device memory and have been verified: the frame counter, the accumulated count, each family's own count,
+    // the per-slot tile counts (stored only while they differ from the accumulated count) and the frame-level pair.
+    struct CheckpointBooks
+    {
+        struct Family
+        {
+            bool     on;
+            uint32_t samples; // 0: restarted (its read returns zeros)
+        };
+        uint32_t              frameCount = 0, accumulated = 0, frameLeadingSamples = 0, frameMinTileSamples = 0;
+        uint32_t              aovFlags = 0, moments = 0, directWord = 0, bucketsWord = 0;
+        Family                family[5] = {}; // S, the AOVs, Q, D, the buckets
+        std::vector<uint32_t> tileSamples;    // one count per tile of the shard, in slot order (the uniform state: the accumulated count)
+        const void*           planes[20] = {}; // S, AC, ND, Q, D, bucket 0 .. 14
+        uint32_t              camera[19] = {}, sky[6] = {}, numBounces = 0, samplesPerPixel = 0; // the render-parameter guard, as bit patterns, and the cap
+        uint64_t              sceneCounts[4] = {}; // BVH nodes, triangles, textures, texels
+        uint32_t              rootBounds[6] = {};  // the root node's box, as bit patterns
+    };
+    // prepare == false: the books alone, as they stand -- no device call, nothing zeroed, planes all nullptr (what a load compares a blob's guards with before it
+    // touches anything).  checkpointScratch: device memory of at least `bytes` that the handle keeps between digests (the tile words and the tile table).
+    CheckpointBooks checkpointBooks(bool prepare = true);
+    void*           checkpointScratch(uint64_t bytes);
+    void            checkpointRestart(bool zeroNow);
+    void            checkpointAdopt(const CheckpointBooks& books);
     // Zero the accumulation buffer (on the handle's stream) if nothing has been rendered into it since the last reset, so that a
     // reader on the device (the frame exchange) never sees the previous frame's sums.
     void     clearAccumulationIfStale();
