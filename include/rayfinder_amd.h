@@ -1052,11 +1052,15 @@ RF_API int rf_bvh_visualizer_pass(const rf_camera* camera, uint32_t width, uint3
  * CPU-side scene preparation (host code, runs without a GPU)
  * ------------------------------------------------------------------------------------------ */
 /* Bvh buildBvh(std::span<const Positions>) (src/common/bvh.hpp:33, bvh.cpp:263-291).
- * nodes_out: room for 2*num_triangles 48-B nodes; triangle_indices_out[src] = leaf-order index. */
+ * nodes_out: room for 2*num_triangles 48-B nodes; triangle_indices_out[src] = leaf-order index.
+ * RF_ERROR_INVALID_ARGUMENT, nothing written, when a position is NaN or infinite (the message names the first such triangle);
+ * so do rf_build_bvh_gpu, decided on the host before the device is touched, and the bakes (rf_pt_format_from_gltf /
+ * _from_triangles) with either builder. */
 RF_API int rf_build_bvh(const float* positions36, uint64_t num_triangles, void* nodes_out, uint64_t* num_nodes_out,
                         uint64_t* triangle_indices_out, int32_t* depth_out /* NULL ok */);
 
-/* The same build on the GPU (device_ordinal): identical node bytes and identical triangle_indices_out
+/* The same build on the GPU (device_ordinal): identical node bytes -- except the sign of a zero box coordinate where a
+ * node holds both -0 and +0 at that extreme (rf_bvh_gpu.hip header), which no ray can see -- and identical triangle_indices_out
  * (the order inside multi-triangle leaves decides closest-hit ties between coincident triangles; the
  * reference's is whatever its standard library's std::partition leaves -- rf_build_bvh uses libstdc++'s,
  * and the GPU builder reproduces that permutation).  Replaces the

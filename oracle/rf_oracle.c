@@ -181,8 +181,10 @@ static inline size_t bucket_of(const Prim* p, int axis, Box centroidAabb)
     const size_t numBuckets = 12;
     float  q = (float)numBuckets * (v3_get(p->centroid, axis) - v3_get(centroidAabb.min, axis)) /
               (v3_get(centroidAabb.max, axis) - v3_get(centroidAabb.min, axis));
-    size_t b = (size_t)q;
-    return b < numBuckets - 1 ? b : numBuckets - 1;
+    /* NaN, +inf or >= 11: the last bucket, decided before the conversion (undefined for such a float; the reference is
+     * undefined there).  A documented choice, the same expression in the product's two builders (rf_bvh.cpp::bucketIndex,
+     * rf_bvh_gpu.hip::bucketOf). */
+    return !(q < (float)(numBuckets - 1)) ? numBuckets - 1 : (size_t)q;
 }
 
 static size_t build_recursive(BuildCtx* c, Prim* prims, size_t count, size_t orderedOffset, int depth)

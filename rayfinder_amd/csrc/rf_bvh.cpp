@@ -16,6 +16,7 @@
 #include "rf_aabb.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <limits>
 #include <stdexcept>
 #include <string>
@@ -40,8 +41,12 @@ inline std::size_t bucketIndex(const Primitive& p, int axis, const Box& centers)
 {
     // bvh.cpp:152-155 -- float(12) * (c - min) / (max - min), evaluated left to right
     const float       q = static_cast<float>(kBuckets) * (p.center[axis] - centers.lo[axis]) / (centers.hi[axis] - centers.lo[axis]);
-    const std::size_t b = static_cast<std::size_t>(q);
-    return std::min(b, kBuckets - 1);
+    // A quotient that is NaN, +inf or >= 11 goes to the last bucket BEFORE the conversion: converting such a float to an
+    // integer is undefined, and x86 and gfx950 resolve it oppositely (cvttss2si gives the "indefinite" value, v_cvt_u32_f32
+    // saturates).  q is +inf when 12 * (c - min) overflows under a finite extent, NaN at c == max once max - min itself
+    // overflows; it is never negative.  A documented choice (the reference is undefined there), the same expression in
+    // rf_bvh_gpu.hip::bucketOf and the test oracle's bucket_of; DESIGN.md, float policy.
+    return !(q < static_cast<float>(kBuckets - 1)) ? kBuckets - 1 : static_cast<std::size_t>(q);
 }
 
 struct Task
@@ -54,11 +59,21 @@ struct Task
 };
 } // namespace
 
+void requireFinitePositions(std::span<const Positions> triangles)
+{
+    static_assert(sizeof(Positions) == 9 * sizeof(float));
+    const float* const f = reinterpret_cast<const float*>(triangles.data());
+    for (std::size_t i = 0; i < 9 * triangles.size(); ++i)
+        if (!std::isfinite(f[i]))
+            throw std::invalid_argument("triangle " + std::to_string(i / 9) + " has a non-finite position (NaN or infinity): the BVH builders refuse it");
+}
+
 Bvh buildBvh(std::span<const Positions> triangles)
 {
     Bvh               out;
     const std::size_t n = triangles.size();
     if (n == 0) return out;
+    requireFinitePositions(triangles);
 
     std::vector<Primitive> prims(n);
     for (std::size_t i = 0; i < n; ++i)

@@ -20,6 +20,11 @@ struct Bvh
 
 Bvh buildBvh(std::span<const Positions> triangles);
 
+// Throws std::invalid_argument naming the first triangle with a NaN or infinite coordinate.  Both builders call it first
+// (the GPU one before it touches the device): with a NaN in play the boxes stop being a function of the SET of triangles
+// (minf / maxf keep whichever operand came first, the GPU's integer atomics order NaN above +inf), so no tree is defined.
+void requireFinitePositions(std::span<const Positions> triangles);
+
 // Structural check of a flattened BVH + attribute arrays that come from outside (a .pt file, the C ABI).
 // The reference leans on WGSL robust buffer access for malformed scenes; HIP has none, so a scene is
 // validated once before it is uploaded.  Throws std::runtime_error naming the first violation:

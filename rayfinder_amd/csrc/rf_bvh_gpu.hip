@@ -37,8 +37,14 @@
 // smaller).  Result: triangleIndices -- and therefore a whole baked .pt -- equals the host builder's
 // byte for byte (tests/test_gpu_bvh_build.py), coincident triangles included.
 //
-// Difference from the host builder that remains: the sign of a zero box coordinate when a node holds
-// both -0.0f and +0.0f (the host keeps whichever its merge order met first).
+// Difference from the host builder that remains: the sign of a zero box coordinate when the boxes of a
+// node's triangles hold both -0.0f and +0.0f at the extreme of that coordinate (a triangle's own box is
+// boundsOf on both sides).  Every node box here is a min / max over the integer order of the encodings, in
+// which -0 < +0: the box takes -0 for a min and +0 for a max.  The host keeps whichever its fold met first.  No ray can see it (tests/test_gpu_bvh_edges.py pins the rule, the
+// traversal counters and a rendered image).
+//
+// Non-finite positions are refused by both builders (requireFinitePositions, rf_bvh.hpp); the bucket of a
+// non-finite quotient, which finite but enormous extents still produce, is defined at bucketOf.
 #include "rf_bvh_gpu.hpp"
 
 #include "rf_aabb.hpp"
@@ -84,6 +90,24 @@ __device__ __forceinline__ Box decodeBox(const EncBox& e)
     b.lo = vec3(decodeFloat(e.lo[0]), decodeFloat(e.lo[1]), decodeFloat(e.lo[2]));
     b.hi = vec3(decodeFloat(e.hi[0]), decodeFloat(e.hi[1]), decodeFloat(e.hi[2]));
     return b;
+}
+__host__ __device__ __forceinline__ EncBox emptyEncBox()
+{
+    EncBox e;
+    for (int k = 0; k < 3; ++k)
+    {
+        e.lo[k] = encodeFloat(FLT_MAX);
+        e.hi[k] = encodeFloat(-FLT_MAX);
+    }
+    return e;
+}
+__device__ __forceinline__ void mergeEnc(EncBox& a, const EncBox& b)
+{
+    for (int k = 0; k < 3; ++k)
+    {
+        a.lo[k] = min(a.lo[k], b.lo[k]);
+        a.hi[k] = max(a.hi[k], b.hi[k]);
+    }
 }
 // A triangle in flight: bounds, centroid, source index.  Two float4 + one float2 streams, moved
 // physically by every partition so that each pass reads them coalesced.
@@ -148,8 +172,10 @@ __device__ __forceinline__ uint32_t bucketOf(float c, float cmin, float cmax)
 {
     // bvh.cpp:152-155 -- float(12) * (c - min) / (max - min), evaluated left to right
     const float    q = static_cast<float>(kBuckets) * (c - cmin) / (cmax - cmin);
-    const uint32_t b = static_cast<uint32_t>(q);
-    return b < kBuckets - 1 ? b : kBuckets - 1;
+    // NaN, +inf or >= 11: the last bucket, decided BEFORE the conversion.  Undefined in C++ for such a float, and the two
+    // targets resolve it oppositely (v_cvt_u32_f32 saturates: inf -> 11, NaN -> 0; x86's cvttss2si: inf -> 0, NaN -> 11).
+    // A documented choice, the same expression as rf_bvh.cpp::bucketIndex and the test oracle's bucket_of.
+    return !(q < static_cast<float>(kBuckets - 1)) ? kBuckets - 1 : static_cast<uint32_t>(q);
 }
 
 // Leaf test of bvh.cpp:111-121 (single triangles are handled by the callers).
@@ -159,6 +185,15 @@ __device__ __forceinline__ bool mustBeLeaf(const Box& box, const Box& centers, i
 }
 
 // The SAH sweep of bvh.cpp:162-206 over 12 filled buckets.  Returns false when the node becomes a leaf.
+//
+// Termination of the level loop (`while (active > 0)` in buildBvhGpu) and of kSmall's stack for ANY finite input, extents
+// that overflow included: a split that is chosen has both sides non-empty.  Were the buckets 0..i all empty, `box` would
+// still be the merge of empty boxes, [lowest, max] by the two-point constructor's min AND max (rf_aabb.hpp), whose area
+// is +inf; 0 * inf = NaN, so cost[i] is NaN and never `< best`.  The same for an empty side above.  So every split hands
+// each child fewer triangles than the node had, the depth is at most n, and where no cost is finite the node becomes a
+// leaf below.  The histogram and the partition predicate both go through bucketOf, so the counts the sweep saw are the
+// counts the partition produces.  The host builder and the test oracle take the same decisions: their depth on an input is the
+// number of levels here.
 __device__ __forceinline__ bool chooseSplit(const uint32_t (&bucketCount)[kBuckets], const Box (&bucketBox)[kBuckets], const Box& nodeBox,
                                             uint32_t count, uint32_t& bestBucket)
 {
@@ -424,24 +459,29 @@ __global__ void kSplitLarge(uint32_t numLevelNodes, LevelNode* level, const Buck
         l.leftNext = l.rightNext = kNone;
         return; // GNode keeps axis = kNone: leaf over [first, first + count)
     }
+    // The children's boxes are unions of bucket boxes, taken on the ENCODINGS like every other box of this file, so that a
+    // zero coordinate's sign follows the one rule of the file header (-0 for a min, +0 for a max when the set holds both)
+    // instead of the bucket order a float min / max would keep.  The values are the same either way.
     uint32_t leftCount = 0;
-    Box      leftBox, rightBox, leftCenters, rightCenters;
+    EncBox   leftEnc = emptyEncBox(), rightEnc = emptyEncBox(), leftCentersEnc = emptyEncBox(), rightCentersEnc = emptyEncBox();
     for (uint32_t k = 0; k < kBuckets; ++k)
     {
         if (bucketCount[k] == 0) continue; // an empty bucket's boxes are the merge identity
-        const Box cb = decodeBox(buckets[static_cast<size_t>(i) * kBuckets + k].centers);
+        const Bucket& bk = buckets[static_cast<size_t>(i) * kBuckets + k];
         if (k <= best)
         {
             leftCount += bucketCount[k];
-            leftBox = merge(leftBox, bucketBox[k]);
-            leftCenters = merge(leftCenters, cb);
+            mergeEnc(leftEnc, bk.bounds);
+            mergeEnc(leftCentersEnc, bk.centers);
         }
         else
         {
-            rightBox = merge(rightBox, bucketBox[k]);
-            rightCenters = merge(rightCenters, cb);
+            mergeEnc(rightEnc, bk.bounds);
+            mergeEnc(rightCentersEnc, bk.centers);
         }
     }
+    const Box leftBox = decodeBox(leftEnc), rightBox = decodeBox(rightEnc);
+    const Box leftCenters = decodeBox(leftCentersEnc), rightCenters = decodeBox(rightCentersEnc);
     l.split = 1;
     l.bestBucket = best;
     l.leftCount = leftCount;
@@ -876,6 +916,7 @@ Bvh buildBvhGpu(std::span<const Positions> triangles, int deviceOrdinal, float* 
     if (n64 == 0) return out;
     if (n64 >= (1ull << 31)) throw std::runtime_error("buildBvhGpu: too many triangles");
     const uint32_t n = static_cast<uint32_t>(n64);
+    requireFinitePositions(triangles); // decided on the host, before the device is touched (rf_bvh.hpp)
     int              deviceCount = 0;
     const hipError_t countErr = hipGetDeviceCount(&deviceCount);
     if (countErr != hipSuccess || deviceCount == 0)

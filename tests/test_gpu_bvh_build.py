@@ -7,6 +7,11 @@ wgsl:508), so the GPU builder reproduces the permutation of libstdc++'s std::par
 std::nth_element that the host builder and the oracle inherit (SURVEY.md Appendix A, H6: the reference's
 own order is whatever ITS standard library leaves).  A scene baked with either builder is the same .pt,
 byte for byte.
+
+The one exception: byte-identical except the sign of zero box coordinates (`rf_bvh_gpu.hip` header: a node that
+holds both -0.0f and +0.0f at the extreme of a coordinate gets -0 for the min and +0 for the max on the GPU, the
+first one met on the host), which no ray can see: `tests/test_gpu_bvh_edges.py` pins the rule and shows that.  None
+of the inputs of this file has such a node.
 """
 import numpy as np
 import pytest
