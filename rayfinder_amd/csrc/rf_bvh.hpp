@@ -25,6 +25,21 @@ Bvh buildBvh(std::span<const Positions> triangles);
 // (minf / maxf keep whichever operand came first, the GPU's integer atomics order NaN above +inf), so no tree is defined.
 void requireFinitePositions(std::span<const Positions> triangles);
 
+// A scene as it comes from outside: the arrays validateScene checks, packScene (rf_scene_pack.hpp) packs and the renderer uploads
+struct TextureView
+{
+    const uint32_t* pixels;
+    uint32_t        width, height;
+};
+
+struct SceneView
+{
+    std::span<const BvhNode>           bvhNodes;
+    std::span<const PositionAttribute> positionAttributes;
+    std::span<const VertexAttributes>  vertexAttributes;
+    std::span<const TextureView>       baseColorTextures;
+};
+
 // Structural check of a flattened BVH + attribute arrays that come from outside (a .pt file, the C ABI).
 // The reference leans on WGSL robust buffer access for malformed scenes; HIP has none, so a scene is
 // validated once before it is uploaded.  Throws std::runtime_error naming the first violation:

@@ -12,6 +12,7 @@
 #include "rf_query.hpp"
 #include "rf_renderer.hpp"
 #include "rf_sky.hpp"
+#include "rf_wide_build.hpp"
 
 #include <cstring>
 #include <exception>

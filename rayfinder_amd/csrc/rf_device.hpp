@@ -31,6 +31,7 @@ constexpr int      kSpillStack = 72;      // further entries in scratch (total d
 constexpr uint32_t kMiss = 0xFFFFFFFFu;
 constexpr uint32_t kLeafAxis = 3u;
 constexpr uint32_t kTriStride = 4u;     // float4 per device triangle: 48 B of PositionAttribute padded to one 64-B sector
+constexpr uint32_t kSortBins = 256; // kShade<SORTED>: triangle ranges of its counting sort (the host derives sortScale from it: rf_scene_pack.cpp)
 
 struct DeviceScene
 {

@@ -351,9 +351,6 @@ constexpr uint32_t kShadeLastBounce = 1u, kShadeFirstBounce = 2u;
 constexpr uint32_t kShadeSelfShadow = 4u;
 constexpr uint32_t kLookFirstBounce = 1u, kLookNoRayCount = 2u; // kShadowFirstLook's flags
 
-
-constexpr uint32_t kSortBins = 256; // kShade<SORTED>: triangle ranges of its counting sort (the host derives sortScale from it)
-
 // ------------------------------------------------------------------------------------------------
 // Scheduling constants of the persistent traversal kernel (tuned on the atrium, tools/gpu_ab.py).
 // ------------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 // rf_renderer.hip -- wavefront path tracer for MI355X (gfx950): the host driver (the kernels live in rf_trace.hip, rf_shade.hip and rf_sums.hip, what the
-// units share in rf_kernels.hpp).
+// units share in rf_kernels.hpp; the scene's device layouts are built and packed by host-only code, rf_scene_pack.cpp and rf_wide_build.cpp, and uploaded here).
 //
 // The reference traces one full path per fragment-shader invocation
 // (src/pt/reference_path_tracer.wgsl:34-64,180-234).  Here the same per-path arithmetic is cut
@@ -26,6 +26,7 @@
 #include "rf_kernels.hpp"
 #include "rf_noise.hpp"
 #include "rf_robust.hpp"
+#include "rf_scene_pack.hpp"
 #include "rf_sums.hpp"
 
 #include <map>
@@ -1306,234 +1307,55 @@ Renderer::Renderer(const RendererDescriptor& desc, const SceneView& sceneView) :
         throw std::runtime_error("position and vertex attribute counts differ");
     // child links, leaf ranges and texture indices are followed blindly on the device: check them once here
     validateScene(sceneView.bvhNodes, sceneView.positionAttributes.size(), sceneView.vertexAttributes, sceneView.baseColorTextures.size());
-    m.sortScale = static_cast<uint32_t>(std::min<uint64_t>((static_cast<uint64_t>(kSortBins) << 32) / std::max<uint64_t>(sceneView.positionAttributes.size(), 1), 0xFFFFFFFFull));
+    // the device layouts in host memory and the facts about the scene (rf_scene_pack.cpp); everything below copies
+    const PackedScene packed = packScene(sceneView);
     {
-        uint64_t texelCount = 0;
-        for (const TextureView& t : sceneView.baseColorTextures) texelCount += static_cast<uint64_t>(t.width) * t.height;
-        m.sceneCounts[0] = sceneView.bvhNodes.size(), m.sceneCounts[1] = sceneView.positionAttributes.size(), m.sceneCounts[2] = sceneView.baseColorTextures.size(), m.sceneCounts[3] = texelCount;
-        const Aabb& root = sceneView.bvhNodes[0].aabb;
-        const float bounds[6] = {root.min.x, root.min.y, root.min.z, root.max.x, root.max.y, root.max.z};
-        std::memcpy(m.sceneRootBounds, bounds, sizeof bounds);
-    }
-
-    // 48-B reference nodes -> 32-B device nodes
-    bool                  treeNestedRegular = false; // every child's box inside its parent's, all finite and ordered (buildWide)
-    std::vector<uint32_t> quadIndexOfNode; // buildWide's numbering of the quad records, for the occluder-cache entries of the leaves (leafBoxesIntoTriangles)
-    {
-        std::vector<float4> packed(2 * sceneView.bvhNodes.size());
-        for (size_t i = 0; i < sceneView.bvhNodes.size(); ++i)
-        {
-            const BvhNode& n = sceneView.bvhNodes[i];
-            const bool     leaf = n.triangleCount > 0;
-            if (n.triangleCount >= (1u << 30)) throw std::runtime_error("BVH leaf too large");
-            const uint32_t link = leaf ? n.trianglesOffset : n.secondChildOffset;
-            const uint32_t meta = leaf ? ((n.triangleCount << 2) | kLeafAxis) : (n.splitAxis & 3u);
-            if (!leaf && n.splitAxis > 2) throw std::runtime_error("interior BVH node with invalid split axis");
-            packed[2 * i] = make_float4(n.aabb.min.x, n.aabb.min.y, n.aabb.min.z, bitsFloat(link));
-            packed[2 * i + 1] = make_float4(n.aabb.max.x, n.aabb.max.y, n.aabb.max.z, bitsFloat(meta));
-        }
-        m.nodes.upload(packed.data(), packed.size());
-        const WideBuild wb = buildWide(sceneView.bvhNodes.data(), sceneView.bvhNodes.size());
-        quadIndexOfNode = wb.quadIndexOfNode;
-        treeNestedRegular = wb.boxesNested && wb.boxesRegular;
-        m.wideNodes.upload(wb.nodes.data(), wb.nodes.size());
-        m.bigLeaves.upload(wb.bigLeaves.data(), wb.bigLeaves.size());
-        m.wide.nodes = m.wideNodes.ptr;
-        m.wide.compact = nullptr;
+        // (an empty array -- a layout this scene does not get -- uploads as nullptr)
+        const auto up = [](auto& buffer, const auto& host) { buffer.upload(host.data(), host.size()); return buffer.ptr; };
+        const WideBuild& wb = packed.wide;
+        m.wide.nodes = up(m.wideNodes, wb.nodes);
 #if defined(RF_EXP_LEGACY_LAYOUTS)
-        if (wb.compactUsable && !wb.compact.empty())
-        {
-            m.wideCompact.upload(wb.compact.data(), wb.compact.size());
-            m.wide.compact = m.wideCompact.ptr;
-        }
+        m.wide.compact = up(m.wideCompact, wb.compact);
+        m.wide.hot = up(m.wideHot, wb.hot);
+        m.wide.own = up(m.wideOwn, wb.own);
 #endif
-        m.wide.hot = m.wide.own = nullptr;
-#if defined(RF_EXP_LEGACY_LAYOUTS)
-        if (wb.hotUsable && !wb.hot.empty())
-        {
-            m.wideHot.upload(wb.hot.data(), wb.hot.size());
-            m.wideOwn.upload(wb.own.data(), wb.own.size());
-            m.wide.hot = m.wideHot.ptr;
-            m.wide.own = m.wideOwn.ptr;
-        }
-#endif
-        m.wide.quad = nullptr;
-        if (wb.quadUsable && !wb.quad.empty())
-        {
-            m.wideQuad.upload(wb.quad.data(), wb.quad.size());
-            m.wide.quad = m.wideQuad.ptr;
-        }
-        m.wide.quadHalf = nullptr;
+        m.wide.quad = up(m.wideQuad, wb.quad);
+        m.wide.quadHalf = up(m.wideQuadHalf, wb.quadHalf);
         m.wide.originBound = wb.originBound;
-        if (!wb.quadHalf.empty())
-        {
-            m.wideQuadHalf.upload(wb.quadHalf.data(), wb.quadHalf.size());
-            m.wide.quadHalf = m.wideQuadHalf.ptr;
-            // default (rf_wide.hpp, kQuadHalfMaxAreaRatio): the closest-hit launches read the half-precision records unless the binary16
-            // grid is too coarse for this scene; the shadow launches prefer the local-grid records (below)
-            m.optQuadHalfFromBounce = m.optQuadHalfShadowFromBounce = wb.quadHalfAreaRatio <= kQuadHalfMaxAreaRatio ? 1u : 0u;
-            m.quadHalfAreaRatio = wb.quadHalfAreaRatio;
-        }
-        m.wide.quadLocal = nullptr;
-        if (!wb.quadLocal.empty())
-        {
-            m.wideQuadLocal.upload(wb.quadLocal.data(), wb.quadLocal.size());
-            m.wide.quadLocal = m.wideQuadLocal.ptr;
-            // closest-hit: the per-record 8-bit grid where binary16 of absolute coordinates is too coarse (small triangles far from the
-            // origin); shadow: the local grid unless the scene is so finely tessellated that the exact records win (kQuadLocalShadowMaxAreaRatio)
-            const float ratio = wb.quadHalf.empty() ? 2.0f : wb.quadHalfAreaRatio;
-            // (from bounce 2: the coherent launches of bounce 1 gain nothing from it and lose 5 - 25 % in the larger scenes; the shadow launches
-            // of bounce 1 stay on the half-precision records where those suit the scene, on the exact ones elsewhere)
-            m.optQuadLocalFromBounce = m.optQuadHalfFromBounce == 0u ? 2u : 0u;
-            m.optQuadLocalShadowFromBounce = ratio <= kQuadLocalShadowMaxAreaRatio ? 2u : 0u;
-        }
-        m.wide.oct = nullptr;
-        m.treeBytes = static_cast<uint64_t>(wb.quadLocal.size()) * sizeof(uint4) + static_cast<uint64_t>(sceneView.positionAttributes.size()) * kTriStride * sizeof(float4);
-        if (!wb.oct.empty())
-        {
-            m.wideOct.upload(wb.oct.data(), wb.oct.size());
-            m.wide.oct = m.wideOct.ptr;
-            // NOT selected by default: measured 17 % SLOWER than the local-grid quad records on the out-of-cache atrium (profiles/r05_hbm: the launch is bound by
-            // L1 -> L2 requests, and a 112-byte record is two of them per step for 0.65 x the steps); option oct_from_bounce turns it on
-            m.optOctFromBounce = 0u;
-        }
-        m.wide.bigLeaves = m.bigLeaves.ptr;
+        m.wide.quadLocal = up(m.wideQuadLocal, wb.quadLocal);
+        m.wide.oct = up(m.wideOct, wb.oct);
+        m.wide.bigLeaves = up(m.bigLeaves, wb.bigLeaves);
         m.wide.rootLo = wb.rootLo;
         m.wide.rootHi = wb.rootHi;
         m.wide.rootLeaf = wb.rootLeaf;
         m.wide.numRecords = static_cast<uint32_t>(wb.nodes.size() / 4);
-        m.wideUsable = wb.boxesRegular; // NaN / inverted boxes: only the reference-ordered scalar kernels are exact
-    }
-    {
-        // 48-B PositionAttribute -> 64-B aligned device triangles (one L2 sector per triangle test)
-        const size_t        n = sceneView.positionAttributes.size();
-        std::vector<float4> padded(kTriStride * n, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-        for (size_t i = 0; i < n; ++i)
-        {
-            const PositionAttribute& t = sceneView.positionAttributes[i];
-            padded[kTriStride * i] = make_float4(t.p0.x, t.p0.y, t.p0.z, 0.0f);
-            padded[kTriStride * i + 1] = make_float4(t.p1.x, t.p1.y, t.p1.z, 0.0f);
-            padded[kTriStride * i + 2] = make_float4(t.p2.x, t.p2.y, t.p2.z, 0.0f);
-        }
-        // ... and the exact box of every leaf in the spare floats of its first triangle (read by the half-precision quad kernels)
-        {
-            // What the occluder cache remembers per stopped ray: the leaf -- or, where the leaves are small against the sun disc's footprint at the occluder (the
-            // next ray from the same place is stopped by a NEIGHBOUR of that triangle), a record a few levels above it.  Footprint: the disc's 0.51 degrees over a
-            // third of the scene = 0.003 extents; every quad level doubles the patch.  Atrium (18-cm leaves in 30 m): 0 -- the leaf; its x8 tessellation (2.3 cm): 2
-            // (shadow launches -22 % against -2 % with leaves: profiles/r04_occluder/x8_hint_levels.log).
-            std::vector<float> diag;
-            diag.reserve(sceneView.bvhNodes.size() / 2 + 1);
-            for (const BvhNode& nd : sceneView.bvhNodes)
-                if (nd.triangleCount != 0)
-                {
-                    m.maxLeafTriangles = std::max(m.maxLeafTriangles, nd.triangleCount);
-                    const float dx = nd.aabb.max.x - nd.aabb.min.x, dy = nd.aabb.max.y - nd.aabb.min.y, dz = nd.aabb.max.z - nd.aabb.min.z;
-                    diag.push_back(std::sqrt(dx * dx + dy * dy + dz * dz));
-                }
-            const Aabb& root = sceneView.bvhNodes[0].aabb;
-            const float extent = std::max({root.max.x - root.min.x, root.max.y - root.min.y, root.max.z - root.min.z});
-            m.occluderHintLevels = 0;
-            if (!diag.empty() && extent > 0.0f)
-            {
-                std::nth_element(diag.begin(), diag.begin() + diag.size() / 2, diag.end());
-                const float median = diag[diag.size() / 2];
-                if (median > 0.0f && std::isfinite(median) && std::isfinite(extent))
-                    m.occluderHintLevels = static_cast<uint32_t>(std::clamp(static_cast<int>(std::floor(std::log2(0.003f * extent / median))) + 1, 0, 3));
-            }
-            if (const char* v = std::getenv("RF_OCCLUDER_HINT_LEVELS")) m.occluderHintLevels = static_cast<uint32_t>(std::clamp(std::atoi(v), 0, 8)); // experiments
-        }
-        m.leafBoxesValid = leafBoxesIntoTriangles(sceneView.bvhNodes.data(), sceneView.bvhNodes.size(), padded.data(), n, m.occluderHintLevels, &quadIndexOfNode);
-        if (!m.leafBoxesValid)
-        {
-            // leaves that share a first triangle (hand-made tree): one slot cannot hold two exact boxes, so the layouts that cull a leaf by
-            // the box in that slot stay off and the exact records (which carry every box themselves) are used
-            m.wide.quadHalf = m.wide.quadLocal = m.wide.oct = nullptr;
-            m.wideQuadHalf.release(), m.wideQuadLocal.release(), m.wideOct.release();
-            m.optQuadHalfFromBounce = m.optQuadHalfShadowFromBounce = m.optQuadLocalFromBounce = m.optQuadLocalShadowFromBounce = m.optOctFromBounce = 0u;
-        }
-        m.triangles.upload(padded.data(), padded.size());
-    }
-    {
-        // 80-B VertexAttributes (three padded normals, three uvs, texture index, pad) -> 64 B = one L2 sector per shaded hit
-        const size_t        n = sceneView.vertexAttributes.size();
-        std::vector<float4> packed(4 * n);
-        for (size_t i = 0; i < n; ++i)
-        {
-            const VertexAttributes& v = sceneView.vertexAttributes[i];
-            packed[4 * i] = make_float4(v.n0.x, v.n0.y, v.n0.z, v.n1.x);
-            packed[4 * i + 1] = make_float4(v.n1.y, v.n1.z, v.n2.x, v.n2.y);
-            packed[4 * i + 2] = make_float4(v.n2.z, v.uv0.x, v.uv0.y, v.uv1.x);
-            packed[4 * i + 3] = make_float4(v.uv1.y, v.uv2.x, v.uv2.y, bitsFloat(v.textureIdx));
-        }
-        m.attributes.upload(packed.data(), packed.size());
-        // kShade's record: positions + these four float4, 128 B per triangle
-        std::vector<float4> rec(8 * n, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-        for (size_t i = 0; i < n; ++i)
-        {
-            const PositionAttribute& t = sceneView.positionAttributes[i];
-            rec[8 * i] = make_float4(t.p0.x, t.p0.y, t.p0.z, 0.0f);
-            rec[8 * i + 1] = make_float4(t.p1.x, t.p1.y, t.p1.z, 0.0f);
-            rec[8 * i + 2] = make_float4(t.p2.x, t.p2.y, t.p2.z, 0.0f);
-            for (int k = 0; k < 4; ++k) rec[8 * i + 3 + k] = packed[4 * i + k];
-        }
-        // kShadeSelfShadow: the exact box of the leaf a triangle sits in, in the spare floats of its record ({p0 lo.x} {p1 lo.y} {p2 lo.z} ... {hi.xyz, 1}).  Only where the
-        // argument holds (kShade): boxes nested and regular all the way up (buildWide checked every parent / child pair), and the triangle in exactly ONE leaf.
-        m.selfShadowOk = treeNestedRegular;
-        if (m.selfShadowOk)
-        {
-            std::vector<uint8_t> leaves(n, 0);
-            for (const BvhNode& nd : sceneView.bvhNodes)
-                for (uint32_t t = 0; t < nd.triangleCount; ++t)
-                {
-                    const size_t i = static_cast<size_t>(nd.trianglesOffset) + t;
-                    if (i >= n) continue; // (validateScene has rejected this)
-                    const bool regular = std::fabs(nd.aabb.min.x) < 1e30f && std::fabs(nd.aabb.min.y) < 1e30f && std::fabs(nd.aabb.min.z) < 1e30f && std::fabs(nd.aabb.max.x) < 1e30f &&
-                                         std::fabs(nd.aabb.max.y) < 1e30f && std::fabs(nd.aabb.max.z) < 1e30f && nd.aabb.min.x <= nd.aabb.max.x && nd.aabb.min.y <= nd.aabb.max.y &&
-                                         nd.aabb.min.z <= nd.aabb.max.z;
-                    leaves[i] = static_cast<uint8_t>(std::min(leaves[i] + (regular ? 1 : 2), 2));
-                    rec[8 * i].w = nd.aabb.min.x, rec[8 * i + 1].w = nd.aabb.min.y, rec[8 * i + 2].w = nd.aabb.min.z;
-                    rec[8 * i + 7] = make_float4(nd.aabb.max.x, nd.aabb.max.y, nd.aabb.max.z, 0.0f);
-                }
-            for (size_t i = 0; i < n; ++i) rec[8 * i + 7].w = leaves[i] == 1 ? 1.0f : 0.0f;
-        }
-        m.shadeRecords.upload(rec.data(), rec.size());
-    }
-
-    // texture blob + descriptors in the order of the model's textures (reference_path_tracer.cpp:210-270)
-    {
-        std::vector<TextureDescriptor> descs;
-        std::vector<uint32_t>          blob;
-        for (const TextureView& t : sceneView.baseColorTextures)
-        {
-            const uint32_t offset = static_cast<uint32_t>(blob.size());
-            const size_t   n = static_cast<size_t>(t.width) * t.height;
-            blob.insert(blob.end(), t.pixels, t.pixels + n);
-            descs.push_back({t.width, t.height, offset});
-        }
-        // the reference refuses texture blobs above its 1 GiB binding limit (reference_path_tracer.cpp:254-263,
-        // gpu_limits.hpp); HBM has room, but u32 texel offsets cap the blob at 2^32 texels
-        if (blob.size() > 0xFFFFFFFFull) throw std::runtime_error("Texture buffer size exceeds the 32-bit texel offset range.");
-        if (blob.empty()) blob.push_back(0xFFFFFFFFu);
-        if (descs.empty()) descs.push_back({1, 1, 0});
-        m.textureDescriptors.upload(descs.data(), descs.size());
-        m.texels.upload(blob.data(), blob.size());
-    }
-    {
+        m.scene.nodes = up(m.nodes, packed.nodes);
+        m.scene.triangles = up(m.triangles, packed.triangles);
+        m.scene.attributes = up(m.attributes, packed.attributes);
+        m.scene.shadeRecords = up(m.shadeRecords, packed.shadeRecords);
+        m.scene.textureDescriptors = up(m.textureDescriptors, packed.textureDescriptors);
+        m.scene.texels = up(m.texels, packed.texels);
+        m.scene.numTexels = m.texels.count;
         m.blueNoise.upload(blueNoiseTable(), 128 * 128 * 2);
-        float lut[256];
-        for (int i = 0; i < 256; ++i)
-            lut[i] = static_cast<float>(std::pow(static_cast<double>(static_cast<float>(i) / 255.0f), static_cast<double>(2.2f)));
-        m.albedoLut.upload(lut, 256);
+        m.scene.blueNoise = m.blueNoise.ptr;
+        m.scene.albedoLut = up(m.albedoLut, packed.albedoLut);
     }
-    m.scene.nodes = m.nodes.ptr;
-    m.scene.triangles = m.triangles.ptr;
-    m.scene.attributes = m.attributes.ptr;
-    m.scene.shadeRecords = m.shadeRecords.ptr;
-    m.scene.textureDescriptors = m.textureDescriptors.ptr;
-    m.scene.texels = m.texels.ptr;
-    m.scene.numTexels = m.texels.count;
-    m.scene.blueNoise = m.blueNoise.ptr;
-    m.scene.albedoLut = m.albedoLut.ptr;
+    {
+        const SceneFacts& f = packed.facts;
+        std::memcpy(m.sceneCounts, f.sceneCounts, sizeof m.sceneCounts);
+        std::memcpy(m.sceneRootBounds, f.sceneRootBounds, sizeof m.sceneRootBounds);
+        m.sortScale = f.sortScale;
+        m.wideUsable = f.wideUsable;
+        m.leafBoxesValid = f.leafBoxesValid;
+        m.selfShadowOk = f.selfShadowOk;
+        m.maxLeafTriangles = f.maxLeafTriangles;
+        m.occluderHintLevels = f.occluderHintLevels;
+        m.treeBytes = f.treeBytes;
+        m.quadHalfAreaRatio = f.quadHalfAreaRatio;
+        m.optQuadHalfFromBounce = f.quadHalfFromBounce, m.optQuadHalfShadowFromBounce = f.quadHalfShadowFromBounce;
+        m.optQuadLocalFromBounce = f.quadLocalFromBounce, m.optQuadLocalShadowFromBounce = f.quadLocalShadowFromBounce;
+        m.optOctFromBounce = f.octFromBounce;
+    }
 
     DeviceCounters zero{};
     m.counters.upload(&zero, 1);
@@ -2698,358 +2520,6 @@ void Renderer::occludedRays(const float* rays6, uint64_t numRays, float tMax, fl
     RF_HIP(hipGetLastError());
     RF_HIP(hipStreamSynchronize(m.stream));
     RF_HIP(hipMemcpy(visibilityOut, vis.ptr, numRays * 4, hipMemcpyDeviceToHost));
-}
-uint32_t checkWideLayouts(std::span<const BvhNode> nodes, float* quadHalfAreaRatio)
-{
-    if (nodes.empty()) throw std::runtime_error("checkWideLayouts: no nodes");
-    const WideBuild wb = buildWide(nodes.data(), nodes.size());
-    if (quadHalfAreaRatio) *quadHalfAreaRatio = wb.quadHalf.empty() ? 0.0f : wb.quadHalfAreaRatio;
-    const uint32_t  flags = (wb.boxesRegular ? 1u : 0u) | (!wb.compact.empty() ? 2u : 0u) | (!wb.hot.empty() ? 4u : 0u) | (!wb.quad.empty() ? 8u : 0u) | (!wb.quadHalf.empty() ? 16u : 0u) | (!wb.quadLocal.empty() ? 32u : 0u) | (!wb.oct.empty() ? 64u : 0u);
-    const size_t    records = wb.nodes.size() / 4;
-    const auto      fail = [](size_t r, const char* what) { throw std::runtime_error("wide layout mismatch at record " + std::to_string(r) + ": " + what); };
-    if (!wb.quadHalf.empty())
-    {
-        // The half-precision quad records: same words as the f32 quad records, every binary16 plane on the conservative side of the f32
-        // plane by at least the margin of the proof (rf_wide.hpp), never subnormal, finite.
-        if (wb.quadHalf.size() * 2 != wb.quad.size()) throw std::runtime_error("wide layout mismatch: half-precision quad records do not pair up with the quad records");
-        double R = 0.0;
-        for (const float c : {wb.rootLo.x, wb.rootLo.y, wb.rootLo.z, wb.rootHi.x, wb.rootHi.y, wb.rootHi.z}) R = std::max(R, static_cast<double>(std::fabs(c)));
-        // What the proof needs (rf_wide.hpp): margin >= u (4 originBound + 3 R + margin) with u = 2^-24, the unit roundoff of the f32 operations it counts.  `built` is
-        // the margin buildWide adds before its directed roundings, the largest a plane can be displaced by, and stands for the `+ margin` term.  The builder's
-        // 2^-21 (originBound + R) = u (40 R + 8) is more than twice u (19 R + 4 + margin) at EVERY R.  (Until the scale sweep this line had 2^-23 for u: a requirement of
-        // 2^-21 (4.75 R + 1) * 1.0001, which for R < 4e-4 is MORE than the builder's 2^-21 (5 R + 1) -- a plane that the directed rounding leaves exactly on the
-        // builder's target, such as an upper plane rounded to binary16 zero, then failed a check that the proof does not ask for.  The builder was right.)
-        const double built = (static_cast<double>(wb.originBound) + R) * 4.76837158203125e-07;
-        const double margin = 5.9604644775390625e-08 * (4.0 * static_cast<double>(wb.originBound) + 3.0 * R + built) * 1.0001;
-        if (!(static_cast<double>(wb.originBound) >= 4.0 * R)) throw std::runtime_error("wide layout mismatch: origin bound of the half-precision quad records");
-        for (size_t r = 0; r < wb.quadHalf.size() / 4; ++r)
-        {
-            const float4* q = &wb.quad[8 * r];
-            const uint4*  h = &wb.quadHalf[4 * r];
-            const uint32_t d[16] = {h[0].x, h[0].y, h[0].z, h[0].w, h[1].x, h[1].y, h[1].z, h[1].w, h[2].x, h[2].y, h[2].z, h[2].w, h[3].x, h[3].y, h[3].z, h[3].w};
-            if (d[12] != floatBits(q[6].x) || d[13] != floatBits(q[6].y) || d[14] != floatBits(q[6].z) || d[15] != floatBits(q[6].w)) fail(r, "half-precision quad record: words differ");
-            for (int k = 0; k < 2; ++k)
-            {
-                const float4 a = q[3 * k], z = q[3 * k + 1], b = q[3 * k + 2];
-                const float  lo[2][3] = {{a.x, a.y, z.x}, {b.x, b.y, z.z}}, hi[2][3] = {{a.z, a.w, z.y}, {b.z, b.w, z.w}};
-                for (int j = 0; j < 2; ++j)
-                    for (int ax = 0; ax < 3; ++ax)
-                    {
-                        const uint32_t w = d[3 * (2 * k + j) + ax];
-                        if (d[12 + 2 * k + j] == kQuadEmpty)
-                        {
-                            // (an empty slot holds the inverted box that no ray passes: the traversal kernel does not test its word)
-                            if (w != kHalfEmptyPlanes) fail(r, "half-precision quad record: an empty slot does not hold the inverted box");
-                            continue;
-                        }
-                        const uint16_t l16 = static_cast<uint16_t>(w & 0xFFFFu), h16 = static_cast<uint16_t>(w >> 16);
-                        for (const uint16_t v : {l16, h16})
-                            if (((v >> 10) & 0x1Fu) == 0x1Fu || (((v >> 10) & 0x1Fu) == 0u && (v & 0x3FFu) != 0u)) fail(r, "half-precision quad record: a plane is not a normal number or zero");
-                        if (!(static_cast<double>(halfBitsToFloat(l16)) <= static_cast<double>(lo[j][ax]) - margin)) fail(r, "half-precision quad record: a lower plane is not below its f32 plane by the margin");
-                        if (!(static_cast<double>(halfBitsToFloat(h16)) >= static_cast<double>(hi[j][ax]) + margin)) fail(r, "half-precision quad record: an upper plane is not above its f32 plane by the margin");
-                    }
-            }
-        }
-    }
-    if (!wb.quadLocal.empty())
-    {
-        // The local-grid quad records: same words, power-of-two scales, every decoded plane (anchor + byte * scale, exact in double) on the
-        // conservative side of the f32 plane by at least the margin of the proof (rf_wide.hpp).
-        if (wb.quadLocal.size() * 2 != wb.quad.size()) throw std::runtime_error("wide layout mismatch: local-grid quad records do not pair up with the quad records");
-        double R = 0.0;
-        for (const float c : {wb.rootLo.x, wb.rootLo.y, wb.rootLo.z, wb.rootHi.x, wb.rootHi.y, wb.rootHi.z}) R = std::max(R, static_cast<double>(std::fabs(c)));
-        for (size_t r = 0; r < wb.quadLocal.size() / 4; ++r)
-        {
-            const float4*  q = &wb.quad[8 * r];
-            const uint4*   l = &wb.quadLocal[4 * r];
-            const uint32_t words[4] = {l[3].x, l[3].y, l[3].z, l[3].w};
-            if (words[0] != floatBits(q[6].x) || words[1] != floatBits(q[6].y) || words[2] != floatBits(q[6].z) || words[3] != floatBits(q[6].w)) fail(r, "local-grid quad record: words differ");
-            const float    anchor[3] = {bitsFloat(l[0].x), bitsFloat(l[0].y), bitsFloat(l[0].z)}, scale[3] = {bitsFloat(l[0].w), bitsFloat(l[1].x), bitsFloat(l[1].y)};
-            const uint32_t axisWords[3][2] = {{l[1].z, l[1].w}, {l[2].x, l[2].y}, {l[2].z, l[2].w}};
-            for (int ax = 0; ax < 3; ++ax)
-            {
-                int          ex = 0;
-                const double m = std::frexp(static_cast<double>(scale[ax]), &ex);
-                if (!(m == 0.5) || !std::isfinite(anchor[ax])) fail(r, "local-grid quad record: scale is not a power of two, or the anchor is not finite");
-                // (u = 2^-24 as in the proof; the builder's 2^-18 (originBound + R) = u (320 R + 64) against u (46 R + 6) here: 6.9 x at R >> 1, 10.6 x at R << 1)
-                const double margin = 5.9604644775390625e-08 * (6.03 * (static_cast<double>(wb.originBound) + R) + 1024.0 * static_cast<double>(scale[ax])) * 1.0001;
-                for (int e = 0; e < 4; ++e)
-                {
-                    if (words[e] == kQuadEmpty) continue;
-                    const int    k = e / 2, j = e % 2;
-                    const float4 a = q[3 * k], z = q[3 * k + 1], b = q[3 * k + 2];
-                    const double lo = ax == 0 ? (j ? b.x : a.x) : ax == 1 ? (j ? b.y : a.y) : (j ? z.z : z.x), hi = ax == 0 ? (j ? b.z : a.z) : ax == 1 ? (j ? b.w : a.w) : (j ? z.w : z.y);
-                    const uint32_t pair = (axisWords[ax][e / 2] >> (16 * (e % 2))) & 0xFFFFu;
-                    const double   dlo = static_cast<double>(anchor[ax]) + static_cast<double>(pair & 0xFFu) * static_cast<double>(scale[ax]),
-                                 dhi = static_cast<double>(anchor[ax]) + static_cast<double>(pair >> 8) * static_cast<double>(scale[ax]);
-                    if (!(dlo <= lo - margin)) fail(r, "local-grid quad record: a lower plane is not below its f32 plane by the margin");
-                    if (!(dhi >= hi + margin)) fail(r, "local-grid quad record: an upper plane is not above its f32 plane by the margin");
-                }
-            }
-        }
-    }
-    if (!wb.quad.empty())
-    {
-        // The leaf boxes and occluder-cache entries leafBoxesIntoTriangles writes into the triangle records (round 4): every leaf's box is its node's; an entry is 0
-        // ("the leaf itself") or the index of a quad record from which the leaf is reached within `levels` steps -- in range, and really above THAT leaf.
-        size_t numTriangles = 0;
-        for (const BvhNode& n : nodes)
-            if (n.triangleCount != 0) numTriangles = std::max(numTriangles, static_cast<size_t>(n.trianglesOffset) + n.triangleCount);
-        const size_t numQuad = wb.quad.size() / 8;
-        for (uint32_t levels = 0; levels <= 3; ++levels)
-        {
-            std::vector<float4> tri(4 * numTriangles, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-            const bool          distinct = leafBoxesIntoTriangles(nodes.data(), nodes.size(), tri.data(), numTriangles, levels, &wb.quadIndexOfNode);
-            if (!distinct) break; // (leaves sharing a first triangle: the renderer keeps the layouts that read these slots off)
-            for (size_t i = 0; i < nodes.size(); ++i)
-            {
-                const BvhNode& n = nodes[i];
-                if (n.triangleCount == 0) continue;
-                const float4* t = &tri[4 * static_cast<size_t>(n.trianglesOffset)];
-                if (floatBits(t[0].w) != floatBits(n.aabb.min.x) || floatBits(t[1].w) != floatBits(n.aabb.min.y) || floatBits(t[2].w) != floatBits(n.aabb.min.z) ||
-                    floatBits(t[3].x) != floatBits(n.aabb.max.x) || floatBits(t[3].y) != floatBits(n.aabb.max.y) || floatBits(t[3].z) != floatBits(n.aabb.max.z))
-                    fail(i, "leaf box in the triangle record differs from the node's");
-                const uint32_t hint = floatBits(t[3].w);
-                if (levels == 0 && hint != 0u) fail(i, "occluder-cache entry of a leaf: not 0 at level 0");
-                if (hint == 0u) continue;
-                if (hint >= numQuad) fail(i, "occluder-cache entry of a leaf: quad record index out of range");
-                std::vector<uint32_t> frontier{hint};
-                bool                  found = false;
-                for (uint32_t l = 0; l < levels && !found; ++l)
-                {
-                    std::vector<uint32_t> next;
-                    for (const uint32_t r : frontier)
-                    {
-                        const float4*  q = &wb.quad[8 * static_cast<size_t>(r)];
-                        const uint32_t raw[4] = {floatBits(q[6].x), floatBits(q[6].y), floatBits(q[6].z), floatBits(q[6].w)};
-                        for (int e = 0; e < 4; ++e)
-                        {
-                            if (raw[e] == kQuadEmpty) continue;
-                            const uint32_t w = e == 2 ? raw[e] : raw[e] & ~(3u << kWideAxisShift); // (entries 0, 1 and 3 carry split axes)
-                            if ((w & kWideLeafBit) == 0u)
-                            {
-                                if (w >= numQuad) fail(i, "occluder-cache entry of a leaf: a record below it names a record out of range");
-                                next.push_back(w);
-                                continue;
-                            }
-                            uint32_t first = w & ((1u << kWideIndexBits) - 1u);
-                            if (((w >> kWideIndexBits) & 7u) == 7u) first = wb.bigLeaves[first].x;
-                            if (first == n.trianglesOffset) found = true;
-                        }
-                    }
-                    frontier.swap(next);
-                }
-                if (!found) fail(i, "occluder-cache entry of a leaf: the leaf is not below the record it names");
-            }
-        }
-    }
-    if (!wb.quad.empty())
-    {
-        // Walk the quad records from the root next to the 64-byte records: the entries of a quad record must be the children of
-        // the children the plain record of the same node names (a leaf child filling one slot), with the same leaf words, the
-        // split axes of both levels, and the skipped child's box must be the union of its entries (what makes the skip exact).
-        struct Pair
-        {
-            uint32_t plain, quad;
-        };
-        std::vector<Pair> todo{{0u, 0u}};
-        size_t            visited = 0;
-        while (!todo.empty())
-        {
-            const Pair at = todo.back();
-            todo.pop_back();
-            ++visited;
-            if (at.plain >= records || 8 * static_cast<size_t>(at.quad) + 8 > wb.quad.size()) fail(at.plain, "quad record index out of range");
-            const float4*  w = &wb.nodes[4 * static_cast<size_t>(at.plain)];
-            const float4*  q = &wb.quad[8 * static_cast<size_t>(at.quad)];
-            const uint32_t qw[4] = {floatBits(q[6].x), floatBits(q[6].y), floatBits(q[6].z), floatBits(q[6].w)};
-            const uint32_t pw[2] = {floatBits(w[3].x) & ~(3u << kWideAxisShift), floatBits(w[3].y)};
-            if (((qw[0] >> kWideAxisShift) & 3u) != ((floatBits(w[3].x) >> kWideAxisShift) & 3u)) fail(at.plain, "quad record: split axis of the node differs");
-            const float cbox[2][6] = {{w[0].x, w[0].y, w[0].z, w[0].w, w[1].x, w[1].y}, {w[2].x, w[2].y, w[2].z, w[2].w, w[1].z, w[1].w}};
-            for (int k = 0; k < 2; ++k)
-            {
-                const float4*  e = q + 3 * k;
-                const float    b0[6] = {e[0].x, e[0].y, e[0].z, e[0].w, e[1].x, e[1].y}, b1[6] = {e[2].x, e[2].y, e[2].z, e[2].w, e[1].z, e[1].w};
-                const uint32_t wa = qw[2 * k], wb2 = qw[2 * k + 1];
-                if (pw[k] & kWideLeafBit)
-                {
-                    // a leaf child fills slot 2k with itself
-                    if ((wa & ~(3u << kWideAxisShift)) != pw[k] || wb2 != kQuadEmpty) fail(at.plain, "quad record: leaf child not passed through");
-                    for (int j = 0; j < 6; ++j)
-                        if (!(b0[j] == cbox[k][j])) fail(at.plain, "quad record: leaf child's box differs");
-                    continue;
-                }
-                const float4*  cw = &wb.nodes[4 * static_cast<size_t>(pw[k])]; // the child's own plain record = its children
-                const float    g0[6] = {cw[0].x, cw[0].y, cw[0].z, cw[0].w, cw[1].x, cw[1].y}, g1[6] = {cw[2].x, cw[2].y, cw[2].z, cw[2].w, cw[1].z, cw[1].w};
-                const uint32_t gw[2] = {floatBits(cw[3].x) & ~(3u << kWideAxisShift), floatBits(cw[3].y)};
-                const uint32_t childAxis = (floatBits(cw[3].x) >> kWideAxisShift) & 3u;
-                for (int j = 0; j < 6; ++j)
-                {
-                    if (!(b0[j] == g0[j]) || !(b1[j] == g1[j])) fail(at.plain, "quad record: grandchild box differs");
-                    const float u = (j == 0 || j == 1 || j == 4) ? std::min(g0[j], g1[j]) : std::max(g0[j], g1[j]);
-                    if (!(u == cbox[k][j])) fail(at.plain, "quad record: skipped child's box is not the union of its children's");
-                }
-                const uint32_t tagged = k == 0 ? wb2 : wb2; // slot 2k+1 carries the child's split axis
-                if (((tagged >> kWideAxisShift) & 3u) != childAxis) fail(at.plain, "quad record: split axis of a child differs");
-                const uint32_t ea = k == 0 ? (wa & ~(3u << kWideAxisShift)) : wa, eb = wb2 & ~(3u << kWideAxisShift);
-                const uint32_t ent[2] = {ea, eb};
-                for (int j = 0; j < 2; ++j)
-                {
-                    if (gw[j] & kWideLeafBit)
-                    {
-                        if (ent[j] != gw[j]) fail(at.plain, "quad record: grandchild leaf word differs");
-                    }
-                    else
-                    {
-                        if (ent[j] & kWideLeafBit) fail(at.plain, "quad record: interior grandchild encoded as a leaf");
-                        todo.push_back(Pair{gw[j], ent[j]});
-                    }
-                }
-            }
-        }
-        if (visited != wb.quad.size() / 8) fail(0, "quad records: not every record is reachable from the root exactly once");
-    }
-    if (!wb.oct.empty())
-    {
-        // Oct records (round 5): walk them from the root next to the reference nodes.  Slot e = 4 c + 2 g + k must hold what the three levels below the member hold
-        // at that place (a leaf fills the first slot of its range), every plane must lie outside its f32 plane by the margin, an empty slot must fail for every
-        // ray (lo = 255, hi = 0), and for each of the eight direction-sign patterns the positions the KERNEL derives from the order table (kTraceWide, COMPACT == 6)
-        // must put the slots into the order in which the reference's walk (wgsl:409-417 at each of the three levels) reaches them.
-        double R = 0.0;
-        for (const float c : {wb.rootLo.x, wb.rootLo.y, wb.rootLo.z, wb.rootHi.x, wb.rootHi.y, wb.rootHi.z}) R = std::max(R, static_cast<double>(std::fabs(c)));
-        // 2^-18 (originBound + R), the margin the builder ADDS (a hair less: its floor / ceil run in double) -- 6.9 x what the proof of the local-grid records needs at
-        // any R (see the local-grid check above), so this asks for more than the proof; it holds because the decoded planes anchor + byte * scale are exact in double
-        const double margin = (static_cast<double>(wb.originBound) + R) * 3.814697265625e-06 * 0.999;
-        const size_t numOct = wb.oct.size() / 8;
-        struct Item
-        {
-            uint32_t node, rec;
-        };
-        std::vector<Item> todo{{0u, 0u}};
-        size_t            visited = 0;
-        while (!todo.empty())
-        {
-            const Item at = todo.back();
-            todo.pop_back();
-            ++visited;
-            if (at.rec >= numOct || at.node >= nodes.size() || nodes[at.node].triangleCount != 0) fail(at.rec, "oct record: index out of range or not an interior node");
-            uint32_t slotNode[8];
-            for (uint32_t& v : slotNode) v = kQuadEmpty;
-            const std::function<void(uint32_t, int, int)> place = [&](uint32_t nd, int depth, int base) {
-                if (depth == 3 || (depth > 0 && nodes[nd].triangleCount != 0)) { slotNode[base] = nd; return; }
-                place(nd + 1, depth + 1, base);
-                place(nodes[nd].secondChildOffset, depth + 1, base + (4 >> depth));
-            };
-            place(at.node, 0, 0);
-            const uint4*   o = &wb.oct[8 * static_cast<size_t>(at.rec)];
-            const float    anchor[3] = {bitsFloat(o[0].x), bitsFloat(o[0].y), bitsFloat(o[0].z)}, scale[3] = {bitsFloat(o[0].w), bitsFloat(o[1].x), bitsFloat(o[1].y)};
-            const uint32_t words[8] = {o[5].x, o[5].y, o[5].z, o[5].w, o[6].x, o[6].y, o[6].z, o[6].w};
-            const uint32_t axisWords[3][4] = {{o[2].x, o[2].y, o[2].z, o[2].w}, {o[3].x, o[3].y, o[3].z, o[3].w}, {o[4].x, o[4].y, o[4].z, o[4].w}};
-            for (int e = 0; e < 8; ++e)
-            {
-                for (int ax = 0; ax < 3; ++ax)
-                {
-                    const uint32_t pair = (axisWords[ax][e / 2] >> (16 * (e % 2))) & 0xFFFFu;
-                    if (slotNode[e] == kQuadEmpty)
-                    {
-                        if (pair != 0x00FFu) fail(at.rec, "oct record: an empty slot does not hold the planes no ray passes");
-                        continue;
-                    }
-                    const BvhNode& en = nodes[slotNode[e]];
-                    const double   lo = ax == 0 ? en.aabb.min.x : ax == 1 ? en.aabb.min.y : en.aabb.min.z, hi = ax == 0 ? en.aabb.max.x : ax == 1 ? en.aabb.max.y : en.aabb.max.z;
-                    const double   dlo = static_cast<double>(anchor[ax]) + static_cast<double>(pair & 0xFFu) * static_cast<double>(scale[ax]),
-                                 dhi = static_cast<double>(anchor[ax]) + static_cast<double>(pair >> 8) * static_cast<double>(scale[ax]);
-                    if (!(dlo <= lo - margin)) fail(at.rec, "oct record: a lower plane is not below its f32 plane by the margin");
-                    if (!(dhi >= hi + margin)) fail(at.rec, "oct record: an upper plane is not above its f32 plane by the margin");
-                }
-                if (slotNode[e] == kQuadEmpty)
-                {
-                    if (words[e] != kQuadEmpty) fail(at.rec, "oct record: an empty slot names something");
-                    continue;
-                }
-                const BvhNode& en = nodes[slotNode[e]];
-                if (en.triangleCount != 0)
-                {
-                    if ((words[e] & kWideLeafBit) == 0u) fail(at.rec, "oct record: a leaf encoded as an interior entry");
-                    uint32_t first = words[e] & ((1u << kWideIndexBits) - 1u), cnt = ((words[e] >> kWideIndexBits) & 7u) + 1u;
-                    if (cnt == 8u) cnt = wb.bigLeaves[first].y, first = wb.bigLeaves[first].x;
-                    if (first != en.trianglesOffset || cnt != en.triangleCount) fail(at.rec, "oct record: leaf word names other triangles");
-                }
-                else
-                {
-                    if ((words[e] & kWideLeafBit) != 0u || words[e] != wb.octIndexOfNode[slotNode[e]]) fail(at.rec, "oct record: interior entry names another record");
-                    todo.push_back(Item{slotNode[e], words[e]});
-                }
-            }
-            const unsigned long long table = (static_cast<unsigned long long>(o[1].w) << 32) | o[1].z;
-            for (uint32_t signs = 0; signs < 8; ++signs)
-            {
-                std::vector<int>                              want; // slots in the order the reference reaches them
-                const std::function<void(uint32_t, int, int)> walk = [&](uint32_t nd, int depth, int base) {
-                    if (depth == 3 || (depth > 0 && nodes[nd].triangleCount != 0)) { want.push_back(base); return; }
-                    const bool     neg = ((signs >> (nodes[nd].splitAxis & 3u)) & 1u) != 0u;
-                    const uint32_t kid[2] = {nd + 1, nodes[nd].secondChildOffset};
-                    const int      kidBase[2] = {base, base + (4 >> depth)};
-                    for (int k = 0; k < 2; ++k) walk(kid[neg ? 1 - k : k], depth + 1, kidBase[neg ? 1 - k : k]);
-                };
-                walk(at.node, 0, 0);
-                // the kernel's rule (refill + oct step)
-                const uint32_t signXY = signs & 3u, negZ = signs >> 2;
-                const uint32_t octKey = negZ ? ((16u * (3u - signXY)) | (0x7777u << 8)) : 16u * signXY;
-                const uint32_t ord = static_cast<uint32_t>(table >> (octKey & 63u)) ^ (octKey >> 8);
-                int            slotAt[8];
-                for (int& v : slotAt) v = -1;
-                for (int j = 0; j < 4; ++j)
-                {
-                    const uint32_t p0 = (ord >> (4 * j)) & 7u;
-                    if (slotNode[2 * j] != kQuadEmpty) slotAt[p0] = 2 * j;
-                    if (slotNode[2 * j + 1] != kQuadEmpty) slotAt[p0 ^ 1u] = 2 * j + 1;
-                }
-                std::vector<int> got;
-                for (const int v : slotAt)
-                    if (v >= 0) got.push_back(v);
-                if (got != want) fail(at.rec, "oct record: the order table does not reproduce the reference's visit order");
-            }
-        }
-        if (visited != numOct) fail(0, "oct records: not every record is reachable from the root exactly once");
-    }
-    for (size_t r = 0; r < records; ++r)
-    {
-        const float4* w = &wb.nodes[4 * r];
-        // child planes of the plain record, in the order {lo.x lo.y hi.x hi.y lo.z hi.z}
-        const float    c0[6] = {w[0].x, w[0].y, w[0].z, w[0].w, w[1].x, w[1].y}, c1[6] = {w[2].x, w[2].y, w[2].z, w[2].w, w[1].z, w[1].w};
-        const uint32_t word0 = floatBits(w[3].x), word1 = floatBits(w[3].y);
-        float          own[6]; // the node's own box: the union of its children's (lo: min, hi: max)
-        for (int k = 0; k < 6; ++k) own[k] = (k == 0 || k == 1 || k == 4) ? std::min(c0[k], c1[k]) : std::max(c0[k], c1[k]);
-        if (!wb.compact.empty())
-        {
-            const float4*  c = &wb.compact[4 * r];
-            const uint32_t cw0 = floatBits(c[2].x), cw1 = floatBits(c[2].z);
-            const bool     selLo = (cw1 >> kWideAxisShift) & 1u, selHi = (cw1 >> (kWideAxisShift + 1)) & 1u;
-            const float    d0[6] = {selLo ? c[3].x : c[0].x, c[0].y, selHi ? c[3].y : c[0].z, c[0].w, c[1].x, c[1].y};
-            const float    d1[6] = {selLo ? c[0].x : c[3].x, c[2].y, selHi ? c[0].z : c[3].y, c[2].w, c[1].z, c[1].w};
-            for (int k = 0; k < 6; ++k)
-                if (!(d0[k] == c0[k]) || !(d1[k] == c1[k])) fail(r, "compact-capable record decodes to other planes");
-            if (cw0 != word0 || (cw1 & ~(3u << kWideAxisShift)) != word1) fail(r, "compact-capable record holds other child words");
-            if (!(c[3].x == own[0]) || !(c[3].y == own[2])) fail(r, "compact-capable record: outer x planes are not the node's");
-        }
-        if (!wb.hot.empty())
-        {
-            const float4*  h = &wb.hot[2 * r];
-            const float4*  o = &wb.own[2 * r];
-            const uint32_t hw0 = floatBits(h[1].z), hw1 = floatBits(h[1].w);
-            const float    inner[6] = {h[0].x, h[0].y, h[0].z, h[0].w, h[1].x, h[1].y}, outer[6] = {o[0].x, o[0].y, o[0].z, o[0].w, o[1].x, o[1].y};
-            const bool     sel[6] = {((hw0 >> 25) & 1u) != 0u, ((hw0 >> 24) & 1u) != 0u, ((hw1 >> 25) & 1u) != 0u,
-                                     ((hw1 >> 24) & 1u) != 0u, ((hw1 >> 30) & 1u) != 0u, ((hw1 >> 29) & 1u) != 0u};
-            for (int k = 0; k < 6; ++k)
-            {
-                if (!((sel[k] ? outer[k] : inner[k]) == c0[k]) || !((sel[k] ? inner[k] : outer[k]) == c1[k])) fail(r, "32-byte record decodes to other planes");
-                if (!(outer[k] == own[k])) fail(r, "own-box array does not hold the union of the children");
-            }
-            if ((hw0 & ~(3u << 24)) != word0 || (hw1 & ~((3u << 24) | (3u << kWideAxisShift))) != word1) fail(r, "32-byte record holds other child words");
-        }
-    }
-    return flags;
 }
 } // namespace rf
 

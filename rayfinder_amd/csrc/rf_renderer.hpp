@@ -11,6 +11,7 @@
 // and the bvh-visualizer node-visit pass (src/bvh-visualizer/main.cpp:60-78) on the GPU.
 #pragma once
 
+#include "rf_bvh.hpp" // SceneView
 #include "rf_sky.hpp"
 #include "rf_types.hpp"
 
@@ -43,20 +44,6 @@ struct RenderParameters
     float          exposure = 1.0f;
 };
 bool operator==(const RenderParameters& a, const RenderParameters& b);
-
-struct TextureView
-{
-    const uint32_t* pixels;
-    uint32_t        width, height;
-};
-
-struct SceneView
-{
-    std::span<const BvhNode>           bvhNodes;
-    std::span<const PositionAttribute> positionAttributes;
-    std::span<const VertexAttributes>  vertexAttributes;
-    std::span<const TextureView>       baseColorTextures;
-};
 
 struct RendererDescriptor
 {
@@ -465,10 +452,4 @@ private:
     struct Impl;
     std::unique_ptr<Impl> mImpl;
 };
-
-// Host-only check of the render path's BVH layouts (rf_wide.hpp) for a flattened tree: builds the 64-byte records and their
-// compact-capable / 32-byte variants and verifies that every variant decodes to the same child planes and child words as the
-// plain record, and that the carried "own" planes are the union of the children's.  Returns bit 0: boxes regular (wide layout
-// usable), bit 1: compact-capable records usable, bit 2: 32-byte records usable; throws std::runtime_error on a mismatch.
-uint32_t checkWideLayouts(std::span<const BvhNode> nodes, float* quadHalfAreaRatio = nullptr);
 } // namespace rf
