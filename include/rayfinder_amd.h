@@ -331,6 +331,78 @@ RF_API int rf_denoise_split_tiles(int32_t device_ordinal, uint32_t width, uint32
                                   const float* albedo_coverage4, const float* normal_depth4, const rf_denoise_parameters* direct, const rf_denoise_parameters* indirect,
                                   float exposure, float* out_rgba, uint32_t* out_bgra8);
 
+/* Feature export: the frame's per-pixel feature channels as ONE tensor in caller-owned DEVICE memory -- what a learned denoiser, a compositor or any tensor pipeline
+ * takes -- without the sums leaving the device: one kernel reads the sums where they lie (tile-major on a handle, row-major on the root of a gather), divides every
+ * pixel by its own sample count and writes planar or interleaved f32 / f16.  No reference counterpart.
+ *
+ * A request (rf_feature_request) is a channel mask, a layout and an element type; `reserved` is 0.  The output holds, for every pixel of the width x height frame,
+ * the selected channels in ascending bit order.  f32, one IEEE operation at a time in the order written, no contraction, as everywhere in this header.
+ * Nf = float(count), count = N, the frame's one sample count -- or, where a count per tile is used (the non-uniform state of rf_renderer_render_adaptive, a gather
+ * with RF_GATHER_TILE_COUNTS, tile_samples), count = tile_samples[(y >> 5) * ceil(width / 32) + (x >> 5)].  A pixel whose count is 0 gives +0 in every channel.
+ *
+ *   bit    name                  channels  value
+ *   0x001  RF_FEATURE_COLOR      3         S.c / Nf  (kTonemap's division; rf_renderer_read_mean's)
+ *   0x002  RF_FEATURE_ALBEDO     3         AC.c / Nf
+ *   0x004  RF_FEATURE_NORMAL     3         background: 0, 0, 0; else m = ND.xyz / Nf, n = m * (1 / sqrt(dot(m, m))) with dot = (m.x m.x + m.y m.y) + m.z m.z -- the
+ *                                          denoiser's guide normal, computed exactly as its prep computes it; (0, 0, 0) where dot(m, m) is 0 or not finite
+ *   0x008  RF_FEATURE_DEPTH      1         background: 0; else z = ND.w / AC.w
+ *   0x010  RF_FEATURE_COVERAGE   1         AC.w / Nf
+ *   0x020  RF_FEATURE_DIRECT     3         D.c / Nf
+ *   0x040  RF_FEATURE_INDIRECT   3         (S.c - D.c) / Nf  (one subtraction, one division: rf_comm_read_split's)
+ *   0x080  RF_FEATURE_VARIANCE   3         per channel, mu and v exactly as the noise estimate forms them: mu = S.c / Nf; v = (Q.c - S.c mu) / (Nf - 1);
+ *                                          v = v > 0 ? v : 0; out = v / Nf, the variance of the mean
+ *   0x100  RF_FEATURE_ERROR      1         the noise estimate's per-pixel e (its error_map), 0 where e <= FLT_MAX is false
+ *   0x200  RF_FEATURE_SAMPLES    1         Nf
+ * Background is the denoiser's test: AC.w == 0, or z = ND.w / AC.w not > 0.
+ *
+ * Layouts: RF_FEATURES_CHW -- plane after plane, each row-major: element (c * height + y) * width + x; RF_FEATURES_HWC -- element (y * width + x) * C + c.
+ * Element types: RF_FEATURES_F32; RF_FEATURES_F16 -- the f32 value converted with ONE round-to-nearest-even conversion (overflow to +-inf, half subnormals kept, NaN
+ * stays NaN: numpy's float32 -> float16).  rf_feature_channel_count gives C; the buffer holds width * height * C elements, contiguous; the destination needs element
+ * alignment only (4 or 2 bytes; a 16-byte aligned destination of a frame whose width is a multiple of 4 (f32) / 8 (f16) is written 16 bytes per lane, any other
+ * element by element: the same values).
+ *
+ * rf_renderer_export_features: over the handle's own sums.  Enqueued on the handle's stream and then waited for: when it returns the buffer may be used from any
+ * stream (torch's current one, say).  *sample_count (may be NULL): the accumulated (leading) count.  In the non-uniform state every pixel takes its tile's own count
+ * (the call first waits for the stream and copies the counts to the device, as the other per-tile reads do).  READ-ONLY: every sum, count, snapshot, statistic and the
+ * frame counter stay as they are.  It needs no scratch but the counts' buffer of the per-tile reads; a handle that never calls it allocates and launches nothing for it.
+ * RF_ERROR_INVALID_ARGUMENT, the state kept, each before any launch: a NULL argument; unknown channel, layout or dtype bits, an empty mask or reserved != 0;
+ * dst_bytes smaller than the frame needs; dst_device that hipPointerGetAttributes does not report as device memory on the handle's device (a host pointer never
+ * reaches the kernel); a tile shard is set (gather the frame and call rf_comm_export_features on the root); no sample accumulated; a selected channel's family is
+ * off or does not cover the accumulation (the AOVs for ALBEDO / NORMAL / DEPTH / COVERAGE, D for DIRECT / INDIRECT, the moments for VARIANCE / ERROR); in the
+ * non-uniform state, a selected family that was kept without its tile-count bit (RF_AOV_TILE_COUNTS, RF_DIRECT_TILE_COUNTS); VARIANCE / ERROR with fewer than 2
+ * samples.  COLOR and SAMPLES need nothing but samples.
+ * rf_comm_export_features (declared with the communicator's calls, below): the same over the row-major planes gathered on the root -- planes 0 .. 3 and 5, and the
+ * gathered tile counts when the gather carried them --, on the root's handle's stream, then waited for.  Bit for bit what the un-sharded handle's own export writes.
+ * Refused when a selected channel's plane was not gathered, on a rank that was not the root, and as above.
+ * rf_export_features_images: the same over host-assembled row-major width*height*4 sums, into HOST memory (out_host: width * height * C elements); synchronous,
+ * like rf_denoise_images.  tile_samples NULL: `samples` for every pixel; else one count per tile (host memory) and `samples` is not used.  An input pointer may be
+ * NULL when no selected channel reads it (COLOR / INDIRECT / VARIANCE / ERROR read color_sum4, VARIANCE / ERROR sumsq4, ALBEDO / NORMAL / DEPTH / COVERAGE both AOV
+ * sums, DIRECT / INDIRECT direct_sum4).  A NULL that is needed, a zero size, samples == 0 without tile_samples, a tile count of 0 (rf_denoise_tiles' rule) and, where
+ * VARIANCE / ERROR are selected, any count below 2 are refused before any device call. */
+#define RF_FEATURE_COLOR 0x001u
+#define RF_FEATURE_ALBEDO 0x002u
+#define RF_FEATURE_NORMAL 0x004u
+#define RF_FEATURE_DEPTH 0x008u
+#define RF_FEATURE_COVERAGE 0x010u
+#define RF_FEATURE_DIRECT 0x020u
+#define RF_FEATURE_INDIRECT 0x040u
+#define RF_FEATURE_VARIANCE 0x080u
+#define RF_FEATURE_ERROR 0x100u
+#define RF_FEATURE_SAMPLES 0x200u
+#define RF_FEATURES_CHW 0u
+#define RF_FEATURES_HWC 1u
+#define RF_FEATURES_F32 0u
+#define RF_FEATURES_F16 1u
+typedef struct rf_feature_request
+{
+    uint32_t channels, layout, dtype, reserved;
+} rf_feature_request;
+RF_API int rf_feature_channel_count(uint32_t channels, uint32_t* count);
+RF_API int rf_renderer_export_features(rf_renderer* r, const rf_feature_request* req, void* dst_device, uint64_t dst_bytes, uint32_t* sample_count);
+RF_API int rf_export_features_images(int32_t device_ordinal, uint32_t width, uint32_t height, uint32_t samples, const uint32_t* tile_samples /* NULL: `samples` for all */,
+                                     const float* color_sum4, const float* sumsq4, const float* albedo_coverage4, const float* normal_depth4, const float* direct_sum4,
+                                     const rf_feature_request* req, void* out_host);
+
 /* Radiance second moments and the noise estimate: how noisy the accumulation still is, per pixel, per 32x32 tile and for the frame, and a render call that stops
  * at a noise target.  No reference counterpart (the reference counts samples: renderProgressPercentage).
  *
@@ -888,6 +960,8 @@ RF_API int  rf_comm_denoise_robust(rf_comm* c, rf_renderer* r, const rf_denoise_
 /* After a gather with RF_GATHER_DIRECT, on the root (DIRECT SUMS ACROSS RANKS, above) */
 RF_API int  rf_comm_denoise_split(rf_comm* c, rf_renderer* r, const rf_denoise_parameters* direct, const rf_denoise_parameters* indirect); /* NULL = that component's default; needs RF_GATHER_AOVS | RF_GATHER_DIRECT */
 RF_API int  rf_comm_read_split(rf_comm* c, rf_renderer* r, float* direct_rgba, float* indirect_rgba);  /* either may be NULL, not both */
+/* The feature export (above) over the gathered planes, on the root: into caller-owned device memory on the root's device; sample_count (may be NULL): N */
+RF_API int  rf_comm_export_features(rf_comm* c, rf_renderer* r, const rf_feature_request* req, void* dst_device, uint64_t dst_bytes, uint32_t* sample_count);
 /* Max over ranks of *value (timing plumbing for hosts without another collective layer; also a barrier). */
 RF_API int  rf_comm_all_reduce_max(rf_comm* c, rf_renderer* r /* NULL: default stream */, double* value);
 /* What RCCL reports for the communicator (ncclCommCount / ncclCommUserRank / ncclCommCuDevice); any pointer may be NULL.

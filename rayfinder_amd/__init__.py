@@ -584,6 +584,107 @@ class TileComm:
         return direct, indirect
 
 
+    def export_features(self, renderer, channels=("color", "albedo", "normal", "depth"), layout="chw", dtype="f32", out=None):
+        """Root: ReferencePathTracer.export_features over the gathered planes where they lie (the gather needs the planes the channels read: aovs, moments, direct; with
+        tile_counts=True every pixel takes its tile's count) -> torch tensor on the communicator's device, bit for bit what the un-sharded handle's export gives."""
+        req, count = _feature_request(channels, layout, dtype)
+        g = self.gathered_planes()
+        device = C.c_int32(0)
+        check(lib.rf_comm_info(self._h, None, None, C.byref(device)))
+        shape = (count, g["height"], g["width"]) if layout == "chw" else (g["height"], g["width"], count)
+        out = _feature_tensor("TileComm.export_features", out, shape, dtype, device.value)
+        check(lib.rf_comm_export_features(self._h, renderer._h, C.byref(req), C.c_void_p(out.data_ptr()), out.numel() * out.element_size(), None))
+        return out
+
+
+# ------------------------------------------------------------------------------------- feature export
+def feature_channels(mask_or_names):
+    """-> (channel names in output order, C) of a feature request: an RF_FEATURE_* mask, one group name or an iterable of group names out of color, albedo, normal,
+    depth, coverage, direct, indirect, variance, error, samples.  The output order is the groups' bit order whatever the order given; a group of three gives
+    name.r / .g / .b (normal: .x / .y / .z).  ValueError for an empty or unknown selection."""
+    names, _, count = _feature_selection(mask_or_names)
+    return names, count
+
+
+def _feature_selection(mask_or_names):
+    bits = {name: bit for name, bit, _ in _ffi.FEATURE_GROUPS}
+    if isinstance(mask_or_names, (int, np.integer)) and not isinstance(mask_or_names, bool):
+        mask = int(mask_or_names)
+    else:
+        groups = (mask_or_names,) if isinstance(mask_or_names, str) else tuple(mask_or_names)
+        unknown = [g for g in groups if g not in bits]
+        if unknown:
+            raise ValueError(f"unknown feature channels {unknown}: choose from {[g for g, _, _ in _ffi.FEATURE_GROUPS]}")
+        mask = 0
+        for g in groups:
+            mask |= bits[g]
+    if mask <= 0 or mask & ~sum(bits.values()):
+        raise ValueError("feature channels: the selection is empty or holds unknown RF_FEATURE_* bits")
+    names = []
+    for name, bit, n in _ffi.FEATURE_GROUPS:
+        if mask & bit:
+            names += [name] if n == 1 else [f"{name}.{c}" for c in ("xyz" if name == "normal" else "rgb")]
+    count = C.c_uint32(0)
+    check(lib.rf_feature_channel_count(mask, C.byref(count)))
+    assert count.value == len(names)
+    return tuple(names), mask, count.value
+
+
+def _feature_request(channels, layout, dtype):
+    _, mask, count = _feature_selection(channels)
+    layouts = {"chw": _ffi.RF_FEATURES_CHW, "hwc": _ffi.RF_FEATURES_HWC}
+    dtypes = {"f32": _ffi.RF_FEATURES_F32, "f16": _ffi.RF_FEATURES_F16}
+    if layout not in layouts:
+        raise ValueError(f"feature layout {layout!r}: 'chw' or 'hwc'")
+    if dtype not in dtypes:
+        raise ValueError(f"feature dtype {dtype!r}: 'f32' or 'f16'")
+    return _ffi.FeatureRequest(mask, layouts[layout], dtypes[dtype], 0), count
+
+
+def _feature_tensor(what, out, shape, dtype, device_ordinal):
+    """The destination of an export: a new torch tensor on the device, or the caller's `out` once its device, dtype, shape and contiguity have been checked (a storage
+    offset is fine: the library needs element alignment only)."""
+    import torch
+    tdtype = torch.float16 if dtype == "f16" else torch.float32
+    if out is None:
+        return torch.empty(shape, dtype=tdtype, device=torch.device("cuda", device_ordinal))
+    if not isinstance(out, torch.Tensor):
+        raise TypeError(f"{what}: out must be a torch.Tensor")
+    if out.device.type != "cuda" or (out.device.index or 0) != device_ordinal:
+        raise ValueError(f"{what}: out lies on {out.device}, the sums on cuda:{device_ordinal}")
+    if out.dtype != tdtype:
+        raise ValueError(f"{what}: out is {out.dtype}, the request asks for {tdtype}")
+    if tuple(out.shape) != tuple(shape):
+        raise ValueError(f"{what}: out has shape {tuple(out.shape)}, the request gives {tuple(shape)}")
+    if not out.is_contiguous():
+        raise ValueError(f"{what}: out must be contiguous")
+    return out
+
+
+def export_features_images(color_sum=None, sumsq=None, albedo_coverage=None, normal_depth=None, direct_sum=None, samples=0, tile_samples=None,
+                           channels=("color", "albedo", "normal", "depth"), layout="chw", dtype="f32", device_ordinal=0):
+    """rf_export_features_images: the feature export over (H, W, 4) f32 sums held on the host -- the accumulation S, the second moments Q, {albedo, coverage},
+    {normal, depth} and the direct sums D; one that no selected channel reads may be None -- of `samples` samples, or with one count per 32x32 tile (tile_samples in
+    tile order, as denoise_tiles takes them).  -> numpy (C, H, W) or (H, W, C) array of float32 / float16."""
+    req, count = _feature_request(channels, layout, dtype)
+    given = [a for a in (color_sum, sumsq, albedo_coverage, normal_depth, direct_sum) if a is not None]
+    if not given:
+        raise ValueError("export_features_images: no sum was given (the frame size comes from the sums; samples alone needs color_sum too)")
+    planes = [None if a is None else _f32(a) for a in (color_sum, sumsq, albedo_coverage, normal_depth, direct_sum)]
+    h, w = _f32(given[0]).shape[:2]
+    for a in planes:
+        if a is not None and a.shape != (h, w, 4):
+            raise ValueError("export_features_images: the sums must be (H, W, 4) arrays of one size")
+    counts = None
+    if tile_samples is not None:
+        counts = np.ascontiguousarray(tile_samples, np.uint32).reshape(-1)
+        if counts.size != _noise_tiles(w, h):
+            raise ValueError(f"export_features_images: {_noise_tiles(w, h)} tile counts expected, got {counts.size}")
+    out = np.zeros((count, h, w) if layout == "chw" else (h, w, count), np.float16 if dtype == "f16" else np.float32)
+    check(lib.rf_export_features_images(device_ordinal, w, h, int(samples), _ptr(counts), *(_ptr(a) for a in planes), C.byref(req), _ptr(out)))
+    return out
+
+
 # ------------------------------------------------------------------------------------- renderer
 def denoise_defaults():
     """-> dict of the denoiser's default parameters (rf_denoise_default_parameters)."""
@@ -791,6 +892,7 @@ class ReferencePathTracer:
         desc = _ffi.RendererDescriptor(render_params, max_width, max_height, device_ordinal, max_paths_in_flight)
         self._h = C.c_void_p()
         self._params = render_params
+        self._device_ordinal = device_ordinal
         check(lib.rf_renderer_create(C.byref(desc), C.byref(scene), C.byref(self._h)))
 
     def close(self):
@@ -894,6 +996,19 @@ class ReferencePathTracer:
         read_denoised reads the result.  direct / indirect: dicts of iterations, sigma_color, sigma_normal, sigma_depth (the rest: that component's defaults)."""
         pd, pi = _split_parameters(direct, indirect)
         check(lib.rf_renderer_denoise_split(self._h, C.byref(pd), C.byref(pi)))
+
+    # the feature export (rf_renderer_export_features; include/rayfinder_amd.h states every channel's arithmetic)
+    def export_features(self, channels=("color", "albedo", "normal", "depth"), layout="chw", dtype="f32", out=None):
+        """The frame as a tensor on the GPU: the selected feature channels -- out of color, albedo, normal, depth, coverage, direct, indirect, variance, error, samples;
+        always in that order -- of the handle's own sums, every pixel divided by its (tile's) sample count, written by one kernel into a torch tensor on the handle's
+        device: (C, H, W) for layout "chw", (H, W, C) for "hwc"; torch.float32 for dtype "f32", torch.float16 for "f16".  out: a contiguous tensor of that shape, dtype
+        and device to write into (a storage offset is fine); None: torch.empty.  The call waits for the kernel: the tensor may be used on any stream at once.  Needs the
+        sums its channels read on from the first sample (set_aovs, set_direct, set_moments; after render_adaptive with tile_counts=True) and no tile shard."""
+        req, count = _feature_request(channels, layout, dtype)
+        h, w = self._params.height, self._params.width
+        out = _feature_tensor("export_features", out, (count, h, w) if layout == "chw" else (h, w, count), dtype, self._device_ordinal)
+        check(lib.rf_renderer_export_features(self._h, C.byref(req), C.c_void_p(out.data_ptr()), out.numel() * out.element_size(), None))
+        return out
 
     # radiance second moments, the noise estimate and render-to-a-noise-target (include/rayfinder_amd.h states the estimate's arithmetic)
     def set_moments(self, enabled=True):

@@ -42,6 +42,15 @@ RF_AOV_TILE_COUNTS = 0x100
 RF_BUCKETS_TILE_COUNTS = 0x100
 RF_DIRECT_TILE_COUNTS = 0x100
 RF_BUCKETS_SHARD_TILE_COUNTS = 0x400
+# the feature export's channel groups in output order (name, RF_FEATURE_* bit, channels), its layouts and its element types
+FEATURE_GROUPS = (("color", 0x001, 3), ("albedo", 0x002, 3), ("normal", 0x004, 3), ("depth", 0x008, 1), ("coverage", 0x010, 1), ("direct", 0x020, 3),
+                  ("indirect", 0x040, 3), ("variance", 0x080, 3), ("error", 0x100, 1), ("samples", 0x200, 1))
+RF_FEATURES_CHW, RF_FEATURES_HWC = 0, 1
+RF_FEATURES_F32, RF_FEATURES_F16 = 0, 1
+
+
+class FeatureRequest(C.Structure):
+    _fields_ = [("channels", C.c_uint32), ("layout", C.c_uint32), ("dtype", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class DenoiseParameters(C.Structure):
@@ -173,6 +182,11 @@ SIGNATURES = {
                                           C.c_void_p, C.c_void_p]),
     "rf_denoise_split_tiles": (C.c_int, [C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
                                          C.c_void_p, C.c_void_p]),
+    "rf_feature_channel_count": (C.c_int, [C.c_uint32, C.POINTER(C.c_uint32)]),
+    "rf_renderer_export_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32)]),
+    "rf_comm_export_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32)]),
+    "rf_export_features_images": (C.c_int, [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p]),
     "rf_renderer_set_moments": (C.c_int, [C.c_void_p, C.c_int]),
     "rf_renderer_read_moments": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
     "rf_renderer_set_buckets": (C.c_int, [C.c_void_p, C.c_uint32]),

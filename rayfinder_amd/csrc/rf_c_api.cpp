@@ -7,6 +7,7 @@
 #include "rf_camera.hpp"
 #include "rf_checkpoint.hpp"
 #include "rf_comm.hpp"
+#include "rf_feature_request.hpp"
 #include "rf_gltf.hpp"
 #include "rf_pt_format.hpp"
 #include "rf_query.hpp"
@@ -27,6 +28,10 @@ static_assert(RF_AOV_TILE_COUNTS == rf::Renderer::kAovTileCounts);
 static_assert(RF_DIRECT_TILE_COUNTS == rf::Renderer::kDirectTileCounts && rf::Renderer::kDirectOn == 1u);
 static_assert(RF_BUCKETS_TILE_COUNTS == rf::Renderer::kBucketsTileCounts);
 static_assert(RF_BUCKETS_SHARD_TILE_COUNTS == rf::Renderer::kBucketsShardTileCounts);
+static_assert(RF_FEATURE_COLOR == rf::kFeatureColor && RF_FEATURE_ALBEDO == rf::kFeatureAlbedo && RF_FEATURE_NORMAL == rf::kFeatureNormal && RF_FEATURE_DEPTH == rf::kFeatureDepth &&
+              RF_FEATURE_COVERAGE == rf::kFeatureCoverage && RF_FEATURE_DIRECT == rf::kFeatureDirect && RF_FEATURE_INDIRECT == rf::kFeatureIndirect &&
+              RF_FEATURE_VARIANCE == rf::kFeatureVariance && RF_FEATURE_ERROR == rf::kFeatureError && RF_FEATURE_SAMPLES == rf::kFeatureSamples);
+static_assert(RF_FEATURES_CHW == rf::kFeaturesChw && RF_FEATURES_HWC == rf::kFeaturesHwc && RF_FEATURES_F32 == rf::kFeaturesF32 && RF_FEATURES_F16 == rf::kFeaturesF16);
 
 struct rf_renderer
 {
@@ -138,6 +143,13 @@ rf::DenoiseParameters toSplitParams(const rf_denoise_parameters* p, const rf::De
 rf_noise_estimate toNoiseEstimate(const rf::NoiseEstimate& e)
 {
     return rf_noise_estimate{e.meanError, e.maxError, e.worstTile, e.samples, e.pixels, e.nonfinitePixels};
+}
+
+// a feature request, checked before anything touches a device
+rf::FeatureRequest toFeatureRequest(const rf_feature_request* req)
+{
+    require(req, "null argument");
+    return rf::checkedFeatureRequest(req->channels, req->layout, req->dtype, req->reserved);
 }
 
 rf::AdaptiveParameters toAdaptiveParams(const rf_adaptive_parameters& p) { return rf::AdaptiveParameters{p.target_tile_error, p.check_every, p.min_samples, p.max_samples}; }
@@ -440,6 +452,41 @@ int rf_denoise_split_tiles(int32_t device_ordinal, uint32_t width, uint32_t heig
         require(std::isfinite(exposure), "exposure must be finite");
         rf::denoiseSplitTiles(device_ordinal, width, height, tile_samples, leading, color_sum4, direct_sum4, albedo_coverage4, normal_depth4, pd, pi, exposure, out_rgba,
                               out_bgra8);
+        return RF_OK;
+    });
+}
+
+int rf_feature_channel_count(uint32_t channels, uint32_t* count)
+{
+    return guarded([&] {
+        require(count, "null argument");
+        rf::checkedFeatureRequest(channels, RF_FEATURES_CHW, RF_FEATURES_F32, 0u);
+        *count = rf::featureChannelCount(channels);
+        return RF_OK;
+    });
+}
+
+int rf_renderer_export_features(rf_renderer* r, const rf_feature_request* req, void* dst_device, uint64_t dst_bytes, uint32_t* sample_count)
+{
+    return guarded([&] {
+        require(r && req && dst_device, "null argument");
+        const rf::FeatureRequest request = toFeatureRequest(req);
+        const uint32_t           samples = r->impl->exportFeatures(request, dst_device, dst_bytes);
+        if (sample_count) *sample_count = samples;
+        return RF_OK;
+    });
+}
+
+int rf_export_features_images(int32_t device_ordinal, uint32_t width, uint32_t height, uint32_t samples, const uint32_t* tile_samples, const float* color_sum4,
+                              const float* sumsq4, const float* albedo_coverage4, const float* normal_depth4, const float* direct_sum4, const rf_feature_request* req,
+                              void* out_host)
+{
+    return guarded([&] {
+        const rf::FeatureRequest request = toFeatureRequest(req);
+        const uint32_t           have = (color_sum4 ? rf::kFeatureReadsS : 0u) | (sumsq4 ? rf::kFeatureReadsQ : 0u) |
+                              (albedo_coverage4 && normal_depth4 ? rf::kFeatureReadsAovs : 0u) | (direct_sum4 ? rf::kFeatureReadsD : 0u);
+        rf::checkFeatureImages(width, height, samples, tile_samples, have, request, out_host);
+        rf::exportFeaturesImages(device_ordinal, width, height, samples, tile_samples, color_sum4, sumsq4, albedo_coverage4, normal_depth4, direct_sum4, request, out_host);
         return RF_OK;
     });
 }
@@ -998,6 +1045,18 @@ int rf_comm_read_split(rf_comm* c, rf_renderer* r, float* direct_rgba, float* in
         require(c && r && (direct_rgba || indirect_rgba), "null argument");
         require(r->impl->deviceOrdinal() == c->impl->deviceOrdinal(), "the renderer and the communicator are on different devices");
         c->impl->readSplit(direct_rgba, indirect_rgba, r->impl->streamHandle());
+        return RF_OK;
+    });
+}
+
+int rf_comm_export_features(rf_comm* c, rf_renderer* r, const rf_feature_request* req, void* dst_device, uint64_t dst_bytes, uint32_t* sample_count)
+{
+    return guarded([&] {
+        require(c && r && req && dst_device, "null argument");
+        const rf::FeatureRequest request = toFeatureRequest(req);
+        require(r->impl->deviceOrdinal() == c->impl->deviceOrdinal(), "the renderer and the communicator are on different devices");
+        const uint32_t samples = c->impl->exportFeatures(request, dst_device, dst_bytes, r->impl->streamHandle());
+        if (sample_count) *sample_count = samples;
         return RF_OK;
     });
 }

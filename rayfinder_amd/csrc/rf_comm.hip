@@ -3,6 +3,7 @@
 #include "rf_comm.hpp"
 
 #include "rf_denoise.hpp"
+#include "rf_features.hpp"
 #include "rf_hip_host.hpp"
 #include "rf_noise.hpp"
 #include "rf_renderer.hpp" // tilesForRank, TileGrid
@@ -861,6 +862,33 @@ void TileComm::readSplit(float* directRgba, float* indirectRgba, void* streamHan
     if (directRgba) RF_HIP(hipMemcpyAsync(directRgba, direct, n * sizeof(float4), hipMemcpyDeviceToHost, stream));
     if (indirectRgba) RF_HIP(hipMemcpyAsync(indirectRgba, indirect, n * sizeof(float4), hipMemcpyDeviceToHost, stream));
     RF_HIP(hipStreamSynchronize(stream));
+}
+
+uint32_t TileComm::exportFeatures(const FeatureRequest& request, void* dstDevice, uint64_t dstBytes, void* streamHandle)
+{
+    Impl& m = *mImpl;
+    m.requireGathered("rf_comm_export_features", kPlaneMaskImage, kPlaneNames[kPlaneImage]);
+    const uint32_t reads = featureReads(request.channels);
+    if (reads & kFeatureReadsAovs) m.requireGathered("rf_comm_export_features", kPlaneMaskAovs, "the first-hit AOVs (gather with RF_GATHER_AOVS)");
+    if (reads & kFeatureReadsQ) m.requireGathered("rf_comm_export_features", kPlaneMaskMoments, "the radiance second moments (gather with RF_GATHER_MOMENTS)");
+    if (reads & kFeatureReadsD) m.requireGathered("rf_comm_export_features", kPlaneMaskDirect, "the direct sums (plane 5, D: gather with RF_GATHER_DIRECT)");
+    if (static_cast<uint64_t>(m.imageW) * m.imageH >= (1ull << 31)) throw std::invalid_argument("rf_comm_export_features: image too large");
+    requireFeatureDestination(dstDevice, dstBytes, featureBytes(m.imageW, m.imageH, request), m.device, "rf_comm_export_features");
+    if (m.gatheredSamples == 0u) throw std::invalid_argument("rf_comm_export_features: the gathered sums hold no sample");
+    const bool perTile = (m.gatheredMask & kGatherMaskTileCounts) != 0u;
+    if (featureNeedsTwoSamples(request.channels) &&
+        (m.gatheredSamples < 2u || (perTile && *std::min_element(m.frameCountsHost.begin(), m.frameCountsHost.end()) < 2u)))
+        throw std::invalid_argument("rf_comm_export_features: RF_FEATURE_VARIANCE / RF_FEATURE_ERROR need at least 2 samples in every tile of the gathered frame");
+    hipStream_t stream = static_cast<hipStream_t>(streamHandle);
+    RF_HIP(hipSetDevice(m.device));
+    // the gathered planes are row-major and hold one count N -- or, gathered with the counts, each tile its own (a tile without a sample: +0 in every channel)
+    FeatureSources s;
+    s.colorSum = m.images[kPlaneImage].ptr, s.sumSq = m.images[kPlaneMoments].ptr, s.albedoCoverage = m.images[kPlaneAlbedoCoverage].ptr;
+    s.normalDepth = m.images[kPlaneNormalDepth].ptr, s.directSum = m.images[kPlaneDirect].ptr;
+    s.samples = m.gatheredSamples, s.tileSamples = perTile ? m.frameCounts.ptr : nullptr;
+    enqueueExportFeatures(stream, s, m.imageW, m.imageH, false, request, dstDevice);
+    RF_HIP(hipStreamSynchronize(stream));
+    return m.gatheredSamples;
 }
 
 double TileComm::allReduceMax(double value, void* streamHandle)

@@ -161,6 +161,10 @@ public:
     // indirect = {(S.rgb - D.rgb) / float(n), 1}, n = N or, gathered with the counts, the pixel's tile's count ({0, 0, 0, 1} for both in a tile without a sample: readMean's
     // rule; without the counts N = 0 is refused).  One kernel (rf_noise.hpp: enqueueSplitMeanRows) on `stream`, then waited for.  Needs kPlaneMaskDirect.
     void readSplit(float* directRgba, float* indirectRgba, void* stream);
+    // The feature export (rf_features.hpp; the definition: include/rayfinder_amd.h) over the gathered row-major planes 0 .. 3 and 5 where they lie, per tile count when the
+    // counts travelled: into `dstDevice` (caller-owned memory of this device), enqueued on `stream`, then waited for; -> N.  Needs the planes the request's channels read;
+    // VARIANCE / ERROR need every count >= 2.
+    uint32_t exportFeatures(const FeatureRequest& request, void* dstDevice, uint64_t dstBytes, void* stream);
     // Max over ranks of a host double / barrier (timing plumbing for callers that have no other collective layer).
     double allReduceMax(double value, void* stream);
 

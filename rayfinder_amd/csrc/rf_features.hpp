@@ -1,0 +1,34 @@
+// rf_features.hpp -- the feature export (rf_features.hip; the definition: include/rayfinder_amd.h, "Feature export"): the per-pixel feature channels of a frame's sums
+// -- means, first-hit guides, the variance of the mean, the noise estimate's error, the sample count -- written as one planar (CHW) or interleaved (HWC) f32 / f16
+// tensor into caller-owned device memory.  Shared by rf_renderer_export_features (the handle's own compact tile-major sums), rf_comm_export_features (the row-major
+// planes gathered on the root) and the standalone rf_export_features_images (host-assembled row-major sums).
+#pragma once
+
+#include "rf_feature_request.hpp"
+#include "rf_hip_host.hpp"
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace rf
+{
+// The sums of one frame in device memory, all in one layout; a plane no selected channel reads may be nullptr.  tileSamples (device, one count per tile of the frame's
+// 32 x 32 grid, tile_y * ceil(width / 32) + tile_x) == nullptr: `samples` for every pixel.
+struct FeatureSources
+{
+    const float4 *  colorSum = nullptr, *sumSq = nullptr, *albedoCoverage = nullptr, *normalDepth = nullptr, *directSum = nullptr;
+    const uint32_t* tileSamples = nullptr;
+    uint32_t        samples = 0;
+};
+
+// std::invalid_argument unless hipPointerGetAttributes reports `dst` as device memory of device `deviceOrdinal` (a host pointer, registered or managed memory and
+// another device's memory are all refused), or when `bytes` is smaller than `needed`.  No launch.
+void requireFeatureDestination(const void* dst, uint64_t bytes, uint64_t needed, int deviceOrdinal, const char* what);
+
+// Enqueue the one export kernel on `stream`: one 256-lane workgroup per 32 x 32 tile.  tileMajor: the sums are compact tile-major buffers holding every tile of the
+// frame in tile order (a handle without a tile shard); else row-major.  width * height < 2^31; the request is valid; dst holds featureBytes() and is element aligned.
+void enqueueExportFeatures(hipStream_t stream, const FeatureSources& sources, uint32_t width, uint32_t height, bool tileMajor, const FeatureRequest& request, void* dst);
+
+// (the standalone export over host-assembled sums, exportFeaturesImages, is declared with the other *Images calls: rf_renderer.hpp)
+} // namespace rf

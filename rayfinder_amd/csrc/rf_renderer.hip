@@ -23,6 +23,7 @@
 // device memory, so a whole batch is enqueued without any host round trip.
 #include "rayfinder_amd.h"
 #include "rf_denoise.hpp"
+#include "rf_features.hpp"
 #include "rf_kernels.hpp"
 #include "rf_noise.hpp"
 #include "rf_robust.hpp"
@@ -1659,6 +1660,45 @@ void Renderer::denoiseSplit(const DenoiseParameters& direct, const DenoiseParame
                         direct, indirect, m.params.exposure, perTile ? m.uploadTileSamples() : nullptr);
     m.denoisedValid = true;
     m.denoisedSamples = m.accumulated;
+}
+
+uint32_t Renderer::exportFeatures(const FeatureRequest& request, void* dstDevice, uint64_t dstBytes)
+{
+    Impl&          m = *mImpl;
+    const uint32_t reads = featureReads(request.channels);
+    requireFeatureDestination(dstDevice, dstBytes, featureBytes(m.params.width, m.params.height, request), m.device, "rf_renderer_export_features");
+    if (m.worldSize != 1u)
+        throw std::invalid_argument("export_features needs the whole frame: a tile shard is set (gather the frame -- rf_renderer_gather_frame -- and call rf_comm_export_features on the root)");
+    if (m.accumulated == 0u) throw std::invalid_argument("export_features: no sample has been accumulated");
+    // each selected channel's family: on, covering the accumulation and -- in the non-uniform state -- kept per tile count (the moments always are: render_adaptive needs them)
+    const bool perTile = m.nonUniform();
+    const auto family = [&](uint32_t bit, const SumChannel& sums, bool tileCounts, const char* name, const char* hint) {
+        if (!(reads & bit)) return;
+        if (!sums.on) throw std::invalid_argument(std::string("export_features: a selected channel needs ") + name + ": turn them on (" + hint + ") before the first sample");
+        if (!sums.covers(m.accumulated))
+            throw std::invalid_argument(std::string("export_features: the sample count of ") + name + " (" + std::to_string(sums.samples) + ") differs from the accumulated sample count (" +
+                                        std::to_string(m.accumulated) + "): turn them on before the first sample");
+        if (perTile && !tileCounts)
+            m.requireUniform("rf_renderer_export_features", (std::string(", and ") + name + " were not kept with per-tile counts (" + hint + " with the tile-count bit before the first sample)").c_str());
+    };
+    family(kFeatureReadsAovs, m.aovSums, m.aovTileCounts(), "the first-hit AOVs", "rf_renderer_set_aovs");
+    family(kFeatureReadsD, m.directSums, m.directTileCounts(), "the direct sums", "rf_renderer_set_direct");
+    family(kFeatureReadsQ, m.momentSums, true, "the radiance second moments", "rf_renderer_set_moments");
+    if (featureNeedsTwoSamples(request.channels))
+    {
+        if (m.accumulated < 2u) throw std::invalid_argument("export_features: RF_FEATURE_VARIANCE / RF_FEATURE_ERROR need at least 2 accumulated samples");
+        if (perTile && *std::min_element(m.tileSamples.begin(), m.tileSamples.end()) < 2u)
+            throw std::invalid_argument("export_features: RF_FEATURE_VARIANCE / RF_FEATURE_ERROR need at least 2 samples in every tile");
+    }
+    RF_HIP(hipSetDevice(m.device));
+    FeatureSources s;
+    s.colorSum = m.image, s.sumSq = m.moments(), s.albedoCoverage = m.aovAlbedoCoverage(), s.normalDepth = m.aovNormalDepth(), s.directSum = m.direct();
+    s.samples = m.accumulated;
+    // (per tile: the call first waits for the stream and copies the counts to the device)
+    s.tileSamples = perTile ? m.uploadTileSamples() : nullptr;
+    enqueueExportFeatures(m.stream, s, m.params.width, m.params.height, true, request, dstDevice);
+    RF_HIP(hipStreamSynchronize(m.stream)); // the buffer may be used from any stream once the call returns
+    return m.accumulated;
 }
 
 void Renderer::setBuckets(uint32_t word)

@@ -28,6 +28,8 @@ struct rf_launch_plan; // include/rayfinder_amd.h
 
 namespace rf
 {
+struct FeatureRequest; // rf_feature_request.hpp
+
 struct SamplingParams
 {
     uint32_t numSamplesPerPixel = 128;
@@ -154,6 +156,12 @@ void denoiseSplitTiles(int deviceOrdinal, uint32_t width, uint32_t height, const
                        const float* albedoCoverage, const float* normalDepth, const DenoiseParameters& direct, const DenoiseParameters& indirect, float exposure,
                        float* outRgba, uint32_t* outBgra8);
 
+// The feature export (rf_features.hip; the definition: include/rayfinder_amd.h) over host-assembled row-major width*height*4 sums (NULL where no selected channel reads
+// them) on device `deviceOrdinal`, into host memory: width * height * C elements.  tileSamples as denoiseTiles takes them, nullptr: `samples` for every pixel.
+// Synchronous; allocates and frees its own device memory.  The arguments have passed checkFeatureImages (rf_feature_request.hpp).
+void exportFeaturesImages(int deviceOrdinal, uint32_t width, uint32_t height, uint32_t samples, const uint32_t* tileSamples, const float* colorSum, const float* sumSq,
+                          const float* albedoCoverage, const float* normalDepth, const float* directSum, const FeatureRequest& request, void* outHost);
+
 // The firefly-robust mean (rf_robust.hip; the definition: include/rayfinder_amd.h) over host-assembled bucket planes -- K x width*height*4 floats, plane after plane,
 // each row-major -- of `samples` >= K samples, on device `deviceOrdinal`: the mean RGBA (.w = 1), its BGRA8 under `exposure` and the trim count of every pixel
 // (NULL = skip).  K odd, 3 .. 15.  Synchronous; allocates and frees its own device memory.
@@ -271,6 +279,12 @@ public:
     // and both cover the accumulation (prep then divides each pixel by its tile's count; the snapshot's count is the leading count; the call first waits for the
     // stream and copies the counts to the device), and refuses as requireUniformTileSamples does otherwise -- before any other check.
     void denoiseSplit(const DenoiseParameters& direct, const DenoiseParameters& indirect);
+    // The feature export (rf_renderer_export_features; the definition: include/rayfinder_amd.h): the request's channels of the handle's own tile-major sums into
+    // `dstDevice` (caller-owned memory of the handle's device, dstBytes of it), enqueued on the handle's stream and waited for; -> the accumulated (leading) count.  In the
+    // non-uniform state every pixel takes its tile's count (uploadTileSamples, as the other per-tile reads).  Read-only.  std::invalid_argument, before any launch: a
+    // destination that is too small or not device memory of this device, a tile shard, no sample, a selected channel whose family is off, does not cover the accumulation
+    // or -- in the non-uniform state -- was kept without its tile-count bit, VARIANCE / ERROR below 2 samples.
+    uint32_t exportFeatures(const FeatureRequest& request, void* dstDevice, uint64_t dstBytes);
     // Bucket sums (rf_renderer_set_buckets / rf_renderer_read_buckets): K = 0 off (the default), else odd, 3 .. 15.  While on, K more compact tile-major float4 planes
     // in one allocation: plane b holds {sum r.x, sum r.y, sum r.z, 0} over the samples whose ordinal -- the bucket sample count just before the sample -- is b mod K,
     // in sample order.  Their own sample count; cleared with the image and whenever the word changes.  The word is K, or K | kBucketsTileCounts (K > 0): until
