@@ -133,6 +133,13 @@ typedef struct rf_stats
      * path came from (wgsl:511-519), so wherever the sun stands behind that normal shadowRay (wgsl:321-368) finds the surface itself.  The shading stage tests exactly that
      * (the leaf's exact box, then the triangle, with the reference's arithmetic) and such a ray is never queued for an any-hit launch.  Same visibility bit. */
     uint64_t shadow_rays_self_answered;
+    /* Bounce 1 over per-pixel leaf lists (option primary_lists, default on).  Under a pinhole camera all samples of a pixel share one origin and a pixel-sized bundle of
+     * directions; a batch with enough samples per pixel walks the tree ONCE per pixel (interval slab tests over the pixel's direction box, the reference's visit order) and
+     * every sample then tests only the exact boxes and the triangles of the few leaves on its pixel's list -- same hits bit for bit.  primary_list_rays: bounce-1 rays of the
+     * batches that did so (0: a thin-lens camera, the option off, a counting build, batches below primary_list_min_samples samples per pixel, a tree whose boxes are not
+     * nested).  primary_fallback_rays: of those, rays handed on to the ordinary traversal launch (a pixel whose directions change sign on an axis, whose list would
+     * exceed primary_list_capacity entries or holds a leaf of more than 7 triangles; a ray with an infinite 1 / direction component). */
+    uint64_t primary_list_rays, primary_fallback_rays;
 } rf_stats;
 
 typedef struct rf_renderer rf_renderer;
@@ -685,6 +692,12 @@ RF_API int rf_renderer_set_timing(rf_renderer* r, int enabled);
  *                                      scene (default 1024); occluder_grid_log2_cells n: table of 2^n cells x 16 bytes (default 22);
  *                                      shadow_first_look_from_bounce b: from this bounce on that first look is a dense pass of its own
  *                                      (kShadowFirstLook; default 2, 0: never).  Same image with any setting.
+ *   primary_lists 0 | 1                bounce 1 of a pinhole camera over per-pixel leaf lists (default 1): a batch with at least primary_list_min_samples samples per
+ *                                      pixel (default 16: the crossover measured at 1080p lies at about 10) walks the tree once per pixel and gives every sample the
+ *                                      exact box and triangle tests of the leaves on its pixel's list; primary_list_capacity n: entries per pixel (1 .. 64,
+ *                                      default 64; 65 words of device memory per pixel of a batch, counted by rf_renderer_memory_info and the batch-depth fit; a
+ *                                      pixel that needs more takes the ordinary launch).  rf_stats.primary_list_rays / primary_fallback_rays say what ran.
+ *                                      Same image with any setting.
  *   transcendentals 0 | 1              THE ONE OPTION THAT CHANGES RESULTS (round 6; default 0).  0: sin / cos / acos / exp / pow(x, 1.5) of ray generation and the sky dome are
  *                                      the f32 rounding of a specified f64 evaluation (GPU == test oracle bit for bit); 1: the device math library's f32 functions (libm-grade) --
  *                                      WGSL's own builtins are f32 with implementation-defined ulps (wgsl:247-275,568-616).  Within SURVEY 8(d)'s tolerance of the default

@@ -762,6 +762,8 @@ int rf_renderer_get_stats(rf_renderer* r, rf_stats* out)
         out->scalar_redo_rays = s.scalarRedoRays;
         out->shadow_rays_hint_answered = s.shadowRaysHintAnswered;
         out->shadow_rays_self_answered = s.shadowRaysSelfAnswered;
+        out->primary_list_rays = s.primaryListRays;
+        out->primary_fallback_rays = s.primaryFallbackRays;
         return RF_OK;
     });
 }

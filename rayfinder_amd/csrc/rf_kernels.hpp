@@ -121,6 +121,9 @@ struct DeviceCounters
     // RF_EXP_PHASE builds (round 6): what the lanes that do NOT take a step in a descend trip are doing -- parked at a leaf (waiting for the leaf phase) or without a ray
     // (finished / never filled: waiting for the refill); and, in the leaf passes, lanes that still stand at an interior node / lanes without a ray.  Lane-trips, [closest, shadow]
     unsigned long long descendParked[2], descendIdle[2], leafInterior[2], leafIdle[2];
+    // all builds: bounce-1 rays of the batches whose primary launch ran over the per-pixel leaf lists (kTraceLeafLists counts its whole queue), and those of them it handed
+    // on to the kTraceWide launch behind it (rf_primary_lists.hip)
+    unsigned long long primaryListRays, primaryFallbackRays;
 };
 
 // Division of a 32-bit unsigned by a divisor that is a RUN-TIME value but the same for a whole launch (samples per batch, tiles per row, samples per pixel): the exact quotient from
@@ -383,6 +386,10 @@ static_assert(kOccSlots == 1 || kOccSlots == 2 || kOccSlots == 4, "one aligned l
 // (no leaf word reaches them: that would take count field 7 with big-leaf index 0x0FFFFFFE).
 constexpr uint32_t kNodeIdle = 0xFFFFFFFFu; // no ray
 constexpr uint32_t kNodeDone = 0xFFFFFFFEu; // ray finished, result not yet written
+// length word of a pixel without a leaf list (kPixelLeafLists): bit 31, and in its low bits why -- its rays take the kTraceWide launch
+constexpr uint32_t kNoPrimaryList = 0x80000000u;
+constexpr uint32_t kNoListSigns = 1u, kNoListOverflow = 2u, kNoListBigLeaf = 3u, kNoListStack = 4u; // the direction box touches zero on an axis / more leaves than the capacity / a leaf of 8 or more triangles / a walk deeper than its stack
+constexpr uint32_t kPrimaryListMaxCapacity = 64u; // (the length sits in bits 7..0 of the word, the direction signs in bits 10..8)
 
 
 // ---- kernel entry points (defined in rf_trace.hip / rf_shade.hip; nullptr: that instantiation is not compiled into this build)
@@ -394,6 +401,8 @@ using SkyKernel = void (*)(SkyStateGpu sky, PathStreams ps, const uint32_t* miss
 using TraceShadowKernel = void (*)(DeviceScene scene, SkyStateGpu sky, SunBasis sunBasis, PathStreams ps, const uint32_t* queue, const uint32_t* queueCount, DeviceCounters* counters, uint32_t firstBounce);
 using TraceWideKernel = void (*)(DeviceScene scene, WideScene wide, SkyStateGpu sky, SunBasis sunBasis, PathStreams ps, const uint32_t* queue, const uint32_t* queueCount, uint32_t* cursor, DeviceCounters* counters, uint32_t refillMin, uint32_t leafVote, uint32_t chunkMax, float tMax, uint32_t flags);
 using ShadowFirstLookKernel = void (*)(DeviceScene scene, WideScene wide, SkyStateGpu sky, SunBasis sunBasis, PathStreams ps, const uint32_t* queue, const uint32_t* inList, const uint32_t* inCount, uint32_t* list, uint32_t* listCount, DeviceCounters* counters, float tMax, uint32_t flags);
+using PixelLeafListsKernel = void (*)(FrameParams fp, DeviceScene scene, const uint32_t* tileIds, uint32_t capacity, uint32_t* lists, uint32_t* lengths);
+using TraceLeafListsKernel = void (*)(DeviceScene scene, PathStreams ps, const uint32_t* queueCount, FastDiv divNumSamples, float originX, float originY, float originZ, const uint32_t* lists, const uint32_t* lengths, uint32_t capacity, uint32_t* fallback, uint32_t* fallbackCount, DeviceCounters* counters, float tMax);
 using TracePacketKernel = void (*)(DeviceScene scene, WideScene wide, SkyStateGpu sky, SunBasis sunBasis, PathStreams ps, const uint32_t* queue, const uint32_t* queueCount, DeviceCounters* counters, float tMax, uint32_t flags);
 using HitPointsKernel = void (*)(DeviceScene scene, const float4* hit, P3* rayO, uint32_t n);
 using BounceTotalsKernel = void (*)(const uint32_t* queueCounts, uint32_t numBounces, unsigned long long* totals, const uint32_t* listCounts, unsigned long long lookMask, unsigned long long* lookBatch, const uint32_t* shadowListCounts, unsigned long long selfMask, DeviceCounters* counters);
@@ -413,6 +422,9 @@ HitPointsKernel       hitPointsKernel();
 PrimaryStatsKernel    primaryStatsKernel();
 IntersectRaysKernel   intersectRaysKernel();
 OccludedRaysKernel    occludedRaysKernel();
+// rf_primary_lists.hip
+PixelLeafListsKernel pixelLeafListsKernel();
+TraceLeafListsKernel traceLeafListsKernel();
 // rf_shade.hip
 SamplePermutationKernel samplePermutationKernel();
 RaygenKernel            raygenKernel(bool f32Transcendentals);

@@ -314,6 +314,13 @@ struct Renderer::Impl
     bool     optShadowSelfTest = true; // kShade tests every shadow ray against the triangle it starts on first (kShadeSelfShadow); needs selfShadowOk
     bool     selfShadowOk = false;     // the tree's boxes are nested and regular, and the shading records carry their triangles' leaf boxes
     bool     optConstPrimaryOrigin = true; // a pinhole camera's primary launch takes its one origin as a kernel argument (kFlagConstOrigin): kRaygen writes no origins
+    // Bounce 1 over per-pixel leaf lists (rf_primary_lists.hip; option primary_lists, default on): where the plan selects them (planBatch) kPixelLeafLists walks the tree once per
+    // pixel and kTraceLeafLists gives every sample the exact tests of the few leaves on its pixel's list; what the lists do not cover takes the bounce's kTraceWide launch.
+    // primary_list_capacity: entries per pixel (a longer list: no list for that pixel); primary_list_min_samples: batches with fewer samples per pixel keep the old launch
+    // (the list pass costs a few rays' worth per pixel: profiles/primary_lists/README.md)
+    bool     optPrimaryLists = true;
+    uint32_t optPrimaryListCapacity = 64, optPrimaryListMinSamples = 16;
+    DeviceBuffer<uint32_t> primaryLists, primaryLengths; // [valid-pixel rank of the batch][capacity] leaf words / [rank] length word; allocated by the first batch that uses them
     bool                   optSampleSort = true, optAccumulateRuns = true;
     uint32_t               optCompactFromBounce = 3;       // closest-hit launches of bounce >= this use the compact-capable records (0: never)
     uint32_t               optCompactShadowFromBounce = 2; // ... and the shadow launches of bounce >= this
@@ -373,6 +380,12 @@ struct Renderer::Impl
     static constexpr uint64_t kAovBytesPerPath = 2 * sizeof(float4);
     uint64_t bytesPerPath() const { return kBytesPerPath + (aovSums.on ? kAovBytesPerPath : 0u); }
     uint64_t pathStateBytes() const { return allocatedPaths * kBytesPerPath + sAov.count * sizeof(float4); }
+    // the per-pixel leaf lists of bounce 1: capacity + 1 words per valid pixel of a batch (1080p at the default capacity of 64: 539 MB)
+    uint64_t primaryListBytes() const { return (primaryLists.count + primaryLengths.count) * sizeof(uint32_t); }
+    uint64_t primaryListBytesWanted(uint64_t pixels) const { return primaryListsPossible() ? pixels * (std::min(std::max(optPrimaryListCapacity, 1u), kPrimaryListMaxCapacity) + 1ull) * sizeof(uint32_t) : 0u; }
+    // what does not depend on the batch: the option, and the gates the conservative records and kShade's own-triangle test already rest on -- boxes regular and nested all
+    // the way up, every leaf's exact box in its first triangle record
+    bool primaryListsPossible() const { return optPrimaryLists && !counting && traversalVariant != 0 && selfShadowOk && leafBoxesValid; }
     // the path state holds a batch of `paths` (the AOV records included while the AOVs are on)
     bool pathStateHolds(uint64_t paths) const { return paths <= allocatedPaths && (!aovSums.on || sAov.count >= 2 * paths); }
 
@@ -425,8 +438,11 @@ struct Renderer::Impl
     {
         size_t freeBytes = 0, totalBytes = 0;
         RF_HIP(hipMemGetInfo(&freeBytes, &totalBytes));
+        // (the per-pixel leaf lists of bounce 1, where a batch would use them: what is not allocated yet comes off the budget)
+        const uint64_t listsWanted = primaryListBytesWanted(validPixels), listsHeld = primaryListBytes();
         const uint64_t budget = static_cast<uint64_t>(freeBytes) + pathStateBytes();
-        return budget / 10 * 9 / bytesPerPath();
+        const uint64_t reserve = listsWanted > listsHeld ? listsWanted - listsHeld : 0u;
+        return (budget > reserve ? budget - reserve : 0u) / 10 * 9 / bytesPerPath();
     }
 
     void configureShard()
@@ -581,6 +597,8 @@ struct Renderer::Impl
     {
         uint32_t numSamples, numBounces, numTiles, pixelsPadded;
         bool     samplePerm, denseRaygen, constOrigin;
+        bool     primaryLists;        // bounce 1's closest-hit group: kPixelLeafLists + kTraceLeafLists + the bounce's kTraceWide launch over what they hand on
+        uint32_t primaryListCapacity; // entries per pixel
         int      primaryLayout;
         bool     occluderGrid; // the batch's any-hit launches get the occluder grid: occluderGridEntries words, cells found by occScale / occMask
         uint64_t occluderGridEntries;
@@ -609,7 +627,10 @@ struct Renderer::Impl
         uint32_t*                 base;
         uint32_t                  numBounces;
         static constexpr uint32_t kLine = kLineWords, kCursorWords = kLine * kShards;
-        uint32_t words() const { return kLine * (2 * numBounces + 1) + kCursorWords * 2 * numBounces + kLine * numBounces + kLine * numBounces; }
+        uint32_t words() const { return primaryFallbackWord() + kLine; }
+        // (behind everything else: the length of the list of bounce-1 rays kTraceLeafLists hands on to the bounce's kTraceWide launch)
+        uint32_t primaryFallbackWord() const { return kLine * (2 * numBounces + 1) + kCursorWords * 2 * numBounces + kLine * numBounces + kLine * numBounces; }
+        uint32_t* primaryFallbackCount() const { return base + primaryFallbackWord(); }
         uint32_t queueWord(uint32_t b) const { return kLine * b; }
         uint32_t missWord(uint32_t b) const { return kLine * (numBounces + 1) + kLine * (b - 1); }
         uint32_t cursorClosestWord(uint32_t b) const { return kLine * (2 * numBounces + 1) + kCursorWords * 2 * (b - 1); }
@@ -786,6 +807,11 @@ struct Renderer::Impl
                         finite3(camNow.origin) && finite3(camNow.right) && finite3(camNow.up) && b.primaryLayout != kLayoutScalar && b.primaryLayout != kLayoutPacket;
         // (kRaygen computes its queue positions instead of appending with one atomic per 1 024 slots, where the slot order allows it: FrameParams::tileValidBefore)
         b.denseRaygen = optDenseRaygen && (optSlotGroupShift == 0u || optSlotGroupShift == kSlotSampleMajor) && static_cast<uint64_t>(validPixels) * numSamples <= 0xFFFFFFFFull;
+        // Bounce 1 over per-pixel leaf lists: one origin for the whole batch (constOrigin: a pinhole camera, primary launch on kTraceWide), the scene's gates
+        // (primaryListsPossible), a queue in which a pixel's samples are contiguous by the pixel's rank (dense kRaygen, pixel-major slots), at least one bounce, and enough
+        // samples per pixel for the once-per-pixel walk to pay.  A thin-lens camera, a counting build and small batches keep the kTraceWide launch alone.
+        b.primaryListCapacity = std::min(std::max(optPrimaryListCapacity, 1u), kPrimaryListMaxCapacity);
+        b.primaryLists = primaryListsPossible() && b.constOrigin && b.denseRaygen && optSlotGroupShift == 0u && b.numBounces != 0u && numSamples >= std::max(optPrimaryListMinSamples, 1u);
         b.occluderGrid = optOccluderCacheBounces != 0u && optOccluderGridCells != 0u;
         if (b.occluderGrid)
         {
@@ -1080,6 +1106,22 @@ struct Renderer::Impl
         dim3          persistentGrid;
     };
     static dim3 cappedGrid(uint32_t blocks, uint32_t cap) { return dim3(cap ? std::min(blocks, cap) : blocks); }
+    // Bounce 1 over the per-pixel leaf lists (BatchPlan::primaryLists): the lists for this batch's pixels, the walker over the whole queue, then the bounce's own
+    // kTraceWide launch over the queue positions the walker handed on (WideScene::rayList; the walker has counted the queue's rays).  The bounce's OUTPUT queue is
+    // free until kShade appends to it and holds that list meanwhile; its length is a device word, so an empty list costs one short launch.
+    void enqueuePrimaryLists(const BatchPlan& b, const FrameParams& fp, const TraversalPlan& t, const BounceIo& io)
+    {
+        uint32_t* const countIn = io.words.queueCount(0);
+        hipLaunchKernelGGL(pixelLeafListsKernel(), dim3((fp.pixelsPadded + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, fp, scene, tileIds.ptr, b.primaryListCapacity, primaryLists.ptr,
+                           primaryLengths.ptr);
+        hipLaunchKernelGGL(traceLeafListsKernel(), cappedGrid(io.itemBlocks, std::max(multiProcessors, 1u) * 32u), dim3(kBlock), 0, stream, scene, io.ps, countIn, fp.divNumSamples, wide.constOriginX,
+                           wide.constOriginY, wide.constOriginZ, primaryLists.ptr, primaryLengths.ptr, b.primaryListCapacity, io.out, io.words.primaryFallbackCount(), counters.ptr, kTMax);
+        WideScene     w = wide;
+        TraversalPlan rest = t;
+        w.rayList = io.out;
+        rest.flags |= kFlagNoRayCount;
+        launchWide(rest, w, WideArgs{io.ps, io.in, io.words.primaryFallbackCount(), io.words.cursorClosest(io.bounce), kTMax, io.persistentGrid, io.blocks});
+    }
     void enqueueClosest(const TraversalPlan& t, const BounceIo& io)
     {
         uint32_t* const countIn = io.words.queueCount(io.bounce - 1);
@@ -1246,6 +1288,28 @@ struct Renderer::Impl
         }
         else if (firstLookHoldOff != 0u) --firstLookHoldOff;
         batch.firstLookReady = occluderGridWarm && firstLookHoldOff == 0u;
+        if (batch.primaryLists)
+        {
+            // (grown, never shrunk; a batch that cannot have them keeps the kTraceWide launch -- same image)
+            const uint64_t entries = validPixels * batch.primaryListCapacity;
+            if (primaryLists.count < entries || primaryLengths.count < validPixels)
+            {
+                RF_HIP(hipStreamSynchronize(stream)); // an earlier batch may still read the old ones
+                primaryLists.release(), primaryLengths.release();
+                void *pl = nullptr, *pn = nullptr;
+                if (hipMalloc(&pl, std::max<uint64_t>(entries, 1) * sizeof(uint32_t)) == hipSuccess && hipMalloc(&pn, std::max<uint64_t>(validPixels, 1) * sizeof(uint32_t)) == hipSuccess)
+                {
+                    primaryLists.ptr = static_cast<uint32_t*>(pl), primaryLists.count = std::max<uint64_t>(entries, 1);
+                    primaryLengths.ptr = static_cast<uint32_t*>(pn), primaryLengths.count = std::max<uint64_t>(validPixels, 1);
+                }
+                else
+                {
+                    (void)hipGetLastError(); // out of device memory: clear the sticky error
+                    if (pl != nullptr) (void)hipFree(pl);
+                    batch.primaryLists = false;
+                }
+            }
+        }
         RF_HIP(hipMemsetAsync(lookBatch.ptr, 0, 2 * sizeof(unsigned long long), stream));
         BatchTiming bt{getEvent(), getEvent(), numSamples};
         RF_HIP(hipEventRecord(bt.start, stream));
@@ -1269,7 +1333,9 @@ struct Renderer::Impl
             const BouncePlan plan = planBounce(io.bounce, batch);
             if (plan.selfShadow) selfMask |= 1ull << (io.bounce - 1);
             if (plan.firstLook) lookMask |= 1ull << (io.bounce - 1);
-            launchTimed(1, [&] { enqueueClosest(plan.closest, io); }, io.bounce - 1);
+            // (the list launches run inside the timing group of the bounce's closest-hit launch: ms_closest, launches_closest and the per-bounce figures keep their meaning)
+            const bool lists = io.bounce == 1u && batch.primaryLists && plan.closest.kernel == kKernelWide && !plan.closest.count;
+            launchTimed(1, [&] { if (lists) enqueuePrimaryLists(batch, fp, plan.closest, io); else enqueueClosest(plan.closest, io); }, io.bounce - 1);
             launchTimed(2, [&] { enqueueShadeAndSky(plan, io); });
             launchTimed(3, [&] { enqueueShadow(plan, io); }, io.bounce - 1);
             if (io.bounce == 1u && directSums.on) launchTimed(4, [&] { enqueueDirect(batch, fp, io.ps); });
@@ -1286,6 +1352,25 @@ struct Renderer::Impl
             lookPending = true;
         }
         if (wide.occGrid != nullptr) occluderGridWarm = true;
+        // RF_DEBUG_PRIMARY_LISTS: the batch's list lengths as a histogram on stderr (waits for the batch: a measurement aid, profiles/primary_lists)
+        if (batch.primaryLists && numBounces != 0u && std::getenv("RF_DEBUG_PRIMARY_LISTS") != nullptr)
+        {
+            std::vector<uint32_t> len(validPixels);
+            RF_HIP(hipStreamSynchronize(stream));
+            RF_HIP(hipMemcpy(len.data(), primaryLengths.ptr, len.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            std::vector<uint64_t> histogram(kPrimaryListMaxCapacity + 1u, 0);
+            uint64_t              none = 0, sum = 0, why[8] = {};
+            for (const uint32_t w : len)
+                if ((w & kNoPrimaryList) != 0u) ++none, ++why[w & 7u];
+                else ++histogram[w & 0xFFu], sum += w & 0xFFu;
+            std::fprintf(stderr, "[rf-primary-lists] pixels %zu, without a list %llu (%.4f %%), mean length %.3f, capacity %u, samples %u | length:count", len.size(),
+                         static_cast<unsigned long long>(none), len.empty() ? 0.0 : 100.0 * static_cast<double>(none) / static_cast<double>(len.size()),
+                         len.size() > none ? static_cast<double>(sum) / static_cast<double>(len.size() - none) : 0.0, batch.primaryListCapacity, numSamples);
+            for (size_t l = 0; l < histogram.size(); ++l)
+                if (histogram[l] != 0) std::fprintf(stderr, " %zu:%llu", l, static_cast<unsigned long long>(histogram[l]));
+            std::fprintf(stderr, " | no list: signs %llu, overflow %llu, big leaf %llu, stack %llu\n", static_cast<unsigned long long>(why[kNoListSigns]),
+                         static_cast<unsigned long long>(why[kNoListOverflow]), static_cast<unsigned long long>(why[kNoListBigLeaf]), static_cast<unsigned long long>(why[kNoListStack]));
+        }
         launchTimed(4, [&] { enqueueSums(batch, fp, io.ps); });
         RF_HIP(hipGetLastError());
         RF_HIP(hipEventRecord(bt.stop, stream));
@@ -1374,6 +1459,9 @@ Renderer::Renderer(const RendererDescriptor& desc, const SceneView& sceneView) :
         m.skyBlocks = 8u * static_cast<uint32_t>(prop.multiProcessorCount);
         if (const char* v = std::getenv("RF_TRAVERSAL_VARIANT")) m.traversalVariant = std::atoi(v);
         if (const char* v = std::getenv("RF_PACKET_BOUNCES")) m.optPacketBounces = static_cast<uint32_t>(std::max(std::atoi(v), 0)); // experiments: whole test suite through kTracePacket
+        // soak runs (tools/gpu_fuzz.py): the leaf lists of bounce 1 for batches of any depth, at a given capacity -- what the options primary_list_min_samples / primary_list_capacity set per handle
+        if (const char* v = std::getenv("RF_PRIMARY_LIST_MIN_SAMPLES")) m.optPrimaryListMinSamples = static_cast<uint32_t>(std::clamp(std::atoi(v), 1, 1 << 30));
+        if (const char* v = std::getenv("RF_PRIMARY_LIST_CAPACITY")) m.optPrimaryListCapacity = static_cast<uint32_t>(std::clamp(std::atoi(v), 1, static_cast<int>(kPrimaryListMaxCapacity)));
         if (!m.wideUsable) m.traversalVariant = 0;
     }
 
@@ -2205,7 +2293,7 @@ void Renderer::memoryInfo(uint64_t& pathStateBytes, uint64_t& pathsAllocated, ui
 {
     const Impl& m = *mImpl;
     pathsAllocated = m.allocatedPaths;
-    pathStateBytes = m.pathStateBytes() + m.directSums.buffers[0].count * sizeof(float4); // (the direct sums, while they are on: 16 B per pixel of the shard's tiles)
+    pathStateBytes = m.pathStateBytes() + m.directSums.buffers[0].count * sizeof(float4) + m.primaryListBytes(); // (the direct sums, while they are on: 16 B per pixel of the shard's tiles; the leaf lists of bounce 1)
     maxPathsPerBatch = m.effectivePaths ? std::min(m.effectivePaths, m.maxPaths) : m.maxPaths;
     sceneBytes = (m.nodes.count + m.triangles.count + m.wideNodes.count + m.wideCompact.count + m.wideHot.count + m.wideOwn.count + m.wideQuad.count + m.wideQuadHalf.count + m.wideQuadLocal.count + m.wideOct.count + m.attributes.count + m.shadeRecords.count) * sizeof(float4) +
                  m.texels.count * sizeof(uint32_t) + m.bigLeaves.count * sizeof(uint2) + m.occluderGrid.count * sizeof(uint32_t); // (the occluder grid: allocated by the first batch)
@@ -2347,6 +2435,10 @@ void Renderer::setOption(const std::string& name, int64_t value)
     else if (name == "shade_blocks") mImpl->optShadeBlocks = static_cast<uint32_t>(value);
     else if (name == "const_primary_origin") mImpl->optConstPrimaryOrigin = value != 0;
     else if (name == "shadow_self_test") mImpl->optShadowSelfTest = value != 0;
+    // bounce 1 over per-pixel leaf lists (rf_primary_lists.hip; planBatch says when): 0 keeps the kTraceWide launch alone -- same image either way
+    else if (name == "primary_lists") mImpl->optPrimaryLists = value != 0;
+    else if (name == "primary_list_capacity") mImpl->optPrimaryListCapacity = static_cast<uint32_t>(std::clamp<int64_t>(value, 1, kPrimaryListMaxCapacity));
+    else if (name == "primary_list_min_samples") mImpl->optPrimaryListMinSamples = static_cast<uint32_t>(std::clamp<int64_t>(value, 1, 1 << 30));
     // 0 (default): sin / cos / acos / exp / pow as the f32 rounding of a specified f64 evaluation (bit-identical to the test oracle); 1: the device math library's f32 functions
     // (kRaygen's lens / cone angle, kSky's dome: rf_device.hpp tSin ...), graded by SURVEY 8(d)'s tolerance.  Set it before the first sample of an accumulation.
     else if (name == "transcendentals") mImpl->optTranscendentalsF32 = value != 0;
@@ -2425,6 +2517,7 @@ RenderStats Renderer::stats()
     s.paths = m.primaryRaysHost;
     s.abandonedRays = c.abandonedRays;
     s.scalarRedoRays = c.scalarRedo[0] + c.scalarRedo[1];
+    s.primaryListRays = c.primaryListRays, s.primaryFallbackRays = c.primaryFallbackRays;
     if (std::getenv("RF_DEBUG_COUNTERS"))
         std::fprintf(stderr, "[rf] rays redone by the scalar traversal: closest %llu of %llu, shadow %llu of %llu\n", c.scalarRedo[0], c.closestRays, c.scalarRedo[1], c.shadowRays);
 #if defined(RF_EXP_PHASE)
