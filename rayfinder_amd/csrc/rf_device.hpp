@@ -19,13 +19,13 @@
 //              because lanes l and l+32 sit in different halves), overflow in scratch.
 #pragma once
 
+#include "rf_launch_constants.hpp"
 #include "rf_types.hpp"
 
 #include <hip/hip_runtime.h>
 
 namespace rf
 {
-constexpr int      kBlock = 256;          // 4 waves
 constexpr int      kLdsStack = 24;        // entries kept in LDS per lane
 constexpr int      kSpillStack = 72;      // further entries in scratch (total depth 96)
 constexpr uint32_t kMiss = 0xFFFFFFFFu;

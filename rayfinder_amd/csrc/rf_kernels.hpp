@@ -13,6 +13,7 @@
 #include "rf_data.hpp"
 #include "rf_device.hpp"
 #include "rf_hip_host.hpp"
+#include "rf_launch_constants.hpp"
 #include "rf_wide.hpp"
 
 #include <hip/hip_runtime.h>
@@ -198,8 +199,6 @@ __device__ __forceinline__ uint32_t validRankInTile(uint32_t w, uint32_t vw, uin
     return vw * min(vh, 8u * by) + ch * min(vw, 8u * bx) + cw * ly + lx;                     // block rows above + blocks to the left + rows above inside the block + pixels to the left
 }
 
-constexpr uint32_t kSlotSampleMajor = 31u;
-
 __device__ __forceinline__ void slotToSamplePixel(const FrameParams& fp, uint32_t slot, uint32_t& k, uint32_t& lp)
 {
     if (fp.slotGroupShift == kSlotSampleMajor) fp.divPixelsPadded.divmod(slot, k, lp);
@@ -348,39 +347,8 @@ __device__ __forceinline__ Vec3 sunSample(const SkyStateGpu& sky, const SunBasis
     return basisTimes(basis.u, basis.v, sun, local);
 }
 
-constexpr uint32_t kShadeLastBounce = 1u, kShadeFirstBounce = 2u;
-// kShadeSelfShadow: kShade tests every hit's shadow ray against the hit triangle ITSELF (its leaf's exact box, then the triangle: both sit in the shading record it has in
-// registers) and writes the positions of the hits that this does not settle to `shadowList`; the bounce's any-hit launches work through that list only (see kShade)
-constexpr uint32_t kShadeSelfShadow = 4u;
-constexpr uint32_t kLookFirstBounce = 1u, kLookNoRayCount = 2u; // kShadowFirstLook's flags
-
-// ------------------------------------------------------------------------------------------------
-// Scheduling constants of the persistent traversal kernel (tuned on the atrium, tools/gpu_ab.py).
-// ------------------------------------------------------------------------------------------------
-constexpr uint32_t kChunk = 128;   // queue entries claimed per atomic (small enough that the tail stays balanced)
-constexpr uint32_t kShards = 16;   // work cursors per launch, one 64-byte line each: a single cursor
-                                   // saturates near 90 claims/us (8 M rays / 64 per 1.2 ms = 100/us)
-constexpr uint32_t kLineWords = 16;
-constexpr uint32_t kRefillMin = 40; // refill once this many lanes are idle (r02 sweep: 32 -> 40 = +1 %)
-constexpr uint32_t kLeafVote = 20; // leave the descent loop when fewer lanes than this are descending (16..24 measure the same)
-
-// record layouts (kTraceWide's COMPACT parameter) + the two paths outside kTraceWide
-constexpr int kLayoutBinary = 0, kLayoutCompact = 1, kLayoutHot = 2, kLayoutQuad = 3, kLayoutQuadHalf = 4, kLayoutQuadLocal = 5, kLayoutOct = 6, kLayoutScalar = 7, kLayoutPacket = 8;
-constexpr uint32_t kFlagShadowDirFromStream = 1u; // any-hit: direction from ps.rayD instead of the sun sample
-constexpr uint32_t kFlagUniformTri = 8u;          // the same for the triangles of a leaf phase
-constexpr uint32_t kFlagUniformFetch = 4u;        // try the scalar-cache path for records that every descending lane shares
-constexpr uint32_t kFlagFirstBounce = 2u;         // any-hit: radiance so far is 0 and not in memory yet (kRaygen does not store it)
-constexpr uint32_t kFlagOccluderCache = 16u;      // any-hit: a new ray first visits the leaves that stopped the last rays from its cell of the scene (see kTraceWide)
-constexpr uint32_t kFlagOccluderNoTry = 32u;      // ... the launch runs behind kShadowFirstLook: its rays have had their first look, it only records what stopped them
-constexpr uint32_t kFlagNoRayCount = 64u;
-constexpr uint32_t kFlagConstOrigin = 128u;      // closest-hit, bounce 1: every ray starts at WideScene::constOrigin (a pinhole camera: kRaygen does not write the origins, the refill does not read them)
-constexpr uint32_t kFlagDenseLeafShift = 8u;       // bits 11..8: leaf phases in which a parked lane holds this many triangles or more run over dense (lane, triangle) pairs (0: never; see kTraceWide)         // the launch's rays are counted elsewhere (kShadowFirstLook counted the whole queue)
-#if defined(RF_EXP_OCC_SLOTS)
-constexpr int kOccSlots = RF_EXP_OCC_SLOTS;
-#else
-constexpr int kOccSlots = 4; // entries per cell of the occluder grid (1, 2 or 4: shadow launches of the atrium -19 / -29 / -34 %, profiles/r04_occluder)
-#endif
-static_assert(kOccSlots == 1 || kOccSlots == 2 || kOccSlots == 4, "one aligned load per cell");
+// (the flags of kShade and kShadowFirstLook, the scheduling constants of the persistent traversal kernel, the record layouts, the launch flags and kOccSlots:
+// rf_launch_constants.hpp, shared with the host-only launch policy)
 // Lane state of kTraceWide lives in ONE register, the next thing to visit: a child word of
 // rf_wide.hpp (bit 31 clear: interior record index; set: leaf descriptor) or one of two sentinels
 // (no leaf word reaches them: that would take count field 7 with big-leaf index 0x0FFFFFFE).
@@ -389,7 +357,7 @@ constexpr uint32_t kNodeDone = 0xFFFFFFFEu; // ray finished, result not yet writ
 // length word of a pixel without a leaf list (kPixelLeafLists): bit 31, and in its low bits why -- its rays take the kTraceWide launch
 constexpr uint32_t kNoPrimaryList = 0x80000000u;
 constexpr uint32_t kNoListSigns = 1u, kNoListOverflow = 2u, kNoListBigLeaf = 3u, kNoListStack = 4u; // the direction box touches zero on an axis / more leaves than the capacity / a leaf of 8 or more triangles / a walk deeper than its stack
-constexpr uint32_t kPrimaryListMaxCapacity = 64u; // (the length sits in bits 7..0 of the word, the direction signs in bits 10..8)
+// (kPrimaryListMaxCapacity: rf_launch_constants.hpp -- the length sits in bits 7..0 of the word, the direction signs in bits 10..8)
 
 
 // ---- kernel entry points (defined in rf_trace.hip / rf_shade.hip; nullptr: that instantiation is not compiled into this build)

@@ -1,5 +1,6 @@
 // rf_renderer.hip -- wavefront path tracer for MI355X (gfx950): the host driver (the kernels live in rf_trace.hip, rf_shade.hip and rf_sums.hip, what the
-// units share in rf_kernels.hpp; the scene's device layouts are built and packed by host-only code, rf_scene_pack.cpp and rf_wide_build.cpp, and uploaded here).
+// units share in rf_kernels.hpp; the scene's device layouts are built and packed by host-only code, rf_scene_pack.cpp and rf_wide_build.cpp, and uploaded here; which
+// kernel runs with which parameters is planned by host-only code too, rf_launch_policy.cpp, and enqueued here).
 //
 // The reference traces one full path per fragment-shader invocation
 // (src/pt/reference_path_tracer.wgsl:34-64,180-234).  Here the same per-path arithmetic is cut
@@ -25,6 +26,7 @@
 #include "rf_denoise.hpp"
 #include "rf_features.hpp"
 #include "rf_kernels.hpp"
+#include "rf_launch_policy.hpp"
 #include "rf_noise.hpp"
 #include "rf_robust.hpp"
 #include "rf_scene_pack.hpp"
@@ -185,15 +187,14 @@ struct Renderer::Impl
     uint32_t         maxWidth = 0, maxHeight = 0;
     uint32_t         frameCount = 0, accumulated = 0;
     uint32_t         rank = 0, worldSize = 1;
-    // a checkpoint's scene guard (checkpointBooks): the counts of BVH nodes, triangles, textures and texels the handle was created with, and the root node's box
-    uint64_t         sceneCounts[4] = {};
-    uint32_t         sceneRootBounds[6] = {};
+    // what the scene packing found (rf_scene_pack.hpp): the launch policy's facts, and a checkpoint's scene guard (checkpointBooks) -- the counts of BVH nodes,
+    // triangles, textures and texels the handle was created with, and the root node's box
+    SceneFacts       facts;
     DeviceBuffer<uint64_t> checkpointWork; // the state digest's tile words and, behind them, its tile table (checkpointScratch): grown on demand, kept
 
     std::vector<uint32_t>   tiles;
     DeviceBuffer<uint32_t>  tileIds; // the tile list of the next batch: the shard's own (configureShard) or an active list (uploadTileList), and behind the ids each tile's slot in the shard
     DeviceBuffer<uint32_t>  tileValidBefore; // prefix sum of the valid pixels of the shard's tiles (numTiles + 1): kRaygen's queue positions without an atomic (FrameParams)
-    bool                    optDenseRaygen = true;
     DeviceBuffer<float4>    ownedImage;
     float4*                 image = nullptr; // compact tile-major accumulation buffer
     uint64_t                imageBytes = 0;
@@ -266,19 +267,13 @@ struct Renderer::Impl
     DeviceBuffer<float>    deferredSample, deferredAccum;
     DeviceBuffer<uint32_t> deferredBgra;
 
-    bool counting = false, timing = false;
-    int      traversalVariant = 2; // 0 = one ray per thread over 32-B nodes (A/B baseline), 2 = persistent waves over 64-B wide nodes
+    bool timing = false;
+    LaunchOptions options; // every knob of the launch policy (rf_launch_policy.hpp): the plans are computed from these and policyInputs()
     uint32_t wideBlocks = 0;
     bool     wideBlocksForced = false; // option persistent_blocks: every persistent launch takes that grid
     uint32_t multiProcessors = 0;
     std::map<std::pair<const void*, uint32_t>, uint32_t> residentCache; // kernel, extra LDS -> workgroups the device holds at once
     uint32_t skyBlocks = 2048; // grid of the per-bounce kSky launches (grid-stride; set from the CU count)
-    bool     wideUsable = true;
-    int      queryVariant = 0; // 2: rf_renderer_intersect_rays / _occluded_rays run through kTraceWide (test hook; no per-ray counters)
-    bool     shadowNearestFirst = true; // shadow rays: nearest child first (visibility is order independent)
-    // the cached any-hit launches of bounce >= this run behind kShadowFirstLook (0: never).  From bounce 2: the coherent launch of bounce 1 costs less per ray than
-    // a pass over the queue does (atrium -4 %, Duck +14 % with it: profiles/r04_occluder/firstlook_scenes2.log)
-    uint32_t optShadowFirstLookFromBounce = 2;
     bool     occluderGridWarm = false;       // a batch has filled the occluder grid since it was allocated
     // kShadowFirstLook pays where most shadow rays are stopped by their cell's leaves; in a scene lit from everywhere it only adds a pass over the queue.  Every
     // batch reports {answered, rays} of its first looks (asynchronously: read when the copy has landed); below a quarter the next 16 batches go without.
@@ -287,58 +282,9 @@ struct Renderer::Impl
     hipEvent_t                       lookEvent = nullptr;
     bool                             lookPending = false;
     uint32_t                         firstLookHoldOff = 0;
-    uint32_t occluderHintLevels = 0;  // see leafBoxesIntoTriangles (0: the cache remembers leaves)
-    bool     leafBoxesValid = false;   // every leaf's exact box sits in its first triangle record (leafBoxesIntoTriangles)
-    uint32_t optOccluderGridLog2Cells = 22; // table size: 2^n cells of kOccSlots words
-    uint32_t optOccluderGridCells = 1024; // occluder grid: cells along the longest axis of the root box (0: no occluder cache)
     DeviceBuffer<uint32_t> occluderGrid;
-    uint32_t optOccluderCacheBounces = 64; // the any-hit launches of bounces 1..n first visit the leaves their ray's cell of the occluder grid names (kFlagOccluderCache)
-    bool     optShadowSignOrder = true; // the half-precision / local-grid shadow launches (VALU bound) visit entries in record order: a cheaper step beats the shorter walks of nearest-first there
-    uint32_t optRefillMin = kRefillMin, optLeafVote = kLeafVote, optChunk = kChunk;
-    // closest-hit launches of scenes without long leaves whose tree stays cache resident leave the descend loop later (round 6: 14 instead of 20 lanes still descending; plain atrium
-    // closest-hit -1.5 %, Duck -1.4 %; the dense-leaf instantiations +4.7 % and the out-of-cache scene +1 % with it: they keep 20 -- profiles/r06_lanes/ab_leaf_vote*.log)
-    uint32_t optLeafVoteClosest = 14;
-    // leaf phases in which a parked lane holds this many triangles or more run over dense (lane, triangle) pairs (kTraceWide; 0: never), from this bounce on
-    uint32_t optDenseLeafMin = 5, optDenseLeafFromBounce = 1; // (5: the plain atrium's leaves of up to 4 triangles keep the loop -- 3 measured +1 % there; the clutter scene gains the same with 2 .. 5)
-    uint32_t maxLeafTriangles = 0; // of the scene (upload): scenes without a leaf as long as the threshold run the instantiations WITHOUT the dense block
-    uint32_t optShadeSortFromBounce = 2, sortScale = 0;         // kShade of bounce >= this appends its tile's hits in triangle order (0: never)
-    uint32_t optChunkEarly = 256, optChunkEarlyBounces = 2;      // queue entries per cursor claim at bounces 1-2
-    uint32_t optRefillMinDeep = 12, optRefillMinDeepDense = 22, optRefillMinDeepQuad = 40, optRefillDeepFromBounce = 2; // closest-hit launches of bounce >= 2 (3 until the eager-leaves schedule: bounce 2 -2.6 % with it) refill at another count: 12 idle lanes (22 until round 6: with the
-                                                                                             // refill trip's claim logic on the scalar unit and its one-test classification, 16 ... 4 measure the same and 1.3 % under 22: profiles/r06_lanes) on the 64-byte and the
-                                                                                             // half-precision quad records (VALU bound: idle lanes cost most), 40 on the exact quad records (L1 bound: a refill is a wave-wide stall)
-    // kShade grid cap (0: one workgroup per tile of 1024 entries, the default: workgroups then append to the hit queue in
-    // roughly queue order, which keeps neighbouring pixels' rays together -- a capped, grid-striding kShade saved its empty
-    // workgroups but cost the traversal kernels 2-5 %)
-    uint32_t optShadeBlocks = 0;
-    bool     optTranscendentalsF32 = false; // option `transcendentals`: kRaygen / kSky call the f32 math library instead of the specified f64 evaluation (opt-in)
-    bool     optShadowSelfTest = true; // kShade tests every shadow ray against the triangle it starts on first (kShadeSelfShadow); needs selfShadowOk
-    bool     selfShadowOk = false;     // the tree's boxes are nested and regular, and the shading records carry their triangles' leaf boxes
-    bool     optConstPrimaryOrigin = true; // a pinhole camera's primary launch takes its one origin as a kernel argument (kFlagConstOrigin): kRaygen writes no origins
-    // Bounce 1 over per-pixel leaf lists (rf_primary_lists.hip; option primary_lists, default on): where the plan selects them (planBatch) kPixelLeafLists walks the tree once per
-    // pixel and kTraceLeafLists gives every sample the exact tests of the few leaves on its pixel's list; what the lists do not cover takes the bounce's kTraceWide launch.
-    // primary_list_capacity: entries per pixel (a longer list: no list for that pixel); primary_list_min_samples: batches with fewer samples per pixel keep the old launch
-    // (the list pass costs a few rays' worth per pixel: profiles/primary_lists/README.md)
-    bool     optPrimaryLists = true;
-    uint32_t optPrimaryListCapacity = 64, optPrimaryListMinSamples = 16;
     DeviceBuffer<uint32_t> primaryLists, primaryLengths; // [valid-pixel rank of the batch][capacity] leaf words / [rank] length word; allocated by the first batch that uses them
-    bool                   optSampleSort = true, optAccumulateRuns = true;
-    uint32_t               optCompactFromBounce = 3;       // closest-hit launches of bounce >= this use the compact-capable records (0: never)
-    uint32_t               optCompactShadowFromBounce = 2; // ... and the shadow launches of bounce >= this
-    uint32_t               optQuadFromBounce = 1, optQuadShadowFromBounce = 1; // the 128-byte quad records (two levels per fetch) from this bounce on (0: never); takes precedence over the others
-    uint32_t               optQuadExceptMask = 0, optQuadShadowExceptMask = 0; // ... except at the bounces whose bit (bounce - 1) is set here
-    uint32_t               optQuadHalfFromBounce = 0, optQuadHalfShadowFromBounce = 0; // quad launches of bounce >= this read the 64-byte half-precision quad records (0: never; set to 1 at upload when the scene suits them)
-    float                  quadHalfAreaRatio = 0.0f;
-    uint32_t               optQuadLocalFromBounce = 0, optQuadLocalShadowFromBounce = 0; // ... the 64-byte local-grid quad records (0: never; set to 1 at upload when the half-precision ones do not suit the scene)
-    // closest-hit launches of bounce >= this read the 128-byte oct records (three levels per fetch; 0: never -- the default: measured slower, see the upload)
-    uint32_t               optOctFromBounce = 0;
-    uint64_t               treeBytes = 0; // quad records + triangle records: what the traversal launches touch
-    uint32_t               optHotFromBounce = 0, optHotShadowFromBounce = 0; // the 32-byte records (all six planes carried) from this bounce on (0: never); takes precedence
-    int                    optQueryCompact = 0;            // the ray-query entry points use the compact-capable (1) / 32-byte (2) records too (tests)
-    uint32_t               optExtraLds = 0;      // experiment: dynamic LDS bytes added to the kTraceWide launches (lowers the occupancy)
-    uint32_t               optPacketBounces = 0; // bounces 1..n traced by kTracePacket (one wave = one lockstep packet) instead of kTraceWide
-    int                    optUniformFetch = 2; // scalar-cache fetch for wave-uniform steps: 0 = never (5 878 Mrays/s), 1 = records (6 039), 2 = records + leaf triangles (6 059), -1 = records at bounces 1-2 only
     DeviceBuffer<uint32_t> samplePerm;
-    uint32_t optSlotGroupShift = 0; // see FrameParams::slotGroupShift (r02 A/B on the atrium, Mrays/s: sample-major 5282; unsorted g = 6: 5416, 2: 5507, 0: 5450; with sorted samples g = 2: 5519, 1: 5589, 0: 5650)
     RenderStats hostStats;
 
     struct TimedLaunch
@@ -382,10 +328,20 @@ struct Renderer::Impl
     uint64_t pathStateBytes() const { return allocatedPaths * kBytesPerPath + sAov.count * sizeof(float4); }
     // the per-pixel leaf lists of bounce 1: capacity + 1 words per valid pixel of a batch (1080p at the default capacity of 64: 539 MB)
     uint64_t primaryListBytes() const { return (primaryLists.count + primaryLengths.count) * sizeof(uint32_t); }
-    uint64_t primaryListBytesWanted(uint64_t pixels) const { return primaryListsPossible() ? pixels * (std::min(std::max(optPrimaryListCapacity, 1u), kPrimaryListMaxCapacity) + 1ull) * sizeof(uint32_t) : 0u; }
-    // what does not depend on the batch: the option, and the gates the conservative records and kShade's own-triangle test already rest on -- boxes regular and nested all
-    // the way up, every leaf's exact box in its first triangle record
-    bool primaryListsPossible() const { return optPrimaryLists && !counting && traversalVariant != 0 && selfShadowOk && leafBoxesValid; }
+    // What the launch policy reads besides the options, as the handle stands (active: the tile list of a batch of render_adaptive)
+    PolicyInputs policyInputs(const ActiveTiles* active = nullptr) const
+    {
+        PolicyInputs in;
+        in.facts = facts;
+        const void* const present[] = {wide.nodes, wide.compact, wide.hot, wide.quad, wide.quadHalf, wide.quadLocal, wide.oct}; // by kLayoutBinary .. kLayoutOct
+        for (int layout = kLayoutBinary; layout <= kLayoutOct; ++layout) in.layouts |= present[layout] != nullptr ? 1u << layout : 0u;
+        in.rootLo = wide.rootLo, in.rootHi = wide.rootHi, in.originBound = wide.originBound;
+        in.camera = params.camera, in.numBounces = params.samplingParams.numBounces;
+        in.aovs = aovSums.on, in.moments = momentSums.on, in.buckets = bucketSums.on, in.bucketPlanes = bucketSums.planes, in.bucketSamples = bucketSums.samples;
+        in.numTiles = static_cast<uint32_t>(tiles.size()), in.validPixels = validPixels;
+        if (active) in.active = *active;
+        return in;
+    }
     // the path state holds a batch of `paths` (the AOV records included while the AOVs are on)
     bool pathStateHolds(uint64_t paths) const { return paths <= allocatedPaths && (!aovSums.on || sAov.count >= 2 * paths); }
 
@@ -439,7 +395,7 @@ struct Renderer::Impl
         size_t freeBytes = 0, totalBytes = 0;
         RF_HIP(hipMemGetInfo(&freeBytes, &totalBytes));
         // (the per-pixel leaf lists of bounce 1, where a batch would use them: what is not allocated yet comes off the budget)
-        const uint64_t listsWanted = primaryListBytesWanted(validPixels), listsHeld = primaryListBytes();
+        const uint64_t listsWanted = primaryListBytesWanted(options, policyInputs(), validPixels), listsHeld = primaryListBytes();
         const uint64_t budget = static_cast<uint64_t>(freeBytes) + pathStateBytes();
         const uint64_t reserve = listsWanted > listsHeld ? listsWanted - listsHeld : 0u;
         return (budget > reserve ? budget - reserve : 0u) / 10 * 9 / bytesPerPath();
@@ -578,75 +534,6 @@ struct Renderer::Impl
         pendingBatches.clear();
     }
 
-    // ---- The launch policy.  planBatch (once per batch) and planBounce (once per bounce) are the only places that decide which kernel runs with which parameters, and
-    // BatchCounters is the only place that knows the words of queueCounts; traceBatch and its launch members enqueue what the plans say.  The plans hold no pointer, and
-    // planning enqueues nothing and touches no device memory: rf_renderer_launch_plan reads the same plans out.
-    enum : uint32_t { kKernelScalar = 0, kKernelPacket = 1, kKernelWide = 2 };            // TraversalPlan::kernel
-    enum : uint32_t { kFromQueue = 0, kFromShadeList = 1, kFromLookList = 2 };            // BouncePlan::shadowSource
-    enum : uint32_t { kAccumulatePixels = 0, kAccumulateRuns = 1, kAccumulateTiles = 2 }; // BatchPlan::accumulateKernel
-    // One traversal launch, resolved: what actually runs.  kKernelWide: the kTraceWide instantiation named by (any-hit, counting build, nearest-first, record layout,
-    // dense leaf phase) from rf_trace.hip's table and its scheduling arguments; the other two kernels take the flags only.
-    struct TraversalPlan
-    {
-        uint32_t kernel;
-        int      layout; // which record layout the launch reads (kTraceWide's COMPACT parameter), or kLayoutScalar / kLayoutPacket
-        bool     anyHit, count, nearest, dense;
-        uint32_t refillMin, chunk, leafVote, flags, extraLds;
-    };
-    struct BatchPlan
-    {
-        uint32_t numSamples, numBounces, numTiles, pixelsPadded;
-        bool     samplePerm, denseRaygen, constOrigin;
-        bool     primaryLists;        // bounce 1's closest-hit group: kPixelLeafLists + kTraceLeafLists + the bounce's kTraceWide launch over what they hand on
-        uint32_t primaryListCapacity; // entries per pixel
-        int      primaryLayout;
-        bool     occluderGrid; // the batch's any-hit launches get the occluder grid: occluderGridEntries words, cells found by occScale / occMask
-        uint64_t occluderGridEntries;
-        float    occScale;
-        uint32_t occMask;
-        bool     firstLookReady; // a fact the batch mutates, as it stands for THIS batch (traceBatch / nextBatchFirstLookReady): the grid is warm and no hold-off runs
-        bool     runs, tileList;
-        bool     shardList; // a tile list under a tile shard: the sums are addressed through the slots behind the ids (SumAddressing::ShardList)
-        uint32_t accumulateKernel, accumulatePixels, aovPixels, momentPixels; // pixels per workgroup of the sums' launches; 0: that sum is not launched
-        uint32_t bucketPixels, buckets, bucketPhase; // the bucket sums' launch: K planes, the batch's sample k onto plane (bucketPhase + k) mod K
-    };
-    struct BouncePlan
-    {
-        TraversalPlan closest, shadow;
-        bool          shadeSorted, shadeAov;
-        uint32_t      shadeFlags, sortScale, skyFirstBounce;
-        uint32_t      itemGridCap; // kShade's and kShadowFirstLook's grid cap (0: one workgroup per 1 024 entries)
-        bool          cached, firstLook, selfShadow;
-        uint32_t      lookFlags, shadowSource; // shadowSource: whose count word and list the any-hit launch reads
-    };
-    // queueCounts by name.  Device words, one per 64-byte line (they are all hot atomics): the queue lengths [0, B] (0: raygen's queue, b: what kShade of bounce b
-    // leaves), the miss-list length per bounce, two work cursors of kShards lines per bounce for the traversal launches, the lengths of the lists kShadowFirstLook
-    // leaves to the any-hit launches per bounce, the lengths of kShade's lists of shadow rays still to trace (kShadeSelfShadow) per bounce.  b = 1 .. numBounces.
-    struct BatchCounters
-    {
-        uint32_t*                 base;
-        uint32_t                  numBounces;
-        static constexpr uint32_t kLine = kLineWords, kCursorWords = kLine * kShards;
-        uint32_t words() const { return primaryFallbackWord() + kLine; }
-        // (behind everything else: the length of the list of bounce-1 rays kTraceLeafLists hands on to the bounce's kTraceWide launch)
-        uint32_t primaryFallbackWord() const { return kLine * (2 * numBounces + 1) + kCursorWords * 2 * numBounces + kLine * numBounces + kLine * numBounces; }
-        uint32_t* primaryFallbackCount() const { return base + primaryFallbackWord(); }
-        uint32_t queueWord(uint32_t b) const { return kLine * b; }
-        uint32_t missWord(uint32_t b) const { return kLine * (numBounces + 1) + kLine * (b - 1); }
-        uint32_t cursorClosestWord(uint32_t b) const { return kLine * (2 * numBounces + 1) + kCursorWords * 2 * (b - 1); }
-        uint32_t cursorShadowWord(uint32_t b) const { return cursorClosestWord(b) + kCursorWords; }
-        uint32_t listWord(uint32_t b) const { return kLine * (2 * numBounces + 1) + kCursorWords * 2 * numBounces + kLine * (b - 1); }
-        uint32_t shadowListWord(uint32_t b) const { return listWord(b) + kLine * numBounces; }
-        // the count word an any-hit launch (or kShadowFirstLook) of bounce b reads, by BouncePlan::shadowSource
-        uint32_t shadowCountWord(uint32_t b, uint32_t source) const { return source == kFromLookList ? listWord(b) : (source == kFromShadeList ? shadowListWord(b) : queueWord(b)); }
-        uint32_t* queueCount(uint32_t b) const { return base + queueWord(b); }
-        uint32_t* missCount(uint32_t b) const { return base + missWord(b); }
-        uint32_t* cursorClosest(uint32_t b) const { return base + cursorClosestWord(b); }
-        uint32_t* cursorShadow(uint32_t b) const { return base + cursorShadowWord(b); }
-        uint32_t* listCount(uint32_t b) const { return base + listWord(b); }
-        uint32_t* shadowListCount(uint32_t b) const { return base + shadowListWord(b); }
-        uint32_t* shadowCount(uint32_t b, uint32_t source) const { return base + shadowCountWord(b, source); }
-    };
     // what a kTraceWide launch takes besides its plan: the streams, the queue with its count and cursor, the batch's geometry
     struct WideArgs
     {
@@ -680,170 +567,6 @@ struct Renderer::Impl
         if (a.blocksWanted != 0u && !wideBlocksForced && !t.count) grid = dim3(std::min(a.blocksWanted, residentBlocks(k, t.extraLds)));
         hipLaunchKernelGGL(k, grid, dim3(kBlock), t.extraLds, stream, scene, w, sky, sunBasis, a.ps, a.queue, a.count, a.cursor, counters.ptr, t.refillMin, t.leafVote, t.chunk, a.tMax, t.flags);
     }
-    // the layout a test asks for, if this scene has it (else the binary records)
-    int layoutIfPresent(int want) const
-    {
-        switch (want)
-        {
-        case kLayoutOct: return wide.oct != nullptr ? want : kLayoutBinary;
-        case kLayoutQuadLocal: return wide.quadLocal != nullptr ? want : kLayoutBinary;
-        case kLayoutQuadHalf: return wide.quadHalf != nullptr ? want : kLayoutBinary;
-        case kLayoutQuad: return wide.quad != nullptr ? want : kLayoutBinary;
-        case kLayoutHot: return wide.hot != nullptr ? want : kLayoutBinary;
-        case kLayoutCompact: return wide.compact != nullptr ? want : kLayoutBinary;
-        default: return kLayoutBinary;
-        }
-    }
-    // does a launch with these flags want the dense leaf phase?  (the scene has a leaf as long as the threshold the flags carry: the instantiations that
-    // contain the block -- the layouts the renderer picks by itself -- are used only then: its mere presence costs a launch 2.5 %, profiles/r05_leaf)
-    bool denseWanted(uint32_t flags) const
-    {
-        const uint32_t threshold = (flags >> kFlagDenseLeafShift) & 15u;
-        return threshold != 0u && maxLeafTriangles >= threshold;
-    }
-    // the conservative layouts (VALU bound): the half-precision and the local-grid quad records
-    static bool conservativeLayout(int layout) { return layout == kLayoutQuadLocal || layout == kLayoutQuadHalf; }
-    // the layouts whose any-hit launch can work through a list of queue positions (the kTraceWide instantiations with the occluder-cache code: quad / half / local-grid records)
-    static bool worksThroughList(int layout) { return layout == kLayoutQuad || layout == kLayoutQuadHalf || layout == kLayoutQuadLocal; }
-    // The traversal launch of a layout, resolved (render path and ray queries alike).  nearest (any-hit): entries ordered by slab distance (NEAREST_FIRST); else record
-    // order (the conservative layouts' default: optShadowSignOrder) -- the compact and hot records always nearest-first.  A combination rf_trace.hip's table does not
-    // hold falls back to the same one without the dense leaf phase (options can ask for it on a layout it is not built for): the plan then says dense = false.
-    TraversalPlan resolveTraversal(bool anyHit, int layout, bool count, bool nearest, uint32_t flags, uint32_t refillMin, uint32_t chunk, uint32_t leafVote, uint32_t extraLds) const
-    {
-        TraversalPlan t{};
-        t.kernel = layout == kLayoutScalar ? kKernelScalar : (layout == kLayoutPacket ? kKernelPacket : kKernelWide);
-        t.layout = layout, t.anyHit = anyHit, t.count = count, t.flags = flags;
-        if (t.kernel != kKernelWide) return t;
-        if (count) t.layout = kLayoutBinary, t.nearest = anyHit && nearest;
-        else if (!anyHit) t.layout = layout <= kLayoutOct ? layout : kLayoutBinary;
-        else
-        {
-            t.layout = (layout <= kLayoutQuadLocal) ? layout : kLayoutBinary;
-            t.nearest = (t.layout == kLayoutCompact || t.layout == kLayoutHot) ? true : nearest;
-        }
-        t.dense = !count && denseWanted(flags) && traceWideKernel(anyHit, false, t.nearest, t.layout, true) != nullptr;
-        t.refillMin = refillMin, t.chunk = chunk, t.leafVote = leafVote ? leafVote : optLeafVote, t.extraLds = extraLds; // (leafVote 0: optLeafVote)
-        return t;
-    }
-    // The layout the renderer picks BY ITSELF for the closest-hit / any-hit launch of a bounce (the per-scene defaults set at upload + the options; reported by
-    // rf_renderer_layout_info and used by traceBatch): kLayoutScalar = the one-ray-per-thread kernels (trees the packed tests cannot serve), kLayoutPacket = kTracePacket
-    int closestLayoutFor(uint32_t bounce) const
-    {
-        if (traversalVariant == 0) return kLayoutScalar;
-        if (counting) return kLayoutBinary;
-#if defined(RF_EXP_LEGACY_LAYOUTS)
-        if (bounce <= optPacketBounces) return kLayoutPacket;
-#endif
-        const bool  quadNow = wide.quad != nullptr && optQuadFromBounce != 0u && bounce >= optQuadFromBounce && !((optQuadExceptMask >> std::min(bounce - 1u, 31u)) & 1u);
-        // A camera that stands outside the conservative records' origin bound (4 R + 1 for a root box within +-R: a turntable shot from far away) would
-        // send EVERY primary ray to the scalar traversal (2 x the launch, tools/gpu_far_camera.py): that launch reads the exact quad records, which have
-        // no such bound.  Later bounces start on surfaces, inside the bound.
-        const float camReach = std::max({std::fabs(params.camera.origin.x), std::fabs(params.camera.origin.y), std::fabs(params.camera.origin.z)}) + (std::fabs(params.camera.lensRadius) * 2.0f);
-        const bool  primaryOutside = bounce == 1u && !(camReach <= wide.originBound);
-        if (quadNow && !primaryOutside)
-        {
-            if (wide.oct != nullptr && optOctFromBounce != 0u && bounce >= optOctFromBounce) return kLayoutOct;
-            if (wide.quadHalf != nullptr && optQuadHalfFromBounce != 0u && bounce >= optQuadHalfFromBounce) return kLayoutQuadHalf;
-            if (wide.quadLocal != nullptr && optQuadLocalFromBounce != 0u && bounce >= optQuadLocalFromBounce) return kLayoutQuadLocal;
-        }
-        if (quadNow) return kLayoutQuad;
-        if (wide.hot != nullptr && optHotFromBounce != 0u && bounce >= optHotFromBounce) return kLayoutHot;
-        if (wide.compact != nullptr && optCompactFromBounce != 0u && bounce >= optCompactFromBounce) return kLayoutCompact;
-        return kLayoutBinary;
-    }
-    int shadowLayoutFor(uint32_t bounce) const
-    {
-        if (traversalVariant == 0) return kLayoutScalar;
-#if defined(RF_EXP_LEGACY_LAYOUTS)
-        if (!counting && bounce <= optPacketBounces) return kLayoutPacket;
-#endif
-        if (counting || !shadowNearestFirst) return kLayoutBinary;
-        const bool quadShadowNow = optQuadShadowFromBounce != 0u && bounce >= optQuadShadowFromBounce && !((optQuadShadowExceptMask >> std::min(bounce - 1u, 31u)) & 1u);
-        if (quadShadowNow)
-        {
-            if (wide.quadLocal != nullptr && optQuadLocalShadowFromBounce != 0u && bounce >= optQuadLocalShadowFromBounce) return kLayoutQuadLocal;
-            if (wide.quadHalf != nullptr && optQuadHalfShadowFromBounce != 0u && bounce >= optQuadHalfShadowFromBounce) return kLayoutQuadHalf;
-            if (wide.quad != nullptr) return kLayoutQuad;
-        }
-        if (wide.hot != nullptr && optHotShadowFromBounce != 0u && bounce >= optHotShadowFromBounce) return kLayoutHot;
-        if (wide.compact != nullptr && optCompactShadowFromBounce != 0u && bounce >= optCompactShadowFromBounce) return kLayoutCompact;
-        return kLayoutBinary;
-    }
-    // does the any-hit launch of this bounce start at the occluder cache's entries? (kTraceWide, kFlagOccluderCache)
-    bool cachedShadowFor(uint32_t bounce) const
-    {
-        const int layout = shadowLayoutFor(bounce);
-        const bool exactQuad = layout == kLayoutQuad && leafBoxesValid; // (its leaf visits then apply the box in the leaf's triangle record)
-        return layout != kLayoutScalar && layout != kLayoutPacket && !counting && shadowNearestFirst && (conservativeLayout(layout) || exactQuad) && bounce <= optOccluderCacheBounces &&
-               optOccluderGridCells != 0u;
-    }
-
-    // The tile list a batch of rf_renderer_render_adaptive traces: while one is in use, tileIds / tileValidBefore hold IT (uploadTileList) and not the shard's list
-    struct ActiveTiles
-    {
-        uint32_t numTiles;
-        uint64_t validPixels;
-        bool     shardSlots; // the sums are addressed through the slots behind the ids (rf_comm_render_adaptive: the handle's sums are compact over its shard)
-    };
-    // The once-per-batch decisions, for a batch of numSamples samples of the shard's tiles (or of the `active` list of render_adaptive)
-    BatchPlan planBatch(uint32_t numSamples, const ActiveTiles* active) const
-    {
-        BatchPlan b{};
-        const uint64_t validPixels = active ? active->validPixels : this->validPixels;
-        b.numSamples = numSamples;
-        b.numBounces = params.samplingParams.numBounces;
-        b.numTiles = active ? active->numTiles : static_cast<uint32_t>(tiles.size());
-        b.pixelsPadded = b.numTiles * 1024u;
-        // (kSamplePermutation ranks by counting, O(S^2): fine for the few hundred samples a batch of a real frame holds,
-        // skipped for the huge sample counts a tiny frame can put into one batch)
-        b.samplePerm = optSampleSort && numSamples > 1 && numSamples <= 8192 && optSlotGroupShift != kSlotSampleMajor;
-        // Pinhole camera (lensRadius == 0): kRaygen's origin = camera.origin + (0 * right + 0 * up) is camera.origin itself for every path, bit for bit, as long as no
-        // component of camera.origin is a zero (whose sign the +-0 addend could flip) and right / up are finite (0 * inf = NaN).  The primary launch then takes it as a kernel
-        // argument and kRaygen writes 28 instead of 40 bytes per path.  Only the wide traversal kernels know the flag (the scalar kernels read ps.rayO).
-        const auto finite3 = [](Vec3 v) { return std::isfinite(v.x) && std::isfinite(v.y) && std::isfinite(v.z); };
-        const Camera& camNow = params.camera;
-        b.primaryLayout = closestLayoutFor(1);
-        b.constOrigin = optConstPrimaryOrigin && camNow.lensRadius == 0.0f && camNow.origin.x != 0.0f && camNow.origin.y != 0.0f && camNow.origin.z != 0.0f &&
-                        finite3(camNow.origin) && finite3(camNow.right) && finite3(camNow.up) && b.primaryLayout != kLayoutScalar && b.primaryLayout != kLayoutPacket;
-        // (kRaygen computes its queue positions instead of appending with one atomic per 1 024 slots, where the slot order allows it: FrameParams::tileValidBefore)
-        b.denseRaygen = optDenseRaygen && (optSlotGroupShift == 0u || optSlotGroupShift == kSlotSampleMajor) && static_cast<uint64_t>(validPixels) * numSamples <= 0xFFFFFFFFull;
-        // Bounce 1 over per-pixel leaf lists: one origin for the whole batch (constOrigin: a pinhole camera, primary launch on kTraceWide), the scene's gates
-        // (primaryListsPossible), a queue in which a pixel's samples are contiguous by the pixel's rank (dense kRaygen, pixel-major slots), at least one bounce, and enough
-        // samples per pixel for the once-per-pixel walk to pay.  A thin-lens camera, a counting build and small batches keep the kTraceWide launch alone.
-        b.primaryListCapacity = std::min(std::max(optPrimaryListCapacity, 1u), kPrimaryListMaxCapacity);
-        b.primaryLists = primaryListsPossible() && b.constOrigin && b.denseRaygen && optSlotGroupShift == 0u && b.numBounces != 0u && numSamples >= std::max(optPrimaryListMinSamples, 1u);
-        b.occluderGrid = optOccluderCacheBounces != 0u && optOccluderGridCells != 0u;
-        if (b.occluderGrid)
-        {
-            b.occluderGridEntries = (uint64_t{1} << optOccluderGridLog2Cells) * kOccSlots;
-            const float extent = std::max({wide.rootHi.x - wide.rootLo.x, wide.rootHi.y - wide.rootLo.y, wide.rootHi.z - wide.rootLo.z, 1e-20f});
-            b.occScale = static_cast<float>(optOccluderGridCells) / extent;
-            b.occMask = static_cast<uint32_t>(b.occluderGridEntries / kOccSlots - 1);
-        }
-        // The sums in sample order.  Where the slot order is pixel-major and the step long enough, the LDS-staged "runs" kernels (a 64-lane workgroup per
-        // `pixelsPerGroup` pixels); else one thread per pixel
-        b.runs = optSlotGroupShift == 0u && numSamples > 4u && optAccumulateRuns;
-        b.tileList = active != nullptr;
-        b.shardList = b.tileList && active->shardSlots;
-        const uint32_t perThread = static_cast<uint32_t>(kBlock);
-        if (b.tileList) b.accumulateKernel = kAccumulateTiles, b.accumulatePixels = b.runs ? kMomentPixels : perThread;
-        else if (b.runs && numSamples <= kAccMaxSamples)
-        {
-            // (pixels per workgroup by the LDS their runs take: <= ~8 KB per workgroup keeps twenty of them resident per CU)
-            b.accumulateKernel = kAccumulateRuns, b.accumulatePixels = numSamples > 640u ? 1u : (numSamples > 160u ? 2u : kAccPixels);
-        }
-        else b.accumulateKernel = kAccumulatePixels, b.accumulatePixels = perThread;
-        // the first-hit AOV sums (no bounce, no primary hit: the records were not written): a launch of their own, under a tile list the tile-list AOV kernel; the
-        // radiance second moments: a launch of their own unless the tile-list kernel adds them with the image
-        b.aovPixels = (aovSums.on && b.numBounces != 0u) ? (b.runs ? kAovPixels : perThread) : 0u;
-        b.momentPixels = (!b.tileList && momentSums.on) ? (b.runs ? kMomentPixels : perThread) : 0u;
-        // the bucket sums (under a tile list -- kBucketsTileCounts, checkAdaptive -- their tile-list kernels, under a shard's -- kBucketsShardTileCounts -- their
-        // slot-list kernels: every active tile holds bucketSums.samples samples, so one phase serves the list): the batch's first sample has ordinal bucketSums.samples
-        b.bucketPixels = bucketSums.on ? (b.runs ? kBucketPixels : perThread) : 0u;
-        b.buckets = bucketSums.on ? bucketSums.planes : 0u;
-        b.bucketPhase = bucketSums.on ? bucketSums.samples % bucketSums.planes : 0u;
-        return b;
-    }
     // Is a cached any-hit launch of the handle's NEXT batch free to run behind kShadowFirstLook, as far as the books a batch keeps go?  traceBatch's own bookkeeping,
     // foreseen without touching it (rf_renderer_launch_plan): a grid of another size starts cold, a report that has landed may start a hold-off, a running one counts down.
     bool nextBatchFirstLookReady(const BatchPlan& b) const
@@ -852,52 +575,6 @@ struct Renderer::Impl
         if (lookPending && hipEventQuery(lookEvent) == hipSuccess) return !(lookBatchHost[1] != 0ull && lookBatchHost[0] * 4ull < lookBatchHost[1]) && firstLookHoldOff == 0u;
         return firstLookHoldOff <= 1u;
     }
-    // Everything the launches of one bounce need
-    BouncePlan planBounce(uint32_t bounce, const BatchPlan& batch) const
-    {
-        BouncePlan p{};
-        const uint32_t uniformFlag = ((optUniformFetch < 0 ? bounce <= 2 : optUniformFetch > 0) ? kFlagUniformFetch : 0u) | (optUniformFetch >= 2 ? kFlagUniformTri : 0u) |
-                                     (bounce >= optDenseLeafFromBounce ? (std::min(optDenseLeafMin, 15u) << kFlagDenseLeafShift) : 0u);
-        // incoherent closest-hit launches refill earlier: their rays differ most in length, so lanes go idle sooner (per-bounce
-        // sweep, profiles/r02_final/bounce_sweep*.log: bounces 3-8 -4 % at 20-24 idle lanes, bounces 1-2 and the shadow launches +6 .. +10 %)
-        // ... and the coherent launches of the first bounces, whose rays are short and alike, claim larger chunks (one cursor atomic = one
-        // wave-wide stall: bounce 1 -4 % at 256 entries, the deep bounces +0.5 %)
-        const uint32_t chunkNow = bounce <= optChunkEarlyBounces ? optChunkEarly : optChunk;
-        const int      layoutClosest = closestLayoutFor(bounce);
-        // (scenes with long leaves -- the DENSE_LEAVES instantiations -- keep 22: a phase over dense (lane, triangle) pairs wants many parked lanes; clutter atrium +2.4 % at 12: profiles/r06_lanes)
-        const uint32_t refillClosest = bounce >= optRefillDeepFromBounce ? (layoutClosest == kLayoutQuad ? optRefillMinDeepQuad : (denseWanted(uniformFlag) ? optRefillMinDeepDense : optRefillMinDeep)) : optRefillMin;
-        // (kInfinityCacheBytes: the scene's records + triangles against the 256-MB Infinity Cache, as the layout selector's own test)
-        const uint32_t leafVoteClosest = (!counting && !denseWanted(uniformFlag) && treeBytes <= (192ull << 20)) ? optLeafVoteClosest : 0u;
-        const bool     wideClosest = layoutClosest != kLayoutScalar && layoutClosest != kLayoutPacket; // (the other two kernels take no flags)
-        p.closest = resolveTraversal(false, layoutClosest, counting, false, wideClosest ? (uniformFlag | (bounce == 1 && batch.constOrigin ? kFlagConstOrigin : 0u)) : 0u,
-                                     counting ? optRefillMin : refillClosest, chunkNow, leafVoteClosest, counting ? 0u : optExtraLds);
-        // kShade's own-triangle test of the shadow rays (kShadeSelfShadow): wherever this bounce's any-hit launch is one that can work through a list of queue positions
-        // and nothing has to be counted node by node
-        const int layoutShadow = shadowLayoutFor(bounce);
-        // (bounce <= 64: kBounceTotals keeps one mask bit per bounce -- as for firstLook below; deeper bounces trace every shadow ray and count them in the launch: ADVICE r5)
-        p.selfShadow = optShadowSelfTest && selfShadowOk && !counting && bounce <= 64u && worksThroughList(layoutShadow);
-        // (the first-hit AOVs are written by the unsorted bounce-1 kernel, whatever shade_sort_from_bounce says: the sort is a scheduling choice)
-        p.shadeAov = aovSums.on && bounce == 1;
-        p.shadeSorted = !p.shadeAov && optShadeSortFromBounce != 0u && bounce >= optShadeSortFromBounce;
-        p.shadeFlags = (bounce == batch.numBounces ? kShadeLastBounce : 0u) | (bounce == 1 ? kShadeFirstBounce : 0u) | (p.selfShadow ? kShadeSelfShadow : 0u);
-        p.sortScale = p.shadeSorted ? sortScale : 0u;
-        p.skyFirstBounce = bounce == 1 ? 1u : 0u;
-        p.itemGridCap = optShadeBlocks;
-        // occluder cache (kTraceWide, kFlagOccluderCache): the conservative-record any-hit launches of bounces 1..optOccluderCacheBounces; their rays are
-        // short (a third of the steps), so the deep launches refill earlier
-        p.cached = cachedShadowFor(bounce);
-        // ... behind kShadowFirstLook (see there) from the second batch on: the first batch of a renderer fills the grid (the traversal kernel's own first look serves)
-        p.firstLook = p.cached && occluderHintLevels == 0u && optShadowFirstLookFromBounce != 0u && bounce >= optShadowFirstLookFromBounce && bounce <= 64u && batch.firstLookReady;
-        p.shadowSource = p.firstLook ? kFromLookList : (p.selfShadow ? kFromShadeList : kFromQueue);
-        p.lookFlags = p.firstLook ? ((bounce == 1 ? kLookFirstBounce : 0u) | (p.selfShadow ? kLookNoRayCount : 0u)) : 0u;
-        const uint32_t shadowFlags = (bounce == 1 ? kFlagFirstBounce : 0u) | uniformFlag | (p.cached ? kFlagOccluderCache : 0u) | (p.firstLook ? (kFlagOccluderNoTry | kFlagNoRayCount) : 0u) | (p.selfShadow ? kFlagNoRayCount : 0u);
-        // the conservative layouts (VALU bound) visit a record's entries in record order unless asked otherwise; the exact and binary records nearest-first
-        const bool nearest = shadowNearestFirst && !(conservativeLayout(layoutShadow) && optShadowSignOrder);
-        // (the one-ray-per-thread kernel takes "first bounce" alone, the packet kernel that bit of the flag word)
-        const uint32_t flagsRun = layoutShadow == kLayoutScalar ? (bounce == 1 ? 1u : 0u) : (layoutShadow == kLayoutPacket ? (shadowFlags & kFlagFirstBounce) : shadowFlags);
-        p.shadow = resolveTraversal(true, layoutShadow, counting, nearest, flagsRun, optRefillMin, chunkNow, 0u, counting ? 0u : optExtraLds);
-        return p;
-    }
 
     // Test hook (option query_variant = 2): arbitrary rays through the render path's persistent
     // traversal kernel.  closest: out0 = hit stream {tri, u, v, t}, out1 = rayO stream (offset hit
@@ -905,7 +582,9 @@ struct Renderer::Impl
     void queryWide(const float* rays6, uint64_t n, float tMax, bool shadow, std::vector<float4>& out0, std::vector<float4>& out1)
     {
         if (n > 0xFFFFFFFFull) throw std::runtime_error("too many rays");
-        const uint32_t denseFlag = std::min(optDenseLeafMin, 15u) << kFlagDenseLeafShift; // (the dense leaf phase, as in the render path)
+        const LaunchOptions& opt = options;
+        const PolicyInputs   in = policyInputs();
+        const uint32_t denseFlag = std::min(opt.optDenseLeafMin, 15u) << kFlagDenseLeafShift; // (the dense leaf phase, as in the render path)
         if (!ensurePathState(n)) throw std::runtime_error("out of device memory for the ray batch");
         std::vector<P3>       o(n), d(n);
         std::vector<uint32_t> ids(n);
@@ -937,8 +616,8 @@ struct Renderer::Impl
             RF_HIP(hipMemsetAsync(sRad.ptr, 0, n * sizeof(float4), stream));
             RF_HIP(hipStreamSynchronize(stream)); // `ones` leaves scope before the launches are waited for
             // (the ray-query entry points take the layout the test asks for -- query_compact -- where the scene has it; the oct records serve closest-hit rays only)
-            const int layout = layoutIfPresent((optQueryCompact == kLayoutOct || (!shadowNearestFirst && optQueryCompact < kLayoutQuad)) ? kLayoutBinary : optQueryCompact);
-            launchWide(resolveTraversal(true, layout, false, shadowNearestFirst, kFlagShadowDirFromStream | denseFlag, optRefillMin, optChunk, 0u, 0u), wide, wa);
+            const int layout = layoutIfPresent(in, (opt.optQueryCompact == kLayoutOct || (!opt.shadowNearestFirst && opt.optQueryCompact < kLayoutQuad)) ? kLayoutBinary : opt.optQueryCompact);
+            launchWide(resolveTraversal(opt, in, true, layout, false, opt.shadowNearestFirst, kFlagShadowDirFromStream | denseFlag, opt.optRefillMin, opt.optChunk, 0u, 0u), wide, wa);
         }
         else
         {
@@ -965,7 +644,7 @@ struct Renderer::Impl
                 RF_HIP(hipEventCreate(&e1));
                 RF_HIP(hipEventRecord(e0, stream));
             }
-            launchWide(resolveTraversal(false, layoutIfPresent(optQueryCompact), false, false, denseFlag, optRefillMin, optChunk, 0u, 0u), wq, wa);
+            launchWide(resolveTraversal(opt, in, false, layoutIfPresent(in, opt.optQueryCompact), false, false, denseFlag, opt.optRefillMin, opt.optChunk, 0u, 0u), wq, wa);
             if (timed) RF_HIP(hipEventRecord(e1, stream));
             hipLaunchKernelGGL(hitPointsKernel(), dim3((count + 255) / 256), dim3(256), 0, stream, scene, sHit.ptr, sRayO.ptr, count);
             if (timed)
@@ -1143,7 +822,7 @@ struct Renderer::Impl
         // the paths that left the scene at this bounce, while its direction / throughput arrays are intact
         // (its slot comes with the miss list: kSky reads nothing of the bounce's queue -- round 5: reading the slot through the queue position was a third
         // dependent gather, and kShade + kSky went from 19.7 to 15.8 ms per 64 spp without it)
-        hipLaunchKernelGGL(skyKernel(optTranscendentalsF32), dim3(std::min(io.blocks, skyBlocks)), dim3(kBlock), 0, stream, sky, io.ps, missSlots.ptr, missQueue.ptr, missCount, p.skyFirstBounce);
+        hipLaunchKernelGGL(skyKernel(options.optTranscendentalsF32), dim3(std::min(io.blocks, skyBlocks)), dim3(kBlock), 0, stream, sky, io.ps, missSlots.ptr, missQueue.ptr, missCount, p.skyFirstBounce);
     }
     void enqueueShadow(const BouncePlan& p, const BounceIo& io)
     {
@@ -1225,7 +904,8 @@ struct Renderer::Impl
     void traceBatch(uint32_t firstFrame, uint32_t numSamples, const ActiveTiles* active = nullptr)
     {
         const uint64_t validPixels = active ? active->validPixels : this->validPixels;
-        BatchPlan      batch = planBatch(numSamples, active);
+        const PolicyInputs in = policyInputs(active);
+        BatchPlan      batch = planBatch(options, in, numSamples);
         FrameParams    fp{};
         fp.width = params.width;
         fp.height = params.height;
@@ -1236,7 +916,7 @@ struct Renderer::Impl
         fp.numSamples = numSamples;
         fp.numTiles = batch.numTiles;
         fp.pixelsPadded = batch.pixelsPadded;
-        fp.slotGroupShift = optSlotGroupShift;
+        fp.slotGroupShift = options.optSlotGroupShift;
         fp.samplePerm = fp.sampleInvPerm = nullptr;
         if (batch.samplePerm)
         {
@@ -1326,11 +1006,11 @@ struct Renderer::Impl
             hipLaunchKernelGGL(samplePermutationKernel(), dim3((numSamples + 255) / 256), dim3(256), 0, stream, firstFrame, fp.samplesPerPixel, numSamples,
                                const_cast<uint32_t*>(fp.samplePerm), const_cast<uint32_t*>(fp.sampleInvPerm));
         launchTimed(0, [&] {
-            hipLaunchKernelGGL(raygenKernel(optTranscendentalsF32), dim3(itemBlocks), dim3(kBlock), 0, stream, fp, scene, tileIds.ptr, io.ps, io.in, words.queueCount(0), counters.ptr);
+            hipLaunchKernelGGL(raygenKernel(options.optTranscendentalsF32), dim3(itemBlocks), dim3(kBlock), 0, stream, fp, scene, tileIds.ptr, io.ps, io.in, words.queueCount(0), counters.ptr);
         });
         for (io.bounce = 1; io.bounce <= numBounces; ++io.bounce)
         {
-            const BouncePlan plan = planBounce(io.bounce, batch);
+            const BouncePlan plan = planBounce(options, in, io.bounce, batch);
             if (plan.selfShadow) selfMask |= 1ull << (io.bounce - 1);
             if (plan.firstLook) lookMask |= 1ull << (io.bounce - 1);
             // (the list launches run inside the timing group of the bounce's closest-hit launch: ms_closest, launches_closest and the per-bounce figures keep their meaning)
@@ -1426,22 +1106,8 @@ Renderer::Renderer(const RendererDescriptor& desc, const SceneView& sceneView) :
         m.scene.blueNoise = m.blueNoise.ptr;
         m.scene.albedoLut = up(m.albedoLut, packed.albedoLut);
     }
-    {
-        const SceneFacts& f = packed.facts;
-        std::memcpy(m.sceneCounts, f.sceneCounts, sizeof m.sceneCounts);
-        std::memcpy(m.sceneRootBounds, f.sceneRootBounds, sizeof m.sceneRootBounds);
-        m.sortScale = f.sortScale;
-        m.wideUsable = f.wideUsable;
-        m.leafBoxesValid = f.leafBoxesValid;
-        m.selfShadowOk = f.selfShadowOk;
-        m.maxLeafTriangles = f.maxLeafTriangles;
-        m.occluderHintLevels = f.occluderHintLevels;
-        m.treeBytes = f.treeBytes;
-        m.quadHalfAreaRatio = f.quadHalfAreaRatio;
-        m.optQuadHalfFromBounce = f.quadHalfFromBounce, m.optQuadHalfShadowFromBounce = f.quadHalfShadowFromBounce;
-        m.optQuadLocalFromBounce = f.quadLocalFromBounce, m.optQuadLocalShadowFromBounce = f.quadLocalShadowFromBounce;
-        m.optOctFromBounce = f.octFromBounce;
-    }
+    m.facts = packed.facts;
+    m.options.applySceneDefaults(m.facts);
 
     DeviceCounters zero{};
     m.counters.upload(&zero, 1);
@@ -1457,12 +1123,7 @@ Renderer::Renderer(const RendererDescriptor& desc, const SceneView& sceneView) :
         m.wideBlocks = static_cast<uint32_t>(std::max(perCu, 1)) * static_cast<uint32_t>(prop.multiProcessorCount);
         m.multiProcessors = static_cast<uint32_t>(prop.multiProcessorCount);
         m.skyBlocks = 8u * static_cast<uint32_t>(prop.multiProcessorCount);
-        if (const char* v = std::getenv("RF_TRAVERSAL_VARIANT")) m.traversalVariant = std::atoi(v);
-        if (const char* v = std::getenv("RF_PACKET_BOUNCES")) m.optPacketBounces = static_cast<uint32_t>(std::max(std::atoi(v), 0)); // experiments: whole test suite through kTracePacket
-        // soak runs (tools/gpu_fuzz.py): the leaf lists of bounce 1 for batches of any depth, at a given capacity -- what the options primary_list_min_samples / primary_list_capacity set per handle
-        if (const char* v = std::getenv("RF_PRIMARY_LIST_MIN_SAMPLES")) m.optPrimaryListMinSamples = static_cast<uint32_t>(std::clamp(std::atoi(v), 1, 1 << 30));
-        if (const char* v = std::getenv("RF_PRIMARY_LIST_CAPACITY")) m.optPrimaryListCapacity = static_cast<uint32_t>(std::clamp(std::atoi(v), 1, static_cast<int>(kPrimaryListMaxCapacity)));
-        if (!m.wideUsable) m.traversalVariant = 0;
+        m.options.applyEnvironment(m.facts.wideUsable);
     }
 
     m.maxWidth = desc.maxWidth ? desc.maxWidth : desc.renderParams.width;
@@ -2007,7 +1668,7 @@ AdaptiveResult Renderer::renderAdaptiveFrom(const AdaptiveParameters& p, uint32_
             try { m.uploadTileList(m.tiles, nullptr); } catch (...) {}
         }
     } restore{m};
-    Impl::ActiveTiles list{numTiles, m.validPixels, shardSlots};
+    ActiveTiles list{numTiles, m.validPixels, shardSlots};
     bool              listStale = active.size() != numTiles;
     const auto        idsOf = [&](const std::vector<uint32_t>& slots) {
         std::vector<uint32_t> ids;
@@ -2022,7 +1683,7 @@ AdaptiveResult Renderer::renderAdaptiveFrom(const AdaptiveParameters& p, uint32_
         {
             RF_HIP(hipStreamSynchronize(m.stream));
             restore.armed = true;
-            list = Impl::ActiveTiles{static_cast<uint32_t>(active.size()), m.uploadTileList(activeIds, &active), shardSlots};
+            list = ActiveTiles{static_cast<uint32_t>(active.size()), m.uploadTileList(activeIds, &active), shardSlots};
             listStale = false;
         }
         m.clearStaleSums(static_cast<uint64_t>(numTiles) * 1024);
@@ -2199,8 +1860,8 @@ Renderer::CheckpointBooks Renderer::checkpointBooks(bool prepare)
     const float sky[6] = {m.params.sky.turbidity, m.params.sky.albedo[0], m.params.sky.albedo[1], m.params.sky.albedo[2], m.params.sky.sunZenithDegrees, m.params.sky.sunAzimuthDegrees};
     std::memcpy(b.sky, sky, sizeof sky);
     b.numBounces = m.params.samplingParams.numBounces, b.samplesPerPixel = m.params.samplingParams.numSamplesPerPixel;
-    std::memcpy(b.sceneCounts, m.sceneCounts, sizeof b.sceneCounts);
-    std::memcpy(b.rootBounds, m.sceneRootBounds, sizeof b.rootBounds);
+    std::memcpy(b.sceneCounts, m.facts.sceneCounts, sizeof b.sceneCounts);
+    std::memcpy(b.rootBounds, m.facts.sceneRootBounds, sizeof b.rootBounds);
     return b;
 }
 
@@ -2238,23 +1899,7 @@ void Renderer::clearAccumulationIfStale()
 
 void Renderer::layoutInfo(uint32_t (&layouts)[48], uint32_t (&misc)[4], float& quadHalfAreaRatio, uint64_t& treeBytes) const
 {
-    const Impl&           m = *mImpl;
-    const Impl::BatchPlan batch = m.planBatch(1u, nullptr);
-    for (uint32_t b = 1; b <= 16; ++b)
-    {
-        const Impl::BouncePlan p = m.planBounce(b, batch);
-        layouts[b - 1] = static_cast<uint32_t>(p.closest.layout);
-        layouts[16 + b - 1] = static_cast<uint32_t>(p.shadow.layout);
-        layouts[32 + b - 1] = p.cached ? 1u : 0u;
-    }
-    misc[0] = m.occluderHintLevels, misc[1] = m.optShadowFirstLookFromBounce, misc[2] = m.optDenseLeafMin;
-#if defined(RF_EXP_LEGACY_LAYOUTS)
-    misc[3] = 1u;
-#else
-    misc[3] = 0u;
-#endif
-    quadHalfAreaRatio = m.quadHalfAreaRatio;
-    treeBytes = m.treeBytes;
+    writeLayoutInfo(mImpl->options, mImpl->policyInputs(), layouts, misc, quadHalfAreaRatio, treeBytes);
 }
 
 void Renderer::launchPlan(uint32_t bounce, uint32_t numSamples, rf_launch_plan& out) const
@@ -2262,31 +1907,10 @@ void Renderer::launchPlan(uint32_t bounce, uint32_t numSamples, rf_launch_plan& 
     const Impl& m = *mImpl;
     if (bounce == 0u || bounce > m.params.samplingParams.numBounces || numSamples == 0u) throw std::invalid_argument("launch plan: bounce must be 1 .. the bounce count, num_samples >= 1");
     (void)hipSetDevice(m.device);
-    Impl::BatchPlan batch = m.planBatch(numSamples, nullptr);
+    const PolicyInputs in = m.policyInputs();
+    BatchPlan          batch = planBatch(m.options, in, numSamples);
     batch.firstLookReady = m.nextBatchFirstLookReady(batch);
-    const Impl::BouncePlan    p = m.planBounce(bounce, batch);
-    const Impl::BatchCounters words{nullptr, batch.numBounces};
-    static_assert(sizeof(rf_launch_plan) == 52 * sizeof(uint32_t) && offsetof(rf_launch_plan, closest_extra_lds) - offsetof(rf_launch_plan, closest_kernel) == 9 * sizeof(uint32_t) &&
-                  offsetof(rf_launch_plan, shadow_extra_lds) - offsetof(rf_launch_plan, shadow_kernel) == 9 * sizeof(uint32_t));
-    out = rf_launch_plan{};
-    out.num_samples = batch.numSamples, out.num_bounces = batch.numBounces;
-    out.sample_perm = batch.samplePerm, out.dense_raygen = batch.denseRaygen, out.const_origin = batch.constOrigin, out.primary_layout = static_cast<uint32_t>(batch.primaryLayout);
-    out.occluder_grid = batch.occluderGrid, out.occluder_mask = batch.occMask;
-    std::memcpy(&out.occluder_scale_bits, &batch.occScale, sizeof(uint32_t));
-    out.runs = batch.runs, out.tile_list = batch.tileList, out.accumulate_kernel = batch.accumulateKernel, out.accumulate_pixels = batch.accumulatePixels;
-    out.aov_pixels = batch.aovPixels, out.moment_pixels = batch.momentPixels, out.raygen_count_word = words.queueWord(0);
-    const auto traversal = [](const Impl::TraversalPlan& t, uint32_t* w) { // the ten words of a traversal launch, in the struct's order
-        const uint32_t v[10] = {t.kernel, static_cast<uint32_t>(t.layout), t.count, t.nearest, t.dense, t.refillMin, t.chunk, t.leafVote, t.flags, t.extraLds};
-        std::memcpy(w, v, sizeof v);
-    };
-    traversal(p.closest, &out.closest_kernel);
-    out.closest_count_word = words.queueWord(bounce - 1), out.closest_cursor_word = p.closest.kernel == Impl::kKernelWide ? words.cursorClosestWord(bounce) : 0u;
-    out.shade_sorted = p.shadeSorted, out.shade_aov = p.shadeAov, out.shade_flags = p.shadeFlags, out.shade_sort_scale = p.sortScale, out.shade_grid_cap = p.itemGridCap;
-    traversal(p.shadow, &out.shadow_kernel);
-    out.shadow_count_word = words.shadowCountWord(bounce, p.shadowSource);
-    out.shadow_cursor_word = p.shadow.kernel == Impl::kKernelWide ? words.cursorShadowWord(bounce) : 0u;
-    out.shadow_cached = p.cached, out.shadow_first_look = p.firstLook, out.shadow_self = p.selfShadow, out.shadow_source = p.shadowSource, out.look_flags = p.lookFlags;
-    if (p.firstLook) out.look_count_word = words.shadowCountWord(bounce, p.selfShadow ? Impl::kFromShadeList : Impl::kFromQueue), out.look_list_word = words.listWord(bounce);
+    writeLaunchPlan(batch, planBounce(m.options, in, bounce, batch), bounce, out);
 }
 
 void Renderer::memoryInfo(uint64_t& pathStateBytes, uint64_t& pathsAllocated, uint64_t& maxPathsPerBatch, uint64_t& sceneBytes) const
@@ -2399,61 +2023,15 @@ void Renderer::readDeferred(float* sampleRgb, float* accumulationRgb, uint32_t* 
     if (bgra8) RF_HIP(hipMemcpy(bgra8, m.deferredBgra.ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
 }
 
-void Renderer::setCounting(bool enabled) { mImpl->counting = enabled; }
+void Renderer::setCounting(bool enabled) { mImpl->options.counting = enabled; }
 
+// The names that need the device are handled here; every other one is a knob of the launch policy (LaunchOptions::set)
 void Renderer::setOption(const std::string& name, int64_t value)
 {
-    if (name == "traversal_variant") mImpl->traversalVariant = mImpl->wideUsable ? static_cast<int>(value) : 0;
-    else if (name == "refill_min") mImpl->optRefillMin = mImpl->optRefillMinDeep = mImpl->optRefillMinDeepDense = mImpl->optRefillMinDeepQuad = static_cast<uint32_t>(value); // (all: a sweep of one value covers every launch)
-    else if (name == "refill_min_deep") mImpl->optRefillMinDeep = mImpl->optRefillMinDeepDense = mImpl->optRefillMinDeepQuad = static_cast<uint32_t>(value);
-    else if (name == "refill_deep_from_bounce") mImpl->optRefillDeepFromBounce = static_cast<uint32_t>(std::max<int64_t>(value, 1));
-    else if (name == "leaf_vote") mImpl->optLeafVote = mImpl->optLeafVoteClosest = static_cast<uint32_t>(value);
-    else if (name == "dense_leaf_min") mImpl->optDenseLeafMin = static_cast<uint32_t>(std::clamp<int64_t>(value, 0, 15));
-    else if (name == "dense_leaf_from_bounce") mImpl->optDenseLeafFromBounce = static_cast<uint32_t>(std::max<int64_t>(value, 1));
-    else if (name == "chunk") mImpl->optChunk = mImpl->optChunkEarly = static_cast<uint32_t>(std::clamp<int64_t>(value, 1, 1 << 20)); // (both, as refill_min)
-    else if (name == "chunk_early") mImpl->optChunkEarly = static_cast<uint32_t>(std::clamp<int64_t>(value, 1, 1 << 20));
-    else if (name == "shade_sort_from_bounce") mImpl->optShadeSortFromBounce = static_cast<uint32_t>(std::max<int64_t>(value, 0));
-    else if (name == "chunk_early_bounces") mImpl->optChunkEarlyBounces = static_cast<uint32_t>(std::max<int64_t>(value, 0));
-    else if (name == "sample_sort") mImpl->optSampleSort = value != 0;
-    else if (name == "accumulate_runs") mImpl->optAccumulateRuns = value != 0;
-    else if (name == "uniform_fetch") mImpl->optUniformFetch = static_cast<int>(value);
-    else if (name == "compact_from_bounce") mImpl->optCompactFromBounce = static_cast<uint32_t>(std::max<int64_t>(value, 0));
-    else if (name == "compact_shadow_from_bounce") mImpl->optCompactShadowFromBounce = static_cast<uint32_t>(std::max<int64_t>(value, 0));
-    else if (name == "query_compact") mImpl->optQueryCompact = static_cast<int>(value);
-    else if (name == "quad_from_bounce") mImpl->optQuadFromBounce = static_cast<uint32_t>(std::max<int64_t>(value, 0));
-    else if (name == "quad_shadow_from_bounce") mImpl->optQuadShadowFromBounce = static_cast<uint32_t>(std::max<int64_t>(value, 0));
-    else if (name == "quad_local_from_bounce") mImpl->optQuadLocalFromBounce = static_cast<uint32_t>(std::max<int64_t>(value, 0));
-    else if (name == "quad_local_shadow_from_bounce") mImpl->optQuadLocalShadowFromBounce = static_cast<uint32_t>(std::max<int64_t>(value, 0));
-    else if (name == "quad_half_from_bounce") mImpl->optQuadHalfFromBounce = static_cast<uint32_t>(std::max<int64_t>(value, 0));
-    else if (name == "quad_half_shadow_from_bounce") mImpl->optQuadHalfShadowFromBounce = static_cast<uint32_t>(std::max<int64_t>(value, 0));
-    else if (name == "quad_except_mask") mImpl->optQuadExceptMask = static_cast<uint32_t>(value);
-    else if (name == "quad_shadow_except_mask") mImpl->optQuadShadowExceptMask = static_cast<uint32_t>(value);
-    else if (name == "oct_from_bounce") mImpl->optOctFromBounce = static_cast<uint32_t>(std::max<int64_t>(value, 0));
-    else if (name == "hot_from_bounce") mImpl->optHotFromBounce = static_cast<uint32_t>(std::max<int64_t>(value, 0));
-    else if (name == "hot_shadow_from_bounce") mImpl->optHotShadowFromBounce = static_cast<uint32_t>(std::max<int64_t>(value, 0));
-    else if (name == "packet_bounces") mImpl->optPacketBounces = static_cast<uint32_t>(std::max<int64_t>(value, 0));
-    else if (name == "shade_blocks") mImpl->optShadeBlocks = static_cast<uint32_t>(value);
-    else if (name == "const_primary_origin") mImpl->optConstPrimaryOrigin = value != 0;
-    else if (name == "shadow_self_test") mImpl->optShadowSelfTest = value != 0;
-    // bounce 1 over per-pixel leaf lists (rf_primary_lists.hip; planBatch says when): 0 keeps the kTraceWide launch alone -- same image either way
-    else if (name == "primary_lists") mImpl->optPrimaryLists = value != 0;
-    else if (name == "primary_list_capacity") mImpl->optPrimaryListCapacity = static_cast<uint32_t>(std::clamp<int64_t>(value, 1, kPrimaryListMaxCapacity));
-    else if (name == "primary_list_min_samples") mImpl->optPrimaryListMinSamples = static_cast<uint32_t>(std::clamp<int64_t>(value, 1, 1 << 30));
-    // 0 (default): sin / cos / acos / exp / pow as the f32 rounding of a specified f64 evaluation (bit-identical to the test oracle); 1: the device math library's f32 functions
-    // (kRaygen's lens / cone angle, kSky's dome: rf_device.hpp tSin ...), graded by SURVEY 8(d)'s tolerance.  Set it before the first sample of an accumulation.
-    else if (name == "transcendentals") mImpl->optTranscendentalsF32 = value != 0;
-    else if (name == "dense_raygen") mImpl->optDenseRaygen = value != 0; // 0: kRaygen appends to the first queue with one atomic per 1 024 slots (until round 6)
-    else if (name == "slot_group_shift") mImpl->optSlotGroupShift = value < 0 || value > 10 ? kSlotSampleMajor : static_cast<uint32_t>(value); // -1: sample-major
-    else if (name == "shadow_nearest_first") mImpl->shadowNearestFirst = value != 0;
-    else if (name == "shadow_sign_order" || name == "shadow_record_order") mImpl->optShadowSignOrder = value != 0;
-    else if (name == "shadow_first_look_from_bounce") mImpl->optShadowFirstLookFromBounce = static_cast<uint32_t>(std::max<int64_t>(value, 0));
-    else if (name == "occluder_grid_log2_cells") mImpl->optOccluderGridLog2Cells = static_cast<uint32_t>(std::clamp<int64_t>(value, 4, 26));
-    else if (name == "occluder_grid_cells") mImpl->optOccluderGridCells = static_cast<uint32_t>(std::clamp<int64_t>(value, 0, 1 << 16));
-    else if (name == "occluder_cache_bounces") mImpl->optOccluderCacheBounces = static_cast<uint32_t>(std::max<int64_t>(value, 0));
-    else if (name == "reserve_samples")
+    Impl& m = *mImpl;
+    if (name == "reserve_samples")
     {
         // allocate path state for batches of up to `value` samples now (otherwise it grows on first use)
-        Impl&          m = *mImpl;
         const uint64_t pixelsPadded = static_cast<uint64_t>(m.tiles.size()) * 1024;
         RF_HIP(hipSetDevice(m.device));
         if (pixelsPadded)
@@ -2463,24 +2041,22 @@ void Renderer::setOption(const std::string& name, int64_t value)
             (void)m.ensurePathState(samples * pixelsPadded); // best effort: render() falls back to smaller batches
         }
     }
-    else if (name == "query_variant") mImpl->queryVariant = mImpl->wideUsable ? static_cast<int>(value) : 0;
     else if (name == "persistent_blocks")
     {
         // > 0: every persistent launch takes that grid; 0: back to what the device holds of the kernel launched (residentBlocks)
-        mImpl->wideBlocksForced = value > 0;
-        mImpl->wideBlocks = value > 0 ? static_cast<uint32_t>(value) : mImpl->residentBlocks(traceWideKernel(false, false, false, 0, false), mImpl->optExtraLds);
+        m.wideBlocksForced = value > 0;
+        m.wideBlocks = value > 0 ? static_cast<uint32_t>(value) : m.residentBlocks(traceWideKernel(false, false, false, 0, false), m.options.optExtraLds);
     }
+    else if (!m.options.set(name, value, m.facts.wideUsable)) throw std::invalid_argument("unknown option " + name);
     else if (name == "extra_lds")
     {
-        Impl& m = *mImpl;
-        m.optExtraLds = static_cast<uint32_t>(std::max<int64_t>(value, 0));
+        // (the persistent grid, sized again for the occupancy that is left)
         hipDeviceProp_t prop{};
         RF_HIP(hipGetDeviceProperties(&prop, m.device));
         int perCu = 0;
-        RF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, reinterpret_cast<const void*>(traceWideKernel(false, false, false, 0, false)), kBlock, m.optExtraLds));
+        RF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, reinterpret_cast<const void*>(traceWideKernel(false, false, false, 0, false)), kBlock, m.options.optExtraLds));
         m.wideBlocks = static_cast<uint32_t>(std::max(perCu, 1)) * static_cast<uint32_t>(prop.multiProcessorCount);
     }
-    else throw std::invalid_argument("unknown option " + name);
 }
 void Renderer::setTiming(bool enabled) { mImpl->timing = enabled; }
 
@@ -2521,7 +2097,7 @@ RenderStats Renderer::stats()
     if (std::getenv("RF_DEBUG_COUNTERS"))
         std::fprintf(stderr, "[rf] rays redone by the scalar traversal: closest %llu of %llu, shadow %llu of %llu\n", c.scalarRedo[0], c.closestRays, c.scalarRedo[1], c.shadowRays);
 #if defined(RF_EXP_PHASE)
-    if (std::getenv("RF_DEBUG_COUNTERS") && !m.counting)
+    if (std::getenv("RF_DEBUG_COUNTERS") && !m.options.counting)
     {
         for (int k = 0; k < 2; ++k)
         {
@@ -2539,7 +2115,7 @@ RenderStats Renderer::stats()
         std::fprintf(stderr, "[rf-phase] occluder cache: shadow rays %llu, occluded %llu, cache tried %llu, answered at the cached leaf %llu\n", c.shadowRays, c.occludedRays, c.occluderTried, c.occluderHit);
     }
 #endif
-    if (std::getenv("RF_DEBUG_COUNTERS") && m.counting)
+    if (std::getenv("RF_DEBUG_COUNTERS") && m.options.counting)
     {
         for (int k = 0; k < 2; ++k)
         {
@@ -2595,7 +2171,7 @@ void Renderer::intersectRays(const float* rays6, uint64_t numRays, float tMax, u
     Impl& m = *mImpl;
     synchronize();
     if (numRays == 0) return;
-    if (m.queryVariant == 2)
+    if (m.options.queryVariant == 2)
     {
         std::vector<float4> hit, p4;
         m.queryWide(rays6, numRays, tMax, false, hit, p4);
@@ -2638,7 +2214,7 @@ void Renderer::occludedRays(const float* rays6, uint64_t numRays, float tMax, fl
     Impl& m = *mImpl;
     synchronize();
     if (numRays == 0) return;
-    if (m.queryVariant == 2)
+    if (m.options.queryVariant == 2)
     {
         std::vector<float4> rad, unused;
         m.queryWide(rays6, numRays, tMax, true, rad, unused);

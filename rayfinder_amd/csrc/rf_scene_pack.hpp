@@ -9,7 +9,7 @@
 
 namespace rf
 {
-// What the launch policy (rf_renderer.hip: planBatch, planBounce, resolveTraversal) and the checkpoint's scene guard are told about the scene
+// What the launch policy (rf_launch_policy.cpp: planBatch, planBounce, resolveTraversal) and the checkpoint's scene guard are told about the scene
 struct SceneFacts
 {
     uint64_t sceneCounts[4] = {};     // BVH nodes, triangles, textures, texels

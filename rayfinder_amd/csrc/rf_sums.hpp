@@ -1,10 +1,11 @@
 // rf_sums.hpp -- the per-pixel sums in sample order (rf_sums.hip): every kernel that adds a batch's per-slot records onto a running sum of the handle -- the image S,
-// the radiance second moments Q, the two first-hit AOV sums, the K bucket sums -- and the constants of their launches.  The host (Impl::planBatch / enqueueSums) picks a
+// the radiance second moments Q, the two first-hit AOV sums, the K bucket sums -- and the constants of their launches.  The host (planBatch, rf_launch_policy.cpp / Impl::enqueueSums) picks a
 // kernel by (sum, LDS-staged or one lane per pixel, shard-compact or tile-list addressing) and launches them with one argument list; the headline image kernel and the
 // bucket kernels (K planes, a phase) keep their own.
 #pragma once
 
 #include "rf_kernels.hpp"
+#include "rf_launch_constants.hpp"
 
 namespace rf
 {
@@ -30,8 +31,7 @@ using SumKernel = void (*)(FrameParams fp, const uint32_t* tileIds, const float4
 // Compiled: Radiance (one lane per pixel; its staged kernel is accumulateRunsKernel) and Moments with shard-compact addressing, RadianceMoments with a tile list, Aov
 // with both, RadianceMoments and Aov with a shard's slot list; Radiance with a tile list and with a shard's slot list in both forms (the direct sums D under
 // RF_DIRECT_TILE_COUNTS: the staged form takes kMomentPixels pixels in chunks of kMomentChunk, 6 336 B of LDS); anything else throws.
-constexpr uint32_t kMomentPixels = 16, kMomentChunk = 32;
-constexpr uint32_t kAovPixels = 8, kAovChunk = 32;
+constexpr uint32_t kMomentChunk = 32, kAovChunk = 32; // (kMomentPixels, kAovPixels: rf_launch_constants.hpp)
 enum class SumAddressing : uint32_t
 {
     Compact,   // the sums of local pixel lp at lp
@@ -42,12 +42,7 @@ SumKernel sumKernel(Sum sum, bool runs, SumAddressing addressing);
 
 // Radiance, pixel-major slot order, the WHOLE run in LDS: pixelsPerWorkgroup (1, 2 or kAccPixels) x 3 x (numSamples + 1) floats of dynamic LDS, numSamples <= kAccMaxSamples;
 // the image sits at lp (no tile list).  Its source is ps.rad
-#if defined(RF_EXP_ACC_PIXELS)
-constexpr uint32_t kAccPixels = RF_EXP_ACC_PIXELS;
-#else
-constexpr uint32_t kAccPixels = 4;
-#endif
-constexpr uint32_t kAccMaxSamples = 1024;
+// (kAccPixels, kAccMaxSamples: rf_launch_constants.hpp)
 using AccumulateRunsKernel = void (*)(FrameParams fp, const uint32_t* tileIds, PathStreams ps, float4* image);
 AccumulateRunsKernel accumulateRunsKernel(uint32_t pixelsPerWorkgroup);
 
@@ -63,7 +58,7 @@ AccumulateRunsKernel accumulateRunsKernel(uint32_t pixelsPerWorkgroup);
 // shardList (rf_comm_render_adaptive with RF_BUCKETS_SHARD_TILE_COUNTS): the same under a tile shard, every plane holds the SHARD and the sums of local pixel lp sit at
 // tileIds[fp.numTiles + (lp >> 10)] * 1024 + (lp & 1023) of it.  A rank's active tiles all sit at the frame's leading count, which is that rank's bucket sample count:
 // one phase serves the launch there too.
-constexpr uint32_t kMaxBuckets = 15, kBucketPixels = 4, kBucketChunk = 32;
+constexpr uint32_t kMaxBuckets = 15, kBucketChunk = 32; // (kBucketPixels: rf_launch_constants.hpp)
 using BucketKernel = void (*)(FrameParams fp, const uint32_t* tileIds, const float4* src, float4* planes, size_t planeStride, uint32_t K, uint32_t phase);
 BucketKernel bucketKernel(bool runs, SumAddressing addressing);
 } // namespace rf

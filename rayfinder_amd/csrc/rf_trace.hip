@@ -3,6 +3,7 @@
 // reference-ordered kernels (scalar fallback, bvh-visualizer pass, ray queries) and -- experiment builds -- the packet kernel.  Launched from
 // rf_renderer.hip through the accessors at the end of this file (rf_kernels.hpp).
 #include "rf_kernels.hpp"
+#include "rf_trace_wide_list.hpp"
 
 namespace rf
 {
@@ -1967,19 +1968,10 @@ namespace kern
 {
 TraceWideKernel traceWideKernel(bool anyHit, bool count, bool nearestFirst, int compact, bool denseLeaves)
 {
-    // the instantiations this build ships: the layouts the renderer picks by itself (+ the oct records, an option), each closest-hit one and the any-hit
-    // variants it pairs them with; with the dense leaf phase only where a default launch can reach it (rf_renderer.hip: launchClosestWide / launchShadowWide)
+    // the instantiations this build ships: rf_trace_wide_list.hpp
 #define RF_TW(A, C, N, L, D) \
     if (anyHit == A && count == C && nearestFirst == N && compact == L && denseLeaves == D) return kTraceWide<A, C, N, L, D>;
-    RF_TW(false, true, false, 0, false) RF_TW(true, true, true, 0, false) RF_TW(true, true, false, 0, false)
-    RF_TW(false, false, false, 0, false) RF_TW(false, false, false, 3, false) RF_TW(false, false, false, 4, false) RF_TW(false, false, false, 5, false) RF_TW(false, false, false, 6, false)
-    RF_TW(false, false, false, 3, true) RF_TW(false, false, false, 4, true) RF_TW(false, false, false, 5, true)
-    RF_TW(true, false, true, 0, false) RF_TW(true, false, false, 0, false)
-    RF_TW(true, false, true, 3, false) RF_TW(true, false, false, 3, false) RF_TW(true, false, true, 4, false) RF_TW(true, false, false, 4, false) RF_TW(true, false, true, 5, false) RF_TW(true, false, false, 5, false)
-    RF_TW(true, false, true, 3, true) RF_TW(true, false, false, 4, true) RF_TW(true, false, false, 5, true)
-#if defined(RF_EXP_LEGACY_LAYOUTS)
-    RF_TW(false, false, false, 1, false) RF_TW(false, false, false, 2, false) RF_TW(true, false, true, 1, false) RF_TW(true, false, true, 2, false)
-#endif
+    RF_TRACE_WIDE_INSTANTIATIONS(RF_TW)
 #undef RF_TW
     return nullptr;
 }

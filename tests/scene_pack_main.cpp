@@ -3,14 +3,15 @@
 // tests/golden/scene_pack_parent.json, recorded from the renderer's constructor before the packing left it (profiles/scene_pack/record_parent.hip includes this
 // file with its own copy of that code behind the same names).
 //
-// Scene file: "RFSCENE1", u64 nodes, u64 triangles, u64 textures, then the 48-byte nodes, the 48-byte position attributes, the 80-byte vertex attributes and per
-// texture {u32 width, u32 height, width * height u32 texels}.
+// Scene file: tests/scene_file.hpp.
 // Usage: scene_pack_main [--time N] file...      (--time N: also N timed runs of packScene alone per scene, "pack_ms" in the line)
 #if !defined(SCENE_PACK_PARENT_RECORDER)
 #include "rf_bvh.hpp"
 #include "rf_scene_pack.hpp"
 #include "rf_wide_build.hpp"
 #endif
+
+#include "scene_file.hpp"
 
 #include <chrono>
 #include <cstdint>
@@ -25,53 +26,6 @@
 
 namespace
 {
-struct SceneFile
-{
-    std::vector<rf::BvhNode>               nodes;
-    std::vector<rf::PositionAttribute>     positions;
-    std::vector<rf::VertexAttributes>      attributes;
-    std::vector<std::vector<uint32_t>>     texels;
-    std::vector<rf::TextureView>           textures;
-    rf::SceneView view() const { return {nodes, positions, attributes, textures}; }
-};
-
-template<typename T>
-void readArray(std::ifstream& in, std::vector<T>& out, uint64_t count, uint64_t bytesLeft)
-{
-    if (count > bytesLeft / sizeof(T)) throw std::runtime_error("scene file: an array is longer than the file");
-    out.resize(count);
-    in.read(reinterpret_cast<char*>(out.data()), static_cast<std::streamsize>(count * sizeof(T)));
-    if (!in) throw std::runtime_error("scene file: truncated");
-}
-
-SceneFile readScene(const std::string& path)
-{
-    std::ifstream in(path, std::ios::binary | std::ios::ate);
-    if (!in) throw std::runtime_error("scene file: cannot open " + path);
-    const uint64_t size = static_cast<uint64_t>(in.tellg());
-    in.seekg(0);
-    char     magic[8];
-    uint64_t counts[3];
-    in.read(magic, 8);
-    in.read(reinterpret_cast<char*>(counts), sizeof counts);
-    if (!in || std::memcmp(magic, "RFSCENE1", 8) != 0) throw std::runtime_error("scene file: bad header");
-    SceneFile s;
-    readArray(in, s.nodes, counts[0], size);
-    readArray(in, s.positions, counts[1], size);
-    readArray(in, s.attributes, counts[1], size);
-    if (counts[2] > size / 8) throw std::runtime_error("scene file: more textures than the file holds");
-    s.texels.resize(counts[2]);
-    for (auto& px : s.texels)
-    {
-        uint32_t wh[2];
-        in.read(reinterpret_cast<char*>(wh), sizeof wh);
-        if (!in) throw std::runtime_error("scene file: truncated");
-        readArray(in, px, static_cast<uint64_t>(wh[0]) * wh[1], size);
-        s.textures.push_back({px.data(), wh[0], wh[1]});
-    }
-    return s;
-}
-
 uint64_t fnv(const void* data, size_t bytes, uint64_t h = 0xcbf29ce484222325ull)
 {
     const auto* p = static_cast<const unsigned char*>(data);

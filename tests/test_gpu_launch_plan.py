@@ -4,99 +4,25 @@ None of the host driver's choices shows in the image (the contract is "same imag
 exit vote, claim size or count word.  tests/golden/launch_plan_parent.json is a recording made at the launch sites of that parent commit (a throw-away patch that
 printed one line per launch: profiles/plan/parent_capture.patch, run by profiles/plan/record_parent.py over the matrix below), reworded into the fields of
 rf_launch_plan.  A characterisation: the recording is the reference and every field must EQUAL it.  rf_renderer_layout_info must say what the plan says, and two
-counters that exist already tie the plan to what ran."""
-import json
-import os
+counters that exist already tie the plan to what ran.
 
-import numpy as np
+Its CPU twin, tests/test_launch_policy.py, replays the same matrix (tests/launch_plan_cases.py) through the host-only policy unit without a device; this test is what
+ties the C ABI, the policy and what actually ran together."""
+import json
+
 import pytest
 
 import rayfinder_amd as rf
-from rayfinder_amd import scenes
+from launch_plan_cases import BOUNCES, CASES, H, RECORDING, SAMPLE_COUNTS, SCENES, SPP, STATES, W, MATRIX, camera, pt, scene_arrays
 
 pytestmark = pytest.mark.gpu
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-RECORDING = os.path.join(GOLDEN, "launch_plan_parent.json")
-W, H, BOUNCES, SPP = 64, 48, 4, 1024          # 2 x 2 tiles, the lower row half outside the frame
-SAMPLE_COUNTS = (2, 8, 200, 700)              # per batch: across the <= 4 cutoff (no runs) and the 160 / 640 steps of the pixels per workgroup
-STATES = ("cold", "warm")                     # before the handle's first batch / after one 2-sample render (the occluder grid is warm: first look is eligible)
-
-
-def _case(*options, **kw):
-    return dict(options=options, **kw)
-
-
-CASES = {
-    "nothing_set": _case(),
-    "counting": _case(counting=True),
-    "traversal_variant_0": _case(("traversal_variant", 0)),
-    "aovs": _case(aovs=True),
-    "moments": _case(moments=True),
-    "shade_sort_from_bounce_0": _case(("shade_sort_from_bounce", 0)),
-    "occluder_cache_bounces_0": _case(("occluder_cache_bounces", 0)),
-    "shadow_self_test_0": _case(("shadow_self_test", 0)),
-    "shadow_nearest_first_0": _case(("shadow_nearest_first", 0)),
-    "shadow_sign_order_0": _case(("shadow_sign_order", 0)),
-    "shadow_first_look_from_bounce_1": _case(("shadow_first_look_from_bounce", 1)),
-    "shadow_first_look_from_bounce_0": _case(("shadow_first_look_from_bounce", 0)),
-    "quad_half_from_bounce_1": _case(("quad_half_from_bounce", 1), ("quad_half_shadow_from_bounce", 1)),
-    "quad_local_from_bounce_1": _case(("quad_local_from_bounce", 1), ("quad_local_shadow_from_bounce", 1)),
-    "quad_from_bounce_0": _case(("quad_from_bounce", 0)),
-    "quad_except_mask_2": _case(("quad_except_mask", 2)),
-    "oct_from_bounce_2": _case(("oct_from_bounce", 2)),
-    "dense_leaf_min_2": _case(("dense_leaf_min", 2)),
-    "dense_leaf_from_bounce_3": _case(("dense_leaf_from_bounce", 3)),
-    "uniform_fetch_m1": _case(("uniform_fetch", -1)),
-    "uniform_fetch_0": _case(("uniform_fetch", 0)),
-    "uniform_fetch_1": _case(("uniform_fetch", 1)),
-    "refill_min_7": _case(("refill_min", 7)),
-    "refill_min_deep_9": _case(("refill_min_deep", 9)),
-    "refill_deep_from_bounce_3": _case(("refill_deep_from_bounce", 3)),
-    "leaf_vote_11": _case(("leaf_vote", 11)),
-    "chunk_64": _case(("chunk", 64)),
-    "chunk_early_bounces_0": _case(("chunk_early_bounces", 0)),
-    "slot_group_shift_m1": _case(("slot_group_shift", -1)),
-    "slot_group_shift_2": _case(("slot_group_shift", 2)),
-    "accumulate_runs_0": _case(("accumulate_runs", 0)),
-    "sample_sort_0": _case(("sample_sort", 0)),
-    "camera_far_outside": _case(camera="far"),        # the primaryOutside branch
-    "lens": _case(camera="lens"),                     # no constant origin
-    "tree_not_nested": _case(tree="poke"),            # a child box sticks out of its parent's: binary records, no cache
-}
-SCENES = ("duck", "quad")
-# (the hand-made tree is the Duck's with one box enlarged: the quad scene's tree is a single leaf)
-MATRIX = [(s, c) for s in SCENES for c in CASES if not (s == "quad" and CASES[c].get("tree"))]
-
-_pts = {}
-
-
-def _pt(scene):
-    if scene not in _pts:
-        _pts[scene] = rf.PtFormat.from_gltf(os.path.join(GOLDEN, "Duck.glb")) if scene == "duck" else scenes.quad_scene()
-    return _pts[scene]
 
 
 def make_handle(scene, case):
     """The handle of one cell of the matrix, before its first batch (the recorder builds the very same ones)"""
     c = CASES[case]
-    pt = _pt(scene)
-    a = pt.arrays()
-    if c.get("tree") == "poke":
-        nodes = a["bvhNodes"].copy()
-        nodes[1]["max"] = tuple(np.asarray(nodes[0]["max"]) + np.float32(1.0))
-        sc = rf.scene_from_arrays(nodes, a["trianglePositionAttributes"], a["triangleVertexAttributes"], [(px, w, h) for (px, w, h) in a["baseColorTextures"]])
-    else:
-        sc = pt.scene()
-    if c.get("camera") == "far":      # (the camera of test_camera_far_outside_the_scene_keeps_primary_rays_off_the_scalar_path, distance 1000)
-        lo, hi = np.array(a["bvhNodes"][0]["min"][:3]), np.array(a["bvhNodes"][0]["max"][:3])
-        centre, size, distance = 0.5 * (lo + hi), float(np.max(hi - lo)), 1000.0
-        eye = centre + np.array([0.6, 0.4, 0.7]) / np.linalg.norm([0.6, 0.4, 0.7]) * distance * size
-        cam = rf.create_camera(eye, centre, 0.0, 1.0, float(2.0 * np.arctan(0.75 / distance)), W / H)
-    elif c.get("camera") == "lens":
-        cam = rf.fly_camera(W, H, aperture=0.1)
-    else:
-        cam = rf.fly_camera(W, H)
-    r = rf.ReferencePathTracer(rf.make_render_parameters(W, H, cam, SPP, BOUNCES, rf.make_sky(), 0.25), sc)
+    sc = rf.scene_from_arrays(*scene_arrays(scene, c["tree"])) if c.get("tree") else pt(scene).scene()
+    r = rf.ReferencePathTracer(rf.make_render_parameters(W, H, camera(scene, case), SPP, BOUNCES, rf.make_sky(), 0.25), sc)
     for name, value in c["options"]:
         r.set_option(name, value)
     if c.get("counting"):
