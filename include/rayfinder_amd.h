@@ -140,6 +140,10 @@ typedef struct rf_stats
      * nested).  primary_fallback_rays: of those, rays handed on to the ordinary traversal launch (a pixel whose directions change sign on an axis, whose list would
      * exceed primary_list_capacity entries or holds a leaf of more than 7 triangles; a ray with an infinite 1 / direction component). */
     uint64_t primary_list_rays, primary_fallback_rays;
+    /* Of primary_list_rays: rays of the batches whose bounce 1 ran as ONE kernel per path (option primary_fused, default on): the lane that generates the ray walks its
+     * pixel's list and shades the hit from its registers, so queue entry, direction, hit record and blue-noise triple of a covered ray are never written.  0: the option
+     * off, the first-hit AOVs on, or `transcendentals` 1 -- those batches keep the three launches.  Same image bit for bit. */
+    uint64_t primary_fused_rays;
 } rf_stats;
 
 typedef struct rf_renderer rf_renderer;
@@ -698,6 +702,9 @@ RF_API int rf_renderer_set_timing(rf_renderer* r, int enabled);
  *                                      default 64; 65 words of device memory per pixel of a batch, counted by rf_renderer_memory_info and the batch-depth fit; a
  *                                      pixel that needs more takes the ordinary launch).  rf_stats.primary_list_rays / primary_fallback_rays say what ran.
  *                                      Same image with any setting.
+ *   primary_fused 0 | 1                where those lists run, the first-hit AOVs are off and `transcendentals` is 0: bounce 1's ray generation, list walk and shading
+ *                                      in ONE kernel per path (default 1) instead of three that hand the path on through memory.  rf_stats.ms_raygen is then 0 and
+ *                                      bounce 1's closest-hit time contains generation and shading; rf_stats.primary_fused_rays says what ran.  Same image.
  *   transcendentals 0 | 1              THE ONE OPTION THAT CHANGES RESULTS (round 6; default 0).  0: sin / cos / acos / exp / pow(x, 1.5) of ray generation and the sky dome are
  *                                      the f32 rounding of a specified f64 evaluation (GPU == test oracle bit for bit); 1: the device math library's f32 functions (libm-grade) --
  *                                      WGSL's own builtins are f32 with implementation-defined ulps (wgsl:247-275,568-616).  Within SURVEY 8(d)'s tolerance of the default

@@ -131,7 +131,7 @@ class Stats(C.Structure):
                 ("launches_shadow", C.c_uint32), ("launches_accumulate", C.c_uint32), ("batches_traced", C.c_uint32),
                 ("closest_record_fetches", C.c_uint64), ("shadow_record_fetches", C.c_uint64),
                 ("abandoned_rays", C.c_uint64), ("scalar_redo_rays", C.c_uint64), ("shadow_rays_hint_answered", C.c_uint64), ("shadow_rays_self_answered", C.c_uint64),
-                ("primary_list_rays", C.c_uint64), ("primary_fallback_rays", C.c_uint64)]
+                ("primary_list_rays", C.c_uint64), ("primary_fallback_rays", C.c_uint64), ("primary_fused_rays", C.c_uint64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}

@@ -764,6 +764,7 @@ int rf_renderer_get_stats(rf_renderer* r, rf_stats* out)
         out->shadow_rays_self_answered = s.shadowRaysSelfAnswered;
         out->primary_list_rays = s.primaryListRays;
         out->primary_fallback_rays = s.primaryFallbackRays;
+        out->primary_fused_rays = s.primaryFusedRays;
         return RF_OK;
     });
 }

@@ -125,6 +125,8 @@ struct DeviceCounters
     // all builds: bounce-1 rays of the batches whose primary launch ran over the per-pixel leaf lists (kTraceLeafLists counts its whole queue), and those of them it handed
     // on to the kTraceWide launch behind it (rf_primary_lists.hip)
     unsigned long long primaryListRays, primaryFallbackRays;
+    // ... and the bounce-1 rays of the batches that generated, intersected and shaded them in one kernel (kPrimaryFused counts its whole queue)
+    unsigned long long primaryFusedRays;
 };
 
 // Division of a 32-bit unsigned by a divisor that is a RUN-TIME value but the same for a whole launch (samples per batch, tiles per row, samples per pixel): the exact quotient from
@@ -364,13 +366,14 @@ constexpr uint32_t kNoListSigns = 1u, kNoListOverflow = 2u, kNoListBigLeaf = 3u,
 using SamplePermutationKernel = void (*)(uint32_t firstFrame, uint32_t spp, uint32_t numSamples, uint32_t* perm, uint32_t* inv);
 using RaygenKernel = void (*)(FrameParams fp, DeviceScene scene, const uint32_t* tileIds, PathStreams ps, uint32_t* queue, uint32_t* queueCount, DeviceCounters* counters);
 using TraceClosestKernel = void (*)(DeviceScene scene, PathStreams ps, const uint32_t* queue, const uint32_t* queueCount, DeviceCounters* counters);
-using ShadeKernel = void (*)(DeviceScene scene, SkyStateGpu sky, SunBasis sunBasis, PathStreams ps, const uint32_t* queue, const uint32_t* queueCount, uint32_t* hitQueue, uint32_t* hitCount, uint32_t* missQueue, uint32_t* missSlots, uint32_t* missCount, uint32_t* shadowList, uint32_t* shadowListCount, uint32_t bounceFlags, uint32_t sortScale, float4* aov);
+using ShadeKernel = void (*)(DeviceScene scene, SkyStateGpu sky, SunBasis sunBasis, PathStreams ps, const uint32_t* queue, const uint32_t* queueCount, uint32_t* hitQueue, uint32_t* hitCount, uint32_t* missQueue, uint32_t* missSlots, uint32_t* missCount, uint32_t* shadowList, uint32_t* shadowListCount, uint32_t bounceFlags, uint32_t sortScale, float4* aov, const uint32_t* list);
 using SkyKernel = void (*)(SkyStateGpu sky, PathStreams ps, const uint32_t* missSlots, const uint32_t* missQueue, const uint32_t* missCount, uint32_t firstBounce);
 using TraceShadowKernel = void (*)(DeviceScene scene, SkyStateGpu sky, SunBasis sunBasis, PathStreams ps, const uint32_t* queue, const uint32_t* queueCount, DeviceCounters* counters, uint32_t firstBounce);
 using TraceWideKernel = void (*)(DeviceScene scene, WideScene wide, SkyStateGpu sky, SunBasis sunBasis, PathStreams ps, const uint32_t* queue, const uint32_t* queueCount, uint32_t* cursor, DeviceCounters* counters, uint32_t refillMin, uint32_t leafVote, uint32_t chunkMax, float tMax, uint32_t flags);
 using ShadowFirstLookKernel = void (*)(DeviceScene scene, WideScene wide, SkyStateGpu sky, SunBasis sunBasis, PathStreams ps, const uint32_t* queue, const uint32_t* inList, const uint32_t* inCount, uint32_t* list, uint32_t* listCount, DeviceCounters* counters, float tMax, uint32_t flags);
 using PixelLeafListsKernel = void (*)(FrameParams fp, DeviceScene scene, const uint32_t* tileIds, uint32_t capacity, uint32_t* lists, uint32_t* lengths);
 using TraceLeafListsKernel = void (*)(DeviceScene scene, PathStreams ps, const uint32_t* queueCount, FastDiv divNumSamples, float originX, float originY, float originZ, const uint32_t* lists, const uint32_t* lengths, uint32_t capacity, uint32_t* fallback, uint32_t* fallbackCount, DeviceCounters* counters, float tMax);
+using PrimaryFusedKernel = void (*)(FrameParams fp, DeviceScene scene, SkyStateGpu sky, SunBasis sunBasis, const uint32_t* tileIds, PathStreams ps, uint32_t* queue, uint32_t* queueCount, const uint32_t* lists, const uint32_t* lengths, uint32_t capacity, uint32_t* hitQueue, uint32_t* hitCount, uint32_t* missQueue, uint32_t* missSlots, uint32_t* missCount, uint32_t* shadowList, uint32_t* shadowListCount, uint32_t* fallback, uint32_t* fallbackCount, DeviceCounters* counters, uint32_t bounceFlags, float tMax);
 using TracePacketKernel = void (*)(DeviceScene scene, WideScene wide, SkyStateGpu sky, SunBasis sunBasis, PathStreams ps, const uint32_t* queue, const uint32_t* queueCount, DeviceCounters* counters, float tMax, uint32_t flags);
 using HitPointsKernel = void (*)(DeviceScene scene, const float4* hit, P3* rayO, uint32_t n);
 using BounceTotalsKernel = void (*)(const uint32_t* queueCounts, uint32_t numBounces, unsigned long long* totals, const uint32_t* listCounts, unsigned long long lookMask, unsigned long long* lookBatch, const uint32_t* shadowListCounts, unsigned long long selfMask, DeviceCounters* counters);
@@ -393,10 +396,12 @@ OccludedRaysKernel    occludedRaysKernel();
 // rf_primary_lists.hip
 PixelLeafListsKernel pixelLeafListsKernel();
 TraceLeafListsKernel traceLeafListsKernel();
+PrimaryFusedKernel   primaryFusedKernel();
 // rf_shade.hip
 SamplePermutationKernel samplePermutationKernel();
 RaygenKernel            raygenKernel(bool f32Transcendentals);
 ShadeKernel             shadeKernel(bool sorted, bool aov = false); // aov: the bounce-1 instantiation that also writes the first-hit AOVs (unsorted only)
+ShadeKernel             shadeListedKernel(); // kShade<false, false, true>: the unsorted kernel over a list of queue positions (bounce 1 behind kPrimaryFused)
 SkyKernel               skyKernel(bool f32Transcendentals);
 BounceTotalsKernel      bounceTotalsKernel();
 TonemapKernel           tonemapKernel();

@@ -25,6 +25,7 @@ void LaunchOptions::applyEnvironment(bool wideUsable)
     // soak runs (tools/gpu_fuzz.py): the leaf lists of bounce 1 for batches of any depth, at a given capacity -- what the options primary_list_min_samples / primary_list_capacity set per handle
     if (const char* v = std::getenv("RF_PRIMARY_LIST_MIN_SAMPLES")) optPrimaryListMinSamples = static_cast<uint32_t>(std::clamp(std::atoi(v), 1, 1 << 30));
     if (const char* v = std::getenv("RF_PRIMARY_LIST_CAPACITY")) optPrimaryListCapacity = static_cast<uint32_t>(std::clamp(std::atoi(v), 1, static_cast<int>(kPrimaryListMaxCapacity)));
+    if (const char* v = std::getenv("RF_PRIMARY_FUSED")) optPrimaryFused = std::atoi(v) != 0; // (soak runs: the three bounce-1 launches against the fused one)
     if (!wideUsable) traversalVariant = 0;
 }
 
@@ -65,6 +66,8 @@ bool LaunchOptions::set(const std::string& name, int64_t value, bool wideUsable)
     // bounce 1 over per-pixel leaf lists (rf_primary_lists.hip; planBatch says when): 0 keeps the kTraceWide launch alone -- same image either way
     else if (name == "primary_lists") optPrimaryLists = value != 0;
     else if (name == "primary_list_capacity") optPrimaryListCapacity = static_cast<uint32_t>(std::clamp<int64_t>(value, 1, kPrimaryListMaxCapacity));
+    // ... generated, walked and shaded by one kernel (kPrimaryFused; planBatch says when): 0 keeps kRaygen, kTraceLeafLists and kShade -- same image either way
+    else if (name == "primary_fused") optPrimaryFused = value != 0;
     else if (name == "primary_list_min_samples") optPrimaryListMinSamples = static_cast<uint32_t>(std::clamp<int64_t>(value, 1, 1 << 30));
     // 0 (default): sin / cos / acos / exp / pow as the f32 rounding of a specified f64 evaluation (bit-identical to the test oracle); 1: the device math library's f32 functions
     // (kRaygen's lens / cone angle, kSky's dome: rf_device.hpp tSin ...), graded by SURVEY 8(d)'s tolerance.  Set it before the first sample of an accumulation.
@@ -226,6 +229,8 @@ BatchPlan planBatch(const LaunchOptions& o, const PolicyInputs& in, uint32_t num
     // samples per pixel for the once-per-pixel walk to pay.  A thin-lens camera, a counting build and small batches keep the kTraceWide launch alone.
     b.primaryListCapacity = std::min(std::max(o.optPrimaryListCapacity, 1u), kPrimaryListMaxCapacity);
     b.primaryLists = primaryListsPossible(o, in) && b.constOrigin && b.denseRaygen && o.optSlotGroupShift == 0u && b.numBounces != 0u && numSamples >= std::max(o.optPrimaryListMinSamples, 1u);
+    // ... fused with generation and shading (kPrimaryFused): the instantiation that exists writes no AOV records and evaluates sin / cos as specified
+    b.primaryFused = b.primaryLists && o.optPrimaryFused && !in.aovs && !o.optTranscendentalsF32;
     b.occluderGrid = o.optOccluderCacheBounces != 0u && o.optOccluderGridCells != 0u;
     if (b.occluderGrid)
     {

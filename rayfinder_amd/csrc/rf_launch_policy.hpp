@@ -55,6 +55,9 @@ struct LaunchOptions
     // (the list pass costs a few rays' worth per pixel: profiles/primary_lists/README.md)
     bool     optPrimaryLists = true;
     uint32_t optPrimaryListCapacity = 64, optPrimaryListMinSamples = 16;
+    // ... with generation, list walk and shading of a path in ONE kernel (kPrimaryFused; option primary_fused, default on): where the lists run, the AOVs are off and
+    // `transcendentals` is the default.  Bounce 1's three streaming kernels handed each path to each other through memory; 0 keeps them (profiles/primary_fused/README.md)
+    bool     optPrimaryFused = true;
     bool                   optSampleSort = true, optAccumulateRuns = true;
     uint32_t               optCompactFromBounce = 3;       // closest-hit launches of bounce >= this use the compact-capable records (0: never)
     uint32_t               optCompactShadowFromBounce = 2; // ... and the shadow launches of bounce >= this
@@ -73,7 +76,7 @@ struct LaunchOptions
 
     // the layouts the scene gets with no option set (SceneFacts: the five *FromBounce defaults)
     void applySceneDefaults(const SceneFacts& facts);
-    // RF_TRAVERSAL_VARIANT, RF_PACKET_BOUNCES, RF_PRIMARY_LIST_MIN_SAMPLES, RF_PRIMARY_LIST_CAPACITY (experiments and soak runs), then the clamp of a scene whose
+    // RF_TRAVERSAL_VARIANT, RF_PACKET_BOUNCES, RF_PRIMARY_LIST_MIN_SAMPLES, RF_PRIMARY_LIST_CAPACITY, RF_PRIMARY_FUSED (experiments and soak runs), then the clamp of a scene whose
     // boxes the wide kernels cannot serve.  A new handle: applySceneDefaults, then this
     void applyEnvironment(bool wideUsable);
     // rf_renderer_set_option's names, but for the ones that need the device (rf_renderer.hip: Renderer::setOption).  false: a name it does not know
@@ -123,6 +126,7 @@ struct BatchPlan
     bool     samplePerm, denseRaygen, constOrigin;
     bool     primaryLists;        // bounce 1's closest-hit group: kPixelLeafLists + kTraceLeafLists + the bounce's kTraceWide launch over what they hand on
     uint32_t primaryListCapacity; // entries per pixel
+    bool     primaryFused;        // ... as kPixelLeafLists + kPrimaryFused (generates, walks and shades: no kRaygen launch) + kTraceWide and kShade<false, false, true> over what it hands on
     int      primaryLayout;
     bool     occluderGrid; // the batch's any-hit launches get the occluder grid: occluderGridEntries words, cells found by occScale / occMask
     uint64_t occluderGridEntries;

@@ -1,7 +1,7 @@
 // rf_primary_lists.hip -- bounce 1 under a pinhole camera without the tree walk: kPixelLeafLists (once per batch, one thread per pixel: the leaves ANY primary ray
 // of that pixel can reach, in the reference's visit order) and kTraceLeafLists (one ray per lane: the exact box and the triangles of the leaves on its pixel's
 // list).  Launched from rf_renderer.hip (enqueueClosest) through the accessors at the end of this file; kTraceWide is not touched and takes whatever the lists do
-// not cover.
+// not cover.  kPrimaryFused (further down): the same walk in the lane that generates the ray and shades its hit -- bounce 1 as one kernel per path.
 //
 // Why.  A batch holds hundreds of samples of a pixel; under a pinhole camera they share one origin and their directions lie within the pixel's footprint, so the
 // traversal's interior decisions come out the same hundreds of times.  The wave-uniform fetches of kTraceWide save the memory traffic of that, not the per-lane
@@ -23,6 +23,7 @@
 //     walk deeper than its stack, and -- per ray -- anything that is not class A or whose signs are not the list's: the ray's queue position goes onto a list that
 //     the bounce's ordinary kTraceWide launch works through (WideScene::rayList).
 #include "rf_kernels.hpp"
+#include "rf_shade_device.hpp"
 
 namespace rf
 {
@@ -310,11 +311,169 @@ __global__ __launch_bounds__(kBlock) void kTraceLeafLists(DeviceScene scene, Pat
     const unsigned long long total = waveSum(static_cast<unsigned long long>(handedOn));
     if (__lane_id() == 0 && total != 0ull) atomicAdd(&counters->primaryFallbackRays, total);
 }
+// ------------------------------------------------------------------------------------------------
+// kPrimaryFused: bounce 1 of a batch whose primary launch runs over the lists, in ONE kernel per path -- kRaygen's generation, kTraceLeafLists' walk and kShade's
+// shading (BatchPlan::primaryFused: the lists, no AOVs, the specified f64 sin / cos).  The three kernels handed a path to each other through memory, one lane per
+// path, in the same order: queue entry, direction, hit record and blue-noise triple were written once to be read back once, 88 of the chain's 156 bytes per path.
+// Here the lane that generates the ray walks its pixel's list and shades the hit out of its registers, and only kShade's outputs are left to write.
+//
+// kRaygen's shape: kItems slots per thread, slot = (blockIdx * kItems + k) * kBlock + tid, pixel-major slots (slotGroupShift 0) with closed-form queue positions:
+// consecutive lanes hold consecutive samples of one pixel, which is what the walk's scalar-cache path wants (a wave is UNIFORM where its valid lanes hold one
+// pixel's samples).  Per slot the same device functions run on the same values in the same order as in the three kernels, so every output keeps its bits:
+//   a covered ray (`walks`) that hits is appended to the hit queue and shaded on the spot (shadeHit, rf_shade_device.hpp) with the batch's bounce-1 shade flags;
+//     one that misses goes onto the miss lists with its queue position, where it writes its direction -- all kSky reads of it at bounce 1;
+//   an uncovered ray (no list, overflow, big leaf, not class A, sign mismatch) writes what kRaygen wrote -- queue entry, direction, triple -- and its queue position
+//     onto `fallback`: the bounce's kTraceWide launch and kShade<false, false, true> work through that list behind this kernel.
+// A covered ray writes no queue entry, no hit record and no input triple: nothing else reads them at bounce 1 (the AOV kernel would, and keeps the three launches).
+// `fallback` cannot be the bounce's output queue as under kTraceLeafLists -- this kernel appends hits there; the driver hands in the bounce's input throughput
+// stream, which holds nothing at bounce 1.
+// ------------------------------------------------------------------------------------------------
+#if defined(RF_EXP_FUSED_WAVES)
+#define RF_FUSED_BOUNDS __launch_bounds__(kBlock, RF_EXP_FUSED_WAVES)
+#else
+#define RF_FUSED_BOUNDS __launch_bounds__(kBlock) // (102 registers, four waves per SIMD; forced into 96 for five, bounce 1's group measured 17.3 -> 18.4 ms per 256 spp)
+#endif
+__global__ RF_FUSED_BOUNDS void kPrimaryFused(FrameParams fp, DeviceScene scene, SkyStateGpu sky, SunBasis sunBasis, const uint32_t* tileIds, PathStreams ps, uint32_t* queue,
+                                                         uint32_t* queueCount, const uint32_t* lists, const uint32_t* lengths, uint32_t capacity, uint32_t* hitQueue, uint32_t* hitCount,
+                                                         uint32_t* missQueue, uint32_t* missSlots, uint32_t* missCount, uint32_t* shadowList, uint32_t* shadowListCount, uint32_t* fallback,
+                                                         uint32_t* fallbackCount, DeviceCounters* counters, uint32_t bounceFlags, float tMax)
+{
+    __shared__ uint32_t sScratch[8];
+    __shared__ float    sLut[256];
+    static_assert(kBlock == 256, "one table entry per thread");
+    sLut[threadIdx.x] = scene.albedoLut[threadIdx.x];
+    __syncthreads();
+    const uint32_t total = fp.numSamples * fp.pixelsPadded;
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+    {
+        const uint32_t count = fp.validPixels * fp.numSamples;
+        *queueCount = count;
+        atomicAdd(&counters->closestRays, static_cast<unsigned long long>(count));
+        atomicAdd(&counters->primaryListRays, static_cast<unsigned long long>(count));
+        atomicAdd(&counters->primaryFusedRays, static_cast<unsigned long long>(count));
+    }
+    const bool isLastBounce = (bounceFlags & kShadeLastBounce) != 0u, selfShadow = (bounceFlags & kShadeSelfShadow) != 0u;
+    const Vec3 o = fp.camera.origin; // (the batch's one origin: BatchPlan::constOrigin)
+    bool       isHit[kItems], isMiss[kItems], handOn[kItems];
+    uint32_t   slots[kItems], pos[kItems], hitTri[kItems], outPos[kItems];
+    float      hitU[kItems], hitV[kItems];
+    Vec3       noise[kItems];
+#pragma unroll
+    for (int k = 0; k < kItems; ++k)
+    {
+        // ---- generate (kRaygen's pass 1 and pass 2)
+        const uint32_t slot = (blockIdx.x * kItems + k) * kBlock + threadIdx.x;
+        bool           valid = slot < total;
+        uint32_t       x = 0, y = 0, sampleIdx = 0, lp = 0;
+        if (valid) slotToSamplePixel(fp, slot, sampleIdx, lp);
+        if (valid) valid = localPixelToXY(fp, tileIds, lp, x, y);
+        slots[k] = slot;
+        isHit[k] = isMiss[k] = handOn[k] = false;
+        pos[k] = 0u, hitTri[k] = kMiss, hitU[k] = hitV[k] = 0.0f, noise[k] = Vec3{};
+        if (!valid) continue;
+        uint32_t rank;
+        {
+            const uint32_t tile = tileIds[lp >> 10];
+            uint32_t       tileX, tileY;
+            fp.divTilesX.divmod(tile, tileY, tileX);
+            const uint32_t x0 = tileX * kTileSize, y0 = tileY * kTileSize;
+            rank = fp.tileValidBefore[lp >> 10] + validRankInTile(lp & 1023u, min(kTileSize, fp.width - x0), min(kTileSize, fp.height - y0));
+        }
+        const uint32_t j = rank * fp.numSamples + sampleIdx; // the path's position in the bounce's queue
+        pos[k] = j;
+        const uint32_t frame = fp.firstFrame + (fp.samplePerm ? fp.samplePerm[sampleIdx] : sampleIdx);
+        float          nx, ny;
+        animatedBlueNoiseN(scene.blueNoise, x, y, frame - fp.divSamplesPerPixel.div(frame) * fp.samplesPerPixel, nx, ny);
+
+        const float u = (static_cast<float>(x) + 0.5f) / static_cast<float>(fp.width);
+        const float v = (static_cast<float>(y) + 0.5f) / static_cast<float>(fp.height);
+        const float s = u + nx / static_cast<float>(fp.width);
+        const float t = (1.0f - v) + ny / static_cast<float>(fp.height);
+
+        const float phi = 2.0f * kPi * ny;
+        const float cosPhi = tCos<false>(phi), sinPhi = tSin<false>(phi);
+        const float r = rf_sqrt(nx);
+        const float lensX = fp.camera.lensRadius * (r * cosPhi);
+        const float lensY = fp.camera.lensRadius * (r * sinPhi);
+        const Vec3  origin = fp.camera.origin + (lensX * fp.camera.right + lensY * fp.camera.up);
+        const Vec3  dir = normalize(fp.camera.lowerLeftCorner + s * fp.camera.horizontal + t * fp.camera.vertical - origin);
+        noise[k] = vec3(nx, cosPhi, sinPhi);
+
+        // ---- intersect (kTraceLeafLists' body)
+        const RayPrep   ray = prepareRay(o, dir);
+        const PackedRay pr = packRay(ray);
+        const uint32_t  signs = ray.negX | (ray.negY << 1) | (ray.negZ << 2);
+        const bool      plain = classifyRay(ray) == kRayPlain;
+        ListHit         best{kMiss, 0.0f, 0.0f, tMax};
+        // (the lanes that are here -- the wave's slots that are pixels of the image -- and whether they all hold one pixel's samples)
+        const uint32_t uRank = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(rank)));
+        bool           walks;
+        if (__ballot(rank != uRank) == 0ull)
+        {
+            const uint32_t word = ((ConstU32)lengths)[uRank];
+            walks = (word & kNoPrimaryList) == 0u && plain && ((word >> 8) & 7u) == signs;
+            if ((word & kNoPrimaryList) == 0u) walkLeafList<true>(scene, lists + static_cast<size_t>(uRank) * capacity, word & 0xFFu, o, dir, pr, walks, best);
+        }
+        else
+        {
+            const uint32_t word = lengths[rank];
+            walks = (word & kNoPrimaryList) == 0u && plain && ((word >> 8) & 7u) == signs;
+            if (walks) walkLeafList<false>(scene, lists + static_cast<size_t>(rank) * capacity, word & 0xFFu, o, dir, pr, true, best);
+        }
+        isHit[k] = walks && best.tri != kMiss;
+        isMiss[k] = walks && best.tri == kMiss;
+        handOn[k] = !walks;
+        hitTri[k] = best.tri, hitU[k] = best.u, hitV[k] = best.v;
+        // (a miss: its direction, for kSky; a ray handed on: what kRaygen writes, for kTraceWide and the listed kShade; a hit keeps everything in registers)
+        if (!isHit[k]) store3(ps.rayD + j, dir);
+        if (handOn[k])
+        {
+            queue[j] = slot;
+            store3(ps.noise + j, noise[k]);
+        }
+    }
+    uint32_t handedOn = 0;
+#pragma unroll
+    for (int k = 0; k < kItems; ++k) handedOn += handOn[k] ? 1u : 0u;
+    // kShade's appends: the hits know their position in the next queue before they are shaded; the misses carry queue position and slot
+    blockAppend<kItems>(isHit, slots, hitQueue, hitCount, sScratch, &outPos);
+    blockAppend<kItems>(isMiss, pos, missQueue, missCount, sScratch, nullptr, &slots, missSlots);
+    blockAppend<kItems>(handOn, pos, fallback, fallbackCount, sScratch);
+
+    // ---- shade the hits (kShade<false, false>'s pass 2: one entry at a time)
+    bool needShadow[kItems];
+#pragma unroll
+    for (int k = 0; k < kItems; ++k) needShadow[k] = false;
+    // (one entry at a time, as kShade<false, false>: unrolled -- 113 registers, the per-item arrays in registers instead of LDS -- the group measured 17.1 against 17.3 ms
+    // and the frame the same: profiles/primary_fused)
+#if defined(RF_EXP_FUSED_UNROLL)
+#pragma unroll
+#else
+#pragma unroll 1
+#endif
+    for (int k = 0; k < kItems; ++k)
+    {
+        if (!isHit[k]) continue;
+        const auto inputs = [&](Vec3& throughput, Vec3& nz) {
+            throughput = vec3(1.0f, 1.0f, 1.0f); // wgsl:184
+            nz = noise[k];
+        };
+        const bool need = shadeHit<false, false>(scene, sky, sunBasis, ps, sLut, true, isLastBounce, selfShadow, hitU[k], hitV[k], 0.0f, fetchShadeRecord<false>(scene, hitTri[k], selfShadow),
+                                                 outPos[k], nullptr, inputs, [&] { return slots[k]; });
+#pragma unroll
+        for (int i = 0; i < kItems; ++i) needShadow[i] = i == k ? need : needShadow[i];
+    }
+    if (selfShadow) blockAppend<kItems>(needShadow, outPos, shadowList, shadowListCount, sScratch);
+    // (rare: one atomic per wave that handed rays on)
+    const unsigned long long sum = waveSum(static_cast<unsigned long long>(handedOn));
+    if (__lane_id() == 0 && sum != 0ull) atomicAdd(&counters->primaryFallbackRays, sum);
+}
 } // namespace
 
 namespace kern
 {
 PixelLeafListsKernel pixelLeafListsKernel() { return kPixelLeafLists; }
 TraceLeafListsKernel traceLeafListsKernel() { return kTraceLeafLists; }
+PrimaryFusedKernel   primaryFusedKernel() { return kPrimaryFused; }
 } // namespace kern
 } // namespace rf

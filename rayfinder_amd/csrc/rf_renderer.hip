@@ -801,6 +801,24 @@ struct Renderer::Impl
         rest.flags |= kFlagNoRayCount;
         launchWide(rest, w, WideArgs{io.ps, io.in, io.words.primaryFallbackCount(), io.words.cursorClosest(io.bounce), kTMax, io.persistentGrid, io.blocks});
     }
+    // The same with generation and shading in the list walk's kernel (BatchPlan::primaryFused): kPixelLeafLists, kPrimaryFused -- which fills the queue's count word,
+    // appends its hits to the bounce's output queue, its misses to the miss lists and, with the batch's bounce-1 shade flags, the shadow rays still to trace to the
+    // shadow list --, then kTraceWide over the positions it handed on.  That list lives in the bounce's INPUT throughput stream (12 B per path, nothing in it at
+    // bounce 1: kShade and kSky take throughput 1 there); kShade<false, false, true> works through it in the bounce's shade group (enqueueShadeAndSky).
+    static uint32_t* primaryFusedFallback(const BounceIo& io) { return reinterpret_cast<uint32_t*>(io.ps.thr); }
+    void enqueuePrimaryFused(const BatchPlan& b, const FrameParams& fp, const BouncePlan& p, const BounceIo& io)
+    {
+        hipLaunchKernelGGL(pixelLeafListsKernel(), dim3((fp.pixelsPadded + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, fp, scene, tileIds.ptr, b.primaryListCapacity, primaryLists.ptr,
+                           primaryLengths.ptr);
+        hipLaunchKernelGGL(primaryFusedKernel(), dim3(io.itemBlocks), dim3(kBlock), 0, stream, fp, scene, sky, sunBasis, tileIds.ptr, io.ps, io.in, io.words.queueCount(0), primaryLists.ptr,
+                           primaryLengths.ptr, b.primaryListCapacity, io.out, io.words.queueCount(1), missQueue.ptr, missSlots.ptr, io.words.missCount(1), shadowList.ptr,
+                           io.words.shadowListCount(1), primaryFusedFallback(io), io.words.primaryFallbackCount(), counters.ptr, p.shadeFlags, kTMax);
+        WideScene     w = wide;
+        TraversalPlan rest = p.closest;
+        w.rayList = primaryFusedFallback(io);
+        rest.flags |= kFlagNoRayCount;
+        launchWide(rest, w, WideArgs{io.ps, io.in, io.words.primaryFallbackCount(), io.words.cursorClosest(io.bounce), kTMax, io.persistentGrid, io.blocks});
+    }
     void enqueueClosest(const TraversalPlan& t, const BounceIo& io)
     {
         uint32_t* const countIn = io.words.queueCount(io.bounce - 1);
@@ -813,12 +831,18 @@ struct Renderer::Impl
         else
             launchWide(t, wide, WideArgs{io.ps, io.in, countIn, io.words.cursorClosest(io.bounce), kTMax, io.persistentGrid, io.blocks});
     }
-    void enqueueShadeAndSky(const BouncePlan& p, const BounceIo& io)
+    void enqueueShadeAndSky(const BouncePlan& p, const BounceIo& io, bool fused = false)
     {
         uint32_t* const missCount = io.words.missCount(io.bounce);
+        // (behind kPrimaryFused only the rays it handed on are left to shade: the unsorted kernel over their list, on a grid sized for a list that is short)
+        if (fused)
+            hipLaunchKernelGGL(shadeListedKernel(), cappedGrid(io.itemBlocks, std::max(multiProcessors, 1u) * 32u), dim3(kBlock), 0, stream, scene, sky, sunBasis, io.ps, io.in,
+                               io.words.primaryFallbackCount(), io.out, io.words.queueCount(io.bounce), missQueue.ptr, missSlots.ptr, missCount, shadowList.ptr,
+                               io.words.shadowListCount(io.bounce), p.shadeFlags, p.sortScale, nullptr, primaryFusedFallback(io));
+        else
         hipLaunchKernelGGL(shadeKernel(p.shadeSorted, p.shadeAov), cappedGrid(io.itemBlocks, p.itemGridCap), dim3(kBlock), 0, stream, scene, sky, sunBasis, io.ps, io.in,
                            io.words.queueCount(io.bounce - 1), io.out, io.words.queueCount(io.bounce), missQueue.ptr, missSlots.ptr, missCount, shadowList.ptr,
-                           io.words.shadowListCount(io.bounce), p.shadeFlags, p.sortScale, p.shadeAov ? sAov.ptr : nullptr);
+                           io.words.shadowListCount(io.bounce), p.shadeFlags, p.sortScale, p.shadeAov ? sAov.ptr : nullptr, nullptr);
         // the paths that left the scene at this bounce, while its direction / throughput arrays are intact
         // (its slot comes with the miss list: kSky reads nothing of the bounce's queue -- round 5: reading the slot through the queue position was a third
         // dependent gather, and kShade + kSky went from 19.7 to 15.8 ms per 64 spp without it)
@@ -1005,9 +1029,18 @@ struct Renderer::Impl
         if (fp.samplePerm)
             hipLaunchKernelGGL(samplePermutationKernel(), dim3((numSamples + 255) / 256), dim3(256), 0, stream, firstFrame, fp.samplesPerPixel, numSamples,
                                const_cast<uint32_t*>(fp.samplePerm), const_cast<uint32_t*>(fp.sampleInvPerm));
-        launchTimed(0, [&] {
-            hipLaunchKernelGGL(raygenKernel(options.optTranscendentalsF32), dim3(itemBlocks), dim3(kBlock), 0, stream, fp, scene, tileIds.ptr, io.ps, io.in, words.queueCount(0), counters.ptr);
-        });
+        // (bounce 1 fused: the plan's flag, a bounce-1 launch that takes the lists, and a shade launch that is the plain unsorted kernel)
+        bool fused = false;
+        if (batch.primaryLists && batch.primaryFused && numBounces != 0u)
+        {
+            const BouncePlan first = planBounce(options, in, 1u, batch);
+            fused = first.closest.kernel == kKernelWide && !first.closest.count && !first.shadeSorted && !first.shadeAov;
+        }
+        // (fused: kPrimaryFused generates the rays inside bounce 1's closest-hit group; nothing runs here and ms_raygen stays 0)
+        if (!fused)
+            launchTimed(0, [&] {
+                hipLaunchKernelGGL(raygenKernel(options.optTranscendentalsF32), dim3(itemBlocks), dim3(kBlock), 0, stream, fp, scene, tileIds.ptr, io.ps, io.in, words.queueCount(0), counters.ptr);
+            });
         for (io.bounce = 1; io.bounce <= numBounces; ++io.bounce)
         {
             const BouncePlan plan = planBounce(options, in, io.bounce, batch);
@@ -1015,8 +1048,13 @@ struct Renderer::Impl
             if (plan.firstLook) lookMask |= 1ull << (io.bounce - 1);
             // (the list launches run inside the timing group of the bounce's closest-hit launch: ms_closest, launches_closest and the per-bounce figures keep their meaning)
             const bool lists = io.bounce == 1u && batch.primaryLists && plan.closest.kernel == kKernelWide && !plan.closest.count;
-            launchTimed(1, [&] { if (lists) enqueuePrimaryLists(batch, fp, plan.closest, io); else enqueueClosest(plan.closest, io); }, io.bounce - 1);
-            launchTimed(2, [&] { enqueueShadeAndSky(plan, io); });
+            const bool fusedNow = fused && io.bounce == 1u;
+            launchTimed(1, [&] {
+                if (fusedNow) enqueuePrimaryFused(batch, fp, plan, io);
+                else if (lists) enqueuePrimaryLists(batch, fp, plan.closest, io);
+                else enqueueClosest(plan.closest, io);
+            }, io.bounce - 1);
+            launchTimed(2, [&] { enqueueShadeAndSky(plan, io, fusedNow); });
             launchTimed(3, [&] { enqueueShadow(plan, io); }, io.bounce - 1);
             if (io.bounce == 1u && directSums.on) launchTimed(4, [&] { enqueueDirect(batch, fp, io.ps); });
             std::swap(io.in, io.out);
@@ -2093,7 +2131,7 @@ RenderStats Renderer::stats()
     s.paths = m.primaryRaysHost;
     s.abandonedRays = c.abandonedRays;
     s.scalarRedoRays = c.scalarRedo[0] + c.scalarRedo[1];
-    s.primaryListRays = c.primaryListRays, s.primaryFallbackRays = c.primaryFallbackRays;
+    s.primaryListRays = c.primaryListRays, s.primaryFallbackRays = c.primaryFallbackRays, s.primaryFusedRays = c.primaryFusedRays;
     if (std::getenv("RF_DEBUG_COUNTERS"))
         std::fprintf(stderr, "[rf] rays redone by the scalar traversal: closest %llu of %llu, shadow %llu of %llu\n", c.scalarRedo[0], c.closestRays, c.scalarRedo[1], c.shadowRays);
 #if defined(RF_EXP_PHASE)

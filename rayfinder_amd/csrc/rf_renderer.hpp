@@ -76,6 +76,7 @@ struct RenderStats
     uint64_t scalarRedoRays = 0; // rays redone by the reference-ordered scalar traversal (irregular rays, LDS stack overflow); every build
     uint64_t primaryListRays = 0;     // bounce-1 rays of the batches whose primary launch ran over the per-pixel leaf lists (rf_primary_lists.hip); 0: every batch kept the kTraceWide launch
     uint64_t primaryFallbackRays = 0; // of those: handed on to the kTraceWide launch (a pixel without a list, a ray that is not class A)
+    uint64_t primaryFusedRays = 0;    // ... of the batches that generated, intersected and shaded them in one kernel (kPrimaryFused); 0: every batch kept kRaygen, kTraceLeafLists and kShade
     uint64_t shadowRaysSelfAnswered = 0; // of shadowRays: stopped by the triangle they start on, found by kShade's own test (kShadeSelfShadow); never queued for an any-hit launch
     uint64_t shadowRaysHintAnswered = 0; // of shadowRays: answered by kShadowHint at the leaf the occluder grid named (never entered the traversal); every build
     // hipEvent-timed kernel time (ms) and launch counts, per kernel class, while timing is enabled
