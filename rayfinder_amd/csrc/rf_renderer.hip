@@ -1,6 +1,7 @@
 // rf_renderer.hip -- wavefront path tracer for MI355X (gfx950): the host driver (the kernels live in rf_trace.hip, rf_shade.hip and rf_sums.hip, what the
 // units share in rf_kernels.hpp; the scene's device layouts are built and packed by host-only code, rf_scene_pack.cpp and rf_wide_build.cpp, and uploaded here; which
-// kernel runs with which parameters is planned by host-only code too, rf_launch_policy.cpp, and enqueued here).
+// kernel runs with which parameters is planned by host-only code too, rf_launch_policy.cpp, and enqueued here; the accumulation's books -- the counts, the switches, the
+// snapshots' validity -- and every refusal that rests on them are host-only code as well, rf_books.cpp: this unit keeps the sums' storage and enqueues).
 //
 // The reference traces one full path per fragment-shader invocation
 // (src/pt/reference_path_tracer.wgsl:34-64,180-234).  Here the same per-path arithmetic is cut
@@ -23,6 +24,7 @@
 // Kernel grids are sized for the worst case (all paths alive) and read the live count from
 // device memory, so a whole batch is enqueued without any host round trip.
 #include "rayfinder_amd.h"
+#include "rf_books.hpp"
 #include "rf_denoise.hpp"
 #include "rf_features.hpp"
 #include "rf_kernels.hpp"
@@ -117,47 +119,30 @@ void untileHostTexels(const void* compact, const uint32_t* tileIds, uint32_t num
     }
 }
 
-// One sum over the samples of an accumulation, and its books: the image (always on; its buffer is the handle's own or a bound one, Impl::image), the first-hit
-// AOV sums (two buffers), the radiance second moments (one).  All compact tile-major float4 buffers of the shard, summed in sample order.
-// What the driver relies on (Impl::restartAccumulation, Impl::clearStaleSums and Impl::step are the only writers):
-//   * dirty is raised only together with samples = 0, and cleared only by the zeroing in front of the next sample: dirty implies samples == 0;
-//   * the image's dirty flag is raised only by restartAccumulation, which sets accumulated = 0 and restarts every channel: a dirty image implies
-//     accumulated == 0 and every channel dirty.  (A read may zero a dirty image and clear the flag before any sample: accumulated == 0 does not imply dirty);
-//   * hence covers(accumulated) with accumulated != 0 says that the channel was on for every sample of the accumulation, whatever the image's flag says.
-struct SumChannel
-{
-    bool                 on = false;
-    bool                 dirty = true; // restarted: to be zeroed before the next sample
-    uint32_t             samples = 0;  // samples summed since it was last restarted
-    DeviceBuffer<float4> buffers[2];   // the AOVs: {albedo.rgb, coverage}, {normal.xyz, depth}; the moments: [0]; the image: none (Impl::image)
-    uint32_t             numBuffers = 0;
-    uint32_t             planes = 1;   // float4 per pixel in each buffer, plane after plane (the bucket sums: K)
+using Books = AccumulationBooks;
+static_assert(Renderer::kAovTileCounts == Books::kWordTileCounts && Renderer::kDirectTileCounts == Books::kWordTileCounts && Renderer::kBucketsTileCounts == Books::kWordTileCounts &&
+              Renderer::kBucketsShardTileCounts == Books::kWordShardTileCounts && kMaxBuckets == Books::kMaxBuckets);
 
-    SumChannel(bool on_, uint32_t numBuffers_) : on(on_), numBuffers(numBuffers_) {}
-    // the sums start again: zeroed before the next sample, sized for the shard then
-    void restart()
-    {
-        samples = 0;
-        dirty = true;
-    }
+// The storage of one family of sums (its books: AccumulationBooks::Sums): compact tile-major float4 buffers of the shard -- the AOVs: {albedo.rgb, coverage}, {normal.xyz,
+// depth}; the moments, the direct sums and the bucket planes: [0]; the image: none (Impl::image, the handle's own buffer or a bound one)
+struct SumStorage
+{
+    uint32_t             numBuffers = 0;
+    DeviceBuffer<float4> buffers[2];
+
     void release()
     {
         for (auto& b : buffers) b.release();
     }
-    bool covers(uint32_t accumulated) const { return !dirty && samples == accumulated; }
-    bool empty() const { return !on || dirty || samples == 0u; }
-    // before the first sample after a restart: room for the shard (the stream is waited for before a smaller buffer is freed), then zeros
-    void zeroIfStale(hipStream_t stream, uint64_t pixelsPadded)
+    // before the first sample after a restart: room for `texels` (the stream is waited for before a smaller buffer is freed), then zeros
+    void zero(hipStream_t stream, uint64_t texels)
     {
-        if (!on || !dirty) return;
-        const uint64_t texels = pixelsPadded * planes;
         if (numBuffers != 0u && buffers[0].count < texels)
         {
             RF_HIP(hipStreamSynchronize(stream)); // (a smaller buffer may still be read by the last batch or estimate)
             for (uint32_t i = 0; i < numBuffers; ++i) buffers[i].alloc(texels);
         }
         for (uint32_t i = 0; i < numBuffers; ++i) RF_HIP(hipMemsetAsync(buffers[i].ptr, 0, texels * sizeof(float4), stream));
-        dirty = false;
     }
 };
 
@@ -185,8 +170,8 @@ struct Renderer::Impl
 
     void updateSunBasis() { pixarOnb(vec3(sky.sunDirection[0], sky.sunDirection[1], sky.sunDirection[2]), sunBasis.u, sunBasis.v); }
     uint32_t         maxWidth = 0, maxHeight = 0;
-    uint32_t         frameCount = 0, accumulated = 0;
-    uint32_t         rank = 0, worldSize = 1;
+    // the frame counter, the accumulated count, the shard, the per-tile counts, every family's switch and count, both snapshots' validity: rf_books.hpp
+    Books            books;
     // what the scene packing found (rf_scene_pack.hpp): the launch policy's facts, and a checkpoint's scene guard (checkpointBooks) -- the counts of BVH nodes,
     // triangles, textures and texels the handle was created with, and the root node's box
     SceneFacts       facts;
@@ -198,59 +183,25 @@ struct Renderer::Impl
     DeviceBuffer<float4>    ownedImage;
     float4*                 image = nullptr; // compact tile-major accumulation buffer
     uint64_t                imageBytes = 0;
-    // The sums (SumChannel).  The image restarts on the events of restartAccumulation; the other two on those and whenever their switch changes.
-    SumChannel              imageSums{true, 0};
-    // first-hit AOVs (rf_renderer_set_aovs; off by default: nothing is allocated or launched then)
-    SumChannel              aovSums{false, 2};
-    uint32_t                aovFlags = 0; // the flags as set (rf_renderer_set_aovs): kAovFirstHit says which AOVs are kept (aovSums.on), kAovTileCounts how
-    bool                    aovTileCounts() const { return (aovFlags & kAovTileCounts) != 0u; }
-    // radiance second moments (rf_renderer_set_moments; off by default: nothing is allocated or launched then): {sum r r per channel, 0}
-    SumChannel              momentSums{false, 1};
-    float4*                 aovAlbedoCoverage() const { return aovSums.buffers[0].ptr; }
-    float4*                 aovNormalDepth() const { return aovSums.buffers[1].ptr; }
-    float4*                 moments() const { return momentSums.buffers[0].ptr; }
-    // direct radiance sums (rf_renderer_set_direct; off by default: nothing is allocated or launched then): D = the sum of each sample's radiance as it stands after
-    // bounce 1 (the primary miss's sky term, or the first hit's sun term times its visibility), in the image's layout and the image's order
-    SumChannel              directSums{false, 1};
-    uint32_t                directFlags = 0; // the word as set (rf_renderer_set_direct): kDirectOn says that D is kept (directSums.on), kDirectTileCounts how
-    bool                    directTileCounts() const { return (directFlags & kDirectTileCounts) != 0u; }
-    float4*                 direct() const { return directSums.buffers[0].ptr; }
-    // bucket sums (rf_renderer_set_buckets; off by default: nothing is allocated or launched then): bucketSums.planes = K planes of the shard's tiles x 1024 float4 each
-    // in one buffer, plane b = the radiance sum over the samples of ordinal b mod K (under render_adaptive, bucketTileCounts: of the TILE's samples -- every active tile
-    // holds bucketSums.samples of them); the robust mean's buffers and the snapshot they hold -- valid until the bucket sums are restarted
-    SumChannel              bucketSums{false, 1};
-    bool                    bucketTileCounts = false; // kBucketsTileCounts as set: render_adaptive runs with the buckets on and the planes follow the per-tile counts
-    bool                    bucketShardTileCounts = false; // kBucketsShardTileCounts as set: so under a tile shard (rf_comm_render_adaptive), and through the frame gather
-    float4*                 bucketPlanes() const { return bucketSums.buffers[0].ptr; }
+    // The sums' storage, by family (off: nothing is allocated or launched).  The first-hit AOVs (rf_renderer_set_aovs); the radiance second moments
+    // (rf_renderer_set_moments): {sum r r per channel, 0}; the direct sums (rf_renderer_set_direct): D = the sum of each sample's radiance as it stands after bounce 1 (the
+    // primary miss's sky term, or the first hit's sun term times its visibility), in the image's layout and the image's order; the bucket sums (rf_renderer_set_buckets):
+    // K planes of the shard's tiles x 1024 float4 each in one buffer, plane b = the radiance sum over the samples of ordinal b mod K (under render_adaptive with the
+    // tile-count bit: of the TILE's samples -- every active tile holds the family's count of them)
+    SumStorage              storage[Books::kFamilies] = {{0}, {2}, {1}, {1}, {1}};
+    float4*                 aovAlbedoCoverage() const { return storage[Books::kAovs].buffers[0].ptr; }
+    float4*                 aovNormalDepth() const { return storage[Books::kAovs].buffers[1].ptr; }
+    float4*                 moments() const { return storage[Books::kMoments].buffers[0].ptr; }
+    float4*                 direct() const { return storage[Books::kDirect].buffers[0].ptr; }
+    float4*                 bucketPlanes() const { return storage[Books::kBuckets].buffers[0].ptr; }
     size_t                  bucketStride() const { return tiles.size() * 1024; }
     RobustWork              robustWork;
     DeviceBuffer<float4>    robustShard; // enqueueShardRobustMean's {M.rgb, float(c)} of the shard's pixels, shard-compact tile-major: what the frame gather sends as plane 4
-    bool                    robustValid = false;
-    uint32_t                robustSamples = 0;
-    // the denoiser (rf_renderer_denoise): its work buffers, allocated by the first denoise, and the snapshot they hold -- valid until the AOV sums are restarted
+    // the denoiser (rf_renderer_denoise): its work buffers, allocated by the first denoise, and the snapshot they hold (valid: the books)
     DenoiseWork             denoiseWork;
-    bool                    denoisedValid = false;
-    uint32_t                denoisedSamples = 0;
     NoiseWork               noiseWork; // the estimate's device buffers, allocated by the first rf_renderer_noise_estimate
-    // tile-adaptive sampling (rf_renderer_render_adaptive).  tileSamples[t], t in the frame's tile numbering, is the sample count of tile t; EMPTY = the uniform
-    // state: every tile holds `accumulated` samples (the only state a handle that never called render_adaptive is ever in).  Non-empty: the counts differ, `accumulated`
-    // is the leading count L, and the tiles still at L are the only ones a later render_adaptive samples.  Cleared by restartAccumulation.
-    std::vector<uint32_t>   tileSamples;
-    DeviceBuffer<uint32_t>  tileSamplesDevice; // the counts for the per-tile reads (mean, tonemap, estimate), uploaded by them
+    DeviceBuffer<uint32_t>  tileSamplesDevice; // the per-tile counts (the books') for the per-tile reads (mean, tonemap, estimate), uploaded by them
     DeviceBuffer<float4>    meanImage;         // rf_renderer_read_mean / the non-uniform rf_renderer_read_tonemapped: compact tile-major, allocated by the first read
-
-    // Under a tile shard (rf_comm_render_adaptive) the FRAME's largest and smallest tile count over all ranks, as the call's all-reduces left them on every rank:
-    // while they differ the frame is non-uniform, on a rank whose own tiles share one count too.  Both 0: no such call since the accumulation was restarted.
-    uint32_t                frameLeadingSamples = 0, frameMinTileSamples = 0;
-
-    bool nonUniform() const { return !tileSamples.empty(); } // this handle's own tiles: which form its per-tile reads take
-    bool frameNonUniform() const { return frameLeadingSamples != frameMinTileSamples; }
-    void requireUniform(const char* what, const char* unless = "") const
-    {
-        if (nonUniform() || frameNonUniform())
-            throw std::invalid_argument(std::string(what) + ": the tiles hold different sample counts after rf_renderer_render_adaptive" + unless +
-                                        " (continue with render_adaptive, or restart the accumulation with rf_renderer_set_render_parameters)");
-    }
 
     uint64_t                validPixels = 0;     // pixels of this rank's tiles that lie inside the frame
     unsigned long long      primaryRaysHost = 0; // samples traced x validPixels since the last resetStats()
@@ -324,7 +275,7 @@ struct Renderer::Impl
     static constexpr uint64_t kBytesPerPath = 8 * sizeof(P3) + 2 * sizeof(float4) + 5 * sizeof(uint32_t);
     // ... plus the 32-byte AOV record while the first-hit AOVs are on
     static constexpr uint64_t kAovBytesPerPath = 2 * sizeof(float4);
-    uint64_t bytesPerPath() const { return kBytesPerPath + (aovSums.on ? kAovBytesPerPath : 0u); }
+    uint64_t bytesPerPath() const { return kBytesPerPath + (books.on(Books::kAovs) ? kAovBytesPerPath : 0u); }
     uint64_t pathStateBytes() const { return allocatedPaths * kBytesPerPath + sAov.count * sizeof(float4); }
     // the per-pixel leaf lists of bounce 1: capacity + 1 words per valid pixel of a batch (1080p at the default capacity of 64: 539 MB)
     uint64_t primaryListBytes() const { return (primaryLists.count + primaryLengths.count) * sizeof(uint32_t); }
@@ -337,13 +288,14 @@ struct Renderer::Impl
         for (int layout = kLayoutBinary; layout <= kLayoutOct; ++layout) in.layouts |= present[layout] != nullptr ? 1u << layout : 0u;
         in.rootLo = wide.rootLo, in.rootHi = wide.rootHi, in.originBound = wide.originBound;
         in.camera = params.camera, in.numBounces = params.samplingParams.numBounces;
-        in.aovs = aovSums.on, in.moments = momentSums.on, in.buckets = bucketSums.on, in.bucketPlanes = bucketSums.planes, in.bucketSamples = bucketSums.samples;
+        in.aovs = books.on(Books::kAovs), in.moments = books.on(Books::kMoments), in.buckets = books.on(Books::kBuckets);
+        in.bucketPlanes = books.sums(Books::kBuckets).planes, in.bucketSamples = books.sums(Books::kBuckets).samples;
         in.numTiles = static_cast<uint32_t>(tiles.size()), in.validPixels = validPixels;
         if (active) in.active = *active;
         return in;
     }
     // the path state holds a batch of `paths` (the AOV records included while the AOVs are on)
-    bool pathStateHolds(uint64_t paths) const { return paths <= allocatedPaths && (!aovSums.on || sAov.count >= 2 * paths); }
+    bool pathStateHolds(uint64_t paths) const { return paths <= allocatedPaths && (!books.on(Books::kAovs) || sAov.count >= 2 * paths); }
 
     void releasePathState()
     {
@@ -378,7 +330,7 @@ struct Renderer::Impl
         const bool ok = tryAlloc(sRayO, paths) && tryAlloc(sRayD, paths) && tryAlloc(sRayD2, paths) && tryAlloc(sThr, paths) && tryAlloc(sThr2, paths) &&
                         tryAlloc(sRad, paths) && tryAlloc(sHit, paths) && tryAlloc(sPending, paths) && tryAlloc(sNoise, paths) && tryAlloc(sNoise2, paths) &&
                         tryAlloc(queueA, paths) && tryAlloc(queueB, paths) && tryAlloc(missQueue, paths) && tryAlloc(missSlots, paths) && tryAlloc(shadowList, paths) &&
-                        (!aovSums.on || tryAlloc(sAov, 2 * paths));
+                        (!books.on(Books::kAovs) || tryAlloc(sAov, 2 * paths));
         if (!ok)
         {
             releasePathState();
@@ -403,7 +355,8 @@ struct Renderer::Impl
 
     void configureShard()
     {
-        tiles = tilesForRank(params.width, params.height, rank, worldSize);
+        tiles = tilesForRank(params.width, params.height, books.rank(), books.worldSize());
+        books.setShardTiles(static_cast<uint32_t>(tiles.size()));
         tileIds.alloc(2 * tiles.size());
         const uint64_t pixelsPadded = static_cast<uint64_t>(tiles.size()) * 1024;
         const TileGrid::Prefix valid = grid().validPrefix(tiles);
@@ -420,40 +373,9 @@ struct Renderer::Impl
             throw std::runtime_error("bound accumulation buffer is too small for this shard");
         }
         if (image == ownedImage.ptr) imageBytes = pixelsPadded * sizeof(float4);
-        restartAccumulation();
+        books.restartAccumulation();
     }
 
-    // A new accumulation (new parameters, another shard, another accumulation buffer): no sample, every tile at the same count, every sum to be zeroed before the
-    // next sample, no denoised snapshot.  The only place that does this.
-    void restartAccumulation()
-    {
-        accumulated = 0;
-        tileSamples.clear();
-        frameLeadingSamples = frameMinTileSamples = 0;
-        imageSums.restart();
-        restartAovs();
-        momentSums.restart();
-        restartBuckets();
-        restartDirect();
-    }
-    // (also when the switch changes: a split-denoised snapshot was filtered from these sums)
-    void restartDirect()
-    {
-        directSums.restart();
-        denoisedValid = false;
-    }
-    // (also when K changes: the snapshot was combined from these sums)
-    void restartBuckets()
-    {
-        bucketSums.restart();
-        robustValid = false;
-    }
-    // (also when the AOV switch changes: the snapshot was filtered with these sums as guides)
-    void restartAovs()
-    {
-        aovSums.restart();
-        denoisedValid = false;
-    }
     // Zero `bytes` of the image (on the stream) if no sample has gone into it since the accumulation was restarted.  The callers' byte counts, kept as they were:
     //   clearStaleSums (render, render_adaptive)    the shard's tiles x 1024 x 16
     //   meanOnDevice, readTonemapped                the same, from the 32-bit pixel count these two launch their kernels with
@@ -461,9 +383,9 @@ struct Renderer::Impl
     // (configureShard and bindAccumulationBuffer refuse a bound buffer smaller than the shard, so the first two stay inside it as well)
     void zeroImageIfStale(uint64_t bytes)
     {
-        if (!imageSums.dirty) return;
+        if (!books.stale(Books::kImage)) return;
         RF_HIP(hipMemsetAsync(image, 0, bytes, stream)); // wgsl:47-49
-        imageSums.dirty = false;
+        books.zeroed(Books::kImage);
     }
     TileGrid grid() const { return TileGrid(params.width, params.height); }
     // row-major width * height * 4 floats <- a compact tile-major buffer of the shard; nullptr (nothing summed yet): all zeros, without a device copy
@@ -674,10 +596,13 @@ struct Renderer::Impl
     void clearStaleSums(uint64_t pixelsPadded)
     {
         zeroImageIfStale(pixelsPadded * sizeof(float4));
-        aovSums.zeroIfStale(stream, pixelsPadded);
-        momentSums.zeroIfStale(stream, pixelsPadded);
-        bucketSums.zeroIfStale(stream, pixelsPadded);
-        directSums.zeroIfStale(stream, pixelsPadded);
+        for (uint32_t i = Books::kAovs; i < Books::kFamilies; ++i)
+        {
+            const Books::Family f = static_cast<Books::Family>(i);
+            if (!books.stale(f)) continue;
+            storage[f].zero(stream, pixelsPadded * books.sums(f).planes);
+            books.zeroed(f);
+        }
     }
 
     // Samples per batch for `todo` samples of `pixelsPadded` path slots per sample (the shard's tiles, or the active tiles of render_adaptive), with the path state
@@ -727,6 +652,7 @@ struct Renderer::Impl
     const uint32_t* uploadTileSamples()
     {
         RF_HIP(hipStreamSynchronize(stream));
+        const std::vector<uint32_t>& tileSamples = books.tileSamples();
         if (tileSamplesDevice.count < tileSamples.size()) tileSamplesDevice.alloc(tileSamples.size());
         RF_HIP(hipMemcpy(tileSamplesDevice.ptr, tileSamples.data(), tileSamples.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         return tileSamplesDevice.ptr;
@@ -738,8 +664,8 @@ struct Renderer::Impl
         RF_HIP(hipStreamSynchronize(stream));
         if (meanImage.count < n) meanImage.alloc(n);
         zeroImageIfStale(static_cast<size_t>(n) * sizeof(float4));
-        const uint32_t* counts = nonUniform() ? uploadTileSamples() : nullptr;
-        hipLaunchKernelGGL(tileMeanKernel(), dim3((n + 255) / 256), dim3(256), 0, stream, static_cast<const float4*>(image), counts, accumulated, n, meanImage.ptr);
+        const uint32_t* counts = books.nonUniform() ? uploadTileSamples() : nullptr;
+        hipLaunchKernelGGL(tileMeanKernel(), dim3((n + 255) / 256), dim3(256), 0, stream, static_cast<const float4*>(image), counts, books.accumulated(), n, meanImage.ptr);
         RF_HIP(hipGetLastError());
         RF_HIP(hipStreamSynchronize(stream));
         return meanImage.ptr;
@@ -762,14 +688,9 @@ struct Renderer::Impl
     uint32_t step(uint32_t todo, uint64_t pixelsPadded, const ActiveTiles* active)
     {
         const uint32_t n = batchSamples(todo, pixelsPadded);
-        traceBatch(frameCount, n, active);
+        traceBatch(books.frameCount(), n, active);
         hostStats.batchSamplesUsed = n, hostStats.batchPathsUsed = static_cast<uint64_t>(n) * pixelsPadded, ++hostStats.batchesTraced;
-        frameCount += n;
-        accumulated += n;
-        if (aovSums.on) aovSums.samples += n;
-        if (momentSums.on) momentSums.samples += n;
-        if (bucketSums.on) bucketSums.samples += n;
-        if (directSums.on) directSums.samples += n;
+        books.recordStep(n);
         return n;
     }
 
@@ -1056,7 +977,7 @@ struct Renderer::Impl
             }, io.bounce - 1);
             launchTimed(2, [&] { enqueueShadeAndSky(plan, io, fusedNow); });
             launchTimed(3, [&] { enqueueShadow(plan, io); }, io.bounce - 1);
-            if (io.bounce == 1u && directSums.on) launchTimed(4, [&] { enqueueDirect(batch, fp, io.ps); });
+            if (io.bounce == 1u && books.on(Books::kDirect)) launchTimed(4, [&] { enqueueDirect(batch, fp, io.ps); });
             std::swap(io.in, io.out);
             std::swap(io.ps.rayD, io.ps.rayDOut);
             std::swap(io.ps.thr, io.ps.thrOut);
@@ -1184,6 +1105,7 @@ Renderer::Renderer(const RendererDescriptor& desc, const SceneView& sceneView) :
     m.params = desc.renderParams;
     if (alignedSkyState(m.params.sky, m.sky) != SkyResult::Success) throw std::runtime_error("sky parameters out of range");
     m.updateSunBasis();
+    m.books.setSampleCap(m.params.samplingParams.numSamplesPerPixel);
     m.configureShard();
 }
 
@@ -1221,19 +1143,18 @@ void Renderer::setRenderParameters(const RenderParameters& p)
     m.params = p;
     m.sky = sky;
     m.updateSunBasis();
-    m.restartAccumulation();
+    m.books.setSampleCap(p.samplingParams.numSamplesPerPixel);
+    m.books.restartAccumulation();
     if (resized) m.configureShard();
 }
 
 void Renderer::setTileShard(uint32_t rank, uint32_t worldSize)
 {
     Impl& m = *mImpl;
-    if (worldSize == 0 || rank >= worldSize) throw std::runtime_error("invalid tile shard");
-    m.requireUniform("rf_renderer_set_tile_shard");
+    m.books.refuseSetTileShard(rank, worldSize);
     RF_HIP(hipSetDevice(m.device));
     RF_HIP(hipStreamSynchronize(m.stream));
-    m.rank = rank;
-    m.worldSize = worldSize;
+    m.books.setShard(rank, worldSize);
     m.configureShard();
 }
 
@@ -1242,22 +1163,16 @@ std::span<const uint32_t> Renderer::shardTiles() const { return mImpl->tiles; }
 void Renderer::render(uint32_t numFrames)
 {
     Impl& m = *mImpl;
-    m.requireUniform("rf_renderer_render");
+    m.books.refuseRender();
     RF_HIP(hipSetDevice(m.device));
-    const uint32_t spp = m.params.samplingParams.numSamplesPerPixel;
     const uint64_t pixelsPadded = static_cast<uint64_t>(m.tiles.size()) * 1024;
     // Each reference render() call: frame = frameCount++, then one sample if accumulated < spp
-    // (reference_path_tracer.cpp:577-591, wgsl:47-57).  Calls past spp only advance frameCount.
+    // (reference_path_tracer.cpp:577-591, wgsl:47-57).  Calls past spp only advance frameCount (AccumulationBooks::framesToTrace).
     uint32_t remaining = numFrames;
-    while (remaining > 0)
+    while (const uint32_t todo = m.books.framesToTrace(remaining))
     {
-        if (m.accumulated >= spp || pixelsPadded == 0)
-        {
-            m.frameCount += remaining;
-            break;
-        }
         m.clearStaleSums(pixelsPadded);
-        remaining -= m.step(std::min(remaining, spp - m.accumulated), pixelsPadded, nullptr);
+        remaining -= m.step(todo, pixelsPadded, nullptr);
     }
 }
 
@@ -1274,14 +1189,14 @@ float Renderer::averageRenderpassDurationMs() const
 
 float Renderer::renderProgressPercentage() const
 {
-    return 100.0f * static_cast<float>(mImpl->accumulated) / static_cast<float>(mImpl->params.samplingParams.numSamplesPerPixel);
+    return 100.0f * static_cast<float>(mImpl->books.accumulated()) / static_cast<float>(mImpl->params.samplingParams.numSamplesPerPixel);
 }
 
-uint32_t Renderer::accumulatedSampleCount() const { return mImpl->accumulated; }
+uint32_t Renderer::accumulatedSampleCount() const { return mImpl->books.accumulated(); }
 uint32_t Renderer::width() const { return mImpl->params.width; }
 uint32_t Renderer::height() const { return mImpl->params.height; }
-uint32_t Renderer::shardRank() const { return mImpl->rank; }
-uint32_t Renderer::shardWorldSize() const { return mImpl->worldSize; }
+uint32_t Renderer::shardRank() const { return mImpl->books.rank(); }
+uint32_t Renderer::shardWorldSize() const { return mImpl->books.worldSize(); }
 int      Renderer::deviceOrdinal() const { return mImpl->device; }
 float    Renderer::exposure() const { return mImpl->params.exposure; }
 void*    Renderer::streamHandle() const { return mImpl->stream; }
@@ -1297,156 +1212,116 @@ void Renderer::readAccumulation(float* dst)
 {
     Impl& m = *mImpl;
     synchronize();
-    m.readCompact(m.imageSums.dirty ? nullptr : m.image, dst);
+    m.readCompact(m.books.stale(Books::kImage) ? nullptr : m.image, dst);
 }
 
 void Renderer::setAovs(uint32_t flags)
 {
     Impl& m = *mImpl;
-    if (flags == m.aovFlags) return;
+    // any change of the value restarts the sums, kAovFirstHit <-> kAovFirstHit | kAovTileCounts included (the buffers stay: they are the same two either way)
+    const Books::Change change = m.books.setAovs(flags);
+    if (change == Books::Change::Unchanged) return;
     RF_HIP(hipSetDevice(m.device));
     RF_HIP(hipStreamSynchronize(m.stream)); // (a batch in flight may still write the records or the sums)
-    // any change of the value restarts the sums, kAovFirstHit <-> kAovFirstHit | kAovTileCounts included (the buffers stay: they are the same two either way)
-    m.aovFlags = flags;
-    m.aovSums.on = (flags & kAovFirstHit) != 0u;
-    m.restartAovs();
-    if (!m.aovSums.on)
+    if (change == Books::Change::RestartedOff)
     {
         // off: nothing of the AOVs stays allocated (the path state keeps its depth; the next batch that needs the records allocates them again)
         m.sAov.release();
-        m.aovSums.release();
+        m.storage[Books::kAovs].release();
     }
 }
 
-uint32_t Renderer::aovFlags() const { return mImpl->aovFlags; }
+uint32_t Renderer::aovFlags() const { return mImpl->books.sums(Books::kAovs).word; }
 
 void Renderer::readAovs(float* albedoCoverage, float* normalDepth, uint32_t* sampleCount)
 {
     Impl& m = *mImpl;
     synchronize();
-    const bool empty = m.aovSums.empty();
+    const bool empty = m.books.empty(Books::kAovs);
     if (albedoCoverage) m.readCompact(empty ? nullptr : m.aovAlbedoCoverage(), albedoCoverage);
     if (normalDepth) m.readCompact(empty ? nullptr : m.aovNormalDepth(), normalDepth);
-    if (sampleCount) *sampleCount = empty ? 0u : m.aovSums.samples;
+    if (sampleCount) *sampleCount = m.books.readCount(Books::kAovs);
 }
 
 void Renderer::denoise(const DenoiseParameters& params)
 {
     Impl& m = *mImpl;
-    // the non-uniform state: prep divides each pixel by its tile's own count, which the AOV sums must have been kept for (kAovTileCounts, from the first sample on)
-    const bool perTile = m.nonUniform();
-    if (perTile && !(m.aovSums.on && m.aovTileCounts() && m.aovSums.covers(m.accumulated)))
-        m.requireUniform("rf_renderer_denoise", ", and the first-hit AOVs were not kept with per-tile counts for the whole accumulation: set RF_AOV_FIRST_HIT | RF_AOV_TILE_COUNTS "
-                                                "(rf_renderer_set_aovs) before the first sample and rf_renderer_denoise runs in this state");
-    if (!m.aovSums.on) throw std::invalid_argument("denoise needs the first-hit AOVs: turn them on (rf_renderer_set_aovs) before the first sample");
-    if (m.worldSize != 1u) throw std::invalid_argument("denoise needs the whole frame: a tile shard is set (use rf_denoise_images on the gathered sums)");
-    if (m.accumulated == 0u) throw std::invalid_argument("denoise: no sample has been accumulated");
-    if (!m.aovSums.covers(m.accumulated))
-        throw std::invalid_argument("denoise: the AOV sample count (" + std::to_string(m.aovSums.samples) + ") differs from the accumulated sample count (" +
-                                    std::to_string(m.accumulated) + "): turn the AOVs on before the first sample");
+    m.books.refuseDenoise();
     RF_HIP(hipSetDevice(m.device));
-    // (the snapshot's sample count is the leading count)
-    enqueueDenoise(m.stream, m.denoiseWork, m.image, m.aovAlbedoCoverage(), m.aovNormalDepth(), m.params.width, m.params.height, m.grid().tilesX, m.accumulated, params,
-                   m.params.exposure, perTile ? m.uploadTileSamples() : nullptr);
-    m.denoisedValid = true;
-    m.denoisedSamples = m.accumulated;
+    // (the non-uniform state: prep divides each pixel by its tile's own count)
+    enqueueDenoise(m.stream, m.denoiseWork, m.image, m.aovAlbedoCoverage(), m.aovNormalDepth(), m.params.width, m.params.height, m.grid().tilesX, m.books.accumulated(), params,
+                   m.params.exposure, m.books.nonUniform() ? m.uploadTileSamples() : nullptr);
+    m.books.noteDenoised();
 }
 
 void Renderer::readDenoised(float* rgba, uint32_t* bgra8, uint32_t* sampleCount)
 {
     Impl& m = *mImpl;
-    if (!m.denoisedValid) throw std::invalid_argument("no denoised image: call rf_renderer_denoise first (the image is dropped when the accumulation or the AOVs are cleared)");
+    m.books.refuseReadDenoised();
     synchronize();
     const size_t n = static_cast<size_t>(m.params.width) * m.params.height;
     if (rgba) RF_HIP(hipMemcpy(rgba, m.denoiseWork.out.ptr, n * sizeof(float4), hipMemcpyDeviceToHost));
     if (bgra8) RF_HIP(hipMemcpy(bgra8, m.denoiseWork.bgra.ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (sampleCount) *sampleCount = m.denoisedSamples;
+    if (sampleCount) *sampleCount = m.books.denoisedSamples();
 }
 
 void Renderer::setMoments(bool enabled)
 {
     Impl& m = *mImpl;
-    if (enabled == m.momentSums.on) return;
+    const Books::Change change = m.books.setMoments(enabled);
+    if (change == Books::Change::Unchanged) return;
     RF_HIP(hipSetDevice(m.device));
     RF_HIP(hipStreamSynchronize(m.stream)); // (a batch in flight may still write the sums)
-    m.momentSums.on = enabled;
-    m.momentSums.restart();
-    if (!enabled)
+    if (change == Books::Change::RestartedOff)
     {
         // off: nothing of the moments stays allocated
-        m.momentSums.release();
+        m.storage[Books::kMoments].release();
         m.noiseWork.release();
     }
 }
 
-bool Renderer::momentsEnabled() const { return mImpl->momentSums.on; }
+bool Renderer::momentsEnabled() const { return mImpl->books.on(Books::kMoments); }
 
 void Renderer::readMoments(float* sumSq, uint32_t* sampleCount)
 {
     Impl& m = *mImpl;
     synchronize();
-    const bool empty = m.momentSums.empty();
-    if (sumSq) m.readCompact(empty ? nullptr : m.moments(), sumSq);
-    if (sampleCount) *sampleCount = empty ? 0u : m.momentSums.samples;
+    if (sumSq) m.readCompact(m.books.empty(Books::kMoments) ? nullptr : m.moments(), sumSq);
+    if (sampleCount) *sampleCount = m.books.readCount(Books::kMoments);
 }
 
 void Renderer::setDirect(uint32_t flags)
 {
     Impl& m = *mImpl;
-    if ((flags & ~(kDirectOn | kDirectTileCounts)) != 0u || flags == kDirectTileCounts)
-        throw std::invalid_argument("set_direct: the word must be 0 (off), 1 (on) or 1 | RF_DIRECT_TILE_COUNTS (the bit says how D is kept: valid only together with 1)");
-    const bool enabled = (flags & kDirectOn) != 0u;
-    // (with the bit too: D must hold every tile's samples from the tile's first one on, and the tiles below the leading count get no more)
-    if (enabled) m.requireUniform("rf_renderer_set_direct", ": the direct sums keep ONE sample count for the frame");
-    if (flags == m.directFlags) return;
+    // any change of the value restarts the sums, kDirectOn <-> kDirectOn | kDirectTileCounts included (the buffer stays: it is the same one either way)
+    const Books::Change change = m.books.setDirect(flags);
+    if (change == Books::Change::Unchanged) return;
     RF_HIP(hipSetDevice(m.device));
     RF_HIP(hipStreamSynchronize(m.stream)); // (a batch in flight may still write the sums)
-    // any change of the value restarts the sums, kDirectOn <-> kDirectOn | kDirectTileCounts included (the buffer stays: it is the same one either way)
-    m.directFlags = flags;
-    m.directSums.on = enabled;
-    m.restartDirect();
     // off: nothing of the direct sums stays allocated
-    if (!enabled) m.directSums.release();
+    if (change == Books::Change::RestartedOff) m.storage[Books::kDirect].release();
 }
 
-bool     Renderer::directEnabled() const { return mImpl->directSums.on; }
-uint32_t Renderer::directFlags() const { return mImpl->directFlags; }
+bool     Renderer::directEnabled() const { return mImpl->books.on(Books::kDirect); }
+uint32_t Renderer::directFlags() const { return mImpl->books.sums(Books::kDirect).word; }
 
 void Renderer::readDirect(float* directSum, uint32_t* sampleCount)
 {
     Impl& m = *mImpl;
     synchronize();
-    const bool empty = m.directSums.empty();
-    if (directSum) m.readCompact(empty ? nullptr : m.direct(), directSum);
-    if (sampleCount) *sampleCount = empty ? 0u : m.directSums.samples;
+    if (directSum) m.readCompact(m.books.empty(Books::kDirect) ? nullptr : m.direct(), directSum);
+    if (sampleCount) *sampleCount = m.books.readCount(Books::kDirect);
 }
 
 void Renderer::denoiseSplit(const DenoiseParameters& direct, const DenoiseParameters& indirect)
 {
     Impl& m = *mImpl;
-    // the non-uniform state: prep divides each pixel by its tile's own count, which D and the AOV sums must both have been kept for, from the first sample on
-    const bool perTile = m.nonUniform();
-    if (perTile && !(m.directSums.on && m.directTileCounts() && m.directSums.covers(m.accumulated) && m.aovSums.on && m.aovTileCounts() && m.aovSums.covers(m.accumulated)))
-        m.requireUniform("rf_renderer_denoise_split", ", and the direct sums and the first-hit AOVs were not both kept with per-tile counts for the whole accumulation: set "
-                                                      "1 | RF_DIRECT_TILE_COUNTS (rf_renderer_set_direct) and RF_AOV_FIRST_HIT | RF_AOV_TILE_COUNTS (rf_renderer_set_aovs) "
-                                                      "before the first sample and rf_renderer_denoise_split runs in this state");
-    if (!perTile) m.requireUniform("rf_renderer_denoise_split");
-    if (!m.aovSums.on) throw std::invalid_argument("denoise_split needs the first-hit AOVs: turn them on (rf_renderer_set_aovs) before the first sample");
-    if (!m.directSums.on) throw std::invalid_argument("denoise_split needs the direct sums: turn them on (rf_renderer_set_direct) before the first sample");
-    if (m.worldSize != 1u) throw std::invalid_argument("denoise_split needs the whole frame: a tile shard is set (use rf_denoise_split_images on the sum of the ranks' reads)");
-    if (m.accumulated == 0u) throw std::invalid_argument("denoise_split: no sample has been accumulated");
-    if (!m.aovSums.covers(m.accumulated))
-        throw std::invalid_argument("denoise_split: the AOV sample count (" + std::to_string(m.aovSums.samples) + ") differs from the accumulated sample count (" +
-                                    std::to_string(m.accumulated) + "): turn the AOVs on before the first sample");
-    if (!m.directSums.covers(m.accumulated))
-        throw std::invalid_argument("denoise_split: the direct sample count (" + std::to_string(m.directSums.samples) + ") differs from the accumulated sample count (" +
-                                    std::to_string(m.accumulated) + "): turn the direct sums on before the first sample");
+    m.books.refuseDenoiseSplit();
     RF_HIP(hipSetDevice(m.device));
-    // (per tile: the call first waits for the stream and copies the counts to the device; the snapshot's sample count is the leading count)
-    enqueueDenoiseSplit(m.stream, m.denoiseWork, m.image, m.direct(), m.aovAlbedoCoverage(), m.aovNormalDepth(), m.params.width, m.params.height, m.grid().tilesX, m.accumulated,
-                        direct, indirect, m.params.exposure, perTile ? m.uploadTileSamples() : nullptr);
-    m.denoisedValid = true;
-    m.denoisedSamples = m.accumulated;
+    // (per tile: the call first waits for the stream and copies the counts to the device)
+    enqueueDenoiseSplit(m.stream, m.denoiseWork, m.image, m.direct(), m.aovAlbedoCoverage(), m.aovNormalDepth(), m.params.width, m.params.height, m.grid().tilesX,
+                        m.books.accumulated(), direct, indirect, m.params.exposure, m.books.nonUniform() ? m.uploadTileSamples() : nullptr);
+    m.books.noteDenoised();
 }
 
 uint32_t Renderer::exportFeatures(const FeatureRequest& request, void* dstDevice, uint64_t dstBytes)
@@ -1454,213 +1329,106 @@ uint32_t Renderer::exportFeatures(const FeatureRequest& request, void* dstDevice
     Impl&          m = *mImpl;
     const uint32_t reads = featureReads(request.channels);
     requireFeatureDestination(dstDevice, dstBytes, featureBytes(m.params.width, m.params.height, request), m.device, "rf_renderer_export_features");
-    if (m.worldSize != 1u)
-        throw std::invalid_argument("export_features needs the whole frame: a tile shard is set (gather the frame -- rf_renderer_gather_frame -- and call rf_comm_export_features on the root)");
-    if (m.accumulated == 0u) throw std::invalid_argument("export_features: no sample has been accumulated");
-    // each selected channel's family: on, covering the accumulation and -- in the non-uniform state -- kept per tile count (the moments always are: render_adaptive needs them)
-    const bool perTile = m.nonUniform();
-    const auto family = [&](uint32_t bit, const SumChannel& sums, bool tileCounts, const char* name, const char* hint) {
-        if (!(reads & bit)) return;
-        if (!sums.on) throw std::invalid_argument(std::string("export_features: a selected channel needs ") + name + ": turn them on (" + hint + ") before the first sample");
-        if (!sums.covers(m.accumulated))
-            throw std::invalid_argument(std::string("export_features: the sample count of ") + name + " (" + std::to_string(sums.samples) + ") differs from the accumulated sample count (" +
-                                        std::to_string(m.accumulated) + "): turn them on before the first sample");
-        if (perTile && !tileCounts)
-            m.requireUniform("rf_renderer_export_features", (std::string(", and ") + name + " were not kept with per-tile counts (" + hint + " with the tile-count bit before the first sample)").c_str());
-    };
-    family(kFeatureReadsAovs, m.aovSums, m.aovTileCounts(), "the first-hit AOVs", "rf_renderer_set_aovs");
-    family(kFeatureReadsD, m.directSums, m.directTileCounts(), "the direct sums", "rf_renderer_set_direct");
-    family(kFeatureReadsQ, m.momentSums, true, "the radiance second moments", "rf_renderer_set_moments");
-    if (featureNeedsTwoSamples(request.channels))
-    {
-        if (m.accumulated < 2u) throw std::invalid_argument("export_features: RF_FEATURE_VARIANCE / RF_FEATURE_ERROR need at least 2 accumulated samples");
-        if (perTile && *std::min_element(m.tileSamples.begin(), m.tileSamples.end()) < 2u)
-            throw std::invalid_argument("export_features: RF_FEATURE_VARIANCE / RF_FEATURE_ERROR need at least 2 samples in every tile");
-    }
+    m.books.refuseExportFeatures(reads, featureNeedsTwoSamples(request.channels));
     RF_HIP(hipSetDevice(m.device));
     FeatureSources s;
     s.colorSum = m.image, s.sumSq = m.moments(), s.albedoCoverage = m.aovAlbedoCoverage(), s.normalDepth = m.aovNormalDepth(), s.directSum = m.direct();
-    s.samples = m.accumulated;
+    s.samples = m.books.accumulated();
     // (per tile: the call first waits for the stream and copies the counts to the device)
-    s.tileSamples = perTile ? m.uploadTileSamples() : nullptr;
+    s.tileSamples = m.books.nonUniform() ? m.uploadTileSamples() : nullptr;
     enqueueExportFeatures(m.stream, s, m.params.width, m.params.height, true, request, dstDevice);
     RF_HIP(hipStreamSynchronize(m.stream)); // the buffer may be used from any stream once the call returns
-    return m.accumulated;
+    return m.books.accumulated();
 }
 
 void Renderer::setBuckets(uint32_t word)
 {
     Impl& m = *mImpl;
-    // the low byte is K, HOW starts at bit 8 (as in the AOV flags word)
-    const uint32_t K = word & 0xFFu;
-    const bool     tileCounts = (word & kBucketsTileCounts) != 0u, shardTileCounts = (word & kBucketsShardTileCounts) != 0u;
-    if ((word & ~(0xFFu | kBucketsTileCounts | kBucketsShardTileCounts)) != 0u || (K == 0u && tileCounts) || (K != 0u && (K % 2u == 0u || K < 3u || K > kMaxBuckets)) ||
-        (shardTileCounts && !tileCounts))
-        throw std::invalid_argument("set_buckets: K must be 0 (off) or odd with 3 <= K <= 15, alone or ORed with RF_BUCKETS_TILE_COUNTS (K > 0 only), and with "
-                                    "RF_BUCKETS_SHARD_TILE_COUNTS on top of that bit only");
-    if (K != 0u) m.requireUniform("rf_renderer_set_buckets", ": the bucket sums keep ONE sample count for the frame");
-    if (K == (m.bucketSums.on ? m.bucketSums.planes : 0u) && tileCounts == m.bucketTileCounts && shardTileCounts == m.bucketShardTileCounts) return;
+    const Books::Change change = m.books.setBuckets(word);
+    if (change == Books::Change::Unchanged) return;
     RF_HIP(hipSetDevice(m.device));
     RF_HIP(hipStreamSynchronize(m.stream)); // (a batch in flight may still write the sums)
-    m.bucketSums.on = K != 0u;
-    m.bucketSums.planes = K != 0u ? K : 1u;
-    m.bucketTileCounts = tileCounts; // (a change of either bit alone clears the sums too)
-    m.bucketShardTileCounts = shardTileCounts;
-    m.restartBuckets();
     // another K is another allocation (sized before the next sample); off: nothing of the buckets stays allocated
-    m.bucketSums.release();
+    m.storage[Books::kBuckets].release();
     m.robustShard.release();
-    if (K == 0u) m.robustWork.release();
+    if (change == Books::Change::RestartedOff) m.robustWork.release();
 }
 
-uint32_t Renderer::buckets() const { return mImpl->bucketSums.on ? mImpl->bucketSums.planes : 0u; }
+uint32_t Renderer::buckets() const { return mImpl->books.buckets(); }
 
 void Renderer::readBuckets(float* planes, uint32_t* K, uint32_t* sampleCount)
 {
     Impl& m = *mImpl;
     synchronize();
-    const bool   empty = m.bucketSums.empty();
+    const bool   empty = m.books.empty(Books::kBuckets);
     const size_t plane = static_cast<size_t>(m.params.width) * m.params.height * 4;
     if (planes)
         for (uint32_t b = 0; b < buckets(); ++b) m.readCompact(empty ? nullptr : m.bucketPlanes() + b * m.bucketStride(), planes + b * plane);
     if (K) *K = buckets();
-    if (sampleCount) *sampleCount = empty ? 0u : m.bucketSums.samples;
+    if (sampleCount) *sampleCount = m.books.readCount(Books::kBuckets);
 }
 
-// What rf_renderer_robust_mean and rf_renderer_denoise_robust check alike
-static void requireRobustMean(const char* what, bool on, bool covers, uint32_t K, uint32_t bucketSamples, uint32_t accumulated, uint32_t worldSize)
-{
-    const std::string w(what);
-    if (!on) throw std::invalid_argument(w + " needs the bucket sums: turn them on (rf_renderer_set_buckets) before the first sample");
-    if (worldSize != 1u) throw std::invalid_argument(w + " needs the whole frame: a tile shard is set (use rf_robust_mean_images on the sum of the ranks' bucket reads)");
-    // (first: with nothing accumulated the counts agree, at 0, and there is still nothing to combine)
-    if (accumulated < K) throw std::invalid_argument(w + ": every one of the " + std::to_string(K) + " buckets needs a sample, and only " + std::to_string(accumulated) + " are accumulated");
-    if (!covers)
-        throw std::invalid_argument(w + ": the bucket sample count (" + std::to_string(bucketSamples) + ") differs from the accumulated sample count (" +
-                                    std::to_string(accumulated) + "): turn the buckets on before the first sample");
-}
-
-// the non-uniform state: the planes follow the per-tile counts when the buckets carry kBucketsTileCounts (they were on before render_adaptive made the state)
-bool Renderer::bucketsPerTile() const { return mImpl->nonUniform() && !mImpl->frameNonUniform() && mImpl->bucketSums.on && mImpl->bucketTileCounts; }
-
-// What the two check on top in that state: every bucket of every tile needs a sample
-static void requireTileBuckets(const char* what, uint32_t K, const std::vector<uint32_t>& tileSamples)
-{
-    const uint32_t least = *std::min_element(tileSamples.begin(), tileSamples.end());
-    if (least < K)
-        throw std::invalid_argument(std::string(what) + ": every one of the " + std::to_string(K) + " buckets of every tile needs a sample, and the smallest tile count is " +
-                                    std::to_string(least) + " (sample adaptively with min_samples >= K)");
-}
+bool Renderer::bucketsPerTile() const { return mImpl->books.bucketsPerTile(); }
 
 void Renderer::robustMean()
 {
     Impl& m = *mImpl;
-    const bool perTile = bucketsPerTile();
-    if (!perTile) m.requireUniform("rf_renderer_robust_mean");
-    requireRobustMean("robust_mean", m.bucketSums.on, m.bucketSums.covers(m.accumulated), buckets(), m.bucketSums.samples, m.accumulated, m.worldSize);
-    if (perTile) requireTileBuckets("robust_mean", buckets(), m.tileSamples);
+    m.books.refuseRobustMean();
     RF_HIP(hipSetDevice(m.device));
-    // (per tile: the call first waits for the stream and copies the counts to the device, as the other per-tile reads do; the snapshot's count is the leading count)
-    enqueueRobustMean(m.stream, m.robustWork, m.bucketPlanes(), m.bucketStride(), m.params.width, m.params.height, m.grid().tilesX, buckets(), m.accumulated, m.params.exposure,
-                      perTile ? m.uploadTileSamples() : nullptr);
-    m.robustValid = true;
-    m.robustSamples = m.accumulated;
+    // (per tile: the call first waits for the stream and copies the counts to the device, as the other per-tile reads do)
+    enqueueRobustMean(m.stream, m.robustWork, m.bucketPlanes(), m.bucketStride(), m.params.width, m.params.height, m.grid().tilesX, buckets(), m.books.accumulated(), m.params.exposure,
+                      bucketsPerTile() ? m.uploadTileSamples() : nullptr);
+    m.books.noteRobustMean();
 }
 
 void Renderer::readRobustMean(float* rgba, uint32_t* bgra8, uint8_t* trim, uint32_t* sampleCount)
 {
     Impl& m = *mImpl;
-    if (!m.robustValid) throw std::invalid_argument("no robust mean: call rf_renderer_robust_mean first (the image is dropped when the accumulation or the bucket sums are cleared)");
+    m.books.refuseReadRobustMean();
     synchronize();
     const size_t n = static_cast<size_t>(m.params.width) * m.params.height;
     if (rgba) RF_HIP(hipMemcpy(rgba, m.robustWork.mean.ptr, n * sizeof(float4), hipMemcpyDeviceToHost));
     if (bgra8) RF_HIP(hipMemcpy(bgra8, m.robustWork.bgra.ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (trim) RF_HIP(hipMemcpy(trim, m.robustWork.trim.ptr, n * sizeof(uint8_t), hipMemcpyDeviceToHost));
-    if (sampleCount) *sampleCount = m.robustSamples;
+    if (sampleCount) *sampleCount = m.books.robustSamples();
 }
 
 void Renderer::denoiseRobust(const DenoiseParameters& params)
 {
     Impl& m = *mImpl;
-    // rf_renderer_denoise's refusals (the non-uniform state: as there, the AOV sums must have been kept per tile count for the whole accumulation -- and the buckets
-    // too), then the robust mean's
-    const bool perTile = m.nonUniform();
-    if (perTile && !(m.aovSums.on && m.aovTileCounts() && m.aovSums.covers(m.accumulated)))
-        m.requireUniform("rf_renderer_denoise_robust", ", and the first-hit AOVs were not kept with per-tile counts for the whole accumulation: set RF_AOV_FIRST_HIT | "
-                                                       "RF_AOV_TILE_COUNTS (rf_renderer_set_aovs) before the first sample and rf_renderer_denoise_robust runs in this state");
-    if (!perTile) m.requireUniform("rf_renderer_denoise_robust");
-    if (!m.aovSums.on) throw std::invalid_argument("denoise_robust needs the first-hit AOVs: turn them on (rf_renderer_set_aovs) before the first sample");
-    if (m.worldSize != 1u) throw std::invalid_argument("denoise_robust needs the whole frame: a tile shard is set");
-    if (m.accumulated == 0u) throw std::invalid_argument("denoise_robust: no sample has been accumulated");
-    if (!m.aovSums.covers(m.accumulated))
-        throw std::invalid_argument("denoise_robust: the AOV sample count (" + std::to_string(m.aovSums.samples) + ") differs from the accumulated sample count (" +
-                                    std::to_string(m.accumulated) + "): turn the AOVs on before the first sample");
+    m.books.refuseDenoiseRobust();
     robustMean();
     // (per tile: the counts robustMean uploaded are still on the device, and nothing but this stream reads them)
-    enqueueDenoise(m.stream, m.denoiseWork, m.image, m.aovAlbedoCoverage(), m.aovNormalDepth(), m.params.width, m.params.height, m.grid().tilesX, m.accumulated, params,
-                   m.params.exposure, perTile ? m.tileSamplesDevice.ptr : nullptr, m.robustWork.mean.ptr);
-    m.denoisedValid = true;
-    m.denoisedSamples = m.accumulated;
+    enqueueDenoise(m.stream, m.denoiseWork, m.image, m.aovAlbedoCoverage(), m.aovNormalDepth(), m.params.width, m.params.height, m.grid().tilesX, m.books.accumulated(), params,
+                   m.params.exposure, m.books.nonUniform() ? m.tileSamplesDevice.ptr : nullptr, m.robustWork.mean.ptr);
+    m.books.noteDenoised();
 }
 
 NoiseEstimate Renderer::noiseEstimate(float* errorMap, float* tileSum, float* tileMax)
 {
     Impl& m = *mImpl;
-    if (!m.momentSums.on) throw std::invalid_argument("the noise estimate needs the radiance second moments: turn them on (rf_renderer_set_moments) before the first sample");
-    if (m.worldSize != 1u) throw std::invalid_argument("the noise estimate needs the whole frame: a tile shard is set (use rf_noise_estimate_images on the ranks' sums)");
-    // (a dirty channel's count is 0 and a dirty image's accumulated count is 0 -- SumChannel -- so the counts print as they are)
-    if (!m.momentSums.covers(m.accumulated))
-        throw std::invalid_argument("noise estimate: the moment sample count (" + std::to_string(m.momentSums.samples) + ") differs from the accumulated sample count (" +
-                                    std::to_string(m.accumulated) + "): turn the moments on before the first sample");
-    if (m.accumulated < 2u) throw std::invalid_argument("noise estimate: a variance needs at least 2 accumulated samples");
+    m.books.refuseNoiseEstimate();
     RF_HIP(hipSetDevice(m.device));
-    if (m.nonUniform())
+    if (m.books.nonUniform())
     {
         // every tile with its own count (each >= 2: a tile stops at an estimate); `samples` reports the leading count
         TileSelection sel;
         sel.tileSamplesDevice = m.uploadTileSamples();
-        return runNoiseEstimateTiles(m.stream, m.noiseWork, m.image, m.moments(), m.params.width, m.params.height, true, sel, m.accumulated, errorMap, tileSum, tileMax, nullptr);
+        return runNoiseEstimateTiles(m.stream, m.noiseWork, m.image, m.moments(), m.params.width, m.params.height, true, sel, m.books.accumulated(), errorMap, tileSum, tileMax, nullptr);
     }
-    return runNoiseEstimate(m.stream, m.noiseWork, m.image, m.moments(), m.params.width, m.params.height, true, m.accumulated, errorMap, tileSum, tileMax);
+    return runNoiseEstimate(m.stream, m.noiseWork, m.image, m.moments(), m.params.width, m.params.height, true, m.books.accumulated(), errorMap, tileSum, tileMax);
 }
 
 // What rf_renderer_render_adaptive and rf_comm_render_adaptive check alike before anything is traced (or exchanged)
 void Renderer::checkAdaptive(const AdaptiveParameters& p, bool sharded) const
 {
-    const Impl& m = *mImpl;
-    if (m.directSums.on && !m.directTileCounts())
-        throw std::invalid_argument("render_adaptive: the direct sums are on (rf_renderer_set_direct), and they keep ONE sample count for the frame: turn them off "
-                                    "(rf_renderer_set_direct(r, 0)) before sampling adaptively");
-    if (m.bucketSums.on && m.bucketTileCounts && sharded && !m.bucketShardTileCounts)
-        throw std::invalid_argument("render_adaptive: the bucket sums are on (rf_renderer_set_buckets), and RF_BUCKETS_TILE_COUNTS covers rf_renderer_render_adaptive only: "
-                                    "bucket planes under a tile shard are not kept per tile count; turn the buckets off (rf_renderer_set_buckets(r, 0)) first");
-    if (m.bucketSums.on && !m.bucketTileCounts)
-        throw std::invalid_argument("render_adaptive: the bucket sums are on (rf_renderer_set_buckets), and they keep ONE sample count for the frame: turn the buckets off "
-                                    "(rf_renderer_set_buckets(r, 0)) before sampling adaptively");
-    if (!m.momentSums.on) throw std::invalid_argument("render_adaptive needs the radiance second moments: turn them on (rf_renderer_set_moments) before the first sample");
-    if (m.aovSums.on && !m.aovTileCounts())
-        throw std::invalid_argument("render_adaptive: the first-hit AOVs are on without RF_AOV_TILE_COUNTS (their sums and the denoiser then keep ONE sample count): set "
-                                    "RF_AOV_FIRST_HIT | RF_AOV_TILE_COUNTS before the first sample, or turn the AOVs off");
-    if (p.checkEvery == 0u) throw std::invalid_argument("render_adaptive: check_every must be >= 1");
-    if (!std::isfinite(p.targetTileError) || p.targetTileError < 0.0f) throw std::invalid_argument("render_adaptive: target_tile_error must be finite and >= 0");
-    if (m.accumulated != 0u && !m.momentSums.covers(m.accumulated))
-        throw std::invalid_argument("render_adaptive: the moments do not cover the accumulation (turned on partway through): restart the accumulation first");
-    if (m.aovSums.on && m.accumulated != 0u && !m.aovSums.covers(m.accumulated))
-        throw std::invalid_argument("render_adaptive: the AOV sample count does not cover the accumulation (the AOVs were turned on partway through): restart the accumulation first");
-    if (m.bucketSums.on && m.accumulated != 0u && !m.bucketSums.covers(m.accumulated))
-        throw std::invalid_argument("render_adaptive: the bucket sample count does not cover the accumulation (the buckets were turned on partway through): restart the accumulation first");
-    if (m.directSums.on && m.accumulated != 0u && !m.directSums.covers(m.accumulated))
-        throw std::invalid_argument("render_adaptive: the direct sample count does not cover the accumulation (the direct sums were turned on partway through): restart the accumulation first");
+    mImpl->books.refuseAdaptive(p.checkEvery, p.targetTileError, sharded);
 }
 
 AdaptiveResult Renderer::renderAdaptive(const AdaptiveParameters& p)
 {
-    Impl& m = *mImpl;
-    // (the order of the checks, and so which message a call with several faults gets, is the one this call always had)
-    if ((m.directSums.on && !m.directTileCounts()) || (m.bucketSums.on && !m.bucketTileCounts) || !m.momentSums.on || (m.aovSums.on && !m.aovTileCounts())) checkAdaptive(p);
-    if (m.worldSize != 1u) throw std::invalid_argument("render_adaptive needs the whole frame: a tile shard is set (rf_comm_render_adaptive samples a sharded frame adaptively)");
-    checkAdaptive(p);
-    return renderAdaptiveFrom(p, m.accumulated, false);
+    mImpl->books.refuseRenderAdaptive(p.checkEvery, p.targetTileError);
+    return renderAdaptiveFrom(p, mImpl->books.accumulated(), false);
 }
 
 // The loop of rf_renderer_render_adaptive over the handle's own tiles -- the whole frame, or a tile shard -- with `leading` the frame's leading count: the handle's
@@ -1669,8 +1437,8 @@ AdaptiveResult Renderer::renderAdaptive(const AdaptiveParameters& p)
 // take the id for the slot (rf_renderer_render_adaptive's, as ever).  rf_comm_render_adaptive passes true at every world size, 1 included.
 AdaptiveResult Renderer::renderAdaptiveFrom(const AdaptiveParameters& p, uint32_t leading, bool shardSlots)
 {
-    if (!shardSlots && mImpl->worldSize != 1u) throw std::logic_error("a tile shard's sums are addressed by slot");
     Impl& m = *mImpl;
+    m.books.requireSlotAddressing(shardSlots);
     RF_HIP(hipSetDevice(m.device));
     const uint32_t spp = m.params.samplingParams.numSamplesPerPixel;
     const uint32_t cap = p.maxSamples == 0u ? spp : std::min(p.maxSamples, spp);
@@ -1684,12 +1452,12 @@ AdaptiveResult Renderer::renderAdaptiveFrom(const AdaptiveParameters& p, uint32_
 
     // the counts (by slot) as a vector for the length of the call (the uniform state: every tile at the accumulated count); the tiles at the leading count are the
     // active ones -- none on a rank whose tiles all stopped below the frame's leading count
-    std::vector<uint32_t> counts = m.nonUniform() ? m.tileSamples : std::vector<uint32_t>(numTiles, m.accumulated);
+    std::vector<uint32_t> counts = m.books.tileCounts();
     std::vector<uint32_t> active, activeIds; // slots; their frame ids
     for (uint32_t k = 0; k < numTiles; ++k)
         if (counts[k] == leading) active.push_back(k);
     const uint64_t pixelSamplesBefore = pixelSamples(counts);
-    const uint32_t frameCountBefore = m.frameCount;
+    const uint32_t frameCountBefore = m.books.frameCount();
 
     AdaptiveResult        out;
     std::vector<float>    sums(frameTiles);
@@ -1714,7 +1482,7 @@ AdaptiveResult Renderer::renderAdaptiveFrom(const AdaptiveParameters& p, uint32_
         return ids;
     };
     activeIds = idsOf(active);
-    while (!active.empty() && m.accumulated < cap)
+    while (!active.empty() && m.books.accumulated() < cap)
     {
         const uint64_t pixelsPadded = static_cast<uint64_t>(active.size()) * 1024;
         if (listStale)
@@ -1725,16 +1493,16 @@ AdaptiveResult Renderer::renderAdaptiveFrom(const AdaptiveParameters& p, uint32_
             listStale = false;
         }
         m.clearStaleSums(static_cast<uint64_t>(numTiles) * 1024);
-        uint32_t remaining = std::min(p.checkEvery, cap - m.accumulated);
+        uint32_t remaining = std::min(p.checkEvery, cap - m.books.accumulated());
         while (remaining > 0) remaining -= m.step(remaining, pixelsPadded, &list);
-        for (const uint32_t k : active) counts[k] = m.accumulated;
-        m.tileSamples = counts; // (non-uniform from here on, should an estimate throw; settled below)
-        if (m.accumulated < firstCheck) continue;
+        for (const uint32_t k : active) counts[k] = m.books.accumulated();
+        m.books.setTileSamples(counts); // (non-uniform from here on, should an estimate throw; settled below)
+        if (m.books.accumulated() < firstCheck) continue;
         // the active tiles' estimate, Nf = float(L) for all of them; tileIds holds the list (the shard's own while every tile is active)
         TileSelection sel;
         sel.listDevice = m.tileIds.ptr, sel.listHost = activeIds.data(), sel.listCount = static_cast<uint32_t>(active.size());
         sel.slotsBehindList = shardSlots;
-        out.last = runNoiseEstimateTiles(m.stream, m.noiseWork, m.image, m.moments(), m.params.width, m.params.height, true, sel, m.accumulated, nullptr, sums.data(), nullptr,
+        out.last = runNoiseEstimateTiles(m.stream, m.noiseWork, m.image, m.moments(), m.params.width, m.params.height, true, sel, m.books.accumulated(), nullptr, sums.data(), nullptr,
                                          pixels.data());
         ++out.estimatePasses;
         std::vector<uint32_t> still;
@@ -1748,44 +1516,34 @@ AdaptiveResult Renderer::renderAdaptiveFrom(const AdaptiveParameters& p, uint32_
 
     out.tiles = numTiles;
     out.minTileSamples = out.maxTileSamples = numTiles ? counts[0] : 0u;
-    for (uint32_t k = 0; k < numTiles; ++k)
-    {
-        out.minTileSamples = std::min(out.minTileSamples, counts[k]), out.maxTileSamples = std::max(out.maxTileSamples, counts[k]);
-        if (counts[k] != m.accumulated) ++out.stoppedTiles;
-    }
+    for (uint32_t k = 0; k < numTiles; ++k) out.minTileSamples = std::min(out.minTileSamples, counts[k]), out.maxTileSamples = std::max(out.maxTileSamples, counts[k]);
     out.pixelSamples = pixelSamples(counts);
     out.tracedPixelSamples = out.pixelSamples - pixelSamplesBefore;
-    out.framesTraced = m.frameCount - frameCountBefore;
-    if (out.stoppedTiles == 0u) m.tileSamples.clear(); // every tile of the handle at its leading count: its per-tile reads take the ordinary form
-    else m.tileSamples = counts;
+    out.framesTraced = m.books.frameCount() - frameCountBefore;
+    out.stoppedTiles = m.books.settleTileSamples(counts);
     return out;
 }
 
 uint32_t Renderer::settleFrameTileSamples(uint32_t leading, uint32_t minimum, uint32_t skipFrames)
 {
-    Impl& m = *mImpl;
-    m.frameLeadingSamples = leading, m.frameMinTileSamples = minimum;
-    m.frameCount += skipFrames;
-    uint32_t below = 0;
-    for (size_t k = 0; k < m.tiles.size(); ++k) below += (m.nonUniform() ? m.tileSamples[k] : m.accumulated) < leading ? 1u : 0u;
-    return below;
+    return mImpl->books.settleFrameTileSamples(leading, minimum, skipFrames);
 }
 
 const uint32_t* Renderer::shardTileSamplesDevice()
 {
     Impl& m = *mImpl;
     RF_HIP(hipSetDevice(m.device));
-    if (m.nonUniform()) return m.uploadTileSamples();
+    if (m.books.nonUniform()) return m.uploadTileSamples();
     // the ordinary form: every tile of the shard at the accumulated count
-    const std::vector<uint32_t> counts(m.tiles.size(), m.accumulated);
+    const std::vector<uint32_t> counts = m.books.tileCounts();
     RF_HIP(hipStreamSynchronize(m.stream));
     if (m.tileSamplesDevice.count < counts.size()) m.tileSamplesDevice.alloc(counts.size());
     if (!counts.empty()) RF_HIP(hipMemcpy(m.tileSamplesDevice.ptr, counts.data(), counts.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     return m.tileSamplesDevice.ptr;
 }
 
-bool Renderer::tileSamplesUniform() const { return !mImpl->nonUniform() && !mImpl->frameNonUniform(); }
-void Renderer::requireUniformTileSamples(const char* what) const { mImpl->requireUniform(what); }
+bool Renderer::tileSamplesUniform() const { return !mImpl->books.nonUniform() && !mImpl->books.frameNonUniform(); }
+void Renderer::requireUniformTileSamples(const char* what) const { mImpl->books.requireUniform(what); }
 
 uint32_t Renderer::readTileSamples(uint32_t* tileSamples) const
 {
@@ -1794,7 +1552,7 @@ uint32_t Renderer::readTileSamples(uint32_t* tileSamples) const
     if (tileSamples)
     {
         std::fill(tileSamples, tileSamples + frameTiles, 0u);
-        for (size_t i = 0; i < m.tiles.size(); ++i) tileSamples[m.tiles[i]] = m.nonUniform() ? m.tileSamples[i] : m.accumulated; // (0 after a restart)
+        for (size_t i = 0; i < m.tiles.size(); ++i) tileSamples[m.tiles[i]] = m.books.tileCount(i); // (0 after a restart)
     }
     return frameTiles;
 }
@@ -1809,21 +1567,16 @@ void Renderer::readMean(float* rgba)
 uint32_t Renderer::renderUntil(float targetMeanError, uint32_t checkEvery, uint32_t maxFrames, NoiseEstimate* last)
 {
     Impl& m = *mImpl;
-    if (!m.momentSums.on) throw std::invalid_argument("render_until needs the radiance second moments: turn them on (rf_renderer_set_moments) before the first sample");
-    m.requireUniform("rf_renderer_render_until"); // (first: under a tile shard this is the state rf_comm_render_adaptive left)
-    if (m.worldSize != 1u) throw std::invalid_argument("render_until needs the whole frame: a tile shard is set");
-    if (checkEvery == 0u) throw std::invalid_argument("render_until: check_every must be >= 1");
-    if (m.accumulated != 0u && !m.momentSums.covers(m.accumulated))
-        throw std::invalid_argument("render_until: the moments do not cover the accumulation (turned on partway through): restart the accumulation first");
+    m.books.refuseRenderUntil(checkEvery);
     const uint32_t spp = m.params.samplingParams.numSamplesPerPixel;
     NoiseEstimate  estimate;
     uint32_t       frames = 0;
-    while (frames < maxFrames && m.accumulated < spp)
+    while (frames < maxFrames && m.books.accumulated() < spp)
     {
-        const uint32_t n = std::min({checkEvery, maxFrames - frames, spp - m.accumulated});
+        const uint32_t n = std::min({checkEvery, maxFrames - frames, spp - m.books.accumulated()});
         render(n);
         frames += n;
-        if (m.accumulated < 2u) continue;
+        if (m.books.accumulated() < 2u) continue;
         estimate = noiseEstimate(nullptr, nullptr, nullptr);
         if (estimate.meanError <= static_cast<double>(targetMeanError)) break;
     }
@@ -1836,27 +1589,23 @@ void*    Renderer::accumulationDevicePointer() const { return mImpl->image; }
 Renderer::ShardSums Renderer::shardSums() const
 {
     const Impl& m = *mImpl;
-    const auto  channel = [&](const auto& sums) { return ShardSums::Channel{sums.on, sums.on && m.accumulated != 0u && sums.covers(m.accumulated), sums.samples}; };
-    // (frameLeadingSamples != 0: rf_comm_render_adaptive has settled the frame's figures since the accumulation was restarted)
-    uint32_t least = m.accumulated;
-    if (m.frameLeadingSamples != 0u) least = m.frameMinTileSamples;
-    else if (m.nonUniform()) least = *std::min_element(m.tileSamples.begin(), m.tileSamples.end());
-    return ShardSums{{m.image, m.aovAlbedoCoverage(), m.aovNormalDepth(), m.moments()}, channel(m.aovSums), channel(m.momentSums), m.accumulated, !m.tiles.empty(),
-                     channel(m.bucketSums), buckets(), m.bucketSums.on && m.bucketShardTileCounts, least, channel(m.directSums), m.directSums.on && m.directTileCounts(), m.direct()};
+    const Books& b = m.books;
+    return ShardSums{{m.image, m.aovAlbedoCoverage(), m.aovNormalDepth(), m.moments()}, b.shardChannel(Books::kAovs), b.shardChannel(Books::kMoments), b.accumulated(), !m.tiles.empty(),
+                     b.shardChannel(Books::kBuckets), buckets(), b.shardTileCounts(Books::kBuckets), b.minTileSamples(), b.shardChannel(Books::kDirect), b.tileCounts(Books::kDirect), m.direct()};
 }
 
 const void* Renderer::enqueueShardRobustMean(const uint32_t* slotCounts)
 {
     Impl& m = *mImpl;
     if (m.tiles.empty()) return nullptr;
-    if (!m.bucketSums.on || !m.bucketSums.covers(m.accumulated) || m.accumulated < buckets()) throw std::logic_error("enqueueShardRobustMean: the bucket sums do not cover the accumulation");
+    m.books.requireShardRobustMean();
     RF_HIP(hipSetDevice(m.device));
     if (m.robustShard.count < m.bucketStride())
     {
         RF_HIP(hipStreamSynchronize(m.stream)); // (the last gather may still read the smaller one)
         m.robustShard.alloc(m.bucketStride());
     }
-    enqueueRobustMeanShard(m.stream, m.bucketPlanes(), m.bucketStride(), static_cast<uint32_t>(m.tiles.size()), buckets(), m.accumulated, m.robustShard.ptr, slotCounts);
+    enqueueRobustMeanShard(m.stream, m.bucketPlanes(), m.bucketStride(), static_cast<uint32_t>(m.tiles.size()), buckets(), m.books.accumulated(), m.robustShard.ptr, slotCounts);
     return m.robustShard.ptr;
 }
 
@@ -1878,19 +1627,17 @@ Renderer::CheckpointBooks Renderer::checkpointBooks(bool prepare)
     if (prepare) synchronize();
     if (pixelsPadded != 0u) m.clearStaleSums(pixelsPadded);
     CheckpointBooks b;
-    b.frameCount = m.frameCount, b.accumulated = m.accumulated, b.frameLeadingSamples = m.frameLeadingSamples, b.frameMinTileSamples = m.frameMinTileSamples;
-    b.aovFlags = m.aovFlags, b.moments = m.momentSums.on ? 1u : 0u, b.directWord = m.directFlags;
-    b.bucketsWord = buckets() == 0u ? 0u : (buckets() | (m.bucketTileCounts ? kBucketsTileCounts : 0u) | (m.bucketShardTileCounts ? kBucketsShardTileCounts : 0u));
-    const SumChannel* const channels[5] = {&m.imageSums, &m.aovSums, &m.momentSums, &m.directSums, &m.bucketSums};
-    for (uint32_t f = 0; f < 5; ++f) b.family[f] = {channels[f]->on, (!channels[f]->on || channels[f]->dirty) ? 0u : channels[f]->samples};
-    b.family[0].samples = m.accumulated; // (the image keeps no count of its own)
-    b.tileSamples = m.nonUniform() ? m.tileSamples : std::vector<uint32_t>(m.tiles.size(), m.accumulated);
+    const Books::Checkpoint c = m.books.checkpoint();
+    b.frameCount = c.frameCount, b.accumulated = c.accumulated, b.frameLeadingSamples = c.frameLeadingSamples, b.frameMinTileSamples = c.frameMinTileSamples;
+    b.aovFlags = c.word[Books::kAovs], b.moments = c.word[Books::kMoments], b.directWord = c.word[Books::kDirect], b.bucketsWord = c.word[Books::kBuckets];
+    std::copy(c.family, c.family + Books::kFamilies, b.family);
+    b.tileSamples = c.tileSamples;
     if (pixelsPadded != 0u)
     {
         b.planes[0] = m.image;
-        if (m.aovSums.on) b.planes[1] = m.aovAlbedoCoverage(), b.planes[2] = m.aovNormalDepth();
-        if (m.momentSums.on) b.planes[3] = m.moments();
-        if (m.directSums.on) b.planes[4] = m.direct();
+        if (c.family[Books::kAovs].on) b.planes[1] = m.aovAlbedoCoverage(), b.planes[2] = m.aovNormalDepth();
+        if (c.family[Books::kMoments].on) b.planes[3] = m.moments();
+        if (c.family[Books::kDirect].on) b.planes[4] = m.direct();
         for (uint32_t k = 0; k < buckets(); ++k) b.planes[5 + k] = m.bucketPlanes() + k * m.bucketStride();
     }
     static_assert(sizeof(Camera) == sizeof b.camera && sizeof(float) * 6 == sizeof b.sky);
@@ -1907,30 +1654,24 @@ void Renderer::checkpointRestart(bool zeroNow)
 {
     Impl& m = *mImpl;
     synchronize();
-    m.restartAccumulation();
+    m.books.restartAccumulation();
     const uint64_t pixelsPadded = static_cast<uint64_t>(m.tiles.size()) * 1024;
     if (zeroNow && pixelsPadded != 0u) m.clearStaleSums(pixelsPadded);
 }
 
 void Renderer::checkpointAdopt(const CheckpointBooks& b)
 {
-    Impl& m = *mImpl;
-    if (b.tileSamples.size() != m.tiles.size()) throw std::logic_error("checkpointAdopt: one count per tile of the shard");
-    m.frameCount = b.frameCount;
-    m.accumulated = b.accumulated;
-    SumChannel* const channels[5] = {&m.imageSums, &m.aovSums, &m.momentSums, &m.directSums, &m.bucketSums};
-    for (uint32_t f = 1; f < 5; ++f)
-        if (channels[f]->on) channels[f]->samples = b.family[f].samples;
-    const bool uniform = std::all_of(b.tileSamples.begin(), b.tileSamples.end(), [&](uint32_t c) { return c == b.accumulated; });
-    if (uniform) m.tileSamples.clear();
-    else m.tileSamples = b.tileSamples;
-    m.frameLeadingSamples = b.frameLeadingSamples, m.frameMinTileSamples = b.frameMinTileSamples;
+    Books::Checkpoint c;
+    c.frameCount = b.frameCount, c.accumulated = b.accumulated, c.frameLeadingSamples = b.frameLeadingSamples, c.frameMinTileSamples = b.frameMinTileSamples;
+    std::copy(b.family, b.family + Books::kFamilies, c.family);
+    c.tileSamples = b.tileSamples;
+    mImpl->books.adopt(c);
 }
 
 void Renderer::clearAccumulationIfStale()
 {
     Impl& m = *mImpl;
-    if (!m.imageSums.dirty || m.image == nullptr) return;
+    if (!m.books.stale(Books::kImage) || m.image == nullptr) return;
     RF_HIP(hipSetDevice(m.device));
     m.zeroImageIfStale(std::min<uint64_t>(accumulationBytes(), m.imageBytes));
 }
@@ -1955,7 +1696,7 @@ void Renderer::memoryInfo(uint64_t& pathStateBytes, uint64_t& pathsAllocated, ui
 {
     const Impl& m = *mImpl;
     pathsAllocated = m.allocatedPaths;
-    pathStateBytes = m.pathStateBytes() + m.directSums.buffers[0].count * sizeof(float4) + m.primaryListBytes(); // (the direct sums, while they are on: 16 B per pixel of the shard's tiles; the leaf lists of bounce 1)
+    pathStateBytes = m.pathStateBytes() + m.storage[Books::kDirect].buffers[0].count * sizeof(float4) + m.primaryListBytes(); // (the direct sums, while they are on: 16 B per pixel of the shard's tiles; the leaf lists of bounce 1)
     maxPathsPerBatch = m.effectivePaths ? std::min(m.effectivePaths, m.maxPaths) : m.maxPaths;
     sceneBytes = (m.nodes.count + m.triangles.count + m.wideNodes.count + m.wideCompact.count + m.wideHot.count + m.wideOwn.count + m.wideQuad.count + m.wideQuadHalf.count + m.wideQuadLocal.count + m.wideOct.count + m.attributes.count + m.shadeRecords.count) * sizeof(float4) +
                  m.texels.count * sizeof(uint32_t) + m.bigLeaves.count * sizeof(uint2) + m.occluderGrid.count * sizeof(uint32_t); // (the occluder grid: allocated by the first batch)
@@ -1980,7 +1721,7 @@ void Renderer::bindAccumulationBuffer(void* devicePtr, uint64_t bytes)
     if (bytes < accumulationBytes()) throw std::runtime_error("accumulation buffer too small");
     m.image = static_cast<float4*>(devicePtr);
     m.imageBytes = bytes;
-    m.restartAccumulation();
+    m.books.restartAccumulation();
 }
 
 void Renderer::readTonemapped(uint32_t* dst)
@@ -1993,8 +1734,8 @@ void Renderer::readTonemapped(uint32_t* dst)
     m.zeroImageIfStale(static_cast<size_t>(n) * sizeof(float4));
     // (non-uniform tile counts: kTonemap over the per-tile mean with accumulatedSamples = 1, the denoiser's display path; x / 1 is exact, so the uniform state's texels are
     // the ones the direct launch gives)
-    if (n && m.nonUniform()) hipLaunchKernelGGL(tonemapKernel(), dim3((n + 255) / 256), dim3(256), 0, m.stream, m.meanOnDevice(), n, 1u, m.params.exposure, out.ptr);
-    else if (n) hipLaunchKernelGGL(tonemapKernel(), dim3((n + 255) / 256), dim3(256), 0, m.stream, m.image, n, m.accumulated, m.params.exposure, out.ptr);
+    if (n && m.books.nonUniform()) hipLaunchKernelGGL(tonemapKernel(), dim3((n + 255) / 256), dim3(256), 0, m.stream, m.meanOnDevice(), n, 1u, m.params.exposure, out.ptr);
+    else if (n) hipLaunchKernelGGL(tonemapKernel(), dim3((n + 255) / 256), dim3(256), 0, m.stream, m.image, n, m.books.accumulated(), m.params.exposure, out.ptr);
     RF_HIP(hipStreamSynchronize(m.stream));
     std::vector<uint32_t> compact(n);
     if (n) RF_HIP(hipMemcpy(compact.data(), out.ptr, static_cast<size_t>(n) * 4, hipMemcpyDeviceToHost));

@@ -11,6 +11,7 @@
 // and the bvh-visualizer node-visit pass (src/bvh-visualizer/main.cpp:60-78) on the GPU.
 #pragma once
 
+#include "rf_books.hpp" // SumCoverage, SumCount
 #include "rf_bvh.hpp" // SceneView
 #include "rf_sky.hpp"
 #include "rf_types.hpp"
@@ -362,11 +363,7 @@ public:
     // samples (on from the first sample, at least one accumulated: what the gather requires before it sends them) and its own sample count.
     struct ShardSums
     {
-        struct Channel
-        {
-            bool     on, coversAccumulation;
-            uint32_t samples;
-        };
+        using Channel = SumCoverage; // on, coversAccumulation, samples
         const void* planes[4];
         Channel     aovs, moments;
         uint32_t    accumulated;
@@ -396,11 +393,7 @@ public:
     // the per-slot tile counts (stored only while they differ from the accumulated count) and the frame-level pair.
     struct CheckpointBooks
     {
-        struct Family
-        {
-            bool     on;
-            uint32_t samples; // 0: restarted (its read returns zeros)
-        };
+        using Family = SumCount; // on, samples (0: restarted -- its read returns zeros)
         uint32_t              frameCount = 0, accumulated = 0, frameLeadingSamples = 0, frameMinTileSamples = 0;
         uint32_t              aovFlags = 0, moments = 0, directWord = 0, bucketsWord = 0;
         Family                family[5] = {}; // S, the AOVs, Q, D, the buckets
