@@ -715,7 +715,8 @@ RF_API int rf_renderer_set_timing(rf_renderer* r, int enabled);
  *                                      descend loop to go on; queue entries per cursor claim).  Same image with any setting.
  *   slot_group_shift, sample_sort, accumulate_runs, shade_blocks, reserve_samples, persistent_blocks, extra_lds
  *                                      path-slot order, accumulation kernel, grid sizes, occupancy experiments
- *   query_variant 0 | 2, query_compact 0 .. 5       kernels / record layout behind rf_renderer_intersect_rays / _occluded_rays (tests) */
+ *   query_variant 0 | 2, query_compact 0 .. 5       kernels / record layout behind rf_renderer_intersect_rays / _occluded_rays (tests)
+ *   cast_chunk n                                    rf_renderer_cast_rays traces at most n rays per chunk (0 = automatic: the path depth and the free memory) */
 RF_API int rf_renderer_set_option(rf_renderer* r, const char* name, int64_t value);
 RF_API int rf_renderer_reset_stats(rf_renderer* r);
 RF_API int rf_renderer_get_stats(rf_renderer* r, rf_stats* out);
@@ -1104,6 +1105,51 @@ RF_API int rf_renderer_intersect_rays(rf_renderer* r, const float* rays6, uint64
                                       float* t, float* uv, float* p, uint32_t* nodes_visited, uint32_t* triangle_tests);
 /* shadowRay (wgsl:321-368): visibility[i] = 1.0 if nothing is hit, else 0.0. */
 RF_API int rf_renderer_occluded_rays(rf_renderer* r, const float* rays6, uint64_t num_rays, float t_max, float* visibility);
+
+/* Cast rays from device memory: what do these rays hit, and what is the surface there?  The rays are read from caller-owned device memory, traced by the renderer's
+ * production traversal (kTraceWide, with the record layout and parameters the launch policy picks for an incoherent closest-hit / any-hit launch of this scene; the
+ * reference-order scalar traversal where the scene's wide records are unusable), and the hit and the chosen surface attributes are written into caller-owned device
+ * memory -- any number of rays, in chunks of one path-state allocation (option cast_chunk caps the chunk; 0 = automatic).
+ * Values.  triangle, t, bary and position are bit for bit rf_intersect_bvh_batch's for the same ray; on a miss every float output is +0 and the two index outputs are
+ * 0xFFFFFFFF.  The attributes come from the shading stage's own device functions in its order of operations (f32, one IEEE operation at a time, no contraction): the
+ * first-hit AOVs of a 1-sample render are this call's albedo, normal and t on that sample's primary rays, bit for bit up to the sign of a zero: the AOVs are SUMS,
+ * +0 + value after one sample, so a component this call gives as -0 reads +0 there.  visibility is bit for bit rf_renderer_occluded_rays'.
+ * Rays that start far outside the scene are answered correctly but, on the conservative record layouts, one by one by the reference-order traversal inside the
+ * kernel (rf_ray_query.hip's header): slower, by an amount that has not been measured.
+ * Stream rule.  The call is enqueued on the handle's stream and then waited for: when it returns the outputs may be used from any stream.  The caller makes sure the
+ * inputs are complete before the call.
+ * Read-only for the handle: every sum, count, snapshot and the frame counter, rf_renderer_state_digest, the image a later render produces, rf_stats and
+ * rf_renderer_get_bounce_stats are unchanged by it (the query's rays are not render rays: they count into a counter block of their own, no field of rf_stats sees
+ * them).  The path state is scratch between render calls and is used; a call with more rays per chunk than the path state holds grows it, as a render call does.
+ * The occluder cache and the first-look bookkeeping are neither used nor disturbed.  A tile shard does not matter: every handle holds the whole scene.
+ * num_rays == 0 returns 0 and reads, checks and touches nothing else.  RF_ERROR_INVALID_ARGUMENT, decided before any launch and with the state kept: a NULL batch, NULL
+ * origins or directions; a stride below 3; an unknown kind; a non-zero reserved word; no output given; a CLOSEST output with RF_RAYS_ANY, or visibility with
+ * RF_RAYS_CLOSEST; t_max NaN; an input or output that hipPointerGetAttributes does not report as device memory of the handle's device for its whole byte range (host,
+ * registered and managed memory are refused); an output range that overlaps another output or an input. */
+#define RF_RAYS_CLOSEST 0u   /* rayIntersectBvh's answer, plus the attributes at the hit */
+#define RF_RAYS_ANY     1u   /* shadowRay's answer */
+typedef struct rf_ray_batch
+{
+    const float* origins;      /* device; ray i at origins + i * origin_stride (floats), 3 floats */
+    const float* directions;   /* device; likewise with direction_stride */
+    uint32_t     origin_stride, direction_stride;   /* in floats, >= 3 */
+    uint64_t     num_rays;
+    float        t_max;
+    uint32_t     kind;         /* RF_RAYS_CLOSEST | RF_RAYS_ANY */
+    uint32_t     reserved[2];  /* 0 */
+    /* outputs: device, contiguous, 4-byte aligned, NULL = not wanted; at least one is given */
+    uint32_t* triangle;         /* N     CLOSEST  leaf-order index, 0xFFFFFFFF on a miss */
+    float*    t;                /* N     CLOSEST */
+    float*    bary;             /* N x 2 CLOSEST  u, v (weights 1-u-v, u, v) */
+    float*    position;         /* N x 3 CLOSEST  the OFFSET hit point (offsetRay): the origin a bounce or shadow ray starts from */
+    float*    geometric_normal; /* N x 3 CLOSEST  normalize(cross(e1, e2)), the normal offsetRay pushes along */
+    float*    normal;           /* N x 3 CLOSEST  unit shading normal: n = (b0 n0 + b1 n1) + b2 n2 (wgsl:396), then exactly the first-hit AOV's rule: (0,0,0) where dot(n,n) is 0 or not finite, else normalize(n) */
+    float*    texcoord;         /* N x 2 CLOSEST  (b0 uv0 + b1 uv1) + b2 uv2, not wrapped */
+    float*    albedo;           /* N x 3 CLOSEST  evalTexture at that texcoord: the value kShade multiplies the throughput by */
+    uint32_t* texture;          /* N     CLOSEST  texture descriptor index, 0xFFFFFFFF on a miss */
+    float*    visibility;       /* N     ANY      1.0 if nothing is hit in (1e-5, t_max), else 0.0 */
+} rf_ray_batch;
+RF_API int rf_renderer_cast_rays(rf_renderer* r, const rf_ray_batch* batch);
 
 /* ---------------------------------------------------------------------------------------------
  * BVH queries on the HOST (no GPU needed; re-entrant pure functions)

@@ -661,6 +661,82 @@ def _feature_tensor(what, out, shape, dtype, device_ordinal):
     return out
 
 
+# ------------------------------------------------------------------------------------- rays from device tensors
+def _ray_tensor(what, name, t):
+    """One input of cast_rays / cast_occlusion, checked before the library is called: a float32 tensor (N, 3) whose rows are 3 consecutive floats at a row stride of
+    at least 3 (a contiguous (N, 3) tensor, either half of an (N, 6) one, rows with padding).  -> the row stride in floats.  (Its device: _ray_device)"""
+    import torch
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{what}: {name} must be a torch.Tensor")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{what}: {name} is {t.dtype}, the rays are torch.float32")
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError(f"{what}: {name} has shape {tuple(t.shape)}, the rays are (N, 3)")
+    if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < 3):
+        raise ValueError(f"{what}: {name} has strides {tuple(t.stride())}: a row is 3 consecutive floats, rows at least 3 floats apart")
+    return int(t.stride(0)) if t.shape[0] > 1 else 3
+
+
+def _ray_device(what, name, t, device_ordinal):
+    if t.device.type != "cuda" or (t.device.index or 0) != device_ordinal:
+        raise ValueError(f"{what}: {name} lies on {t.device}, the scene on cuda:{device_ordinal}")
+
+
+def _ray_output(what, name, out, n):
+    """The type, dtype, shape and contiguity of a caller's output tensor (as _feature_tensor checks an export's destination; a storage offset is fine), or
+    None -> (dtype, shape) of the tensor to make"""
+    import torch
+    width, kind = {o[0]: (o[2], o[3]) for o in _ffi.RAY_OUTPUTS}[name]
+    # (uint32 words travel as int32 tensors: -1 is the miss word 0xFFFFFFFF)
+    tdtype, shape = (torch.float32 if kind == "f" else torch.int32), ((n,) if width == 1 else (n, width))
+    if out is None:
+        return tdtype, shape
+    if not isinstance(out, torch.Tensor):
+        raise TypeError(f"{what}: out[{name!r}] must be a torch.Tensor")
+    if out.dtype != tdtype:
+        raise ValueError(f"{what}: out[{name!r}] is {out.dtype}, {name} is {tdtype}")
+    if tuple(out.shape) != shape:
+        raise ValueError(f"{what}: out[{name!r}] has shape {tuple(out.shape)}, {name} of {n} rays is {shape}")
+    if not out.is_contiguous():
+        raise ValueError(f"{what}: out[{name!r}] must be contiguous")
+    return tdtype, shape
+
+
+def _ray_batch(what, origins, directions, t_max, kind, names, out, device_ordinal):
+    """-> (the rf_ray_batch of a call, its output tensors by name); every check that needs no library call: the names, the tensors' layouts, then their devices"""
+    import torch
+    known = [o[0] for o in _ffi.RAY_OUTPUTS if o[1] == kind]
+    names = (names,) if isinstance(names, str) else tuple(names)
+    unknown = [n for n in names if n not in known]
+    if unknown or not names or len(set(names)) != len(names):
+        raise ValueError(f"{what}: outputs {list(names)}: choose one or more of {known}, each once")
+    so, sd = _ray_tensor(what, "origins", origins), _ray_tensor(what, "directions", directions)
+    if origins.shape[0] != directions.shape[0]:
+        raise ValueError(f"{what}: {origins.shape[0]} origins, {directions.shape[0]} directions")
+    t_max = float(t_max)
+    if t_max != t_max:
+        raise ValueError(f"{what}: t_max is NaN")
+    if out is not None and not isinstance(out, dict):
+        raise TypeError(f"{what}: out must be a dict of torch tensors by output name")
+    if out is not None and set(out) - set(names):
+        raise ValueError(f"{what}: out holds {sorted(set(out) - set(names), key=str)}, which outputs={list(names)} does not ask for")
+    n = int(origins.shape[0])
+    given = {name: None if out is None else out.get(name) for name in names}
+    made = {name: _ray_output(what, name, given[name], n) for name in names}
+    _ray_device(what, "origins", origins, device_ordinal)
+    _ray_device(what, "directions", directions, device_ordinal)
+    for name in names:
+        if given[name] is not None:
+            _ray_device(what, f"out[{name!r}]", given[name], device_ordinal)
+    tensors = {name: given[name] if given[name] is not None else torch.empty(made[name][1], dtype=made[name][0], device=torch.device("cuda", device_ordinal)) for name in names}
+    batch = _ffi.RayBatch()
+    batch.origins, batch.directions, batch.origin_stride, batch.direction_stride = origins.data_ptr(), directions.data_ptr(), so, sd
+    batch.num_rays, batch.t_max, batch.kind = n, t_max, kind
+    for name, t in tensors.items():
+        setattr(batch, name, t.data_ptr())
+    return batch, tensors
+
+
 def export_features_images(color_sum=None, sumsq=None, albedo_coverage=None, normal_depth=None, direct_sum=None, samples=0, tile_samples=None,
                            channels=("color", "albedo", "normal", "depth"), layout="chw", dtype="f32", device_ordinal=0):
     """rf_export_features_images: the feature export over (H, W, 4) f32 sums held on the host -- the accumulation S, the second moments Q, {albedo, coverage},
@@ -1009,6 +1085,35 @@ class ReferencePathTracer:
         out = _feature_tensor("export_features", out, (count, h, w) if layout == "chw" else (h, w, count), dtype, self._device_ordinal)
         check(lib.rf_renderer_export_features(self._h, C.byref(req), C.c_void_p(out.data_ptr()), out.numel() * out.element_size(), None))
         return out
+
+    # rays from device tensors (rf_renderer_cast_rays; include/rayfinder_amd.h states every output's value)
+    def _cast(self, what, origins, directions, t_max, kind, names, out):
+        import torch
+        batch, tensors = _ray_batch(what, origins, directions, t_max, kind, names, out, self._device_ordinal)
+        if batch.num_rays:
+            # the inputs are complete before the library reads them on the handle's own stream
+            torch.cuda.current_stream(torch.device("cuda", self._device_ordinal)).synchronize()
+            check(lib.rf_renderer_cast_rays(self._h, C.byref(batch)))
+        return tensors
+
+    def cast_rays(self, origins, directions, t_max=10000.0, outputs=("triangle", "t", "position", "normal", "albedo"), out=None):
+        """What do these rays hit, and what is the surface there?  origins, directions: float32 CUDA tensors (N, 3) on the handle's device, rows of 3 consecutive floats
+        at a row stride >= 3 (the two halves of an (N, 6) tensor qualify).  The rays go through the renderer's production traversal in (1e-5, t_max); -> a dict of
+        torch tensors on the device, one per name in `outputs`: triangle (N,) int32 (-1: a miss), t (N,), bary (N, 2), position (N, 3) the offset hit point,
+        geometric_normal (N, 3), normal (N, 3) the unit shading normal, texcoord (N, 2), albedo (N, 3), texture (N,) int32; float32, +0 on a miss.  out: a dict of
+        contiguous tensors of those shapes and dtypes to write into (a storage offset is fine; names it lacks are allocated).  Torch's current stream on the device is
+        synchronised first, the call waits for its kernels: the tensors may be used on any stream at once.  Nothing of the render state changes."""
+        return self._cast("cast_rays", origins, directions, t_max, _ffi.RF_RAYS_CLOSEST, outputs, out)
+
+    def cast_occlusion(self, origins, directions, t_max=10000.0, out=None):
+        """-> float32 tensor (N,): 1.0 where nothing is hit in (1e-5, t_max) along the ray, else 0.0 (shadowRay's answer).  Rays, stream rule and `out` (here one
+        tensor) as cast_rays."""
+        if out is not None:
+            import torch
+            if not isinstance(out, torch.Tensor):
+                raise TypeError("cast_occlusion: out must be a torch.Tensor")
+            out = {"visibility": out}
+        return self._cast("cast_occlusion", origins, directions, t_max, _ffi.RF_RAYS_ANY, ("visibility",), out)["visibility"]
 
     # radiance second moments, the noise estimate and render-to-a-noise-target (include/rayfinder_amd.h states the estimate's arithmetic)
     def set_moments(self, enabled=True):

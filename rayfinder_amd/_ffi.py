@@ -53,6 +53,17 @@ class FeatureRequest(C.Structure):
     _fields_ = [("channels", C.c_uint32), ("layout", C.c_uint32), ("dtype", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+# rf_renderer_cast_rays: the kinds, and the outputs in the struct's order (name, kind, floats or words per ray, "f" float32 / "u" uint32)
+RF_RAYS_CLOSEST, RF_RAYS_ANY = 0, 1
+RAY_OUTPUTS = (("triangle", 0, 1, "u"), ("t", 0, 1, "f"), ("bary", 0, 2, "f"), ("position", 0, 3, "f"), ("geometric_normal", 0, 3, "f"), ("normal", 0, 3, "f"),
+               ("texcoord", 0, 2, "f"), ("albedo", 0, 3, "f"), ("texture", 0, 1, "u"), ("visibility", 1, 1, "f"))
+
+
+class RayBatch(C.Structure):
+    _fields_ = [("origins", C.c_void_p), ("directions", C.c_void_p), ("origin_stride", C.c_uint32), ("direction_stride", C.c_uint32), ("num_rays", C.c_uint64),
+                ("t_max", C.c_float), ("kind", C.c_uint32), ("reserved", C.c_uint32 * 2)] + [(name, C.c_void_p) for name, _, _, _ in RAY_OUTPUTS]
+
+
 class DenoiseParameters(C.Structure):
     _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float)]
 
@@ -255,6 +266,7 @@ SIGNATURES = {
     "rf_renderer_get_bounce_stats": (C.c_int, [C.c_void_p, C.c_uint32] + [C.c_void_p] * 5),
     "rf_renderer_intersect_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_float] + [C.c_void_p] * 6),
     "rf_renderer_occluded_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, C.c_void_p]),
+    "rf_renderer_cast_rays": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rf_intersect_bvh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint64, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
     "rf_intersect_bvh_batch": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint64, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rf_bvh_visualizer_pass": (C.c_int, [C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32,

@@ -1335,6 +1335,24 @@ int rf_renderer_occluded_rays(rf_renderer* r, const float* rays6, uint64_t num_r
     });
 }
 
+int rf_renderer_cast_rays(rf_renderer* r, const rf_ray_batch* batch)
+{
+    return guarded([&] {
+        require(r && batch, "null argument");
+        rf::RayQueryRequest q;
+        const auto          address = [](const void* p) { return static_cast<uint64_t>(reinterpret_cast<uintptr_t>(p)); };
+        q.origins = address(batch->origins), q.directions = address(batch->directions);
+        q.originStride = batch->origin_stride, q.directionStride = batch->direction_stride;
+        q.numRays = batch->num_rays, q.tMax = batch->t_max, q.kind = batch->kind;
+        q.reserved[0] = batch->reserved[0], q.reserved[1] = batch->reserved[1];
+        const void* const outputs[rf::kCastOutputs] = {batch->triangle, batch->t,        batch->bary,   batch->position, batch->geometric_normal,
+                                                       batch->normal,   batch->texcoord, batch->albedo, batch->texture,  batch->visibility};
+        for (uint32_t i = 0; i < rf::kCastOutputs; ++i) q.outputs[i] = address(outputs[i]);
+        r->impl->castRays(q);
+        return RF_OK;
+    });
+}
+
 // ---------------------------------------------------------------------------------------- CPU side
 int rf_build_bvh(const float* positions36, uint64_t num_triangles, void* nodes_out, uint64_t* num_nodes_out,
                  uint64_t* triangle_indices_out, int32_t* depth_out)

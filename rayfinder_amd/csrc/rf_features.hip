@@ -186,21 +186,27 @@ void requireFeatureDestination(const void* dst, uint64_t bytes, uint64_t needed,
     if (!dst) throw std::invalid_argument("null argument");
     if (bytes < needed)
         throw std::invalid_argument(name + ": the destination holds " + std::to_string(bytes) + " bytes, the frame's features need " + std::to_string(needed));
+    requireDeviceRange(dst, needed, deviceOrdinal, what, "the destination", "the frame's features", "the sums");
+}
+
+void requireDeviceRange(const void* p, uint64_t bytes, int deviceOrdinal, const char* what, const char* noun, const char* content, const char* owner)
+{
+    const std::string name(what), buffer(noun);
     hipPointerAttribute_t attr{};
-    if (hipPointerGetAttributes(&attr, dst) != hipSuccess)
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess)
     {
         (void)hipGetLastError(); // (the failed lookup must not show up as the next call's error)
-        throw std::invalid_argument(name + ": the destination is not device memory (hipPointerGetAttributes does not know the pointer)");
+        throw std::invalid_argument(name + ": " + buffer + " is not device memory (hipPointerGetAttributes does not know the pointer)");
     }
-    if (attr.type != hipMemoryTypeDevice) throw std::invalid_argument(name + ": the destination is not device memory (host, registered or managed memory is refused)");
+    if (attr.type != hipMemoryTypeDevice) throw std::invalid_argument(name + ": " + buffer + " is not device memory (host, registered or managed memory is refused)");
     if (attr.device != deviceOrdinal)
-        throw std::invalid_argument(name + ": the destination lies on device " + std::to_string(attr.device) + ", the sums on device " + std::to_string(deviceOrdinal));
-    // the allocation the pointer lies in, where the runtime can tell: the frame's features must fit behind the pointer
+        throw std::invalid_argument(name + ": " + buffer + " lies on device " + std::to_string(attr.device) + ", " + owner + " on device " + std::to_string(deviceOrdinal));
+    // the allocation the pointer lies in, where the runtime can tell: the bytes must fit behind the pointer
     hipDeviceptr_t base = nullptr;
     size_t         size = 0;
-    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(dst)) != hipSuccess) (void)hipGetLastError();
-    else if (static_cast<const char*>(dst) + needed > static_cast<const char*>(base) + size)
-        throw std::invalid_argument(name + ": the frame's features do not fit into the allocation behind the destination pointer");
+    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) (void)hipGetLastError();
+    else if (static_cast<const char*>(p) + bytes > static_cast<const char*>(base) + size)
+        throw std::invalid_argument(name + ": " + content + " do not fit into the allocation " + buffer + " points into");
 }
 
 void enqueueExportFeatures(hipStream_t stream, const FeatureSources& s, uint32_t width, uint32_t height, bool tileMajor, const FeatureRequest& request, void* dst)

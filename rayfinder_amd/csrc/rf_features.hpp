@@ -25,6 +25,11 @@ struct FeatureSources
 // std::invalid_argument unless hipPointerGetAttributes reports `dst` as device memory of device `deviceOrdinal` (a host pointer, registered or managed memory and
 // another device's memory are all refused), or when `bytes` is smaller than `needed`.  No launch.
 void requireFeatureDestination(const void* dst, uint64_t bytes, uint64_t needed, int deviceOrdinal, const char* what);
+// The pointer part of it, for any caller-owned buffer (rf_renderer_cast_rays checks every input and output with it): std::invalid_argument unless
+// hipPointerGetAttributes reports `p` as device memory of device `deviceOrdinal` and, where the runtime can tell the allocation, `bytes` fit behind it.  `what`: the
+// entry point, `noun`: the buffer ("the destination", "origins"), `content`: what must fit ("the frame's features"), `owner`: what lives on deviceOrdinal ("the sums",
+// "the scene").  No launch.
+void requireDeviceRange(const void* p, uint64_t bytes, int deviceOrdinal, const char* what, const char* noun, const char* content, const char* owner);
 
 // Enqueue the one export kernel on `stream`: one 256-lane workgroup per 32 x 32 tile.  tileMajor: the sums are compact tile-major buffers holding every tile of the
 // frame in tile order (a handle without a tile shard); else row-major.  width * height < 2^31; the request is valid; dst holds featureBytes() and is element aligned.

@@ -81,6 +81,7 @@ bool LaunchOptions::set(const std::string& name, int64_t value, bool wideUsable)
     else if (name == "occluder_grid_cells") optOccluderGridCells = static_cast<uint32_t>(std::clamp<int64_t>(value, 0, 1 << 16));
     else if (name == "occluder_cache_bounces") optOccluderCacheBounces = static_cast<uint32_t>(std::max<int64_t>(value, 0));
     else if (name == "query_variant") queryVariant = wideUsable ? static_cast<int>(value) : 0;
+    else if (name == "cast_chunk") optCastChunk = static_cast<uint32_t>(std::clamp<int64_t>(value, 0, 0xFFFFFFFFll));
     else if (name == "extra_lds") optExtraLds = static_cast<uint32_t>(std::max<int64_t>(value, 0)); // (the driver then sizes its persistent grid again: Renderer::setOption)
     else return false;
     return true;
@@ -308,6 +309,28 @@ BouncePlan planBounce(const LaunchOptions& o, const PolicyInputs& in, uint32_t b
     const uint32_t flagsRun = layoutShadow == kLayoutScalar ? (bounce == 1 ? 1u : 0u) : (layoutShadow == kLayoutPacket ? (shadowFlags & kFlagFirstBounce) : shadowFlags);
     p.shadow = resolveTraversal(o, in, true, layoutShadow, o.counting, nearest, flagsRun, o.optRefillMin, chunkNow, 0u, o.counting ? 0u : o.optExtraLds);
     return p;
+}
+
+TraversalPlan planRayQuery(const LaunchOptions& o, const PolicyInputs& in, bool anyHit)
+{
+    constexpr uint32_t kIncoherentBounce = 2u;
+    PolicyInputs       q = in;
+    q.numBounces = std::max(in.numBounces, kIncoherentBounce); // (bounce 2 is then never "the last bounce"; the traversal plans do not read it)
+    q.active.reset();
+    BatchPlan batch = planBatch(o, q, 1u);
+    batch.firstLookReady = false;
+    const BouncePlan p = planBounce(o, q, kIncoherentBounce, batch);
+    TraversalPlan    t = anyHit ? p.shadow : p.closest;
+    if (!in.facts.wideUsable || t.kernel != kKernelWide)
+    {
+        t = TraversalPlan{};
+        t.kernel = kKernelScalar, t.layout = kLayoutScalar, t.anyHit = anyHit;
+        return t;
+    }
+    // (an any-hit launch without the cache applies the exact quad records' boxes at the parent's step, as its uncached launches in the render path do)
+    t.flags &= ~(kFlagOccluderCache | kFlagOccluderNoTry | kFlagNoRayCount | kFlagFirstBounce | kFlagConstOrigin);
+    if (anyHit) t.flags |= kFlagShadowDirFromStream;
+    return t;
 }
 
 void writeLaunchPlan(const BatchPlan& batch, const BouncePlan& p, uint32_t bounce, rf_launch_plan& out)

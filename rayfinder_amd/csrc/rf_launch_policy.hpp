@@ -72,6 +72,7 @@ struct LaunchOptions
     uint32_t               optExtraLds = 0;      // experiment: dynamic LDS bytes added to the kTraceWide launches (lowers the occupancy)
     uint32_t               optPacketBounces = 0; // bounces 1..n traced by kTracePacket (one wave = one lockstep packet) instead of kTraceWide
     int                    optUniformFetch = 2; // scalar-cache fetch for wave-uniform steps: 0 = never (5 878 Mrays/s), 1 = records (6 039), 2 = records + leaf triangles (6 059), -1 = records at bounces 1-2 only
+    uint32_t optCastChunk = 0; // option cast_chunk: rf_renderer_cast_rays traces at most this many rays per chunk (0: what the path depth and the free memory allow; tests force many small chunks)
     uint32_t optSlotGroupShift = 0; // see FrameParams::slotGroupShift (r02 A/B on the atrium, Mrays/s: sample-major 5282; unsorted g = 6: 5416, 2: 5507, 0: 5450; with sorted samples g = 2: 5519, 1: 5589, 0: 5650)
 
     // the layouts the scene gets with no option set (SceneFacts: the five *FromBounce defaults)
@@ -196,6 +197,12 @@ int closestLayoutFor(const LaunchOptions& o, const PolicyInputs& in, uint32_t bo
 int shadowLayoutFor(const LaunchOptions& o, const PolicyInputs& in, uint32_t bounce);
 // does the any-hit launch of this bounce start at the occluder cache's entries? (kTraceWide, kFlagOccluderCache)
 bool cachedShadowFor(const LaunchOptions& o, const PolicyInputs& in, uint32_t bounce);
+// The traversal launch of a ray query (rf_renderer_cast_rays): a caller's rays are arbitrary, so they are planned as the render path plans an INCOHERENT launch of this
+// scene -- the closest-hit / any-hit launch of bounce 2 (planBounce: its layout, instantiation, refill count, chunk and leaf vote) -- without what belongs to a render
+// batch: no occluder cache and no first look (the cache is the batch's, a query neither uses nor disturbs it), no "first bounce", and an any-hit launch that reads its
+// directions from the ray stream (kFlagShadowDirFromStream).  kernel == kKernelScalar: the reference-order scalar traversal (a scene whose wide records are unusable,
+// traversal_variant 0, a packet-kernel experiment)
+TraversalPlan planRayQuery(const LaunchOptions& o, const PolicyInputs& in, bool anyHit);
 // The once-per-batch decisions, for a batch of numSamples samples of the shard's tiles (or of the `active` list of render_adaptive).  firstLookReady is the driver's
 // to fill in (traceBatch / nextBatchFirstLookReady)
 BatchPlan planBatch(const LaunchOptions& o, const PolicyInputs& in, uint32_t numSamples);

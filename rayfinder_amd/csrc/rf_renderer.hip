@@ -30,6 +30,7 @@
 #include "rf_kernels.hpp"
 #include "rf_launch_policy.hpp"
 #include "rf_noise.hpp"
+#include "rf_ray_query.hpp"
 #include "rf_robust.hpp"
 #include "rf_scene_pack.hpp"
 #include "rf_sums.hpp"
@@ -211,6 +212,8 @@ struct Renderer::Impl
     DeviceBuffer<float4>    sAov; // [2 slot, 2 slot + 1] the first-hit AOV record of each path (kShade<false, true>); allocated with the path state while the AOVs are on
     DeviceBuffer<uint32_t>  queueA, queueB, missQueue, missSlots, shadowList, queueCounts; // shadowList: kShade's list of the shadow rays its own-triangle test has not settled (kShadeSelfShadow)
     DeviceBuffer<DeviceCounters> counters;
+    DeviceBuffer<DeviceCounters> castCounters; // what the traversal launches of rf_renderer_cast_rays count into: never read (the query's rays are not render rays)
+    DeviceBuffer<uint32_t>       castWords;    // ... and their queue length and cursors, apart from queueCounts: [0] the count, [kLine ..) the launch's cursor lines
     DeviceBuffer<unsigned long long> bounceTotals; // 4 x kMaxBounceStats: closest-hit rays, shadow rays, shadow rays answered by kShadowFirstLook, shadow rays settled by kShade's own-triangle test
 
     // deferred-lighting variant: its own frame counter and buffers (array<array<f32, 3>>)
@@ -466,6 +469,7 @@ struct Renderer::Impl
         float           tMax;
         dim3            grid;
         uint32_t        blocksWanted = 0; // != 0: the launch's worst-case workgroup count; the grid becomes min(this, what the device holds of the kernel launched)
+        DeviceCounters* counters = nullptr; // nullptr: the handle's; a ray query's rays count into a block of their own (castRays), rf_stats never sees them
     };
     // Workgroups of THIS instantiation the device holds at once.  The persistent grid used to be sized once, from the closest-hit kernel (6 per CU: 80 VGPRs, 24 KB of LDS); the
     // any-hit instantiations need 63 ... 72 VGPRs and -- round 6: their stack holds child words only, 4 bytes per entry -- 12 KB: most of them fit 7 per CU.
@@ -487,7 +491,7 @@ struct Renderer::Impl
         if (k == nullptr) throw std::logic_error("kTraceWide: record layout " + std::to_string(t.layout) + " is not compiled into this build");
         dim3 grid = a.grid;
         if (a.blocksWanted != 0u && !wideBlocksForced && !t.count) grid = dim3(std::min(a.blocksWanted, residentBlocks(k, t.extraLds)));
-        hipLaunchKernelGGL(k, grid, dim3(kBlock), t.extraLds, stream, scene, w, sky, sunBasis, a.ps, a.queue, a.count, a.cursor, counters.ptr, t.refillMin, t.leafVote, t.chunk, a.tMax, t.flags);
+        hipLaunchKernelGGL(k, grid, dim3(kBlock), t.extraLds, stream, scene, w, sky, sunBasis, a.ps, a.queue, a.count, a.cursor, a.counters ? a.counters : counters.ptr, t.refillMin, t.leafVote, t.chunk, a.tMax, t.flags);
     }
     // Is a cached any-hit launch of the handle's NEXT batch free to run behind kShadowFirstLook, as far as the books a batch keeps go?  traceBatch's own bookkeeping,
     // foreseen without touching it (rf_renderer_launch_plan): a grid of another size starts cold, a report that has landed may start a hold-off, a running one counts down.
@@ -590,6 +594,47 @@ struct Renderer::Impl
             out1.resize(n);
             for (uint64_t i = 0; i < n; ++i) out1[i] = make_float4(packed[i].x, packed[i].y, packed[i].z, 0.0f);
         }
+    }
+
+    // rf_renderer_cast_rays: chunk by chunk kCastLoad, the traversal launch the policy picks, kCastResolve (rf_ray_query.hip), all on the handle's stream with one wait at
+    // the end.  The path state is scratch between render calls (as queryWide assumes); the queue words and the counter block are the query's own, the occluder grid and
+    // the first-look bookkeeping are neither read nor written.  Every refusal has been made before the first launch (Renderer::castRays).
+    void castRays(const RayQueryRequest& q, const ChunkPlan& chunks)
+    {
+        const bool          anyHit = q.kind == kRaysAny;
+        const TraversalPlan t = planRayQuery(options, policyInputs(), anyHit);
+        if (!ensurePathState(chunks.depth())) throw std::runtime_error("out of device memory for a chunk of " + std::to_string(chunks.depth()) + " rays (option cast_chunk makes the chunks smaller)");
+        constexpr uint32_t kWords = BatchCounters::kLine + BatchCounters::kCursorWords;
+        if (castWords.count < kWords) castWords.alloc(kWords);
+        if (castCounters.count < 1) castCounters.alloc(1);
+        RF_HIP(hipMemsetAsync(castCounters.ptr, 0, sizeof(DeviceCounters), stream));
+        const PathStreams ps{sRayO.ptr, sRayD.ptr, sThr.ptr, sRad.ptr, sHit.ptr, sPending.ptr, sNoise.ptr, sRayD2.ptr, sThr2.ptr, sNoise2.ptr};
+        WideScene         w = wide; // (no list of queue positions, no occluder grid: the render batches' own)
+        w.rayList = nullptr, w.occGrid = nullptr;
+        const uint32_t mask = q.mask();
+        const auto     advanced = [&](uint32_t output, uint64_t firstRay) -> uint64_t { return q.outputs[output] ? q.outputs[output] + firstRay * kCastOutputWidth[output] * 4u : 0u; };
+        for (uint64_t c = 0; c < chunks.count(); ++c)
+        {
+            const uint64_t firstRay = chunks.first(c);
+            // (workgroup counts in 64 bits: a chunk may hold up to 2^32 - 1 rays, whatever the device's memory allows today)
+            const uint32_t n = static_cast<uint32_t>(chunks.size(c));
+            const uint32_t blocks = static_cast<uint32_t>((uint64_t{n} + kBlock - 1) / kBlock), castBlocks = static_cast<uint32_t>((uint64_t{n} + kCastBlock - 1) / kCastBlock);
+            RF_HIP(hipMemsetAsync(castWords.ptr, 0, kWords * sizeof(uint32_t), stream)); // the cursors start at 0
+            hipLaunchKernelGGL(castLoadKernel(anyHit), dim3(castBlocks), dim3(kCastBlock), 0, stream, reinterpret_cast<const float*>(q.origins + firstRay * q.originStride * 4u),
+                               reinterpret_cast<const float*>(q.directions + firstRay * q.directionStride * 4u), q.originStride, q.directionStride, n, ps, queueA.ptr, castWords.ptr);
+            if (t.kernel == kKernelWide)
+                launchWide(t, w, WideArgs{ps, queueA.ptr, castWords.ptr, castWords.ptr + BatchCounters::kLine, q.tMax, dim3(std::min(blocks, wideBlocks)), blocks, castCounters.ptr});
+            else hipLaunchKernelGGL(castScalarKernel(anyHit), dim3(blocks), dim3(kBlock), 0, stream, scene, ps, n, q.tMax);
+            CastOutputs out{};
+            out.triangle = reinterpret_cast<uint32_t*>(advanced(0, firstRay)), out.t = reinterpret_cast<float*>(advanced(1, firstRay));
+            out.bary = reinterpret_cast<float*>(advanced(2, firstRay)), out.position = reinterpret_cast<float*>(advanced(3, firstRay));
+            out.geometricNormal = reinterpret_cast<float*>(advanced(4, firstRay)), out.normal = reinterpret_cast<float*>(advanced(5, firstRay));
+            out.texcoord = reinterpret_cast<float*>(advanced(6, firstRay)), out.albedo = reinterpret_cast<float*>(advanced(7, firstRay));
+            out.texture = reinterpret_cast<uint32_t*>(advanced(8, firstRay)), out.visibility = reinterpret_cast<float*>(advanced(9, firstRay));
+            hipLaunchKernelGGL(castResolveKernel(), dim3(castBlocks), dim3(kCastBlock), 0, stream, scene, sHit.ptr, sRad.ptr, out, n, mask);
+        }
+        RF_HIP(hipGetLastError());
+        RF_HIP(hipStreamSynchronize(stream)); // the outputs may be used from any stream once the call returns
     }
 
     // Before the first sample of an accumulation: zero the sums that were cleared (the image, and the AOV sums / moments while they are on), sized for the shard
@@ -2009,5 +2054,23 @@ void Renderer::occludedRays(const float* rays6, uint64_t numRays, float tMax, fl
     RF_HIP(hipStreamSynchronize(m.stream));
     RF_HIP(hipMemcpy(visibilityOut, vis.ptr, numRays * 4, hipMemcpyDeviceToHost));
 }
-} // namespace rf
 
+void Renderer::castRays(const RayQueryRequest& q)
+{
+    Impl& m = *mImpl;
+    if (q.numRays == 0) return; // nothing is read, checked or touched
+    checkRayQueryRequest(q);
+    checkRayQueryOverlaps(q); // (every range's arithmetic first: it refuses what does not fit 64 bits)
+    RF_HIP(hipSetDevice(m.device));
+    const ByteRange origins = inputRange(q.origins, q.numRays, q.originStride, "origins"), directions = inputRange(q.directions, q.numRays, q.directionStride, "directions");
+    requireDeviceRange(reinterpret_cast<const void*>(q.origins), origins.end - origins.begin, m.device, "rf_renderer_cast_rays", "origins", "the rays", "the scene");
+    requireDeviceRange(reinterpret_cast<const void*>(q.directions), directions.end - directions.begin, m.device, "rf_renderer_cast_rays", "directions", "the rays", "the scene");
+    for (uint32_t i = 0; i < kCastOutputs; ++i)
+    {
+        if (q.outputs[i] == 0u) continue;
+        const ByteRange r = outputRange(q, i);
+        requireDeviceRange(reinterpret_cast<const void*>(q.outputs[i]), r.end - r.begin, m.device, "rf_renderer_cast_rays", kCastOutputName[i], "the rays' values", "the scene");
+    }
+    m.castRays(q, planChunks(q.numRays, m.maxPaths, m.pathsThatFit(), m.options.optCastChunk));
+}
+} // namespace rf

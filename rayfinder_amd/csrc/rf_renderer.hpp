@@ -13,6 +13,7 @@
 
 #include "rf_books.hpp" // SumCoverage, SumCount
 #include "rf_bvh.hpp" // SceneView
+#include "rf_ray_query_request.hpp"
 #include "rf_sky.hpp"
 #include "rf_types.hpp"
 
@@ -457,6 +458,10 @@ public:
     void intersectRays(const float* rays6, uint64_t numRays, float tMax, uint32_t* triangleOut, float* tOut, float* uvOut,
                        float* pOut, uint32_t* nodesVisitedOut, uint32_t* triangleTestsOut);
     void occludedRays(const float* rays6, uint64_t numRays, float tMax, float* visibilityOut);
+    // rf_renderer_cast_rays (the definition: include/rayfinder_amd.h): rays from caller-owned device memory through the production traversal, the hit and the surface
+    // attributes at it into caller-owned device memory, in chunks of one path-state allocation; enqueued on the handle's stream, then waited for.  Read-only for the
+    // handle's sums, books and statistics.  std::invalid_argument, before any launch, for what the header lists (the request's own checks: rf_ray_query_request.hpp)
+    void castRays(const RayQueryRequest& request);
 
 private:
     struct Impl;

@@ -56,6 +56,37 @@ __device__ __forceinline__ ShadeRecord fetchShadeRecord(const DeviceScene& scene
     return r;
 }
 
+// The surface at a hit, barycentrics (hu, hv) on the triangle of `cur`: what shadeHit computes of it, as functions of their own so that the ray queries' resolve kernel
+// (kCastResolve, rf_ray_query.hip) gives a caller the very values the shading stage uses -- same functions, same order of operations.
+// The hit point pushed off the surface along the geometric normal (wgsl:511-519,523-544): origin of the shadow ray and of the next bounce; same arithmetic as the scalar
+// traversal (rf_device.hpp).  geometricNormal: normalize(cross(e1, e2)), the normal it is pushed along.
+// (The point is computed BEFORE the normal, as the arguments of the one offsetRay call shadeHit used to make were evaluated: with the two statements exchanged kShade and
+// kPrimaryFused compile to other instructions -- same values, another schedule -- and tools/kernel_code_compare.py against the commit before says CHANGED.)
+__device__ __forceinline__ Vec3 offsetHitPoint(const ShadeRecord& cur, float hu, float hv, Vec3& geometricNormal)
+{
+    const Vec3 p0 = cur.p0, p1 = cur.p1, p2 = cur.p2;
+    const Vec3 e1 = p1 - p0, e2 = p2 - p0;
+    const Vec3 p = p0 + hu * e1 + hv * e2;
+    geometricNormal = normalize(cross(e1, e2));
+    return offsetRay(p, geometricNormal);
+}
+// The interpolated shading normal (not normalised, wgsl:396) and texture coordinates (not wrapped); the texture's descriptor index is __float_as_uint(cur.a3.w)
+__device__ __forceinline__ void interpolateAttributes(const ShadeRecord& cur, float hu, float hv, Vec3& n, float& uvx, float& uvy)
+{
+    const float4  a0 = cur.a0, a1 = cur.a1, a2 = cur.a2, a3 = cur.a3;
+    const Vec3    n0 = vec3(a0.x, a0.y, a0.z), n1 = vec3(a0.w, a1.x, a1.y), n2 = vec3(a1.z, a1.w, a2.x);
+    const float   b0 = 1.0f - hu - hv, b1 = hu, b2 = hv; // wgsl:515
+    n = (b0 * n0 + b1 * n1) + b2 * n2;
+    uvx = (b0 * a2.y + b1 * a2.w) + b2 * a3.y;
+    uvy = (b0 * a2.z + b1 * a3.x) + b2 * a3.z;
+}
+// The first-hit AOV's normal: the unit shading normal, 0 where n has no direction (|n|^2 zero or not finite)
+__device__ __forceinline__ Vec3 unitShadingNormal(Vec3 n)
+{
+    const float nn = dot(n, n);
+    return (nn != 0.0f && isfinite(nn)) ? normalize(n) : Vec3{};
+}
+
 // Shade one hit: barycentrics (hu, hv) on the triangle of `cur`, written at position `out` of the next queue.  `inputs(throughput, nz)` hands in the path's throughput
 // and blue-noise triple {u.x, cos(2 pi u.y), sin(2 pi u.y)} (asked for after the origin's store, where kShade has always loaded them); `slotOf()` the path's slot
 // (needed by the AOV record and by a settled shadow ray only).  -> false: the shadow ray was stopped by the triangle it starts on (kShadeSelfShadow) and is finished
@@ -80,11 +111,8 @@ __device__ __forceinline__ bool shadeHit(const DeviceScene& scene, const SkyStat
 {
     Vec3 shadowOrigin;
     {
-        // hit point pushed off the surface along the geometric normal (wgsl:511-519,523-544): origin of
-        // the shadow ray and of the next bounce; same arithmetic as the scalar traversal (rf_device.hpp)
-        const Vec3 p0 = cur.p0, p1 = cur.p1, p2 = cur.p2;
-        const Vec3 e1 = p1 - p0, e2 = p2 - p0;
-        const Vec3 hp = offsetRay(p0 + hu * e1 + hv * e2, normalize(cross(e1, e2)));
+        Vec3       geometricNormal;
+        const Vec3 hp = offsetHitPoint(cur, hu, hv, geometricNormal);
         store3nt(ps.rayO + out, hp); // (this bounce's origins have been consumed by the closest-hit launch)
         shadowOrigin = hp;
     }
@@ -92,12 +120,10 @@ __device__ __forceinline__ bool shadeHit(const DeviceScene& scene, const SkyStat
     inputs(throughput, nz);
     const float nx = nz.x, cosPhi = nz.y, sinPhi = nz.z;
     store3nt(ps.noiseOut + out, nz); // travels with the path: dense for this bounce's shadow launch and for the next kShade
-    const float4  a0 = cur.a0, a1 = cur.a1, a2 = cur.a2, a3 = cur.a3;
-    const Vec3    n0 = vec3(a0.x, a0.y, a0.z), n1 = vec3(a0.w, a1.x, a1.y), n2 = vec3(a1.z, a1.w, a2.x);
-    const float   b0 = 1.0f - hu - hv, b1 = hu, b2 = hv; // wgsl:515
-    const Vec3    n = (b0 * n0 + b1 * n1) + b2 * n2;         // not normalised, wgsl:396
-    const float   uvx = (b0 * a2.y + b1 * a2.w) + b2 * a3.y;
-    const float   uvy = (b0 * a2.z + b1 * a3.x) + b2 * a3.z;
+    const float4  a3 = cur.a3;
+    Vec3          n; // not normalised, wgsl:396
+    float         uvx, uvy;
+    interpolateAttributes(cur, hu, hv, n, uvx, uvy);
 #if defined(RF_EXP_SHADE_ABLATE) && (RF_EXP_SHADE_ABLATE == 1 || RF_EXP_SHADE_ABLATE == 4)
     const Vec3    albedo = SORTED ? vec3(sLut[__float_as_uint(a3.w) & 255u], uvx - floorf(uvx), uvy - floorf(uvy)) : evalTexture(scene, sLut, __float_as_uint(a3.w), uvx, uvy); // ablation (timing only): no texel fetch
 #else
@@ -106,9 +132,7 @@ __device__ __forceinline__ bool shadeHit(const DeviceScene& scene, const SkyStat
     if constexpr (AOV)
     {
         // first-hit AOVs: the texel, the unit shading normal (0 where n has no direction: |n|^2 zero or not finite) and the distance along the unit primary direction
-        const float nn = dot(n, n);
-        const Vec3  unitN = (nn != 0.0f && isfinite(nn)) ? normalize(n) : Vec3{};
-        storeAov(aov, slotOf(), albedo, 1.0f, unitN, hitT);
+        storeAov(aov, slotOf(), albedo, 1.0f, unitShadingNormal(n), hitT);
     }
     else (void)hitT, (void)aov;
 
