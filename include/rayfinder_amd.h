@@ -561,6 +561,91 @@ RF_API int rf_robust_mean_tiles(int32_t device_ordinal, uint32_t width, uint32_t
                                 float* out_rgba, uint32_t* out_bgra8, uint8_t* out_trim);
 RF_API int rf_renderer_denoise_robust(rf_renderer* r, const rf_denoise_parameters* params);
 
+/* Temporal history: the last view's frame reprojected into a new camera.  A camera change restarts the accumulation and the first frames of the new view are as noisy
+ * as if the previous one had never been rendered; but the scene is static, so the first hit of a pixel can be looked up in the previous view's frame, and where the
+ * surface is the same one the previous view's samples stand behind the new view's.  One side kernel over planes the handle keeps anyway; the trace and shading
+ * kernels, every sum and every other snapshot are untouched.  No reference counterpart.
+ *
+ * The definition.  Inputs: the sums S, AC, ND of one accumulation with ONE count N (Nf = float(N)), the camera C of that accumulation, the frame size W x H
+ * (Wf = float(W), Hf = float(H)); the history -- the previous view's camera C' and two row-major float4 planes of the same W x H, T' = {mean colour rgb, effective
+ * sample count h} and G' = {unit normal xyz, depth z}, G'.w = 0 marking background -- which may be absent; and rf_temporal_parameters {max_history, depth_tolerance,
+ * min_normal_dot, reserved}: max_history and depth_tolerance finite and > 0, min_normal_dot in [-1, 1], reserved = 0.  All arithmetic is f32, one IEEE operation at a
+ * time in the order written, with the parentheses written (correctly rounded divide and sqrt, denormals kept, no FMA contraction; the only conversions are float(uint)
+ * and one float-to-integer conversion that is guarded before it happens): a numpy float32 restatement reproduces T, G and the texels bit for bit.  dot(a, b) =
+ * (a.x b.x + a.y b.y) + a.z b.z;  cross(a, b) = (a.y b.z - b.y a.z, a.z b.x - b.z a.x, a.x b.y - b.x a.y);  a scalar times a vector and a sum of vectors work per
+ * component.  Per pixel p = (x, y), y counted from the top as everywhere:
+ *   1 prep:         exactly the denoiser's prep (above): c = S.rgb / Nf;  z = ND.w / AC.w;  background iff AC.w == 0 or not (z > 0);  otherwise m = ND.xyz / Nf,
+ *                   d = dot(m, m), n = (d != 0 and |d| <= FLT_MAX) ? m (1 / sqrt(d)) : 0.
+ *                   background:  T = {c, Nf}, G = {0, 0, 0, 0}; steps 2 .. 4 are not taken (sky pixels take no history: they carry no noise).
+ *   2 world point:  kRaygen's own expressions with the blue-noise pair replaced by its mean (0.5, 0.5) and no lens offset -- a thin-lens camera is accepted and
+ *                   treated as its pinhole centre `origin`; lens_radius, up and right are not read:
+ *                   u = (float(x) + 0.5) / Wf;  v = (float(y) + 0.5) / Hf;  s = u + (0.5 / Wf);  t = (1 - v) + (0.5 / Hf)
+ *                   e = ((llc + s horizontal) + t vertical) - origin;  dir = e (1 / sqrt(dot(e, e)));  P = origin + (z dir)
+ *   3 old view:     no history given: NO HISTORY.  Otherwise, with the members of C':
+ *                   w = P - origin';  L = llc' - origin';  Nn = cross(horizontal', vertical');  den = dot(Nn, w);  k = dot(Nn, L) / den
+ *                   not (k > 0) -- the point lies behind or in the plane through origin' parallel to the old image plane, or k is NaN: NO HISTORY.  (k w is where the
+ *                   line from origin' to P meets the old image plane.  The sign of den alone does not say "in front": it depends on the handedness of horizontal' x
+ *                   vertical', and for the cameras rf_create_camera makes Nn points AWAY from the scene; the ratio k does not.)
+ *                   q = (k w) - L;  nn = dot(Nn, Nn)
+ *                   a = dot(cross(q, vertical'), Nn) / nn;  b = dot(cross(horizontal', q), Nn) / nn      (Cramer's rule: horizontal' and vertical' need not be
+ *                   perpendicular)
+ *                   fx = (a Wf) - 1;  fy = (1 - b) Hf      (the continuous pixel coordinate: step 2 inverted in real arithmetic; a pixel centre maps to an integer)
+ *                   not (fx >= -1 and fx < Wf and fy >= -1 and fy < Hf): NO HISTORY -- written so that a NaN fails, and decided BEFORE any conversion to an integer.
+ *                   xf = floor(fx);  yf = floor(fy);  tx = fx - xf;  ty = fy - yf;  x0 = int(xf);  y0 = int(yf)      (-1 <= x0 <= W - 1, -1 <= y0 <= H - 1)
+ *                   z' = sqrt(dot(w, w))      (the depth the old view would have recorded for P)
+ *   4 taps:         the four taps (x0 + i, y0 + j) in the order j = 0, 1, inside it i = 0, 1, with bx = i ? tx : (1 - tx), by = j ? ty : (1 - ty), β = bx by.
+ *                   A tap is VALID iff it lies inside the frame and, with its T' and G':  T'.w > 0  and  G'.w > 0  and  |G'.w - z'| <= (depth_tolerance z')  and
+ *                   dot(n, G'.xyz) >= min_normal_dot  (every comparison false for a NaN).  An invalid tap is SKIPPED, not multiplied by zero: a NaN or an
+ *                   infinity in an invalid tap does not reach the output; one in a valid tap does.
+ *                   From +0, in tap order over the valid taps:  sumB += β;  sumC.rgb += β T'.rgb;  sumH += β T'.w
+ *                   not (sumB > 0): NO HISTORY.  Otherwise hist = sumC.rgb / sumB;  h = sumH / sumB.
+ *   5 blend:        NO HISTORY:  T = {c, Nf}.  Otherwise he = (h < max_history) ? h : max_history (a NaN h gives max_history);
+ *                   T.rgb = ((Nf c) + (he hist)) / (Nf + he) per channel;  T.w = Nf + he.
+ *                   G = {n, z} for a foreground pixel.  The BGRA8 texel is kTonemap over T.rgb with accumulatedSamples = 1 and the exposure, as for the robust mean.
+ * T.w is the weight the NEXT view gives this frame: the samples behind a pixel, capped at max_history so that an old frame's lighting fades out.
+ *
+ * rf_temporal_default_parameters: max_history = 64, depth_tolerance = 0.05, min_normal_dot = 0.9 (kept after the sweep of profiles/temporal/README.md:
+ * over a six-view orbit of the Duck at 4 samples per view every one of the 36 triples takes the RMSE against 1024 samples from 1.70 to 1.11 - 1.16; the sweep's best
+ * is 16 / 0.02 / 0.8 at 1.1075, these values give 1.1312 -- 2.1 % above it; the depth tolerance orders the table, and 0.05 is kept for surfaces at a grazing angle).
+ * rf_renderer_temporal_accumulate: the definition over the handle's own sums, its current camera and its kept history, if it has one (rf_renderer_temporal_commit);
+ * params NULL = the defaults.  Enqueued on the handle's stream: ONE kernel (kTemporalReproject) does prep, reprojection, blend and the texel; the tile-major sums are read
+ * where they lie, and row-major and tile-major sources give identical bits.  The result is a snapshot -- T, G, the texels, the camera and the count N -- tracked as the
+ * denoise snapshot is, and dropped whenever the AOV sums are cleared.  Calling it again later in the same accumulation recomputes from the SAME history: history is
+ * never counted twice.  The first call allocates two pairs of float4 planes and one u32 plane, 68 bytes per pixel (rf_renderer_memory_info counts them in
+ * path_state_bytes once they exist; a handle that never calls it allocates nothing).  RF_ERROR_INVALID_ARGUMENT, before any launch and with the state kept, in this
+ * order: a NULL handle; bad parameters; the AOVs off; the AOV sample count different from the accumulated count; no sample accumulated; a tile shard set (use
+ * rf_temporal_images on the gathered sums -- the root of a frame gather has no history of its own); the non-uniform state of rf_renderer_render_adaptive.
+ * rf_renderer_temporal_commit: the current result becomes the history, by a pointer swap and no copy; the result snapshot is then gone (refused without one).  The
+ * history survives a restart of the accumulation -- that is its purpose -- and is dropped when the frame size changes, when a tile shard is set, and by
+ * rf_renderer_temporal_reset, which drops the result snapshot as well and keeps the buffers.
+ * rf_renderer_read_temporal: row-major width*height*4 floats {T.rgb, T.w}, the BGRA8 texels, width*height*4 floats G and the snapshot's sample count N; any pointer may
+ * be NULL.  RF_ERROR_INVALID_ARGUMENT without a result.
+ * rf_renderer_denoise_temporal: rf_renderer_temporal_accumulate, then the a-trous filter of rf_renderer_denoise with prep's colour c = T.rgb (rf_renderer_denoise_robust's
+ * one change, with T in M's place); the result is the ordinary denoise snapshot (rf_renderer_read_denoised).  Refused as either half would be.
+ * rf_temporal_images: the same kernel over row-major host planes on device device_ordinal: color_sum4 / albedo_coverage4 / normal_depth4 of `samples` samples, the
+ * camera, and the history (history_color4 = T', history_geometry4 = G', history_camera = C': all three NULL or all three given); out_color4 = T, out_geometry4 = G,
+ * out_bgra8 may be NULL.  Synchronous.  A NULL input, a zero size, a zero sample count, a history given in part and bad parameters are refused before any device call.
+ * These calls leave every sum, count and tile count, the other snapshots, rf_renderer_read_tonemapped, the stats, the frame counter and rf_renderer_state_digest exactly
+ * as they were.  NOT covered, deliberately: a tile shard and the root of a gather (refused); the non-uniform state (refused); the history is not part of a checkpoint
+ * or of the state digest; rf-render has no option for it; the geometry does not move -- the scene is static. */
+typedef struct rf_temporal_parameters
+{
+    float    max_history;     /* finite, > 0: the cap on the effective sample count a pixel takes from the history */
+    float    depth_tolerance; /* finite, > 0: a tap is the same surface when |z_tap - z'| <= depth_tolerance z' */
+    float    min_normal_dot;  /* in [-1, 1]: ... and when dot(n, n_tap) >= min_normal_dot */
+    uint32_t reserved;        /* 0 */
+} rf_temporal_parameters;
+RF_API int rf_temporal_default_parameters(rf_temporal_parameters* params);
+RF_API int rf_renderer_temporal_accumulate(rf_renderer* r, const rf_temporal_parameters* params);
+RF_API int rf_renderer_temporal_commit(rf_renderer* r);
+RF_API int rf_renderer_temporal_reset(rf_renderer* r);
+RF_API int rf_renderer_read_temporal(rf_renderer* r, float* rgba, uint32_t* bgra8, float* geometry, uint32_t* sample_count);
+RF_API int rf_renderer_denoise_temporal(rf_renderer* r, const rf_temporal_parameters* tparams, const rf_denoise_parameters* dparams);
+RF_API int rf_temporal_images(int32_t device_ordinal, uint32_t width, uint32_t height, uint32_t samples, const float* color_sum4, const float* albedo_coverage4,
+                              const float* normal_depth4, const rf_camera* camera, const float* history_color4, const float* history_geometry4,
+                              const rf_camera* history_camera, const rf_temporal_parameters* params, float exposure, float* out_color4, float* out_geometry4,
+                              uint32_t* out_bgra8);
+
 /* Tile-adaptive sampling: a render call that keeps sampling only the 32x32 tiles that are still noisy, and the per-tile sample count that the reads then honour.
  * No reference counterpart.  rf_renderer_render_adaptive: the whole frame only (no tile shard; across ranks: rf_comm_render_adaptive, below); needs the moments on from the first sample and the AOVs off, or on with RF_AOV_TILE_COUNTS
  * (from the first sample as well).

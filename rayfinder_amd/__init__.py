@@ -881,6 +881,50 @@ def robust_mean_images(buckets, samples, exposure=1.0, device_ordinal=0):
     return dict(mean=rgba[..., :3], bgra8=bgra, trim=trim, samples=int(samples))
 
 
+def temporal_defaults():
+    """-> dict of the temporal history's default parameters (rf_temporal_default_parameters)."""
+    d = _ffi.TemporalParameters()
+    check(lib.rf_temporal_default_parameters(C.byref(d)))
+    return dict(max_history=d.max_history, depth_tolerance=d.depth_tolerance, min_normal_dot=d.min_normal_dot)
+
+
+def _temporal_parameters(params):
+    unknown = set(params) - {"max_history", "depth_tolerance", "min_normal_dot"}
+    if unknown:
+        raise TypeError(f"unknown temporal parameters: {sorted(unknown)}")
+    p = dict(temporal_defaults(), **params)
+    return _ffi.TemporalParameters(float(p["max_history"]), float(p["depth_tolerance"]), float(p["min_normal_dot"]), 0)
+
+
+def _camera_arg(cam):
+    return cam if isinstance(cam, _ffi.Camera) else camera_from_array(cam)
+
+
+def temporal_images(color_sum, albedo_coverage, normal_depth, samples, camera, history=None, exposure=1.0, device_ordinal=0, **params):
+    """rf_temporal_images: the temporal reprojection over (H,W,4) f32 sums held on the host (accumulation, {albedo, coverage}, {normal, depth}) of `samples` samples seen
+    by `camera` (_ffi.Camera or its 19 floats).  history: None, or dict(color (H,W,4) = {mean rgb, effective sample count}, geometry (H,W,4) = {unit normal, depth},
+    camera): the previous view's result as this function or read_temporal returns it, plus its camera.  Keyword arguments: max_history, depth_tolerance,
+    min_normal_dot.  -> dict(color (H,W,4) f32 {T.rgb, T.w}, geometry (H,W,4) f32 {n, z}, bgra8 (H,W) u32 display texels under `exposure`, samples)."""
+    color_sum, albedo_coverage, normal_depth = (_f32(a) for a in (color_sum, albedo_coverage, normal_depth))
+    h, w = color_sum.shape[:2]
+    planes = [color_sum, albedo_coverage, normal_depth]
+    hist_color = hist_geometry = hist_camera = None
+    if history is not None:
+        hist_color, hist_geometry = _f32(history["color"]), _f32(history["geometry"])
+        hist_camera = C.byref(_camera_arg(history["camera"]))
+        planes += [hist_color, hist_geometry]
+    for a in planes:
+        if a.shape != (h, w, 4):
+            raise ValueError("temporal_images: the sums and the history planes must be (H, W, 4) arrays of one size")
+    color = np.zeros((h, w, 4), np.float32)
+    geometry = np.zeros((h, w, 4), np.float32)
+    bgra = np.zeros((h, w), np.uint32)
+    check(lib.rf_temporal_images(device_ordinal, w, h, int(samples), _ptr(color_sum), _ptr(albedo_coverage), _ptr(normal_depth), C.byref(_camera_arg(camera)),
+                                 _ptr(hist_color), _ptr(hist_geometry), hist_camera, C.byref(_temporal_parameters(params)), exposure, _ptr(color), _ptr(geometry),
+                                 _ptr(bgra)))
+    return dict(color=color, geometry=geometry, bgra8=bgra, samples=int(samples))
+
+
 def robust_mean_tiles(buckets, tile_samples, exposure=1.0, device_ordinal=0):
     """rf_robust_mean_tiles: robust_mean_images with one sample count (>= K) per 32x32 tile, tile_samples in tile order (tile_y * ceil(W / 32) + tile_x): every
     pixel is combined with its own tile's count (read_buckets and read_tile_samples of a frame of render_adaptive).  -> dict(mean, bgra8, trim, tile_samples)."""
@@ -1165,6 +1209,38 @@ class ReferencePathTracer:
         """robust_mean, then denoise with the robust mean in place of the plain mean (needs what both need); read_denoised reads the result.  Keyword arguments as
         for denoise."""
         check(lib.rf_renderer_denoise_robust(self._h, C.byref(_denoise_parameters(params))))
+
+    # the temporal history (include/rayfinder_amd.h, "Temporal history"): the previous view's frame reprojected into the current camera
+    def temporal_accumulate(self, **params):
+        """Blend the current view's samples with the kept history, reprojected into the current camera (needs the AOVs on from the first sample, at least one sample,
+        no tile shard, the uniform state); without a history the result is the plain mean.  Calling it again later in the same accumulation recomputes from the same
+        history.  Keyword arguments: max_history, depth_tolerance, min_normal_dot (temporal_defaults()).  read_temporal reads the result."""
+        check(lib.rf_renderer_temporal_accumulate(self._h, C.byref(_temporal_parameters(params))))
+
+    def temporal_commit(self):
+        """The current temporal result becomes the history of the views that follow (no copy); the result is then gone.  The history survives
+        set_render_parameters; a new frame size, a tile shard and temporal_reset drop it."""
+        check(lib.rf_renderer_temporal_commit(self._h))
+
+    def temporal_reset(self):
+        """Drop the temporal history and the current result (a cut: the next view shares nothing with the last)."""
+        check(lib.rf_renderer_temporal_reset(self._h))
+
+    def read_temporal(self):
+        """-> dict(color (H,W,4) f32 {T.rgb, T.w = the effective sample count}, bgra8 (H,W) u32 display texels, geometry (H,W,4) f32 {unit normal, depth; zeros:
+        background}, samples: the count of the current view's accumulation)"""
+        h, w = self._params.height, self._params.width
+        rgba = np.zeros((h, w, 4), np.float32)
+        bgra = np.zeros((h, w), np.uint32)
+        geometry = np.zeros((h, w, 4), np.float32)
+        n = C.c_uint32(0)
+        check(lib.rf_renderer_read_temporal(self._h, _ptr(rgba), _ptr(bgra), _ptr(geometry), C.byref(n)))
+        return dict(color=rgba, bgra8=bgra, geometry=geometry, samples=n.value)
+
+    def denoise_temporal(self, temporal=None, **params):
+        """temporal_accumulate (temporal: its parameter dict, None = the defaults), then denoise with the temporal result in place of the plain mean; read_denoised
+        reads the result.  Keyword arguments as for denoise."""
+        check(lib.rf_renderer_denoise_temporal(self._h, C.byref(_temporal_parameters(dict(temporal or {}))), C.byref(_denoise_parameters(params))))
 
     def noise_estimate(self):
         """The noise estimate over the accumulation and the moments (needs the moments on from the first sample, >= 2 samples, no tile shard).

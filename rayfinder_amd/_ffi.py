@@ -68,6 +68,10 @@ class DenoiseParameters(C.Structure):
     _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float)]
 
 
+class TemporalParameters(C.Structure):
+    _fields_ = [("max_history", C.c_float), ("depth_tolerance", C.c_float), ("min_normal_dot", C.c_float), ("reserved", C.c_uint32)]
+
+
 class NoiseEstimate(C.Structure):
     _fields_ = [("mean_error", C.c_double), ("max_error", C.c_float), ("worst_tile", C.c_uint32), ("samples", C.c_uint32), ("pixels", C.c_uint64),
                 ("nonfinite_pixels", C.c_uint64)]
@@ -208,6 +212,14 @@ SIGNATURES = {
     "rf_robust_mean_images": (C.c_int, [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rf_robust_mean_tiles": (C.c_int, [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rf_renderer_denoise_robust": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rf_temporal_default_parameters": (C.c_int, [C.c_void_p]),
+    "rf_renderer_temporal_accumulate": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rf_renderer_temporal_commit": (C.c_int, [C.c_void_p]),
+    "rf_renderer_temporal_reset": (C.c_int, [C.c_void_p]),
+    "rf_renderer_read_temporal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
+    "rf_renderer_denoise_temporal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rf_temporal_images": (C.c_int, [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rf_renderer_noise_estimate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rf_noise_estimate_images": (C.c_int, [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rf_renderer_render_until": (C.c_int, [C.c_void_p, C.c_float, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p]),

@@ -71,6 +71,7 @@ void AccumulationBooks::restart(Family f)
     mSums[f].dirty = true;
     if (kWords[f].drops == Drops::Denoised) mDenoised.valid = false;
     if (kWords[f].drops == Drops::RobustMean) mRobust.valid = false;
+    if (f == kAovs) mTemporal.valid = false; // (the temporal result is made from S and the AOV sums; S never restarts without them.  The temporal HISTORY stays)
 }
 
 void AccumulationBooks::restartAccumulation()
@@ -341,6 +342,32 @@ void AccumulationBooks::refuseReadDenoised() const
 void AccumulationBooks::refuseReadRobustMean() const
 {
     if (!mRobust.valid) throw std::invalid_argument("no robust mean: call rf_renderer_robust_mean first (the image is dropped when the accumulation or the bucket sums are cleared)");
+}
+
+// The temporal history.  The count check is skipped while nothing is accumulated: the two counts then agree, at 0 (a family's count never exceeds the accumulated one),
+// and "no sample" is the message.
+void AccumulationBooks::refuseTemporalAccumulate(bool denoise) const
+{
+    const std::string what = denoise ? "denoise_temporal" : "temporal_accumulate";
+    requireOn(what, kAovs);
+    if (mAccumulated != 0u) requireCovers(what, kAovs);
+    requireSamples(what);
+    requireWholeFrame(what, " (use rf_temporal_images on the gathered sums)");
+    requireUniform(denoise ? "rf_renderer_denoise_temporal" : "rf_renderer_temporal_accumulate");
+}
+
+void AccumulationBooks::refuseTemporalCommit() const
+{
+    if (!mTemporal.valid)
+        throw std::invalid_argument("no temporal result to commit: call rf_renderer_temporal_accumulate first (the result is dropped when the accumulation or the AOVs are "
+                                    "cleared, and a commit takes it)");
+}
+
+void AccumulationBooks::refuseReadTemporal() const
+{
+    if (!mTemporal.valid)
+        throw std::invalid_argument("no temporal result: call rf_renderer_temporal_accumulate first (the result is dropped when the accumulation or the AOVs are cleared, "
+                                    "and a commit takes it)");
 }
 
 void AccumulationBooks::requireShardRobustMean() const

@@ -74,7 +74,7 @@ public:
     uint32_t worldSize() const { return mWorldSize; }
     uint32_t shardTiles() const { return mShardTiles; }
     void     setSampleCap(uint32_t samplesPerPixel) { mSampleCap = samplesPerPixel; }
-    void     setShard(uint32_t rank, uint32_t worldSize) { mRank = rank, mWorldSize = worldSize; } // (refuseSetTileShard has passed)
+    void     setShard(uint32_t rank, uint32_t worldSize) { mRank = rank, mWorldSize = worldSize, mTemporalHistory = false; } // (refuseSetTileShard has passed; the temporal history goes)
     void     setShardTiles(uint32_t numTiles) { mShardTiles = numTiles; }                          // (the caller restarts the accumulation)
     // Tile-adaptive sampling.  The per-tile counts, by slot of the shard; EMPTY = the uniform state: every tile holds `accumulated` samples (the only state a handle that
     // never called render_adaptive is ever in).  Non-empty: the counts differ, `accumulated` is the leading count L, and the tiles still at L are the only ones a later
@@ -111,6 +111,16 @@ public:
     uint32_t robustSamples() const { return mRobust.samples; }
     void     noteDenoised() { mDenoised = {true, mAccumulated}; } // (the snapshot's sample count is the leading count)
     void     noteRobustMean() { mRobust = {true, mAccumulated}; }
+    // ... and the temporal result (rf_renderer_temporal_accumulate: the current view's sums blended with the reprojected history), tracked as the denoised image is and
+    // dropped with the AOV sums; and the temporal HISTORY, which is not a snapshot of this accumulation: a commit makes the result the history (the result is then gone),
+    // restartAccumulation leaves it -- that is its purpose --, and a new frame size (frameResized), a tile shard (setShard) and resetTemporal drop it.
+    bool     temporalValid() const { return mTemporal.valid; }
+    uint32_t temporalSamples() const { return mTemporal.samples; }
+    bool     temporalHistory() const { return mTemporalHistory; }
+    void     noteTemporal() { mTemporal = {true, mAccumulated}; }
+    void     commitTemporal() { mTemporal.valid = false, mTemporalHistory = true; } // (refuseTemporalCommit has passed)
+    void     resetTemporal() { mTemporal.valid = false, mTemporalHistory = false; }
+    void     frameResized() { mTemporalHistory = false; } // (the caller restarts the accumulation)
 
     // ---- transitions
     // A new accumulation (new parameters, another shard, another accumulation buffer): no sample, every tile at the same count, every sum to be zeroed before the
@@ -151,6 +161,11 @@ public:
     void refuseExportFeatures(uint32_t reads, bool twoSamples) const;
     void refuseReadDenoised() const;
     void refuseReadRobustMean() const;
+    // the temporal history: the AOVs on, their count the accumulated count, a sample, the whole frame, the uniform state -- in that order; denoise: the call is
+    // rf_renderer_denoise_temporal (whose second half, the denoiser's own refusals, these imply)
+    void refuseTemporalAccumulate(bool denoise = false) const;
+    void refuseTemporalCommit() const;
+    void refuseReadTemporal() const;
     void requireShardRobustMean() const;               // Renderer::enqueueShardRobustMean: the caller has checked, so std::logic_error
     void requireSlotAddressing(bool shardSlots) const; // Renderer::renderAdaptiveFrom
 
@@ -194,6 +209,7 @@ private:
     std::vector<uint32_t> mTileSamples;
     uint32_t              mFrameLeadingSamples = 0, mFrameMinTileSamples = 0;
     Sums                  mSums[kFamilies];
-    Snapshot              mDenoised, mRobust;
+    Snapshot              mDenoised, mRobust, mTemporal;
+    bool                  mTemporalHistory = false;
 };
 } // namespace rf

@@ -138,6 +138,18 @@ rf::DenoiseParameters toDenoiseParams(const rf_denoise_parameters* p)
     out.sigmaColor = p->sigma_color, out.sigmaNormal = p->sigma_normal, out.sigmaDepth = p->sigma_depth;
     return out;
 }
+// the temporal history's parameters (NULL: the defaults), checked before anything touches a device
+rf::TemporalParameters toTemporalParams(const rf_temporal_parameters* p)
+{
+    rf::TemporalParameters out;
+    if (!p) return out;
+    require(std::isfinite(p->max_history) && p->max_history > 0.0f, "temporal max_history must be finite and > 0");
+    require(std::isfinite(p->depth_tolerance) && p->depth_tolerance > 0.0f, "temporal depth_tolerance must be finite and > 0");
+    require(p->min_normal_dot >= -1.0f && p->min_normal_dot <= 1.0f, "temporal min_normal_dot must lie in [-1, 1]");
+    require(p->reserved == 0u, "temporal parameters: reserved must be 0");
+    out.maxHistory = p->max_history, out.depthTolerance = p->depth_tolerance, out.minNormalDot = p->min_normal_dot;
+    return out;
+}
 // one component's parameters of the split-component denoiser (NULL: that component's default)
 rf::DenoiseParameters toSplitParams(const rf_denoise_parameters* p, const rf::DenoiseParameters& fallback) { return p ? toDenoiseParams(p) : fallback; }
 rf_noise_estimate toNoiseEstimate(const rf::NoiseEstimate& e)
@@ -588,6 +600,84 @@ int rf_renderer_denoise_robust(rf_renderer* r, const rf_denoise_parameters* para
         const rf::DenoiseParameters p = toDenoiseParams(params);
         require(r, "null argument");
         r->impl->denoiseRobust(p);
+        return RF_OK;
+    });
+}
+
+int rf_temporal_default_parameters(rf_temporal_parameters* params)
+{
+    return guarded([&] {
+        require(params, "null argument");
+        const rf::TemporalParameters d;
+        *params = rf_temporal_parameters{d.maxHistory, d.depthTolerance, d.minNormalDot, 0u};
+        return RF_OK;
+    });
+}
+
+int rf_renderer_temporal_accumulate(rf_renderer* r, const rf_temporal_parameters* params)
+{
+    return guarded([&] {
+        require(r, "null argument");
+        const rf::TemporalParameters p = toTemporalParams(params);
+        r->impl->temporalAccumulate(p);
+        return RF_OK;
+    });
+}
+
+int rf_renderer_temporal_commit(rf_renderer* r)
+{
+    return guarded([&] {
+        require(r, "null argument");
+        r->impl->temporalCommit();
+        return RF_OK;
+    });
+}
+
+int rf_renderer_temporal_reset(rf_renderer* r)
+{
+    return guarded([&] {
+        require(r, "null argument");
+        r->impl->temporalReset();
+        return RF_OK;
+    });
+}
+
+int rf_renderer_read_temporal(rf_renderer* r, float* rgba, uint32_t* bgra8, float* geometry, uint32_t* sample_count)
+{
+    return guarded([&] {
+        require(r, "null argument");
+        r->impl->readTemporal(rgba, bgra8, geometry, sample_count);
+        return RF_OK;
+    });
+}
+
+int rf_renderer_denoise_temporal(rf_renderer* r, const rf_temporal_parameters* tparams, const rf_denoise_parameters* dparams)
+{
+    return guarded([&] {
+        require(r, "null argument");
+        const rf::TemporalParameters tp = toTemporalParams(tparams);
+        const rf::DenoiseParameters  dp = toDenoiseParams(dparams);
+        r->impl->denoiseTemporal(tp, dp);
+        return RF_OK;
+    });
+}
+
+int rf_temporal_images(int32_t device_ordinal, uint32_t width, uint32_t height, uint32_t samples, const float* color_sum4, const float* albedo_coverage4,
+                       const float* normal_depth4, const rf_camera* camera, const float* history_color4, const float* history_geometry4, const rf_camera* history_camera,
+                       const rf_temporal_parameters* params, float exposure, float* out_color4, float* out_geometry4, uint32_t* out_bgra8)
+{
+    return guarded([&] {
+        const rf::TemporalParameters p = toTemporalParams(params);
+        require(color_sum4 && albedo_coverage4 && normal_depth4 && camera, "null argument");
+        const int given = (history_color4 ? 1 : 0) + (history_geometry4 ? 1 : 0) + (history_camera ? 1 : 0);
+        require(given == 0 || given == 3, "the history is given whole or not at all: history_color4, history_geometry4 and history_camera are all NULL or all set");
+        require(width > 0 && height > 0, "image size must be non-zero");
+        require(static_cast<uint64_t>(width) * height < (1ull << 31), "image too large");
+        require(samples > 0, "sample count must be > 0");
+        require(std::isfinite(exposure), "exposure must be finite");
+        const rf::Camera cam = toCamera(*camera), old = history_camera ? toCamera(*history_camera) : cam;
+        rf::temporalImages(device_ordinal, width, height, samples, color_sum4, albedo_coverage4, normal_depth4, cam, history_color4, history_geometry4,
+                           history_camera ? &old : nullptr, p, exposure, out_color4, out_geometry4, out_bgra8);
         return RF_OK;
     });
 }

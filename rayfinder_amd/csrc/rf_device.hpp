@@ -360,6 +360,25 @@ __device__ __forceinline__ float wPow(float x, float y)
 {
     return static_cast<float>(pow(static_cast<double>(x), static_cast<double>(y)));
 }
+// wgsl:59-63,277-285 -> the BGRA8Unorm texel of one pixel's radiance sum, for kTemporalReproject (rf_temporal.hip), which forms its texel in the lane that blended the
+// pixel.  The text is kTonemap's body (rf_shade.hip), operation for operation.  kTonemap keeps its own copy: calling this function from it compiled to the same
+// arithmetic behind an inverted loop branch, and rf_shade.hip's code object is held byte for byte.  tests/test_gpu_temporal.py holds the texels to the CPU restatement of the display transform.
+__device__ __forceinline__ uint32_t tonemapTexel(float4 px, uint32_t accumulatedSamples, float exposure)
+{
+    const float in[3] = {px.x, px.y, px.z};
+    uint32_t    q[3];
+    for (int c = 0; c < 3; ++c)
+    {
+        const float est = in[c] / static_cast<float>(accumulatedSamples);
+        const float x = exposure * est;
+        const float a = 2.51f, b = 0.03f, cc = 2.43f, d = 0.59f, e = 0.14f;
+        float       y = (x * (a * x + b)) / (x * (cc * x + d) + e);
+        y = minf(maxf(y, 0.0f), 1.0f);
+        const float srgb = wPow(y, 1.0f / 2.2f);
+        q[c] = static_cast<uint32_t>(floorf(srgb * 255.0f + 0.5f));
+    }
+    return q[2] | (q[1] << 8) | (q[0] << 16) | (255u << 24);
+}
 // pow(x, 1.5f) of the sky model's Mie term = x * sqrt(x) in f64 (correctly rounded sqrt, one rounded product: within 1.5 ulp(f64) of
 // x^1.5), the same expression in the test oracle.  Negative x gives NaN, -0 gives +0... as pow does.
 __device__ __forceinline__ float wPow15(float x)

@@ -32,6 +32,7 @@
 #include "rf_noise.hpp"
 #include "rf_ray_query.hpp"
 #include "rf_robust.hpp"
+#include "rf_temporal.hpp"
 #include "rf_scene_pack.hpp"
 #include "rf_sums.hpp"
 
@@ -200,6 +201,8 @@ struct Renderer::Impl
     DeviceBuffer<float4>    robustShard; // enqueueShardRobustMean's {M.rgb, float(c)} of the shard's pixels, shard-compact tile-major: what the frame gather sends as plane 4
     // the denoiser (rf_renderer_denoise): its work buffers, allocated by the first denoise, and the snapshot they hold (valid: the books)
     DenoiseWork             denoiseWork;
+    // the temporal history (rf_renderer_temporal_accumulate): the result's and the history's planes, allocated by the first call (which of them is valid: the books)
+    TemporalWork            temporalWork;
     NoiseWork               noiseWork; // the estimate's device buffers, allocated by the first rf_renderer_noise_estimate
     DeviceBuffer<uint32_t>  tileSamplesDevice; // the per-tile counts (the books') for the per-tile reads (mean, tonemap, estimate), uploaded by them
     DeviceBuffer<float4>    meanImage;         // rf_renderer_read_mean / the non-uniform rf_renderer_read_tonemapped: compact tile-major, allocated by the first read
@@ -1190,7 +1193,7 @@ void Renderer::setRenderParameters(const RenderParameters& p)
     m.updateSunBasis();
     m.books.setSampleCap(p.samplingParams.numSamplesPerPixel);
     m.books.restartAccumulation();
-    if (resized) m.configureShard();
+    if (resized) m.books.frameResized(), m.configureShard(); // (the temporal history is of the old size: gone)
 }
 
 void Renderer::setTileShard(uint32_t rank, uint32_t worldSize)
@@ -1446,6 +1449,55 @@ void Renderer::denoiseRobust(const DenoiseParameters& params)
     // (per tile: the counts robustMean uploaded are still on the device, and nothing but this stream reads them)
     enqueueDenoise(m.stream, m.denoiseWork, m.image, m.aovAlbedoCoverage(), m.aovNormalDepth(), m.params.width, m.params.height, m.grid().tilesX, m.books.accumulated(), params,
                    m.params.exposure, m.books.nonUniform() ? m.tileSamplesDevice.ptr : nullptr, m.robustWork.mean.ptr);
+    m.books.noteDenoised();
+}
+
+void Renderer::temporalAccumulate(const TemporalParameters& params)
+{
+    Impl& m = *mImpl;
+    m.books.refuseTemporalAccumulate();
+    RF_HIP(hipSetDevice(m.device));
+    TemporalWork& w = m.temporalWork;
+    w.reserve(static_cast<uint64_t>(m.params.width) * m.params.height, m.stream);
+    const bool     history = m.books.temporalHistory();
+    const uint32_t out = w.result, in = w.history();
+    enqueueTemporal(m.stream, m.image, m.aovAlbedoCoverage(), m.aovNormalDepth(), m.params.width, m.params.height, m.grid().tilesX, m.books.accumulated(), m.params.camera,
+                    history ? w.color[in].ptr : nullptr, history ? w.geometry[in].ptr : nullptr, history ? &w.camera[in] : nullptr, params, m.params.exposure, w.color[out].ptr,
+                    w.geometry[out].ptr, w.bgra.ptr);
+    w.camera[out] = m.params.camera;
+    m.books.noteTemporal();
+}
+
+void Renderer::temporalCommit()
+{
+    Impl& m = *mImpl;
+    m.books.refuseTemporalCommit();
+    m.temporalWork.commit(); // (the next accumulate writes the other pair: on the same stream, behind whatever still reads it)
+    m.books.commitTemporal();
+}
+
+void Renderer::temporalReset() { mImpl->books.resetTemporal(); }
+
+void Renderer::readTemporal(float* rgba, uint32_t* bgra8, float* geometry, uint32_t* sampleCount)
+{
+    Impl& m = *mImpl;
+    m.books.refuseReadTemporal();
+    synchronize();
+    const TemporalWork& w = m.temporalWork;
+    const size_t        n = static_cast<size_t>(m.params.width) * m.params.height;
+    if (rgba) RF_HIP(hipMemcpy(rgba, w.color[w.result].ptr, n * sizeof(float4), hipMemcpyDeviceToHost));
+    if (bgra8) RF_HIP(hipMemcpy(bgra8, w.bgra.ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (geometry) RF_HIP(hipMemcpy(geometry, w.geometry[w.result].ptr, n * sizeof(float4), hipMemcpyDeviceToHost));
+    if (sampleCount) *sampleCount = m.books.temporalSamples();
+}
+
+void Renderer::denoiseTemporal(const TemporalParameters& temporal, const DenoiseParameters& params)
+{
+    Impl& m = *mImpl;
+    m.books.refuseTemporalAccumulate(true);
+    temporalAccumulate(temporal);
+    enqueueDenoise(m.stream, m.denoiseWork, m.image, m.aovAlbedoCoverage(), m.aovNormalDepth(), m.params.width, m.params.height, m.grid().tilesX, m.books.accumulated(), params,
+                   m.params.exposure, nullptr, m.temporalWork.color[m.temporalWork.result].ptr);
     m.books.noteDenoised();
 }
 
@@ -1741,7 +1793,7 @@ void Renderer::memoryInfo(uint64_t& pathStateBytes, uint64_t& pathsAllocated, ui
 {
     const Impl& m = *mImpl;
     pathsAllocated = m.allocatedPaths;
-    pathStateBytes = m.pathStateBytes() + m.storage[Books::kDirect].buffers[0].count * sizeof(float4) + m.primaryListBytes(); // (the direct sums, while they are on: 16 B per pixel of the shard's tiles; the leaf lists of bounce 1)
+    pathStateBytes = m.pathStateBytes() + m.storage[Books::kDirect].buffers[0].count * sizeof(float4) + m.primaryListBytes() + m.temporalWork.bytes(); // (the direct sums, while they are on: 16 B per pixel of the shard's tiles; the leaf lists of bounce 1; the temporal planes once they exist: 68 B per pixel)
     maxPathsPerBatch = m.effectivePaths ? std::min(m.effectivePaths, m.maxPaths) : m.maxPaths;
     sceneBytes = (m.nodes.count + m.triangles.count + m.wideNodes.count + m.wideCompact.count + m.wideHot.count + m.wideOwn.count + m.wideQuad.count + m.wideQuadHalf.count + m.wideQuadLocal.count + m.wideOct.count + m.attributes.count + m.shadeRecords.count) * sizeof(float4) +
                  m.texels.count * sizeof(uint32_t) + m.bigLeaves.count * sizeof(uint2) + m.occluderGrid.count * sizeof(uint32_t); // (the occluder grid: allocated by the first batch)

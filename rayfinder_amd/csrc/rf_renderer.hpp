@@ -177,6 +177,19 @@ void robustMeanImages(int deviceOrdinal, uint32_t width, uint32_t height, uint32
 void robustMeanTiles(int deviceOrdinal, uint32_t width, uint32_t height, uint32_t K, const uint32_t* tileSamples, const float* buckets, float exposure, float* outRgba,
                      uint32_t* outBgra8, uint8_t* outTrim);
 
+// The temporal history (rf_temporal.hip; the definition: include/rayfinder_amd.h, "Temporal history"): maxHistory and depthTolerance finite and > 0, minNormalDot in
+// [-1, 1] (the C ABI checks them before any device call)
+struct TemporalParameters
+{
+    float maxHistory = 64.0f, depthTolerance = 0.05f, minNormalDot = 0.9f;
+};
+// The reprojection over host-assembled row-major width*height*4 sums of `samples` samples seen by `camera`, and a history of the same size -- histColor = {mean rgb,
+// effective sample count}, histGeometry = {unit normal, depth}, histCamera: all three nullptr (no history) or all three given -- on device `deviceOrdinal`: outColor =
+// {T.rgb, T.w}, outGeometry = {n, z}, the BGRA8 of T.rgb under `exposure` (NULL = skip).  Synchronous; allocates and frees its own device memory.
+void temporalImages(int deviceOrdinal, uint32_t width, uint32_t height, uint32_t samples, const float* colorSum, const float* albedoCoverage, const float* normalDepth,
+                    const Camera& camera, const float* histColor, const float* histGeometry, const Camera* histCamera, const TemporalParameters& params, float exposure,
+                    float* outColor, float* outGeometry, uint32_t* outBgra8);
+
 // The noise estimate over the accumulation and the radiance second moments (rf_noise.hip; the definition: include/rayfinder_amd.h)
 struct NoiseEstimate
 {
@@ -316,6 +329,20 @@ public:
     // robustMean, then the a-trous filter of denoise with prep's colour c = M.rgb: the result is denoise's snapshot (readDenoised).  Refused as denoise and robustMean are
     // (the non-uniform state: the AOVs with kAovTileCounts and the buckets with kBucketsTileCounts, both covering the accumulation; prep divides by each tile's count).
     void denoiseRobust(const DenoiseParameters& params);
+    // The temporal history (rf_renderer_temporal_*; the arithmetic: include/rayfinder_amd.h, "Temporal history").  temporalAccumulate: the current view's sums blended
+    // with the kept history reprojected into the current camera, enqueued on the handle's stream; keeps a snapshot (T, G, texels, camera, count: allocated by the first
+    // call, dropped whenever the AOV sums are cleared); a later call in the same accumulation recomputes from the same history.  std::invalid_argument when the AOVs
+    // are off or do not cover the accumulation, nothing is accumulated, a tile shard is set or the tiles hold different counts.
+    // temporalCommit: the result becomes the history (a swap of roles, no copy) and the snapshot is gone; std::invalid_argument without a result.  The history survives
+    // a restart of the accumulation; a change of the frame size, a tile shard and temporalReset drop it.
+    // readTemporal: row-major width*height*4 floats {T.rgb, T.w}, BGRA8, width*height*4 floats {n, z} (NULL = skip) and the snapshot's sample count;
+    // std::invalid_argument without a result.
+    void temporalAccumulate(const TemporalParameters& params);
+    void temporalCommit();
+    void temporalReset();
+    void readTemporal(float* rgba, uint32_t* bgra8, float* geometry, uint32_t* sampleCount);
+    // temporalAccumulate, then the a-trous filter of denoise with prep's colour c = T.rgb: the result is denoise's snapshot (readDenoised).  Refused as either half is.
+    void denoiseTemporal(const TemporalParameters& temporal, const DenoiseParameters& params);
     // The noise estimate over the handle's own sums (rf_renderer_noise_estimate): enqueued on the handle's stream, then waited for.  std::invalid_argument when the
     // moments are off, their count differs from the accumulated count, fewer than 2 samples are accumulated or a tile shard is set.  Host pointers, NULL = skip.
     NoiseEstimate noiseEstimate(float* errorMap, float* tileSum, float* tileMax);
