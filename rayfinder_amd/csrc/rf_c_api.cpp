@@ -99,6 +99,19 @@ void require(bool cond, const char* what)
     if (!cond) throw std::invalid_argument(what);
 }
 
+// The *_tiles calls' counts, one per tile of the frame's 32 x 32 grid: each at least `minimum` (else `what`) -> the leading one
+uint32_t requireTileSamples(const uint32_t* tile_samples, uint32_t width, uint32_t height, uint32_t minimum, const char* what)
+{
+    const uint32_t tiles = ((width + 31u) / 32u) * ((height + 31u) / 32u);
+    uint32_t       leading = 0;
+    for (uint32_t t = 0; t < tiles; ++t)
+    {
+        require(tile_samples[t] >= minimum, what);
+        leading = tile_samples[t] > leading ? tile_samples[t] : leading;
+    }
+    return leading;
+}
+
 rf::Vec3 v3(const float* p) { return rf::vec3(p[0], p[1], p[2]); }
 
 rf::Camera toCamera(const rf_camera& c)
@@ -371,13 +384,7 @@ int rf_denoise_tiles(int32_t device_ordinal, uint32_t width, uint32_t height, co
         require(tile_samples && color_sum4 && albedo_coverage4 && normal_depth4, "null argument");
         require(width > 0 && height > 0, "image size must be non-zero");
         require(static_cast<uint64_t>(width) * height < (1ull << 31), "image too large");
-        const uint32_t tiles = ((width + 31u) / 32u) * ((height + 31u) / 32u);
-        uint32_t       leading = 0;
-        for (uint32_t t = 0; t < tiles; ++t)
-        {
-            require(tile_samples[t] > 0, "the sample count of every tile must be > 0");
-            leading = tile_samples[t] > leading ? tile_samples[t] : leading;
-        }
+        const uint32_t leading = requireTileSamples(tile_samples, width, height, 1u, "the sample count of every tile must be > 0");
         require(std::isfinite(exposure), "exposure must be finite");
         rf::denoiseTiles(device_ordinal, width, height, tile_samples, leading, color_sum4, albedo_coverage4, normal_depth4, p, exposure, out_rgba, out_bgra8);
         return RF_OK;
@@ -454,13 +461,7 @@ int rf_denoise_split_tiles(int32_t device_ordinal, uint32_t width, uint32_t heig
         require(tile_samples && color_sum4 && direct_sum4 && albedo_coverage4 && normal_depth4, "null argument");
         require(width > 0 && height > 0, "image size must be non-zero");
         require(static_cast<uint64_t>(width) * height < (1ull << 31), "image too large");
-        const uint32_t tiles = ((width + 31u) / 32u) * ((height + 31u) / 32u);
-        uint32_t       leading = 0;
-        for (uint32_t t = 0; t < tiles; ++t)
-        {
-            require(tile_samples[t] > 0, "the sample count of every tile must be > 0");
-            leading = tile_samples[t] > leading ? tile_samples[t] : leading;
-        }
+        const uint32_t leading = requireTileSamples(tile_samples, width, height, 1u, "the sample count of every tile must be > 0");
         require(std::isfinite(exposure), "exposure must be finite");
         rf::denoiseSplitTiles(device_ordinal, width, height, tile_samples, leading, color_sum4, direct_sum4, albedo_coverage4, normal_depth4, pd, pi, exposure, out_rgba,
                               out_bgra8);
@@ -586,8 +587,7 @@ int rf_robust_mean_tiles(int32_t device_ordinal, uint32_t width, uint32_t height
         require(width > 0 && height > 0, "image size must be non-zero");
         require(static_cast<uint64_t>(width) * height < (1ull << 31), "image too large");
         require(K % 2u == 1u && K >= 3u && K <= 15u, "K must be odd with 3 <= K <= 15");
-        const uint32_t tiles = ((width + 31u) / 32u) * ((height + 31u) / 32u);
-        for (uint32_t t = 0; t < tiles; ++t) require(tile_samples[t] >= K, "every bucket of every tile needs a sample: every tile count must be >= K");
+        (void)requireTileSamples(tile_samples, width, height, K, "every bucket of every tile needs a sample: every tile count must be >= K");
         require(std::isfinite(exposure), "exposure must be finite");
         rf::robustMeanTiles(device_ordinal, width, height, K, tile_samples, buckets, exposure, out_rgba, out_bgra8, out_trim);
         return RF_OK;
@@ -751,13 +751,7 @@ int rf_noise_estimate_tiles(int32_t device_ordinal, uint32_t width, uint32_t hei
         require(tile_samples && color_sum4 && sumsq4 && out, "null argument");
         require(width > 0 && height > 0, "image size must be non-zero");
         require(static_cast<uint64_t>(width) * height < (1ull << 31), "image too large");
-        const uint32_t tiles = ((width + 31u) / 32u) * ((height + 31u) / 32u);
-        uint32_t       leading = 0;
-        for (uint32_t t = 0; t < tiles; ++t)
-        {
-            require(tile_samples[t] >= 2, "a variance needs a sample count >= 2 in every tile");
-            leading = tile_samples[t] > leading ? tile_samples[t] : leading;
-        }
+        const uint32_t leading = requireTileSamples(tile_samples, width, height, 2u, "a variance needs a sample count >= 2 in every tile");
         *out = toNoiseEstimate(rf::noiseEstimateTiles(device_ordinal, width, height, tile_samples, leading, color_sum4, sumsq4, error_map, tile_sum, tile_max));
         return RF_OK;
     });

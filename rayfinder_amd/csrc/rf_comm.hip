@@ -431,6 +431,26 @@ struct TileComm::Impl
             throw std::invalid_argument(std::string(what) + ": the last gather did not carry " + needName);
     }
 
+    // What the root-side passes read (rf_frame_sums.hpp): the gathered planes where they lie, row-major, at the recorded N -- gathered with the counts, each tile its
+    // own.  (A plane the last gather did not carry is whatever an earlier one left: requireGathered is the caller's check.)
+    bool      perTile() const { return (gatheredMask & kGatherMaskTileCounts) != 0u; }
+    FrameSums gathered() const
+    {
+        return FrameSums{images[kPlaneImage].ptr, images[kPlaneMoments].ptr, images[kPlaneAlbedoCoverage].ptr, images[kPlaneNormalDepth].ptr, images[kPlaneDirect].ptr, imageW, imageH, 0u,
+                         gatheredSamples, perTile() ? frameCounts.ptr : nullptr};
+    }
+    // ... and what they check behind their planes, in this order: `minimum` samples (1, or a variance's 2), a frame the kernels can index and, gathered with the
+    // counts, `minimum` samples in every tile
+    void requireSamples(const char* what, uint32_t minimum) const
+    {
+        const std::string name(what);
+        const bool        variance = minimum >= 2u;
+        if (gatheredSamples < minimum) throw std::invalid_argument(name + (variance ? ": a variance needs at least 2 accumulated samples" : ": the gathered sums hold no sample"));
+        if (static_cast<uint64_t>(imageW) * imageH >= (1ull << 31)) throw std::invalid_argument(name + ": image too large");
+        if (perTile() && *std::min_element(frameCountsHost.begin(), frameCountsHost.end()) < minimum)
+            throw std::invalid_argument(name + (variance ? ": a variance needs at least 2 samples in every tile of the gathered frame" : ": a tile of the gathered frame holds no sample"));
+    }
+
     // ---- one gather, step by step (TileComm::gatherPlanes).  What the steps share:
     struct Gather
     {
@@ -709,15 +729,11 @@ void TileComm::denoise(const DenoiseParameters& params, float exposure, void* st
 {
     Impl& m = *mImpl;
     m.requireGathered("rf_comm_denoise", kPlaneMaskImage | kPlaneMaskAovs, "the first-hit AOVs (gather with RF_GATHER_AOVS)");
-    if (m.gatheredSamples == 0u) throw std::invalid_argument("rf_comm_denoise: the gathered sums hold no sample");
-    if (static_cast<uint64_t>(m.imageW) * m.imageH >= (1ull << 31)) throw std::invalid_argument("rf_comm_denoise: image too large");
-    const bool perTile = (m.gatheredMask & kGatherMaskTileCounts) != 0u;
-    if (perTile && *std::min_element(m.frameCountsHost.begin(), m.frameCountsHost.end()) == 0u) throw std::invalid_argument("rf_comm_denoise: a tile of the gathered frame holds no sample");
+    m.requireSamples("rf_comm_denoise", 1u);
     RF_HIP(hipSetDevice(m.device));
     // the gathered planes are row-major (tilesX = 0) and hold one count N: the filter rf_denoise_images runs, without the sums leaving the device -- or, gathered with
     // the counts, each tile its own: rf_denoise_tiles'
-    enqueueDenoise(static_cast<hipStream_t>(streamHandle), m.denoiseWork, m.images[kPlaneImage].ptr, m.images[kPlaneAlbedoCoverage].ptr, m.images[kPlaneNormalDepth].ptr, m.imageW,
-                   m.imageH, 0u, m.gatheredSamples, params, exposure, perTile ? m.frameCounts.ptr : nullptr);
+    enqueueDenoise(static_cast<hipStream_t>(streamHandle), m.denoiseWork, m.gathered(), params, exposure);
     m.denoisedValid = true;
 }
 
@@ -739,21 +755,10 @@ NoiseEstimate TileComm::noiseEstimate(float* errorMap, float* tileSum, float* ti
 {
     Impl& m = *mImpl;
     m.requireGathered("rf_comm_noise_estimate", kPlaneMaskImage | kPlaneMaskMoments, "the radiance second moments (gather with RF_GATHER_MOMENTS)");
-    if (m.gatheredSamples < 2u) throw std::invalid_argument("rf_comm_noise_estimate: a variance needs at least 2 accumulated samples");
-    if (static_cast<uint64_t>(m.imageW) * m.imageH >= (1ull << 31)) throw std::invalid_argument("rf_comm_noise_estimate: image too large");
+    m.requireSamples("rf_comm_noise_estimate", 2u);
     RF_HIP(hipSetDevice(m.device));
-    if (m.gatheredMask & kGatherMaskTileCounts)
-    {
-        // every tile with its own count; `samples` reports the largest
-        if (*std::min_element(m.frameCountsHost.begin(), m.frameCountsHost.end()) < 2u)
-            throw std::invalid_argument("rf_comm_noise_estimate: a variance needs at least 2 samples in every tile of the gathered frame");
-        TileSelection sel;
-        sel.tileSamplesDevice = m.frameCounts.ptr;
-        return runNoiseEstimateTiles(static_cast<hipStream_t>(streamHandle), m.noiseWork, m.images[kPlaneImage].ptr, m.images[kPlaneMoments].ptr, m.imageW, m.imageH, false, sel,
-                                     m.gatheredSamples, errorMap, tileSum, tileMax, nullptr);
-    }
-    return runNoiseEstimate(static_cast<hipStream_t>(streamHandle), m.noiseWork, m.images[kPlaneImage].ptr, m.images[kPlaneMoments].ptr, m.imageW, m.imageH, false,
-                            m.gatheredSamples, errorMap, tileSum, tileMax);
+    // (gathered with the counts: every tile with its own count; `samples` reports the largest)
+    return runNoiseEstimate(static_cast<hipStream_t>(streamHandle), m.noiseWork, m.gathered(), errorMap, tileSum, tileMax);
 }
 
 uint32_t TileComm::readTileSamples(uint32_t* tileSamples) const
@@ -812,15 +817,10 @@ void TileComm::denoiseRobust(const DenoiseParameters& params, float exposure, vo
     Impl& m = *mImpl;
     m.requireGathered("rf_comm_denoise_robust", kPlaneMaskImage | kPlaneMaskAovs, "the first-hit AOVs (gather with RF_GATHER_AOVS | RF_GATHER_ROBUST_MEAN)");
     m.requireGathered("rf_comm_denoise_robust", kPlaneMaskRobustMean, "the robust mean (plane 4: gather with RF_GATHER_AOVS | RF_GATHER_ROBUST_MEAN)");
-    if (m.gatheredSamples == 0u) throw std::invalid_argument("rf_comm_denoise_robust: the gathered sums hold no sample");
-    if (static_cast<uint64_t>(m.imageW) * m.imageH >= (1ull << 31)) throw std::invalid_argument("rf_comm_denoise_robust: image too large");
-    const bool perTile = (m.gatheredMask & kGatherMaskTileCounts) != 0u;
-    if (perTile && *std::min_element(m.frameCountsHost.begin(), m.frameCountsHost.end()) == 0u)
-        throw std::invalid_argument("rf_comm_denoise_robust: a tile of the gathered frame holds no sample");
+    m.requireSamples("rf_comm_denoise_robust", 1u);
     RF_HIP(hipSetDevice(m.device));
     // denoise()'s call with prep's colour = the gathered M (rf_denoise.hpp: plane 0 is then not read)
-    enqueueDenoise(static_cast<hipStream_t>(streamHandle), m.denoiseWork, m.images[kPlaneImage].ptr, m.images[kPlaneAlbedoCoverage].ptr, m.images[kPlaneNormalDepth].ptr, m.imageW,
-                   m.imageH, 0u, m.gatheredSamples, params, exposure, perTile ? m.frameCounts.ptr : nullptr, m.images[kPlaneRobustMean].ptr);
+    enqueueDenoise(static_cast<hipStream_t>(streamHandle), m.denoiseWork, m.gathered(), params, exposure, m.images[kPlaneRobustMean].ptr);
     m.denoisedValid = true;
 }
 
@@ -829,15 +829,10 @@ void TileComm::denoiseSplit(const DenoiseParameters& direct, const DenoiseParame
     Impl& m = *mImpl;
     m.requireGathered("rf_comm_denoise_split", kPlaneMaskImage | kPlaneMaskAovs, "the first-hit AOVs (gather with RF_GATHER_AOVS | RF_GATHER_DIRECT)");
     m.requireGathered("rf_comm_denoise_split", kPlaneMaskDirect, "the direct sums (plane 5, D: gather with RF_GATHER_AOVS | RF_GATHER_DIRECT)");
-    if (m.gatheredSamples == 0u) throw std::invalid_argument("rf_comm_denoise_split: the gathered sums hold no sample");
-    if (static_cast<uint64_t>(m.imageW) * m.imageH >= (1ull << 31)) throw std::invalid_argument("rf_comm_denoise_split: image too large");
-    const bool perTile = (m.gatheredMask & kGatherMaskTileCounts) != 0u;
-    if (perTile && *std::min_element(m.frameCountsHost.begin(), m.frameCountsHost.end()) == 0u)
-        throw std::invalid_argument("rf_comm_denoise_split: a tile of the gathered frame holds no sample");
+    m.requireSamples("rf_comm_denoise_split", 1u);
     RF_HIP(hipSetDevice(m.device));
     // the filter rf_denoise_split_images runs over row-major sums (tilesX = 0), without the sums leaving the device -- or, gathered with the counts, rf_denoise_split_tiles'
-    enqueueDenoiseSplit(static_cast<hipStream_t>(streamHandle), m.denoiseWork, m.images[kPlaneImage].ptr, m.images[kPlaneDirect].ptr, m.images[kPlaneAlbedoCoverage].ptr,
-                        m.images[kPlaneNormalDepth].ptr, m.imageW, m.imageH, 0u, m.gatheredSamples, direct, indirect, exposure, perTile ? m.frameCounts.ptr : nullptr);
+    enqueueDenoiseSplit(static_cast<hipStream_t>(streamHandle), m.denoiseWork, m.gathered(), direct, indirect, exposure);
     m.denoisedValid = true;
 }
 
@@ -845,7 +840,7 @@ void TileComm::readSplit(float* directRgba, float* indirectRgba, void* streamHan
 {
     Impl& m = *mImpl;
     m.requireGathered("rf_comm_read_split", kPlaneMaskImage | kPlaneMaskDirect, kPlaneNames[kPlaneDirect]);
-    const bool perTile = (m.gatheredMask & kGatherMaskTileCounts) != 0u;
+    const bool perTile = m.perTile();
     if (!perTile && m.gatheredSamples == 0u) throw std::invalid_argument("rf_comm_read_split: the gathered sums hold no sample");
     const size_t n = static_cast<size_t>(m.imageW) * m.imageH;
     if (n >= (1ull << 31)) throw std::invalid_argument("rf_comm_read_split: image too large");
@@ -875,18 +870,13 @@ uint32_t TileComm::exportFeatures(const FeatureRequest& request, void* dstDevice
     if (static_cast<uint64_t>(m.imageW) * m.imageH >= (1ull << 31)) throw std::invalid_argument("rf_comm_export_features: image too large");
     requireFeatureDestination(dstDevice, dstBytes, featureBytes(m.imageW, m.imageH, request), m.device, "rf_comm_export_features");
     if (m.gatheredSamples == 0u) throw std::invalid_argument("rf_comm_export_features: the gathered sums hold no sample");
-    const bool perTile = (m.gatheredMask & kGatherMaskTileCounts) != 0u;
     if (featureNeedsTwoSamples(request.channels) &&
-        (m.gatheredSamples < 2u || (perTile && *std::min_element(m.frameCountsHost.begin(), m.frameCountsHost.end()) < 2u)))
+        (m.gatheredSamples < 2u || (m.perTile() && *std::min_element(m.frameCountsHost.begin(), m.frameCountsHost.end()) < 2u)))
         throw std::invalid_argument("rf_comm_export_features: RF_FEATURE_VARIANCE / RF_FEATURE_ERROR need at least 2 samples in every tile of the gathered frame");
     hipStream_t stream = static_cast<hipStream_t>(streamHandle);
     RF_HIP(hipSetDevice(m.device));
     // the gathered planes are row-major and hold one count N -- or, gathered with the counts, each tile its own (a tile without a sample: +0 in every channel)
-    FeatureSources s;
-    s.colorSum = m.images[kPlaneImage].ptr, s.sumSq = m.images[kPlaneMoments].ptr, s.albedoCoverage = m.images[kPlaneAlbedoCoverage].ptr;
-    s.normalDepth = m.images[kPlaneNormalDepth].ptr, s.directSum = m.images[kPlaneDirect].ptr;
-    s.samples = m.gatheredSamples, s.tileSamples = perTile ? m.frameCounts.ptr : nullptr;
-    enqueueExportFeatures(stream, s, m.imageW, m.imageH, false, request, dstDevice);
+    enqueueExportFeatures(stream, m.gathered(), request, dstDevice);
     RF_HIP(hipStreamSynchronize(stream));
     return m.gatheredSamples;
 }

@@ -374,25 +374,24 @@ void DenoiseWork::reserve(uint64_t n, hipStream_t stream, bool split)
     if (withSplit) eI[0].alloc(room), eI[1].alloc(room);
 }
 
-void enqueueDenoise(hipStream_t stream, DenoiseWork& w, const float4* colorSum, const float4* albedoCoverage, const float4* normalDepth, uint32_t width,
-                    uint32_t height, uint32_t tilesX, uint32_t samples, const DenoiseParameters& p, float exposure, const uint32_t* tileSamples, const float4* mean)
+void enqueueDenoise(hipStream_t stream, DenoiseWork& w, const FrameSums& s, const DenoiseParameters& p, float exposure, const float4* mean)
 {
-    const uint32_t n = width * height;
+    const uint32_t width = s.width, height = s.height, n = width * height;
     w.reserve(n, stream);
-    const float nf = static_cast<float>(samples);
+    const float nf = static_cast<float>(s.samples);
     const dim3  prepGrid((n + 255) / 256);
     // prep into (e, guide, albedo), or for L = 0 into the mean: with the frame's one count, or with each pixel's tile's own
     const auto prep = [&](float4* e, float4* guide, float4* albedo, float4* meanOut) {
-        if (mean && tileSamples)
-            hipLaunchKernelGGL(kDenoisePrepMeanTiles, prepGrid, dim3(256), 0, stream, mean, albedoCoverage, normalDepth, width, height, tilesX, tileSamples,
+        if (mean && s.tileSamples)
+            hipLaunchKernelGGL(kDenoisePrepMeanTiles, prepGrid, dim3(256), 0, stream, mean, s.albedoCoverage, s.normalDepth, width, height, s.tilesX, s.tileSamples,
                                TileGrid(width, height).tilesX, e, guide, albedo, meanOut);
         else if (mean)
-            hipLaunchKernelGGL(kDenoisePrepMean, prepGrid, dim3(256), 0, stream, mean, albedoCoverage, normalDepth, width, height, tilesX, nf, e, guide, albedo, meanOut);
-        else if (tileSamples)
-            hipLaunchKernelGGL(kDenoisePrepTiles, prepGrid, dim3(256), 0, stream, colorSum, albedoCoverage, normalDepth, width, height, tilesX, tileSamples,
+            hipLaunchKernelGGL(kDenoisePrepMean, prepGrid, dim3(256), 0, stream, mean, s.albedoCoverage, s.normalDepth, width, height, s.tilesX, nf, e, guide, albedo, meanOut);
+        else if (s.tileSamples)
+            hipLaunchKernelGGL(kDenoisePrepTiles, prepGrid, dim3(256), 0, stream, s.colorSum, s.albedoCoverage, s.normalDepth, width, height, s.tilesX, s.tileSamples,
                                TileGrid(width, height).tilesX, e, guide, albedo, meanOut);
         else
-            hipLaunchKernelGGL(kDenoisePrep, prepGrid, dim3(256), 0, stream, colorSum, albedoCoverage, normalDepth, width, height, tilesX, nf, e, guide, albedo, meanOut);
+            hipLaunchKernelGGL(kDenoisePrep, prepGrid, dim3(256), 0, stream, s.colorSum, s.albedoCoverage, s.normalDepth, width, height, s.tilesX, nf, e, guide, albedo, meanOut);
     };
     if (p.iterations == 0) prep(nullptr, nullptr, nullptr, w.out.ptr);
     else
@@ -416,22 +415,20 @@ void enqueueDenoise(hipStream_t stream, DenoiseWork& w, const float4* colorSum, 
 // but noise-free and wants next to no filtering; the indirect light wants a short chain whose colour term is as good as off, its edges left to the normal and depth terms.
 SplitDenoiseDefaults splitDenoiseDefaults() { return SplitDenoiseDefaults{DenoiseParameters{1u, 0.25f, 0.1f, 0.1f}, DenoiseParameters{2u, 256.0f, 0.1f, 0.1f}}; }
 
-void enqueueDenoiseSplit(hipStream_t stream, DenoiseWork& w, const float4* colorSum, const float4* directSum, const float4* albedoCoverage, const float4* normalDepth,
-                         uint32_t width, uint32_t height, uint32_t tilesX, uint32_t samples, const DenoiseParameters& pd, const DenoiseParameters& pi, float exposure,
-                         const uint32_t* tileSamples)
+void enqueueDenoiseSplit(hipStream_t stream, DenoiseWork& w, const FrameSums& s, const DenoiseParameters& pd, const DenoiseParameters& pi, float exposure)
 {
-    const uint32_t n = width * height;
+    const uint32_t width = s.width, height = s.height, n = width * height;
     w.reserve(n, stream, true);
-    const float    nf = static_cast<float>(samples);
+    const float    nf = static_cast<float>(s.samples);
     const dim3     prepGrid((n + 255) / 256);
     const uint32_t passes = std::max(pd.iterations, pi.iterations);
     // prep into (eD, eI, guide, albedo), or for L_D = L_I = 0 into the mean: with the frame's one count, or with each pixel's tile's own
     const auto prep = [&](float4* eD, float4* eI, float4* guide, float4* albedo, float4* meanOut) {
-        if (tileSamples)
-            hipLaunchKernelGGL(kDenoisePrepSplitTiles, prepGrid, dim3(256), 0, stream, colorSum, directSum, albedoCoverage, normalDepth, width, height, tilesX, tileSamples,
+        if (s.tileSamples)
+            hipLaunchKernelGGL(kDenoisePrepSplitTiles, prepGrid, dim3(256), 0, stream, s.colorSum, s.directSum, s.albedoCoverage, s.normalDepth, width, height, s.tilesX, s.tileSamples,
                                TileGrid(width, height).tilesX, eD, eI, guide, albedo, meanOut);
         else
-            hipLaunchKernelGGL(kDenoisePrepSplit, prepGrid, dim3(256), 0, stream, colorSum, directSum, albedoCoverage, normalDepth, width, height, tilesX, nf, eD, eI, guide,
+            hipLaunchKernelGGL(kDenoisePrepSplit, prepGrid, dim3(256), 0, stream, s.colorSum, s.directSum, s.albedoCoverage, s.normalDepth, width, height, s.tilesX, nf, eD, eI, guide,
                                albedo, meanOut);
     };
     if (passes == 0) prep(nullptr, nullptr, nullptr, nullptr, w.out.ptr);
@@ -472,30 +469,12 @@ void denoiseSplitTiles(int deviceOrdinal, uint32_t width, uint32_t height, const
                        const float* albedoCoverage, const float* normalDepth, const DenoiseParameters& direct, const DenoiseParameters& indirect, float exposure,
                        float* outRgba, uint32_t* outBgra8)
 {
-    requireDevice(deviceOrdinal);
-    const uint64_t n = static_cast<uint64_t>(width) * height;
-    const uint32_t tiles = TileGrid(width, height).count();
-    // (leaving the scope: the stream is synchronised, the buffers are freed, the stream is destroyed -- ScopedStream)
-    ScopedStream           stream;
-    DeviceBuffer<float4>   in[4];
-    DeviceBuffer<uint32_t> counts;
-    DenoiseWork            work;
-    ScopedStream::Drain    drain{stream};
-    if (tileSamples)
-    {
-        counts.alloc(tiles);
-        RF_HIP(hipMemcpyAsync(counts.ptr, tileSamples, tiles * sizeof(uint32_t), hipMemcpyHostToDevice, stream.handle));
-    }
-    const float*           src[4] = {colorSum, directSum, albedoCoverage, normalDepth};
-    for (int b = 0; b < 4; ++b)
-    {
-        in[b].alloc(n);
-        RF_HIP(hipMemcpyAsync(in[b].ptr, src[b], n * sizeof(float4), hipMemcpyHostToDevice, stream.handle));
-    }
-    enqueueDenoiseSplit(stream.handle, work, in[0].ptr, in[1].ptr, in[2].ptr, in[3].ptr, width, height, 0u, samples, direct, indirect, exposure, counts.ptr);
-    if (outRgba) RF_HIP(hipMemcpyAsync(outRgba, work.out.ptr, n * sizeof(float4), hipMemcpyDeviceToHost, stream.handle));
-    if (outBgra8) RF_HIP(hipMemcpyAsync(outBgra8, work.bgra.ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream.handle));
-    RF_HIP(hipStreamSynchronize(stream.handle));
+    DenoiseWork work; // (before the stage: freed after it has drained its stream)
+    StagedFrame f(deviceOrdinal, width, height, samples, tileSamples, colorSum, nullptr, albedoCoverage, normalDepth, directSum);
+    enqueueDenoiseSplit(f.stream.handle, work, f.sums, direct, indirect, exposure);
+    f.download(outRgba, work.out.ptr, f.pixels() * sizeof(float4));
+    f.download(outBgra8, work.bgra.ptr, f.pixels() * sizeof(uint32_t));
+    f.wait();
 }
 
 void denoiseImages(int deviceOrdinal, uint32_t width, uint32_t height, uint32_t samples, const float* colorSum, const float* albedoCoverage, const float* normalDepth,
@@ -507,29 +486,11 @@ void denoiseImages(int deviceOrdinal, uint32_t width, uint32_t height, uint32_t 
 void denoiseTiles(int deviceOrdinal, uint32_t width, uint32_t height, const uint32_t* tileSamples, uint32_t samples, const float* colorSum, const float* albedoCoverage,
                   const float* normalDepth, const DenoiseParameters& params, float exposure, float* outRgba, uint32_t* outBgra8)
 {
-    requireDevice(deviceOrdinal);
-    const uint64_t n = static_cast<uint64_t>(width) * height;
-    const uint32_t tiles = TileGrid(width, height).count();
-    // (leaving the scope: the stream is synchronised, the buffers are freed, the stream is destroyed -- ScopedStream)
-    ScopedStream           stream;
-    DeviceBuffer<float4>   in[3];
-    DeviceBuffer<uint32_t> counts;
-    DenoiseWork            work;
-    ScopedStream::Drain    drain{stream};
-    if (tileSamples)
-    {
-        counts.alloc(tiles);
-        RF_HIP(hipMemcpyAsync(counts.ptr, tileSamples, tiles * sizeof(uint32_t), hipMemcpyHostToDevice, stream.handle));
-    }
-    const float*         src[3] = {colorSum, albedoCoverage, normalDepth};
-    for (int b = 0; b < 3; ++b)
-    {
-        in[b].alloc(n);
-        RF_HIP(hipMemcpyAsync(in[b].ptr, src[b], n * sizeof(float4), hipMemcpyHostToDevice, stream.handle));
-    }
-    enqueueDenoise(stream.handle, work, in[0].ptr, in[1].ptr, in[2].ptr, width, height, 0u, samples, params, exposure, counts.ptr);
-    if (outRgba) RF_HIP(hipMemcpyAsync(outRgba, work.out.ptr, n * sizeof(float4), hipMemcpyDeviceToHost, stream.handle));
-    if (outBgra8) RF_HIP(hipMemcpyAsync(outBgra8, work.bgra.ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream.handle));
-    RF_HIP(hipStreamSynchronize(stream.handle));
+    DenoiseWork work; // (before the stage: freed after it has drained its stream)
+    StagedFrame f(deviceOrdinal, width, height, samples, tileSamples, colorSum, nullptr, albedoCoverage, normalDepth, nullptr);
+    enqueueDenoise(f.stream.handle, work, f.sums, params, exposure);
+    f.download(outRgba, work.out.ptr, f.pixels() * sizeof(float4));
+    f.download(outBgra8, work.bgra.ptr, f.pixels() * sizeof(uint32_t));
+    f.wait();
 }
 } // namespace rf

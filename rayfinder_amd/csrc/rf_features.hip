@@ -209,15 +209,16 @@ void requireDeviceRange(const void* p, uint64_t bytes, int deviceOrdinal, const 
         throw std::invalid_argument(name + ": " + content + " do not fit into the allocation " + buffer + " points into");
 }
 
-void enqueueExportFeatures(hipStream_t stream, const FeatureSources& s, uint32_t width, uint32_t height, bool tileMajor, const FeatureRequest& request, void* dst)
+void enqueueExportFeatures(hipStream_t stream, const FrameSums& s, const FeatureRequest& request, void* dst)
 {
+    const uint32_t    width = s.width, height = s.height;
     const TileGrid    grid(width, height);
     const uint32_t    C = featureChannelCount(request.channels);
     const bool        f16 = request.dtype == kFeaturesF16;
     const bool        vec = featureStoresVectorised(width, reinterpret_cast<uint64_t>(dst), request.dtype);
     const FeatureArgs args{s.colorSum, s.sumSq,        s.albedoCoverage, s.normalDepth,     s.directSum, s.tileSamples, s.samples, width, height, grid.tilesX,
                            request.channels, C, request.layout == kFeaturesHwc ? 1u : 0u, featureReads(request.channels)};
-    const auto        kernel = tileMajor ? exportKernel<true>(f16, vec) : exportKernel<false>(f16, vec);
+    const auto        kernel = s.tilesX != 0u ? exportKernel<true>(f16, vec) : exportKernel<false>(f16, vec);
     const uint32_t    ldsBytes = C * 8u * (args.hwc ? kTileSize : kChwRunStride) * sizeof(float);
     hipLaunchKernelGGL(kernel, dim3(grid.count()), dim3(256), ldsBytes, stream, args, dst);
     RF_HIP(hipGetLastError());
@@ -226,36 +227,16 @@ void enqueueExportFeatures(hipStream_t stream, const FeatureSources& s, uint32_t
 void exportFeaturesImages(int deviceOrdinal, uint32_t width, uint32_t height, uint32_t samples, const uint32_t* tileSamples, const float* colorSum, const float* sumSq,
                           const float* albedoCoverage, const float* normalDepth, const float* directSum, const FeatureRequest& request, void* outHost)
 {
-    requireDevice(deviceOrdinal);
-    const uint64_t n = static_cast<uint64_t>(width) * height, bytes = featureBytes(width, height, request);
-    const uint32_t tiles = TileGrid(width, height).count();
-    // (leaving the scope: the stream is synchronised, the buffers are freed, the stream is destroyed -- ScopedStream)
-    ScopedStream           stream;
-    DeviceBuffer<float4>   in[5];
-    DeviceBuffer<uint32_t> counts;
-    DeviceBuffer<uint8_t>  out;
-    ScopedStream::Drain    drain{stream};
-    if (tileSamples)
-    {
-        counts.alloc(tiles);
-        RF_HIP(hipMemcpyAsync(counts.ptr, tileSamples, tiles * sizeof(uint32_t), hipMemcpyHostToDevice, stream.handle));
-    }
+    const uint64_t bytes = featureBytes(width, height, request);
     // only the planes a selected channel reads travel (the others may be NULL)
     const uint32_t reads = featureReads(request.channels);
-    const float*   src[5] = {colorSum, sumSq, albedoCoverage, normalDepth, directSum};
-    const uint32_t family[5] = {kFeatureReadsS, kFeatureReadsQ, kFeatureReadsAovs, kFeatureReadsAovs, kFeatureReadsD};
-    for (int b = 0; b < 5; ++b)
-    {
-        if (!(reads & family[b])) continue;
-        in[b].alloc(n);
-        RF_HIP(hipMemcpyAsync(in[b].ptr, src[b], n * sizeof(float4), hipMemcpyHostToDevice, stream.handle));
-    }
+    const auto     read = [&](uint32_t family, const float* plane) { return reads & family ? plane : nullptr; };
+    DeviceBuffer<uint8_t> out; // (before the stage: freed after it has drained its stream)
+    StagedFrame           f(deviceOrdinal, width, height, samples, tileSamples, read(kFeatureReadsS, colorSum), read(kFeatureReadsQ, sumSq), read(kFeatureReadsAovs, albedoCoverage),
+                            read(kFeatureReadsAovs, normalDepth), read(kFeatureReadsD, directSum));
     out.alloc(bytes);
-    FeatureSources s;
-    s.colorSum = in[0].ptr, s.sumSq = in[1].ptr, s.albedoCoverage = in[2].ptr, s.normalDepth = in[3].ptr, s.directSum = in[4].ptr;
-    s.tileSamples = counts.ptr, s.samples = samples;
-    enqueueExportFeatures(stream.handle, s, width, height, false, request, out.ptr);
-    RF_HIP(hipMemcpyAsync(outHost, out.ptr, bytes, hipMemcpyDeviceToHost, stream.handle));
-    RF_HIP(hipStreamSynchronize(stream.handle));
+    enqueueExportFeatures(f.stream.handle, f.sums, request, out.ptr);
+    f.download(outHost, out.ptr, bytes);
+    f.wait();
 }
 } // namespace rf

@@ -5,6 +5,7 @@
 #pragma once
 
 #include "rf_feature_request.hpp"
+#include "rf_frame_sums.hpp"
 #include "rf_hip_host.hpp"
 
 #include <hip/hip_runtime.h>
@@ -13,15 +14,6 @@
 
 namespace rf
 {
-// The sums of one frame in device memory, all in one layout; a plane no selected channel reads may be nullptr.  tileSamples (device, one count per tile of the frame's
-// 32 x 32 grid, tile_y * ceil(width / 32) + tile_x) == nullptr: `samples` for every pixel.
-struct FeatureSources
-{
-    const float4 *  colorSum = nullptr, *sumSq = nullptr, *albedoCoverage = nullptr, *normalDepth = nullptr, *directSum = nullptr;
-    const uint32_t* tileSamples = nullptr;
-    uint32_t        samples = 0;
-};
-
 // std::invalid_argument unless hipPointerGetAttributes reports `dst` as device memory of device `deviceOrdinal` (a host pointer, registered or managed memory and
 // another device's memory are all refused), or when `bytes` is smaller than `needed`.  No launch.
 void requireFeatureDestination(const void* dst, uint64_t bytes, uint64_t needed, int deviceOrdinal, const char* what);
@@ -31,9 +23,9 @@ void requireFeatureDestination(const void* dst, uint64_t bytes, uint64_t needed,
 // "the scene").  No launch.
 void requireDeviceRange(const void* p, uint64_t bytes, int deviceOrdinal, const char* what, const char* noun, const char* content, const char* owner);
 
-// Enqueue the one export kernel on `stream`: one 256-lane workgroup per 32 x 32 tile.  tileMajor: the sums are compact tile-major buffers holding every tile of the
-// frame in tile order (a handle without a tile shard); else row-major.  width * height < 2^31; the request is valid; dst holds featureBytes() and is element aligned.
-void enqueueExportFeatures(hipStream_t stream, const FeatureSources& sources, uint32_t width, uint32_t height, bool tileMajor, const FeatureRequest& request, void* dst);
+// Enqueue the one export kernel on `stream` over the frame's sums (rf_frame_sums.hpp; a plane no selected channel reads may be nullptr): one 256-lane workgroup per
+// 32 x 32 tile.  The request is valid; dst holds featureBytes() and is element aligned.
+void enqueueExportFeatures(hipStream_t stream, const FrameSums& sums, const FeatureRequest& request, void* dst);
 
 // (the standalone export over host-assembled sums, exportFeaturesImages, is declared with the other *Images calls: rf_renderer.hpp)
 } // namespace rf

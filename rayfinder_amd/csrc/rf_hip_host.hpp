@@ -54,28 +54,6 @@ struct DeviceBuffer
     }
 };
 
-// A non-blocking stream of the current device, for the length of a scope: synchronised, then destroyed.  The buffers its work uses are declared AFTER it and a Drain
-// after them, so that leaving the scope -- by return or by exception -- synchronises the stream, frees the buffers and destroys the stream, in that order.
-struct ScopedStream
-{
-    hipStream_t handle = nullptr;
-
-    ScopedStream() { RF_HIP(hipStreamCreateWithFlags(&handle, hipStreamNonBlocking)); }
-    ScopedStream(const ScopedStream&) = delete;
-    ScopedStream& operator=(const ScopedStream&) = delete;
-    ~ScopedStream()
-    {
-        (void)hipStreamSynchronize(handle);
-        (void)hipStreamDestroy(handle);
-    }
-
-    struct Drain
-    {
-        const ScopedStream& stream;
-        ~Drain() { (void)hipStreamSynchronize(stream.handle); }
-    };
-};
-
 // -> the number of HIP devices; std::runtime_error when there is none
 inline int requireAnyDevice()
 {
@@ -91,4 +69,31 @@ inline void requireDevice(int ordinal)
     if (ordinal < 0 || ordinal >= count) throw std::invalid_argument("device ordinal out of range");
     RF_HIP(hipSetDevice(ordinal));
 }
+
+// A non-blocking stream of device `deviceOrdinal` (made current: requireDevice), for the length of a scope: synchronised, then destroyed.  The buffers its work uses
+// are declared AFTER it and a Drain after them, so that leaving the scope -- by return or by exception -- synchronises the stream, frees the buffers and destroys the
+// stream, in that order (StagedFrame, rf_frame_sums.hpp, is the one place that does).
+struct ScopedStream
+{
+    hipStream_t handle = nullptr;
+
+    explicit ScopedStream(int deviceOrdinal)
+    {
+        requireDevice(deviceOrdinal);
+        RF_HIP(hipStreamCreateWithFlags(&handle, hipStreamNonBlocking));
+    }
+    ScopedStream(const ScopedStream&) = delete;
+    ScopedStream& operator=(const ScopedStream&) = delete;
+    ~ScopedStream()
+    {
+        (void)hipStreamSynchronize(handle);
+        (void)hipStreamDestroy(handle);
+    }
+
+    struct Drain
+    {
+        const ScopedStream& stream;
+        ~Drain() { (void)hipStreamSynchronize(stream.handle); }
+    };
+};
 } // namespace rf

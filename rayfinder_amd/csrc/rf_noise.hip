@@ -199,35 +199,35 @@ void NoiseWork::release()
     tiles = 0;
 }
 
-NoiseEstimate runNoiseEstimate(hipStream_t stream, NoiseWork& w, const float4* colorSum, const float4* sumSq, uint32_t width, uint32_t height, bool tileMajor, uint32_t samples,
-                               float* errorMap, float* tileSum, float* tileMax)
+NoiseEstimate runNoiseEstimate(hipStream_t stream, NoiseWork& w, const FrameSums& sums, float* errorMap, float* tileSum, float* tileMax)
 {
-    return runNoiseEstimateTiles(stream, w, colorSum, sumSq, width, height, tileMajor, TileSelection{}, samples, errorMap, tileSum, tileMax, nullptr);
+    return runNoiseEstimateTiles(stream, w, sums, TileSelection{}, errorMap, tileSum, tileMax, nullptr);
 }
 
-NoiseEstimate runNoiseEstimateTiles(hipStream_t stream, NoiseWork& w, const float4* colorSum, const float4* sumSq, uint32_t width, uint32_t height, bool tileMajor,
-                                    const TileSelection& sel, uint32_t samples, float* errorMap, float* tileSum, float* tileMax, uint32_t* tilePixels)
+NoiseEstimate runNoiseEstimateTiles(hipStream_t stream, NoiseWork& w, const FrameSums& s, const TileSelection& sel, float* errorMap, float* tileSum, float* tileMax,
+                                    uint32_t* tilePixels)
 {
-    const uint32_t tilesX = TileGrid(width, height).tilesX, tiles = TileGrid(width, height).count();
+    const uint32_t width = s.width, height = s.height, tilesX = TileGrid(width, height).tilesX, tiles = TileGrid(width, height).count();
+    const uint32_t tileMajor = s.tilesX != 0u ? 1u : 0u; // (the kernels take a flag and the grid's own tilesX)
     const uint32_t listed = sel.listDevice ? sel.listCount : tiles;
     const uint64_t n = static_cast<uint64_t>(width) * height;
     NoiseEstimate  out;
-    out.samples = samples;
+    out.samples = s.samples;
     if (listed == 0) return out;
     w.reserve(tiles, errorMap ? n : 0, stream);
-    const float nf = static_cast<float>(samples), nf1 = nf - 1.0f;
+    const float nf = static_cast<float>(s.samples), nf1 = nf - 1.0f;
     float* const map = errorMap ? w.errorMap.ptr : static_cast<float*>(nullptr);
     if (sel.slotsBehindList)
     {
-        if (!tileMajor || sel.listDevice == nullptr || sel.tileSamplesDevice != nullptr) throw std::logic_error("a shard's slot list: tile-major sums, a list, one count");
-        hipLaunchKernelGGL(kNoiseEstimateSlots, dim3(listed), dim3(256), 0, stream, colorSum, sumSq, width, height, tilesX, sel.listDevice, listed, nf, map, w.tileSumMax.ptr,
+        if (!tileMajor || sel.listDevice == nullptr || s.tileSamples != nullptr) throw std::logic_error("a shard's slot list: tile-major sums, a list, one count");
+        hipLaunchKernelGGL(kNoiseEstimateSlots, dim3(listed), dim3(256), 0, stream, s.colorSum, s.sumSq, width, height, tilesX, sel.listDevice, listed, nf, map, w.tileSumMax.ptr,
                            w.tileSumMax.ptr + w.tiles, w.tileCounts.ptr, w.tileCounts.ptr + w.tiles);
     }
-    else if (sel.listDevice == nullptr && sel.tileSamplesDevice == nullptr)
-        hipLaunchKernelGGL(kNoiseEstimate, dim3(tiles), dim3(256), 0, stream, colorSum, sumSq, width, height, tilesX, tileMajor ? 1u : 0u, nf, nf1, map, w.tileSumMax.ptr,
+    else if (sel.listDevice == nullptr && s.tileSamples == nullptr)
+        hipLaunchKernelGGL(kNoiseEstimate, dim3(tiles), dim3(256), 0, stream, s.colorSum, s.sumSq, width, height, tilesX, tileMajor, nf, nf1, map, w.tileSumMax.ptr,
                            w.tileSumMax.ptr + w.tiles, w.tileCounts.ptr, w.tileCounts.ptr + w.tiles);
     else
-        hipLaunchKernelGGL(kNoiseEstimateTiles, dim3(listed), dim3(256), 0, stream, colorSum, sumSq, width, height, tilesX, tileMajor ? 1u : 0u, sel.listDevice, sel.tileSamplesDevice,
+        hipLaunchKernelGGL(kNoiseEstimateTiles, dim3(listed), dim3(256), 0, stream, s.colorSum, s.sumSq, width, height, tilesX, tileMajor, sel.listDevice, s.tileSamples,
                            nf, map, w.tileSumMax.ptr, w.tileSumMax.ptr + w.tiles, w.tileCounts.ptr, w.tileCounts.ptr + w.tiles);
     RF_HIP(hipGetLastError());
     std::vector<float>    sums(tiles), maxima(tiles);
@@ -268,28 +268,8 @@ NoiseEstimate noiseEstimateImages(int deviceOrdinal, uint32_t width, uint32_t he
 NoiseEstimate noiseEstimateTiles(int deviceOrdinal, uint32_t width, uint32_t height, const uint32_t* tileSamples, uint32_t samples, const float* colorSum, const float* sumSq,
                                  float* errorMap, float* tileSum, float* tileMax)
 {
-    requireDevice(deviceOrdinal);
-    const uint64_t n = static_cast<uint64_t>(width) * height;
-    const uint32_t tiles = TileGrid(width, height).count();
-    // (leaving the scope: the stream is synchronised, the buffers are freed, the stream is destroyed -- ScopedStream)
-    ScopedStream           stream;
-    DeviceBuffer<float4>   in[2];
-    DeviceBuffer<uint32_t> counts;
-    NoiseWork              work;
-    ScopedStream::Drain    drain{stream};
-    const float*           src[2] = {colorSum, sumSq};
-    for (int b = 0; b < 2; ++b)
-    {
-        in[b].alloc(n);
-        RF_HIP(hipMemcpyAsync(in[b].ptr, src[b], n * sizeof(float4), hipMemcpyHostToDevice, stream.handle));
-    }
-    TileSelection sel;
-    if (tileSamples)
-    {
-        counts.alloc(tiles);
-        RF_HIP(hipMemcpyAsync(counts.ptr, tileSamples, tiles * sizeof(uint32_t), hipMemcpyHostToDevice, stream.handle));
-        sel.tileSamplesDevice = counts.ptr;
-    }
-    return runNoiseEstimateTiles(stream.handle, work, in[0].ptr, in[1].ptr, width, height, false, sel, samples, errorMap, tileSum, tileMax, nullptr);
+    NoiseWork   work; // (before the stage: freed after it has drained its stream)
+    StagedFrame f(deviceOrdinal, width, height, samples, tileSamples, colorSum, sumSq, nullptr, nullptr, nullptr);
+    return runNoiseEstimate(f.stream.handle, work, f.sums, errorMap, tileSum, tileMax);
 }
 } // namespace rf

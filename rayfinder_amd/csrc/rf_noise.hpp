@@ -1,8 +1,9 @@
 // rf_noise.hpp -- the noise estimate over the radiance sum and its second moments (rf_noise.hip; the sums themselves: rf_sums.hpp): the launch sequence of the
-// estimate, shared by rf_renderer_noise_estimate (inputs: the handle's own compact tile-major sums) and the standalone rf_noise_estimate_images (inputs: row-major
-// sums), and the per-tile mean.
+// estimate, shared by rf_renderer_noise_estimate (inputs: the handle's own compact tile-major sums), rf_comm_noise_estimate (the planes gathered on the root) and the
+// standalone rf_noise_estimate_images (inputs: row-major sums) -- each hands in its FrameSums --, and the per-tile mean.
 #pragma once
 
+#include "rf_frame_sums.hpp"
 #include "rf_kernels.hpp"
 
 namespace rf
@@ -31,14 +32,12 @@ struct NoiseWork
     void release();
 };
 
-// Enqueue kNoiseEstimate on `stream`, copy the per-tile results (and the map) back, wait, and reduce them on the host (the definition: include/rayfinder_amd.h).
-// tileMajor: the sums are compact tile-major buffers holding every tile of the frame in tile order (a handle without a tile shard); else row-major.
-// errorMap (width * height), tileSum, tileMax (one entry per tile of the 32 x 32 grid): host pointers, NULL = skip.  samples >= 2, width * height < 2^31.
-NoiseEstimate runNoiseEstimate(hipStream_t stream, NoiseWork& work, const float4* colorSum, const float4* sumSq, uint32_t width, uint32_t height, bool tileMajor,
-                               uint32_t samples, float* errorMap, float* tileSum, float* tileMax);
+// Enqueue the estimate over the frame's S and Q (rf_frame_sums.hpp) on `stream`, copy the per-tile results (and the map) back, wait, and reduce them on the host (the
+// definition: include/rayfinder_amd.h).  sums.samples >= 2; with sums.tileSamples (kNoiseEstimateTiles; without: kNoiseEstimate) every count >= 2, and the result's
+// `samples` still reports sums.samples.  errorMap (width * height), tileSum, tileMax (one entry per tile of the 32 x 32 grid): host pointers, NULL = skip.
+NoiseEstimate runNoiseEstimate(hipStream_t stream, NoiseWork& work, const FrameSums& sums, float* errorMap, float* tileSum, float* tileMax);
 
-// Which tiles an estimate covers and with what counts.  listDevice / listHost: the same ascending list of listCount tile ids (nullptr: every tile of the frame);
-// tileSamplesDevice: one sample count per tile of the frame, each >= 2 (nullptr: `samples` for all).  Both nullptr: kNoiseEstimate itself.
+// Which tiles an estimate covers.  listDevice / listHost: the same ascending list of listCount tile ids (nullptr: every tile of the frame).
 // slotsBehindList: the sums are the compact tile-major buffers of a tile SHARD, and listDevice holds, behind the listCount ids, each listed tile's slot in them
 // (tile-major, a list and no per-tile counts: rf_comm_render_adaptive's estimate).
 struct TileSelection
@@ -46,11 +45,10 @@ struct TileSelection
     const uint32_t* listDevice = nullptr;
     const uint32_t* listHost = nullptr;
     uint32_t        listCount = 0;
-    const uint32_t* tileSamplesDevice = nullptr;
     bool            slotsBehindList = false;
 };
 // runNoiseEstimate for a selection: the result's mean, maximum and counts are over the listed tiles (worst_tile in the frame's numbering).  tilePixels (host, one entry
 // per tile of the frame, NULL = skip): in-frame pixels.  With a list, only the listed tiles' entries of tileSum / tileMax / tilePixels and of the map are written.
-NoiseEstimate runNoiseEstimateTiles(hipStream_t stream, NoiseWork& work, const float4* colorSum, const float4* sumSq, uint32_t width, uint32_t height, bool tileMajor,
-                                    const TileSelection& selection, uint32_t samples, float* errorMap, float* tileSum, float* tileMax, uint32_t* tilePixels);
+NoiseEstimate runNoiseEstimateTiles(hipStream_t stream, NoiseWork& work, const FrameSums& sums, const TileSelection& selection, float* errorMap, float* tileSum,
+                                    float* tileMax, uint32_t* tilePixels);
 } // namespace rf

@@ -705,6 +705,14 @@ struct Renderer::Impl
         RF_HIP(hipMemcpy(tileSamplesDevice.ptr, tileSamples.data(), tileSamples.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         return tileSamplesDevice.ptr;
     }
+    // the counts the per-tile reads take: the non-uniform state's, uploaded (the call first waits for the stream), or nullptr: the accumulated count for every pixel
+    const uint32_t* nonUniformTileSamples() { return books.nonUniform() ? uploadTileSamples() : nullptr; }
+    // What the post-process passes read (rf_frame_sums.hpp): the handle's own compact tile-major sums (a family that is off: nullptr) at the accumulated count;
+    // tileSamples: the per-tile counts on the device, as the pass is to see them
+    FrameSums frameSums(const uint32_t* tileSamples) const
+    {
+        return FrameSums{image, moments(), aovAlbedoCoverage(), aovNormalDepth(), direct(), params.width, params.height, grid().tilesX, books.accumulated(), tileSamples};
+    }
     // kTileMean over the accumulation into meanImage, waited for: every pixel divided by its tile's count (uniform state: the accumulated count; nothing accumulated: 0)
     const float4* meanOnDevice()
     {
@@ -712,7 +720,7 @@ struct Renderer::Impl
         RF_HIP(hipStreamSynchronize(stream));
         if (meanImage.count < n) meanImage.alloc(n);
         zeroImageIfStale(static_cast<size_t>(n) * sizeof(float4));
-        const uint32_t* counts = books.nonUniform() ? uploadTileSamples() : nullptr;
+        const uint32_t* counts = nonUniformTileSamples();
         hipLaunchKernelGGL(tileMeanKernel(), dim3((n + 255) / 256), dim3(256), 0, stream, static_cast<const float4*>(image), counts, books.accumulated(), n, meanImage.ptr);
         RF_HIP(hipGetLastError());
         RF_HIP(hipStreamSynchronize(stream));
@@ -1297,8 +1305,7 @@ void Renderer::denoise(const DenoiseParameters& params)
     m.books.refuseDenoise();
     RF_HIP(hipSetDevice(m.device));
     // (the non-uniform state: prep divides each pixel by its tile's own count)
-    enqueueDenoise(m.stream, m.denoiseWork, m.image, m.aovAlbedoCoverage(), m.aovNormalDepth(), m.params.width, m.params.height, m.grid().tilesX, m.books.accumulated(), params,
-                   m.params.exposure, m.books.nonUniform() ? m.uploadTileSamples() : nullptr);
+    enqueueDenoise(m.stream, m.denoiseWork, m.frameSums(m.nonUniformTileSamples()), params, m.params.exposure);
     m.books.noteDenoised();
 }
 
@@ -1366,9 +1373,7 @@ void Renderer::denoiseSplit(const DenoiseParameters& direct, const DenoiseParame
     Impl& m = *mImpl;
     m.books.refuseDenoiseSplit();
     RF_HIP(hipSetDevice(m.device));
-    // (per tile: the call first waits for the stream and copies the counts to the device)
-    enqueueDenoiseSplit(m.stream, m.denoiseWork, m.image, m.direct(), m.aovAlbedoCoverage(), m.aovNormalDepth(), m.params.width, m.params.height, m.grid().tilesX,
-                        m.books.accumulated(), direct, indirect, m.params.exposure, m.books.nonUniform() ? m.uploadTileSamples() : nullptr);
+    enqueueDenoiseSplit(m.stream, m.denoiseWork, m.frameSums(m.nonUniformTileSamples()), direct, indirect, m.params.exposure);
     m.books.noteDenoised();
 }
 
@@ -1379,12 +1384,7 @@ uint32_t Renderer::exportFeatures(const FeatureRequest& request, void* dstDevice
     requireFeatureDestination(dstDevice, dstBytes, featureBytes(m.params.width, m.params.height, request), m.device, "rf_renderer_export_features");
     m.books.refuseExportFeatures(reads, featureNeedsTwoSamples(request.channels));
     RF_HIP(hipSetDevice(m.device));
-    FeatureSources s;
-    s.colorSum = m.image, s.sumSq = m.moments(), s.albedoCoverage = m.aovAlbedoCoverage(), s.normalDepth = m.aovNormalDepth(), s.directSum = m.direct();
-    s.samples = m.books.accumulated();
-    // (per tile: the call first waits for the stream and copies the counts to the device)
-    s.tileSamples = m.books.nonUniform() ? m.uploadTileSamples() : nullptr;
-    enqueueExportFeatures(m.stream, s, m.params.width, m.params.height, true, request, dstDevice);
+    enqueueExportFeatures(m.stream, m.frameSums(m.nonUniformTileSamples()), request, dstDevice);
     RF_HIP(hipStreamSynchronize(m.stream)); // the buffer may be used from any stream once the call returns
     return m.books.accumulated();
 }
@@ -1423,9 +1423,8 @@ void Renderer::robustMean()
     Impl& m = *mImpl;
     m.books.refuseRobustMean();
     RF_HIP(hipSetDevice(m.device));
-    // (per tile: the call first waits for the stream and copies the counts to the device, as the other per-tile reads do)
-    enqueueRobustMean(m.stream, m.robustWork, m.bucketPlanes(), m.bucketStride(), m.params.width, m.params.height, m.grid().tilesX, buckets(), m.books.accumulated(), m.params.exposure,
-                      bucketsPerTile() ? m.uploadTileSamples() : nullptr);
+    // (per tile -- the buckets' own bit, not the non-uniform state: the call first waits for the stream and copies the counts to the device, as the other per-tile reads do)
+    enqueueRobustMean(m.stream, m.robustWork, m.bucketPlanes(), m.bucketStride(), buckets(), m.frameSums(bucketsPerTile() ? m.uploadTileSamples() : nullptr), m.params.exposure);
     m.books.noteRobustMean();
 }
 
@@ -1447,8 +1446,7 @@ void Renderer::denoiseRobust(const DenoiseParameters& params)
     m.books.refuseDenoiseRobust();
     robustMean();
     // (per tile: the counts robustMean uploaded are still on the device, and nothing but this stream reads them)
-    enqueueDenoise(m.stream, m.denoiseWork, m.image, m.aovAlbedoCoverage(), m.aovNormalDepth(), m.params.width, m.params.height, m.grid().tilesX, m.books.accumulated(), params,
-                   m.params.exposure, m.books.nonUniform() ? m.tileSamplesDevice.ptr : nullptr, m.robustWork.mean.ptr);
+    enqueueDenoise(m.stream, m.denoiseWork, m.frameSums(m.books.nonUniform() ? m.tileSamplesDevice.ptr : nullptr), params, m.params.exposure, m.robustWork.mean.ptr);
     m.books.noteDenoised();
 }
 
@@ -1461,9 +1459,8 @@ void Renderer::temporalAccumulate(const TemporalParameters& params)
     w.reserve(static_cast<uint64_t>(m.params.width) * m.params.height, m.stream);
     const bool     history = m.books.temporalHistory();
     const uint32_t out = w.result, in = w.history();
-    enqueueTemporal(m.stream, m.image, m.aovAlbedoCoverage(), m.aovNormalDepth(), m.params.width, m.params.height, m.grid().tilesX, m.books.accumulated(), m.params.camera,
-                    history ? w.color[in].ptr : nullptr, history ? w.geometry[in].ptr : nullptr, history ? &w.camera[in] : nullptr, params, m.params.exposure, w.color[out].ptr,
-                    w.geometry[out].ptr, w.bgra.ptr);
+    enqueueTemporal(m.stream, m.frameSums(nullptr), m.params.camera, history ? w.color[in].ptr : nullptr, history ? w.geometry[in].ptr : nullptr,
+                    history ? &w.camera[in] : nullptr, params, m.params.exposure, w.color[out].ptr, w.geometry[out].ptr, w.bgra.ptr);
     w.camera[out] = m.params.camera;
     m.books.noteTemporal();
 }
@@ -1496,8 +1493,7 @@ void Renderer::denoiseTemporal(const TemporalParameters& temporal, const Denoise
     Impl& m = *mImpl;
     m.books.refuseTemporalAccumulate(true);
     temporalAccumulate(temporal);
-    enqueueDenoise(m.stream, m.denoiseWork, m.image, m.aovAlbedoCoverage(), m.aovNormalDepth(), m.params.width, m.params.height, m.grid().tilesX, m.books.accumulated(), params,
-                   m.params.exposure, nullptr, m.temporalWork.color[m.temporalWork.result].ptr);
+    enqueueDenoise(m.stream, m.denoiseWork, m.frameSums(nullptr), params, m.params.exposure, m.temporalWork.color[m.temporalWork.result].ptr); // (one count: no tile counts)
     m.books.noteDenoised();
 }
 
@@ -1506,14 +1502,8 @@ NoiseEstimate Renderer::noiseEstimate(float* errorMap, float* tileSum, float* ti
     Impl& m = *mImpl;
     m.books.refuseNoiseEstimate();
     RF_HIP(hipSetDevice(m.device));
-    if (m.books.nonUniform())
-    {
-        // every tile with its own count (each >= 2: a tile stops at an estimate); `samples` reports the leading count
-        TileSelection sel;
-        sel.tileSamplesDevice = m.uploadTileSamples();
-        return runNoiseEstimateTiles(m.stream, m.noiseWork, m.image, m.moments(), m.params.width, m.params.height, true, sel, m.books.accumulated(), errorMap, tileSum, tileMax, nullptr);
-    }
-    return runNoiseEstimate(m.stream, m.noiseWork, m.image, m.moments(), m.params.width, m.params.height, true, m.books.accumulated(), errorMap, tileSum, tileMax);
+    // (the non-uniform state: every tile with its own count -- each >= 2: a tile stops at an estimate --; `samples` reports the leading count)
+    return runNoiseEstimate(m.stream, m.noiseWork, m.frameSums(m.nonUniformTileSamples()), errorMap, tileSum, tileMax);
 }
 
 // What rf_renderer_render_adaptive and rf_comm_render_adaptive check alike before anything is traced (or exchanged)
@@ -1599,8 +1589,7 @@ AdaptiveResult Renderer::renderAdaptiveFrom(const AdaptiveParameters& p, uint32_
         TileSelection sel;
         sel.listDevice = m.tileIds.ptr, sel.listHost = activeIds.data(), sel.listCount = static_cast<uint32_t>(active.size());
         sel.slotsBehindList = shardSlots;
-        out.last = runNoiseEstimateTiles(m.stream, m.noiseWork, m.image, m.moments(), m.params.width, m.params.height, true, sel, m.books.accumulated(), nullptr, sums.data(), nullptr,
-                                         pixels.data());
+        out.last = runNoiseEstimateTiles(m.stream, m.noiseWork, m.frameSums(nullptr), sel, nullptr, sums.data(), nullptr, pixels.data());
         ++out.estimatePasses;
         std::vector<uint32_t> still;
         for (const uint32_t k : active)

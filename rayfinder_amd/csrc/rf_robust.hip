@@ -207,16 +207,15 @@ void RobustWork::release()
     bgra.release();
 }
 
-void enqueueRobustMean(hipStream_t stream, RobustWork& w, const float4* planes, size_t planeStride, uint32_t width, uint32_t height, uint32_t tilesX, uint32_t K,
-                       uint32_t samples, float exposure, const uint32_t* tileSamples)
+void enqueueRobustMean(hipStream_t stream, RobustWork& w, const float4* planes, size_t planeStride, uint32_t K, const FrameSums& f, float exposure)
 {
-    const uint32_t n = width * height;
+    const uint32_t width = f.width, height = f.height, n = width * height;
     w.reserve(n, stream);
-    if (tileSamples)
-        hipLaunchKernelGGL(robustTilesKernel(K), dim3((n + 255) / 256), dim3(256), 0, stream, planes, planeStride, width, height, tilesX, tileSamples,
+    if (f.tileSamples)
+        hipLaunchKernelGGL(robustTilesKernel(K), dim3((n + 255) / 256), dim3(256), 0, stream, planes, planeStride, width, height, f.tilesX, f.tileSamples,
                            TileGrid(width, height).tilesX, w.mean.ptr, w.trim.ptr);
     else
-        hipLaunchKernelGGL(robustKernel(K), dim3((n + 255) / 256), dim3(256), 0, stream, planes, planeStride, width, height, tilesX, samples, w.mean.ptr, w.trim.ptr);
+        hipLaunchKernelGGL(robustKernel(K), dim3((n + 255) / 256), dim3(256), 0, stream, planes, planeStride, width, height, f.tilesX, f.samples, w.mean.ptr, w.trim.ptr);
     hipLaunchKernelGGL(tonemapKernel(), dim3((n + 255) / 256), dim3(256), 0, stream, static_cast<const float4*>(w.mean.ptr), n, 1u, exposure, w.bgra.ptr);
     RF_HIP(hipGetLastError());
 }
@@ -241,27 +240,15 @@ void enqueueRobustTexels(hipStream_t stream, const float4* mean, uint32_t pixels
 static void robustMeanHost(int deviceOrdinal, uint32_t width, uint32_t height, uint32_t K, uint32_t samples, const uint32_t* tileSamples, const float* buckets, float exposure,
                            float* outRgba, uint32_t* outBgra8, uint8_t* outTrim)
 {
-    requireDevice(deviceOrdinal);
-    const uint64_t n = static_cast<uint64_t>(width) * height;
-    // (leaving the scope: the stream is synchronised, the buffers are freed, the stream is destroyed -- ScopedStream)
-    ScopedStream           stream;
-    DeviceBuffer<float4>   in;
-    DeviceBuffer<uint32_t> counts;
-    RobustWork             work;
-    ScopedStream::Drain    drain{stream};
-    in.alloc(K * n);
-    RF_HIP(hipMemcpyAsync(in.ptr, buckets, K * n * sizeof(float4), hipMemcpyHostToDevice, stream.handle));
-    if (tileSamples)
-    {
-        const uint32_t tiles = TileGrid(width, height).count();
-        counts.alloc(tiles);
-        RF_HIP(hipMemcpyAsync(counts.ptr, tileSamples, tiles * sizeof(uint32_t), hipMemcpyHostToDevice, stream.handle));
-    }
-    enqueueRobustMean(stream.handle, work, in.ptr, n, width, height, 0u, K, samples, exposure, tileSamples ? counts.ptr : nullptr);
-    if (outRgba) RF_HIP(hipMemcpyAsync(outRgba, work.mean.ptr, n * sizeof(float4), hipMemcpyDeviceToHost, stream.handle));
-    if (outBgra8) RF_HIP(hipMemcpyAsync(outBgra8, work.bgra.ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream.handle));
-    if (outTrim) RF_HIP(hipMemcpyAsync(outTrim, work.trim.ptr, n * sizeof(uint8_t), hipMemcpyDeviceToHost, stream.handle));
-    RF_HIP(hipStreamSynchronize(stream.handle));
+    DeviceBuffer<float4> in; // (the two before the stage: freed after it has drained its stream)
+    RobustWork           work;
+    StagedFrame          f(deviceOrdinal, width, height, samples, tileSamples, nullptr, nullptr, nullptr, nullptr, nullptr);
+    f.upload(in, reinterpret_cast<const float4*>(buckets), K * f.pixels());
+    enqueueRobustMean(f.stream.handle, work, in.ptr, f.pixels(), K, f.sums, exposure);
+    f.download(outRgba, work.mean.ptr, f.pixels() * sizeof(float4));
+    f.download(outBgra8, work.bgra.ptr, f.pixels() * sizeof(uint32_t));
+    f.download(outTrim, work.trim.ptr, f.pixels() * sizeof(uint8_t));
+    f.wait();
 }
 
 void robustMeanImages(int deviceOrdinal, uint32_t width, uint32_t height, uint32_t K, uint32_t samples, const float* buckets, float exposure, float* outRgba,

@@ -3,6 +3,7 @@
 // standalone rf_robust_mean_images (inputs: row-major planes).
 #pragma once
 
+#include "rf_frame_sums.hpp"
 #include "rf_hip_host.hpp"
 #include "rf_renderer.hpp"
 
@@ -23,12 +24,10 @@ struct RobustWork
     void release();
 };
 
-// Enqueue kRobustMean<K> and kTonemap on `stream`.  planes: K planes of planeStride float4 each.  tilesX != 0: every plane is a compact tile-major buffer holding every
-// tile of the frame in tile order (a handle without a tile shard), tilesX tiles per row; 0: row-major.  width * height < 2^31; K odd, 3 .. 15; samples >= K.
-// tileSamples (device, one count >= K per tile of the frame's 32 x 32 grid, tile_y * ceil(width / 32) + tile_x) != nullptr: every pixel is combined with its tile's
-// count (kRobustMeanTiles<K>) and `samples` is not used; the buffer must stay as it is until the stream has run the kernel.
-void enqueueRobustMean(hipStream_t stream, RobustWork& work, const float4* planes, size_t planeStride, uint32_t width, uint32_t height, uint32_t tilesX, uint32_t K,
-                       uint32_t samples, float exposure, const uint32_t* tileSamples = nullptr);
+// Enqueue kRobustMean<K> and kTonemap on `stream`.  planes: K planes of planeStride float4 each, every one laid out as `frame` says (rf_frame_sums.hpp: its size,
+// layout and counts are used, its five planes are not).  K odd, 3 .. 15; frame.samples >= K.
+// frame.tileSamples (every count >= K) != nullptr: every pixel is combined with its tile's count (kRobustMeanTiles<K>).
+void enqueueRobustMean(hipStream_t stream, RobustWork& work, const float4* planes, size_t planeStride, uint32_t K, const FrameSums& frame, float exposure);
 
 // A tile shard's own combine ahead of the frame gather: enqueue kRobustMeanShard<K> on `stream` over the shard-compact tile-major planes (K planes of planeStride float4
 // each, shardTiles * 1024 pixels used, one count `samples` >= K) -> out[i] = {M.rgb, float(c)} in the same layout (shardTiles * 1024 float4).  Nothing is enqueued

@@ -137,16 +137,16 @@ void TemporalWork::release()
     bgra.release();
 }
 
-void enqueueTemporal(hipStream_t stream, const float4* colorSum, const float4* albedoCoverage, const float4* normalDepth, uint32_t width, uint32_t height, uint32_t tilesX,
-                     uint32_t samples, const Camera& camera, const float4* histColor, const float4* histGeometry, const Camera* histCamera, const TemporalParameters& params,
-                     float exposure, float4* outColor, float4* outGeometry, uint32_t* outBgra)
+void enqueueTemporal(hipStream_t stream, const FrameSums& s, const Camera& camera, const float4* histColor, const float4* histGeometry, const Camera* histCamera,
+                     const TemporalParameters& params, float exposure, float4* outColor, float4* outGeometry, uint32_t* outBgra)
 {
+    const uint32_t     width = s.width, height = s.height;
     const bool         history = histColor != nullptr && histGeometry != nullptr && histCamera != nullptr;
-    const TemporalArgs args{colorSum,    albedoCoverage, normalDepth, history ? histColor : nullptr, history ? histGeometry : nullptr, outColor, outGeometry, outBgra, camera,
-                            history ? *histCamera : camera, width, height, tilesX, static_cast<float>(samples), params.maxHistory, params.depthTolerance, params.minNormalDot,
+    const TemporalArgs args{s.colorSum,  s.albedoCoverage, s.normalDepth, history ? histColor : nullptr, history ? histGeometry : nullptr, outColor, outGeometry, outBgra, camera,
+                            history ? *histCamera : camera, width, height, s.tilesX, static_cast<float>(s.samples), params.maxHistory, params.depthTolerance, params.minNormalDot,
                             exposure};
     const dim3         grid((width + 15) / 16, (height + 15) / 16);
-    hipLaunchKernelGGL(tilesX ? kTemporalReproject<true> : kTemporalReproject<false>, grid, dim3(256), 0, stream, args);
+    hipLaunchKernelGGL(s.tilesX ? kTemporalReproject<true> : kTemporalReproject<false>, grid, dim3(256), 0, stream, args);
     RF_HIP(hipGetLastError());
 }
 
@@ -154,26 +154,17 @@ void temporalImages(int deviceOrdinal, uint32_t width, uint32_t height, uint32_t
                     const Camera& camera, const float* histColor, const float* histGeometry, const Camera* histCamera, const TemporalParameters& params, float exposure,
                     float* outColor, float* outGeometry, uint32_t* outBgra8)
 {
-    requireDevice(deviceOrdinal);
-    const uint64_t n = static_cast<uint64_t>(width) * height;
-    // (leaving the scope: the stream is synchronised, the buffers are freed, the stream is destroyed -- ScopedStream)
-    ScopedStream           stream;
-    DeviceBuffer<float4>   in[5], out[2];
+    DeviceBuffer<float4>   hist[2], out[2]; // (all before the stage: freed after it has drained its stream)
     DeviceBuffer<uint32_t> bgra;
-    ScopedStream::Drain    drain{stream};
-    const float*           src[5] = {colorSum, albedoCoverage, normalDepth, histColor, histGeometry};
-    for (int b = 0; b < 5; ++b)
-    {
-        if (!src[b]) continue; // (no history)
-        in[b].alloc(n);
-        RF_HIP(hipMemcpyAsync(in[b].ptr, src[b], n * sizeof(float4), hipMemcpyHostToDevice, stream.handle));
-    }
+    StagedFrame            f(deviceOrdinal, width, height, samples, nullptr, colorSum, nullptr, albedoCoverage, normalDepth, nullptr);
+    const uint64_t         n = f.pixels();
+    if (histColor) f.upload(hist[0], reinterpret_cast<const float4*>(histColor), n); // (else: no history)
+    if (histGeometry) f.upload(hist[1], reinterpret_cast<const float4*>(histGeometry), n);
     out[0].alloc(n), out[1].alloc(n), bgra.alloc(n);
-    enqueueTemporal(stream.handle, in[0].ptr, in[1].ptr, in[2].ptr, width, height, 0u, samples, camera, in[3].ptr, in[4].ptr, histCamera, params, exposure, out[0].ptr,
-                    out[1].ptr, bgra.ptr);
-    if (outColor) RF_HIP(hipMemcpyAsync(outColor, out[0].ptr, n * sizeof(float4), hipMemcpyDeviceToHost, stream.handle));
-    if (outGeometry) RF_HIP(hipMemcpyAsync(outGeometry, out[1].ptr, n * sizeof(float4), hipMemcpyDeviceToHost, stream.handle));
-    if (outBgra8) RF_HIP(hipMemcpyAsync(outBgra8, bgra.ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream.handle));
-    RF_HIP(hipStreamSynchronize(stream.handle));
+    enqueueTemporal(f.stream.handle, f.sums, camera, hist[0].ptr, hist[1].ptr, histCamera, params, exposure, out[0].ptr, out[1].ptr, bgra.ptr);
+    f.download(outColor, out[0].ptr, n * sizeof(float4));
+    f.download(outGeometry, out[1].ptr, n * sizeof(float4));
+    f.download(outBgra8, bgra.ptr, n * sizeof(uint32_t));
+    f.wait();
 }
 } // namespace rf

@@ -3,6 +3,7 @@
 // (inputs: the handle's own compact tile-major sums) and the standalone rf_temporal_images (inputs: row-major planes).
 #pragma once
 
+#include "rf_frame_sums.hpp"
 #include "rf_hip_host.hpp"
 #include "rf_renderer.hpp"
 
@@ -30,10 +31,9 @@ struct TemporalWork
     uint64_t bytes() const { return (color[0].count + color[1].count + geometry[0].count + geometry[1].count) * sizeof(float4) + bgra.count * sizeof(uint32_t); }
 };
 
-// Enqueue kTemporalReproject on `stream`: prep, reprojection, blend and the texel of every pixel in one pass.  tilesX != 0: the sums are compact tile-major buffers
-// holding every tile of the frame in tile order (a handle without a tile shard), tilesX tiles per row; 0: row-major.  histColor / histGeometry / histCamera: all
-// nullptr (no history) or all given; the outputs are row-major and all given.  width * height < 2^31; samples > 0; the parameters are valid.
-void enqueueTemporal(hipStream_t stream, const float4* colorSum, const float4* albedoCoverage, const float4* normalDepth, uint32_t width, uint32_t height, uint32_t tilesX,
-                     uint32_t samples, const Camera& camera, const float4* histColor, const float4* histGeometry, const Camera* histCamera, const TemporalParameters& params,
-                     float exposure, float4* outColor, float4* outGeometry, uint32_t* outBgra);
+// Enqueue kTemporalReproject on `stream` over the frame's S, AC and ND (rf_frame_sums.hpp; one count, sums.samples > 0: tileSamples is not read): prep, reprojection,
+// blend and the texel of every pixel in one pass.  histColor / histGeometry / histCamera: all nullptr (no history) or all given; the outputs are row-major and all
+// given.  The parameters are valid.
+void enqueueTemporal(hipStream_t stream, const FrameSums& sums, const Camera& camera, const float4* histColor, const float4* histGeometry, const Camera* histCamera,
+                     const TemporalParameters& params, float exposure, float4* outColor, float4* outGeometry, uint32_t* outBgra);
 } // namespace rf

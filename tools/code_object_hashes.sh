@@ -5,7 +5,8 @@
 TREE=$(cd "${1:-$(dirname "$0")/..}" && pwd)
 TMP=$(mktemp -d)
 trap 'rm -rf "$TMP"' EXIT
-for UNIT in rf_renderer rf_trace rf_shade rf_sums rf_bvh_gpu rf_comm rf_denoise rf_noise rf_robust rf_checkpoint; do
+# (the twelve kernel units of tools/kernel_resources.sh, the host driver and the GPU builder)
+for UNIT in rf_renderer rf_bvh_gpu rf_shade rf_sums rf_trace rf_primary_lists rf_denoise rf_noise rf_robust rf_comm rf_checkpoint rf_features rf_ray_query rf_temporal; do
   [ -f "$TREE/rayfinder_amd/csrc/$UNIT.hip" ] || continue
   (
     /opt/rocm/bin/hipcc -std=c++20 -O3 -fPIC -ffp-contract=off -fno-fast-math -fvisibility=hidden --offload-arch=gfx950 -fhip-fp32-correctly-rounded-divide-sqrt \
